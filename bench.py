@@ -14,7 +14,7 @@ inputs resident in HBM.  N GPUs = N processes, rank g owns the virtual sampler t
 chunk of the tables and the updated chunks are all-gathered.  Per-GPU batch is held at ~34 014 positives
 (nbatches = 8/N), so scaling is weak.
 
-python bench.py --gpus N --steps K --warmup W
+python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
 N > 1 from a bare shell: this process starts the N ranks itself (`python -m torch.distributed.run`, one rank per GPU, RCCL over
 xGMI) BEFORE anything touches a GPU, relays rank 0's JSON line and exits with the job's status -- what the reference's launcher
 does with TFCluster.run (main_spark.py:340).  Under an external torchrun (WORLD_SIZE set) it is one of the ranks.
@@ -23,6 +23,7 @@ import argparse
 import json
 import os
 import sys
+import tempfile
 import time
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
@@ -235,7 +236,7 @@ def launch_ranks(n, argv):
     return 0
 
 
-def eval_leg(device, epochs=6):
+def eval_leg(device, data_dir, epochs=6):
     """The second half of BASELINE's metric -- filtered MR / Hits@10 -- on a bounded run (tests/test_gpu_metric.py's protocol,
     shortened): a typed synthetic graph with FB15k-237's cardinalities (learnable structure; the reference ships no data), TransE
     dim 100, SGD, 4 negatives, the reference's auto batch 2 721; the ENGINE trains `epochs` x 100 steps on device-sampled
@@ -248,7 +249,7 @@ def eval_leg(device, epochs=6):
     from openkeonspark_amd import Config, TransE
     from openkeonspark_amd.synthetic import make_typed_dataset, FB15K237_TYPED
     from oracle import oracle
-    path = make_typed_dataset("/tmp/okes_typed_fb", FB15K237_TYPED)
+    path = make_typed_dataset(os.path.join(data_dir, "fb15k237_typed"), FB15K237_TYPED)
     dim, n, alpha = 100, 4, 10.0
     con = Config()
     con.device = device
@@ -297,6 +298,19 @@ def eval_leg(device, epochs=6):
                                         "from L2 / Infinity Cache, not HBM) plus the filter's binary searches; counted: scores x dim x 4 B" % dim}}
 
 
+def dump_outputs(out_dir, con, rank):
+    """What the timed path hands its caller after its last step, as DIR/<name>.npy (float32): that step's loss and the
+    trained tables (TransE dim 200 on the FB15k-237-shaped graph: about 12 MB in all).  Every rank calls it (gathering a
+    row-sharded table is a collective); rank 0 writes."""
+    import numpy as np
+    arrays = dict(con.get_parameters(), loss=con._loss.detach().cpu().numpy().reshape(1))
+    if rank != 0:
+        return
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
+
+
 def adam_step_bytes(ent_total, rel_total, dim):
     """TF1 'sparse' Adam is a dense sweep: every element of p, m, v is read and written each step
     (24 B) and the summed gradient image is read and re-zeroed (8 B)."""
@@ -314,6 +328,8 @@ def main():
     ap.add_argument("--prefetch-sampling", choices=["auto", "on", "off"], default="auto",
                     help="batch i+1 sampled on a side stream behind the emit kernel of step i (Config.prefetch_sampling; "
                          "bit-identical batches).  auto = the Config default")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write the last timed step's loss and the trained tables to DIR/<name>.npy")
     args = ap.parse_args()
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
@@ -349,11 +365,10 @@ def main():
     from openkeonspark_amd.synthetic import make_dataset, FB15K237
     from openkeonspark_amd import Config, TransE
 
-    if rank == 0:
-        fb_dir = make_dataset("/tmp/okes_fb15k237_shaped", FB15K237)
-    if use_dist:
-        dist.barrier()
-    fb_dir = make_dataset("/tmp/okes_fb15k237_shaped", FB15K237)
+    # every process regenerates the graphs from their seeds into a directory of its own: a copy some other run left in a
+    # shared place (another version of the generator, another user) is never what gets measured
+    data_tmp = tempfile.TemporaryDirectory(prefix="okes_bench_")
+    fb_dir = make_dataset(os.path.join(data_tmp.name, "fb15k237_shaped"), FB15K237)
 
     if PER_GPU_NBATCHES % world:
         raise SystemExit("--gpus must divide %d" % PER_GPU_NBATCHES)
@@ -416,6 +431,8 @@ def main():
         con.train_step(sync=False)
     sync()
     dt = time.perf_counter() - t0
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, con, rank)
     if use_dist:
         con.comm_fence("pg")
         t = torch.tensor([dt], device="cuda", dtype=torch.float64)
@@ -523,7 +540,7 @@ def main():
                 devnull_fd = os.open(os.devnull, os.O_WRONLY)
                 os.dup2(devnull_fd, 1)
                 try:
-                    out["eval"] = eval_leg("cuda:%d" % local_rank)
+                    out["eval"] = eval_leg("cuda:%d" % local_rank, data_tmp.name)
                 finally:
                     sys.stdout.flush()
                     ctypes.CDLL(None).fflush(None)
@@ -538,6 +555,7 @@ def main():
     if use_dist:
         dist.barrier()
         dist.destroy_process_group()
+    data_tmp.cleanup()
 
 
 if __name__ == "__main__":

@@ -16,16 +16,16 @@ def pytest_configure(config):
 
 @pytest.fixture(scope="session")
 def fb_dir(tmp_path_factory):
-    """FB15k-237-shaped synthetic graph (generated, never committed)."""
+    """FB15k-237-shaped synthetic graph (generated from its seed into this session's temporary directory, never committed)."""
     from openkeonspark_amd.synthetic import make_dataset, FB15K237
-    return make_dataset("/tmp/okes_fb15k237_shaped", FB15K237)
+    return make_dataset(str(tmp_path_factory.mktemp("fb15k237_shaped")), FB15K237)
 
 
 @pytest.fixture(scope="session")
 def wn_dir(tmp_path_factory):
     """WN18RR-shaped synthetic graph (BASELINE config #3)."""
     from openkeonspark_amd.synthetic import make_dataset, WN18RR
-    return make_dataset("/tmp/okes_wn18rr_shaped", WN18RR)
+    return make_dataset(str(tmp_path_factory.mktemp("wn18rr_shaped")), WN18RR)
 
 
 def parity_report(test, **metrics):

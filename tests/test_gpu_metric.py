@@ -54,13 +54,13 @@ KEYS = ("r_filter_rank", "l_filter_rank", "r_filter_tot", "l_filter_tot", "r_ran
 
 
 @pytest.mark.parametrize("graph", ["small_typed", "fb15k237_typed"])
-def test_trained_model_reaches_the_oracle_trained_metrics(graph):
+def test_trained_model_reaches_the_oracle_trained_metrics(graph, tmp_path):
     from openkeonspark_amd.synthetic import make_typed_dataset, FB15K237_TYPED, SMALL_TYPED
     if graph == "small_typed":
-        path = make_typed_dataset("/tmp/okes_typed_small", SMALL_TYPED)
+        path = make_typed_dataset(str(tmp_path / "typed_small"), SMALL_TYPED)
         dim, nbatches, n, alpha, epochs, sample = 32, 10, 4, 3.0, 40, 200
     else:   # configs[0]'s shape: FB15k-237 cardinalities, dim 100, the auto batch 2 721 (nbatches 100)
-        path = make_typed_dataset("/tmp/okes_typed_fb", FB15K237_TYPED)
+        path = make_typed_dataset(str(tmp_path / "typed_fb"), FB15K237_TYPED)
         dim, nbatches, n, alpha, epochs, sample = 100, 100, 4, 10.0, 20, 150
     con, orc, untrained, (out_g, met_g, loss_g), (out_o, met_o, loss_o), steps = train_both(path, dim, nbatches, n, alpha, epochs)
     # (1) the oracle's own ranker on the oracle-trained tables == the device ranker's 8-vectors (sample of the test set)
@@ -108,13 +108,13 @@ def test_trained_model_reaches_the_oracle_trained_metrics(graph):
 
 
 @pytest.mark.parametrize("model", ["TransH", "TransD"])
-def test_trained_through_the_pair_count_path_reaches_the_oracle_trained_metrics(model):
+def test_trained_through_the_pair_count_path_reaches_the_oracle_trained_metrics(model, tmp_path):
     """The same comparison for TransH / TransD with 8 negatives per positive, every step through the pair-count path (csrc/pairs.hip:
     int8 sign records keyed by (entity, relation), backward once per pair; forced here for this small graph): engine-trained
     and oracle-trained tables ranked by the device ranker over the whole test set."""
     from openkeonspark_amd import _lib
     from openkeonspark_amd.synthetic import make_typed_dataset, SMALL_TYPED
-    path = make_typed_dataset("/tmp/okes_typed_small", SMALL_TYPED)
+    path = make_typed_dataset(str(tmp_path / "typed_small"), SMALL_TYPED)
     L = _lib.lib()
     L.kge_set_option(b"float_records_min", 0)
     try:
