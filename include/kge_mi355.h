@@ -164,6 +164,9 @@ const char *kge_version(void);
  *   "persist_ahead":     1 (default) = teams without a group draw the next batch during the forward/backward phase
  *   "persist_trace":     1 = kge_train_steps_persistent stamps its phase boundaries (read with kge_persistent_trace)
  *   "persist_threads":   threads per workgroup of the persistent launch, 512 (default) or 1024
+ *   "topk_table_max_bytes": kge_topk_entities (TransE / TransH / TransD / TransR) scores the candidates from a table of their
+ *                     projected, normalised vectors while it is at most this many bytes (E x dim x 4; default 1 GiB); larger
+ *                     tables, or 0, compute the candidate side on the fly from the parameter rows (same functions, same bits)
  *   "libc_rand_restart": restart the glibc-compatible seed generator, as in a fresh process (the next
  *                        randReset then yields 1804289383, 846930886, ... again) */
 int kge_set_option(const char *name, INT value);
@@ -467,6 +470,21 @@ int kge_persistent_trace(uint64_t *h_out, INT n_steps);
  * testHead's (zeros if test_head == 0).  Needs importTestFiles (+ Type / Ontology files if present). */
 int kge_link_prediction(const kge_model_desc *m, const float *const tables[KGE_MAX_TABLES], INT first, INT count,
                         INT test_head, int64_t *h_out, void *stream);
+
+/* Batched top-k entity prediction on the device.  Query i: d_head[i] == 0 asks for the k best tails of (d_fixed[i], d_rel[i], ?),
+ * d_head[i] != 0 for the k best heads of (?, d_rel[i], d_fixed[i]); sides and relations may be mixed in any order.  d_ids /
+ * d_scores (DEVICE, row-major [n][k]) receive the candidates in ascending (score, id) order -- NaN after every number -- with
+ * kge_predict's score for that triple up to the contraction of its products (ulp level; TransR: each query with its own
+ * relation's matrix), identical on the table and on-the-fly paths; rows with fewer
+ * than k eligible candidates are padded with id -1 / score +inf.  flags: KGE_TOPK_FILTERED drops candidates forming a known
+ * triple (train + valid + test, needs importTestFiles), KGE_TOPK_TYPED keeps only the relation's head / tail type list (needs
+ * importTypeFiles) -- what kge_link_prediction's filtered / type-constrained ranks count.  1 <= k <= 1024.  Ids are the
+ * caller's precondition.  No [n x E] score matrix is formed; TransE needs no host synchronisation, the other models one
+ * (queries are grouped by relation).  Option "topk_table_max_bytes" chooses between a candidate table and on-the-fly sides. */
+#define KGE_TOPK_FILTERED 1
+#define KGE_TOPK_TYPED 2
+int kge_topk_entities(const kge_model_desc *m, const float *const tables[KGE_MAX_TABLES], const int32_t *d_fixed, const int32_t *d_rel,
+                      const int32_t *d_head, INT n, INT k, INT flags, int32_t *d_ids, float *d_scores, void *stream);
 
 /* predict op: score n triples.  TransE: mean over the dimension (TransE.py:58); others: sum
  * (TransH.py:82, TransR.py:87 with predict_r[0]'s matrix for all, TransD.py:98). */

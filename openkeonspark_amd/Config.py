@@ -1387,6 +1387,53 @@ class Config(object):
         print("triple (%d,%d,%d) is %s" % (h, t, r, "correct" if ok else "wrong"))
         return ok
 
+    def top_k_tails(self, h, r, k, filtered=False, type_constrained=False):
+        """The k best tails of (h, r, ?) for every query, ranked on the device (kge_topk_entities).  h and r are ints or 1-D
+        arrays, broadcast against each other.  Returns (ids int64 [n, k], scores float32 [n, k]) in ascending (score, id)
+        order, padded with -1 / +inf where fewer than k candidates are eligible; numpy in gives numpy out, device tensors in
+        give device tensors out.  filtered drops known triples (train + valid + test), type_constrained keeps the relation's
+        tail type list -- both need init_link_prediction()."""
+        return self._top_k_entities(h, r, k, False, filtered, type_constrained)
+
+    def top_k_heads(self, t, r, k, filtered=False, type_constrained=False):
+        """The k best heads of (?, r, t) for every query; as top_k_tails."""
+        return self._top_k_entities(t, r, k, True, filtered, type_constrained)
+
+    def _top_k_entities(self, fixed, rel, k, head, filtered, type_constrained):
+        import torch
+        if self._sharded("ent_embeddings"):
+            raise KgeError("top-k prediction over an entity table sharded across ranks is not supported")
+        k = int(k)
+        if not 1 <= k <= _lib.TOPK_MAX_K:
+            raise KgeError("top-k prediction: k must be in [1, %d], got %d" % (_lib.TOPK_MAX_K, k))
+        on_device = any(isinstance(x, torch.Tensor) and x.device.type != "cpu" for x in (fixed, rel))
+        if on_device:
+            f, r = (x if isinstance(x, torch.Tensor) else torch.as_tensor(np.asarray(x)) for x in (fixed, rel))
+            f, r = torch.broadcast_tensors(f.to(self.device).reshape(-1), r.to(self.device).reshape(-1))
+            f = f.to(torch.int32).contiguous()
+            r = r.to(torch.int32).contiguous()
+            n = f.shape[0]
+            if n:   # the ids index device tables directly: checked before any launch (four numbers come back)
+                lim = torch.stack([f.min(), f.max(), r.min(), r.max()]).cpu().tolist()
+                if lim[0] < 0 or lim[1] >= self.entTotal or lim[2] < 0 or lim[3] >= self.relTotal:
+                    raise KgeError("entity / relation id out of range in the top-k queries")
+        else:
+            fh, rh = np.broadcast_arrays(np.asarray(fixed).reshape(-1), np.asarray(rel).reshape(-1))
+            n = fh.shape[0]
+            if n and (fh.min() < 0 or fh.max() >= self.entTotal or rh.min() < 0 or rh.max() >= self.relTotal):
+                raise KgeError("entity / relation id out of range in the top-k queries")
+            f = torch.from_numpy(np.ascontiguousarray(fh, dtype=np.int32)).to(self.device)
+            r = torch.from_numpy(np.ascontiguousarray(rh, dtype=np.int32)).to(self.device)
+        side = torch.full((n,), 1 if head else 0, dtype=torch.int32, device=self.device)
+        ids = torch.empty((n, k), dtype=torch.int32, device=self.device)
+        scores = torch.empty((n, k), dtype=torch.float32, device=self.device)
+        flags = (_lib.TOPK_FILTERED if filtered else 0) | (_lib.TOPK_TYPED if type_constrained else 0)
+        _lib.check(self.lib.kge_topk_entities(ctypes.byref(self._desc), self._tab_ptrs, f.data_ptr(), r.data_ptr(), side.data_ptr(),
+                                              n, k, flags, ids.data_ptr(), scores.data_ptr(), self._stream()), self.lib)
+        if on_device:
+            return ids.long(), scores
+        return ids.cpu().numpy().astype(np.int64), scores.cpu().numpy()
+
     @staticmethod
     def _lp_sums(out, test_head=True):
         """Un-normalised accumulators of main_spark.py:430-448 over the rows of `out` (they add across test-set slices)."""

@@ -13,6 +13,8 @@ LIB_PATH = os.path.join(_HERE, "csrc", "libkge_mi355.so")
 TRANSE, TRANSH, TRANSR, TRANSD = 0, 1, 2, 3
 NO_EVENT = 1   # kge_stream_wait_emit: nothing was recorded since the previous wait (include/kge_mi355.h KGE_NO_EVENT)
 KGE_MAX_TABLES = 4
+TOPK_FILTERED, TOPK_TYPED = 1, 2   # kge_topk_entities flags (include/kge_mi355.h KGE_TOPK_*)
+TOPK_MAX_K = 1024
 
 
 class KgeError(RuntimeError):
@@ -87,6 +89,7 @@ def _declare(L):
     L.kge_sgd_update_tables.argtypes = [i32, vp, vp, vp, f32, vp]
     L.kge_adam_update_tables.argtypes = [i32, vp, vp, vp, vp, vp, f32, f32, f32, f32, vp]
     L.kge_predict.argtypes = [ctypes.POINTER(ModelDesc), tabs, vp, vp, vp, i64, vp, vp]
+    L.kge_topk_entities.argtypes = [ctypes.POINTER(ModelDesc), tabs, vp, vp, vp, i64, i64, i64, vp, vp, vp]
     L.kge_transe_counts_supported.argtypes = [ctypes.POINTER(ModelDesc), i64]
     L.kge_transe_forward_counts.argtypes = [ctypes.POINTER(ModelDesc), vp, vp, vp, vp, vp, i64, i64, i64, i64, vp, vp, vp, vp, vp]
     L.kge_transe_apply_counts.argtypes = [vp, vp, vp, vp, vp, i64, i32, i64, i32, f32, f32, f32, f32, vp]

@@ -14,7 +14,7 @@
 #include <cmath>
 #include <cstring>
 
-#include "engine.hpp"
+#include "eval_dev.hpp"
 
 namespace kge {
 
@@ -89,6 +89,17 @@ static int ensure_eval_device() {
     return KGE_OK;
 }
 
+int eval_filter_view(bool need_types, EvalFilterView &v) {
+    if (!g_eh.loaded) return fail(KGE_ERR_NO_DATASET, "importTestFiles has not been called: no known triples to filter by");
+    if (need_types && !g_eh.types) return fail(KGE_ERR_NO_DATASET, "importTypeFiles has not been called: no relation type lists");
+    int rc = ensure_eval_device();
+    if (rc) return rc;
+    v.all = g_ed.all; v.all_t = g_ed.all_t; v.n_all = (long long)g_eh.all.size();
+    v.head_lef = g_ed.head_lef; v.head_rig = g_ed.head_rig; v.tail_lef = g_ed.tail_lef; v.tail_rig = g_ed.tail_rig;
+    v.head_type = g_ed.head_type; v.tail_type = g_ed.tail_type;
+    return KGE_OK;
+}
+
 // ---------------------------------------------------------------------------------------------
 struct RankArgs {
     const float *scores;     // [n_req][E]
@@ -101,22 +112,6 @@ struct RankArgs {
     long long *out;            // [n_req][8]
     int E;
 };
-
-// [lo, hi) of the entries whose first two fields are (a, b) in an array sorted by (x, y, z): the third fields of that
-// range are the known tails of (h, r) in `all`, or the known heads of (t, r) in `all_t`, in increasing order
-__device__ __forceinline__ void pair_range(const int4 *__restrict__ arr, long long n, int a, int b, long long &lo, long long &hi) {
-    long long l = 0, r = n;
-    while (l < r) { const long long mid = (l + r) >> 1; const int4 m = arr[mid]; if (m.x < a || (m.x == a && m.y < b)) l = mid + 1; else r = mid; }
-    lo = l;
-    r = n;
-    while (l < r) { const long long mid = (l + r) >> 1; const int4 m = arr[mid]; if (m.x < a || (m.x == a && m.y <= b)) l = mid + 1; else r = mid; }
-    hi = l;
-}
-__device__ __forceinline__ bool in_range(const int4 *__restrict__ arr, long long lo, long long hi, int j) {
-    const long long end = hi;
-    while (lo < hi) { const long long mid = (lo + hi) >> 1; if (arr[mid].z < j) lo = mid + 1; else hi = mid; }
-    return lo < end && arr[lo].z == j;
-}
 
 struct MinPair { float v; int j; };
 __device__ __forceinline__ void take(MinPair &a, float v, int j) { if (v < a.v || (v == a.v && j < a.j)) { a.v = v; a.j = j; } }

@@ -1,0 +1,34 @@
+// The evaluation filter on the device, shared by the ranker (eval.hip) and the top-k selection (topk.hip): the union of
+// train + valid + test sorted by (h,r,t) and by (t,r,h), and the per-relation head / tail type lists.
+#pragma once
+#include "engine.hpp"
+
+namespace kge {
+
+// device copies uploaded by eval.hip (importTestFiles / importTypeFiles); read-only for their users
+struct EvalFilterView {
+    const int4 *all, *all_t;   // (h,r,t,0) sorted by (h,r,t); (t,r,h,0) sorted by (t,r,h)
+    long long n_all;
+    const int32_t *head_lef, *head_rig, *tail_lef, *tail_rig, *head_type, *tail_type;
+};
+// fills `v` with the uploaded arrays (uploading them on first use); KGE_ERR_NO_DATASET when importTestFiles, or with
+// need_types importTypeFiles, has not been called
+int eval_filter_view(bool need_types, EvalFilterView &v);
+
+// [lo, hi) of the entries whose first two fields are (a, b) in an array sorted by (x, y, z): the third fields of that
+// range are the known tails of (h, r) in `all`, or the known heads of (t, r) in `all_t`, in increasing order
+__device__ __forceinline__ void pair_range(const int4 *__restrict__ arr, long long n, int a, int b, long long &lo, long long &hi) {
+    long long l = 0, r = n;
+    while (l < r) { const long long mid = (l + r) >> 1; const int4 m = arr[mid]; if (m.x < a || (m.x == a && m.y < b)) l = mid + 1; else r = mid; }
+    lo = l;
+    r = n;
+    while (l < r) { const long long mid = (l + r) >> 1; const int4 m = arr[mid]; if (m.x < a || (m.x == a && m.y <= b)) l = mid + 1; else r = mid; }
+    hi = l;
+}
+__device__ __forceinline__ bool in_range(const int4 *__restrict__ arr, long long lo, long long hi, int j) {
+    const long long end = hi;
+    while (lo < hi) { const long long mid = (lo + hi) >> 1; if (arr[mid].z < j) lo = mid + 1; else hi = mid; }
+    return lo < end && arr[lo].z == j;
+}
+
+}  // namespace kge
