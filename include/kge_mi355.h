@@ -167,6 +167,10 @@ const char *kge_version(void);
  *   "topk_table_max_bytes": kge_topk_entities (TransE / TransH / TransD / TransR) scores the candidates from a table of their
  *                     projected, normalised vectors while it is at most this many bytes (E x dim x 4; default 1 GiB); larger
  *                     tables, or 0, compute the candidate side on the fly from the parameter rows (same functions, same bits)
+ *   "relpred_chunk_bytes": kge_topk_relations / kge_relation_prediction score their queries in chunks whose [chunk x R] fp32 score
+ *                     block is at most this many bytes (default 256 MiB; at least one query per chunk); TransR's buffer of
+ *                     projected distinct entities is held to the same size (at least one relation per block).  Results do not
+ *                     depend on it, bit for bit
  *   "libc_rand_restart": restart the glibc-compatible seed generator, as in a fresh process (the next
  *                        randReset then yields 1804289383, 846930886, ... again) */
 int kge_set_option(const char *name, INT value);
@@ -485,6 +489,25 @@ int kge_link_prediction(const kge_model_desc *m, const float *const tables[KGE_M
 #define KGE_TOPK_TYPED 2
 int kge_topk_entities(const kge_model_desc *m, const float *const tables[KGE_MAX_TABLES], const int32_t *d_fixed, const int32_t *d_rel,
                       const int32_t *d_head, INT n, INT k, INT flags, int32_t *d_ids, float *d_scores, void *stream);
+
+/* Batched top-k relation prediction on the device: the k best relations of (d_h[i], ?, d_t[i]) for n queries (DEVICE int32 ids).
+ * d_ids / d_scores (DEVICE, row-major [n][k]) receive the relations in ascending (score, id) order -- NaN after every number --
+ * with kge_predict's score of (h, t, r) up to the contraction of its products (ulp level); TransR scores every relation with
+ * that relation's own matrix (kge_predict called on all relations at once would not).  Rows with fewer than k eligible
+ * relations are padded with id -1 / score +inf.  flags as for kge_topk_entities: KGE_TOPK_FILTERED drops relations forming a
+ * known triple (train + valid + test, needs importTestFiles), KGE_TOPK_TYPED keeps relations whose head type list holds h
+ * and whose tail type list holds t (needs importTypeFiles).  1 <= k <= 1024.  Ids out of range score NaN (callers check them).
+ * KGE_ERR_UNSUPPORTED for an embedding (TransR: relation) dimension above 1024.  No host synchronisation. */
+int kge_topk_relations(const kge_model_desc *m, const float *const tables[KGE_MAX_TABLES], const int32_t *d_h,
+                       const int32_t *d_t, INT n, INT k, INT flags, int32_t *d_ids, float *d_scores, void *stream);
+/* Relation prediction for test triples [first, first+count) in kge_link_prediction's order (importTestFiles' (r, h, t) sort):
+ * h_out (HOST) receives count x 4 int64, the number of relations r' != r scoring strictly below the true relation r (scores
+ * as kge_topk_relations; NaN never counts): [0] raw, [1] filtered (r' with (h, r', t) in train + valid + test left out),
+ * [2] typed (only r' whose head type list holds h and tail type list holds t), [3] filtered and typed.  Without
+ * importTypeFiles no relation is typed and columns 2 / 3 are 0, as kge_link_prediction's constrained columns count nothing
+ * then.  KGE_ERR_NO_DATASET before importTestFiles.  One host synchronisation, at the end. */
+int kge_relation_prediction(const kge_model_desc *m, const float *const tables[KGE_MAX_TABLES], INT first, INT count,
+                            int64_t *h_out, void *stream);
 
 /* predict op: score n triples.  TransE: mean over the dimension (TransE.py:58); others: sum
  * (TransH.py:82, TransR.py:87 with predict_r[0]'s matrix for all, TransD.py:98). */

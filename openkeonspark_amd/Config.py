@@ -50,6 +50,7 @@ class Config(object):
             self.importName = None
             self.opt_method = "SGD"
             self.test_link_prediction = False
+            self.test_relation_prediction = False
             self.test_triple_classification = False
             self.valid_triple_classification = False
             # engine-side additions
@@ -87,7 +88,7 @@ class Config(object):
                 self.bt = self.lib.getBatchTotal()
                 self.set_mini_batch()
                 self._alloc_batch_buffers()
-            if self.test_link_prediction:
+            if self.test_link_prediction or self.test_relation_prediction:
                 self.init_link_prediction()
             # triple-classification inputs (Test.h:266-444) are not built yet
 
@@ -167,6 +168,10 @@ class Config(object):
 
     def set_test_link_prediction(self, flag):
         self.test_link_prediction = flag
+
+    def set_test_relation_prediction(self, flag):
+        """test() also reports the rel* relation-prediction metrics (relation_prediction); init() then imports the test files."""
+        self.test_relation_prediction = flag
 
     def set_test_triple_classification(self, flag):
         self.test_triple_classification = flag
@@ -1350,6 +1355,8 @@ class Config(object):
             result["acc"] = float(self.acc[0])
         if self.test_link_prediction:
             result.update(self.link_prediction()[1])
+        if self.test_relation_prediction:
+            result.update(self.relation_prediction()[1])
         print("\nElapsed test time (seconds): {}".format(time.time() - t0))
         return result
 
@@ -1370,7 +1377,8 @@ class Config(object):
 
     def predict_relation(self, h, t, k):
         """The k relations that score best for (h, t, ?) (Config.py:616-635; TransR's predict op uses the matrix of
-        the FIRST relation of a call, TransR.py:83, like the reference)."""
+        the FIRST relation of a call, TransR.py:83, like the reference).
+        Batched, filtered and type-constrained on the device, each TransR relation with its own matrix: top_k_relations."""
         ar = np.arange(self.relTotal)
         return self._top_k(self.test_step(np.full(self.relTotal, h), np.full(self.relTotal, t), ar), k)
 
@@ -1399,37 +1407,60 @@ class Config(object):
         """The k best heads of (?, r, t) for every query; as top_k_tails."""
         return self._top_k_entities(t, r, k, True, filtered, type_constrained)
 
+    def top_k_relations(self, h, t, k, filtered=False, type_constrained=False):
+        """The k best relations of (h, ?, t) for every query, scored and selected on the device (kge_topk_relations).  h and t
+        are ints or 1-D arrays, broadcast against each other.  Returns (ids int64 [n, k], scores float32 [n, k]) in ascending
+        (score, id) order, padded with -1 / +inf where fewer than k relations are eligible; numpy in gives numpy out, device
+        tensors in give device tensors out.  Scores are kge_predict's, TransR with each relation's own matrix.  filtered drops
+        relations forming a known triple (train + valid + test), type_constrained keeps relations whose head / tail type lists
+        hold h / t -- both need init_link_prediction()."""
+        h, t, n, on_device = self._topk_queries(h, t, k, self.entTotal, self.entTotal)
+        return self._topk_call(self.lib.kge_topk_relations, (h.data_ptr(), t.data_ptr()), n, k, filtered, type_constrained, on_device)
+
     def _top_k_entities(self, fixed, rel, k, head, filtered, type_constrained):
+        import torch
+        f, r, n, on_device = self._topk_queries(fixed, rel, k, self.entTotal, self.relTotal)
+        side = torch.full((n,), 1 if head else 0, dtype=torch.int32, device=self.device)
+        return self._topk_call(self.lib.kge_topk_entities, (f.data_ptr(), r.data_ptr(), side.data_ptr()), n, k, filtered,
+                               type_constrained, on_device)
+
+    def _topk_queries(self, a, b, k, a_total, b_total):
+        """Argument handling of the top-k methods: the sharding and k checks, the two id arrays broadcast against each other
+        and checked against [0, a_total) / [0, b_total) before any launch.  -> (a, b as int32 device tensors, n, on_device)."""
         import torch
         if self._sharded("ent_embeddings"):
             raise KgeError("top-k prediction over an entity table sharded across ranks is not supported")
         k = int(k)
         if not 1 <= k <= _lib.TOPK_MAX_K:
             raise KgeError("top-k prediction: k must be in [1, %d], got %d" % (_lib.TOPK_MAX_K, k))
-        on_device = any(isinstance(x, torch.Tensor) and x.device.type != "cpu" for x in (fixed, rel))
+        on_device = any(isinstance(x, torch.Tensor) and x.device.type != "cpu" for x in (a, b))
         if on_device:
-            f, r = (x if isinstance(x, torch.Tensor) else torch.as_tensor(np.asarray(x)) for x in (fixed, rel))
-            f, r = torch.broadcast_tensors(f.to(self.device).reshape(-1), r.to(self.device).reshape(-1))
-            f = f.to(torch.int32).contiguous()
-            r = r.to(torch.int32).contiguous()
-            n = f.shape[0]
+            a, b = (x if isinstance(x, torch.Tensor) else torch.as_tensor(np.asarray(x)) for x in (a, b))
+            a, b = torch.broadcast_tensors(a.to(self.device).reshape(-1), b.to(self.device).reshape(-1))
+            a = a.to(torch.int32).contiguous()
+            b = b.to(torch.int32).contiguous()
+            n = a.shape[0]
             if n:   # the ids index device tables directly: checked before any launch (four numbers come back)
-                lim = torch.stack([f.min(), f.max(), r.min(), r.max()]).cpu().tolist()
-                if lim[0] < 0 or lim[1] >= self.entTotal or lim[2] < 0 or lim[3] >= self.relTotal:
+                lim = torch.stack([a.min(), a.max(), b.min(), b.max()]).cpu().tolist()
+                if lim[0] < 0 or lim[1] >= a_total or lim[2] < 0 or lim[3] >= b_total:
                     raise KgeError("entity / relation id out of range in the top-k queries")
         else:
-            fh, rh = np.broadcast_arrays(np.asarray(fixed).reshape(-1), np.asarray(rel).reshape(-1))
-            n = fh.shape[0]
-            if n and (fh.min() < 0 or fh.max() >= self.entTotal or rh.min() < 0 or rh.max() >= self.relTotal):
+            ah, bh = np.broadcast_arrays(np.asarray(a).reshape(-1), np.asarray(b).reshape(-1))
+            n = ah.shape[0]
+            if n and (ah.min() < 0 or ah.max() >= a_total or bh.min() < 0 or bh.max() >= b_total):
                 raise KgeError("entity / relation id out of range in the top-k queries")
-            f = torch.from_numpy(np.ascontiguousarray(fh, dtype=np.int32)).to(self.device)
-            r = torch.from_numpy(np.ascontiguousarray(rh, dtype=np.int32)).to(self.device)
-        side = torch.full((n,), 1 if head else 0, dtype=torch.int32, device=self.device)
+            a = torch.from_numpy(np.ascontiguousarray(ah, dtype=np.int32)).to(self.device)
+            b = torch.from_numpy(np.ascontiguousarray(bh, dtype=np.int32)).to(self.device)
+        return a, b, n, on_device
+
+    def _topk_call(self, fn, query_ptrs, n, k, filtered, type_constrained, on_device):
+        import torch
+        k = int(k)
         ids = torch.empty((n, k), dtype=torch.int32, device=self.device)
         scores = torch.empty((n, k), dtype=torch.float32, device=self.device)
         flags = (_lib.TOPK_FILTERED if filtered else 0) | (_lib.TOPK_TYPED if type_constrained else 0)
-        _lib.check(self.lib.kge_topk_entities(ctypes.byref(self._desc), self._tab_ptrs, f.data_ptr(), r.data_ptr(), side.data_ptr(),
-                                              n, k, flags, ids.data_ptr(), scores.data_ptr(), self._stream()), self.lib)
+        _lib.check(fn(ctypes.byref(self._desc), self._tab_ptrs, *query_ptrs, n, k, flags, ids.data_ptr(), scores.data_ptr(),
+                      self._stream()), self.lib)
         if on_device:
             return ids.long(), scores
         return ids.cpu().numpy().astype(np.int64), scores.cpu().numpy()
@@ -1464,8 +1495,6 @@ class Config(object):
     def link_prediction_distributed(self, test_head=True):
         """The whole test set, split into one contiguous range per rank (the static split of
         distribute_training.py:430-441) and reduced like main_spark.py:430-448: every rank returns the global metrics."""
-        import torch
-        import torch.distributed as dist
         total = self.lib.getTestTotal()
         per = (total + self.world_size - 1) // self.world_size
         lo = min(self.rank * per, total)
@@ -1474,7 +1503,12 @@ class Config(object):
         if hi > lo:
             _lib.check(self.lib.kge_link_prediction(ctypes.byref(self._desc), self._tab_ptrs, lo, hi - lo,
                                                     1 if test_head else 0, out.ctypes.data, self._stream()), self.lib)
-        sums = self._lp_sums(out, test_head)
+        return self._lp_normalise(self._all_reduce_sums(self._lp_sums(out, test_head)), total)
+
+    def _all_reduce_sums(self, sums):
+        """The accumulators of every rank added up (main_spark.py:430-448's reduction)."""
+        import torch
+        import torch.distributed as dist
         keys = sorted(sums)
         vec = torch.tensor([sums[k] for k in keys], dtype=torch.float64)
         if self.world_size > 1:
@@ -1482,7 +1516,7 @@ class Config(object):
             if dist.get_backend(self._pg) == "nccl":
                 vec = vec.to(self.device)
             dist.all_reduce(vec, op=dist.ReduceOp.SUM, group=self._pg)
-        return self._lp_normalise(dict(zip(keys, vec.cpu().tolist())), total)
+        return dict(zip(keys, vec.cpu().tolist()))
 
     def link_prediction(self, first=0, count=None, test_head=True):
         """Rank every test triple in [first, first+count) on the device (replaces the per-triple loop of
@@ -1496,6 +1530,50 @@ class Config(object):
                                                 1 if test_head else 0, out.ctypes.data, self._stream()), self.lib)
         d = self._lp_normalise(self._lp_sums(out, test_head), count)
         return out, d
+
+    @staticmethod
+    def _rel_sums(out):
+        """Un-normalised relation-prediction accumulators over the rows of `out` [count, 4] (raw, filtered, typed, filtered +
+        typed counts), named as _lp_sums names them with the prefix "rel" (they add across test-set slices)."""
+        d = {}
+        for suffix, cols in (("", (0, 1)), ("_constrain", (2, 3))):
+            for name, col in (("", cols[0]), ("_filter", cols[1])):
+                cnt = out[:, col]
+                d["rel" + name + "_tot" + suffix] = float((cnt < 10).sum())                # Hits@10
+                d["rel3" + name + "_tot" + suffix] = float((cnt < 3).sum())                # Hits@3
+                d["rel1" + name + "_tot" + suffix] = float((cnt < 1).sum())                # Hits@1
+                d["rel" + name + "_rank" + suffix] = float((1 + cnt).sum())                # MR
+                d["rel" + name + "_reci_rank" + suffix] = float((1.0 / (1 + cnt)).sum())   # MRR
+        return d
+
+    def relation_prediction(self, first=0, count=None):
+        """Rank the true relation of every test triple in [first, first+count) (kge_link_prediction's order) among all
+        relations on the device (kge_relation_prediction).  Returns (raw int64 [count, 4]: the relations scoring strictly
+        better, raw / filtered / typed / filtered + typed, and the 20 rel* metrics normalised by the number of triples).
+        Without type_constrain.txt the typed columns are 0."""
+        if count is None:
+            count = self.lib.getTestTotal() - first
+        out = np.zeros((count, 4), dtype=np.int64)
+        self._relation_counts(first, count, out)
+        return out, self._lp_normalise(self._rel_sums(out), count)
+
+    def relation_prediction_distributed(self):
+        """relation_prediction over the whole test set split into one contiguous range per rank and all-reduced, as
+        link_prediction_distributed does: every rank returns the global metrics."""
+        total = self.lib.getTestTotal()
+        per = (total + self.world_size - 1) // self.world_size
+        lo = min(self.rank * per, total)
+        hi = min(lo + per, total)
+        out = np.zeros((hi - lo, 4), dtype=np.int64)
+        if hi > lo:
+            self._relation_counts(lo, hi - lo, out)
+        return self._lp_normalise(self._all_reduce_sums(self._rel_sums(out)), total)
+
+    def _relation_counts(self, first, count, out):
+        if self._sharded("ent_embeddings"):
+            raise KgeError("relation prediction over an entity table sharded across ranks is not supported")
+        _lib.check(self.lib.kge_relation_prediction(ctypes.byref(self._desc), self._tab_ptrs, first, count, out.ctypes.data,
+                                                    self._stream()), self.lib)
 
     # ------------------------------------------------------------------------------------------
     # parameters by the reference's variable names (Config.py:378-421)

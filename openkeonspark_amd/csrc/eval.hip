@@ -30,6 +30,7 @@ struct EvalHost {
 struct EvalDev {
     bool uploaded = false;
     int4 *test = nullptr, *all = nullptr, *all_t = nullptr;   // all_t: the same triples as (t,r,h,0) sorted by (t,r,h)
+    int4 *all_ht = nullptr;       // ... and as (h,t,r,0) sorted by (h,t,r) (relation prediction's filter)
     int32_t *head_lef = nullptr, *head_rig = nullptr, *tail_lef = nullptr, *tail_rig = nullptr, *head_type = nullptr, *tail_type = nullptr;
     int32_t *sup_lef = nullptr, *sup_rig = nullptr, *sub_lef = nullptr, *sub_rig = nullptr, *sup_type = nullptr, *sub_type = nullptr;
     float *scores = nullptr;      // staging for testHead/testTail and kge_link_prediction
@@ -73,6 +74,13 @@ static int ensure_eval_device() {
             if (a.x != b.x) return a.x < b.x; if (a.y != b.y) return a.y < b.y; return a.z < b.z; });
         if ((rc = up(g_ed.all_t, by_tail, "upload triples by tail"))) return rc;
     }
+    {   // third order for relation prediction: the known relations of an (h, t) pair are then contiguous
+        std::vector<Int4> by_pair(g_eh.all.size());
+        for (size_t i = 0; i < by_pair.size(); i++) by_pair[i] = Int4{g_eh.all[i].x, g_eh.all[i].z, g_eh.all[i].y, 0};
+        std::sort(by_pair.begin(), by_pair.end(), [](const Int4 &a, const Int4 &b) {
+            if (a.x != b.x) return a.x < b.x; if (a.y != b.y) return a.y < b.y; return a.z < b.z; });
+        if ((rc = up(g_ed.all_ht, by_pair, "upload triples by pair"))) return rc;
+    }
     if ((rc = up(g_ed.head_lef, g_eh.head_lef, "upload types"))) return rc;
     if ((rc = up(g_ed.head_rig, g_eh.head_rig, "upload types"))) return rc;
     if ((rc = up(g_ed.tail_lef, g_eh.tail_lef, "upload types"))) return rc;
@@ -94,9 +102,17 @@ int eval_filter_view(bool need_types, EvalFilterView &v) {
     if (need_types && !g_eh.types) return fail(KGE_ERR_NO_DATASET, "importTypeFiles has not been called: no relation type lists");
     int rc = ensure_eval_device();
     if (rc) return rc;
-    v.all = g_ed.all; v.all_t = g_ed.all_t; v.n_all = (long long)g_eh.all.size();
+    v.all = g_ed.all; v.all_t = g_ed.all_t; v.all_ht = g_ed.all_ht; v.n_all = (long long)g_eh.all.size();
     v.head_lef = g_ed.head_lef; v.head_rig = g_ed.head_rig; v.tail_lef = g_ed.tail_lef; v.tail_rig = g_ed.tail_rig;
     v.head_type = g_ed.head_type; v.tail_type = g_ed.tail_type;
+    return KGE_OK;
+}
+
+int eval_test_view(const int4 *&test, int64_t &total) {
+    int rc = ensure_eval_device();
+    if (rc) return rc;
+    test = g_ed.test;
+    total = g_eh.test_total;
     return KGE_OK;
 }
 

@@ -1,5 +1,5 @@
 // The evaluation filter on the device, shared by the ranker (eval.hip) and the top-k selection (topk.hip): the union of
-// train + valid + test sorted by (h,r,t) and by (t,r,h), and the per-relation head / tail type lists.
+// train + valid + test sorted by (h,r,t), by (t,r,h) and by (h,t,r), and the per-relation head / tail type lists.
 #pragma once
 #include "engine.hpp"
 
@@ -8,15 +8,20 @@ namespace kge {
 // device copies uploaded by eval.hip (importTestFiles / importTypeFiles); read-only for their users
 struct EvalFilterView {
     const int4 *all, *all_t;   // (h,r,t,0) sorted by (h,r,t); (t,r,h,0) sorted by (t,r,h)
+    const int4 *all_ht;        // (h,t,r,0) sorted by (h,t,r): the known relations of an (h, t) pair are one range
     long long n_all;
     const int32_t *head_lef, *head_rig, *tail_lef, *tail_rig, *head_type, *tail_type;
 };
 // fills `v` with the uploaded arrays (uploading them on first use); KGE_ERR_NO_DATASET when importTestFiles, or with
 // need_types importTypeFiles, has not been called
 int eval_filter_view(bool need_types, EvalFilterView &v);
+// the uploaded test triples (h,t,r,0) in importTestFiles' (r,h,t) order -- the order kge_link_prediction's [first, first+count)
+// indexes -- and their number; KGE_ERR_NO_DATASET before importTestFiles
+int eval_test_view(const int4 *&test, int64_t &total);
 
 // [lo, hi) of the entries whose first two fields are (a, b) in an array sorted by (x, y, z): the third fields of that
-// range are the known tails of (h, r) in `all`, or the known heads of (t, r) in `all_t`, in increasing order
+// range are the known tails of (h, r) in `all`, the known heads of (t, r) in `all_t`, or the known relations of (h, t) in
+// `all_ht`, in increasing order
 __device__ __forceinline__ void pair_range(const int4 *__restrict__ arr, long long n, int a, int b, long long &lo, long long &hi) {
     long long l = 0, r = n;
     while (l < r) { const long long mid = (l + r) >> 1; const int4 m = arr[mid]; if (m.x < a || (m.x == a && m.y < b)) l = mid + 1; else r = mid; }

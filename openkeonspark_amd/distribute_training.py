@@ -61,6 +61,7 @@ def parse_args(argv=None):
     p.add_argument("--debug", type=int, default=0)
     p.add_argument("--mode", type=str, default="train")
     p.add_argument("--test_head", type=int, default=0)
+    p.add_argument("--test_relation", type=int, default=0, help="1: --mode test also ranks the true relation of each test triple (rel* metrics)")
     p.add_argument("--work_threads", type=int, default=8, help="virtual sampler threads (Config.py:65 hard-codes 8)")
     p.add_argument("--seed", type=int, default=0, help="parameter initialisation seed")
     p.add_argument("--sparse_rows", type=int, default=-1, help="1 / 0: force / forbid the touched-rows-only update: TransE int8 records (SGD, or the opt-in non-parity "
@@ -342,8 +343,12 @@ def main_fun(argv):
     if argv.mode != "train":
         if distributed:   # one contiguous slice of the test set per rank, accumulators all-reduced
             metrics = con.link_prediction_distributed(test_head=bool(argv.test_head))
+            if argv.test_relation:
+                metrics.update(con.relation_prediction_distributed())
         else:
             out, metrics = con.link_prediction(test_head=bool(argv.test_head))
+            if argv.test_relation:
+                metrics.update(con.relation_prediction()[1])
         if rank == 0:
             print(json.dumps(metrics, indent=1))
             if argv.output_path:
