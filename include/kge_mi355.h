@@ -475,6 +475,28 @@ int kge_persistent_trace(uint64_t *h_out, INT n_steps);
 int kge_link_prediction(const kge_model_desc *m, const float *const tables[KGE_MAX_TABLES], INT first, INT count,
                         INT test_head, int64_t *h_out, void *stream);
 
+/* Link prediction against a ROW RANGE of the entity table (a table sharded by rows across ranks; csrc/lp_shard.hip).
+ * Rank test triples [first, first+count) (kge_link_prediction's order) against the candidate entities [row_lo, row_lo+rows)
+ * only.  tables[0] holds exactly those rows (row i = entity row_lo+i); tables[1] is the whole relation table.  d_query_rows
+ * (DEVICE fp32 [count][2][ent_dim]) holds the raw h and t rows of each test triple.
+ * d_counts (DEVICE int64 [count][2][4], written): side 0 tail / side 1 head; raw, filtered, typed, filtered+typed counts of the
+ *   candidates in the range (the target excluded) scoring strictly below the true triple; NaN never counts.
+ * d_keys (DEVICE int64 [count][2][4], written): the four arg-mins as pack_key(score, id) (select_dev.hpp), INT64_MAX if no
+ *   candidate in the range scores below.  Counted scores are >= +0, so the keys order as int64 the way they order unsigned.
+ * The score is the L1 distance |hn + rn - tn| summed in one fixed order (TransE's predict op divides it by the dimension), the
+ * true triple's score by the same function from d_query_rows: an entity whose row equals the target's ties with it and is not
+ * counted, in whichever range it lies.  Merging ranges: SUM of d_counts, MIN of d_keys -- exactly, bit for bit, for any cut.
+ * TransE only (KGE_ERR_UNSUPPORTED otherwise; ent_dim <= 1024).  Needs importTestFiles.  No host synchronisation. */
+int kge_link_prediction_range(const kge_model_desc *m, const float *const tables[KGE_MAX_TABLES], INT row_lo, INT rows,
+                              const float *d_query_rows, INT first, INT count, INT test_head, int64_t *d_counts, int64_t *d_keys,
+                              void *stream);
+/* Merged counts + keys -> kge_link_prediction's host layout [count][2][8] (side 1 zero when test_head == 0), ontology classes
+ * resolved as rank_kernel does (Test.h:113-135: shared, never-rewinding cursors).  One host synchronisation. */
+int kge_link_prediction_finish(INT first, INT count, INT test_head, const int64_t *d_counts, const int64_t *d_keys, int64_t *h_out,
+                               void *stream);
+/* d_ids (DEVICE int32 [count][2]) = the head and tail ids of test triples [first, first+count), kge_link_prediction's order. */
+int kge_test_entity_ids(INT first, INT count, int32_t *d_ids, void *stream);
+
 /* Batched top-k entity prediction on the device.  Query i: d_head[i] == 0 asks for the k best tails of (d_fixed[i], d_rel[i], ?),
  * d_head[i] != 0 for the k best heads of (?, d_rel[i], d_fixed[i]); sides and relations may be mixed in any order.  d_ids /
  * d_scores (DEVICE, row-major [n][k]) receive the candidates in ascending (score, id) order -- NaN after every number -- with

@@ -61,6 +61,9 @@ class Config(object):
             self.global_step = 0
             self.rank, self.world_size = 0, 1
             self._pg = None
+            # link_prediction on an entity table sharded across ranks: the test set goes in chunks whose fetched query rows
+            # (2 rows of 4 * dim bytes per triple) take at most this many bytes (at least one triple per chunk)
+            self.lp_shard_query_bytes = 256 << 20
 
     # ------------------------------------------------------------------------------------------
     # Config.py:153-210
@@ -1285,16 +1288,101 @@ class Config(object):
     def test_step(self, test_h, test_t, test_r):
         '''
         Score triples with the model's predict op (Config.py:478-488)
+        On an entity table sharded across ranks this is a collective (every rank calls it, each with its own triples, possibly
+        none): the rows of the triples' entities are fetched from their owners and scored as a compact table, with the bits of
+        the single-process call.
         '''
         import torch
         host = np.stack([np.asarray(test_h), np.asarray(test_t), np.asarray(test_r)]).astype(np.int32)
         self._check_ids(host)
+        if self._sharded("ent_embeddings"):
+            return self._test_step_sharded(host)
         dev = torch.from_numpy(host).to(self.device)
         out = torch.empty(host.shape[1], dtype=torch.float32, device=self.device)
         _lib.check(self.lib.kge_predict(ctypes.byref(self._desc), self._tab_ptrs, dev[0].data_ptr(), dev[1].data_ptr(),
                                         dev[2].data_ptr(), host.shape[1], out.data_ptr(), self._stream()), self.lib)
         self.trainModel.predict = out
         return out.cpu().numpy()
+
+    def _test_step_sharded(self, host):
+        import torch
+        n = host.shape[1]
+        ids = torch.from_numpy(np.ascontiguousarray(host[:2].reshape(-1))).to(self.device)    # the n heads, then the n tails
+        rows, slot_of = self._fetch_rows(ids, 2 * n)
+        out = torch.empty(n, dtype=torch.float32, device=self.device)
+        if n:
+            slots = slot_of.view(2, n)
+            rel = torch.from_numpy(np.ascontiguousarray(host[2])).to(self.device)
+            desc = self._desc_with(ent_total=rows.shape[0])       # entity ids are slots of the fetched rows
+            ptrs = _lib.table_ptrs([rows.data_ptr()] + [t.data_ptr() for t in self._tables[1:]])
+            _lib.check(self.lib.kge_predict(ctypes.byref(desc), ptrs, slots[0].data_ptr(), slots[1].data_ptr(), rel.data_ptr(), n,
+                                            out.data_ptr(), self._stream()), self.lib)
+        self.trainModel.predict = out
+        return out.cpu().numpy()
+
+    def _fetch_rows(self, ids, n):
+        """Collective on a sharded entity table: the rows of the n global entity ids in `ids` (int32 device tensor), fetched from
+        their owners by the sharded step's exchange (ids out, rows back).  -> (rows float32 [max(n, 1), D], slot_of int32 [n]:
+        the row holding entity ids[i])."""
+        import torch
+        from . import parallel as par
+        L, st, W, D, pg = self.lib, self._stream(), self.world_size, self.hidden_size, self._pg
+        sh, dev, i32 = self._shard, self.device, torch.int32
+        self.comm_fence("pg")
+        counts = torch.zeros(W, dtype=i32, device=dev)
+        cursor = torch.zeros(W, dtype=i32, device=dev)
+        send_ids = torch.empty(max(n, 1), dtype=i32, device=dev)
+        slot_of = torch.empty(max(n, 1), dtype=i32, device=dev)
+        _lib.check(L.kge_shard_count(ids.data_ptr(), n, sh["chunk"], W, counts.data_ptr(), st), L)
+        send, recv, gmax = par.exchange_counts_max(counts, pg)
+        _lib.check(L.kge_shard_scatter(ids.data_ptr(), n, sh["chunk"], W, (ctypes.c_int64 * W)(*send), cursor.data_ptr(),
+                                       send_ids.data_ptr(), slot_of.data_ptr(), st), L)
+        n_recv = sum(recv)
+        recv_ids = torch.empty(max(n_recv, 1), dtype=i32, device=dev)
+        rows_out = torch.empty((max(n_recv, 1), D), dtype=torch.float32, device=dev)
+        rows = torch.zeros((max(n, 1), D), dtype=torch.float32, device=dev)
+        par.all_to_all_rows(recv_ids, send_ids, recv, send, pg, max_rows=gmax)
+        _lib.check(L.kge_shard_gather_rows(self._tables[0].data_ptr(), recv_ids.data_ptr(), n_recv, sh["lo"], sh["chunk"], D,
+                                           rows_out.data_ptr(), st), L)
+        par.all_to_all_rows(rows, rows_out, send, recv, pg, max_rows=gmax)
+        return rows, slot_of[:n]
+
+    def _all_reduce_on_pg(self, t, op):
+        """In-place all-reduce of a device tensor on the process group (staged through the host for gloo)."""
+        import torch.distributed as dist
+        self.comm_fence("pg")
+        if dist.get_backend(self._pg) == "nccl":
+            dist.all_reduce(t, op=op, group=self._pg)
+        else:
+            h = t.cpu()
+            dist.all_reduce(h, op=op, group=self._pg)
+            t.copy_(h)
+
+    def _link_prediction_sharded(self, first, count, test_head):
+        """link_prediction on a sharded entity table (collective): every rank ranks the test triples against its own rows
+        [lo, hi), the counts are summed and the arg-min keys minimised across ranks, then resolved as kge_link_prediction does."""
+        import torch
+        import torch.distributed as dist
+        L, st, D = self.lib, self._stream(), self.hidden_size
+        lo, hi = self._shard["lo"], self._shard["hi"]
+        th = 1 if test_head else 0
+        out = np.zeros((count, 2, 8), dtype=np.int64)
+        per = max(1, int(self.lp_shard_query_bytes) // (2 * D * 4))
+        for c0 in range(first, first + count, per):
+            n = min(per, first + count - c0)
+            ids = torch.empty(2 * n, dtype=torch.int32, device=self.device)
+            _lib.check(L.kge_test_entity_ids(c0, n, ids.data_ptr(), st), L)
+            rows, slot_of = self._fetch_rows(ids, 2 * n)
+            query = rows.index_select(0, slot_of.long())      # [2n, D]: the h and t rows of each triple
+            del rows
+            counts = torch.empty((n, 2, 4), dtype=torch.int64, device=self.device)
+            keys = torch.empty_like(counts)
+            _lib.check(L.kge_link_prediction_range(ctypes.byref(self._desc), self._tab_ptrs, lo, hi - lo, query.data_ptr(), c0, n, th,
+                                                   counts.data_ptr(), keys.data_ptr(), st), L)
+            self._all_reduce_on_pg(counts, dist.ReduceOp.SUM)
+            self._all_reduce_on_pg(keys, dist.ReduceOp.MIN)
+            _lib.check(L.kge_link_prediction_finish(c0, n, th, counts.data_ptr(), keys.data_ptr(), out[c0 - first:].ctypes.data, st), L)
+        return out
 
     # ------------------------------------------------------------------------------------------
     # triple classification and the predict_* helpers (Config.py:83-151, 491-516, 574-663)
@@ -1365,13 +1453,20 @@ class Config(object):
         print(res)
         return res
 
+    def _refuse_sharded_predict(self, what):
+        if self._sharded("ent_embeddings"):
+            raise KgeError("%s over an entity table sharded across ranks would fetch every row to every rank: rank test triples with "
+                           "link_prediction (a collective on sharded tables) instead" % what)
+
     def predict_head_entity(self, t, r, k):
         """The k head entities that score best for (?, t, r) (Config.py:574-593)."""
+        self._refuse_sharded_predict("predict_head_entity")
         ar = np.arange(self.entTotal)
         return self._top_k(self.test_step(ar, np.full(self.entTotal, t), np.full(self.entTotal, r)), k)
 
     def predict_tail_entity(self, h, r, k):
         """The k tail entities that score best for (h, ?, r) (Config.py:595-614)."""
+        self._refuse_sharded_predict("predict_tail_entity")
         ar = np.arange(self.entTotal)
         return self._top_k(self.test_step(np.full(self.entTotal, h), ar, np.full(self.entTotal, r)), k)
 
@@ -1494,8 +1589,11 @@ class Config(object):
 
     def link_prediction_distributed(self, test_head=True):
         """The whole test set, split into one contiguous range per rank (the static split of
-        distribute_training.py:430-441) and reduced like main_spark.py:430-448: every rank returns the global metrics."""
+        distribute_training.py:430-441) and reduced like main_spark.py:430-448: every rank returns the global metrics.
+        On a sharded entity table the candidates are split instead: link_prediction over the whole test set, a collective."""
         total = self.lib.getTestTotal()
+        if self._sharded("ent_embeddings"):
+            return self.link_prediction(0, total, test_head)[1]
         per = (total + self.world_size - 1) // self.world_size
         lo = min(self.rank * per, total)
         hi = min(lo + per, total)
@@ -1522,9 +1620,16 @@ class Config(object):
         """Rank every test triple in [first, first+count) on the device (replaces the per-triple loop of
         distribute_training.py:465-590).  Returns (raw int64 [count,2,8] as testTail/testHead give them,
         metrics dict with the reference's accumulator names normalised by the number of triples, the way
-        main_spark.py:430-448 reduces them: r_* = tail prediction, l_* = head prediction)."""
+        main_spark.py:430-448 reduces them: r_* = tail prediction, l_* = head prediction).
+        On an entity table sharded across ranks it is a collective (every rank calls it with the same arguments and gets the same
+        result): each rank ranks the triples against its own rows (kge_link_prediction_range) and the counts and arg-mins are merged
+        across ranks.  Its scores may place a near-tie (a candidate within an ulp or so of the true triple) on the other side of
+        the true triple than kge_link_prediction does."""
         if count is None:
             count = self.lib.getTestTotal() - first
+        if self._sharded("ent_embeddings"):
+            out = self._link_prediction_sharded(first, count, test_head)
+            return out, self._lp_normalise(self._lp_sums(out, test_head), count)
         out = np.zeros((count, 2, 8), dtype=np.int64)
         _lib.check(self.lib.kge_link_prediction(ctypes.byref(self._desc), self._tab_ptrs, first, count,
                                                 1 if test_head else 0, out.ctypes.data, self._stream()), self.lib)

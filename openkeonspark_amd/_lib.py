@@ -92,6 +92,9 @@ def _declare(L):
     L.kge_topk_entities.argtypes = [ctypes.POINTER(ModelDesc), tabs, vp, vp, vp, i64, i64, i64, vp, vp, vp]
     L.kge_topk_relations.argtypes = [ctypes.POINTER(ModelDesc), tabs, vp, vp, i64, i64, i64, vp, vp, vp]
     L.kge_relation_prediction.argtypes = [ctypes.POINTER(ModelDesc), tabs, i64, i64, vp, vp]
+    L.kge_link_prediction_range.argtypes = [ctypes.POINTER(ModelDesc), tabs, i64, i64, vp, i64, i64, i64, vp, vp, vp]
+    L.kge_link_prediction_finish.argtypes = [i64, i64, i64, vp, vp, vp, vp]
+    L.kge_test_entity_ids.argtypes = [i64, i64, vp, vp]
     L.kge_transe_counts_supported.argtypes = [ctypes.POINTER(ModelDesc), i64]
     L.kge_transe_forward_counts.argtypes = [ctypes.POINTER(ModelDesc), vp, vp, vp, vp, vp, i64, i64, i64, i64, vp, vp, vp, vp, vp]
     L.kge_transe_apply_counts.argtypes = [vp, vp, vp, vp, vp, i64, i32, i64, i32, f32, f32, f32, f32, vp]

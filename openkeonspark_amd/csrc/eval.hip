@@ -116,6 +116,14 @@ int eval_test_view(const int4 *&test, int64_t &total) {
     return KGE_OK;
 }
 
+int eval_ontology_view(EvalOntologyView &v) {
+    int rc = ensure_eval_device();
+    if (rc) return rc;
+    v.sup_lef = g_ed.sup_lef; v.sup_rig = g_ed.sup_rig; v.sub_lef = g_ed.sub_lef; v.sub_rig = g_ed.sub_rig;
+    v.sup_type = g_ed.sup_type; v.sub_type = g_ed.sub_type;
+    return KGE_OK;
+}
+
 // ---------------------------------------------------------------------------------------------
 struct RankArgs {
     const float *scores;     // [n_req][E]

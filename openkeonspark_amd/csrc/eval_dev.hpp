@@ -1,4 +1,4 @@
-// The evaluation filter on the device, shared by the ranker (eval.hip) and the top-k selection (topk.hip): the union of
+// The evaluation filter on the device, shared by the rankers (eval.hip, lp_shard.hip) and the top-k selection (topk.hip): the union of
 // train + valid + test sorted by (h,r,t), by (t,r,h) and by (h,t,r), and the per-relation head / tail type lists.
 #pragma once
 #include "engine.hpp"
@@ -18,6 +18,12 @@ int eval_filter_view(bool need_types, EvalFilterView &v);
 // the uploaded test triples (h,t,r,0) in importTestFiles' (r,h,t) order -- the order kge_link_prediction's [first, first+count)
 // indexes -- and their number; KGE_ERR_NO_DATASET before importTestFiles
 int eval_test_view(const int4 *&test, int64_t &total);
+// the ontology lists of importOntologyFiles (per entity: [sup_lef, sup_rig) of sup_type, [sub_lef, sub_rig) of sub_type, all
+// empty without the file), read-only, for resolving arg-min classes as rank_kernel does; KGE_ERR_NO_DATASET before importTestFiles
+struct EvalOntologyView {
+    const int32_t *sup_lef, *sup_rig, *sub_lef, *sub_rig, *sup_type, *sub_type;
+};
+int eval_ontology_view(EvalOntologyView &v);
 
 // [lo, hi) of the entries whose first two fields are (a, b) in an array sorted by (x, y, z): the third fields of that
 // range are the known tails of (h, r) in `all`, the known heads of (t, r) in `all_t`, or the known relations of (h, t) in
