@@ -164,7 +164,8 @@ const char *kge_version(void);
  *   "persist_ahead":     1 (default) = teams without a group draw the next batch during the forward/backward phase
  *   "persist_trace":     1 = kge_train_steps_persistent stamps its phase boundaries (read with kge_persistent_trace)
  *   "persist_threads":   threads per workgroup of the persistent launch, 512 (default) or 1024
- *   "topk_table_max_bytes": kge_topk_entities (TransE / TransH / TransD / TransR) scores the candidates from a table of their
+ *   "topk_table_max_bytes": kge_topk_entities (TransE / TransH / TransD / TransR) and kge_topk_entities_range (rows x dim x 4)
+ *                     score the candidates from a table of their
  *                     projected, normalised vectors while it is at most this many bytes (E x dim x 4; default 1 GiB); larger
  *                     tables, or 0, compute the candidate side on the fly from the parameter rows (same functions, same bits)
  *   "relpred_chunk_bytes": kge_topk_relations / kge_relation_prediction score their queries in chunks whose [chunk x R] fp32 score
@@ -511,6 +512,26 @@ int kge_test_entity_ids(INT first, INT count, int32_t *d_ids, void *stream);
 #define KGE_TOPK_TYPED 2
 int kge_topk_entities(const kge_model_desc *m, const float *const tables[KGE_MAX_TABLES], const int32_t *d_fixed, const int32_t *d_rel,
                       const int32_t *d_head, INT n, INT k, INT flags, int32_t *d_ids, float *d_scores, void *stream);
+/* Top-k entities against a ROW RANGE of the entity table (a table sharded by rows across ranks; csrc/topk.hip).  The queries
+ * of kge_topk_entities, scored against the candidates with global ids [row_lo, row_lo+rows) only: tables[0] holds exactly
+ * those rows (row i = entity row_lo+i), tables[1] is the whole relation table, and d_query_rows (DEVICE fp32 [n][ent_dim])
+ * holds the raw row of each query's fixed entity d_fixed[i] (which may lie outside the range).  The filter and the type lists
+ * test the global id.  d_keys (DEVICE uint64 [n][k], written) receives each query's k smallest keys in ascending order,
+ * padded with KGE_TOPK_NO_KEY.  Key layout (select_dev.hpp pack_key): bits 63..32 the score's bits made orderable as an
+ * unsigned integer (sign bit set for a positive float, all bits flipped for a negative one; every NaN 0xFFFFFFFF), bits 31..0
+ * the global entity id -- keys order as (score, id), NaN after every number, and are unique per query.  rows == 0 is legal
+ * (all padding).  The score bits are kge_topk_entities' (same functions, same per-dimension bucket), so merging the ranges of
+ * any cut with kge_topk_merge_keys gives kge_topk_entities on the whole table, ids and score bits alike.  TransE only
+ * (KGE_ERR_UNSUPPORTED otherwise; ent_dim <= 1024).  Option "topk_table_max_bytes" as for kge_topk_entities (rows x dim x 4).
+ * No host synchronisation.  With n == 0 only the arguments (and the files the flags need) are checked. */
+#define KGE_TOPK_NO_KEY 0xFFFFFFFFFFFFFFFFull
+int kge_topk_entities_range(const kge_model_desc *m, const float *const tables[KGE_MAX_TABLES], INT row_lo, INT rows,
+                            const float *d_query_rows, const int32_t *d_fixed, const int32_t *d_rel, const int32_t *d_head, INT n,
+                            INT k, INT flags, uint64_t *d_keys, void *stream);
+/* The k smallest keys of `parts` key lists per query -- d_keys (DEVICE uint64 [parts][n][k], e.g. the ranges' kge_topk_entities_range
+ * outputs grouped by source) -- unpacked into d_ids / d_scores (DEVICE [n][k]) as kge_topk_entities writes them: ascending, padded
+ * with id -1 / score +inf.  1 <= k <= 1024.  No host synchronisation. */
+int kge_topk_merge_keys(const uint64_t *d_keys, INT n, INT parts, INT k, int32_t *d_ids, float *d_scores, void *stream);
 
 /* Batched top-k relation prediction on the device: the k best relations of (d_h[i], ?, d_t[i]) for n queries (DEVICE int32 ids).
  * d_ids / d_scores (DEVICE, row-major [n][k]) receive the relations in ascending (score, id) order -- NaN after every number --

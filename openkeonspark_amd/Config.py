@@ -64,6 +64,10 @@ class Config(object):
             # link_prediction on an entity table sharded across ranks: the test set goes in chunks whose fetched query rows
             # (2 rows of 4 * dim bytes per triple) take at most this many bytes (at least one triple per chunk)
             self.lp_shard_query_bytes = 256 << 20
+            # top_k_tails / top_k_heads on such a table: all ranks' queries go in chunks whose fetched fixed-side rows and key
+            # lists (4 * dim + 8 * k bytes per query) take at most this many bytes (at least one query per chunk; the smallest
+            # value over the ranks holds)
+            self.topk_shard_query_bytes = 256 << 20
 
     # ------------------------------------------------------------------------------------------
     # Config.py:153-210
@@ -1495,7 +1499,11 @@ class Config(object):
         arrays, broadcast against each other.  Returns (ids int64 [n, k], scores float32 [n, k]) in ascending (score, id)
         order, padded with -1 / +inf where fewer than k candidates are eligible; numpy in gives numpy out, device tensors in
         give device tensors out.  filtered drops known triples (train + valid + test), type_constrained keeps the relation's
-        tail type list -- both need init_link_prediction()."""
+        tail type list -- both need init_link_prediction().
+        On an entity table sharded across ranks it is a collective: every rank calls it the same number of times, each with
+        its own queries (possibly none) and the same k, side and flags, and gets the results of its own queries, with the bits
+        of one process over the whole table (kge_topk_entities_range, kge_topk_merge_keys).  Arguments invalid on any rank,
+        or k / side / flags differing between ranks, raise KgeError on every rank."""
         return self._top_k_entities(h, r, k, False, filtered, type_constrained)
 
     def top_k_heads(self, t, r, k, filtered=False, type_constrained=False):
@@ -1509,22 +1517,24 @@ class Config(object):
         tensors in give device tensors out.  Scores are kge_predict's, TransR with each relation's own matrix.  filtered drops
         relations forming a known triple (train + valid + test), type_constrained keeps relations whose head / tail type lists
         hold h / t -- both need init_link_prediction()."""
+        if self._sharded("ent_embeddings"):
+            raise KgeError("top-k relation prediction over an entity table sharded across ranks is not supported")
         h, t, n, on_device = self._topk_queries(h, t, k, self.entTotal, self.entTotal)
         return self._topk_call(self.lib.kge_topk_relations, (h.data_ptr(), t.data_ptr()), n, k, filtered, type_constrained, on_device)
 
     def _top_k_entities(self, fixed, rel, k, head, filtered, type_constrained):
         import torch
+        if self._sharded("ent_embeddings"):
+            return self._top_k_entities_sharded(fixed, rel, k, head, filtered, type_constrained)
         f, r, n, on_device = self._topk_queries(fixed, rel, k, self.entTotal, self.relTotal)
         side = torch.full((n,), 1 if head else 0, dtype=torch.int32, device=self.device)
         return self._topk_call(self.lib.kge_topk_entities, (f.data_ptr(), r.data_ptr(), side.data_ptr()), n, k, filtered,
                                type_constrained, on_device)
 
     def _topk_queries(self, a, b, k, a_total, b_total):
-        """Argument handling of the top-k methods: the sharding and k checks, the two id arrays broadcast against each other
-        and checked against [0, a_total) / [0, b_total) before any launch.  -> (a, b as int32 device tensors, n, on_device)."""
+        """Argument handling of the top-k methods: the k check, the two id arrays broadcast against each other and checked
+        against [0, a_total) / [0, b_total) before any launch.  -> (a, b as int32 device tensors, n, on_device)."""
         import torch
-        if self._sharded("ent_embeddings"):
-            raise KgeError("top-k prediction over an entity table sharded across ranks is not supported")
         k = int(k)
         if not 1 <= k <= _lib.TOPK_MAX_K:
             raise KgeError("top-k prediction: k must be in [1, %d], got %d" % (_lib.TOPK_MAX_K, k))
@@ -1547,6 +1557,82 @@ class Config(object):
             a = torch.from_numpy(np.ascontiguousarray(ah, dtype=np.int32)).to(self.device)
             b = torch.from_numpy(np.ascontiguousarray(bh, dtype=np.int32)).to(self.device)
         return a, b, n, on_device
+
+    def _top_k_entities_sharded(self, fixed, rel, k, head, filtered, type_constrained):
+        """top_k_tails / top_k_heads on a sharded entity table (collective).  The ranks first agree on a header (query count,
+        k, side, flags, validity), so a bad call raises on every rank and leaves none waiting in a collective.  Then all ranks'
+        queries are taken in chunks: their fixed rows are fetched from the owners, each query's k best among this rank's rows
+        [lo, hi) are selected as packed keys (kge_topk_entities_range), each requester is sent the key lists of its own queries
+        only, and the W lists received for each of this rank's queries are merged (kge_topk_merge_keys)."""
+        import torch
+        from . import parallel as par
+        L, st, W, D, dev, pg = self.lib, self._stream(), self.world_size, self.hidden_size, self.device, self._pg
+        lo, hi = self._shard["lo"], self._shard["hi"]
+        flags = (_lib.TOPK_FILTERED if filtered else 0) | (_lib.TOPK_TYPED if type_constrained else 0)
+        err, f, r, n, on_device = None, None, None, 0, False
+        try:
+            f, r, n, on_device = self._topk_queries(fixed, rel, k, self.entTotal, self.relTotal)
+            k = int(k)
+            # the arguments, and the evaluation files the flags need, checked without a launch (no queries)
+            _lib.check(L.kge_topk_entities_range(ctypes.byref(self._desc), self._tab_ptrs, lo, hi - lo, None, None, None, None, 0, k,
+                                                 flags, None, st), L)
+        except (KgeError, ValueError, TypeError, RuntimeError) as e:
+            err, n = e, 0
+        kk = k if err is None else -1
+        per = max(1, int(self.topk_shard_query_bytes) // (4 * D + 8 * max(kk, 1)))
+        hdr = torch.tensor([0 if err else 1, n, kk, 1 if head else 0, flags, per], dtype=torch.int64, device=dev)
+        self.comm_fence("pg")
+        allh = torch.empty((W, hdr.numel()), dtype=torch.int64, device=dev)
+        par.all_gather_chunks(allh.view(-1), hdr, pg)
+        allh = allh.cpu().numpy()
+        if err is not None:
+            raise KgeError("top-k prediction on a sharded entity table: %s" % err) from err
+        if not allh[:, 0].all():
+            raise KgeError("top-k prediction on a sharded entity table: rank(s) %s passed invalid arguments"
+                           % np.nonzero(allh[:, 0] == 0)[0].tolist())
+        if (allh[:, 2:5] != allh[0, 2:5]).any():
+            raise KgeError("top-k prediction on a sharded entity table: the ranks passed different k, side or flags")
+        ns = allh[:, 1]
+        off = np.concatenate([[0], np.cumsum(ns)]).tolist()
+        N, me = off[-1], self.rank
+        per = int(allh[:, 5].min())
+        ids = torch.empty((n, k), dtype=torch.int32, device=dev)
+        scores = torch.empty((n, k), dtype=torch.float32, device=dev)
+        if N:
+            # every rank's queries (fixed, relation), rank-major: padded to the largest count for one all-gather
+            nmax = int(ns.max())
+            q = torch.zeros((nmax, 2), dtype=torch.int32, device=dev)
+            if n:
+                q[:n, 0] = f
+                q[:n, 1] = r
+            allq = torch.empty((W, nmax, 2), dtype=torch.int32, device=dev)
+            par.all_gather_chunks(allq.view(-1), q.view(-1), pg)
+            allq = torch.cat([allq[g, :int(ns[g])] for g in range(W)])
+            gf, gr = allq[:, 0].contiguous(), allq[:, 1].contiguous()
+            side = torch.full((N,), 1 if head else 0, dtype=torch.int32, device=dev)
+            for c0 in range(0, N, per):
+                c1 = min(N, c0 + per)
+                m = c1 - c0
+                rows, slot_of = self._fetch_rows(gf[c0:c1], m)
+                query = rows.index_select(0, slot_of.long())          # [m, D]: the fixed rows of the chunk's queries
+                del rows
+                keys = torch.empty((m, k), dtype=torch.int64, device=dev)
+                _lib.check(L.kge_topk_entities_range(ctypes.byref(self._desc), self._tab_ptrs, lo, hi - lo, query.data_ptr(),
+                                                     gf[c0:].data_ptr(), gr[c0:].data_ptr(), side[c0:].data_ptr(), m, k, flags,
+                                                     keys.data_ptr(), st), L)
+                del query
+                # rank g's queries are [off[g], off[g+1]): their key lists in this chunk go back to g alone
+                send = [max(0, min(c1, off[g + 1]) - max(c0, off[g])) for g in range(W)]
+                mine = send[me]
+                got = torch.empty((max(W * mine, 1), k), dtype=torch.int64, device=dev)
+                self.comm_fence("pg")
+                par.all_to_all_rows(got, keys, [mine] * W, send, pg, max_rows=max(send))
+                if mine:      # [W][mine][k]: one key list per source rank
+                    o0 = max(c0, off[me]) - off[me]
+                    _lib.check(L.kge_topk_merge_keys(got.data_ptr(), mine, W, k, ids[o0].data_ptr(), scores[o0].data_ptr(), st), L)
+        if on_device:
+            return ids.long(), scores
+        return ids.cpu().numpy().astype(np.int64), scores.cpu().numpy()
 
     def _topk_call(self, fn, query_ptrs, n, k, filtered, type_constrained, on_device):
         import torch

@@ -90,6 +90,8 @@ def _declare(L):
     L.kge_adam_update_tables.argtypes = [i32, vp, vp, vp, vp, vp, f32, f32, f32, f32, vp]
     L.kge_predict.argtypes = [ctypes.POINTER(ModelDesc), tabs, vp, vp, vp, i64, vp, vp]
     L.kge_topk_entities.argtypes = [ctypes.POINTER(ModelDesc), tabs, vp, vp, vp, i64, i64, i64, vp, vp, vp]
+    L.kge_topk_entities_range.argtypes = [ctypes.POINTER(ModelDesc), tabs, i64, i64, vp, vp, vp, vp, i64, i64, i64, vp, vp]
+    L.kge_topk_merge_keys.argtypes = [vp, i64, i64, i64, vp, vp, vp]
     L.kge_topk_relations.argtypes = [ctypes.POINTER(ModelDesc), tabs, vp, vp, i64, i64, i64, vp, vp, vp]
     L.kge_relation_prediction.argtypes = [ctypes.POINTER(ModelDesc), tabs, i64, i64, vp, vp]
     L.kge_link_prediction_range.argtypes = [ctypes.POINTER(ModelDesc), tabs, i64, i64, vp, i64, i64, i64, vp, vp, vp]

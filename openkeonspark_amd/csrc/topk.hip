@@ -15,6 +15,11 @@
 // in LDS) back to its k smallest keys and the threshold is raised.  Each (query, slice) leaves k keys.
 // Stage 2 (topk_merge_kernel), one workgroup per query: the same buffer logic over the slices' k-lists, then the unpack into
 // ids / scores.  With one slice the first stage writes the ids / scores itself.
+// Row range (kge_topk_entities_range, TransE; RANGE instantiations): the candidates are the rows of a shard of the table, global
+// ids [row_lo, row_lo + rows), and the fixed sides come from the caller's rows, not from the table (their owner may be another
+// rank).  The same side_xp, fma chain, team_sum and (L, C) bucket as the whole table, so every candidate's key carries the same
+// bits; both stages leave packed keys.  kge_topk_merge_keys takes the k smallest of several sources' key lists and unpacks
+// them: keys are unique per query (the id is the low word), so the k smallest of k-smallests over any cut is the whole table's.
 #include <algorithm>
 #include <cstring>
 #include <vector>
@@ -84,6 +89,9 @@ struct TopkArgs {
     uint64_t *part;            // [nq][slices][k] keys by launch position, or nullptr: write ids / scores directly
     int32_t *ids;
     float *scores;
+    long long row_lo;          // RANGE: global id of candidate row 0 (the candidate tables hold rows [row_lo, row_lo + E))
+    const float *qrows;        // RANGE: [nq][D] raw rows of the queries' fixed sides
+    uint64_t *keys;            // RANGE: [nq][k] keys out (with one slice the first stage writes them as its part)
 };
 
 __device__ __forceinline__ void emit_row(const TopkArgs &a, long long p, const uint64_t *b, int cnt) {
@@ -108,7 +116,7 @@ __device__ __forceinline__ bool eligible(const TopkArgs &a, bool hd, long long k
     return true;
 }
 
-template <int MODEL, int L, int C, int Q, int U, bool DIRECT>
+template <int MODEL, int L, int C, int Q, int U, bool DIRECT, bool RANGE>
 __global__ __launch_bounds__(256) void topk_select_kernel(TopkArgs a) {
     constexpr int TEAMS = 256 / L;
     constexpr int ROUND = TEAMS * U;   // candidates per round: the most a buffer can grow between two checks
@@ -165,7 +173,11 @@ __global__ __launch_bounds__(256) void topk_select_kernel(TopkArgs a) {
                 for (int c = 0; c < C; c++) cw0[c] = cx.cw[c];   // one relation per launch for the projecting models
             }
             float fv[C], finv;
-            if constexpr (DIRECT) {
+            if constexpr (RANGE) {
+                FbArgs qa = a.fa;
+                qa.ent = a.qrows;
+                finv = side_xp<MODEL, L, C>(tm, qa, qi, cx.cw, fv);
+            } else if constexpr (DIRECT) {
                 finv = side_xp<MODEL, L, C>(tm, a.fa, f, cx.cw, fv);
             } else {
                 tm.load(a.T, f, fv);
@@ -221,8 +233,9 @@ __global__ __launch_bounds__(256) void topk_select_kernel(TopkArgs a) {
                     }
                     s = team_sum<L>(s);
                     if (tm.lane == 0 && j < j1) {
-                        const uint64_t key = pack_key(MODEL == KGE_TRANSE ? s / dim : s, (int)j);
-                        if (key < thr[q] && eligible(a, hd, s_klo[q], s_khi[q], s_tlo[q], s_thi[q], (int)j))
+                        const int id = (int)(RANGE ? a.row_lo + j : j);
+                        const uint64_t key = pack_key(MODEL == KGE_TRANSE ? s / dim : s, id);
+                        if (key < thr[q] && eligible(a, hd, s_klo[q], s_khi[q], s_tlo[q], s_thi[q], id))
                             s_keys[(long long)q * a.cap + atomicAdd(&s_cnt[q], 1)] = key;
                     }
                 }
@@ -242,7 +255,7 @@ __global__ __launch_bounds__(256) void topk_select_kernel(TopkArgs a) {
     for (int q = 0; q < nb; q++) {
         const uint64_t *b = s_keys + (long long)q * a.cap;
         const int cnt = s_cnt[q];
-        if (a.part) {
+        if (RANGE || a.part) {
             uint64_t *o = a.part + ((p0 + q) * gridDim.y + blockIdx.y) * (long long)a.k;
             for (int i = threadIdx.x; i < a.k; i += blockDim.x) o[i] = i < cnt ? b[i] : kNoKey;
         } else {
@@ -251,7 +264,9 @@ __global__ __launch_bounds__(256) void topk_select_kernel(TopkArgs a) {
     }
 }
 
-// one workgroup per query: the k smallest of its slices' k-lists
+// one workgroup per query: the k smallest of its `slices` k-lists, [nq][slices][k] (stage 1's partial lists) or, IN_PARTS,
+// [slices][nq][k] (kge_topk_merge_keys: one list per source); unpacked into ids / scores or, OUT_KEYS, written as keys
+template <bool IN_PARTS, bool OUT_KEYS>
 __global__ __launch_bounds__(256) void topk_merge_kernel(TopkArgs a, int slices) {
     extern __shared__ uint64_t s_keys[];
     __shared__ uint64_t s_thr[1];
@@ -259,13 +274,13 @@ __global__ __launch_bounds__(256) void topk_merge_kernel(TopkArgs a, int slices)
     const long long p = blockIdx.x;
     if (threadIdx.x == 0) { s_thr[0] = kNoKey; s_cnt[0] = 0; }
     __syncthreads();
-    const uint64_t *in = a.part + p * (long long)slices * a.k;
+    const uint64_t *in = a.part + p * (long long)(IN_PARTS ? 1 : slices) * a.k;
     const long long total = (long long)slices * a.k;
     uint64_t thr = kNoKey;
     for (long long base = 0; base < total; base += 256) {
         const long long i = base + threadIdx.x;
         if (i < total) {
-            const uint64_t key = in[i];
+            const uint64_t key = IN_PARTS ? in[(i / a.k) * a.nq * a.k + i % a.k] : in[i];
             if (key < thr) s_keys[atomicAdd(&s_cnt[0], 1)] = key;
         }
         __syncthreads();
@@ -277,7 +292,11 @@ __global__ __launch_bounds__(256) void topk_merge_kernel(TopkArgs a, int slices)
         }
     }
     shrink_buffers(s_keys, a.cap, 1, 1u, a.k, s_cnt, s_thr);
-    emit_row(a, p, s_keys, s_cnt[0]);
+    if constexpr (OUT_KEYS) {
+        for (int i = threadIdx.x; i < a.k; i += blockDim.x) a.keys[p * a.k + i] = i < s_cnt[0] ? s_keys[i] : kNoKey;
+    } else {
+        emit_row(a, p, s_keys, s_cnt[0]);
+    }
 }
 
 unsigned pow2_at_least(unsigned x) { unsigned p = 1; while (p < x) p <<= 1; return p; }
@@ -330,7 +349,7 @@ int launch_table(int model, const FbArgs &a, int64_t r, int64_t E, float *T, flo
 
 constexpr int kSelectLdsBytes = 48 << 10;   // key buffers of one workgroup: two workgroups of 4 waves per CU
 
-template <int MODEL, int L, int C, int Q, int U, bool DIRECT>
+template <int MODEL, int L, int C, int Q, int U, bool DIRECT, bool RANGE>
 int launch_select_t(TopkArgs a, hipStream_t stream) {
     const int KP = (int)pow2_at_least((unsigned)std::max(a.k, 64));
     a.cap = 2 * KP;   // >= k + ROUND (ROUND <= 64)
@@ -346,15 +365,15 @@ int launch_select_t(TopkArgs a, hipStream_t stream) {
         if ((rc = grow(g_part, g_part_cap, a.nq * slices * a.k, "alloc top-k partial lists"))) return rc;
         a.part = g_part;
     } else {
-        a.part = nullptr;
+        a.part = RANGE ? a.keys : nullptr;
     }
     const size_t lds = (size_t)a.qn * a.cap * sizeof(uint64_t);
-    hipLaunchKernelGGL((topk_select_kernel<MODEL, L, C, Q, U, DIRECT>), dim3((unsigned)qblocks, (unsigned)slices), dim3(256), lds, stream, a);
+    hipLaunchKernelGGL((topk_select_kernel<MODEL, L, C, Q, U, DIRECT, RANGE>), dim3((unsigned)qblocks, (unsigned)slices), dim3(256), lds, stream, a);
     if ((rc = hip_check(hipGetLastError(), "top-k select launch"))) return rc;
     if (slices > 1) {
         a.cap = (int)pow2_at_least((unsigned)(a.k + 256));
         a.cap = std::max(a.cap, 2 * KP);
-        hipLaunchKernelGGL(topk_merge_kernel, dim3((unsigned)a.nq), dim3(256), (size_t)a.cap * sizeof(uint64_t), stream, a, (int)slices);
+        hipLaunchKernelGGL((topk_merge_kernel<false, RANGE>), dim3((unsigned)a.nq), dim3(256), (size_t)a.cap * sizeof(uint64_t), stream, a, (int)slices);
         if ((rc = hip_check(hipGetLastError(), "top-k merge launch"))) return rc;
     }
     return KGE_OK;
@@ -362,16 +381,16 @@ int launch_select_t(TopkArgs a, hipStream_t stream) {
 
 // (L, C) per width as launch_lp_scores; Q queries per workgroup and U rows per team so that the query vectors (2 Q C floats)
 // and the rows in flight (U C) stay in registers
-template <int MODEL, bool DIRECT>
+template <int MODEL, bool DIRECT, bool RANGE = false>
 int launch_select_d(const TopkArgs &a, hipStream_t stream) {
     const int D = a.fa.D;
-    if (D <= 16) return launch_select_t<MODEL, 16, 1, 16, 4, DIRECT>(a, stream);
-    if (D <= 32) return launch_select_t<MODEL, 16, 2, 16, 4, DIRECT>(a, stream);
-    if (D <= 64) return launch_select_t<MODEL, 16, 4, 16, 4, DIRECT>(a, stream);
-    if (D <= 128) return launch_select_t<MODEL, 32, 4, 16, 4, DIRECT>(a, stream);
-    if (D <= 256) return launch_select_t<MODEL, 64, 4, 16, 4, DIRECT>(a, stream);
-    if (D <= 512) return launch_select_t<MODEL, 64, 8, 8, 2, DIRECT>(a, stream);
-    if (D <= 1024) return launch_select_t<MODEL, 64, 16, 4, 1, DIRECT>(a, stream);
+    if (D <= 16) return launch_select_t<MODEL, 16, 1, 16, 4, DIRECT, RANGE>(a, stream);
+    if (D <= 32) return launch_select_t<MODEL, 16, 2, 16, 4, DIRECT, RANGE>(a, stream);
+    if (D <= 64) return launch_select_t<MODEL, 16, 4, 16, 4, DIRECT, RANGE>(a, stream);
+    if (D <= 128) return launch_select_t<MODEL, 32, 4, 16, 4, DIRECT, RANGE>(a, stream);
+    if (D <= 256) return launch_select_t<MODEL, 64, 4, 16, 4, DIRECT, RANGE>(a, stream);
+    if (D <= 512) return launch_select_t<MODEL, 64, 8, 8, 2, DIRECT, RANGE>(a, stream);
+    if (D <= 1024) return launch_select_t<MODEL, 64, 16, 4, 1, DIRECT, RANGE>(a, stream);
     return fail(KGE_ERR_UNSUPPORTED, "kge_topk_entities: embedding dimension > 1024");
 }
 
@@ -458,4 +477,65 @@ extern "C" int kge_topk_entities(const kge_model_desc *m, const float *const tab
         q0 = q1;
     }
     return KGE_OK;
+}
+
+extern "C" int kge_topk_entities_range(const kge_model_desc *m, const float *const tables[KGE_MAX_TABLES], INT row_lo, INT rows,
+                                       const float *d_query_rows, const int32_t *d_fixed, const int32_t *d_rel,
+                                       const int32_t *d_head, INT n, INT k, INT flags, uint64_t *d_keys, void *stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    if (!m || !tables) return fail(KGE_ERR_BAD_ARG, "kge_topk_entities_range: null model or tables");
+    if (m->model != KGE_TRANSE) return fail(KGE_ERR_UNSUPPORTED, "kge_topk_entities_range: TransE only");
+    if (m->ent_dim < 1 || m->ent_dim > 1024) return fail(KGE_ERR_UNSUPPORTED, "kge_topk_entities_range: embedding dimension must be in [1, 1024]");
+    if (k < 1 || k > 1024) return fail(KGE_ERR_BAD_ARG, "kge_topk_entities_range: k must be in [1, 1024]");
+    if (flags & ~(INT)(KGE_TOPK_FILTERED | KGE_TOPK_TYPED)) return fail(KGE_ERR_BAD_ARG, "kge_topk_entities_range: unknown flags");
+    if (n < 0) return fail(KGE_ERR_BAD_ARG, "kge_topk_entities_range: negative query count");
+    if (m->ent_total < 1 || m->rel_total < 1) return fail(KGE_ERR_BAD_ARG, "kge_topk_entities_range: empty model");
+    if (row_lo < 0 || rows < 0 || row_lo + rows > m->ent_total) return fail(KGE_ERR_BAD_ARG, "kge_topk_entities_range: row range outside the entity table");
+    if (!device_ok()) return fail(KGE_ERR_NO_DEVICE, "kge_topk_entities_range: no usable HIP device");
+    TopkArgs a = {};
+    if (flags) {
+        int rc = eval_filter_view((flags & KGE_TOPK_TYPED) != 0, a.ev);
+        if (rc) return rc;
+    }
+    if (n == 0) return KGE_OK;
+    if (!d_fixed || !d_rel || !d_head || !d_query_rows || !d_keys || !tables[1] || (rows > 0 && !tables[0]))
+        return fail(KGE_ERR_BAD_ARG, "kge_topk_entities_range: null table, query or output array");
+    int rc;
+    if (rows == 0)   // an empty shard: nothing to offer, every key padding
+        return hip_check(hipMemsetAsync(d_keys, 0xFF, sizeof(uint64_t) * (size_t)(n * k), stream), "top-k range padding");
+    const int D = (int)m->ent_dim;
+    a.fa.ent = tables[0]; a.fa.rel = tables[1];
+    a.fa.D = D;
+    a.fixed = d_fixed; a.rel = d_rel; a.head = d_head;
+    a.order = nullptr; a.nq = n;
+    a.E = rows; a.row_lo = row_lo; a.qrows = d_query_rows; a.keys = d_keys;
+    a.k = (int)k; a.flags = (int)flags;
+    const int64_t budget = engine().topk_table_max_bytes;
+    const bool table = budget > 0 && rows * D * (int64_t)sizeof(float) <= budget;
+    if (table) {
+        if ((rc = grow(g_inv, g_inv_cap, rows, "alloc top-k inverse norms"))) return rc;
+        if ((rc = launch_table(KGE_TRANSE, a.fa, 0, rows, nullptr, g_inv, stream))) return rc;
+        a.T = a.fa.ent;
+        a.Tinv = g_inv;
+        return launch_select_d<KGE_TRANSE, false, true>(a, stream);
+    }
+    return launch_select_d<KGE_TRANSE, true, true>(a, stream);
+}
+
+extern "C" int kge_topk_merge_keys(const uint64_t *d_keys, INT n, INT parts, INT k, int32_t *d_ids, float *d_scores, void *stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    if (k < 1 || k > 1024) return fail(KGE_ERR_BAD_ARG, "kge_topk_merge_keys: k must be in [1, 1024]");
+    if (n < 0 || parts < 1) return fail(KGE_ERR_BAD_ARG, "kge_topk_merge_keys: negative query count or no key list");
+    if (parts > (INT)1 << 20) return fail(KGE_ERR_BAD_ARG, "kge_topk_merge_keys: more than 2^20 key lists per query");
+    if (!device_ok()) return fail(KGE_ERR_NO_DEVICE, "kge_topk_merge_keys: no usable HIP device");
+    if (n == 0) return KGE_OK;
+    if (!d_keys || !d_ids || !d_scores) return fail(KGE_ERR_BAD_ARG, "kge_topk_merge_keys: null key or output array");
+    TopkArgs a = {};
+    a.part = const_cast<uint64_t *>(d_keys);
+    a.nq = n; a.k = (int)k;
+    a.ids = d_ids; a.scores = d_scores;
+    const int KP = (int)pow2_at_least((unsigned)std::max(a.k, 64));
+    a.cap = std::max((int)pow2_at_least((unsigned)(a.k + 256)), 2 * KP);   // as launch_select_t's merge
+    hipLaunchKernelGGL((topk_merge_kernel<true, false>), dim3((unsigned)n), dim3(256), (size_t)a.cap * sizeof(uint64_t), stream, a, (int)parts);
+    return hip_check(hipGetLastError(), "top-k key merge launch");
 }
