@@ -168,10 +168,10 @@ const char *kge_version(void);
  *                     score the candidates from a table of their
  *                     projected, normalised vectors while it is at most this many bytes (E x dim x 4; default 1 GiB); larger
  *                     tables, or 0, compute the candidate side on the fly from the parameter rows (same functions, same bits)
- *   "relpred_chunk_bytes": kge_topk_relations / kge_relation_prediction score their queries in chunks whose [chunk x R] fp32 score
- *                     block is at most this many bytes (default 256 MiB; at least one query per chunk); TransR's buffer of
- *                     projected distinct entities is held to the same size (at least one relation per block).  Results do not
- *                     depend on it, bit for bit
+ *   "relpred_chunk_bytes": kge_topk_relations / kge_relation_prediction / kge_relation_prediction_rows score their queries in
+ *                     chunks whose [chunk x R] fp32 score block is at most this many bytes (default 256 MiB; at least one query
+ *                     per chunk); TransR's buffer of projected distinct entities is held to the same size (at least one relation
+ *                     per block).  Results do not depend on it, bit for bit
  *   "libc_rand_restart": restart the glibc-compatible seed generator, as in a fresh process (the next
  *                        randReset then yields 1804289383, 846930886, ... again) */
 int kge_set_option(const char *name, INT value);
@@ -551,6 +551,16 @@ int kge_topk_relations(const kge_model_desc *m, const float *const tables[KGE_MA
  * then.  KGE_ERR_NO_DATASET before importTestFiles.  One host synchronisation, at the end. */
 int kge_relation_prediction(const kge_model_desc *m, const float *const tables[KGE_MAX_TABLES], INT first, INT count,
                             int64_t *h_out, void *stream);
+/* Relation prediction with the entity rows supplied by the caller (an entity table sharded by rows across ranks;
+ * csrc/relpred.hip).  Test triples [first, first+count) in kge_relation_prediction's order; d_query_rows (DEVICE fp32
+ * [count][2][ent_dim]) holds the raw h and t rows of each triple, the layout kge_link_prediction_range takes.  d_counts (DEVICE
+ * int64 [count][4], written) receives kge_relation_prediction's four columns: raw, filtered, typed, filtered + typed.  tables[0]
+ * is never read (on a sharded rank it is the shard); tables[1] is the whole relation table.  The scores come from the same
+ * kernel instantiation on the same row values, so the counts equal kge_relation_prediction's exactly.  TransE only
+ * (KGE_ERR_UNSUPPORTED otherwise; ent_dim <= 1024).  KGE_ERR_NO_DATASET before importTestFiles, KGE_ERR_BAD_ARG for a range
+ * outside the test set.  With count == 0 only the arguments and the files are checked.  No host synchronisation. */
+int kge_relation_prediction_rows(const kge_model_desc *m, const float *const tables[KGE_MAX_TABLES], const float *d_query_rows,
+                                 INT first, INT count, int64_t *d_counts, void *stream);
 
 /* predict op: score n triples.  TransE: mean over the dimension (TransE.py:58); others: sum
  * (TransH.py:82, TransR.py:87 with predict_r[0]'s matrix for all, TransD.py:98). */

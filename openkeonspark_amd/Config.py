@@ -61,8 +61,9 @@ class Config(object):
             self.global_step = 0
             self.rank, self.world_size = 0, 1
             self._pg = None
-            # link_prediction on an entity table sharded across ranks: the test set goes in chunks whose fetched query rows
-            # (2 rows of 4 * dim bytes per triple) take at most this many bytes (at least one triple per chunk)
+            # link_prediction and relation_prediction on an entity table sharded across ranks: the test set goes in chunks
+            # whose fetched query rows (2 rows of 4 * dim bytes per triple) take at most this many bytes (at least one triple
+            # per chunk; for relation_prediction, the smallest value over the ranks holds)
             self.lp_shard_query_bytes = 256 << 20
             # top_k_tails / top_k_heads on such a table: all ranks' queries go in chunks whose fetched fixed-side rows and key
             # lists (4 * dim + 8 * k bytes per query) take at most this many bytes (at least one query per chunk; the smallest
@@ -1741,17 +1742,27 @@ class Config(object):
         """Rank the true relation of every test triple in [first, first+count) (kge_link_prediction's order) among all
         relations on the device (kge_relation_prediction).  Returns (raw int64 [count, 4]: the relations scoring strictly
         better, raw / filtered / typed / filtered + typed, and the 20 rel* metrics normalised by the number of triples).
-        Without type_constrain.txt the typed columns are 0."""
+        Without type_constrain.txt the typed columns are 0.
+        On an entity table sharded across ranks it is a collective: every rank calls it with the same arguments and gets the
+        same result, bit for bit that of one process over the whole table.  Each rank ranks one contiguous slice of the
+        triples from h / t rows fetched from their owners (kge_relation_prediction_rows) and the counts are summed across
+        ranks.  Arguments invalid on any rank, or first / count differing between ranks, raise KgeError on every rank."""
         if count is None:
             count = self.lib.getTestTotal() - first
-        out = np.zeros((count, 4), dtype=np.int64)
-        self._relation_counts(first, count, out)
+        if self._sharded("ent_embeddings"):
+            out = self._relation_prediction_sharded(first, count)
+        else:
+            out = np.zeros((count, 4), dtype=np.int64)
+            self._relation_counts(first, count, out)
         return out, self._lp_normalise(self._rel_sums(out), count)
 
     def relation_prediction_distributed(self):
         """relation_prediction over the whole test set split into one contiguous range per rank and all-reduced, as
-        link_prediction_distributed does: every rank returns the global metrics."""
+        link_prediction_distributed does: every rank returns the global metrics.
+        On a sharded entity table it is relation_prediction over the whole test set, a collective."""
         total = self.lib.getTestTotal()
+        if self._sharded("ent_embeddings"):
+            return self.relation_prediction(0, total)[1]
         per = (total + self.world_size - 1) // self.world_size
         lo = min(self.rank * per, total)
         hi = min(lo + per, total)
@@ -1761,10 +1772,62 @@ class Config(object):
         return self._lp_normalise(self._all_reduce_sums(self._rel_sums(out)), total)
 
     def _relation_counts(self, first, count, out):
-        if self._sharded("ent_embeddings"):
-            raise KgeError("relation prediction over an entity table sharded across ranks is not supported")
         _lib.check(self.lib.kge_relation_prediction(ctypes.byref(self._desc), self._tab_ptrs, first, count, out.ctypes.data,
                                                     self._stream()), self.lib)
+
+    def _relation_prediction_sharded(self, first, count):
+        """relation_prediction on a sharded entity table (collective).  The ranks first agree on a header (validity, first,
+        count, triples per round), so a bad call raises on every rank and leaves none waiting in a collective.  Then rank g
+        takes the g-th contiguous slice of [first, first+count) in rounds of at most `per` triples: the h / t rows come from
+        their owners (_fetch_rows, which every rank joins in every round, with no ids once its slice is done) and
+        kge_relation_prediction_rows writes the slice's rows of a zeroed [count, 4]; one SUM all-reduce merges them."""
+        import torch
+        import torch.distributed as dist
+        from . import parallel as par
+        L, st, W, D, dev, pg = self.lib, self._stream(), self.world_size, self.hidden_size, self.device, self._pg
+        if not dist.is_initialized():      # no process group, so no other rank can be waiting for this one
+            raise KgeError("relation prediction on a sharded entity table needs the process group it was sharded over")
+        err = None
+        try:
+            first, count = int(first), int(count)
+            if first < 0 or count < 0:
+                raise KgeError("relation prediction: bad range (first %d, count %d)" % (first, count))
+            # the arguments and the evaluation files, checked without a launch: the range's end, then no triples
+            _lib.check(L.kge_relation_prediction_rows(ctypes.byref(self._desc), self._tab_ptrs, None, first + count, 0, None, st), L)
+        except (KgeError, ValueError, TypeError, OverflowError) as e:
+            err, first, count = e, -1, -1
+        per = max(1, int(self.lp_shard_query_bytes) // (2 * D * 4))
+        hdr = torch.tensor([0 if err else 1, first, count, per], dtype=torch.int64, device=dev)
+        self.comm_fence("pg")
+        allh = torch.empty((W, hdr.numel()), dtype=torch.int64, device=dev)
+        par.all_gather_chunks(allh.view(-1), hdr, pg)
+        allh = allh.cpu().numpy()
+        if err is not None:
+            raise KgeError("relation prediction on a sharded entity table: %s" % err) from err
+        if not allh[:, 0].all():
+            raise KgeError("relation prediction on a sharded entity table: rank(s) %s passed invalid arguments"
+                           % np.nonzero(allh[:, 0] == 0)[0].tolist())
+        if (allh[:, 1:3] != allh[0, 1:3]).any():
+            raise KgeError("relation prediction on a sharded entity table: the ranks passed different first or count")
+        per = int(allh[:, 3].min())
+        cs = par.chunk_size(count, W)
+        lo = first + min(self.rank * cs, count)
+        hi = first + min((self.rank + 1) * cs, count)
+        counts = torch.zeros((max(count, 1), 4), dtype=torch.int64, device=dev)
+        for r0 in range(0, cs, per):
+            c0 = min(lo + r0, hi)
+            n = min(per, hi - c0)
+            ids = torch.empty(max(2 * n, 1), dtype=torch.int32, device=dev)
+            _lib.check(L.kge_test_entity_ids(c0, n, ids.data_ptr(), st), L)
+            rows, slot_of = self._fetch_rows(ids, 2 * n)
+            if n:
+                query = rows.index_select(0, slot_of.long())      # [2n, D]: the h and t rows of each triple
+                _lib.check(L.kge_relation_prediction_rows(ctypes.byref(self._desc), self._tab_ptrs, query.data_ptr(), c0, n,
+                                                          counts[c0 - first].data_ptr(), st), L)
+                del query
+            del rows
+        self._all_reduce_on_pg(counts, dist.ReduceOp.SUM)
+        return counts[:count].cpu().numpy()
 
     # ------------------------------------------------------------------------------------------
     # parameters by the reference's variable names (Config.py:378-421)

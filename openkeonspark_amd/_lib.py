@@ -94,6 +94,7 @@ def _declare(L):
     L.kge_topk_merge_keys.argtypes = [vp, i64, i64, i64, vp, vp, vp]
     L.kge_topk_relations.argtypes = [ctypes.POINTER(ModelDesc), tabs, vp, vp, i64, i64, i64, vp, vp, vp]
     L.kge_relation_prediction.argtypes = [ctypes.POINTER(ModelDesc), tabs, i64, i64, vp, vp]
+    L.kge_relation_prediction_rows.argtypes = [ctypes.POINTER(ModelDesc), tabs, vp, i64, i64, vp, vp]
     L.kge_link_prediction_range.argtypes = [ctypes.POINTER(ModelDesc), tabs, i64, i64, vp, i64, i64, i64, vp, vp, vp]
     L.kge_link_prediction_finish.argtypes = [i64, i64, i64, vp, vp, vp, vp]
     L.kge_test_entity_ids.argtypes = [i64, i64, vp, vp]

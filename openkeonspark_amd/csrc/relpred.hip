@@ -21,6 +21,8 @@
 //  - relpred_rank_kernel: the relations r' != r scoring strictly below the true relation's score (NaN never counts, as in
 //    rank_kernel), raw, filtered, typed and filtered + typed.
 // No host synchronisation between chunks or relation blocks; kge_relation_prediction copies its counts back once at the end.
+// kge_relation_prediction_rows (TransE, a sharded entity table) runs the same two stages on h / t rows the caller supplies and
+// leaves its counts on the device.
 #include <algorithm>
 #include <cstring>
 #include <vector>
@@ -383,6 +385,12 @@ int32_t *g_uent = nullptr;        // [ucap] distinct entities, then [1] their co
 int64_t g_uent_cap = 0;
 long long *g_counts = nullptr;
 int64_t g_counts_cap = 0;
+int32_t *g_qslot = nullptr;       // [cap] = 0, 1, ..., cap-1: the query slots of kge_relation_prediction_rows' chunk rows
+int64_t g_qslot_cap = 0;
+
+__global__ void relpred_iota_kernel(int32_t *__restrict__ out, long long n) {
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) out[i] = (int32_t)i;
+}
 
 template <typename T>
 int grow(T *&buf, int64_t &cap, int64_t need, const char *what) {
@@ -581,4 +589,53 @@ extern "C" int kge_relation_prediction(const kge_model_desc *m, const float *con
     }
     if ((rc = hip_check(hipMemcpyAsync(h_out, g_counts, sizeof(int64_t) * 4 * (size_t)count, hipMemcpyDeviceToHost, stream), "copy relation ranks"))) return rc;
     return hip_check(hipStreamSynchronize(stream), "relation rank sync");
+}
+
+// kge_relation_prediction with the h / t rows supplied by the caller (a sharded entity table).  Each chunk's 2 * nc rows are
+// scored as an entity table of their own -- a descriptor with ent_total = 2 * nc, tables[0] = the chunk's rows, query ids
+// 2i / 2i+1 read from g_qslot at stride 2 -- by the same relpred_score_kernel instantiation on the same row values, so the
+// scores, and the counts relpred_rank_kernel forms from them with the test set's global (h, t, r), are kge_relation_prediction's.
+extern "C" int kge_relation_prediction_rows(const kge_model_desc *m, const float *const tables[KGE_MAX_TABLES], const float *d_query_rows,
+                                            INT first, INT count, int64_t *d_counts, void *stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    if (!m || !tables) return fail(KGE_ERR_BAD_ARG, "kge_relation_prediction_rows: null model or tables");
+    if (m->model != KGE_TRANSE) return fail(KGE_ERR_UNSUPPORTED, "kge_relation_prediction_rows: TransE only");
+    if (m->ent_dim < 1 || m->ent_dim > 1024) return fail(KGE_ERR_UNSUPPORTED, "kge_relation_prediction_rows: embedding dimension must be in [1, 1024]");
+    if (m->rel_total < 1) return fail(KGE_ERR_BAD_ARG, "kge_relation_prediction_rows: empty model");
+    if (!device_ok()) return fail(KGE_ERR_NO_DEVICE, "kge_relation_prediction_rows: no usable HIP device");
+    RelSelectArgs s = {};
+    int rc = eval_filter_view(false, s.ev);
+    if (rc) return rc;
+    const int4 *test;
+    int64_t total;
+    if ((rc = eval_test_view(test, total))) return rc;
+    if (first < 0 || count < 0 || first + count > total) return fail(KGE_ERR_BAD_ARG, "kge_relation_prediction_rows: bad range");
+    if (count == 0) return KGE_OK;
+    if (!d_query_rows || !d_counts || !tables[1]) return fail(KGE_ERR_BAD_ARG, "kge_relation_prediction_rows: null relation table, query or output array");
+    int64_t chunk;
+    if ((rc = prepare(*m, count, chunk))) return rc;
+    if (g_qslot_cap < 2 * chunk) {
+        if ((rc = grow(g_qslot, g_qslot_cap, 2 * chunk, "alloc relation query slots"))) return rc;
+        hipLaunchKernelGGL(relpred_iota_kernel, dim3((unsigned)std::min<int64_t>((g_qslot_cap + 255) / 256, 4096)), dim3(256), 0, stream,
+                           g_qslot, (long long)g_qslot_cap);
+        if ((rc = hip_check(hipGetLastError(), "relation query slots launch"))) return rc;
+    }
+    const int64_t D = m->ent_dim;
+    kge_model_desc mc = *m;
+    const float *tabs[KGE_MAX_TABLES];
+    for (int i = 0; i < KGE_MAX_TABLES; i++) tabs[i] = tables[i];
+    const int32_t *base = reinterpret_cast<const int32_t *>(test + first);   // (h, t, r, 0)
+    s.S = g_S; s.qs = 4; s.R = m->rel_total;
+    for (int64_t c0 = 0; c0 < count; c0 += chunk) {
+        const int64_t nc = std::min<int64_t>(chunk, count - c0);
+        mc.ent_total = 2 * nc;
+        tabs[0] = d_query_rows + 2 * c0 * D;
+        if ((rc = score_chunk(mc, tabs, g_qslot, g_qslot + 1, 2, nc, stream))) return rc;
+        const int32_t *qh = base + 4 * c0;
+        s.qh = qh; s.qt = qh + 1; s.qr = qh + 2; s.n = nc;
+        s.counts = (long long *)d_counts + 4 * c0;
+        hipLaunchKernelGGL(relpred_rank_kernel, dim3((unsigned)nc), dim3(256), 0, stream, s);
+        if ((rc = hip_check(hipGetLastError(), "relation rank launch"))) return rc;
+    }
+    return KGE_OK;
 }
