@@ -14,7 +14,11 @@ inputs resident in HBM.  N GPUs = N processes, rank g owns the virtual sampler t
 chunk of the tables and the updated chunks are all-gathered.  Per-GPU batch is held at ~34 014 positives
 (nbatches = 8/N), so scaling is weak.
 
-python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full [--no-cpu-baseline]]
+A plain run sets up, warms up, times the K steps and prints the result line (with the emit kernel's roofline from the
+launches timed inside the region).  --full adds what the headline does not need: at N = 1 the CPU baselines, the engine on
+config #1, the eval leg and the exchange rehearsal (--no-cpu-baseline leaves these out), and for short runs further steps
+after the timed region until 50 emit launches are timed.
 N > 1 from a bare shell: this process starts the N ranks itself (`python -m torch.distributed.run`, one rank per GPU, RCCL over
 xGMI) BEFORE anything touches a GPU, relays rank 0's JSON line and exits with the job's status -- what the reference's launcher
 does with TFCluster.run (main_spark.py:340).  Under an external torchrun (WORLD_SIZE set) it is one of the ranks.
@@ -191,7 +195,7 @@ def exchange_rehearsal(steps=100, warmup=20, timeout=240):
     env = dict(os.environ, KGE_BENCH_FORCE_DIST="1", KGE_BENCH_FORCE_DP="1", MASTER_ADDR="127.0.0.1",
                MASTER_PORT=str(29650 + os.getpid() % 300), RANK="0", WORLD_SIZE="1", LOCAL_RANK="0")
     try:
-        p = subprocess.run([sys.executable, os.path.abspath(__file__), "--steps", str(steps), "--warmup", str(warmup), "--no-cpu-baseline"],
+        p = subprocess.run([sys.executable, os.path.abspath(__file__), "--steps", str(steps), "--warmup", str(warmup)],
                            env=env, stdout=subprocess.PIPE, stderr=subprocess.DEVNULL, timeout=timeout, check=False)
         line = [l for l in p.stdout.decode(errors="replace").splitlines() if l.startswith("{")][-1]
         d = json.loads(line)
@@ -324,7 +328,11 @@ def main():
     # the first ~30 steps carry more gradient records than the rest of an epoch (0.27 ms/step over steps 5..25, 0.22 from step 20 on)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: CPU baselines, config #1, eval, exchange rehearsal, "
+                         "and the top-up of the emit kernel's timing sample to 50 launches")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out the CPU baselines, config #1, eval "
+                                                                   "and the exchange rehearsal")
     ap.add_argument("--prefetch-sampling", choices=["auto", "on", "off"], default="auto",
                     help="batch i+1 sampled on a side stream behind the emit kernel of step i (Config.prefetch_sampling; "
                          "bit-identical batches).  auto = the Config default")
@@ -457,9 +465,9 @@ def main():
     timed = ctypes.c_int64()
     in_region = (args.steps + 3) // 4
     extra = 0
-    # --steps >= 200: all >= 50 timed launches lie INSIDE the timed region and nothing more is run; shorter runs top the sample up
-    # with further steps of the same training run after the region (the regime is reported: roofline.kernel_ms_regime)
-    while in_region + extra // 4 < 50 and extra < 400:
+    # --steps >= 200: all >= 50 timed launches lie INSIDE the timed region and nothing more is run; under --full shorter runs top
+    # the sample up with further steps of the same training run after the region (the regime is reported: roofline.kernel_ms_regime)
+    while args.full and in_region + extra // 4 < 50 and extra < 400:
         con.train_step(sync=False)
         extra += 1
     sync()
@@ -517,7 +525,7 @@ def main():
                          "step": {"algorithmic_bytes": step_bytes, "achieved": step_gbps, "frac": step_gbps / HBM_PEAK_GBS,
                                   "unit": "GB/s", "what": "gather bytes of the step + the dense TF1 Adam sweep, over ms_per_step"}},
         }
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline(fb_dir, n_local)
             # the survey's own protocol (config #1, workThreads 1 and all cores, median + p10/p90) with the engine beside it
             sys.stdout.flush()

@@ -7,16 +7,16 @@ out=$1
 cd /tmp && export TMPDIR=/tmp
 mkdir -p $GRAFT_REPO_ROOT/$out
 cd $GRAFT_REPO_ROOT
-python3 bench.py > $out/bench_default.log 2>&1; grep -a "^{" $out/bench_default.log | tail -1 > $out/bench_line_default.json
-python3 bench.py --steps 20 --warmup 5 > $out/bench_steps20.log 2>&1; grep -a "^{" $out/bench_steps20.log | tail -1 > $out/bench_line_steps20.json
+python3 bench.py --full > $out/bench_default.log 2>&1; grep -a "^{" $out/bench_default.log | tail -1 > $out/bench_line_default.json
+python3 bench.py --full --steps 20 --warmup 5 > $out/bench_steps20.log 2>&1; grep -a "^{" $out/bench_steps20.log | tail -1 > $out/bench_line_steps20.json
 echo "bench lines done"
-rocprofv3 --kernel-trace --stats -d $out/kt -o r -- python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline > $out/kt.log 2>&1
+rocprofv3 --kernel-trace --stats -d $out/kt -o r -- python3 bench.py --full --steps 20 --warmup 5 --no-cpu-baseline > $out/kt.log 2>&1
 python3 tools/rocpd_stats.py $out/kt/r_results.db $out/kernel_stats_bench.csv
 python3 tools/step_durations.py $out/kt/r_results.db 0 30 > $out/step_durations_bench.txt
 python3 tools/step_durations.py $out/kt/r_results.db 150 156 >> $out/step_durations_bench.txt
 rm -rf $out/kt
-rocprofv3 --pmc FETCH_SIZE -d $out/pmc_fetch -o r -- python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline > $out/pmc_fetch.log 2>&1
-rocprofv3 --pmc WRITE_SIZE -d $out/pmc_write -o r -- python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline > $out/pmc_write.log 2>&1
+rocprofv3 --pmc FETCH_SIZE -d $out/pmc_fetch -o r -- python3 bench.py --full --steps 20 --warmup 5 --no-cpu-baseline > $out/pmc_fetch.log 2>&1
+rocprofv3 --pmc WRITE_SIZE -d $out/pmc_write -o r -- python3 bench.py --full --steps 20 --warmup 5 --no-cpu-baseline > $out/pmc_write.log 2>&1
 python3 - <<PY
 import sqlite3, json
 res = {}

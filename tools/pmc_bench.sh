@@ -7,9 +7,9 @@ pat="${@:-segapply emit_vec bkt_ apply_counts}"
 cd /tmp && export TMPDIR=/tmp
 mkdir -p $GRAFT_REPO_ROOT/$out
 cd $GRAFT_REPO_ROOT
-rocprofv3 --pmc SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_SCA SQ_ACTIVE_INST_VMEM SQ_WAVES -d $out/pmcA -o r -- python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline > $out/pmcA.log 2>&1
-rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_INSTS_SMEM SQ_INSTS_LDS SQ_INSTS_BRANCH SQ_BUSY_CYCLES -d $out/pmcB -o r -- python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline > $out/pmcB.log 2>&1
-rocprofv3 --pmc TA_TA_BUSY_sum TA_TOTAL_WAVEFRONTS_sum TCP_TOTAL_ACCESSES_sum TCP_TCC_READ_REQ_sum TCP_PENDING_STALL_CYCLES_sum TCP_TCP_TA_DATA_STALL_CYCLES_sum GRBM_GUI_ACTIVE -d $out/pmcC -o r -- python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline > $out/pmcC.log 2>&1 || true
+rocprofv3 --pmc SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_SCA SQ_ACTIVE_INST_VMEM SQ_WAVES -d $out/pmcA -o r -- python3 bench.py --full --steps 20 --warmup 5 --no-cpu-baseline > $out/pmcA.log 2>&1
+rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_INSTS_SMEM SQ_INSTS_LDS SQ_INSTS_BRANCH SQ_BUSY_CYCLES -d $out/pmcB -o r -- python3 bench.py --full --steps 20 --warmup 5 --no-cpu-baseline > $out/pmcB.log 2>&1
+rocprofv3 --pmc TA_TA_BUSY_sum TA_TOTAL_WAVEFRONTS_sum TCP_TOTAL_ACCESSES_sum TCP_TCC_READ_REQ_sum TCP_PENDING_STALL_CYCLES_sum TCP_TCP_TA_DATA_STALL_CYCLES_sum GRBM_GUI_ACTIVE -d $out/pmcC -o r -- python3 bench.py --full --steps 20 --warmup 5 --no-cpu-baseline > $out/pmcC.log 2>&1 || true
 python3 - "$out" $pat <<'PY'
 import sqlite3, sys, os
 out, pats = sys.argv[1], sys.argv[2:]
