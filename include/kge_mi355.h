@@ -293,6 +293,9 @@ int kge_float_records_apply(const kge_model_desc *m, float *const tables[KGE_MAX
 /* 1 when kge_forward_backward on a step of this shape takes the TransH / TransD pair-count path (whose emit kernel also records
  * the event above), else 0 */
 int kge_pair_path_active(const kge_model_desc *m, INT n_pos, INT n_neg);
+/* 1 when kge_forward_backward_sampled on a TransR step of this shape takes the group layout (groups sorted by relation, the
+ * vector stage in the projection's epilogue: option "transr_groups"), else 0 -- what the tests of that layout assert */
+int kge_transr_group_layout_active(const kge_model_desc *m, INT n_pos, INT n_neg);
 
 /* The same call for a batch the caller KNOWS to be sampler-shaped -- what kge_sampling_device / `sampling` produce
  * (Base.cpp:109-139): every negative differs from its positive in exactly one entity slot, or (negative_rel) in the relation.

@@ -77,6 +77,7 @@ def _declare(L):
     L.kge_forward_backward.argtypes = [ctypes.POINTER(ModelDesc), tabs, vp, vp, vp, i64, i64, i64, i64, tabs, vp, vp]
     L.kge_stream_wait_emit.argtypes = [vp]
     L.kge_pair_path_active.argtypes = [ctypes.POINTER(ModelDesc), i64, i64]
+    L.kge_transr_group_layout_active.argtypes = [ctypes.POINTER(ModelDesc), i64, i64]
     L.kge_loss_limbs_target.argtypes = [vp]
     L.kge_forward_backward_sgd_rows.argtypes = [ctypes.POINTER(ModelDesc), tabs, vp, vp, vp, i64, i64, i64, i64, f32, vp, vp]
     L.kge_forward_backward_records.argtypes = [ctypes.POINTER(ModelDesc), tabs, vp, vp, vp, i64, i64, i64, i64, i64, vp, vp, i64, i64, vp, vp]

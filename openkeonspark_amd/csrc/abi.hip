@@ -422,6 +422,10 @@ int kge_sgd_rows_skipped(int32_t *n_negatives) {
 
 int kge_pair_path_active(const kge_model_desc *m, INT n_pos, INT n_neg) { return m && pair_path_active(*m, n_pos, n_neg) ? 1 : 0; }
 
+int kge_transr_group_layout_active(const kge_model_desc *m, INT n_pos, INT n_neg) {
+    return m && transr_group_layout_active(*m, n_pos, n_neg) ? 1 : 0;
+}
+
 int kge_stream_wait_emit(void *stream) {
     Engine &e = engine();
     // nothing recorded since the last wait (recording off, or this step's path has no emit kernel): the caller must order the

@@ -44,7 +44,7 @@ struct TrWork {
     int32_t *bucket_start = nullptr;  // [R+2]
     int32_t *tile_rel = nullptr, *tile_row0 = nullptr, *n_tiles = nullptr;
     int32_t *bucket_rows = nullptr;   // group layout: start of every relation's ROW space ([R + 2]; bucket_start holds the group starts there)
-    int64_t cap_rel_rows = 0, pad_ready = -1;
+    int64_t cap_rel_rows = 0;
     int32_t *rel_hist = nullptr;      // two alternating pairs of [kRelBins] bucket sizes + [kRelBins] scatter cursors
     int rel_parity = 0;
     void *sort_tmp = nullptr;
@@ -80,7 +80,7 @@ int ensure_work(int64_t slots, int64_t dr, int64_t R) {
             if ((rc = hip_check(hipMalloc(&g_w.sort_tmp, bytes), "transr sort temp"))) return rc;
             g_w.sort_tmp_bytes = bytes;
         }
-        g_w.cap_slots = s; g_w.cap_dim = d; g_w.pad_ready = -1;
+        g_w.cap_slots = s; g_w.cap_dim = d;
     }
     if (R > g_w.cap_rel) {
         if ((rc = grow(g_w.bucket_start, (size_t)R + 2, "transr bucket_start"))) return rc;
@@ -363,7 +363,8 @@ struct GemmArgs {
     // group layout (sampler-shaped batches, negative_rel == 0, 2 + n <= 16): GROUPS, not (triple, side) jobs, are sorted by relation, and
     // the U = 2 + n canonical rows of a group (h, t, the new entity of each negative) sit side by side inside one 16-row sub-tile of
     // the relation's row space (gps = 16 / U groups per sub-tile, the rest of a sub-tile are pad rows: slot `pad_slot`, a zero GP row).
-    // The projection derives its rows from the sorted groups and writes sorted_slots / job_ent / row_ent for dgrad and wgrad.
+    // The projection derives its rows from the sorted groups and writes sorted_slots / job_ent / row_ent for dgrad and wgrad, and
+    // the pad slot's zero GP row and entity 0 (GP_w, job_ent_w) on every call.
     const int32_t *sorted_groups, *group_start, *bh, *bt;
     int32_t *sorted_slots_w, *job_ent_w;
     long long n_pos, stride;
@@ -820,6 +821,12 @@ __global__ __launch_bounds__(256, 2) void rows_gemm3_kernel(GemmArgs a) {
     __shared__ float red_loss[4];
     __shared__ __attribute__((aligned(16))) unsigned char Bs[2 * BIMG];
     __shared__ int s_slot[RW3], s_ent[RW3];
+    if (MODE == GEMM_PROJECT && a.sorted_groups && tile == 0) {
+        // group layout: the pad slot (a zero GP row, entity 0), written on every call -- the workspace is shared with other calls
+        // (other widths, the three-kernel path), which may have left anything there.  dgrad and wgrad read it after this kernel.
+        for (int j = threadIdx.x; j < a.Dr; j += 256) a.GP_w[(long long)a.pad_slot * a.Dr + j] = 0.f;
+        if (threadIdx.x == 0) a.job_ent_w[a.pad_slot] = 0;
+    }
     if (tile >= a.n_tiles[0]) {
         if (MODE == GEMM_PROJECT && a.fuse_vec)     // every workgroup reports a loss partial
             finish_loss_sh<4>(a.fb, red_loss, 0.f, threadIdx.x & 63, threadIdx.x >> 6, reinterpret_cast<float *>(Bs));
@@ -1559,7 +1566,26 @@ __global__ __launch_bounds__(256, 2) void wgrad3_kernel(GemmArgs a, float *__res
 
 int bits_for(int64_t v) { int b = 1; while ((int64_t(1) << b) <= v) b++; return b; }
 
+// v2 kernels (16x16x4 MFMA, 128-row tiles): dims multiples of 4 up to 208, one workgroup covers all columns
+bool transr_v2_dims(const kge_model_desc &m) {
+    const int De = m.ent_dim, Dr = m.rel_dim;
+    return De % 4 == 0 && Dr % 4 == 0 && De >= 4 && Dr >= 4 && De <= LDB2 && Dr <= LDB2 && engine().transr_v1 != 1;
+}
+
 }  // namespace
+
+// does a sampler-shaped TransR step of this shape take the group layout?  (also behind kge_transr_group_layout_active)
+bool transr_group_layout_active(const kge_model_desc &m, int64_t n_pos, int64_t n_neg) {
+    const Engine &e = engine();
+    const int64_t R = m.rel_total, U = 2 + n_neg;
+    const bool v3g = transr_v2_dims(m) && e.transr_bf16x3 && e.transr_v1 == 0 && e.transr_groups;
+    // well-filled buckets only (the same bound as wgrad's spans): at the reference's own batch (~46 rows per relation) the longer
+    // epilogue of the one tile a relation has costs more than the vector-stage launch it replaces (192 vs 177 us at B = 2 721);
+    // transr_groups = 2 takes the layout at any size (tests)
+    const bool big = n_pos * U >= 64 * R || e.transr_groups == 2;
+    return m.model == KGE_TRANSR && v3g && big && n_pos > 0 && m.negative_rel == 0 && U <= 16 && (R + 1) * kRelSub <= kRelBins &&
+           !e.counts_force_sort;
+}
 
 int launch_forward_backward_transr(const kge_model_desc &m, const float *const tables[4], const int32_t *d_h,
                                    const int32_t *d_t, const int32_t *d_r, int64_t n_pos, int64_t n_neg, int64_t stride,
@@ -1574,26 +1600,15 @@ int launch_forward_backward_transr(const kge_model_desc &m, const float *const t
     if (rc) return rc;
     int blocks = (int)((slots + 255) / 256);
     if (blocks > 4096) blocks = 4096;
-    // v2 kernels (16x16x4 MFMA, 128-row tiles): dims multiples of 4 up to 208, one workgroup covers all columns
-    const bool v2 = De % 4 == 0 && Dr % 4 == 0 && De >= 4 && Dr >= 4 && De <= LDB2 && Dr <= LDB2 && engine().transr_v1 != 1;
+    const bool v2 = transr_v2_dims(m);
     // ---- group layout (GemmArgs): device-sampled batches with the positive's matrix for every negative, 2 + n <= 16 rows per group ----
     {
         const int U = 2 + (int)n_neg;
-        const bool v3g = v2 && engine().transr_bf16x3 && engine().transr_v1 == 0 && engine().transr_groups;
-        // well-filled buckets only (the same bound as wgrad's spans): at the reference's own batch (~46 rows per relation) the longer
-        // epilogue of the one tile a relation has costs more than the vector-stage launch it replaces (192 vs 177 us at B = 2 721);
-        // transr_groups = 2 takes the layout at any size (tests)
-        const bool big = n_pos * U >= 64 * R || engine().transr_groups == 2;
-        if (v3g && big && sampler_shaped && m.negative_rel == 0 && U <= 16 && (R + 1) * kRelSub <= kRelBins && !engine().counts_force_sort) {
+        if (sampler_shaped && transr_group_layout_active(m, n_pos, n_neg)) {
             const int gps = 16 / U;
             const int64_t rows_max = 16 * ((n_pos + gps - 1) / gps + R + 1);       // sum over relations of 16 ceil(groups / gps)
             if ((rc = ensure_work(slots + 1 > rows_max ? slots + 1 : rows_max, Dr, R))) return rc;
             if (R + 2 > g_w.cap_rel_rows) { if ((rc = grow(g_w.bucket_rows, (size_t)R + 2, "transr bucket_rows"))) return rc; g_w.cap_rel_rows = R + 2; }
-            if (g_w.pad_ready != slots) {     // the pad slot: a zero GP row, entity 0 (never written by the vector stage)
-                if ((rc = hip_check(hipMemsetAsync(g_w.GP + (size_t)slots * Dr, 0, sizeof(float) * (size_t)Dr, stream), "zero pad GP row"))) return rc;
-                if ((rc = hip_check(hipMemsetAsync(g_w.job_ent + slots, 0, sizeof(int32_t), stream), "pad entity"))) return rc;
-                g_w.pad_ready = slots;
-            }
             float *drec = nullptr;
             int32_t *ddst = nullptr;
             const bool records = engine().transr_dgrad_records && slots >= engine().transr_dgrad_records_min;
@@ -1624,7 +1639,7 @@ int launch_forward_backward_transr(const kge_model_desc &m, const float *const t
             ga.De = De; ga.Dr = Dr;
             ga.rec_out = drec; ga.rec_dst = ddst; ga.row_ent = g_w.row_ent;
             ga.sorted_groups = g_w.keys2; ga.group_start = g_w.bucket_start; ga.bh = d_h; ga.bt = d_t;
-            ga.sorted_slots_w = g_w.vals2; ga.job_ent_w = g_w.job_ent; ga.n_pos = n_pos; ga.stride = stride;
+            ga.sorted_slots_w = g_w.vals2; ga.job_ent_w = g_w.job_ent; ga.GP_w = g_w.GP; ga.n_pos = n_pos; ga.stride = stride;
             ga.U = U; ga.gps = gps; ga.pad_slot = (int)slots;
             const unsigned max_tiles = (unsigned)(rows_max / RW3 + R + 1);
             // the vector stage in the projection's epilogue: widths the one-float4-per-lane layout covers, a grid the loss hand-off can count
@@ -1632,7 +1647,7 @@ int launch_forward_backward_transr(const kge_model_desc &m, const float *const t
             if (fuse) {
                 if ((rc = ensure_loss_buffers())) return rc;
                 guard_loss_stream(stream);
-                ga.fuse_vec = 1; ga.rel = tables[1]; ga.g_rel = grads[1]; ga.GP_w = g_w.GP;
+                ga.fuse_vec = 1; ga.rel = tables[1]; ga.g_rel = grads[1];
                 ga.fb.loss_partials = engine().dev.loss_partials; ga.fb.loss_out = d_loss; ga.fb.loss_ticket = engine().dev.loss_ticket;
                 ga.fb.unit = 1.0f / (float)denom; ga.fb.margin = m.margin;
             }

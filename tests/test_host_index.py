@@ -194,3 +194,42 @@ def test_pair_count_path_selection_rule():
         assert active(H, 40943, 11, 200, 43417, 25) == 0
     finally:
         L.kge_set_option(b"pair_counts", 1)
+
+
+def test_transr_group_layout_selection_rule():
+    """kge_transr_group_layout_active (include/kge_mi355.h): which sampler-shaped TransR steps take the group layout -- host
+    logic only: dims that are multiples of 4 up to 208, 2 + n <= 16, the positive's matrix for every negative, (R + 1) * 4
+    relation bins at most 4096, and (transr_groups = 1) at least 64 rows per relation; the launcher asks the same function."""
+    from openkeonspark_amd import _lib
+    L = _lib.lib()
+
+    def active(model, R, De, Dr, B, n, nr=0):
+        d = _lib.ModelDesc(model, nr, 14541, R, De, Dr, 1.0, 0)
+        return L.kge_transr_group_layout_active(ctypes.byref(d), B, n)
+
+    Rm = _lib.TRANSR
+    assert active(Rm, 237, 200, 200, 34014, 1) == 1                                          # config #4 at nbatches 8
+    assert active(Rm, 237, 200, 200, 2721, 1) == 0                                           # the reference's batch: 34 rows per relation
+    assert active(Rm, 237, 200, 200, 34014, 14) == 1 and active(Rm, 237, 200, 200, 34014, 15) == 0     # U = 16 fits a sub-tile
+    assert active(Rm, 237, 200, 200, 34014, 1, nr=1) == 0                                    # a negative's own matrix
+    assert active(Rm, 237, 202, 200, 34014, 1) == 0 and active(Rm, 237, 200, 212, 34014, 1) == 0
+    assert active(Rm, 237, 208, 4, 34014, 1) == 1
+    assert active(Rm, 237, 200, 200, 0, 1) == 0
+    assert active(_lib.TRANSE, 237, 200, 200, 34014, 1) == 0 and active(_lib.TRANSH, 237, 200, 200, 34014, 1) == 0
+    L.kge_set_option(b"transr_groups", 2)
+    try:
+        assert active(Rm, 237, 200, 200, 300, 1) == 1
+        assert active(Rm, 1023, 64, 100, 300, 1) == 1 and active(Rm, 1024, 64, 100, 300, 1) == 0   # (R + 1) * 4 <= 4096
+        for opt, val in ((b"transr_bf16x3", 0), (b"transr_v1", 1), (b"counts_force_sort", 1)):
+            L.kge_set_option(opt, val)
+            try:
+                assert active(Rm, 237, 200, 200, 34014, 1) == 0, opt
+            finally:
+                L.kge_set_option(opt, {b"transr_bf16x3": 1}.get(opt, 0))
+    finally:
+        L.kge_set_option(b"transr_groups", 1)
+    L.kge_set_option(b"transr_groups", 0)
+    try:
+        assert active(Rm, 237, 200, 200, 34014, 1) == 0
+    finally:
+        L.kge_set_option(b"transr_groups", 1)
