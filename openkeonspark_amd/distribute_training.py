@@ -7,6 +7,11 @@ patience + 5` (`:103,226-234`), loss-based early stop with `stop.txt` (`:336-360
 on restore (`main_spark.py:74-98`: xavier rows for parameters, zero rows for the Adam slots).  One
 process per GPU (torchrun) replaces the ps/worker cluster; rank 0 plays the chief.
 
+A run whose entity table is sharded by row range (`--sparse_rows 1` on N ranks, SGD or LazyAdam) checkpoints without gathering
+it: every rank writes its rows -- with LazyAdam their two moment rows too -- into `model.ckpt-<step>.shard<g>of<N>.npz` beside the
+main file.  Such a checkpoint resumes at any number of ranks or in one process, a one-process checkpoint resumes sharded, and
+new entities are grown on shards exactly as one process grows them.
+
     python -m openkeonspark_amd.distribute_training --input_path DATA/ --output_path OUT/ --model TransE ...
     torchrun --nproc-per-node 8 -m openkeonspark_amd.distribute_training ...
 
@@ -24,6 +29,7 @@ import json
 import os
 import sys
 import time
+import zipfile
 
 import numpy as np
 
@@ -65,7 +71,8 @@ def parse_args(argv=None):
     p.add_argument("--work_threads", type=int, default=8, help="virtual sampler threads (Config.py:65 hard-codes 8)")
     p.add_argument("--seed", type=int, default=0, help="parameter initialisation seed")
     p.add_argument("--sparse_rows", type=int, default=-1, help="1 / 0: force / forbid the touched-rows-only update: TransE int8 records (SGD, or the opt-in non-parity "
-                                                             "--optimizer LazyAdam; on N ranks the entity table is sharded by row range), TransH / TransD float records "
+                                                             "--optimizer LazyAdam; on N ranks the entity table is sharded by row range and each rank checkpoints its own rows "
+                                                             "and moments), TransH / TransD float records "
                                                              "added to the parameter rows in place (SGD, one process).  Default: automatic for large tables")
     return p.parse_args(argv)
 
@@ -131,18 +138,17 @@ def checkpoint_arrays(con):
     """Variables under the reference's names, Adam slots as `<var>/Adam`, `<var>/Adam_1`
     (main_spark.py:74-98), plus the optimiser scalars and the sampler's rng streams.  COLLECTIVE in data-parallel
     runs (owner-kept Adam slots are gathered): every rank calls it, rank 0 writes.  A SHARDED entity table (the
-    table-sharded sparse mode) is not gathered: every rank writes its own rows beside the main file (save_checkpoint)."""
+    table-sharded sparse mode) is not gathered: every rank writes its own rows -- and, with LazyAdam, their two moment rows --
+    beside the main file (save_checkpoint); the main file holds what is replicated."""
     con.sync_optimizer_state()
-    if _sharded(con) and con._has_slots:
-        from ._lib import KgeError
-        raise KgeError("checkpoints of a table-sharded LazyAdam run are not written yet: the moment shards would have to travel with "
-                       "the row shards (train with --optimizer SGD on N ranks, or LazyAdam in one process, where checkpoints work)")
     if _sharded(con):
         out = {n: t.detach().cpu().numpy() for n, t in con.trainModel.parameter_lists.items() if n != "ent_embeddings"}
     else:
         out = dict(con.get_parameters())
     if con._has_slots:
         for name, m, v in zip(con.trainModel.table_names, con._adam_m, con._adam_v):
+            if con._sharded(name):
+                continue      # shard-sized: in this rank's shard file as `adam` / `adam_1`
             out[name + "/Adam"] = m.detach().cpu().numpy()
             out[name + "/Adam_1"] = v.detach().cpu().numpy()
         out["beta1_power"] = np.float32(con._beta1_power)
@@ -159,10 +165,14 @@ def _step_of(path):
 
 
 def _atomic_savez(path, **arrays):
-    """np.savez under a temporary name, renamed into place: a reader (or a crash) never sees a half-written file."""
+    """np.savez under a temporary name, renamed into place: a reader (or a crash) never sees a half-written file.  A value may
+    be a callable returning the array: it is called when its member is written and dropped right after, so that a shard file
+    of several shard-sized arrays holds one of them in host memory at a time (np.savez's own layout: stored, zip64)."""
     tmp = path + ".tmp%d" % os.getpid()
-    with open(tmp, "wb") as f:
-        np.savez(f, **arrays)
+    with zipfile.ZipFile(tmp, mode="w", compression=zipfile.ZIP_STORED, allowZip64=True) as zf:
+        for key, val in arrays.items():
+            with zf.open(key + ".npy", "w", force_zip64=True) as f:
+                np.lib.format.write_array(f, np.asanyarray(val() if callable(val) else val), allow_pickle=False)
     os.replace(tmp, path)
 
 
@@ -170,16 +180,21 @@ def save_checkpoint(con, output_path, max_to_keep=10, write=True):
     """COLLECTIVE in data-parallel runs.  Order of a SHARDED checkpoint (needs an `output_path` every rank can write and, on
     restore, read -- a shared directory): every rank writes its shard file -> barrier -> rank 0 writes the main file and only
     THEN the `checkpoint` pointer, then prunes.  The pointer therefore never names a step whose shard files are incomplete, and
-    older complete checkpoints are deleted only after the new one is whole."""
+    older complete checkpoints are deleted only after the new one is whole.  A shard file holds `rows` (this rank's rows
+    [lo, hi) of the entity table), `lo`, `hi`, `ent_total` and, for LazyAdam, the moment rows `adam` / `adam_1` of the same range."""
     arrays = checkpoint_arrays(con)
     step = con.global_step
     base = os.path.join(output_path, "model.ckpt-%d" % step)
     if _sharded(con):      # this rank's rows of the entity table: model.ckpt-<step>.shard<g>of<N>.npz
         os.makedirs(output_path, exist_ok=True)
         sh = con._shard
-        rows = con.trainModel.parameter_lists["ent_embeddings"][:sh["hi"] - sh["lo"]].detach().cpu().numpy()
-        _atomic_savez(base + ".shard%dof%d.npz" % (con.rank, con.world_size), rows=rows, lo=np.int64(sh["lo"]), hi=np.int64(sh["hi"]),
-                      ent_total=np.int64(con.entTotal))
+        n = sh["hi"] - sh["lo"]
+        host = lambda t: (lambda: t[:n].detach().cpu().numpy())
+        parts = dict(rows=host(con.trainModel.parameter_lists["ent_embeddings"]), lo=np.int64(sh["lo"]), hi=np.int64(sh["hi"]),
+                     ent_total=np.int64(con.entTotal))
+        if con._has_slots:     # LazyAdam: the moment rows travel with their entity rows
+            parts.update(adam=host(con._adam_m[0]), adam_1=host(con._adam_v[0]))
+        _atomic_savez(base + ".shard%dof%d.npz" % (con.rank, con.world_size), **parts)
         import torch.distributed as dist
         con.comm_fence("pg")
         dist.barrier(group=getattr(con, "_pg", None))      # all shard files of this step exist before anything points at them
@@ -199,21 +214,46 @@ def save_checkpoint(con, output_path, max_to_keep=10, write=True):
     return base + ".npz"
 
 
-def read_entity_rows(base, lo, hi, dim):
-    """Rows [lo, hi) of the entity table of a sharded checkpoint, from whichever shard files hold them (the number of ranks
-    may differ from the run that wrote them)."""
+def shard_files(base, keys=("rows",)):
+    """The shard files of the sharded checkpoint `base` (model.ckpt-<step>) as [(path, lo, hi)] sorted by `lo`, and the entity
+    count they were written for.  Checked before anything is read -- every rank sees the same files and so fails the same way,
+    none is left waiting in a collective: the files must tile [0, ent_total) and each must hold the arrays `keys`."""
+    parts, totals = [], set()
+    for path in glob.glob(base + ".shard*of*.npz"):
+        with np.load(path) as z:
+            missing = [k for k in keys if k not in z.files]
+            if missing:
+                raise ValueError("sharded checkpoint %s: shard file %s has no %s" % (base, os.path.basename(path), ", ".join(missing)))
+            parts.append((path, int(z["lo"]), int(z["hi"])))
+            totals.add(int(z["ent_total"]))
+    if len(totals) != 1:
+        raise ValueError("sharded checkpoint %s: %s" % (base, "no shard files" if not totals else
+                                                        "shard files of different entity counts %s" % sorted(totals)))
+    ent_total = totals.pop()
+    parts.sort(key=lambda p: p[1])
+    end = 0
+    for _, lo, hi in parts:
+        if lo > end:
+            break
+        end = max(end, hi)
+    if end < ent_total:
+        raise ValueError("sharded checkpoint %s: entity rows [%d, %d) are not in any of its shard files" % (base, end, ent_total))
+    return parts, ent_total
+
+
+def read_entity_rows(base, lo, hi, dim, key="rows", parts=None):
+    """Rows [lo, hi) of the array `key` of a sharded checkpoint -- `rows`: the entity table, `adam` / `adam_1`: its LazyAdam
+    moments -- from whichever shard files hold them (the number of ranks may differ from the run that wrote them).  Returns
+    (array of hi - lo rows, ent_total): rows at or beyond the checkpoint's entity count `ent_total` are NEW entities, left zero
+    for the caller to fill; a row below it that no shard file holds is an error (shard_files; `parts`: its result)."""
+    parts, ent_total = parts if parts is not None else shard_files(base, (key,))
     out = np.zeros((hi - lo, dim), np.float32)
-    got = 0
-    for part in sorted(glob.glob(base + ".shard*of*.npz")):
-        z = np.load(part)
-        plo, phi = int(z["lo"]), int(z["hi"])
-        a, b = max(lo, plo), min(hi, phi)
+    for path, plo, phi in parts:
+        a, b = max(lo, plo), min(hi, phi, ent_total)
         if a < b:
-            out[a - lo:b - lo] = z["rows"][a - plo:b - plo]
-            got += b - a
-    if got != hi - lo:
-        raise ValueError("sharded checkpoint %s: entity rows [%d, %d) are not all present in its shard files" % (base, lo, hi))
-    return out
+            with np.load(path) as z:
+                out[a - lo:b - lo] = z[key][a - plo:b - plo]
+    return out, ent_total
 
 
 def grow_table(table, rows, rng, zeros=False):
@@ -230,13 +270,51 @@ def grow_table(table, rows, rng, zeros=False):
     return np.concatenate([table, new], axis=0)
 
 
+def _set_slots(con, i, name, m, v):
+    """Adam moments of table i from whole-table arrays; a sharded entity table keeps its rows [lo, hi)."""
+    import torch
+    for slots, full in ((con._adam_m, m), (con._adam_v, v)):
+        if con._sharded(name):
+            lo, hi = con._shard["lo"], con._shard["hi"]
+            slots[i][:hi - lo].copy_(torch.from_numpy(np.ascontiguousarray(full[lo:hi])))
+        else:
+            slots[i].copy_(torch.from_numpy(full))
+
+
+def _restore_sharded_rows(con, i, name, base, z, rows, dim, allow_growth, rng):
+    """Table i (the entity table) from the shard files of a sharded checkpoint, into this rank's shard [lo, hi) of the new run or,
+    in one process, whole.  Rows of entities the checkpoint does not know are grown as one process grows them (grow_table):
+    every rank draws the same xavier block for rows [ent_total, rows) from `rng` and keeps its own part; their moments are zero.
+    An Adam-family checkpoint (it has `beta1_power`) resumed with slots must carry the moment rows in its shard files; an SGD
+    checkpoint resumed with slots starts from zero moments."""
+    import torch
+    moments = con._has_slots and "beta1_power" in z
+    parts = shard_files(base, ("rows", "adam", "adam_1") if moments else ("rows",))
+    ent_total = parts[1]
+    if rows != ent_total and (not allow_growth or rows < ent_total):
+        raise ValueError("checkpoint table %s has %d rows, model needs %d" % (name, ent_total, rows))
+    new = xavier_normal(rng, (rows - ent_total, dim), fan_in=rows) if rows > ent_total else None
+    lo, hi = (con._shard["lo"], con._shard["hi"]) if con._sharded(name) else (0, rows)
+    if hi <= lo:
+        return
+    for key, dst in (("rows", con._tables[i]),) + ((("adam", con._adam_m[i]), ("adam_1", con._adam_v[i])) if moments else ()):
+        part, _ = read_entity_rows(base, lo, hi, dim, key, parts)
+        if key == "rows" and new is not None and hi > ent_total:
+            a = max(lo, ent_total)
+            part[a - lo:] = new[a - ent_total:hi - ent_total]
+        dst[:hi - lo].copy_(torch.from_numpy(part))
+        del part
+    con.tables_changed()
+
+
 def restore_checkpoint(con, path, allow_growth=True, arrays=None):
     """Load a checkpoint into an initialised Config (after set_model_and_session).  If the dataset
     gained entities since the checkpoint was written, entity tables are grown as the reference's
     `update_entities_and_model` does.  `arrays`: the checkpoint's contents when they were read elsewhere
     (rank 0 reads the file and broadcasts it: for replicated tables the other ranks need not see the output directory; a
-    SHARDED entity table is read by every rank from the shard files, so that mode needs a shared `output_path`)."""
-    import torch
+    SHARDED entity table is read by every rank from the shard files, so that mode needs a shared `output_path`).  Sharded and
+    whole checkpoints restore into sharded and one-process runs alike, at any number of ranks: a rank takes its rows [lo, hi)
+    of the entity table (and of its LazyAdam moments) from whichever file holds them."""
     z = arrays if arrays is not None else {k.replace("__", "/"): v for k, v in np.load(path).items()}
     rng = np.random.default_rng(getattr(con, "seed", 0) + 1)
     shapes = con.trainModel.table_shapes()
@@ -244,14 +322,7 @@ def restore_checkpoint(con, path, allow_growth=True, arrays=None):
         rows = shapes[name][0]
         if name not in z:      # a sharded checkpoint: the entity rows live in per-rank shard files beside the main file
             base = path[:-4] if path.endswith(".npz") else path
-            if _sharded(con):
-                sh = con._shard
-                if sh["hi"] > sh["lo"]:
-                    part = read_entity_rows(base, sh["lo"], sh["hi"], shapes[name][1])
-                    con.trainModel.parameter_lists[name][:sh["hi"] - sh["lo"]].copy_(torch.from_numpy(part))
-                    con.tables_changed()
-            else:
-                con.set_parameters_by_name(name, read_entity_rows(base, 0, rows, shapes[name][1]))
+            _restore_sharded_rows(con, i, name, base, z, rows, shapes[name][1], allow_growth, rng)
             continue
         tab = z[name]
         if tab.shape[0] != rows:
@@ -260,13 +331,14 @@ def restore_checkpoint(con, path, allow_growth=True, arrays=None):
             tab = grow_table(tab, rows, rng)
         con.set_parameters_by_name(name, tab)
         if con._has_slots and name + "/Adam" in z:
-            con._adam_m[i].copy_(torch.from_numpy(grow_table(z[name + "/Adam"], rows, rng, zeros=True)))
-            con._adam_v[i].copy_(torch.from_numpy(grow_table(z[name + "/Adam_1"], rows, rng, zeros=True)))
+            _set_slots(con, i, name, grow_table(z[name + "/Adam"], rows, rng, zeros=True),
+                       grow_table(z[name + "/Adam_1"], rows, rng, zeros=True))
     if con._has_slots and "beta1_power" in z:
         con._beta1_power = np.float32(z["beta1_power"])
         con._beta2_power = np.float32(z["beta2_power"])
     con.global_step = int(z.get("global_step", 0))
     if "rng_streams" in z and len(z["rng_streams"]) == con.workThreads:
+        import torch
         s = np.ascontiguousarray(z["rng_streams"], dtype=np.uint64)
         if torch.cuda.is_available():
             torch.cuda.synchronize()   # a sampler prefetched on the side stream may still be writing the other half of the state buffer
