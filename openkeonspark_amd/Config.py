@@ -16,7 +16,7 @@ import os
 
 import numpy as np
 
-from . import _lib
+from . import _lib, shard_eval
 from ._lib import KgeError
 
 
@@ -1301,93 +1301,13 @@ class Config(object):
         host = np.stack([np.asarray(test_h), np.asarray(test_t), np.asarray(test_r)]).astype(np.int32)
         self._check_ids(host)
         if self._sharded("ent_embeddings"):
-            return self._test_step_sharded(host)
+            return shard_eval.test_step(self, host)
         dev = torch.from_numpy(host).to(self.device)
         out = torch.empty(host.shape[1], dtype=torch.float32, device=self.device)
         _lib.check(self.lib.kge_predict(ctypes.byref(self._desc), self._tab_ptrs, dev[0].data_ptr(), dev[1].data_ptr(),
                                         dev[2].data_ptr(), host.shape[1], out.data_ptr(), self._stream()), self.lib)
         self.trainModel.predict = out
         return out.cpu().numpy()
-
-    def _test_step_sharded(self, host):
-        import torch
-        n = host.shape[1]
-        ids = torch.from_numpy(np.ascontiguousarray(host[:2].reshape(-1))).to(self.device)    # the n heads, then the n tails
-        rows, slot_of = self._fetch_rows(ids, 2 * n)
-        out = torch.empty(n, dtype=torch.float32, device=self.device)
-        if n:
-            slots = slot_of.view(2, n)
-            rel = torch.from_numpy(np.ascontiguousarray(host[2])).to(self.device)
-            desc = self._desc_with(ent_total=rows.shape[0])       # entity ids are slots of the fetched rows
-            ptrs = _lib.table_ptrs([rows.data_ptr()] + [t.data_ptr() for t in self._tables[1:]])
-            _lib.check(self.lib.kge_predict(ctypes.byref(desc), ptrs, slots[0].data_ptr(), slots[1].data_ptr(), rel.data_ptr(), n,
-                                            out.data_ptr(), self._stream()), self.lib)
-        self.trainModel.predict = out
-        return out.cpu().numpy()
-
-    def _fetch_rows(self, ids, n):
-        """Collective on a sharded entity table: the rows of the n global entity ids in `ids` (int32 device tensor), fetched from
-        their owners by the sharded step's exchange (ids out, rows back).  -> (rows float32 [max(n, 1), D], slot_of int32 [n]:
-        the row holding entity ids[i])."""
-        import torch
-        from . import parallel as par
-        L, st, W, D, pg = self.lib, self._stream(), self.world_size, self.hidden_size, self._pg
-        sh, dev, i32 = self._shard, self.device, torch.int32
-        self.comm_fence("pg")
-        counts = torch.zeros(W, dtype=i32, device=dev)
-        cursor = torch.zeros(W, dtype=i32, device=dev)
-        send_ids = torch.empty(max(n, 1), dtype=i32, device=dev)
-        slot_of = torch.empty(max(n, 1), dtype=i32, device=dev)
-        _lib.check(L.kge_shard_count(ids.data_ptr(), n, sh["chunk"], W, counts.data_ptr(), st), L)
-        send, recv, gmax = par.exchange_counts_max(counts, pg)
-        _lib.check(L.kge_shard_scatter(ids.data_ptr(), n, sh["chunk"], W, (ctypes.c_int64 * W)(*send), cursor.data_ptr(),
-                                       send_ids.data_ptr(), slot_of.data_ptr(), st), L)
-        n_recv = sum(recv)
-        recv_ids = torch.empty(max(n_recv, 1), dtype=i32, device=dev)
-        rows_out = torch.empty((max(n_recv, 1), D), dtype=torch.float32, device=dev)
-        rows = torch.zeros((max(n, 1), D), dtype=torch.float32, device=dev)
-        par.all_to_all_rows(recv_ids, send_ids, recv, send, pg, max_rows=gmax)
-        _lib.check(L.kge_shard_gather_rows(self._tables[0].data_ptr(), recv_ids.data_ptr(), n_recv, sh["lo"], sh["chunk"], D,
-                                           rows_out.data_ptr(), st), L)
-        par.all_to_all_rows(rows, rows_out, send, recv, pg, max_rows=gmax)
-        return rows, slot_of[:n]
-
-    def _all_reduce_on_pg(self, t, op):
-        """In-place all-reduce of a device tensor on the process group (staged through the host for gloo)."""
-        import torch.distributed as dist
-        self.comm_fence("pg")
-        if dist.get_backend(self._pg) == "nccl":
-            dist.all_reduce(t, op=op, group=self._pg)
-        else:
-            h = t.cpu()
-            dist.all_reduce(h, op=op, group=self._pg)
-            t.copy_(h)
-
-    def _link_prediction_sharded(self, first, count, test_head):
-        """link_prediction on a sharded entity table (collective): every rank ranks the test triples against its own rows
-        [lo, hi), the counts are summed and the arg-min keys minimised across ranks, then resolved as kge_link_prediction does."""
-        import torch
-        import torch.distributed as dist
-        L, st, D = self.lib, self._stream(), self.hidden_size
-        lo, hi = self._shard["lo"], self._shard["hi"]
-        th = 1 if test_head else 0
-        out = np.zeros((count, 2, 8), dtype=np.int64)
-        per = max(1, int(self.lp_shard_query_bytes) // (2 * D * 4))
-        for c0 in range(first, first + count, per):
-            n = min(per, first + count - c0)
-            ids = torch.empty(2 * n, dtype=torch.int32, device=self.device)
-            _lib.check(L.kge_test_entity_ids(c0, n, ids.data_ptr(), st), L)
-            rows, slot_of = self._fetch_rows(ids, 2 * n)
-            query = rows.index_select(0, slot_of.long())      # [2n, D]: the h and t rows of each triple
-            del rows
-            counts = torch.empty((n, 2, 4), dtype=torch.int64, device=self.device)
-            keys = torch.empty_like(counts)
-            _lib.check(L.kge_link_prediction_range(ctypes.byref(self._desc), self._tab_ptrs, lo, hi - lo, query.data_ptr(), c0, n, th,
-                                                   counts.data_ptr(), keys.data_ptr(), st), L)
-            self._all_reduce_on_pg(counts, dist.ReduceOp.SUM)
-            self._all_reduce_on_pg(keys, dist.ReduceOp.MIN)
-            _lib.check(L.kge_link_prediction_finish(c0, n, th, counts.data_ptr(), keys.data_ptr(), out[c0 - first:].ctypes.data, st), L)
-        return out
 
     # ------------------------------------------------------------------------------------------
     # triple classification and the predict_* helpers (Config.py:83-151, 491-516, 574-663)
@@ -1526,7 +1446,7 @@ class Config(object):
     def _top_k_entities(self, fixed, rel, k, head, filtered, type_constrained):
         import torch
         if self._sharded("ent_embeddings"):
-            return self._top_k_entities_sharded(fixed, rel, k, head, filtered, type_constrained)
+            return shard_eval.top_k_entities(self, fixed, rel, k, head, filtered, type_constrained)
         f, r, n, on_device = self._topk_queries(fixed, rel, k, self.entTotal, self.relTotal)
         side = torch.full((n,), 1 if head else 0, dtype=torch.int32, device=self.device)
         return self._topk_call(self.lib.kge_topk_entities, (f.data_ptr(), r.data_ptr(), side.data_ptr()), n, k, filtered,
@@ -1559,90 +1479,21 @@ class Config(object):
             b = torch.from_numpy(np.ascontiguousarray(bh, dtype=np.int32)).to(self.device)
         return a, b, n, on_device
 
-    def _top_k_entities_sharded(self, fixed, rel, k, head, filtered, type_constrained):
-        """top_k_tails / top_k_heads on a sharded entity table (collective).  The ranks first agree on a header (query count,
-        k, side, flags, validity), so a bad call raises on every rank and leaves none waiting in a collective.  Then all ranks'
-        queries are taken in chunks: their fixed rows are fetched from the owners, each query's k best among this rank's rows
-        [lo, hi) are selected as packed keys (kge_topk_entities_range), each requester is sent the key lists of its own queries
-        only, and the W lists received for each of this rank's queries are merged (kge_topk_merge_keys)."""
-        import torch
-        from . import parallel as par
-        L, st, W, D, dev, pg = self.lib, self._stream(), self.world_size, self.hidden_size, self.device, self._pg
-        lo, hi = self._shard["lo"], self._shard["hi"]
-        flags = (_lib.TOPK_FILTERED if filtered else 0) | (_lib.TOPK_TYPED if type_constrained else 0)
-        err, f, r, n, on_device = None, None, None, 0, False
-        try:
-            f, r, n, on_device = self._topk_queries(fixed, rel, k, self.entTotal, self.relTotal)
-            k = int(k)
-            # the arguments, and the evaluation files the flags need, checked without a launch (no queries)
-            _lib.check(L.kge_topk_entities_range(ctypes.byref(self._desc), self._tab_ptrs, lo, hi - lo, None, None, None, None, 0, k,
-                                                 flags, None, st), L)
-        except (KgeError, ValueError, TypeError, RuntimeError) as e:
-            err, n = e, 0
-        kk = k if err is None else -1
-        per = max(1, int(self.topk_shard_query_bytes) // (4 * D + 8 * max(kk, 1)))
-        hdr = torch.tensor([0 if err else 1, n, kk, 1 if head else 0, flags, per], dtype=torch.int64, device=dev)
-        self.comm_fence("pg")
-        allh = torch.empty((W, hdr.numel()), dtype=torch.int64, device=dev)
-        par.all_gather_chunks(allh.view(-1), hdr, pg)
-        allh = allh.cpu().numpy()
-        if err is not None:
-            raise KgeError("top-k prediction on a sharded entity table: %s" % err) from err
-        if not allh[:, 0].all():
-            raise KgeError("top-k prediction on a sharded entity table: rank(s) %s passed invalid arguments"
-                           % np.nonzero(allh[:, 0] == 0)[0].tolist())
-        if (allh[:, 2:5] != allh[0, 2:5]).any():
-            raise KgeError("top-k prediction on a sharded entity table: the ranks passed different k, side or flags")
-        ns = allh[:, 1]
-        off = np.concatenate([[0], np.cumsum(ns)]).tolist()
-        N, me = off[-1], self.rank
-        per = int(allh[:, 5].min())
-        ids = torch.empty((n, k), dtype=torch.int32, device=dev)
-        scores = torch.empty((n, k), dtype=torch.float32, device=dev)
-        if N:
-            # every rank's queries (fixed, relation), rank-major: padded to the largest count for one all-gather
-            nmax = int(ns.max())
-            q = torch.zeros((nmax, 2), dtype=torch.int32, device=dev)
-            if n:
-                q[:n, 0] = f
-                q[:n, 1] = r
-            allq = torch.empty((W, nmax, 2), dtype=torch.int32, device=dev)
-            par.all_gather_chunks(allq.view(-1), q.view(-1), pg)
-            allq = torch.cat([allq[g, :int(ns[g])] for g in range(W)])
-            gf, gr = allq[:, 0].contiguous(), allq[:, 1].contiguous()
-            side = torch.full((N,), 1 if head else 0, dtype=torch.int32, device=dev)
-            for c0 in range(0, N, per):
-                c1 = min(N, c0 + per)
-                m = c1 - c0
-                rows, slot_of = self._fetch_rows(gf[c0:c1], m)
-                query = rows.index_select(0, slot_of.long())          # [m, D]: the fixed rows of the chunk's queries
-                del rows
-                keys = torch.empty((m, k), dtype=torch.int64, device=dev)
-                _lib.check(L.kge_topk_entities_range(ctypes.byref(self._desc), self._tab_ptrs, lo, hi - lo, query.data_ptr(),
-                                                     gf[c0:].data_ptr(), gr[c0:].data_ptr(), side[c0:].data_ptr(), m, k, flags,
-                                                     keys.data_ptr(), st), L)
-                del query
-                # rank g's queries are [off[g], off[g+1]): their key lists in this chunk go back to g alone
-                send = [max(0, min(c1, off[g + 1]) - max(c0, off[g])) for g in range(W)]
-                mine = send[me]
-                got = torch.empty((max(W * mine, 1), k), dtype=torch.int64, device=dev)
-                self.comm_fence("pg")
-                par.all_to_all_rows(got, keys, [mine] * W, send, pg, max_rows=max(send))
-                if mine:      # [W][mine][k]: one key list per source rank
-                    o0 = max(c0, off[me]) - off[me]
-                    _lib.check(L.kge_topk_merge_keys(got.data_ptr(), mine, W, k, ids[o0].data_ptr(), scores[o0].data_ptr(), st), L)
-        if on_device:
-            return ids.long(), scores
-        return ids.cpu().numpy().astype(np.int64), scores.cpu().numpy()
-
     def _topk_call(self, fn, query_ptrs, n, k, filtered, type_constrained, on_device):
         import torch
         k = int(k)
         ids = torch.empty((n, k), dtype=torch.int32, device=self.device)
         scores = torch.empty((n, k), dtype=torch.float32, device=self.device)
-        flags = (_lib.TOPK_FILTERED if filtered else 0) | (_lib.TOPK_TYPED if type_constrained else 0)
-        _lib.check(fn(ctypes.byref(self._desc), self._tab_ptrs, *query_ptrs, n, k, flags, ids.data_ptr(), scores.data_ptr(),
-                      self._stream()), self.lib)
+        _lib.check(fn(ctypes.byref(self._desc), self._tab_ptrs, *query_ptrs, n, k, self._topk_flags(filtered, type_constrained),
+                      ids.data_ptr(), scores.data_ptr(), self._stream()), self.lib)
+        return self._topk_result(ids, scores, on_device)
+
+    @staticmethod
+    def _topk_flags(filtered, type_constrained):
+        return (_lib.TOPK_FILTERED if filtered else 0) | (_lib.TOPK_TYPED if type_constrained else 0)
+
+    @staticmethod
+    def _topk_result(ids, scores, on_device):
         if on_device:
             return ids.long(), scores
         return ids.cpu().numpy().astype(np.int64), scores.cpu().numpy()
@@ -1681,14 +1532,18 @@ class Config(object):
         total = self.lib.getTestTotal()
         if self._sharded("ent_embeddings"):
             return self.link_prediction(0, total, test_head)[1]
-        per = (total + self.world_size - 1) // self.world_size
-        lo = min(self.rank * per, total)
-        hi = min(lo + per, total)
+        lo, hi = self._test_slice(total)
         out = np.zeros((hi - lo, 2, 8), dtype=np.int64)
         if hi > lo:
             _lib.check(self.lib.kge_link_prediction(ctypes.byref(self._desc), self._tab_ptrs, lo, hi - lo,
                                                     1 if test_head else 0, out.ctypes.data, self._stream()), self.lib)
         return self._lp_normalise(self._all_reduce_sums(self._lp_sums(out, test_head)), total)
+
+    def _test_slice(self, total):
+        """This rank's contiguous range [lo, hi) of `total` test triples (the static split of distribute_training.py:430-441)."""
+        per = (total + self.world_size - 1) // self.world_size
+        lo = min(self.rank * per, total)
+        return lo, min(lo + per, total)
 
     def _all_reduce_sums(self, sums):
         """The accumulators of every rank added up (main_spark.py:430-448's reduction)."""
@@ -1697,10 +1552,9 @@ class Config(object):
         keys = sorted(sums)
         vec = torch.tensor([sums[k] for k in keys], dtype=torch.float64)
         if self.world_size > 1:
-            self.comm_fence("pg")
             if dist.get_backend(self._pg) == "nccl":
                 vec = vec.to(self.device)
-            dist.all_reduce(vec, op=dist.ReduceOp.SUM, group=self._pg)
+            shard_eval.all_reduce(self, vec, dist.ReduceOp.SUM)
         return dict(zip(keys, vec.cpu().tolist()))
 
     def link_prediction(self, first=0, count=None, test_head=True):
@@ -1715,13 +1569,12 @@ class Config(object):
         if count is None:
             count = self.lib.getTestTotal() - first
         if self._sharded("ent_embeddings"):
-            out = self._link_prediction_sharded(first, count, test_head)
-            return out, self._lp_normalise(self._lp_sums(out, test_head), count)
-        out = np.zeros((count, 2, 8), dtype=np.int64)
-        _lib.check(self.lib.kge_link_prediction(ctypes.byref(self._desc), self._tab_ptrs, first, count,
-                                                1 if test_head else 0, out.ctypes.data, self._stream()), self.lib)
-        d = self._lp_normalise(self._lp_sums(out, test_head), count)
-        return out, d
+            out = shard_eval.link_prediction(self, first, count, test_head)
+        else:
+            out = np.zeros((count, 2, 8), dtype=np.int64)
+            _lib.check(self.lib.kge_link_prediction(ctypes.byref(self._desc), self._tab_ptrs, first, count,
+                                                    1 if test_head else 0, out.ctypes.data, self._stream()), self.lib)
+        return out, self._lp_normalise(self._lp_sums(out, test_head), count)
 
     @staticmethod
     def _rel_sums(out):
@@ -1750,7 +1603,7 @@ class Config(object):
         if count is None:
             count = self.lib.getTestTotal() - first
         if self._sharded("ent_embeddings"):
-            out = self._relation_prediction_sharded(first, count)
+            out = shard_eval.relation_prediction(self, first, count)
         else:
             out = np.zeros((count, 4), dtype=np.int64)
             self._relation_counts(first, count, out)
@@ -1763,9 +1616,7 @@ class Config(object):
         total = self.lib.getTestTotal()
         if self._sharded("ent_embeddings"):
             return self.relation_prediction(0, total)[1]
-        per = (total + self.world_size - 1) // self.world_size
-        lo = min(self.rank * per, total)
-        hi = min(lo + per, total)
+        lo, hi = self._test_slice(total)
         out = np.zeros((hi - lo, 4), dtype=np.int64)
         if hi > lo:
             self._relation_counts(lo, hi - lo, out)
@@ -1774,60 +1625,6 @@ class Config(object):
     def _relation_counts(self, first, count, out):
         _lib.check(self.lib.kge_relation_prediction(ctypes.byref(self._desc), self._tab_ptrs, first, count, out.ctypes.data,
                                                     self._stream()), self.lib)
-
-    def _relation_prediction_sharded(self, first, count):
-        """relation_prediction on a sharded entity table (collective).  The ranks first agree on a header (validity, first,
-        count, triples per round), so a bad call raises on every rank and leaves none waiting in a collective.  Then rank g
-        takes the g-th contiguous slice of [first, first+count) in rounds of at most `per` triples: the h / t rows come from
-        their owners (_fetch_rows, which every rank joins in every round, with no ids once its slice is done) and
-        kge_relation_prediction_rows writes the slice's rows of a zeroed [count, 4]; one SUM all-reduce merges them."""
-        import torch
-        import torch.distributed as dist
-        from . import parallel as par
-        L, st, W, D, dev, pg = self.lib, self._stream(), self.world_size, self.hidden_size, self.device, self._pg
-        if not dist.is_initialized():      # no process group, so no other rank can be waiting for this one
-            raise KgeError("relation prediction on a sharded entity table needs the process group it was sharded over")
-        err = None
-        try:
-            first, count = int(first), int(count)
-            if first < 0 or count < 0:
-                raise KgeError("relation prediction: bad range (first %d, count %d)" % (first, count))
-            # the arguments and the evaluation files, checked without a launch: the range's end, then no triples
-            _lib.check(L.kge_relation_prediction_rows(ctypes.byref(self._desc), self._tab_ptrs, None, first + count, 0, None, st), L)
-        except (KgeError, ValueError, TypeError, OverflowError) as e:
-            err, first, count = e, -1, -1
-        per = max(1, int(self.lp_shard_query_bytes) // (2 * D * 4))
-        hdr = torch.tensor([0 if err else 1, first, count, per], dtype=torch.int64, device=dev)
-        self.comm_fence("pg")
-        allh = torch.empty((W, hdr.numel()), dtype=torch.int64, device=dev)
-        par.all_gather_chunks(allh.view(-1), hdr, pg)
-        allh = allh.cpu().numpy()
-        if err is not None:
-            raise KgeError("relation prediction on a sharded entity table: %s" % err) from err
-        if not allh[:, 0].all():
-            raise KgeError("relation prediction on a sharded entity table: rank(s) %s passed invalid arguments"
-                           % np.nonzero(allh[:, 0] == 0)[0].tolist())
-        if (allh[:, 1:3] != allh[0, 1:3]).any():
-            raise KgeError("relation prediction on a sharded entity table: the ranks passed different first or count")
-        per = int(allh[:, 3].min())
-        cs = par.chunk_size(count, W)
-        lo = first + min(self.rank * cs, count)
-        hi = first + min((self.rank + 1) * cs, count)
-        counts = torch.zeros((max(count, 1), 4), dtype=torch.int64, device=dev)
-        for r0 in range(0, cs, per):
-            c0 = min(lo + r0, hi)
-            n = min(per, hi - c0)
-            ids = torch.empty(max(2 * n, 1), dtype=torch.int32, device=dev)
-            _lib.check(L.kge_test_entity_ids(c0, n, ids.data_ptr(), st), L)
-            rows, slot_of = self._fetch_rows(ids, 2 * n)
-            if n:
-                query = rows.index_select(0, slot_of.long())      # [2n, D]: the h and t rows of each triple
-                _lib.check(L.kge_relation_prediction_rows(ctypes.byref(self._desc), self._tab_ptrs, query.data_ptr(), c0, n,
-                                                          counts[c0 - first].data_ptr(), st), L)
-                del query
-            del rows
-        self._all_reduce_on_pg(counts, dist.ReduceOp.SUM)
-        return counts[:count].cpu().numpy()
 
     # ------------------------------------------------------------------------------------------
     # parameters by the reference's variable names (Config.py:378-421)

@@ -130,10 +130,6 @@ def get_last_step(output_path):
     return last_global_step
 
 
-def _sharded(con):
-    return con._dp and getattr(con, "sparse_rows", False) and hasattr(con, "_shard")
-
-
 def checkpoint_arrays(con):
     """Variables under the reference's names, Adam slots as `<var>/Adam`, `<var>/Adam_1`
     (main_spark.py:74-98), plus the optimiser scalars and the sampler's rng streams.  COLLECTIVE in data-parallel
@@ -141,7 +137,7 @@ def checkpoint_arrays(con):
     table-sharded sparse mode) is not gathered: every rank writes its own rows -- and, with LazyAdam, their two moment rows --
     beside the main file (save_checkpoint); the main file holds what is replicated."""
     con.sync_optimizer_state()
-    if _sharded(con):
+    if con._sharded("ent_embeddings"):
         out = {n: t.detach().cpu().numpy() for n, t in con.trainModel.parameter_lists.items() if n != "ent_embeddings"}
     else:
         out = dict(con.get_parameters())
@@ -185,7 +181,7 @@ def save_checkpoint(con, output_path, max_to_keep=10, write=True):
     arrays = checkpoint_arrays(con)
     step = con.global_step
     base = os.path.join(output_path, "model.ckpt-%d" % step)
-    if _sharded(con):      # this rank's rows of the entity table: model.ckpt-<step>.shard<g>of<N>.npz
+    if con._sharded("ent_embeddings"):      # this rank's rows of the entity table: model.ckpt-<step>.shard<g>of<N>.npz
         os.makedirs(output_path, exist_ok=True)
         sh = con._shard
         n = sh["hi"] - sh["lo"]

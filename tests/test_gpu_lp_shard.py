@@ -12,10 +12,10 @@ import sys
 import numpy as np
 import pytest
 
-from conftest import GOLDEN, ROOT
+from conftest import ROOT
+from shard_rig import KG, finish_rank, load_ranks, make_config, run_worlds, start_rank, union_config
 
 pytestmark = pytest.mark.gpu
-KG = os.path.join(GOLDEN, "kg_small")
 NO_KEY = np.iinfo(np.int64).max
 
 
@@ -25,22 +25,6 @@ def require_entry_points():
     for name in ("kge_link_prediction_range", "kge_link_prediction_finish", "kge_test_entity_ids"):
         assert hasattr(L, name), name + " is not exported"
     return L
-
-
-def make_config(dim, path=KG, scale=3.0):
-    import openkeonspark_amd as pkg
-    con = pkg.Config()
-    con.set_in_path(path)
-    con.set_work_threads(1)
-    con.set_dimension(dim)
-    con.set_test_link_prediction(True)
-    con.init()
-    con.set_model_and_session(pkg.TransE)
-    if scale != 1.0:
-        for t in con._tables:      # spread the scores: xavier-initialised tables rank almost at random
-            t.mul_(scale)
-        con.tables_changed()
-    return con
 
 
 def lp_ranges(con, parts, first=0, count=None, test_head=True):
@@ -256,29 +240,8 @@ def test_filtered_typed_and_ontology_columns(graph, typed_graph):
 # 5-7: ranks (gloo, one GPU)
 # ---------------------------------------------------------------------------------------------------------------------------
 def _rank_worker(rank, world, port, out_dir, data):
-    sys.path.insert(0, ROOT)
-    import torch
-    import torch.distributed as dist
-    os.environ["MASTER_ADDR"] = "127.0.0.1"
-    os.environ["MASTER_PORT"] = str(port)
-    dist.init_process_group("gloo", rank=rank, world_size=world)
     import openkeonspark_amd as pkg
-    pkg._lib.lib().kge_set_option(b"inv_table_max_bytes", 0)
-    con = pkg.Config()
-    con.set_in_path(data)
-    con.set_work_threads(8); con.set_bern(1); con.set_dimension(48); con.set_nbatches(10)
-    con.set_ent_neg_rate(3); con.set_alpha(0.02); con.set_opt_method("SGD")
-    con.sparse_rows = True
-    con.prefetch_sampling = False
-    con.counts_min_records = 0
-    con.set_test_link_prediction(True)
-    con.init()
-    con.set_model_and_session(pkg.TransE)
-    con.init_distributed()
-    assert con._sharded("ent_embeddings") and con._tables[0].shape[0] == con._shard["chunk"]
-    for _ in range(4):
-        con.train_step()
-    torch.cuda.synchronize()
+    con = start_rank(rank, world, port, data)
     total = con.lib.getTestTotal()
     res = {}
     res["dist"] = con.link_prediction_distributed()
@@ -306,39 +269,21 @@ def _rank_worker(rank, world, port, out_dir, data):
             fn(0, 0, 5)
         except pkg.KgeError as e:
             refused += "link_prediction" in str(e)
-    params = con.get_parameters()      # (collective: the shards gathered; small tables only)
-    np.savez(os.path.join(out_dir, "w%d_r%d.npz" % (world, rank)), out_all=out_all, out_part=out_part, out_tail=out_tail,
-             out_chunked=out_chunked, h=h, t=t, r=r, scores=scores, refused=refused, metrics=json.dumps(res),
-             ent=params["ent_embeddings"], rel=params["rel_embeddings"])
-    dist.barrier()
-    dist.destroy_process_group()
+    finish_rank(con, out_dir, world, rank, out_all=out_all, out_part=out_part, out_tail=out_tail, out_chunked=out_chunked,
+                h=h, t=t, r=r, scores=scores, refused=refused, metrics=json.dumps(res))
 
 
 @pytest.fixture(scope="module")
 def sharded_runs(tmp_path_factory):
     require_entry_points()
-    import torch.multiprocessing as mp
-    from openkeonspark_amd import synthetic
-    base = tmp_path_factory.mktemp("lp_shard_ranks")
-    data = synthetic.make_typed_dataset(str(base / "kg1003"), synthetic.SMALL_TYPED, entities=1003, train=6000, valid=100, test=60)
-    port = 31900 + os.getpid() % 1000
-    for i, w in enumerate((2, 4)):
-        mp.start_processes(_rank_worker, args=(w, port + i, str(base), data), nprocs=w, join=True, start_method="spawn")
-    return str(base), data
-
-
-def _union_config(data, z):
-    con = make_config(48, path=data, scale=1.0)
-    con.set_parameters_by_name("ent_embeddings", z["ent"])
-    con.set_parameters_by_name("rel_embeddings", z["rel"])
-    return con
+    return run_worlds(_rank_worker, tmp_path_factory.mktemp("lp_shard_ranks"), 31900 + os.getpid() % 1000)
 
 
 @pytest.mark.parametrize("world", [2, 4])
 def test_ranks_equal_one_process_over_the_union_table(sharded_runs, world):
     base, data = sharded_runs
-    zs = [np.load(os.path.join(base, "w%d_r%d.npz" % (world, g))) for g in range(world)]
-    con = _union_config(data, zs[0])
+    zs = load_ranks(base, world)
+    con = union_config(data, zs[0])
     assert con.entTotal == 1003 and con.entTotal % world
     total = con.lib.getTestTotal()
     want, _, _ = lp_ranges(con, [(0, con.entTotal)])
@@ -362,8 +307,8 @@ def test_ranks_equal_one_process_over_the_union_table(sharded_runs, world):
 @pytest.mark.parametrize("world", [2, 4])
 def test_sharded_test_step_scores_bit_for_bit(sharded_runs, world):
     base, data = sharded_runs
-    zs = [np.load(os.path.join(base, "w%d_r%d.npz" % (world, g))) for g in range(world)]
-    con = _union_config(data, zs[0])
+    zs = load_ranks(base, world)
+    con = union_config(data, zs[0])
     for g, z in enumerate(zs):
         if len(z["h"]) == 0:           # (the rank that passed no triples took part in the exchange and got no scores)
             assert z["scores"].shape == (0,)
@@ -377,8 +322,8 @@ def test_sharded_test_step_scores_bit_for_bit(sharded_runs, world):
 @pytest.mark.parametrize("world", [2, 4])
 def test_predict_entity_helpers_refuse_a_sharded_table(sharded_runs, world):
     base, _ = sharded_runs
-    for g in range(world):
-        assert int(np.load(os.path.join(base, "w%d_r%d.npz" % (world, g)))["refused"]) == 2
+    for z in load_ranks(base, world):
+        assert int(z["refused"]) == 2
 
 
 # ---------------------------------------------------------------------------------------------------------------------------

@@ -7,6 +7,7 @@ rank agrees on, and the driver's --mode test --test_relation 1 on a sharded chec
 Every test first checks that the new entry point exists."""
 import ctypes
 import datetime
+import functools
 import json
 import os
 import sys
@@ -14,10 +15,11 @@ import sys
 import numpy as np
 import pytest
 
-from conftest import GOLDEN, ROOT
+from conftest import ROOT
+from shard_rig import KG, finish_rank, load_ranks, run_worlds, start_rank, union_config
+from shard_rig import make_config as rig_config
 
 pytestmark = pytest.mark.gpu
-KG = os.path.join(GOLDEN, "kg_small")
 OK, BAD_ARG, UNSUPPORTED = 0, -3, -4
 
 
@@ -28,20 +30,7 @@ def require_entry_point():
     return L
 
 
-def make_config(dim, path=KG, model="TransE", scale=3.0):
-    import openkeonspark_amd as pkg
-    con = pkg.Config()
-    con.set_in_path(path)
-    con.set_work_threads(1)
-    con.set_dimension(dim)
-    con.set_test_relation_prediction(True)
-    con.init()
-    con.set_model_and_session(getattr(pkg, model))
-    if scale != 1.0:
-        for t in con._tables:      # spread the scores: xavier-initialised tables rank almost at random
-            t.mul_(scale)
-        con.tables_changed()
-    return con
+make_config = functools.partial(rig_config, relation=True)
 
 
 def rows_counts(con, first, count):
@@ -139,29 +128,8 @@ def test_bad_ranges_are_refused_and_count_zero_checks_only():
 # 3-4: ranks (gloo, one GPU)
 # ---------------------------------------------------------------------------------------------------------------------------
 def _rank_worker(rank, world, port, out_dir, data):
-    sys.path.insert(0, ROOT)
-    import torch
-    import torch.distributed as dist
-    os.environ["MASTER_ADDR"] = "127.0.0.1"
-    os.environ["MASTER_PORT"] = str(port)
-    dist.init_process_group("gloo", rank=rank, world_size=world, timeout=datetime.timedelta(seconds=60))
     import openkeonspark_amd as pkg
-    pkg._lib.lib().kge_set_option(b"inv_table_max_bytes", 0)
-    con = pkg.Config()
-    con.set_in_path(data)
-    con.set_work_threads(8); con.set_bern(1); con.set_dimension(48); con.set_nbatches(10)
-    con.set_ent_neg_rate(3); con.set_alpha(0.02); con.set_opt_method("SGD")
-    con.sparse_rows = True
-    con.prefetch_sampling = False
-    con.counts_min_records = 0
-    con.set_test_relation_prediction(True)
-    con.init()
-    con.set_model_and_session(pkg.TransE)
-    con.init_distributed()
-    assert con._sharded("ent_embeddings") and con._tables[0].shape[0] == con._shard["chunk"]
-    for _ in range(4):
-        con.train_step()
-    torch.cuda.synchronize()
+    con = start_rank(rank, world, port, data, relation=True, timeout=datetime.timedelta(seconds=60))
     total = int(con.lib.getTestTotal())
     out = {}
     out["all"], m_all = con.relation_prediction()
@@ -184,33 +152,20 @@ def _rank_worker(rank, world, port, out_dir, data):
             raised.append(1)
     out["raised"] = np.array(raised)
     out["after"], _ = con.relation_prediction(3, 10)        # a valid call still works afterwards
-    params = con.get_parameters()      # (collective: the shards gathered; small tables only)
-    np.savez(os.path.join(out_dir, "w%d_r%d.npz" % (world, rank)), ent=params["ent_embeddings"], rel=params["rel_embeddings"],
-             metrics=json.dumps(dict(all=m_all, dist=m_dist)), **out)
-    dist.barrier()
-    dist.destroy_process_group()
+    finish_rank(con, out_dir, world, rank, metrics=json.dumps(dict(all=m_all, dist=m_dist)), **out)
 
 
 @pytest.fixture(scope="module")
 def sharded_runs(tmp_path_factory):
     require_entry_point()
-    import torch.multiprocessing as mp
-    from openkeonspark_amd import synthetic
-    base = tmp_path_factory.mktemp("relpred_shard_ranks")
-    data = synthetic.make_typed_dataset(str(base / "kg1003"), synthetic.SMALL_TYPED, entities=1003, train=6000, valid=100, test=60)
-    port = 35100 + os.getpid() % 1000
-    for i, w in enumerate((2, 4)):
-        mp.start_processes(_rank_worker, args=(w, port + i, str(base), data), nprocs=w, join=True, start_method="spawn")
-    return str(base), data
+    return run_worlds(_rank_worker, tmp_path_factory.mktemp("relpred_shard_ranks"), 35100 + os.getpid() % 1000)
 
 
 @pytest.mark.parametrize("world", [2, 4])
 def test_ranks_equal_one_process_over_the_union_table(sharded_runs, world):
     base, data = sharded_runs
-    zs = [np.load(os.path.join(base, "w%d_r%d.npz" % (world, g))) for g in range(world)]
-    con = make_config(48, path=data, scale=1.0)
-    con.set_parameters_by_name("ent_embeddings", zs[0]["ent"])
-    con.set_parameters_by_name("rel_embeddings", zs[0]["rel"])
+    zs = load_ranks(base, world)
+    con = union_config(data, zs[0], relation=True)
     assert con.entTotal == 1003 and con.entTotal % world
     total = int(con.lib.getTestTotal())
     want, m_want = con.relation_prediction()
@@ -232,8 +187,7 @@ def test_ranks_equal_one_process_over_the_union_table(sharded_runs, world):
 @pytest.mark.parametrize("world", [2, 4])
 def test_bad_calls_raise_on_every_rank(sharded_runs, world):
     base, _ = sharded_runs
-    for g in range(world):
-        z = np.load(os.path.join(base, "w%d_r%d.npz" % (world, g)))
+    for g, z in enumerate(load_ranks(base, world)):
         assert z["raised"].tolist() == [1, 1], g
 
 

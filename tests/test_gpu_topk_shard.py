@@ -8,15 +8,13 @@ Every test first checks that the new entry points exist."""
 import ctypes
 import datetime
 import os
-import sys
 
 import numpy as np
 import pytest
 
-from conftest import GOLDEN, ROOT
+from shard_rig import finish_rank, load_ranks, make_config, run_worlds, start_rank, union_config
 
 pytestmark = pytest.mark.gpu
-KG = os.path.join(GOLDEN, "kg_small")
 FILTERED, TYPED = 1, 2
 UNSUPPORTED = -4
 
@@ -27,22 +25,6 @@ def require_entry_points():
     for name in ("kge_topk_entities_range", "kge_topk_merge_keys"):
         assert hasattr(L, name), name + " is not exported"
     return L
-
-
-def make_config(dim, path=KG, model="TransE", scale=3.0):
-    import openkeonspark_amd as pkg
-    con = pkg.Config()
-    con.set_in_path(path)
-    con.set_work_threads(1)
-    con.set_dimension(dim)
-    con.set_test_link_prediction(True)
-    con.init()
-    con.set_model_and_session(getattr(pkg, model))
-    if scale != 1.0:
-        for t in con._tables:      # spread the scores: xavier-initialised tables rank almost at random
-            t.mul_(scale)
-        con.tables_changed()
-    return con
 
 
 def queries(con, n=48, seed=0):
@@ -206,29 +188,9 @@ CALLS = [("tail", "tail", 10, False, False, False, False),
 
 
 def _rank_worker(rank, world, port, out_dir, data):
-    sys.path.insert(0, ROOT)
     import torch
-    import torch.distributed as dist
-    os.environ["MASTER_ADDR"] = "127.0.0.1"
-    os.environ["MASTER_PORT"] = str(port)
-    dist.init_process_group("gloo", rank=rank, world_size=world, timeout=datetime.timedelta(seconds=60))
     import openkeonspark_amd as pkg
-    pkg._lib.lib().kge_set_option(b"inv_table_max_bytes", 0)
-    con = pkg.Config()
-    con.set_in_path(data)
-    con.set_work_threads(8); con.set_bern(1); con.set_dimension(48); con.set_nbatches(10)
-    con.set_ent_neg_rate(3); con.set_alpha(0.02); con.set_opt_method("SGD")
-    con.sparse_rows = True
-    con.prefetch_sampling = False
-    con.counts_min_records = 0
-    con.set_test_link_prediction(True)
-    con.init()
-    con.set_model_and_session(pkg.TransE)
-    con.init_distributed()
-    assert con._sharded("ent_embeddings") and con._tables[0].shape[0] == con._shard["chunk"]
-    for _ in range(4):
-        con.train_step()
-    torch.cuda.synchronize()
+    con = start_rank(rank, world, port, data, timeout=datetime.timedelta(seconds=60))
     E, R, chunk = con.entTotal, con.relTotal, con._shard["chunk"]
     f, r = _rank_queries(rank, world, E, R, chunk)
     out = dict(f=f, r=r)
@@ -262,32 +224,20 @@ def _rank_worker(rank, world, port, out_dir, data):
     except pkg.KgeError:
         refused = 1
     out["refused"] = np.array(refused)
-    params = con.get_parameters()      # (collective: the shards gathered; small tables only)
-    np.savez(os.path.join(out_dir, "w%d_r%d.npz" % (world, rank)), ent=params["ent_embeddings"], rel=params["rel_embeddings"], **out)
-    dist.barrier()
-    dist.destroy_process_group()
+    finish_rank(con, out_dir, world, rank, **out)
 
 
 @pytest.fixture(scope="module")
 def sharded_runs(tmp_path_factory):
     require_entry_points()
-    import torch.multiprocessing as mp
-    from openkeonspark_amd import synthetic
-    base = tmp_path_factory.mktemp("topk_shard_ranks")
-    data = synthetic.make_typed_dataset(str(base / "kg1003"), synthetic.SMALL_TYPED, entities=1003, train=6000, valid=100, test=60)
-    port = 33900 + os.getpid() % 1000
-    for i, w in enumerate((2, 4)):
-        mp.start_processes(_rank_worker, args=(w, port + i, str(base), data), nprocs=w, join=True, start_method="spawn")
-    return str(base), data
+    return run_worlds(_rank_worker, tmp_path_factory.mktemp("topk_shard_ranks"), 33900 + os.getpid() % 1000)
 
 
 @pytest.mark.parametrize("world", [2, 4])
 def test_ranks_equal_one_process_over_the_union_table(sharded_runs, world):
     base, data = sharded_runs
-    zs = [np.load(os.path.join(base, "w%d_r%d.npz" % (world, g))) for g in range(world)]
-    con = make_config(48, path=data, scale=1.0)
-    con.set_parameters_by_name("ent_embeddings", zs[0]["ent"])
-    con.set_parameters_by_name("rel_embeddings", zs[0]["rel"])
+    zs = load_ranks(base, world)
+    con = union_config(data, zs[0])
     assert con.entTotal == 1003 and con.entTotal % world
     assert len(zs[-1]["f"]) == 0 and len(zs[0]["f"]) > 0
     for g, z in enumerate(zs):
@@ -304,7 +254,6 @@ def test_ranks_equal_one_process_over_the_union_table(sharded_runs, world):
 @pytest.mark.parametrize("world", [2, 4])
 def test_bad_calls_raise_on_every_rank(sharded_runs, world):
     base, _ = sharded_runs
-    for g in range(world):
-        z = np.load(os.path.join(base, "w%d_r%d.npz" % (world, g)))
+    for g, z in enumerate(load_ranks(base, world)):
         assert z["raised"].tolist() == [1, 1], g
         assert int(z["refused"]) == 1, g       # top-k relations still refuse a sharded table

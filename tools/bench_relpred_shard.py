@@ -5,8 +5,8 @@ kge_relation_prediction on the same table.
   (a) the FB15k-237-shaped test set (synthetic.FB15K237_TYPED: 14 541 entities, 237 relations, 20 466 test triples, TransE
       D = 200): kge_relation_prediction_rows with the query rows already gathered, against kge_relation_prediction;
   (b) the same graph through the whole sharded Config.relation_prediction on one GPU: a one-rank RCCL group with
-      Config.force_data_parallel, which shards the table into one shard.  The row exchange (kge_test_entity_ids, _fetch_rows,
-      index_select, as relation_prediction runs them) is timed on its own and reported as a share of the call.
+      Config.force_data_parallel, which shards the table into one shard.  The row exchange (kge_test_entity_ids,
+      shard_eval.query_rows, as relation_prediction runs them) is timed on its own and reported as a share of the call.
 Kernel times: run under `rocprofv3 --kernel-trace --stats` (relpred_score_kernel, relpred_rank_kernel, relpred_iota_kernel).
 usage: bench_relpred_shard.py [--which a,b] [--reps R] [--dir DIR]"""
 import argparse
@@ -91,7 +91,7 @@ def workload_a(d, reps):
 def workload_b(d, reps):
     import torch
     import torch.distributed as dist
-    from openkeonspark_amd import _lib
+    from openkeonspark_amd import _lib, shard_eval
     os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
     os.environ.setdefault("MASTER_PORT", "29561")
     torch.cuda.set_device(0)
@@ -109,8 +109,7 @@ def workload_b(d, reps):
                 m = min(per, n - c0)
                 ids = torch.empty(2 * m, dtype=torch.int32, device=con.device)
                 _lib.check(L.kge_test_entity_ids(c0, m, ids.data_ptr(), st), L)
-                rows, slot_of = con._fetch_rows(ids, 2 * m)
-                rows.index_select(0, slot_of.long())
+                shard_eval.query_rows(con, ids, 2 * m)
         t_all = timed(lambda: con.relation_prediction(), reps)
         t_ex = timed(exchange, reps)
         t_ref = timed(reference_counts(con, n), reps)
