@@ -427,10 +427,13 @@ int kge_transe_reduce_apply_records_sgd(const kge_model_desc *m, const uint32_t 
  *                             (slot 0/1 = the positive's head/tail, 2 = relation, 3+k = the new entity of negative k)
  *   kge_shard_count         : d_counts[o] = how many of d_ids (ids < 0 skipped) rank o = id / chunk owns   (n_owners <= 64)
  *   kge_shard_scatter       : d_sorted = the live ids grouped by owner (h_counts = HOST copy of d_counts), d_slot_of[i] = position of
- *                             d_ids[i] in d_sorted or -1; d_cursor = n_owners ints of scratch
+ *                             d_ids[i] in d_sorted or -1; d_cursor = n_owners ints of scratch.  Only the first sum(h_counts)
+ *                             entries of d_sorted are written, in any order inside an owner's group; h_counts summing to more
+ *                             than n, or more than 64 owners, is KGE_ERR_BAD_ARG and nothing is written
  *   kge_shard_remap_batch   : the batch with entity ids replaced by positions in the fetched-row list (d_slot_of from the
  *                             requests), so the unchanged emit kernel runs against the fetched rows as its "entity table"
- *   kge_shard_gather_rows   : d_out[i,:] = d_table[d_ids[i] - row_lo, :]  (the owner's reply; dim % 4 == 0)
+ *   kge_shard_gather_rows   : d_out[i,:] = d_table[d_ids[i] - row_lo, :]  (the owner's reply; dim % 4 == 0); the ids come from a
+ *                             peer, so the row index is clamped into [0, rows - 1]: nothing outside the shard is read
  *   kge_shard_record_ids    : d_ids[m] = global entity id of record m when its destination is a fetched-row slot, else -1
  *   kge_shard_pack_records  : d_out[d_slot_of[m], :] = d_rec[m, :] for the records that travel
  *   kge_shard_relation_counts: relation records (destination >= cache_rows) summed into the dense int32 image [R, dim]

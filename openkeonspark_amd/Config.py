@@ -1101,10 +1101,10 @@ class Config(object):
                      rel_counts=torch.zeros((self.relTotal, D), dtype=i32, device=dev),
                      rel_rows=torch.arange(self.entTotal, self.entTotal + self.relTotal, dtype=i32, device=dev),
                      n_rel=torch.full((1,), self.relTotal, dtype=i32, device=dev), n_rows=torch.zeros(1, dtype=i32, device=dev), dw=dw)
-        if n_recv_rows > b["rr"]:
+        if n_recv_rows > b["rr"] or "recv_ids" not in b:       # (also for an owner that is never asked for a row: an empty shard)
             cap = max(int(n_recv_rows * 1.25), 64)
             b.update(rr=cap, recv_ids=torch.empty(cap, dtype=i32, device=dev), rows_out=torch.empty((cap, D), dtype=torch.float32, device=dev))
-        if n_recv_rec > b["rc"]:
+        if n_recv_rec > b["rc"] or "recv_rec" not in b:
             cap = max(int(n_recv_rec * 1.25), 64)
             b.update(rc=cap, recv_rows2=torch.empty(cap, dtype=i32, device=dev), recv_rec=torch.empty((cap, dw), dtype=i32, device=dev),
                      rows=torch.empty(cap, dtype=i32, device=dev), row_counts=torch.empty((cap, D), dtype=i32, device=dev))
@@ -1155,14 +1155,16 @@ class Config(object):
         # 4. relation rows: dense int32 image, all-reduced (the relation table is replicated)
         b["rel_counts"].zero_()
         if self._lazy_adam:
-            # which relations have a record on THIS rank -- the relation-slot destinations of its active groups (before the reduce below
-            # rewrites the destination keys in place); summed over the ranks with the counts.  Entry R collects the inactive groups.
+            # which relations have a record on THIS rank -- the relation-slot destinations of its active groups and, with relation
+            # negatives, the destinations of its active relation-corrupted negatives (slots 3 + k; a relation may take records from
+            # those alone, and one process moves its row then) -- read before the reduce below rewrites the destination keys in place;
+            # summed over the ranks with the counts.  Entry R collects everything else (no record, or a fetched-row slot).
             if "rel_live" not in b:
                 b["rel_live"] = torch.zeros(self.relTotal + 1, dtype=torch.int32, device=self.device)
             b["rel_live"].zero_()
             if n_pos > 0:
-                d = b["dst"][2 * n_pos:3 * n_pos]
-                idx = torch.where(d >= 0, d - int(desc2.ent_total), torch.full_like(d, self.relTotal))
+                d = b["dst"][2 * n_pos:(M if self.negative_rel > 0 else 3 * n_pos)]
+                idx = torch.where(d >= int(desc2.ent_total), d - int(desc2.ent_total), torch.full_like(d, self.relTotal))
                 b["rel_live"].index_fill_(0, idx.long(), 1)
         if D % 4 == 0 and self.negative_rel == 0 and n_pos > 0:
             # the relation-side records are slot 2 of every group -- records [2 n_pos, 3 n_pos): ordered by relation, summed by

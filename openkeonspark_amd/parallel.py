@@ -24,14 +24,15 @@ device collectives for these ops: CUDA tensors are staged through the host there
 
 
 def thread_range(rank, world_size, work_threads):
-    """Half-open range of virtual sampler threads owned by `rank`."""
+    """Half-open range of virtual sampler threads owned by `rank`: [rank*W/G, (rank+1)*W/G) in integers -- equal shares where the
+    ranks divide the threads, shares of floor(W/G) or one more otherwise (8 threads on 3 ranks: 2, 3, 3); every rank owns at
+    least one thread."""
     if world_size < 1 or not (0 <= rank < world_size):
         raise ValueError("bad rank/world_size")
-    if work_threads % world_size != 0:
-        raise ValueError("workThreads (%d) must be a multiple of the number of ranks (%d): "
+    if work_threads < world_size:
+        raise ValueError("workThreads (%d) must be at least the number of ranks (%d): "
                          "use Config.set_work_threads" % (work_threads, world_size))
-    per = work_threads // world_size
-    return rank * per, (rank + 1) * per
+    return rank * work_threads // world_size, (rank + 1) * work_threads // world_size
 
 
 def slice_positions(batch_size, work_threads, thread_lo, thread_hi):

@@ -12,7 +12,10 @@ from conftest import GOLDEN, ROOT
 pytestmark = pytest.mark.gpu
 
 
-def _worker(rank, world, port, out_dir, model_name, opt, sparse=False, prefetch=False, nbatches=10, pieces=0, rccl_one_rank=False):
+def _worker(rank, world, port, out_dir, model_name, opt, sparse=False, prefetch=False, nbatches=10, pieces=0, rccl_one_rank=False,
+            data=None, dim=48, rel_neg_rate=0, ent_neg_rate=3, trace=False):
+    """`data`: an OpenKE directory instead of kg_small.  `trace` (sparse rows only): also save, per step, the rng stream states the
+    step's batch was drawn from and which relation rows the step's row list held (trace_states, trace_rel_rows)."""
     sys.path.insert(0, ROOT)
     import torch
     import torch.distributed as dist
@@ -30,9 +33,9 @@ def _worker(rank, world, port, out_dir, model_name, opt, sparse=False, prefetch=
         pkg._lib.lib().kge_set_option(b"float_records_min", 0)
         pkg._lib.lib().kge_set_option(b"pair_counts_min_neg", 1)
     con = pkg.Config()
-    con.set_in_path(os.path.join(GOLDEN, "kg_small"))
-    con.set_work_threads(8); con.set_bern(1); con.set_dimension(48); con.set_nbatches(nbatches)  # B = 600 by default
-    con.set_ent_neg_rate(3); con.set_alpha(0.02); con.set_opt_method(opt)
+    con.set_in_path(data or os.path.join(GOLDEN, "kg_small"))
+    con.set_work_threads(8); con.set_bern(1); con.set_dimension(dim); con.set_nbatches(nbatches)  # B = 600 by default
+    con.set_ent_neg_rate(ent_neg_rate); con.set_rel_neg_rate(rel_neg_rate); con.set_alpha(0.02); con.set_opt_method(opt)
     con.sparse_rows = sparse
     con.prefetch_sampling = prefetch   # (data-parallel default: on; then the rng states run one batch ahead)
     con.counts_min_records = 0
@@ -51,10 +54,19 @@ def _worker(rank, world, port, out_dir, model_name, opt, sparse=False, prefetch=
         assert con._dp and dist.get_backend() == "nccl" and (sparse or hasattr(con, "_flat_p"))
         if not sparse and not pieces:       # one piece: the collectives run on the engine's own stream (parallel.StreamRccl)
             assert con._stream_rccl() is not None
-    losses = [con.train_step() for _ in range(4)]
+    losses, extra = [], {}
+    if trace:
+        extra = dict(trace_states=[], trace_rel_rows=np.zeros((4, con.relTotal), dtype=bool), trace_batch=con.batch_size)
+    for step in range(4):
+        if trace:
+            extra["trace_states"].append(con.get_stream_states())
+        losses.append(con.train_step())
+        if trace and world == 1 and not rccl_one_rank:      # (the one-process sparse step lists every row that had a record)
+            rows = con.sparse_row_gradients()[0].cpu().numpy()
+            extra["trace_rel_rows"][step, rows[rows >= con.entTotal] - con.entTotal] = True
     torch.cuda.synchronize()
     np.savez(os.path.join(out_dir, "w%d_r%d%s.npz" % (world, rank, "_rccl" if rccl_one_rank else "")), losses=np.array(losses),
-             states=con.get_stream_states(), **con.get_parameters())
+             states=con.get_stream_states(), **extra, **con.get_parameters())
     if world > 1 or rccl_one_rank:
         dist.barrier()
         dist.destroy_process_group()
@@ -151,6 +163,97 @@ def test_ranks_sharded_lazy_adam(tmp_path, world):
         for k in one.files:
             if k not in ("losses", "states"):
                 assert np.array_equal(r[k], one[k]), k
+
+
+def _sharded_equals_one_process(res, world):
+    """test_ranks_sharded_sparse_table's assertions: rng stream states equal, every table equal bit for bit on every rank, the
+    loss (summed over the ranks in another order) to rtol 2e-5."""
+    one = res[1][0]
+    tables = [k for k in one.files if k not in ("losses", "states") and not k.startswith("trace_")]
+    assert "ent_embeddings" in tables and "rel_embeddings" in tables
+    for r in res[world]:
+        assert np.array_equal(r["states"], one["states"])
+        assert np.allclose(r["losses"], one["losses"], rtol=2e-5, atol=0)
+        for k in tables:
+            assert r[k].shape == one[k].shape and np.array_equal(r[k], one[k]), k
+
+
+def test_ranks_sharded_at_dim_512_on_eight_ranks(tmp_path):
+    """BASELINE config #5's width and rank count: dim 512 (128-dword records: the per-row loops of the pack, gather and relation
+    count kernels run more than one round), 8 ranks, 1003 entities (chunk 126: the last shard holds 121 rows)."""
+    from openkeonspark_amd import synthetic
+    data = synthetic.make_typed_dataset(str(tmp_path / "kg1003"), synthetic.SMALL_TYPED, entities=1003, train=6000, valid=100, test=60)
+    res = _run_worlds(tmp_path, [1, 8], "TransE", "SGD", True, False, 10, 0, False, data, 512)
+    _sharded_equals_one_process(res, 8)
+
+
+def test_ranks_sharded_on_three_ranks(tmp_path):
+    """Three ranks: the 8 virtual sampler threads split 2 / 3 / 3 (parallel.thread_range) and kg_small's 1000 entities 334 / 334 / 332."""
+    res = _run_worlds(tmp_path, [1, 3], "TransE", "SGD", True)
+    _sharded_equals_one_process(res, 3)
+
+
+@pytest.mark.parametrize("opt", ["SGD", "LazyAdam"])
+def test_ranks_sharded_with_an_empty_shard(tmp_path, opt):
+    """33 entities on 8 ranks: chunk 5, so rank 6 owns three rows and rank 7 NONE (lo == hi == 33).  The empty owner still joins
+    every collective, answers no request, receives no record, and applies the relation update like everyone else."""
+    from openkeonspark_amd import parallel, synthetic
+    E, R, n = 33, 5, 400
+    assert parallel.chunk_size(E, 8) == 5 and 7 * 5 >= E > 6 * 5
+    rng = np.random.default_rng(33)
+    data = synthetic.write_openke_dir(str(tmp_path / "kg33"), E, R, rng.integers(0, E, n), rng.integers(0, E, n), rng.integers(0, R, n))
+    res = _run_worlds(tmp_path, [1, 8], "TransE", opt, True, False, 10, 0, False, data)
+    _sharded_equals_one_process(res, 8)
+
+
+@pytest.mark.parametrize("world", [2, 4])
+def test_ranks_sharded_with_relation_negatives(tmp_path, world):
+    """ent_neg_rate 2, rel_neg_rate 2: the relation-corrupted negatives' records (destination ent_total + r', slot 3 + k) request no
+    entity row, reuse both cache slots of their positive, stay out of the entity exchange and reach the relation image through
+    kge_shard_relation_counts -- the branch of Config._sharded_step that no other test runs on a record."""
+    res = _run_worlds(tmp_path, [1, world], "TransE", "SGD", True, False, 10, 0, False, None, 48, 2, 2)
+    _sharded_equals_one_process(res, world)
+
+
+LAZY_REL = dict(entities=1003, relations=40, train=6000, valid=100, test=60)    # (SMALL_TYPED with 40 relations)
+LAZY_REL_NBATCHES = 250                                                          # B = 24 positives, 48 relation negatives per step
+
+
+def _relations_only_negatives_touch(data, z, ent_neg, rel_neg):
+    """Per step of the one-process run `z` (saved with trace=True): the relations whose row the step listed (so some record went
+    to it) although no positive of the step's batch has them -- a relation row takes records from its positives' relation slot
+    and from ACTIVE relation-corrupted negatives only, so these are exactly the relations an active negative alone brought in.
+    The batches are the oracle sampler's from the run's own stream states (equal to the device sampler's bit for bit,
+    tests/test_gpu_sampler.py)."""
+    from oracle import oracle
+    kg = oracle.KG(data, work_threads=8, bern=1)
+    B = int(z["trace_batch"])
+    assert 16 <= B <= 32 and kg.relTotal == 40
+    out = []
+    for step in range(4):
+        kg.set_stream_states(z["trace_states"][step])
+        bh, bt, br, _ = kg.sampling(B, ent_neg, rel_neg)
+        br = np.asarray(br).reshape(1 + ent_neg + rel_neg, B)
+        neg_new = np.unique(br[1 + ent_neg:][br[1 + ent_neg:] != br[0]])
+        listed = np.nonzero(z["trace_rel_rows"][step])[0]
+        only_neg = np.setdiff1d(listed, br[0])
+        assert np.isin(only_neg, neg_new).all()         # (nothing else can have put a record on such a row)
+        out.append(only_neg)
+    return out
+
+
+@pytest.mark.parametrize("world", [2, 4])
+def test_ranks_sharded_lazy_adam_with_relation_negatives(tmp_path, world):
+    """LazyAdam on a sharded table with relation negatives, 24 positives over 40 relations: in some step a relation takes records
+    ONLY from relation-corrupted negatives.  One process lists that row and moves it and its moments; the sharded step must mark
+    it live too (Config._sharded_step), or the replicated relation table leaves the one-process table at that step.  The
+    precondition -- such a relation exists in at least one of the four steps -- is asserted first."""
+    from openkeonspark_amd import synthetic
+    data = synthetic.make_typed_dataset(str(tmp_path / "kg40rel"), synthetic.SMALL_TYPED, **LAZY_REL)
+    res = _run_worlds(tmp_path, [1, world], "TransE", "LazyAdam", True, False, LAZY_REL_NBATCHES, 0, False, data, 48, 2, 2, True)
+    only_neg = _relations_only_negatives_touch(data, res[1][0], 2, 2)
+    assert sum(len(x) for x in only_neg) > 0, only_neg
+    _sharded_equals_one_process(res, world)
 
 
 @pytest.mark.parametrize("model_name,world", [("TransH", 2), ("TransH", 4), ("TransD", 2)])

@@ -61,8 +61,17 @@ def test_thread_range_requires_divisibility():
     from openkeonspark_amd.parallel import thread_range
     assert thread_range(1, 2, 8) == (4, 8)
     assert thread_range(7, 8, 8) == (7, 8)
-    with pytest.raises(ValueError):
-        thread_range(0, 3, 8)
+    # ranks that do not divide the threads take floor(W / G) threads or one more, in order, and cover every thread once
+    assert [thread_range(g, 3, 8) for g in range(3)] == [(0, 2), (2, 5), (5, 8)]
+    for W in range(1, 17):
+        for G in range(1, W + 1):
+            cuts = [thread_range(g, G, W) for g in range(G)]
+            assert cuts[0][0] == 0 and cuts[-1][1] == W and all(a[1] == b[0] for a, b in zip(cuts, cuts[1:]))
+            assert all(W // G <= hi - lo <= -(-W // G) for lo, hi in cuts)
+            if W % G == 0:
+                assert cuts == [(g * (W // G), (g + 1) * (W // G)) for g in range(G)]
+    with pytest.raises(ValueError):     # fewer threads than ranks: a rank would own no sampler stream at all
+        thread_range(0, 9, 8)
 
 
 def _collectives_worker(rank, world, port, out_dir):
