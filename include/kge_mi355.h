@@ -290,6 +290,22 @@ int kge_forward_backward_records(const kge_model_desc *m, const float *const tab
                                  int32_t *d_dst, INT rec_offset, INT rec_slice, float *d_loss, void *stream);
 int kge_float_records_apply(const kge_model_desc *m, float *const tables[KGE_MAX_TABLES], const float *d_rec, int32_t *d_dst, INT n_records,
                             INT n_pos_total, INT n_neg, float lr, void *stream);
+/* NON-PARITY, opt-in: the two entry points above ending in LAZY ADAM instead of the add -- the reference trains with TF1's
+ * AdamOptimizer, which moves every row of every table each step (distribute_training.py:95-101; kge_adam_update_tables is the
+ * parity path).  Here the records are ordered by a stable sort and every destination row's COMPLETE sum (one team per run, record
+ * order; the copies of a relation-side row folded in copy order; no atomics) goes through the Adam element rule on that row's
+ * value and its moments adam_m / adam_v (one per table of the model, shaped like it), in place: EVERY element of a row that has a
+ * record -- elements whose summed gradient is exactly zero decay m and v and move too, as kge_transe_apply_rows_adam_lazy
+ * documents -- and no element of a row without one (keys < 0 or beyond the row space carry no record).  No buffer shaped like a
+ * table and no pass over one.  The order of every sum is fixed: a step is reproducible bit for bit, and ranks that apply the same
+ * records keep bit-identical replicas.  lr_t = lr sqrt(1 - beta2^t) / (1 - beta1^t) from the caller.  TransE / TransH / TransD;
+ * TransR: KGE_ERR_UNSUPPORTED.  kge_sgd_rows_skipped applies as above. */
+int kge_forward_backward_adam_rows(const kge_model_desc *m, float *const tables[KGE_MAX_TABLES], float *const adam_m[KGE_MAX_TABLES],
+                                   float *const adam_v[KGE_MAX_TABLES], const int32_t *d_h, const int32_t *d_t, const int32_t *d_r, INT n_pos,
+                                   INT n_neg, INT stride, INT denom, float lr_t, float beta1, float beta2, float eps, float *d_loss, void *stream);
+int kge_float_records_apply_adam(const kge_model_desc *m, float *const tables[KGE_MAX_TABLES], float *const adam_m[KGE_MAX_TABLES],
+                                 float *const adam_v[KGE_MAX_TABLES], const float *d_rec, int32_t *d_dst, INT n_records, INT n_pos_total,
+                                 INT n_neg, float lr_t, float beta1, float beta2, float eps, void *stream);
 /* 1 when kge_forward_backward on a step of this shape takes the TransH / TransD pair-count path (whose emit kernel also records
  * the event above), else 0 */
 int kge_pair_path_active(const kge_model_desc *m, INT n_pos, INT n_neg);

@@ -287,13 +287,16 @@ class Config(object):
         # gradient records (kge_forward_backward_sgd_rows) -- no gradient tables, no sweep.  On request, or by itself for tables
         # beyond 2 GB (measured at 4 GB, dim 200, B = 131 072, n = 1: TransH 1.63 -> 0.70 ms, TransD 2.83 -> 0.97 ms per step and
         # half the memory, profiles/r03_h_*; the dense form's sweep scales with the table, so the two tie near 1 GB)
+        # With LazyAdam the same records end in the Adam rule on the touched rows and their moments instead of the add
+        # (kge_forward_backward_adam_rows): asking for LazyAdam IS asking for touched rows, whatever `sparse_rows` says.
         vector_model = m.model_id in (_lib.TRANSE, _lib.TRANSH, _lib.TRANSD)
-        self.sparse_inplace = bool(not self.sparse_rows and vector_model and not self._has_slots and
-                                   (requested or (requested is None and table_bytes > (2 << 30))))
+        self.sparse_inplace = bool(not self.sparse_rows and vector_model and not self._adam and
+                                   (self._lazy_adam or requested or (requested is None and table_bytes > (2 << 30))))
+        if self._lazy_adam and not (self.sparse_rows or self.sparse_inplace):
+            raise KgeError("LazyAdam (touched rows only, NON-PARITY) needs TransE, TransH or TransD: TransR's gradient is a whole "
+                           "matrix per relation and has no record path")
         if requested and not (self.sparse_rows or self.sparse_inplace):
-            raise KgeError("sparse_rows needs TransE / TransH / TransD with SGD (TransE on the sign-count path also with LazyAdam)")
-        if self._lazy_adam and not self.sparse_rows:
-            raise KgeError("LazyAdam (touched rows only, NON-PARITY) needs TransE on the sign-count path: 1..63 negatives")
+            raise KgeError("sparse_rows needs TransE / TransH / TransD with SGD or LazyAdam")
         self._grads = [] if (self.sparse_rows or self.sparse_inplace) else [torch.zeros_like(t) for t in self._tables]
         if self._has_slots:
             self._adam_m = [torch.zeros_like(t) for t in self._tables]
@@ -845,9 +848,16 @@ class Config(object):
             if batch_h is None and self.prefetch_sampling:
                 self._prefetch_next_batch()
         elif self.sparse_inplace:
-            _lib.check(self.lib.kge_forward_backward_sgd_rows(
-                ctypes.byref(self._desc), self._tab_ptrs, dev[0].data_ptr(), dev[1].data_ptr(), dev[2].data_ptr(), n_pos, n_neg,
-                stride, denom, float(self.alpha), self._loss.data_ptr(), self._stream()), self.lib)
+            if self._lazy_adam:
+                _lib.check(self.lib.kge_forward_backward_adam_rows(
+                    ctypes.byref(self._desc), self._tab_ptrs, self._adam_m_ptrs, self._adam_v_ptrs, dev[0].data_ptr(), dev[1].data_ptr(),
+                    dev[2].data_ptr(), n_pos, n_neg, stride, denom, float(self._adam_lr_t()), self.adam_beta1, self.adam_beta2,
+                    self.adam_epsilon, self._loss.data_ptr(), self._stream()), self.lib)
+                self._adam_advance()
+            else:
+                _lib.check(self.lib.kge_forward_backward_sgd_rows(
+                    ctypes.byref(self._desc), self._tab_ptrs, dev[0].data_ptr(), dev[1].data_ptr(), dev[2].data_ptr(), n_pos, n_neg,
+                    stride, denom, float(self.alpha), self._loss.data_ptr(), self._stream()), self.lib)
             if batch_h is not None:       # a hand-fed batch may hold negatives the in-place update cannot take (the sampler draws none)
                 skipped = ctypes.c_int32(0)
                 _lib.check(self.lib.kge_sgd_rows_skipped(ctypes.byref(skipped)), self.lib)
@@ -984,10 +994,10 @@ class Config(object):
         return out
 
     def _records_step(self, dev_batch, n_pos, stride, denom):
-        """Row-wise SGD in place across ranks (TransH / TransD, or TransE off the sign-count path, with sparse_rows): the tables
-        are replicated; every rank turns ITS slice of the batch into float gradient records, the records (rows + destination
+        """Row-wise SGD (or lazy Adam) in place across ranks (TransH / TransD, or TransE off the sign-count path, with sparse_rows):
+        the tables -- and with LazyAdam their moments -- are replicated; every rank turns ITS slice of the batch into float gradient records, the records (rows + destination
         keys) are all-gathered -- the sparse touched-row exchange: only rows a step touches travel -- and every rank adds -lr * the
-        per-row sums of ALL records to its replica.  Every rank reduces the same records in the same order, so the replicas stay
+        per-row sums of ALL records to its replica (LazyAdam: puts them through the Adam rule on the rows that have a record).  Every rank reduces the same records in the same order, so the replicas stay
         bit-identical; against the single-process step the per-row sums differ in fp32 order only.  Replaces the scatter_sub
         updates the reference's workers send to its parameter servers (distribute_training.py:99-101,193-196)."""
         import torch
@@ -1012,9 +1022,16 @@ class Config(object):
             all_gather_chunks(b["rec"].view(-1), b["rec"][off:off + per].view(-1), self._pg)
             all_gather_chunks(b["dst"], b["dst"][off:off + per], self._pg)
             allreduce_sum([self._loss], self._pg)
-        _lib.check(self.lib.kge_float_records_apply(
-            ctypes.byref(self._desc), self._tab_ptrs, b["rec"].data_ptr(), b["dst"].data_ptr(), W * per, self.batch_size, n_neg,
-            float(self.alpha), self._stream()), self.lib)
+        if self._lazy_adam:      # m and v are replicated like the tables: the same lr_t and the same records on every rank
+            _lib.check(self.lib.kge_float_records_apply_adam(
+                ctypes.byref(self._desc), self._tab_ptrs, self._adam_m_ptrs, self._adam_v_ptrs, b["rec"].data_ptr(), b["dst"].data_ptr(),
+                W * per, self.batch_size, n_neg, float(self._adam_lr_t()), self.adam_beta1, self.adam_beta2, self.adam_epsilon,
+                self._stream()), self.lib)
+            self._adam_advance()
+        else:
+            _lib.check(self.lib.kge_float_records_apply(
+                ctypes.byref(self._desc), self._tab_ptrs, b["rec"].data_ptr(), b["dst"].data_ptr(), W * per, self.batch_size, n_neg,
+                float(self.alpha), self._stream()), self.lib)
         self.global_step += 1
 
     def _sparse_step(self, dev_batch, n_pos, stride, denom, check_shape=False):

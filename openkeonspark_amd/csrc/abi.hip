@@ -410,6 +410,40 @@ int kge_float_records_apply(const kge_model_desc *m, float *const tables[KGE_MAX
     return launch_float_records_apply(*m, tables, d_rec, d_dst, n_records, n_pos_total, n_neg, lr, (hipStream_t)stream);
 }
 
+// the moments of the model's tables (a table the model does not have: ignored), or false if one is missing
+static bool adam_rows_of(const kge_model_desc &m, float *const tables[KGE_MAX_TABLES], float *const adam_m[KGE_MAX_TABLES],
+                         float *const adam_v[KGE_MAX_TABLES], float lr_t, float beta1, float beta2, float eps, AdamRows &ad) {
+    ad = {};
+    for (int t = 0; t < 4; t++) {
+        if (!tables[t]) continue;
+        if (!adam_m[t] || !adam_v[t]) return false;
+        ad.m[t] = adam_m[t]; ad.v[t] = adam_v[t];
+    }
+    ad.lr_t = lr_t; ad.b1 = beta1; ad.b2 = beta2; ad.eps = eps;
+    return true;
+}
+
+int kge_forward_backward_adam_rows(const kge_model_desc *m, float *const tables[KGE_MAX_TABLES], float *const adam_m[KGE_MAX_TABLES],
+                                   float *const adam_v[KGE_MAX_TABLES], const int32_t *d_h, const int32_t *d_t, const int32_t *d_r, INT n_pos,
+                                   INT n_neg, INT stride, INT denom, float lr_t, float beta1, float beta2, float eps, float *d_loss, void *stream) {
+    if (!m || !tables || !adam_m || !adam_v || !d_loss) return fail(KGE_ERR_BAD_ARG, "kge_forward_backward_adam_rows: null argument");
+    if (m->model == KGE_TRANSR) return fail(KGE_ERR_UNSUPPORTED, "lazy Adam on the touched rows: TransE / TransH / TransD only");
+    AdamRows ad;
+    if (!adam_rows_of(*m, tables, adam_m, adam_v, lr_t, beta1, beta2, eps, ad))
+        return fail(KGE_ERR_BAD_ARG, "kge_forward_backward_adam_rows: every table needs its two moment tables");
+    return launch_forward_backward(*m, tables, d_h, d_t, d_r, n_pos, n_neg, stride, denom, tables, d_loss, (hipStream_t)stream, false, 0.f, &ad);
+}
+
+int kge_float_records_apply_adam(const kge_model_desc *m, float *const tables[KGE_MAX_TABLES], float *const adam_m[KGE_MAX_TABLES],
+                                 float *const adam_v[KGE_MAX_TABLES], const float *d_rec, int32_t *d_dst, INT n_records, INT n_pos_total,
+                                 INT n_neg, float lr_t, float beta1, float beta2, float eps, void *stream) {
+    if (!m || !tables || !adam_m || !adam_v) return fail(KGE_ERR_BAD_ARG, "kge_float_records_apply_adam: null argument");
+    AdamRows ad;
+    if (!adam_rows_of(*m, tables, adam_m, adam_v, lr_t, beta1, beta2, eps, ad))
+        return fail(KGE_ERR_BAD_ARG, "kge_float_records_apply_adam: every table needs its two moment tables");
+    return launch_float_records_apply_adam(*m, tables, ad, d_rec, d_dst, n_records, n_pos_total, n_neg, (hipStream_t)stream);
+}
+
 int kge_loss_limbs_target(int32_t *d_limbs4) {
     engine().loss_limbs = d_limbs4;
     return KGE_OK;

@@ -153,9 +153,19 @@ int float_records_workspace(int64_t M, int D, float *&rec, int32_t *&dst);
 // deterministic: stable sort + one team per run + ordered fold of the hub copies (bit-identical on every rank that reduces the same records)
 int float_records_reduce(int64_t M, int D, const FloatRowSpace &rs, hipStream_t stream, const float *rec_ext = nullptr, int32_t *dst_ext = nullptr,
                          bool deterministic = false);
+// lazy Adam on the touched rows (NON-PARITY): the moments of the four tables in the order of kge_model_desc's tables, and the rule's constants
+struct AdamRows {
+    float *m[4], *v[4];
+    float lr_t, b1, b2, eps;
+};
+// the deterministic reduce ending in adam_one on every row that has a record (rs.g_* = the parameter tables; rs.scale unused)
+int float_records_reduce_adam(int64_t M, int D, const FloatRowSpace &rs, const AdamRows &ad, hipStream_t stream, const float *rec_ext = nullptr,
+                              int32_t *dst_ext = nullptr);
 int launch_forward_backward_records(const kge_model_desc &m, const float *const tables[4], const int32_t *d_h, const int32_t *d_t,
                                     const int32_t *d_r, int64_t n_pos, int64_t n_neg, int64_t stride, int64_t denom, int64_t n_pos_total,
                                     float *d_rec, int32_t *d_dst, int64_t rec_offset, int64_t rec_slice, float *d_loss, hipStream_t stream);
+int launch_float_records_apply_adam(const kge_model_desc &m, float *const tables[4], const AdamRows &ad, const float *d_rec, int32_t *d_dst,
+                                    int64_t M_total, int64_t n_pos_total, int64_t n_neg, hipStream_t stream);
 int launch_float_records_apply(const kge_model_desc &m, float *const tables[4], const float *d_rec, int32_t *d_dst, int64_t M_total,
                                int64_t n_pos_total, int64_t n_neg, float lr, hipStream_t stream);
 
@@ -170,7 +180,8 @@ int launch_sampler(int32_t *d_h, int32_t *d_t, int32_t *d_r, int64_t B, int64_t 
 int launch_widen(const int32_t *src3, int64_t *dst3_and_y, int64_t B, int64_t total, hipStream_t stream);
 int launch_forward_backward(const kge_model_desc &m, const float *const tables[4], const int32_t *d_h, const int32_t *d_t,
                             const int32_t *d_r, int64_t n_pos, int64_t n_neg, int64_t stride, int64_t denom,
-                            float *const grads[4], float *d_loss, hipStream_t stream, bool sampler_shaped = false, float inplace_lr = 0.f);
+                            float *const grads[4], float *d_loss, hipStream_t stream, bool sampler_shaped = false, float inplace_lr = 0.f,
+                            const AdamRows *inplace_adam = nullptr);
 int launch_predict(const kge_model_desc &m, const float *const tables[4], const int32_t *d_h, const int32_t *d_t,
                    const int32_t *d_r, int64_t n, float *d_out, hipStream_t stream);
 int launch_lp_table(const kge_model_desc &m, const float *const tables[4], const float *P_all, int64_t r, float *T, hipStream_t stream);

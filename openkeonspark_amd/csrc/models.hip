@@ -1154,18 +1154,39 @@ int launch_float_records_apply(const kge_model_desc &m, float *const tables[4], 
     return float_records_reduce(M_total, m.ent_dim, rs, stream, d_rec, d_dst, true);
 }
 
+int launch_float_records_apply_adam(const kge_model_desc &m, float *const tables[4], const AdamRows &ad, const float *d_rec, int32_t *d_dst,
+                                    int64_t M_total, int64_t n_pos_total, int64_t n_neg, hipStream_t stream) {
+    if (!device_ok()) return fail(KGE_ERR_NO_DEVICE, "kge_float_records_apply_adam: no usable HIP device");
+    if (!d_rec || !d_dst || M_total < 0 || n_pos_total < 0) return fail(KGE_ERR_BAD_ARG, "kge_float_records_apply_adam: bad arguments");
+    if (m.model != KGE_TRANSE && m.model != KGE_TRANSH && m.model != KGE_TRANSD)
+        return fail(KGE_ERR_UNSUPPORTED, "gradient rows as float records: TransE / TransH / TransD only");
+    if (M_total == 0) return KGE_OK;
+    if (M_total >= (int64_t(1) << 31)) return fail(KGE_ERR_UNSUPPORTED, "kge_float_records_apply_adam: too many records for the record sort");
+    const RecordSpace sp = record_space(m, n_pos_total, n_neg);
+    if (sp.rows >= (int64_t(1) << 31) - 1 || m.ent_dim > 1024) return fail(KGE_ERR_UNSUPPORTED, "gradient rows as float records: row space too large");
+    FloatRowSpace rs;
+    rs.g_ent = tables[0]; rs.g_rel = tables[1]; rs.g_auxr = tables[2]; rs.g_auxe = tables[3];
+    rs.E = m.ent_total; rs.R = m.rel_total; rs.hub_base = sp.ent_rows; rs.hub_rows = sp.hub_rows; rs.rows = sp.rows;
+    tables_written();
+    return float_records_reduce_adam(M_total, m.ent_dim, rs, ad, stream, d_rec, d_dst);
+}
+
 int launch_forward_backward(const kge_model_desc &m, const float *const tables[4], const int32_t *d_h, const int32_t *d_t,
                             const int32_t *d_r, int64_t n_pos, int64_t n_neg, int64_t stride, int64_t denom,
-                            float *const grads[4], float *d_loss, hipStream_t stream, bool sampler_shaped, float inplace_lr) {
+                            float *const grads[4], float *d_loss, hipStream_t stream, bool sampler_shaped, float inplace_lr,
+                            const AdamRows *inplace_adam) {
     // inplace_lr != 0 (kge_forward_backward_sgd_rows): `grads` ARE the parameter tables; the step's gradient rows go through the
     // float-record path whatever its size and every summed run is added to its row as -lr * sum -- SGD on the touched rows, no
     // gradient tables, no sweep.  The forward has finished reading the tables when the segmented sum starts (one stream).
+    // inplace_adam (kge_forward_backward_adam_rows): the same, ending in lazy Adam on the touched rows and their moments
+    // (float_records_reduce_adam) instead of the add.
+    const bool inplace = inplace_lr != 0.f || inplace_adam;
     Engine &e = engine();
     if (!device_ok()) return fail(KGE_ERR_NO_DEVICE, "kge_forward_backward: no usable HIP device");
     if (n_pos < 0 || n_neg < 1 || stride < n_pos || denom <= 0) return fail(KGE_ERR_BAD_ARG, "kge_forward_backward: bad sizes");
     { int rc = ensure_loss_buffers(); if (rc) return rc; }
     if (m.model == KGE_TRANSR) {
-        if (inplace_lr != 0.f) return fail(KGE_ERR_UNSUPPORTED, "row-wise SGD in place: TransE / TransH / TransD only");
+        if (inplace) return fail(KGE_ERR_UNSUPPORTED, "row-wise update in place: TransE / TransH / TransD only");
         return launch_forward_backward_transr(m, tables, d_h, d_t, d_r, n_pos, n_neg, stride, denom, grads, d_loss, stream, sampler_shaped);
     }
     if (m.ent_dim != m.rel_dim) return fail(KGE_ERR_BAD_ARG, "TransE/H/D need ent_dim == rel_dim (hidden_size)");
@@ -1179,7 +1200,7 @@ int launch_forward_backward(const kge_model_desc &m, const float *const tables[4
     a.P = nullptr; a.GP = nullptr; a.negative_rel = m.negative_rel;
     int rc;
     // Pair-count path (TransH / TransD): int8 sign records keyed by (entity, relation), the backward applied once per pair
-    if (inplace_lr == 0.f && pair_path_active(m, n_pos, n_neg)) {     // (its per-pair backward re-reads the rows: not for in-place updates)
+    if (!inplace && pair_path_active(m, n_pos, n_neg)) {     // (its per-pair backward re-reads the rows: not for in-place updates)
         const int64_t M = n_pos * (2 + n_neg);
         const int rd = pair_record_dwords(a.D);
         if ((rc = pair_records_workspace(M, rd, a.rec, a.dst, a.pair_aux))) return rc;
@@ -1228,16 +1249,16 @@ int launch_forward_backward(const kge_model_desc &m, const float *const tables[4
     const int64_t slots = sp.slots, ent_rows = sp.ent_rows, hub_rows = sp.hub_rows, hub_k = sp.hub_k, rows = sp.rows;
     const int64_t M = n_pos * slots;
     const bool records_fit = M < (int64_t(1) << 31) && rows < (int64_t(1) << 31) - 1 && a.D <= 1024;
-    if (inplace_lr != 0.f && !records_fit) return fail(KGE_ERR_UNSUPPORTED, "row-wise SGD in place: step or row space too large for the record sort");
-    if (n_pos == 0 && inplace_lr != 0.f) return hip_check(hipMemsetAsync(d_loss, 0, sizeof(float), stream), "zero loss");
-    if (records_fit && (inplace_lr != 0.f || (e.float_records && M >= e.float_records_min))) {
+    if (inplace && !records_fit) return fail(KGE_ERR_UNSUPPORTED, "row-wise update in place: step or row space too large for the record sort");
+    if (n_pos == 0 && inplace) return hip_check(hipMemsetAsync(d_loss, 0, sizeof(float), stream), "zero loss");
+    if (records_fit && (inplace || (e.float_records && M >= e.float_records_min))) {
         float *frec = nullptr;
         int32_t *fdst = nullptr;
         if ((rc = float_records_workspace(M, a.D, frec, fdst))) return rc;
         a.frec = frec; a.fdst = fdst;
         a.ent_total = (int)m.ent_total; a.rel_total = (int)m.rel_total;
         a.hub_base = ent_rows; a.hub_k = (int)hub_k; a.hub_rows = (int)hub_rows;
-        if (inplace_lr != 0.f) {
+        if (inplace) {
             if (!g_skipped && (rc = hip_check(hipMalloc(&g_skipped, sizeof(int32_t)), "alloc skipped-negatives counter"))) return rc;
             if ((rc = hip_check(hipMemsetAsync(g_skipped, 0, sizeof(int32_t), stream), "zero skipped-negatives counter"))) return rc;
             a.skipped = g_skipped;
@@ -1252,7 +1273,9 @@ int launch_forward_backward(const kge_model_desc &m, const float *const tables[4
         FloatRowSpace rs;
         rs.g_ent = grads[0]; rs.g_rel = grads[1]; rs.g_auxr = grads[2]; rs.g_auxe = grads[3];
         rs.E = m.ent_total; rs.R = m.rel_total; rs.hub_base = ent_rows; rs.hub_rows = hub_rows; rs.rows = rows;
-        if (inplace_lr != 0.f) { rs.scale = -inplace_lr; tables_written(); }
+        if (inplace) tables_written();
+        if (inplace_adam) return float_records_reduce_adam(M, a.D, rs, *inplace_adam, stream);
+        if (inplace_lr != 0.f) rs.scale = -inplace_lr;
         return float_records_reduce(M, a.D, rs, stream);
     }
     // atomic path: hub copies for the relation-side rows when a row would take hundreds of adds per step

@@ -25,6 +25,7 @@
 #include "engine.hpp"
 #include "team.hpp"
 #include "sampler_dev.hpp"
+#include "optim_dev.hpp"
 
 namespace kge {
 
@@ -44,6 +45,8 @@ struct CtWork {
     uint32_t *rec = nullptr;
     float *hub_sums = nullptr;         // deterministic float-record reduce: per-copy sums of the relation-side rows
     size_t hub_sums_cap = 0;
+    int32_t *hub_marks = nullptr;      // lazy-Adam form of it: [copy][hub row] 1 = the copy took a record this step (zero between steps)
+    size_t hub_marks_cap = 0;
     int32_t *dst = nullptr, *dst_sorted = nullptr, *ids = nullptr, *ids_sorted = nullptr;
     int32_t *n_valid = nullptr;
     int32_t *tile_hist = nullptr, *bucket_start = nullptr;   // LDS-bucket path: bucket totals + cursors, bucket starts
@@ -773,6 +776,152 @@ __global__ __launch_bounds__(256) void hub_fold_det_kernel(float *__restrict__ h
     }
 }
 
+// Lazy-Adam form of the deterministic sum (kge_forward_backward_adam_rows / kge_float_records_apply_adam): same order of every sum,
+// but a row's COMPLETE sum ends in adam_one on the row's p, m and v instead of p += scale * sum.  Adam is not linear in the
+// gradient, so nothing is applied from a partial sum and nothing is added atomically: an entity-side row has one run and is updated
+// by the team that summed it; a relation-side row's copies go to hub_sums, each copy that took a record sets hub_marks[copy][row],
+// and hub_fold_adam_kernel folds the marked copies in copy order and applies the rule once per row.  A row is touched iff a record
+// carries one of its keys -- the mark decides, not `sum != 0`: a touched row's zero-gradient elements decay m and v and move p too
+// (the rule of kge_transe_apply_rows_adam_lazy), a row without a record keeps p, m and v bit for bit.
+// A lane holds C groups of V consecutive floats (V = 4: float4 loads and stores, D % 4 == 0; V = 1: any D).
+__global__ void blank_keys_kernel(int32_t *dst, long long M, int sentinel) {   // keys < 0 or >= rows carry no record: all sort last
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < M; i += (long long)gridDim.x * blockDim.x)
+        if ((unsigned)dst[i] > (unsigned)sentinel) dst[i] = sentinel;
+}
+
+template <int V> struct RowVec;
+template <> struct RowVec<1> {
+    float x[1];
+    __device__ __forceinline__ void load(const float *p) { x[0] = p[0]; }
+    __device__ __forceinline__ void store(float *p) const { p[0] = x[0]; }
+};
+template <> struct RowVec<4> {
+    float x[4];
+    __device__ __forceinline__ void load(const float *p) { const float4 q = *reinterpret_cast<const float4 *>(p); x[0] = q.x; x[1] = q.y; x[2] = q.z; x[3] = q.w; }
+    __device__ __forceinline__ void store(float *p) const { *reinterpret_cast<float4 *>(p) = make_float4(x[0], x[1], x[2], x[3]); }
+};
+
+// where virtual row `row` (< hub_base) or hub row `q` lives: table index into AdamRows::m / v and the row's element offset
+__device__ __forceinline__ float *adam_row_ptrs(const FloatRowSpace &rs, const AdamRows &ad, bool hub, long long row, int D, float *&m, float *&v) {
+    int t;
+    long long r;
+    if (!hub) { t = row < rs.E ? 0 : 3; r = row < rs.E ? row : row - rs.E; }
+    else { t = row < rs.R ? 1 : 2; r = row < rs.R ? row : row - rs.R; }
+    m = ad.m[t] + r * D;
+    v = ad.v[t] + r * D;
+    return (t == 0 ? rs.g_ent : t == 1 ? rs.g_rel : t == 2 ? rs.g_auxr : rs.g_auxe) + r * D;
+}
+
+template <int L, int C, int V>
+__device__ __forceinline__ void adam_row_apply(float *p, float *m, float *v, const RowVec<V> (&g)[C], int lane, int D, const AdamRows &ad) {
+    RowVec<V> pv[C], mv[C], vv[C];
+#pragma unroll
+    for (int c = 0; c < C; c++) {
+        const int e = (lane + L * c) * V;
+        if (e < D) { pv[c].load(p + e); mv[c].load(m + e); vv[c].load(v + e); }
+    }
+#pragma unroll
+    for (int c = 0; c < C; c++) {
+        const int e = (lane + L * c) * V;
+        if (e < D) {
+#pragma unroll
+            for (int k = 0; k < V; k++) adam_one(pv[c].x[k], mv[c].x[k], vv[c].x[k], g[c].x[k], ad.lr_t, ad.b1, ad.b2, ad.eps);
+            pv[c].store(p + e); mv[c].store(m + e); vv[c].store(v + e);
+        }
+    }
+}
+
+template <int L, int C, int V>
+__global__ __launch_bounds__(256) void segsum_adam_runs_kernel(const float *__restrict__ rec, const int32_t *__restrict__ keys,
+                                                               const int32_t *__restrict__ ids, const int32_t *__restrict__ n_valid_p,
+                                                               FloatRowSpace rs, AdamRows ad, int D, float *__restrict__ hub_sums,
+                                                               int32_t *__restrict__ hub_marks) {
+    constexpr int TEAMS = 256 / L;
+    const int lane = threadIdx.x % L;
+    const int n_valid = n_valid_p[0];
+    for (long long i = (long long)blockIdx.x * TEAMS + threadIdx.x / L; i < n_valid; i += (long long)gridDim.x * TEAMS) {
+        const int key = keys[i];
+        if (i > 0 && keys[i - 1] == key) continue;           // not the first record of its run
+        RowVec<V> acc[C];
+#pragma unroll
+        for (int c = 0; c < C; c++)
+#pragma unroll
+            for (int k = 0; k < V; k++) acc[c].x[k] = 0.f;
+        long long j = i;
+        int id = ids[j];
+        bool more;
+        do {                                                 // the run in record order; the next record's key and id are fetched beside this one's row
+            const float *p = rec + (long long)id * D;
+            more = j + 1 < n_valid && keys[j + 1] == key;
+            const int next_id = more ? ids[j + 1] : 0;
+#pragma unroll
+            for (int c = 0; c < C; c++) {
+                const int e = (lane + L * c) * V;
+                if (e < D) {
+                    RowVec<V> x;
+                    x.load(p + e);
+#pragma unroll
+                    for (int k = 0; k < V; k++) acc[c].x[k] += x.x[k];
+                }
+            }
+            id = next_id;
+            j++;
+        } while (more);
+        if (key < rs.hub_base) {
+            float *m, *v;
+            float *p = adam_row_ptrs(rs, ad, false, key, D, m, v);
+            adam_row_apply<L, C, V>(p, m, v, acc, lane, D, ad);
+        } else {
+            float *p = hub_sums + (long long)(key - rs.hub_base) * D;
+#pragma unroll
+            for (int c = 0; c < C; c++) { const int e = (lane + L * c) * V; if (e < D) acc[c].store(p + e); }
+            if (lane == 0) hub_marks[key - rs.hub_base] = 1;
+        }
+    }
+}
+
+// relation-side rows: one team per row adds the copies that took a record, in copy order, applies the rule to the whole row and
+// leaves hub_sums and hub_marks zero for the next step
+template <int L, int C, int V>
+__global__ __launch_bounds__(256) void hub_fold_adam_kernel(float *__restrict__ hub_sums, int32_t *__restrict__ hub_marks, FloatRowSpace rs,
+                                                            AdamRows ad, int D, int K) {
+    constexpr int TEAMS = 256 / L;
+    const int lane = threadIdx.x % L;
+    for (long long q = (long long)blockIdx.x * TEAMS + threadIdx.x / L; q < rs.hub_rows; q += (long long)gridDim.x * TEAMS) {
+        RowVec<V> acc[C];
+#pragma unroll
+        for (int c = 0; c < C; c++)
+#pragma unroll
+            for (int k = 0; k < V; k++) acc[c].x[k] = 0.f;
+        bool any = false;
+#pragma unroll 4
+        for (int k = 0; k < K; k++) {
+            const long long slot = (long long)k * rs.hub_rows + q;
+            const bool marked = hub_marks[slot] != 0;        // (the same for every lane of the team)
+            any = any || marked;
+            float *s = hub_sums + slot * D;
+#pragma unroll
+            for (int c = 0; c < C; c++) {
+                const int e = (lane + L * c) * V;
+                if (e < D && marked) {
+                    RowVec<V> x, z;
+                    x.load(s + e);
+#pragma unroll
+                    for (int u = 0; u < V; u++) { acc[c].x[u] += x.x[u]; z.x[u] = 0.f; }
+                    z.store(s + e);
+                }
+            }
+        }
+        if (!any) continue;
+        // every lane has consumed the marks it read (the branch above depends on them) before lane 0 clears them
+        if (lane == 0)
+            for (int k = 0; k < K; k++) hub_marks[(long long)k * rs.hub_rows + q] = 0;
+        float *m, *v;
+        float *p = adam_row_ptrs(rs, ad, true, q, D, m, v);
+        adam_row_apply<L, C, V>(p, m, v, acc, lane, D, ad);
+    }
+}
+
 // ---------------------------------------------------------------------------------------------
 // Pair-count path (TransH / TransD; stage 1 is pairs.hip's pair_emit_kernel): int8 sign records keyed by
 // (entity x, relation r) as x*R + r.  The records of a key are summed as integers; at the end of a run the
@@ -1051,6 +1200,68 @@ int float_records_reduce(int64_t M, int D, const FloatRowSpace &rs, hipStream_t 
     else if (D <= 128) KGE_SEGF(32, 4) else if (D <= 256) KGE_SEGF(64, 4) else if (D <= 512) KGE_SEGF(64, 8) else KGE_SEGF(64, 16)
 #undef KGE_SEGF
     return hip_check(hipGetLastError(), "float records reduce launch");
+}
+
+// rs.g_* are the PARAMETER tables, ad their moments (segsum_adam_runs_kernel).  The records are the workspace's, or the caller's
+// (read through local pointers: the workspace's own are not touched).
+int float_records_reduce_adam(int64_t M, int D, const FloatRowSpace &rs, const AdamRows &ad, hipStream_t stream, const float *rec_ext,
+                              int32_t *dst_ext) {
+    int rc;
+    const bool ext = rec_ext && dst_ext;
+    if ((rc = ensure_counts_work(M, ext ? 0 : (size_t)D))) return rc;
+    const float *rec = ext ? rec_ext : reinterpret_cast<const float *>(g_c.rec);
+    int32_t *dst = ext ? dst_ext : g_c.dst;
+    const int rows = (int)rs.rows;
+    int blocks = (int)((M + 255) / 256);
+    if (blocks > 4096) blocks = 4096;
+    hipLaunchKernelGGL(blank_keys_kernel, dim3(blocks), dim3(256), 0, stream, dst, (long long)M, rows);
+    size_t tmp = g_c.sort_tmp_bytes;
+    rc = hip_check(rocprim::radix_sort_pairs(g_c.sort_tmp, tmp, dst, g_c.dst_sorted, g_c.ids, g_c.ids_sorted, (size_t)M, 0,
+                                             bits_for_rows(rows), stream), "float records sort");
+    if (rc) return rc;
+    hipLaunchKernelGGL(count_valid_kernel, dim3(1), dim3(64), 0, stream, g_c.dst_sorted, (int)M, rows, g_c.n_valid);
+    const int64_t hub_virtual = rs.rows - rs.hub_base;          // copies x hub rows
+    const int K = rs.hub_rows > 0 ? (int)(hub_virtual / rs.hub_rows) : 0;
+    const size_t need = (size_t)hub_virtual * D;
+    if (need > g_c.hub_sums_cap) {
+        if ((rc = regrow(g_c.hub_sums, need, "hub copy sums"))) return rc;
+        if ((rc = hip_check(hipMemsetAsync(g_c.hub_sums, 0, sizeof(float) * need, stream), "zero hub copy sums"))) return rc;
+        g_c.hub_sums_cap = need;
+    }
+    if ((size_t)hub_virtual > g_c.hub_marks_cap) {
+        if ((rc = regrow(g_c.hub_marks, (size_t)hub_virtual, "hub copy marks"))) return rc;
+        if ((rc = hip_check(hipMemsetAsync(g_c.hub_marks, 0, sizeof(int32_t) * (size_t)hub_virtual, stream), "zero hub copy marks"))) return rc;
+        g_c.hub_marks_cap = (size_t)hub_virtual;
+    }
+    // float4 rows where every row of every buffer starts on 16 bytes
+    bool vec = D % 4 == 0 && (reinterpret_cast<uintptr_t>(rec) & 15) == 0;
+    const float *const bases[4] = {rs.g_ent, rs.g_rel, rs.g_auxr, rs.g_auxe};
+    for (int t = 0; t < 4; t++)
+        vec = vec && ((reinterpret_cast<uintptr_t>(bases[t]) | reinterpret_cast<uintptr_t>(ad.m[t]) | reinterpret_cast<uintptr_t>(ad.v[t])) & 15) == 0;
+#define KGE_SEGA(LL, CC, VV)                                                                                          \
+    {                                                                                                                 \
+        long long nb = (M + (256 / LL) - 1) / (256 / LL);                                                             \
+        if (nb > 16384) nb = 16384;                                                                                   \
+        hipLaunchKernelGGL((segsum_adam_runs_kernel<LL, CC, VV>), dim3((unsigned)nb), dim3(256), 0, stream, rec, g_c.dst_sorted, \
+                           g_c.ids_sorted, g_c.n_valid, rs, ad, D, g_c.hub_sums, g_c.hub_marks);                      \
+        if (K > 0) {                                                                                                  \
+            long long nf = (rs.hub_rows + (256 / LL) - 1) / (256 / LL);                                               \
+            if (nf > 16384) nf = 16384;                                                                               \
+            hipLaunchKernelGGL((hub_fold_adam_kernel<LL, CC, VV>), dim3((unsigned)nf), dim3(256), 0, stream, g_c.hub_sums, g_c.hub_marks, \
+                               rs, ad, D, K);                                                                         \
+        }                                                                                                             \
+    }
+    const int units = vec ? D / 4 : D;       // groups of V floats per row
+    if (vec) {
+        if (units <= 16) KGE_SEGA(16, 1, 4) else if (units <= 32) KGE_SEGA(16, 2, 4) else if (units <= 64) KGE_SEGA(16, 4, 4)
+        else if (units <= 128) KGE_SEGA(32, 4, 4) else KGE_SEGA(64, 4, 4)
+    } else {
+        if (units <= 16) KGE_SEGA(16, 1, 1) else if (units <= 32) KGE_SEGA(16, 2, 1) else if (units <= 64) KGE_SEGA(16, 4, 1)
+        else if (units <= 128) KGE_SEGA(32, 4, 1) else if (units <= 256) KGE_SEGA(64, 4, 1) else if (units <= 512) KGE_SEGA(64, 8, 1)
+        else KGE_SEGA(64, 16, 1)
+    }
+#undef KGE_SEGA
+    return hip_check(hipGetLastError(), "float records lazy Adam reduce launch");
 }
 
 // ---- pair-count path, host side (see segsum_pairs_kernel) ----

@@ -73,7 +73,9 @@ def parse_args(argv=None):
     p.add_argument("--sparse_rows", type=int, default=-1, help="1 / 0: force / forbid the touched-rows-only update: TransE int8 records (SGD, or the opt-in non-parity "
                                                              "--optimizer LazyAdam; on N ranks the entity table is sharded by row range and each rank checkpoints its own rows "
                                                              "and moments), TransH / TransD float records "
-                                                             "added to the parameter rows in place (SGD, one process).  Default: automatic for large tables")
+                                                             "applied to the parameter rows in place (SGD, or --optimizer LazyAdam: the Adam rule on the rows a step "
+                                                             "touches and on their moments; tables and moments replicated across ranks).  Default: automatic for "
+                                                             "large tables; LazyAdam always takes the touched-rows update")
     return p.parse_args(argv)
 
 

@@ -24,7 +24,8 @@ def main():
     ap.add_argument("--ent-exponent", type=float, default=0.8, help="Zipf exponent of entity popularity (0 = uniform)")
     ap.add_argument("--dense", action="store_true", help="dense count image instead of the sparse-row path")
     ap.add_argument("--force-dp", action="store_true", help="one-rank RCCL group + Config.force_data_parallel: the table-sharded multi-GPU step, every exchange a copy")
-    ap.add_argument("--model", default="TransE", help="TransE | TransH | TransD (the latter two: --dense = gradient tables + sweep, else row-wise SGD in place)")
+    ap.add_argument("--model", default="TransE", help="TransE | TransH | TransD (the latter two: --dense = gradient tables + sweep, else the row-wise "
+                                                      "update in place from float records: SGD, or with --opt LazyAdam the Adam rule on the touched rows)")
     ap.add_argument("--opt", default="SGD", help="SGD | Adam (TF1 dense sweep, parity; implies --dense) | LazyAdam (touched rows only, NON-PARITY)")
     a = ap.parse_args()
     import numpy as np
@@ -78,7 +79,11 @@ def main():
     B = con.batch_size
     print(json.dumps({"workload": "synthetic KG %dM entities / %dM triples %s dim=%d %s %d neg/pos, %s" % (
         a.entities // 1_000_000, a.triples // 1_000_000, a.model, a.dim, a.opt, a.neg,
-        ("dense image / gradient tables + sweep" if (a.dense or a.opt == "Adam") else "sparse rows") + (", table-sharded step on a one-rank RCCL group" if a.force_dp else "")),
+        ("dense image / gradient tables + sweep" if (a.dense or a.opt == "Adam") else
+         "sparse rows: lazy Adam in place from float records" if (con.sparse_inplace and con._lazy_adam) else
+         "sparse rows: SGD in place from float records" if con.sparse_inplace else "sparse rows") +
+        (", data-parallel step on a one-rank RCCL group" if a.force_dp and con.sparse_inplace else
+         ", table-sharded step on a one-rank RCCL group" if a.force_dp else "")),
         "ent_exponent": a.ent_exponent, "batch": B, "ms_per_step": 1e3 * dt / a.steps, "positives_per_s": B * a.steps / dt, "loss": float(loss.item()),
         "hbm_allocated_GB": torch.cuda.max_memory_allocated() / 1e9,
         "seconds": {"generate": round(t_gen, 1), "index": round(t_index, 1), "table_init": round(t_init, 1)}}))
