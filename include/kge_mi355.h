@@ -584,6 +584,30 @@ int kge_relation_prediction(const kge_model_desc *m, const float *const tables[K
 int kge_relation_prediction_rows(const kge_model_desc *m, const float *const tables[KGE_MAX_TABLES], const float *d_query_rows,
                                  INT first, INT count, int64_t *d_counts, void *stream);
 
+/* ---- Triple classification on the device (csrc/tclass.hip): getBestThreshold / test_triple_classification over DEVICE score
+ * arrays, with the host routines' bits.  Scores are fp32 in the order of the validation / test list (sorted by relation, the
+ * order getValidBatch / getTestBatch fill).  Need importTestFiles: before it, KGE_ERR_NO_DATASET with the host routines' message.
+ * KGE_ERR_NO_DEVICE without a GPU, KGE_ERR_BAD_ARG for a null array or a size that is not the split's total.
+ *
+ * kge_tc_fit: d_thresh[r] (DEVICE fp32 [rel_total]) = getBestThreshold's threshold of every relation with validation triples
+ *   -- the lowest grid point fmaf(i, 0.01f, min), i = 0..n_interval, of the best float accuracy -- and is left untouched for the
+ *   others.  d_n_interval (DEVICE int32 [rel_total], or NULL) receives get_n_interval's value of every relation (0 without
+ *   validation triples).  n_valid must be getValidTotal().  A non-finite score (the host's INT conversion is undefined there) is
+ *   KGE_ERR_BAD_ARG, a relation whose n_interval is 2^24 or more, or grids needing more than 2^28 histogram bins together,
+ *   KGE_ERR_UNSUPPORTED; in these cases NO threshold is written and d_n_interval is left untouched too.  Those return codes come from the scores, so the call waits
+ *   ONCE on `stream`, behind its min / max pass, for a 16-byte status; the binning, prefix sums and arg-max that follow are
+ *   enqueued and not waited for, and no other stream is touched.  The fit's working state (per-relation ranges, the global
+ *   histogram, the status word) is one per process: ONE kge_tc_fit at a time -- do not call it from two threads or enqueue
+ *   fits on two streams that may run concurrently.
+ * kge_tc_apply: split 0 = validation scores, 1 = test scores (n = that list's total).  d_counts (DEVICE int64 [4], written) =
+ *   TP, TN, FP, FN over the relations that have both validation and split triples (Test.h:353), a positive counted right when
+ *   score <= d_thresh[r], a negative when score > d_thresh[r]; d_rel (DEVICE int64 [rel_total][2] or NULL, written) = each
+ *   relation's right answers and answers (0, 0 for a relation left out).  Integer sums: the same for any order.  No host
+ *   synchronisation. */
+int kge_tc_fit(const float *d_pos, const float *d_neg, INT n_valid, float *d_thresh, int32_t *d_n_interval, void *stream);
+int kge_tc_apply(INT split, const float *d_thresh, const float *d_pos, const float *d_neg, INT n, int64_t *d_counts, int64_t *d_rel,
+                 void *stream);
+
 /* predict op: score n triples.  TransE: mean over the dimension (TransE.py:58); others: sum
  * (TransH.py:82, TransR.py:87 with predict_r[0]'s matrix for all, TransD.py:98). */
 int kge_predict(const kge_model_desc *m, const float *const tables[KGE_MAX_TABLES], const int32_t *d_h,

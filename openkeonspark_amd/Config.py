@@ -1367,6 +1367,21 @@ class Config(object):
         res_neg = np.ascontiguousarray(self.test_step(self.valid_neg_h, self.valid_neg_t, self.valid_neg_r).reshape(-1), dtype=np.float32)
         L.getBestThreshold(self.relThresh_addr, res_pos.ctypes.data, res_neg.ctypes.data)
 
+    def _test_triple_classification_host(self):
+        """The host path (Config.py:491-503): thresholds from the validation scores, then the reference's routine on the test
+        scores, which prints its four lines and gives the accuracy."""
+        if not hasattr(self, "test_pos_h"):
+            self.init_triple_classification()
+        L = self.lib
+        self._fit_thresholds()
+        L.getTestBatch(self.test_pos_h_addr, self.test_pos_t_addr, self.test_pos_r_addr,
+                       self.test_neg_h_addr, self.test_neg_t_addr, self.test_neg_r_addr)
+        res_pos = np.ascontiguousarray(self.test_step(self.test_pos_h, self.test_pos_t, self.test_pos_r).reshape(-1), dtype=np.float32)
+        res_neg = np.ascontiguousarray(self.test_step(self.test_neg_h, self.test_neg_t, self.test_neg_r).reshape(-1), dtype=np.float32)
+        L.test_triple_classification(self.relThresh_addr, res_pos.ctypes.data, res_neg.ctypes.data, self.acc_addr)
+        _lib.raise_if_error(L)
+        return float(self.acc[0])
+
     def test(self):
         """Triple classification on the test set with thresholds fitted on the validation set, and / or link prediction,
         as the flags say (Config.py:491-516).  Returns a dict: {"acc": ..} and / or the link-prediction metrics."""
@@ -1374,23 +1389,131 @@ class Config(object):
         t0 = time.time()
         result = {}
         if self.test_triple_classification:
-            if not hasattr(self, "test_pos_h"):
-                self.init_triple_classification()
-            L = self.lib
-            self._fit_thresholds()
-            L.getTestBatch(self.test_pos_h_addr, self.test_pos_t_addr, self.test_pos_r_addr,
-                           self.test_neg_h_addr, self.test_neg_t_addr, self.test_neg_r_addr)
-            res_pos = np.ascontiguousarray(self.test_step(self.test_pos_h, self.test_pos_t, self.test_pos_r).reshape(-1), dtype=np.float32)
-            res_neg = np.ascontiguousarray(self.test_step(self.test_neg_h, self.test_neg_t, self.test_neg_r).reshape(-1), dtype=np.float32)
-            L.test_triple_classification(self.relThresh_addr, res_pos.ctypes.data, res_neg.ctypes.data, self.acc_addr)
-            _lib.raise_if_error(L)
-            result["acc"] = float(self.acc[0])
+            result["acc"] = self._test_triple_classification_host()
         if self.test_link_prediction:
             result.update(self.link_prediction()[1])
         if self.test_relation_prediction:
             result.update(self.relation_prediction()[1])
         print("\nElapsed test time (seconds): {}".format(time.time() - t0))
         return result
+
+    # ---- triple classification on the device (csrc/tclass.hip) ----
+    def _tc_upload(self, cols):
+        """Six int64 id arrays (positives h, t, r; negatives h, t, r) -> one int32 device tensor [6, n], checked like test_step's."""
+        import torch
+        host = np.stack([np.asarray(c) for c in cols]).astype(np.int32)
+        self._check_ids(host[:3])
+        self._check_ids(host[3:])
+        return torch.from_numpy(host).to(self.device)
+
+    def _tc_scores(self, ids):
+        """kge_predict over the positives and over the negatives of an uploaded batch, each in ONE call of the whole length as
+        test_step makes it (the same arguments, so the same score bits) -> (pos, neg) device tensors."""
+        import torch
+        n = ids.shape[1]
+        out = torch.empty((2, n), dtype=torch.float32, device=self.device)
+        for side in range(2):
+            _lib.check(self.lib.kge_predict(ctypes.byref(self._desc), self._tab_ptrs, ids[3 * side].data_ptr(), ids[3 * side + 1].data_ptr(),
+                                            ids[3 * side + 2].data_ptr(), n, out[side].data_ptr(), self._stream()), self.lib)
+        return out
+
+    def _tc_result_buffer(self):
+        """One device allocation read back in one copy: int64 TP, TN, FP, FN followed by the fp32 thresholds."""
+        import torch
+        if getattr(self, "_tc_buf", None) is None or self._tc_buf.numel() != 32 + 4 * self.relTotal:
+            self._tc_buf = torch.zeros(32 + 4 * self.relTotal, dtype=torch.uint8, device=self.device)
+        return self._tc_buf, self._tc_buf[:32].view(torch.int64), self._tc_buf[32:].view(torch.float32)
+
+    def _tc_fit_apply(self, valid_ids, split_ids, split):
+        """predict -> kge_tc_fit -> (predict) -> kge_tc_apply on the current stream; the device thresholds and counts."""
+        buf, counts, thresh = self._tc_result_buffer()
+        st = self._stream()
+        v = self._tc_scores(valid_ids)
+        n_valid = valid_ids.shape[1]
+        _lib.check(self.lib.kge_tc_fit(v[0].data_ptr(), v[1].data_ptr(), n_valid, thresh.data_ptr(), None, st), self.lib)
+        s = v if split_ids is valid_ids else self._tc_scores(split_ids)
+        _lib.check(self.lib.kge_tc_apply(split, thresh.data_ptr(), s[0].data_ptr(), s[1].data_ptr(), split_ids.shape[1],
+                                         counts.data_ptr(), None, st), self.lib)
+        return buf
+
+    def _validation_accuracy_host(self, valid):
+        ph, pt, pr, nh, nt, nr = valid
+        pos = np.ascontiguousarray(self.test_step(ph, pt, pr).reshape(-1), dtype=np.float32)
+        neg = np.ascontiguousarray(self.test_step(nh, nt, nr).reshape(-1), dtype=np.float32)
+        thresh = np.zeros(self.relTotal, np.float32)
+        self.lib.getBestThreshold(thresh.ctypes.data, pos.ctypes.data, neg.ctypes.data)
+        correct = (pos <= thresh[pr]).sum() + (neg > thresh[nr]).sum()
+        return float(correct) / (2.0 * max(len(pos), 1))
+
+    def validation_accuracy(self, valid=None):
+        """The early-stop check's accuracy (distribute_training.py:295-333): thresholds fitted on the validation triples and
+        their negatives, then the share of those 2 V answers the thresholds get right -- correct / (2 V), the Python float the
+        host formula gives.  `valid` = the six id arrays getValidBatch filled (positives h, t, r; negatives h, t, r); None draws
+        them with getValidBatch on the first call.  The ids go to the device once and stay there for as long as the same
+        list object is passed -- its arrays must not be refilled in place (pass a new list for a new batch); scores, thresholds and counts never leave it, and only the four counts are read back.
+        On an entity table sharded across ranks this is the host path (test_step is a collective there): the scores come to
+        the host and getBestThreshold runs on them, as before."""
+        if valid is None:
+            valid = getattr(self, "_tc_valid_drawn", None)
+            if valid is None:
+                if not hasattr(self, "valid_pos_h"):
+                    self.init_valid_triple_classification()
+                self.lib.getValidBatch(self.valid_pos_h_addr, self.valid_pos_t_addr, self.valid_pos_r_addr,
+                                       self.valid_neg_h_addr, self.valid_neg_t_addr, self.valid_neg_r_addr)
+                _lib.raise_if_error(self.lib)
+                # copies: test() and triple_classification() draw new negatives into the same buffers
+                valid = self._tc_valid_drawn = [a.copy() for a in (self.valid_pos_h, self.valid_pos_t, self.valid_pos_r,
+                                                                   self.valid_neg_h, self.valid_neg_t, self.valid_neg_r)]
+        if self._sharded("ent_embeddings"):
+            return self._validation_accuracy_host(valid)
+        cached = getattr(self, "_tc_valid_dev", None)
+        if cached is None or cached[0] is not valid:
+            cached = self._tc_valid_dev = (valid, self._tc_upload(valid))
+        ids = cached[1]
+        if ids.shape[1] == 0:
+            return 0.0
+        counts = self._tc_fit_apply(ids, ids, 0)[:32].cpu().numpy().view(np.int64)
+        return float(int(counts[0]) + int(counts[1])) / (2.0 * max(ids.shape[1], 1))
+
+    def triple_classification(self, split="test"):
+        """Triple classification of a split ("test" or "valid") with thresholds fitted on the validation set, on the device:
+        {"acc", "precision", "recall", "f1", "tp", "tn", "fp", "fn"}.  The batches are drawn on the host exactly as test() draws
+        them (getValidBatch, then for "test" getTestBatch: the same libc rand() draws, the same negatives), uploaded once per call as
+        int32; kge_predict, kge_tc_fit and kge_tc_apply then run on one stream and a single copy brings back the four
+        counts and the thresholds, which fill self.relThresh for predict_triple.  "acc" is the float32 test() returns.
+        On an entity table sharded across ranks this is test()'s host path unchanged (test_step is a collective there): the
+        test split only, and the result holds "acc" alone, which is all the host routine returns."""
+        if split not in ("test", "valid"):
+            raise KgeError("triple_classification: split must be 'test' or 'valid'")
+        if self._sharded("ent_embeddings"):
+            if split != "test":
+                raise KgeError("triple_classification over an entity table sharded across ranks: the host path classifies the test split only")
+            return {"acc": self._test_triple_classification_host()}
+        if not hasattr(self, "test_pos_h"):
+            self.init_triple_classification()
+        L = self.lib
+        L.getValidBatch(self.valid_pos_h_addr, self.valid_pos_t_addr, self.valid_pos_r_addr,
+                        self.valid_neg_h_addr, self.valid_neg_t_addr, self.valid_neg_r_addr)
+        valid = [self.valid_pos_h, self.valid_pos_t, self.valid_pos_r, self.valid_neg_h, self.valid_neg_t, self.valid_neg_r]
+        batch = valid
+        if split == "test":
+            L.getTestBatch(self.test_pos_h_addr, self.test_pos_t_addr, self.test_pos_r_addr,
+                           self.test_neg_h_addr, self.test_neg_t_addr, self.test_neg_r_addr)
+            batch = [self.test_pos_h, self.test_pos_t, self.test_pos_r, self.test_neg_h, self.test_neg_t, self.test_neg_r]
+        _lib.raise_if_error(L)
+        import torch
+        valid_ids = self._tc_upload(valid)      # new negatives every call: nothing to keep beyond it
+        split_ids = self._tc_upload(batch) if split == "test" else valid_ids
+        _, _, thresh = self._tc_result_buffer()
+        thresh.copy_(torch.from_numpy(self.relThresh))     # relations without validation triples keep their value, as on the host
+        host = self._tc_fit_apply(valid_ids, split_ids, 1 if split == "test" else 0).cpu().numpy()
+        tp, tn, fp, fn = (int(x) for x in host[:32].view(np.int64))
+        self.relThresh[:] = host[32:].view(np.float32)
+        ratio = lambda a, b: a / b if b else float("nan")
+        precision, recall = ratio(1.0 * tp, tp + fp), ratio(1.0 * tp, tp + fn)
+        acc = ratio(1.0 * (tp + tn), tp + tn + fp + fn)
+        return {"acc": float(np.float32(acc)), "precision": precision, "recall": recall,
+                "f1": ratio(2 * precision * recall, precision + recall), "tp": tp, "tn": tn, "fp": fp, "fn": fn}
 
     def _top_k(self, scores, k):
         res = np.asarray(scores).reshape(-1).argsort()[:k]

@@ -46,6 +46,8 @@ static EvalDev g_ed;
 // ranges of the sorted valid / test lists (Reader.h:263-291)
 static std::vector<Int4> g_valid;
 static std::vector<int32_t> g_valid_lef, g_valid_rig, g_test_lef, g_test_rig;
+// bumped by every importTestFiles: tclass.hip keeps device copies of the four range arrays for as long as it stands
+static uint64_t g_tc_generation = 0;
 
 template <typename T, typename V>
 static int up(T *&dst, const std::vector<V> &src, const char *what) {
@@ -269,6 +271,7 @@ void importTestFiles(void) {
     g_eh = EvalHost();
     g_ed.uploaded = false;
     g_valid.clear();
+    g_tc_generation++;
     std::vector<int64_t> te, tr, va, tmp;
     const std::string &d = e.in_path;
     if (!read_all_longs(d + "relation2id.txt", tmp)) { set_error("`" + d + "relation2id.txt` does not exist"); return; }
@@ -741,3 +744,16 @@ int kge_link_prediction(const kge_model_desc *m, const float *const tables[KGE_M
 }
 
 }  // extern "C"
+
+namespace kge {
+
+uint64_t eval_tc_generation() { return g_tc_generation; }
+
+int eval_tc_lists(TcLists &v) {
+    if (!ensure_classification_lists()) return KGE_ERR_NO_DATASET;
+    v.lef[0] = &g_valid_lef; v.rig[0] = &g_valid_rig; v.lef[1] = &g_test_lef; v.rig[1] = &g_test_rig;
+    v.total[0] = g_eh.valid_total; v.total[1] = g_eh.test_total;
+    return KGE_OK;
+}
+
+}  // namespace kge

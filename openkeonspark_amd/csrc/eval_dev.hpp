@@ -25,6 +25,17 @@ struct EvalOntologyView {
 };
 int eval_ontology_view(EvalOntologyView &v);
 
+// triple classification (tclass.hip): the per-relation ranges [lef[r], rig[r]] (-1 / -1 without triples) of the validation
+// (index 0) and test (index 1) lists sorted by relation, as getBestThreshold / test_triple_classification read them, and the
+// lists' lengths.  Host vectors owned by eval.hip, rebuilt by the call; KGE_ERR_NO_DATASET (with the host routines' message)
+// before importTestFiles.  eval_tc_generation changes with every importTestFiles.
+struct TcLists {
+    const std::vector<int32_t> *lef[2], *rig[2];
+    int64_t total[2];
+};
+int eval_tc_lists(TcLists &v);
+uint64_t eval_tc_generation();
+
 // [lo, hi) of the entries whose first two fields are (a, b) in an array sorted by (x, y, z): the third fields of that
 // range are the known tails of (h, r) in `all`, the known heads of (t, r) in `all_t`, or the known relations of (h, t) in
 // `all_ht`, in increasing order

@@ -369,13 +369,9 @@ def _init_validation(con, argv):
 
 
 def _validation_accuracy(con, valid):
-    ph, pt, pr, nh, nt, nr = valid
-    pos = np.ascontiguousarray(con.test_step(ph, pt, pr).reshape(-1), dtype=np.float32)
-    neg = np.ascontiguousarray(con.test_step(nh, nt, nr).reshape(-1), dtype=np.float32)
-    thresh = np.zeros(con.relTotal, np.float32)
-    con.lib.getBestThreshold(thresh.ctypes.data, pos.ctypes.data, neg.ctypes.data)
-    correct = (pos <= thresh[pr]).sum() + (neg > thresh[nr]).sum()
-    return float(correct) / (2.0 * max(len(pos), 1))
+    """Thresholds fitted on the validation scores, then the share of the 2 V answers they get right: on the device
+    (Config.validation_accuracy: ids uploaded once, four counts read back), on the host where the entity table is sharded."""
+    return con.validation_accuracy(valid)
 
 
 def main_fun(argv):
