@@ -137,6 +137,9 @@ const char *kge_version(void);
  *                     G . M_r^T are stored as float records and summed per entity by the record sort + segmented sum from
  *                     `_min` (default 32768) projected rows per step on; 0 = fp32 atomics always
  *   "inv_carry": 0 = recompute that table in front of every emit launch (test hook; default 1)
+ *   "emit_rounds": 1 (default) = the TransE emit kernel at widths 132..256 (multiples of 4) walks a group's negatives in rounds
+ *                     of one corruption kind with raw buffer gathers and one merged reduction per round; 0 = its earlier body
+ *                     (kernel transe_emit_vec_v1_kernel), which computes the same bits: A/B measurements and the tests' reference
  *   "record_emit_event": 1 = record an event behind every TransE emit launch (kge_stream_wait_emit); default 0
  *   "pair_counts":       1 (default) = TransH / TransD steps of at least float_records_min entity-side rows (widths that are
  *                        multiples of 4 up to 256, at most 63 negatives, ent_total*rel_total below 2^31) take the
@@ -403,9 +406,16 @@ int kge_transe_apply_counts_range(const kge_model_desc *m, float *const d_p[2], 
  *   kge_transe_deferred_groups: groups of the last emit whose negatives were not sampler-shaped (each negative
  *                              differing from its positive in exactly one slot).  With residual accumulators they
  *                              were handled by the fp32 path; with d_resid_* == NULL they were SKIPPED and the
- *                              caller must treat a non-zero count as an error.  Synchronises. */
+ *                              caller must treat a non-zero count as an error.  Synchronises.
+ *   kge_transe_step_scratch_read: test hook.  Copies `count` 32-bit words from word `offset` of the engine-owned buffers the
+ *                              last kge_transe_forward_counts / kge_transe_train_step_counts call wrote to the host:
+ *                              which = 0 the records (3 * n_pos int8 records of kge_transe_record_dwords words each, then --
+ *                              the fused step at widths that are multiples of 4 -- the 2-bit record of negative k of group b
+ *                              as record k * n_pos + b of a quarter of that size), which = 1 the destination keys as the
+ *                              call left them (inactive slots hold its sentinel, the largest key).  Synchronises. */
 INT kge_transe_record_dwords(const kge_model_desc *m);
 int kge_transe_deferred_groups(int32_t *n_groups);
+int kge_transe_step_scratch_read(int which, INT offset, INT count, void *host_out);
 int kge_transe_emit_records(const kge_model_desc *m, const float *d_ent, const float *d_rel, const int32_t *d_h, const int32_t *d_t,
                             const int32_t *d_r, INT n_pos, INT n_neg, INT stride, INT denom, uint32_t *d_rec, int32_t *d_dst,
                             float *d_resid_ent, float *d_resid_rel, float *d_loss, void *stream);

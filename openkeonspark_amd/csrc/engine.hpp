@@ -68,6 +68,7 @@ struct Engine {
     int32_t *loss_limbs = nullptr;   // kge_loss_limbs_target: where the TransE emit kernel also writes its loss as limbs (null = nowhere)
     int counts_krel = 4;        // dense TransE path: virtual copies of the relation rows in the record sort (1 = none; measured 1/2/4/8/16/64: 4 best); a power of two
     int inv_carry = 1;          // 0 = always recompute the table in front of the emit kernel (test hook)
+    int emit_rounds = 1;        // TransE emit at 132 <= D <= 256: rounds of one corruption kind with merged reductions (models.hip transe_emit_rounds_body); 0 = the earlier body, as transe_emit_vec_v1_kernel (A/B runs, test reference)
     int64_t inv_table_max_bytes = int64_t(256) << 20;  // TransE emit: per-row inverse-norm table only while the tables are this small
     int float_records = 1;              // TransH / TransD (and TransE without counts): record + segmented-sum path instead of fp32 atomics
     int64_t float_records_min = 1 << 16; // ... from this many gradient rows per step (below it the atomic kernel alone is quicker)

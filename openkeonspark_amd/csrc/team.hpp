@@ -37,6 +37,32 @@ __device__ __forceinline__ float team_sum(float v) {
     return v;
 }
 
+// Four wave-wide sums in the instructions of little more than one (L == 64 only): the totals of a, b, c, d come back in lanes
+// 60, 61, 62, 63 of the result, each with the bits team_sum<64> returns for it.  odd = lane & 1, hi2 = lane & 2.
+//   steps 1-2  the two quad steps also transpose: after lane ^ 1, even lanes carry a's (c's) pair sums and odd lanes b's (d's);
+//              after lane ^ 2, lane q of every quad carries the quad sum of value q.  Every lane forms exactly the sum
+//              team_sum forms for the value it keeps (own + partner; at the lane ^ 2 step the operands come swapped, and
+//              an IEEE add is commutative);
+//   steps 3-4  the row rotations move a lane by multiples of four, so lane 4i + q stays with value q and gets the row sum in
+//              the association of quad i.  team_sum reads lane 63 and its row broadcasts read lanes 15 / 31 / 47: quad 3;
+//   steps 5-6  team_sum adds row 0 into row 1 and row 2 into row 3, then rows 0+1 into row 3: (R3 + R2) + (R1 + R0).
+//              row_bcast could only hand on ONE lane per row, so the four lanes 12..15 travel by row swaps instead
+//              (v_permlane16_swap / v_permlane32_swap on two copies of the register): odd rows meet even rows, then the
+//              upper half meets the lower half -- the same two adds with the same operands.
+__device__ __forceinline__ float team_sum4(float a, float b, float c, float d, bool odd, bool hi2) {
+    const float X = (odd ? b : a) + dpp_f<0xB1>(odd ? a : b);
+    const float Y = (odd ? d : c) + dpp_f<0xB1>(odd ? c : d);
+    float Z = (hi2 ? Y : X) + dpp_f<0x4E>(hi2 ? X : Y);
+    Z += dpp_f<0x124>(Z);
+    Z += dpp_f<0x128>(Z);
+    const unsigned z = __builtin_bit_cast(unsigned, Z);
+    const auto r16 = __builtin_amdgcn_permlane16_swap(z, z, false, false);   // [0]: rows 0 0 2 2, [1]: rows 1 1 3 3
+    const float W = __builtin_bit_cast(float, (unsigned)r16[1]) + __builtin_bit_cast(float, (unsigned)r16[0]);
+    const unsigned w = __builtin_bit_cast(unsigned, W);
+    const auto r32 = __builtin_amdgcn_permlane32_swap(w, w, false, false);   // [0]: rows 0+1 everywhere, [1]: rows 2+3
+    return __builtin_bit_cast(float, (unsigned)r32[1]) + __builtin_bit_cast(float, (unsigned)r32[0]);
+}
+
 // 1/sqrt(x) for x >= 1e-12: the hardware estimate (1 ulp) refined by one Newton step -- 5 instructions where the IEEE
 // sqrt + divide sequence takes ~25 (it sits in the per-negative path of the pair-count kernels; results agree with
 // 1.0f / sqrtf(x) to the last bit or two, far inside the 1e-5 parity tolerance)

@@ -1928,6 +1928,17 @@ int kge_transe_emit_records(const kge_model_desc *m, const float *d_ent, const f
                               d_loss, stream, true);
 }
 
+int kge_transe_step_scratch_read(int which, INT offset, INT count, void *host_out) {
+    if (!device_ok()) return fail(KGE_ERR_NO_DEVICE, "kge_transe_step_scratch_read: no usable HIP device");
+    const size_t have = which == 0 ? g_c.rec_elems : (which == 1 ? (size_t)g_c.cap_idx : 0);
+    const void *base = which == 0 ? (const void *)g_c.rec : (const void *)g_c.dst;
+    if (!host_out || offset < 0 || count < 0 || (size_t)offset + (size_t)count > have || !base)
+        return fail(KGE_ERR_BAD_ARG, "kge_transe_step_scratch_read: bad arguments");
+    int rc = hip_check(hipDeviceSynchronize(), "kge_transe_step_scratch_read: synchronize");
+    if (rc) return rc;
+    return hip_check(hipMemcpy(host_out, (const char *)base + 4 * (size_t)offset, 4 * (size_t)count, hipMemcpyDeviceToHost), "kge_transe_step_scratch_read: copy");
+}
+
 int kge_transe_deferred_groups(int32_t *n_groups) {
     if (!n_groups) return fail(KGE_ERR_BAD_ARG, "kge_transe_deferred_groups: null output");
     return transe_deferred_groups(n_groups);
