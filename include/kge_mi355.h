@@ -618,6 +618,32 @@ int kge_tc_fit(const float *d_pos, const float *d_neg, INT n_valid, float *d_thr
 int kge_tc_apply(INT split, const float *d_thresh, const float *d_pos, const float *d_neg, INT n, int64_t *d_counts, int64_t *d_rel,
                  void *stream);
 
+/* kge_tc_roc: get_TPFP's counts for EVERY relation at once, and the exact area under each relation's ROC polyline.  d_vpos /
+ *   d_vneg = the validation scores (n_valid = getValidTotal()): they give each relation's grid g(i) = fmaf(i, 0.01f, min),
+ *   i = 0..n_interval, kge_tc_fit's grid bit for bit.  split 0 = validation list, 1 = test list; d_pos / d_neg = that list's
+ *   scores, n = its total (split 0 may pass the validation arrays again).
+ *   h_offsets (HOST int64 [rel_total + 1], written before the call returns) = prefix sums of 2 * (n_interval + 1) over the
+ *   relations with validation triples; a relation without them has an empty slice.
+ *   d_tpfp (DEVICE int64, or NULL for the areas alone): d_tpfp[h_offsets[r] .. h_offsets[r + 1]) = get_TPFP(r)'s layout,
+ *   TP(0..n_interval) then FP(0..n_interval), TP(i) / FP(i) = the relation's split positives / negatives with score <= g(i);
+ *   zeros for a relation with validation but no split triples (as the host get_TPFP of this library gives).  tpfp_capacity =
+ *   the int64 elements d_tpfp holds: below h_offsets[rel_total] is KGE_ERR_BAD_ARG, with h_offsets filled so that the caller
+ *   can size the buffer.
+ *   d_auc2 (DEVICE int64 [rel_total][2], every element written) = (area2, n_r) for a relation with validation AND split
+ *   triples, (0, 0) otherwise: n_r = its triples in the split, area2 = twice the trapezoid area, in counts, under the polyline
+ *   (0,0), (FP(0),TP(0)), ..., (FP(n_interval),TP(n_interval)), (n_r,n_r), so AUC = area2 / (2 n_r^2).  An integer sum: the
+ *   same for any order of arrival.
+ *   Errors as kge_tc_fit's (KGE_ERR_NO_DATASET, KGE_ERR_NO_DEVICE, KGE_ERR_BAD_ARG for a null array, a wrong size, a split
+ *   outside {0, 1} or a non-finite validation score, KGE_ERR_UNSUPPORTED for a grid of 2^24 points or more or more than 2^28
+ *   int32 histogram bins, hpos and hneg counted, over the relations on the global path); a non-finite score in the split is
+ *   KGE_ERR_BAD_ARG too.  On every error NO device output is written.  The call waits ONCE on `stream`, where the fit
+ *   waits: behind the min / max pass over the validation scores and a finiteness pass over the split's, for the status and
+ *   every relation's n_interval; the binning, the prefix sums and the writes that follow are enqueued and not waited for.
+ *   It works in the fit's per-process state (ranges, global histogram, status word), so the fit's rule covers it: ONE
+ *   kge_tc_fit or kge_tc_roc at a time -- not from two threads, not enqueued on two streams that may run concurrently. */
+int kge_tc_roc(const float *d_vpos, const float *d_vneg, INT n_valid, INT split, const float *d_pos, const float *d_neg, INT n,
+               int64_t *d_auc2, int64_t *d_tpfp, INT tpfp_capacity, int64_t *h_offsets, void *stream);
+
 /* predict op: score n triples.  TransE: mean over the dimension (TransE.py:58); others: sum
  * (TransH.py:82, TransR.py:87 with predict_r[0]'s matrix for all, TransD.py:98). */
 int kge_predict(const kge_model_desc *m, const float *const tables[KGE_MAX_TABLES], const int32_t *d_h,

@@ -1475,6 +1475,24 @@ class Config(object):
         counts = self._tc_fit_apply(ids, ids, 0)[:32].cpu().numpy().view(np.int64)
         return float(int(counts[0]) + int(counts[1])) / (2.0 * max(ids.shape[1], 1))
 
+    def _tc_draw(self, split):
+        """The batches of a device classification call, drawn exactly as test() draws them (getValidBatch, then for "test"
+        getTestBatch) and uploaded once -> (valid ids, split ids), the same tensor for "valid"."""
+        if not hasattr(self, "test_pos_h"):
+            self.init_triple_classification()
+        L = self.lib
+        L.getValidBatch(self.valid_pos_h_addr, self.valid_pos_t_addr, self.valid_pos_r_addr,
+                        self.valid_neg_h_addr, self.valid_neg_t_addr, self.valid_neg_r_addr)
+        valid = [self.valid_pos_h, self.valid_pos_t, self.valid_pos_r, self.valid_neg_h, self.valid_neg_t, self.valid_neg_r]
+        batch = valid
+        if split == "test":
+            L.getTestBatch(self.test_pos_h_addr, self.test_pos_t_addr, self.test_pos_r_addr,
+                           self.test_neg_h_addr, self.test_neg_t_addr, self.test_neg_r_addr)
+            batch = [self.test_pos_h, self.test_pos_t, self.test_pos_r, self.test_neg_h, self.test_neg_t, self.test_neg_r]
+        _lib.raise_if_error(L)
+        valid_ids = self._tc_upload(valid)      # new negatives every call: nothing to keep beyond it
+        return valid_ids, (self._tc_upload(batch) if split == "test" else valid_ids)
+
     def triple_classification(self, split="test"):
         """Triple classification of a split ("test" or "valid") with thresholds fitted on the validation set, on the device:
         {"acc", "precision", "recall", "f1", "tp", "tn", "fp", "fn"}.  The batches are drawn on the host exactly as test() draws
@@ -1489,21 +1507,8 @@ class Config(object):
             if split != "test":
                 raise KgeError("triple_classification over an entity table sharded across ranks: the host path classifies the test split only")
             return {"acc": self._test_triple_classification_host()}
-        if not hasattr(self, "test_pos_h"):
-            self.init_triple_classification()
-        L = self.lib
-        L.getValidBatch(self.valid_pos_h_addr, self.valid_pos_t_addr, self.valid_pos_r_addr,
-                        self.valid_neg_h_addr, self.valid_neg_t_addr, self.valid_neg_r_addr)
-        valid = [self.valid_pos_h, self.valid_pos_t, self.valid_pos_r, self.valid_neg_h, self.valid_neg_t, self.valid_neg_r]
-        batch = valid
-        if split == "test":
-            L.getTestBatch(self.test_pos_h_addr, self.test_pos_t_addr, self.test_pos_r_addr,
-                           self.test_neg_h_addr, self.test_neg_t_addr, self.test_neg_r_addr)
-            batch = [self.test_pos_h, self.test_pos_t, self.test_pos_r, self.test_neg_h, self.test_neg_t, self.test_neg_r]
-        _lib.raise_if_error(L)
         import torch
-        valid_ids = self._tc_upload(valid)      # new negatives every call: nothing to keep beyond it
-        split_ids = self._tc_upload(batch) if split == "test" else valid_ids
+        valid_ids, split_ids = self._tc_draw(split)
         _, _, thresh = self._tc_result_buffer()
         thresh.copy_(torch.from_numpy(self.relThresh))     # relations without validation triples keep their value, as on the host
         host = self._tc_fit_apply(valid_ids, split_ids, 1 if split == "test" else 0).cpu().numpy()
@@ -1514,6 +1519,146 @@ class Config(object):
         acc = ratio(1.0 * (tp + tn), tp + tn + fp + fn)
         return {"acc": float(np.float32(acc)), "precision": precision, "recall": recall,
                 "f1": ratio(2 * precision * recall, precision + recall), "tp": tp, "tn": tn, "fp": fp, "fn": fn}
+
+    # ---- ROC curves and AUC on the device (kge_tc_roc, csrc/tclass.hip) ----
+    def _roc_device(self, split, rel_index=None):
+        """Draw and score as triple_classification(split) does, then kge_tc_roc for every relation at once ->
+        (auc2 [R, 2] int64 on the host, curve).  With rel_index a first call with an empty count buffer only reports the
+        sizes (it ends behind its wait, before any binning), a second fills a buffer of that size, and curve = (that
+        relation's get_TPFP counts, its n_interval, the minimum of its validation scores); without it curve is None and
+        only the [R][2] buffer is read back."""
+        import torch
+        if split not in ("test", "valid"):
+            raise KgeError("roc: split must be 'test' or 'valid'")
+        if self._sharded("ent_embeddings"):
+            raise KgeError("ROC curves over an entity table sharded across ranks would fetch the rows of every validation and "
+                           "test triple to one rank: triple_classification (the host path, a collective there) is what sharded tables have")
+        R = self.relTotal
+        if rel_index is not None and not 0 <= rel_index < R:      # before the draw: a refused call consumes no rand()
+            raise KgeError("roc_curve: relation %r out of range" % (rel_index,))
+        valid_ids, split_ids = self._tc_draw(split)
+        st = self._stream()
+        v = self._tc_scores(valid_ids)
+        s = v if split_ids is valid_ids else self._tc_scores(split_ids)
+        auc2 = torch.empty((R, 2), dtype=torch.int64, device=self.device)
+        offsets = np.zeros(R + 1, dtype=np.int64)
+
+        def call(tpfp, capacity):
+            return self.lib.kge_tc_roc(v[0].data_ptr(), v[1].data_ptr(), valid_ids.shape[1], 1 if split == "test" else 0,
+                                       s[0].data_ptr(), s[1].data_ptr(), split_ids.shape[1], auc2.data_ptr(),
+                                       tpfp.data_ptr() if tpfp is not None else None, capacity, offsets.ctypes.data, st)
+        if rel_index is None:
+            _lib.check(call(None, 0), self.lib)
+            return auc2.cpu().numpy(), None
+        # sizes first: a count buffer declared empty makes the call stop behind its one wait, h_offsets filled and nothing
+        # binned or written (a relation without validation triples is then refused before any binning too)
+        offsets[R] = -1
+        tpfp = torch.empty(1, dtype=torch.int64, device=self.device)
+        rc = call(tpfp, 0)
+        if offsets[R] < 0:
+            _lib.check(rc, self.lib)      # another error: its own message
+        self.lib.kge_clear_error()
+        lo, hi = int(offsets[rel_index]), int(offsets[rel_index + 1])
+        if hi == lo:
+            raise KgeError("roc_curve: relation %d has no validation triples, so no threshold grid" % rel_index)
+        tpfp = torch.empty(int(offsets[R]), dtype=torch.int64, device=self.device)
+        _lib.check(call(tpfp, tpfp.numel()), self.lib)
+        mask = valid_ids[2] == rel_index
+        mn = torch.minimum(v[0][mask].min(), v[1][mask].min()).cpu().numpy() + np.float32(0.0)      # -0 -> +0, as the kernel
+        return auc2.cpu().numpy(), (tpfp[lo:hi].cpu().numpy(), (hi - lo) // 2 - 1, np.float32(mn))
+
+    @staticmethod
+    def _grid_points(mn, n_interval):
+        """g(i) = fmaf((float)i, 0.01f, mn), i = 0..n_interval, with ONE rounding as the library forms it: the product is exact
+        in double, the sum is rounded to odd there (TwoSum gives its exact error), so the rounding to float32 is the correct one."""
+        p = np.arange(n_interval + 1, dtype=np.float64) * np.float64(np.float32(0.01))
+        b = np.float64(mn)
+        s = p + b
+        bb = s - p
+        err = (p - (s - bb)) + (b - bb)
+        even = (s.view(np.int64) & 1) == 0
+        s = np.where((err != 0) & even, np.nextafter(s, np.where(err > 0, np.inf, -np.inf)), s)
+        return s.astype(np.float32)
+
+    def roc_auc(self, split="test"):
+        """Area under every relation's ROC curve on a split ("test" or "valid"), on the device: {"auc": float64 [relTotal],
+        NaN for a relation without validation or without split triples, "n": int64 [relTotal] the relation's triples in the
+        split, "macro": the mean of the defined values, "weighted": sum n_r auc_r / sum n_r}.  The curve of relation r is
+        get_TPFP's: the split's positives (TP) and negatives (FP) at or below each point of the grid the validation scores span,
+        closed by (0, 0) and (n_r, n_r); auc_r = area2 / (2 n_r^2), one Python-float division of the exact integers kge_tc_roc
+        returns.  The batches are drawn exactly as triple_classification(split) draws them (the same libc rand() draws, the same
+        negatives), uploaded once, scored by one kge_predict per side, and one [relTotal][2] buffer is read back.
+        Raises KgeError on an entity table sharded across ranks."""
+        auc2, _ = self._roc_device(split)
+        n = auc2[:, 1].copy()
+        auc = np.array([int(a) / (2 * int(k) * int(k)) if k else float("nan") for a, k in auc2], dtype=np.float64).reshape(-1)
+        have = n > 0
+        macro = float(auc[have].mean()) if have.any() else float("nan")
+        weighted = float((n[have] * auc[have]).sum() / n[have].sum()) if have.any() else float("nan")
+        return {"auc": auc, "n": n, "macro": macro, "weighted": weighted}
+
+    def roc_curve(self, rel_index, split="test"):
+        """The ROC curve of one relation on a split: {"tp", "fp": int64 [n_interval + 1], get_TPFP's counts at every grid
+        point, "thresholds": the float32 grid points fmaf(i, 0.01f, min), "tpr", "fpr": the counts over the relation's OWN
+        number of split triples n_r (NaN when it has none), "auc": as roc_auc's, "n": n_r}.  Draws and scores as roc_auc does.
+        Raises KgeError for a relation without validation triples (where get_TPFP returns 0) and on a sharded entity table."""
+        auc2, (counts, n_interval, mn) = self._roc_device(split, int(rel_index))
+        tp, fp = counts[:n_interval + 1].copy(), counts[n_interval + 1:].copy()
+        area2, n_r = int(auc2[rel_index, 0]), int(auc2[rel_index, 1])
+        nan = float("nan")
+        with np.errstate(divide="ignore", invalid="ignore"):
+            tpr, fpr = (tp / np.float64(n_r), fp / np.float64(n_r)) if n_r else (np.full(len(tp), nan), np.full(len(fp), nan))
+        return {"tp": tp, "fp": fp, "thresholds": self._grid_points(mn, n_interval), "tpr": tpr, "fpr": fpr,
+                "auc": area2 / (2 * n_r * n_r) if n_r else nan, "n": n_r}
+
+    @staticmethod
+    def _roc_lists(counts, n_interval, total):
+        """The reference's TPR / FPR lists and area (Config.py:536-556) from get_TPFP's counts (TP(0..n) then FP(0..n)) ->
+        (TPR, FPR, auc): a (0, 0) start point unless the first grid point already counts nothing, the counts, an end point
+        (total, total) unless the last grid point already counts the whole list, every element divided by the last, np.trapz."""
+        res = [int(c) for c in counts]
+        TPR, FPR = [], []
+        if res[0] != 0 or res[0 + n_interval + 1] != 0:
+            TPR.append(0)
+            FPR.append(0)
+        for i in range(0, n_interval + 1):
+            TPR.append(res[i])
+            FPR.append(res[i + n_interval + 1])
+        if TPR[len(TPR) - 1] != total or FPR[len(FPR) - 1] != total:
+            TPR.append(total)
+            FPR.append(total)
+        for i in range(len(TPR)):
+            TPR[i] /= TPR[-1]
+        for i in range(len(FPR)):
+            FPR[i] /= FPR[-1]
+        trapz = getattr(np, "trapezoid", None) or np.trapz      # one function under two names across NumPy versions
+        return TPR, FPR, trapz(TPR, FPR)
+
+    def plot_roc(self, rel_index, fig_name=None):
+        """The reference's plot_roc (Config.py:519-571): the ROC curve of one relation on the test split, drawn with the
+        reference's labels and shown, or saved when fig_name is given; returns (FPR, TPR, auc) as plotted.  The lists are
+        built literally as the reference builds them (_roc_lists), whose end point is the length of the WHOLE test list: it is
+        the relation's own count only for a one-relation test list, so on any other the plotted curve ends in a long closing
+        segment and its area is not the relation's AUC.  roc_curve normalises by the relation's own count for that reason.
+        The counts come from kge_tc_roc.  Raises KgeError as roc_curve does."""
+        _, (counts, n_interval, _) = self._roc_device("test", int(rel_index))
+        TPR, FPR, auc = self._roc_lists(counts, n_interval, len(self.test_pos_h))
+        import matplotlib.pyplot as plt
+        plt.figure()
+        lw = 2
+        plt.plot(FPR, TPR, color='darkorange', lw=lw, label='ROC curve (area = %0.3f)' % auc)
+        plt.plot([0, 1], [0, 1], color='navy', lw=lw, linestyle='--')
+        plt.xlim([0.0, 1.0])
+        plt.ylim([0.0, 1.05])
+        plt.xlabel('False Positive Rate (FPR)')
+        plt.ylabel('True Positive Rate (TPR)')
+        plt.title('ROC Curve')
+        plt.legend(loc="lower right")
+        if fig_name is None or fig_name == '':
+            plt.show()
+        else:
+            plt.savefig(fig_name)
+        return FPR, TPR, auc
 
     def _top_k(self, scores, k):
         res = np.asarray(scores).reshape(-1).argsort()[:k]

@@ -102,6 +102,7 @@ def _declare(L):
     L.kge_link_prediction_finish.argtypes = [i64, i64, i64, vp, vp, vp, vp]
     L.kge_tc_fit.argtypes = [vp, vp, i64, vp, vp, vp]
     L.kge_tc_apply.argtypes = [i64, vp, vp, vp, i64, vp, vp, vp]
+    L.kge_tc_roc.argtypes = [vp, vp, i64, i64, vp, vp, i64, vp, vp, i64, vp, vp]
     L.kge_test_entity_ids.argtypes = [i64, i64, vp, vp]
     L.kge_transe_counts_supported.argtypes = [ctypes.POINTER(ModelDesc), i64]
     L.kge_transe_forward_counts.argtypes = [ctypes.POINTER(ModelDesc), vp, vp, vp, vp, vp, i64, i64, i64, i64, vp, vp, vp, vp, vp]

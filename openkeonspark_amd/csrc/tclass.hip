@@ -20,6 +20,19 @@
 // A relation takes the LDS path when its n_interval + 2 bins fit the 16 000-bin LDS histogram AND it has at most 4096
 // validation triples; a relation with more triples (the skewed ones) or a wider grid takes the global path, where its
 // binning is spread over one workgroup per 2048 triples and only the scan is left to a single workgroup.
+//
+// ROC curves and AUC (kge_tc_roc): get_TPFP (eval.hip, Test.h:410-444) counts, for every point of the SAME
+// grid, the split's positives and negatives at or below it.  With hpos[k] / hneg[k] = the split's positives / negatives of bin
+// k(s), TP(i) = sum_{k <= i} hpos[k] and FP(i) = sum_{k <= i} hneg[k]: the fit's binning pass with two counters and its scan
+// carrying two sums.  Twice the trapezoid area under (0,0), (FP(i),TP(i))..., (n_r,n_r) is the integer
+// area2 = sum_k hneg[k] * (2 * TPexcl[k] + hpos[k]) over all n_interval + 2 bins (the last bin is the closing segment).
+// Launches of a ROC call (one stream): tc_init, tc_minmax, tc_prepare on the validation scores as above, then
+//   tc_finite       flags a non-finite split score (before the wait, so that an error writes nothing)
+//   tc_roc_prepare  per relation: the path by the SPLIT's triple count, its slice of the doubled global histogram and of d_tpfp
+//   -- the one wait: status and every relation's n_interval (the host forms h_offsets from them) --
+//   tc_roc_bin      (global path) one workgroup per chunk of the split's list, hpos then hneg in the relation's slice
+//   tc_roc          one workgroup per relation: LDS path = zero, bin both sides into 16-bit halves of one word, scan, write;
+//                   global path = scan, write; a relation without split triples gets zeros, one without validation (0, 0)
 #include <cfloat>
 
 #include "eval_dev.hpp"
@@ -36,8 +49,8 @@ constexpr int kFusedMaxTriples = 4096;  // LDS path: one workgroup bins the whol
 constexpr long long kMaxGlobalBins = 1ll << 28;   // 1 GiB of int32 bins
 constexpr long long kMaxInterval = 1ll << 24;     // (float)i is exact and g monotone below this
 constexpr float kInterval = 0.01f;      // Setting.h:118
-enum { kPathNone = 0, kPathLds = 1, kPathGlobal = 2 };
-enum { kFlagNonFinite = 1, kFlagTooWide = 2 };
+enum { kPathNone = 0, kPathLds = 1, kPathGlobal = 2, kPathEmpty = 3 };   // kPathEmpty (ROC): validation but no split triples
+enum { kFlagNonFinite = 1, kFlagTooWide = 2, kFlagSplitNonFinite = 4 };
 
 struct TcStatus {
     int32_t flags, pad;
@@ -59,6 +72,9 @@ struct TcDev {
     long long hist_cap = 0;
     TcStatus *status = nullptr, *status_host = nullptr;
     hipEvent_t ev = nullptr;
+    long long *out_off = nullptr;             // ROC: every relation's first element of d_tpfp
+    int32_t *nint_host = nullptr;             // ROC: pinned [R], read in the one wait
+    std::vector<char> has_valid;              // ROC: host copy of lef[0][r] >= 0
 };
 TcDev g_tc;
 
@@ -257,6 +273,148 @@ __global__ __launch_bounds__(kThreads) void tc_apply_kernel(const int4 *__restri
     }
 }
 
+// ---- ROC (kge_tc_roc) ----
+__global__ __launch_bounds__(kThreads) void tc_finite_kernel(const float *__restrict__ pos, const float *__restrict__ neg, int64_t n,
+                                                             TcStatus *__restrict__ st) {
+    bool bad = false;
+    for (int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x; i < n; i += (int64_t)gridDim.x * kThreads)
+        bad |= !(fabsf(pos[i]) <= FLT_MAX) || !(fabsf(neg[i]) <= FLT_MAX);
+    if (__any(bad) && (threadIdx.x & 63) == 0) atomicOr(&st->flags, kFlagSplitNonFinite);
+}
+
+// one workgroup, behind tc_prepare (which has left the grid in mn / nint): the path of every relation by the SPLIT's side,
+// its slice of the global histogram (hpos then hneg, n_interval + 2 bins each) and of the output (TP then FP, n_interval + 1 each)
+__global__ __launch_bounds__(kThreads) void tc_roc_prepare_kernel(int64_t R, const int32_t *__restrict__ valid_lef,
+                                                                  const int32_t *__restrict__ lef, const int32_t *__restrict__ rig,
+                                                                  const int32_t *__restrict__ nint, int32_t *__restrict__ path,
+                                                                  long long *__restrict__ off, long long *__restrict__ out_off,
+                                                                  TcStatus *__restrict__ st) {
+    __shared__ long long seg_need[kThreads], seg_out[kThreads];
+    const int64_t seg = (R + kThreads - 1) / kThreads;
+    const int64_t r0 = min((int64_t)threadIdx.x * seg, R), r1 = min(r0 + seg, R);
+    long long need = 0, out = 0;
+    for (int64_t r = r0; r < r1; r++) {
+        int p = kPathNone;
+        if (valid_lef[r] >= 0) {
+            const long long n = nint[r];
+            const int n_r = lef[r] >= 0 ? rig[r] - lef[r] + 1 : 0;
+            out += 2 * (n + 1);
+            if (n_r == 0) p = kPathEmpty;
+            else if (n + 2 <= kLdsBins && n_r <= kFusedMaxTriples) p = kPathLds;
+            else { p = kPathGlobal; need += 2 * (n + 2); }
+        }
+        path[r] = p;
+    }
+    seg_need[threadIdx.x] = need;
+    seg_out[threadIdx.x] = out;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        long long run = 0, run_out = 0;
+        for (int i = 0; i < kThreads; i++) {
+            const long long v = seg_need[i], w = seg_out[i];
+            seg_need[i] = run; seg_out[i] = run_out;
+            run += v; run_out += w;
+        }
+        st->bins = run;
+    }
+    __syncthreads();
+    long long run = seg_need[threadIdx.x], run_out = seg_out[threadIdx.x];
+    for (int64_t r = r0; r < r1; r++) {
+        off[r] = run;
+        out_off[r] = run_out;
+        if (path[r] == kPathGlobal) run += 2 * ((long long)nint[r] + 2);
+        if (path[r] != kPathNone) run_out += 2 * ((long long)nint[r] + 1);
+    }
+}
+
+__global__ __launch_bounds__(kThreads) void tc_roc_bin_kernel(const int4 *__restrict__ items, const float *__restrict__ pos,
+                                                              const float *__restrict__ neg, const float *__restrict__ mnv,
+                                                              const int32_t *__restrict__ nint, const int32_t *__restrict__ path,
+                                                              const long long *__restrict__ off, int32_t *__restrict__ hist) {
+    const int4 it = items[blockIdx.x];
+    if (path[it.x] != kPathGlobal) return;
+    const float mn = mnv[it.x];
+    const int n = nint[it.x];
+    int32_t *hp = hist + off[it.x], *hn = hp + n + 2;
+    for (int i = threadIdx.x; i < it.z; i += kThreads) {
+        atomicAdd(&hp[grid_bin(pos[it.y + i], mn, n)], 1);
+        atomicAdd(&hn[grid_bin(neg[it.y + i], mn, n)], 1);
+    }
+}
+
+// lef / rig: the split's ranges.  On the LDS path a word of `bins` holds hpos in its low and hneg in its high 16 bits: a
+// relation on that path has at most kFusedMaxTriples = 4096 triples, so neither half overflows.
+__global__ __launch_bounds__(kFitThreads) void tc_roc_kernel(const int32_t *__restrict__ lef, const int32_t *__restrict__ rig,
+                                                             const float *__restrict__ pos, const float *__restrict__ neg,
+                                                             const float *__restrict__ mnv, const int32_t *__restrict__ nint,
+                                                             const int32_t *__restrict__ path, const long long *__restrict__ off,
+                                                             const int32_t *__restrict__ hist, const long long *__restrict__ out_off,
+                                                             int64_t *__restrict__ tpfp, int64_t *__restrict__ auc2) {
+    __shared__ uint32_t bins[kLdsBins];
+    __shared__ int32_t wave_tp[kFitWaves], wave_fp[kFitWaves];
+    __shared__ long long wave_area[kFitWaves];
+    const int r = blockIdx.x, p = path[r];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int n = nint[r];
+    int64_t *out = tpfp ? tpfp + out_off[r] : nullptr;
+    if (p == kPathNone || p == kPathEmpty) {
+        if (p == kPathEmpty && out)
+            for (int i = tid; i < 2 * (n + 1); i += kFitThreads) out[i] = 0;
+        if (tid == 0) { auc2[2 * (size_t)r] = 0; auc2[2 * (size_t)r + 1] = 0; }
+        return;
+    }
+    const float mn = mnv[r];
+    const int lo = lef[r], n_r = rig[r] - lo + 1;
+    const int32_t *hp = hist + off[r], *hn = hp + n + 2;
+    if (p == kPathLds) {
+        for (int i = tid; i < n + 2; i += kFitThreads) bins[i] = 0u;
+        __syncthreads();
+        for (int i = tid; i < n_r; i += kFitThreads) {
+            atomicAdd(&bins[grid_bin(pos[lo + i], mn, n)], 1u);
+            atomicAdd(&bins[grid_bin(neg[lo + i], mn, n)], 1u << 16);
+        }
+        __syncthreads();
+    }
+    long long carry_tp = 0, carry_fp = 0, area = 0;
+    for (int base = 0; base <= n + 1; base += kFitThreads) {
+        const int i = base + tid;
+        int a = 0, b = 0;     // hpos[i], hneg[i]
+        if (i <= n + 1) {
+            if (p == kPathLds) { const uint32_t v = bins[i]; a = (int)(v & 0xFFFFu); b = (int)(v >> 16); }
+            else { a = hp[i]; b = hn[i]; }
+        }
+        int x = a, y = b;
+        for (int o = 1; o < 64; o <<= 1) {
+            const int xo = __shfl_up(x, o), yo = __shfl_up(y, o);
+            if (lane >= o) { x += xo; y += yo; }
+        }
+        if (lane == 63) { wave_tp[wave] = x; wave_fp[wave] = y; }
+        __syncthreads();
+        int before_tp = 0, all_tp = 0, before_fp = 0, all_fp = 0;
+        for (int w = 0; w < kFitWaves; w++) {
+            const int s = wave_tp[w], t = wave_fp[w];
+            if (w < wave) { before_tp += s; before_fp += t; }
+            all_tp += s; all_fp += t;
+        }
+        if (i <= n + 1) {
+            const long long tp = carry_tp + before_tp + x, fp = carry_fp + before_fp + y;
+            area += (long long)b * (2 * (tp - a) + a);
+            if (out && i <= n) { out[i] = tp; out[(size_t)n + 1 + i] = fp; }
+        }
+        carry_tp += all_tp;
+        carry_fp += all_fp;
+        __syncthreads();
+    }
+    for (int o = 32; o > 0; o >>= 1) area += __shfl_xor(area, o);
+    if (lane == 0) wave_area[wave] = area;
+    __syncthreads();
+    if (tid == 0) {
+        for (int w = 1; w < kFitWaves; w++) area += wave_area[w];
+        auc2[2 * (size_t)r] = area;
+        auc2[2 * (size_t)r + 1] = n_r;
+    }
+}
+
 // ---------------------------------------------------------------------------------------------
 template <typename T>
 int upload_vec(T *&dst, const std::vector<T> &src, const char *what) {
@@ -303,6 +461,11 @@ int ensure_tc_device() {
     if ((rc = alloc_n(d.nint, (size_t)R, "alloc classification state"))) return rc;
     if ((rc = alloc_n(d.path, (size_t)R, "alloc classification state"))) return rc;
     if ((rc = alloc_n(d.off, (size_t)R, "alloc classification state"))) return rc;
+    if ((rc = alloc_n(d.out_off, (size_t)R, "alloc classification state"))) return rc;
+    if (d.nint_host) { (void)hipHostFree(d.nint_host); d.nint_host = nullptr; }
+    if ((rc = hip_check(hipHostMalloc(&d.nint_host, sizeof(int32_t) * (size_t)(R ? R : 1)), "alloc classification status"))) return rc;
+    d.has_valid.assign((size_t)R, 0);
+    for (int64_t r = 0; r < R; r++) d.has_valid[(size_t)r] = (*l.lef[0])[(size_t)r] >= 0;
     if (!d.status && (rc = alloc_n(d.status, 1, "alloc classification state"))) return rc;
     if (!d.status_host && (rc = hip_check(hipHostMalloc(&d.status_host, sizeof(TcStatus)), "alloc classification status"))) return rc;
     if (!d.ev && (rc = hip_check(hipEventCreateWithFlags(&d.ev, hipEventDisableTiming), "create event"))) return rc;
@@ -370,4 +533,52 @@ extern "C" int kge_tc_apply(INT split, const float *d_thresh, const float *d_pos
         tc_apply_kernel<<<d.n_items[split], kThreads, 0, stream>>>(d.items[split], d.lef[0], d_thresh, d_pos, d_neg,
                                                                    (unsigned long long *)d_counts, (unsigned long long *)d_rel);
     return hip_check(hipGetLastError(), "kge_tc_apply launch");
+}
+
+extern "C" int kge_tc_roc(const float *d_vpos, const float *d_vneg, INT n_valid, INT split, const float *d_pos, const float *d_neg,
+                          INT n, int64_t *d_auc2, int64_t *d_tpfp, INT tpfp_capacity, int64_t *h_offsets, void *stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    if (!d_vpos || !d_vneg || !d_pos || !d_neg || !d_auc2 || !h_offsets) return fail(KGE_ERR_BAD_ARG, "kge_tc_roc: null score, result or offset array");
+    if (split != 0 && split != 1) return fail(KGE_ERR_BAD_ARG, "kge_tc_roc: split must be 0 (validation) or 1 (test)");
+    if (!device_ok()) return fail(KGE_ERR_NO_DEVICE, "kge_tc_roc: no usable HIP device");
+    int rc = ensure_tc_device();
+    if (rc) return rc;
+    TcDev &d = g_tc;
+    if (n_valid != d.total[0]) return fail(KGE_ERR_BAD_ARG, "kge_tc_roc: n_valid is not the validation set's size");
+    if (n != d.total[split]) return fail(KGE_ERR_BAD_ARG, "kge_tc_roc: n is not the split's size");
+    const unsigned rel_blocks = (unsigned)((d.R + kThreads - 1) / kThreads);
+    tc_init_kernel<<<rel_blocks ? rel_blocks : 1, kThreads, 0, stream>>>(d.R, d.kmin, d.kmax, d.status);
+    if (d.n_items[0] > 0)
+        tc_minmax_kernel<<<d.n_items[0], kThreads, 0, stream>>>(d.items[0], d_vpos, d_vneg, d.kmin, d.kmax, d.status);
+    tc_prepare_kernel<<<1, kThreads, 0, stream>>>(d.R, d.lef[0], d.rig[0], d.kmin, d.kmax, d.mn, d.nint, d.path, d.off, d.status);
+    if (n > 0)
+        tc_finite_kernel<<<(unsigned)std::min<int64_t>((n + kChunk - 1) / kChunk, 1024), kThreads, 0, stream>>>(d_pos, d_neg, n, d.status);
+    tc_roc_prepare_kernel<<<1, kThreads, 0, stream>>>(d.R, d.lef[0], d.lef[split], d.rig[split], d.nint, d.path, d.off, d.out_off, d.status);
+    if ((rc = hip_check(hipMemcpyAsync(d.status_host, d.status, sizeof(TcStatus), hipMemcpyDeviceToHost, stream), "read classification status"))) return rc;
+    if (d.R > 0 && (rc = hip_check(hipMemcpyAsync(d.nint_host, d.nint, sizeof(int32_t) * (size_t)d.R, hipMemcpyDeviceToHost, stream), "read n_interval"))) return rc;
+    if ((rc = hip_check(hipEventRecord(d.ev, stream), "record event"))) return rc;
+    if ((rc = hip_check(hipEventSynchronize(d.ev), "wait for the score ranges"))) return rc;
+    const TcStatus st = *d.status_host;
+    if (st.flags & kFlagNonFinite) return fail(KGE_ERR_BAD_ARG, "kge_tc_roc: non-finite validation score (nothing written)");
+    if (st.flags & kFlagSplitNonFinite) return fail(KGE_ERR_BAD_ARG, "kge_tc_roc: non-finite score in the split (nothing written)");
+    if (st.flags & kFlagTooWide) return fail(KGE_ERR_UNSUPPORTED, "kge_tc_roc: a relation's grid has 2^24 points or more (nothing written)");
+    if (st.bins > kMaxGlobalBins) return fail(KGE_ERR_UNSUPPORTED, "kge_tc_roc: the relations' grids need more than 2^28 histogram bins (nothing written)");
+    h_offsets[0] = 0;
+    for (int64_t r = 0; r < d.R; r++)
+        h_offsets[r + 1] = h_offsets[r] + (d.has_valid[(size_t)r] ? 2 * ((int64_t)d.nint_host[r] + 1) : 0);
+    if (d_tpfp && tpfp_capacity < h_offsets[d.R]) return fail(KGE_ERR_BAD_ARG, "kge_tc_roc: tpfp_capacity is below h_offsets[rel_total] (nothing written)");
+    if (d.R == 0) return KGE_OK;
+    if (st.bins > 0) {
+        if (d.hist_cap < st.bins) {
+            if ((rc = alloc_n(d.hist, (size_t)st.bins, "alloc classification histogram"))) { d.hist_cap = 0; return rc; }
+            d.hist_cap = st.bins;
+        }
+        if ((rc = hip_check(hipMemsetAsync(d.hist, 0, sizeof(int32_t) * (size_t)st.bins, stream), "clear classification histogram"))) return rc;
+        tc_roc_bin_kernel<<<d.n_items[split], kThreads, 0, stream>>>(d.items[split], d_pos, d_neg, d.mn, d.nint, d.path, d.off, d.hist);
+    } else if (!d.hist) {
+        if ((rc = alloc_n(d.hist, 1, "alloc classification histogram"))) return rc;   // tc_roc forms hist + off[r] on every path
+    }
+    tc_roc_kernel<<<(unsigned)d.R, kFitThreads, 0, stream>>>(d.lef[split], d.rig[split], d_pos, d_neg, d.mn, d.nint, d.path, d.off, d.hist,
+                                                            d.out_off, d_tpfp, d_auc2);
+    return hip_check(hipGetLastError(), "kge_tc_roc launch");
 }

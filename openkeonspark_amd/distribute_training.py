@@ -33,7 +33,7 @@ import zipfile
 
 import numpy as np
 
-from .Config import Config
+from .Config import Config, KgeError
 from .Model import xavier_normal
 from .TransD import TransD
 from .TransE import TransE
@@ -68,6 +68,7 @@ def parse_args(argv=None):
     p.add_argument("--mode", type=str, default="train")
     p.add_argument("--test_head", type=int, default=0)
     p.add_argument("--test_relation", type=int, default=0, help="1: --mode test also ranks the true relation of each test triple (rel* metrics)")
+    p.add_argument("--test_roc", type=int, default=0, help="1: --mode test also gives the per-relation ROC AUC on the test split (roc_auc_macro, roc_auc_weighted)")
     p.add_argument("--work_threads", type=int, default=8, help="virtual sampler threads (Config.py:65 hard-codes 8)")
     p.add_argument("--seed", type=int, default=0, help="parameter initialisation seed")
     p.add_argument("--sparse_rows", type=int, default=-1, help="1 / 0: force / forbid the touched-rows-only update: TransE int8 records (SGD, or the opt-in non-parity "
@@ -407,6 +408,8 @@ def main_fun(argv):
         restore_checkpoint(con, os.path.join(argv.output_path, "model.ckpt-%d.npz" % last_global_step), arrays=arrays)
 
     if argv.mode != "train":
+        if argv.test_roc and con._sharded("ent_embeddings"):      # before the rankers run, not after them
+            raise KgeError("--test_roc over an entity table sharded across ranks is not supported (Config.roc_auc refuses it)")
         if distributed:   # one contiguous slice of the test set per rank, accumulators all-reduced
             metrics = con.link_prediction_distributed(test_head=bool(argv.test_head))
             if argv.test_relation:
@@ -415,6 +418,10 @@ def main_fun(argv):
             out, metrics = con.link_prediction(test_head=bool(argv.test_head))
             if argv.test_relation:
                 metrics.update(con.relation_prediction()[1])
+        if argv.test_roc:      # every rank draws and scores the same lists
+            roc = con.roc_auc("test")
+            # None (JSON null) when no relation has both validation and test triples: a bare NaN is not JSON
+            metrics.update({"roc_auc_" + k: (None if roc[k] != roc[k] else roc[k]) for k in ("macro", "weighted")})
         if rank == 0:
             print(json.dumps(metrics, indent=1))
             if argv.output_path:
