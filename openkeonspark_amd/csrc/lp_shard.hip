@@ -22,6 +22,7 @@
 #include "eval_dev.hpp"
 #include "select_dev.hpp"
 #include "team.hpp"
+#include "team_shape.hpp"
 
 namespace kge {
 
@@ -293,17 +294,18 @@ int launch_range_t(RangeArgs a, hipStream_t stream) {
     return hip_check(hipGetLastError(), "lp range launch");
 }
 
-// (L, C) per width as topk.hip; Q triples per workgroup so that the 2Q request vectors (2 Q C floats) stay at 128 registers
+// Q triples per workgroup so that the 2Q request vectors (2 Q C floats) stay at 128 registers, U rows per team in flight:
+// (Q, U) = (8, 4), (8, 4), (8, 2), (8, 2), (16, 2), (8, 2), (4, 1) by rung
+constexpr int range_q(int L, int C) { return L == 64 && C == 4 ? 16 : (C == 16 ? 4 : 8); }
+constexpr int range_u(int C) { return C <= 2 ? 4 : (C == 16 ? 1 : 2); }
+
 int launch_range(const RangeArgs &a, hipStream_t stream) {
-    const int D = a.D;
-    if (D <= 16) return launch_range_t<16, 1, 8, 4>(a, stream);
-    if (D <= 32) return launch_range_t<16, 2, 8, 4>(a, stream);
-    if (D <= 64) return launch_range_t<16, 4, 8, 2>(a, stream);
-    if (D <= 128) return launch_range_t<32, 4, 8, 2>(a, stream);
-    if (D <= 256) return launch_range_t<64, 4, 16, 2>(a, stream);
-    if (D <= 512) return launch_range_t<64, 8, 8, 2>(a, stream);
-    if (D <= 1024) return launch_range_t<64, 16, 4, 1>(a, stream);
-    return fail(KGE_ERR_UNSUPPORTED, "kge_link_prediction_range: embedding dimension > 1024");
+    int rc = KGE_OK;
+    const bool shaped = for_team_shape(a.D, [&](auto t) {
+        constexpr int L = decltype(t)::L, C = decltype(t)::C;
+        rc = launch_range_t<L, C, range_q(L, C), range_u(C)>(a, stream);
+    });
+    return shaped ? rc : fail(KGE_ERR_UNSUPPORTED, "kge_link_prediction_range: embedding dimension > 1024");
 }
 
 long long *g_out = nullptr;

@@ -21,6 +21,7 @@
 // TF1 forms before the optimizer) with hardware fp32 atomics.
 #include "models_dev.hpp"
 #include "sampler_dev.hpp"
+#include "team_shape.hpp"
 
 namespace kge {
 
@@ -810,12 +811,9 @@ int ensure_loss_buffers() {
     return KGE_OK;
 }
 
-// team shape used for dimension D (shared with transe_counts.hip through these two helpers)
+// the numbers of the TransE count-path rung for dimension D (team_shape.hpp), for callers that size buffers by them
 void transe_team_shape(int D, int &L, int &C) {
-    if (D % 4 == 0 && D <= 64) { L = 16; C = 4; }  // vectorised kernel: one float4 per lane
-    else if (D <= 16) { L = 16; C = 1; } else if (D <= 32) { L = 16; C = 2; } else if (D <= 64) { L = 16; C = 4; }
-    else if (D <= 128) { L = 32; C = 4; } else if (D <= 256) { L = 64; C = 4; } else if (D <= 512) { L = 64; C = 8; }
-    else { L = 64; C = 16; }
+    for_transe_team_shape_or_last(D, [&](auto t) { L = decltype(t)::L; C = decltype(t)::C; });
 }
 
 static int32_t *g_defer_list = nullptr, *g_defer_count = nullptr;
@@ -878,16 +876,8 @@ int launch_transe_emit(const kge_model_desc &m, const float *ent, const float *r
     a.rec = rec; a.rec2 = (m.ent_dim % 4 == 0) ? rec2 : nullptr; a.dst = dst; a.ent_total = (int)m.ent_total; a.rel_total = (int)m.rel_total; a.krel = 1;
     a.loss_limbs = track_deferred ? nullptr : e.loss_limbs;   // (with a deferred pass the loss is finalised by loss_finalize_kernel: the caller converts it)
     while (a.krel * 2 <= krel) a.krel *= 2;      // a power of two: the kernels take b & (krel - 1)
-    const int D = a.D;
-    if (D % 4 == 0 && D <= 64) launch_emit<16, 4>(a, d_loss, stream);
-    else if (D <= 16) launch_emit<16, 1>(a, d_loss, stream);
-    else if (D <= 32) launch_emit<16, 2>(a, d_loss, stream);
-    else if (D <= 64) launch_emit<16, 4>(a, d_loss, stream);
-    else if (D <= 128) launch_emit<32, 4>(a, d_loss, stream);
-    else if (D <= 256) launch_emit<64, 4>(a, d_loss, stream);
-    else if (D <= 512) launch_emit<64, 8>(a, d_loss, stream);
-    else if (D <= 1024) launch_emit<64, 16>(a, d_loss, stream);
-    else return fail(KGE_ERR_UNSUPPORTED, "embedding dimension > 1024");
+    if (!for_transe_team_shape(a.D, [&](auto t) { launch_emit<decltype(t)::L, decltype(t)::C>(a, d_loss, stream); }))
+        return fail(KGE_ERR_UNSUPPORTED, "embedding dimension > 1024");
     return hip_check(hipGetLastError(), "transe emit launch");
 }
 
@@ -961,15 +951,8 @@ static void launch_fb_records(const FbArgs &a, float *d_loss, hipStream_t stream
 
 template <int MODEL>
 static int dispatch_fb_records(const FbArgs &a, float *d_loss, hipStream_t stream) {
-    const int D = a.D;
-    if (D <= 16) launch_fb_records<MODEL, 16, 1>(a, d_loss, stream);
-    else if (D <= 32) launch_fb_records<MODEL, 16, 2>(a, d_loss, stream);
-    else if (D <= 64) launch_fb_records<MODEL, 16, 4>(a, d_loss, stream);
-    else if (D <= 128) launch_fb_records<MODEL, 32, 4>(a, d_loss, stream);
-    else if (D <= 256) launch_fb_records<MODEL, 64, 4>(a, d_loss, stream);
-    else if (D <= 512) launch_fb_records<MODEL, 64, 8>(a, d_loss, stream);
-    else if (D <= 1024) launch_fb_records<MODEL, 64, 16>(a, d_loss, stream);
-    else return fail(KGE_ERR_UNSUPPORTED, "embedding dimension > 1024 is not supported by the vector-model kernels");
+    if (!for_team_shape(a.D, [&](auto t) { launch_fb_records<MODEL, decltype(t)::L, decltype(t)::C>(a, d_loss, stream); }))
+        return fail(KGE_ERR_UNSUPPORTED, "embedding dimension > 1024 is not supported by the vector-model kernels");
     return KGE_OK;
 }
 
@@ -996,15 +979,8 @@ __global__ __launch_bounds__(256) void hub_fold_kernel(float *__restrict__ copie
 
 template <int MODEL>
 static int dispatch_fb(const FbArgs &a, float *d_loss, hipStream_t stream) {
-    const int D = a.D;
-    if (D <= 16) launch_fb<MODEL, 16, 1>(a, d_loss, stream);
-    else if (D <= 32) launch_fb<MODEL, 16, 2>(a, d_loss, stream);
-    else if (D <= 64) launch_fb<MODEL, 16, 4>(a, d_loss, stream);
-    else if (D <= 128) launch_fb<MODEL, 32, 4>(a, d_loss, stream);
-    else if (D <= 256) launch_fb<MODEL, 64, 4>(a, d_loss, stream);
-    else if (D <= 512) launch_fb<MODEL, 64, 8>(a, d_loss, stream);
-    else if (D <= 1024) launch_fb<MODEL, 64, 16>(a, d_loss, stream);
-    else return fail(KGE_ERR_UNSUPPORTED, "embedding dimension > 1024 is not supported by the vector-model kernels");
+    if (!for_team_shape(a.D, [&](auto t) { launch_fb<MODEL, decltype(t)::L, decltype(t)::C>(a, d_loss, stream); }))
+        return fail(KGE_ERR_UNSUPPORTED, "embedding dimension > 1024 is not supported by the vector-model kernels");
     return KGE_OK;
 }
 
@@ -1063,13 +1039,10 @@ bool pair_path_active(const kge_model_desc &m, int64_t n_pos, int64_t n_neg) {
 // the exact fp32 kernel over the groups an emit kernel deferred (a.group_list), partial losses behind the emit kernel's
 template <int MODEL>
 static int dispatch_fb_deferred(const FbArgs &a, hipStream_t stream) {
-    const int D = a.D;
-#define KGE_DEFER(LL, CC) hipLaunchKernelGGL((fwdbwd_kernel<MODEL, LL, CC>), dim3(kDeferBlocks), dim3(256), 0, stream, a)
-    if (D <= 16) KGE_DEFER(16, 1); else if (D <= 32) KGE_DEFER(16, 2); else if (D <= 64) KGE_DEFER(16, 4);
-    else if (D <= 128) KGE_DEFER(32, 4); else if (D <= 256) KGE_DEFER(64, 4); else if (D <= 512) KGE_DEFER(64, 8);
-    else if (D <= 1024) KGE_DEFER(64, 16);
-    else return fail(KGE_ERR_UNSUPPORTED, "embedding dimension > 1024 is not supported by the vector-model kernels");
-#undef KGE_DEFER
+    if (!for_team_shape(a.D, [&](auto t) {
+            hipLaunchKernelGGL((fwdbwd_kernel<MODEL, decltype(t)::L, decltype(t)::C>), dim3(kDeferBlocks), dim3(256), 0, stream, a);
+        }))
+        return fail(KGE_ERR_UNSUPPORTED, "embedding dimension > 1024 is not supported by the vector-model kernels");
     return KGE_OK;
 }
 
@@ -1560,23 +1533,14 @@ __global__ __launch_bounds__(256) void predict_kernel(FbArgs a, long long n, flo
 
 template <int MODEL>
 static int dispatch_predict(const FbArgs &a, long long n, float *out, hipStream_t stream) {
-    const int D = a.D;
-#define KGE_PRED(LL, CC)                                                                                     \
-    {                                                                                                        \
-        long long blocks = (n + (256 / LL) - 1) / (256 / LL);                                                \
-        if (blocks > 8192) blocks = 8192;                                                                    \
-        if (blocks < 1) blocks = 1;                                                                          \
-        hipLaunchKernelGGL((predict_kernel<MODEL, LL, CC>), dim3((unsigned)blocks), dim3(256), 0, stream, a, n, out); \
-    }
-    if (D <= 16) KGE_PRED(16, 1)
-    else if (D <= 32) KGE_PRED(16, 2)
-    else if (D <= 64) KGE_PRED(16, 4)
-    else if (D <= 128) KGE_PRED(32, 4)
-    else if (D <= 256) KGE_PRED(64, 4)
-    else if (D <= 512) KGE_PRED(64, 8)
-    else if (D <= 1024) KGE_PRED(64, 16)
-    else return fail(KGE_ERR_UNSUPPORTED, "embedding dimension > 1024 is not supported by the vector-model kernels");
-#undef KGE_PRED
+    const bool shaped = for_team_shape(a.D, [&](auto t) {
+        constexpr int L = decltype(t)::L, C = decltype(t)::C;
+        long long blocks = (n + (256 / L) - 1) / (256 / L);
+        if (blocks > 8192) blocks = 8192;
+        if (blocks < 1) blocks = 1;
+        hipLaunchKernelGGL((predict_kernel<MODEL, L, C>), dim3((unsigned)blocks), dim3(256), 0, stream, a, n, out);
+    });
+    if (!shaped) return fail(KGE_ERR_UNSUPPORTED, "embedding dimension > 1024 is not supported by the vector-model kernels");
     return KGE_OK;
 }
 
@@ -1663,26 +1627,17 @@ int launch_lp_table(const kge_model_desc &m, const float *const tables[4], const
     a.ent = tables[0]; a.rel = tables[1]; a.auxr = tables[2]; a.auxe = tables[3]; a.P = P_all;
     a.D = m.model == KGE_TRANSR ? m.rel_dim : m.ent_dim;
     const long long E = m.ent_total;
-    const int D = a.D;
-#define KGE_LPT(MODEL, LL, CC)                                                                                         \
-    {                                                                                                                  \
-        long long blocks = (E + (256 / LL) - 1) / (256 / LL);                                                          \
-        if (blocks > 4096) blocks = 4096;                                                                              \
-        hipLaunchKernelGGL((lp_table_kernel<MODEL, LL, CC>), dim3((unsigned)blocks), dim3(256), 0, stream, a, (long long)r, E, T); \
-    }
-#define KGE_LPT_D(MODEL)                                                                                               \
-    if (D <= 16) KGE_LPT(MODEL, 16, 1) else if (D <= 32) KGE_LPT(MODEL, 16, 2) else if (D <= 64) KGE_LPT(MODEL, 16, 4)  \
-    else if (D <= 128) KGE_LPT(MODEL, 32, 4) else if (D <= 256) KGE_LPT(MODEL, 64, 4) else if (D <= 512) KGE_LPT(MODEL, 64, 8) \
-    else if (D <= 1024) KGE_LPT(MODEL, 64, 16) else return fail(KGE_ERR_UNSUPPORTED, "embedding dimension > 1024");
-    switch (m.model) {
-        case KGE_TRANSE: KGE_LPT_D(KGE_TRANSE) break;
-        case KGE_TRANSH: KGE_LPT_D(KGE_TRANSH) break;
-        case KGE_TRANSR: KGE_LPT_D(KGE_TRANSR) break;
-        case KGE_TRANSD: KGE_LPT_D(KGE_TRANSD) break;
-        default: return fail(KGE_ERR_BAD_ARG, "unknown model id");
-    }
-#undef KGE_LPT_D
-#undef KGE_LPT
+    bool shaped = false;
+    const bool known = for_model(m.model, [&](auto mt) {
+        shaped = for_team_shape(a.D, [&](auto t) {
+            constexpr int L = decltype(t)::L, C = decltype(t)::C;
+            long long blocks = (E + (256 / L) - 1) / (256 / L);
+            if (blocks > 4096) blocks = 4096;
+            hipLaunchKernelGGL((lp_table_kernel<decltype(mt)::MODEL, L, C>), dim3((unsigned)blocks), dim3(256), 0, stream, a, (long long)r, E, T);
+        });
+    });
+    if (!known) return fail(KGE_ERR_BAD_ARG, "unknown model id");
+    if (!shaped) return fail(KGE_ERR_UNSUPPORTED, "embedding dimension > 1024");
     return hip_check(hipGetLastError(), "lp table launch");
 }
 
@@ -1693,28 +1648,19 @@ int launch_lp_scores(const kge_model_desc &m, const float *const tables[4], cons
     a.ent = tables[0]; a.rel = tables[1]; a.auxr = tables[2]; a.auxe = tables[3];
     a.D = m.model == KGE_TRANSR ? m.rel_dim : m.ent_dim;
     const long long E = m.ent_total;
-    const int D = a.D;
-#define KGE_LPS(MODEL, LL, CC)                                                                                         \
-    {                                                                                                                  \
-        long long bx = (E + (256 / LL) * 16 - 1) / ((256 / LL) * 16);   /* ~16 candidates per team */                  \
-        if (bx > 1024) bx = 1024;                                                                                      \
-        if (bx < 1) bx = 1;                                                                                            \
-        hipLaunchKernelGGL((lp_score_kernel<MODEL, LL, CC>), dim3((unsigned)bx, (unsigned)n_req), dim3(256), 0, stream, a, T, \
-                           (long long)r, d_req_fixed, d_req_head, E, d_scores);                                        \
-    }
-#define KGE_LPS_D(MODEL)                                                                                               \
-    if (D <= 16) KGE_LPS(MODEL, 16, 1) else if (D <= 32) KGE_LPS(MODEL, 16, 2) else if (D <= 64) KGE_LPS(MODEL, 16, 4)  \
-    else if (D <= 128) KGE_LPS(MODEL, 32, 4) else if (D <= 256) KGE_LPS(MODEL, 64, 4) else if (D <= 512) KGE_LPS(MODEL, 64, 8) \
-    else if (D <= 1024) KGE_LPS(MODEL, 64, 16) else return fail(KGE_ERR_UNSUPPORTED, "embedding dimension > 1024");
-    switch (m.model) {   // only ctx_forward's relation vector and the TransE mean differ between models here
-        case KGE_TRANSE: KGE_LPS_D(KGE_TRANSE) break;
-        case KGE_TRANSH: KGE_LPS_D(KGE_TRANSH) break;
-        case KGE_TRANSR: KGE_LPS_D(KGE_TRANSR) break;
-        case KGE_TRANSD: KGE_LPS_D(KGE_TRANSD) break;
-        default: return fail(KGE_ERR_BAD_ARG, "unknown model id");
-    }
-#undef KGE_LPS_D
-#undef KGE_LPS
+    bool shaped = false;
+    const bool known = for_model(m.model, [&](auto mt) {   // only ctx_forward's relation vector and the TransE mean differ between models here
+        shaped = for_team_shape(a.D, [&](auto t) {
+            constexpr int L = decltype(t)::L, C = decltype(t)::C;
+            long long bx = (E + (256 / L) * 16 - 1) / ((256 / L) * 16);   // ~16 candidates per team
+            if (bx > 1024) bx = 1024;
+            if (bx < 1) bx = 1;
+            hipLaunchKernelGGL((lp_score_kernel<decltype(mt)::MODEL, L, C>), dim3((unsigned)bx, (unsigned)n_req), dim3(256), 0, stream, a, T,
+                               (long long)r, d_req_fixed, d_req_head, E, d_scores);
+        });
+    });
+    if (!known) return fail(KGE_ERR_BAD_ARG, "unknown model id");
+    if (!shaped) return fail(KGE_ERR_UNSUPPORTED, "embedding dimension > 1024");
     return hip_check(hipGetLastError(), "lp score launch");
 }
 

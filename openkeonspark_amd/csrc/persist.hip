@@ -25,6 +25,7 @@
 #include "models_dev.hpp"
 #include "optim_dev.hpp"
 #include "sampler_dev.hpp"
+#include "team_shape.hpp"
 
 namespace kge {
 namespace {
@@ -444,31 +445,31 @@ extern "C" int kge_train_steps_persistent(const kge_model_desc *m, float *const 
         pa.trace = g_trace;
     }
     // 1024 threads: 16 waves per CU behind ONE barrier participant (<= 128 VGPRs); 512: half the waves, twice the registers
-    const int D = a.D;
     const bool wide = e.persist_threads != 512;
     // Cooperative launch: the runtime checks the grid against what can be co-resident and REFUSES one that cannot be
     // (hipErrorCooperativeLaunchTooLarge) instead of leaving it to the bounded spins to find out half way through a step; its
     // +15-19 us of host time is paid once per launch of n_steps steps.
     void *kargs[] = {&pa};
     hipError_t launch_err = hipSuccess;
-#define KGE_PERSIST(MODEL, LL, CC)                                                                                                 \
-    {                                                                                                                              \
-        if (wide) launch_err = hipLaunchCooperativeKernel((const void *)persistent_steps_kernel<MODEL, LL, CC, 1024>, dim3(blocks), \
-                                                          dim3(1024), kargs, 0, stream);                                           \
-        else launch_err = hipLaunchCooperativeKernel((const void *)persistent_steps_kernel<MODEL, LL, CC, 512>, dim3(blocks),      \
-                                                     dim3(512), kargs, 0, stream);                                                 \
-    }
-#define KGE_PERSIST_D(MODEL)                                                                   \
-    if (D <= 16) KGE_PERSIST(MODEL, 16, 1) else if (D <= 32) KGE_PERSIST(MODEL, 16, 2)         \
-    else if (D <= 64) KGE_PERSIST(MODEL, 16, 4) else if (D <= 128) KGE_PERSIST(MODEL, 32, 4)   \
-    else KGE_PERSIST(MODEL, 64, 4)
+    bool shaped = false;
+    auto launch = [&](auto mt) {
+        for_team_shape(a.D, [&](auto t) {
+            constexpr int MODEL = decltype(mt)::MODEL, L = decltype(t)::L, C = decltype(t)::C;
+            if constexpr (C <= 4) {   // the ladder stops at (64, 4): width <= 256, checked on entry
+                shaped = true;
+                if (wide) launch_err = hipLaunchCooperativeKernel((const void *)persistent_steps_kernel<MODEL, L, C, 1024>, dim3(blocks),
+                                                                  dim3(1024), kargs, 0, stream);
+                else launch_err = hipLaunchCooperativeKernel((const void *)persistent_steps_kernel<MODEL, L, C, 512>, dim3(blocks),
+                                                             dim3(512), kargs, 0, stream);
+            }
+        });
+    };
     switch (m->model) {
-        case KGE_TRANSE: KGE_PERSIST_D(KGE_TRANSE) break;
-        case KGE_TRANSH: KGE_PERSIST_D(KGE_TRANSH) break;
-        default: KGE_PERSIST_D(KGE_TRANSD) break;
+        case KGE_TRANSE: launch(ModelTag<KGE_TRANSE>{}); break;
+        case KGE_TRANSH: launch(ModelTag<KGE_TRANSH>{}); break;
+        default: launch(ModelTag<KGE_TRANSD>{}); break;
     }
-#undef KGE_PERSIST_D
-#undef KGE_PERSIST
+    if (!shaped) return fail(KGE_ERR_UNSUPPORTED, "kge_train_steps_persistent: embedding width <= 256");
     if (launch_err == hipErrorCooperativeLaunchTooLarge)
         return fail(KGE_ERR_UNSUPPORTED, "kge_train_steps_persistent: one workgroup per compute unit cannot be co-resident on this device "
                                          "(compute units masked or held by another process?)");

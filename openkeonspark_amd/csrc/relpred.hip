@@ -30,6 +30,7 @@
 #include "eval_dev.hpp"
 #include "models_dev.hpp"
 #include "select_dev.hpp"
+#include "team_shape.hpp"
 
 namespace kge {
 
@@ -413,15 +414,9 @@ int launch_score_t(RelScoreArgs a, hipStream_t stream) {
 
 template <int MODEL>
 int launch_score_m(const RelScoreArgs &a, hipStream_t stream) {
-    const int D = a.fa.D;
-    if (D <= 16) return launch_score_t<MODEL, 16, 1>(a, stream);
-    if (D <= 32) return launch_score_t<MODEL, 16, 2>(a, stream);
-    if (D <= 64) return launch_score_t<MODEL, 16, 4>(a, stream);
-    if (D <= 128) return launch_score_t<MODEL, 32, 4>(a, stream);
-    if (D <= 256) return launch_score_t<MODEL, 64, 4>(a, stream);
-    if (D <= 512) return launch_score_t<MODEL, 64, 8>(a, stream);
-    if (D <= 1024) return launch_score_t<MODEL, 64, 16>(a, stream);
-    return fail(KGE_ERR_UNSUPPORTED, "relation prediction: embedding dimension > 1024");
+    int rc = KGE_OK;
+    const bool shaped = for_team_shape(a.fa.D, [&](auto t) { rc = launch_score_t<MODEL, decltype(t)::L, decltype(t)::C>(a, stream); });
+    return shaped ? rc : fail(KGE_ERR_UNSUPPORTED, "relation prediction: embedding dimension > 1024");
 }
 
 template <int L, int C>
@@ -436,15 +431,9 @@ int launch_transr_t(const RelScoreArgs &a, hipStream_t stream) {
 }
 
 int launch_transr_stage(const RelScoreArgs &a, hipStream_t stream) {
-    const int D = a.fa.D;
-    if (D <= 16) return launch_transr_t<16, 1>(a, stream);
-    if (D <= 32) return launch_transr_t<16, 2>(a, stream);
-    if (D <= 64) return launch_transr_t<16, 4>(a, stream);
-    if (D <= 128) return launch_transr_t<32, 4>(a, stream);
-    if (D <= 256) return launch_transr_t<64, 4>(a, stream);
-    if (D <= 512) return launch_transr_t<64, 8>(a, stream);
-    if (D <= 1024) return launch_transr_t<64, 16>(a, stream);
-    return fail(KGE_ERR_UNSUPPORTED, "relation prediction: relation dimension > 1024");
+    int rc = KGE_OK;
+    const bool shaped = for_team_shape(a.fa.D, [&](auto t) { rc = launch_transr_t<decltype(t)::L, decltype(t)::C>(a, stream); });
+    return shaped ? rc : fail(KGE_ERR_UNSUPPORTED, "relation prediction: relation dimension > 1024");
 }
 
 // scores of queries [0, n) of the chunk into g_S

@@ -27,6 +27,7 @@
 #include "eval_dev.hpp"
 #include "models_dev.hpp"
 #include "select_dev.hpp"
+#include "team_shape.hpp"
 
 namespace kge {
 
@@ -321,30 +322,19 @@ int grow(T *&buf, int64_t &cap, int64_t need, const char *what) {
     return rc;
 }
 
-template <int MODEL>
-int launch_table_m(const FbArgs &a, int64_t r, int64_t E, float *T, float *inv, hipStream_t stream) {
-    const int D = a.D;
-#define KGE_TKT(LL, CC)                                                                                                \
-    {                                                                                                                  \
-        long long blocks = (E + (256 / LL) - 1) / (256 / LL);                                                          \
-        if (blocks > 4096) blocks = 4096;                                                                              \
-        hipLaunchKernelGGL((topk_table_kernel<MODEL, LL, CC>), dim3((unsigned)blocks), dim3(256), 0, stream, a, (long long)r, (long long)E, T, inv); \
-    }
-    if (D <= 16) KGE_TKT(16, 1) else if (D <= 32) KGE_TKT(16, 2) else if (D <= 64) KGE_TKT(16, 4) else if (D <= 128) KGE_TKT(32, 4)
-    else if (D <= 256) KGE_TKT(64, 4) else if (D <= 512) KGE_TKT(64, 8) else if (D <= 1024) KGE_TKT(64, 16)
-    else return fail(KGE_ERR_UNSUPPORTED, "kge_topk_entities: embedding dimension > 1024");
-#undef KGE_TKT
-    return hip_check(hipGetLastError(), "top-k table launch");
-}
-
 int launch_table(int model, const FbArgs &a, int64_t r, int64_t E, float *T, float *inv, hipStream_t stream) {
-    switch (model) {
-        case KGE_TRANSE: return launch_table_m<KGE_TRANSE>(a, r, E, T, inv, stream);
-        case KGE_TRANSH: return launch_table_m<KGE_TRANSH>(a, r, E, T, inv, stream);
-        case KGE_TRANSD: return launch_table_m<KGE_TRANSD>(a, r, E, T, inv, stream);
-        case KGE_TRANSR: return launch_table_m<KGE_TRANSR>(a, r, E, T, inv, stream);
-        default: return fail(KGE_ERR_BAD_ARG, "unknown model id");
-    }
+    bool shaped = false;
+    const bool known = for_model(model, [&](auto mt) {
+        shaped = for_team_shape(a.D, [&](auto t) {
+            constexpr int L = decltype(t)::L, C = decltype(t)::C;
+            long long blocks = (E + (256 / L) - 1) / (256 / L);
+            if (blocks > 4096) blocks = 4096;
+            hipLaunchKernelGGL((topk_table_kernel<decltype(mt)::MODEL, L, C>), dim3((unsigned)blocks), dim3(256), 0, stream, a, (long long)r, (long long)E, T, inv);
+        });
+    });
+    if (!known) return fail(KGE_ERR_BAD_ARG, "unknown model id");
+    if (!shaped) return fail(KGE_ERR_UNSUPPORTED, "kge_topk_entities: embedding dimension > 1024");
+    return hip_check(hipGetLastError(), "top-k table launch");
 }
 
 constexpr int kSelectLdsBytes = 48 << 10;   // key buffers of one workgroup: two workgroups of 4 waves per CU
@@ -379,29 +369,28 @@ int launch_select_t(TopkArgs a, hipStream_t stream) {
     return KGE_OK;
 }
 
-// (L, C) per width as launch_lp_scores; Q queries per workgroup and U rows per team so that the query vectors (2 Q C floats)
-// and the rows in flight (U C) stay in registers
+// Q queries per workgroup and U rows per team so that the query vectors (2 Q C floats) and the rows in flight (U C) stay in
+// registers: (16, 4) up to C = 4, then (8, 2), then (4, 1)
+constexpr int select_q(int C) { return C <= 4 ? 16 : (C <= 8 ? 8 : 4); }
+constexpr int select_u(int C) { return C <= 4 ? 4 : (C <= 8 ? 2 : 1); }
+
 template <int MODEL, bool DIRECT, bool RANGE = false>
 int launch_select_d(const TopkArgs &a, hipStream_t stream) {
-    const int D = a.fa.D;
-    if (D <= 16) return launch_select_t<MODEL, 16, 1, 16, 4, DIRECT, RANGE>(a, stream);
-    if (D <= 32) return launch_select_t<MODEL, 16, 2, 16, 4, DIRECT, RANGE>(a, stream);
-    if (D <= 64) return launch_select_t<MODEL, 16, 4, 16, 4, DIRECT, RANGE>(a, stream);
-    if (D <= 128) return launch_select_t<MODEL, 32, 4, 16, 4, DIRECT, RANGE>(a, stream);
-    if (D <= 256) return launch_select_t<MODEL, 64, 4, 16, 4, DIRECT, RANGE>(a, stream);
-    if (D <= 512) return launch_select_t<MODEL, 64, 8, 8, 2, DIRECT, RANGE>(a, stream);
-    if (D <= 1024) return launch_select_t<MODEL, 64, 16, 4, 1, DIRECT, RANGE>(a, stream);
-    return fail(KGE_ERR_UNSUPPORTED, "kge_topk_entities: embedding dimension > 1024");
+    int rc = KGE_OK;
+    const bool shaped = for_team_shape(a.fa.D, [&](auto t) {
+        constexpr int L = decltype(t)::L, C = decltype(t)::C;
+        rc = launch_select_t<MODEL, L, C, select_q(C), select_u(C), DIRECT, RANGE>(a, stream);
+    });
+    return shaped ? rc : fail(KGE_ERR_UNSUPPORTED, "kge_topk_entities: embedding dimension > 1024");
 }
 
 int launch_select(int model, bool direct, const TopkArgs &a, hipStream_t stream) {
-    switch (model) {
-        case KGE_TRANSE: return direct ? launch_select_d<KGE_TRANSE, true>(a, stream) : launch_select_d<KGE_TRANSE, false>(a, stream);
-        case KGE_TRANSH: return direct ? launch_select_d<KGE_TRANSH, true>(a, stream) : launch_select_d<KGE_TRANSH, false>(a, stream);
-        case KGE_TRANSD: return direct ? launch_select_d<KGE_TRANSD, true>(a, stream) : launch_select_d<KGE_TRANSD, false>(a, stream);
-        case KGE_TRANSR: return direct ? launch_select_d<KGE_TRANSR, true>(a, stream) : launch_select_d<KGE_TRANSR, false>(a, stream);
-        default: return fail(KGE_ERR_BAD_ARG, "unknown model id");
-    }
+    int rc = KGE_OK;
+    const bool known = for_model(model, [&](auto mt) {
+        constexpr int MODEL = decltype(mt)::MODEL;
+        rc = direct ? launch_select_d<MODEL, true>(a, stream) : launch_select_d<MODEL, false>(a, stream);
+    });
+    return known ? rc : fail(KGE_ERR_BAD_ARG, "unknown model id");
 }
 
 }  // namespace

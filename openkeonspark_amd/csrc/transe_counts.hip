@@ -24,6 +24,7 @@
 
 #include "engine.hpp"
 #include "team.hpp"
+#include "team_shape.hpp"
 #include "sampler_dev.hpp"
 #include "optim_dev.hpp"
 
@@ -458,15 +459,15 @@ static unsigned take_ride(SamplerArgs &ride, int which) {
     if (pct == 0 || upload_jump_table() != KGE_OK || !take_attached_sampler(ride, n_ride, pct >= 100 ? 1.0f : 0.01f * (float)pct)) n_ride = 0;
     return n_ride;
 }
-static void launch_bkt_hist(int n_tiles, int M, int rpb, int32_t *totals, int32_t *plan_counter, hipStream_t stream) {
+static void launch_bkt_hist(const int32_t *dst, int n_tiles, int M, int rpb, int32_t *totals, int32_t *plan_counter, hipStream_t stream) {
     SamplerArgs ride = {};
     const unsigned n_ride = take_ride(ride, 0);
-    hipLaunchKernelGGL(bkt_hist_kernel, dim3((unsigned)n_tiles + n_ride), dim3(256), 0, stream, g_c.dst, M, rpb, totals, plan_counter, ride, n_tiles);
+    hipLaunchKernelGGL(bkt_hist_kernel, dim3((unsigned)n_tiles + n_ride), dim3(256), 0, stream, dst, M, rpb, totals, plan_counter, ride, n_tiles);
 }
-static void launch_bkt_scatter(int n_tiles, int M, int rpb, int32_t *totals, int32_t *cursor, int2 *pairs, hipStream_t stream) {
+static void launch_bkt_scatter(const int32_t *dst, int n_tiles, int M, int rpb, int32_t *totals, int32_t *cursor, int2 *pairs, hipStream_t stream) {
     SamplerArgs ride = {};
     const unsigned n_ride = take_ride(ride, 1);
-    hipLaunchKernelGGL(bkt_scatter_kernel, dim3((unsigned)n_tiles + n_ride), dim3(256), 0, stream, g_c.dst, M, rpb, totals, g_c.bucket_start,
+    hipLaunchKernelGGL(bkt_scatter_kernel, dim3((unsigned)n_tiles + n_ride), dim3(256), 0, stream, dst, M, rpb, totals, g_c.bucket_start,
                        cursor, pairs, ride, n_tiles, (int)n_ride);
 }
 
@@ -1109,6 +1110,70 @@ __global__ __launch_bounds__(256) void segsum_pairs_kernel(const uint32_t *__res
     flush_row(true);
 }
 
+// ---- "order the records by row": the stage every reduce path starts with, in its two forms.  Both leave the row-sorted
+// (key, record id) pairs in g_c.dst_sorted / g_c.ids_sorted and hand back where the number of live records lies. ----
+
+// Two-level bucket sort of the M keys in `dst` (-1 = no record) over `rows` rows, rpb rows per bucket (row spaces up to NB * 8192).
+// plan: the fused step's form (bkt_sort_kernel<true>); the hist launch re-zeroes its piece counter.
+int bucket_sort_records(const int32_t *dst, int64_t M, int rows, int rpb, const SegPlan *plan, hipStream_t stream, const int32_t *&n_live) {
+    int rc;
+    if (!g_c.bucket_start) {
+        if ((rc = regrow(g_c.bucket_start, NB + 2, "counts bucket_start"))) return rc;
+        if ((rc = regrow(g_c.tile_hist, 2 * (NB + 2), "counts bucket totals/cursors"))) return rc;
+        if ((rc = hip_check(hipMemset(g_c.tile_hist, 0, sizeof(int32_t) * 2 * (NB + 2)), "zero bucket totals"))) return rc;
+    }
+    const int n_tiles = (int)((M + BTILE - 1) / BTILE);
+    int32_t *totals = g_c.tile_hist, *cursor = g_c.tile_hist + (NB + 2);
+    int2 *pairs = reinterpret_cast<int2 *>(g_c.pairs);
+    launch_bkt_hist(dst, n_tiles, (int)M, rpb, totals, plan ? plan->n_pieces : nullptr, stream);
+    launch_bkt_scatter(dst, n_tiles, (int)M, rpb, totals, cursor, pairs, stream);
+    if (plan) launch_bkt_sort<true>(pairs, rpb, rows, totals, cursor, *plan, stream);
+    else launch_bkt_sort<false>(pairs, rpb, rows, totals, cursor, SegPlan(), stream);
+    n_live = g_c.bucket_start + NB;   // start of the trash bucket == number of live records
+    return KGE_OK;
+}
+
+// rocPRIM's radix sort on the same keys: any row space.  Keys that carry no record (-1; with `blank` also keys >= rows) first
+// become the sentinel `rows`, so they sort last and count_valid_kernel finds the number of live records by bisection.
+int radix_sort_records(int32_t *dst, int64_t M, int rows, bool blank, const char *what, hipStream_t stream, const int32_t *&n_live) {
+    int blocks = (int)((M + 255) / 256);
+    if (blocks > 4096) blocks = 4096;
+    if (blank) hipLaunchKernelGGL(blank_keys_kernel, dim3(blocks), dim3(256), 0, stream, dst, (long long)M, rows);
+    else hipLaunchKernelGGL(fix_keys_kernel, dim3(blocks), dim3(256), 0, stream, dst, (long long)M, rows);
+    size_t tmp = g_c.sort_tmp_bytes;
+    int rc = hip_check(rocprim::radix_sort_pairs(g_c.sort_tmp, tmp, dst, g_c.dst_sorted, g_c.ids, g_c.ids_sorted, (size_t)M, 0,
+                                                 bits_for_rows(rows), stream), what);
+    if (rc) return rc;
+    hipLaunchKernelGGL(count_valid_kernel, dim3(1), dim3(64), 0, stream, g_c.dst_sorted, (int)M, rows, g_c.n_valid);
+    n_live = g_c.n_valid;
+    return KGE_OK;
+}
+
+// per-copy sums of the relation-side rows, [copy][hub row][D] (zero between steps: the fold kernels re-zero what they fold)
+int ensure_hub_sums(size_t need, hipStream_t stream) {
+    if (need <= g_c.hub_sums_cap) return KGE_OK;
+    int rc;
+    if ((rc = regrow(g_c.hub_sums, need, "hub copy sums"))) return rc;
+    if ((rc = hip_check(hipMemsetAsync(g_c.hub_sums, 0, sizeof(float) * need, stream), "zero hub copy sums"))) return rc;
+    g_c.hub_sums_cap = need;
+    return KGE_OK;
+}
+
+// the lazy-Adam reduce of sorted float records and the fold of its hub copies, V floats per unit of a row
+template <int L, int C, int V>
+void launch_segsum_adam(int64_t M, const float *rec, const FloatRowSpace &rs, const AdamRows &ad, int D, int K, hipStream_t stream) {
+    long long nb = (M + (256 / L) - 1) / (256 / L);
+    if (nb > 16384) nb = 16384;
+    hipLaunchKernelGGL((segsum_adam_runs_kernel<L, C, V>), dim3((unsigned)nb), dim3(256), 0, stream, rec, g_c.dst_sorted,
+                       g_c.ids_sorted, g_c.n_valid, rs, ad, D, g_c.hub_sums, g_c.hub_marks);
+    if (K > 0) {
+        long long nf = (rs.hub_rows + (256 / L) - 1) / (256 / L);
+        if (nf > 16384) nf = 16384;
+        hipLaunchKernelGGL((hub_fold_adam_kernel<L, C, V>), dim3((unsigned)nf), dim3(256), 0, stream, g_c.hub_sums, g_c.hub_marks,
+                           rs, ad, D, K);
+    }
+}
+
 }  // namespace
 
 int float_records_workspace(int64_t M, int D, float *&rec, int32_t *&dst) {
@@ -1121,65 +1186,28 @@ int float_records_workspace(int64_t M, int D, float *&rec, int32_t *&dst) {
 
 int float_records_reduce(int64_t M, int D, const FloatRowSpace &rs, hipStream_t stream, const float *rec_ext, int32_t *dst_ext, bool deterministic) {
     int rc;
-    // records held by the caller: size the sort's work buffers for M, then let the launches below read the caller's arrays (the
-    // pointers are passed by value at launch, so the workspace's own are put back before returning)
-    struct Swap {
-        uint32_t *rec; int32_t *dst; bool on;
-        ~Swap() { if (on) { g_c.rec = rec; g_c.dst = dst; } }
-    } swap = {g_c.rec, g_c.dst, false};
-    if (rec_ext && dst_ext) {
-        if ((rc = ensure_counts_work(M, (size_t)D))) return rc;
-        swap.rec = g_c.rec; swap.dst = g_c.dst; swap.on = true;
-        g_c.rec = reinterpret_cast<uint32_t *>(const_cast<float *>(rec_ext));
-        g_c.dst = dst_ext;
-    }
+    // records held by the caller: size the sort's work buffers for M; the launches below read the caller's arrays
+    const bool ext = rec_ext && dst_ext;
+    if (ext && (rc = ensure_counts_work(M, (size_t)D))) return rc;
+    const float *rec = ext ? rec_ext : reinterpret_cast<const float *>(g_c.rec);
+    int32_t *dst = ext ? dst_ext : g_c.dst;
     const int rows = (int)rs.rows;
     const int32_t *n_valid_p = nullptr;
     const int rpb = (rows + NB - 1) / NB;
-    if (rpb <= 8192 && !engine().counts_force_sort && !deterministic) {
-        const int n_tiles = (int)((M + BTILE - 1) / BTILE);
-        if (!g_c.bucket_start) {
-            if ((rc = regrow(g_c.bucket_start, NB + 2, "counts bucket_start"))) return rc;
-            if ((rc = regrow(g_c.tile_hist, 2 * (NB + 2), "counts bucket totals/cursors"))) return rc;
-            if ((rc = hip_check(hipMemset(g_c.tile_hist, 0, sizeof(int32_t) * 2 * (NB + 2)), "zero bucket totals"))) return rc;
-        }
-        int32_t *totals = g_c.tile_hist, *cursor = g_c.tile_hist + (NB + 2);
-        int2 *pairs = reinterpret_cast<int2 *>(g_c.pairs);
-        launch_bkt_hist(n_tiles, (int)M, rpb, totals, nullptr, stream);
-        launch_bkt_scatter(n_tiles, (int)M, rpb, totals, cursor, pairs, stream);
-        launch_bkt_sort<false>(pairs, rpb, rows, totals, cursor, SegPlan(), stream);
-        n_valid_p = g_c.bucket_start + NB;
-    } else {
-        int blocks = (int)((M + 255) / 256);
-        if (blocks > 4096) blocks = 4096;
-        hipLaunchKernelGGL(fix_keys_kernel, dim3(blocks), dim3(256), 0, stream, g_c.dst, (long long)M, rows);
-        size_t tmp = g_c.sort_tmp_bytes;
-        rc = hip_check(rocprim::radix_sort_pairs(g_c.sort_tmp, tmp, g_c.dst, g_c.dst_sorted, g_c.ids, g_c.ids_sorted, (size_t)M, 0,
-                                                 bits_for_rows(rows), stream), "float records sort");
-        if (rc) return rc;
-        hipLaunchKernelGGL(count_valid_kernel, dim3(1), dim3(64), 0, stream, g_c.dst_sorted, (int)M, rows, g_c.n_valid);
-        n_valid_p = g_c.n_valid;
-    }
-    const float *rec = reinterpret_cast<const float *>(g_c.rec);
+    if (rpb <= 8192 && !engine().counts_force_sort && !deterministic) rc = bucket_sort_records(dst, M, rows, rpb, nullptr, stream, n_valid_p);
+    else rc = radix_sort_records(dst, M, rows, false, "float records sort", stream, n_valid_p);
+    if (rc) return rc;
     if (deterministic) {
         const int64_t hub_virtual = rs.rows - rs.hub_base;          // copies x hub rows
         const int K = rs.hub_rows > 0 ? (int)(hub_virtual / rs.hub_rows) : 0;
-        const size_t need = (size_t)hub_virtual * D;
-        if (need > g_c.hub_sums_cap) {
-            if ((rc = regrow(g_c.hub_sums, need, "hub copy sums"))) return rc;
-            if ((rc = hip_check(hipMemsetAsync(g_c.hub_sums, 0, sizeof(float) * need, stream), "zero hub copy sums"))) return rc;
-            g_c.hub_sums_cap = need;
-        }
-#define KGE_SEGR(LL, CC)                                                                                              \
-    {                                                                                                                 \
-        long long nb = (M + (256 / LL) - 1) / (256 / LL);                                                             \
-        if (nb > 16384) nb = 16384;                                                                                   \
-        hipLaunchKernelGGL((segsum_f32_runs_kernel<LL, CC>), dim3((unsigned)nb), dim3(256), 0, stream, rec, g_c.dst_sorted, \
-                           g_c.ids_sorted, n_valid_p, rs, D, g_c.hub_sums);                                           \
-    }
-        if (D <= 16) KGE_SEGR(16, 1) else if (D <= 32) KGE_SEGR(16, 2) else if (D <= 64) KGE_SEGR(16, 4)
-        else if (D <= 128) KGE_SEGR(32, 4) else if (D <= 256) KGE_SEGR(64, 4) else if (D <= 512) KGE_SEGR(64, 8) else KGE_SEGR(64, 16)
-#undef KGE_SEGR
+        if ((rc = ensure_hub_sums((size_t)hub_virtual * D, stream))) return rc;
+        for_team_shape_or_last(D, [&](auto t) {
+            constexpr int L = decltype(t)::L, C = decltype(t)::C;
+            long long nb = (M + (256 / L) - 1) / (256 / L);
+            if (nb > 16384) nb = 16384;
+            hipLaunchKernelGGL((segsum_f32_runs_kernel<L, C>), dim3((unsigned)nb), dim3(256), 0, stream, rec, g_c.dst_sorted,
+                               g_c.ids_sorted, n_valid_p, rs, D, g_c.hub_sums);
+        });
         if (K > 0) {
             long long nb = (rs.hub_rows * D + 255) / 256;
             if (nb > 4096) nb = 4096;
@@ -1189,16 +1217,13 @@ int float_records_reduce(int64_t M, int D, const FloatRowSpace &rs, hipStream_t 
     }
     // shorter chunks while the step is small: the per-team record loop is a chain of dependent loads
     const int chunk_len = M >= (int64_t(1) << 20) ? 64 : (M >= (int64_t(1) << 18) ? 32 : 16);
-#define KGE_SEGF(LL, CC)                                                                                              \
-    {                                                                                                                 \
-        const long long chunks = (M + chunk_len - 1) / chunk_len;                                                     \
-        const long long nb = (chunks + (256 / LL) - 1) / (256 / LL);                                                  \
-        hipLaunchKernelGGL((segsum_f32_kernel<LL, CC>), dim3((unsigned)nb), dim3(256), 0, stream, rec, g_c.dst_sorted, \
-                           g_c.ids_sorted, n_valid_p, rs, D, chunk_len);                                              \
-    }
-    if (D <= 16) KGE_SEGF(16, 1) else if (D <= 32) KGE_SEGF(16, 2) else if (D <= 64) KGE_SEGF(16, 4)
-    else if (D <= 128) KGE_SEGF(32, 4) else if (D <= 256) KGE_SEGF(64, 4) else if (D <= 512) KGE_SEGF(64, 8) else KGE_SEGF(64, 16)
-#undef KGE_SEGF
+    for_team_shape_or_last(D, [&](auto t) {
+        constexpr int L = decltype(t)::L, C = decltype(t)::C;
+        const long long chunks = (M + chunk_len - 1) / chunk_len;
+        const long long nb = (chunks + (256 / L) - 1) / (256 / L);
+        hipLaunchKernelGGL((segsum_f32_kernel<L, C>), dim3((unsigned)nb), dim3(256), 0, stream, rec, g_c.dst_sorted,
+                           g_c.ids_sorted, n_valid_p, rs, D, chunk_len);
+    });
     return hip_check(hipGetLastError(), "float records reduce launch");
 }
 
@@ -1211,23 +1236,11 @@ int float_records_reduce_adam(int64_t M, int D, const FloatRowSpace &rs, const A
     if ((rc = ensure_counts_work(M, ext ? 0 : (size_t)D))) return rc;
     const float *rec = ext ? rec_ext : reinterpret_cast<const float *>(g_c.rec);
     int32_t *dst = ext ? dst_ext : g_c.dst;
-    const int rows = (int)rs.rows;
-    int blocks = (int)((M + 255) / 256);
-    if (blocks > 4096) blocks = 4096;
-    hipLaunchKernelGGL(blank_keys_kernel, dim3(blocks), dim3(256), 0, stream, dst, (long long)M, rows);
-    size_t tmp = g_c.sort_tmp_bytes;
-    rc = hip_check(rocprim::radix_sort_pairs(g_c.sort_tmp, tmp, dst, g_c.dst_sorted, g_c.ids, g_c.ids_sorted, (size_t)M, 0,
-                                             bits_for_rows(rows), stream), "float records sort");
-    if (rc) return rc;
-    hipLaunchKernelGGL(count_valid_kernel, dim3(1), dim3(64), 0, stream, g_c.dst_sorted, (int)M, rows, g_c.n_valid);
+    const int32_t *n_valid_p;
+    if ((rc = radix_sort_records(dst, M, (int)rs.rows, true, "float records sort", stream, n_valid_p))) return rc;
     const int64_t hub_virtual = rs.rows - rs.hub_base;          // copies x hub rows
     const int K = rs.hub_rows > 0 ? (int)(hub_virtual / rs.hub_rows) : 0;
-    const size_t need = (size_t)hub_virtual * D;
-    if (need > g_c.hub_sums_cap) {
-        if ((rc = regrow(g_c.hub_sums, need, "hub copy sums"))) return rc;
-        if ((rc = hip_check(hipMemsetAsync(g_c.hub_sums, 0, sizeof(float) * need, stream), "zero hub copy sums"))) return rc;
-        g_c.hub_sums_cap = need;
-    }
+    if ((rc = ensure_hub_sums((size_t)hub_virtual * D, stream))) return rc;
     if ((size_t)hub_virtual > g_c.hub_marks_cap) {
         if ((rc = regrow(g_c.hub_marks, (size_t)hub_virtual, "hub copy marks"))) return rc;
         if ((rc = hip_check(hipMemsetAsync(g_c.hub_marks, 0, sizeof(int32_t) * (size_t)hub_virtual, stream), "zero hub copy marks"))) return rc;
@@ -1238,29 +1251,13 @@ int float_records_reduce_adam(int64_t M, int D, const FloatRowSpace &rs, const A
     const float *const bases[4] = {rs.g_ent, rs.g_rel, rs.g_auxr, rs.g_auxe};
     for (int t = 0; t < 4; t++)
         vec = vec && ((reinterpret_cast<uintptr_t>(bases[t]) | reinterpret_cast<uintptr_t>(ad.m[t]) | reinterpret_cast<uintptr_t>(ad.v[t])) & 15) == 0;
-#define KGE_SEGA(LL, CC, VV)                                                                                          \
-    {                                                                                                                 \
-        long long nb = (M + (256 / LL) - 1) / (256 / LL);                                                             \
-        if (nb > 16384) nb = 16384;                                                                                   \
-        hipLaunchKernelGGL((segsum_adam_runs_kernel<LL, CC, VV>), dim3((unsigned)nb), dim3(256), 0, stream, rec, g_c.dst_sorted, \
-                           g_c.ids_sorted, g_c.n_valid, rs, ad, D, g_c.hub_sums, g_c.hub_marks);                      \
-        if (K > 0) {                                                                                                  \
-            long long nf = (rs.hub_rows + (256 / LL) - 1) / (256 / LL);                                               \
-            if (nf > 16384) nf = 16384;                                                                               \
-            hipLaunchKernelGGL((hub_fold_adam_kernel<LL, CC, VV>), dim3((unsigned)nf), dim3(256), 0, stream, g_c.hub_sums, g_c.hub_marks, \
-                               rs, ad, D, K);                                                                         \
-        }                                                                                                             \
-    }
-    const int units = vec ? D / 4 : D;       // groups of V floats per row
-    if (vec) {
-        if (units <= 16) KGE_SEGA(16, 1, 4) else if (units <= 32) KGE_SEGA(16, 2, 4) else if (units <= 64) KGE_SEGA(16, 4, 4)
-        else if (units <= 128) KGE_SEGA(32, 4, 4) else KGE_SEGA(64, 4, 4)
-    } else {
-        if (units <= 16) KGE_SEGA(16, 1, 1) else if (units <= 32) KGE_SEGA(16, 2, 1) else if (units <= 64) KGE_SEGA(16, 4, 1)
-        else if (units <= 128) KGE_SEGA(32, 4, 1) else if (units <= 256) KGE_SEGA(64, 4, 1) else if (units <= 512) KGE_SEGA(64, 8, 1)
-        else KGE_SEGA(64, 16, 1)
-    }
-#undef KGE_SEGA
+    // groups of V floats per row; the float4 ladder stops at (64, 4): 256 units = width 1024
+    const int units = vec ? std::min(D / 4, 256) : D;
+    for_team_shape_or_last(units, [&](auto t) {
+        constexpr int L = decltype(t)::L, C = decltype(t)::C;
+        if (!vec) launch_segsum_adam<L, C, 1>(M, rec, rs, ad, D, K, stream);
+        else if constexpr (C <= 4) launch_segsum_adam<L, C, 4>(M, rec, rs, ad, D, K, stream);
+    });
     return hip_check(hipGetLastError(), "float records lazy Adam reduce launch");
 }
 
@@ -1289,32 +1286,11 @@ int pair_records_reduce(int model, int64_t M, int64_t n_int8, int D, int rd, int
     const int rows = (int)(ent_total * rel_total);
     const int rpb = (rows + NB - 1) / NB;
     const int32_t *n_valid_p;
-    if (rpb <= 8192 && !engine().counts_force_sort) {
-        // two-level counting sort: key spaces up to NB * 8192 = 4.2 M (entity, relation) pairs
-        const int n_tiles = (int)((M + BTILE - 1) / BTILE);
-        if (!g_c.bucket_start) {
-            if ((rc = regrow(g_c.bucket_start, NB + 2, "counts bucket_start"))) return rc;
-            if ((rc = regrow(g_c.tile_hist, 2 * (NB + 2), "counts bucket totals/cursors"))) return rc;
-            if ((rc = hip_check(hipMemset(g_c.tile_hist, 0, sizeof(int32_t) * 2 * (NB + 2)), "zero bucket totals"))) return rc;
-        }
-        int32_t *totals = g_c.tile_hist, *cursor = g_c.tile_hist + (NB + 2);
-        int2 *pairs = reinterpret_cast<int2 *>(g_c.pairs);
-        launch_bkt_hist(n_tiles, (int)M, rpb, totals, nullptr, stream);
-        launch_bkt_scatter(n_tiles, (int)M, rpb, totals, cursor, pairs, stream);
-        launch_bkt_sort<false>(pairs, rpb, rows, totals, cursor, SegPlan(), stream);
-        n_valid_p = g_c.bucket_start + NB;   // start of the trash bucket == number of live records
-    } else {
-        // larger key spaces (e.g. FB15k: 14 951 entities x 1 345 relations): rocPRIM's radix sort on the same keys
-        int blocks = (int)((M + 255) / 256);
-        if (blocks > 4096) blocks = 4096;
-        hipLaunchKernelGGL(fix_keys_kernel, dim3(blocks), dim3(256), 0, stream, g_c.dst, (long long)M, rows);
-        size_t tmp = g_c.sort_tmp_bytes;
-        rc = hip_check(rocprim::radix_sort_pairs(g_c.sort_tmp, tmp, g_c.dst, g_c.dst_sorted, g_c.ids, g_c.ids_sorted, (size_t)M, 0,
-                                                 bits_for_rows(rows), stream), "pair records sort");
-        if (rc) return rc;
-        hipLaunchKernelGGL(count_valid_kernel, dim3(1), dim3(64), 0, stream, g_c.dst_sorted, (int)M, rows, g_c.n_valid);
-        n_valid_p = g_c.n_valid;
-    }
+    // two-level counting sort for key spaces up to NB * 8192 = 4.2 M (entity, relation) pairs; larger ones (e.g. FB15k: 14 951
+    // entities x 1 345 relations): the radix sort
+    if (rpb <= 8192 && !engine().counts_force_sort) rc = bucket_sort_records(g_c.dst, M, rows, rpb, nullptr, stream, n_valid_p);
+    else rc = radix_sort_records(g_c.dst, M, rows, false, "pair records sort", stream, n_valid_p);
+    if (rc) return rc;
     PairRed pr;
     pr.ent = tables[0]; pr.ctx = tables[2]; pr.auxe = tables[3];
     pr.g_ent = grads[0]; pr.g_auxe = grads[3];
@@ -1693,12 +1669,38 @@ __global__ __launch_bounds__(256) void segapply_kernel(SegApplyArgs sa) {
     }
 }
 
-#define KGE_SHAPE_DISPATCH(D, CALL)                                      \
-    if (D % 4 == 0 && D <= 64) { CALL(16, 4); }                          \
-    else if (D <= 16) { CALL(16, 1); } else if (D <= 32) { CALL(16, 2); } \
-    else if (D <= 64) { CALL(16, 4); } else if (D <= 128) { CALL(32, 4); } \
-    else if (D <= 256) { CALL(64, 4); } else if (D <= 512) { CALL(64, 8); } \
-    else { CALL(64, 16); }
+// segsum_kernel over the row-sorted records, one team per CHUNK records; nat: the records are in natural element order (D % 4 == 0)
+template <int L, int C>
+void launch_segsum(bool nat, int64_t M, const uint32_t *rec, const int32_t *n_valid_p, const int32_t *uidx, int32_t *S, int D,
+                   const FuseArgs &fold, hipStream_t stream) {
+    const long long chunks = (M + CHUNK - 1) / CHUNK;
+    const long long nb = (chunks + (256 / L) - 1) / (256 / L);
+    if (nat) hipLaunchKernelGGL((segsum_kernel<L, C, true>), dim3((unsigned)nb), dim3(256), 0, stream, rec, g_c.dst_sorted, g_c.ids_sorted,
+                                n_valid_p, uidx, S, D, fold);
+    else hipLaunchKernelGGL((segsum_kernel<L, C, false>), dim3((unsigned)nb), dim3(256), 0, stream, rec, g_c.dst_sorted, g_c.ids_sorted,
+                            n_valid_p, uidx, S, D, fold);
+}
+
+// apply_counts_kernel over a row list: row-wise SGD and lazy Adam are the same launch
+void launch_apply_listed_rows(const ApplyArgs &a, long long max_rows, hipStream_t stream) {
+    for_transe_team_shape_or_last(a.D, [&](auto t) {
+        constexpr int L = decltype(t)::L, C = decltype(t)::C;
+        long long nb = (max_rows + (256 / L) - 1) / (256 / L);
+        if (nb > 8192) nb = 8192;
+        hipLaunchKernelGGL((apply_counts_kernel<L, C, true>), dim3((unsigned)nb), dim3(256), 0, stream, a);
+    });
+}
+
+// The emit kernel's 1/|row| table stays current only when the apply launch about to be made rewrites its entries: the whole row
+// space of exactly the tables it was computed for.  Returns the table for ApplyArgs::inv_out then; any other update of those
+// tables makes it stale: null, and the tables are marked written.
+float *inv_table_kept(bool whole_row_space, const float *ent, const float *rel, long long all_rows) {
+    Engine &e = engine();
+    const bool keeps = e.inv_carry && e.inv_valid && e.inv_norm && whole_row_space && e.inv_for_ent == ent && e.inv_for_rel == rel &&
+                       e.inv_cap >= all_rows;
+    if (!keeps) tables_written();
+    return keeps ? e.inv_norm : nullptr;
+}
 
 
 }  // namespace
@@ -1767,9 +1769,7 @@ static int forward_counts_impl(const kge_model_desc *m, const float *d_ent, cons
     FuseArgs fold = FuseArgs();
     if (krel > 1) { fold.fold_E = (int)m->ent_total; fold.fold_R = (int)m->rel_total; }
     if (fused) {
-        int L_, C_;
-        transe_team_shape(D, L_, C_);
-        const int cap = std::min(engine().counts_fused_cap > 0 ? engine().counts_fused_cap : 64, std::min(127, 4 * L_));   // (the kernel holds min(128, 4 L) ids per list; 127: the packed 2-bit sums stay below 256)
+        const int cap = std::min(engine().counts_fused_cap > 0 ? engine().counts_fused_cap : 64, std::min(127, 4 * L));   // (the kernel holds min(128, 4 L) ids per list; 127: the packed 2-bit sums stay below 256)
         const int64_t max_pieces = 3 * (M / cap + 1) + 16;     // sum of ceil(c / cap) over both lists of the rows with a list of more than cap records
         if (max_pieces > g_c.pieces_cap) {
             if ((rc = regrow(g_c.pieces, (size_t)max_pieces, "fused step piece table"))) return rc;
@@ -1783,19 +1783,10 @@ static int forward_counts_impl(const kge_model_desc *m, const float *d_ent, cons
             if ((rc = regrow(g_c.row_span, (size_t)rows2, "fused step row spans"))) return rc;
             g_c.row_span_cap = rows2;
         }
-        const int n_tiles = (int)((M + BTILE - 1) / BTILE);
-        if (!g_c.bucket_start) {
-            if ((rc = regrow(g_c.bucket_start, NB + 2, "counts bucket_start"))) return rc;
-            if ((rc = regrow(g_c.tile_hist, 2 * (NB + 2), "counts bucket totals/cursors"))) return rc;
-            if ((rc = hip_check(hipMemset(g_c.tile_hist, 0, sizeof(int32_t) * 2 * (NB + 2)), "zero bucket totals"))) return rc;
-        }
-        int32_t *totals = g_c.tile_hist, *cursor = g_c.tile_hist + (NB + 2);
-        int2 *pairs = reinterpret_cast<int2 *>(g_c.pairs);
         SegPlan plan;
         plan.row_span = g_c.row_span; plan.pieces = g_c.pieces; plan.n_pieces = g_c.n_pieces; plan.cap = cap;
-        launch_bkt_hist(n_tiles, (int)M, rpb2, totals, g_c.n_pieces, stream);
-        launch_bkt_scatter(n_tiles, (int)M, rpb2, totals, cursor, pairs, stream);
-        launch_bkt_sort<true>(pairs, rpb2, rows2, totals, cursor, plan, stream);
+        const int32_t *n_valid_p;
+        if ((rc = bucket_sort_records(g_c.dst, M, rows2, rpb2, &plan, stream, n_valid_p))) return rc;
         const long long all_rows = m->ent_total + m->rel_total;
         SegApplyArgs sa = {};
         sa.rec = g_c.rec; sa.rec2_off = (unsigned)((size_t)3 * (size_t)n_pos * rd * 4); sa.ids = g_c.ids_sorted; sa.row_span = g_c.row_span;
@@ -1807,76 +1798,34 @@ static int forward_counts_impl(const kge_model_desc *m, const float *d_ent, cons
         a.S = d_counts; a.rows = all_rows; a.row_lo = 0; a.E = m->ent_total; a.D = D;
         a.unit = 1.0f / (float)denom; a.lr = fo->lr; a.b1 = fo->b1; a.b2 = fo->b2; a.eps = fo->eps; a.adam = fo->adam;
         a.row_span = g_c.row_span; a.span_cap = cap;
-        {
-            Engine &e = engine();     // (as kge_transe_apply_counts_range: the two kernels together rewrite every row's 1/|row| entry)
-            const bool keeps = e.inv_carry && e.inv_valid && e.inv_norm && e.inv_for_ent == fo->p[0] && e.inv_for_rel == fo->p[1] && e.inv_cap >= all_rows;
-            if (keeps) a.inv_out = e.inv_norm;
-            else tables_written();
-        }
-#define KGE_SEGAPPLY(LL, CC)                                                                                          \
-    {                                                                                                                 \
-        const long long nb = ((long long)rows + max_pieces + (256 / LL) - 1) / (256 / LL);                            \
-        hipLaunchKernelGGL((segapply_kernel<LL, CC>), dim3((unsigned)nb), dim3(256), 0, stream, sa);                   \
-        long long nb2 = (all_rows + (256 / LL) - 1) / (256 / LL);                                                     \
-        if (nb2 > 8192) nb2 = 8192;                                                                                   \
-        SamplerArgs ride = {};                                                                                        \
-        const unsigned n_ride = take_ride(ride, 3);                                                                   \
-        hipLaunchKernelGGL((apply_counts_kernel<LL, CC, false>), dim3((unsigned)nb2 + n_ride), dim3(256), 0, stream, a, ride, (int)nb2); \
-    }
-        if (D <= 64) KGE_SEGAPPLY(16, 4) else if (D <= 128) KGE_SEGAPPLY(32, 4) else if (D <= 256) KGE_SEGAPPLY(64, 4)
-        else if (D <= 512) KGE_SEGAPPLY(64, 8) else KGE_SEGAPPLY(64, 16)
-#undef KGE_SEGAPPLY
+        a.inv_out = inv_table_kept(true, fo->p[0], fo->p[1], all_rows);   // (the two kernels together rewrite every row's 1/|row| entry)
+        const bool shaped = for_transe_team_shape(D, [&](auto t) {
+            constexpr int L = decltype(t)::L, C = decltype(t)::C;
+            if constexpr (C >= 4) {   // natural-layout records only: the ladder starts at (16, 4)
+                const long long nb = ((long long)rows + max_pieces + (256 / L) - 1) / (256 / L);
+                hipLaunchKernelGGL((segapply_kernel<L, C>), dim3((unsigned)nb), dim3(256), 0, stream, sa);
+                long long nb2 = (all_rows + (256 / L) - 1) / (256 / L);
+                if (nb2 > 8192) nb2 = 8192;
+                SamplerArgs ride = {};
+                const unsigned n_ride = take_ride(ride, 3);
+                hipLaunchKernelGGL((apply_counts_kernel<L, C, false>), dim3((unsigned)nb2 + n_ride), dim3(256), 0, stream, a, ride, (int)nb2);
+            }
+        });
+        if (!shaped) return fail(KGE_ERR_UNSUPPORTED, "sign-count path: TransE, dim <= 1024, 1..63 negatives");
         fo->done = true;
         return hip_check(hipGetLastError(), "fused counts step launch");
     }
-    if (rpb <= 8192 && !engine().counts_force_sort) {
-        // ---- two-level counting sort (hand-written) + segmented sum: row spaces up to NB*8192 rows ----
-        const int n_tiles = (int)((M + BTILE - 1) / BTILE);
-        if (!g_c.bucket_start) {
-            if ((rc = regrow(g_c.bucket_start, NB + 2, "counts bucket_start"))) return rc;
-            if ((rc = regrow(g_c.tile_hist, 2 * (NB + 2), "counts bucket totals/cursors"))) return rc;
-            if ((rc = hip_check(hipMemset(g_c.tile_hist, 0, sizeof(int32_t) * 2 * (NB + 2)), "zero bucket totals"))) return rc;
-        }
-        int32_t *totals = g_c.tile_hist, *cursor = g_c.tile_hist + (NB + 2);
-        int2 *pairs = reinterpret_cast<int2 *>(g_c.pairs);
-        launch_bkt_hist(n_tiles, (int)M, rpb, totals, nullptr, stream);
-        launch_bkt_scatter(n_tiles, (int)M, rpb, totals, cursor, pairs, stream);
-        launch_bkt_sort<false>(pairs, rpb, rows, totals, cursor, SegPlan(), stream);
-        const int32_t *n_valid_p = g_c.bucket_start + NB;   // start of the trash bucket == number of live records
-#define KGE_SEG2(LL, CC)                                                                                              \
-    {                                                                                                                 \
-        const long long chunks = (M + CHUNK - 1) / CHUNK;                                                             \
-        const long long nb = (chunks + (256 / LL) - 1) / (256 / LL);                                                  \
-        if (nat) hipLaunchKernelGGL((segsum_kernel<LL, CC, true>), dim3((unsigned)nb), dim3(256), 0, stream, g_c.rec,  \
-                                    g_c.dst_sorted, g_c.ids_sorted, n_valid_p, nullptr, d_counts, D, fold);           \
-        else hipLaunchKernelGGL((segsum_kernel<LL, CC, false>), dim3((unsigned)nb), dim3(256), 0, stream, g_c.rec,     \
-                                g_c.dst_sorted, g_c.ids_sorted, n_valid_p, nullptr, d_counts, D, fold);               \
-    }
-        KGE_SHAPE_DISPATCH(D, KGE_SEG2)
-#undef KGE_SEG2
-        return hip_check(hipGetLastError(), "counts bucket reduce launch");
-    }
-    // ---- general path: sort + segmented sum (large row spaces) ----
-    int blocks = (int)((M + 255) / 256);
-    if (blocks > 4096) blocks = 4096;
-    hipLaunchKernelGGL(fix_keys_kernel, dim3(blocks), dim3(256), 0, stream, g_c.dst, (long long)M, rows);
-    size_t tmp = g_c.sort_tmp_bytes;
-    rc = hip_check(rocprim::radix_sort_pairs(g_c.sort_tmp, tmp, g_c.dst, g_c.dst_sorted, g_c.ids, g_c.ids_sorted, (size_t)M, 0,
-                                             bits_for_rows(rows), stream), "counts sort");
+    // two-level counting sort (hand-written): row spaces up to NB*8192 rows; general path (large row spaces): radix sort
+    const bool bucket = rpb <= 8192 && !engine().counts_force_sort;
+    const int32_t *n_valid_p;
+    if (bucket) rc = bucket_sort_records(g_c.dst, M, rows, rpb, nullptr, stream, n_valid_p);
+    else rc = radix_sort_records(g_c.dst, M, rows, false, "counts sort", stream, n_valid_p);
     if (rc) return rc;
-    hipLaunchKernelGGL(count_valid_kernel, dim3(1), dim3(64), 0, stream, g_c.dst_sorted, (int)M, rows, g_c.n_valid);
-#define KGE_SEG(LL, CC)                                                                                               \
-    {                                                                                                                 \
-        const long long chunks = (M + CHUNK - 1) / CHUNK;                                                             \
-        const long long nb = (chunks + (256 / LL) - 1) / (256 / LL);                                                  \
-        if (nat) hipLaunchKernelGGL((segsum_kernel<LL, CC, true>), dim3((unsigned)nb), dim3(256), 0, stream, g_c.rec,  \
-                                    g_c.dst_sorted, g_c.ids_sorted, g_c.n_valid, nullptr, d_counts, D, fold);         \
-        else hipLaunchKernelGGL((segsum_kernel<LL, CC, false>), dim3((unsigned)nb), dim3(256), 0, stream, g_c.rec,     \
-                                g_c.dst_sorted, g_c.ids_sorted, g_c.n_valid, nullptr, d_counts, D, fold);             \
-    }
-    KGE_SHAPE_DISPATCH(D, KGE_SEG)
-#undef KGE_SEG
-    return hip_check(hipGetLastError(), "counts reduce launch");
+    if (!for_transe_team_shape(D, [&](auto t) {
+            launch_segsum<decltype(t)::L, decltype(t)::C>(nat, M, g_c.rec, n_valid_p, nullptr, d_counts, D, fold, stream);
+        }))
+        return fail(KGE_ERR_UNSUPPORTED, "sign-count path: TransE, dim <= 1024, 1..63 negatives");
+    return hip_check(hipGetLastError(), bucket ? "counts bucket reduce launch" : "counts reduce launch");
 }
 
 extern "C" {
@@ -1961,12 +1910,8 @@ static int reduce_records_impl(const kge_model_desc *m, const uint32_t *d_rec, i
     int blocks = (int)((M + 255) / 256);
     if (blocks > 4096) blocks = 4096;
     // order (row, record id) pairs by row: rocPRIM radix sort handles any row space
-    hipLaunchKernelGGL(fix_keys_kernel, dim3(blocks), dim3(256), 0, stream, d_dst, (long long)M, rows);
-    size_t tmp = g_c.sort_tmp_bytes;
-    rc = hip_check(rocprim::radix_sort_pairs(g_c.sort_tmp, tmp, d_dst, g_c.dst_sorted, g_c.ids, g_c.ids_sorted, (size_t)M, 0,
-                                             bits_for_rows(rows), stream), "records sort");
-    if (rc) return rc;
-    hipLaunchKernelGGL(count_valid_kernel, dim3(1), dim3(64), 0, stream, g_c.dst_sorted, (int)M, rows, g_c.n_valid);
+    const int32_t *n_valid_p;
+    if ((rc = radix_sort_records(d_dst, M, rows, false, "records sort", stream, n_valid_p))) return rc;
     // unique-row index of every record (flags -> inclusive scan), row list, boundary rows cleared
     int32_t *uidx = g_c.pairs;   // [M] scratch
     hipLaunchKernelGGL(run_flags_kernel, dim3(blocks), dim3(256), 0, stream, g_c.dst_sorted, g_c.n_valid, (int)M, uidx);
@@ -1998,32 +1943,22 @@ static int reduce_records_impl(const kge_model_desc *m, const uint32_t *d_rec, i
         hipLaunchKernelGGL(zero_boundary_rows_kernel, dim3((unsigned)zb), dim3(256), 0, stream, uidx, g_c.n_valid, d_row_counts, D);
     }
     if (fuse) {
-#define KGE_SEGFUSE(LL, CC)                                                                                           \
-    {                                                                                                                 \
-        const long long chunks = (M + CHUNK - 1) / CHUNK;                                                             \
-        const long long nb = (chunks + (256 / LL) - 1) / (256 / LL);                                                  \
-        hipLaunchKernelGGL((segsum_kernel<LL, CC, true, true>), dim3((unsigned)nb), dim3(256), 0, stream, d_rec,      \
-                           g_c.dst_sorted, g_c.ids_sorted, g_c.n_valid, uidx, d_row_counts, D, *fuse);                \
-        long long nb2 = (M + (256 / LL) - 1) / (256 / LL);                                                            \
-        if (nb2 > 8192) nb2 = 8192;                                                                                   \
-        hipLaunchKernelGGL((apply_rows_nat_kernel<LL, CC>), dim3((unsigned)nb2), dim3(256), 0, stream, *fuse, d_rows,  \
-                           d_row_counts, d_n_rows, bflag, D);                                                         \
-    }
-        KGE_SHAPE_DISPATCH(D, KGE_SEGFUSE)
-#undef KGE_SEGFUSE
+        for_transe_team_shape_or_last(D, [&](auto t) {
+            constexpr int L = decltype(t)::L, C = decltype(t)::C;
+            const long long chunks = (M + CHUNK - 1) / CHUNK;
+            const long long nb = (chunks + (256 / L) - 1) / (256 / L);
+            hipLaunchKernelGGL((segsum_kernel<L, C, true, true>), dim3((unsigned)nb), dim3(256), 0, stream, d_rec,
+                               g_c.dst_sorted, g_c.ids_sorted, g_c.n_valid, uidx, d_row_counts, D, *fuse);
+            long long nb2 = (M + (256 / L) - 1) / (256 / L);
+            if (nb2 > 8192) nb2 = 8192;
+            hipLaunchKernelGGL((apply_rows_nat_kernel<L, C>), dim3((unsigned)nb2), dim3(256), 0, stream, *fuse, d_rows,
+                               d_row_counts, d_n_rows, bflag, D);
+        });
         return hip_check(hipGetLastError(), "records reduce+apply launch");
     }
-#define KGE_SEGC(LL, CC)                                                                                              \
-    {                                                                                                                 \
-        const long long chunks = (M + CHUNK - 1) / CHUNK;                                                             \
-        const long long nb = (chunks + (256 / LL) - 1) / (256 / LL);                                                  \
-        if (nat) hipLaunchKernelGGL((segsum_kernel<LL, CC, true>), dim3((unsigned)nb), dim3(256), 0, stream, d_rec,    \
-                                    g_c.dst_sorted, g_c.ids_sorted, g_c.n_valid, uidx, d_row_counts, D);              \
-        else hipLaunchKernelGGL((segsum_kernel<LL, CC, false>), dim3((unsigned)nb), dim3(256), 0, stream, d_rec,       \
-                                g_c.dst_sorted, g_c.ids_sorted, g_c.n_valid, uidx, d_row_counts, D);                  \
-    }
-    KGE_SHAPE_DISPATCH(D, KGE_SEGC)
-#undef KGE_SEGC
+    for_transe_team_shape_or_last(D, [&](auto t) {
+        launch_segsum<decltype(t)::L, decltype(t)::C>(nat, M, d_rec, g_c.n_valid, uidx, d_row_counts, D, FuseArgs(), stream);
+    });
     return hip_check(hipGetLastError(), "records reduce launch");
 }
 
@@ -2053,28 +1988,19 @@ int kge_transe_apply_rows_sgd(const kge_model_desc *m, float *d_ent, float *d_re
     if (D % 4 == 0) {   // the arithmetic of the fused kernel: a row gets the same bits whichever kernel handles it
         FuseArgs fz;
         fz.ent = d_ent; fz.rel = d_rel; fz.E = m->ent_total; fz.unit = 1.0f / (float)denom; fz.lr = lr;
-#define KGE_RNAT(LL, CC)                                                                                          \
-    {                                                                                                             \
-        long long nb = (max_rows + (256 / LL) - 1) / (256 / LL);                                                  \
-        if (nb > 8192) nb = 8192;                                                                                 \
-        hipLaunchKernelGGL((apply_rows_nat_kernel<LL, CC>), dim3((unsigned)nb), dim3(256), 0, stream, fz, d_rows, \
-                           d_row_counts, d_n_rows, (const int32_t *)nullptr, D);                                  \
-    }
-        KGE_SHAPE_DISPATCH(D, KGE_RNAT)
-#undef KGE_RNAT
+        for_transe_team_shape_or_last(D, [&](auto t) {
+            constexpr int L = decltype(t)::L, C = decltype(t)::C;
+            long long nb = (max_rows + (256 / L) - 1) / (256 / L);
+            if (nb > 8192) nb = 8192;
+            hipLaunchKernelGGL((apply_rows_nat_kernel<L, C>), dim3((unsigned)nb), dim3(256), 0, stream, fz, d_rows,
+                               d_row_counts, d_n_rows, (const int32_t *)nullptr, D);
+        });
         return hip_check(hipGetLastError(), "apply rows launch");
     }
     ApplyArgs a = {};
     a.p = d_ent; a.p2 = d_rel; a.row_list = d_rows; a.S = const_cast<int32_t *>(d_row_counts); a.n_rows = d_n_rows;
     a.E = m->ent_total; a.D = m->ent_dim; a.unit = 1.0f / (float)denom; a.lr = lr; a.adam = 0;
-#define KGE_RAPPLY(LL, CC)                                                                                  \
-    {                                                                                                       \
-        long long nb = (max_rows + (256 / LL) - 1) / (256 / LL);                                            \
-        if (nb > 8192) nb = 8192;                                                                           \
-        hipLaunchKernelGGL((apply_counts_kernel<LL, CC, true>), dim3((unsigned)nb), dim3(256), 0, stream, a); \
-    }
-    KGE_SHAPE_DISPATCH(D, KGE_RAPPLY)
-#undef KGE_RAPPLY
+    launch_apply_listed_rows(a, max_rows, stream);
     return hip_check(hipGetLastError(), "apply rows launch");
 }
 
@@ -2096,15 +2022,7 @@ int kge_transe_apply_rows_adam_lazy(const kge_model_desc *m, float *d_ent, float
     a.row_list = d_rows; a.S = const_cast<int32_t *>(d_row_counts); a.n_rows = d_n_rows;
     a.E = m->ent_total; a.D = m->ent_dim; a.unit = 1.0f / (float)denom; a.lr = lr_t; a.b1 = beta1; a.b2 = beta2; a.eps = eps; a.adam = 1;
     a.row_live = g_lazy_row_live; g_lazy_row_live = nullptr;      // (one call only)
-    const int D = m->ent_dim;
-#define KGE_RLAZY(LL, CC)                                                                                   \
-    {                                                                                                       \
-        long long nb = (max_rows + (256 / LL) - 1) / (256 / LL);                                            \
-        if (nb > 8192) nb = 8192;                                                                           \
-        hipLaunchKernelGGL((apply_counts_kernel<LL, CC, true>), dim3((unsigned)nb), dim3(256), 0, stream, a); \
-    }
-    KGE_SHAPE_DISPATCH(D, KGE_RLAZY)
-#undef KGE_RLAZY
+    launch_apply_listed_rows(a, max_rows, stream);
     return hip_check(hipGetLastError(), "lazy adam rows launch");
 }
 
@@ -2118,15 +2036,13 @@ int kge_transe_apply_counts(float *d_p, float *d_m, float *d_v, int32_t *d_count
     ApplyArgs a = {};
     a.p = d_p; a.m = d_m; a.v = d_v; a.S = d_counts; a.resid = d_resid; a.rows = rows; a.D = dim; a.E = rows;
     a.unit = 1.0f / (float)denom; a.lr = lr; a.b1 = beta1; a.b2 = beta2; a.eps = eps; a.adam = adam;
-    const int D = dim;
-#define KGE_APPLY(LL, CC)                                                                                   \
-    {                                                                                                       \
-        long long nb = (rows + (256 / LL) - 1) / (256 / LL);                                                \
-        if (nb > 4096) nb = 4096;                                                                           \
-        hipLaunchKernelGGL((apply_counts_kernel<LL, CC, false>), dim3((unsigned)nb), dim3(256), 0, stream, a); \
-    }
-    KGE_SHAPE_DISPATCH(D, KGE_APPLY)
-#undef KGE_APPLY
+    const bool shaped = for_transe_team_shape(dim, [&](auto t) {
+        constexpr int L = decltype(t)::L, C = decltype(t)::C;
+        long long nb = (rows + (256 / L) - 1) / (256 / L);
+        if (nb > 4096) nb = 4096;
+        hipLaunchKernelGGL((apply_counts_kernel<L, C, false>), dim3((unsigned)nb), dim3(256), 0, stream, a);
+    });
+    if (!shaped) return fail(KGE_ERR_UNSUPPORTED, "kge_transe_apply_counts: embedding dimension > 1024");
     return hip_check(hipGetLastError(), "apply counts launch");
 }
 
@@ -2148,26 +2064,15 @@ int kge_transe_apply_counts_range(const kge_model_desc *m, float *const d_p[2], 
     if (adam) { a.m = d_m[0]; a.m2 = d_m[1]; a.v = d_v[0]; a.v2 = d_v[1]; }
     a.S = d_counts_chunk; a.rows = row_hi; a.row_lo = row_lo; a.E = m->ent_total; a.D = m->ent_dim;
     a.unit = 1.0f / (float)denom; a.lr = lr; a.b1 = beta1; a.b2 = beta2; a.eps = eps; a.adam = adam;
-    {
-        // the emit kernel's 1/|row| table stays current only when THIS launch rewrites its entries: the whole row space of exactly
-        // the tables it was computed for; any other update of those tables makes it stale
-        Engine &e = engine();
-        const bool keeps = e.inv_carry && e.inv_valid && e.inv_norm && row_lo == 0 && row_hi == all_rows && e.inv_for_ent == d_p[0] &&
-                           e.inv_for_rel == d_p[1] && e.inv_cap >= all_rows;
-        if (keeps) a.inv_out = e.inv_norm;
-        else tables_written();
-    }
-    const int D = m->ent_dim;
-#define KGE_APPLY2(LL, CC)                                                                                  \
-    {                                                                                                       \
-        long long nb = (rows + (256 / LL) - 1) / (256 / LL);                                                \
-        if (nb > 8192) nb = 8192;                                                                           \
-        SamplerArgs ride = {};                                                                              \
-        const unsigned n_ride = take_ride(ride, 3);                                                         \
-        hipLaunchKernelGGL((apply_counts_kernel<LL, CC, false>), dim3((unsigned)nb + n_ride), dim3(256), 0, stream, a, ride, (int)nb); \
-    }
-    KGE_SHAPE_DISPATCH(D, KGE_APPLY2)
-#undef KGE_APPLY2
+    a.inv_out = inv_table_kept(row_lo == 0 && row_hi == all_rows, d_p[0], d_p[1], all_rows);
+    for_transe_team_shape_or_last(a.D, [&](auto t) {
+        constexpr int L = decltype(t)::L, C = decltype(t)::C;
+        long long nb = (rows + (256 / L) - 1) / (256 / L);
+        if (nb > 8192) nb = 8192;
+        SamplerArgs ride = {};
+        const unsigned n_ride = take_ride(ride, 3);
+        hipLaunchKernelGGL((apply_counts_kernel<L, C, false>), dim3((unsigned)nb + n_ride), dim3(256), 0, stream, a, ride, (int)nb);
+    });
     return hip_check(hipGetLastError(), "apply counts launch");
 }
 

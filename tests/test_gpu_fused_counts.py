@@ -53,7 +53,7 @@ def state(con):
     return out
 
 
-@pytest.mark.parametrize("dim", [200, 64, 100, 512, 16])
+@pytest.mark.parametrize("dim", [200, 64, 100, 512, 16, 520, 30, 7])
 @pytest.mark.parametrize("opt", ["Adam", "SGD"])
 @pytest.mark.parametrize("cap", [0, 7])
 def test_fused_step_equals_the_two_call_step_on_sampled_batches(dim, opt, cap):

@@ -213,7 +213,10 @@ def p_allowance(p1, step):
     return 2.0 ** -21 * np.abs(step).astype(np.float64) + np.spacing(np.abs(p1)).astype(np.float64)
 
 
-@pytest.mark.parametrize("model,D", [("transd", 4), ("transd", 7), ("transd", 200), ("transh", 1024), ("transe", 50)])
+@pytest.mark.parametrize("model,D", [("transd", 4), ("transd", 7), ("transd", 200), ("transh", 1024), ("transe", 50),
+                                     # the other rungs: float4 (16, 2) and (32, 4); scalar (16, 2), (32, 4), (64, 4), (64, 8), (64, 16)
+                                     ("transd", 100), ("transh", 260), ("transe", 30), ("transh", 70), ("transd", 130), ("transe", 258),
+                                     ("transh", 514)])
 def test_the_apply_stage_alone_bit_for_bit(model, D):
     """kge_float_records_apply_adam on made-up records, keys over the whole virtual row space (entity rows, ent_transfer rows,
     hub copies of both relation-side tables) plus keys that carry no record (-1, -7, rows, rows + 5): m and v must equal,

@@ -148,7 +148,7 @@ def check_near_tie_rule(con, path, out_new, out_old, test_head):
 # ---------------------------------------------------------------------------------------------------------------------------
 # 1-4: one process
 # ---------------------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("dim", [24, 48, 200, 512])
+@pytest.mark.parametrize("dim", [12, 24, 48, 100, 200, 512, 520])
 @pytest.mark.parametrize("test_head", [True, False])
 def test_whole_table_as_one_range_matches_the_ranker(dim, test_head):
     require_entry_points()

@@ -90,7 +90,7 @@ def make_engine(model, E, R, D, n, nr, margin=1.0, opt="SGD", alpha=0.01, params
 
 
 CASES = [("transe", 300, 11, 16), ("transe", 300, 11, 100), ("transe", 200, 7, 200), ("transe", 100, 5, 512),
-         ("transe", 64, 5, 50), ("transe", 64, 5, 7),
+         ("transe", 64, 5, 50), ("transe", 64, 5, 7), ("transe", 64, 5, 30), ("transh", 64, 5, 520),
          ("transh", 300, 11, 24), ("transh", 200, 7, 200), ("transh", 64, 5, 100),
          ("transd", 300, 11, 20), ("transd", 200, 7, 200), ("transd", 64, 5, 100)]
 

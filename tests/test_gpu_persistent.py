@@ -47,6 +47,7 @@ def update_err(got, want, start, tol):
     ("TransD", "fb", 64, 0, 2, 1, "Adam"),
     ("TransE", "small", 50, 7, 3, 1, "Adam"),     # ragged slices (857 positives over 8 threads), dim % 4 != 0
     ("TransH", "small", 24, 10, 2, 0, "SGD"),
+    ("TransH", "small", 12, 10, 2, 0, "SGD"),
 ])
 def test_persistent_steps_equal_separate_launches(fb_dir, wn_dir, model, graph, dim, nbatches, n, nr, opt):
     from openkeonspark_amd import _lib

@@ -19,6 +19,8 @@ MARGIN = 64                 # int32 elements (256 bytes: the 16-byte accesses of
 KGE_ERR_BAD_ARG = -3
 DIMS = [4, 48, 64, 68, 128, 200, 256, 260, 512, 1024]     # every branch of transe_team_shape, both sides of the 64-dword line
 RECORD_DWORDS = {4: 16, 48: 16, 64: 16, 68: 32, 128: 32, 200: 64, 256: 64, 260: 128, 512: 128, 1024: 256}
+SCALAR_DIMS = [7, 30]     # the two scalar rungs (16, 1) and (16, 2), which only widths that are no multiple of 4 take
+RECORD_DWORDS.update({7: 16, 30: 16})
 
 
 def _env():
@@ -308,9 +310,10 @@ def test_record_ids(n_records):
     assert np.array_equal(ids.get(), np.where(slot, cache_ids[np.where(slot, dst, 0)], -1))
 
 
-@pytest.mark.parametrize("dim", DIMS)
+@pytest.mark.parametrize("dim", DIMS + SCALAR_DIMS)
 def test_pack_records(dim):
-    """out[slot_of[m], :] = rec[m, :] for slot_of[m] >= 0; output rows no record is sent to stay as they were."""
+    """out[slot_of[m], :] = rec[m, :] for slot_of[m] >= 0; output rows no record is sent to stay as they were.  (The packing copies
+    dwords whatever they hold, so the scalar widths ride along: their record size is what is checked for them.)"""
     torch, _lib, L = _env()
     rng = np.random.default_rng(dim + 1)
     dw = RECORD_DWORDS[dim]

@@ -104,7 +104,7 @@ def run_mixed(con, fixed, rel, head, k, **kw):
     return ids.cpu().numpy().astype(np.int64), sc.cpu().numpy()
 
 
-CASES = [("TransE", 16), ("TransE", 40), ("TransE", 200), ("TransE", 512),
+CASES = [("TransE", 16), ("TransE", 30), ("TransE", 40), ("TransE", 100), ("TransE", 200), ("TransE", 512), ("TransE", 520),
          ("TransH", 16), ("TransH", 40), ("TransH", 200),
          ("TransD", 16), ("TransD", 40), ("TransD", 200),
          ("TransR", 16), ("TransR", 40), ("TransR", 200)]
