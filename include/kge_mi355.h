@@ -530,6 +530,22 @@ int kge_link_prediction_finish(INT first, INT count, INT test_head, const int64_
 /* d_ids (DEVICE int32 [count][2]) = the head and tail ids of test triples [first, first+count), kge_link_prediction's order. */
 int kge_test_entity_ids(INT first, INT count, int32_t *d_ids, void *stream);
 
+/* Filtered ranks of caller-supplied triples on the device (csrc/rank.hip): triple i = (d_h[i], d_t[i], d_r[i]) (DEVICE int32),
+ * in any order, with any mix of relations and with duplicates -- the validation split, or any triples of the caller's.
+ * d_counts (DEVICE int64 [n][2][4], every element written): side 0 ranks all entities as the tail of (h, r, ?), side 1 as the
+ * head of (?, r, t) (all zeros when test_head == 0); the four columns are the numbers of candidates other than the target that
+ * score strictly below the true triple -- raw, filtered, typed, filtered + typed -- exactly as columns 0..3 of
+ * kge_link_prediction's 8-vectors: NaN never counts, the filter is the train + valid + test union of importTestFiles (the triple
+ * itself need not be in it), typed means membership in the relation's head / tail type list (0 without importTypeFiles).  No
+ * arg-mins and no ontology classes.  The scores are kge_predict's bits, the ones kge_link_prediction ranks (TransR: each
+ * relation's own matrix).  All four models; embedding dimension (TransR: relation dimension) <= 1024, KGE_ERR_UNSUPPORTED above.
+ * Needs importTestFiles (KGE_ERR_NO_DATASET).  Ids are the caller's precondition.  No [n x E] score matrix is formed; one host
+ * synchronisation (the triples are grouped by relation).  With n == 0 only the arguments (null pointers included) and the files are checked.  Nothing is
+ * written to d_counts when an error is returned.  Option "rank_slices" (test hook): N > 0 cuts the candidates into N slices,
+ * 0 chooses; the counts do not depend on it. */
+int kge_rank_triples(const kge_model_desc *m, const float *const tables[KGE_MAX_TABLES], const int32_t *d_h, const int32_t *d_t,
+                     const int32_t *d_r, INT n, INT test_head, int64_t *d_counts, void *stream);
+
 /* Batched top-k entity prediction on the device.  Query i: d_head[i] == 0 asks for the k best tails of (d_fixed[i], d_rel[i], ?),
  * d_head[i] != 0 for the k best heads of (?, d_rel[i], d_fixed[i]); sides and relations may be mixed in any order.  d_ids /
  * d_scores (DEVICE, row-major [n][k]) receive the candidates in ascending (score, id) order -- NaN after every number -- with

@@ -1863,6 +1863,72 @@ class Config(object):
                                                     1 if test_head else 0, out.ctypes.data, self._stream()), self.lib)
         return out, self._lp_normalise(self._lp_sums(out, test_head), count)
 
+    def _rank_device(self, dev, test_head):
+        """kge_rank_triples on an int32 device tensor [3, n] (h, t, r; ids already checked) -> int64 numpy [n, 2, 4]."""
+        import torch
+        n = dev.shape[1]
+        counts = torch.empty((n, 2, 4), dtype=torch.int64, device=self.device)
+        # (an empty tensor has no address and the entry point refuses null pointers: n == 0 still checks the files, on a spare row)
+        ids, out = (dev, counts) if n else (torch.zeros((3, 1), dtype=torch.int32, device=self.device),
+                                            torch.zeros((1, 2, 4), dtype=torch.int64, device=self.device))
+        _lib.check(self.lib.kge_rank_triples(ctypes.byref(self._desc), self._tab_ptrs, ids[0].data_ptr(), ids[1].data_ptr(),
+                                             ids[2].data_ptr(), n, 1 if test_head else 0, out.data_ptr(), self._stream()), self.lib)
+        return counts.cpu().numpy()
+
+    def _refuse_sharded_rank(self, what):
+        if self._sharded("ent_embeddings"):
+            raise KgeError("%s over an entity table sharded across ranks is not supported: rank the test triples with "
+                           "link_prediction (a collective on sharded tables) instead" % what)
+
+    def rank_triples(self, h, t, r, test_head=True):
+        """Rank any triples on the device (kge_rank_triples): h, t, r are 1-D id arrays of one length, in any order, with any
+        mix of relations and with duplicates -- the validation split, or triples of the caller's own.  Returns (counts int64
+        [n, 2, 4], metrics): counts[i, 0] ranks every entity as the tail of (h, r, ?), counts[i, 1] as the head of (?, r, t)
+        (zeros with test_head=False); the columns are the numbers of candidates other than the target that score strictly below
+        the true triple -- raw, filtered (train + valid + test), typed, filtered + typed -- exactly columns 0..3 of
+        link_prediction's rows, from the same score bits.  metrics has link_prediction's names, normalised by n.  Needs
+        init_link_prediction().  An id out of range raises KgeError before anything is launched."""
+        import torch
+        self._refuse_sharded_rank("rank_triples")
+        host = np.stack([np.asarray(h).reshape(-1), np.asarray(t).reshape(-1), np.asarray(r).reshape(-1)]).astype(np.int32)
+        self._check_ids(host)
+        counts = self._rank_device(torch.from_numpy(host).to(self.device), test_head)
+        return counts, self._lp_normalise(self._lp_sums(counts, test_head), host.shape[1])
+
+    def _valid_positives(self):
+        """The triples of valid2id.txt in file order, int32 [3, V] (h, t, r), read once."""
+        if getattr(self, "_valid_pos", None) is None:
+            path = self.in_path if self.in_path.endswith("/") else self.in_path + "/"
+            with open(path + "valid2id.txt") as f:
+                tok = f.read().split()
+            total = int(tok[0]) if tok else 0
+            self._valid_pos = np.asarray(tok[1:1 + 3 * total], dtype=np.int64).reshape(total, 3).T.astype(np.int32)   # on disk: head, tail, relation
+        return self._valid_pos
+
+    def validation_link_prediction(self, test_head=True, sample=0):
+        """rank_triples on the positives of valid2id.txt (read from in_path in file order; getValidBatch is not used, so the
+        libc rand() sequence does not move): (counts, metrics) as rank_triples returns them -- filtered Hits@10 and MRR on the
+        validation split for model selection.  sample = N > 0 ranks the N triples at the indices floor(i V / N), i < N (all
+        of them when N >= V); one check scores V x E pairs per side otherwise.  The device ids are kept between calls."""
+        import torch
+        self._refuse_sharded_rank("validation_link_prediction")
+        valid = self._valid_positives()
+        total = valid.shape[1]
+        sample = int(sample)
+        if sample < 0:
+            raise KgeError("validation_link_prediction: sample must be >= 0, got %d" % sample)
+        if 0 < sample < total:
+            valid = valid[:, (np.arange(sample, dtype=np.int64) * total) // sample]
+        else:
+            sample = 0
+        cached = getattr(self, "_valid_rank_dev", None)
+        if cached is None or cached[0] != sample:
+            host = np.ascontiguousarray(valid)
+            self._check_ids(host)
+            cached = self._valid_rank_dev = (sample, torch.from_numpy(host).to(self.device))
+        counts = self._rank_device(cached[1], test_head)
+        return counts, self._lp_normalise(self._lp_sums(counts, test_head), counts.shape[0])
+
     @staticmethod
     def _rel_sums(out):
         """Un-normalised relation-prediction accumulators over the rows of `out` [count, 4] (raw, filtered, typed, filtered +

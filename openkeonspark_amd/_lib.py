@@ -92,6 +92,7 @@ def _declare(L):
     L.kge_sgd_update_tables.argtypes = [i32, vp, vp, vp, f32, vp]
     L.kge_adam_update_tables.argtypes = [i32, vp, vp, vp, vp, vp, f32, f32, f32, f32, vp]
     L.kge_predict.argtypes = [ctypes.POINTER(ModelDesc), tabs, vp, vp, vp, i64, vp, vp]
+    L.kge_rank_triples.argtypes = [ctypes.POINTER(ModelDesc), tabs, vp, vp, vp, i64, i64, vp, vp]
     L.kge_topk_entities.argtypes = [ctypes.POINTER(ModelDesc), tabs, vp, vp, vp, i64, i64, i64, vp, vp, vp]
     L.kge_topk_entities_range.argtypes = [ctypes.POINTER(ModelDesc), tabs, i64, i64, vp, vp, vp, vp, i64, i64, i64, vp, vp]
     L.kge_topk_merge_keys.argtypes = [vp, i64, i64, i64, vp, vp, vp]

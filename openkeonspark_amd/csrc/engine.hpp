@@ -85,6 +85,7 @@ struct Engine {
     int64_t topk_table_max_bytes = int64_t(1) << 30;  // kge_topk_entities: candidate table T_r while E*D*4 fits, on-the-fly sides above
     int64_t relpred_chunk_bytes = int64_t(256) << 20;  // kge_topk_relations / kge_relation_prediction: [queries x R] fp32 score block per chunk (TransR: also its projection buffer)
     int lp_v1 = 0;              // test hook: link prediction through the generic predict kernel on materialised candidate batches
+    int rank_slices = 0;        // test hook: kge_rank_triples cuts the candidates into this many slices (0 = automatic)
     int transr_v1 = 0;          // test hook: 1 = the 32x32x2 / 32-row-tile TransR kernels even where the v2 tiles apply; 2 = v2 with its all-tiles wgrad forced
     int fb_occ4 = 1;            // projecting models at <= 4 elements per lane: the forward/backward body compiled for four waves per SIMD
     int persist_ahead = 1;      // persistent launch: idle teams sample the next batch during the forward/backward phase

@@ -63,6 +63,14 @@ def parse_args(argv=None):
     p.add_argument("--early_stop_patience", type=int, default=5)
     p.add_argument("--early_stop_stopping_step", type=int, default=1)
     p.add_argument("--early_stop_start_step", type=int, default=1)
+    p.add_argument("--early_stop_metric", type=str, default="accuracy", choices=("accuracy", "hits10", "mrr"),
+                   help="what an early-stop check measures on the validation split: accuracy = triple classification (the default), "
+                        "hits10 / mrr = filtered Hits@10 / mean reciprocal rank of the validation triples (tail side; head side too with "
+                        "--test_head 1), higher is better.  A ranking check scores every validation triple against every entity -- on a "
+                        "large graph several training epochs of GPU time -- so rank a sample with --early_stop_rank_triples and / or "
+                        "check less often with --early_stop_stopping_step")
+    p.add_argument("--early_stop_rank_triples", type=int, default=0,
+                   help="hits10 / mrr: rank only this many validation triples, evenly spaced through valid2id.txt (0 = all of them)")
     p.add_argument("--model", type=str, default="TransE")
     p.add_argument("--debug", type=int, default=0)
     p.add_argument("--mode", type=str, default="train")
@@ -375,6 +383,25 @@ def _validation_accuracy(con, valid):
     return con.validation_accuracy(valid)
 
 
+def _init_rank_validation(con):
+    """The files a ranking early-stop check needs (Config.init_link_prediction); None when valid2id.txt / test2id.txt are absent."""
+    path = con.in_path if con.in_path.endswith("/") else con.in_path + "/"
+    if not all(os.path.exists(path + f) for f in ("valid2id.txt", "test2id.txt")):
+        return None
+    con.init_link_prediction()
+    return True
+
+
+def _validation_rank_metric(con, argv):
+    """Filtered Hits@10 or MRR of the validation triples, the mean over the ranked sides (Config.validation_link_prediction).
+    With replicated tables every rank ranks the same triples itself: identical tables, identical decisions, no collective."""
+    test_head = bool(argv.test_head)
+    metrics = con.validation_link_prediction(test_head=test_head, sample=argv.early_stop_rank_triples)[1]
+    name = "_filter_tot" if argv.early_stop_metric == "hits10" else "_filter_reci_rank"
+    sides = ("r", "l") if test_head else ("r",)
+    return sum(metrics[p + name] for p in sides) / len(sides)
+
+
 def main_fun(argv):
     """Train or evaluate (distribute_training.py:161-612)."""
     import torch
@@ -429,7 +456,11 @@ def main_fun(argv):
                     json.dump(metrics, f, indent=1)
         return metrics
 
-    valid = _init_validation(con, argv)
+    metric = argv.early_stop_metric
+    if metric != "accuracy" and con._sharded("ent_embeddings"):
+        raise KgeError("--early_stop_metric %s over an entity table sharded across ranks is not supported "
+                       "(Config.validation_link_prediction refuses it); use --early_stop_metric accuracy" % metric)
+    valid = _init_validation(con, argv) if metric == "accuracy" else _init_rank_validation(con)
     best_acc, wait_steps_acc, best_step_acc = -1.0, 0, last_global_step
     iterations = con.train_times * con.nbatches + last_global_step      # distribute_training.py:205
     patience = argv.early_stop_patience
@@ -462,17 +493,18 @@ def main_fun(argv):
         if g < iterations and g >= to_reach_step:
             while g >= to_reach_step:
                 to_reach_step += stopping_step
-            if valid is not None:   # accuracy criterion of distribute_training.py:295-333
-                acc = _validation_accuracy(con, valid)
+            if valid is not None:   # accuracy criterion of distribute_training.py:295-333, or validation Hits@10 / MRR in its place
+                acc = _validation_accuracy(con, valid) if metric == "accuracy" else _validation_rank_metric(con, argv)
                 if argv.debug and rank == 0:
-                    print("[ Early Stop Check (Accuracy) ] best %.10f now %.10f" % (best_acc, acc))
+                    print("[ Early Stop Check (%s) ] best %.10f now %.10f" % ("Accuracy" if metric == "accuracy" else metric, best_acc, acc))
                 if acc > best_acc:
                     best_acc, wait_steps_acc, best_step_acc = acc, 0, g
                 elif wait_steps_acc < patience:
                     wait_steps_acc += 1
                 if wait_steps_acc >= patience:
                     if rank == 0:
-                        print('Accuracy early stop. Accuracy has not been improved enough in {} times'.format(patience))
+                        what = "Accuracy" if metric == "accuracy" else metric
+                        print('{} early stop. {} has not been improved enough in {} times'.format(what, what, patience))
                         if argv.output_path:
                             with open(os.path.join(argv.output_path, "stop.txt"), "w") as f:
                                 f.write(str(best_step_acc) + "\n")

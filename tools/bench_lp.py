@@ -12,11 +12,8 @@ sys.path.insert(0, ROOT)
 import numpy as np
 
 
-def main():
-    model = sys.argv[1] if len(sys.argv) > 1 else "TransE"
-    dim = int(sys.argv[2]) if len(sys.argv) > 2 else 200
-    import torch
-    import openkeonspark_amd as pkg
+def dataset():
+    """The FB15k-237-shaped graph with its public test / valid cardinalities, written once; shared with bench_rank.py."""
     from openkeonspark_amd.synthetic import FB15K237, generate_triples, write_openke_dir
     d = "/tmp/okes_fb15k237_lp/"
     if not os.path.exists(d + ".complete"):
@@ -30,6 +27,15 @@ def main():
                 f.write("%d\n" % (hi - lo))
                 np.savetxt(f, np.stack([h[lo:hi], t[lo:hi], r[lo:hi]], axis=1), fmt="%d")
         open(d + ".complete", "w").write("ok\n")
+    return d
+
+
+def main():
+    model = sys.argv[1] if len(sys.argv) > 1 else "TransE"
+    dim = int(sys.argv[2]) if len(sys.argv) > 2 else 200
+    import torch
+    import openkeonspark_amd as pkg
+    d = dataset()
     con = pkg.Config()
     con.set_in_path(d); con.set_work_threads(8); con.set_bern(1); con.set_dimension(dim); con.set_nbatches(8)
     con.set_ent_neg_rate(25); con.set_alpha(0.001); con.set_opt_method("Adam")
