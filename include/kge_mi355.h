@@ -140,6 +140,10 @@ const char *kge_version(void);
  *   "emit_rounds": 1 (default) = the TransE emit kernel at widths 132..256 (multiples of 4) walks a group's negatives in rounds
  *                     of one corruption kind with raw buffer gathers and one merged reduction per round; 0 = its earlier body
  *                     (kernel transe_emit_vec_v1_kernel), which computes the same bits: A/B measurements and the tests' reference
+ *   "emit_pack": 1 (default) = the _packed sampler entry points also write one packed word per negative, a group's words side by
+ *                     side (kge_sampling_device_packed), and that round body reads a group's negatives from them -- one line per
+ *                     group instead of a line per negative and id array; 0 = no pack is written or read and kge_emit_pack_words
+ *                     returns 0, which is the step without it, bit for bit: A/B measurements and the tests' reference
  *   "record_emit_event": 1 = record an event behind every TransE emit launch (kge_stream_wait_emit); default 0
  *   "pair_counts":       1 (default) = TransH / TransD steps of at least float_records_min entity-side rows (widths that are
  *                        multiples of 4 up to 256, at most 63 negatives, ent_total*rel_total below 2^31) take the
@@ -227,6 +231,21 @@ int kge_sampling_device(int32_t *d_h, int32_t *d_t, int32_t *d_r, INT batchSize,
 int kge_sampling_attach(int32_t *d_h, int32_t *d_t, int32_t *d_r, INT batchSize, INT negRate, INT negRelRate,
                         INT thread_lo, INT thread_hi, INT out_stride, INT *n_local, void *stream);
 int kge_sampling_flush(void *stream);
+/* The same two calls, which ALSO write the batch's packed negatives for the TransE emit kernel: d_pack[(b << kshift) + k], one
+ * int32 per slot k of local positive b, kshift = ceil(log2(1 + negRate + negRelRate)) -- bits 0..27 the row the kernel gathers for
+ * negative k (the new head, tail or relation id), bits 28..29 which one (0 new head, 1 new tail, 2 new relation), bit 31 set
+ * when not exactly one slot differs from the positive; slot 0 and the slots past the last negative are 0.  The word is derived
+ * from the very ids written to d_h / d_t / d_r, by the classification the emit kernel itself applies to them.  d_pack holds
+ * kge_emit_pack_words(n_local, negRate, negRelRate) words; it is not written when that is 0, or when d_pack is NULL (= the
+ * calls above).  Hand the pointer to the _packed step entry point that consumes THIS batch and to no other: the library never
+ * guesses a pack from a batch pointer. */
+int kge_sampling_device_packed(int32_t *d_h, int32_t *d_t, int32_t *d_r, int32_t *d_pack, INT batchSize, INT negRate, INT negRelRate,
+                               INT thread_lo, INT thread_hi, INT out_stride, INT *n_local, void *stream);
+int kge_sampling_attach_packed(int32_t *d_h, int32_t *d_t, int32_t *d_r, int32_t *d_pack, INT batchSize, INT negRate, INT negRelRate,
+                               INT thread_lo, INT thread_hi, INT out_stride, INT *n_local, void *stream);
+/* words of the pack of n_positions positives; 0 = batches of this shape have none (option emit_pack = 0, more than 63 negatives,
+ * 2^28 or more entities or relations) or, with dim > 0, a TransE step of that width would not read it (dim = 0: any width) */
+INT kge_emit_pack_words(INT n_positions, INT negRate, INT negRelRate, INT dim);
 /* number of batch positions owned by virtual threads [thread_lo, thread_hi) for this batchSize */
 INT kge_slice_positions(INT batchSize, INT thread_lo, INT thread_hi, INT *first_position);
 
@@ -367,6 +386,12 @@ int kge_transe_counts_supported(const kge_model_desc *m, INT n_neg);
 int kge_transe_forward_counts(const kge_model_desc *m, const float *d_ent, const float *d_rel, const int32_t *d_h,
                               const int32_t *d_t, const int32_t *d_r, INT n_pos, INT n_neg, INT stride, INT denom,
                               int32_t *d_counts, float *d_resid_ent, float *d_resid_rel, float *d_loss, void *stream);
+/* kge_transe_forward_counts on a sampler-shaped batch (no residual tables) with the pack kge_sampling_device_packed /
+ * kge_sampling_attach_packed wrote for it (NULL = none): at widths 132..256 (multiples of 4) the emit kernel reads the negatives
+ * from it.  Same results, bit for bit. */
+int kge_transe_forward_counts_packed(const kge_model_desc *m, const float *d_ent, const float *d_rel, const int32_t *d_h,
+                                     const int32_t *d_t, const int32_t *d_r, const int32_t *d_pack, INT n_pos, INT n_neg, INT stride,
+                                     INT denom, int32_t *d_counts, float *d_loss, void *stream);
 int kge_transe_apply_counts(float *d_p, float *d_m, float *d_v, int32_t *d_counts, float *d_resid, int64_t rows, int32_t dim,
                             INT denom, int32_t adam, float lr, float beta1, float beta2, float eps, void *stream);
 /* The whole single-process step of the sign-count path in one call -- what sess.run([train_op, loss, global_step]) does for TransE
@@ -382,6 +407,12 @@ int kge_transe_train_step_counts(const kge_model_desc *m, float *const d_p[2], f
                                  const int32_t *d_t, const int32_t *d_r, INT n_pos, INT n_neg, INT stride, INT denom, int32_t *d_counts,
                                  float *const d_resid[2], int32_t sampler_shaped, int32_t adam, float lr, float beta1, float beta2, float eps,
                                  float *d_loss, void *stream);
+/* the same with the batch's pack (see kge_sampling_device_packed; NULL = none, and ignored unless sampler_shaped = 1) */
+int kge_transe_train_step_counts_packed(const kge_model_desc *m, float *const d_p[2], float *const d_m[2], float *const d_v[2],
+                                        const int32_t *d_h, const int32_t *d_t, const int32_t *d_r, const int32_t *d_pack, INT n_pos,
+                                        INT n_neg, INT stride, INT denom, int32_t *d_counts, float *const d_resid[2],
+                                        int32_t sampler_shaped, int32_t adam, float lr, float beta1, float beta2, float eps, float *d_loss,
+                                        void *stream);
 /* both tables ([0] = ent_embeddings, [1] = rel_embeddings; d_counts = the whole [(E+R), D] image) in one launch */
 int kge_transe_apply_counts_tables(const kge_model_desc *m, float *const d_p[2], float *const d_m[2], float *const d_v[2],
                                    int32_t *d_counts, float *const d_resid[2], INT denom, int32_t adam, float lr, float beta1,

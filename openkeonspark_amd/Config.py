@@ -307,6 +307,9 @@ class Config(object):
         self._refresh_pointers()
         self._dist_ready = 0
         self._dev_batch = None
+        self._dev_pack = None          # the sampler's packed negatives of the two batch slots (_pack_for)
+        self._batch_pack = 0           # pack of the batch the current step trains on (device pointer; 0 = none)
+        self._prefetched_pack = 0      # ... of the batch drawn ahead
         self._dev_batch2 = None
         self._side_stream = None
         self._prefetched = None
@@ -559,15 +562,33 @@ class Config(object):
             self._dev_batch = torch.zeros((2, 3, n), dtype=torch.int32, device=self.device)  # two slots: double buffer
         return self._dev_batch
 
+    def _pack_for(self, slot):
+        """Device pointer of batch slot `slot`'s packed negatives (include/kge_mi355.h kge_sampling_device_packed), 0 = this
+        configuration's step reads none: only the TransE sign-count step does, and the engine says for which batch shapes
+        (kge_emit_pack_words; option emit_pack).  Allocated next to the batch: two slots of n_local << kshift words."""
+        import torch
+        n_neg = self.negative_ent + self.negative_rel
+        if not (self.use_counts and not self.sparse_rows and not self.sparse_inplace and
+                self.batch_size * (3 + n_neg) >= self.counts_min_records * self.world_size):
+            return 0
+        words = int(self.lib.kge_emit_pack_words(self._n_local, self.negative_ent, self.negative_rel, self.hidden_size))
+        if words <= 0:
+            return 0
+        if self._dev_pack is None or self._dev_pack.shape[1] != words:
+            self._dev_pack = torch.zeros((2, words), dtype=torch.int32, device=self.device)
+        return self._dev_pack[slot].data_ptr()
+
     def sample_device(self, slot=0):
         """Sample this rank's slice of the next batch on the device; returns (int32[3,n] tensor, n_pos)."""
         stride = max(self._n_local, 1)
         buf = self._ensure_dev_batch(stride)[slot]
         nl = ctypes.c_int64(0)
-        _lib.check(self.lib.kge_sampling_device(buf[0].data_ptr(), buf[1].data_ptr(), buf[2].data_ptr(),
-                                                self.batch_size, self.negative_ent, self.negative_rel,
-                                                self._thread_lo, self._thread_hi, stride, ctypes.byref(nl),
-                                                self._stream()), self.lib)
+        pack = self._pack_for(slot)
+        _lib.check(self.lib.kge_sampling_device_packed(buf[0].data_ptr(), buf[1].data_ptr(), buf[2].data_ptr(), pack or None,
+                                                       self.batch_size, self.negative_ent, self.negative_rel,
+                                                       self._thread_lo, self._thread_hi, stride, ctypes.byref(nl),
+                                                       self._stream()), self.lib)
+        self._batch_pack = pack        # (a pack goes with the batch drawn in the same call, and with no other)
         return buf, nl.value
 
     def _next_sampled_batch(self):
@@ -584,6 +605,7 @@ class Config(object):
             dev, n_pos = self.sample_device(self._slot)
         else:
             dev, n_pos, ev = self._prefetched
+            self._batch_pack = self._prefetched_pack
             if ev is not None:            # (None: drawn on this stream by a sampler that rode in a launch of the step)
                 torch.cuda.current_stream().wait_event(ev)
         return dev, n_pos
@@ -596,10 +618,12 @@ class Config(object):
         self._slot ^= 1
         buf = self._ensure_dev_batch(stride)[self._slot]
         nl = ctypes.c_int64(0)
-        _lib.check(self.lib.kge_sampling_attach(buf[0].data_ptr(), buf[1].data_ptr(), buf[2].data_ptr(), self.batch_size,
-                                                self.negative_ent, self.negative_rel, self._thread_lo, self._thread_hi, stride,
-                                                ctypes.byref(nl), self._stream()), self.lib)
+        pack = self._pack_for(self._slot)
+        _lib.check(self.lib.kge_sampling_attach_packed(buf[0].data_ptr(), buf[1].data_ptr(), buf[2].data_ptr(), pack or None,
+                                                       self.batch_size, self.negative_ent, self.negative_rel, self._thread_lo,
+                                                       self._thread_hi, stride, ctypes.byref(nl), self._stream()), self.lib)
         self._prefetched = (buf, nl.value, None)
+        self._prefetched_pack = pack
 
     def _flush_next_batch(self):
         _lib.check(self.lib.kge_sampling_flush(self._stream()), self.lib)
@@ -628,6 +652,7 @@ class Config(object):
             ev = torch.cuda.Event()
             ev.record(self._side_stream)
         self._prefetched = (dev, n_pos, ev)
+        self._prefetched_pack = self._batch_pack
 
     def forward_backward(self, dev_batch, n_pos, stride, denom, sampler_shaped=False):
         """Add dLoss/dTables of the batch into the gradient accumulators; loss -> self._loss.
@@ -831,7 +856,9 @@ class Config(object):
         if batch_h is None:
             dev, n_pos = self._next_sampled_batch() if self.prefetch_sampling else self.sample_device()
             stride = max(self._n_local, 1)
+            pack = self._batch_pack        # written by the sampler call that drew `dev`
         else:
+            pack = 0
             if self._dp:      # (also a one-rank group under force_data_parallel: the sharded step has no check for hand-made negatives)
                 raise KgeError("feeding a host batch is single-process only")
             host = np.stack([np.asarray(batch_h), np.asarray(batch_t), np.asarray(batch_r)]).astype(np.int32)
@@ -890,9 +917,9 @@ class Config(object):
             one_call = not self._dp and bool(getattr(self, "fused_counts", True))
             try:
                 if one_call:
-                    self.step_counts(dev, n_pos, stride, denom, sampler_shaped=batch_h is None)
+                    self.step_counts(dev, n_pos, stride, denom, sampler_shaped=batch_h is None, pack=pack)
                 else:
-                    self.forward_counts(dev, n_pos, stride, denom, sampler_shaped=batch_h is None)
+                    self.forward_counts(dev, n_pos, stride, denom, sampler_shaped=batch_h is None, pack=pack)
             finally:
                 if ahead:                              # launched on its own if the step's path had no scatter kernel -- and
                     self._flush_next_batch()           # also when the forward call failed: an armed sampler never outlives its buffers
@@ -1253,9 +1280,17 @@ class Config(object):
         n = int(self._sparse_buf["n_rows"].item())
         return self._sparse_buf["rows"][:n], self._sparse_buf["row_counts"][:n]
 
-    def forward_counts(self, dev_batch, n_pos, stride, denom, sampler_shaped=False):
+    def forward_counts(self, dev_batch, n_pos, stride, denom, sampler_shaped=False, pack=0):
         """TransE sign-count forward/backward: exact int32 gradient counts -> self._counts.
-        sampler_shaped=True (a device-sampled batch): no residual pass is needed (include/kge_mi355.h)."""
+        sampler_shaped=True (a device-sampled batch): no residual pass is needed (include/kge_mi355.h).
+        pack: the packed negatives the sampler wrote for THIS batch (_pack_for), 0 = none."""
+        if sampler_shaped and pack:
+            _lib.check(self.lib.kge_transe_forward_counts_packed(
+                ctypes.byref(self._desc), self._tables[0].data_ptr(), self._tables[1].data_ptr(),
+                dev_batch[0].data_ptr(), dev_batch[1].data_ptr(), dev_batch[2].data_ptr(), pack, n_pos,
+                self.negative_ent + self.negative_rel, stride, denom, self._counts.data_ptr(),
+                self._loss.data_ptr(), self._stream()), self.lib)
+            return
         resid = (None, None) if sampler_shaped else (self._grads[0].data_ptr(), self._grads[1].data_ptr())
         _lib.check(self.lib.kge_transe_forward_counts(
             ctypes.byref(self._desc), self._tables[0].data_ptr(), self._tables[1].data_ptr(),
@@ -1263,13 +1298,14 @@ class Config(object):
             self.negative_ent + self.negative_rel, stride, denom, self._counts.data_ptr(),
             resid[0], resid[1], self._loss.data_ptr(), self._stream()), self.lib)
 
-    def step_counts(self, dev_batch, n_pos, stride, denom, sampler_shaped=False):
+    def step_counts(self, dev_batch, n_pos, stride, denom, sampler_shaped=False, pack=0):
         """TransE sign-count step in one call: forward_counts + apply_counts with the middle fused on the device
         (include/kge_mi355.h kge_transe_train_step_counts; distribute_training.py:95-101,282).  Same bits as the two calls."""
         lr = float(self._adam_lr_t()) if self._adam else float(self.alpha)
-        _lib.check(self.lib.kge_transe_train_step_counts(
+        _lib.check(self.lib.kge_transe_train_step_counts_packed(
             ctypes.byref(self._desc), self._tab_ptrs, self._adam_m_ptrs if self._adam else None, self._adam_v_ptrs if self._adam else None,
-            dev_batch[0].data_ptr(), dev_batch[1].data_ptr(), dev_batch[2].data_ptr(), n_pos, self.negative_ent + self.negative_rel,
+            dev_batch[0].data_ptr(), dev_batch[1].data_ptr(), dev_batch[2].data_ptr(), (pack if sampler_shaped else 0) or None, n_pos,
+            self.negative_ent + self.negative_rel,
             stride, denom, self._counts.data_ptr(), self._grad_ptrs, 1 if sampler_shaped else 0, 1 if self._adam else 0, lr,
             self.adam_beta1, self.adam_beta2, self.adam_epsilon, self._loss.data_ptr(), self._stream()), self.lib)
         if self._adam:

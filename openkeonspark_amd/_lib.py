@@ -69,6 +69,10 @@ def _declare(L):
     L.kge_set_stream_states.argtypes = [vp, i64]
     L.kge_sampling_device.argtypes = [vp, vp, vp, i64, i64, i64, i64, i64, i64, ctypes.POINTER(i64), vp]
     L.kge_sampling_attach.argtypes = [vp, vp, vp, i64, i64, i64, i64, i64, i64, ctypes.POINTER(i64), vp]
+    L.kge_sampling_device_packed.argtypes = [vp, vp, vp, vp, i64, i64, i64, i64, i64, i64, ctypes.POINTER(i64), vp]
+    L.kge_sampling_attach_packed.argtypes = [vp, vp, vp, vp, i64, i64, i64, i64, i64, i64, ctypes.POINTER(i64), vp]
+    L.kge_emit_pack_words.argtypes = [i64, i64, i64, i64]
+    L.kge_emit_pack_words.restype = i64
     L.kge_sampling_flush.argtypes = [vp]
     L.kge_slice_positions.restype = i64
     L.kge_slice_positions.argtypes = [i64, i64, i64, ctypes.POINTER(i64)]
@@ -107,12 +111,15 @@ def _declare(L):
     L.kge_test_entity_ids.argtypes = [i64, i64, vp, vp]
     L.kge_transe_counts_supported.argtypes = [ctypes.POINTER(ModelDesc), i64]
     L.kge_transe_forward_counts.argtypes = [ctypes.POINTER(ModelDesc), vp, vp, vp, vp, vp, i64, i64, i64, i64, vp, vp, vp, vp, vp]
+    L.kge_transe_forward_counts_packed.argtypes = [ctypes.POINTER(ModelDesc), vp, vp, vp, vp, vp, vp, i64, i64, i64, i64, vp, vp, vp]
     L.kge_transe_apply_counts.argtypes = [vp, vp, vp, vp, vp, i64, i32, i64, i32, f32, f32, f32, f32, vp]
     L.kge_transe_deferred_groups.argtypes = [ctypes.POINTER(ctypes.c_int32)]
     L.kge_transe_step_scratch_read.argtypes = [ctypes.c_int, i64, i64, vp]
     L.kge_transe_apply_counts_tables.argtypes = [ctypes.POINTER(ModelDesc), vp, vp, vp, vp, vp, i64, i32, f32, f32, f32, f32, vp]
     L.kge_transe_train_step_counts.argtypes = [ctypes.POINTER(ModelDesc), vp, vp, vp, vp, vp, vp, i64, i64, i64, i64, vp, vp, i32, i32,
                                                f32, f32, f32, f32, vp, vp]
+    L.kge_transe_train_step_counts_packed.argtypes = [ctypes.POINTER(ModelDesc), vp, vp, vp, vp, vp, vp, vp, i64, i64, i64, i64, vp, vp,
+                                                      i32, i32, f32, f32, f32, f32, vp, vp]
     L.kge_transe_lazy_row_live.argtypes = [vp]
     L.kge_transe_record_dwords.restype = i64
     L.kge_transe_record_dwords.argtypes = [ctypes.POINTER(ModelDesc)]

@@ -124,6 +124,7 @@ static std::string build_and_adopt(int64_t E, int64_t R, int64_t nb, int64_t n, 
     return "";
 }
 
+void transe_team_shape(int D, int &L, int &C);   // models.hip
 }  // namespace kge
 
 using namespace kge;
@@ -234,6 +235,7 @@ int kge_set_option(const char *name, INT value) {
     if (n == "counts_krel") { int k = 1; while (k * 2 <= value && k < 64) k *= 2; engine().counts_krel = k; return KGE_OK; }
     if (n == "inv_carry") { engine().inv_carry = value != 0; tables_written(); return KGE_OK; }
     if (n == "emit_rounds") { engine().emit_rounds = value != 0; return KGE_OK; }
+    if (n == "emit_pack") { engine().emit_pack = value != 0; return KGE_OK; }
     if (n == "float_records") { engine().float_records = value != 0; return KGE_OK; }
     if (n == "float_records_min") { engine().float_records_min = value; return KGE_OK; }
     if (n == "index_device_min") { engine().index_device_min = value; return KGE_OK; }
@@ -349,19 +351,40 @@ INT kge_slice_positions(INT batchSize, INT thread_lo, INT thread_hi, INT *first_
 
 int kge_sampling_attach(int32_t *d_h, int32_t *d_t, int32_t *d_r, INT batchSize, INT negRate, INT negRelRate,
                         INT thread_lo, INT thread_hi, INT out_stride, INT *n_local, void *stream) {
+    return kge_sampling_attach_packed(d_h, d_t, d_r, nullptr, batchSize, negRate, negRelRate, thread_lo, thread_hi, out_stride, n_local, stream);
+}
+
+int kge_sampling_attach_packed(int32_t *d_h, int32_t *d_t, int32_t *d_r, int32_t *d_pack, INT batchSize, INT negRate, INT negRelRate,
+                               INT thread_lo, INT thread_hi, INT out_stride, INT *n_local, void *stream) {
     int64_t nl = 0;
-    int rc = attach_sampler(d_h, d_t, d_r, batchSize, negRate, negRelRate, thread_lo, thread_hi, out_stride, &nl, (hipStream_t)stream);
+    int rc = attach_sampler(d_h, d_t, d_r, batchSize, negRate, negRelRate, thread_lo, thread_hi, out_stride, &nl, (hipStream_t)stream, d_pack);
     if (n_local) *n_local = nl;
     return rc;
+}
+
+INT kge_emit_pack_words(INT n_positions, INT negRate, INT negRelRate, INT dim) {
+    const KgIndex &ix = engine().index;
+    if (n_positions <= 0 || negRate < 0 || negRelRate < 0 || !emit_pack_shape(ix.ent_total, ix.rel_total, negRate, negRelRate)) return 0;
+    if (dim > 0) {   // only the round body reads a pack: the widths whose team is one wave with four elements per lane
+        int L = 0, C = 0;
+        transe_team_shape((int)dim, L, C);
+        if (dim % 4 != 0 || L != 64 || C > 4) return 0;
+    }
+    return n_positions << sampler_kshift(negRate, negRelRate);
 }
 
 int kge_sampling_flush(void *stream) { return flush_attached_sampler((hipStream_t)stream); }
 
 int kge_sampling_device(int32_t *d_h, int32_t *d_t, int32_t *d_r, INT batchSize, INT negRate, INT negRelRate,
                         INT thread_lo, INT thread_hi, INT out_stride, INT *n_local, void *stream) {
+    return kge_sampling_device_packed(d_h, d_t, d_r, nullptr, batchSize, negRate, negRelRate, thread_lo, thread_hi, out_stride, n_local, stream);
+}
+
+int kge_sampling_device_packed(int32_t *d_h, int32_t *d_t, int32_t *d_r, int32_t *d_pack, INT batchSize, INT negRate, INT negRelRate,
+                               INT thread_lo, INT thread_hi, INT out_stride, INT *n_local, void *stream) {
     int64_t nl = 0;
     int rc = launch_sampler(d_h, d_t, d_r, batchSize, negRate, negRelRate, thread_lo, thread_hi, out_stride, &nl,
-                            (hipStream_t)stream);
+                            (hipStream_t)stream, d_pack);
     if (n_local) *n_local = nl;
     return rc;
 }

@@ -69,6 +69,7 @@ struct Engine {
     int counts_krel = 4;        // dense TransE path: virtual copies of the relation rows in the record sort (1 = none; measured 1/2/4/8/16/64: 4 best); a power of two
     int inv_carry = 1;          // 0 = always recompute the table in front of the emit kernel (test hook)
     int emit_rounds = 1;        // TransE emit at 132 <= D <= 256: rounds of one corruption kind with merged reductions (models.hip transe_emit_rounds_body); 0 = the earlier body, as transe_emit_vec_v1_kernel (A/B runs, test reference)
+    int emit_pack = 1;          // device-sampled TransE batches: the sampler also writes one packed word per negative, a group's words in one line, and the round body reads those instead of the strided h/t/r arrays (sampler_dev.hpp SamplerArgs::pack); 0 = no pack written or read (A/B runs, test reference)
     int64_t inv_table_max_bytes = int64_t(256) << 20;  // TransE emit: per-row inverse-norm table only while the tables are this small
     int float_records = 1;              // TransH / TransD (and TransE without counts): record + segmented-sum path instead of fp32 atomics
     int64_t float_records_min = 1 << 16; // ... from this many gradient rows per step (below it the atomic kernel alone is quicker)
@@ -110,7 +111,7 @@ struct SamplerArgs;
 bool take_attached_sampler(SamplerArgs &a, unsigned &blocks, float share = 1.0f);   // true: `a` / `blocks` describe the part taken (sampler.hip)
 int flush_attached_sampler(hipStream_t stream);                 // launches an armed sampler on its own
 int attach_sampler(int32_t *d_h, int32_t *d_t, int32_t *d_r, int64_t B, int64_t neg, int64_t negrel, int64_t thread_lo,
-                   int64_t thread_hi, int64_t out_stride, int64_t *n_local_out, hipStream_t stream);
+                   int64_t thread_hi, int64_t out_stride, int64_t *n_local_out, hipStream_t stream, int32_t *d_pack = nullptr);
 void set_error(const std::string &msg);
 int fail(int code, const std::string &msg);
 bool device_ok();
@@ -178,7 +179,14 @@ std::string build_index_device(KgIndex &ix, DeviceIndex &dev, int64_t E, int64_t
 
 // ---- launchers implemented in the .hip files ------------------------------------------------
 int launch_sampler(int32_t *d_h, int32_t *d_t, int32_t *d_r, int64_t B, int64_t neg, int64_t negrel, int64_t thread_lo,
-                   int64_t thread_hi, int64_t out_stride, int64_t *n_local, hipStream_t stream);
+                   int64_t thread_hi, int64_t out_stride, int64_t *n_local, hipStream_t stream, int32_t *d_pack = nullptr);
+// The packed negatives line (SamplerArgs::pack): slots per positive as a shift, and whether a batch of this shape has one at all
+inline int sampler_kshift(int64_t neg, int64_t negrel) { int k = 0; while ((int64_t(1) << k) < 1 + neg + negrel) k++; return k; }
+constexpr int kPackRowBits = 28;   // bits 0..27 of a word: the row; 28..29: the corruption code; 31: not sampler-shaped
+inline bool emit_pack_shape(int64_t ent_total, int64_t rel_total, int64_t neg, int64_t negrel) {
+    return engine().emit_pack && sampler_kshift(neg, negrel) <= 6 && neg + negrel >= 1 && ent_total < (int64_t(1) << kPackRowBits) &&
+           rel_total < (int64_t(1) << kPackRowBits);
+}
 int launch_widen(const int32_t *src3, int64_t *dst3_and_y, int64_t B, int64_t total, hipStream_t stream);
 int launch_forward_backward(const kge_model_desc &m, const float *const tables[4], const int32_t *d_h, const int32_t *d_t,
                             const int32_t *d_r, int64_t n_pos, int64_t n_neg, int64_t stride, int64_t denom,

@@ -486,7 +486,10 @@ __device__ __forceinline__ void transe_emit_vec_body(const FbArgs &a) {
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 template <int V> struct IntC { static constexpr int value = V; };
 
-template <bool INV_TAB, bool REC2>
+// PACK: the negatives' ids come from the sampler's packed line of the group (FbArgs::neg_pack) -- one coalesced load of at most
+// 63 consecutive words instead of three loads that touch a line per negative each (the batch holds a group's negatives `stride`
+// words apart).  The word was made by classify_negative on the ids the sampler wrote to those arrays, so both reads agree.
+template <bool INV_TAB, bool REC2, bool PACK = false>
 __device__ __forceinline__ void transe_emit_rounds_body(const FbArgs &a) {
     constexpr int L = 64, TEAMS = 256 / L;
     __shared__ float red[TEAMS];
@@ -516,6 +519,14 @@ __device__ __forceinline__ void transe_emit_rounds_body(const FbArgs &a) {
         int my_code = 0, my_row = 0;
         float my_f = 0.f;
         bool bad = false;
+        if constexpr (PACK) {   // (n_neg < L: one word per lane says it all)
+            if (lane < n_neg) {
+                const int w = a.neg_pack[(b << a.pack_shift) + lane + 1];
+                my_row = w & ((1 << kPackRowBits) - 1);
+                my_code = (w >> kPackRowBits) & 3;
+                bad = w < 0;
+            }
+        } else
         for (int k = lane; k < n_neg; k += L) {
             const long long j = b + (long long)(k + 1) * a.stride;
             const int nh = a.bh[j], nt = a.bt[j], nr = a.br[j];
@@ -567,7 +578,7 @@ __device__ __forceinline__ void transe_emit_rounds_body(const FbArgs &a) {
         s16x2 Ah_lo = 0, Ah_hi = 0, At_lo = 0, At_hi = 0, Ar_lo = 0, Ar_hi = 0;
         int cnt = 0;
         for (int k0 = 0; k0 < n_neg; k0 += L) {
-            if (k0 > 0) {   // later rounds (n_neg > L): fetch and classify this round's ids
+            if (!PACK && k0 > 0) {   // later rounds (n_neg > L, never with a pack): fetch and classify this round's ids
                 const int my_k = k0 + lane;
                 my_code = 0; my_row = 0; my_f = 0.f;
                 if (my_k < n_neg) {
@@ -688,6 +699,11 @@ __global__ __launch_bounds__(256, WPE) void transe_emit_vec_kernel(FbArgs a) {
     else transe_emit_vec_body<L, Q, K, INV_TAB, REC2>(a);
 }
 
+// The round body on the sampler's packed negatives (engine option emit_pack = 1, a device-sampled batch).  A kernel of its own, so
+// that the instantiations above keep their names in traces.
+template <bool INV_TAB, bool REC2>
+__global__ __launch_bounds__(256, 1) void transe_emit_pack_kernel(FbArgs a) { transe_emit_rounds_body<INV_TAB, REC2, true>(a); }
+
 // transe_emit_vec_body at every shape (engine option emit_rounds = 0): the reference the rounds body is tested against, bit for bit
 template <int L, int Q, int K, int WPE, bool INV_TAB, bool REC2 = false>
 __global__ __launch_bounds__(256, WPE) void transe_emit_vec_v1_kernel(FbArgs a) { transe_emit_vec_body<L, Q, K, INV_TAB, REC2>(a); }
@@ -765,7 +781,18 @@ static void launch_emit(const FbArgs &a_in, float *d_loss, hipStream_t stream) {
                 else hipLaunchKernelGGL((transe_emit_vec_v1_kernel<L, Q, 4, 1, false>), grid, block, 0, stream, a);
             }
         }
-        if (v1) {
+        bool packed = false;   // the round body reading the sampler's packed negatives
+        if constexpr (L == 64 && Q == 1) {
+            if (!v1 && a.neg_pack && a.n_neg < L) {
+                packed = true;
+                if (a.rec2) {
+                    if (inv_tab) hipLaunchKernelGGL((transe_emit_pack_kernel<true, true>), grid, block, 0, stream, a);
+                    else hipLaunchKernelGGL((transe_emit_pack_kernel<false, true>), grid, block, 0, stream, a);
+                } else if (inv_tab) hipLaunchKernelGGL((transe_emit_pack_kernel<true, false>), grid, block, 0, stream, a);
+                else hipLaunchKernelGGL((transe_emit_pack_kernel<false, false>), grid, block, 0, stream, a);
+            }
+        }
+        if (v1 || packed) {
         } else if (a.rec2) {
             if (inv_tab) hipLaunchKernelGGL((transe_emit_vec_kernel<L, Q, 4, 1, true, true>), grid, block, 0, stream, a);
             else hipLaunchKernelGGL((transe_emit_vec_kernel<L, Q, 4, 1, false, true>), grid, block, 0, stream, a);
@@ -836,7 +863,8 @@ int transe_deferred_groups(int32_t *out) {
 int launch_transe_emit(const kge_model_desc &m, const float *ent, const float *rel, float *resid_ent, float *resid_rel,
                        const int32_t *d_h, const int32_t *d_t, const int32_t *d_r, int64_t n_pos, int64_t n_neg, int64_t stride,
                        int64_t denom, uint32_t *rec, int32_t *dst, int krel, float *d_loss, hipStream_t stream, bool track_deferred,
-                       uint8_t *rec2) {
+                       uint8_t *rec2, const int32_t *neg_pack) {
+    // neg_pack: the packed negatives the sampler wrote for THIS batch (SamplerArgs::pack), or null; only the round body reads it
     // rec2: 2-bit records for the negatives (FbArgs::rec2; widths that are multiples of 4 only -- the caller checks); null = int8
     // track_deferred = false: the caller guarantees sampler-shaped negatives (a device-sampled batch): no
     // deferral list, no counter reset, no fp32 pass
@@ -876,6 +904,10 @@ int launch_transe_emit(const kge_model_desc &m, const float *ent, const float *r
     a.rec = rec; a.rec2 = (m.ent_dim % 4 == 0) ? rec2 : nullptr; a.dst = dst; a.ent_total = (int)m.ent_total; a.rel_total = (int)m.rel_total; a.krel = 1;
     a.loss_limbs = track_deferred ? nullptr : e.loss_limbs;   // (with a deferred pass the loss is finalised by loss_finalize_kernel: the caller converts it)
     while (a.krel * 2 <= krel) a.krel *= 2;      // a power of two: the kernels take b & (krel - 1)
+    if (neg_pack && e.emit_pack && !track_deferred && emit_pack_shape(m.ent_total, m.rel_total, n_neg, 0) &&
+        m.ent_total + (int64_t)a.krel * m.rel_total < (int64_t(1) << kPackRowBits)) {
+        a.neg_pack = neg_pack; a.pack_shift = sampler_kshift(n_neg, 0);
+    }
     if (!for_transe_team_shape(a.D, [&](auto t) { launch_emit<decltype(t)::L, decltype(t)::C>(a, d_loss, stream); }))
         return fail(KGE_ERR_UNSUPPORTED, "embedding dimension > 1024");
     return hip_check(hipGetLastError(), "transe emit launch");

@@ -64,6 +64,10 @@ struct FbArgs {
     // fwdbwd_ride_kernel): the number of workgroups that are this kernel's -- what the loss ticket and the group loop count with
     // instead of gridDim.x; 0 = the whole grid
     int loss_blocks;
+    // TransE round body on a device-sampled batch (transe_emit_rounds_body<.., PACK>): the sampler's packed negatives,
+    // neg_pack[(b << pack_shift) + k] for slot k = 1..n_neg of group b (sampler_dev.hpp SamplerArgs::pack); null = read bh / bt / br
+    const int32_t *neg_pack;
+    int pack_shift;
 };
 
 int ensure_loss_buffers();

@@ -49,7 +49,7 @@ __global__ void widen_kernel(const int32_t *__restrict__ src, long long *__restr
 }
 
 // Validates the call and fills the launch description.  blocks = 0: this rank's slice is empty (only the streams advance).
-static int build_sampler(int32_t *d_h, int32_t *d_t, int32_t *d_r, int64_t B, int64_t neg, int64_t negrel, int64_t thread_lo,
+static int build_sampler(int32_t *d_h, int32_t *d_t, int32_t *d_r, int32_t *d_pack, int64_t B, int64_t neg, int64_t negrel, int64_t thread_lo,
                          int64_t thread_hi, int64_t out_stride, int64_t *n_local_out, SamplerArgs &a, unsigned &blocks, bool &wide) {
     Engine &e = engine();
     int rc = ensure_device_index();
@@ -77,9 +77,9 @@ static int build_sampler(int32_t *d_h, int32_t *d_t, int32_t *d_r, int64_t B, in
     a.neg = (int)neg; a.negrel = (int)negrel; a.bern = e.bern ? 1 : 0;
     a.pick_div = (unsigned long long)(a.new_batch > 0 ? a.new_batch : a.train_dup);
     a.pick_magic = ~0ull / a.pick_div;
-    int kshift = 0;
-    while ((1 << kshift) < 1 + neg + negrel) kshift++;
+    const int kshift = sampler_kshift(neg, negrel);
     a.kshift = kshift;
+    a.pack = emit_pack_shape(a.ent_total, a.rel_total, neg, negrel) ? d_pack : nullptr;   // [n_local << kshift] words
     a.streams_next = e.dev.streams_next; a.W = W; a.B = B;
     wide = kshift > 6;
     int64_t nb = n_local > 0 ? ((n_local << kshift) + 255) / 256 : 0;
@@ -124,12 +124,12 @@ int flush_attached_sampler(hipStream_t stream) {
 }
 
 int attach_sampler(int32_t *d_h, int32_t *d_t, int32_t *d_r, int64_t B, int64_t neg, int64_t negrel, int64_t thread_lo,
-                   int64_t thread_hi, int64_t out_stride, int64_t *n_local_out, hipStream_t stream) {
+                   int64_t thread_hi, int64_t out_stride, int64_t *n_local_out, hipStream_t stream, int32_t *d_pack) {
     Engine &e = engine();
     int rc = flush_attached_sampler(stream);    // at most one armed sampler: batches are drawn in order
     if (rc) return rc;
     SamplerArgs a; unsigned blocks; bool wide;
-    if ((rc = build_sampler(d_h, d_t, d_r, B, neg, negrel, thread_lo, thread_hi, out_stride, n_local_out, a, blocks, wide))) return rc;
+    if ((rc = build_sampler(d_h, d_t, d_r, d_pack, B, neg, negrel, thread_lo, thread_hi, out_stride, n_local_out, a, blocks, wide))) return rc;
     if (blocks == 0) {       // empty slice: nothing to carry, the streams advance now
         hipLaunchKernelGGL(advance_streams_kernel, dim3((unsigned)((a.W + 63) / 64)), dim3(64), 0, stream, e.dev.streams,
                            (long long)a.W, (long long)B, (long long)a.per_thread, (unsigned long long)(1 + 2 * neg + negrel));
@@ -143,12 +143,12 @@ int attach_sampler(int32_t *d_h, int32_t *d_t, int32_t *d_r, int64_t B, int64_t 
 }
 
 int launch_sampler(int32_t *d_h, int32_t *d_t, int32_t *d_r, int64_t B, int64_t neg, int64_t negrel, int64_t thread_lo,
-                   int64_t thread_hi, int64_t out_stride, int64_t *n_local_out, hipStream_t stream) {
+                   int64_t thread_hi, int64_t out_stride, int64_t *n_local_out, hipStream_t stream, int32_t *d_pack) {
     Engine &e = engine();
     int rc = flush_attached_sampler(stream);    // an armed sampler draws the batch BEFORE this one
     if (rc) return rc;
     SamplerArgs a; unsigned blocks; bool wide;
-    if ((rc = build_sampler(d_h, d_t, d_r, B, neg, negrel, thread_lo, thread_hi, out_stride, n_local_out, a, blocks, wide))) return rc;
+    if ((rc = build_sampler(d_h, d_t, d_r, d_pack, B, neg, negrel, thread_lo, thread_hi, out_stride, n_local_out, a, blocks, wide))) return rc;
     if (blocks > 0) {
         if (!wide) hipLaunchKernelGGL(sample_kernel, dim3(blocks), dim3(256), 0, stream, a);
         else hipLaunchKernelGGL(sample_kernel_wide, dim3(blocks), dim3(256), 0, stream, a);

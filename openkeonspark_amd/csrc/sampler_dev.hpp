@@ -26,6 +26,11 @@ struct SamplerArgs {
     uint64_t *streams_next;   // sample_kernel: every stream's state after this batch (null: not written)
     long long W, B;           // virtual threads, global batch (for streams_next)
     int32_t *out_h, *out_t, *out_r;
+    // sample_block only, null = not written: pack[(b << kshift) + k] says in one word what the TransE emit kernel needs of slot k
+    // of local positive b -- bits 0..27 the row it gathers, bits 28..29 the corruption (0 new head, 1 new tail, 2 new relation),
+    // bit 31 not a single-slot corruption; slot 0 and the padding slots are 0.  A group's negatives are one contiguous run (one
+    // 128-byte line at 25 negatives) where the h/t/r arrays hold them out_stride words apart.
+    int32_t *pack;
     long long per_thread;  // positions per virtual thread: B/W, or B/W+1 when W does not divide B
     long long pos_lo;      // first global batch position written by this launch
     long long n_local;     // positions written by this launch
@@ -250,6 +255,16 @@ __device__ __forceinline__ void sample_block(const SamplerArgs &a, long long blo
         if (live) {
             const long long o = b + (long long)k * a.out_stride;
             a.out_h[o] = oh; a.out_t[o] = ot; a.out_r[o] = orr;
+        }
+        if (a.pack && g < total) {   // the wave's 64 consecutive words; classified by the emit kernel's own function, not from the coin
+            int w = 0;
+            if (live && k >= 1) {
+                const NegClass nc = classify_negative<KGE_TRANSE>(tr.x, tr.y, tr.z, oh, ot, orr, 0);
+                const int code = !nc.same_h ? 0 : (!nc.same_t ? 1 : 2);
+                const int row = !nc.same_h ? oh : (!nc.same_t ? ot : orr);
+                w = row | (code << kPackRowBits) | (nc.fast ? 0 : (int)0x80000000u);
+            }
+            a.pack[g] = w;
         }
     }
 }

@@ -34,7 +34,7 @@ void transe_team_shape(int D, int &L, int &C);
 int launch_transe_emit(const kge_model_desc &m, const float *ent, const float *rel, float *resid_ent, float *resid_rel,
                        const int32_t *d_h, const int32_t *d_t, const int32_t *d_r, int64_t n_pos, int64_t n_neg, int64_t stride,
                        int64_t denom, uint32_t *rec, int32_t *dst, int krel, float *d_loss, hipStream_t stream, bool track_deferred,
-                       uint8_t *rec2 = nullptr);
+                       uint8_t *rec2 = nullptr, const int32_t *neg_pack = nullptr);
 
 int transe_deferred_groups(int32_t *out);
 
@@ -1731,7 +1731,8 @@ struct FusedOpt {
 
 static int forward_counts_impl(const kge_model_desc *m, const float *d_ent, const float *d_rel, const int32_t *d_h,
                                const int32_t *d_t, const int32_t *d_r, INT n_pos, INT n_neg, INT stride, INT denom,
-                               int32_t *d_counts, float *d_resid_ent, float *d_resid_rel, float *d_loss, void *stream_, FusedOpt *fo) {
+                               int32_t *d_counts, float *d_resid_ent, float *d_resid_rel, float *d_loss, void *stream_, FusedOpt *fo,
+                               const int32_t *d_pack = nullptr) {
     hipStream_t stream = (hipStream_t)stream_;
     if (!device_ok()) return fail(KGE_ERR_NO_DEVICE, "kge_transe_forward_counts: no usable HIP device");
     if (!m || !kge_transe_counts_supported(m, n_neg)) return fail(KGE_ERR_UNSUPPORTED, "sign-count path: TransE, dim <= 1024, 1..63 negatives");
@@ -1764,7 +1765,7 @@ static int forward_counts_impl(const kge_model_desc *m, const float *d_ent, cons
                        (uint64_t)M * rd * 4 < (uint64_t(1) << 32) && rows2 < (1 << 30);
     uint8_t *rec2 = fused ? reinterpret_cast<uint8_t *>(g_c.rec + (size_t)3 * (size_t)n_pos * rd) : nullptr;
     rc = launch_transe_emit(*m, d_ent, d_rel, d_resid_ent, d_resid_rel, d_h, d_t, d_r, n_pos, n_neg, stride, denom, g_c.rec, g_c.dst,
-                            krel, d_loss, stream, d_resid_ent != nullptr && d_resid_rel != nullptr, rec2);
+                            krel, d_loss, stream, d_resid_ent != nullptr && d_resid_rel != nullptr, rec2, d_pack);
     if (rc) return rc;
     FuseArgs fold = FuseArgs();
     if (krel > 1) { fold.fold_E = (int)m->ent_total; fold.fold_R = (int)m->rel_total; }
@@ -1837,10 +1838,26 @@ int kge_transe_forward_counts(const kge_model_desc *m, const float *d_ent, const
                                stream_, nullptr);
 }
 
+int kge_transe_forward_counts_packed(const kge_model_desc *m, const float *d_ent, const float *d_rel, const int32_t *d_h,
+                                     const int32_t *d_t, const int32_t *d_r, const int32_t *d_pack, INT n_pos, INT n_neg, INT stride,
+                                     INT denom, int32_t *d_counts, float *d_loss, void *stream_) {
+    return forward_counts_impl(m, d_ent, d_rel, d_h, d_t, d_r, n_pos, n_neg, stride, denom, d_counts, nullptr, nullptr, d_loss, stream_,
+                               nullptr, d_pack);
+}
+
 int kge_transe_train_step_counts(const kge_model_desc *m, float *const d_p[2], float *const d_m[2], float *const d_v[2], const int32_t *d_h,
                                  const int32_t *d_t, const int32_t *d_r, INT n_pos, INT n_neg, INT stride, INT denom, int32_t *d_counts,
                                  float *const d_resid[2], int32_t sampler_shaped, int32_t adam, float lr, float beta1, float beta2, float eps,
                                  float *d_loss, void *stream_) {
+    return kge_transe_train_step_counts_packed(m, d_p, d_m, d_v, d_h, d_t, d_r, nullptr, n_pos, n_neg, stride, denom, d_counts, d_resid,
+                                               sampler_shaped, adam, lr, beta1, beta2, eps, d_loss, stream_);
+}
+
+int kge_transe_train_step_counts_packed(const kge_model_desc *m, float *const d_p[2], float *const d_m[2], float *const d_v[2],
+                                        const int32_t *d_h, const int32_t *d_t, const int32_t *d_r, const int32_t *d_pack, INT n_pos,
+                                        INT n_neg, INT stride, INT denom, int32_t *d_counts, float *const d_resid[2],
+                                        int32_t sampler_shaped, int32_t adam, float lr, float beta1, float beta2, float eps, float *d_loss,
+                                        void *stream_) {
     if (!m || !d_p || !d_p[0] || !d_p[1] || !d_counts || !d_resid || !d_resid[0] || !d_resid[1] || denom <= 0)
         return fail(KGE_ERR_BAD_ARG, "kge_transe_train_step_counts: bad arguments");
     if (adam && (!d_m || !d_v || !d_m[0] || !d_m[1] || !d_v[0] || !d_v[1]))
@@ -1851,7 +1868,7 @@ int kge_transe_train_step_counts(const kge_model_desc *m, float *const d_p[2], f
     fo.adam = adam; fo.lr = lr; fo.b1 = beta1; fo.b2 = beta2; fo.eps = eps;
     const bool fed = !sampler_shaped;     // a hand-made batch: deferral bookkeeping + the exact fp32 pass into the residual tables
     int rc = forward_counts_impl(m, d_p[0], d_p[1], d_h, d_t, d_r, n_pos, n_neg, stride, denom, d_counts, fed ? d_resid[0] : nullptr,
-                                 fed ? d_resid[1] : nullptr, d_loss, stream_, &fo);
+                                 fed ? d_resid[1] : nullptr, d_loss, stream_, &fo, fed ? nullptr : d_pack);
     if (rc || fo.done) return rc;
     // (this width / table size has no fused kernels: the image is complete, the apply kernel finishes the step)
     return kge_transe_apply_counts_range(m, d_p, d_m, d_v, d_counts, d_resid, 0, m->ent_total + m->rel_total, denom, adam, lr, beta1, beta2,

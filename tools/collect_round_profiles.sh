@@ -25,8 +25,8 @@ for name, d in (("FETCH_SIZE", "$out/pmc_fetch/r_results.db"), ("WRITE_SIZE", "$
     # one row per (dispatch, counter instance): sum the instances of a dispatch, then average over the emit kernel's dispatches
     rows = db.execute("select kernel_name, dispatch_id, sum(value) from counters_collection where counter_name = ? group by kernel_name, dispatch_id",
                       (name,)).fetchall()
-    per = [v for kn, _, v in rows if "transe_emit_vec_kernel" in kn]
-    kn = [kn for kn, _, _ in rows if "transe_emit_vec_kernel" in kn][0].split("(")[0]
+    per = [v for kn, _, v in rows if "transe_emit_" in kn]
+    kn = [kn for kn, _, _ in rows if "transe_emit_" in kn][0].split("(")[0]
     res[name] = dict(kernel=kn, launches=len(per), KB_per_launch=sum(per) / len(per))
 print(json.dumps(res))
 open("$out/pmc_emit_traffic.json", "w").write(json.dumps(res, indent=1))

@@ -3,7 +3,7 @@
 # Two separate --pmc passes (no trace domains beside them), summed over counter instances, averaged over a kernel's launches.
 set -e
 out=$1; shift
-pat="${@:-segapply emit_vec bkt_ apply_counts}"
+pat="${@:-segapply transe_emit_ bkt_ apply_counts}"
 cd /tmp && export TMPDIR=/tmp
 mkdir -p $GRAFT_REPO_ROOT/$out
 cd $GRAFT_REPO_ROOT

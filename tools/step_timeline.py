@@ -3,7 +3,7 @@
 Prints, per kernel of two consecutive steps, start / end relative to the first emit kernel's start (us), and the stream (queue)."""
 import sqlite3, sys
 db = sqlite3.connect(sys.argv[1])
-key = sys.argv[2] if len(sys.argv) > 2 else "transe_emit_vec_kernel"
+key = sys.argv[2] if len(sys.argv) > 2 else "transe_emit_"
 tabs = [r[0] for r in db.execute("select name from sqlite_master where type in ('table','view')")]
 rows = db.execute("select name, start, end, queue_id from kernels order by start").fetchall() if "kernels" in tabs else []
 emits = [i for i, r in enumerate(rows) if key in r[0]]
