@@ -164,6 +164,8 @@ const char *kge_version(void);
  *   "transr_v1":         test hooks for the TransR MFMA tilings (default 0 = automatic): 1 = always the 32x32x2 tiles; 2 = 16x16x4
  *                        tiles with the all-output-tiles wgrad and its 512-row spans forced; 3 = 16x16x4 tiles with the 32x32x2 wgrad
  *   "time_emit":         N > 0 = bracket every N-th launch of the TransE emit kernel with HIP events on its launch stream
+ *   "time_sampler":      N > 0 = the same around every N-th launch of the sampler's own kernels (kernel name "sampler"; a sampler
+ *                        that rides in another kernel's launch is not timed)
  *   "fb_occ4":           1 (default) = TransH / TransD / TransR's vector stage at <= 4 elements per lane run the forward/backward body
  *                        compiled for four waves per SIMD (128 VGPRs); 0 = the uncapped build
  *   "persist_touch":     1 = the persistent launch requests all rows of a group together before its dependent gathers (default 0:
@@ -182,9 +184,9 @@ const char *kge_version(void);
  *   "libc_rand_restart": restart the glibc-compatible seed generator, as in a fresh process (the next
  *                        randReset then yields 1804289383, 846930886, ... again) */
 int kge_set_option(const char *name, INT value);
-/* elapsed time of the most recent launch of a timed kernel; name = "transe_emit" (needs time_emit) */
+/* elapsed time of the most recent launch of a timed kernel; name = "transe_emit" (needs time_emit) or "sampler" (time_sampler) */
 int kge_last_kernel_ms(const char *name, float *ms);
-/* mean over the launches since "time_emit" was switched on (the most recent 512 of them); one event pair per launch, read
+/* mean over the launches since "time_emit" / "time_sampler" was switched on (the most recent 512 of them); one event pair per launch, read
  * back here, so nothing synchronises inside the timed region */
 int kge_kernel_ms_mean(const char *name, float *mean_ms, INT *launches);
 
@@ -203,8 +205,36 @@ int kge_import_train_arrays(INT ent_total, INT rel_total, INT n, const INT *h, c
  *   "ht"        int32[trainTotal_][2]  (ht_off,ht_len) per file-order triple
  *   "left_mean" / "right_mean" float[relationTotal]               (Reader.h:160-177)
  *   "bern_prob" float[relationTotal]  1000*right/(right+left)      (Base.cpp:117)
+ * and, built on first request from the imported type lists (kge_set_typed_sampling; an error without importTypeFiles),
+ *   "type_tails" / "type_heads"  int32[]  every relation's tail / head type list, sorted, duplicates removed, back to back
+ *   "type_bounds"  int32[relationTotal][4]  (tail_off,tail_len,head_off,head_len) into those two
+ *   "typed_pos_hr" / "typed_pos_tr"  int32[trainTotal]  at a group's offset in tails_hr / heads_tr: the increasing positions
+ *               inside the relation's list of the group's known ids that occur in it, then -1 up to the group's length
+ *   "typed_len"  int32[trainTotal_][2]  per file-order triple: how many positions its (h,r) group and its (t,r) group have
  * Returns the number of BYTES the array holds (copying at most `bytes` of them), <0 on error. */
 int64_t kge_index_copy(const char *what, void *dst, int64_t bytes);
+
+/* Type-constrained negative sampling for TRAINING (NON-PARITY, off by default; the reference trains on untyped negatives,
+ * Corrupt.h:7-69): an entity negative is drawn from the corrupted side's type list of its relation (type_constrain.txt) instead
+ * of from all entities.  Nothing about the random stream changes: a positive still consumes 1 + 2*negRate + negRelRate draws,
+ * draw 0 picks the training triple, entity negative k uses draw 1 + 2(k-1) as the head-or-tail coin (compared in float with the
+ * Bernoulli probability or 500) and the next draw s for the corruption; relation negatives are untouched.  Only how s becomes
+ * an id changes.  Coin says "new tail":
+ *     L  = the tail type list of r, sorted, duplicates removed
+ *     K' = the increasing positions in L of the known tails of (h, r) (training set) that occur in L
+ *     c  = |L| - |K'|
+ *     c > 0:  tmp = s mod c,  pos = tmp + #{ j : K'[j] - j <= tmp },  new tail = L[pos]
+ *     c = 0:  the reference's untyped draw from the same s (no list, an empty list, or a list the known tails exhaust)
+ * Coin says "new head": the same with the head type list of r and the known heads of (t, r).  Known ids outside L do not count.
+ * So positives, coins, relation negatives and all stream states are bit-identical to the untyped batch, and a typed negative
+ * with c > 0 lies in the list and is not a training triple.
+ * kge_set_typed_sampling(1) needs importTypeFiles (error otherwise), runs an armed sampler first (kge_sampling_flush), builds the
+ * typed index on the host at once and uploads it with the first batch drawn; importing the training set or the type file again
+ * marks it stale (rebuilt on next use).  `sampling`, kge_sampling_device(_packed) and kge_sampling_attach(_packed) honour it; an
+ * armed typed sampler rides in no other launch (kge_sampling_flush launches it), and kge_train_steps_persistent refuses while it
+ * is on.  kge_typed_sampling: the current setting. */
+int kge_set_typed_sampling(INT on);
+int kge_typed_sampling(void);
 
 /* rng stream states of the virtual threads (host view; Random.h:6) */
 int kge_get_stream_states(uint64_t *dst, INT n);

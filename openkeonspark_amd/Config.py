@@ -53,6 +53,7 @@ class Config(object):
             self.test_relation_prediction = False
             self.test_triple_classification = False
             self.valid_triple_classification = False
+            self.type_constrained_sampling = False
             # engine-side additions
             self.seed = 0                 # parameter initialisation seed
             self.device = "cuda"
@@ -98,6 +99,8 @@ class Config(object):
                 self._alloc_batch_buffers()
             if self.test_link_prediction or self.test_relation_prediction:
                 self.init_link_prediction()
+            if self.in_path != None:
+                self._apply_typed_sampling()      # (the engine is one per process: an earlier Config's setting must not linger)
             # triple-classification inputs (Test.h:266-444) are not built yet
 
     def init_link_prediction(self):
@@ -115,9 +118,39 @@ class Config(object):
         _lib.raise_if_error(self.lib)
         self.testTotal = self.lib.getTestTotal()
         self.validTotal = self.lib.getValidTotal()
+        if self.type_constrained_sampling:        # importTestFiles dropped the type lists: typed sampling needs them (and says so if they are gone)
+            self._apply_typed_sampling()
+
+    def set_type_constrained_sampling(self, flag):
+        """Type-constrained negative sampling (NON-PARITY, off by default): an entity negative is drawn from the corrupted side's
+        type list of its relation (type_constrain.txt) minus the known triples, instead of from all entities; a relation without
+        a list, or a group that exhausts its list, falls back to the untyped draw.  Same random stream, positives, head-or-tail
+        coins and relation negatives (include/kge_mi355.h kge_set_typed_sampling has the exact draw).  Callable before init(),
+        which then imports type_constrain.txt even when link prediction is off, or after it, for the batches drawn from then
+        on.  While it is on the sampler is a launch of its own and persistent_supported() is False."""
+        self.type_constrained_sampling = bool(flag)
+        if getattr(self, "trainTotal", None) is not None:      # after init(): switch the engine now
+            self._apply_typed_sampling()
+
+    def _apply_typed_sampling(self):
+        on = bool(self.type_constrained_sampling)
+        if on:
+            if self.in_path is None:
+                raise KgeError("type-constrained sampling needs a dataset directory with type_constrain.txt; "
+                               "init_from_arrays has no file to read the type lists from")
+            path = self.in_path if self.in_path.endswith("/") else self.in_path + "/"
+            if not os.path.exists(path + "type_constrain.txt"):
+                raise KgeError("type-constrained sampling: `%stype_constrain.txt` does not exist" % path)
+            self.lib.kge_clear_error()
+            self.lib.importTypeFiles()
+            _lib.raise_if_error(self.lib)
+        _lib.check(self.lib.kge_set_typed_sampling(1 if on else 0), self.lib)
 
     def init_from_arrays(self, ent_total, rel_total, h, t, r, new_batch_total=0):
         """Same as init() with the training triples (file order) given as arrays instead of files."""
+        if self.type_constrained_sampling:
+            raise KgeError("type-constrained sampling needs a dataset directory with type_constrain.txt; "
+                           "init_from_arrays has no file to read the type lists from")
         h = np.ascontiguousarray(h, dtype=np.int64)
         t = np.ascontiguousarray(t, dtype=np.int64)
         r = np.ascontiguousarray(r, dtype=np.int64)
@@ -131,6 +164,7 @@ class Config(object):
         self.entTotal = self.lib.getEntityTotal()
         self.trainTotal = self.lib.getTrainTotal_()
         self.testTotal = self.validTotal = 0
+        _lib.check(self.lib.kge_set_typed_sampling(0), self.lib)     # (one engine per process: an earlier Config's setting must not linger)
         self.bt = self.lib.getBatchTotal()
         self.set_mini_batch()
         self._alloc_batch_buffers()
@@ -954,7 +988,10 @@ class Config(object):
 
     def persistent_supported(self):
         """Can train_steps() run its steps inside one persistent launch (csrc/persist.hip)?  Single process, the dense
-        fp32-accumulator path of TransE / TransH / TransD at a launch-latency-bound step size."""
+        fp32-accumulator path of TransE / TransH / TransD at a launch-latency-bound step size.  Not with type-constrained
+        sampling: the persistent kernel has the untyped sampler only."""
+        if self.type_constrained_sampling:
+            return False
         if self._dp or self.sparse_rows or self.sparse_inplace or self.hidden_size > 256:
             return False
         if self.trainModel.model_id not in (_lib.TRANSE, _lib.TRANSH, _lib.TRANSD):
@@ -983,7 +1020,9 @@ class Config(object):
             return np.zeros(0, np.float32)
         use = self.persistent_preferred() if persistent is None else bool(persistent)
         if use and not self.persistent_supported():
-            raise KgeError("train_steps(persistent=True): this configuration has no persistent-launch path")
+            raise KgeError("train_steps(persistent=True): this configuration has no persistent-launch path" +
+                           (" (type-constrained sampling is on: the persistent kernel samples untyped negatives only)"
+                            if self.type_constrained_sampling else ""))
         if not use:
             out = [self.train_step(sync=False).clone() for _ in range(n_steps)]   # (the loss scalar is one reused device buffer)
             return torch.stack([o.reshape(()) for o in out]).cpu().numpy()

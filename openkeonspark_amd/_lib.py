@@ -65,6 +65,9 @@ def _declare(L):
     L.kge_kernel_ms_mean.argtypes = [ctypes.c_char_p, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(i64)]
     L.kge_index_copy.restype = i64
     L.kge_index_copy.argtypes = [ctypes.c_char_p, vp, i64]
+    L.kge_set_typed_sampling.argtypes = [i64]
+    L.kge_typed_sampling.argtypes = []
+    L.kge_typed_sampling.restype = ctypes.c_int
     L.kge_get_stream_states.argtypes = [vp, i64]
     L.kge_set_stream_states.argtypes = [vp, i64]
     L.kge_sampling_device.argtypes = [vp, vp, vp, i64, i64, i64, i64, i64, i64, ctypes.POINTER(i64), vp]

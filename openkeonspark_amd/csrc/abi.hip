@@ -86,6 +86,37 @@ int ensure_device_index() {
     return KGE_OK;
 }
 
+int ensure_typed_host_index() {
+    Engine &e = engine();
+    if (!e.index.loaded) return fail(KGE_ERR_NO_DATASET, "type-constrained sampling: no training set imported");
+    if (e.index.typed_built) return KGE_OK;
+    TypeListsHost v;
+    if (!eval_type_lists_host(v))
+        return fail(KGE_ERR_NO_DATASET, "type-constrained sampling: no type file imported (importTypeFiles reads type_constrain.txt)");
+    const std::string err = build_typed_index(e.index, *v.head_lef, *v.head_rig, *v.head_type, *v.tail_lef, *v.tail_rig, *v.tail_type);
+    e.dev.typed_uploaded = false;
+    if (!err.empty()) return fail(KGE_ERR_BAD_ARG, "type-constrained sampling: " + err);
+    return KGE_OK;
+}
+
+int ensure_typed_index() {
+    Engine &e = engine();
+    if (!e.typed_sampling) return KGE_OK;
+    int rc = ensure_typed_host_index();
+    if (rc) return rc;
+    if (e.dev.typed_uploaded) return KGE_OK;
+    if (!device_ok()) return fail(KGE_ERR_NO_DEVICE, "no usable HIP device: the sampler has no CPU fallback");
+    const KgIndex &ix = e.index;
+    if ((rc = upload(e.dev.typed_len, ix.typed_len.data(), ix.typed_len.size(), "upload typed lengths"))) return rc;
+    if ((rc = upload(e.dev.type_bounds, ix.type_bounds.data(), ix.type_bounds.size(), "upload type bounds"))) return rc;
+    if ((rc = upload(e.dev.type_tails, ix.type_tails.data(), ix.type_tails.size(), "upload tail type lists"))) return rc;
+    if ((rc = upload(e.dev.type_heads, ix.type_heads.data(), ix.type_heads.size(), "upload head type lists"))) return rc;
+    if ((rc = upload(e.dev.typed_pos_hr, ix.typed_pos_hr.data(), ix.typed_pos_hr.size(), "upload typed positions"))) return rc;
+    if ((rc = upload(e.dev.typed_pos_tr, ix.typed_pos_tr.data(), ix.typed_pos_tr.size(), "upload typed positions"))) return rc;
+    e.dev.typed_uploaded = true;
+    return KGE_OK;
+}
+
 static int pull_streams() {
     Engine &e = engine();
     { int rc = flush_attached_sampler(nullptr); if (rc) return rc; }   // an armed sampler has yet to write the states being read
@@ -252,6 +283,7 @@ int kge_set_option(const char *name, INT value) {
     if (n == "rank_slices") { engine().rank_slices = value > 0 ? (int)value : 0; return KGE_OK; }
     if (n == "transr_v1") { engine().transr_v1 = (int)value; return KGE_OK; }
     if (n == "time_emit") { engine().time_emit = value > 0 ? (int)value : 0; if (value > 0) { engine().emit_launches = 0; engine().emit_seen = 0; } return KGE_OK; }
+    if (n == "time_sampler") { engine().time_sampler = value > 0 ? (int)value : 0; if (value > 0) { engine().samp_launches = 0; engine().samp_seen = 0; } return KGE_OK; }
     if (n == "fb_occ4") { engine().fb_occ4 = value != 0; return KGE_OK; }
     if (n == "persist_ahead") { engine().persist_ahead = value != 0; return KGE_OK; }
     if (n == "persist_touch") { engine().persist_touch = value != 0; return KGE_OK; }
@@ -264,25 +296,31 @@ int kge_set_option(const char *name, INT value) {
 int kge_last_kernel_ms(const char *name, float *ms) {
     Engine &e = engine();
     std::string n = name ? name : "";
-    if (n != "transe_emit" || !ms) return fail(KGE_ERR_BAD_ARG, "kge_last_kernel_ms: unknown kernel " + n);
-    if (e.emit_launches <= 0) return fail(KGE_ERR_BAD_ARG, "kge_last_kernel_ms: enable option time_emit and run a step first");
-    const int slot = (int)((e.emit_launches - 1) % Engine::kEmitRing);
-    if (hip_check(hipEventSynchronize(e.ev_emit1[slot]), "event sync")) return KGE_ERR_NO_DEVICE;
-    return hip_check(hipEventElapsedTime(ms, e.ev_emit0[slot], e.ev_emit1[slot]), "event elapsed");
+    if ((n != "transe_emit" && n != "sampler") || !ms) return fail(KGE_ERR_BAD_ARG, "kge_last_kernel_ms: unknown kernel " + n);
+    const bool samp = n == "sampler";
+    const long long done = samp ? e.samp_launches : e.emit_launches;
+    hipEvent_t *ev0 = samp ? e.ev_samp0 : e.ev_emit0, *ev1 = samp ? e.ev_samp1 : e.ev_emit1;
+    if (done <= 0) return fail(KGE_ERR_BAD_ARG, "kge_last_kernel_ms: enable option time_emit / time_sampler and run a step first");
+    const int slot = (int)((done - 1) % Engine::kEmitRing);
+    if (hip_check(hipEventSynchronize(ev1[slot]), "event sync")) return KGE_ERR_NO_DEVICE;
+    return hip_check(hipEventElapsedTime(ms, ev0[slot], ev1[slot]), "event elapsed");
 }
 
 int kge_kernel_ms_mean(const char *name, float *mean_ms, INT *launches) {
     Engine &e = engine();
     std::string n = name ? name : "";
-    if (n != "transe_emit" || !mean_ms) return fail(KGE_ERR_BAD_ARG, "kge_kernel_ms_mean: unknown kernel " + n);
-    const long long have = e.emit_launches < Engine::kEmitRing ? e.emit_launches : (long long)Engine::kEmitRing;
-    if (have <= 0) return fail(KGE_ERR_BAD_ARG, "kge_kernel_ms_mean: enable option time_emit and run steps first");
+    if ((n != "transe_emit" && n != "sampler") || !mean_ms) return fail(KGE_ERR_BAD_ARG, "kge_kernel_ms_mean: unknown kernel " + n);
+    const bool samp = n == "sampler";
+    const long long done = samp ? e.samp_launches : e.emit_launches;
+    hipEvent_t *ev0 = samp ? e.ev_samp0 : e.ev_emit0, *ev1 = samp ? e.ev_samp1 : e.ev_emit1;
+    const long long have = done < Engine::kEmitRing ? done : (long long)Engine::kEmitRing;
+    if (have <= 0) return fail(KGE_ERR_BAD_ARG, "kge_kernel_ms_mean: enable option time_emit / time_sampler and run steps first");
     double sum = 0.0;
     for (long long i = 0; i < have; i++) {
-        const int slot = (int)((e.emit_launches - 1 - i) % Engine::kEmitRing);
+        const int slot = (int)((done - 1 - i) % Engine::kEmitRing);
         float ms = 0.f;
-        if (hip_check(hipEventSynchronize(e.ev_emit1[slot]), "event sync")) return KGE_ERR_NO_DEVICE;
-        if (hip_check(hipEventElapsedTime(&ms, e.ev_emit0[slot], e.ev_emit1[slot]), "event elapsed")) return KGE_ERR_NO_DEVICE;
+        if (hip_check(hipEventSynchronize(ev1[slot]), "event sync")) return KGE_ERR_NO_DEVICE;
+        if (hip_check(hipEventElapsedTime(&ms, ev0[slot], ev1[slot]), "event elapsed")) return KGE_ERR_NO_DEVICE;
         sum += ms;
     }
     *mean_ms = (float)(sum / (double)have);
@@ -304,17 +342,33 @@ int64_t kge_index_copy(const char *what, void *dst, int64_t bytes) {
     const void *src = nullptr;
     int64_t have = 0;
     std::string w = what ? what : "";
+    const bool typed = w == "type_tails" || w == "type_heads" || w == "type_bounds" || w == "typed_pos_hr" || w == "typed_pos_tr" ||
+                       w == "typed_len";
+    if (typed) { int rc = ensure_typed_host_index(); if (rc) return rc; }
 #define KGE_ARR(name, vec) if (w == name) { src = (vec).data(); have = (int64_t)((vec).size() * sizeof((vec)[0])); }
     KGE_ARR("tails_hr", ix.tails_hr) KGE_ARR("heads_tr", ix.heads_tr) KGE_ARR("rels_ht", ix.rels_ht)
     KGE_ARR("pos", ix.pos) KGE_ARR("grp", ix.grp) KGE_ARR("ht", ix.ht)
     KGE_ARR("left_mean", ix.left_mean) KGE_ARR("right_mean", ix.right_mean) KGE_ARR("bern_prob", ix.bern_prob)
+    KGE_ARR("type_tails", ix.type_tails) KGE_ARR("type_heads", ix.type_heads) KGE_ARR("type_bounds", ix.type_bounds)
+    KGE_ARR("typed_pos_hr", ix.typed_pos_hr) KGE_ARR("typed_pos_tr", ix.typed_pos_tr) KGE_ARR("typed_len", ix.typed_len)
 #undef KGE_ARR
-    if (!src && have == 0 && w != "tails_hr" && w != "heads_tr" && w != "rels_ht" && w != "pos" && w != "grp" && w != "ht" &&
+    if (!src && have == 0 && !typed && w != "tails_hr" && w != "heads_tr" && w != "rels_ht" && w != "pos" && w != "grp" && w != "ht" &&
         w != "left_mean" && w != "right_mean" && w != "bern_prob")
         return fail(KGE_ERR_BAD_ARG, "kge_index_copy: unknown array " + w);
     if (dst && bytes > 0 && have > 0) std::memcpy(dst, src, (size_t)(bytes < have ? bytes : have));
     return have;
 }
+
+int kge_set_typed_sampling(INT on) {
+    Engine &e = engine();
+    int rc = flush_attached_sampler(nullptr);   // an armed sampler draws its batch in the mode it was armed in
+    if (rc) return rc;
+    if (on && (rc = ensure_typed_host_index())) return rc;   // (the device copy follows with the first batch drawn)
+    e.typed_sampling = on ? 1 : 0;
+    return KGE_OK;
+}
+
+int kge_typed_sampling(void) { return engine().typed_sampling; }
 
 int kge_get_stream_states(uint64_t *dst, INT n) {
     Engine &e = engine();

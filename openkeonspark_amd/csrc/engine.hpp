@@ -34,6 +34,11 @@ struct DeviceIndex {
     int64_t stage_cap = 0;
     float *loss_partials = nullptr;  // per-block partial losses
     unsigned *loss_ticket = nullptr; // blocks-done counter: the last block of a forward/backward kernel adds the partials
+    // type-constrained sampling: device copies of KgIndex's typed arrays (ensure_typed_index)
+    bool typed_uploaded = false;
+    int2 *typed_len = nullptr;
+    int4 *type_bounds = nullptr;
+    int32_t *type_tails = nullptr, *type_heads = nullptr, *typed_pos_hr = nullptr, *typed_pos_tr = nullptr;
 };
 
 struct Engine {
@@ -57,6 +62,10 @@ struct Engine {
     hipEvent_t ev_emit0[kEmitRing] = {}, ev_emit1[kEmitRing] = {};
     long long emit_launches = 0;   // timed launches since time_emit was switched on
     long long emit_seen = 0;       // all launches since then (time_emit = N times every N-th)
+    // the same for the sampler's own launches (option time_sampler, kernel name "sampler"; a sampler that rides elsewhere is not timed)
+    int time_sampler = 0;
+    hipEvent_t ev_samp0[kEmitRing] = {}, ev_samp1[kEmitRing] = {};
+    long long samp_launches = 0, samp_seen = 0;
     // per-row 1/|row| table of the vectorised TransE emit kernel.  inv_valid = 1: it holds the norms of the CURRENT contents of
     // inv_for_ent / inv_for_rel -- set by the pre-pass, kept by the full-table apply kernel
     // (which rewrites the entry of every row it changes), cleared by every other entry point that writes tables and by
@@ -100,6 +109,7 @@ struct Engine {
     int ride_shares = 100 << 8;
     int counts_fused = 1;       // kge_transe_train_step_counts: 1 = segmented sum and optimizer in one kernel (segapply_kernel); 0 = segsum + apply kernels
     int counts_fused_diag = 0;  // measurement hook, see SegApplyArgs::diag
+    int typed_sampling = 0;     // kge_set_typed_sampling: entity negatives from the relation's type lists (sampler_dev.hpp typed_pick)
     int counts_fused_cap = 0;   // test hook: rows of more than this many records go through the count image (0 = the kernel's capacity, 3 x team width)
 };
 
@@ -117,6 +127,12 @@ int fail(int code, const std::string &msg);
 bool device_ok();
 // uploads index / rng streams if needed; returns KGE_OK or an error code
 int ensure_device_index();
+// typed sampling on: builds the typed part of the host index if it is stale and uploads it (after ensure_device_index); off: nothing
+int ensure_typed_index();
+int ensure_typed_host_index();   // the host part alone (no device needed)
+// eval.hip: the imported relation type lists (importTypeFiles), false when none are
+struct TypeListsHost { const std::vector<int32_t> *head_lef, *head_rig, *head_type, *tail_lef, *tail_rig, *tail_type; };
+bool eval_type_lists_host(TypeListsHost &v);
 int hip_check(hipError_t e, const char *what);
 
 constexpr int kMaxLossBlocks = 4096;

@@ -110,6 +110,11 @@ int eval_filter_view(bool need_types, EvalFilterView &v) {
     return KGE_OK;
 }
 
+bool eval_type_lists_host(TypeListsHost &v) {
+    v = TypeListsHost{&g_eh.head_lef, &g_eh.head_rig, &g_eh.head_type, &g_eh.tail_lef, &g_eh.tail_rig, &g_eh.tail_type};
+    return g_eh.types;
+}
+
 int eval_test_view(const int4 *&test, int64_t &total) {
     int rc = ensure_eval_device();
     if (rc) return rc;
@@ -270,6 +275,7 @@ void importTestFiles(void) {
     Engine &e = engine();
     g_eh = EvalHost();
     g_ed.uploaded = false;
+    e.index.typed_built = false;   // the type lists go with the rest: typed sampling needs importTypeFiles again
     g_valid.clear();
     g_tc_generation++;
     std::vector<int64_t> te, tr, va, tmp;
@@ -306,6 +312,7 @@ void importTypeFiles(void) {
     const int64_t R = e.index.rel_total;
     g_eh.head_lef.assign(R, 0); g_eh.head_rig.assign(R, 0); g_eh.tail_lef.assign(R, 0); g_eh.tail_rig.assign(R, 0);
     g_eh.head_type.clear(); g_eh.tail_type.clear();
+    e.index.typed_built = false;   // typed sampling rebuilds its index from the new lists on next use
     size_t p = 1;
     for (int64_t i = 0; i < R && p + 1 < a.size(); i++) {   // Reader.h:344-362
         int64_t rel = a[p], tot = a[p + 1]; p += 2;

@@ -204,6 +204,58 @@ void relation_means(KgIndex &ix, const std::vector<int64_t> &freq_rel, const std
     }
 }
 
+std::string build_typed_index(KgIndex &ix, const std::vector<int32_t> &head_lef, const std::vector<int32_t> &head_rig,
+                              const std::vector<int32_t> &head_type, const std::vector<int32_t> &tail_lef,
+                              const std::vector<int32_t> &tail_rig, const std::vector<int32_t> &tail_type) {
+    ix.typed_built = false;
+    if (!ix.loaded) return "no training set imported";
+    const int64_t R = ix.rel_total, E = ix.ent_total, U = ix.train_uniq, n = ix.train_dup;
+    if ((int64_t)head_lef.size() != R || (int64_t)head_rig.size() != R || (int64_t)tail_lef.size() != R || (int64_t)tail_rig.size() != R)
+        return "type_constrain.txt was imported for another relation total: import it again after the training set";
+    ix.type_tails.clear(); ix.type_heads.clear();
+    ix.type_bounds.assign((size_t)R, Int4{0, 0, 0, 0});
+    // sorted ranges -> sorted ranges without repeats, back to back
+    auto dedup = [&](const std::vector<int32_t> &src, int32_t lef, int32_t rig, std::vector<int32_t> &dst, int32_t &off, int32_t &len) {
+        off = (int32_t)dst.size();
+        if (lef < 0 || rig > (int64_t)src.size() || lef > rig) return false;
+        for (int32_t q = lef; q < rig; q++) {
+            if (src[q] < 0 || src[q] >= E) return false;
+            if (q == lef || src[q] != src[q - 1]) dst.push_back(src[q]);
+        }
+        len = (int32_t)dst.size() - off;
+        return true;
+    };
+    for (int64_t r = 0; r < R; r++) {
+        Int4 &b = ix.type_bounds[r];
+        if (!dedup(tail_type, tail_lef[r], tail_rig[r], ix.type_tails, b.x, b.y) ||
+            !dedup(head_type, head_lef[r], head_rig[r], ix.type_heads, b.z, b.w))
+            return "type_constrain.txt: entity id out of range in the lists of relation " + std::to_string(r);
+    }
+    // every group once: positions of its known ids inside the relation's list (both increasing, so the positions are too)
+    ix.typed_pos_hr.assign((size_t)U, -1); ix.typed_pos_tr.assign((size_t)U, -1);
+    std::vector<int32_t> cnt_hr((size_t)U, -1), cnt_tr((size_t)U, -1);   // by group offset; -1 = group not visited yet
+    auto positions = [](const std::vector<int32_t> &known, int32_t off, int32_t len, const std::vector<int32_t> &list, int32_t loff,
+                        int32_t llen, std::vector<int32_t> &out) {
+        int32_t cnt = 0;
+        const int32_t *lb = list.data() + loff, *le = lb + llen;
+        for (int32_t q = 0; q < len; q++) {
+            const int32_t *it = std::lower_bound(lb, le, known[(size_t)off + q]);
+            if (it != le && *it == known[(size_t)off + q]) out[(size_t)off + cnt++] = (int32_t)(it - lb);
+        }
+        return cnt;
+    };
+    ix.typed_len.resize((size_t)n);
+    for (int64_t i = 0; i < n; i++) {
+        const Int4 &g = ix.grp[i];
+        const Int4 &b = ix.type_bounds[ix.pos[i].z];
+        if (cnt_hr[g.x] < 0) cnt_hr[g.x] = positions(ix.tails_hr, g.x, g.y, ix.type_tails, b.x, b.y, ix.typed_pos_hr);
+        if (cnt_tr[g.z] < 0) cnt_tr[g.z] = positions(ix.heads_tr, g.z, g.w, ix.type_heads, b.z, b.w, ix.typed_pos_tr);
+        ix.typed_len[i] = Int2{cnt_hr[g.x], cnt_tr[g.z]};
+    }
+    ix.typed_built = true;
+    return "";
+}
+
 LibcRand::LibcRand() {
     int32_t w = 1;
     s_[0] = uint32_t(w);

@@ -29,6 +29,15 @@ struct KgIndex {
     std::vector<int32_t> rels_ht;   // [train_uniq] == trainRel[].r
     std::vector<float> left_mean, right_mean, bern_prob;  // [rel_total]
     bool loaded = false;
+    // Type-constrained negative sampling (build_typed_index; empty until typed sampling is switched on).  L_tail(r) / L_head(r):
+    // relation r's tail / head type list, sorted, duplicates removed.
+    std::vector<int32_t> type_tails, type_heads;   // every L_tail(r) / L_head(r), back to back
+    std::vector<Int4> type_bounds;                 // [rel_total]  (tail_off,tail_len,head_off,head_len) into the two arrays above
+    // [train_uniq], at the offsets of tails_hr / heads_tr: a group's first typed_len entries are the increasing POSITIONS inside
+    // L_tail(r) / L_head(r) of its known tails / heads that occur in the list; the rest of the group's slots hold -1
+    std::vector<int32_t> typed_pos_hr, typed_pos_tr;
+    std::vector<Int2> typed_len;                   // [train_dup]  (positions of the (h,r) group, positions of the (t,r) group)
+    bool typed_built = false;
 };
 
 // Reader.h:27-100 text parse (first line of relation2id/entity2id/batch2id, N + N lines "h t r").
@@ -46,6 +55,13 @@ std::string build_index(KgIndex &ix, int64_t ent_total, int64_t rel_total, int64
 // Reader.h:160-177 + Base.cpp:117 from the three per-relation integer counts (shared by the host and device builds)
 void relation_means(KgIndex &ix, const std::vector<int64_t> &freq_rel, const std::vector<int64_t> &groups_hr,
                     const std::vector<int64_t> &groups_tr);
+
+// The arrays of type-constrained sampling from the imported type lists (importTypeFiles: per relation [lef, rig) into
+// head_type / tail_type, each range sorted, duplicates kept).  One binary search per known (group, entity).  Returns an empty
+// string on success.
+std::string build_typed_index(KgIndex &ix, const std::vector<int32_t> &head_lef, const std::vector<int32_t> &head_rig,
+                              const std::vector<int32_t> &head_type, const std::vector<int32_t> &tail_lef,
+                              const std::vector<int32_t> &tail_rig, const std::vector<int32_t> &tail_type);
 
 // glibc rand() with the default seed, continuing across calls (Random.h:9-13 never calls srand).
 class LibcRand {

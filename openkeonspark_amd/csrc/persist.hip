@@ -339,6 +339,8 @@ extern "C" int kge_train_steps_persistent(const kge_model_desc *m, float *const 
         return fail(KGE_ERR_UNSUPPORTED, "kge_train_steps_persistent: TransE / TransH / TransD (TransR's MFMA stages are separate launches)");
     if (m->ent_dim != m->rel_dim || m->ent_dim > 256) return fail(KGE_ERR_UNSUPPORTED, "kge_train_steps_persistent: embedding width <= 256");
     if (adam && (!adam_m || !adam_v)) return fail(KGE_ERR_BAD_ARG, "kge_train_steps_persistent: Adam needs the moment tables");
+    if (e.typed_sampling)
+        return fail(KGE_ERR_UNSUPPORTED, "kge_train_steps_persistent: type-constrained sampling is on and the persistent kernel samples untyped");
     int rc = ensure_device_index();
     if (rc) return rc;
     if ((rc = flush_attached_sampler(stream))) return rc;

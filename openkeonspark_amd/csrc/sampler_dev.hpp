@@ -45,6 +45,17 @@ struct SamplerArgs {
     unsigned ride_first, ride_total;
 };
 
+// Type-constrained sampling: what the TYPED instantiations read on top of that -- the arrays of KgIndex's typed part.  A type of
+// its own, so that SamplerArgs, a by-value argument of every kernel a sampler rides in, stays as it is: those kernels are
+// compiled from the untyped body and do not change with this mode.
+struct TypedSamplerArgs : SamplerArgs {
+    const int2 *typed_len = nullptr;          // [train_dup], loaded together with pos / grp
+    const int4 *type_bounds = nullptr;        // [rel_total]
+    const int32_t *type_tails = nullptr, *type_heads = nullptr, *typed_pos_hr = nullptr, *typed_pos_tr = nullptr;
+};
+template <bool TYPED> struct SamplerArgsOf { using type = SamplerArgs; };
+template <> struct SamplerArgsOf<true> { using type = TypedSamplerArgs; };
+
 __device__ __forceinline__ uint64_t lcg_step(uint64_t s) { return s * kLcgMul + kLcgAdd; }
 
 __device__ __forceinline__ uint64_t lcg_skip(uint64_t s, uint64_t n) {
@@ -107,6 +118,39 @@ __device__ __forceinline__ int filtered_pick_short(const int32_t *__restrict__ v
     return (int)(tmp + lo);
 }
 
+// Type-constrained corruption: the replacement comes from the relation's own tail (new_tail) or head type list L, minus the known
+// tails of (h, r) / heads of (t, r) that occur in it.  K' = the increasing positions inside L of those known ids (typed_pos_hr /
+// typed_pos_tr, `len` of them at the group's offset), c = |L| - |K'|: the pick is filtered_pick's closed form on POSITIONS with
+// tmp = s mod c, then one gather L[pos] -- the only load that depends on the others.  SHORT: up to four positions are requested
+// together with the relation's bounds (clamped, unconditional: a group has at least one slot, so slot 0 can always be read).
+// Returns -1 when c = 0 (no list, or the group exhausts it): the caller then makes the reference's untyped draw from the same s.
+template <bool SHORT>
+__device__ __forceinline__ int typed_pick(const TypedSamplerArgs &a, uint64_t s, bool new_tail, int r, const int4 &gq, const int2 &tl) {
+    const int32_t *__restrict__ vals = new_tail ? a.typed_pos_hr + gq.x : a.typed_pos_tr + gq.z;
+    const int len = new_tail ? tl.x : tl.y;
+    int v[4] = {0, 0, 0, 0};
+    if (SHORT) {
+        const int last = len > 0 ? len - 1 : 0;
+#pragma unroll
+        for (int j = 0; j < 4; j++) v[j] = vals[j < last ? j : last];
+    }
+    const int4 tb = a.type_bounds[r];
+    const int loff = new_tail ? tb.x : tb.z, llen = new_tail ? tb.y : tb.w;
+    const int c = llen - len;
+    if (c <= 0) return -1;
+    const long long tmp = (long long)mod_u64_u32(s, (uint32_t)c);
+    int pos;
+    if (SHORT && len <= 4) {
+        int lo = 0;
+#pragma unroll
+        for (int j = 0; j < 4; j++) lo += (j < len && (long long)v[j] - j <= tmp) ? 1 : 0;
+        pos = (int)(tmp + lo);
+    } else
+        pos = filtered_pick(vals, len, tmp);
+    pos = min(pos, llen - 1);   // (never binding for a consistent index)
+    return (new_tail ? a.type_tails : a.type_heads)[loff + pos];
+}
+
 // s advanced by n < 2^16 steps, n different in every lane: a masked multiply-add per bit with the first jump entries read
 // through compile-time offsets (scalar loads the compiler batches), as many rounds as the widest n of the wave needs
 __device__ __forceinline__ uint64_t lcg_skip_lanes(uint64_t s, unsigned n) {
@@ -122,8 +166,9 @@ __device__ __forceinline__ uint64_t lcg_skip_lanes(uint64_t s, unsigned n) {
 // One scored triple of the batch: slot k of the positive at global batch position p (k = 0 the positive, 1..neg entity
 // negatives, then relation negatives), drawn exactly as virtual thread `id` of the reference draws it (Base.cpp:95-140).
 // `skip_batches` whole batches of this thread's slice are skipped first (a persistent launch samples step s from the
-// states the launch started with).
-__device__ __forceinline__ void sample_slot(const SamplerArgs &a, long long p, long long k, unsigned long long skip_draws, int &oh, int &ot,
+// states the launch started with).  TYPED: entity negatives by typed_pick (the random stream is the same either way).
+template <bool TYPED = false>
+__device__ __forceinline__ void sample_slot(const typename SamplerArgsOf<TYPED>::type &a, long long p, long long k, unsigned long long skip_draws, int &oh, int &ot,
                                             int &orr) {
     const long long id = (long long)((unsigned)p / (unsigned)a.per_thread);   // owning virtual thread (Base.cpp:85-92); B < 2^31
     const long long off = p - id * a.per_thread;  // index inside its slice
@@ -133,6 +178,8 @@ __device__ __forceinline__ void sample_slot(const SamplerArgs &a, long long p, l
     long long i = (long long)mod_magic(s, a.pick_div, a.pick_magic) + (a.new_batch > 0 ? a.train_dup - a.new_batch : 0);
     const int4 tr = a.pos[i];  // (h, t, r, -)
     const int4 gq = a.grp[i];  // loaded together with it (not after the coin): one memory latency instead of two
+    int2 tl = make_int2(0, 0);
+    if constexpr (TYPED) tl = a.typed_len[i];
     oh = tr.x; ot = tr.y; orr = tr.z;
     if (k >= 1 && k <= a.neg) {
         s = lcg_skip(s, 2ull * (unsigned long long)(k - 1));
@@ -140,6 +187,13 @@ __device__ __forceinline__ void sample_slot(const SamplerArgs &a, long long p, l
         const float prob = a.bern ? a.bern_prob[orr] : 500.0f;
         const bool keep_head = (float)(s % 1000ull) < prob;
         s = lcg_step(s);  // Corrupt.h:25: the one draw of the corruption
+        if constexpr (TYPED) {
+            const int typed_id = typed_pick<false>(a, s, keep_head, orr, gq, tl);
+            if (typed_id >= 0) {
+                if (keep_head) ot = typed_id; else oh = typed_id;
+                return;
+            }
+        }
         if (keep_head) {  // corrupt_head(h, r): new TAIL outside tails(h,r)
             long long tmp = (long long)mod_u64_u32(s, (uint32_t)(a.ent_total - gq.y));
             ot = min(filtered_pick(a.tails_hr + gq.x, gq.y, tmp), a.ent_total - 1);   // (clamp: only reachable in that degenerate case)
@@ -168,7 +222,8 @@ __device__ __forceinline__ void write_next_streams(const SamplerArgs &a, int kp,
 }
 
 // More than 64 slots per positive (over 63 negatives): one independent thread per slot, each with its own full jump.
-__device__ __forceinline__ void sample_block_wide(const SamplerArgs &a, long long block, long long n_blocks) {
+template <bool TYPED = false>
+__device__ __forceinline__ void sample_block_wide(const typename SamplerArgsOf<TYPED>::type &a, long long block, long long n_blocks) {
     const int kshift = a.kshift, kp = 1 + a.neg + a.negrel;
     write_next_streams(a, kp, block, n_blocks);
     for (long long g = block * 256 + threadIdx.x; (g >> kshift) < a.n_local; g += n_blocks * 256) {
@@ -176,7 +231,7 @@ __device__ __forceinline__ void sample_block_wide(const SamplerArgs &a, long lon
         const long long k = g & ((1 << kshift) - 1);
         if (k >= kp) continue;
         int oh, ot, orr;
-        sample_slot(a, a.pos_lo + b, k, 0ull, oh, ot, orr);
+        sample_slot<TYPED>(a, a.pos_lo + b, k, 0ull, oh, ot, orr);
         const long long o = b + k * a.out_stride;
         a.out_h[o] = oh; a.out_t[o] = ot; a.out_r[o] = orr;
     }
@@ -195,7 +250,9 @@ constexpr int kBernLds = 2048;
 // Same draws in the same order as Base.cpp:95-140, so the batch is bit-identical to sample_slot's.
 // `block` of `n_blocks` 256-thread workgroups: the body of sample_kernel, also run by workgroups that ride along in another
 // kernel's launch (transe_counts.hip: the bucket scatter carries the NEXT batch's sampler, see kge_sampling_attach).
-__device__ __forceinline__ void sample_block(const SamplerArgs &a, long long block, long long n_blocks, float *bern_lds) {
+// TYPED: entity negatives by typed_pick; only sampler.hip's own kernels instantiate it -- every rider is the untyped body.
+template <bool TYPED = false>
+__device__ __forceinline__ void sample_block(const typename SamplerArgsOf<TYPED>::type &a, long long block, long long n_blocks, float *bern_lds) {
     const int kshift = a.kshift, kp = 1 + a.neg + a.negrel, kmask = (1 << kshift) - 1;
     const unsigned long long draws = 1ull + 2ull * a.neg + a.negrel;
     write_next_streams(a, kp, block, n_blocks);
@@ -235,12 +292,18 @@ __device__ __forceinline__ void sample_block(const SamplerArgs &a, long long blo
         const long long i = __shfl((int)pick, lane & ~kmask);      // the positive's k = 0 lane holds the real one (train_dup < 2^31)
         const int4 tr = a.pos[i];  // (h, t, r, -)
         const int4 gq = a.grp[i];  // loaded together with it (not after the coin): one memory latency instead of two
+        int2 tl = make_int2(0, 0);
+        if constexpr (TYPED) tl = a.typed_len[i];
         int oh = tr.x, ot = tr.y, orr = tr.z;
         if (kk >= 1 && kk <= a.neg) {
             const float prob = a.bern ? (bern_in_lds ? bern_lds[orr] : a.bern_prob[orr]) : 500.0f;
             const bool keep_head = (float)(s % 1000ull) < prob;      // Base.cpp:118: compared in float
             s = lcg_step(s);                                           // Corrupt.h:25: the one draw of the corruption
-            if (keep_head) {  // corrupt_head(h, r): new TAIL outside tails(h,r)
+            int typed_id = -1;
+            if constexpr (TYPED) typed_id = typed_pick<true>(a, s, keep_head, orr, gq, tl);
+            if (typed_id >= 0) {
+                if (keep_head) ot = typed_id; else oh = typed_id;
+            } else if (keep_head) {  // corrupt_head(h, r): new TAIL outside tails(h,r)
                 const long long tmp = (long long)mod_u64_u32(s, (uint32_t)(a.ent_total - gq.y));
                 ot = min(filtered_pick_short(a.tails_hr + gq.x, gq.y, tmp), a.ent_total - 1);   // (clamp: only reachable in that degenerate case)
             } else {          // corrupt_tail(t, r): new HEAD outside heads(t,r)
@@ -272,7 +335,7 @@ __device__ __forceinline__ void sample_block(const SamplerArgs &a, long long blo
 
 // workgroup `i` of the part of an armed sampler that rides in this launch
 __device__ __forceinline__ void sample_block_ride(const SamplerArgs &a, long long i, float *bern_lds) {
-    sample_block(a, (long long)a.ride_first + i, (long long)a.ride_total, bern_lds);
+    sample_block<false>(a, (long long)a.ride_first + i, (long long)a.ride_total, bern_lds);
 }
 
 }  // namespace kge

@@ -85,6 +85,10 @@ def parse_args(argv=None):
                                                              "applied to the parameter rows in place (SGD, or --optimizer LazyAdam: the Adam rule on the rows a step "
                                                              "touches and on their moments; tables and moments replicated across ranks).  Default: automatic for "
                                                              "large tables; LazyAdam always takes the touched-rows update")
+    p.add_argument("--type_constrained_sampling", type=int, default=0,
+                   help="1: entity negatives of a training batch come from the relation's own head / tail type list "
+                        "(type_constrain.txt in --input_path, required then) instead of from all entities; same random stream, "
+                        "same positives (Config.set_type_constrained_sampling)")
     return p.parse_args(argv)
 
 
@@ -115,6 +119,7 @@ def get_conf(argv):
     con.seed = getattr(argv, "seed", 0)
     if getattr(argv, "sparse_rows", -1) >= 0:
         con.sparse_rows = bool(argv.sparse_rows)
+    con.set_type_constrained_sampling(bool(getattr(argv, "type_constrained_sampling", 0)))
     con.init()
     name = argv.model.lower()
     con.set_model({"transh": TransH, "transr": TransR, "transd": TransD}.get(name, TransE))
