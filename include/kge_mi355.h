@@ -590,6 +590,25 @@ int kge_link_prediction_finish(INT first, INT count, INT test_head, const int64_
                                void *stream);
 /* d_ids (DEVICE int32 [count][2]) = the head and tail ids of test triples [first, first+count), kge_link_prediction's order. */
 int kge_test_entity_ids(INT first, INT count, int32_t *d_ids, void *stream);
+/* kge_rank_triples against a ROW RANGE of the entity table (csrc/lp_shard.hip: kge_link_prediction_range's scan for any triples,
+ * counts only).  Triple i = (d_h[i], d_t[i], d_r[i]) (DEVICE int32; any order, any mix of relations, duplicates); tables[0]
+ * holds rows [row_lo, row_lo+rows) of the entity table (row j = entity row_lo+j), tables[1] the whole relation table, and
+ * d_query_rows (DEVICE fp32 [n][2][ent_dim]) the raw h and t row of each triple, which may lie outside the range.
+ * d_counts (DEVICE int64 [n][2][4], zeroed and then accumulated into): side 0 tail / side 1 head (zeros when test_head == 0);
+ *   raw, filtered (train + valid + test), typed, filtered + typed counts of the candidates in the range, other than the target,
+ *   that score strictly below the true triple; NaN never counts.
+ * The score bits are kge_link_prediction_range's (one definition for candidates and targets: a row equal to the target's row
+ * ties and is not counted, whichever range holds it), so for the triples of the test split d_counts equals its d_counts bit for
+ * bit, and the SUM over any cut of the table into ranges equals the whole table as one range.  Against kge_rank_triples a
+ * candidate within an ulp or so of the true triple may fall on the other side of it.
+ * A triple with an id outside [0, ent_total) / [0, rel_total) is disabled -- all its counts stay zero and nothing is indexed
+ * with its ids -- and the call still returns KGE_OK.  n == 0 checks the arguments and the files and launches nothing; rows == 0
+ * only zeroes d_counts.  No host synchronisation and no copy of the triples to the host.  TransE only (KGE_ERR_UNSUPPORTED
+ * otherwise; ent_dim in [1, 1024]); 0 <= n < 2^30, the range inside the table and non-null arrays when n > 0 (KGE_ERR_BAD_ARG);
+ * needs importTestFiles (KGE_ERR_NO_DATASET).  Nothing is written to d_counts when an error is returned. */
+int kge_rank_triples_range(const kge_model_desc *m, const float *const tables[KGE_MAX_TABLES], INT row_lo, INT rows,
+                           const float *d_query_rows, const int32_t *d_h, const int32_t *d_t, const int32_t *d_r, INT n, INT test_head,
+                           int64_t *d_counts, void *stream);
 
 /* Filtered ranks of caller-supplied triples on the device (csrc/rank.hip): triple i = (d_h[i], d_t[i], d_r[i]) (DEVICE int32),
  * in any order, with any mix of relations and with duplicates -- the validation split, or any triples of the caller's.

@@ -1938,22 +1938,24 @@ class Config(object):
                                                     1 if test_head else 0, out.ctypes.data, self._stream()), self.lib)
         return out, self._lp_normalise(self._lp_sums(out, test_head), count)
 
-    def _rank_device(self, dev, test_head):
-        """kge_rank_triples on an int32 device tensor [3, n] (h, t, r; ids already checked) -> int64 numpy [n, 2, 4]."""
+    def _rank_device(self, dev, test_head, into=None):
+        """kge_rank_triples on an int32 device tensor [3, n] (h, t, r; ids already checked) -> int64 numpy [n, 2, 4]; with
+        `into` (a contiguous int64 device tensor [n, 2, 4]) the counts are left there and nothing is copied back."""
         import torch
         n = dev.shape[1]
-        counts = torch.empty((n, 2, 4), dtype=torch.int64, device=self.device)
+        counts = into if into is not None else torch.empty((n, 2, 4), dtype=torch.int64, device=self.device)
         # (an empty tensor has no address and the entry point refuses null pointers: n == 0 still checks the files, on a spare row)
         ids, out = (dev, counts) if n else (torch.zeros((3, 1), dtype=torch.int32, device=self.device),
                                             torch.zeros((1, 2, 4), dtype=torch.int64, device=self.device))
         _lib.check(self.lib.kge_rank_triples(ctypes.byref(self._desc), self._tab_ptrs, ids[0].data_ptr(), ids[1].data_ptr(),
                                              ids[2].data_ptr(), n, 1 if test_head else 0, out.data_ptr(), self._stream()), self.lib)
-        return counts.cpu().numpy()
+        return counts.cpu().numpy() if into is None else None
 
     def _refuse_sharded_rank(self, what):
         if self._sharded("ent_embeddings"):
-            raise KgeError("%s over an entity table sharded across ranks is not supported: rank the test triples with "
-                           "link_prediction (a collective on sharded tables) instead" % what)
+            raise KgeError("%s over an entity table sharded across ranks is not supported: call the collective "
+                           "%s_distributed on every rank (or rank the test triples with link_prediction, a collective on "
+                           "sharded tables)" % (what, what))
 
     def rank_triples(self, h, t, r, test_head=True):
         """Rank any triples on the device (kge_rank_triples): h, t, r are 1-D id arrays of one length, in any order, with any
@@ -1970,6 +1972,32 @@ class Config(object):
         counts = self._rank_device(torch.from_numpy(host).to(self.device), test_head)
         return counts, self._lp_normalise(self._lp_sums(counts, test_head), host.shape[1])
 
+    def rank_triples_distributed(self, h, t, r, test_head=True):
+        """rank_triples as a collective: every rank passes the same triples and gets the same (counts int64 [n, 2, 4],
+        metrics), with rank_triples's column meaning and metric names.  Arguments invalid on any rank (an id out of range is
+        found before anything is launched), or n / test_head differing between ranks, raise KgeError on every rank and leave
+        none waiting.
+        On an entity table sharded across ranks (TransE) every rank ranks the triples against its own rows
+        (kge_rank_triples_range), in rounds of lp_shard_query_bytes // (2 D 4) triples whose h and t rows come from their
+        owners, and one SUM all-reduce merges the counts: bit for bit those of one process over the whole table with the same
+        kernel, for any number of ranks.  Its scores are link_prediction's on a sharded table: a candidate within an ulp or so
+        of the true triple may fall on the other side of it than kge_rank_triples (rank_triples) puts it.
+        On replicated tables (all four models) rank g ranks the g-th contiguous slice of the triples with kge_rank_triples and
+        one SUM all-reduce merges the slices: exactly rank_triples's counts.  With one process and no process group it is
+        rank_triples."""
+        import torch
+        if not self._sharded("ent_embeddings") and self.world_size <= 1:
+            return self.rank_triples(h, t, r, test_head)
+        err, dev = None, None
+        try:
+            host = np.stack([np.asarray(h).reshape(-1), np.asarray(t).reshape(-1), np.asarray(r).reshape(-1)]).astype(np.int32)
+            self._check_ids(host)
+            dev = torch.from_numpy(np.ascontiguousarray(host)).to(self.device)
+        except (KgeError, ValueError, TypeError, OverflowError) as e:
+            err = e
+        counts = shard_eval.rank_triples(self, dev, err, test_head)
+        return counts, self._lp_normalise(self._lp_sums(counts, test_head), counts.shape[0])
+
     def _valid_positives(self):
         """The triples of valid2id.txt in file order, int32 [3, V] (h, t, r), read once."""
         if getattr(self, "_valid_pos", None) is None:
@@ -1985,13 +2013,19 @@ class Config(object):
         libc rand() sequence does not move): (counts, metrics) as rank_triples returns them -- filtered Hits@10 and MRR on the
         validation split for model selection.  sample = N > 0 ranks the N triples at the indices floor(i V / N), i < N (all
         of them when N >= V); one check scores V x E pairs per side otherwise.  The device ids are kept between calls."""
-        import torch
         self._refuse_sharded_rank("validation_link_prediction")
+        counts = self._rank_device(self._valid_rank_ids(sample, "validation_link_prediction"), test_head)
+        return counts, self._lp_normalise(self._lp_sums(counts, test_head), counts.shape[0])
+
+    def _valid_rank_ids(self, sample, what):
+        """The validation positives a check ranks, as an int32 device tensor [3, n] (h, t, r; ids checked): all V of
+        valid2id.txt, or with 0 < sample < V those at the indices floor(i V / sample).  Kept between calls."""
+        import torch
         valid = self._valid_positives()
         total = valid.shape[1]
         sample = int(sample)
         if sample < 0:
-            raise KgeError("validation_link_prediction: sample must be >= 0, got %d" % sample)
+            raise KgeError("%s: sample must be >= 0, got %d" % (what, sample))
         if 0 < sample < total:
             valid = valid[:, (np.arange(sample, dtype=np.int64) * total) // sample]
         else:
@@ -2001,7 +2035,21 @@ class Config(object):
             host = np.ascontiguousarray(valid)
             self._check_ids(host)
             cached = self._valid_rank_dev = (sample, torch.from_numpy(host).to(self.device))
-        counts = self._rank_device(cached[1], test_head)
+        return cached[1]
+
+    def validation_link_prediction_distributed(self, test_head=True, sample=0):
+        """validation_link_prediction as a collective, ranked as rank_triples_distributed ranks (sharded or replicated
+        tables; its near-tie caveat on a sharded table applies): the same valid2id.txt positives, the same `sample` rule and
+        the same cached device ids; every rank calls it with the same arguments and gets the same (counts, metrics).  A bad
+        `sample` or an unreadable valid2id.txt on any rank raises KgeError on every rank."""
+        if not self._sharded("ent_embeddings") and self.world_size <= 1:
+            return self.validation_link_prediction(test_head, sample)
+        err, dev = None, None
+        try:
+            dev = self._valid_rank_ids(sample, "validation_link_prediction_distributed")
+        except (KgeError, ValueError, TypeError, OverflowError, OSError) as e:
+            err = e
+        counts = shard_eval.rank_triples(self, dev, err, test_head)
         return counts, self._lp_normalise(self._lp_sums(counts, test_head), counts.shape[0])
 
     @staticmethod

@@ -108,6 +108,7 @@ def _declare(L):
     L.kge_relation_prediction_rows.argtypes = [ctypes.POINTER(ModelDesc), tabs, vp, i64, i64, vp, vp]
     L.kge_link_prediction_range.argtypes = [ctypes.POINTER(ModelDesc), tabs, i64, i64, vp, i64, i64, i64, vp, vp, vp]
     L.kge_link_prediction_finish.argtypes = [i64, i64, i64, vp, vp, vp, vp]
+    L.kge_rank_triples_range.argtypes = [ctypes.POINTER(ModelDesc), tabs, i64, i64, vp, vp, vp, vp, i64, i64, vp, vp]
     L.kge_tc_fit.argtypes = [vp, vp, i64, vp, vp, vp]
     L.kge_tc_apply.argtypes = [i64, vp, vp, vp, i64, vp, vp, vp]
     L.kge_tc_roc.argtypes = [vp, vp, i64, i64, vp, vp, i64, vp, vp, i64, vp, vp]

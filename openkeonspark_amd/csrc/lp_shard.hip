@@ -15,8 +15,16 @@
 // (request, column) and one 64-bit atomicMin per arg-min per workgroup.  Integer sums and a min: the result does not depend on
 // the schedule, nor on how the table is cut into ranges.
 // Stage 2 (lp_finish_kernel), one thread per (triple, side): arg-mins and ontology classes as rank_kernel resolves them.
+//
+// kge_rank_triples_range is the same scan for ANY device-resident triple list (d_h, d_t, d_r), counts only: lp_range_kernel's
+// KEYS = false instantiation takes triple p from the three id arrays instead of the sorted test split, disables a triple
+// whose ids are out of range before anything is indexed with them, and carries no arg-min keys (no s_key, no key registers, no
+// 64-bit atomicMin, no stage 2).  usum / inv_norm / pair_score and the order of every operation are shared, so the counts of
+// the test split's triples are kge_link_prediction_range's, bit for bit.  TransE's candidates do not depend on the relation:
+// no grouping by relation, no host synchronisation.
 #include <algorithm>
 #include <cstring>
+#include <type_traits>
 #include <vector>
 
 #include "eval_dev.hpp"
@@ -83,19 +91,52 @@ struct RangeArgs {
     const float *ent;          // rows [row_lo, row_lo + rows) of the entity table, row i = entity row_lo + i
     const float *rel;          // the whole relation table
     const float *qrows;        // [count][2][D]: raw h and t rows of the test triples
-    const int4 *test;          // (h, t, r) in kge_link_prediction's order
+    const int4 *test;          // KEYS: (h, t, r) in kge_link_prediction's order, triple p at test[first + p]
     EvalFilterView ev;
     long long first, count, row_lo, rows, slice_len;
     int D, test_head;
-    long long *counts, *keys;  // [count][2][4]
+    long long *counts, *keys;  // [count][2][4] (keys: KEYS only)
 };
+// the counts-only instantiation's arguments: the caller's triples in place of `test` / `first`
+struct TripleRangeArgs : RangeArgs {
+    const int32_t *h, *t, *r;  // triple p = (h[p], t[p], r[p]), ids unchecked
+    long long E, R;            // the id bounds a triple is checked against
+};
+template <bool KEYS>
+using RangeArgsOf = std::conditional_t<KEYS, RangeArgs, TripleRangeArgs>;
 
-template <int L, int C, int Q, int U>
-__global__ __launch_bounds__(256) void lp_range_kernel(RangeArgs a) {
+// Triple p of the call.  KEYS: from the library's own test split, in range by construction.  !KEYS: from the caller's arrays;
+// false (and nothing may be indexed with the ids) when one of them is out of range.
+template <bool KEYS>
+__device__ __forceinline__ bool triple_at(const RangeArgsOf<KEYS> &a, long long p, int &h, int &t, int &r) {
+    if constexpr (KEYS) {
+        const int4 tt = a.test[a.first + p];
+        h = tt.x; t = tt.y; r = tt.z;
+        return true;
+    } else {
+        h = a.h[p]; t = a.t[p]; r = a.r[p];
+        return h >= 0 && h < a.E && t >= 0 && t < a.E && r >= 0 && r < a.R;
+    }
+}
+
+// Its relation alone, for the gather of the relation's row; false as triple_at.
+template <bool KEYS>
+__device__ __forceinline__ bool relation_at(const RangeArgsOf<KEYS> &a, long long p, int &r) {
+    if constexpr (KEYS) {
+        r = a.test[a.first + p].z;
+        return true;
+    } else {
+        int h, t;
+        return triple_at<false>(a, p, h, t, r);
+    }
+}
+
+template <bool KEYS, int L, int C, int Q, int U>
+__global__ __launch_bounds__(256) void lp_range_kernel(RangeArgsOf<KEYS> a) {
     constexpr int TEAMS = 256 / L;
     constexpr int NR = 2 * Q;               // requests: q < Q tail of triple q, q >= Q head of triple q - Q
     __shared__ int s_cnt[NR][4];
-    __shared__ unsigned long long s_key[NR][4];
+    __shared__ unsigned long long s_key[KEYS ? NR : 1][4];
     // per request, read on the slow path only: known range (and its first / last id), type range (and its first / last id)
     __shared__ long long s_klo[NR], s_khi[NR];
     __shared__ int s_kmin[NR], s_kmax[NR], s_tlo[NR], s_thi[NR], s_tmin[NR], s_tmax[NR], s_tgt[NR];
@@ -105,14 +146,17 @@ __global__ __launch_bounds__(256) void lp_range_kernel(RangeArgs a) {
     const int team = threadIdx.x / L;
     const long long p0 = (long long)blockIdx.x * Q;
     const int nb = (int)min((long long)Q, a.count - p0);
-    for (int i = threadIdx.x; i < NR * 4; i += blockDim.x) { s_cnt[i / 4][i % 4] = 0; s_key[i / 4][i % 4] = kNoKey; }
+    if constexpr (KEYS) {
+        for (int i = threadIdx.x; i < NR * 4; i += blockDim.x) { s_cnt[i / 4][i % 4] = 0; s_key[i / 4][i % 4] = kNoKey; }
+    } else {
+        for (int i = threadIdx.x; i < NR * 4; i += blockDim.x) s_cnt[i / 4][i % 4] = 0;
+    }
     if ((int)threadIdx.x < NR) {
         const int q = threadIdx.x, p = q < Q ? q : q - Q;
         const bool head = q >= Q;
         s_tgt[q] = -1; s_klo[q] = s_khi[q] = 0; s_kmin[q] = s_kmax[q] = 0; s_tlo[q] = s_thi[q] = 0; s_tmin[q] = s_tmax[q] = 0;
-        if (p < nb && (!head || a.test_head)) {
-            const int4 tt = a.test[a.first + p0 + p];
-            const int h = tt.x, t = tt.y, r = tt.z;
+        int h, t, r;
+        if (p < nb && (!head || a.test_head) && triple_at<KEYS>(a, p0 + p, h, t, r)) {
             s_tgt[q] = head ? h : t;
             const int4 *known = head ? a.ev.all_t : a.ev.all;
             long long lo, hi;
@@ -132,8 +176,8 @@ __global__ __launch_bounds__(256) void lp_range_kernel(RangeArgs a) {
     for (int q = 0; q < Q; q++) {
 #pragma unroll
         for (int c = 0; c < C; c++) { V[q][c] = 0.f; V[Q + q][c] = 0.f; }
-        if (q < nb) {
-            const int r = a.test[a.first + p0 + q].z;
+        int r;
+        if (q < nb && relation_at<KEYS>(a, p0 + q, r)) {   // (a disabled triple keeps zero vectors and no target)
             float xh[C], xt[C], xr[C];
             tm.load(a.qrows, 2 * (p0 + q), xh);
             tm.load(a.qrows, 2 * (p0 + q) + 1, xt);
@@ -156,7 +200,7 @@ __global__ __launch_bounds__(256) void lp_range_kernel(RangeArgs a) {
     const int4 *known_arr = hd ? a.ev.all_t : a.ev.all;
     const int32_t *types = hd ? a.ev.head_type : a.ev.tail_type;
     int cnt[4] = {0, 0, 0, 0};
-    unsigned long long key[4] = {kNoKey, kNoKey, kNoKey, kNoKey};
+    unsigned long long key[4] = {kNoKey, kNoKey, kNoKey, kNoKey};   // (never read without KEYS)
     const long long j0 = (long long)blockIdx.y * a.slice_len;
     const long long j1 = min(a.rows, j0 + a.slice_len);
     const int nr = a.test_head ? NR : Q;   // (block-uniform: head requests are scored only when asked for)
@@ -197,13 +241,19 @@ __global__ __launch_bounds__(256) void lp_range_kernel(RangeArgs a) {
                 while (lo < hi) { const int mid = (lo + hi) >> 1; if (types[mid] < id) lo = mid + 1; else hi = mid; }
                 typed = lo < th && types[lo] == id;
             }
-            const unsigned long long k = pack_key(s, id);
-            cnt[0]++; key[0] = min(key[0], k);
-            if (!known) cnt[1]++;
-            if (hd || !known) key[1] = min(key[1], k);   // Test.h:69-74: the head side updates this arg-min outside the filter
-            if (typed) {
-                cnt[2]++; key[2] = min(key[2], k);
-                if (!known) { cnt[3]++; key[3] = min(key[3], k); }
+            if constexpr (KEYS) {
+                const unsigned long long k = pack_key(s, id);
+                cnt[0]++; key[0] = min(key[0], k);
+                if (!known) cnt[1]++;
+                if (hd || !known) key[1] = min(key[1], k);   // Test.h:69-74: the head side updates this arg-min outside the filter
+                if (typed) {
+                    cnt[2]++; key[2] = min(key[2], k);
+                    if (!known) { cnt[3]++; key[3] = min(key[3], k); }
+                }
+            } else {
+                cnt[0]++;
+                if (!known) cnt[1]++;
+                if (typed) { cnt[2]++; if (!known) cnt[3]++; }
             }
         }
     }
@@ -211,7 +261,7 @@ __global__ __launch_bounds__(256) void lp_range_kernel(RangeArgs a) {
 #pragma unroll
         for (int i = 0; i < 4; i++) {
             if (cnt[i]) atomicAdd(&s_cnt[own][i], cnt[i]);
-            if (key[i] != kNoKey) atomicMin(&s_key[own][i], key[i]);
+            if constexpr (KEYS) { if (key[i] != kNoKey) atomicMin(&s_key[own][i], key[i]); }
         }
     }
     __syncthreads();
@@ -221,7 +271,7 @@ __global__ __launch_bounds__(256) void lp_range_kernel(RangeArgs a) {
         const long long o = ((p0 + (q < Q ? q : q - Q)) * 2 + (q >= Q ? 1 : 0)) * 4 + col;
         if (s_cnt[q][col]) atomicAdd((unsigned long long *)&a.counts[o], (unsigned long long)s_cnt[q][col]);
         // counted scores are >= +0, so their keys have the top bit set: as int64 they are negative and order as the unsigned keys do
-        if (s_key[q][col] != kNoKey) atomicMin(&a.keys[o], (long long)s_key[q][col]);
+        if constexpr (KEYS) { if (s_key[q][col] != kNoKey) atomicMin(&a.keys[o], (long long)s_key[q][col]); }
     }
 }
 
@@ -283,14 +333,14 @@ __global__ void test_entity_ids_kernel(const int4 *test, long long first, long l
 }
 
 // about 2 048 workgroups (eight per CU) over the (triple block x slice) grid, slices of at least 1 024 rows
-template <int L, int C, int Q, int U>
-int launch_range_t(RangeArgs a, hipStream_t stream) {
+template <bool KEYS, int L, int C, int Q, int U>
+int launch_range_t(RangeArgsOf<KEYS> a, hipStream_t stream) {
     const long long qblocks = (a.count + Q - 1) / Q;
     long long slices = (2048 + qblocks - 1) / qblocks;
     slices = std::max(1LL, std::min(slices, a.rows / 1024));
     a.slice_len = (a.rows + slices - 1) / slices;
     slices = (a.rows + a.slice_len - 1) / a.slice_len;
-    hipLaunchKernelGGL((lp_range_kernel<L, C, Q, U>), dim3((unsigned)qblocks, (unsigned)slices), dim3(256), 0, stream, a);
+    hipLaunchKernelGGL((lp_range_kernel<KEYS, L, C, Q, U>), dim3((unsigned)qblocks, (unsigned)slices), dim3(256), 0, stream, a);
     return hip_check(hipGetLastError(), "lp range launch");
 }
 
@@ -299,13 +349,14 @@ int launch_range_t(RangeArgs a, hipStream_t stream) {
 constexpr int range_q(int L, int C) { return L == 64 && C == 4 ? 16 : (C == 16 ? 4 : 8); }
 constexpr int range_u(int C) { return C <= 2 ? 4 : (C == 16 ? 1 : 2); }
 
-int launch_range(const RangeArgs &a, hipStream_t stream) {
+template <bool KEYS>
+int launch_range(const RangeArgsOf<KEYS> &a, hipStream_t stream) {
     int rc = KGE_OK;
     const bool shaped = for_team_shape(a.D, [&](auto t) {
         constexpr int L = decltype(t)::L, C = decltype(t)::C;
-        rc = launch_range_t<L, C, range_q(L, C), range_u(C)>(a, stream);
+        rc = launch_range_t<KEYS, L, C, range_q(L, C), range_u(C)>(a, stream);
     });
-    return shaped ? rc : fail(KGE_ERR_UNSUPPORTED, "kge_link_prediction_range: embedding dimension > 1024");
+    return shaped ? rc : fail(KGE_ERR_UNSUPPORTED, "link prediction over a row range: embedding dimension > 1024");
 }
 
 long long *g_out = nullptr;
@@ -346,7 +397,34 @@ int kge_link_prediction_range(const kge_model_desc *m, const float *const tables
     a.first = first; a.count = count; a.row_lo = row_lo; a.rows = rows;
     a.D = (int)m->ent_dim; a.test_head = test_head ? 1 : 0;
     a.counts = (long long *)d_counts; a.keys = (long long *)d_keys;
-    return launch_range(a, stream);
+    return launch_range<true>(a, stream);
+}
+
+int kge_rank_triples_range(const kge_model_desc *m, const float *const tables[KGE_MAX_TABLES], INT row_lo, INT rows,
+                           const float *d_query_rows, const int32_t *d_h, const int32_t *d_t, const int32_t *d_r, INT n, INT test_head,
+                           int64_t *d_counts, void *stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    if (!m || !tables) return fail(KGE_ERR_BAD_ARG, "kge_rank_triples_range: null model or tables");
+    if (m->model != KGE_TRANSE) return fail(KGE_ERR_UNSUPPORTED, "kge_rank_triples_range: TransE only");
+    if (m->ent_dim < 1 || m->ent_dim > 1024) return fail(KGE_ERR_UNSUPPORTED, "kge_rank_triples_range: embedding dimension must be in [1, 1024]");
+    if (row_lo < 0 || rows < 0 || row_lo + rows > m->ent_total) return fail(KGE_ERR_BAD_ARG, "kge_rank_triples_range: row range outside the entity table");
+    if (n < 0) return fail(KGE_ERR_BAD_ARG, "kge_rank_triples_range: negative triple count");
+    if (n >= (INT(1) << 30)) return fail(KGE_ERR_BAD_ARG, "kge_rank_triples_range: more than 2^30 triples in one call");
+    if (!device_ok()) return fail(KGE_ERR_NO_DEVICE, "kge_rank_triples_range: no usable HIP device");
+    TripleRangeArgs a = {};
+    int rc = eval_filter_view(false, a.ev);
+    if (rc) return rc;
+    if (n == 0) return KGE_OK;
+    if (!d_counts || !d_query_rows || !d_h || !d_t || !d_r || (rows > 0 && (!tables[0] || !tables[1])))
+        return fail(KGE_ERR_BAD_ARG, "kge_rank_triples_range: null table, query, triple or output array");
+    if ((rc = hip_check(hipMemsetAsync(d_counts, 0, sizeof(int64_t) * 8 * (size_t)n, stream), "zero rank range counts"))) return rc;
+    if (rows == 0) return KGE_OK;
+    a.ent = tables[0]; a.rel = tables[1]; a.qrows = d_query_rows;
+    a.h = d_h; a.t = d_t; a.r = d_r;
+    a.count = n; a.row_lo = row_lo; a.rows = rows; a.E = m->ent_total; a.R = m->rel_total;
+    a.D = (int)m->ent_dim; a.test_head = test_head ? 1 : 0;
+    a.counts = (long long *)d_counts;
+    return launch_range<false>(a, stream);
 }
 
 int kge_link_prediction_finish(INT first, INT count, INT test_head, const int64_t *d_counts, const int64_t *d_keys, int64_t *h_out,

@@ -68,7 +68,9 @@ def parse_args(argv=None):
                         "hits10 / mrr = filtered Hits@10 / mean reciprocal rank of the validation triples (tail side; head side too with "
                         "--test_head 1), higher is better.  A ranking check scores every validation triple against every entity -- on a "
                         "large graph several training epochs of GPU time -- so rank a sample with --early_stop_rank_triples and / or "
-                        "check less often with --early_stop_stopping_step")
+                        "check less often with --early_stop_stopping_step.  With an entity table sharded across ranks "
+                        "(--sparse_rows 1 on N ranks, TransE) the check is a collective: every rank ranks the triples against its own "
+                        "rows and the counts are all-reduced, so every rank takes the same decision")
     p.add_argument("--early_stop_rank_triples", type=int, default=0,
                    help="hits10 / mrr: rank only this many validation triples, evenly spaced through valid2id.txt (0 = all of them)")
     p.add_argument("--model", type=str, default="TransE")
@@ -399,9 +401,12 @@ def _init_rank_validation(con):
 
 def _validation_rank_metric(con, argv):
     """Filtered Hits@10 or MRR of the validation triples, the mean over the ranked sides (Config.validation_link_prediction).
-    With replicated tables every rank ranks the same triples itself: identical tables, identical decisions, no collective."""
+    With replicated tables every rank ranks the same triples itself: identical tables, identical decisions, no collective.
+    With a sharded entity table it is the collective Config.validation_link_prediction_distributed: every rank reaches the
+    check at the same global step and receives the same all-reduced counts, so the decisions agree without a broadcast."""
     test_head = bool(argv.test_head)
-    metrics = con.validation_link_prediction(test_head=test_head, sample=argv.early_stop_rank_triples)[1]
+    rank_valid = con.validation_link_prediction_distributed if con._sharded("ent_embeddings") else con.validation_link_prediction
+    metrics = rank_valid(test_head=test_head, sample=argv.early_stop_rank_triples)[1]
     name = "_filter_tot" if argv.early_stop_metric == "hits10" else "_filter_reci_rank"
     sides = ("r", "l") if test_head else ("r",)
     return sum(metrics[p + name] for p in sides) / len(sides)
@@ -462,9 +467,6 @@ def main_fun(argv):
         return metrics
 
     metric = argv.early_stop_metric
-    if metric != "accuracy" and con._sharded("ent_embeddings"):
-        raise KgeError("--early_stop_metric %s over an entity table sharded across ranks is not supported "
-                       "(Config.validation_link_prediction refuses it); use --early_stop_metric accuracy" % metric)
     valid = _init_validation(con, argv) if metric == "accuracy" else _init_rank_validation(con)
     best_acc, wait_steps_acc, best_step_acc = -1.0, 0, last_global_step
     iterations = con.train_times * con.nbatches + last_global_step      # distribute_training.py:205

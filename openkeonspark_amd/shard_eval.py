@@ -1,7 +1,7 @@
 """Evaluation over an entity table sharded across ranks (`con._shard`).  Every function here is a collective: each rank calls it
 the same number of times, and the order in which it enters torch.distributed collectives (fetch_rows, all_reduce, agree and the
-`parallel` calls written out in it) is its contract with the other ranks.  top_k_entities and relation_prediction open with
-agree; test_step and link_prediction have no header step.  Functions take the Config first; its public methods dispatch here.
+`parallel` calls written out in it) is its contract with the other ranks.  top_k_entities, relation_prediction and rank_triples
+open with agree; test_step and link_prediction have no header step.  rank_triples also serves replicated tables.  Functions take the Config first; its public methods dispatch here.
 """
 import ctypes
 
@@ -56,7 +56,7 @@ def all_reduce(con, t, op):
         t.copy_(h)
 
 
-def agree(con, what, err, fields, same, differ, per):
+def agree(con, what, err, fields, same, differ, per, where=" on a sharded entity table"):
     """The first collective of a call whose arguments can be wrong: one all-gather of the int64 header [ok, *fields, per], so
     that a bad call raises KgeError on every rank and leaves none waiting in a later collective.  `err` is what this
     rank's own argument check raised (or None), `same` the header columns that must be equal on all ranks, `differ` their
@@ -67,7 +67,7 @@ def agree(con, what, err, fields, same, differ, per):
     allh = torch.empty((con.world_size, hdr.numel()), dtype=torch.int64, device=con.device)
     par.all_gather_chunks(allh.view(-1), hdr, con._pg)
     allh = allh.cpu().numpy()
-    on = "%s on a sharded entity table: " % what
+    on = "%s%s: " % (what, where)
     if err is not None:
         raise KgeError(on + "%s" % err) from err
     if not allh[:, 0].all():
@@ -216,3 +216,53 @@ def relation_prediction(con, first, count):
         del query
     all_reduce(con, counts, dist.ReduceOp.SUM)
     return counts[:count].cpu().numpy()
+
+
+def rank_triples(con, ids, err, test_head):
+    """Config.rank_triples_distributed.  `ids` is the int32 device tensor [3, n] (h, t, r; ids already checked) or None, `err`
+    what this rank's own argument check raised (or None).  The ranks first agree on a header (validity, n, test_head, triples
+    per round); the evaluation files are checked before it, without a launch.  -> int64 numpy [n, 2, 4].
+    Sharded entity table: in rounds of `per` triples the 2 per h and t rows come from their owners (query_rows, laid out
+    [per][2][D]) and kge_rank_triples_range ranks the round against this rank's rows [lo, hi) into its slice of one
+    [n, 2, 4] device tensor; ONE SUM all-reduce of that tensor follows the last round.
+    Replicated tables (any model): rank g ranks the g-th contiguous slice of the triples with kge_rank_triples into a zeroed
+    [n, 2, 4]; one SUM all-reduce merges the slices."""
+    import torch
+    import torch.distributed as dist
+    L, st, W, D, dev = con.lib, con._stream(), con.world_size, con.hidden_size, con.device
+    sharded = con._sharded("ent_embeddings")
+    if sharded and not dist.is_initialized():      # no process group, so no other rank can be waiting for this one
+        raise KgeError("rank_triples_distributed on a sharded entity table needs the process group it was sharded over")
+    th = 1 if test_head else 0
+    n = -1
+    if err is None:
+        n = int(ids.shape[1])
+        try:      # the arguments and the evaluation files, checked without a launch (no triples)
+            if sharded:
+                lo, hi = con._shard["lo"], con._shard["hi"]
+                _lib.check(L.kge_rank_triples_range(ctypes.byref(con._desc), con._tab_ptrs, lo, hi - lo, None, None, None, None, 0, th,
+                                                    None, st), L)
+            else:
+                con._rank_device(ids[:, :0], test_head)
+        except KgeError as e:
+            err, n = e, -1
+    per = max(1, int(con.lp_shard_query_bytes) // (2 * D * 4))
+    _, per = agree(con, "rank_triples_distributed", err, (n, th), [1, 2], "numbers of triples or test_head", per,
+                   where=" on a sharded entity table" if sharded else "")
+    counts = torch.zeros((max(n, 1), 2, 4), dtype=torch.int64, device=dev)
+    if sharded:
+        for c0 in range(0, n, per):
+            m = min(per, n - c0)
+            pairs = ids[:2, c0:c0 + m].t().contiguous().view(-1)      # h0, t0, h1, t1, ...
+            query = query_rows(con, pairs, 2 * m)                      # [m][2][D]: the raw h and t row of each triple
+            _lib.check(L.kge_rank_triples_range(ctypes.byref(con._desc), con._tab_ptrs, lo, hi - lo, query.data_ptr(),
+                                                ids[0, c0:].data_ptr(), ids[1, c0:].data_ptr(), ids[2, c0:].data_ptr(), m, th,
+                                                counts[c0].data_ptr(), st), L)
+            del query
+    else:
+        cs = par.chunk_size(n, W)
+        c0, c1 = min(con.rank * cs, n), min((con.rank + 1) * cs, n)
+        if c1 > c0:
+            con._rank_device(ids[:, c0:c1].contiguous(), test_head, into=counts[c0:c1])
+    all_reduce(con, counts, dist.ReduceOp.SUM)
+    return counts[:n].cpu().numpy()

@@ -1,0 +1,558 @@
+"""Ranks of caller-supplied triples over a row range of the entity table (kge_rank_triples_range) and the collectives built on
+it (Config.rank_triples_distributed / validation_link_prediction_distributed; the driver's --early_stop_metric hits10 | mrr on
+a sharded table): bit equality with kge_link_prediction_range's counts on the test split, invariance under any cut of the table
+and any order of the triples, kge_rank_triples under a constructive near-tie rule, ties with a copied target row, the filtered
+and typed columns, the refusals, 2 and 4 gloo ranks against one process over the union table, replicated tables, the driver.
+
+Every test first checks that the entry point and the collective exist."""
+import datetime
+import json
+import os
+import sys
+
+import numpy as np
+import pytest
+
+from conftest import ROOT
+from shard_rig import KG, finish_rank, load_ranks, make_config, run_worlds, start_rank, union_config
+from test_gpu_lp_shard import cuts, known_set, lp_ranges, read_triples, sorted_test_triples, type_lists
+
+pytestmark = pytest.mark.gpu
+
+KGE_ERR_NO_DATASET, KGE_ERR_BAD_ARG, KGE_ERR_UNSUPPORTED = -2, -3, -4
+DIMS = [12, 24, 48, 100, 200, 512, 520]                               # one per rung of for_team_shape
+BLOCK = {12: 8, 24: 8, 48: 8, 100: 8, 200: 16, 512: 8, 520: 4}       # Q, the triples of one workgroup, on that rung
+PG_TIMEOUT = datetime.timedelta(seconds=60)
+
+
+def require_entry_points():
+    from openkeonspark_amd import _lib
+    from openkeonspark_amd.Config import Config
+    L = _lib.lib()
+    assert hasattr(L, "kge_rank_triples_range"), "kge_rank_triples_range is not exported"
+    assert hasattr(Config, "rank_triples_distributed"), "Config.rank_triples_distributed is missing"
+    assert hasattr(Config, "validation_link_prediction_distributed")
+    return L
+
+
+def split(path, name):
+    """The triples of a split file as int64 [n, 3] (h, t, r), file order."""
+    return np.stack(read_triples(path, name + "2id.txt"), axis=1)
+
+
+def raw_call(con, L, ptrs, lo, rows, query, ids, n, test_head, counts, desc=None):
+    import ctypes
+    import torch
+    ptr = lambda x: None if x is None else x.data_ptr()
+    h, t, r = ids if ids is not None else (None, None, None)
+    rc = L.kge_rank_triples_range(ctypes.byref(desc if desc is not None else con._desc), ptrs, lo, rows, ptr(query), ptr(h), ptr(t),
+                                  ptr(r), n, 1 if test_head else 0, ptr(counts), con._stream())
+    torch.cuda.synchronize()
+    return rc
+
+
+def device_triples(con, triples):
+    """-> (int32 device [3, n], the raw h and t rows [n][2][D])."""
+    import torch
+    ids = torch.from_numpy(np.ascontiguousarray(np.asarray(triples, dtype=np.int64).reshape(-1, 3).T.astype(np.int32))).to(con.device)
+    query = con._tables[0].index_select(0, ids[:2].t().reshape(-1).long()).contiguous()
+    return ids, query
+
+
+def rank_ranges(con, parts, triples, test_head=True):
+    """kge_rank_triples_range over the cut `parts` [(lo, hi), ...] of con's entity table, each range in a tensor of its own and
+    each call into a buffer pre-filled with -9: -> the summed counts, int64 numpy [n, 2, 4]."""
+    import torch
+    from openkeonspark_amd import _lib
+    L = require_entry_points()
+    ent, rel = con._tables[0], con._tables[1]
+    ids, query = device_triples(con, triples)
+    n = ids.shape[1]
+    total = torch.zeros((n, 2, 4), dtype=torch.int64, device=con.device)
+    for lo, hi in parts:
+        part = ent[lo:hi].clone() if hi > lo else torch.empty((1, ent.shape[1]), dtype=ent.dtype, device=ent.device)
+        c = torch.full((max(n, 1), 2, 4), -9, dtype=torch.int64, device=con.device)
+        rc = raw_call(con, L, _lib.table_ptrs([part.data_ptr(), rel.data_ptr()]), lo, hi - lo, query, (ids[0], ids[1], ids[2]), n,
+                      test_head, c)
+        _lib.check(rc, L)
+        if n == 0:
+            assert bool((c == -9).all().item())          # nothing launched
+        else:
+            assert bool((c >= 0).all().item())           # every element written
+            total += c[:n]
+    return total.cpu().numpy()
+
+
+def triple_pool(path, E, R, seed=3, randoms=30):
+    """Validation, test and made-up triples (one of them with h == t), int64 [n, 3]."""
+    rng = np.random.default_rng(seed)
+    made_up = np.stack([rng.integers(0, E, randoms), rng.integers(0, E, randoms), rng.integers(0, R, randoms)], axis=1)
+    made_up[0, 1] = made_up[0, 0]
+    return np.concatenate([split(path, "valid"), split(path, "test"), made_up])
+
+
+def with_repeats(pool, seed=3, repeats=25, among=None):
+    """Every row of the pool once plus `repeats` duplicates (of the rows `among`, all by default), shuffled: -> (triples
+    [n, 3], pick: each row's index in the pool)."""
+    rng = np.random.default_rng(seed + 1000)
+    among = np.arange(len(pool)) if among is None else np.asarray(among)
+    pick = np.concatenate([rng.permutation(len(pool)), among[rng.integers(0, len(among), repeats)]])
+    rng.shuffle(pick)
+    return pool[pick], pick
+
+
+def mixed_triples(path, E, R, seed=3, randoms=30, repeats=25):
+    return with_repeats(triple_pool(path, E, R, seed, randoms), seed, repeats)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# 1-6: one process, the raw entry point
+# ---------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("dim", DIMS)
+@pytest.mark.parametrize("test_head", [True, False])
+def test_test_split_counts_equal_link_prediction_range(dim, test_head):
+    require_entry_points()
+    con = make_config(dim)
+    E = con.entTotal
+    tt = np.stack(sorted_test_triples(KG), axis=1)
+    _, want, _ = lp_ranges(con, [(0, E)], test_head=test_head)
+    assert want[:, 0].any()
+    Q = BLOCK[dim]
+    for n in (0, 1, Q - 1, Q, Q + 1, len(tt)):           # around one workgroup's block, then a few blocks
+        got = rank_ranges(con, [(0, E)], tt[:n], test_head=test_head)
+        assert got.shape == (n, 2, 4) and np.array_equal(got, want[:n]), n
+        if not test_head:
+            assert not got[:, 1].any()
+    assert len(tt) > 2 * Q
+
+
+@pytest.mark.parametrize("dim", [48, 200])
+def test_any_cut_and_any_order_give_the_same_bits(dim):
+    require_entry_points()
+    con = make_config(dim)
+    E = con.entTotal
+    valid = split(KG, "valid")
+    mixed, pick = mixed_triples(KG, E, con.relTotal)
+    for triples in (valid, mixed):
+        ref = rank_ranges(con, cuts(E)[1], triples)
+        assert ref[:, :, 0].any()
+        for k, parts in cuts(E).items():
+            assert np.array_equal(rank_ranges(con, parts, triples), ref), k
+    # a duplicate gets the row of its first occurrence
+    first = {}
+    for i, p in enumerate(pick.tolist()):
+        assert np.array_equal(ref[i], ref[first.setdefault(p, i)])
+    assert len(first) < len(pick)
+    # a permutation of the input permutes the output rows
+    perm = np.random.default_rng(8).permutation(len(mixed))
+    assert np.array_equal(rank_ranges(con, cuts(E)[7], mixed[perm]), ref[perm])
+    tail = rank_ranges(con, cuts(E)[3], mixed, test_head=False)
+    assert np.array_equal(tail[:, 0], ref[:, 0]) and not tail[:, 1].any()
+
+
+def near_tie_slack(ent, rel, triples, path):
+    """For every (triple, side, column): the number of eligible candidates whose fp64 score lies within
+    64 * spacing(float32(true triple's score)) of the true triple's -- the counts that two correct fp32 rankers may disagree on.
+    Depends on the tables and fp64 arithmetic only."""
+    ent, rel = ent.astype(np.float64), rel.astype(np.float64)
+    norm = lambda x: x / np.sqrt(np.maximum((x * x).sum(-1, keepdims=True), 1e-12))
+    en, rn = norm(ent), norm(rel)
+    E = ent.shape[0]
+    known_tails, known_heads = {}, {}
+    for h, t, r in known_set(path):
+        known_tails.setdefault((h, r), []).append(t)
+        known_heads.setdefault((t, r), []).append(h)
+    heads, tails = type_lists(path, rel.shape[0])
+    ids = np.arange(E)
+    slack = np.zeros((len(triples), 2, 4), dtype=np.int64)
+    for i, (h, t, r) in enumerate(np.asarray(triples).tolist()):
+        for side in (0, 1):
+            if side == 0:
+                sc, target = np.abs(en[h] + rn[r] - en).sum(1), t
+                kn_ids, ty_ids = known_tails.get((h, r), []), list(tails[r])
+            else:
+                sc, target = np.abs(en + rn[r] - en[t]).sum(1), h
+                kn_ids, ty_ids = known_heads.get((t, r), []), list(heads[r])
+            kn, ty = np.zeros(E, dtype=bool), np.zeros(E, dtype=bool)
+            kn[kn_ids] = True
+            ty[ty_ids] = True
+            near = (ids != target) & (np.abs(sc - sc[target]) <= 64 * np.spacing(np.float32(sc[target])))
+            slack[i, side] = [near.sum(), (near & ~kn).sum(), (near & ty).sum(), (near & ty & ~kn).sum()]
+    return slack
+
+
+NEAR_TIE_CELLS = 0.02     # at most this share of the (triple, side, column) cells may have any slack
+
+
+def within_the_near_tie_cap(slack):
+    """The triple set is chosen, from the fp64 slack alone, so that the near-tie rule cannot hide a failure: every triple of the
+    pool without any slack, and triples with slack in pool order for as long as the cells with slack stay within NEAR_TIE_CELLS
+    of the chosen cells.  (TransE normalises every row, so the scale of the tables does not move the scores apart; at D = 200
+    and 512 about a tenth of the pool's cells have a candidate that close.)  -> the mask of the chosen rows."""
+    cells = (slack > 0).reshape(len(slack), -1).sum(1)
+    keep = cells == 0
+    n_keep, n_slack = int(keep.sum()), 0
+    for i in np.nonzero(cells)[0]:
+        if n_slack + cells[i] <= NEAR_TIE_CELLS * 8 * (n_keep + 1):
+            keep[i] = True
+            n_keep, n_slack = n_keep + 1, n_slack + int(cells[i])
+    return keep
+
+
+@pytest.mark.parametrize("dim", DIMS)
+def test_equals_rank_triples_up_to_near_ties(dim):
+    require_entry_points()
+    con = make_config(dim)
+    params = con.get_parameters()
+    pool = triple_pool(KG, con.entTotal, con.relTotal, randoms=60)
+    pool_slack = near_tie_slack(params["ent_embeddings"], params["rel_embeddings"], pool, KG)
+    keep = within_the_near_tie_cap(pool_slack)
+    assert keep.sum() >= 60, keep.sum()
+    kept_slack = pool_slack[keep]
+    triples, pick = with_repeats(pool[keep], among=np.nonzero(~kept_slack.any(axis=(1, 2)))[0])    # (repeats add no slack cells)
+    slack = kept_slack[pick]
+    share = float((slack > 0).mean())
+    print("dim %d: %d of %d pool triples, cells with slack %.4f" % (dim, keep.sum(), len(pool), share))
+    assert share <= NEAR_TIE_CELLS            # the rule cannot hide a failure: nearly every cell must agree exactly
+    want, _ = con.rank_triples(triples[:, 0], triples[:, 1], triples[:, 2])
+    got = rank_ranges(con, [(0, con.entTotal)], triples)
+    assert want[:, :, 0].any() and (want[:, :, 1] < want[:, :, 0]).any() and (want[:, :, 2] < want[:, :, 0]).any()
+    diff = np.abs(got - want)
+    print("dim %d: cells that differ %d of %d, largest difference %d" % (dim, int((diff > 0).sum()), diff.size, int(diff.max())))
+    assert (diff <= slack).all(), np.argwhere(diff > slack)[:5]
+
+
+def test_a_copy_of_the_target_row_in_another_range_ties_and_is_never_counted():
+    require_entry_points()
+    con = make_config(48)
+    E = con.entTotal
+    triples = split(KG, "valid")[:9]
+    i = 4
+    h, t = int(triples[i, 0]), int(triples[i, 1])
+    ent = con._tables[0]
+    for side, target in ((0, t), (1, h)):
+        # a stand-in in the other half of the table from the target, not an entity of triple i
+        x = next(j for j in (range(E - 1, 0, -1) if target < E // 2 else range(1, E)) if j not in (h, t))
+        base = {k: rank_ranges(con, parts, triples) for k, parts in cuts(E).items()}
+        alone = rank_ranges(con, [(x, x + 1)], triples)[i, side]      # what x itself adds with its own row
+        saved = ent[x].clone()
+        ent[x] = ent[target]           # the same bits as the target's row
+        con.tables_changed()
+        assert not rank_ranges(con, [(x, x + 1)], triples)[i, side].any(), side
+        for k, parts in cuts(E).items():
+            assert np.array_equal(rank_ranges(con, parts, triples)[i, side], base[k][i, side] - alone), (side, k)
+        ent[x] = saved
+        con.tables_changed()
+
+
+@pytest.fixture(scope="module")
+def typed_graph(tmp_path_factory):
+    from openkeonspark_amd import synthetic
+    return synthetic.make_typed_dataset(str(tmp_path_factory.mktemp("typed_rank") / "kg1003"), synthetic.SMALL_TYPED, entities=1003,
+                                        train=6000, valid=100, test=60)
+
+
+def test_filtered_and_typed_columns_on_the_typed_graph(typed_graph):
+    require_entry_points()
+    con = make_config(32, path=typed_graph)
+    E = con.entTotal
+    assert E == 1003
+    params = con.get_parameters()
+    triples = split(typed_graph, "valid")
+    slack = near_tie_slack(params["ent_embeddings"], params["rel_embeddings"], triples, typed_graph)
+    keep = within_the_near_tie_cap(slack)
+    assert keep.sum() >= 60
+    triples, slack = triples[keep], slack[keep]
+    whole = rank_ranges(con, [(0, E)], triples)
+    raw, filt, typed, both = (whole[:, :, c] for c in range(4))
+    assert filt.any() and typed.any() and both.any()
+    assert (filt < raw).any() and (typed < raw).any() and (both < typed).any()
+    assert (filt <= raw).all() and (typed <= raw).all() and (both <= typed).all() and (both <= filt).all()
+    assert np.array_equal(rank_ranges(con, [(lo, min(lo + 97, E)) for lo in range(0, E, 97)], triples), whole)
+    assert float((slack > 0).mean()) <= NEAR_TIE_CELLS
+    want, _ = con.rank_triples(triples[:, 0], triples[:, 1], triples[:, 2])
+    assert (np.abs(whole - want) <= slack).all()
+
+
+def test_refusals_launch_nothing_and_bad_ids_are_disabled(tmp_path):
+    import torch
+    from openkeonspark_amd import _lib
+    L = require_entry_points()
+    con = make_config(16)
+    E, R = con.entTotal, con.relTotal
+    triples = split(KG, "valid")[:11]
+    n = len(triples)
+    ids, query = device_triples(con, triples)
+    h, t, r = ids[0], ids[1], ids[2]
+    counts = torch.full((n, 2, 4), -9, dtype=torch.int64, device=con.device)
+    untouched = lambda: bool((counts == -9).all().item())
+    tp = con._tab_ptrs
+    call = lambda **kw: raw_call(con, L, kw.get("ptrs", tp), kw.get("lo", 0), kw.get("rows", E), kw.get("query", query),
+                                 kw.get("ids", (h, t, r)), kw.get("n", n), True, kw.get("counts", counts), kw.get("desc"))
+    assert call(desc=con._desc_with(model=1)) == KGE_ERR_UNSUPPORTED and untouched()          # TransH
+    assert call(desc=con._desc_with(ent_dim=1025)) == KGE_ERR_UNSUPPORTED and untouched()
+    assert call(desc=con._desc_with(ent_dim=0)) == KGE_ERR_UNSUPPORTED and untouched()
+    assert call(lo=1, rows=E) == KGE_ERR_BAD_ARG and untouched()
+    assert call(lo=-1, rows=2) == KGE_ERR_BAD_ARG and untouched()
+    assert call(rows=-1) == KGE_ERR_BAD_ARG and untouched()
+    assert call(n=-1) == KGE_ERR_BAD_ARG and untouched()
+    assert call(n=1 << 30) == KGE_ERR_BAD_ARG and untouched()
+    assert call(query=None) == KGE_ERR_BAD_ARG and untouched()
+    for bad in ((None, t, r), (h, None, r), (h, t, None)):
+        assert call(ids=bad) == KGE_ERR_BAD_ARG and untouched()
+    assert call(counts=None) == KGE_ERR_BAD_ARG
+    assert call(ptrs=_lib.table_ptrs([None, con._tables[1].data_ptr()])) == KGE_ERR_BAD_ARG and untouched()
+    assert call(n=0) == 0 and untouched()                         # n == 0: arguments and files only
+    L.kge_clear_error()
+    good = rank_ranges(con, [(0, E)], triples)
+    assert good[:, 0, 0].all() and good[:, 1, 0].all()           # (no triple of these ranks first: a zeroed row shows)
+    assert call(rows=0) == 0 and not counts.any().item()          # rows == 0: only zeroes
+    # one triple of several with an id out of range: KGE_OK, its counts zero, the others unchanged
+    for row, col, value in ((3, 0, E), (0, 1, -1), (n - 1, 2, R), (5, 2, -7), (6, 0, 2 ** 31 - 1)):
+        bad = triples.copy()
+        bad[row, col] = value
+        ids_b = torch.from_numpy(np.ascontiguousarray(bad.T.astype(np.int32))).to(con.device)
+        counts.fill_(-9)
+        assert call(ids=(ids_b[0], ids_b[1], ids_b[2])) == 0
+        got = counts.cpu().numpy()
+        assert not got[row].any(), (row, col)
+        keep = np.arange(n) != row
+        assert np.array_equal(got[keep], good[keep]), (row, col)
+    counts.fill_(-9)
+    assert call() == 0 and np.array_equal(counts.cpu().numpy(), good)          # a later call still works
+    # before importTestFiles (a failed import leaves the library without evaluation lists)
+    empty = tmp_path / "train_only"
+    os.makedirs(str(empty))
+    L.setInPath((str(empty) + "/").encode())
+    L.kge_clear_error()
+    L.importTestFiles()
+    L.kge_clear_error()
+    counts.fill_(-9)
+    assert call() == KGE_ERR_NO_DATASET and untouched()
+    assert call(n=0) == KGE_ERR_NO_DATASET and untouched()
+    L.kge_clear_error()
+    L.setInPath((KG + "/").encode())
+    con.init_link_prediction()
+    assert call() == 0 and np.array_equal(counts.cpu().numpy(), good)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# 7: ranks (gloo, one GPU), a sharded entity table
+# ---------------------------------------------------------------------------------------------------------------------------
+def spread_triples(data, E, R, world):
+    """Validation and test triples, triples whose ids sit at the first and last row of every rank's shard, duplicates: the same
+    list on every rank and in the parent."""
+    chunk = -(-E // world)
+    edge = [(min(g * chunk, E - 1), min((g + 1) * chunk - 1, E - 1), g % R) for g in range(world)]
+    edge += [(t, h, r) for h, t, r in edge]
+    mixed, _ = mixed_triples(data, E, R, seed=21, randoms=12, repeats=9)
+    return np.concatenate([np.asarray(edge, dtype=np.int64), mixed, np.asarray(edge[:2], dtype=np.int64)])
+
+
+def _rank_worker(rank, world, port, out_dir, data):
+    import openkeonspark_amd as pkg
+    con = start_rank(rank, world, port, data, timeout=PG_TIMEOUT)
+    va = split(data, "valid")
+    res, met = {}, {}
+    res["valid"], met["valid"] = con.rank_triples_distributed(va[:, 0], va[:, 1], va[:, 2])
+    sp = spread_triples(data, con.entTotal, con.relTotal, world)
+    res["spread"], met["spread"] = con.rank_triples_distributed(sp[:, 0], sp[:, 1], sp[:, 2])
+    res["none"], met["none"] = con.rank_triples_distributed([], [], [])
+    res["tail"], met["tail"] = con.rank_triples_distributed(va[:, 0], va[:, 1], va[:, 2], test_head=False)
+    saved = con.lp_shard_query_bytes
+    con.lp_shard_query_bytes = 5 * 2 * 48 * 4          # five triples per round
+    res["rounds"], met["rounds"] = con.rank_triples_distributed(va[:, 0], va[:, 1], va[:, 2])
+    con.lp_shard_query_bytes = saved
+    res["v_all"], met["v_all"] = con.validation_link_prediction_distributed()
+    res["v_7"], met["v_7"] = con.validation_link_prediction_distributed(sample=7)
+    res["v_7_tail"], met["v_7_tail"] = con.validation_link_prediction_distributed(test_head=False, sample=7)
+    # the last rank alone passes an id out of range: KgeError on every rank, and the next collective works
+    h = va[:, 0].copy()
+    if rank == world - 1:
+        h[3] = con.entTotal
+    raised = []
+    for call in (lambda: con.rank_triples_distributed(h, va[:, 1], va[:, 2]),
+                 lambda: con.rank_triples_distributed(va[:3 + (rank == 0), 0], va[:3 + (rank == 0), 1], va[:3 + (rank == 0), 2]),   # differing n
+                 lambda: con.rank_triples_distributed(va[:, 0], va[:, 1], va[:, 2], test_head=rank == 0),
+                 lambda: con.validation_link_prediction_distributed(sample=-1 if rank == world - 1 else 0)):
+        try:
+            call()
+            raised.append(0)
+        except pkg.KgeError:
+            raised.append(1)
+    res["after"], _ = con.rank_triples_distributed(va[:5, 0], va[:5, 1], va[:5, 2])
+    refused = []      # the one-process methods keep refusing, and say where to go
+    for call, name in ((lambda: con.rank_triples([0], [1], [0]), "rank_triples_distributed"),
+                       (lambda: con.validation_link_prediction(), "validation_link_prediction_distributed")):
+        try:
+            call()
+            refused.append(0)
+        except pkg.KgeError as e:
+            refused.append(1 if name in str(e) else -1)
+    finish_rank(con, out_dir, world, rank, raised=np.array(raised), refused=np.array(refused), metrics=json.dumps(met), **res)
+
+
+@pytest.fixture(scope="module")
+def sharded_runs(tmp_path_factory):
+    require_entry_points()
+    return run_worlds(_rank_worker, tmp_path_factory.mktemp("rank_shard_ranks"), 38100 + os.getpid() % 1000)
+
+
+@pytest.mark.parametrize("world", [2, 4])
+def test_ranks_equal_one_process_over_the_union_table(sharded_runs, world):
+    base, data = sharded_runs
+    zs = load_ranks(base, world)
+    con = union_config(data, zs[0])
+    E = con.entTotal
+    assert E == 1003 and E % world
+    va = split(data, "valid")
+    V = len(va)
+    sp = spread_triples(data, E, con.relTotal, world)
+    idx = (np.arange(7) * V) // 7
+    whole = [(0, E)]
+    want = {"valid": rank_ranges(con, whole, va), "spread": rank_ranges(con, whole, sp), "none": np.zeros((0, 2, 4), np.int64),
+            "tail": rank_ranges(con, whole, va, test_head=False), "v_7": rank_ranges(con, whole, va[idx]),
+            "v_7_tail": rank_ranges(con, whole, va[idx], test_head=False), "after": rank_ranges(con, whole, va[:5])}
+    want["rounds"] = want["v_all"] = want["valid"]
+    assert want["valid"][:, :, 0].any() and want["valid"][:, :, 3].any() and (want["valid"][:, :, 1] < want["valid"][:, :, 0]).any()
+    owners = np.minimum(sp[:, :2] // (-(-E // world)), world - 1)
+    assert set(owners.reshape(-1).tolist()) == set(range(world))          # ids owned by every rank
+    names = set(con.rank_triples(va[:, 0], va[:, 1], va[:, 2])[1])          # the one-process method's metric names
+    assert len(names) == 40
+    for g, z in enumerate(zs):
+        assert np.array_equal(z["ent"], zs[0]["ent"]) and np.array_equal(z["rel"], zs[0]["rel"])
+        met = json.loads(str(z["metrics"]))
+        for k, w in want.items():
+            assert z[k].dtype == np.int64 and z[k].shape == w.shape and np.array_equal(z[k], w), (g, k)
+            if k == "after":
+                continue
+            th = "tail" not in k
+            assert met[k] == pytest.approx(con._lp_normalise(con._lp_sums(w, th), w.shape[0]), rel=0, abs=0), (g, k)
+            assert set(met[k]) == (names if th else {x for x in names if x.startswith("r")}), (g, k)
+        assert z["raised"].tolist() == [1, 1, 1, 1], g
+        assert z["refused"].tolist() == [1, 1], g
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# 8: replicated tables
+# ---------------------------------------------------------------------------------------------------------------------------
+def _replicated_worker(rank, world, port, out_dir, model):
+    sys.path.insert(0, ROOT)
+    import torch.distributed as dist
+    os.environ["MASTER_ADDR"] = "127.0.0.1"
+    os.environ["MASTER_PORT"] = str(port)
+    dist.init_process_group("gloo", rank=rank, world_size=world, timeout=PG_TIMEOUT)
+    import openkeonspark_amd as pkg
+    con = pkg.Config()               # make_config's tables (the same seed, the same scale), with a work thread per rank
+    con.set_in_path(KG)
+    con.set_work_threads(2)
+    con.set_dimension(32)
+    con.set_test_link_prediction(True)
+    con.init()
+    con.set_model_and_session(getattr(pkg, model))
+    for t in con._tables:
+        t.mul_(3.0)
+    con.tables_changed()
+    con.init_distributed()
+    assert not con._sharded("ent_embeddings") and con.world_size == world
+    tr = np.concatenate([split(KG, "valid"), split(KG, "test")[:1], split(KG, "valid")[:4]])      # 35 triples: not a multiple of 2
+    res = {}
+    for name, part, th in (("odd", tr, True), ("one", tr[:1], True), ("none", tr[:0], True), ("tail", tr[:8], False)):
+        got, met = con.rank_triples_distributed(part[:, 0], part[:, 1], part[:, 2], test_head=th)
+        want, want_met = con.rank_triples(part[:, 0], part[:, 1], part[:, 2], test_head=th)      # this rank's own whole tables
+        res[name], res[name + "_local"] = got, want
+        assert met == want_met, name
+    res["v_7"], _ = con.validation_link_prediction_distributed(sample=7)
+    raised = 0
+    try:
+        con.rank_triples_distributed([con.entTotal if rank == world - 1 else 0], [1], [0])
+    except pkg.KgeError:
+        raised = 1
+    res["after"], _ = con.rank_triples_distributed(tr[:3, 0], tr[:3, 1], tr[:3, 2])
+    np.savez(os.path.join(out_dir, "%s_r%d.npz" % (model, rank)), raised=raised, **res)
+    dist.barrier()
+    dist.destroy_process_group()
+
+
+@pytest.mark.parametrize("model", ["TransE", "TransH"])
+def test_replicated_tables_equal_rank_triples(tmp_path, model):
+    require_entry_points()
+    import torch.multiprocessing as mp
+    port = 38600 + os.getpid() % 1000 + (model == "TransH")
+    mp.start_processes(_replicated_worker, args=(2, port, str(tmp_path), model), nprocs=2, join=True, start_method="spawn")
+    con = make_config(32, model=model)
+    tr = np.concatenate([split(KG, "valid"), split(KG, "test")[:1], split(KG, "valid")[:4]])
+    assert len(tr) % 2 == 1
+    V = len(split(KG, "valid"))
+    idx = (np.arange(7) * V) // 7
+    want = {"odd": con.rank_triples(tr[:, 0], tr[:, 1], tr[:, 2])[0], "one": con.rank_triples(tr[:1, 0], tr[:1, 1], tr[:1, 2])[0],
+            "none": np.zeros((0, 2, 4), np.int64), "tail": con.rank_triples(tr[:8, 0], tr[:8, 1], tr[:8, 2], test_head=False)[0],
+            "v_7": con.rank_triples(tr[idx, 0], tr[idx, 1], tr[idx, 2])[0], "after": con.rank_triples(tr[:3, 0], tr[:3, 1], tr[:3, 2])[0]}
+    assert want["odd"][:, :, 0].any()
+    for g in range(2):
+        z = np.load(os.path.join(str(tmp_path), "%s_r%d.npz" % (model, g)))
+        for k, w in want.items():
+            assert z[k].shape == w.shape and np.array_equal(z[k], w), (g, k)
+            if k + "_local" in z:
+                assert np.array_equal(z[k + "_local"], w), (g, k)
+        assert int(z["raised"]) == 1
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# 9: the driver
+# ---------------------------------------------------------------------------------------------------------------------------
+def _driver_worker(rank, world, port, out_dir, run, extra):
+    sys.path.insert(0, ROOT)
+    env = {"MASTER_ADDR": "127.0.0.1", "MASTER_PORT": str(port), "RANK": str(rank), "WORLD_SIZE": str(world),
+           "LOCAL_RANK": str(rank), "KGE_SINGLE_DEVICE": "1", "KGE_DIST_BACKEND": "gloo", "KGE_COUNTS_MIN_RECORDS": "0"}
+    os.environ.update(env)
+    import torch.distributed as dist
+    dist.init_process_group("gloo", rank=rank, world_size=world, timeout=PG_TIMEOUT)      # (the driver keeps a caller's group)
+    from openkeonspark_amd import _lib
+    from openkeonspark_amd import distribute_training as dt
+    from openkeonspark_amd.Config import Config
+    _lib.lib().kge_set_option(b"inv_table_max_bytes", 0)
+    calls, plain = [], []
+    real, real_plain = Config.validation_link_prediction_distributed, Config.validation_link_prediction
+
+    def spy(self, test_head=True, sample=0):
+        counts, metrics = real(self, test_head=test_head, sample=sample)
+        calls.append(dict(test_head=bool(test_head), sample=int(sample), rows=int(counts.shape[0]), step=int(self.global_step),
+                          counts=counts.tolist(), metrics=metrics))
+        return counts, metrics
+
+    def spy_plain(self, *a, **kw):
+        plain.append(1)
+        return real_plain(self, *a, **kw)
+    Config.validation_link_prediction_distributed = spy
+    Config.validation_link_prediction = spy_plain
+    args = ["--input_path", KG, "--output_path", os.path.join(out_dir, run), "--embedding_dimension", "32",
+            "--n_mini_batches", "5", "--ent_neg_rate", "3", "--alpha", "0.05", "--optimizer", "SGD", "--bern_flag", "1",
+            "--train_times", "4", "--sparse_rows", "1", "--early_stop_rank_triples", "5", "--debug", "1"] + list(extra)
+    con = dt.main_fun(dt.parse_args(args))
+    with open(os.path.join(out_dir, "%s_calls_r%d.json" % (run, rank)), "w") as f:
+        json.dump(dict(calls=calls, plain=len(plain), sharded=bool(con._sharded("ent_embeddings")), nbatches=int(con.nbatches),
+                       step=int(con.global_step)), f)
+    dist.barrier()
+    dist.destroy_process_group()
+
+
+@pytest.mark.parametrize("metric,test_head", [("mrr", 0), ("hits10", 1)])
+def test_driver_early_stop_metric_on_a_sharded_table(tmp_path, metric, test_head):
+    require_entry_points()
+    import torch.multiprocessing as mp
+    port = 38900 + os.getpid() % 1000 + test_head
+    extra = ["--early_stop_metric", metric] + (["--test_head", "1"] if test_head else [])
+    mp.start_processes(_driver_worker, args=(2, port, str(tmp_path), metric, extra), nprocs=2, join=True, start_method="spawn")
+    assert any(".shard" in f for f in os.listdir(str(tmp_path / metric)))
+    logs = [json.load(open(str(tmp_path / ("%s_calls_r%d.json" % (metric, g))))) for g in range(2)]
+    for z in logs:
+        assert z["sharded"] and z["plain"] == 0 and z["nbatches"] == 5 and z["step"] == 20
+        # a check after every epoch but the last (start step 1, stopping step 1; patience 5 cannot run out in 3 checks)
+        assert [c["step"] for c in z["calls"]] == [5, 10, 15]
+        assert all(c["test_head"] == bool(test_head) and c["sample"] == 5 and c["rows"] == 5 for c in z["calls"])
+    assert logs[0]["calls"] == logs[1]["calls"]           # the same counts and metric values on both ranks, check by check
+    name = "_filter_reci_rank" if metric == "mrr" else "_filter_tot"
+    values = [sum(c["metrics"][p + name] for p in ("rl" if test_head else "r")) for c in logs[0]["calls"]]
+    assert all(0.0 <= v <= 2.0 for v in values)
+    assert any(np.asarray(c["counts"])[:, 0, 0].any() for c in logs[0]["calls"])
