@@ -116,6 +116,9 @@ const char *kge_version(void);
  *   "ride_shares":       where an armed sampler (kge_sampling_attach) rides: percent of its workgroups for the bucket histogram /
  *                        bucket scatter / bucket sort / the launch that ends the step, one byte each (default 100 << 8: all of it in
  *                        the scatter launch; parts that no launch took are launched by kge_sampling_flush)
+ *   "sampler_magic_len": T (default 2048): filter groups of fewer than T known ids take the modulus of their filtered pick from the
+ *                        tables "ent_magic" / "rel_magic" (kge_index_copy), longer ones from two fp64 divisions.  Same draws; the
+ *                        tables of an imported training set are rebuilt at once (tests lower it so that both ways run)
  *   "counts_fused_diag": measurement hook of the fused kernel (1: no record loops, 2: no row update);
  *                        any value but 0 gives WRONG results
  *   "counts_fused_cap":  test hook: rows of more than this many records take the image path (0 = the kernel's capacity)
@@ -211,6 +214,10 @@ int kge_import_train_arrays(INT ent_total, INT rel_total, INT n, const INT *h, c
  *   "typed_pos_hr" / "typed_pos_tr"  int32[trainTotal]  at a group's offset in tails_hr / heads_tr: the increasing positions
  *               inside the relation's list of the group's known ids that occur in it, then -1 up to the group's length
  *   "typed_len"  int32[trainTotal_][2]  per file-order triple: how many positions its (h,r) group and its (t,r) group have
+ * and the device sampler's tables,
+ *   "jump_digits"  uint64[4 * 512][2]  entry [k * 512 + d]: (mul, add) of x -> mul * x + add after d * 512^k steps of the 64-bit LCG
+ *   "ent_magic" / "rel_magic"  uint64[sampler_magic_len]  entry len: (2^64 - 1) / (entityTotal - len) resp. (relationTotal - len),
+ *               0 where that divisor is not positive
  * Returns the number of BYTES the array holds (copying at most `bytes` of them), <0 on error. */
 int64_t kge_index_copy(const char *what, void *dst, int64_t bytes);
 

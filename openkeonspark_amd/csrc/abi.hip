@@ -65,6 +65,13 @@ int ensure_device_index() {
         if ((rc = upload(e.dev.bern_prob, ix.bern_prob.data(), ix.bern_prob.size(), "upload bern"))) return rc;
         e.dev.uploaded = true;
     }
+    if (!e.dev.tables_uploaded) {
+        const KgIndex &ix = e.index;
+        if ((rc = upload(e.dev.jump_digits, e.jump_digits.data(), e.jump_digits.size(), "upload jump digits"))) return rc;
+        if ((rc = upload(e.dev.ent_magic, ix.ent_magic.data(), ix.ent_magic.size(), "upload entity moduli"))) return rc;
+        if ((rc = upload(e.dev.rel_magic, ix.rel_magic.data(), ix.rel_magic.size(), "upload relation moduli"))) return rc;
+        e.dev.tables_uploaded = true;
+    }
     if ((int64_t)e.streams.size() != e.work_threads) {
         // setWorkThreads without randReset: the reference would read unallocated memory; give zeros
         e.streams.assign((size_t)e.work_threads, 0);
@@ -146,12 +153,14 @@ static std::string build_and_adopt(int64_t E, int64_t R, int64_t nb, int64_t n, 
         std::string err = build_index_device(ix, e.dev, E, R, nb, n, h, t, r);
         if (!err.empty()) { e.dev.uploaded = false; return err; }
         e.index = std::move(ix);   // e.dev already holds the arrays (uploaded = true)
-        return "";
+    } else {
+        KgIndex ix;
+        std::string err = build_index(ix, E, R, nb, n, h, t, r);
+        if (!err.empty()) return err;
+        adopt_index(std::move(ix));
     }
-    KgIndex ix;
-    std::string err = build_index(ix, E, R, nb, n, h, t, r);
-    if (!err.empty()) return err;
-    adopt_index(std::move(ix));
+    build_magic_tables(e.index, e.sampler_magic_len);
+    e.dev.tables_uploaded = false;
     return "";
 }
 
@@ -254,6 +263,14 @@ const char *kge_version(void) { return "kge_mi355 0.1 (gfx950)"; }
 int kge_set_option(const char *name, INT value) {
     std::string n = name ? name : "";
     if (n == "counts_force_sort") { engine().counts_force_sort = value != 0; return KGE_OK; }
+    if (n == "sampler_magic_len") {   // an armed sampler points into the tables that are about to be replaced: run it first
+        Engine &e = engine();
+        if (device_ok()) { (void)flush_attached_sampler(nullptr); (void)hipDeviceSynchronize(); }
+        e.sampler_magic_len = value > 0 ? value : 0;
+        if (e.index.loaded) build_magic_tables(e.index, e.sampler_magic_len);
+        e.dev.tables_uploaded = false;
+        return KGE_OK;
+    }
     if (n == "ride_shares") { engine().ride_shares = (int)value; return KGE_OK; }
     if (n == "transr_bf16x3") { engine().transr_bf16x3 = value != 0; return KGE_OK; }
     if (n == "transr_groups") { engine().transr_groups = (int)value; return KGE_OK; }
@@ -351,8 +368,9 @@ int64_t kge_index_copy(const char *what, void *dst, int64_t bytes) {
     KGE_ARR("left_mean", ix.left_mean) KGE_ARR("right_mean", ix.right_mean) KGE_ARR("bern_prob", ix.bern_prob)
     KGE_ARR("type_tails", ix.type_tails) KGE_ARR("type_heads", ix.type_heads) KGE_ARR("type_bounds", ix.type_bounds)
     KGE_ARR("typed_pos_hr", ix.typed_pos_hr) KGE_ARR("typed_pos_tr", ix.typed_pos_tr) KGE_ARR("typed_len", ix.typed_len)
+    KGE_ARR("jump_digits", engine().jump_digits) KGE_ARR("ent_magic", ix.ent_magic) KGE_ARR("rel_magic", ix.rel_magic)
 #undef KGE_ARR
-    if (!src && have == 0 && !typed && w != "tails_hr" && w != "heads_tr" && w != "rels_ht" && w != "pos" && w != "grp" && w != "ht" &&
+    if (!src && have == 0 && !typed && w != "jump_digits" && w != "ent_magic" && w != "rel_magic" && w != "tails_hr" && w != "heads_tr" && w != "rels_ht" && w != "pos" && w != "grp" && w != "ht" &&
         w != "left_mean" && w != "right_mean" && w != "bern_prob")
         return fail(KGE_ERR_BAD_ARG, "kge_index_copy: unknown array " + w);
     if (dst && bytes > 0 && have > 0) std::memcpy(dst, src, (size_t)(bytes < have ? bytes : have));

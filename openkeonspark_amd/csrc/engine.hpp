@@ -24,6 +24,10 @@ struct DeviceIndex {
     int2 *ht = nullptr;       // [train_dup]
     int32_t *tails_hr = nullptr, *heads_tr = nullptr, *rels_ht = nullptr;  // [train_uniq]
     float *bern_prob = nullptr;                                            // [rel_total]
+    // the sampler's tables (ensure_device_index): Engine::jump_digits, KgIndex::ent_magic / rel_magic
+    bool tables_uploaded = false;
+    LcgAffine *jump_digits = nullptr;
+    uint64_t *ent_magic = nullptr, *rel_magic = nullptr;   // [sampler_magic_len] each
     uint64_t *streams = nullptr;                                           // [work_threads]: the CURRENT states
     uint64_t *streams_next = nullptr;   // the other half of the same allocation: the sampler writes the advanced states there, then the two swap
     int64_t streams_cap = 0;
@@ -51,6 +55,8 @@ struct Engine {
     LibcRand libc;
     std::vector<uint64_t> streams;  // host view of next_random[] (Random.h:6)
     LcgJumpTable jump = make_jump_table();
+    std::vector<LcgAffine> jump_digits = make_jump_digit_table(jump);
+    int64_t sampler_magic_len = 2048;   // group lengths below this take their filtered-pick modulus from KgIndex::ent_magic / rel_magic (option sampler_magic_len; tests lower it)
     DeviceIndex dev;
     std::string last_error;
     int device_state = 0;  // 0 unknown, 1 ok, -1 none

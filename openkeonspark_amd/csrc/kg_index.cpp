@@ -295,4 +295,27 @@ uint64_t lcg_jump(const LcgJumpTable &tab, uint64_t state, uint64_t steps) {
     return state;
 }
 
+std::vector<LcgAffine> make_jump_digit_table(const LcgJumpTable &tab) {
+    const int n = 1 << kJumpDigitBits;
+    std::vector<LcgAffine> dig((size_t)kJumpDigitLevels * n);
+    for (int k = 0; k < kJumpDigitLevels; k++) {
+        const uint64_t a = tab.mulA[k * kJumpDigitBits], c = tab.addC[k * kJumpDigitBits];   // one digit step of this level
+        LcgAffine cur = {1, 0};
+        for (int d = 0; d < n; d++) {
+            dig[(size_t)k * n + d] = cur;
+            cur = {a * cur.mul, a * cur.add + c};   // one more digit step after the d so far
+        }
+    }
+    return dig;
+}
+
+void build_magic_tables(KgIndex &ix, int64_t T) {
+    auto fill = [T](std::vector<uint64_t> &m, int64_t total) {
+        m.assign((size_t)(T < 0 ? 0 : T), 0);
+        for (int64_t len = 0; len < T && len < total; len++) m[(size_t)len] = ~0ull / (uint64_t)(total - len);
+    };
+    fill(ix.ent_magic, ix.ent_total);
+    fill(ix.rel_magic, ix.rel_total);
+}
+
 }  // namespace kge

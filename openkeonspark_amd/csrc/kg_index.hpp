@@ -28,6 +28,9 @@ struct KgIndex {
     std::vector<int32_t> heads_tr;  // [train_uniq] == trainTail[].h
     std::vector<int32_t> rels_ht;   // [train_uniq] == trainRel[].r
     std::vector<float> left_mean, right_mean, bern_prob;  // [rel_total]
+    // moduli of the filtered pick by multiply-high (build_magic_tables): [T] entries each,
+    // ent_magic[len] = floor((2^64-1) / (ent_total - len)), rel_magic the same for rel_total; 0 where the divisor is 0 (never used)
+    std::vector<uint64_t> ent_magic, rel_magic;
     bool loaded = false;
     // Type-constrained negative sampling (build_typed_index; empty until typed sampling is switched on).  L_tail(r) / L_head(r):
     // relation r's tail / head type list, sorted, duplicates removed.
@@ -80,6 +83,13 @@ constexpr uint64_t kLcgAdd = 11ULL;
 struct LcgJumpTable { uint64_t mulA[64]; uint64_t addC[64]; };
 LcgJumpTable make_jump_table();
 uint64_t lcg_jump(const LcgJumpTable &tab, uint64_t state, uint64_t steps);
+// The same jumps by 9-bit digits: entry [k * 512 + d] is the map x -> mul * x + add of d * 512^k steps (d = 0: the identity),
+// four levels, so any count below 2^36 is at most four multiply-adds whose table entries can all be requested at once.
+constexpr int kJumpDigitBits = 9, kJumpDigitLevels = 4;
+struct LcgAffine { uint64_t mul, add; };
+std::vector<LcgAffine> make_jump_digit_table(const LcgJumpTable &tab);
+// KgIndex::ent_magic / rel_magic for group lengths below T
+void build_magic_tables(KgIndex &ix, int64_t T);
 
 // Base.cpp:85-92: half-open slice [lef,rig) of batch positions owned by virtual thread `id`.
 inline void thread_slice(int64_t batch, int64_t threads, int64_t id, int64_t &lef, int64_t &rig) {

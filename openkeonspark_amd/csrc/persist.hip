@@ -423,6 +423,7 @@ extern "C" int kge_train_steps_persistent(const kge_model_desc *m, float *const 
     s.neg = (int)negRate; s.negrel = (int)negRelRate; s.bern = e.bern ? 1 : 0;
     s.pick_div = (unsigned long long)(s.new_batch > 0 ? s.new_batch : s.train_dup);
     s.pick_magic = ~0ull / s.pick_div;
+    set_sampler_tables(s);
     int kshift = 0;
     while ((1 << kshift) < 1 + negRate + negRelRate) kshift++;
     s.kshift = kshift;

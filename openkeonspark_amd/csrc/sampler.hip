@@ -87,6 +87,7 @@ static int build_sampler(int32_t *d_h, int32_t *d_t, int32_t *d_r, int32_t *d_pa
     a.neg = (int)neg; a.negrel = (int)negrel; a.bern = e.bern ? 1 : 0;
     a.pick_div = (unsigned long long)(a.new_batch > 0 ? a.new_batch : a.train_dup);
     a.pick_magic = ~0ull / a.pick_div;
+    set_sampler_tables(a);
     const int kshift = sampler_kshift(neg, negrel);
     a.kshift = kshift;
     a.pack = emit_pack_shape(a.ent_total, a.rel_total, neg, negrel) ? d_pack : nullptr;   // [n_local << kshift] words

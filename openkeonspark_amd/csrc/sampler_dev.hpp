@@ -43,7 +43,19 @@ struct SamplerArgs {
     // a PART of the sampler's grid riding in another kernel's launch (take_attached_sampler): the rider's extra workgroup i runs
     // workgroup ride_first + i of ride_total
     unsigned ride_first, ride_total;
+    // tables of the device index (DeviceIndex): the LCG's jumps by 9-bit digits (kg_index.hpp make_jump_digit_table) and the
+    // multiply-high constants of the filtered pick's modulus for group lengths below magic_len (KgIndex::ent_magic / rel_magic)
+    const LcgAffine *jump_digits;
+    const uint64_t *ent_magic, *rel_magic;
+    int magic_len;
 };
+
+// where build_sampler / the persistent launch take them from
+static inline void set_sampler_tables(SamplerArgs &a) {
+    const Engine &e = engine();
+    a.jump_digits = e.dev.jump_digits; a.ent_magic = e.dev.ent_magic; a.rel_magic = e.dev.rel_magic;
+    a.magic_len = (int)e.sampler_magic_len;
+}
 
 // Type-constrained sampling: what the TYPED instantiations read on top of that -- the arrays of KgIndex's typed part.  A type of
 // its own, so that SamplerArgs, a by-value argument of every kernel a sampler rides in, stays as it is: those kernels are
@@ -62,6 +74,35 @@ __device__ __forceinline__ uint64_t lcg_skip(uint64_t s, uint64_t n) {
     for (int j = 0; n != 0; ++j, n >>= 1)
         if (n & 1) s = c_jump.mulA[j] * s + c_jump.addC[j];
     return s;
+}
+
+// The same jump from the digit tables: a 16-byte entry and a multiply-add per digit instead of a data-dependent loop over the
+// bits, and every entry is requested before the first multiply.  The tables never change while a kernel runs and are read
+// through the constant address space, so a wave-uniform n (sample_block) takes scalar loads and a per-lane n (sample_slot) vector
+// loads.  Counts beyond the tables (2^36) keep the bit loop.
+typedef unsigned long long u64x2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ u64x2 jump_digit(const LcgAffine *dig, int level, unsigned d) {
+    return ((const __attribute__((address_space(4))) u64x2 *)dig)[(level << kJumpDigitBits) + (int)(d & ((1u << kJumpDigitBits) - 1u))];
+}
+// (requested and applied in two steps, so that a caller can put other requests between them)
+struct LcgJump { u64x2 e0, e1, e2, e3; };
+__device__ __forceinline__ LcgJump lcg_jump_request(const LcgAffine *dig, uint64_t n) {
+    LcgJump j;
+    j.e0 = jump_digit(dig, 0, (unsigned)n); j.e1 = jump_digit(dig, 1, (unsigned)(n >> kJumpDigitBits));
+    j.e2 = j.e3 = u64x2{1ull, 0ull};
+    if (n >> (2 * kJumpDigitBits)) {
+        j.e2 = jump_digit(dig, 2, (unsigned)(n >> (2 * kJumpDigitBits))); j.e3 = jump_digit(dig, 3, (unsigned)(n >> (3 * kJumpDigitBits)));
+    }
+    return j;
+}
+__device__ __forceinline__ uint64_t lcg_jump_apply(const LcgJump &j, uint64_t s, uint64_t n) {
+    if (n >> (kJumpDigitBits * kJumpDigitLevels)) return lcg_skip(s, n);
+    s = j.e1.x * (j.e0.x * s + j.e0.y) + j.e1.y;
+    if (n >> (2 * kJumpDigitBits)) s = j.e3.x * (j.e2.x * s + j.e2.y) + j.e3.y;
+    return s;
+}
+__device__ __forceinline__ uint64_t lcg_skip_tab(const LcgAffine *dig, uint64_t s, uint64_t n) {
+    return lcg_jump_apply(lcg_jump_request(dig, n), s, n);
 }
 
 // s % d for a 64-bit LCG state, exact, without the 64-bit division sequence (~100 instructions each, three per thread):
@@ -103,19 +144,50 @@ __device__ __forceinline__ int filtered_pick(const int32_t *__restrict__ vals, i
     return (int)(tmp + lo);
 }
 
-// The same pick with ONE memory round trip for groups of up to four known ids (most (h, r) / (t, r) groups of a sparse KG):
-// the four candidates are requested together (clamped, unconditional) and the monotone predicate is counted; longer lists
-// fall through to the binary search.
-__device__ __forceinline__ int filtered_pick_short(const int32_t *__restrict__ vals, int len, long long tmp) {
-    if (len > 4) return filtered_pick(vals, len, tmp);
-    if (len <= 0) return (int)tmp;
-    int v[4];
+// The draw of one corruption (Corrupt.h:25-36): tmp = s mod (total - len), then the same pick by an (M + 1)-ary search -- a level
+// requests its M pivots together (clamped, unconditional), counts the true ones of the monotone predicate and keeps the one
+// part of the range the answer can still lie in, so a list of up to M ids takes one memory round trip, up to (M + 1)^2 - 1 two,
+// where the bisection takes one per bit.  The first level's pivots do not depend on tmp: they are requested together with
+// the modulus' constant magic[len] (len < magic_len; longer groups keep mod_u64_u32).  total - len = 0 gives tmp = 0 as there.
+constexpr int kPickFan =
+#ifdef KGE_PICK_FAN
+    KGE_PICK_FAN;
+#else
+    4;
+#endif
+template <int M>
+__device__ __forceinline__ int filtered_pick_wide(const int32_t *__restrict__ vals, int len, int total, const uint64_t *__restrict__ magic,
+                                                  int magic_len, uint64_t s) {
+    int lo = 0, hi = len, v[M];
+    int step = (len + M) / (M + 1);
+    const int last = len > 0 ? len - 1 : 0;   // (a group has at least one slot, so slot 0 can always be read)
 #pragma unroll
-    for (int j = 0; j < 4; j++) v[j] = vals[j < len ? j : len - 1];
-    int lo = 0;
+    for (int j = 0; j < M; j++) v[j] = vals[min((j + 1) * step - 1 < 0 ? 0 : (j + 1) * step - 1, last)];
+    const uint32_t d = (uint32_t)(total - len);
+    int tmp;
+    if (len < magic_len) {
+        const uint64_t m = magic[len];
+        uint64_t r = s - __umul64hi(s, m) * d;   // < 3 d
+        if (r >= d) r -= d;
+        if (r >= d) r -= d;
+        tmp = d == 0 ? 0 : (int)r;
+    } else
+        tmp = (int)mod_u64_u32(s, d);
+    while (lo < hi) {
+        int t = 0;
 #pragma unroll
-    for (int j = 0; j < 4; j++) lo += (j < len && (long long)v[j] - j <= tmp) ? 1 : 0;
-    return (int)(tmp + lo);
+        for (int j = 0; j < M; j++) {
+            const int p = lo + (j + 1) * step - 1;
+            t += (p < hi && v[j] - p <= tmp) ? 1 : 0;   // (ids and positions are below 2^31 and v[j] >= p)
+        }
+        lo += t * step;                               // pivots below lo are true,
+        if (t < M) hi = min(hi, lo + step - 1);       // the first false one bounds the count from above
+        if (lo >= hi) break;
+        step = (hi - lo + M) / (M + 1);
+#pragma unroll
+        for (int j = 0; j < M; j++) v[j] = vals[min(lo + (j + 1) * step - 1, hi - 1)];
+    }
+    return tmp + lo;
 }
 
 // Type-constrained corruption: the replacement comes from the relation's own tail (new_tail) or head type list L, minus the known
@@ -151,18 +223,6 @@ __device__ __forceinline__ int typed_pick(const TypedSamplerArgs &a, uint64_t s,
     return (new_tail ? a.type_tails : a.type_heads)[loff + pos];
 }
 
-// s advanced by n < 2^16 steps, n different in every lane: a masked multiply-add per bit with the first jump entries read
-// through compile-time offsets (scalar loads the compiler batches), as many rounds as the widest n of the wave needs
-__device__ __forceinline__ uint64_t lcg_skip_lanes(uint64_t s, unsigned n) {
-#pragma unroll
-    for (int j = 0; j < 16; j++) {
-        if (!__any((n >> j) != 0u)) break;
-        const uint64_t t = c_jump.mulA[j] * s + c_jump.addC[j];
-        s = ((n >> j) & 1u) ? t : s;
-    }
-    return s;
-}
-
 // One scored triple of the batch: slot k of the positive at global batch position p (k = 0 the positive, 1..neg entity
 // negatives, then relation negatives), drawn exactly as virtual thread `id` of the reference draws it (Base.cpp:95-140).
 // `skip_batches` whole batches of this thread's slice are skipped first (a persistent launch samples step s from the
@@ -173,7 +233,7 @@ __device__ __forceinline__ void sample_slot(const typename SamplerArgsOf<TYPED>:
     const long long id = (long long)((unsigned)p / (unsigned)a.per_thread);   // owning virtual thread (Base.cpp:85-92); B < 2^31
     const long long off = p - id * a.per_thread;  // index inside its slice
     const unsigned long long draws = 1ull + 2ull * a.neg + a.negrel;
-    uint64_t s = lcg_skip(a.streams[id], skip_draws + (unsigned long long)off * draws);
+    uint64_t s = lcg_skip_tab(a.jump_digits, a.streams[id], skip_draws + (unsigned long long)off * draws);
     s = lcg_step(s);  // Base.cpp:101-106: which training triple
     long long i = (long long)mod_magic(s, a.pick_div, a.pick_magic) + (a.new_batch > 0 ? a.train_dup - a.new_batch : 0);
     const int4 tr = a.pos[i];  // (h, t, r, -)
@@ -182,7 +242,7 @@ __device__ __forceinline__ void sample_slot(const typename SamplerArgsOf<TYPED>:
     if constexpr (TYPED) tl = a.typed_len[i];
     oh = tr.x; ot = tr.y; orr = tr.z;
     if (k >= 1 && k <= a.neg) {
-        s = lcg_skip(s, 2ull * (unsigned long long)(k - 1));
+        s = lcg_skip_tab(a.jump_digits, s, 2ull * (unsigned long long)(k - 1));
         s = lcg_step(s);  // Base.cpp:118: head-or-tail coin, compared in float
         const float prob = a.bern ? a.bern_prob[orr] : 500.0f;
         const bool keep_head = (float)(s % 1000ull) < prob;
@@ -202,7 +262,7 @@ __device__ __forceinline__ void sample_slot(const typename SamplerArgsOf<TYPED>:
             oh = min(filtered_pick(a.heads_tr + gq.z, gq.w, tmp), a.ent_total - 1);
         }
     } else if (k > a.neg) {  // Base.cpp:133-139: corrupt_rel(h, t)
-        s = lcg_skip(s, 2ull * a.neg + (unsigned long long)(k - 1 - a.neg));
+        s = lcg_skip_tab(a.jump_digits, s, 2ull * a.neg + (unsigned long long)(k - 1 - a.neg));
         s = lcg_step(s);
         const int2 g = a.ht[i];
         long long tmp = (long long)mod_u64_u32(s, (uint32_t)(a.rel_total - g.y));
@@ -242,9 +302,9 @@ constexpr int kBernLds = 2048;
 // Up to 64 slots per positive (the usual case).  The 1+neg+negrel draws of one positive sit in ADJACENT lanes (k = 0 the
 // positive, 1..neg entity negatives, then relation negatives; padded to a power of two <= 64): they read the same pos / grp
 // record and search the same groups, so those loads coalesce.  What the slots of a WAVE share is computed once:
-//   * the long jump (up to 64 table steps: slice offset x draws per positive) is done for the wave's FIRST positive only, on
+//   * the long jump (lcg_skip_tab: slice offset x draws per positive) is done for the wave's FIRST positive only, on
 //     wave-uniform values (scalar unit); a lane then advances by the few draws between that state and its own slot -- at
-//     most 64 positives' worth, a masked multiply-add per bit (lcg_skip_lanes) -- instead of repeating the long jump;
+//     most 64 positives' worth, two digits of the jump tables -- instead of repeating the long jump;
 //   * the training-triple pick of a positive (one 64-bit modulo) is made by its k = 0 lane and handed to the others;
 //   * the Bernoulli table sits in LDS (one dependent global load less per negative).
 // Same draws in the same order as Base.cpp:95-140, so the batch is bit-identical to sample_slot's.
@@ -256,64 +316,103 @@ __device__ __forceinline__ void sample_block(const typename SamplerArgsOf<TYPED>
     const int kshift = a.kshift, kp = 1 + a.neg + a.negrel, kmask = (1 << kshift) - 1;
     const unsigned long long draws = 1ull + 2ull * a.neg + a.negrel;
     write_next_streams(a, kp, block, n_blocks);
+    const int lane = threadIdx.x & 63;
+    const long long total = a.n_local << kshift;
+    const long long wave0 = block * 256 + (__builtin_amdgcn_readfirstlane(threadIdx.x) & ~63);
+    // What 64 slots starting at g0 need before anything that depends on memory: the state of the wave's first positive's virtual
+    // thread and the digits of its long jump (wave-uniform: scalar loads), and per lane the two digits of its short jump, all
+    // requested side by side.
+    struct Slots {
+        unsigned long long n0;      // draws between the stream's state and the wave's first positive
+        uint64_t st0, st;           // that stream's state; the lane's own stream's where it is another one
+        LcgJump jump0;
+        u64x2 j0, j1;
+        long long b;
+        int k, kk;
+        bool live, same;
+    };
+    auto request = [&](long long g0) {
+        Slots w;
+        // ---- wave-uniform: state in front of the first draw of the wave's first positive ----
+        const long long p0 = a.pos_lo + (g0 >> kshift);
+        const long long id0 = (long long)((unsigned)p0 / (unsigned)a.per_thread);   // owning virtual thread (Base.cpp:85-92); B < 2^31
+        const long long off0 = p0 - id0 * a.per_thread;
+        w.n0 = (unsigned long long)off0 * draws;
+        w.jump0 = lcg_jump_request(a.jump_digits, w.n0);
+        // (a launch reads the current half of the stream states and writes the other one: constant while it runs, so this is a
+        // scalar load like the digits' and not a vector load whose wait would stand in front of the requests below)
+        w.st0 = ((const __attribute__((address_space(4))) uint64_t *)a.streams)[id0];
+        // ---- per lane ----
+        const long long g = g0 + lane;
+        w.b = g >> kshift;
+        w.k = (int)(g & kmask);
+        w.live = w.b < a.n_local && w.k < kp;
+        if (w.b >= a.n_local) w.b = a.n_local - 1;
+        w.kk = w.k < kp ? w.k : kp - 1;
+        const long long p = a.pos_lo + w.b;
+        const long long id = (long long)((unsigned)p / (unsigned)a.per_thread);
+        const long long off = p - id * a.per_thread;
+        w.same = id == id0;                  // (a wave may cross into the next virtual thread's slice)
+        unsigned ahead = (unsigned)((w.same ? off - off0 : off) * (long long)draws);   // < 64 positives' draws
+        // draw 0 of a positive picks the training triple; entity negative k uses draws 1 + 2(k-1) (coin) and the next one
+        // (corruption); relation negative k uses draw 1 + 2 neg + (k - 1 - neg)   (Base.cpp:101-139)
+        if (w.kk >= 1) ahead += w.kk <= a.neg ? 1u + 2u * (unsigned)(w.kk - 1) : 1u + 2u * (unsigned)a.neg + (unsigned)(w.kk - 1 - a.neg);
+        // ahead < 2^18 (65 positives of at most 127 draws): two digits
+        w.j0 = jump_digit(a.jump_digits, 0, ahead); w.j1 = jump_digit(a.jump_digits, 1, ahead >> kJumpDigitBits);
+        w.st = 0;
+        if (!w.same) w.st = a.streams[id];
+        return w;
+    };
+    // the first 64 slots' requests go out before the Bernoulli table's, so the two waits are one
+    Slots w = request(wave0 < total ? wave0 : 0);
     const bool bern_in_lds = a.bern && a.rel_total <= kBernLds;
     if (bern_in_lds) {
         for (int i = threadIdx.x; i < a.rel_total; i += 256) bern_lds[i] = a.bern_prob[i];
         __syncthreads();
     }
-    const int lane = threadIdx.x & 63;
-    const long long total = a.n_local << kshift;
-    const long long wave0 = block * 256 + (__builtin_amdgcn_readfirstlane(threadIdx.x) & ~63);
     for (long long g0 = wave0; g0 < total; g0 += n_blocks * 256) {
-        // ---- wave-uniform: state in front of the first draw of the wave's first positive ----
-        const long long p0 = a.pos_lo + (g0 >> kshift);
-        const long long id0 = (long long)((unsigned)p0 / (unsigned)a.per_thread);   // owning virtual thread (Base.cpp:85-92); B < 2^31
-        const long long off0 = p0 - id0 * a.per_thread;
-        const uint64_t base0 = lcg_skip(a.streams[id0], (unsigned long long)off0 * draws);
-        // ---- per lane ----
-        const long long g = g0 + lane;
-        long long b = g >> kshift;
-        const int k = (int)(g & kmask);
-        const bool live = b < a.n_local && k < kp;
-        if (b >= a.n_local) b = a.n_local - 1;
-        const int kk = k < kp ? k : kp - 1;
-        const long long p = a.pos_lo + b;
-        const long long id = (long long)((unsigned)p / (unsigned)a.per_thread);
-        const long long off = p - id * a.per_thread;
-        const bool same = id == id0;                  // (a wave may cross into the next virtual thread's slice)
-        uint64_t s = same ? base0 : a.streams[id];
-        unsigned ahead = (unsigned)((same ? off - off0 : off) * (long long)draws);   // < 64 positives' draws
-        // draw 0 of a positive picks the training triple; entity negative k uses draws 1 + 2(k-1) (coin) and the next one
-        // (corruption); relation negative k uses draw 1 + 2 neg + (k - 1 - neg)   (Base.cpp:101-139)
-        if (kk >= 1) ahead += kk <= a.neg ? 1u + 2u * (unsigned)(kk - 1) : 1u + 2u * (unsigned)a.neg + (unsigned)(kk - 1 - a.neg);
-        s = lcg_skip_lanes(s, ahead);
+        if (g0 != wave0) w = request(g0);
+        const long long g = g0 + lane, b = w.b;
+        const int k = w.k, kk = w.kk;
+        const bool live = w.live;
+        uint64_t s = w.same ? lcg_jump_apply(w.jump0, w.st0, w.n0) : w.st;
+        s = w.j1.x * (w.j0.x * s + w.j0.y) + w.j1.y;
         s = lcg_step(s);                              // k = 0: the pick; entity negative: the coin; relation negative: its draw
         const long long pick = (long long)mod_magic(s, a.pick_div, a.pick_magic) + (a.new_batch > 0 ? a.train_dup - a.new_batch : 0);
         const long long i = __shfl((int)pick, lane & ~kmask);      // the positive's k = 0 lane holds the real one (train_dup < 2^31)
         const int4 tr = a.pos[i];  // (h, t, r, -)
-        const int4 gq = a.grp[i];  // loaded together with it (not after the coin): one memory latency instead of two
+        int4 gq = a.grp[i];        // loaded together with it (not after the coin): one memory latency instead of two
+        int2 gr = make_int2(0, 0);
+        if (a.negrel > 0) gr = a.ht[i];
+        // (only the negatives' lanes use the group records, and the compiler sinks a load into the branch of its only use, behind the
+        // wait for pos: a second round trip.  Values that must exist here keep the requests side by side.)
+        asm volatile("" : "+v"(gq.x), "+v"(gq.y), "+v"(gq.z), "+v"(gq.w), "+v"(gr.x), "+v"(gr.y));
         int2 tl = make_int2(0, 0);
         if constexpr (TYPED) tl = a.typed_len[i];
         int oh = tr.x, ot = tr.y, orr = tr.z;
-        if (kk >= 1 && kk <= a.neg) {
-            const float prob = a.bern ? (bern_in_lds ? bern_lds[orr] : a.bern_prob[orr]) : 500.0f;
-            const bool keep_head = (float)(s % 1000ull) < prob;      // Base.cpp:118: compared in float
-            s = lcg_step(s);                                           // Corrupt.h:25: the one draw of the corruption
+        if (kk >= 1) {
+            // one path for a new tail (corrupt_head(h, r): outside tails(h,r)), a new head (corrupt_tail(t, r): outside
+            // heads(t,r)) and a new relation (Base.cpp:133-139 corrupt_rel(h, t)): the list, its length and the modulus' table are
+            // selected, one modulo and one search follow, and selects route the result
+            const bool ent = kk <= a.neg;
+            bool keep_head = false;
             int typed_id = -1;
-            if constexpr (TYPED) typed_id = typed_pick<true>(a, s, keep_head, orr, gq, tl);
-            if (typed_id >= 0) {
-                if (keep_head) ot = typed_id; else oh = typed_id;
-            } else if (keep_head) {  // corrupt_head(h, r): new TAIL outside tails(h,r)
-                const long long tmp = (long long)mod_u64_u32(s, (uint32_t)(a.ent_total - gq.y));
-                ot = min(filtered_pick_short(a.tails_hr + gq.x, gq.y, tmp), a.ent_total - 1);   // (clamp: only reachable in that degenerate case)
-            } else {          // corrupt_tail(t, r): new HEAD outside heads(t,r)
-                const long long tmp = (long long)mod_u64_u32(s, (uint32_t)(a.ent_total - gq.w));
-                oh = min(filtered_pick_short(a.heads_tr + gq.z, gq.w, tmp), a.ent_total - 1);
+            if (ent) {
+                const float prob = a.bern ? (bern_in_lds ? bern_lds[orr] : a.bern_prob[orr]) : 500.0f;
+                keep_head = (float)(s % 1000ull) < prob;      // Base.cpp:118: compared in float
+                s = lcg_step(s);                               // Corrupt.h:25: the one draw of the corruption
+                if constexpr (TYPED) typed_id = typed_pick<true>(a, s, keep_head, orr, gq, tl);
             }
-        } else if (kk > a.neg) {  // Base.cpp:133-139: corrupt_rel(h, t)
-            const int2 gr = a.ht[i];
-            const long long tmp = (long long)mod_u64_u32(s, (uint32_t)(a.rel_total - gr.y));
-            orr = min(filtered_pick_short(a.rels_ht + gr.x, gr.y, tmp), a.rel_total - 1);
+            int v = typed_id;
+            if (typed_id < 0) {
+                const int32_t *vals = !ent ? a.rels_ht + gr.x : (keep_head ? a.tails_hr + gq.x : a.heads_tr + gq.z);
+                const int len = !ent ? gr.y : (keep_head ? gq.y : gq.w);
+                const int total = ent ? a.ent_total : a.rel_total;
+                v = min(filtered_pick_wide<kPickFan>(vals, len, total, ent ? a.ent_magic : a.rel_magic, a.magic_len, s), total - 1);   // (clamp: only reachable when the group holds every candidate)
+            }
+            orr = ent ? orr : v;
+            ot = ent && keep_head ? v : ot;
+            oh = ent && !keep_head ? v : oh;
         }
         if (live) {
             const long long o = b + (long long)k * a.out_stride;
