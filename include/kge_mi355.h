@@ -365,6 +365,21 @@ int kge_forward_backward_adam_rows(const kge_model_desc *m, float *const tables[
 int kge_float_records_apply_adam(const kge_model_desc *m, float *const tables[KGE_MAX_TABLES], float *const adam_m[KGE_MAX_TABLES],
                                  float *const adam_v[KGE_MAX_TABLES], const float *d_rec, int32_t *d_dst, INT n_records, INT n_pos_total,
                                  INT n_neg, float lr_t, float beta1, float beta2, float eps, void *stream);
+/* Opt-in ("Adagrad"): the same two entry points ending in TF1's AdagradOptimizer on the touched rows -- per element, in fp32,
+ *     if (g != 0) { a += g*g;  p -= lr * g / sqrt(a); }
+ * with no epsilon (the caller fills the accumulators `acc` -- one per table of the model, shaped like it -- with a positive
+ * value before the first step; TF's default is 0.1) and no step-dependent factor.  Unlike lazy Adam this IS the dense rule: an
+ * element with zero gradient keeps its value and its accumulator bit for bit, so updating only the rows that have a record
+ * gives the tables kge_adagrad_update_tables gives from the same summed gradient.  g is a row's complete sum (record order,
+ * hub copies in copy order), as for lazy Adam; the step is reproducible bit for bit.  A missing accumulator: KGE_ERR_BAD_ARG
+ * before anything is launched.  TransE / TransH / TransD; TransR: KGE_ERR_UNSUPPORTED.  kge_sgd_rows_skipped applies as above.
+ * `lr` is used as given, here and on kge_transe_apply_rows_adagrad / kge_adagrad_update(_tables): none of the four checks its
+ * sign or size, as none of the Adam or SGD entry points does. */
+int kge_forward_backward_adagrad_rows(const kge_model_desc *m, float *const tables[KGE_MAX_TABLES], float *const acc[KGE_MAX_TABLES],
+                                      const int32_t *d_h, const int32_t *d_t, const int32_t *d_r, INT n_pos, INT n_neg, INT stride, INT denom,
+                                      float lr, float *d_loss, void *stream);
+int kge_float_records_apply_adagrad(const kge_model_desc *m, float *const tables[KGE_MAX_TABLES], float *const acc[KGE_MAX_TABLES],
+                                    const float *d_rec, int32_t *d_dst, INT n_records, INT n_pos_total, INT n_neg, float lr, void *stream);
 /* 1 when kge_forward_backward on a step of this shape takes the TransH / TransD pair-count path (whose emit kernel also records
  * the event above), else 0 */
 int kge_pair_path_active(const kge_model_desc *m, INT n_pos, INT n_neg);
@@ -397,13 +412,18 @@ int kge_sgd_update(float *d_p, float *d_g, int64_t n, float lr, void *stream);
  * row decays and moves.  lr_t = lr*sqrt(1-beta2^t)/(1-beta1^t) computed by the caller; g = 0 after. */
 int kge_adam_update(float *d_p, float *d_m, float *d_v, float *d_g, int64_t n, float lr_t, float beta1,
                     float beta2, float eps, void *stream);
+/* TF1 AdagradOptimizer on the summed gradient: where g != 0, a += g*g; p -= lr * g / sqrt(a); g = 0 after.  Elements (and whole
+ * 16-byte groups) with zero gradient are left alone, accumulator included.  Null pointers: KGE_ERR_BAD_ARG, nothing launched. */
+int kge_adagrad_update(float *d_p, float *d_acc, float *d_g, int64_t n, float lr, void *stream);
 
-/* The same two updates for all tables of a model in ONE launch (n_tables <= KGE_MAX_TABLES; numel[i] elements each) */
+/* The same updates for all tables of a model in ONE launch (n_tables <= KGE_MAX_TABLES; numel[i] elements each) */
 int kge_sgd_update_tables(int32_t n_tables, float *const d_p[KGE_MAX_TABLES], float *const d_g[KGE_MAX_TABLES],
                           const INT numel[KGE_MAX_TABLES], float lr, void *stream);
 int kge_adam_update_tables(int32_t n_tables, float *const d_p[KGE_MAX_TABLES], float *const d_m[KGE_MAX_TABLES],
                            float *const d_v[KGE_MAX_TABLES], float *const d_g[KGE_MAX_TABLES], const INT numel[KGE_MAX_TABLES],
                            float lr_t, float beta1, float beta2, float eps, void *stream);
+int kge_adagrad_update_tables(int32_t n_tables, float *const d_p[KGE_MAX_TABLES], float *const d_acc[KGE_MAX_TABLES],
+                              float *const d_g[KGE_MAX_TABLES], const INT numel[KGE_MAX_TABLES], float lr, void *stream);
 
 /* ---- TransE sign-count path (exact integer gradients, no fp32 atomics) ----------------------
  * For the L1 score of TransE.py:11-15 the gradient w.r.t. every l2-normalised vector is (1/denom) x an
@@ -439,7 +459,9 @@ int kge_transe_apply_counts(float *d_p, float *d_m, float *d_v, int32_t *d_count
  * rows, relation rows and rows without records go through `d_counts` (zero on entry, zero on return) and one apply launch.
  * sampler_shaped = 1: the batch came from kge_sampling_device (no deferral bookkeeping, no fp32 pass, d_resid tables not read);
  * 0: any batch, d_resid [E,D] / [R,D] (zero on entry and return) take the exact fp32 gradients of groups that are not
- * sampler-shaped.  d_m / d_v may be NULL for SGD (adam = 0, lr); Adam: lr = lr_t. */
+ * sampler-shaped.  d_m / d_v may be NULL for SGD (adam = 0, lr); Adam (adam = any other value): lr = lr_t.  `adam` is a yes / no
+ * flag on this and on the kge_transe_apply_counts* entry points: the dense forms have these two rules only (Adagrad's is the
+ * row-list form, kge_transe_apply_rows_adagrad). */
 int kge_transe_train_step_counts(const kge_model_desc *m, float *const d_p[2], float *const d_m[2], float *const d_v[2], const int32_t *d_h,
                                  const int32_t *d_t, const int32_t *d_r, INT n_pos, INT n_neg, INT stride, INT denom, int32_t *d_counts,
                                  float *const d_resid[2], int32_t sampler_shaped, int32_t adam, float lr, float beta1, float beta2, float eps,
@@ -504,6 +526,13 @@ int kge_transe_lazy_row_live(const int32_t *d_row_live);
 int kge_transe_apply_rows_adam_lazy(const kge_model_desc *m, float *d_ent, float *d_rel, float *d_m_ent, float *d_m_rel, float *d_v_ent,
                                     float *d_v_rel, const int32_t *d_rows, const int32_t *d_row_counts, const int32_t *d_n_rows,
                                     INT max_rows, INT denom, float lr_t, float beta1, float beta2, float eps, void *stream);
+/* Opt-in ("Adagrad"): TF1's AdagradOptimizer on the rows listed in d_rows, from their counts -- the row's gradient g is formed as
+ * the lazy-Adam call forms it, then per element: if (g != 0) { a += g*g; p -= lr * g / sqrt(a); }.  d_acc_ent / d_acc_rel are the
+ * accumulator tables, shaped like the parameter tables.  Rows that are not listed, listed rows whose counts are all zero and
+ * elements whose gradient is zero keep value and accumulator bit for bit -- so no live mask is needed where all rows of a table
+ * are listed with all-reduced counts, and the touched rows are all the dense rule would move. */
+int kge_transe_apply_rows_adagrad(const kge_model_desc *m, float *d_ent, float *d_rel, float *d_acc_ent, float *d_acc_rel, const int32_t *d_rows,
+                                  const int32_t *d_row_counts, const int32_t *d_n_rows, INT max_rows, INT denom, float lr, void *stream);
 /* reduce + apply in one pass (embedding width a multiple of 4): rows whose records all fall inside one 64-record chunk
  * of the sorted list are updated straight from the registers that hold their sum; only chunk-boundary rows go through
  * d_row_counts and a second, small pass.  Same bits as kge_transe_reduce_records + kge_transe_apply_rows_sgd.

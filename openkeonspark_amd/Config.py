@@ -7,7 +7,7 @@ Same constructor, setters, attributes, `init()` and `sampling()` as the referenc
 `sess.run([train_op, loss, global_step], feed_dict)` (distribute_training.py:282) built by
 `create_model` (distribute_training.py:74-105) -- is `train_step()` here: sample on the device,
 run the fused forward/backward operator, exchange gradients over RCCL when data-parallel, apply
-SGD or TF-parity Adam.  Nothing in this module computes on the CPU; without the HIP library or a
+SGD, TF-parity Adam or -- opt-in -- lazy Adam / Adagrad on the touched rows.  Nothing in this module computes on the CPU; without the HIP library or a
 GPU the device calls raise.
 """
 import ctypes
@@ -58,6 +58,8 @@ class Config(object):
             self.seed = 0                 # parameter initialisation seed
             self.device = "cuda"
             self.adam_beta1, self.adam_beta2, self.adam_epsilon = 0.9, 0.999, 1e-8  # TF1 AdamOptimizer defaults
+            self.adagrad_initial_accumulator = 0.1   # TF1 AdagradOptimizer's default; must be positive (the rule has no epsilon)
+            self._adagrad = False                    # set_model_and_session decides it from opt_method
             self.trainModel = None
             self.global_step = 0
             self.rank, self.world_size = 0, 1
@@ -306,6 +308,15 @@ class Config(object):
         # sparse-row path; `_has_slots` = "m / v tables and beta powers exist" (both Adam flavours)
         self._lazy_adam = self.opt_method in ("LazyAdam", "lazyadam", "lazy_adam")
         self._has_slots = self._adam or self._lazy_adam
+        # opt-in: TF1's AdagradOptimizer (upstream OpenKE offers it; the reference sends the name to SGD).  Like LazyAdam it rides on
+        # the touched-rows paths, but exactly: an element with zero gradient keeps its value and its accumulator bit for bit, so
+        # "only the touched rows" IS the dense rule.  One accumulator table per parameter table, nothing to advance between steps.
+        # TransR has no record path and keeps its dense gradient tables (kge_adagrad_update_tables), in one process only.
+        self._adagrad = self.opt_method in ("Adagrad", "adagrad")
+        if self._adagrad and not (float(self.adagrad_initial_accumulator) > 0.0):
+            raise KgeError("adagrad_initial_accumulator must be positive (the Adagrad rule divides by sqrt(accumulator), without an "
+                           "epsilon), got %r" % (self.adagrad_initial_accumulator,))
+        self._rows_rule = self._lazy_adam or self._adagrad        # optimizers that ARE a choice of touched rows
         # TransE: exact integer sign-count gradients instead of fp32 atomics (include/kge_mi355.h)
         n_neg = self.negative_ent + self.negative_rel
         self.use_counts = bool(getattr(self, "use_counts", True)) and bool(
@@ -316,7 +327,7 @@ class Config(object):
         # sweeps every row of m, v and the table each step, which is the dense path by definition.
         requested = getattr(self, "sparse_rows", None)   # None = automatic, True / False = the caller's wish
         table_bytes, sparse = self._wants_sparse_rows(n_neg)
-        self.sparse_rows = (bool(sparse) or self._lazy_adam) and self.use_counts and not self._adam
+        self.sparse_rows = (bool(sparse) or self._rows_rule) and self.use_counts and not self._adam
         # TransH / TransD (and TransE outside the sign-count path) with SGD: the touched rows are updated in place from float
         # gradient records (kge_forward_backward_sgd_rows) -- no gradient tables, no sweep.  On request, or by itself for tables
         # beyond 2 GB (measured at 4 GB, dim 200, B = 131 072, n = 1: TransH 1.63 -> 0.70 ms, TransD 2.83 -> 0.97 ms per step and
@@ -325,18 +336,20 @@ class Config(object):
         # (kge_forward_backward_adam_rows): asking for LazyAdam IS asking for touched rows, whatever `sparse_rows` says.
         vector_model = m.model_id in (_lib.TRANSE, _lib.TRANSH, _lib.TRANSD)
         self.sparse_inplace = bool(not self.sparse_rows and vector_model and not self._adam and
-                                   (self._lazy_adam or requested or (requested is None and table_bytes > (2 << 30))))
+                                   (self._rows_rule or requested or (requested is None and table_bytes > (2 << 30))))
         if self._lazy_adam and not (self.sparse_rows or self.sparse_inplace):
             raise KgeError("LazyAdam (touched rows only, NON-PARITY) needs TransE, TransH or TransD: TransR's gradient is a whole "
                            "matrix per relation and has no record path")
         if requested and not (self.sparse_rows or self.sparse_inplace):
-            raise KgeError("sparse_rows needs TransE / TransH / TransD with SGD or LazyAdam")
+            raise KgeError("sparse_rows needs TransE / TransH / TransD with SGD, LazyAdam or Adagrad")
         self._grads = [] if (self.sparse_rows or self.sparse_inplace) else [torch.zeros_like(t) for t in self._tables]
         if self._has_slots:
             self._adam_m = [torch.zeros_like(t) for t in self._tables]
             self._adam_v = [torch.zeros_like(t) for t in self._tables]
             self._beta1_power = np.float32(self.adam_beta1)
             self._beta2_power = np.float32(self.adam_beta2)
+        if self._adagrad:      # shaped like the tables: a row-sharded entity table (Model.embedding_def) gets a shard-sized accumulator
+            self._adagrad_acc = [torch.full_like(t, float(self.adagrad_initial_accumulator)) for t in self._tables]
         self._loss = torch.zeros(1, dtype=torch.float32, device=self.device)
         self._refresh_pointers()
         self._dist_ready = 0
@@ -384,7 +397,7 @@ class Config(object):
 
     def _plan_entity_shard(self, model):
         """If this process already belongs to a torch.distributed world of N > 1 ranks and the step will be the table-sharded
-        sparse one (TransE on the sign-count path, SGD or LazyAdam), the rows [lo, hi) of the entity table this rank will own:
+        sparse one (TransE on the sign-count path, SGD, LazyAdam or Adagrad), the rows [lo, hi) of the entity table this rank will own:
         the model then draws ONLY those rows (Model.embedding_def) instead of the whole table that _setup_shards would cut
         down -- 102 GB per rank at BASELINE config #5.  None otherwise (the table is created whole, as before)."""
         try:
@@ -403,7 +416,7 @@ class Config(object):
         desc = probe.descriptor()
         if not (bool(getattr(self, "use_counts", True)) and bool(self.lib.kge_transe_counts_supported(ctypes.byref(desc), n_neg))):
             return None
-        lazy = self.opt_method in ("LazyAdam", "lazyadam", "lazy_adam")
+        lazy = self.opt_method in ("LazyAdam", "lazyadam", "lazy_adam", "Adagrad", "adagrad")    # touched rows whatever the table size
         if not (bool(self._wants_sparse_rows(n_neg)[1]) or lazy):
             return None
         from .parallel import chunk_size
@@ -447,6 +460,9 @@ class Config(object):
         self._n_local = self.lib.kge_slice_positions(self.batch_size, lo, hi, ctypes.byref(first))
         self._first_pos = first.value
         if self._dp and self.trainModel is not None and getattr(self, "_dist_ready", 0) != self.world_size:
+            if self._adagrad and not (self.sparse_rows or self.sparse_inplace):
+                raise KgeError("TransR with Adagrad is single-process only: the data-parallel dense step has no flat accumulator "
+                               "for its reduce-scatter exchange")
             if getattr(self, "sparse_inplace", False):
                 pass          # replicated tables, the step's gradient records all-gathered (_records_step): nothing to lay out
             elif self.sparse_rows:
@@ -463,6 +479,8 @@ class Config(object):
         if self._has_slots:
             self._adam_m_ptrs = _lib.table_ptrs([t.data_ptr() for t in self._adam_m])
             self._adam_v_ptrs = _lib.table_ptrs([t.data_ptr() for t in self._adam_v])
+        if self._adagrad:
+            self._adagrad_ptrs = _lib.table_ptrs([t.data_ptr() for t in self._adagrad_acc])
 
     def _setup_flat_buffers(self):
         """Data-parallel layout of the dense path: all tables in ONE flat fp32 buffer cut into world_size equal chunks,
@@ -573,6 +591,12 @@ class Config(object):
                 if hi > lo:
                     slots[0][:hi - lo].copy_(old[lo:hi])
                 del old
+        if self._adagrad:       # the accumulator of the entity rows likewise (pad rows of the last shard: the initial value, never read)
+            old = self._adagrad_acc[0]
+            self._adagrad_acc[0] = torch.full((chunk, D), float(self.adagrad_initial_accumulator), dtype=torch.float32, device=shard.device)
+            if hi > lo:
+                self._adagrad_acc[0][:hi - lo].copy_(old[lo:hi])
+            del old
         torch.cuda.empty_cache()
         self._shard = dict(chunk=chunk, lo=lo, hi=hi)
         self._refresh_pointers()
@@ -714,6 +738,8 @@ class Config(object):
         gradient chunk."""
         st = self._stream()
         if own:       # one piece of this rank's share (train_step's exchange loop calls it per piece and advances Adam once)
+            if self._adagrad:
+                raise KgeError("TransR with Adagrad is single-process only")
             lo, hi = self._piece_own[piece]
             n = hi - lo
             if hi > self._loss_tail:
@@ -732,6 +758,9 @@ class Config(object):
                                                        self._grad_ptrs, self._numel, float(self._adam_lr_t()), self.adam_beta1,
                                                        self.adam_beta2, self.adam_epsilon, st), self.lib)
             self._adam_advance()
+        elif self._adagrad:     # (TransR: every other model takes a touched-rows path under Adagrad)
+            _lib.check(self.lib.kge_adagrad_update_tables(len(self._tables), self._tab_ptrs, self._adagrad_ptrs, self._grad_ptrs,
+                                                          self._numel, float(self.alpha), st), self.lib)
         else:
             _lib.check(self.lib.kge_sgd_update_tables(len(self._tables), self._tab_ptrs, self._grad_ptrs, self._numel,
                                                       float(self.alpha), st), self.lib)
@@ -915,6 +944,10 @@ class Config(object):
                     dev[2].data_ptr(), n_pos, n_neg, stride, denom, float(self._adam_lr_t()), self.adam_beta1, self.adam_beta2,
                     self.adam_epsilon, self._loss.data_ptr(), self._stream()), self.lib)
                 self._adam_advance()
+            elif self._adagrad:
+                _lib.check(self.lib.kge_forward_backward_adagrad_rows(
+                    ctypes.byref(self._desc), self._tab_ptrs, self._adagrad_ptrs, dev[0].data_ptr(), dev[1].data_ptr(), dev[2].data_ptr(),
+                    n_pos, n_neg, stride, denom, float(self.alpha), self._loss.data_ptr(), self._stream()), self.lib)
             else:
                 _lib.check(self.lib.kge_forward_backward_sgd_rows(
                     ctypes.byref(self._desc), self._tab_ptrs, dev[0].data_ptr(), dev[1].data_ptr(), dev[2].data_ptr(), n_pos, n_neg,
@@ -990,7 +1023,7 @@ class Config(object):
         """Can train_steps() run its steps inside one persistent launch (csrc/persist.hip)?  Single process, the dense
         fp32-accumulator path of TransE / TransH / TransD at a launch-latency-bound step size.  Not with type-constrained
         sampling: the persistent kernel has the untyped sampler only."""
-        if self.type_constrained_sampling:
+        if self.type_constrained_sampling or self._adagrad:       # (persist.hip has the SGD and Adam sweeps only)
             return False
         if self._dp or self.sparse_rows or self.sparse_inplace or self.hidden_size > 256:
             return False
@@ -1060,7 +1093,7 @@ class Config(object):
         return out
 
     def _records_step(self, dev_batch, n_pos, stride, denom):
-        """Row-wise SGD (or lazy Adam) in place across ranks (TransH / TransD, or TransE off the sign-count path, with sparse_rows):
+        """Row-wise SGD (or lazy Adam, or Adagrad with its replicated accumulators) in place across ranks (TransH / TransD, or TransE off the sign-count path, with sparse_rows):
         the tables -- and with LazyAdam their moments -- are replicated; every rank turns ITS slice of the batch into float gradient records, the records (rows + destination
         keys) are all-gathered -- the sparse touched-row exchange: only rows a step touches travel -- and every rank adds -lr * the
         per-row sums of ALL records to its replica (LazyAdam: puts them through the Adam rule on the rows that have a record).  Every rank reduces the same records in the same order, so the replicas stay
@@ -1094,6 +1127,10 @@ class Config(object):
                 W * per, self.batch_size, n_neg, float(self._adam_lr_t()), self.adam_beta1, self.adam_beta2, self.adam_epsilon,
                 self._stream()), self.lib)
             self._adam_advance()
+        elif self._adagrad:      # the accumulators are replicated like the tables: the same records in the same order on every rank
+            _lib.check(self.lib.kge_float_records_apply_adagrad(
+                ctypes.byref(self._desc), self._tab_ptrs, self._adagrad_ptrs, b["rec"].data_ptr(), b["dst"].data_ptr(), W * per,
+                self.batch_size, n_neg, float(self.alpha), self._stream()), self.lib)
         else:
             _lib.check(self.lib.kge_float_records_apply(
                 ctypes.byref(self._desc), self._tab_ptrs, b["rec"].data_ptr(), b["dst"].data_ptr(), W * per, self.batch_size, n_neg,
@@ -1143,6 +1180,14 @@ class Config(object):
                 buf["row_counts"].data_ptr(), buf["n_rows"].data_ptr(), dst.numel(), denom, float(self._adam_lr_t()),
                 self.adam_beta1, self.adam_beta2, self.adam_epsilon, st), self.lib)
             self._adam_advance()
+        elif self._adagrad:      # (not the fused reduce-apply: the rule is not linear in the gradient, it needs a row's complete sum)
+            _lib.check(self.lib.kge_transe_reduce_records(
+                ctypes.byref(self._desc), rec.data_ptr(), dst.data_ptr(), dst.numel(), buf["rows"].data_ptr(),
+                buf["row_counts"].data_ptr(), buf["n_rows"].data_ptr(), st), self.lib)
+            _lib.check(self.lib.kge_transe_apply_rows_adagrad(
+                ctypes.byref(self._desc), self._tables[0].data_ptr(), self._tables[1].data_ptr(), self._adagrad_acc[0].data_ptr(),
+                self._adagrad_acc[1].data_ptr(), buf["rows"].data_ptr(), buf["row_counts"].data_ptr(), buf["n_rows"].data_ptr(),
+                dst.numel(), denom, float(self.alpha), st), self.lib)
         elif getattr(self, "sparse_fused", True) and D % 4 == 0:
             # reduce + apply in one pass: only chunk-boundary rows go through the compact count image
             _lib.check(self.lib.kge_transe_reduce_apply_records_sgd(
@@ -1292,6 +1337,13 @@ class Config(object):
                     self._adam_m[1].data_ptr(), self._adam_v[0].data_ptr(), self._adam_v[1].data_ptr(), b["rows"].data_ptr(),
                     b["row_counts"].data_ptr(), b["n_rows"].data_ptr(), n_recv2, denom, float(self._adam_lr_t()), self.adam_beta1,
                     self.adam_beta2, self.adam_epsilon, st), L)
+            elif self._adagrad:
+                _lib.check(L.kge_transe_reduce_records(ctypes.byref(desc3), b["recv_rec"].data_ptr(), b["recv_rows2"].data_ptr(), n_recv2,
+                                                       b["rows"].data_ptr(), b["row_counts"].data_ptr(), b["n_rows"].data_ptr(), st), L)
+                _lib.check(L.kge_transe_apply_rows_adagrad(
+                    ctypes.byref(desc3), self._tables[0].data_ptr(), self._tables[1].data_ptr(), self._adagrad_acc[0].data_ptr(),
+                    self._adagrad_acc[1].data_ptr(), b["rows"].data_ptr(), b["row_counts"].data_ptr(), b["n_rows"].data_ptr(), n_recv2,
+                    denom, float(self.alpha), st), L)
             else:
                 _lib.check(L.kge_transe_reduce_apply_records_sgd(
                     ctypes.byref(desc3), b["recv_rec"].data_ptr(), b["recv_rows2"].data_ptr(), n_recv2, self._tables[0].data_ptr(),
@@ -1307,6 +1359,12 @@ class Config(object):
                 b["rel_counts"].data_ptr(), b["n_rel"].data_ptr(), self.relTotal, denom, float(self._adam_lr_t()), self.adam_beta1,
                 self.adam_beta2, self.adam_epsilon, st), L)
             self._adam_advance()
+        elif self._adagrad:
+            # (no live mask: a relation whose all-reduced counts are zero has zero gradient, and the rule leaves it alone)
+            _lib.check(L.kge_transe_apply_rows_adagrad(
+                ctypes.byref(self._desc), self._tables[0].data_ptr(), self._tables[1].data_ptr(), self._adagrad_acc[0].data_ptr(),
+                self._adagrad_acc[1].data_ptr(), b["rel_rows"].data_ptr(), b["rel_counts"].data_ptr(), b["n_rel"].data_ptr(),
+                self.relTotal, denom, float(self.alpha), st), L)
         else:
             _lib.check(L.kge_transe_apply_rows_sgd(ctypes.byref(self._desc), self._tables[0].data_ptr(), self._tables[1].data_ptr(),
                                                    b["rel_rows"].data_ptr(), b["rel_counts"].data_ptr(), b["n_rel"].data_ptr(),

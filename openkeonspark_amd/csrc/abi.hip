@@ -509,14 +509,14 @@ int kge_float_records_apply(const kge_model_desc *m, float *const tables[KGE_MAX
 
 // the moments of the model's tables (a table the model does not have: ignored), or false if one is missing
 static bool adam_rows_of(const kge_model_desc &m, float *const tables[KGE_MAX_TABLES], float *const adam_m[KGE_MAX_TABLES],
-                         float *const adam_v[KGE_MAX_TABLES], float lr_t, float beta1, float beta2, float eps, AdamRows &ad) {
+                         float *const adam_v[KGE_MAX_TABLES], float lr_t, float beta1, float beta2, float eps, RowRule &ad) {
     ad = {};
     for (int t = 0; t < 4; t++) {
         if (!tables[t]) continue;
         if (!adam_m[t] || !adam_v[t]) return false;
         ad.m[t] = adam_m[t]; ad.v[t] = adam_v[t];
     }
-    ad.lr_t = lr_t; ad.b1 = beta1; ad.b2 = beta2; ad.eps = eps;
+    ad.lr_t = lr_t; ad.b1 = beta1; ad.b2 = beta2; ad.eps = eps; ad.rule = kRuleAdam;
     return true;
 }
 
@@ -525,7 +525,7 @@ int kge_forward_backward_adam_rows(const kge_model_desc *m, float *const tables[
                                    INT n_neg, INT stride, INT denom, float lr_t, float beta1, float beta2, float eps, float *d_loss, void *stream) {
     if (!m || !tables || !adam_m || !adam_v || !d_loss) return fail(KGE_ERR_BAD_ARG, "kge_forward_backward_adam_rows: null argument");
     if (m->model == KGE_TRANSR) return fail(KGE_ERR_UNSUPPORTED, "lazy Adam on the touched rows: TransE / TransH / TransD only");
-    AdamRows ad;
+    RowRule ad;
     if (!adam_rows_of(*m, tables, adam_m, adam_v, lr_t, beta1, beta2, eps, ad))
         return fail(KGE_ERR_BAD_ARG, "kge_forward_backward_adam_rows: every table needs its two moment tables");
     return launch_forward_backward(*m, tables, d_h, d_t, d_r, n_pos, n_neg, stride, denom, tables, d_loss, (hipStream_t)stream, false, 0.f, &ad);
@@ -535,9 +535,42 @@ int kge_float_records_apply_adam(const kge_model_desc *m, float *const tables[KG
                                  float *const adam_v[KGE_MAX_TABLES], const float *d_rec, int32_t *d_dst, INT n_records, INT n_pos_total,
                                  INT n_neg, float lr_t, float beta1, float beta2, float eps, void *stream) {
     if (!m || !tables || !adam_m || !adam_v) return fail(KGE_ERR_BAD_ARG, "kge_float_records_apply_adam: null argument");
-    AdamRows ad;
+    RowRule ad;
     if (!adam_rows_of(*m, tables, adam_m, adam_v, lr_t, beta1, beta2, eps, ad))
         return fail(KGE_ERR_BAD_ARG, "kge_float_records_apply_adam: every table needs its two moment tables");
+    return launch_float_records_apply_adam(*m, tables, ad, d_rec, d_dst, n_records, n_pos_total, n_neg, (hipStream_t)stream);
+}
+
+// the accumulators of the model's tables as the row rule's one slot table each, or false if one is missing
+static bool adagrad_rows_of(float *const tables[KGE_MAX_TABLES], float *const acc[KGE_MAX_TABLES], float lr, RowRule &ad) {
+    ad = {};
+    for (int t = 0; t < 4; t++) {
+        if (!tables[t]) continue;
+        if (!acc[t]) return false;
+        ad.m[t] = acc[t];
+    }
+    ad.lr_t = lr; ad.rule = kRuleAdagrad;
+    return true;
+}
+
+int kge_forward_backward_adagrad_rows(const kge_model_desc *m, float *const tables[KGE_MAX_TABLES], float *const acc[KGE_MAX_TABLES],
+                                      const int32_t *d_h, const int32_t *d_t, const int32_t *d_r, INT n_pos, INT n_neg, INT stride, INT denom,
+                                      float lr, float *d_loss, void *stream) {
+    if (!m || !tables || !acc || !d_loss) return fail(KGE_ERR_BAD_ARG, "kge_forward_backward_adagrad_rows: null argument");
+    if (m->model == KGE_TRANSR) return fail(KGE_ERR_UNSUPPORTED, "Adagrad on the touched rows: TransE / TransH / TransD only");
+    RowRule ad;
+    if (!adagrad_rows_of(tables, acc, lr, ad))
+        return fail(KGE_ERR_BAD_ARG, "kge_forward_backward_adagrad_rows: every table needs its accumulator table");
+    return launch_forward_backward(*m, tables, d_h, d_t, d_r, n_pos, n_neg, stride, denom, tables, d_loss, (hipStream_t)stream, false, 0.f, &ad);
+}
+
+int kge_float_records_apply_adagrad(const kge_model_desc *m, float *const tables[KGE_MAX_TABLES], float *const acc[KGE_MAX_TABLES],
+                                    const float *d_rec, int32_t *d_dst, INT n_records, INT n_pos_total, INT n_neg, float lr, void *stream) {
+    if (!m || !tables || !acc) return fail(KGE_ERR_BAD_ARG, "kge_float_records_apply_adagrad: null argument");
+    if (m->model == KGE_TRANSR) return fail(KGE_ERR_UNSUPPORTED, "Adagrad on the touched rows: TransE / TransH / TransD only");
+    RowRule ad;
+    if (!adagrad_rows_of(tables, acc, lr, ad))
+        return fail(KGE_ERR_BAD_ARG, "kge_float_records_apply_adagrad: every table needs its accumulator table");
     return launch_float_records_apply_adam(*m, tables, ad, d_rec, d_dst, n_records, n_pos_total, n_neg, (hipStream_t)stream);
 }
 
@@ -595,6 +628,18 @@ int kge_adam_update_tables(int32_t n_tables, float *const d_p[KGE_MAX_TABLES], f
                            float lr_t, float beta1, float beta2, float eps, void *stream) {
     tables_written();
     return launch_adam_tables(n_tables, d_p, d_m, d_v, d_g, (const int64_t *)numel, lr_t, beta1, beta2, eps, (hipStream_t)stream);
+}
+
+int kge_adagrad_update(float *d_p, float *d_acc, float *d_g, int64_t n, float lr, void *stream) {
+    if (!d_p || !d_acc || !d_g) return fail(KGE_ERR_BAD_ARG, "kge_adagrad_update: null argument");
+    tables_written();
+    return launch_adagrad(d_p, d_acc, d_g, n, lr, (hipStream_t)stream);
+}
+
+int kge_adagrad_update_tables(int32_t n_tables, float *const d_p[KGE_MAX_TABLES], float *const d_acc[KGE_MAX_TABLES],
+                              float *const d_g[KGE_MAX_TABLES], const INT numel[KGE_MAX_TABLES], float lr, void *stream) {
+    tables_written();
+    return launch_adagrad_tables(n_tables, d_p, d_acc, d_g, (const int64_t *)numel, lr, (hipStream_t)stream);
 }
 
 int kge_predict(const kge_model_desc *m, const float *const tables[KGE_MAX_TABLES], const int32_t *d_h,

@@ -178,18 +178,24 @@ int float_records_workspace(int64_t M, int D, float *&rec, int32_t *&dst);
 // deterministic: stable sort + one team per run + ordered fold of the hub copies (bit-identical on every rank that reduces the same records)
 int float_records_reduce(int64_t M, int D, const FloatRowSpace &rs, hipStream_t stream, const float *rec_ext = nullptr, int32_t *dst_ext = nullptr,
                          bool deterministic = false);
-// lazy Adam on the touched rows (NON-PARITY): the moments of the four tables in the order of kge_model_desc's tables, and the rule's constants
-struct AdamRows {
+// The rule the float-record layers apply to a touched row, with its slot tables (in the order of kge_model_desc's tables) and constants:
+//   kRuleAdam    : lazy Adam on the touched rows (NON-PARITY): m, v = the moments, lr_t = the bias-corrected rate, b1, b2, eps
+//   kRuleAdagrad : adagrad_one (exact, not NON-PARITY: a zero-gradient element keeps p and a bit for bit, so the touched rows are all
+//                  the dense rule moves): m = the accumulators, v unused (null), lr_t = the plain learning rate, b1 / b2 / eps unused
+// The functions that carry it keep `adam` in their names: they are the LazyAdam layers, serving both rules.
+enum { kRuleAdam = 0, kRuleAdagrad = 1 };
+struct RowRule {
     float *m[4], *v[4];
     float lr_t, b1, b2, eps;
+    int rule;
 };
-// the deterministic reduce ending in adam_one on every row that has a record (rs.g_* = the parameter tables; rs.scale unused)
-int float_records_reduce_adam(int64_t M, int D, const FloatRowSpace &rs, const AdamRows &ad, hipStream_t stream, const float *rec_ext = nullptr,
+// the deterministic reduce ending in adam_one / adagrad_one on every row that has a record (rs.g_* = the parameter tables; rs.scale unused)
+int float_records_reduce_adam(int64_t M, int D, const FloatRowSpace &rs, const RowRule &ad, hipStream_t stream, const float *rec_ext = nullptr,
                               int32_t *dst_ext = nullptr);
 int launch_forward_backward_records(const kge_model_desc &m, const float *const tables[4], const int32_t *d_h, const int32_t *d_t,
                                     const int32_t *d_r, int64_t n_pos, int64_t n_neg, int64_t stride, int64_t denom, int64_t n_pos_total,
                                     float *d_rec, int32_t *d_dst, int64_t rec_offset, int64_t rec_slice, float *d_loss, hipStream_t stream);
-int launch_float_records_apply_adam(const kge_model_desc &m, float *const tables[4], const AdamRows &ad, const float *d_rec, int32_t *d_dst,
+int launch_float_records_apply_adam(const kge_model_desc &m, float *const tables[4], const RowRule &ad, const float *d_rec, int32_t *d_dst,
                                     int64_t M_total, int64_t n_pos_total, int64_t n_neg, hipStream_t stream);
 int launch_float_records_apply(const kge_model_desc &m, float *const tables[4], const float *d_rec, int32_t *d_dst, int64_t M_total,
                                int64_t n_pos_total, int64_t n_neg, float lr, hipStream_t stream);
@@ -213,7 +219,7 @@ int launch_widen(const int32_t *src3, int64_t *dst3_and_y, int64_t B, int64_t to
 int launch_forward_backward(const kge_model_desc &m, const float *const tables[4], const int32_t *d_h, const int32_t *d_t,
                             const int32_t *d_r, int64_t n_pos, int64_t n_neg, int64_t stride, int64_t denom,
                             float *const grads[4], float *d_loss, hipStream_t stream, bool sampler_shaped = false, float inplace_lr = 0.f,
-                            const AdamRows *inplace_adam = nullptr);
+                            const RowRule *inplace_adam = nullptr);
 int launch_predict(const kge_model_desc &m, const float *const tables[4], const int32_t *d_h, const int32_t *d_t,
                    const int32_t *d_r, int64_t n, float *d_out, hipStream_t stream);
 int launch_lp_table(const kge_model_desc &m, const float *const tables[4], const float *P_all, int64_t r, float *T, hipStream_t stream);
@@ -226,5 +232,7 @@ int launch_adam_tables(int n_tables, float *const *p, float *const *m, float *co
                        float lr_t, float b1, float b2, float eps, hipStream_t stream);
 int launch_adam(float *p, float *m, float *v, float *g, int64_t n, float lr_t, float b1, float b2, float eps,
                 hipStream_t stream);
+int launch_adagrad_tables(int n_tables, float *const *p, float *const *acc, float *const *g, const int64_t *numel, float lr, hipStream_t stream);
+int launch_adagrad(float *p, float *acc, float *g, int64_t n, float lr, hipStream_t stream);
 
 }  // namespace kge

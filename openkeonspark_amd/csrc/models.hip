@@ -1397,7 +1397,7 @@ int launch_float_records_apply(const kge_model_desc &m, float *const tables[4], 
     return float_records_reduce(M_total, m.ent_dim, rs, stream, d_rec, d_dst, true);
 }
 
-int launch_float_records_apply_adam(const kge_model_desc &m, float *const tables[4], const AdamRows &ad, const float *d_rec, int32_t *d_dst,
+int launch_float_records_apply_adam(const kge_model_desc &m, float *const tables[4], const RowRule &ad, const float *d_rec, int32_t *d_dst,
                                     int64_t M_total, int64_t n_pos_total, int64_t n_neg, hipStream_t stream) {
     if (!device_ok()) return fail(KGE_ERR_NO_DEVICE, "kge_float_records_apply_adam: no usable HIP device");
     if (!d_rec || !d_dst || M_total < 0 || n_pos_total < 0) return fail(KGE_ERR_BAD_ARG, "kge_float_records_apply_adam: bad arguments");
@@ -1417,7 +1417,7 @@ int launch_float_records_apply_adam(const kge_model_desc &m, float *const tables
 int launch_forward_backward(const kge_model_desc &m, const float *const tables[4], const int32_t *d_h, const int32_t *d_t,
                             const int32_t *d_r, int64_t n_pos, int64_t n_neg, int64_t stride, int64_t denom,
                             float *const grads[4], float *d_loss, hipStream_t stream, bool sampler_shaped, float inplace_lr,
-                            const AdamRows *inplace_adam) {
+                            const RowRule *inplace_adam) {
     // inplace_lr != 0 (kge_forward_backward_sgd_rows): `grads` ARE the parameter tables; the step's gradient rows go through the
     // float-record path whatever its size and every summed run is added to its row as -lr * sum -- SGD on the touched rows, no
     // gradient tables, no sweep.  The forward has finished reading the tables when the segmented sum starts (one stream).

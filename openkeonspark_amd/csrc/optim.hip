@@ -6,7 +6,8 @@
 // receive (1-beta)*g, then EVERY row moves -- a dense sweep of three tables per step (SURVEY.md
 // A13).  Both are single streaming passes here: 16 B per lane, grid-stride, the accumulator is
 // re-zeroed in the same pass so no separate memset is needed.  HBM-bound by construction:
-// SGD 16 B/element (read p,g; write p,g), Adam 32 B/element.
+// SGD 16 B/element (read p,g; write p,g), Adam 32 B/element.  Adagrad (TF1 AdagradOptimizer; upstream OpenKE offers it, the
+// reference sends the name to SGD) reads g alone where a group's gradient is zero and moves 24 B/element elsewhere.
 #include "optim_dev.hpp"
 
 namespace kge {
@@ -19,6 +20,11 @@ __global__ __launch_bounds__(256) void sgd_kernel(SweepTables tb, float lr) {
 __global__ __launch_bounds__(256) void adam_kernel(SweepTables tb, float lr_t, float b1, float b2, float eps) {
     adam_sweep(tb.p[blockIdx.y], tb.m[blockIdx.y], tb.v[blockIdx.y], tb.g[blockIdx.y], tb.n[blockIdx.y], lr_t, b1, b2, eps,
                (long long)blockIdx.x * blockDim.x + threadIdx.x, (long long)gridDim.x * blockDim.x);
+}
+
+__global__ __launch_bounds__(256) void adagrad_kernel(SweepTables tb, float lr) {
+    adagrad_sweep(tb.p[blockIdx.y], tb.m[blockIdx.y], tb.g[blockIdx.y], tb.n[blockIdx.y], lr,
+                  (long long)blockIdx.x * blockDim.x + threadIdx.x, (long long)gridDim.x * blockDim.x);
 }
 
 static unsigned sweep_blocks(long long n) {
@@ -37,7 +43,8 @@ static int check_tables(int n_tables, float *const *p, float *const *g, float *c
         tb.p[i] = p[i]; tb.g[i] = g[i]; tb.m[i] = m ? m[i] : nullptr; tb.v[i] = v ? v[i] : nullptr;
         tb.n[i] = numel[i] > 0 ? numel[i] : 0;
         uintptr_t bits = reinterpret_cast<uintptr_t>(p[i]) | reinterpret_cast<uintptr_t>(g[i]);
-        if (m) bits |= reinterpret_cast<uintptr_t>(m[i]) | reinterpret_cast<uintptr_t>(v[i]);
+        if (m) bits |= reinterpret_cast<uintptr_t>(m[i]);
+        if (v) bits |= reinterpret_cast<uintptr_t>(v[i]);
         if (bits & 15) return fail(KGE_ERR_BAD_ARG, "tables must be 16-byte aligned");
         if (tb.n[i] > n_max) n_max = tb.n[i];
     }
@@ -68,6 +75,22 @@ int launch_adam_tables(int n_tables, float *const *p, float *const *m, float *co
     return hip_check(hipGetLastError(), "adam launch");
 }
 
+int launch_adagrad_tables(int n_tables, float *const *p, float *const *acc, float *const *g, const int64_t *numel, float lr,
+                          hipStream_t stream) {
+    if (!device_ok()) return fail(KGE_ERR_NO_DEVICE, "kge_adagrad_update: no usable HIP device");
+    if (!acc) return fail(KGE_ERR_BAD_ARG, "kge_adagrad_update_tables: null accumulator tables");
+    if (p && g && n_tables >= 1 && n_tables <= 4)
+        for (int i = 0; i < n_tables; i++)
+            if (!p[i] || !g[i] || !acc[i]) return fail(KGE_ERR_BAD_ARG, "kge_adagrad_update_tables: every table needs its gradient and its accumulator");
+    SweepTables tb;
+    long long n_max;
+    int rc = check_tables(n_tables, p, g, acc, nullptr, numel, tb, n_max, "kge_adagrad_update_tables");
+    if (rc) return rc;
+    if (n_max <= 0) return KGE_OK;
+    hipLaunchKernelGGL(adagrad_kernel, dim3(sweep_blocks(n_max), (unsigned)n_tables), dim3(256), 0, stream, tb, lr);
+    return hip_check(hipGetLastError(), "adagrad launch");
+}
+
 int launch_sgd(float *p, float *g, int64_t n, float lr, hipStream_t stream) {
     return launch_sgd_tables(1, &p, &g, &n, lr, stream);
 }
@@ -75,6 +98,10 @@ int launch_sgd(float *p, float *g, int64_t n, float lr, hipStream_t stream) {
 int launch_adam(float *p, float *m, float *v, float *g, int64_t n, float lr_t, float b1, float b2, float eps,
                 hipStream_t stream) {
     return launch_adam_tables(1, &p, &m, &v, &g, &n, lr_t, b1, b2, eps, stream);
+}
+
+int launch_adagrad(float *p, float *acc, float *g, int64_t n, float lr, hipStream_t stream) {
+    return launch_adagrad_tables(1, &p, &acc, &g, &n, lr, stream);
 }
 
 }  // namespace kge

@@ -1,5 +1,6 @@
 // Optimiser sweeps as device functions (same arithmetic for the one-launch-per-step kernels of optim.hip and for the
-// persistent multi-step launch of persist.hip): SGD p -= lr*g and TF1-semantics Adam (_apply_sparse_shared op order).
+// persistent multi-step launch of persist.hip): SGD p -= lr*g and TF1-semantics Adam (_apply_sparse_shared op order); and
+// TF1-semantics Adagrad, which the dense sweep of optim.hip and the touched-rows kernels of transe_counts.hip share.
 #pragma once
 #include "engine.hpp"
 #include "team.hpp"
@@ -8,7 +9,7 @@ namespace kge {
 
 // up to four tables per launch: blockIdx.y selects the table (one launch per optimizer step instead of one per table)
 struct SweepTables {
-    float *p[4], *g[4], *m[4], *v[4];
+    float *p[4], *g[4], *m[4], *v[4];   // Adagrad: m = the accumulators, v unused
     long long n[4];
 };
 
@@ -79,6 +80,41 @@ __device__ __forceinline__ void adam_sweep(float *__restrict__ p, float *__restr
     }
     for (long long i = (n4 << 2) + tid; i < n; i += stride) {
         adam_one(p[i], m[i], v[i], g[i], lr_t, b1, b2, eps);
+        g[i] = 0.f;
+    }
+}
+
+// TF1 AdagradOptimizer, one element: a += g*g; p -= lr * g / sqrt(a) -- no epsilon (the accumulators start at a positive value,
+// Config.adagrad_initial_accumulator).  An element with zero gradient keeps p and a bit for bit, which is the plain formula
+// wherever a > 0 and safe whatever a holds: updating only the rows a step touches IS the dense rule.  Contraction off, as above.
+__device__ __forceinline__ void adagrad_one(float &p, float &a, float g, float lr) {
+#pragma clang fp contract(off)
+    if (g != 0.f) {
+        a = add_rn(a, mul_rn(g, g));
+        p = sub_rn(p, __fdiv_rn(mul_rn(lr, g), __fsqrt_rn(a)));
+    }
+}
+
+// the dense form: 16-byte groups whose gradient is all zero are skipped (nothing of theirs changes), the gradient consumed is zeroed
+__device__ __forceinline__ void adagrad_sweep(float *__restrict__ p, float *__restrict__ a, float *__restrict__ g, long long n, float lr,
+                                              long long tid, long long stride) {
+    const long long n4 = n >> 2;
+    float4 *p4 = reinterpret_cast<float4 *>(p), *a4 = reinterpret_cast<float4 *>(a), *g4 = reinterpret_cast<float4 *>(g);
+    for (long long i = tid; i < n4; i += stride) {
+        const float4 gv = g4[i];
+        if (gv.x == 0.f && gv.y == 0.f && gv.z == 0.f && gv.w == 0.f) continue;
+        float4 pv = p4[i], av = a4[i];
+        adagrad_one(pv.x, av.x, gv.x, lr);
+        adagrad_one(pv.y, av.y, gv.y, lr);
+        adagrad_one(pv.z, av.z, gv.z, lr);
+        adagrad_one(pv.w, av.w, gv.w, lr);
+        p4[i] = pv; a4[i] = av;
+        g4[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+    for (long long i = (n4 << 2) + tid; i < n; i += stride) {
+        const float gi = g[i];
+        if (gi == 0.f) continue;
+        adagrad_one(p[i], a[i], gi, lr);
         g[i] = 0.f;
     }
 }

@@ -802,40 +802,52 @@ template <> struct RowVec<4> {
     __device__ __forceinline__ void store(float *p) const { *reinterpret_cast<float4 *>(p) = make_float4(x[0], x[1], x[2], x[3]); }
 };
 
-// where virtual row `row` (< hub_base) or hub row `q` lives: table index into AdamRows::m / v and the row's element offset
-__device__ __forceinline__ float *adam_row_ptrs(const FloatRowSpace &rs, const AdamRows &ad, bool hub, long long row, int D, float *&m, float *&v) {
+// where virtual row `row` (< hub_base) or hub row `q` lives: table index into RowRule::m / v and the row's element offset
+__device__ __forceinline__ float *adam_row_ptrs(const FloatRowSpace &rs, const RowRule &ad, bool hub, long long row, int D, float *&m, float *&v) {
     int t;
     long long r;
     if (!hub) { t = row < rs.E ? 0 : 3; r = row < rs.E ? row : row - rs.E; }
     else { t = row < rs.R ? 1 : 2; r = row < rs.R ? row : row - rs.R; }
     m = ad.m[t] + r * D;
-    v = ad.v[t] + r * D;
+    v = ad.v[t] ? ad.v[t] + r * D : nullptr;   // (Adagrad has no second table)
     return (t == 0 ? rs.g_ent : t == 1 ? rs.g_rel : t == 2 ? rs.g_auxr : rs.g_auxe) + r * D;
 }
 
-template <int L, int C, int V>
-__device__ __forceinline__ void adam_row_apply(float *p, float *m, float *v, const RowVec<V> (&g)[C], int lane, int D, const AdamRows &ad) {
+// RULE = kRuleAdam: adam_one on p, m, v.  RULE = kRuleAdagrad: adagrad_one on p and the accumulator (`m`; `v` is never touched) --
+// a group of V elements whose gradient is all zero is not written at all (its elements would keep their bits anyway).
+template <int L, int C, int V, int RULE>
+__device__ __forceinline__ void adam_row_apply(float *p, float *m, float *v, const RowVec<V> (&g)[C], int lane, int D, const RowRule &ad) {
     RowVec<V> pv[C], mv[C], vv[C];
 #pragma unroll
     for (int c = 0; c < C; c++) {
         const int e = (lane + L * c) * V;
-        if (e < D) { pv[c].load(p + e); mv[c].load(m + e); vv[c].load(v + e); }
+        if (e < D) {
+            pv[c].load(p + e); mv[c].load(m + e);
+            if constexpr (RULE == kRuleAdam) vv[c].load(v + e);
+        }
     }
 #pragma unroll
     for (int c = 0; c < C; c++) {
         const int e = (lane + L * c) * V;
         if (e < D) {
+            if constexpr (RULE == kRuleAdam) {
 #pragma unroll
-            for (int k = 0; k < V; k++) adam_one(pv[c].x[k], mv[c].x[k], vv[c].x[k], g[c].x[k], ad.lr_t, ad.b1, ad.b2, ad.eps);
-            pv[c].store(p + e); mv[c].store(m + e); vv[c].store(v + e);
+                for (int k = 0; k < V; k++) adam_one(pv[c].x[k], mv[c].x[k], vv[c].x[k], g[c].x[k], ad.lr_t, ad.b1, ad.b2, ad.eps);
+                pv[c].store(p + e); mv[c].store(m + e); vv[c].store(v + e);
+            } else {
+                bool any = false;
+#pragma unroll
+                for (int k = 0; k < V; k++) { any = any || g[c].x[k] != 0.f; adagrad_one(pv[c].x[k], mv[c].x[k], g[c].x[k], ad.lr_t); }
+                if (any) { pv[c].store(p + e); mv[c].store(m + e); }
+            }
         }
     }
 }
 
-template <int L, int C, int V>
+template <int L, int C, int V, int RULE>
 __global__ __launch_bounds__(256) void segsum_adam_runs_kernel(const float *__restrict__ rec, const int32_t *__restrict__ keys,
                                                                const int32_t *__restrict__ ids, const int32_t *__restrict__ n_valid_p,
-                                                               FloatRowSpace rs, AdamRows ad, int D, float *__restrict__ hub_sums,
+                                                               FloatRowSpace rs, RowRule ad, int D, float *__restrict__ hub_sums,
                                                                int32_t *__restrict__ hub_marks) {
     constexpr int TEAMS = 256 / L;
     const int lane = threadIdx.x % L;
@@ -871,7 +883,7 @@ __global__ __launch_bounds__(256) void segsum_adam_runs_kernel(const float *__re
         if (key < rs.hub_base) {
             float *m, *v;
             float *p = adam_row_ptrs(rs, ad, false, key, D, m, v);
-            adam_row_apply<L, C, V>(p, m, v, acc, lane, D, ad);
+            adam_row_apply<L, C, V, RULE>(p, m, v, acc, lane, D, ad);
         } else {
             float *p = hub_sums + (long long)(key - rs.hub_base) * D;
 #pragma unroll
@@ -883,9 +895,9 @@ __global__ __launch_bounds__(256) void segsum_adam_runs_kernel(const float *__re
 
 // relation-side rows: one team per row adds the copies that took a record, in copy order, applies the rule to the whole row and
 // leaves hub_sums and hub_marks zero for the next step
-template <int L, int C, int V>
+template <int L, int C, int V, int RULE>
 __global__ __launch_bounds__(256) void hub_fold_adam_kernel(float *__restrict__ hub_sums, int32_t *__restrict__ hub_marks, FloatRowSpace rs,
-                                                            AdamRows ad, int D, int K) {
+                                                            RowRule ad, int D, int K) {
     constexpr int TEAMS = 256 / L;
     const int lane = threadIdx.x % L;
     for (long long q = (long long)blockIdx.x * TEAMS + threadIdx.x / L; q < rs.hub_rows; q += (long long)gridDim.x * TEAMS) {
@@ -919,7 +931,7 @@ __global__ __launch_bounds__(256) void hub_fold_adam_kernel(float *__restrict__ 
             for (int k = 0; k < K; k++) hub_marks[(long long)k * rs.hub_rows + q] = 0;
         float *m, *v;
         float *p = adam_row_ptrs(rs, ad, true, q, D, m, v);
-        adam_row_apply<L, C, V>(p, m, v, acc, lane, D, ad);
+        adam_row_apply<L, C, V, RULE>(p, m, v, acc, lane, D, ad);
     }
 }
 
@@ -1160,18 +1172,23 @@ int ensure_hub_sums(size_t need, hipStream_t stream) {
 }
 
 // the lazy-Adam reduce of sorted float records and the fold of its hub copies, V floats per unit of a row
-template <int L, int C, int V>
-void launch_segsum_adam(int64_t M, const float *rec, const FloatRowSpace &rs, const AdamRows &ad, int D, int K, hipStream_t stream) {
+template <int L, int C, int V, int RULE>
+void launch_segsum_rule(int64_t M, const float *rec, const FloatRowSpace &rs, const RowRule &ad, int D, int K, hipStream_t stream) {
     long long nb = (M + (256 / L) - 1) / (256 / L);
     if (nb > 16384) nb = 16384;
-    hipLaunchKernelGGL((segsum_adam_runs_kernel<L, C, V>), dim3((unsigned)nb), dim3(256), 0, stream, rec, g_c.dst_sorted,
+    hipLaunchKernelGGL((segsum_adam_runs_kernel<L, C, V, RULE>), dim3((unsigned)nb), dim3(256), 0, stream, rec, g_c.dst_sorted,
                        g_c.ids_sorted, g_c.n_valid, rs, ad, D, g_c.hub_sums, g_c.hub_marks);
     if (K > 0) {
         long long nf = (rs.hub_rows + (256 / L) - 1) / (256 / L);
         if (nf > 16384) nf = 16384;
-        hipLaunchKernelGGL((hub_fold_adam_kernel<L, C, V>), dim3((unsigned)nf), dim3(256), 0, stream, g_c.hub_sums, g_c.hub_marks,
+        hipLaunchKernelGGL((hub_fold_adam_kernel<L, C, V, RULE>), dim3((unsigned)nf), dim3(256), 0, stream, g_c.hub_sums, g_c.hub_marks,
                            rs, ad, D, K);
     }
+}
+template <int L, int C, int V>
+void launch_segsum_adam(int64_t M, const float *rec, const FloatRowSpace &rs, const RowRule &ad, int D, int K, hipStream_t stream) {
+    if (ad.rule == kRuleAdagrad) launch_segsum_rule<L, C, V, kRuleAdagrad>(M, rec, rs, ad, D, K, stream);
+    else launch_segsum_rule<L, C, V, kRuleAdam>(M, rec, rs, ad, D, K, stream);
 }
 
 }  // namespace
@@ -1229,7 +1246,7 @@ int float_records_reduce(int64_t M, int D, const FloatRowSpace &rs, hipStream_t 
 
 // rs.g_* are the PARAMETER tables, ad their moments (segsum_adam_runs_kernel).  The records are the workspace's, or the caller's
 // (read through local pointers: the workspace's own are not touched).
-int float_records_reduce_adam(int64_t M, int D, const FloatRowSpace &rs, const AdamRows &ad, hipStream_t stream, const float *rec_ext,
+int float_records_reduce_adam(int64_t M, int D, const FloatRowSpace &rs, const RowRule &ad, hipStream_t stream, const float *rec_ext,
                               int32_t *dst_ext) {
     int rc;
     const bool ext = rec_ext && dst_ext;
@@ -1258,7 +1275,7 @@ int float_records_reduce_adam(int64_t M, int D, const FloatRowSpace &rs, const A
         if (!vec) launch_segsum_adam<L, C, 1>(M, rec, rs, ad, D, K, stream);
         else if constexpr (C <= 4) launch_segsum_adam<L, C, 4>(M, rec, rs, ad, D, K, stream);
     });
-    return hip_check(hipGetLastError(), "float records lazy Adam reduce launch");
+    return hip_check(hipGetLastError(), "float records row-rule reduce launch");
 }
 
 // ---- pair-count path, host side (see segsum_pairs_kernel) ----
@@ -1348,7 +1365,9 @@ __global__ __launch_bounds__(256) void apply_rows_nat_kernel(FuseArgs fz, const 
     }
 }
 
-// stage 3.  optimizer: 0 = SGD (lr), 1 = Adam (lr = lr_t)
+// stage 3.  The optimizer rule of the count path: SGD (lr), Adam (lr = lr_t; m / v = the moments), Adagrad (lr; m / m2 = the
+// accumulators, v unused; row-list form only -- the dense forms' `adam` flag of the C ABI selects between the first two)
+enum ApplyOpt : int { kOptSgd = 0, kOptAdam = 1, kOptAdagrad = 2 };
 struct ApplyArgs {
     float *p, *m, *v;
     int32_t *S;
@@ -1356,7 +1375,7 @@ struct ApplyArgs {
     long long rows;
     int D;
     float unit, lr, b1, b2, eps;
-    int adam;
+    ApplyOpt opt;
     // two tables in one launch: rows [0,E) live in p / m / v / resid, rows [E, rows) in p2 / m2 / v2 / resid2
     // sparse-row form: S is the compact [n_rows, D] image of the rows listed in row_list (same row space);
     // SGD only, no residuals
@@ -1391,10 +1410,11 @@ __device__ __forceinline__ bool apply_row_update(const Team<L, C> &tm, const App
 #pragma unroll
     for (int c = 0; c < C; c++) touched += (s[c] != 0.f || rs[c] != 0.f) ? 1.f : 0.f;
     touched = team_sum<L>(touched);
-    if (touched == 0.f && !a.adam) return false;  // SGD leaves untouched rows alone; TF1 Adam moves every row
+    if (touched == 0.f && a.opt != kOptAdam) return false;  // SGD and Adagrad leave untouched rows alone; TF1 Adam moves every row
     if (!have) {
         tm.load(table, row, x);
-        if (a.adam) { tm.load(mt, row, m_old); tm.load(vt, row, v_old); }
+        if (a.opt != kOptSgd) tm.load(mt, row, m_old);
+        if (a.opt == kOptAdam) tm.load(vt, row, v_old);
     }
     if (touched != 0.f) {
         float xn[C], inv; bool uc;
@@ -1415,7 +1435,14 @@ __device__ __forceinline__ bool apply_row_update(const Team<L, C> &tm, const App
         xnew[c] = 0.f;
         if (e >= a.D) continue;
         float pn = x[c];
-        if (a.adam) {
+        if (a.opt == kOptAdagrad) {
+            if (g[c] != 0.f) {
+                float acc = m_old[c];
+                adagrad_one(pn, acc, g[c], a.lr);
+                mt[row * a.D + e] = acc;
+                pp[e] = pn;
+            }
+        } else if (a.opt == kOptAdam) {
             float *mp = mt + row * a.D + e, *vp = vt + row * a.D + e;
             float mi = mul_rn(m_old[c], a.b1), vi = mul_rn(v_old[c], a.b2);
             if (g[c] != 0.f) {
@@ -1469,7 +1496,7 @@ __global__ __launch_bounds__(256) void apply_counts_kernel(ApplyArgs a, SamplerA
         float x[C], m_old[C], v_old[C];
         // TF1 Adam moves EVERY row: its parameter and moment rows are requested together with the counts, not after the
         // "touched?" reduction (one memory round trip per row instead of two)
-        const bool every_row = !SPARSE && a.adam;
+        const bool every_row = !SPARSE && a.opt == kOptAdam;
         if (every_row) {
             tm.load(table, row, x); tm.load(mt, row, m_old); tm.load(vt, row, v_old);
         }
@@ -1559,13 +1586,13 @@ __global__ __launch_bounds__(256) void segapply_kernel(SegApplyArgs sa) {
         const int4 sp = *reinterpret_cast<const int4 *>(sa.row_span + 2 * row);     // both lists of the row
         start8 = uni(sp.x); n8 = uni(sp.y); start2 = uni(sp.z); n2 = uni(sp.w);
         if (n8 > sa.cap || n2 > sa.cap) return;                                      // a long row: its pieces are teams of their own
-        if (n8 + n2 == 0 && (row >= ap.E || (!ap.adam && !ap.resid))) return;        // nothing to do (TF1 Adam moves record-less rows too)
+        if (n8 + n2 == 0 && (row >= ap.E || (ap.opt != kOptAdam && !ap.resid))) return;        // nothing to do (TF1 Adam moves record-less rows too)
     }
     const bool direct = !piece && row < ap.E;
     float x[C], mo[C], vo[C];
     if (direct) {                      // requested now, needed after the records
         tm.load(ap.p, row, x);
-        if (ap.adam) { tm.load(ap.m, row, mo); tm.load(ap.v, row, vo); }
+        if (ap.opt == kOptAdam) { tm.load(ap.m, row, mo); tm.load(ap.v, row, vo); }
     }
     if (sa.diag & 1) n8 = n2 = 0;
     // The record ids of both lists, requested at once with the parameter rows (lane l holds ids l, l + L, ... of a list), and
@@ -1681,7 +1708,7 @@ void launch_segsum(bool nat, int64_t M, const uint32_t *rec, const int32_t *n_va
                             n_valid_p, uidx, S, D, fold);
 }
 
-// apply_counts_kernel over a row list: row-wise SGD and lazy Adam are the same launch
+// apply_counts_kernel over a row list: row-wise SGD, lazy Adam and Adagrad are the same launch
 void launch_apply_listed_rows(const ApplyArgs &a, long long max_rows, hipStream_t stream) {
     for_transe_team_shape_or_last(a.D, [&](auto t) {
         constexpr int L = decltype(t)::L, C = decltype(t)::C;
@@ -1723,7 +1750,7 @@ namespace kge { namespace {
 // optimizer half of the fused single-process step (kge_transe_train_step_counts); null = forward only (kge_transe_forward_counts)
 struct FusedOpt {
     float *p[2], *m[2], *v[2];
-    int adam;
+    bool adam;
     float lr, b1, b2, eps;
     bool done = false;     // set where the fused kernels ran; false on return = the caller applies the image itself
 };
@@ -1797,7 +1824,7 @@ static int forward_counts_impl(const kge_model_desc *m, const float *d_ent, cons
         a.p = fo->p[0]; a.p2 = fo->p[1]; a.resid = d_resid_ent; a.resid2 = d_resid_rel;
         if (fo->adam) { a.m = fo->m[0]; a.m2 = fo->m[1]; a.v = fo->v[0]; a.v2 = fo->v[1]; }
         a.S = d_counts; a.rows = all_rows; a.row_lo = 0; a.E = m->ent_total; a.D = D;
-        a.unit = 1.0f / (float)denom; a.lr = fo->lr; a.b1 = fo->b1; a.b2 = fo->b2; a.eps = fo->eps; a.adam = fo->adam;
+        a.unit = 1.0f / (float)denom; a.lr = fo->lr; a.b1 = fo->b1; a.b2 = fo->b2; a.eps = fo->eps; a.opt = fo->adam ? kOptAdam : kOptSgd;
         a.row_span = g_c.row_span; a.span_cap = cap;
         a.inv_out = inv_table_kept(true, fo->p[0], fo->p[1], all_rows);   // (the two kernels together rewrite every row's 1/|row| entry)
         const bool shaped = for_transe_team_shape(D, [&](auto t) {
@@ -1865,7 +1892,7 @@ int kge_transe_train_step_counts_packed(const kge_model_desc *m, float *const d_
     FusedOpt fo;
     fo.p[0] = d_p[0]; fo.p[1] = d_p[1];
     fo.m[0] = adam ? d_m[0] : nullptr; fo.m[1] = adam ? d_m[1] : nullptr; fo.v[0] = adam ? d_v[0] : nullptr; fo.v[1] = adam ? d_v[1] : nullptr;
-    fo.adam = adam; fo.lr = lr; fo.b1 = beta1; fo.b2 = beta2; fo.eps = eps;
+    fo.adam = adam != 0; fo.lr = lr; fo.b1 = beta1; fo.b2 = beta2; fo.eps = eps;
     const bool fed = !sampler_shaped;     // a hand-made batch: deferral bookkeeping + the exact fp32 pass into the residual tables
     int rc = forward_counts_impl(m, d_p[0], d_p[1], d_h, d_t, d_r, n_pos, n_neg, stride, denom, d_counts, fed ? d_resid[0] : nullptr,
                                  fed ? d_resid[1] : nullptr, d_loss, stream_, &fo, fed ? nullptr : d_pack);
@@ -2016,7 +2043,7 @@ int kge_transe_apply_rows_sgd(const kge_model_desc *m, float *d_ent, float *d_re
     }
     ApplyArgs a = {};
     a.p = d_ent; a.p2 = d_rel; a.row_list = d_rows; a.S = const_cast<int32_t *>(d_row_counts); a.n_rows = d_n_rows;
-    a.E = m->ent_total; a.D = m->ent_dim; a.unit = 1.0f / (float)denom; a.lr = lr; a.adam = 0;
+    a.E = m->ent_total; a.D = m->ent_dim; a.unit = 1.0f / (float)denom; a.lr = lr; a.opt = kOptSgd;
     launch_apply_listed_rows(a, max_rows, stream);
     return hip_check(hipGetLastError(), "apply rows launch");
 }
@@ -2037,10 +2064,28 @@ int kge_transe_apply_rows_adam_lazy(const kge_model_desc *m, float *d_ent, float
     ApplyArgs a = {};
     a.p = d_ent; a.p2 = d_rel; a.m = d_m_ent; a.m2 = d_m_rel; a.v = d_v_ent; a.v2 = d_v_rel;
     a.row_list = d_rows; a.S = const_cast<int32_t *>(d_row_counts); a.n_rows = d_n_rows;
-    a.E = m->ent_total; a.D = m->ent_dim; a.unit = 1.0f / (float)denom; a.lr = lr_t; a.b1 = beta1; a.b2 = beta2; a.eps = eps; a.adam = 1;
+    a.E = m->ent_total; a.D = m->ent_dim; a.unit = 1.0f / (float)denom; a.lr = lr_t; a.b1 = beta1; a.b2 = beta2; a.eps = eps; a.opt = kOptAdam;
     a.row_live = g_lazy_row_live; g_lazy_row_live = nullptr;      // (one call only)
     launch_apply_listed_rows(a, max_rows, stream);
     return hip_check(hipGetLastError(), "lazy adam rows launch");
+}
+
+int kge_transe_apply_rows_adagrad(const kge_model_desc *m, float *d_ent, float *d_rel, float *d_acc_ent, float *d_acc_rel, const int32_t *d_rows,
+                                  const int32_t *d_row_counts, const int32_t *d_n_rows, INT max_rows, INT denom, float lr, void *stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    if (!device_ok()) return fail(KGE_ERR_NO_DEVICE, "kge_transe_apply_rows_adagrad: no usable HIP device");
+    if (!m || !d_ent || !d_rel || !d_acc_ent || !d_acc_rel || !d_rows || !d_row_counts || !d_n_rows || denom <= 0)
+        return fail(KGE_ERR_BAD_ARG, "kge_transe_apply_rows_adagrad: bad arguments");
+    if (m->model != KGE_TRANSE || m->ent_dim != m->rel_dim || m->ent_dim > 1024)
+        return fail(KGE_ERR_UNSUPPORTED, "kge_transe_apply_rows_adagrad: the sign-count path is TransE's, dim <= 1024");
+    tables_written();
+    if (max_rows <= 0) return KGE_OK;
+    ApplyArgs a = {};
+    a.p = d_ent; a.p2 = d_rel; a.m = d_acc_ent; a.m2 = d_acc_rel;
+    a.row_list = d_rows; a.S = const_cast<int32_t *>(d_row_counts); a.n_rows = d_n_rows;
+    a.E = m->ent_total; a.D = m->ent_dim; a.unit = 1.0f / (float)denom; a.lr = lr; a.opt = kOptAdagrad;
+    launch_apply_listed_rows(a, max_rows, stream);
+    return hip_check(hipGetLastError(), "adagrad rows launch");
 }
 
 int kge_transe_apply_counts(float *d_p, float *d_m, float *d_v, int32_t *d_counts, float *d_resid, int64_t rows, int32_t dim,
@@ -2052,7 +2097,7 @@ int kge_transe_apply_counts(float *d_p, float *d_m, float *d_v, int32_t *d_count
     tables_written();
     ApplyArgs a = {};
     a.p = d_p; a.m = d_m; a.v = d_v; a.S = d_counts; a.resid = d_resid; a.rows = rows; a.D = dim; a.E = rows;
-    a.unit = 1.0f / (float)denom; a.lr = lr; a.b1 = beta1; a.b2 = beta2; a.eps = eps; a.adam = adam;
+    a.unit = 1.0f / (float)denom; a.lr = lr; a.b1 = beta1; a.b2 = beta2; a.eps = eps; a.opt = adam ? kOptAdam : kOptSgd;
     const bool shaped = for_transe_team_shape(dim, [&](auto t) {
         constexpr int L = decltype(t)::L, C = decltype(t)::C;
         long long nb = (rows + (256 / L) - 1) / (256 / L);
@@ -2080,7 +2125,7 @@ int kge_transe_apply_counts_range(const kge_model_desc *m, float *const d_p[2], 
     a.p = d_p[0]; a.p2 = d_p[1]; a.resid = d_resid[0]; a.resid2 = d_resid[1];
     if (adam) { a.m = d_m[0]; a.m2 = d_m[1]; a.v = d_v[0]; a.v2 = d_v[1]; }
     a.S = d_counts_chunk; a.rows = row_hi; a.row_lo = row_lo; a.E = m->ent_total; a.D = m->ent_dim;
-    a.unit = 1.0f / (float)denom; a.lr = lr; a.b1 = beta1; a.b2 = beta2; a.eps = eps; a.adam = adam;
+    a.unit = 1.0f / (float)denom; a.lr = lr; a.b1 = beta1; a.b2 = beta2; a.eps = eps; a.opt = adam ? kOptAdam : kOptSgd;
     a.inv_out = inv_table_kept(row_lo == 0 && row_hi == all_rows, d_p[0], d_p[1], all_rows);
     for_transe_team_shape_or_last(a.D, [&](auto t) {
         constexpr int L = decltype(t)::L, C = decltype(t)::C;

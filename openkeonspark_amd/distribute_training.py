@@ -4,11 +4,11 @@ Same flags as `main_spark.py:299-324`, same `get_conf` (`distribute_training.py:
 log line (`:283`), same checkpoint discovery (`get_last_step`, `:134-156`: the step is parsed from the
 `checkpoint` text file, `model.ckpt-<step>`), one checkpoint per epoch with `max_to_keep =
 patience + 5` (`:103,226-234`), loss-based early stop with `stop.txt` (`:336-360`), new-entity growth
-on restore (`main_spark.py:74-98`: xavier rows for parameters, zero rows for the Adam slots).  One
+on restore (`main_spark.py:74-98`: xavier rows for parameters, zero rows for the Adam slots, rows of the initial value for Adagrad's accumulators).  One
 process per GPU (torchrun) replaces the ps/worker cluster; rank 0 plays the chief.
 
-A run whose entity table is sharded by row range (`--sparse_rows 1` on N ranks, SGD or LazyAdam) checkpoints without gathering
-it: every rank writes its rows -- with LazyAdam their two moment rows too -- into `model.ckpt-<step>.shard<g>of<N>.npz` beside the
+A run whose entity table is sharded by row range (`--sparse_rows 1` on N ranks, SGD, LazyAdam or Adagrad) checkpoints without gathering
+it: every rank writes its rows -- with LazyAdam their two moment rows, with Adagrad their accumulator rows too -- into `model.ckpt-<step>.shard<g>of<N>.npz` beside the
 main file.  Such a checkpoint resumes at any number of ranks or in one process, a one-process checkpoint resumes sharded, and
 new entities are grown on shards exactly as one process grows them.
 
@@ -59,7 +59,11 @@ def parse_args(argv=None):
     p.add_argument("--rel_dimension", type=int, default=0)
     p.add_argument("--ent_neg_rate", type=int, default=1)
     p.add_argument("--rel_neg_rate", type=int, default=0)
-    p.add_argument("--optimizer", type=str, default="SGD")
+    p.add_argument("--optimizer", type=str, default="SGD",
+                   help="SGD (the default, and what any other name means), Adam (TF1's AdamOptimizer: every row moves every step), "
+                        "LazyAdam (opt-in, non-parity: the Adam rule on the rows a step touches) or Adagrad (TF1's AdagradOptimizer, "
+                        "accumulators from 0.1: on the touched rows for TransE / TransH / TransD, which is exactly the dense rule; one "
+                        "accumulator table per parameter table, checkpointed as <var>/Adagrad; TransR in one process only)")
     p.add_argument("--early_stop_patience", type=int, default=5)
     p.add_argument("--early_stop_stopping_step", type=int, default=1)
     p.add_argument("--early_stop_start_step", type=int, default=1)
@@ -86,7 +90,8 @@ def parse_args(argv=None):
                                                              "and moments), TransH / TransD float records "
                                                              "applied to the parameter rows in place (SGD, or --optimizer LazyAdam: the Adam rule on the rows a step "
                                                              "touches and on their moments; tables and moments replicated across ranks).  Default: automatic for "
-                                                             "large tables; LazyAdam always takes the touched-rows update")
+                                                             "large tables; LazyAdam and Adagrad always take the touched-rows update (Adagrad's is exact: an element with zero "
+                                                             "gradient keeps its value and its accumulator, so its checkpoints hold one accumulator row per parameter row)")
     p.add_argument("--type_constrained_sampling", type=int, default=0,
                    help="1: entity negatives of a training batch come from the relation's own head / tail type list "
                         "(type_constrain.txt in --input_path, required then) instead of from all entities; same random stream, "
@@ -167,6 +172,10 @@ def checkpoint_arrays(con):
             out[name + "/Adam_1"] = v.detach().cpu().numpy()
         out["beta1_power"] = np.float32(con._beta1_power)
         out["beta2_power"] = np.float32(con._beta2_power)
+    if getattr(con, "_adagrad", False):      # TF's slot name; a shard-sized accumulator is in this rank's shard file as `adagrad`
+        for name, a in zip(con.trainModel.table_names, con._adagrad_acc):
+            if not con._sharded(name):
+                out[name + "/Adagrad"] = a.detach().cpu().numpy()
     out["global_step"] = np.int64(con.global_step)
     # with sampling one step ahead the device streams are one batch further than the training: store the states the
     # NEXT step's batch starts from, so that a resumed run trains on exactly the batches an uninterrupted one would
@@ -208,6 +217,8 @@ def save_checkpoint(con, output_path, max_to_keep=10, write=True):
                      ent_total=np.int64(con.entTotal))
         if con._has_slots:     # LazyAdam: the moment rows travel with their entity rows
             parts.update(adam=host(con._adam_m[0]), adam_1=host(con._adam_v[0]))
+        if getattr(con, "_adagrad", False):     # Adagrad: the accumulator rows do
+            parts.update(adagrad=host(con._adagrad_acc[0]))
         _atomic_savez(base + ".shard%dof%d.npz" % (con.rank, con.world_size), **parts)
         import torch.distributed as dist
         con.comm_fence("pg")
@@ -255,13 +266,13 @@ def shard_files(base, keys=("rows",)):
     return parts, ent_total
 
 
-def read_entity_rows(base, lo, hi, dim, key="rows", parts=None):
+def read_entity_rows(base, lo, hi, dim, key="rows", parts=None, fill=0.0):
     """Rows [lo, hi) of the array `key` of a sharded checkpoint -- `rows`: the entity table, `adam` / `adam_1`: its LazyAdam
-    moments -- from whichever shard files hold them (the number of ranks may differ from the run that wrote them).  Returns
-    (array of hi - lo rows, ent_total): rows at or beyond the checkpoint's entity count `ent_total` are NEW entities, left zero
-    for the caller to fill; a row below it that no shard file holds is an error (shard_files; `parts`: its result)."""
+    moments, `adagrad`: its Adagrad accumulators -- from whichever shard files hold them (the number of ranks may differ from the run that wrote them).  Returns
+    (array of hi - lo rows, ent_total): rows at or beyond the checkpoint's entity count `ent_total` are NEW entities, left at
+    `fill` (zero: for the caller to fill, or an Adam moment; an Adagrad accumulator starts at its initial value); a row below it that no shard file holds is an error (shard_files; `parts`: its result)."""
     parts, ent_total = parts if parts is not None else shard_files(base, (key,))
-    out = np.zeros((hi - lo, dim), np.float32)
+    out = np.full((hi - lo, dim), fill, np.float32)
     for path, plo, phi in parts:
         a, b = max(lo, plo), min(hi, phi, ent_total)
         if a < b:
@@ -270,16 +281,29 @@ def read_entity_rows(base, lo, hi, dim, key="rows", parts=None):
     return out, ent_total
 
 
-def grow_table(table, rows, rng, zeros=False):
+def slot_keys(z, adam_slots, adagrad):
+    """Which arrays a shard file must hold beside `rows` for a run with these optimizer slots resuming the checkpoint whose main
+    file is `z`: the two moment arrays where an Adam-family run resumes an Adam-family checkpoint (it has `beta1_power`), the
+    accumulator where an Adagrad run resumes an Adagrad checkpoint (its replicated tables have `<var>/Adagrad`).  Anything else
+    -- an SGD checkpoint, or slots the new run has no use for -- reads the rows alone: the run starts from fresh slots."""
+    keys = ("rows",)
+    if adam_slots and "beta1_power" in z:
+        keys += ("adam", "adam_1")
+    if adagrad and any(k.endswith("/Adagrad") for k in z):
+        keys += ("adagrad",)
+    return keys
+
+
+def grow_table(table, rows, rng, zeros=False, fill=0.0):
     """Append rows for new entities (main_spark.py:74-98): xavier-initialised for a parameter table,
-    zeros for an Adam slot.  The reference draws the WHOLE [final rows, dim] variable with the xavier
+    zeros for an Adam slot, `fill` (with zeros=True) for an Adagrad accumulator, whose rows start at its initial value.  The reference draws the WHOLE [final rows, dim] variable with the xavier
     initializer (main_spark.py:78) and keeps its tail, so the new rows' stddev is sqrt(2.6/(rows+dim))
     with rows = the final row count, not the number of appended rows."""
     table = np.asarray(table, dtype=np.float32)
     extra = rows - table.shape[0]
     if extra <= 0:
         return table
-    new = (np.zeros((extra, table.shape[1]), np.float32) if zeros
+    new = (np.full((extra, table.shape[1]), fill, np.float32) if zeros
            else xavier_normal(rng, (extra, table.shape[1]), fan_in=rows))
     return np.concatenate([table, new], axis=0)
 
@@ -295,15 +319,27 @@ def _set_slots(con, i, name, m, v):
             slots[i].copy_(torch.from_numpy(full))
 
 
+def _set_accumulator(con, i, name, acc):
+    """Adagrad accumulator of table i from a whole-table array; a sharded entity table keeps its rows [lo, hi)."""
+    import torch
+    if con._sharded(name):
+        lo, hi = con._shard["lo"], con._shard["hi"]
+        con._adagrad_acc[i][:hi - lo].copy_(torch.from_numpy(np.ascontiguousarray(acc[lo:hi])))
+    else:
+        con._adagrad_acc[i].copy_(torch.from_numpy(np.ascontiguousarray(acc.reshape(tuple(con._adagrad_acc[i].shape)))))
+
+
 def _restore_sharded_rows(con, i, name, base, z, rows, dim, allow_growth, rng):
     """Table i (the entity table) from the shard files of a sharded checkpoint, into this rank's shard [lo, hi) of the new run or,
     in one process, whole.  Rows of entities the checkpoint does not know are grown as one process grows them (grow_table):
     every rank draws the same xavier block for rows [ent_total, rows) from `rng` and keeps its own part; their moments are zero.
     An Adam-family checkpoint (it has `beta1_power`) resumed with slots must carry the moment rows in its shard files; an SGD
-    checkpoint resumed with slots starts from zero moments."""
+    checkpoint resumed with slots starts from zero moments.  Adagrad alike (slot_keys): its accumulator rows come from the shard
+    files' `adagrad`, new entities' rows -- and every row, from a checkpoint without accumulators -- hold the initial value."""
     import torch
-    moments = con._has_slots and "beta1_power" in z
-    parts = shard_files(base, ("rows", "adam", "adam_1") if moments else ("rows",))
+    adagrad = getattr(con, "_adagrad", False)
+    keys = slot_keys(z, con._has_slots, adagrad)
+    parts = shard_files(base, keys)
     ent_total = parts[1]
     if rows != ent_total and (not allow_growth or rows < ent_total):
         raise ValueError("checkpoint table %s has %d rows, model needs %d" % (name, ent_total, rows))
@@ -311,8 +347,16 @@ def _restore_sharded_rows(con, i, name, base, z, rows, dim, allow_growth, rng):
     lo, hi = (con._shard["lo"], con._shard["hi"]) if con._sharded(name) else (0, rows)
     if hi <= lo:
         return
-    for key, dst in (("rows", con._tables[i]),) + ((("adam", con._adam_m[i]), ("adam_1", con._adam_v[i])) if moments else ()):
-        part, _ = read_entity_rows(base, lo, hi, dim, key, parts)
+    dsts = dict(rows=con._tables[i])
+    if "adam" in keys:
+        dsts.update(adam=con._adam_m[i], adam_1=con._adam_v[i])
+    if "adagrad" in keys:
+        dsts.update(adagrad=con._adagrad_acc[i])
+    elif adagrad:
+        con._adagrad_acc[i].fill_(float(con.adagrad_initial_accumulator))
+    for key, dst in dsts.items():
+        part, _ = read_entity_rows(base, lo, hi, dim, key, parts,
+                                   fill=float(con.adagrad_initial_accumulator) if key == "adagrad" else 0.0)
         if key == "rows" and new is not None and hi > ent_total:
             a = max(lo, ent_total)
             part[a - lo:] = new[a - ent_total:hi - ent_total]
@@ -347,6 +391,11 @@ def restore_checkpoint(con, path, allow_growth=True, arrays=None):
         if con._has_slots and name + "/Adam" in z:
             _set_slots(con, i, name, grow_table(z[name + "/Adam"], rows, rng, zeros=True),
                        grow_table(z[name + "/Adam_1"], rows, rng, zeros=True))
+        if getattr(con, "_adagrad", False):      # absent (an SGD checkpoint, say): fresh accumulators
+            a0 = float(con.adagrad_initial_accumulator)
+            acc = grow_table(z[name + "/Adagrad"], rows, rng, zeros=True, fill=a0) if name + "/Adagrad" in z else \
+                np.full((rows, shapes[name][1]), a0, np.float32)
+            _set_accumulator(con, i, name, acc)
     if con._has_slots and "beta1_power" in z:
         con._beta1_power = np.float32(z["beta1_power"])
         con._beta2_power = np.float32(z["beta2_power"])

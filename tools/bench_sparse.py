@@ -25,8 +25,9 @@ def main():
     ap.add_argument("--dense", action="store_true", help="dense count image instead of the sparse-row path")
     ap.add_argument("--force-dp", action="store_true", help="one-rank RCCL group + Config.force_data_parallel: the table-sharded multi-GPU step, every exchange a copy")
     ap.add_argument("--model", default="TransE", help="TransE | TransH | TransD (the latter two: --dense = gradient tables + sweep, else the row-wise "
-                                                      "update in place from float records: SGD, or with --opt LazyAdam the Adam rule on the touched rows)")
-    ap.add_argument("--opt", default="SGD", help="SGD | Adam (TF1 dense sweep, parity; implies --dense) | LazyAdam (touched rows only, NON-PARITY)")
+                                                      "update in place from float records: SGD, or with --opt LazyAdam / Adagrad that rule on the touched rows)")
+    ap.add_argument("--opt", default="SGD", help="SGD | Adam (TF1 dense sweep, parity; implies --dense) | LazyAdam (touched rows only, NON-PARITY) | "
+                                             "Adagrad (TF1 AdagradOptimizer on the touched rows: exact)")
     a = ap.parse_args()
     import numpy as np
     import torch
@@ -81,6 +82,7 @@ def main():
         a.entities // 1_000_000, a.triples // 1_000_000, a.model, a.dim, a.opt, a.neg,
         ("dense image / gradient tables + sweep" if (a.dense or a.opt == "Adam") else
          "sparse rows: lazy Adam in place from float records" if (con.sparse_inplace and con._lazy_adam) else
+         "sparse rows: Adagrad in place from float records" if (con.sparse_inplace and con._adagrad) else
          "sparse rows: SGD in place from float records" if con.sparse_inplace else "sparse rows") +
         (", data-parallel step on a one-rank RCCL group" if a.force_dp and con.sparse_inplace else
          ", table-sharded step on a one-rank RCCL group" if a.force_dp else "")),
