@@ -39,16 +39,6 @@ bool device_ok() {
     return e.device_state > 0;
 }
 
-template <typename T>
-static int upload(T *&dst, const void *src, size_t count, const char *what) {
-    if (dst) { (void)hipFree(dst); dst = nullptr; }
-    size_t bytes = sizeof(T) * (count ? count : 1);
-    int rc = hip_check(hipMalloc(&dst, bytes), what);
-    if (rc) return rc;
-    if (count) rc = hip_check(hipMemcpy(dst, src, sizeof(T) * count, hipMemcpyHostToDevice), what);
-    return rc;
-}
-
 int ensure_device_index() {
     Engine &e = engine();
     if (!e.index.loaded) return fail(KGE_ERR_NO_DATASET, "no training set imported (importTrainFiles / kge_import_train_arrays)");
@@ -56,20 +46,20 @@ int ensure_device_index() {
     int rc = KGE_OK;
     if (!e.dev.uploaded) {
         const KgIndex &ix = e.index;
-        if ((rc = upload(e.dev.pos, ix.pos.data(), ix.pos.size(), "upload pos"))) return rc;
-        if ((rc = upload(e.dev.grp, ix.grp.data(), ix.grp.size(), "upload grp"))) return rc;
-        if ((rc = upload(e.dev.ht, ix.ht.data(), ix.ht.size(), "upload ht"))) return rc;
-        if ((rc = upload(e.dev.tails_hr, ix.tails_hr.data(), ix.tails_hr.size(), "upload tails"))) return rc;
-        if ((rc = upload(e.dev.heads_tr, ix.heads_tr.data(), ix.heads_tr.size(), "upload heads"))) return rc;
-        if ((rc = upload(e.dev.rels_ht, ix.rels_ht.data(), ix.rels_ht.size(), "upload rels"))) return rc;
-        if ((rc = upload(e.dev.bern_prob, ix.bern_prob.data(), ix.bern_prob.size(), "upload bern"))) return rc;
+        if ((rc = e.dev.pos.upload(ix.pos, "upload pos"))) return rc;
+        if ((rc = e.dev.grp.upload(ix.grp, "upload grp"))) return rc;
+        if ((rc = e.dev.ht.upload(ix.ht, "upload ht"))) return rc;
+        if ((rc = e.dev.tails_hr.upload(ix.tails_hr, "upload tails"))) return rc;
+        if ((rc = e.dev.heads_tr.upload(ix.heads_tr, "upload heads"))) return rc;
+        if ((rc = e.dev.rels_ht.upload(ix.rels_ht, "upload rels"))) return rc;
+        if ((rc = e.dev.bern_prob.upload(ix.bern_prob, "upload bern"))) return rc;
         e.dev.uploaded = true;
     }
     if (!e.dev.tables_uploaded) {
         const KgIndex &ix = e.index;
-        if ((rc = upload(e.dev.jump_digits, e.jump_digits.data(), e.jump_digits.size(), "upload jump digits"))) return rc;
-        if ((rc = upload(e.dev.ent_magic, ix.ent_magic.data(), ix.ent_magic.size(), "upload entity moduli"))) return rc;
-        if ((rc = upload(e.dev.rel_magic, ix.rel_magic.data(), ix.rel_magic.size(), "upload relation moduli"))) return rc;
+        if ((rc = e.dev.jump_digits.upload(e.jump_digits, "upload jump digits"))) return rc;
+        if ((rc = e.dev.ent_magic.upload(ix.ent_magic, "upload entity moduli"))) return rc;
+        if ((rc = e.dev.rel_magic.upload(ix.rel_magic, "upload relation moduli"))) return rc;
         e.dev.tables_uploaded = true;
     }
     if ((int64_t)e.streams.size() != e.work_threads) {
@@ -78,14 +68,10 @@ int ensure_device_index() {
         e.dev.streams_sync = 0;
     }
     if (e.dev.streams_sync == 0) {
-        if (e.dev.streams_cap < e.work_threads) {
-            uint64_t *base = e.dev.streams < e.dev.streams_next ? e.dev.streams : e.dev.streams_next;   // one allocation, two halves
-            if (base) (void)hipFree(base);
-            e.dev.streams = e.dev.streams_next = nullptr;
-            if ((rc = hip_check(hipMalloc(&e.dev.streams, sizeof(uint64_t) * 2 * (size_t)e.work_threads), "alloc streams"))) return rc;
-            e.dev.streams_next = e.dev.streams + e.work_threads;
-            e.dev.streams_cap = e.work_threads;
-        }
+        bool grew;
+        rc = e.dev.streams_buf.reserve(2 * e.work_threads, "alloc streams", &grew);
+        if (grew) { e.dev.streams = e.dev.streams_buf; e.dev.streams_next = rc ? nullptr : e.dev.streams + e.work_threads; }   // (both null after a failure)
+        if (rc) return rc;
         if ((rc = hip_check(hipMemcpy(e.dev.streams, e.streams.data(), sizeof(uint64_t) * (size_t)e.work_threads,
                                       hipMemcpyHostToDevice), "upload streams"))) return rc;
         e.dev.streams_sync = 1;
@@ -114,12 +100,12 @@ int ensure_typed_index() {
     if (e.dev.typed_uploaded) return KGE_OK;
     if (!device_ok()) return fail(KGE_ERR_NO_DEVICE, "no usable HIP device: the sampler has no CPU fallback");
     const KgIndex &ix = e.index;
-    if ((rc = upload(e.dev.typed_len, ix.typed_len.data(), ix.typed_len.size(), "upload typed lengths"))) return rc;
-    if ((rc = upload(e.dev.type_bounds, ix.type_bounds.data(), ix.type_bounds.size(), "upload type bounds"))) return rc;
-    if ((rc = upload(e.dev.type_tails, ix.type_tails.data(), ix.type_tails.size(), "upload tail type lists"))) return rc;
-    if ((rc = upload(e.dev.type_heads, ix.type_heads.data(), ix.type_heads.size(), "upload head type lists"))) return rc;
-    if ((rc = upload(e.dev.typed_pos_hr, ix.typed_pos_hr.data(), ix.typed_pos_hr.size(), "upload typed positions"))) return rc;
-    if ((rc = upload(e.dev.typed_pos_tr, ix.typed_pos_tr.data(), ix.typed_pos_tr.size(), "upload typed positions"))) return rc;
+    if ((rc = e.dev.typed_len.upload(ix.typed_len, "upload typed lengths"))) return rc;
+    if ((rc = e.dev.type_bounds.upload(ix.type_bounds, "upload type bounds"))) return rc;
+    if ((rc = e.dev.type_tails.upload(ix.type_tails, "upload tail type lists"))) return rc;
+    if ((rc = e.dev.type_heads.upload(ix.type_heads, "upload head type lists"))) return rc;
+    if ((rc = e.dev.typed_pos_hr.upload(ix.typed_pos_hr, "upload typed positions"))) return rc;
+    if ((rc = e.dev.typed_pos_tr.upload(ix.typed_pos_tr, "upload typed positions"))) return rc;
     e.dev.typed_uploaded = true;
     return KGE_OK;
 }
@@ -227,19 +213,13 @@ void sampling(INT *batch_h, INT *batch_t, INT *batch_r, REAL *batch_y, INT batch
     if (ensure_device_index()) return;
     if (batchSize <= 0 || negRate < 0 || negRelRate < 0) { set_error("sampling: bad sizes"); return; }
     const int64_t total = batchSize * (1 + negRate + negRelRate);
-    if (e.dev.stage_cap < total) {
-        if (e.dev.stage_i32) (void)hipFree(e.dev.stage_i32);
-        if (e.dev.stage_i64) (void)hipFree(e.dev.stage_i64);
-        e.dev.stage_i32 = nullptr; e.dev.stage_i64 = nullptr; e.dev.stage_cap = 0;
-        if (hip_check(hipMalloc(&e.dev.stage_i32, sizeof(int32_t) * 3 * (size_t)total), "alloc stage")) return;
-        if (hip_check(hipMalloc(&e.dev.stage_i64, (sizeof(int64_t) * 3 + sizeof(float)) * (size_t)total), "alloc stage")) return;
-        e.dev.stage_cap = total;
-    }
+    if (e.dev.stage_i32.reserve(3 * total, "alloc stage")) return;
+    if (e.dev.stage_i64.reserve((int64_t)(sizeof(int64_t) * 3 + sizeof(float)) * total, "alloc stage")) return;
     int32_t *s = e.dev.stage_i32;
     // stage arrays are packed at `total` so the widen kernel can address them as [3][total]
     if (launch_sampler(s, s + total, s + 2 * total, batchSize, negRate, negRelRate, 0, e.work_threads, batchSize, nullptr, nullptr)) return;
-    if (launch_widen(s, e.dev.stage_i64, batchSize, total, nullptr)) return;
-    const int64_t *w = e.dev.stage_i64;
+    int64_t *w = reinterpret_cast<int64_t *>(e.dev.stage_i64.ptr());
+    if (launch_widen(s, w, batchSize, total, nullptr)) return;
     if (hip_check(hipMemcpy(batch_h, w, sizeof(int64_t) * total, hipMemcpyDeviceToHost), "copy batch_h")) return;
     if (hip_check(hipMemcpy(batch_t, w + total, sizeof(int64_t) * total, hipMemcpyDeviceToHost), "copy batch_t")) return;
     if (hip_check(hipMemcpy(batch_r, w + 2 * total, sizeof(int64_t) * total, hipMemcpyDeviceToHost), "copy batch_r")) return;

@@ -13,36 +13,35 @@
 #include <vector>
 
 #include "../../include/kge_mi355.h"
+#include "dev_buf.hpp"
 #include "kg_index.hpp"
 
 namespace kge {
 
 struct DeviceIndex {
     bool uploaded = false;
-    int4 *pos = nullptr;      // [train_dup]
-    int4 *grp = nullptr;      // [train_dup]
-    int2 *ht = nullptr;       // [train_dup]
-    int32_t *tails_hr = nullptr, *heads_tr = nullptr, *rels_ht = nullptr;  // [train_uniq]
-    float *bern_prob = nullptr;                                            // [rel_total]
+    DevBuf<int4> pos, grp;    // [train_dup]
+    DevBuf<int2> ht;          // [train_dup]
+    DevBuf<int32_t> tails_hr, heads_tr, rels_ht;  // [train_uniq]
+    DevBuf<float> bern_prob;                      // [rel_total]
     // the sampler's tables (ensure_device_index): Engine::jump_digits, KgIndex::ent_magic / rel_magic
     bool tables_uploaded = false;
-    LcgAffine *jump_digits = nullptr;
-    uint64_t *ent_magic = nullptr, *rel_magic = nullptr;   // [sampler_magic_len] each
-    uint64_t *streams = nullptr;                                           // [work_threads]: the CURRENT states
-    uint64_t *streams_next = nullptr;   // the other half of the same allocation: the sampler writes the advanced states there, then the two swap
-    int64_t streams_cap = 0;
+    DevBuf<LcgAffine> jump_digits;
+    DevBuf<uint64_t> ent_magic, rel_magic;   // [sampler_magic_len] each
+    DevBuf<uint64_t> streams_buf;            // [2 * work_threads]: one allocation, two halves
+    uint64_t *streams = nullptr;             // [work_threads]: the half with the CURRENT states
+    uint64_t *streams_next = nullptr;        // the other half: the sampler writes the advanced states there, then the two swap
     int streams_sync = 0;  // 0: host copy newer (upload before use), 1: in sync, 2: device copy newer
     // staging for the Base.so-compatible host-buffer `sampling`
-    int32_t *stage_i32 = nullptr;    // 3 * cap int32
-    int64_t *stage_i64 = nullptr;    // 3 * cap int64 followed by cap floats
-    int64_t stage_cap = 0;
-    float *loss_partials = nullptr;  // per-block partial losses
-    unsigned *loss_ticket = nullptr; // blocks-done counter: the last block of a forward/backward kernel adds the partials
+    DevBuf<int32_t> stage_i32;    // 3 * total int32
+    DevBuf<char> stage_i64;       // 3 * total int64 followed by total floats
+    DevBuf<float> loss_partials;  // per-block partial losses
+    DevBuf<unsigned> loss_ticket; // blocks-done counter: the last block of a forward/backward kernel adds the partials
     // type-constrained sampling: device copies of KgIndex's typed arrays (ensure_typed_index)
     bool typed_uploaded = false;
-    int2 *typed_len = nullptr;
-    int4 *type_bounds = nullptr;
-    int32_t *type_tails = nullptr, *type_heads = nullptr, *typed_pos_hr = nullptr, *typed_pos_tr = nullptr;
+    DevBuf<int2> typed_len;
+    DevBuf<int4> type_bounds;
+    DevBuf<int32_t> type_tails, type_heads, typed_pos_hr, typed_pos_tr;
 };
 
 struct Engine {
@@ -76,8 +75,7 @@ struct Engine {
     // inv_for_ent / inv_for_rel -- set by the pre-pass, kept by the full-table apply kernel
     // (which rewrites the entry of every row it changes), cleared by every other entry point that writes tables and by
     // kge_set_option("tables_changed") for writes the library cannot see (Config.set_parameters, restore, all-gathers)
-    float *inv_norm = nullptr;
-    int64_t inv_cap = 0;
+    DevBuf<float> inv_norm;
     const float *inv_for_ent = nullptr, *inv_for_rel = nullptr;
     int inv_valid = 0;
     int32_t *loss_limbs = nullptr;   // kge_loss_limbs_target: where the TransE emit kernel also writes its loss as limbs (null = nowhere)
@@ -139,7 +137,6 @@ int ensure_typed_host_index();   // the host part alone (no device needed)
 // eval.hip: the imported relation type lists (importTypeFiles), false when none are
 struct TypeListsHost { const std::vector<int32_t> *head_lef, *head_rig, *head_type, *tail_lef, *tail_rig, *tail_type; };
 bool eval_type_lists_host(TypeListsHost &v);
-int hip_check(hipError_t e, const char *what);
 
 constexpr int kMaxLossBlocks = 4096;
 

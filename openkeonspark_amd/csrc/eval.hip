@@ -29,15 +29,17 @@ struct EvalHost {
 
 struct EvalDev {
     bool uploaded = false;
-    int4 *test = nullptr, *all = nullptr, *all_t = nullptr;   // all_t: the same triples as (t,r,h,0) sorted by (t,r,h)
-    int4 *all_ht = nullptr;       // ... and as (h,t,r,0) sorted by (h,t,r) (relation prediction's filter)
-    int32_t *head_lef = nullptr, *head_rig = nullptr, *tail_lef = nullptr, *tail_rig = nullptr, *head_type = nullptr, *tail_type = nullptr;
-    int32_t *sup_lef = nullptr, *sup_rig = nullptr, *sub_lef = nullptr, *sub_rig = nullptr, *sup_type = nullptr, *sub_type = nullptr;
-    float *scores = nullptr;      // staging for testHead/testTail and kge_link_prediction
-    int64_t scores_cap = 0;
-    int32_t *cand = nullptr;      // 3 * cap candidate ids
-    long long *out = nullptr;     // 8 * requests
-    int64_t out_cap = 0;
+    DevBuf<int4> test, all, all_t;   // all_t: the same triples as (t,r,h,0) sorted by (t,r,h)
+    DevBuf<int4> all_ht;             // ... and as (h,t,r,0) sorted by (h,t,r) (relation prediction's filter)
+    DevBuf<int32_t> head_lef, head_rig, tail_lef, tail_rig, head_type, tail_type;
+    DevBuf<int32_t> sup_lef, sup_rig, sub_lef, sub_rig, sup_type, sub_type;
+    DevBuf<float> scores;         // staging for testHead/testTail and kge_link_prediction
+    DevBuf<int32_t> cand;         // link_prediction_v1: [3][requests x E] candidate ids
+    DevBuf<long long> out;        // 8 * requests
+    DevBuf<int32_t> req_one;      // testHead/testTail: (test index, head flag)
+    DevBuf<int32_t> req_v1;       // link_prediction_v1: [2][64] test index, head flag
+    DevBuf<int32_t> req;          // kge_link_prediction: [3][requests] test index, head flag, fixed entity
+    DevBuf<float> T, P;           // kge_link_prediction: the relation's candidate table, TransR's projections
 };
 
 static EvalHost g_eh;
@@ -49,16 +51,6 @@ static std::vector<int32_t> g_valid_lef, g_valid_rig, g_test_lef, g_test_rig;
 // bumped by every importTestFiles: tclass.hip keeps device copies of the four range arrays for as long as it stands
 static uint64_t g_tc_generation = 0;
 
-template <typename T, typename V>
-static int up(T *&dst, const std::vector<V> &src, const char *what) {
-    static_assert(sizeof(T) == sizeof(V), "size mismatch");
-    if (dst) { (void)hipFree(dst); dst = nullptr; }
-    int rc = hip_check(hipMalloc(&dst, sizeof(T) * (src.size() ? src.size() : 1)), what);
-    if (rc) return rc;
-    if (!src.empty()) rc = hip_check(hipMemcpy(dst, src.data(), sizeof(T) * src.size(), hipMemcpyHostToDevice), what);
-    return rc;
-}
-
 static int ensure_eval_device() {
     if (!g_eh.loaded) return fail(KGE_ERR_NO_DATASET, "importTestFiles has not been called");
     if (!device_ok()) return fail(KGE_ERR_NO_DEVICE, "no usable HIP device: the ranker has no CPU fallback");
@@ -67,34 +59,34 @@ static int ensure_eval_device() {
     const int64_t E = engine().index.ent_total, R = engine().index.rel_total;
     if (g_eh.head_lef.empty()) { g_eh.head_lef.assign(R, 0); g_eh.head_rig.assign(R, 0); g_eh.tail_lef.assign(R, 0); g_eh.tail_rig.assign(R, 0); }
     if (g_eh.sup_lef.empty()) { g_eh.sup_lef.assign(E, 0); g_eh.sup_rig.assign(E, 0); g_eh.sub_lef.assign(E, 0); g_eh.sub_rig.assign(E, 0); }
-    if ((rc = up(g_ed.test, g_eh.test, "upload test"))) return rc;
-    if ((rc = up(g_ed.all, g_eh.all, "upload triples"))) return rc;
+    if ((rc = g_ed.test.upload(g_eh.test, "upload test"))) return rc;
+    if ((rc = g_ed.all.upload(g_eh.all, "upload triples"))) return rc;
     {   // second order for head requests: the known heads of a (t, r) pair are then contiguous
         std::vector<Int4> by_tail(g_eh.all.size());
         for (size_t i = 0; i < by_tail.size(); i++) by_tail[i] = Int4{g_eh.all[i].z, g_eh.all[i].y, g_eh.all[i].x, 0};
         std::sort(by_tail.begin(), by_tail.end(), [](const Int4 &a, const Int4 &b) {
             if (a.x != b.x) return a.x < b.x; if (a.y != b.y) return a.y < b.y; return a.z < b.z; });
-        if ((rc = up(g_ed.all_t, by_tail, "upload triples by tail"))) return rc;
+        if ((rc = g_ed.all_t.upload(by_tail, "upload triples by tail"))) return rc;
     }
     {   // third order for relation prediction: the known relations of an (h, t) pair are then contiguous
         std::vector<Int4> by_pair(g_eh.all.size());
         for (size_t i = 0; i < by_pair.size(); i++) by_pair[i] = Int4{g_eh.all[i].x, g_eh.all[i].z, g_eh.all[i].y, 0};
         std::sort(by_pair.begin(), by_pair.end(), [](const Int4 &a, const Int4 &b) {
             if (a.x != b.x) return a.x < b.x; if (a.y != b.y) return a.y < b.y; return a.z < b.z; });
-        if ((rc = up(g_ed.all_ht, by_pair, "upload triples by pair"))) return rc;
+        if ((rc = g_ed.all_ht.upload(by_pair, "upload triples by pair"))) return rc;
     }
-    if ((rc = up(g_ed.head_lef, g_eh.head_lef, "upload types"))) return rc;
-    if ((rc = up(g_ed.head_rig, g_eh.head_rig, "upload types"))) return rc;
-    if ((rc = up(g_ed.tail_lef, g_eh.tail_lef, "upload types"))) return rc;
-    if ((rc = up(g_ed.tail_rig, g_eh.tail_rig, "upload types"))) return rc;
-    if ((rc = up(g_ed.head_type, g_eh.head_type, "upload types"))) return rc;
-    if ((rc = up(g_ed.tail_type, g_eh.tail_type, "upload types"))) return rc;
-    if ((rc = up(g_ed.sup_lef, g_eh.sup_lef, "upload ontology"))) return rc;
-    if ((rc = up(g_ed.sup_rig, g_eh.sup_rig, "upload ontology"))) return rc;
-    if ((rc = up(g_ed.sub_lef, g_eh.sub_lef, "upload ontology"))) return rc;
-    if ((rc = up(g_ed.sub_rig, g_eh.sub_rig, "upload ontology"))) return rc;
-    if ((rc = up(g_ed.sup_type, g_eh.sup_type, "upload ontology"))) return rc;
-    if ((rc = up(g_ed.sub_type, g_eh.sub_type, "upload ontology"))) return rc;
+    if ((rc = g_ed.head_lef.upload(g_eh.head_lef, "upload types"))) return rc;
+    if ((rc = g_ed.head_rig.upload(g_eh.head_rig, "upload types"))) return rc;
+    if ((rc = g_ed.tail_lef.upload(g_eh.tail_lef, "upload types"))) return rc;
+    if ((rc = g_ed.tail_rig.upload(g_eh.tail_rig, "upload types"))) return rc;
+    if ((rc = g_ed.head_type.upload(g_eh.head_type, "upload types"))) return rc;
+    if ((rc = g_ed.tail_type.upload(g_eh.tail_type, "upload types"))) return rc;
+    if ((rc = g_ed.sup_lef.upload(g_eh.sup_lef, "upload ontology"))) return rc;
+    if ((rc = g_ed.sup_rig.upload(g_eh.sup_rig, "upload ontology"))) return rc;
+    if ((rc = g_ed.sub_lef.upload(g_eh.sub_lef, "upload ontology"))) return rc;
+    if ((rc = g_ed.sub_rig.upload(g_eh.sub_rig, "upload ontology"))) return rc;
+    if ((rc = g_ed.sup_type.upload(g_eh.sup_type, "upload ontology"))) return rc;
+    if ((rc = g_ed.sub_type.upload(g_eh.sub_type, "upload ontology"))) return rc;
     g_ed.uploaded = true;
     return KGE_OK;
 }
@@ -245,13 +237,7 @@ __global__ void candidates_kernel(const int4 *__restrict__ test, const int32_t *
 static int rank_requests(const float *d_scores, const std::vector<int32_t> &index, const std::vector<int32_t> &head,
                          long long *h_out, hipStream_t stream, const int32_t *d_req_index, const int32_t *d_req_head) {
     const int n = (int)index.size();
-    if (g_ed.out_cap < n) {
-        if (g_ed.out) (void)hipFree(g_ed.out);
-        g_ed.out = nullptr;
-        int rc = hip_check(hipMalloc(&g_ed.out, sizeof(long long) * 8 * (size_t)n), "alloc rank out");
-        if (rc) return rc;
-        g_ed.out_cap = n;
-    }
+    { int rc = g_ed.out.reserve(8 * (int64_t)n, "alloc rank out"); if (rc) return rc; }
     RankArgs a;
     a.scores = d_scores; a.test = g_ed.test; a.all = g_ed.all; a.all_t = g_ed.all_t; a.n_all = (long long)g_eh.all.size();
     a.head_lef = g_ed.head_lef; a.head_rig = g_ed.head_rig; a.tail_lef = g_ed.tail_lef; a.tail_rig = g_ed.tail_rig;
@@ -389,14 +375,9 @@ static INT *rank_one_host_scores(INT index, REAL *con, int head) {
     if (ensure_eval_device()) return (INT *)out;
     if (index < 0 || index >= g_eh.test_total) { set_error("testHead/testTail: index out of range"); return (INT *)out; }
     const int64_t E = engine().index.ent_total;
-    if (g_ed.scores_cap < E) {
-        if (g_ed.scores) (void)hipFree(g_ed.scores);
-        g_ed.scores = nullptr;
-        if (hip_check(hipMalloc(&g_ed.scores, sizeof(float) * (size_t)E), "alloc scores")) return (INT *)out;
-        g_ed.scores_cap = E;
-    }
-    static int32_t *d_req = nullptr;
-    if (!d_req && hip_check(hipMalloc(&d_req, sizeof(int32_t) * 2), "alloc req")) return (INT *)out;
+    if (g_ed.scores.reserve(E, "alloc scores")) return (INT *)out;
+    if (g_ed.req_one.reserve(2, "alloc req")) return (INT *)out;
+    int32_t *d_req = g_ed.req_one;
     int32_t req[2] = {(int32_t)index, head};
     if (hip_check(hipMemcpy(g_ed.scores, con, sizeof(float) * (size_t)E, hipMemcpyHostToDevice), "upload scores")) return (INT *)out;
     if (hip_check(hipMemcpy(d_req, req, sizeof(req), hipMemcpyHostToDevice), "upload req")) return (INT *)out;
@@ -608,18 +589,10 @@ static int link_prediction_v1(const kge_model_desc *m, const float *const tables
     const int64_t E = m->ent_total;
     const int sides = test_head ? 2 : 1;
     const int max_req = m->model == KGE_TRANSR ? 1 : 32;   // TransR's predict uses ONE matrix per call (TransR.py:83)
-    if (g_ed.scores_cap < (int64_t)max_req * E) {
-        if (g_ed.scores) (void)hipFree(g_ed.scores);
-        if (g_ed.cand) (void)hipFree(g_ed.cand);
-        g_ed.scores = nullptr; g_ed.cand = nullptr;
-        if ((rc = hip_check(hipMalloc(&g_ed.scores, sizeof(float) * (size_t)max_req * E), "alloc scores"))) return rc;
-        if ((rc = hip_check(hipMalloc(&g_ed.cand, sizeof(int32_t) * 3 * (size_t)max_req * E), "alloc candidates"))) return rc;
-        g_ed.scores_cap = (int64_t)max_req * E;
-    } else if (!g_ed.cand) {
-        if ((rc = hip_check(hipMalloc(&g_ed.cand, sizeof(int32_t) * 3 * (size_t)g_ed.scores_cap), "alloc candidates"))) return rc;
-    }
-    static int32_t *d_req = nullptr;
-    if (!d_req && (rc = hip_check(hipMalloc(&d_req, sizeof(int32_t) * 2 * 64), "alloc req"))) return rc;
+    if ((rc = g_ed.scores.reserve(max_req * E, "alloc scores"))) return rc;
+    if ((rc = g_ed.cand.reserve(3 * max_req * E, "alloc candidates"))) return rc;
+    if ((rc = g_ed.req_v1.reserve(2 * 64, "alloc req"))) return rc;
+    int32_t *d_req = g_ed.req_v1;
     std::memset(out, 0, sizeof(int64_t) * 16 * (size_t)count);
     std::vector<int32_t> idx, hd;
     std::vector<long long> res;
@@ -672,47 +645,18 @@ int kge_link_prediction(const kge_model_desc *m, const float *const tables[KGE_M
         fixed[(size_t)q] = hd[(size_t)q] ? tt.y : tt.x;   // head request: the tail stays; tail request: the head stays
         rel[(size_t)q] = tt.z;
     }
-    static int32_t *d_req = nullptr;     // [3][cap]: test index, head flag, fixed entity
-    static int64_t req_cap = 0;
-    static float *d_T = nullptr, *d_P = nullptr;
-    static int64_t t_cap = 0, p_cap = 0;
-    if (n_req > req_cap) {
-        if (d_req) (void)hipFree(d_req);
-        d_req = nullptr;
-        if ((rc = hip_check(hipMalloc(&d_req, sizeof(int32_t) * 3 * (size_t)n_req), "alloc lp requests"))) return rc;
-        req_cap = n_req;
-    }
-    if (E * D > t_cap) {
-        if (d_T) (void)hipFree(d_T);
-        d_T = nullptr;
-        if ((rc = hip_check(hipMalloc(&d_T, sizeof(float) * (size_t)(E * D)), "alloc lp table"))) return rc;
-        t_cap = E * D;
-    }
-    if (m->model == KGE_TRANSR && (E + 1) * D > p_cap) {
-        if (d_P) (void)hipFree(d_P);
-        d_P = nullptr;
-        if ((rc = hip_check(hipMalloc(&d_P, sizeof(float) * (size_t)((E + 1) * D)), "alloc lp projections"))) return rc;
-        p_cap = (E + 1) * D;
-    }
+    if ((rc = g_ed.req.reserve(3 * n_req, "alloc lp requests"))) return rc;
+    if ((rc = g_ed.T.reserve(E * D, "alloc lp table"))) return rc;
+    if (m->model == KGE_TRANSR && (rc = g_ed.P.reserve((E + 1) * D, "alloc lp projections"))) return rc;
+    float *d_T = g_ed.T, *d_P = g_ed.P;
     // scores for a chunk of requests: at most 1 GiB
     int64_t qmax = (int64_t(1) << 28) / (E > 0 ? E : 1);
     if (qmax < 1) qmax = 1;
     if (qmax > 4096) qmax = 4096;
     if (qmax > n_req) qmax = n_req;
-    if (g_ed.scores_cap < qmax * E) {
-        if (g_ed.scores) (void)hipFree(g_ed.scores);
-        if (g_ed.cand) (void)hipFree(g_ed.cand);
-        g_ed.scores = nullptr; g_ed.cand = nullptr;
-        if ((rc = hip_check(hipMalloc(&g_ed.scores, sizeof(float) * (size_t)(qmax * E)), "alloc scores"))) return rc;
-        g_ed.scores_cap = qmax * E;
-    }
-    if (g_ed.out_cap < n_req) {
-        if (g_ed.out) (void)hipFree(g_ed.out);
-        g_ed.out = nullptr;
-        if ((rc = hip_check(hipMalloc(&g_ed.out, sizeof(long long) * 8 * (size_t)n_req), "alloc rank out"))) return rc;
-        g_ed.out_cap = (int)n_req;
-    }
-    int32_t *d_idx = d_req, *d_hd = d_req + req_cap, *d_fixed = d_req + 2 * req_cap;
+    if ((rc = g_ed.scores.reserve(qmax * E, "alloc scores"))) return rc;
+    if ((rc = g_ed.out.reserve(8 * n_req, "alloc rank out"))) return rc;
+    int32_t *d_idx = g_ed.req, *d_hd = d_idx + n_req, *d_fixed = d_idx + 2 * n_req;
     if ((rc = hip_check(hipMemcpyAsync(d_idx, idx.data(), sizeof(int32_t) * (size_t)n_req, hipMemcpyHostToDevice, stream), "upload req"))) return rc;
     if ((rc = hip_check(hipMemcpyAsync(d_hd, hd.data(), sizeof(int32_t) * (size_t)n_req, hipMemcpyHostToDevice, stream), "upload req"))) return rc;
     if ((rc = hip_check(hipMemcpyAsync(d_fixed, fixed.data(), sizeof(int32_t) * (size_t)n_req, hipMemcpyHostToDevice, stream), "upload req"))) return rc;

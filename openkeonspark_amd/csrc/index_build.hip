@@ -19,17 +19,6 @@ namespace kge {
 
 namespace {
 
-template <typename T>
-struct DevBuf {
-    T *p = nullptr;
-    ~DevBuf() { if (p) (void)hipFree(p); }
-    int alloc(size_t count, const char *what) {
-        if (p) { (void)hipFree(p); p = nullptr; }
-        return hip_check(hipMalloc(&p, sizeof(T) * (count ? count : 1)), what);
-    }
-    T *release() { T *q = p; p = nullptr; return q; }
-};
-
 int bits_for(int64_t count) {  // bits needed for values in [0, count)
     int b = 1;
     while ((int64_t(1) << b) < count) b++;
@@ -133,14 +122,8 @@ __global__ void assemble_kernel(const int32_t *__restrict__ h, const int32_t *__
 }
 
 struct SortScratch {
-    DevBuf<char> tmp;
-    size_t bytes = 0;
-    int ensure(size_t need) {
-        if (need <= bytes) return KGE_OK;
-        int rc = tmp.alloc(need, "index build: sort scratch");
-        if (!rc) bytes = need;
-        return rc;
-    }
+    ScopedDevBuf<char> tmp;
+    int ensure(size_t need) { return tmp.reserve((int64_t)need, "index build: sort scratch"); }
 };
 
 int sort_pairs(SortScratch &sc, const uint64_t *kin, uint64_t *kout, const int32_t *vin, int32_t *vout, size_t n, int bits) {
@@ -148,7 +131,7 @@ int sort_pairs(SortScratch &sc, const uint64_t *kin, uint64_t *kout, const int32
     int rc = hip_check(rocprim::radix_sort_pairs(nullptr, need, kin, kout, vin, vout, n, 0, (unsigned)bits, nullptr), "index sort size");
     if (rc) return rc;
     if ((rc = sc.ensure(need))) return rc;
-    return hip_check(rocprim::radix_sort_pairs(sc.tmp.p, need, kin, kout, vin, vout, n, 0, (unsigned)bits, nullptr), "index sort");
+    return hip_check(rocprim::radix_sort_pairs(sc.tmp.ptr(), need, kin, kout, vin, vout, n, 0, (unsigned)bits, nullptr), "index sort");
 }
 
 int scan_flags(SortScratch &sc, int32_t *flags, size_t n) {
@@ -156,7 +139,7 @@ int scan_flags(SortScratch &sc, int32_t *flags, size_t n) {
     int rc = hip_check(rocprim::inclusive_scan(nullptr, need, flags, flags, n, rocprim::plus<int32_t>(), nullptr), "index scan size");
     if (rc) return rc;
     if ((rc = sc.ensure(need))) return rc;
-    return hip_check(rocprim::inclusive_scan(sc.tmp.p, need, flags, flags, n, rocprim::plus<int32_t>(), nullptr), "index scan");
+    return hip_check(rocprim::inclusive_scan(sc.tmp.ptr(), need, flags, flags, n, rocprim::plus<int32_t>(), nullptr), "index scan");
 }
 
 template <typename T>
@@ -184,94 +167,94 @@ std::string build_index_device(KgIndex &ix, DeviceIndex &dev, int64_t E, int64_t
     const size_t N = (size_t)n;
     int rc;
 #define KGE_TRY(expr) if ((rc = (expr))) return "device index build failed: " + engine().last_error
-    DevBuf<int32_t> h32, t32, r32;
-    KGE_TRY(h32.alloc(N, "index h")); KGE_TRY(t32.alloc(N, "index t")); KGE_TRY(r32.alloc(N, "index r"));
+    ScopedDevBuf<int32_t> h32, t32, r32;
+    KGE_TRY(h32.replace(N, "index h")); KGE_TRY(t32.replace(N, "index t")); KGE_TRY(r32.replace(N, "index r"));
     {
-        DevBuf<int64_t> h64, t64, r64;
-        DevBuf<unsigned long long> bad;
-        KGE_TRY(h64.alloc(N, "index h64")); KGE_TRY(t64.alloc(N, "index t64")); KGE_TRY(r64.alloc(N, "index r64"));
-        KGE_TRY(bad.alloc(1, "index flag"));
-        KGE_TRY(hip_check(hipMemcpy(h64.p, h, sizeof(int64_t) * N, hipMemcpyHostToDevice), "upload h"));
-        KGE_TRY(hip_check(hipMemcpy(t64.p, t, sizeof(int64_t) * N, hipMemcpyHostToDevice), "upload t"));
-        KGE_TRY(hip_check(hipMemcpy(r64.p, r, sizeof(int64_t) * N, hipMemcpyHostToDevice), "upload r"));
-        KGE_TRY(hip_check(hipMemset(bad.p, 0xFF, sizeof(unsigned long long)), "index flag init"));
-        hipLaunchKernelGGL(narrow_kernel, dim3(grid_for(n)), dim3(TPB), 0, nullptr, h64.p, t64.p, r64.p, (long long)n, (long long)E,
-                           (long long)R, h32.p, t32.p, r32.p, bad.p);
+        ScopedDevBuf<int64_t> h64, t64, r64;
+        ScopedDevBuf<unsigned long long> bad;
+        KGE_TRY(h64.replace(N, "index h64")); KGE_TRY(t64.replace(N, "index t64")); KGE_TRY(r64.replace(N, "index r64"));
+        KGE_TRY(bad.replace(1, "index flag"));
+        KGE_TRY(hip_check(hipMemcpy(h64, h, sizeof(int64_t) * N, hipMemcpyHostToDevice), "upload h"));
+        KGE_TRY(hip_check(hipMemcpy(t64, t, sizeof(int64_t) * N, hipMemcpyHostToDevice), "upload t"));
+        KGE_TRY(hip_check(hipMemcpy(r64, r, sizeof(int64_t) * N, hipMemcpyHostToDevice), "upload r"));
+        KGE_TRY(hip_check(hipMemset(bad, 0xFF, sizeof(unsigned long long)), "index flag init"));
+        hipLaunchKernelGGL(narrow_kernel, dim3(grid_for(n)), dim3(TPB), 0, nullptr, h64, t64, r64, (long long)n, (long long)E,
+                           (long long)R, h32, t32, r32, bad);
         unsigned long long first_bad = 0;
-        KGE_TRY(hip_check(hipMemcpy(&first_bad, bad.p, sizeof(first_bad), hipMemcpyDeviceToHost), "index flag read"));
+        KGE_TRY(hip_check(hipMemcpy(&first_bad, bad, sizeof(first_bad), hipMemcpyDeviceToHost), "index flag read"));
         if (first_bad != ~0ULL) return "train2id.txt: id out of range at line " + std::to_string((long long)first_bad + 2);
     }
     SortScratch sc;
-    DevBuf<uint64_t> keys_a, keys_b;
-    DevBuf<int32_t> idx_a, idx_b, flags, head_pos;
-    KGE_TRY(keys_a.alloc(N, "index keys")); KGE_TRY(keys_b.alloc(N, "index keys"));
-    KGE_TRY(idx_a.alloc(N, "index idx")); KGE_TRY(idx_b.alloc(N, "index idx"));
-    KGE_TRY(flags.alloc(N, "index flags")); KGE_TRY(head_pos.alloc(N + 1, "index heads"));
+    ScopedDevBuf<uint64_t> keys_a, keys_b;
+    ScopedDevBuf<int32_t> idx_a, idx_b, flags, head_pos;
+    KGE_TRY(keys_a.replace(N, "index keys")); KGE_TRY(keys_b.replace(N, "index keys"));
+    KGE_TRY(idx_a.replace(N, "index idx")); KGE_TRY(idx_b.replace(N, "index idx"));
+    KGE_TRY(flags.replace(N, "index flags")); KGE_TRY(head_pos.replace(N + 1, "index heads"));
 
     // ---- (h,r,t) order of the file lines, dedup ----------------------------------------------------
-    hipLaunchKernelGGL(pack_kernel, dim3(grid_for(n)), dim3(TPB), 0, nullptr, h32.p, r32.p, t32.p, (long long)n, br, be, keys_a.p, idx_a.p);
-    KGE_TRY(sort_pairs(sc, keys_a.p, keys_b.p, idx_a.p, idx_b.p, N, total_bits));   // keys_b sorted, idx_b = order
-    hipLaunchKernelGGL(flag_kernel, dim3(grid_for(n)), dim3(TPB), 0, nullptr, keys_b.p, (long long)n, 0, flags.p);
-    KGE_TRY(scan_flags(sc, flags.p, N));
+    hipLaunchKernelGGL(pack_kernel, dim3(grid_for(n)), dim3(TPB), 0, nullptr, h32, r32, t32, (long long)n, br, be, keys_a, idx_a);
+    KGE_TRY(sort_pairs(sc, keys_a, keys_b, idx_a, idx_b, N, total_bits));   // keys_b sorted, idx_b = order
+    hipLaunchKernelGGL(flag_kernel, dim3(grid_for(n)), dim3(TPB), 0, nullptr, keys_b, (long long)n, 0, flags);
+    KGE_TRY(scan_flags(sc, flags, N));
     int32_t U32 = 0;
-    KGE_TRY(hip_check(hipMemcpy(&U32, flags.p + (N - 1), sizeof(int32_t), hipMemcpyDeviceToHost), "index unique count"));
+    KGE_TRY(hip_check(hipMemcpy(&U32, flags + (N - 1), sizeof(int32_t), hipMemcpyDeviceToHost), "index unique count"));
     const int64_t U = U32;
     const size_t UU = (size_t)U;
-    DevBuf<uint64_t> ukeys;
-    DevBuf<int32_t> file2uniq, uh, ur, ut;
-    KGE_TRY(ukeys.alloc(UU, "index ukeys")); KGE_TRY(file2uniq.alloc(N, "index file2uniq"));
-    KGE_TRY(uh.alloc(UU, "index uh")); KGE_TRY(ur.alloc(UU, "index ur")); KGE_TRY(ut.alloc(UU, "index ut"));
-    hipLaunchKernelGGL(dedup_kernel, dim3(grid_for(n)), dim3(TPB), 0, nullptr, keys_b.p, flags.p, idx_b.p, (long long)n, ukeys.p, file2uniq.p);
-    hipLaunchKernelGGL(unpack_hrt_kernel, dim3(grid_for(U)), dim3(TPB), 0, nullptr, ukeys.p, (long long)U, be, br, uh.p, ur.p, ut.p);
+    ScopedDevBuf<uint64_t> ukeys;
+    ScopedDevBuf<int32_t> file2uniq, uh, ur, ut;
+    KGE_TRY(ukeys.replace(UU, "index ukeys")); KGE_TRY(file2uniq.replace(N, "index file2uniq"));
+    KGE_TRY(uh.replace(UU, "index uh")); KGE_TRY(ur.replace(UU, "index ur")); KGE_TRY(ut.replace(UU, "index ut"));
+    hipLaunchKernelGGL(dedup_kernel, dim3(grid_for(n)), dim3(TPB), 0, nullptr, keys_b, flags, idx_b, (long long)n, ukeys, file2uniq);
+    hipLaunchKernelGGL(unpack_hrt_kernel, dim3(grid_for(U)), dim3(TPB), 0, nullptr, ukeys, (long long)U, be, br, uh, ur, ut);
 
-    DevBuf<unsigned long long> counters;   // freq_rel | groups_hr | groups_tr
-    KGE_TRY(counters.alloc(3 * (size_t)R, "index relation counters"));
-    KGE_TRY(hip_check(hipMemset(counters.p, 0, sizeof(unsigned long long) * 3 * (size_t)R), "index counters init"));
+    ScopedDevBuf<unsigned long long> counters;   // freq_rel | groups_hr | groups_tr
+    KGE_TRY(counters.replace(3 * (size_t)R, "index relation counters"));
+    KGE_TRY(hip_check(hipMemset(counters, 0, sizeof(unsigned long long) * 3 * (size_t)R), "index counters init"));
     const uint64_t mask_e = (uint64_t(1) << be) - 1, mask_r = (uint64_t(1) << br) - 1;
 
-    DevBuf<int32_t> tails_hr, heads_tr, rels_ht, hr_off, hr_len, tr_off, tr_len, ht_off, ht_len;
-    KGE_TRY(tails_hr.alloc(UU, "index tails")); KGE_TRY(heads_tr.alloc(UU, "index heads")); KGE_TRY(rels_ht.alloc(UU, "index rels"));
-    KGE_TRY(hr_off.alloc(UU, "index hr_off")); KGE_TRY(hr_len.alloc(UU, "index hr_len"));
-    KGE_TRY(tr_off.alloc(UU, "index tr_off")); KGE_TRY(tr_len.alloc(UU, "index tr_len"));
-    KGE_TRY(ht_off.alloc(UU, "index ht_off")); KGE_TRY(ht_len.alloc(UU, "index ht_len"));
+    ScopedDevBuf<int32_t> tails_hr, heads_tr, rels_ht, hr_off, hr_len, tr_off, tr_len, ht_off, ht_len;
+    KGE_TRY(tails_hr.replace(UU, "index tails")); KGE_TRY(heads_tr.replace(UU, "index heads")); KGE_TRY(rels_ht.replace(UU, "index rels"));
+    KGE_TRY(hr_off.replace(UU, "index hr_off")); KGE_TRY(hr_len.replace(UU, "index hr_len"));
+    KGE_TRY(tr_off.replace(UU, "index tr_off")); KGE_TRY(tr_len.replace(UU, "index tr_len"));
+    KGE_TRY(ht_off.replace(UU, "index ht_off")); KGE_TRY(ht_len.replace(UU, "index ht_len"));
 
     // ---- groups (h,r) over the unique triples (already in (h,r,t) order): tails_hr ----------------
-    hipLaunchKernelGGL(flag_kernel, dim3(grid_for(U)), dim3(TPB), 0, nullptr, ukeys.p, (long long)U, be, flags.p);
-    KGE_TRY(scan_flags(sc, flags.p, UU));
-    hipLaunchKernelGGL(heads_kernel, dim3(grid_for(U)), dim3(TPB), 0, nullptr, ukeys.p, flags.p, (long long)U, be, head_pos.p);
-    hipLaunchKernelGGL(groups_kernel, dim3(grid_for(U)), dim3(TPB), 0, nullptr, ukeys.p, flags.p, head_pos.p, (const int32_t *)nullptr,
-                       (long long)U, be, mask_e, be, mask_r, tails_hr.p, hr_off.p, hr_len.p, counters.p, counters.p + R);
+    hipLaunchKernelGGL(flag_kernel, dim3(grid_for(U)), dim3(TPB), 0, nullptr, ukeys, (long long)U, be, flags);
+    KGE_TRY(scan_flags(sc, flags, UU));
+    hipLaunchKernelGGL(heads_kernel, dim3(grid_for(U)), dim3(TPB), 0, nullptr, ukeys, flags, (long long)U, be, head_pos);
+    hipLaunchKernelGGL(groups_kernel, dim3(grid_for(U)), dim3(TPB), 0, nullptr, ukeys, flags, head_pos, (const int32_t *)nullptr,
+                       (long long)U, be, mask_e, be, mask_r, tails_hr, hr_off, hr_len, counters, counters + R);
 
     // ---- (t,r,h) order: heads_tr, groups (t,r) -----------------------------------------------------
-    hipLaunchKernelGGL(pack_kernel, dim3(grid_for(U)), dim3(TPB), 0, nullptr, ut.p, ur.p, uh.p, (long long)U, br, be, keys_a.p, idx_a.p);
-    KGE_TRY(sort_pairs(sc, keys_a.p, keys_b.p, idx_a.p, idx_b.p, UU, total_bits));
-    hipLaunchKernelGGL(flag_kernel, dim3(grid_for(U)), dim3(TPB), 0, nullptr, keys_b.p, (long long)U, be, flags.p);
-    KGE_TRY(scan_flags(sc, flags.p, UU));
-    hipLaunchKernelGGL(heads_kernel, dim3(grid_for(U)), dim3(TPB), 0, nullptr, keys_b.p, flags.p, (long long)U, be, head_pos.p);
-    hipLaunchKernelGGL(groups_kernel, dim3(grid_for(U)), dim3(TPB), 0, nullptr, keys_b.p, flags.p, head_pos.p, idx_b.p, (long long)U, be,
-                       mask_e, be, mask_r, heads_tr.p, tr_off.p, tr_len.p, (unsigned long long *)nullptr, counters.p + 2 * R);
+    hipLaunchKernelGGL(pack_kernel, dim3(grid_for(U)), dim3(TPB), 0, nullptr, ut, ur, uh, (long long)U, br, be, keys_a, idx_a);
+    KGE_TRY(sort_pairs(sc, keys_a, keys_b, idx_a, idx_b, UU, total_bits));
+    hipLaunchKernelGGL(flag_kernel, dim3(grid_for(U)), dim3(TPB), 0, nullptr, keys_b, (long long)U, be, flags);
+    KGE_TRY(scan_flags(sc, flags, UU));
+    hipLaunchKernelGGL(heads_kernel, dim3(grid_for(U)), dim3(TPB), 0, nullptr, keys_b, flags, (long long)U, be, head_pos);
+    hipLaunchKernelGGL(groups_kernel, dim3(grid_for(U)), dim3(TPB), 0, nullptr, keys_b, flags, head_pos, idx_b, (long long)U, be,
+                       mask_e, be, mask_r, heads_tr, tr_off, tr_len, (unsigned long long *)nullptr, counters + 2 * R);
 
     // ---- (h,t,r) order: rels_ht, groups (h,t) ------------------------------------------------------
-    hipLaunchKernelGGL(pack_kernel, dim3(grid_for(U)), dim3(TPB), 0, nullptr, uh.p, ut.p, ur.p, (long long)U, be, br, keys_a.p, idx_a.p);
-    KGE_TRY(sort_pairs(sc, keys_a.p, keys_b.p, idx_a.p, idx_b.p, UU, total_bits));
-    hipLaunchKernelGGL(flag_kernel, dim3(grid_for(U)), dim3(TPB), 0, nullptr, keys_b.p, (long long)U, br, flags.p);
-    KGE_TRY(scan_flags(sc, flags.p, UU));
-    hipLaunchKernelGGL(heads_kernel, dim3(grid_for(U)), dim3(TPB), 0, nullptr, keys_b.p, flags.p, (long long)U, br, head_pos.p);
-    hipLaunchKernelGGL(groups_kernel, dim3(grid_for(U)), dim3(TPB), 0, nullptr, keys_b.p, flags.p, head_pos.p, idx_b.p, (long long)U, br,
-                       mask_r, 0, mask_r, rels_ht.p, ht_off.p, ht_len.p, (unsigned long long *)nullptr, (unsigned long long *)nullptr);
+    hipLaunchKernelGGL(pack_kernel, dim3(grid_for(U)), dim3(TPB), 0, nullptr, uh, ut, ur, (long long)U, be, br, keys_a, idx_a);
+    KGE_TRY(sort_pairs(sc, keys_a, keys_b, idx_a, idx_b, UU, total_bits));
+    hipLaunchKernelGGL(flag_kernel, dim3(grid_for(U)), dim3(TPB), 0, nullptr, keys_b, (long long)U, br, flags);
+    KGE_TRY(scan_flags(sc, flags, UU));
+    hipLaunchKernelGGL(heads_kernel, dim3(grid_for(U)), dim3(TPB), 0, nullptr, keys_b, flags, (long long)U, br, head_pos);
+    hipLaunchKernelGGL(groups_kernel, dim3(grid_for(U)), dim3(TPB), 0, nullptr, keys_b, flags, head_pos, idx_b, (long long)U, br,
+                       mask_r, 0, mask_r, rels_ht, ht_off, ht_len, (unsigned long long *)nullptr, (unsigned long long *)nullptr);
 
     // ---- per file-order line records ----------------------------------------------------------------
-    DevBuf<int4> pos, grp;
-    DevBuf<int2> ht;
-    KGE_TRY(pos.alloc(N, "index pos")); KGE_TRY(grp.alloc(N, "index grp")); KGE_TRY(ht.alloc(N, "index ht"));
-    hipLaunchKernelGGL(assemble_kernel, dim3(grid_for(n)), dim3(TPB), 0, nullptr, h32.p, t32.p, r32.p, file2uniq.p, hr_off.p, hr_len.p,
-                       tr_off.p, tr_len.p, ht_off.p, ht_len.p, (long long)n, pos.p, grp.p, ht.p);
+    ScopedDevBuf<int4> pos, grp;
+    ScopedDevBuf<int2> ht;
+    KGE_TRY(pos.replace(N, "index pos")); KGE_TRY(grp.replace(N, "index grp")); KGE_TRY(ht.replace(N, "index ht"));
+    hipLaunchKernelGGL(assemble_kernel, dim3(grid_for(n)), dim3(TPB), 0, nullptr, h32, t32, r32, file2uniq, hr_off, hr_len,
+                       tr_off, tr_len, ht_off, ht_len, (long long)n, pos, grp, ht);
     KGE_TRY(hip_check(hipDeviceSynchronize(), "index build"));
     KGE_TRY(hip_check(hipGetLastError(), "index build launch"));
 
     // ---- relation statistics: the three integer histograms come back, the float arithmetic is the host's ----
     std::vector<unsigned long long> cnt(3 * (size_t)R);
-    KGE_TRY(hip_check(hipMemcpy(cnt.data(), counters.p, sizeof(unsigned long long) * cnt.size(), hipMemcpyDeviceToHost), "index counters"));
+    KGE_TRY(hip_check(hipMemcpy(cnt.data(), counters, sizeof(unsigned long long) * cnt.size(), hipMemcpyDeviceToHost), "index counters"));
     ix.ent_total = E; ix.rel_total = R; ix.train_dup = n; ix.new_batch = new_batch; ix.train_uniq = U;
     std::vector<int64_t> freq_rel((size_t)R), groups_hr((size_t)R), groups_tr((size_t)R);
     for (int64_t q = 0; q < R; q++) {
@@ -282,18 +265,15 @@ std::string build_index_device(KgIndex &ix, DeviceIndex &dev, int64_t E, int64_t
     relation_means(ix, freq_rel, groups_hr, groups_tr);
 
     // host mirror (kge_index_copy, the evaluation loader)
-    KGE_TRY(download(ix.pos, pos.p, N, "mirror pos")); KGE_TRY(download(ix.grp, grp.p, N, "mirror grp"));
-    KGE_TRY(download(ix.ht, ht.p, N, "mirror ht"));
-    KGE_TRY(download(ix.tails_hr, tails_hr.p, UU, "mirror tails")); KGE_TRY(download(ix.heads_tr, heads_tr.p, UU, "mirror heads"));
-    KGE_TRY(download(ix.rels_ht, rels_ht.p, UU, "mirror rels"));
+    KGE_TRY(download(ix.pos, pos, N, "mirror pos")); KGE_TRY(download(ix.grp, grp, N, "mirror grp"));
+    KGE_TRY(download(ix.ht, ht, N, "mirror ht"));
+    KGE_TRY(download(ix.tails_hr, tails_hr, UU, "mirror tails")); KGE_TRY(download(ix.heads_tr, heads_tr, UU, "mirror heads"));
+    KGE_TRY(download(ix.rels_ht, rels_ht, UU, "mirror rels"));
 
     // adopt the device arrays
-    auto drop = [](auto *&p) { if (p) { (void)hipFree(p); p = nullptr; } };
-    drop(dev.pos); drop(dev.grp); drop(dev.ht); drop(dev.tails_hr); drop(dev.heads_tr); drop(dev.rels_ht); drop(dev.bern_prob);
-    dev.pos = pos.release(); dev.grp = grp.release(); dev.ht = ht.release();
-    dev.tails_hr = tails_hr.release(); dev.heads_tr = heads_tr.release(); dev.rels_ht = rels_ht.release();
-    KGE_TRY(hip_check(hipMalloc(&dev.bern_prob, sizeof(float) * (size_t)(R ? R : 1)), "index bern"));
-    KGE_TRY(hip_check(hipMemcpy(dev.bern_prob, ix.bern_prob.data(), sizeof(float) * (size_t)R, hipMemcpyHostToDevice), "index bern"));
+    dev.pos.adopt(pos.release(), n); dev.grp.adopt(grp.release(), n); dev.ht.adopt(ht.release(), n);
+    dev.tails_hr.adopt(tails_hr.release(), U); dev.heads_tr.adopt(heads_tr.release(), U); dev.rels_ht.adopt(rels_ht.release(), U);
+    KGE_TRY(dev.bern_prob.upload(ix.bern_prob.data(), R, "index bern"));
     dev.uploaded = true;
     ix.loaded = true;
 #undef KGE_TRY

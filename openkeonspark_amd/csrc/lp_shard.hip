@@ -359,8 +359,7 @@ int launch_range(const RangeArgsOf<KEYS> &a, hipStream_t stream) {
     return shaped ? rc : fail(KGE_ERR_UNSUPPORTED, "link prediction over a row range: embedding dimension > 1024");
 }
 
-long long *g_out = nullptr;
-int64_t g_out_cap = 0;
+DevBuf<long long> g_out;
 
 }  // namespace
 
@@ -439,12 +438,7 @@ int kge_link_prediction_finish(INT first, INT count, INT test_head, const int64_
     if (first < 0 || count < 0 || first + count > total) return fail(KGE_ERR_BAD_ARG, "kge_link_prediction_finish: bad test range");
     if (count == 0) return KGE_OK;
     if (!d_counts || !d_keys || !h_out) return fail(KGE_ERR_BAD_ARG, "kge_link_prediction_finish: null array");
-    if (count * 16 > g_out_cap) {
-        if (g_out) (void)hipFree(g_out);
-        g_out = nullptr; g_out_cap = 0;
-        if ((rc = hip_check(hipMalloc(&g_out, sizeof(long long) * 16 * (size_t)count), "alloc lp finish out"))) return rc;
-        g_out_cap = count * 16;
-    }
+    if ((rc = g_out.reserve(16 * count, "alloc lp finish out"))) return rc;
     a.counts = (const long long *)d_counts; a.keys = (const long long *)d_keys;
     a.first = first; a.count = count; a.test_head = test_head ? 1 : 0; a.out = g_out;
     hipLaunchKernelGGL(lp_finish_kernel, dim3((unsigned)((2 * count + 255) / 256)), dim3(256), 0, stream, a);

@@ -825,17 +825,13 @@ void guard_loss_stream(hipStream_t stream) {
 
 int ensure_loss_buffers() {
     Engine &e = engine();
-    if (!e.dev.loss_partials) {
-        int rc = hip_check(hipMalloc(&e.dev.loss_partials, sizeof(float) * (kMaxLossBlocks + 256)), "alloc loss partials");
-        if (rc) return rc;
-    }
-    if (!e.dev.loss_ticket) {
-        const size_t n = 1 + (kMaxLossBlocks + 31) / 32;   // master + one sub-counter per 32 blocks
-        int rc = hip_check(hipMalloc(&e.dev.loss_ticket, sizeof(unsigned) * n), "alloc loss ticket");
-        if (rc) return rc;
-        if ((rc = hip_check(hipMemset(e.dev.loss_ticket, 0, sizeof(unsigned) * n), "zero loss ticket"))) return rc;
-    }
-    return KGE_OK;
+    int rc = e.dev.loss_partials.reserve(kMaxLossBlocks + 256, "alloc loss partials");
+    if (rc) return rc;
+    const int64_t n = 1 + (kMaxLossBlocks + 31) / 32;   // master + one sub-counter per 32 blocks
+    bool grew;
+    if ((rc = e.dev.loss_ticket.reserve(n, "alloc loss ticket", &grew))) return rc;
+    if (grew && (rc = hip_check(hipMemset(e.dev.loss_ticket, 0, sizeof(unsigned) * (size_t)n), "zero loss ticket"))) e.dev.loss_ticket.free();
+    return rc;
 }
 
 // the numbers of the TransE count-path rung for dimension D (team_shape.hpp), for callers that size buffers by them
@@ -843,11 +839,23 @@ void transe_team_shape(int D, int &L, int &C) {
     for_transe_team_shape_or_last(D, [&](auto t) { L = decltype(t)::L; C = decltype(t)::C; });
 }
 
-static int32_t *g_defer_list = nullptr, *g_defer_count = nullptr;
-static int64_t g_defer_cap = 0;
+// groups of the LAST emit launch that were not sampler-shaped: the list an emit kernel defers them to, and how many it holds
+static DevBuf<int32_t> g_defer_list, g_defer_count;
+// room for one entry per group; zero: the count restarts on `stream`
+static int ensure_defer_list(int64_t n_pos, bool zero, hipStream_t stream) {
+    int rc = g_defer_list.reserve(n_pos, "alloc deferred groups");
+    if (!rc) rc = g_defer_count.reserve(1, "alloc deferred count");
+    if (!rc && zero) rc = hip_check(hipMemsetAsync(g_defer_count, 0, sizeof(int32_t), stream), "zero deferred count");
+    return rc;
+}
 
-// groups of the LAST emit launch that were not sampler-shaped (synchronous read of the device counter)
-static int32_t *g_skipped = nullptr;     // negatives the last in-place SGD step skipped (FbArgs::skipped)
+static DevBuf<int32_t> g_skipped;     // negatives the last in-place SGD step skipped (FbArgs::skipped)
+static int arm_skipped_counter(FbArgs &a, hipStream_t stream) {
+    int rc = g_skipped.reserve(1, "alloc skipped-negatives counter");
+    if (!rc) rc = hip_check(hipMemsetAsync(g_skipped, 0, sizeof(int32_t), stream), "zero skipped-negatives counter");
+    a.skipped = g_skipped;
+    return rc;
+}
 int sgd_rows_skipped(int32_t *out) {
     *out = 0;
     if (!g_skipped) return KGE_OK;
@@ -870,31 +878,17 @@ int launch_transe_emit(const kge_model_desc &m, const float *ent, const float *r
     // deferral list, no counter reset, no fp32 pass
     Engine &e = engine();
     { int rc = ensure_loss_buffers(); if (rc) return rc; }
-    int32_t *&defer_list = g_defer_list, *&defer_count = g_defer_count;
-    int64_t &defer_cap = g_defer_cap;
-    if (n_pos > defer_cap) {
-        if (defer_list) (void)hipFree(defer_list);
-        defer_list = nullptr;
-        int rc = hip_check(hipMalloc(&defer_list, sizeof(int32_t) * (size_t)n_pos), "alloc deferred groups");
-        if (rc) return rc;
-        if (!defer_count && (rc = hip_check(hipMalloc(&defer_count, sizeof(int32_t)), "alloc deferred count"))) return rc;
-        defer_cap = n_pos;
-    }
-    if (track_deferred) {
-        int rc = hip_check(hipMemsetAsync(defer_count, 0, sizeof(int32_t), stream), "zero deferred count");
-        if (rc) return rc;
-    }
+    { int rc = ensure_defer_list(n_pos, track_deferred, stream); if (rc) return rc; }
     const bool use_inv_table = (m.ent_total + m.rel_total) * (int64_t)m.ent_dim * 4 <= e.inv_table_max_bytes;
-    if (use_inv_table && m.ent_total + m.rel_total > e.inv_cap) {
-        if (e.inv_norm) (void)hipFree(e.inv_norm);
-        e.inv_norm = nullptr; e.inv_valid = 0;
-        int rc = hip_check(hipMalloc(&e.inv_norm, sizeof(float) * (size_t)(m.ent_total + m.rel_total)), "alloc row inverse norms");
+    if (use_inv_table) {
+        bool grew;
+        int rc = e.inv_norm.reserve(m.ent_total + m.rel_total, "alloc row inverse norms", &grew);
+        if (grew) e.inv_valid = 0;
         if (rc) return rc;
-        e.inv_cap = m.ent_total + m.rel_total;
     }
     FbArgs a = {};
-    a.inv_norm = use_inv_table ? e.inv_norm : nullptr;
-    a.group_list = track_deferred ? defer_list : nullptr; a.group_count = defer_count;
+    a.inv_norm = use_inv_table ? e.inv_norm.ptr() : nullptr;
+    a.group_list = track_deferred ? g_defer_list.ptr() : nullptr; a.group_count = g_defer_count;
     a.ent = ent; a.rel = rel; a.g_ent = resid_ent; a.g_rel = resid_rel;
     a.bh = d_h; a.bt = d_t; a.br = d_r;
     a.n_pos = n_pos; a.n_neg = n_neg; a.stride = stride;
@@ -1016,6 +1010,7 @@ static int dispatch_fb(const FbArgs &a, float *d_loss, hipStream_t stream) {
     return KGE_OK;
 }
 
+static DevBuf<float> g_hub_copies[2];   // rel, auxr
 // Atomic relation-side adds on a KG with few relations: group b adds into copy b % hub_k of [hub_k][R][D] buffers (zero between
 // steps: hub_fold_kernel re-zeroes what it folds) when a relation-side row would take >= 128 adds per step.
 static int attach_hub_copies(const kge_model_desc &m, int64_t n_pos, FbArgs &a) {
@@ -1029,20 +1024,13 @@ static int attach_hub_copies(const kge_model_desc &m, int64_t n_pos, FbArgs &a) 
     const int64_t per_copy = m.rel_total * (int64_t)a.D;
     while (copies > 1 && copies * per_copy * 4 > (int64_t(32) << 20)) copies >>= 1;
     if (copies <= 1) return KGE_OK;
-    static float *buf_rel = nullptr, *buf_auxr = nullptr;
-    static int64_t buf_elems = 0;
-    int rc;
-    if (copies * per_copy > buf_elems) {
-        if (buf_rel) (void)hipFree(buf_rel);
-        if (buf_auxr) (void)hipFree(buf_auxr);
-        buf_rel = buf_auxr = nullptr;
-        buf_elems = copies * per_copy;
-        if ((rc = hip_check(hipMalloc(&buf_rel, sizeof(float) * (size_t)buf_elems), "alloc hub copies"))) return rc;
-        if ((rc = hip_check(hipMalloc(&buf_auxr, sizeof(float) * (size_t)buf_elems), "alloc hub copies"))) return rc;
-        if ((rc = hip_check(hipMemset(buf_rel, 0, sizeof(float) * (size_t)buf_elems), "zero hub copies"))) return rc;
-        if ((rc = hip_check(hipMemset(buf_auxr, 0, sizeof(float) * (size_t)buf_elems), "zero hub copies"))) return rc;
+    for (auto &buf : g_hub_copies) {
+        bool grew;
+        int rc = buf.reserve(copies * per_copy, "alloc hub copies", &grew);
+        if (!rc && grew && (rc = hip_check(hipMemset(buf, 0, sizeof(float) * (size_t)(copies * per_copy)), "zero hub copies"))) buf.free();
+        if (rc) return rc;
     }
-    a.copies_rel = buf_rel; a.copies_auxr = buf_auxr; a.hub_k = (int)copies;
+    a.copies_rel = g_hub_copies[0]; a.copies_auxr = g_hub_copies[1]; a.hub_k = (int)copies;
     a.rel_total = (int)m.rel_total;
     return KGE_OK;
 }
@@ -1279,14 +1267,7 @@ int launch_transr_vector_stage(const float *rel, float *g_rel, const float *P, f
             a.loss_out = d_loss; a.loss_ticket = e.dev.loss_ticket;
             launch(a);
         } else {
-            if (n_pos > g_defer_cap) {
-                if (g_defer_list) (void)hipFree(g_defer_list);
-                g_defer_list = nullptr;
-                if ((rc = hip_check(hipMalloc(&g_defer_list, sizeof(int32_t) * (size_t)n_pos), "alloc deferred groups"))) return rc;
-                if (!g_defer_count && (rc = hip_check(hipMalloc(&g_defer_count, sizeof(int32_t)), "alloc deferred count"))) return rc;
-                g_defer_cap = n_pos;
-            }
-            if ((rc = hip_check(hipMemsetAsync(g_defer_count, 0, sizeof(int32_t), stream), "zero deferred count"))) return rc;
+            if ((rc = ensure_defer_list(n_pos, true, stream))) return rc;
             a.group_list = g_defer_list; a.group_count = g_defer_count;
             launch(a);
             FbArgs d = a;
@@ -1368,9 +1349,7 @@ int launch_forward_backward_records(const kge_model_desc &m, const float *const 
     a.frec = d_rec + (size_t)rec_offset * a.D; a.fdst = d_dst + rec_offset;
     a.ent_total = (int)m.ent_total; a.rel_total = (int)m.rel_total;
     a.hub_base = sp.ent_rows; a.hub_k = (int)sp.hub_k; a.hub_rows = (int)sp.hub_rows;
-    if (!g_skipped && (rc = hip_check(hipMalloc(&g_skipped, sizeof(int32_t)), "alloc skipped-negatives counter"))) return rc;
-    if ((rc = hip_check(hipMemsetAsync(g_skipped, 0, sizeof(int32_t), stream), "zero skipped-negatives counter"))) return rc;
-    a.skipped = g_skipped;
+    if ((rc = arm_skipped_counter(a, stream))) return rc;
     switch (m.model) {
         case KGE_TRANSE: rc = dispatch_fb_records<KGE_TRANSE>(a, d_loss, stream); break;
         case KGE_TRANSH: rc = dispatch_fb_records<KGE_TRANSH>(a, d_loss, stream); break;
@@ -1456,14 +1435,7 @@ int launch_forward_backward(const kge_model_desc &m, const float *const tables[4
             launch_pair_emit(m.model, a, stream);
             record_emit_done(stream);
         } else {
-            if (n_pos > g_defer_cap) {
-                if (g_defer_list) (void)hipFree(g_defer_list);
-                g_defer_list = nullptr;
-                if ((rc = hip_check(hipMalloc(&g_defer_list, sizeof(int32_t) * (size_t)n_pos), "alloc deferred groups"))) return rc;
-                if (!g_defer_count && (rc = hip_check(hipMalloc(&g_defer_count, sizeof(int32_t)), "alloc deferred count"))) return rc;
-                g_defer_cap = n_pos;
-            }
-            if ((rc = hip_check(hipMemsetAsync(g_defer_count, 0, sizeof(int32_t), stream), "zero deferred count"))) return rc;
+            if ((rc = ensure_defer_list(n_pos, true, stream))) return rc;
             a.group_list = g_defer_list; a.group_count = g_defer_count;
             launch_pair_emit(m.model, a, stream);
             record_emit_done(stream);
@@ -1501,11 +1473,7 @@ int launch_forward_backward(const kge_model_desc &m, const float *const tables[4
         a.frec = frec; a.fdst = fdst;
         a.ent_total = (int)m.ent_total; a.rel_total = (int)m.rel_total;
         a.hub_base = ent_rows; a.hub_k = (int)hub_k; a.hub_rows = (int)hub_rows;
-        if (inplace) {
-            if (!g_skipped && (rc = hip_check(hipMalloc(&g_skipped, sizeof(int32_t)), "alloc skipped-negatives counter"))) return rc;
-            if ((rc = hip_check(hipMemsetAsync(g_skipped, 0, sizeof(int32_t), stream), "zero skipped-negatives counter"))) return rc;
-            a.skipped = g_skipped;
-        }
+        if (inplace && (rc = arm_skipped_counter(a, stream))) return rc;
         switch (m.model) {
             case KGE_TRANSE: rc = dispatch_fb_records<KGE_TRANSE>(a, d_loss, stream); break;
             case KGE_TRANSH: rc = dispatch_fb_records<KGE_TRANSH>(a, d_loss, stream); break;

@@ -302,13 +302,11 @@ __global__ __launch_bounds__(THREADS) void persistent_steps_kernel(PersistArgs p
     }
 }
 
-GridBarrier *g_bar = nullptr;
-float *g_partials = nullptr, *g_lr = nullptr;
-int32_t *g_batch = nullptr;
-int64_t g_batch_cap = 0, g_lr_cap = 0;
-float *g_hub_rel = nullptr, *g_hub_auxr = nullptr;
-int64_t g_hub_elems = 0;
-unsigned long long *g_trace = nullptr;
+DevBuf<GridBarrier> g_bar;
+DevBuf<float> g_partials, g_lr;
+DevBuf<int32_t> g_batch;   // two batches of [3][batch_len]: this step's and the next
+DevBuf<float> g_hub[2];    // rel, auxr
+DevBuf<unsigned long long> g_trace;
 
 }  // namespace
 
@@ -358,22 +356,12 @@ extern "C" int kge_train_steps_persistent(const kge_model_desc *m, float *const 
     if (cus < 1) return fail(KGE_ERR_NO_DEVICE, "kge_train_steps_persistent: no compute units reported");
     const unsigned blocks = (unsigned)cus;        // one workgroup per CU: co-resident by construction
     // ---- workspace ----
-    if (!g_bar && (rc = hip_check(hipMalloc(&g_bar, sizeof(GridBarrier)), "alloc grid barrier"))) return rc;
-    if (!g_partials && (rc = hip_check(hipMalloc(&g_partials, sizeof(float) * 2 * 1024), "alloc loss partials"))) return rc;
+    if ((rc = g_bar.reserve(1, "alloc grid barrier"))) return rc;
+    if ((rc = g_partials.reserve(2 * 1024, "alloc loss partials"))) return rc;
     if (blocks > 1024) return fail(KGE_ERR_UNSUPPORTED, "kge_train_steps_persistent: more than 1024 compute units");
     const int64_t batch_len = B * (1 + n_neg);
-    if (batch_len > g_batch_cap) {
-        if (g_batch) (void)hipFree(g_batch);
-        g_batch = nullptr;
-        if ((rc = hip_check(hipMalloc(&g_batch, sizeof(int32_t) * 2 * 3 * (size_t)batch_len), "alloc persistent batch"))) return rc;   // two batches: this step's and the next
-        g_batch_cap = batch_len;
-    }
-    if (n_steps > g_lr_cap) {
-        if (g_lr) (void)hipFree(g_lr);
-        g_lr = nullptr;
-        if ((rc = hip_check(hipMalloc(&g_lr, sizeof(float) * (size_t)n_steps), "alloc learning rates"))) return rc;
-        g_lr_cap = n_steps;
-    }
+    if ((rc = g_batch.reserve(2 * 3 * batch_len, "alloc persistent batch"))) return rc;
+    if ((rc = g_lr.reserve(n_steps, "alloc learning rates"))) return rc;
     if ((rc = hip_check(hipMemcpyAsync(g_lr, h_lr, sizeof(float) * (size_t)n_steps, hipMemcpyHostToDevice, stream), "upload learning rates"))) return rc;
     if ((rc = hip_check(hipMemsetAsync(g_bar, 0, sizeof(GridBarrier), stream), "zero grid barrier"))) return rc;
     PersistArgs pa = {};
@@ -398,17 +386,13 @@ extern "C" int kge_train_steps_persistent(const kge_model_desc *m, float *const 
         if (copies > 64) copies = 64;
         const int64_t per_copy = m->rel_total * (int64_t)a.D;
         if (copies > 1) {
-            if (copies * per_copy > g_hub_elems) {
-                if (g_hub_rel) (void)hipFree(g_hub_rel);
-                if (g_hub_auxr) (void)hipFree(g_hub_auxr);
-                g_hub_rel = g_hub_auxr = nullptr;
-                g_hub_elems = copies * per_copy;
-                if ((rc = hip_check(hipMalloc(&g_hub_rel, sizeof(float) * (size_t)g_hub_elems), "alloc hub copies"))) return rc;
-                if ((rc = hip_check(hipMalloc(&g_hub_auxr, sizeof(float) * (size_t)g_hub_elems), "alloc hub copies"))) return rc;
-                if ((rc = hip_check(hipMemset(g_hub_rel, 0, sizeof(float) * (size_t)g_hub_elems), "zero hub copies"))) return rc;
-                if ((rc = hip_check(hipMemset(g_hub_auxr, 0, sizeof(float) * (size_t)g_hub_elems), "zero hub copies"))) return rc;
+            for (auto &buf : g_hub) {
+                bool grew;
+                rc = buf.reserve(copies * per_copy, "alloc hub copies", &grew);
+                if (!rc && grew && (rc = hip_check(hipMemset(buf, 0, sizeof(float) * (size_t)(copies * per_copy)), "zero hub copies"))) buf.free();
+                if (rc) return rc;
             }
-            a.copies_rel = g_hub_rel; a.copies_auxr = g_hub_auxr; a.hub_k = (int)copies;
+            a.copies_rel = g_hub[0]; a.copies_auxr = g_hub[1]; a.hub_k = (int)copies;
             pa.fold_k = (int)copies; pa.fold_elems = per_copy;
         }
     }
@@ -443,7 +427,7 @@ extern "C" int kge_train_steps_persistent(const kge_model_desc *m, float *const 
     pa.B = B; pa.W = (int)W;
     pa.touch = e.persist_touch; pa.ahead = e.persist_ahead;
     if (e.persist_trace) {
-        if (!g_trace && (rc = hip_check(hipMalloc(&g_trace, sizeof(unsigned long long) * (6 * kTraceSteps + kTraceBlocks)), "alloc phase trace"))) return rc;
+        if ((rc = g_trace.reserve(6 * kTraceSteps + kTraceBlocks, "alloc phase trace"))) return rc;
         if ((rc = hip_check(hipMemsetAsync(g_trace, 0, sizeof(unsigned long long) * (6 * kTraceSteps + kTraceBlocks), stream), "zero phase trace"))) return rc;
         pa.trace = g_trace;
     }
@@ -498,7 +482,7 @@ extern "C" int kge_persistent_aborted(int32_t *flag) {
     *flag = 0;
     if (!g_bar) return KGE_OK;
     unsigned v = 0;
-    int rc = hip_check(hipMemcpy(&v, &g_bar->abort_flag[0], sizeof(unsigned), hipMemcpyDeviceToHost), "read abort flag");
+    int rc = hip_check(hipMemcpy(&v, &g_bar.ptr()->abort_flag[0], sizeof(unsigned), hipMemcpyDeviceToHost), "read abort flag");
     *flag = (int32_t)v;
     return rc;
 }

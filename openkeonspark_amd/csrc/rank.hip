@@ -257,22 +257,10 @@ int launch_rank(bool mean, RankTriplesArgs a, long long nblocks, hipStream_t str
 }
 
 // workspace of the calls, grown on demand; this file's own
-float *g_T = nullptr, *g_P = nullptr;
-int64_t g_T_cap = 0, g_P_cap = 0;
-int4 *g_req = nullptr;
-int64_t g_req_cap = 0;
+DevBuf<float> g_T, g_P;
+DevBuf<int4> g_req;
 std::vector<Int4> g_req_host;   // source of the last upload: rewritten only once g_req_done has passed
 hipEvent_t g_req_done = nullptr;
-
-template <typename T>
-int grow(T *&buf, int64_t &cap, int64_t need, const char *what) {
-    if (need <= cap) return KGE_OK;
-    if (buf) (void)hipFree(buf);
-    buf = nullptr; cap = 0;
-    int rc = hip_check(hipMalloc(&buf, sizeof(T) * (size_t)need), what);
-    if (!rc) cap = need;
-    return rc;
-}
 
 }  // namespace
 
@@ -339,9 +327,9 @@ extern "C" int kge_rank_triples(const kge_model_desc *m, const float *const tabl
         }
         rel_block[(size_t)R] = b;
     }
-    if ((rc = grow(g_req, g_req_cap, n_req + n_blocks, "alloc rank requests"))) return rc;
-    if ((rc = grow(g_T, g_T_cap, E * D, "alloc rank candidate table"))) return rc;
-    if (m->model == KGE_TRANSR && (rc = grow(g_P, g_P_cap, (E + 1) * D, "alloc rank projections"))) return rc;
+    if ((rc = g_req.reserve(n_req + n_blocks, "alloc rank requests"))) return rc;
+    if ((rc = g_T.reserve(E * D, "alloc rank candidate table"))) return rc;
+    if (m->model == KGE_TRANSR && (rc = g_P.reserve((E + 1) * D, "alloc rank projections"))) return rc;
     if (!g_req_done && (rc = hip_check(hipEventCreateWithFlags(&g_req_done, hipEventDisableTiming), "create rank event"))) return rc;
     if ((rc = hip_check(hipMemcpyAsync(g_req, host.data(), sizeof(Int4) * host.size(), hipMemcpyHostToDevice, stream), "upload rank requests"))) return rc;
     if ((rc = hip_check(hipEventRecord(g_req_done, stream), "record rank request upload"))) return rc;

@@ -378,29 +378,14 @@ __global__ __launch_bounds__(256) void relpred_rank_kernel(RelSelectArgs a) {
 unsigned pow2_at_least(unsigned x) { unsigned p = 1; while (p < x) p <<= 1; return p; }
 
 // workspace of the calls, grown on demand
-float *g_S = nullptr, *g_P = nullptr;
-int64_t g_S_cap = 0, g_P_cap = 0;
-int32_t *g_slot = nullptr;        // [E] -1 between calls
-int64_t g_slot_cap = 0;
-int32_t *g_uent = nullptr;        // [ucap] distinct entities, then [1] their count, then [2][chunk] query slots
-int64_t g_uent_cap = 0;
-long long *g_counts = nullptr;
-int64_t g_counts_cap = 0;
-int32_t *g_qslot = nullptr;       // [cap] = 0, 1, ..., cap-1: the query slots of kge_relation_prediction_rows' chunk rows
-int64_t g_qslot_cap = 0;
+DevBuf<float> g_S, g_P;
+DevBuf<int32_t> g_slot;        // [E] -1 between calls
+DevBuf<int32_t> g_uent;        // [ucap] distinct entities, then [1] their count, then [2][chunk] query slots
+DevBuf<long long> g_counts;
+DevBuf<int32_t> g_qslot;       // [cap] = 0, 1, ..., cap-1: the query slots of kge_relation_prediction_rows' chunk rows
 
 __global__ void relpred_iota_kernel(int32_t *__restrict__ out, long long n) {
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) out[i] = (int32_t)i;
-}
-
-template <typename T>
-int grow(T *&buf, int64_t &cap, int64_t need, const char *what) {
-    if (need <= cap) return KGE_OK;
-    if (buf) (void)hipFree(buf);
-    buf = nullptr; cap = 0;
-    int rc = hip_check(hipMalloc(&buf, sizeof(T) * (size_t)need), what);
-    if (!rc) cap = need;
-    return rc;
 }
 
 template <int MODEL, int L, int C>
@@ -465,7 +450,7 @@ int score_chunk(const kge_model_desc &m, const float *const tables[KGE_MAX_TABLE
     hipLaunchKernelGGL(relpred_undedup_kernel, dim3(blocks), dim3(256), 0, stream, g_slot, g_uent, ucount, (long long)ucap);
     if ((rc = hip_check(hipGetLastError(), "relation dedup launch"))) return rc;
     const int64_t per_rel = ucap * Dr;
-    const int64_t rb_max = std::max<int64_t>(1, std::min<int64_t>(R, g_P_cap / per_rel));
+    const int64_t rb_max = std::max<int64_t>(1, std::min<int64_t>(R, g_P.cap() / per_rel));
     a.P = g_P; a.uh = uh; a.ut = ut; a.ucap = ucap;
     for (int64_t r0 = 0; r0 < R; r0 += rb_max) {
         const int rb = (int)std::min<int64_t>(rb_max, R - r0);
@@ -486,22 +471,18 @@ int prepare(const kge_model_desc &m, int64_t n, int64_t &chunk) {
     const int64_t budget = std::max<int64_t>(engine().relpred_chunk_bytes, 1);
     chunk = std::max<int64_t>(1, std::min<int64_t>(n, budget / (R * (int64_t)sizeof(float))));
     int rc;
-    if ((rc = grow(g_S, g_S_cap, chunk * R, "alloc relation scores"))) return rc;
+    if ((rc = g_S.reserve(chunk * R, "alloc relation scores"))) return rc;
     if (m.model == KGE_TRANSR) {
         const int64_t ucap = std::min<int64_t>(2 * chunk, E);
-        if ((rc = grow(g_uent, g_uent_cap, ucap + 1 + 2 * chunk, "alloc distinct entities"))) return rc;
-        if (g_slot_cap < E) {
-            if ((rc = grow(g_slot, g_slot_cap, E, "alloc entity slot map"))) return rc;
-            if ((rc = hip_check(hipMemset(g_slot, 0xFF, sizeof(int32_t) * (size_t)E), "clear entity slot map"))) return rc;
-        }
+        if ((rc = g_uent.reserve(ucap + 1 + 2 * chunk, "alloc distinct entities"))) return rc;
+        bool grew;
+        if ((rc = g_slot.reserve(E, "alloc entity slot map", &grew))) return rc;
+        if (grew && (rc = hip_check(hipMemset(g_slot, 0xFF, sizeof(int32_t) * (size_t)E), "clear entity slot map"))) { g_slot.free(); return rc; }
         // projections of at least one relation, else of as many as fit the chunk budget
         const int64_t per_rel = ucap * m.rel_dim;
         const int64_t want = per_rel * std::max<int64_t>(1, std::min<int64_t>(R, budget / (per_rel * (int64_t)sizeof(float))));
-        if (g_P_cap < want || g_P_cap > 2 * want) {
-            if (g_P) (void)hipFree(g_P);
-            g_P = nullptr; g_P_cap = 0;
-            if ((rc = grow(g_P, g_P_cap, want, "alloc relation projections"))) return rc;
-        }
+        if (g_P.cap() > 2 * want) g_P.free();   // the one shrink rule: a chunk budget that fell leaves no oversized buffer behind
+        if ((rc = g_P.reserve(want, "alloc relation projections"))) return rc;
     }
     return KGE_OK;
 }
@@ -564,7 +545,7 @@ extern "C" int kge_relation_prediction(const kge_model_desc *m, const float *con
     if (count == 0) return KGE_OK;
     int64_t chunk;
     if ((rc = prepare(*m, count, chunk))) return rc;
-    if ((rc = grow(g_counts, g_counts_cap, 4 * count, "alloc relation ranks"))) return rc;
+    if ((rc = g_counts.reserve(4 * count, "alloc relation ranks"))) return rc;
     const int32_t *base = reinterpret_cast<const int32_t *>(test + first);   // (h, t, r, 0)
     s.S = g_S; s.qs = 4; s.R = m->rel_total;
     for (int64_t c0 = 0; c0 < count; c0 += chunk) {
@@ -603,10 +584,11 @@ extern "C" int kge_relation_prediction_rows(const kge_model_desc *m, const float
     if (!d_query_rows || !d_counts || !tables[1]) return fail(KGE_ERR_BAD_ARG, "kge_relation_prediction_rows: null relation table, query or output array");
     int64_t chunk;
     if ((rc = prepare(*m, count, chunk))) return rc;
-    if (g_qslot_cap < 2 * chunk) {
-        if ((rc = grow(g_qslot, g_qslot_cap, 2 * chunk, "alloc relation query slots"))) return rc;
-        hipLaunchKernelGGL(relpred_iota_kernel, dim3((unsigned)std::min<int64_t>((g_qslot_cap + 255) / 256, 4096)), dim3(256), 0, stream,
-                           g_qslot, (long long)g_qslot_cap);
+    bool grew;
+    if ((rc = g_qslot.reserve(2 * chunk, "alloc relation query slots", &grew))) return rc;
+    if (grew) {
+        hipLaunchKernelGGL(relpred_iota_kernel, dim3((unsigned)std::min<int64_t>((g_qslot.cap() + 255) / 256, 4096)), dim3(256), 0, stream,
+                           g_qslot, (long long)g_qslot.cap());
         if ((rc = hip_check(hipGetLastError(), "relation query slots launch"))) return rc;
     }
     const int64_t D = m->ent_dim;

@@ -61,18 +61,18 @@ struct TcDev {
     bool ready = false;
     uint64_t generation = 0;
     int64_t R = 0, total[2] = {0, 0};
-    int32_t *lef[2] = {nullptr, nullptr}, *rig[2] = {nullptr, nullptr};
-    int4 *items[2] = {nullptr, nullptr};      // (relation, first position, count, 0): chunks of at most kChunk triples
+    DevBuf<int32_t> lef[2], rig[2];
+    DevBuf<int4> items[2];                    // (relation, first position, count, 0): chunks of at most kChunk triples
     int n_items[2] = {0, 0};
-    uint32_t *kmin = nullptr, *kmax = nullptr;
-    float *mn = nullptr;
-    int32_t *nint = nullptr, *path = nullptr;
-    long long *off = nullptr;
-    int32_t *hist = nullptr;
-    long long hist_cap = 0;
-    TcStatus *status = nullptr, *status_host = nullptr;
+    DevBuf<uint32_t> kmin, kmax;
+    DevBuf<float> mn;
+    DevBuf<int32_t> nint, path;
+    DevBuf<long long> off;
+    DevBuf<int32_t> hist;
+    DevBuf<TcStatus> status;
+    TcStatus *status_host = nullptr;
     hipEvent_t ev = nullptr;
-    long long *out_off = nullptr;             // ROC: every relation's first element of d_tpfp
+    DevBuf<long long> out_off;                // ROC: every relation's first element of d_tpfp
     int32_t *nint_host = nullptr;             // ROC: pinned [R], read in the one wait
     std::vector<char> has_valid;              // ROC: host copy of lef[0][r] >= 0
 };
@@ -416,21 +416,6 @@ __global__ __launch_bounds__(kFitThreads) void tc_roc_kernel(const int32_t *__re
 }
 
 // ---------------------------------------------------------------------------------------------
-template <typename T>
-int upload_vec(T *&dst, const std::vector<T> &src, const char *what) {
-    if (dst) { (void)hipFree(dst); dst = nullptr; }
-    int rc = hip_check(hipMalloc(&dst, sizeof(T) * (src.size() ? src.size() : 1)), what);
-    if (rc) return rc;
-    if (!src.empty()) rc = hip_check(hipMemcpy(dst, src.data(), sizeof(T) * src.size(), hipMemcpyHostToDevice), what);
-    return rc;
-}
-
-template <typename T>
-int alloc_n(T *&dst, size_t n, const char *what) {
-    if (dst) { (void)hipFree(dst); dst = nullptr; }
-    return hip_check(hipMalloc(&dst, sizeof(T) * (n ? n : 1)), what);
-}
-
 // the range arrays and the chunk lists on the device: once per importTestFiles
 int ensure_tc_device() {
     TcDev &d = g_tc;
@@ -442,8 +427,8 @@ int ensure_tc_device() {
     d.ready = false;
     for (int s = 0; s < 2; s++) {
         if ((int64_t)l.lef[s]->size() != R) return fail(KGE_ERR_BAD_ARG, "triple classification: relation ranges do not match the training set's relations");
-        if ((rc = upload_vec(d.lef[s], *l.lef[s], "upload relation ranges"))) return rc;
-        if ((rc = upload_vec(d.rig[s], *l.rig[s], "upload relation ranges"))) return rc;
+        if ((rc = d.lef[s].upload(*l.lef[s], "upload relation ranges"))) return rc;
+        if ((rc = d.rig[s].upload(*l.rig[s], "upload relation ranges"))) return rc;
         std::vector<int4> items;
         for (int64_t r = 0; r < R; r++) {
             const int lo = (*l.lef[s])[(size_t)r], hi = (*l.rig[s])[(size_t)r];
@@ -451,22 +436,22 @@ int ensure_tc_device() {
             if (hi < lo || hi >= l.total[s]) return fail(KGE_ERR_BAD_ARG, "triple classification: relation range outside its list");
             for (int at = lo; at <= hi; at += kChunk) items.push_back(make_int4((int)r, at, std::min(kChunk, hi - at + 1), 0));
         }
-        if ((rc = upload_vec(d.items[s], items, "upload classification chunks"))) return rc;
+        if ((rc = d.items[s].upload(items, "upload classification chunks"))) return rc;
         d.n_items[s] = (int)items.size();
         d.total[s] = l.total[s];
     }
-    if ((rc = alloc_n(d.kmin, (size_t)R, "alloc classification state"))) return rc;
-    if ((rc = alloc_n(d.kmax, (size_t)R, "alloc classification state"))) return rc;
-    if ((rc = alloc_n(d.mn, (size_t)R, "alloc classification state"))) return rc;
-    if ((rc = alloc_n(d.nint, (size_t)R, "alloc classification state"))) return rc;
-    if ((rc = alloc_n(d.path, (size_t)R, "alloc classification state"))) return rc;
-    if ((rc = alloc_n(d.off, (size_t)R, "alloc classification state"))) return rc;
-    if ((rc = alloc_n(d.out_off, (size_t)R, "alloc classification state"))) return rc;
+    if ((rc = d.kmin.replace(R, "alloc classification state"))) return rc;
+    if ((rc = d.kmax.replace(R, "alloc classification state"))) return rc;
+    if ((rc = d.mn.replace(R, "alloc classification state"))) return rc;
+    if ((rc = d.nint.replace(R, "alloc classification state"))) return rc;
+    if ((rc = d.path.replace(R, "alloc classification state"))) return rc;
+    if ((rc = d.off.replace(R, "alloc classification state"))) return rc;
+    if ((rc = d.out_off.replace(R, "alloc classification state"))) return rc;
     if (d.nint_host) { (void)hipHostFree(d.nint_host); d.nint_host = nullptr; }
     if ((rc = hip_check(hipHostMalloc(&d.nint_host, sizeof(int32_t) * (size_t)(R ? R : 1)), "alloc classification status"))) return rc;
     d.has_valid.assign((size_t)R, 0);
     for (int64_t r = 0; r < R; r++) d.has_valid[(size_t)r] = (*l.lef[0])[(size_t)r] >= 0;
-    if (!d.status && (rc = alloc_n(d.status, 1, "alloc classification state"))) return rc;
+    if ((rc = d.status.reserve(1, "alloc classification state"))) return rc;
     if (!d.status_host && (rc = hip_check(hipHostMalloc(&d.status_host, sizeof(TcStatus)), "alloc classification status"))) return rc;
     if (!d.ev && (rc = hip_check(hipEventCreateWithFlags(&d.ev, hipEventDisableTiming), "create event"))) return rc;
     d.generation = eval_tc_generation();
@@ -503,15 +488,11 @@ extern "C" int kge_tc_fit(const float *d_pos, const float *d_neg, INT n_valid, f
     // the caller's copy only now: on the error returns above d_n_interval is as untouched as d_thresh
     if (d_n_interval && (rc = hip_check(hipMemcpyAsync(d_n_interval, d.nint, sizeof(int32_t) * (size_t)d.R, hipMemcpyDeviceToDevice, stream), "copy n_interval"))) return rc;
     if (d.n_items[0] == 0) return KGE_OK;
+    // at least one bin: tc_fit forms hist + off[r] on every path
+    if ((rc = d.hist.reserve(st.bins > 0 ? st.bins : 1, "alloc classification histogram"))) return rc;
     if (st.bins > 0) {
-        if (d.hist_cap < st.bins) {
-            if ((rc = alloc_n(d.hist, (size_t)st.bins, "alloc classification histogram"))) { d.hist_cap = 0; return rc; }
-            d.hist_cap = st.bins;
-        }
         if ((rc = hip_check(hipMemsetAsync(d.hist, 0, sizeof(int32_t) * (size_t)st.bins, stream), "clear classification histogram"))) return rc;
         tc_bin_kernel<<<d.n_items[0], kThreads, 0, stream>>>(d.items[0], d_pos, d_neg, d.mn, d.nint, d.path, d.off, d.hist);
-    } else if (!d.hist) {
-        if ((rc = alloc_n(d.hist, 1, "alloc classification histogram"))) return rc;   // tc_fit forms hist + off[r] on every path
     }
     tc_fit_kernel<<<(unsigned)d.R, kFitThreads, 0, stream>>>(d.lef[0], d.rig[0], d_pos, d_neg, d.mn, d.nint, d.path, d.off, d.hist, d_thresh);
     return hip_check(hipGetLastError(), "kge_tc_fit launch");
@@ -568,15 +549,11 @@ extern "C" int kge_tc_roc(const float *d_vpos, const float *d_vneg, INT n_valid,
         h_offsets[r + 1] = h_offsets[r] + (d.has_valid[(size_t)r] ? 2 * ((int64_t)d.nint_host[r] + 1) : 0);
     if (d_tpfp && tpfp_capacity < h_offsets[d.R]) return fail(KGE_ERR_BAD_ARG, "kge_tc_roc: tpfp_capacity is below h_offsets[rel_total] (nothing written)");
     if (d.R == 0) return KGE_OK;
+    // at least one bin: tc_roc forms hist + off[r] on every path
+    if ((rc = d.hist.reserve(st.bins > 0 ? st.bins : 1, "alloc classification histogram"))) return rc;
     if (st.bins > 0) {
-        if (d.hist_cap < st.bins) {
-            if ((rc = alloc_n(d.hist, (size_t)st.bins, "alloc classification histogram"))) { d.hist_cap = 0; return rc; }
-            d.hist_cap = st.bins;
-        }
         if ((rc = hip_check(hipMemsetAsync(d.hist, 0, sizeof(int32_t) * (size_t)st.bins, stream), "clear classification histogram"))) return rc;
         tc_roc_bin_kernel<<<d.n_items[split], kThreads, 0, stream>>>(d.items[split], d_pos, d_neg, d.mn, d.nint, d.path, d.off, d.hist);
-    } else if (!d.hist) {
-        if ((rc = alloc_n(d.hist, 1, "alloc classification histogram"))) return rc;   // tc_roc forms hist + off[r] on every path
     }
     tc_roc_kernel<<<(unsigned)d.R, kFitThreads, 0, stream>>>(d.lef[split], d.rig[split], d_pos, d_neg, d.mn, d.nint, d.path, d.off, d.hist,
                                                             d.out_off, d_tpfp, d_auc2);

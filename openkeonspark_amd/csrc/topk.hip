@@ -303,24 +303,11 @@ __global__ __launch_bounds__(256) void topk_merge_kernel(TopkArgs a, int slices)
 unsigned pow2_at_least(unsigned x) { unsigned p = 1; while (p < x) p <<= 1; return p; }
 
 // workspace of the calls, grown on demand
-float *g_T = nullptr, *g_P = nullptr, *g_inv = nullptr;
-int64_t g_T_cap = 0, g_P_cap = 0, g_inv_cap = 0;
-uint64_t *g_part = nullptr;
-int64_t g_part_cap = 0;
-int32_t *g_order = nullptr;
-int64_t g_order_cap = 0;
+DevBuf<float> g_T, g_P, g_inv;
+DevBuf<uint64_t> g_part;
+DevBuf<int32_t> g_order;
 std::vector<int32_t> g_order_host;   // source of the last order upload: rewritten only once g_order_done has passed
 hipEvent_t g_order_done = nullptr;
-
-template <typename T>
-int grow(T *&buf, int64_t &cap, int64_t need, const char *what) {
-    if (need <= cap) return KGE_OK;
-    if (buf) (void)hipFree(buf);
-    buf = nullptr; cap = 0;
-    int rc = hip_check(hipMalloc(&buf, sizeof(T) * (size_t)need), what);
-    if (!rc) cap = need;
-    return rc;
-}
 
 int launch_table(int model, const FbArgs &a, int64_t r, int64_t E, float *T, float *inv, hipStream_t stream) {
     bool shaped = false;
@@ -352,7 +339,7 @@ int launch_select_t(TopkArgs a, hipStream_t stream) {
     slices = (a.E + a.slice_len - 1) / a.slice_len;
     int rc;
     if (slices > 1) {
-        if ((rc = grow(g_part, g_part_cap, a.nq * slices * a.k, "alloc top-k partial lists"))) return rc;
+        if ((rc = g_part.reserve(a.nq * slices * a.k, "alloc top-k partial lists"))) return rc;
         a.part = g_part;
     } else {
         a.part = RANGE ? a.keys : nullptr;
@@ -428,8 +415,8 @@ extern "C" int kge_topk_entities(const kge_model_desc *m, const float *const tab
     int rc;
     // projected rows are stored for TransH / TransD only: TransE's are the entity rows, TransR's the projection buffer
     const bool own_rows = m->model == KGE_TRANSH || m->model == KGE_TRANSD;
-    if (table && own_rows && (rc = grow(g_T, g_T_cap, E * D, "alloc top-k candidate table"))) return rc;
-    if (table && (rc = grow(g_inv, g_inv_cap, E, "alloc top-k inverse norms"))) return rc;
+    if (table && own_rows && (rc = g_T.reserve(E * D, "alloc top-k candidate table"))) return rc;
+    if (table && (rc = g_inv.reserve(E, "alloc top-k inverse norms"))) return rc;
     if (m->model == KGE_TRANSE) {
         // the candidates do not depend on the relation: all queries in the caller's order, one launch, no synchronisation
         if (table && (rc = launch_table(m->model, a.fa, 0, E, nullptr, g_inv, stream))) return rc;
@@ -447,11 +434,11 @@ extern "C" int kge_topk_entities(const kge_model_desc *m, const float *const tab
     order.resize((size_t)n);
     for (int64_t i = 0; i < n; i++) order[(size_t)i] = (int32_t)i;
     std::stable_sort(order.begin(), order.end(), [&](int32_t x, int32_t y) { return rel[(size_t)x] < rel[(size_t)y]; });
-    if ((rc = grow(g_order, g_order_cap, n, "alloc top-k query order"))) return rc;
+    if ((rc = g_order.reserve(n, "alloc top-k query order"))) return rc;
     if ((rc = hip_check(hipMemcpyAsync(g_order, order.data(), sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, stream), "upload query order"))) return rc;
     if (!g_order_done && (rc = hip_check(hipEventCreateWithFlags(&g_order_done, hipEventDisableTiming), "create top-k event"))) return rc;
     if ((rc = hip_check(hipEventRecord(g_order_done, stream), "record top-k order upload"))) return rc;
-    if (m->model == KGE_TRANSR && (rc = grow(g_P, g_P_cap, (E + 1) * D, "alloc top-k projections"))) return rc;
+    if (m->model == KGE_TRANSR && (rc = g_P.reserve((E + 1) * D, "alloc top-k projections"))) return rc;
     for (int64_t q0 = 0; q0 < n;) {
         const int32_t r = rel[(size_t)order[(size_t)q0]];
         int64_t q1 = q0;
@@ -502,7 +489,7 @@ extern "C" int kge_topk_entities_range(const kge_model_desc *m, const float *con
     const int64_t budget = engine().topk_table_max_bytes;
     const bool table = budget > 0 && rows * D * (int64_t)sizeof(float) <= budget;
     if (table) {
-        if ((rc = grow(g_inv, g_inv_cap, rows, "alloc top-k inverse norms"))) return rc;
+        if ((rc = g_inv.reserve(rows, "alloc top-k inverse norms"))) return rc;
         if ((rc = launch_table(KGE_TRANSE, a.fa, 0, rows, nullptr, g_inv, stream))) return rc;
         a.T = a.fa.ent;
         a.Tinv = g_inv;

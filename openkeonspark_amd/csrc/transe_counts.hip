@@ -43,69 +43,51 @@ namespace {
 int bits_for_rows(int64_t v) { int b = 1; while ((int64_t(1) << b) <= v) b++; return b; }
 
 struct CtWork {
-    uint32_t *rec = nullptr;
-    float *hub_sums = nullptr;         // deterministic float-record reduce: per-copy sums of the relation-side rows
-    size_t hub_sums_cap = 0;
-    int32_t *hub_marks = nullptr;      // lazy-Adam form of it: [copy][hub row] 1 = the copy took a record this step (zero between steps)
-    size_t hub_marks_cap = 0;
-    int32_t *dst = nullptr, *dst_sorted = nullptr, *ids = nullptr, *ids_sorted = nullptr;
-    int32_t *n_valid = nullptr;
-    int32_t *tile_hist = nullptr, *bucket_start = nullptr;   // LDS-bucket path: bucket totals + cursors, bucket starts
-    int32_t *pairs = nullptr;                                  // [2*cap] (record id, destination) grouped by bucket
-    float2 *pair_aux = nullptr;                                // [cap] pair-count path: (a, +-1/|projected|) per record
-    int64_t pair_aux_cap = 0;
-    int64_t cap_hist = 0;
-    void *sort_tmp = nullptr;
-    size_t sort_tmp_bytes = 0, rec_elems = 0;
-    int64_t cap_idx = 0;
-    int32_t *bflag = nullptr;
-    int64_t bflag_cap = 0;
+    DevBuf<uint32_t> rec;
+    DevBuf<float> hub_sums;            // deterministic float-record reduce: per-copy sums of the relation-side rows
+    DevBuf<int32_t> hub_marks;         // lazy-Adam form of it: [copy][hub row] 1 = the copy took a record this step (zero between steps)
+    DevBuf<int32_t> dst, dst_sorted, ids, ids_sorted;
+    DevBuf<int32_t> n_valid;
+    DevBuf<int32_t> tile_hist, bucket_start;   // LDS-bucket path: bucket totals + cursors, bucket starts
+    DevBuf<int32_t> pairs;                     // [2*M] (record id, destination) grouped by bucket
+    DevBuf<float2> pair_aux;                   // [M] pair-count path: (a, +-1/|projected|) per record
+    DevBuf<char> sort_tmp;                     // rocPRIM scratch (sort, scan)
+    DevBuf<float> ctxn;                        // pair-count path, TransH: normalised normal vectors
+    DevBuf<int32_t> bflag;
     // fused single-process step: the plan of segapply_kernel
-    int4 *pieces = nullptr;
-    int64_t pieces_cap = 0;
-    int32_t *n_pieces = nullptr;
-    int2 *row_span = nullptr;
-    int64_t row_span_cap = 0;
+    DevBuf<int4> pieces;
+    DevBuf<int32_t> n_pieces;
+    DevBuf<int2> row_span;
 };
 CtWork g_c;
-
-template <typename T>
-int regrow(T *&p, size_t count, const char *what) {
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    return hip_check(hipMalloc(&p, sizeof(T) * (count ? count : 1)), what);
-}
 
 // index workspace for M records (keys, ids, sort scratch) and -- rec_dwords > 0 -- an engine-owned record buffer
 // (callers of the stage-level ABI bring their own records and pass 0)
 int ensure_counts_work(int64_t M, size_t rec_dwords) {
     int rc;
-    if (M > g_c.cap_idx) {
-        const int64_t cap = M;
-        if ((rc = regrow(g_c.dst, (size_t)cap, "counts dst"))) return rc;
-        if ((rc = regrow(g_c.dst_sorted, (size_t)cap, "counts dst_sorted"))) return rc;
-        if ((rc = regrow(g_c.ids, (size_t)cap, "counts ids"))) return rc;
-        if ((rc = regrow(g_c.ids_sorted, (size_t)cap, "counts ids_sorted"))) return rc;
-        if ((rc = regrow(g_c.pairs, (size_t)cap * 2, "counts pairs"))) return rc;
-        if (!g_c.n_valid && (rc = regrow(g_c.n_valid, 1, "counts n_valid"))) return rc;
+    bool grew, sort_grew;
+    if ((rc = g_c.ids.reserve(M, "counts ids", &sort_grew))) return rc;
+    if (sort_grew) {   // record ids 0..M-1 never change; written before anything else can fail, or not kept
+        std::vector<int32_t> iota((size_t)M);
+        for (int64_t i = 0; i < M; i++) iota[(size_t)i] = (int32_t)i;
+        if ((rc = hip_check(hipMemcpy(g_c.ids, iota.data(), sizeof(int32_t) * (size_t)M, hipMemcpyHostToDevice), "counts iota"))) { g_c.ids.free(); return rc; }
+    }
+    DevBuf<int32_t> *const rest[3] = {&g_c.dst, &g_c.dst_sorted, &g_c.ids_sorted};
+    static const char *const names[3] = {"counts dst", "counts dst_sorted", "counts ids_sorted"};
+    for (int i = 0; i < 3; i++) {
+        if ((rc = rest[i]->reserve(M, names[i], &grew))) return rc;
+        sort_grew |= grew;
+    }
+    // the sort's scratch, sized for what the arrays hold, directly behind them: a failure in between would leave it at an earlier,
+    // smaller size with nothing left to grow.  Asked again while there is none (a regrow of it that failed, here or for the scan)
+    if (sort_grew || !g_c.sort_tmp) {
         size_t bytes = 0;
-        (void)rocprim::radix_sort_pairs(nullptr, bytes, g_c.dst, g_c.dst_sorted, g_c.ids, g_c.ids_sorted, (size_t)cap, 0, 32, nullptr);
-        if (bytes > g_c.sort_tmp_bytes) {
-            if (g_c.sort_tmp) (void)hipFree(g_c.sort_tmp);
-            g_c.sort_tmp = nullptr;
-            if ((rc = hip_check(hipMalloc(&g_c.sort_tmp, bytes), "counts sort temp"))) return rc;
-            g_c.sort_tmp_bytes = bytes;
-        }
-        // record ids 0..cap-1 never change
-        std::vector<int32_t> iota((size_t)cap);
-        for (int64_t i = 0; i < cap; i++) iota[(size_t)i] = (int32_t)i;
-        if ((rc = hip_check(hipMemcpy(g_c.ids, iota.data(), sizeof(int32_t) * (size_t)cap, hipMemcpyHostToDevice), "counts iota"))) return rc;
-        g_c.cap_idx = cap;
+        (void)rocprim::radix_sort_pairs(nullptr, bytes, g_c.dst.ptr(), g_c.dst_sorted.ptr(), g_c.ids.ptr(), g_c.ids_sorted.ptr(), (size_t)g_c.dst.cap(), 0, 32, nullptr);
+        if ((rc = g_c.sort_tmp.reserve((int64_t)bytes, "counts sort temp"))) return rc;
     }
-    if (rec_dwords > 0 && (size_t)M * rec_dwords > g_c.rec_elems) {
-        if ((rc = regrow(g_c.rec, (size_t)M * rec_dwords, "counts records"))) return rc;
-        g_c.rec_elems = (size_t)M * rec_dwords;
-    }
+    if ((rc = g_c.pairs.reserve(2 * M, "counts pairs"))) return rc;
+    if ((rc = g_c.n_valid.reserve(1, "counts n_valid"))) return rc;
+    if (rec_dwords > 0 && (rc = g_c.rec.reserve(M * (int64_t)rec_dwords, "counts records"))) return rc;
     return KGE_OK;
 }
 
@@ -1129,14 +1111,13 @@ __global__ __launch_bounds__(256) void segsum_pairs_kernel(const uint32_t *__res
 // plan: the fused step's form (bkt_sort_kernel<true>); the hist launch re-zeroes its piece counter.
 int bucket_sort_records(const int32_t *dst, int64_t M, int rows, int rpb, const SegPlan *plan, hipStream_t stream, const int32_t *&n_live) {
     int rc;
-    if (!g_c.bucket_start) {
-        if ((rc = regrow(g_c.bucket_start, NB + 2, "counts bucket_start"))) return rc;
-        if ((rc = regrow(g_c.tile_hist, 2 * (NB + 2), "counts bucket totals/cursors"))) return rc;
-        if ((rc = hip_check(hipMemset(g_c.tile_hist, 0, sizeof(int32_t) * 2 * (NB + 2)), "zero bucket totals"))) return rc;
-    }
+    bool grew;
+    if ((rc = g_c.bucket_start.reserve(NB + 2, "counts bucket_start"))) return rc;
+    if ((rc = g_c.tile_hist.reserve(2 * (NB + 2), "counts bucket totals/cursors", &grew))) return rc;
+    if (grew && (rc = hip_check(hipMemset(g_c.tile_hist, 0, sizeof(int32_t) * 2 * (NB + 2)), "zero bucket totals"))) { g_c.tile_hist.free(); return rc; }
     const int n_tiles = (int)((M + BTILE - 1) / BTILE);
     int32_t *totals = g_c.tile_hist, *cursor = g_c.tile_hist + (NB + 2);
-    int2 *pairs = reinterpret_cast<int2 *>(g_c.pairs);
+    int2 *pairs = reinterpret_cast<int2 *>(g_c.pairs.ptr());
     launch_bkt_hist(dst, n_tiles, (int)M, rpb, totals, plan ? plan->n_pieces : nullptr, stream);
     launch_bkt_scatter(dst, n_tiles, (int)M, rpb, totals, cursor, pairs, stream);
     if (plan) launch_bkt_sort<true>(pairs, rpb, rows, totals, cursor, *plan, stream);
@@ -1152,8 +1133,8 @@ int radix_sort_records(int32_t *dst, int64_t M, int rows, bool blank, const char
     if (blocks > 4096) blocks = 4096;
     if (blank) hipLaunchKernelGGL(blank_keys_kernel, dim3(blocks), dim3(256), 0, stream, dst, (long long)M, rows);
     else hipLaunchKernelGGL(fix_keys_kernel, dim3(blocks), dim3(256), 0, stream, dst, (long long)M, rows);
-    size_t tmp = g_c.sort_tmp_bytes;
-    int rc = hip_check(rocprim::radix_sort_pairs(g_c.sort_tmp, tmp, dst, g_c.dst_sorted, g_c.ids, g_c.ids_sorted, (size_t)M, 0,
+    size_t tmp = (size_t)g_c.sort_tmp.cap();
+    int rc = hip_check(rocprim::radix_sort_pairs(g_c.sort_tmp.ptr(), tmp, dst, g_c.dst_sorted.ptr(), g_c.ids.ptr(), g_c.ids_sorted.ptr(), (size_t)M, 0,
                                                  bits_for_rows(rows), stream), what);
     if (rc) return rc;
     hipLaunchKernelGGL(count_valid_kernel, dim3(1), dim3(64), 0, stream, g_c.dst_sorted, (int)M, rows, g_c.n_valid);
@@ -1163,12 +1144,10 @@ int radix_sort_records(int32_t *dst, int64_t M, int rows, bool blank, const char
 
 // per-copy sums of the relation-side rows, [copy][hub row][D] (zero between steps: the fold kernels re-zero what they fold)
 int ensure_hub_sums(size_t need, hipStream_t stream) {
-    if (need <= g_c.hub_sums_cap) return KGE_OK;
-    int rc;
-    if ((rc = regrow(g_c.hub_sums, need, "hub copy sums"))) return rc;
-    if ((rc = hip_check(hipMemsetAsync(g_c.hub_sums, 0, sizeof(float) * need, stream), "zero hub copy sums"))) return rc;
-    g_c.hub_sums_cap = need;
-    return KGE_OK;
+    bool grew;
+    int rc = g_c.hub_sums.reserve((int64_t)need, "hub copy sums", &grew);
+    if (!rc && grew && (rc = hip_check(hipMemsetAsync(g_c.hub_sums, 0, sizeof(float) * need, stream), "zero hub copy sums"))) g_c.hub_sums.free();
+    return rc;
 }
 
 // the lazy-Adam reduce of sorted float records and the fold of its hub copies, V floats per unit of a row
@@ -1196,7 +1175,7 @@ void launch_segsum_adam(int64_t M, const float *rec, const FloatRowSpace &rs, co
 int float_records_workspace(int64_t M, int D, float *&rec, int32_t *&dst) {
     int rc = ensure_counts_work(M, (size_t)D);
     if (rc) return rc;
-    rec = reinterpret_cast<float *>(g_c.rec);
+    rec = reinterpret_cast<float *>(g_c.rec.ptr());
     dst = g_c.dst;
     return KGE_OK;
 }
@@ -1205,9 +1184,9 @@ int float_records_reduce(int64_t M, int D, const FloatRowSpace &rs, hipStream_t 
     int rc;
     // records held by the caller: size the sort's work buffers for M; the launches below read the caller's arrays
     const bool ext = rec_ext && dst_ext;
-    if (ext && (rc = ensure_counts_work(M, (size_t)D))) return rc;
-    const float *rec = ext ? rec_ext : reinterpret_cast<const float *>(g_c.rec);
-    int32_t *dst = ext ? dst_ext : g_c.dst;
+    if (ext && (rc = ensure_counts_work(M, 0))) return rc;
+    const float *rec = ext ? rec_ext : reinterpret_cast<const float *>(g_c.rec.ptr());
+    int32_t *dst = ext ? dst_ext : g_c.dst.ptr();
     const int rows = (int)rs.rows;
     const int32_t *n_valid_p = nullptr;
     const int rpb = (rows + NB - 1) / NB;
@@ -1251,18 +1230,16 @@ int float_records_reduce_adam(int64_t M, int D, const FloatRowSpace &rs, const R
     int rc;
     const bool ext = rec_ext && dst_ext;
     if ((rc = ensure_counts_work(M, ext ? 0 : (size_t)D))) return rc;
-    const float *rec = ext ? rec_ext : reinterpret_cast<const float *>(g_c.rec);
-    int32_t *dst = ext ? dst_ext : g_c.dst;
+    const float *rec = ext ? rec_ext : reinterpret_cast<const float *>(g_c.rec.ptr());
+    int32_t *dst = ext ? dst_ext : g_c.dst.ptr();
     const int32_t *n_valid_p;
     if ((rc = radix_sort_records(dst, M, (int)rs.rows, true, "float records sort", stream, n_valid_p))) return rc;
     const int64_t hub_virtual = rs.rows - rs.hub_base;          // copies x hub rows
     const int K = rs.hub_rows > 0 ? (int)(hub_virtual / rs.hub_rows) : 0;
     if ((rc = ensure_hub_sums((size_t)hub_virtual * D, stream))) return rc;
-    if ((size_t)hub_virtual > g_c.hub_marks_cap) {
-        if ((rc = regrow(g_c.hub_marks, (size_t)hub_virtual, "hub copy marks"))) return rc;
-        if ((rc = hip_check(hipMemsetAsync(g_c.hub_marks, 0, sizeof(int32_t) * (size_t)hub_virtual, stream), "zero hub copy marks"))) return rc;
-        g_c.hub_marks_cap = (size_t)hub_virtual;
-    }
+    bool grew;
+    if ((rc = g_c.hub_marks.reserve(hub_virtual, "hub copy marks", &grew))) return rc;
+    if (grew && (rc = hip_check(hipMemsetAsync(g_c.hub_marks, 0, sizeof(int32_t) * (size_t)hub_virtual, stream), "zero hub copy marks"))) { g_c.hub_marks.free(); return rc; }
     // float4 rows where every row of every buffer starts on 16 bytes
     bool vec = D % 4 == 0 && (reinterpret_cast<uintptr_t>(rec) & 15) == 0;
     const float *const bases[4] = {rs.g_ent, rs.g_rel, rs.g_auxr, rs.g_auxe};
@@ -1287,10 +1264,7 @@ bool pair_keys_sortable(int64_t ent_total, int64_t rel_total) {
 int pair_records_workspace(int64_t M, int rd, uint32_t *&rec, int32_t *&dst, float2 *&aux) {
     int rc = ensure_counts_work(M, (size_t)rd);
     if (rc) return rc;
-    if (M > g_c.pair_aux_cap) {
-        if ((rc = regrow(g_c.pair_aux, (size_t)M, "pair records aux"))) return rc;
-        g_c.pair_aux_cap = M;
-    }
+    if ((rc = g_c.pair_aux.reserve(M, "pair records aux"))) return rc;
     rec = g_c.rec;
     dst = g_c.dst;
     aux = g_c.pair_aux;
@@ -1314,16 +1288,11 @@ int pair_records_reduce(int model, int64_t M, int64_t n_int8, int D, int rd, int
     pr.D = D; pr.R = (int)rel_total; pr.RD = rd; pr.unit = unit; pr.aux = g_c.pair_aux; pr.n_int8 = n_int8;
     pr.magic = rel_total == 1 ? 0xFFFFFFFFu : (unsigned)(((uint64_t(1) << 32) + (uint64_t)rel_total - 1) / (uint64_t)rel_total);
     if (model == KGE_TRANSH) {   // normalised normal vectors, once per step
-        static float *ctxn = nullptr;
-        static int64_t ctxn_cap = 0;
-        if (rel_total * D > ctxn_cap) {
-            if ((rc = regrow(ctxn, (size_t)(rel_total * D), "normalised normal vectors"))) return rc;
-            ctxn_cap = rel_total * D;
-        }
+        if ((rc = g_c.ctxn.reserve(rel_total * D, "normalised normal vectors"))) return rc;
         int nb = (int)((rel_total + 3) / 4);
         if (nb > 1024) nb = 1024;
-        hipLaunchKernelGGL(ctx_normalize_kernel, dim3(nb), dim3(256), 0, stream, tables[2], (int)rel_total, D, ctxn);
-        pr.ctx = ctxn;
+        hipLaunchKernelGGL(ctx_normalize_kernel, dim3(nb), dim3(256), 0, stream, tables[2], (int)rel_total, D, g_c.ctxn);
+        pr.ctx = g_c.ctxn;
     }
     const long long chunks = (M + CHUNK - 1) / CHUNK;
     const long long nb = (chunks + 3) / 4;
@@ -1724,7 +1693,7 @@ void launch_apply_listed_rows(const ApplyArgs &a, long long max_rows, hipStream_
 float *inv_table_kept(bool whole_row_space, const float *ent, const float *rel, long long all_rows) {
     Engine &e = engine();
     const bool keeps = e.inv_carry && e.inv_valid && e.inv_norm && whole_row_space && e.inv_for_ent == ent && e.inv_for_rel == rel &&
-                       e.inv_cap >= all_rows;
+                       e.inv_norm.cap() >= all_rows;
     if (!keeps) tables_written();
     return keeps ? e.inv_norm : nullptr;
 }
@@ -1799,18 +1768,11 @@ static int forward_counts_impl(const kge_model_desc *m, const float *d_ent, cons
     if (fused) {
         const int cap = std::min(engine().counts_fused_cap > 0 ? engine().counts_fused_cap : 64, std::min(127, 4 * L));   // (the kernel holds min(128, 4 L) ids per list; 127: the packed 2-bit sums stay below 256)
         const int64_t max_pieces = 3 * (M / cap + 1) + 16;     // sum of ceil(c / cap) over both lists of the rows with a list of more than cap records
-        if (max_pieces > g_c.pieces_cap) {
-            if ((rc = regrow(g_c.pieces, (size_t)max_pieces, "fused step piece table"))) return rc;
-            g_c.pieces_cap = max_pieces;
-        }
-        if (!g_c.n_pieces) {
-            if ((rc = regrow(g_c.n_pieces, 1, "fused step piece counter"))) return rc;
-            if ((rc = hip_check(hipMemset(g_c.n_pieces, 0, sizeof(int32_t)), "zero piece counter"))) return rc;
-        }
-        if (rows2 > g_c.row_span_cap) {
-            if ((rc = regrow(g_c.row_span, (size_t)rows2, "fused step row spans"))) return rc;
-            g_c.row_span_cap = rows2;
-        }
+        bool grew;
+        if ((rc = g_c.pieces.reserve(max_pieces, "fused step piece table"))) return rc;
+        if ((rc = g_c.n_pieces.reserve(1, "fused step piece counter", &grew))) return rc;
+        if (grew && (rc = hip_check(hipMemset(g_c.n_pieces, 0, sizeof(int32_t)), "zero piece counter"))) { g_c.n_pieces.free(); return rc; }
+        if ((rc = g_c.row_span.reserve(rows2, "fused step row spans"))) return rc;
         SegPlan plan;
         plan.row_span = g_c.row_span; plan.pieces = g_c.pieces; plan.n_pieces = g_c.n_pieces; plan.cap = cap;
         const int32_t *n_valid_p;
@@ -1923,8 +1885,8 @@ int kge_transe_emit_records(const kge_model_desc *m, const float *d_ent, const f
 
 int kge_transe_step_scratch_read(int which, INT offset, INT count, void *host_out) {
     if (!device_ok()) return fail(KGE_ERR_NO_DEVICE, "kge_transe_step_scratch_read: no usable HIP device");
-    const size_t have = which == 0 ? g_c.rec_elems : (which == 1 ? (size_t)g_c.cap_idx : 0);
-    const void *base = which == 0 ? (const void *)g_c.rec : (const void *)g_c.dst;
+    const size_t have = which == 0 ? (size_t)g_c.rec.cap() : (which == 1 ? (size_t)g_c.dst.cap() : 0);
+    const void *base = which == 0 ? (const void *)g_c.rec.ptr() : (const void *)g_c.dst.ptr();
     if (!host_out || offset < 0 || count < 0 || (size_t)offset + (size_t)count > have || !base)
         return fail(KGE_ERR_BAD_ARG, "kge_transe_step_scratch_read: bad arguments");
     int rc = hip_check(hipDeviceSynchronize(), "kge_transe_step_scratch_read: synchronize");
@@ -1961,21 +1923,13 @@ static int reduce_records_impl(const kge_model_desc *m, const uint32_t *d_rec, i
     hipLaunchKernelGGL(run_flags_kernel, dim3(blocks), dim3(256), 0, stream, g_c.dst_sorted, g_c.n_valid, (int)M, uidx);
     size_t scan_bytes = 0;
     (void)rocprim::inclusive_scan(nullptr, scan_bytes, uidx, uidx, (size_t)M, rocprim::plus<int32_t>(), stream);
-    if (scan_bytes > g_c.sort_tmp_bytes) {
-        if (g_c.sort_tmp) (void)hipFree(g_c.sort_tmp);
-        g_c.sort_tmp = nullptr;
-        if ((rc = hip_check(hipMalloc(&g_c.sort_tmp, scan_bytes), "scan temp"))) return rc;
-        g_c.sort_tmp_bytes = scan_bytes;
-    }
-    rc = hip_check(rocprim::inclusive_scan(g_c.sort_tmp, scan_bytes, uidx, uidx, (size_t)M, rocprim::plus<int32_t>(), stream), "run scan");
+    if ((rc = g_c.sort_tmp.reserve((int64_t)scan_bytes, "scan temp"))) return rc;
+    rc = hip_check(rocprim::inclusive_scan(g_c.sort_tmp.ptr(), scan_bytes, uidx, uidx, (size_t)M, rocprim::plus<int32_t>(), stream), "run scan");
     if (rc) return rc;
     int32_t *bflag = nullptr;
     if (fuse) {
         if (!nat) return fail(KGE_ERR_UNSUPPORTED, "fused reduce+apply needs an embedding width that is a multiple of 4");
-        if ((int64_t)g_c.bflag_cap < M) {
-            if ((rc = regrow(g_c.bflag, (size_t)M, "boundary flags"))) return rc;
-            g_c.bflag_cap = M;
-        }
+        if ((rc = g_c.bflag.reserve(M, "boundary flags"))) return rc;
         bflag = g_c.bflag;
         if ((rc = hip_check(hipMemsetAsync(bflag, 0, sizeof(int32_t) * (size_t)M, stream), "zero boundary flags"))) return rc;
     }

@@ -39,61 +39,42 @@ int launch_transr_predict_stage(const float *rel, const float *P, const int32_t 
 namespace {
 
 struct TrWork {
-    float *P = nullptr, *GP = nullptr;
-    int32_t *keys = nullptr, *keys2 = nullptr, *vals = nullptr, *vals2 = nullptr, *job_ent = nullptr, *row_ent = nullptr;
-    int32_t *bucket_start = nullptr;  // [R+2]
-    int32_t *tile_rel = nullptr, *tile_row0 = nullptr, *n_tiles = nullptr;
-    int32_t *bucket_rows = nullptr;   // group layout: start of every relation's ROW space ([R + 2]; bucket_start holds the group starts there)
-    int64_t cap_rel_rows = 0;
-    int32_t *rel_hist = nullptr;      // two alternating pairs of [kRelBins] bucket sizes + [kRelBins] scatter cursors
+    DevBuf<float> P, GP;              // [most slots seen][max_dim]
+    int64_t max_dim = 0;              // the widest relation dimension seen
+    DevBuf<int32_t> keys, keys2, vals, vals2, job_ent, row_ent;
+    DevBuf<int32_t> bucket_start;     // [R+2]
+    DevBuf<int32_t> tile_rel, tile_row0, n_tiles;
+    DevBuf<int32_t> bucket_rows;      // group layout: start of every relation's ROW space ([R + 2]; bucket_start holds the group starts there)
+    DevBuf<int32_t> rel_hist;         // two alternating pairs of [kRelBins] bucket sizes + [kRelBins] scatter cursors
     int rel_parity = 0;
-    void *sort_tmp = nullptr;
-    size_t sort_tmp_bytes = 0;
-    int64_t cap_slots = 0, cap_dim = 0, cap_rel = 0, cap_tiles = 0;
+    DevBuf<char> sort_tmp;
 };
 TrWork g_w;
 
-template <typename T>
-int grow(T *&p, size_t count, const char *what) {
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    return hip_check(hipMalloc(&p, sizeof(T) * (count ? count : 1)), what);
-}
-
 int ensure_work(int64_t slots, int64_t dr, int64_t R) {
     int rc;
-    if (slots > g_w.cap_slots || dr > g_w.cap_dim) {
-        int64_t s = slots > g_w.cap_slots ? slots : g_w.cap_slots, d = dr > g_w.cap_dim ? dr : g_w.cap_dim;
-        if ((rc = grow(g_w.P, (size_t)s * d, "transr P"))) return rc;
-        if ((rc = grow(g_w.GP, (size_t)s * d, "transr GP"))) return rc;
-        if ((rc = grow(g_w.keys, (size_t)s, "transr keys"))) return rc;
-        if ((rc = grow(g_w.keys2, (size_t)s, "transr keys2"))) return rc;
-        if ((rc = grow(g_w.vals, (size_t)s, "transr vals"))) return rc;
-        if ((rc = grow(g_w.vals2, (size_t)s, "transr vals2"))) return rc;
-        if ((rc = grow(g_w.job_ent, (size_t)s, "transr job_ent"))) return rc;
-        if ((rc = grow(g_w.row_ent, (size_t)s, "transr row_ent"))) return rc;
+    bool grew, sort_grew = false;
+    DevBuf<int32_t> *const sorted[4] = {&g_w.keys, &g_w.keys2, &g_w.vals, &g_w.vals2};
+    static const char *const names[4] = {"transr keys", "transr keys2", "transr vals", "transr vals2"};
+    for (int i = 0; i < 4; i++) {
+        if ((rc = sorted[i]->reserve(slots, names[i], &grew))) return rc;
+        sort_grew |= grew;
+    }
+    if (sort_grew || !g_w.sort_tmp) {   // (asked again while there is none: a regrow of it that failed)
         size_t bytes = 0;
-        (void)rocprim::radix_sort_pairs(nullptr, bytes, g_w.keys, g_w.keys2, g_w.vals, g_w.vals2, (size_t)s, 0, 32, nullptr);
-        if (bytes > g_w.sort_tmp_bytes) {
-            if (g_w.sort_tmp) (void)hipFree(g_w.sort_tmp);
-            g_w.sort_tmp = nullptr;
-            if ((rc = hip_check(hipMalloc(&g_w.sort_tmp, bytes), "transr sort temp"))) return rc;
-            g_w.sort_tmp_bytes = bytes;
-        }
-        g_w.cap_slots = s; g_w.cap_dim = d;
+        (void)rocprim::radix_sort_pairs(nullptr, bytes, g_w.keys.ptr(), g_w.keys2.ptr(), g_w.vals.ptr(), g_w.vals2.ptr(), (size_t)g_w.keys.cap(), 0, 32, nullptr);
+        if ((rc = g_w.sort_tmp.reserve((int64_t)bytes, "transr sort temp"))) return rc;
     }
-    if (R > g_w.cap_rel) {
-        if ((rc = grow(g_w.bucket_start, (size_t)R + 2, "transr bucket_start"))) return rc;
-        g_w.cap_rel = R;
-    }
-    int64_t tiles = slots / 32 + R + 2;
-    if (tiles > g_w.cap_tiles) {
-        if ((rc = grow(g_w.tile_rel, (size_t)tiles, "transr tile_rel"))) return rc;
-        if ((rc = grow(g_w.tile_row0, (size_t)tiles, "transr tile_row0"))) return rc;
-        if (!g_w.n_tiles && (rc = grow(g_w.n_tiles, 1, "transr n_tiles"))) return rc;
-        g_w.cap_tiles = tiles;
-    }
-    return KGE_OK;
+    if ((rc = g_w.job_ent.reserve(slots, "transr job_ent"))) return rc;
+    if ((rc = g_w.row_ent.reserve(slots, "transr row_ent"))) return rc;
+    if (dr > g_w.max_dim) g_w.max_dim = dr;
+    if ((rc = g_w.P.reserve(g_w.keys.cap() * g_w.max_dim, "transr P"))) return rc;
+    if ((rc = g_w.GP.reserve(g_w.keys.cap() * g_w.max_dim, "transr GP"))) return rc;
+    if ((rc = g_w.bucket_start.reserve(R + 2, "transr bucket_start"))) return rc;
+    const int64_t tiles = slots / 32 + R + 2;
+    if ((rc = g_w.tile_rel.reserve(tiles, "transr tile_rel"))) return rc;
+    if ((rc = g_w.tile_row0.reserve(tiles, "transr tile_row0"))) return rc;
+    return g_w.n_tiles.reserve(1, "transr n_tiles");
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -175,6 +156,13 @@ constexpr int kRelTile = 4096;        // jobs per workgroup of the scatter
 // skewed graph holds a sixth of the jobs and its one LDS counter serialised the wave's atomics (SQ_LDS_BANK_CONFLICT 75-91 % of the
 // LDS cycles of both kernels).  The sub-bins of a relation are adjacent in the sorted order, so together they are its bucket.
 constexpr int kRelSub = 4;
+
+int ensure_rel_hist() {   // zero once: every launch leaves the pair it did not use zeroed for the next
+    bool grew;
+    int rc = g_w.rel_hist.reserve(4 * (int64_t)kRelBins, "transr relation histogram", &grew);
+    if (!rc && grew && (rc = hip_check(hipMemset(g_w.rel_hist, 0, sizeof(int32_t) * 4 * kRelBins), "zero relation histogram"))) g_w.rel_hist.free();
+    return rc;
+}
 
 __global__ __launch_bounds__(256) void rel_count_kernel(const int32_t *__restrict__ keys, int J, int bins, int32_t *__restrict__ hist,
                                                         int32_t *__restrict__ next_pair) {
@@ -1608,7 +1596,7 @@ int launch_forward_backward_transr(const kge_model_desc &m, const float *const t
             const int gps = 16 / U;
             const int64_t rows_max = 16 * ((n_pos + gps - 1) / gps + R + 1);       // sum over relations of 16 ceil(groups / gps)
             if ((rc = ensure_work(slots + 1 > rows_max ? slots + 1 : rows_max, Dr, R))) return rc;
-            if (R + 2 > g_w.cap_rel_rows) { if ((rc = grow(g_w.bucket_rows, (size_t)R + 2, "transr bucket_rows"))) return rc; g_w.cap_rel_rows = R + 2; }
+            if ((rc = g_w.bucket_rows.reserve(R + 2, "transr bucket_rows"))) return rc;
             float *drec = nullptr;
             int32_t *ddst = nullptr;
             const bool records = engine().transr_dgrad_records && slots >= engine().transr_dgrad_records_min;
@@ -1618,10 +1606,7 @@ int launch_forward_backward_transr(const kge_model_desc &m, const float *const t
             if (gb > 4096) gb = 4096;
             hipLaunchKernelGGL(group_keys_kernel, dim3(gb), dim3(256), 0, stream, d_r, (long long)n_pos, g_w.keys, g_w.vals, ddst,
                                (long long)(records ? rows_max : 0));
-            if (!g_w.rel_hist) {
-                if ((rc = grow(g_w.rel_hist, 4 * (size_t)kRelBins, "transr relation histogram"))) return rc;
-                if ((rc = hip_check(hipMemset(g_w.rel_hist, 0, sizeof(int32_t) * 4 * kRelBins), "zero relation histogram"))) return rc;
-            }
+            if ((rc = ensure_rel_hist())) return rc;
             int32_t *pair = g_w.rel_hist + (g_w.rel_parity ? 2 * kRelBins : 0), *other = g_w.rel_hist + (g_w.rel_parity ? 0 : 2 * kRelBins);
             g_w.rel_parity ^= 1;
             const unsigned tiles = (unsigned)((n_pos + kRelTile - 1) / kRelTile);
@@ -1690,10 +1675,7 @@ int launch_forward_backward_transr(const kge_model_desc &m, const float *const t
                        (long long)stride, (int)m.negative_rel, (int)R, g_w.keys, g_w.vals, g_w.job_ent, ddst);
     if ((R + 1) * kRelSub <= kRelBins && !engine().counts_force_sort) {
         // two-launch counting sort by relation; bucket starts and the tile map come with it
-        if (!g_w.rel_hist) {
-            if ((rc = grow(g_w.rel_hist, 4 * (size_t)kRelBins, "transr relation histogram"))) return rc;
-            if ((rc = hip_check(hipMemset(g_w.rel_hist, 0, sizeof(int32_t) * 4 * kRelBins), "zero relation histogram"))) return rc;
-        }
+        if ((rc = ensure_rel_hist())) return rc;
         int32_t *pair = g_w.rel_hist + (g_w.rel_parity ? 2 * kRelBins : 0), *other = g_w.rel_hist + (g_w.rel_parity ? 0 : 2 * kRelBins);
         g_w.rel_parity ^= 1;
         const unsigned tiles = (unsigned)((slots + kRelTile - 1) / kRelTile);
@@ -1705,8 +1687,8 @@ int launch_forward_backward_transr(const kge_model_desc &m, const float *const t
                            pair + kRelBins, g_w.vals2, g_w.bucket_start, g_w.tile_rel, g_w.tile_row0, g_w.n_tiles, v2 ? 7 : 5, ride,
                            (int)tiles, (int)n_ride, 0, (int32_t *)nullptr);
     } else {
-        size_t tmp = g_w.sort_tmp_bytes;
-        rc = hip_check(rocprim::radix_sort_pairs(g_w.sort_tmp, tmp, g_w.keys, g_w.keys2, g_w.vals, g_w.vals2, (size_t)slots, 0,
+        size_t tmp = (size_t)g_w.sort_tmp.cap();
+        rc = hip_check(rocprim::radix_sort_pairs(g_w.sort_tmp.ptr(), tmp, g_w.keys.ptr(), g_w.keys2.ptr(), g_w.vals.ptr(), g_w.vals2.ptr(), (size_t)slots, 0,
                                                  bits_for(R), stream), "transr bucket sort");
         if (rc) return rc;
         hipLaunchKernelGGL(bounds_kernel, dim3(1), dim3(1024), 0, stream, g_w.keys2, (int)slots, (int)R, g_w.bucket_start,
