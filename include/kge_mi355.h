@@ -155,6 +155,8 @@ const char *kge_version(void);
  *   "pair_counts_min_neg": fewest negatives per positive for that path; default 0 = the measured cross-over (TransH 5, TransD 3)
  *   "index_device_min":  training sets with at least this many lines are indexed on the device (rocPRIM sorts,
  *                        same arrays bit for bit); default 4194304, 0 = always, negative = never
+ *   "eval_index_device_min": the same for kge_import_eval_arrays and kge_derive_type_lists, counted in triples of the union
+ *                        train + valid + test (csrc/eval_build.hip); default 4194304 (not measured for that build)
  *   "hub_copies":        1 (default) = on the fp32-atomic TransH/TransD path, relation-side gradient rows that would
  *                        take >= 128 adds per step are accumulated in up to 64 copies and folded (same-address
  *                        atomics serialise); 0 = straight into the accumulators
@@ -208,7 +210,7 @@ int kge_import_train_arrays(INT ent_total, INT rel_total, INT n, const INT *h, c
  *   "ht"        int32[trainTotal_][2]  (ht_off,ht_len) per file-order triple
  *   "left_mean" / "right_mean" float[relationTotal]               (Reader.h:160-177)
  *   "bern_prob" float[relationTotal]  1000*right/(right+left)      (Base.cpp:117)
- * and, built on first request from the imported type lists (kge_set_typed_sampling; an error without importTypeFiles),
+ * and, built on first request from the imported type lists (kge_set_typed_sampling; an error without type lists),
  *   "type_tails" / "type_heads"  int32[]  every relation's tail / head type list, sorted, duplicates removed, back to back
  *   "type_bounds"  int32[relationTotal][4]  (tail_off,tail_len,head_off,head_len) into those two
  *   "typed_pos_hr" / "typed_pos_tr"  int32[trainTotal]  at a group's offset in tails_hr / heads_tr: the increasing positions
@@ -220,6 +222,58 @@ int kge_import_train_arrays(INT ent_total, INT rel_total, INT n, const INT *h, c
  *               0 where that divisor is not positive
  * Returns the number of BYTES the array holds (copying at most `bytes` of them), <0 on error. */
 int64_t kge_index_copy(const char *what, void *dst, int64_t bytes);
+
+/* Same as importTestFiles but from arrays already in memory: the validation and test triples in any order, duplicates kept; the
+ * training triples are the ones the engine holds (file order, duplicates kept -- the list importTestFiles re-reads from
+ * train2id.txt).  Produces the state importTestFiles and the first device use produce for the same triples: `all` (h,r,t,0)
+ * sorted by (h,r,t), `all_t` (t,r,h,0) by (t,r,h), `all_ht` (h,t,r,0) by (h,t,r), `test` and the validation list (h,t,r,0) by
+ * (r,h,t), and the totals behind getTestTotal / getValidTotal / getTripleTotal.  Like importTestFiles it drops the type and
+ * ontology lists, marks the typed sampling index stale and starts a new triple-classification generation.  Ontology lists
+ * cannot be supplied as arrays: the four arg-min classes of a rank stay 0 / 3 as without ontology_constrain.txt.
+ * KGE_ERR_NO_DATASET before a training set; KGE_ERR_BAD_ARG for an id outside [0, entityTotal) / [0, relationTotal) -- the
+ * message names the split ("valid" / "test") and the first offending index -- with the previous evaluation state untouched.
+ * n_valid == 0 and n_test == 0 are legal.  Option "eval_index_device_min" (default 4194304 triples in the union, the value of
+ * "index_device_min" and not measured for this build; 0 = always, negative = never): from that size on, with a device and
+ * 2 bits(entityTotal) + bits(relationTotal) <= 64, the lists are built on the device (csrc/eval_build.hip: packed 64-bit keys,
+ * radix sorts limited to the bits in use, unpacked into the arrays the kernels read; the training triples come from the device
+ * index where it is resident) and the host copies the legacy host routines need are downloaded; below it on the host.  Same
+ * arrays bit for bit either way. */
+int kge_import_eval_arrays(INT n_valid, const INT *valid_h, const INT *valid_t, const INT *valid_r,
+                           INT n_test, const INT *test_h, const INT *test_t, const INT *test_r);
+
+/* The per-relation type lists (importTypeFiles' state) without type_constrain.txt.
+ * kge_set_type_lists: the lists as CSR -- head_off / tail_off hold relationTotal + 1 offsets from 0, relation r's list is
+ *   ids[off[r] .. off[r+1]).  Copied in, every list sorted, duplicates kept, as importTypeFiles leaves them; the typed sampling
+ *   index is stale afterwards.  Offsets that do not start at 0 or decrease, or an id outside [0, entityTotal):
+ *   KGE_ERR_BAD_ARG and nothing changes.
+ * kge_derive_type_lists: what the reference's n_n() writes on every launch (main_spark.py:209-290): for every relation the
+ *   distinct heads and the distinct tails over train + valid + test (the current `all`), each list increasing; a relation
+ *   without triples gets two empty lists.  Needs importTestFiles or kge_import_eval_arrays (KGE_ERR_NO_DATASET otherwise).  On
+ *   the device from "eval_index_device_min" triples on (keys relation << bits(entityTotal) | entity per side: sort, first of
+ *   each equal run, scan, compact, one bound search per relation, written straight into the arrays the rankers read), on the
+ *   host below; same arrays bit for bit.
+ * kge_have_type_lists: 1 when lists are present (file, arrays or derived), else 0.
+ * kge_get_type_lists: the current lists as CSR in increasing relation order (offsets relationTotal + 1 each).  A NULL ids
+ *   pointer skips that copy: offsets alone, for sizing.  KGE_ERR_NO_DATASET without lists.
+ * kge_write_type_constraints: the current lists in the format Reader.h:317-362 reads: a first line relationTotal, then for
+ *   EVERY relation in increasing id a head line and a tail line "rel<TAB>count<TAB>id...", count 0 for a relation without
+ *   triples.  This departs from n_n() on purpose: it writes only the relations that occur (in dictionary order), after a first
+ *   line that counts them, and the reference's reader then loops relationTotal times over a shorter file.  Written under a
+ *   temporary name and renamed into place. */
+int kge_set_type_lists(const INT *head_off, const INT *head_ids, const INT *tail_off, const INT *tail_ids);
+int kge_derive_type_lists(void);
+int kge_have_type_lists(void);
+int kge_get_type_lists(INT *head_off, INT *head_ids, INT *tail_off, INT *tail_ids);
+int kge_write_type_constraints(const char *path);
+
+/* Copies of the evaluation arrays, for inspection and tests; read from the device copies where a device is usable (uploaded on
+ * first use), so a test sees what the kernels see.  `what` is one of
+ *   "all" / "all_t" / "all_ht"  int32[tripleTotal][4]  the union as (h,r,t,0) / (t,r,h,0) / (h,t,r,0), each sorted by its fields
+ *   "test" / "valid"            int32[testTotal][4] / int32[validTotal][4]  (h,t,r,0) sorted by (r,h,t)
+ *   "head_lef" / "head_rig" / "tail_lef" / "tail_rig"  int32[relationTotal]  relation r's list is [lef[r], rig[r]) of
+ *   "head_type" / "tail_type"   int32[]  (all zero / empty without type lists)
+ * Returns the number of BYTES the array holds (copying at most `bytes` of them), <0 on error. */
+int64_t kge_eval_copy(const char *what, void *dst, int64_t bytes);
 
 /* Type-constrained negative sampling for TRAINING (NON-PARITY, off by default; the reference trains on untyped negatives,
  * Corrupt.h:7-69): an entity negative is drawn from the corrupted side's type list of its relation (type_constrain.txt) instead
@@ -235,7 +289,7 @@ int64_t kge_index_copy(const char *what, void *dst, int64_t bytes);
  * Coin says "new head": the same with the head type list of r and the known heads of (t, r).  Known ids outside L do not count.
  * So positives, coins, relation negatives and all stream states are bit-identical to the untyped batch, and a typed negative
  * with c > 0 lies in the list and is not a training triple.
- * kge_set_typed_sampling(1) needs importTypeFiles (error otherwise), runs an armed sampler first (kge_sampling_flush), builds the
+ * kge_set_typed_sampling(1) needs type lists -- importTypeFiles, kge_set_type_lists or kge_derive_type_lists -- (error otherwise), runs an armed sampler first (kge_sampling_flush), builds the
  * typed index on the host at once and uploads it with the first batch drawn; importing the training set or the type file again
  * marks it stale (rebuilt on next use).  `sampling`, kge_sampling_device(_packed) and kge_sampling_attach(_packed) honour it; an
  * armed typed sampler rides in no other launch (kge_sampling_flush launches it), and kge_train_steps_persistent refuses while it

@@ -82,6 +82,7 @@ class Config(object):
         '''
         if self.init_new_entities == False:
             self.trainModel = None
+            self._forget_evaluation()
             if self.in_path != None:
                 path = self.in_path if self.in_path.endswith("/") else self.in_path + "/"
                 self.lib.kge_clear_error()
@@ -111,9 +112,13 @@ class Config(object):
         optional here (the reference crashes without them)
         '''
         path = self.in_path if self.in_path.endswith("/") else self.in_path + "/"
+        derived = getattr(self, "_type_lists_from", None) == "derived"
         self.lib.kge_clear_error()
         self.lib.importTestFiles()
-        if os.path.exists(path + "type_constrain.txt"):
+        self._forget_evaluation()
+        if derived:      # the lists were derived from the triples (derive_type_constraints), not read: derive them from this import too
+            self.derive_type_constraints()
+        elif os.path.exists(path + "type_constrain.txt"):
             self.lib.importTypeFiles()
         if os.path.exists(path + "ontology_constrain.txt"):
             self.lib.importOntologyFiles()
@@ -129,30 +134,49 @@ class Config(object):
         a list, or a group that exhausts its list, falls back to the untyped draw.  Same random stream, positives, head-or-tail
         coins and relation negatives (include/kge_mi355.h kge_set_typed_sampling has the exact draw).  Callable before init(),
         which then imports type_constrain.txt even when link prediction is off, or after it, for the batches drawn from then
-        on.  While it is on the sampler is a launch of its own and persistent_supported() is False."""
+        on.  While it is on the sampler is a launch of its own and persistent_supported() is False.  The lists need not come
+        from the file: after init_evaluation_from_arrays(..., type_lists=...) / (..., derive_types=True) or
+        derive_type_constraints() the engine's lists are used as they stand, which is how a graph given by init_from_arrays
+        gets typed negatives."""
         self.type_constrained_sampling = bool(flag)
         if getattr(self, "trainTotal", None) is not None:      # after init(): switch the engine now
             self._apply_typed_sampling()
 
+    def _forget_evaluation(self, arrays=False):
+        """A new training or evaluation import: what an earlier import by arrays left behind no longer describes the engine.
+        The validation lists kept between calls go only when they are, or were, an array import's (arrays=True: a new one)."""
+        if arrays or getattr(self, "_eval_from_arrays", False):
+            self._valid_pos = self._valid_rank_dev = self._tc_valid_drawn = self._tc_valid_dev = None
+        self._type_lists_from = None      # "arrays" / "derived": the engine's lists did not come from type_constrain.txt
+        self._eval_from_arrays = False
+
+    _HOW_TO_SUPPLY_LISTS = ("; supply them with init_evaluation_from_arrays(valid, test, type_lists=...) or derive them from "
+                            "the triples with init_evaluation_from_arrays(..., derive_types=True) / derive_type_constraints()")
+
     def _apply_typed_sampling(self):
         on = bool(self.type_constrained_sampling)
-        if on:
+        if on and getattr(self, "_type_lists_from", None) and self.lib.kge_have_type_lists():
+            pass      # lists that came by array or by derivation: nothing to read
+        elif on:
             if self.in_path is None:
                 raise KgeError("type-constrained sampling needs a dataset directory with type_constrain.txt; "
-                               "init_from_arrays has no file to read the type lists from")
+                               "init_from_arrays has no file to read the type lists from" + self._HOW_TO_SUPPLY_LISTS)
             path = self.in_path if self.in_path.endswith("/") else self.in_path + "/"
             if not os.path.exists(path + "type_constrain.txt"):
                 raise KgeError("type-constrained sampling: `%stype_constrain.txt` does not exist" % path)
             self.lib.kge_clear_error()
             self.lib.importTypeFiles()
             _lib.raise_if_error(self.lib)
+            self._type_lists_from = None
         _lib.check(self.lib.kge_set_typed_sampling(1 if on else 0), self.lib)
 
     def init_from_arrays(self, ent_total, rel_total, h, t, r, new_batch_total=0):
         """Same as init() with the training triples (file order) given as arrays instead of files."""
         if self.type_constrained_sampling:
             raise KgeError("type-constrained sampling needs a dataset directory with type_constrain.txt; "
-                           "init_from_arrays has no file to read the type lists from")
+                           "init_from_arrays has no file to read the type lists from" + self._HOW_TO_SUPPLY_LISTS +
+                           ", then set_type_constrained_sampling(True)")
+        self._forget_evaluation(arrays=True)
         h = np.ascontiguousarray(h, dtype=np.int64)
         t = np.ascontiguousarray(t, dtype=np.int64)
         r = np.ascontiguousarray(r, dtype=np.int64)
@@ -170,6 +194,71 @@ class Config(object):
         self.bt = self.lib.getBatchTotal()
         self.set_mini_batch()
         self._alloc_batch_buffers()
+
+    def init_evaluation_from_arrays(self, valid, test, type_lists=None, derive_types=False):
+        """What init_link_prediction / init_triple_classification do, with the validation and test triples given as (h, t, r)
+        array triples instead of valid2id.txt / test2id.txt (either may be empty); the training triples are the ones the engine
+        holds, so it works after init() and after init_from_arrays().  type_lists = (head_off, head_ids, tail_off, tail_ids), the
+        per-relation type lists as CSR (relTotal + 1 offsets each), or derive_types=True for the lists the reference writes into
+        type_constrain.txt on every launch: each relation's distinct heads and distinct tails over train + valid + test.
+        Without either, evaluation runs without typed columns, as without the file.  Ontology lists cannot be given as arrays:
+        the classes of a rank stay zero.  From eval_index_device_min triples on the lists are built on the device."""
+        if type_lists is not None and derive_types:
+            raise KgeError("init_evaluation_from_arrays: give type_lists or derive_types=True, not both")
+        cols = [[np.ascontiguousarray(np.asarray(a).reshape(-1), dtype=np.int64) for a in split] for split in (valid, test)]
+        for name, split in zip(("valid", "test"), cols):
+            if len(split) != 3 or not (len(split[0]) == len(split[1]) == len(split[2])):
+                raise KgeError("init_evaluation_from_arrays: %s must be three arrays (h, t, r) of one length" % name)
+        (vh, vt, vr), (th, tt, tr) = cols
+        self.lib.kge_clear_error()
+        _lib.check(self.lib.kge_import_eval_arrays(len(vh), vh.ctypes.data, vt.ctypes.data, vr.ctypes.data,
+                                                   len(th), th.ctypes.data, tt.ctypes.data, tr.ctypes.data), self.lib)
+        self._forget_evaluation(arrays=True)
+        self._eval_from_arrays = True
+        self.testTotal = self.lib.getTestTotal()
+        self.validTotal = self.lib.getValidTotal()
+        self._valid_pos = np.stack([vh, vt, vr]).astype(np.int32)      # validation_link_prediction's positives, in the order given
+        if type_lists is not None:
+            self.set_type_constraints(*type_lists)
+        elif derive_types:
+            self.derive_type_constraints()
+        self._alloc_tc_buffers()
+        if self.type_constrained_sampling:        # the import dropped the lists of an earlier one
+            self._apply_typed_sampling()
+
+    def set_type_constraints(self, head_off, head_ids, tail_off, tail_ids):
+        """The per-relation type lists as CSR arrays (relTotal + 1 offsets from 0 and the ids, heads then tails), in place of
+        type_constrain.txt; each list is sorted on the way in, duplicates kept."""
+        arrs = [np.ascontiguousarray(np.asarray(a).reshape(-1), dtype=np.int64) for a in (head_off, head_ids, tail_off, tail_ids)]
+        if len(arrs[0]) != self.relTotal + 1 or len(arrs[2]) != self.relTotal + 1:
+            raise KgeError("type lists: head_off and tail_off must hold relTotal + 1 = %d offsets" % (self.relTotal + 1))
+        if (len(arrs[0]) and len(arrs[1]) != arrs[0][-1]) or (len(arrs[2]) and len(arrs[3]) != arrs[2][-1]):
+            raise KgeError("type lists: the last offset must be the number of ids")
+        self.lib.kge_clear_error()
+        _lib.check(self.lib.kge_set_type_lists(*[a.ctypes.data for a in arrs]), self.lib)
+        self._type_lists_from = "arrays"
+
+    def derive_type_constraints(self, write=False):
+        """The type lists the reference generates on every launch (main_spark.py n_n()): for every relation the distinct heads
+        and the distinct tails over train + valid + test, after any evaluation import (files or arrays).  write=True also
+        writes them to <in_path>/type_constrain.txt, with a head and a tail line for EVERY relation."""
+        if write and self.in_path is None:
+            raise KgeError("derive_type_constraints(write=True) needs an in_path to write type_constrain.txt into")
+        _lib.check(self.lib.kge_derive_type_lists(), self.lib)
+        self._type_lists_from = "derived"
+        if write:
+            path = self.in_path if self.in_path.endswith("/") else self.in_path + "/"
+            _lib.check(self.lib.kge_write_type_constraints((path + "type_constrain.txt").encode()), self.lib)
+
+    def type_constraints(self):
+        """The engine's current type lists as CSR: (head_off, head_ids, tail_off, tail_ids), int64."""
+        R = self.lib.getRelationTotal()
+        head_off, tail_off = np.zeros(R + 1, np.int64), np.zeros(R + 1, np.int64)
+        self.lib.kge_clear_error()
+        _lib.check(self.lib.kge_get_type_lists(head_off.ctypes.data, None, tail_off.ctypes.data, None), self.lib)
+        head_ids, tail_ids = np.zeros(int(head_off[-1]), np.int64), np.zeros(int(tail_off[-1]), np.int64)
+        _lib.check(self.lib.kge_get_type_lists(head_off.ctypes.data, head_ids.ctypes.data, tail_off.ctypes.data, tail_ids.ctypes.data), self.lib)
+        return head_off, head_ids, tail_off, tail_ids
 
     def _alloc_batch_buffers(self):
         # Config.py:172-180
@@ -1473,10 +1562,16 @@ class Config(object):
 
     def init_valid_triple_classification(self):
         """Evaluation files + the buffers getValidBatch / getBestThreshold fill (Config.py:123-151)."""
-        self.lib.kge_clear_error()
-        self.lib.importTestFiles()
-        self.lib.importTypeFiles()
-        _lib.raise_if_error(self.lib)
+        if not getattr(self, "_eval_from_arrays", False):      # (an import by arrays stands: there are no files to read again)
+            derived = getattr(self, "_type_lists_from", None) == "derived"
+            self.lib.kge_clear_error()
+            self.lib.importTestFiles()
+            self._forget_evaluation()
+            if derived:      # the lists were derived from the triples, not read: derive them from the new import too
+                self.derive_type_constraints()
+            else:
+                self.lib.importTypeFiles()
+            _lib.raise_if_error(self.lib)
         self.testTotal = self.lib.getTestTotal()
         self.validTotal = self.lib.getValidTotal()
         self._tc_buffers("valid", self.validTotal)
@@ -1489,6 +1584,10 @@ class Config(object):
         """The same plus the test-set buffers (Config.py:83-120)."""
         self.init_valid_triple_classification()
         self._tc_buffers("test", self.testTotal)
+
+    def _alloc_tc_buffers(self):
+        """init_triple_classification's buffers for an evaluation import that stands (init_evaluation_from_arrays)."""
+        self.init_triple_classification()
 
     def _fit_thresholds(self):
         """Per-relation thresholds from the validation positives and their type-constrained negatives."""

@@ -65,6 +65,14 @@ def _declare(L):
     L.kge_kernel_ms_mean.argtypes = [ctypes.c_char_p, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(i64)]
     L.kge_index_copy.restype = i64
     L.kge_index_copy.argtypes = [ctypes.c_char_p, vp, i64]
+    L.kge_import_eval_arrays.argtypes = [i64, vp, vp, vp, i64, vp, vp, vp]
+    L.kge_set_type_lists.argtypes = [vp, vp, vp, vp]
+    L.kge_derive_type_lists.argtypes = []
+    L.kge_have_type_lists.argtypes = []
+    L.kge_get_type_lists.argtypes = [vp, vp, vp, vp]
+    L.kge_write_type_constraints.argtypes = [ctypes.c_char_p]
+    L.kge_eval_copy.restype = i64
+    L.kge_eval_copy.argtypes = [ctypes.c_char_p, vp, i64]
     L.kge_set_typed_sampling.argtypes = [i64]
     L.kge_typed_sampling.argtypes = []
     L.kge_typed_sampling.restype = ctypes.c_int

@@ -85,7 +85,8 @@ int ensure_typed_host_index() {
     if (e.index.typed_built) return KGE_OK;
     TypeListsHost v;
     if (!eval_type_lists_host(v))
-        return fail(KGE_ERR_NO_DATASET, "type-constrained sampling: no type file imported (importTypeFiles reads type_constrain.txt)");
+        return fail(KGE_ERR_NO_DATASET, "type-constrained sampling: no type file imported (importTypeFiles reads type_constrain.txt) and no lists set or derived "
+                                        "(kge_set_type_lists / kge_derive_type_lists)");
     const std::string err = build_typed_index(e.index, *v.head_lef, *v.head_rig, *v.head_type, *v.tail_lef, *v.tail_rig, *v.tail_type);
     e.dev.typed_uploaded = false;
     if (!err.empty()) return fail(KGE_ERR_BAD_ARG, "type-constrained sampling: " + err);
@@ -267,6 +268,7 @@ int kge_set_option(const char *name, INT value) {
     if (n == "float_records") { engine().float_records = value != 0; return KGE_OK; }
     if (n == "float_records_min") { engine().float_records_min = value; return KGE_OK; }
     if (n == "index_device_min") { engine().index_device_min = value; return KGE_OK; }
+    if (n == "eval_index_device_min") { engine().eval_index_device_min = value; return KGE_OK; }
     if (n == "hub_copies") { engine().hub_copies = value != 0; return KGE_OK; }
     if (n == "pair_counts") { engine().pair_counts = value != 0; return KGE_OK; }
     if (n == "record_emit_event") { engine().record_emit_event = value != 0; return KGE_OK; }

@@ -87,6 +87,7 @@ struct Engine {
     int float_records = 1;              // TransH / TransD (and TransE without counts): record + segmented-sum path instead of fp32 atomics
     int64_t float_records_min = 1 << 16; // ... from this many gradient rows per step (below it the atomic kernel alone is quicker)
     int64_t index_device_min = int64_t(1) << 22;  // training sets from this many lines on are indexed on the device (index_build.hip); < 0 = never
+    int64_t eval_index_device_min = int64_t(1) << 22;  // evaluation imports from arrays and derived type lists whose union has this many triples are built on the device (eval_build.hip); < 0 = never.  index_device_min's value, not measured at this build's own cross-over
     int transr_dgrad_records = 1;      // TransR dgrad: entity-gradient rows as float records + segmented sum instead of fp32 atomics ...
     int64_t transr_dgrad_records_min = 1 << 15;   // ... from this many (scored triple, side) slots per step
     int transr_bf16x3 = 1;      // TransR row GEMMs (projection, dgrad): fp32 products as six bf16 x bf16 term products of an exact three-term split, on the bf16 matrix pipe (transr.hip rows_gemm3_kernel); 0 = the fp32 MFMA kernels

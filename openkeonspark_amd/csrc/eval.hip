@@ -12,6 +12,7 @@
 // their ontology classes are resolved by one thread with the reference's non-rewinding cursors.
 #include <algorithm>
 #include <cmath>
+#include <cstdio>
 #include <cstring>
 
 #include "eval_dev.hpp"
@@ -20,6 +21,9 @@ namespace kge {
 
 struct EvalHost {
     bool loaded = false, types = false, onto = false;
+    // kge_import_eval_arrays / kge_derive_type_lists on the device (eval_build.hip): EvalDev already holds the five triple lists /
+    // the six type arrays, and ensure_eval_device uploads only the rest
+    bool dev_triples = false, dev_types = false;
     int64_t test_total = 0, valid_total = 0, triple_total = 0;
     std::vector<Int4> test;         // (h,t,r,0) sorted by (r,h,t)   Reader.h:256
     std::vector<Int4> all;          // (h,r,t,0) sorted by (h,r,t)   Reader.h:255
@@ -31,6 +35,7 @@ struct EvalDev {
     bool uploaded = false;
     DevBuf<int4> test, all, all_t;   // all_t: the same triples as (t,r,h,0) sorted by (t,r,h)
     DevBuf<int4> all_ht;             // ... and as (h,t,r,0) sorted by (h,t,r) (relation prediction's filter)
+    DevBuf<int4> valid;              // device build only: the validation list, (h,t,r,0) sorted by (r,h,t)
     DevBuf<int32_t> head_lef, head_rig, tail_lef, tail_rig, head_type, tail_type;
     DevBuf<int32_t> sup_lef, sup_rig, sub_lef, sub_rig, sup_type, sub_type;
     DevBuf<float> scores;         // staging for testHead/testTail and kge_link_prediction
@@ -59,28 +64,32 @@ static int ensure_eval_device() {
     const int64_t E = engine().index.ent_total, R = engine().index.rel_total;
     if (g_eh.head_lef.empty()) { g_eh.head_lef.assign(R, 0); g_eh.head_rig.assign(R, 0); g_eh.tail_lef.assign(R, 0); g_eh.tail_rig.assign(R, 0); }
     if (g_eh.sup_lef.empty()) { g_eh.sup_lef.assign(E, 0); g_eh.sup_rig.assign(E, 0); g_eh.sub_lef.assign(E, 0); g_eh.sub_rig.assign(E, 0); }
-    if ((rc = g_ed.test.upload(g_eh.test, "upload test"))) return rc;
-    if ((rc = g_ed.all.upload(g_eh.all, "upload triples"))) return rc;
-    {   // second order for head requests: the known heads of a (t, r) pair are then contiguous
-        std::vector<Int4> by_tail(g_eh.all.size());
-        for (size_t i = 0; i < by_tail.size(); i++) by_tail[i] = Int4{g_eh.all[i].z, g_eh.all[i].y, g_eh.all[i].x, 0};
-        std::sort(by_tail.begin(), by_tail.end(), [](const Int4 &a, const Int4 &b) {
-            if (a.x != b.x) return a.x < b.x; if (a.y != b.y) return a.y < b.y; return a.z < b.z; });
-        if ((rc = g_ed.all_t.upload(by_tail, "upload triples by tail"))) return rc;
+    if (!g_eh.dev_triples) {
+        if ((rc = g_ed.test.upload(g_eh.test, "upload test"))) return rc;
+        if ((rc = g_ed.all.upload(g_eh.all, "upload triples"))) return rc;
+        {   // second order for head requests: the known heads of a (t, r) pair are then contiguous
+            std::vector<Int4> by_tail(g_eh.all.size());
+            for (size_t i = 0; i < by_tail.size(); i++) by_tail[i] = Int4{g_eh.all[i].z, g_eh.all[i].y, g_eh.all[i].x, 0};
+            std::sort(by_tail.begin(), by_tail.end(), [](const Int4 &a, const Int4 &b) {
+                if (a.x != b.x) return a.x < b.x; if (a.y != b.y) return a.y < b.y; return a.z < b.z; });
+            if ((rc = g_ed.all_t.upload(by_tail, "upload triples by tail"))) return rc;
+        }
+        {   // third order for relation prediction: the known relations of an (h, t) pair are then contiguous
+            std::vector<Int4> by_pair(g_eh.all.size());
+            for (size_t i = 0; i < by_pair.size(); i++) by_pair[i] = Int4{g_eh.all[i].x, g_eh.all[i].z, g_eh.all[i].y, 0};
+            std::sort(by_pair.begin(), by_pair.end(), [](const Int4 &a, const Int4 &b) {
+                if (a.x != b.x) return a.x < b.x; if (a.y != b.y) return a.y < b.y; return a.z < b.z; });
+            if ((rc = g_ed.all_ht.upload(by_pair, "upload triples by pair"))) return rc;
+        }
     }
-    {   // third order for relation prediction: the known relations of an (h, t) pair are then contiguous
-        std::vector<Int4> by_pair(g_eh.all.size());
-        for (size_t i = 0; i < by_pair.size(); i++) by_pair[i] = Int4{g_eh.all[i].x, g_eh.all[i].z, g_eh.all[i].y, 0};
-        std::sort(by_pair.begin(), by_pair.end(), [](const Int4 &a, const Int4 &b) {
-            if (a.x != b.x) return a.x < b.x; if (a.y != b.y) return a.y < b.y; return a.z < b.z; });
-        if ((rc = g_ed.all_ht.upload(by_pair, "upload triples by pair"))) return rc;
+    if (!g_eh.dev_types) {
+        if ((rc = g_ed.head_lef.upload(g_eh.head_lef, "upload types"))) return rc;
+        if ((rc = g_ed.head_rig.upload(g_eh.head_rig, "upload types"))) return rc;
+        if ((rc = g_ed.tail_lef.upload(g_eh.tail_lef, "upload types"))) return rc;
+        if ((rc = g_ed.tail_rig.upload(g_eh.tail_rig, "upload types"))) return rc;
+        if ((rc = g_ed.head_type.upload(g_eh.head_type, "upload types"))) return rc;
+        if ((rc = g_ed.tail_type.upload(g_eh.tail_type, "upload types"))) return rc;
     }
-    if ((rc = g_ed.head_lef.upload(g_eh.head_lef, "upload types"))) return rc;
-    if ((rc = g_ed.head_rig.upload(g_eh.head_rig, "upload types"))) return rc;
-    if ((rc = g_ed.tail_lef.upload(g_eh.tail_lef, "upload types"))) return rc;
-    if ((rc = g_ed.tail_rig.upload(g_eh.tail_rig, "upload types"))) return rc;
-    if ((rc = g_ed.head_type.upload(g_eh.head_type, "upload types"))) return rc;
-    if ((rc = g_ed.tail_type.upload(g_eh.tail_type, "upload types"))) return rc;
     if ((rc = g_ed.sup_lef.upload(g_eh.sup_lef, "upload ontology"))) return rc;
     if ((rc = g_ed.sup_rig.upload(g_eh.sup_rig, "upload ontology"))) return rc;
     if ((rc = g_ed.sub_lef.upload(g_eh.sub_lef, "upload ontology"))) return rc;
@@ -257,6 +266,8 @@ using namespace kge;
 
 extern "C" {
 
+static bool ensure_classification_lists();
+
 void importTestFiles(void) {
     Engine &e = engine();
     g_eh = EvalHost();
@@ -316,6 +327,7 @@ void importTypeFiles(void) {
         std::sort(g_eh.tail_type.begin() + g_eh.tail_lef[rel], g_eh.tail_type.end());
     }
     g_eh.types = true;
+    g_eh.dev_types = false;
     g_ed.uploaded = false;
 }
 
@@ -346,6 +358,238 @@ void importOntologyFiles(void) {
     }
     g_eh.onto = true;
     g_ed.uploaded = false;
+}
+
+// ---- evaluation from arrays, type lists without a file (include/kge_mi355.h) ----------------------------------------------
+static int bad_id(const char *split, INT n, const INT *h, const INT *t, const INT *r, int64_t E, int64_t R) {
+    if (n < 0 || (n > 0 && (!h || !t || !r))) return fail(KGE_ERR_BAD_ARG, std::string("kge_import_eval_arrays: ") + split + ": bad count or null array");
+    for (INT i = 0; i < n; i++)
+        if (h[i] < 0 || h[i] >= E || t[i] < 0 || t[i] >= E || r[i] < 0 || r[i] >= R)
+            return fail(KGE_ERR_BAD_ARG, std::string("kge_import_eval_arrays: ") + split + ": id out of range at index " + std::to_string((long long)i));
+    return KGE_OK;
+}
+
+// what importTestFiles resets, before the new lists move in
+static void reset_eval_state() {
+    g_eh = EvalHost();
+    g_ed.uploaded = false;
+    engine().index.typed_built = false;
+    g_valid.clear();
+    g_tc_generation++;
+}
+
+static int download_int4(std::vector<Int4> &dst, const int4 *src, int64_t n, const char *what) {
+    dst.resize((size_t)n);
+    if (n == 0) return KGE_OK;
+    return hip_check(hipMemcpy(dst.data(), src, sizeof(int4) * (size_t)n, hipMemcpyDeviceToHost), what);
+}
+
+static int download_i32(std::vector<int32_t> &dst, const int32_t *src, int64_t n, const char *what) {
+    dst.resize((size_t)n);
+    if (n == 0) return KGE_OK;
+    return hip_check(hipMemcpy(dst.data(), src, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost), what);
+}
+
+static bool eval_build_on_device(int64_t n_all) {
+    Engine &e = engine();
+    const int64_t min = e.eval_index_device_min;
+    return min >= 0 && n_all >= min && device_ok() && device_eval_build_supported(e.index.ent_total, e.index.rel_total, n_all);
+}
+
+int kge_import_eval_arrays(INT n_valid, const INT *valid_h, const INT *valid_t, const INT *valid_r, INT n_test, const INT *test_h,
+                           const INT *test_t, const INT *test_r) {
+    Engine &e = engine();
+    if (!e.index.loaded) return fail(KGE_ERR_NO_DATASET, "kge_import_eval_arrays: no training set imported (importTrainFiles / kge_import_train_arrays)");
+    const int64_t E = e.index.ent_total, R = e.index.rel_total, n_train = e.index.train_dup;
+    int rc;
+    if ((rc = bad_id("valid", n_valid, valid_h, valid_t, valid_r, E, R))) return rc;
+    if ((rc = bad_id("test", n_test, test_h, test_t, test_r, E, R))) return rc;
+    const int64_t n_all = n_test + n_train + n_valid;
+    if (n_all >= (int64_t(1) << 31)) return fail(KGE_ERR_BAD_ARG, "kge_import_eval_arrays: train + valid + test must stay below 2^31 triples");
+    std::vector<Int4> all, test, valid;
+    if (eval_build_on_device(n_all)) {
+        test.resize((size_t)n_test); valid.resize((size_t)n_valid);   // file order (h,t,r,0), the build's only uploads
+        for (INT i = 0; i < n_test; i++) test[(size_t)i] = Int4{(int32_t)test_h[i], (int32_t)test_t[i], (int32_t)test_r[i], 0};
+        for (INT i = 0; i < n_valid; i++) valid[(size_t)i] = Int4{(int32_t)valid_h[i], (int32_t)valid_t[i], (int32_t)valid_r[i], 0};
+        ScopedDevBuf<int4> train_up;   // the training triples: the device index's `pos` where it is resident
+        const int4 *d_train = e.dev.pos;
+        if (!e.dev.uploaded) {
+            if ((rc = train_up.upload(e.index.pos, "eval build: training triples"))) return rc;
+            d_train = train_up;
+        }
+        EvalTriplesBuilt b;
+        if ((rc = build_eval_lists_device(E, R, d_train, n_train, valid, test, b))) return rc;
+        // host copies for the legacy host routines (getHeadBatch, getValidBatch, find_host, eval_tc_lists), by download
+        if ((rc = download_int4(all, b.all, n_all, "download triples"))) return rc;
+        if ((rc = download_int4(test, b.test, n_test, "download test list"))) return rc;
+        if ((rc = download_int4(valid, b.valid, n_valid, "download valid list"))) return rc;
+        reset_eval_state();
+        g_ed.all.adopt(b.all.release(), n_all); g_ed.all_t.adopt(b.all_t.release(), n_all); g_ed.all_ht.adopt(b.all_ht.release(), n_all);
+        g_ed.test.adopt(b.test.release(), n_test > 0 ? n_test : 1); g_ed.valid.adopt(b.valid.release(), n_valid > 0 ? n_valid : 1);
+        g_eh.dev_triples = true;
+    } else {
+        build_eval_lists(e.index.pos, n_valid, (const int64_t *)valid_h, (const int64_t *)valid_t, (const int64_t *)valid_r, n_test,
+                         (const int64_t *)test_h, (const int64_t *)test_t, (const int64_t *)test_r, all, test, valid);
+        reset_eval_state();
+    }
+    g_eh.all = std::move(all); g_eh.test = std::move(test); g_valid = std::move(valid);
+    g_eh.test_total = n_test; g_eh.valid_total = n_valid; g_eh.triple_total = n_all;
+    g_eh.loaded = true;
+    return KGE_OK;
+}
+
+int kge_set_type_lists(const INT *head_off, const INT *head_ids, const INT *tail_off, const INT *tail_ids) {
+    Engine &e = engine();
+    if (!e.index.loaded) return fail(KGE_ERR_NO_DATASET, "kge_set_type_lists: no training set imported");
+    const int64_t E = e.index.ent_total, R = e.index.rel_total;
+    if (!head_off || !tail_off) return fail(KGE_ERR_BAD_ARG, "kge_set_type_lists: null offsets");
+    const INT *offs[2] = {head_off, tail_off}, *ids[2] = {head_ids, tail_ids};
+    const char *side[2] = {"head", "tail"};
+    for (int s = 0; s < 2; s++) {
+        if (offs[s][0] != 0) return fail(KGE_ERR_BAD_ARG, std::string("kge_set_type_lists: ") + side[s] + " offsets must start at 0");
+        for (int64_t r = 0; r < R; r++)
+            if (offs[s][r + 1] < offs[s][r])
+                return fail(KGE_ERR_BAD_ARG, std::string("kge_set_type_lists: ") + side[s] + " offsets decrease at relation " + std::to_string((long long)r));
+        const INT n = offs[s][R];
+        if (n >= (INT(1) << 31) || (n > 0 && !ids[s])) return fail(KGE_ERR_BAD_ARG, std::string("kge_set_type_lists: ") + side[s] + " ids: null or too many");
+        for (INT i = 0; i < n; i++)
+            if (ids[s][i] < 0 || ids[s][i] >= E)
+                return fail(KGE_ERR_BAD_ARG, std::string("kge_set_type_lists: ") + side[s] + " id out of range at index " + std::to_string((long long)i));
+    }
+    std::vector<int32_t> *lef[2] = {&g_eh.head_lef, &g_eh.tail_lef}, *rig[2] = {&g_eh.head_rig, &g_eh.tail_rig}, *typ[2] = {&g_eh.head_type, &g_eh.tail_type};
+    for (int s = 0; s < 2; s++) {
+        lef[s]->resize((size_t)R); rig[s]->resize((size_t)R);
+        typ[s]->resize((size_t)offs[s][R]);
+        for (INT i = 0; i < offs[s][R]; i++) (*typ[s])[(size_t)i] = (int32_t)ids[s][i];
+        for (int64_t r = 0; r < R; r++) {   // each list sorted, duplicates kept, as importTypeFiles leaves them
+            (*lef[s])[(size_t)r] = (int32_t)offs[s][r]; (*rig[s])[(size_t)r] = (int32_t)offs[s][r + 1];
+            std::sort(typ[s]->begin() + offs[s][r], typ[s]->begin() + offs[s][r + 1]);
+        }
+    }
+    g_eh.types = true;
+    g_eh.dev_types = false;
+    g_ed.uploaded = false;
+    e.index.typed_built = false;
+    return KGE_OK;
+}
+
+int kge_derive_type_lists(void) {
+    Engine &e = engine();
+    if (!g_eh.loaded) return fail(KGE_ERR_NO_DATASET, "kge_derive_type_lists: no evaluation import (importTestFiles / kge_import_eval_arrays)");
+    const int64_t E = e.index.ent_total, R = e.index.rel_total, n_all = (int64_t)g_eh.all.size();
+    if (eval_build_on_device(n_all)) {
+        int rc = ensure_eval_device();   // `all` on the device: built there, or uploaded by the file path
+        if (rc) return rc;
+        TypeListsBuilt b;
+        if ((rc = derive_type_lists_device(E, R, g_ed.all, n_all, b))) return rc;
+        std::vector<int32_t> hl, hr, ht, tl, tr, tt;   // host copies for the typed sampling index and the host classification routines
+        if ((rc = download_i32(hl, b.head_lef, R, "download type lists")) || (rc = download_i32(hr, b.head_rig, R, "download type lists")) ||
+            (rc = download_i32(ht, b.head_type, b.n_head, "download type lists")) || (rc = download_i32(tl, b.tail_lef, R, "download type lists")) ||
+            (rc = download_i32(tr, b.tail_rig, R, "download type lists")) || (rc = download_i32(tt, b.tail_type, b.n_tail, "download type lists")))
+            return rc;
+        g_eh.head_lef.swap(hl); g_eh.head_rig.swap(hr); g_eh.head_type.swap(ht);
+        g_eh.tail_lef.swap(tl); g_eh.tail_rig.swap(tr); g_eh.tail_type.swap(tt);
+        g_ed.head_lef.adopt(b.head_lef.release(), R); g_ed.head_rig.adopt(b.head_rig.release(), R);
+        g_ed.tail_lef.adopt(b.tail_lef.release(), R); g_ed.tail_rig.adopt(b.tail_rig.release(), R);
+        g_ed.head_type.adopt(b.head_type.release(), b.n_head); g_ed.tail_type.adopt(b.tail_type.release(), b.n_tail);
+        g_eh.dev_types = true;   // g_ed.uploaded stays: the views hand out the adopted arrays
+    } else {
+        derive_type_lists(g_eh.all, R, g_eh.head_lef, g_eh.head_rig, g_eh.head_type, g_eh.tail_lef, g_eh.tail_rig, g_eh.tail_type);
+        g_eh.dev_types = false;
+        g_ed.uploaded = false;
+    }
+    g_eh.types = true;
+    e.index.typed_built = false;
+    return KGE_OK;
+}
+
+int kge_have_type_lists(void) { return g_eh.types ? 1 : 0; }
+
+int kge_get_type_lists(INT *head_off, INT *head_ids, INT *tail_off, INT *tail_ids) {
+    if (!g_eh.types) return fail(KGE_ERR_NO_DATASET, "kge_get_type_lists: no type lists (importTypeFiles / kge_set_type_lists / kge_derive_type_lists)");
+    const int64_t R = engine().index.rel_total;
+    auto side = [&](const std::vector<int32_t> &lef, const std::vector<int32_t> &rig, const std::vector<int32_t> &typ, INT *off, INT *ids) {
+        INT k = 0;
+        for (int64_t r = 0; r < R; r++) {
+            if (off) off[r] = k;
+            const int32_t lo = r < (int64_t)lef.size() ? lef[(size_t)r] : 0, hi = r < (int64_t)rig.size() ? rig[(size_t)r] : 0;
+            if (ids) for (int32_t q = lo; q < hi; q++) ids[k + (q - lo)] = typ[(size_t)q];
+            k += hi - lo;
+        }
+        if (off) off[R] = k;
+    };
+    side(g_eh.head_lef, g_eh.head_rig, g_eh.head_type, head_off, head_ids);
+    side(g_eh.tail_lef, g_eh.tail_rig, g_eh.tail_type, tail_off, tail_ids);
+    return KGE_OK;
+}
+
+int kge_write_type_constraints(const char *path) {
+    if (!g_eh.types) return fail(KGE_ERR_NO_DATASET, "kge_write_type_constraints: no type lists (importTypeFiles / kge_set_type_lists / kge_derive_type_lists)");
+    if (!path) return fail(KGE_ERR_BAD_ARG, "kge_write_type_constraints: null path");
+    const std::string tmp = std::string(path) + ".tmp";   // renamed into place: a reader never sees half a file
+    FILE *f = std::fopen(tmp.c_str(), "w");
+    if (!f) return fail(KGE_ERR_BAD_ARG, "kge_write_type_constraints: cannot write `" + tmp + "`");
+    const int64_t R = engine().index.rel_total;
+    std::fprintf(f, "%lld\n", (long long)R);
+    auto line = [&](int64_t r, const std::vector<int32_t> &lef, const std::vector<int32_t> &rig, const std::vector<int32_t> &typ) {
+        const int32_t lo = lef[(size_t)r], hi = rig[(size_t)r];
+        std::fprintf(f, "%lld\t%d", (long long)r, (int)(hi - lo));
+        for (int32_t q = lo; q < hi; q++) std::fprintf(f, "\t%d", (int)typ[(size_t)q]);
+        std::fputc('\n', f);
+    };
+    for (int64_t r = 0; r < R; r++) {
+        line(r, g_eh.head_lef, g_eh.head_rig, g_eh.head_type);
+        line(r, g_eh.tail_lef, g_eh.tail_rig, g_eh.tail_type);
+    }
+    const bool bad = std::ferror(f) != 0;
+    if (std::fclose(f) != 0 || bad || std::rename(tmp.c_str(), path) != 0) return fail(KGE_ERR_BAD_ARG, std::string("kge_write_type_constraints: writing `") + path + "` failed");
+    return KGE_OK;
+}
+
+int64_t kge_eval_copy(const char *what, void *dst, int64_t bytes) {
+    if (!g_eh.loaded) return fail(KGE_ERR_NO_DATASET, "kge_eval_copy: no evaluation import (importTestFiles / kge_import_eval_arrays)");
+    const std::string w = what ? what : "";
+    const int64_t R = engine().index.rel_total, n_all = (int64_t)g_eh.all.size();
+    const bool on_device = device_ok();
+    if (on_device) { int rc = ensure_eval_device(); if (rc) return rc; }
+    if (w == "valid" && !ensure_classification_lists()) return KGE_ERR_NO_DATASET;   // (the file path reads valid2id.txt on first use)
+    if (g_eh.head_lef.empty()) { g_eh.head_lef.assign((size_t)R, 0); g_eh.head_rig.assign((size_t)R, 0); g_eh.tail_lef.assign((size_t)R, 0); g_eh.tail_rig.assign((size_t)R, 0); }
+    std::vector<Int4> order;   // all_t / all_ht without a device: the host sort of ensure_eval_device
+    const void *host = nullptr, *dev = nullptr;
+    int64_t have = -1;
+#define KGE_EVAL_ARR(name, hvec, dbuf, count, elem) if (w == name) { host = (hvec); dev = (dbuf); have = (int64_t)(count) * (int64_t)(elem); }
+    KGE_EVAL_ARR("all", g_eh.all.data(), g_ed.all.ptr(), n_all, 16)
+    KGE_EVAL_ARR("all_t", nullptr, g_ed.all_t.ptr(), n_all, 16)
+    KGE_EVAL_ARR("all_ht", nullptr, g_ed.all_ht.ptr(), n_all, 16)
+    KGE_EVAL_ARR("test", g_eh.test.data(), g_ed.test.ptr(), g_eh.test_total, 16)
+    KGE_EVAL_ARR("valid", g_valid.data(), g_eh.dev_triples ? g_ed.valid.ptr() : nullptr, g_eh.valid_total, 16)
+    KGE_EVAL_ARR("head_lef", g_eh.head_lef.data(), g_ed.head_lef.ptr(), R, 4)
+    KGE_EVAL_ARR("head_rig", g_eh.head_rig.data(), g_ed.head_rig.ptr(), R, 4)
+    KGE_EVAL_ARR("tail_lef", g_eh.tail_lef.data(), g_ed.tail_lef.ptr(), R, 4)
+    KGE_EVAL_ARR("tail_rig", g_eh.tail_rig.data(), g_ed.tail_rig.ptr(), R, 4)
+    KGE_EVAL_ARR("head_type", g_eh.head_type.data(), g_ed.head_type.ptr(), g_eh.head_type.size(), 4)
+    KGE_EVAL_ARR("tail_type", g_eh.tail_type.data(), g_ed.tail_type.ptr(), g_eh.tail_type.size(), 4)
+#undef KGE_EVAL_ARR
+    if (have < 0) return fail(KGE_ERR_BAD_ARG, "kge_eval_copy: unknown array " + w);
+    if (!dst || bytes <= 0 || have == 0) return have;
+    const size_t n = (size_t)(bytes < have ? bytes : have);
+    if (on_device && dev) {
+        int rc = hip_check(hipMemcpy(dst, dev, n, hipMemcpyDeviceToHost), "kge_eval_copy");
+        return rc ? rc : have;
+    }
+    if (!host) {
+        const bool by_tail = w == "all_t";
+        order.resize(g_eh.all.size());
+        for (size_t i = 0; i < order.size(); i++) {
+            const Int4 &a = g_eh.all[i];
+            order[i] = by_tail ? Int4{a.z, a.y, a.x, 0} : Int4{a.x, a.z, a.y, 0};
+        }
+        std::sort(order.begin(), order.end(), [](const Int4 &a, const Int4 &b) {
+            if (a.x != b.x) return a.x < b.x; if (a.y != b.y) return a.y < b.y; return a.z < b.z; });
+        host = order.data();
+    }
+    std::memcpy(dst, host, n);
+    return have;
 }
 
 INT kge_eval_test_total(void) { return g_eh.test_total; }

@@ -36,6 +36,23 @@ struct TcLists {
 int eval_tc_lists(TcLists &v);
 uint64_t eval_tc_generation();
 
+// Device build of the evaluation lists and of derived type lists (eval_build.hip), bit for bit the host builds of kg_index.cpp
+// (build_eval_lists plus ensure_eval_device's two further orders; derive_type_lists).  Triples are packed into 64-bit keys, one
+// field order per list, radix-sorted up to the bits in use and unpacked straight into the int4 arrays the views hand out:
+//   (a,b,c) -> a << (bits(b) + bits(c)) | b << bits(c) | c       needs 2 bits(E) + bits(R) <= 64, as the training index does
+bool device_eval_build_supported(int64_t E, int64_t R, int64_t n_all);
+struct EvalTriplesBuilt { ScopedDevBuf<int4> all, all_t, all_ht, test, valid; };
+// d_train: the file-order training triples (h,t,r,0) on the device; valid / test: (h,t,r,0) on the host, ids already range-checked
+int build_eval_lists_device(int64_t E, int64_t R, const int4 *d_train, int64_t n_train, const std::vector<Int4> &valid,
+                            const std::vector<Int4> &test, EvalTriplesBuilt &out);
+struct TypeListsBuilt {
+    ScopedDevBuf<int32_t> head_lef, head_rig, tail_lef, tail_rig, head_type, tail_type;   // lef / rig [R]; the id arrays [n_head] / [n_tail]
+    int64_t n_head = 0, n_tail = 0;
+};
+// d_all: (h,r,t,0), any order.  Keys r << bits(E) | entity per side: sort, flag the first of each equal run, scan, compact, and a
+// bound search per relation for [lef, rig)
+int derive_type_lists_device(int64_t E, int64_t R, const int4 *d_all, int64_t n_all, TypeListsBuilt &out);
+
 // [lo, hi) of the entries whose first two fields are (a, b) in an array sorted by (x, y, z): the third fields of that
 // range are the known tails of (h, r) in `all`, the known heads of (t, r) in `all_t`, or the known relations of (h, t) in
 // `all_ht`, in increasing order

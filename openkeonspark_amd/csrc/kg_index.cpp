@@ -256,6 +256,52 @@ std::string build_typed_index(KgIndex &ix, const std::vector<int32_t> &head_lef,
     return "";
 }
 
+void build_eval_lists(const std::vector<Int4> &train, int64_t n_valid, const int64_t *vh, const int64_t *vt, const int64_t *vr,
+                      int64_t n_test, const int64_t *th, const int64_t *tt, const int64_t *tr, std::vector<Int4> &all,
+                      std::vector<Int4> &test, std::vector<Int4> &valid) {
+    all.clear(); test.clear(); valid.clear();
+    all.reserve((size_t)n_test + train.size() + (size_t)n_valid);
+    test.reserve((size_t)n_test); valid.reserve((size_t)n_valid);
+    for (int64_t i = 0; i < n_test; i++) {
+        all.push_back(Int4{(int32_t)th[i], (int32_t)tr[i], (int32_t)tt[i], 0});
+        test.push_back(Int4{(int32_t)th[i], (int32_t)tt[i], (int32_t)tr[i], 0});
+    }
+    for (const Int4 &p : train) all.push_back(Int4{p.x, p.z, p.y, 0});
+    for (int64_t i = 0; i < n_valid; i++) {
+        all.push_back(Int4{(int32_t)vh[i], (int32_t)vr[i], (int32_t)vt[i], 0});
+        valid.push_back(Int4{(int32_t)vh[i], (int32_t)vt[i], (int32_t)vr[i], 0});
+    }
+    std::sort(all.begin(), all.end(), [](const Int4 &a, const Int4 &b) {        // Triple.h:18-20
+        if (a.x != b.x) return a.x < b.x; if (a.y != b.y) return a.y < b.y; return a.z < b.z; });
+    auto by_rht = [](const Int4 &a, const Int4 &b) {                            // Triple.h:30-32 (r,h,t)
+        if (a.z != b.z) return a.z < b.z; if (a.x != b.x) return a.x < b.x; return a.y < b.y; };
+    std::sort(test.begin(), test.end(), by_rht);
+    std::sort(valid.begin(), valid.end(), by_rht);
+}
+
+void derive_type_lists(const std::vector<Int4> &all, int64_t R, std::vector<int32_t> &head_lef, std::vector<int32_t> &head_rig,
+                       std::vector<int32_t> &head_type, std::vector<int32_t> &tail_lef, std::vector<int32_t> &tail_rig,
+                       std::vector<int32_t> &tail_type) {
+    // one sort of (relation, entity) keys per side; the distinct keys in order are the lists back to back
+    auto side = [&](bool heads, std::vector<int32_t> &lef, std::vector<int32_t> &rig, std::vector<int32_t> &ids) {
+        std::vector<uint64_t> keys(all.size());
+        for (size_t i = 0; i < all.size(); i++)
+            keys[i] = ((uint64_t)(uint32_t)all[i].y << 32) | (uint32_t)(heads ? all[i].x : all[i].z);
+        std::sort(keys.begin(), keys.end());
+        keys.erase(std::unique(keys.begin(), keys.end()), keys.end());
+        lef.assign((size_t)R, 0); rig.assign((size_t)R, 0);
+        ids.resize(keys.size());
+        size_t k = 0;
+        for (int64_t r = 0; r < R; r++) {
+            lef[(size_t)r] = (int32_t)k;
+            while (k < keys.size() && (int64_t)(keys[k] >> 32) == r) { ids[k] = (int32_t)(keys[k] & 0xffffffffu); k++; }
+            rig[(size_t)r] = (int32_t)k;
+        }
+    };
+    side(true, head_lef, head_rig, head_type);
+    side(false, tail_lef, tail_rig, tail_type);
+}
+
 LibcRand::LibcRand() {
     int32_t w = 1;
     s_[0] = uint32_t(w);

@@ -66,6 +66,20 @@ std::string build_typed_index(KgIndex &ix, const std::vector<int32_t> &head_lef,
                               const std::vector<int32_t> &head_type, const std::vector<int32_t> &tail_lef,
                               const std::vector<int32_t> &tail_rig, const std::vector<int32_t> &tail_type);
 
+// Evaluation lists from arrays (kge_import_eval_arrays; what importTestFiles builds from the three text files, Reader.h:186-261):
+// `all` = test + train + valid as (h,r,t,0) sorted by (h,r,t), `test` and `valid` as (h,t,r,0) sorted by (r,h,t) (Triple.h:18-32),
+// duplicates kept.  train = KgIndex::pos, the file-order training triples.  The ids were range-checked by the caller.
+void build_eval_lists(const std::vector<Int4> &train, int64_t n_valid, const int64_t *vh, const int64_t *vt, const int64_t *vr,
+                      int64_t n_test, const int64_t *th, const int64_t *tt, const int64_t *tr, std::vector<Int4> &all,
+                      std::vector<Int4> &test, std::vector<Int4> &valid);
+
+// Per-relation type lists derived from `all` (main_spark.py:209-290 n_n()): the distinct heads and the distinct tails of every
+// relation, each list increasing, as [lef[r], rig[r]) into head_type / tail_type; a relation without triples gets lef == rig ==
+// the running offset.
+void derive_type_lists(const std::vector<Int4> &all, int64_t rel_total, std::vector<int32_t> &head_lef, std::vector<int32_t> &head_rig,
+                       std::vector<int32_t> &head_type, std::vector<int32_t> &tail_lef, std::vector<int32_t> &tail_rig,
+                       std::vector<int32_t> &tail_type);
+
 // glibc rand() with the default seed, continuing across calls (Random.h:9-13 never calls srand).
 class LibcRand {
    public:

@@ -33,6 +33,7 @@ import zipfile
 
 import numpy as np
 
+from . import _lib
 from .Config import Config, KgeError
 from .Model import xavier_normal
 from .TransD import TransD
@@ -96,6 +97,11 @@ def parse_args(argv=None):
                    help="1: entity negatives of a training batch come from the relation's own head / tail type list "
                         "(type_constrain.txt in --input_path, required then) instead of from all entities; same random stream, "
                         "same positives (Config.set_type_constrained_sampling)")
+    p.add_argument("--derive_type_constraints", type=int, default=0,
+                   help="1: when type_constrain.txt is missing from --input_path, every rank derives the type lists from train + valid + "
+                        "test (each relation's distinct heads and tails, as the reference's launcher regenerates them) and rank 0 also "
+                        "writes the file; the accuracy early stop, --mode test's typed columns and --type_constrained_sampling 1 then "
+                        "run as if the file had been there.  0 (the default): a missing file means none of those")
     return p.parse_args(argv)
 
 
@@ -126,8 +132,20 @@ def get_conf(argv):
     con.seed = getattr(argv, "seed", 0)
     if getattr(argv, "sparse_rows", -1) >= 0:
         con.sparse_rows = bool(argv.sparse_rows)
-    con.set_type_constrained_sampling(bool(getattr(argv, "type_constrained_sampling", 0)))
+    typed = bool(getattr(argv, "type_constrained_sampling", 0))
+    path = argv.input_path if not argv.input_path or argv.input_path.endswith("/") else argv.input_path + "/"
+    derive = bool(getattr(argv, "derive_type_constraints", 0)) and bool(path) and not os.path.exists(path + "type_constrain.txt") and \
+        all(os.path.exists(path + f) for f in ("valid2id.txt", "test2id.txt"))      # (the lists are derived from all three splits)
+    con.set_type_constrained_sampling(typed and not derive)
     con.init()
+    if derive:      # no type file: the lists from the triples, on every rank; the file from rank 0
+        if not con.test_link_prediction:      # (init() imported the evaluation files otherwise)
+            con.lib.kge_clear_error()
+            con.lib.importTestFiles()
+            _lib.raise_if_error(con.lib)
+        con.derive_type_constraints(write=int(os.environ.get("RANK", "0")) == 0)
+        if typed:
+            con.set_type_constrained_sampling(True)
     name = argv.model.lower()
     con.set_model({"transh": TransH, "transr": TransR, "transd": TransD}.get(name, TransE))
     return con
@@ -415,14 +433,17 @@ def _init_validation(con, argv):
     """getValidBatch once before the loop (distribute_training.py:262): validation positives and their
     type-constrained negatives, or None when the evaluation files are absent."""
     path = con.in_path if con.in_path.endswith("/") else con.in_path + "/"
-    if not all(os.path.exists(path + f) for f in ("valid2id.txt", "test2id.txt", "type_constrain.txt")):
+    derived = getattr(con, "_type_lists_from", None) == "derived"      # --derive_type_constraints 1: the lists need no file
+    if not all(os.path.exists(path + f) for f in ("valid2id.txt", "test2id.txt") + (() if derived else ("type_constrain.txt",))):
         return None
     import ctypes
-    from . import _lib
     L = con.lib
     L.kge_clear_error()
     L.importTestFiles()
-    L.importTypeFiles()
+    if derived:
+        con.derive_type_constraints()
+    else:
+        L.importTypeFiles()
     _lib.raise_if_error(L)
     n = L.getValidTotal()
     arrs = [np.zeros(n, np.int64) for _ in range(6)]
