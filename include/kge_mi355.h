@@ -113,9 +113,18 @@ const char *kge_version(void);
  *   "counts_fused":      1 (default) = kge_transe_train_step_counts sums the records of a row and applies the optimizer to it in one
  *                        kernel (rows whose int8 and 2-bit record lists hold up to 64 records each; longer rows and relation rows go through the count image);
  *                        0 = the two-kernel form (segmented sum into the image, then kge_transe_apply_counts_tables).  Same bits.
+ *   "counts_sort_tiles": how the hand-written record sort runs: 1 (default) = two launches -- every tile of 2048 keys sorts its
+ *                        live pairs by bucket and publishes its bucket offsets, then one workgroup per bucket collects its segments
+ *                        and orders them by key -- with no sizing pass and no global atomics; 0 = the three-launch form (bucket
+ *                        histogram, scatter through global cursors, bucket sort), which inputs of more than 2048 tiles (4 194 304
+ *                        keys) take as well.  Same sorted keys and row spans; the order inside a key is unspecified in both.
+ *                        1024 / 4096 = the two-launch form at that tile size (measurements)
  *   "ride_shares":       where an armed sampler (kge_sampling_attach) rides: percent of its workgroups for the bucket histogram /
- *                        bucket scatter / bucket sort / the launch that ends the step, one byte each (default 100 << 8: all of it in
- *                        the scatter launch; parts that no launch took are launched by kge_sampling_flush)
+ *                        bucket scatter / bucket sort / the launch that ends the step, one byte each; parts that no launch took
+ *                        are launched by kge_sampling_flush.  The two-launch sort has no histogram launch: byte 0 is ignored
+ *                        there, byte 1 is its tile pass and byte 2 its bucket pass.  Default -1 = automatic: 100 << 8 (all of it in
+ *                        the scatter launch) with the three-launch sort, 50 << 8 | 50 << 16 (half in each launch) with the
+ *                        two-launch sort
  *   "sampler_magic_len": T (default 2048): filter groups of fewer than T known ids take the modulus of their filtered pick from the
  *                        tables "ent_magic" / "rel_magic" (kge_index_copy), longer ones from two fp64 divisions.  Same draws; the
  *                        tables of an imported training set are rebuilt at once (tests lower it so that both ways run)
@@ -556,10 +565,21 @@ int kge_transe_apply_counts_range(const kge_model_desc *m, float *const d_p[2], 
  *                              which = 0 the records (3 * n_pos int8 records of kge_transe_record_dwords words each, then --
  *                              the fused step at widths that are multiples of 4 -- the 2-bit record of negative k of group b
  *                              as record k * n_pos + b of a quarter of that size), which = 1 the destination keys as the
- *                              call left them (inactive slots hold its sentinel, the largest key).  Synchronises. */
+ *                              call left them (inactive slots hold its sentinel, the largest key).  Synchronises.
+ *   kge_counts_sort_test:      test hook.  Runs the hand-written record sort (option "counts_sort_tiles") on `stream` over the n_keys
+ *                              HOST keys `keys` (a key < 0 = no record, else < rows), buckets of rpb rows (rows <= 512 * rpb,
+ *                              rpb <= 8192), and copies back: sorted_keys / sorted_ids [n_keys] (the first *n_live entries are
+ *                              meaningful), n_live [1], bucket_start [514] (start of each of the 512 buckets, [512] = *n_live,
+ *                              [513] = n_keys).  plan_cap > 0 (rpb even: key = 2 * row + kind) also builds the fused step's plan with
+ *                              lists cut at plan_cap records: row_span [rows][2] = (first position, records) of every key, pieces
+ *                              [max_pieces][4] = (key, first position, records, 0), n_pieces [1] (an error when it exceeds
+ *                              max_pieces).  Synchronises. */
 INT kge_transe_record_dwords(const kge_model_desc *m);
 int kge_transe_deferred_groups(int32_t *n_groups);
 int kge_transe_step_scratch_read(int which, INT offset, INT count, void *host_out);
+int kge_counts_sort_test(const int32_t *keys, INT n_keys, INT rows, INT rpb, INT plan_cap, int32_t *sorted_keys, int32_t *sorted_ids,
+                         int32_t *n_live, int32_t *bucket_start, int32_t *row_span, int32_t *pieces, INT max_pieces, int32_t *n_pieces,
+                         void *stream);
 int kge_transe_emit_records(const kge_model_desc *m, const float *d_ent, const float *d_rel, const int32_t *d_h, const int32_t *d_t,
                             const int32_t *d_r, INT n_pos, INT n_neg, INT stride, INT denom, uint32_t *d_rec, int32_t *d_dst,
                             float *d_resid_ent, float *d_resid_rel, float *d_loss, void *stream);

@@ -132,6 +132,7 @@ def _declare(L):
     L.kge_transe_apply_counts.argtypes = [vp, vp, vp, vp, vp, i64, i32, i64, i32, f32, f32, f32, f32, vp]
     L.kge_transe_deferred_groups.argtypes = [ctypes.POINTER(ctypes.c_int32)]
     L.kge_transe_step_scratch_read.argtypes = [ctypes.c_int, i64, i64, vp]
+    L.kge_counts_sort_test.argtypes = [vp, i64, i64, i64, i64, vp, vp, vp, vp, vp, vp, i64, vp, vp]
     L.kge_transe_apply_counts_tables.argtypes = [ctypes.POINTER(ModelDesc), vp, vp, vp, vp, vp, i64, i32, f32, f32, f32, f32, vp]
     L.kge_transe_train_step_counts.argtypes = [ctypes.POINTER(ModelDesc), vp, vp, vp, vp, vp, vp, i64, i64, i64, i64, vp, vp, i32, i32,
                                                f32, f32, f32, f32, vp, vp]

@@ -108,10 +108,14 @@ struct Engine {
     int persist_trace = 0;      // measurement hook: the persistent launch stamps its phase boundaries (kge_persistent_trace)
     int persist_threads = 512;  // threads per workgroup of the persistent launch (512, or 1024: spills at its 128-register cap, measured slower)
     int counts_force_sort = 0;  // test hook: take the sort+segsum reduction even for small tables
+    int counts_sort_tiles = 1;  // record sort of the counting paths: 1 = two launches (per-tile sort, then one workgroup per bucket collecting its segments: transe_counts.hip bkt_tile_kernel / bkt_merge_kernel), 0 = histogram + scatter + sort (A/B runs, test reference); 1024 / 4096 = two launches at that tile size (measurements; 1 means 2048)
     // percent of an armed sampler's workgroups riding in bkt_hist / bkt_scatter / bkt_sort / the launch that ends the step (byte 0..3).
-    // Default: all of it in the scatter launch.  Spread 20/35/20/25 over the four it was SLOWER (their sum 68 -> 76 us per bench step):
-    // a part of the sampler takes a full latency chain (~8 us) however small it is, and it did not hide behind the host kernels.
-    int ride_shares = 100 << 8;
+    // The two-launch sort has no histogram launch: byte 0 is IGNORED there, byte 1 is its tile pass, byte 2 its bucket pass.
+    // -1 (default) = automatic: the three-launch form carries all of it in the scatter launch -- spread 20/35/20/25 over the four it was
+    // SLOWER (their sum 68 -> 76 us per bench step): a part of the sampler takes a full latency chain (~8 us) however small it is, and
+    // it did not hide behind the host kernels.  The two-launch form carries half in each of its launches (50 << 8 | 50 << 16): measured
+    // against all of it in the tile pass and all of it in the closing launch.
+    int ride_shares = -1;
     int counts_fused = 1;       // kge_transe_train_step_counts: 1 = segmented sum and optimizer in one kernel (segapply_kernel); 0 = segsum + apply kernels
     int counts_fused_diag = 0;  // measurement hook, see SegApplyArgs::diag
     int typed_sampling = 0;     // kge_set_typed_sampling: entity negatives from the relation's type lists (sampler_dev.hpp typed_pick)

@@ -49,7 +49,8 @@ struct CtWork {
     DevBuf<int32_t> dst, dst_sorted, ids, ids_sorted;
     DevBuf<int32_t> n_valid;
     DevBuf<int32_t> tile_hist, bucket_start;   // LDS-bucket path: bucket totals + cursors, bucket starts
-    DevBuf<int32_t> pairs;                     // [2*M] (record id, destination) grouped by bucket
+    DevBuf<int32_t> pairs;                     // [2*M] (record id, destination) grouped by bucket (two-launch sort: by tile, then bucket)
+    DevBuf<int32_t> tile_off;                  // two-launch sort: [tiles][NB + 1] exclusive bucket offsets inside each tile
     DevBuf<float2> pair_aux;                   // [M] pair-count path: (a, +-1/|projected|) per record
     DevBuf<char> sort_tmp;                     // rocPRIM scratch (sort, scan)
     DevBuf<float> ctxn;                        // pair-count path, TransH: normalised normal vectors
@@ -431,12 +432,15 @@ __global__ __launch_bounds__(256) void bkt_scatter_kernel(const int32_t *__restr
 }
 
 
-// The three bucketing launches (and the launch that ends the step) can each take a PART of an armed sampler along: engine option
-// "ride_shares", percent of the sampler's workgroups for hist / scatter / sort / closing launch.  Default: all of it in the
-// scatter launch (measured: spreading it made the step slower, see engine.hpp).
-static unsigned take_ride(SamplerArgs &ride, int which) {
+// The bucketing launches (and the launch that ends the step) can each take a PART of an armed sampler along: engine option
+// "ride_shares", percent of the sampler's workgroups for hist / scatter / sort / closing launch; the two-launch sort reads byte 1
+// for its tile pass and byte 2 for its bucket pass (byte 0 is ignored there).  Default (-1): all of it in the scatter launch of
+// the three-launch form (measured: spreading it made the step slower, see engine.hpp), half in each launch of the two-launch form.
+constexpr int kRideThreeLaunch = 100 << 8, kRideTwoLaunch = (50 << 8) | (50 << 16);
+static unsigned take_ride(SamplerArgs &ride, int which, bool two_launch = false) {
     unsigned n_ride = 0;
-    const int pct = (engine().ride_shares >> (8 * which)) & 0xFF;
+    const int shares = engine().ride_shares >= 0 ? engine().ride_shares : two_launch ? kRideTwoLaunch : kRideThreeLaunch;
+    const int pct = (shares >> (8 * which)) & 0xFF;
     // this translation unit's copy of the jump table first: an armed sampler is only taken along once it can run here
     if (pct == 0 || upload_jump_table() != KGE_OK || !take_attached_sampler(ride, n_ride, pct >= 100 ? 1.0f : 0.01f * (float)pct)) n_ride = 0;
     return n_ride;
@@ -461,7 +465,7 @@ static void launch_bkt_scatter(const int32_t *dst, int n_tiles, int M, int rpb, 
 // lies in the sorted list -- row_span[key] = (first position, number of records), for EVERY key of the bucket, empty ones
 // included -- which is all segapply_kernel needs to give every row a team of its own (a row = two adjacent keys = two
 // homogeneous record lists).  A row with a list of more than `cap` records is cut into pieces of at most `cap` records of one
-// list (slots from one global counter, zeroed by bkt_hist_kernel), each piece a team of its own that adds into the count image.
+// list (slots from one global counter, zeroed by the first launch of the sort), each piece a team of its own that adds into the count image.
 // rpb is even, so the two keys of a row lie in the same bucket.
 struct SegPlan {
     int2 *row_span;        // [2 * virtual rows]
@@ -470,41 +474,28 @@ struct SegPlan {
     int cap;
 };
 
-template <bool PLAN>
-__global__ __launch_bounds__(256) void bkt_sort_kernel(const int2 *__restrict__ pairs, const int32_t *__restrict__ bucket_start,
-                                                       int rpb, int rows, int32_t *__restrict__ out_keys,
-                                                       int32_t *__restrict__ out_ids, int32_t *__restrict__ bucket_total,
-                                                       int32_t *__restrict__ cursor, SegPlan plan, SamplerArgs ride) {
-    extern __shared__ int lds_h[];   // [rpb] histogram, then running offsets
-    if ((int)blockIdx.x >= NB) {           // a part of the next batch's sampler riding along (see bkt_scatter_kernel)
-        __shared__ float bern_lds[kBernLds];
-        sample_block_ride(ride, (long long)blockIdx.x - NB, bern_lds);
-        return;
-    }
-    const int b = blockIdx.x;
-    const int row0 = b * rpb;
-    if (threadIdx.x == 0) {   // totals and cursors back to zero for the next step (block 0 also the trash bucket's)
-        bucket_total[b] = 0; cursor[b] = 0;
-        if (b == 0) { bucket_total[NB] = 0; cursor[NB] = 0; }
-    }
-    if (row0 >= rows) return;
-    const int start = bucket_start[b], end = bucket_start[b + 1];
+// The part of the second level that both forms of the sort share: the pairs of bucket `row0 / rpb` are pair 0 .. end - start - 1 of
+// `fetch`; lds_h [rpb] is the histogram, then the running offsets.  The caller has made whatever fetch reads visible to the block.
+template <bool PLAN, class Fetch>
+__device__ __forceinline__ void bucket_rows_sort(int row0, int start, int end, int rpb, int rows, int *lds_h, int32_t *__restrict__ out_keys,
+                                                 int32_t *__restrict__ out_ids, const SegPlan &plan, Fetch fetch) {
     for (int i = threadIdx.x; i < rpb; i += 256) lds_h[i] = 0;
     if (end == start) {
         if constexpr (PLAN)
             for (int i = threadIdx.x; i < rpb; i += 256) if (row0 + i < rows) plan.row_span[row0 + i] = make_int2(start, 0);
         return;
     }
+    const int n = end - start;
     // the first 256*PC pairs of the bucket (all of it, normally) are read ONCE, into registers, for both passes
     constexpr int PC = 8;
     int2 pr[PC];
 #pragma unroll
-    for (int k = 0; k < PC; k++) pr[k] = pairs[min(start + (int)threadIdx.x + 256 * k, end - 1)];
+    for (int k = 0; k < PC; k++) { const int i = threadIdx.x + 256 * k; pr[k] = i < n ? fetch(i) : make_int2(0, 0); }
     __syncthreads();
 #pragma unroll
     for (int k = 0; k < PC; k++)
         if (start + (int)threadIdx.x + 256 * k < end) atomicAdd(&lds_h[pr[k].y - row0], 1);
-    for (int i = start + 256 * PC + threadIdx.x; i < end; i += 256) atomicAdd(&lds_h[pairs[i].y - row0], 1);
+    for (int i = 256 * PC + threadIdx.x; i < n; i += 256) atomicAdd(&lds_h[fetch(i).y - row0], 1);
     __syncthreads();
     {   // exclusive scan of the rpb counters: every thread sums its own contiguous span, one wave scans the 256 span sums,
         // every thread then rewrites its span (a single wave walking all counters 64 at a time took 105 serial rounds at
@@ -539,8 +530,8 @@ __global__ __launch_bounds__(256) void bkt_sort_kernel(const int2 *__restrict__ 
             out_keys[pos] = pr[k].y;
             out_ids[pos] = pr[k].x;
         }
-    for (int i = start + 256 * PC + threadIdx.x; i < end; i += 256) {
-        const int2 q = pairs[i];
+    for (int i = 256 * PC + threadIdx.x; i < n; i += 256) {
+        const int2 q = fetch(i);
         const int pos = start + atomicAdd(&lds_h[q.y - row0], 1);
         out_keys[pos] = q.y;
         out_ids[pos] = q.x;
@@ -564,6 +555,28 @@ __global__ __launch_bounds__(256) void bkt_sort_kernel(const int2 *__restrict__ 
     }
 }
 
+template <bool PLAN>
+__global__ __launch_bounds__(256) void bkt_sort_kernel(const int2 *__restrict__ pairs, const int32_t *__restrict__ bucket_start,
+                                                       int rpb, int rows, int32_t *__restrict__ out_keys,
+                                                       int32_t *__restrict__ out_ids, int32_t *__restrict__ bucket_total,
+                                                       int32_t *__restrict__ cursor, SegPlan plan, SamplerArgs ride) {
+    extern __shared__ int lds_h[];   // [rpb] histogram, then running offsets
+    if ((int)blockIdx.x >= NB) {           // a part of the next batch's sampler riding along (see bkt_scatter_kernel)
+        __shared__ float bern_lds[kBernLds];
+        sample_block_ride(ride, (long long)blockIdx.x - NB, bern_lds);
+        return;
+    }
+    const int b = blockIdx.x;
+    const int row0 = b * rpb;
+    if (threadIdx.x == 0) {   // totals and cursors back to zero for the next step (block 0 also the trash bucket's)
+        bucket_total[b] = 0; cursor[b] = 0;
+        if (b == 0) { bucket_total[NB] = 0; cursor[NB] = 0; }
+    }
+    if (row0 >= rows) return;
+    const int start = bucket_start[b], end = bucket_start[b + 1];
+    bucket_rows_sort<PLAN>(row0, start, end, rpb, rows, lds_h, out_keys, out_ids, plan, [&](int i) { return pairs[start + i]; });
+}
+
 
 template <bool PLAN>
 static void launch_bkt_sort(int2 *pairs, int rpb, int rows, int32_t *totals, int32_t *cursor, const SegPlan &plan, hipStream_t stream) {
@@ -571,6 +584,159 @@ static void launch_bkt_sort(int2 *pairs, int rpb, int rows, int32_t *totals, int
     const unsigned n_ride = take_ride(ride, 2);
     hipLaunchKernelGGL(bkt_sort_kernel<PLAN>, dim3(NB + n_ride), dim3(256), sizeof(int) * (size_t)rpb, stream, pairs, g_c.bucket_start, rpb, rows,
                        g_c.dst_sorted, g_c.ids_sorted, totals, cursor, plan, ride);
+}
+
+// ---------------------------------------------------------------------------------------------
+// The same sort in TWO launches (engine option "counts_sort_tiles", the default): no sizing pass, no global atomics, nothing
+// to re-zero between steps.
+//   tile pass    one workgroup per tile of T keys: the tile's live pairs, grouped by bucket in an LDS staging buffer, go out as
+//                ONE contiguous run at tile_pairs[t * T ...], and the tile's exclusive bucket offsets to off[t][0 .. NB]
+//                (off[t][NB] = the tile's live count).  Keys that carry no record are dropped at the load: no atomic, no store.
+//   bucket pass  one workgroup per bucket b reads column b and b + 1 of `off`: bucket_start[b] = sum_t off[t][b]; segment t of
+//                the bucket is tile_pairs[t * T + off[t][b] .. t * T + off[t][b + 1]).  The segments are read BY PAIR INDEX over
+//                all 256 threads (a bisection in the LDS table of segment starts): dst is slot-major, so a tile of relation
+//                keys sends ~130 pairs to each of ~31 buckets where an entity bucket gets ~3 per tile -- one thread per segment
+//                would wait on the long ones.  From there on it is bucket_rows_sort, as in bkt_sort_kernel.
+// The bucket pass keeps two words per tile in LDS: at most kSortMaxTiles tiles (M <= 4 194 304 keys at the default tile; the
+// headline batch has 952 392), more take the three-launch form.
+// ---------------------------------------------------------------------------------------------
+constexpr int kSortTile = 2048;       // keys per tile (default; 1024 and 4096 are compiled for measurements)
+constexpr int kSortMaxTiles = 2048;
+constexpr int kOffStride = NB + 1;
+
+template <int T>
+__global__ __launch_bounds__(256) void bkt_tile_kernel(const int32_t *__restrict__ dst, int M, int rpb, int2 *__restrict__ tile_pairs,
+                                                       int32_t *__restrict__ tile_off, int32_t *__restrict__ plan_counter, SamplerArgs ride,
+                                                       int n_tiles) {
+    if ((int)blockIdx.x >= n_tiles) {      // a part of the next batch's sampler riding along (see bkt_scatter_kernel)
+        __shared__ float bern_lds[kBernLds];
+        sample_block_ride(ride, (long long)blockIdx.x - n_tiles, bern_lds);
+        return;
+    }
+    constexpr int K = T / 256;
+    __shared__ int hist[NB];
+    __shared__ int wave_total[4];
+    __shared__ int2 stage[T];
+    if (plan_counter && blockIdx.x == 0 && threadIdx.x == 0) plan_counter[0] = 0;   // fused step: the piece counter the bucket pass adds to
+    const int base = blockIdx.x * T;      // (n_tiles <= kSortMaxTiles: base + T stays far below 2^31)
+    int d[K], code[K];
+#pragma unroll
+    for (int k = 0; k < K; k++) {
+        const int m = base + threadIdx.x + 256 * k;
+        d[k] = m < M ? dst[m] : -1;
+    }
+    for (int i = threadIdx.x; i < NB; i += 256) hist[i] = 0;
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < K; k++) {         // (bucket, rank inside the tile's part of it); a key < 0 is a huge unsigned: no bucket
+        const unsigned bk = (unsigned)d[k] / (unsigned)rpb;
+        code[k] = bk < (unsigned)NB ? (int)(bk << 16) | atomicAdd(&hist[bk], 1) : -1;
+    }
+    __syncthreads();
+    {   // exclusive scan of the NB counters, two per thread: a shuffle scan per wave, the wave totals through LDS
+        const int v0 = hist[2 * threadIdx.x], v1 = hist[2 * threadIdx.x + 1], run = v0 + v1;
+        const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+        int incl = run;
+#pragma unroll
+        for (int off = 1; off < 64; off <<= 1) { const int t = __shfl_up(incl, off); if (lane >= off) incl += t; }
+        if (lane == 63) wave_total[wave] = incl;
+        __syncthreads();
+        int excl = incl - run;
+        for (int w = 0; w < wave; w++) excl += wave_total[w];
+        hist[2 * threadIdx.x] = excl; hist[2 * threadIdx.x + 1] = excl + v0;
+        int32_t *off = tile_off + (size_t)blockIdx.x * kOffStride;
+        off[2 * threadIdx.x] = excl; off[2 * threadIdx.x + 1] = excl + v0;
+        if (threadIdx.x == 255) off[NB] = excl + run;
+    }
+    __syncthreads();
+    const int live = wave_total[0] + wave_total[1] + wave_total[2] + wave_total[3];
+#pragma unroll
+    for (int k = 0; k < K; k++)
+        if (code[k] >= 0) stage[hist[code[k] >> 16] + (code[k] & 0xFFFF)] = make_int2(base + (int)threadIdx.x + 256 * k, d[k]);
+    __syncthreads();
+    for (int i = threadIdx.x; i < live; i += 256) tile_pairs[base + i] = stage[i];
+}
+
+template <bool PLAN, int T>
+__global__ __launch_bounds__(256) void bkt_merge_kernel(const int2 *__restrict__ tile_pairs, const int32_t *__restrict__ tile_off, int n_tiles,
+                                                        int32_t *__restrict__ bucket_start, int M, int rpb, int rows,
+                                                        int32_t *__restrict__ out_keys, int32_t *__restrict__ out_ids, SegPlan plan,
+                                                        SamplerArgs ride) {
+    extern __shared__ int lds_h[];   // [rpb] histogram, then running offsets
+    if ((int)blockIdx.x >= NB) {           // a part of the next batch's sampler riding along (see bkt_scatter_kernel)
+        __shared__ float bern_lds[kBernLds];
+        sample_block_ride(ride, (long long)blockIdx.x - NB, bern_lds);
+        return;
+    }
+    __shared__ int seg_pre[kSortMaxTiles + 1];   // pairs of the bucket in the tiles before t
+    __shared__ int seg_src[kSortMaxTiles];       // where segment t starts in tile_pairs
+    __shared__ int wave_len[4], wave_below[4];
+    const int b = blockIdx.x;
+    // every thread takes a contiguous span of the tiles (all its loads in flight together); the block scans the span sums
+    constexpr int PER = kSortMaxTiles / 256;
+    const int per = (n_tiles + 255) / 256;
+    const int t_lo = min((int)threadIdx.x * per, n_tiles), t_hi = min(t_lo + per, n_tiles);
+    int a[PER], e[PER];
+#pragma unroll
+    for (int j = 0; j < PER; j++) {
+        const int32_t *off = tile_off + (size_t)min(t_lo + j, max(n_tiles - 1, 0)) * kOffStride + b;   // (clamped: always a valid row)
+        const bool mine = t_lo + j < t_hi;
+        a[j] = mine ? off[0] : 0;
+        e[j] = mine ? off[1] : 0;
+    }
+    int len = 0, below = 0;
+#pragma unroll
+    for (int j = 0; j < PER; j++)
+        if (t_lo + j < t_hi) {
+            seg_src[t_lo + j] = (t_lo + j) * T + a[j];
+            seg_pre[t_lo + j] = len;
+            len += e[j] - a[j];
+            below += a[j];
+        }
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    int incl = len;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) { const int t = __shfl_up(incl, off); if (lane >= off) incl += t; }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) below += __shfl_xor(below, off);
+    if (lane == 63) { wave_len[wave] = incl; wave_below[wave] = below; }
+    __syncthreads();
+    int excl = incl - len;
+    for (int w = 0; w < wave; w++) excl += wave_len[w];
+    for (int t = t_lo; t < t_hi; t++) seg_pre[t] += excl;
+    const int start = wave_below[0] + wave_below[1] + wave_below[2] + wave_below[3];
+    const int end = start + wave_len[0] + wave_len[1] + wave_len[2] + wave_len[3];
+    if (threadIdx.x == 0) {
+        seg_pre[n_tiles] = end - start;
+        bucket_start[b] = start;
+        if (b == NB - 1) { bucket_start[NB] = end; bucket_start[NB + 1] = M; }   // [NB]: the number of live records
+    }
+    __syncthreads();
+    const int row0 = b * rpb;
+    if (row0 >= rows) return;
+    bucket_rows_sort<PLAN>(row0, start, end, rpb, rows, lds_h, out_keys, out_ids, plan, [&](int i) {
+        int lo = 0, hi = n_tiles;          // the last tile t with seg_pre[t] <= i (empty segments repeat a value: the last one holds pair i)
+        while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (seg_pre[mid] <= i) lo = mid; else hi = mid; }
+        return tile_pairs[seg_src[lo] + (i - seg_pre[lo])];
+    });
+}
+
+template <int T>
+static void launch_tile_sort(const int32_t *dst, int n_tiles, int M, int rows, int rpb, const SegPlan *plan, hipStream_t stream) {
+    int2 *pairs = reinterpret_cast<int2 *>(g_c.pairs.ptr());
+    SamplerArgs ride = {};
+    unsigned n_ride = take_ride(ride, 1, true);
+    if (n_tiles + n_ride > 0)
+        hipLaunchKernelGGL(bkt_tile_kernel<T>, dim3((unsigned)n_tiles + n_ride), dim3(256), 0, stream, dst, M, rpb, pairs, g_c.tile_off.ptr(),
+                           plan ? plan->n_pieces : nullptr, ride, n_tiles);
+    ride = SamplerArgs();
+    n_ride = take_ride(ride, 2, true);
+    if (plan)
+        hipLaunchKernelGGL((bkt_merge_kernel<true, T>), dim3(NB + n_ride), dim3(256), sizeof(int) * (size_t)rpb, stream, pairs, g_c.tile_off.ptr(),
+                           n_tiles, g_c.bucket_start.ptr(), M, rpb, rows, g_c.dst_sorted.ptr(), g_c.ids_sorted.ptr(), *plan, ride);
+    else
+        hipLaunchKernelGGL((bkt_merge_kernel<false, T>), dim3(NB + n_ride), dim3(256), sizeof(int) * (size_t)rpb, stream, pairs, g_c.tile_off.ptr(),
+                           n_tiles, g_c.bucket_start.ptr(), M, rpb, rows, g_c.dst_sorted.ptr(), g_c.ids_sorted.ptr(), SegPlan(), ride);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1108,11 +1274,24 @@ __global__ __launch_bounds__(256) void segsum_pairs_kernel(const uint32_t *__res
 // (key, record id) pairs in g_c.dst_sorted / g_c.ids_sorted and hand back where the number of live records lies. ----
 
 // Two-level bucket sort of the M keys in `dst` (-1 = no record) over `rows` rows, rpb rows per bucket (row spaces up to NB * 8192).
-// plan: the fused step's form (bkt_sort_kernel<true>); the hist launch re-zeroes its piece counter.
+// plan: the fused step's form (the bucket pass also writes row spans and pieces); the first launch re-zeroes its piece counter.
+// Engine option "counts_sort_tiles": 1 = the two-launch form (tile pass + bucket pass), 0 = hist + scatter + sort; inputs of more
+// than kSortMaxTiles tiles take the latter too.
 int bucket_sort_records(const int32_t *dst, int64_t M, int rows, int rpb, const SegPlan *plan, hipStream_t stream, const int32_t *&n_live) {
     int rc;
     bool grew;
     if ((rc = g_c.bucket_start.reserve(NB + 2, "counts bucket_start"))) return rc;
+    n_live = g_c.bucket_start + NB;   // start of the trash bucket == number of live records
+    const int opt = engine().counts_sort_tiles;
+    const int T = opt == 1024 || opt == 4096 ? opt : kSortTile;
+    const int64_t n_tiles_new = (M + T - 1) / T;
+    if (opt != 0 && n_tiles_new <= kSortMaxTiles) {
+        if ((rc = g_c.tile_off.reserve((n_tiles_new + 1) * kOffStride, "counts tile offsets"))) return rc;
+        if (T == 1024) launch_tile_sort<1024>(dst, (int)n_tiles_new, (int)M, rows, rpb, plan, stream);
+        else if (T == 4096) launch_tile_sort<4096>(dst, (int)n_tiles_new, (int)M, rows, rpb, plan, stream);
+        else launch_tile_sort<kSortTile>(dst, (int)n_tiles_new, (int)M, rows, rpb, plan, stream);
+        return KGE_OK;
+    }
     if ((rc = g_c.tile_hist.reserve(2 * (NB + 2), "counts bucket totals/cursors", &grew))) return rc;
     if (grew && (rc = hip_check(hipMemset(g_c.tile_hist, 0, sizeof(int32_t) * 2 * (NB + 2)), "zero bucket totals"))) { g_c.tile_hist.free(); return rc; }
     const int n_tiles = (int)((M + BTILE - 1) / BTILE);
@@ -1122,7 +1301,6 @@ int bucket_sort_records(const int32_t *dst, int64_t M, int rows, int rpb, const 
     launch_bkt_scatter(dst, n_tiles, (int)M, rpb, totals, cursor, pairs, stream);
     if (plan) launch_bkt_sort<true>(pairs, rpb, rows, totals, cursor, *plan, stream);
     else launch_bkt_sort<false>(pairs, rpb, rows, totals, cursor, SegPlan(), stream);
-    n_live = g_c.bucket_start + NB;   // start of the trash bucket == number of live records
     return KGE_OK;
 }
 
@@ -1881,6 +2059,46 @@ int kge_transe_emit_records(const kge_model_desc *m, const float *d_ent, const f
     if (n_pos == 0) return hip_check(hipMemsetAsync(d_loss, 0, sizeof(float), stream), "zero loss");
     return launch_transe_emit(*m, d_ent, d_rel, d_resid_ent, d_resid_rel, d_h, d_t, d_r, n_pos, n_neg, stride, denom, d_rec, d_dst, 1,
                               d_loss, stream, true);
+}
+
+int kge_counts_sort_test(const int32_t *keys, INT n_keys, INT rows, INT rpb, INT plan_cap, int32_t *sorted_keys, int32_t *sorted_ids,
+                         int32_t *n_live, int32_t *bucket_start, int32_t *row_span, int32_t *pieces, INT max_pieces, int32_t *n_pieces,
+                         void *stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    if (!device_ok()) return fail(KGE_ERR_NO_DEVICE, "kge_counts_sort_test: no usable HIP device");
+    const bool with_plan = plan_cap > 0;
+    if (!keys || n_keys < 1 || n_keys >= (int64_t(1) << 31) || rows < 1 || rpb < 1 || rpb > 8192 || rows > (INT)NB * rpb || !sorted_keys ||
+        !sorted_ids || !n_live || !bucket_start || (with_plan && (rpb % 2 || !row_span || !pieces || !n_pieces || max_pieces < 0)))
+        return fail(KGE_ERR_BAD_ARG, "kge_counts_sort_test: bad arguments");
+    for (INT i = 0; i < n_keys; i++)
+        if (keys[i] >= rows) return fail(KGE_ERR_BAD_ARG, "kge_counts_sort_test: key outside the row space");
+    const int64_t M = n_keys;
+    int rc = ensure_counts_work(M, 0);
+    if (rc) return rc;
+    SegPlan plan = SegPlan();
+    if (with_plan) {
+        bool grew;
+        if ((rc = g_c.pieces.reserve(M / plan_cap + M + 16, "sort test piece table"))) return rc;
+        if ((rc = g_c.n_pieces.reserve(1, "fused step piece counter", &grew))) return rc;
+        if (grew && (rc = hip_check(hipMemset(g_c.n_pieces, 0, sizeof(int32_t)), "zero piece counter"))) { g_c.n_pieces.free(); return rc; }
+        if ((rc = g_c.row_span.reserve(rows, "sort test row spans"))) return rc;
+        plan.row_span = g_c.row_span; plan.pieces = g_c.pieces; plan.n_pieces = g_c.n_pieces; plan.cap = (int)plan_cap;
+    }
+    if ((rc = hip_check(hipMemcpyAsync(g_c.dst, keys, sizeof(int32_t) * (size_t)M, hipMemcpyHostToDevice, stream), "kge_counts_sort_test: upload"))) return rc;
+    const int32_t *n_live_p;
+    if ((rc = bucket_sort_records(g_c.dst, M, (int)rows, (int)rpb, with_plan ? &plan : nullptr, stream, n_live_p))) return rc;
+    if ((rc = hip_check(hipGetLastError(), "kge_counts_sort_test: launch"))) return rc;
+    if ((rc = hip_check(hipDeviceSynchronize(), "kge_counts_sort_test: synchronize"))) return rc;
+    if ((rc = hip_check(hipMemcpy(sorted_keys, g_c.dst_sorted, sizeof(int32_t) * (size_t)M, hipMemcpyDeviceToHost), "kge_counts_sort_test: copy"))) return rc;
+    if ((rc = hip_check(hipMemcpy(sorted_ids, g_c.ids_sorted, sizeof(int32_t) * (size_t)M, hipMemcpyDeviceToHost), "kge_counts_sort_test: copy"))) return rc;
+    if ((rc = hip_check(hipMemcpy(n_live, n_live_p, sizeof(int32_t), hipMemcpyDeviceToHost), "kge_counts_sort_test: copy"))) return rc;
+    if ((rc = hip_check(hipMemcpy(bucket_start, g_c.bucket_start, sizeof(int32_t) * (NB + 2), hipMemcpyDeviceToHost), "kge_counts_sort_test: copy"))) return rc;
+    if (!with_plan) return KGE_OK;
+    if ((rc = hip_check(hipMemcpy(row_span, g_c.row_span, sizeof(int2) * (size_t)rows, hipMemcpyDeviceToHost), "kge_counts_sort_test: copy"))) return rc;
+    if ((rc = hip_check(hipMemcpy(n_pieces, g_c.n_pieces, sizeof(int32_t), hipMemcpyDeviceToHost), "kge_counts_sort_test: copy"))) return rc;
+    if (*n_pieces > max_pieces) return fail(KGE_ERR_BAD_ARG, "kge_counts_sort_test: more pieces than max_pieces");
+    if (*n_pieces > 0) rc = hip_check(hipMemcpy(pieces, g_c.pieces, sizeof(int4) * (size_t)*n_pieces, hipMemcpyDeviceToHost), "kge_counts_sort_test: copy");
+    return rc;
 }
 
 int kge_transe_step_scratch_read(int which, INT offset, INT count, void *host_out) {

@@ -107,7 +107,7 @@ def main():
         torch.cuda.synchronize()
         return (time.perf_counter() - t0) / args.steps * 1e6
 
-    default_shares = 100 << 8
+    default_shares = -1      # automatic (include/kge_mi355.h "ride_shares")
     steps = {"untyped": [], "untyped_own_launch": [], "typed": []}
     for _ in range(args.runs):
         for kind in steps:
