@@ -16,7 +16,7 @@ import os
 
 import numpy as np
 
-from . import _lib, shard_eval
+from . import _lib, shard_eval, step_plan, train_paths
 from ._lib import KgeError
 
 
@@ -386,51 +386,22 @@ class Config(object):
         '''
         import torch
         self.model = model
-        self._shard_plan = self._plan_entity_shard(model)
+        # which path the steps will take (step_plan.py), decided before anything is created: a row-sharded entity table is drawn
+        # shard-sized.  `sparse_rows` None = automatic, True / False = the caller's wish; `use_counts` likewise a wish until here
+        n_neg = self.negative_ent + self.negative_rel
+        probe = model(config=self, define=False)
+        p = self._plan = step_plan.plan(
+            probe.model_id, self.opt_method, getattr(self, "sparse_rows", None), getattr(self, "use_counts", True),
+            self.lib.kge_transe_counts_supported(ctypes.byref(probe.descriptor()), n_neg), self.entTotal, self.relTotal,
+            self.hidden_size, self.batch_size, n_neg, getattr(self, "sparse_threshold_bytes", None), self.adagrad_initial_accumulator)
+        self.use_counts, self.sparse_rows, self.sparse_inplace = p.use_counts, p.sparse_rows, p.sparse_inplace
+        self._adam, self._lazy_adam, self._adagrad = p.adam, p.lazy_adam, p.adagrad
+        self._has_slots, self._rows_rule = p.has_slots, p.rows_rule
+        self._shard_plan = self._plan_entity_shard(probe.model_id)
         self.trainModel = self.model(config=self, define=True)
         m = self.trainModel
         self._desc = m.descriptor()
         self._tables = [m.parameter_lists[n] for n in m.table_names]
-        self._adam = self.opt_method in ("Adam", "adam")  # distribute_training.py:95
-        # opt-in, NON-PARITY: Adam on the touched rows only (tf.contrib.opt.LazyAdamOptimizer's rule) for tables whose dense
-        # TF1-Adam sweep -- 32 bytes per element per step, the reference's semantics -- would dominate the step.  Rides on the
-        # sparse-row path; `_has_slots` = "m / v tables and beta powers exist" (both Adam flavours)
-        self._lazy_adam = self.opt_method in ("LazyAdam", "lazyadam", "lazy_adam")
-        self._has_slots = self._adam or self._lazy_adam
-        # opt-in: TF1's AdagradOptimizer (upstream OpenKE offers it; the reference sends the name to SGD).  Like LazyAdam it rides on
-        # the touched-rows paths, but exactly: an element with zero gradient keeps its value and its accumulator bit for bit, so
-        # "only the touched rows" IS the dense rule.  One accumulator table per parameter table, nothing to advance between steps.
-        # TransR has no record path and keeps its dense gradient tables (kge_adagrad_update_tables), in one process only.
-        self._adagrad = self.opt_method in ("Adagrad", "adagrad")
-        if self._adagrad and not (float(self.adagrad_initial_accumulator) > 0.0):
-            raise KgeError("adagrad_initial_accumulator must be positive (the Adagrad rule divides by sqrt(accumulator), without an "
-                           "epsilon), got %r" % (self.adagrad_initial_accumulator,))
-        self._rows_rule = self._lazy_adam or self._adagrad        # optimizers that ARE a choice of touched rows
-        # TransE: exact integer sign-count gradients instead of fp32 atomics (include/kge_mi355.h)
-        n_neg = self.negative_ent + self.negative_rel
-        self.use_counts = bool(getattr(self, "use_counts", True)) and bool(
-            self.lib.kge_transe_counts_supported(ctypes.byref(self._desc), n_neg))
-        # sparse-row mode: no dense gradient / count image at all.  The int8 records are reduced into a compact
-        # [touched rows, D] image and only those rows are updated; across ranks the records themselves are
-        # all-gathered (the sparse touched-row exchange of BASELINE config #5).  SGD only: TF1's sparse Adam
-        # sweeps every row of m, v and the table each step, which is the dense path by definition.
-        requested = getattr(self, "sparse_rows", None)   # None = automatic, True / False = the caller's wish
-        table_bytes, sparse = self._wants_sparse_rows(n_neg)
-        self.sparse_rows = (bool(sparse) or self._rows_rule) and self.use_counts and not self._adam
-        # TransH / TransD (and TransE outside the sign-count path) with SGD: the touched rows are updated in place from float
-        # gradient records (kge_forward_backward_sgd_rows) -- no gradient tables, no sweep.  On request, or by itself for tables
-        # beyond 2 GB (measured at 4 GB, dim 200, B = 131 072, n = 1: TransH 1.63 -> 0.70 ms, TransD 2.83 -> 0.97 ms per step and
-        # half the memory, profiles/r03_h_*; the dense form's sweep scales with the table, so the two tie near 1 GB)
-        # With LazyAdam the same records end in the Adam rule on the touched rows and their moments instead of the add
-        # (kge_forward_backward_adam_rows): asking for LazyAdam IS asking for touched rows, whatever `sparse_rows` says.
-        vector_model = m.model_id in (_lib.TRANSE, _lib.TRANSH, _lib.TRANSD)
-        self.sparse_inplace = bool(not self.sparse_rows and vector_model and not self._adam and
-                                   (self._rows_rule or requested or (requested is None and table_bytes > (2 << 30))))
-        if self._lazy_adam and not (self.sparse_rows or self.sparse_inplace):
-            raise KgeError("LazyAdam (touched rows only, NON-PARITY) needs TransE, TransH or TransD: TransR's gradient is a whole "
-                           "matrix per relation and has no record path")
-        if requested and not (self.sparse_rows or self.sparse_inplace):
-            raise KgeError("sparse_rows needs TransE / TransH / TransD with SGD, LazyAdam or Adagrad")
         self._grads = [] if (self.sparse_rows or self.sparse_inplace) else [torch.zeros_like(t) for t in self._tables]
         if self._has_slots:
             self._adam_m = [torch.zeros_like(t) for t in self._tables]
@@ -467,28 +438,11 @@ class Config(object):
                                        device=self.device)
         self._setup_partition()
 
-    def _wants_sparse_rows(self, n_neg):
-        """(table bytes, sparse rows wanted?) -- the caller's wish (`sparse_rows` True / False) or, left at None, the measured rule."""
-        table_bytes = (self.entTotal + self.relTotal) * self.hidden_size * 4
-        sparse = getattr(self, "sparse_rows", None)
-        if sparse is None:
-            # Measured cross-over on one MI355X (tools/sparse_crossover.sh, profiles/r03_sparse_crossover.jsonl: dim 512,
-            # B = 131 072, n = 1, tables of 0.26 .. 8.2 GB): the dense step costs the batch's work plus a sweep of the whole
-            # table and count image, the sparse step the batch's work plus its sort -- they tie at 0.26 GB (0.68 vs 0.70 ms),
-            # sparse rows win by 18 % at 0.5 GB and 5.4x at 8 GB.  The tie sits where the table is ~0.3x the bytes of the rows
-            # a step touches (1.07 GB there); below 128 MB the dense path's image fits the caches and it is kept.
-            touched_bytes = self.batch_size * (3 + n_neg) * self.hidden_size * 4
-            threshold = getattr(self, "sparse_threshold_bytes", None)
-            if threshold is None:
-                threshold = max(128 << 20, int(0.3 * touched_bytes))
-            sparse = table_bytes > int(threshold)
-        return table_bytes, sparse
-
-    def _plan_entity_shard(self, model):
+    def _plan_entity_shard(self, model_id):
         """If this process already belongs to a torch.distributed world of N > 1 ranks and the step will be the table-sharded
-        sparse one (TransE on the sign-count path, SGD, LazyAdam or Adagrad), the rows [lo, hi) of the entity table this rank will own:
-        the model then draws ONLY those rows (Model.embedding_def) instead of the whole table that _setup_shards would cut
-        down -- 102 GB per rank at BASELINE config #5.  None otherwise (the table is created whole, as before)."""
+        sparse one (step_plan.shards_at_creation), the rows [lo, hi) of the entity table this rank will own:
+        the model then draws ONLY those rows (Model.embedding_def) instead of the whole table that train_paths.setup_shards
+        would cut down -- 102 GB per rank at BASELINE config #5.  None otherwise (the table is created whole, as before)."""
         try:
             import torch.distributed as dist
             if not (dist.is_available() and dist.is_initialized()):
@@ -496,17 +450,7 @@ class Config(object):
             W, g = dist.get_world_size(), dist.get_rank()
         except Exception:
             return None
-        if W <= 1 or W > 64 or self.hidden_size % 4:
-            return None
-        probe = model(config=self, define=False)
-        if probe.model_id != _lib.TRANSE or self.opt_method in ("Adam", "adam"):
-            return None
-        n_neg = self.negative_ent + self.negative_rel
-        desc = probe.descriptor()
-        if not (bool(getattr(self, "use_counts", True)) and bool(self.lib.kge_transe_counts_supported(ctypes.byref(desc), n_neg))):
-            return None
-        lazy = self.opt_method in ("LazyAdam", "lazyadam", "lazy_adam", "Adagrad", "adagrad")    # touched rows whatever the table size
-        if not (bool(self._wants_sparse_rows(n_neg)[1]) or lazy):
+        if not step_plan.shards_at_creation(self._plan, model_id, W, self.hidden_size):
             return None
         from .parallel import chunk_size
         chunk = chunk_size(self.entTotal, W)
@@ -525,13 +469,14 @@ class Config(object):
             self.prefetch_sampling = self._prefetch_default()
 
     def _prefetch_default(self):
+        if self.trainModel is None:      # init_distributed before a model is set: nothing is known but the caller's `sparse_rows` wish
+            return bool(self.world_size > 1 or not getattr(self, "sparse_rows", False))
+        p = self._plan
         n_neg = self.negative_ent + self.negative_rel
-        counts_path = bool(getattr(self, "use_counts", False)) and not getattr(self, "sparse_rows", False) and \
-            self.batch_size * (3 + n_neg) >= int(getattr(self, "counts_min_records", 1 << 16)) * self.world_size
-        pair_path = getattr(self, "_desc", None) is not None and \
-            bool(self.lib.kge_pair_path_active(ctypes.byref(self._desc), max(self._n_local, 1) if hasattr(self, "_n_local") else self.batch_size, n_neg))
-        transr = getattr(self, "trainModel", None) is not None and self.trainModel.model_id == _lib.TRANSR
-        dense_one_gpu = not getattr(self, "sparse_rows", False) and not getattr(self, "sparse_inplace", False)
+        counts_path = step_plan.large_counts_step(p, self.batch_size, n_neg, self.counts_min_records, self.world_size)
+        pair_path = bool(self.lib.kge_pair_path_active(ctypes.byref(self._desc), max(self._n_local, 1) if hasattr(self, "_n_local") else self.batch_size, n_neg))
+        transr = self.trainModel.model_id == _lib.TRANSR
+        dense_one_gpu = not p.sparse_rows and not p.sparse_inplace
         return bool(self.world_size > 1 or counts_path or pair_path or transr or dense_one_gpu)
 
     @property
@@ -552,12 +497,12 @@ class Config(object):
             if self._adagrad and not (self.sparse_rows or self.sparse_inplace):
                 raise KgeError("TransR with Adagrad is single-process only: the data-parallel dense step has no flat accumulator "
                                "for its reduce-scatter exchange")
-            if getattr(self, "sparse_inplace", False):
-                pass          # replicated tables, the step's gradient records all-gathered (_records_step): nothing to lay out
+            if self.sparse_inplace:
+                pass          # replicated tables, the step's gradient records all-gathered (train_paths.records_step): nothing to lay out
             elif self.sparse_rows:
-                self._setup_shards()
+                train_paths.setup_shards(self)
             else:
-                self._setup_flat_buffers()
+                train_paths.setup_flat_buffers(self)
             self._dist_ready = self.world_size
 
     def _refresh_pointers(self):
@@ -570,125 +515,7 @@ class Config(object):
             self._adam_v_ptrs = _lib.table_ptrs([t.data_ptr() for t in self._adam_v])
         if self._adagrad:
             self._adagrad_ptrs = _lib.table_ptrs([t.data_ptr() for t in self._adagrad_acc])
-
-    def _setup_flat_buffers(self):
-        """Data-parallel layout of the dense path: all tables in ONE flat fp32 buffer cut into world_size equal chunks,
-        rank g owning chunk g.  Per step the gradient image is reduce-scattered, the optimizer runs on the owned chunk only
-        and the updated chunks are all-gathered (what the reference's ps tasks do for their share of the variables,
-        distribute_training.py:193-196).  TransE: the chunk is a whole number of rows of the [(E+R), D] row space, because
-        the sign-count update needs whole rows; other models: any 4-element boundary."""
-        import torch
-        from .parallel import chunk_size
-        W = self.world_size
-        names = list(self.trainModel.table_names)
-        numels = [t.numel() for t in self._tables]
-        # PIECES: the flat buffer is cut into K consecutive segments, each of them exchanged and updated like a small data-parallel
-        # problem of its own (rank g owns the g-th W-th of every segment), so that the optimizer on piece k and its all-gather run
-        # while piece k+1 is still on the wire.  One piece for FB15k-237-sized tables (the exchange is latency-, not size-bound
-        # there); four from 64 MB of image on.  `dp_pieces` overrides (tests force 2 on a small graph).
-        image_bytes = sum(numels) * 4
-        K = int(getattr(self, "dp_pieces", 0)) or (4 if image_bytes >= (64 << 20) else 1)
-        if self.use_counts:     # ent_embeddings then rel_embeddings, back to back: rows of one [(E+R), D] space
-            D = self.hidden_size
-            chunk_rows = chunk_size(self.entTotal + self.relTotal, W, 4 * K)
-            if chunk_rows * W == self.entTotal + self.relTotal:
-                chunk_rows += 4 * K        # at least one spare row at the end: the loss rides in it (train_step)
-            chunk = chunk_rows * D
-            offs = [0, numels[0]]
-        else:
-            offs, off = [], 0
-            for n in numels:
-                offs.append(off)
-                off += -(-n // 64) * 64
-            chunk = chunk_size(off + 4, W, 4 * K)     # (+ 4: a spare tail slot for the loss)
-        total = chunk * W
-        dev = self._tables[0].device
-        flat_p = torch.zeros(total, dtype=torch.float32, device=dev)
-        flat_g = torch.zeros(total, dtype=torch.float32, device=dev)
-        flat_m = torch.zeros(total, dtype=torch.float32, device=dev) if self._adam else None
-        flat_v = torch.zeros(total, dtype=torch.float32, device=dev) if self._adam else None
-        for i, name in enumerate(names):
-            shape = self._tables[i].shape
-            view = flat_p[offs[i]:offs[i] + numels[i]].view(shape)
-            view.copy_(self._tables[i])
-            self._tables[i] = view
-            self.trainModel.parameter_lists[name] = view
-            setattr(self.trainModel, name, view)
-            self._grads[i] = flat_g[offs[i]:offs[i] + numels[i]].view(shape)
-            if self._adam:
-                for flat, slots in ((flat_m, self._adam_m), (flat_v, self._adam_v)):
-                    v = flat[offs[i]:offs[i] + numels[i]].view(shape)
-                    v.copy_(slots[i])
-                    slots[i] = v
-        self._flat_p, self._flat_g, self._flat_m, self._flat_v = flat_p, flat_g, flat_m, flat_v
-        self._chunk = chunk
-        self._pieces = K
-        seg, own = total // K, chunk // K                     # elements per piece, and per (piece, rank)
-        # piece k: segment [k*seg, (k+1)*seg) of the flat buffers; this rank's share of it; where that share sits in the owned images
-        self._piece_seg = [(k * seg, (k + 1) * seg) for k in range(K)]
-        self._piece_own = [(k * seg + self.rank * own, k * seg + (self.rank + 1) * own) for k in range(K)]
-        self._own_len = own
-        self._grads_own = torch.zeros(chunk, dtype=torch.float32, device=dev)
-        self._loss_tail = total - 1                           # spare element (no table reaches it) of the LAST rank's last piece
-        # the loss scalar LIVES in that slot: the step's kernels write this rank's partial loss there, the exchange replaces it by
-        # the global one (no copy in either direction)
-        self._loss = flat_p[self._loss_tail:]
-        if self.use_counts:
-            rows_total = chunk_rows * W
-            seg_r, own_r = rows_total // K, chunk_rows // K
-            live = self.entTotal + self.relTotal
-            self._counts = torch.zeros((rows_total, self.hidden_size), dtype=torch.int32, device=dev)
-            self._counts_own = torch.zeros((chunk_rows, self.hidden_size), dtype=torch.int32, device=dev)
-            self._piece_rows = [(min(k * seg_r + self.rank * own_r, live), min(k * seg_r + (self.rank + 1) * own_r, live)) for k in range(K)]
-            self._own_rows_len = own_r
-        self._opt_state_synced = True
-        self._refresh_pointers()
-
-    def _setup_shards(self):
-        """Table-sharded sparse mode (config #5 on N GPUs): rank g keeps the entity rows [g*chunk, (g+1)*chunk) only; the
-        relation table stays replicated.  The shard is cut from the table this rank initialised with the common seed, so
-        the union of the shards is the single-process table."""
-        import torch
-        from .parallel import chunk_size
-        if self.hidden_size % 4:
-            raise KgeError("the table-sharded sparse mode needs an embedding width that is a multiple of 4")
-        if self.world_size > 64:
-            raise KgeError("the table-sharded sparse mode supports up to 64 ranks")
-        W, g, E, D = self.world_size, self.rank, self.entTotal, self.hidden_size
-        chunk = chunk_size(E, W)
-        lo, hi = min(g * chunk, E), min((g + 1) * chunk, E)
-        if getattr(self, "_ent_is_shard", False):     # the model drew this rank's rows only (_plan_entity_shard); the moments were made shard-sized
-            plan = self._shard_plan
-            if (plan["world"], plan["rank"], plan["chunk"]) != (W, g, chunk) or self._tables[0].shape[0] != chunk:
-                raise KgeError("the entity table was created as the shard of rank %d of %d, the process group has rank %d of %d"
-                               % (plan["rank"], plan["world"], g, W))
-            self._shard = dict(chunk=chunk, lo=lo, hi=hi)
-            self._refresh_pointers()
-            return
-        full = self._tables[0]
-        shard = torch.zeros((chunk, D), dtype=torch.float32, device=full.device)
-        if hi > lo:
-            shard[:hi - lo].copy_(full[lo:hi])
-        self._tables[0] = shard
-        self.trainModel.parameter_lists["ent_embeddings"] = shard
-        self.trainModel.ent_embeddings = shard
-        del full
-        if self._lazy_adam:     # the moments of the entity rows are sharded with them (owner computes); the relation table's stay replicated
-            for slots in (self._adam_m, self._adam_v):
-                old = slots[0]
-                slots[0] = torch.zeros((chunk, D), dtype=torch.float32, device=shard.device)
-                if hi > lo:
-                    slots[0][:hi - lo].copy_(old[lo:hi])
-                del old
-        if self._adagrad:       # the accumulator of the entity rows likewise (pad rows of the last shard: the initial value, never read)
-            old = self._adagrad_acc[0]
-            self._adagrad_acc[0] = torch.full((chunk, D), float(self.adagrad_initial_accumulator), dtype=torch.float32, device=shard.device)
-            if hi > lo:
-                self._adagrad_acc[0][:hi - lo].copy_(old[lo:hi])
-            del old
-        torch.cuda.empty_cache()
-        self._shard = dict(chunk=chunk, lo=lo, hi=hi)
-        self._refresh_pointers()
+        self._rule = train_paths.RowsRule(self)      # (it holds these pointers)
 
     def _stream(self):
         """The current HIP stream of this Config's device, as the C ABI takes it.  Read through the raw accessor: building a
@@ -715,8 +542,7 @@ class Config(object):
         (kge_emit_pack_words; option emit_pack).  Allocated next to the batch: two slots of n_local << kshift words."""
         import torch
         n_neg = self.negative_ent + self.negative_rel
-        if not (self.use_counts and not self.sparse_rows and not self.sparse_inplace and
-                self.batch_size * (3 + n_neg) >= self.counts_min_records * self.world_size):
+        if not step_plan.large_counts_step(self._plan, self.batch_size, n_neg, self.counts_min_records, self.world_size):
             return 0
         words = int(self.lib.kge_emit_pack_words(self._n_local, self.negative_ent, self.negative_rel, self.hidden_size))
         if words <= 0:
@@ -855,74 +681,6 @@ class Config(object):
                                                       float(self.alpha), st), self.lib)
         self.global_step += 1
 
-    def _dp_exchange(self, image, own_image, apply_piece, counts):
-        """The data-parallel part of a dense step: reduce-scatter of the gradient image, the optimizer on the owned share,
-        all-gather of the updated parameters -- piece by piece (see _setup_flat_buffers), every collective asynchronous, so
-        that piece k is updated and sent while piece k+1 is still being summed.  The loss needs no collective of its own: it
-        is added into a spare tail slot of the image (TransE's int32 count image: as four 16-bit limbs of a 2^-32 fixed-point
-        value, kge_loss_to_limbs), summed by the reduce-scatter like everything else, written by its owner -- the last rank --
-        into the spare tail slot of the parameter buffer, and reaches every rank with the all-gather."""
-        from .parallel import reduce_scatter_sum, all_gather_chunks
-        st, W, K = self._stream(), self.world_size, self._pieces
-        flat_img, flat_own = image.view(-1), own_image.view(-1)
-        per_seg, per_own = flat_img.numel() // K, flat_own.numel() // K
-        ride = flat_img.numel() >= 4 and (not counts or self.hidden_size >= 4)
-        last = self.rank == W - 1
-        nat = self._stream_rccl() if (K == 1 and ride) else None
-        self.comm_fence("nat" if nat is not None else "pg")
-        if nat is not None:
-            # one piece (tables below 64 MB): the two collectives go onto the engine's own stream, in order with its kernels
-            # (parallel.StreamRccl) -- no process-group stream, no event hand-offs
-            if counts and not getattr(self, "_limbs_from_emit", False):
-                _lib.check(self.lib.kge_loss_to_limbs(self._loss.data_ptr(), flat_img[flat_img.numel() - self.hidden_size:].data_ptr(), st), self.lib)
-            elif not counts:
-                flat_img[-1:].copy_(self._loss)
-            nat.reduce_scatter_sum(flat_own, flat_img, st)
-            if last:
-                if counts:
-                    _lib.check(self.lib.kge_limbs_to_loss(flat_own[flat_own.numel() - self.hidden_size:].data_ptr(), self._loss.data_ptr(), st), self.lib)
-                else:
-                    self._loss.copy_(flat_own[-1:])
-            apply_piece(0)
-            (slo, shi), (lo, hi) = self._piece_seg[0], self._piece_own[0]
-            nat.all_gather_chunks(self._flat_p[slo:shi], self._flat_p[lo:hi], st)
-            image.zero_()
-            if self._adam:
-                self._adam_advance()
-            self.global_step += 1
-            return
-        if ride:
-            if counts and not getattr(self, "_limbs_from_emit", False):     # (a sampled batch: the emit kernel has written the limbs itself)
-                _lib.check(self.lib.kge_loss_to_limbs(self._loss.data_ptr(), flat_img[flat_img.numel() - self.hidden_size:].data_ptr(), st), self.lib)
-            else:
-                flat_img[-1:].copy_(self._loss)
-        rs = [reduce_scatter_sum(flat_own[k * per_own:(k + 1) * per_own], flat_img[k * per_seg:(k + 1) * per_seg], self._pg, async_op=True)
-              for k in range(K)]
-        if not ride:
-            from .parallel import allreduce_sum
-            allreduce_sum([self._loss], self._pg)
-        ag = []
-        for k in range(K):
-            if rs[k] is not None:
-                rs[k].wait()
-            if ride and last and k == K - 1:      # the summed loss -> the parameter buffer's tail slot (before the all-gather of this piece)
-                if counts:
-                    _lib.check(self.lib.kge_limbs_to_loss(flat_own[flat_own.numel() - self.hidden_size:].data_ptr(),
-                                                          self._flat_p[self._loss_tail:].data_ptr(), st), self.lib)
-                else:
-                    self._loss.copy_(flat_own[-1:])
-            apply_piece(k)
-            (slo, shi), (lo, hi) = self._piece_seg[k], self._piece_own[k]
-            ag.append(all_gather_chunks(self._flat_p[slo:shi], self._flat_p[lo:hi], self._pg, async_op=True))
-        image.zero_()
-        if self._adam:
-            self._adam_advance()
-        self.global_step += 1
-        for w in ag:
-            if w is not None:
-                w.wait()
-        # (ride: self._loss IS the tail slot of the parameter buffer -- the all-gather has just delivered the global loss into it)
-
     def comm_fence(self, kind):
         """Two RCCL communicators live in a data-parallel process: torch's process group ("pg": the sharded step, optimizer-state
         gathers, evaluation reductions, the caller's own barriers) and the engine's own (parallel.StreamRccl, "nat": the dense
@@ -940,47 +698,7 @@ class Config(object):
         self._last_comm = kind
 
     def _stream_rccl(self):
-        """The communicator for collectives on the engine's stream (parallel.StreamRccl): "nccl" backend, `stream_rccl` not switched
-        off (KGE_STREAM_RCCL=0 switches it off from the environment).  Created on first use -- collectively: every rank reaches the
-        first data-parallel step together -- and PROBED before it is trusted: a reduce-scatter and an all-gather of known values
-        through it must give the known sums on every rank, else (or on any error) all ranks fall back to the process group."""
-        if getattr(self, "_nat_rccl", None) is None:
-            import torch.distributed as dist
-            want = getattr(self, "stream_rccl", os.environ.get("KGE_STREAM_RCCL", "1") != "0") and dist.is_initialized() and \
-                dist.get_backend(self._pg) == "nccl"
-            nat = False
-            if want:
-                import sys
-                import torch
-                from .parallel import StreamRccl
-                self.comm_fence("pg")
-                good = 0
-                try:
-                    nat = StreamRccl(self._pg)
-                    torch.cuda.synchronize(self.device)
-                    W, g, st = nat.world, nat.rank, self._stream()
-                    src = torch.arange(4 * W, dtype=torch.int32, device=self.device) + g          # rank g contributes i + g
-                    own = torch.empty(4, dtype=torch.int32, device=self.device)
-                    nat.reduce_scatter_sum(own, src, st)
-                    full = torch.empty(4 * W, dtype=torch.int32, device=self.device)
-                    full[4 * g:4 * g + 4] = own
-                    nat.all_gather_chunks(full, full[4 * g:4 * g + 4], st)
-                    torch.cuda.synchronize(self.device)
-                    want_full = W * torch.arange(4 * W, dtype=torch.int32) + W * (W - 1) // 2      # sum_g (i + g)
-                    good = int(torch.equal(full.cpu(), want_full))
-                    if not good:
-                        print("StreamRccl probe gave wrong sums: collectives stay on the process group's stream", file=sys.stderr)
-                except Exception as exc:       # still RCCL either way: the process-group path is the documented alternative
-                    print("StreamRccl unavailable (%s): collectives stay on the process group's stream" % exc, file=sys.stderr)
-                # every rank must take the same path (a rank on the other communicator would wait for ever): agree on the minimum
-                ok = torch.tensor([good], dtype=torch.int32, device=self.device)
-                dist.all_reduce(ok, op=dist.ReduceOp.MIN, group=self._pg)
-                if int(ok.item()) == 0:
-                    if nat:
-                        nat.close()
-                    nat = False
-            self._nat_rccl = nat
-        return self._nat_rccl or None
+        return train_paths.stream_rccl(self)
 
     def sync_optimizer_state(self):
         """Data-parallel Adam keeps m and v current on their owner only; gather them before they are read as whole tables
@@ -1018,93 +736,25 @@ class Config(object):
             dev = torch.from_numpy(host).to(self.device)
             n_pos = host.shape[1] // (1 + n_neg)
             stride = n_pos
-        denom = self.batch_size * n_neg if batch_h is None else n_pos * n_neg
-        # small steps are launch-bound: the single fused atomic kernel beats the multi-stage count pipeline
-        # (same decision on every rank: it depends on the global batch only)
-        big = (self.batch_size if batch_h is None else n_pos) * (3 + n_neg) >= self.counts_min_records * self.world_size
-        if self.sparse_inplace and self._dp:
-            self._records_step(dev, n_pos, stride, denom)
-            if batch_h is None and self.prefetch_sampling:
-                self._prefetch_next_batch()
-        elif self.sparse_inplace:
-            if self._lazy_adam:
-                _lib.check(self.lib.kge_forward_backward_adam_rows(
-                    ctypes.byref(self._desc), self._tab_ptrs, self._adam_m_ptrs, self._adam_v_ptrs, dev[0].data_ptr(), dev[1].data_ptr(),
-                    dev[2].data_ptr(), n_pos, n_neg, stride, denom, float(self._adam_lr_t()), self.adam_beta1, self.adam_beta2,
-                    self.adam_epsilon, self._loss.data_ptr(), self._stream()), self.lib)
-                self._adam_advance()
-            elif self._adagrad:
-                _lib.check(self.lib.kge_forward_backward_adagrad_rows(
-                    ctypes.byref(self._desc), self._tab_ptrs, self._adagrad_ptrs, dev[0].data_ptr(), dev[1].data_ptr(), dev[2].data_ptr(),
-                    n_pos, n_neg, stride, denom, float(self.alpha), self._loss.data_ptr(), self._stream()), self.lib)
-            else:
-                _lib.check(self.lib.kge_forward_backward_sgd_rows(
-                    ctypes.byref(self._desc), self._tab_ptrs, dev[0].data_ptr(), dev[1].data_ptr(), dev[2].data_ptr(), n_pos, n_neg,
-                    stride, denom, float(self.alpha), self._loss.data_ptr(), self._stream()), self.lib)
-            if batch_h is not None:       # a hand-fed batch may hold negatives the in-place update cannot take (the sampler draws none)
-                skipped = ctypes.c_int32(0)
-                _lib.check(self.lib.kge_sgd_rows_skipped(ctypes.byref(skipped)), self.lib)
-                if skipped.value:
-                    raise KgeError("sparse_rows: %d negatives are not single-slot corruptions of their positive and were left out "
-                                   "of this step; train such batches with sparse_rows=False" % skipped.value)
-            self.global_step += 1
-            if batch_h is None and self.prefetch_sampling:
-                self._prefetch_next_batch()
-        elif self.sparse_rows:
-            if self._dp:
-                self._sharded_step(dev, n_pos, stride, denom)
-            else:
-                self._sparse_step(dev, n_pos, stride, denom, check_shape=batch_h is not None)
-            if batch_h is None and self.prefetch_sampling:
-                self._prefetch_next_batch()
-        elif self.use_counts and big:
-            ahead = batch_h is None and self.prefetch_sampling
-            if ahead:
-                self._attach_next_batch()              # rides in the scatter launch enqueued by forward_counts
-            # data-parallel: the emit kernel of a sampled batch also writes the loss as limbs into the count image's spare tail slot
-            self._limbs_from_emit = bool(self._dp and batch_h is None and self.hidden_size >= 4)
-            target = self._counts.view(-1)[self._counts.numel() - self.hidden_size:].data_ptr() if self._limbs_from_emit else 0
-            if target != getattr(self, "_limbs_target", 0):
-                self.lib.kge_loss_limbs_target(ctypes.c_void_p(target) if target else None)
-                self._limbs_target = target
-            # one process: forward, segmented sum and optimizer in ONE call (kge_transe_train_step_counts) -- the rows whose records one
-            # team can hold are summed in registers and updated there, without the count image; `fused_counts = False` keeps the
-            # two-call form (the data-parallel step needs the image: it is what the ranks exchange)
-            one_call = not self._dp and bool(getattr(self, "fused_counts", True))
-            try:
-                if one_call:
-                    self.step_counts(dev, n_pos, stride, denom, sampler_shaped=batch_h is None, pack=pack)
-                else:
-                    self.forward_counts(dev, n_pos, stride, denom, sampler_shaped=batch_h is None, pack=pack)
-            finally:
-                if ahead:                              # launched on its own if the step's path had no scatter kernel -- and
-                    self._flush_next_batch()           # also when the forward call failed: an armed sampler never outlives its buffers
-            if one_call:
-                pass
+        sampled = batch_h is None
+        denom = self.batch_size * n_neg if sampled else n_pos * n_neg
+        ahead = sampled and self.prefetch_sampling      # draw the next batch during this step
+        if self.sparse_inplace or self.sparse_rows:
+            if self.sparse_inplace and self._dp:
+                train_paths.records_step(self, dev, n_pos, stride, denom)
+            elif self.sparse_inplace:
+                train_paths.inplace_step(self, dev, n_pos, stride, denom, hand_fed=not sampled)
             elif self._dp:
-                # int32 SUM is exact: rank g receives the summed counts of ITS rows, updates them, and the updated rows go round
-                self._dp_exchange(self._counts, self._counts_own, lambda k: self.apply_counts(denom, own=True, piece=k), counts=True)
-                self.tables_changed()
+                train_paths.sharded_step(self, dev, n_pos, stride, denom)
             else:
-                self.apply_counts(denom)
+                train_paths.sparse_step(self, dev, n_pos, stride, denom, check_shape=not sampled)
+            if ahead:
+                self._prefetch_next_batch()
+        elif step_plan.large_counts_step(self._plan, self.batch_size if sampled else n_pos, n_neg, self.counts_min_records, self.world_size):
+            # (small steps are launch-bound: there the single fused atomic kernel of the dense step beats the multi-stage count pipeline)
+            train_paths.counts_step(self, dev, n_pos, stride, denom, sampled, pack, ahead)
         else:
-            # one GPU: the next batch's sampler rides in a launch of the step that leaves most of the chip idle -- TransR's relation
-            # scatter, the record paths' bucket scatter, the atomic path's forward/backward kernel itself (a few hundred
-            # latency-bound workgroups at the reference's batch sizes); a path without such a launch runs it on its own afterwards
-            ride = batch_h is None and self.prefetch_sampling and not self._dp
-            if ride:
-                self._attach_next_batch()
-            try:
-                self.forward_backward(dev, n_pos, stride, denom, sampler_shaped=batch_h is None)
-            finally:
-                if ride:
-                    self._flush_next_batch()
-            if batch_h is None and self.prefetch_sampling and not ride:
-                self._prefetch_next_batch(behind_emit=bool(self.lib.kge_pair_path_active(ctypes.byref(self._desc), n_pos, n_neg)))
-            if self._dp:
-                self._dp_exchange(self._flat_g, self._grads_own, lambda k: self.apply_gradients(own=True, piece=k), counts=False)
-            else:
-                self.apply_gradients()
+            train_paths.dense_step(self, dev, n_pos, stride, denom, sampled, ahead)
         self.trainModel.loss = self._loss
         return float(self._loss.item()) if sync else self._loss
 
@@ -1119,8 +769,8 @@ class Config(object):
         if self.trainModel.model_id not in (_lib.TRANSE, _lib.TRANSH, _lib.TRANSD):
             return False
         n_neg = self.negative_ent + self.negative_rel
-        if self.use_counts and self.batch_size * (3 + n_neg) >= self.counts_min_records:
-            return False       # TransE at a large step: the exact integer-count pipeline is the faster path
+        if step_plan.large_counts_step(self._plan, self.batch_size, n_neg, self.counts_min_records, 1):
+            return False      # TransE at a large step: the exact integer-count pipeline is the faster path
         slots = {_lib.TRANSE: 3 + n_neg, _lib.TRANSH: 4 + n_neg, _lib.TRANSD: 6 + 2 * n_neg}[self.trainModel.model_id]
         return self.batch_size * slots < int(getattr(self, "persistent_max_rows", 1 << 16))
 
@@ -1181,284 +831,12 @@ class Config(object):
         self.trainModel.loss = self._loss
         return out
 
-    def _records_step(self, dev_batch, n_pos, stride, denom):
-        """Row-wise SGD (or lazy Adam, or Adagrad with its replicated accumulators) in place across ranks (TransH / TransD, or TransE off the sign-count path, with sparse_rows):
-        the tables -- and with LazyAdam their moments -- are replicated; every rank turns ITS slice of the batch into float gradient records, the records (rows + destination
-        keys) are all-gathered -- the sparse touched-row exchange: only rows a step touches travel -- and every rank adds -lr * the
-        per-row sums of ALL records to its replica (LazyAdam: puts them through the Adam rule on the rows that have a record).  Every rank reduces the same records in the same order, so the replicas stay
-        bit-identical; against the single-process step the per-row sums differ in fp32 order only.  Replaces the scatter_sub
-        updates the reference's workers send to its parameter servers (distribute_training.py:99-101,193-196)."""
-        import torch
-        from .parallel import all_gather_chunks, allreduce_sum, max_slice_positions
-        n_neg = self.negative_ent + self.negative_rel
-        W, D = self.world_size, self.hidden_size
-        slots = {_lib.TRANSE: 3 + n_neg, _lib.TRANSH: 4 + n_neg, _lib.TRANSD: 6 + 2 * n_neg}[self.trainModel.model_id]
-        b = getattr(self, "_rec_buf", None)
-        if b is None or b["slots"] != slots:
-            per = max_slice_positions(self.lib, self.batch_size, W, self.workThreads) * slots     # records per rank's slice
-            b = dict(slots=slots, per=per,
-                     rec=torch.zeros((W * per, D), dtype=torch.float32, device=self.device),
-                     dst=torch.full((W * per,), -1, dtype=torch.int32, device=self.device))
-            self._rec_buf = b
-        per, off = b["per"], self.rank * b["per"]
-        _lib.check(self.lib.kge_forward_backward_records(
-            ctypes.byref(self._desc), self._tab_ptrs, dev_batch[0].data_ptr(), dev_batch[1].data_ptr(), dev_batch[2].data_ptr(),
-            n_pos, n_neg, stride, denom, self.batch_size, b["rec"].data_ptr(), b["dst"].data_ptr(), off, per,
-            self._loss.data_ptr(), self._stream()), self.lib)
-        if W > 1:
-            self.comm_fence("pg")
-            all_gather_chunks(b["rec"].view(-1), b["rec"][off:off + per].view(-1), self._pg)
-            all_gather_chunks(b["dst"], b["dst"][off:off + per], self._pg)
-            allreduce_sum([self._loss], self._pg)
-        if self._lazy_adam:      # m and v are replicated like the tables: the same lr_t and the same records on every rank
-            _lib.check(self.lib.kge_float_records_apply_adam(
-                ctypes.byref(self._desc), self._tab_ptrs, self._adam_m_ptrs, self._adam_v_ptrs, b["rec"].data_ptr(), b["dst"].data_ptr(),
-                W * per, self.batch_size, n_neg, float(self._adam_lr_t()), self.adam_beta1, self.adam_beta2, self.adam_epsilon,
-                self._stream()), self.lib)
-            self._adam_advance()
-        elif self._adagrad:      # the accumulators are replicated like the tables: the same records in the same order on every rank
-            _lib.check(self.lib.kge_float_records_apply_adagrad(
-                ctypes.byref(self._desc), self._tab_ptrs, self._adagrad_ptrs, b["rec"].data_ptr(), b["dst"].data_ptr(), W * per,
-                self.batch_size, n_neg, float(self.alpha), self._stream()), self.lib)
-        else:
-            _lib.check(self.lib.kge_float_records_apply(
-                ctypes.byref(self._desc), self._tab_ptrs, b["rec"].data_ptr(), b["dst"].data_ptr(), W * per, self.batch_size, n_neg,
-                float(self.alpha), self._stream()), self.lib)
-        self.global_step += 1
-
-    def _sparse_step(self, dev_batch, n_pos, stride, denom, check_shape=False):
-        """Sparse-row TransE step on ONE GPU: emit int8 records -> sort by destination row -> compact per-row counts ->
-        SGD on the touched rows.  Bitwise the same update as the dense count image (integer sums).  N GPUs:
-        _sharded_step."""
-        import torch
-        n_neg = self.negative_ent + self.negative_rel
-        D = self.hidden_size
-        m_local = stride * (3 + n_neg)
-        dw = int(self.lib.kge_transe_record_dwords(ctypes.byref(self._desc)))
-        buf = self._sparse_buf
-        if buf is None or buf.get("m_local") != m_local:
-            dev = self.device
-            buf = dict(m_local=m_local,
-                       rec=torch.empty((m_local, dw), dtype=torch.int32, device=dev),
-                       dst=torch.empty(m_local, dtype=torch.int32, device=dev),
-                       rows=torch.empty(m_local, dtype=torch.int32, device=dev),
-                       row_counts=torch.empty((m_local, D), dtype=torch.int32, device=dev),
-                       n_rows=torch.zeros(1, dtype=torch.int32, device=dev))
-            self._sparse_buf = buf
-        st = self._stream()
-        buf["dst"].fill_(-1)
-        _lib.check(self.lib.kge_transe_emit_records(
-            ctypes.byref(self._desc), self._tables[0].data_ptr(), self._tables[1].data_ptr(),
-            dev_batch[0].data_ptr(), dev_batch[1].data_ptr(), dev_batch[2].data_ptr(), n_pos, n_neg,
-            dev_batch.shape[1] // (1 + n_neg), denom, buf["rec"].data_ptr(), buf["dst"].data_ptr(), None, None,
-            self._loss.data_ptr(), st), self.lib)
-        if check_shape:
-            nd = ctypes.c_int32(0)
-            _lib.check(self.lib.kge_transe_deferred_groups(ctypes.byref(nd)), self.lib)
-            if nd.value:
-                raise KgeError("sparse_rows: %d groups have negatives that are not single-slot corruptions of their "
-                               "positive; train such batches with sparse_rows=False" % nd.value)
-        rec, dst = buf["rec"], buf["dst"]
-        if self._lazy_adam:
-            _lib.check(self.lib.kge_transe_reduce_records(
-                ctypes.byref(self._desc), rec.data_ptr(), dst.data_ptr(), dst.numel(), buf["rows"].data_ptr(),
-                buf["row_counts"].data_ptr(), buf["n_rows"].data_ptr(), st), self.lib)
-            _lib.check(self.lib.kge_transe_apply_rows_adam_lazy(
-                ctypes.byref(self._desc), self._tables[0].data_ptr(), self._tables[1].data_ptr(), self._adam_m[0].data_ptr(),
-                self._adam_m[1].data_ptr(), self._adam_v[0].data_ptr(), self._adam_v[1].data_ptr(), buf["rows"].data_ptr(),
-                buf["row_counts"].data_ptr(), buf["n_rows"].data_ptr(), dst.numel(), denom, float(self._adam_lr_t()),
-                self.adam_beta1, self.adam_beta2, self.adam_epsilon, st), self.lib)
-            self._adam_advance()
-        elif self._adagrad:      # (not the fused reduce-apply: the rule is not linear in the gradient, it needs a row's complete sum)
-            _lib.check(self.lib.kge_transe_reduce_records(
-                ctypes.byref(self._desc), rec.data_ptr(), dst.data_ptr(), dst.numel(), buf["rows"].data_ptr(),
-                buf["row_counts"].data_ptr(), buf["n_rows"].data_ptr(), st), self.lib)
-            _lib.check(self.lib.kge_transe_apply_rows_adagrad(
-                ctypes.byref(self._desc), self._tables[0].data_ptr(), self._tables[1].data_ptr(), self._adagrad_acc[0].data_ptr(),
-                self._adagrad_acc[1].data_ptr(), buf["rows"].data_ptr(), buf["row_counts"].data_ptr(), buf["n_rows"].data_ptr(),
-                dst.numel(), denom, float(self.alpha), st), self.lib)
-        elif getattr(self, "sparse_fused", True) and D % 4 == 0:
-            # reduce + apply in one pass: only chunk-boundary rows go through the compact count image
-            _lib.check(self.lib.kge_transe_reduce_apply_records_sgd(
-                ctypes.byref(self._desc), rec.data_ptr(), dst.data_ptr(), dst.numel(), self._tables[0].data_ptr(),
-                self._tables[1].data_ptr(), buf["rows"].data_ptr(), buf["row_counts"].data_ptr(), buf["n_rows"].data_ptr(),
-                denom, float(self.alpha), st), self.lib)
-        else:
-            _lib.check(self.lib.kge_transe_reduce_records(
-                ctypes.byref(self._desc), rec.data_ptr(), dst.data_ptr(), dst.numel(), buf["rows"].data_ptr(),
-                buf["row_counts"].data_ptr(), buf["n_rows"].data_ptr(), st), self.lib)
-            _lib.check(self.lib.kge_transe_apply_rows_sgd(
-                ctypes.byref(self._desc), self._tables[0].data_ptr(), self._tables[1].data_ptr(), buf["rows"].data_ptr(),
-                buf["row_counts"].data_ptr(), buf["n_rows"].data_ptr(), dst.numel(), denom, float(self.alpha), st),
-                self.lib)
-        self.global_step += 1
-
     def _desc_with(self, **fields):
         """A copy of the model descriptor with some fields replaced (row spaces of a cache / a shard)."""
         d = self._desc
         vals = {name: getattr(d, name) for name, _ in d._fields_}
         vals.update(fields)
         return _lib.ModelDesc(*[vals[name] for name, _ in d._fields_])
-
-    def _shard_buffers(self, M, n_recv_rows, n_recv_rec):
-        """Workspace of the sharded step, grown geometrically (receive sizes vary from step to step)."""
-        import torch
-        D, W, dev = self.hidden_size, self.world_size, self.device
-        dw = int(self.lib.kge_transe_record_dwords(ctypes.byref(self._desc)))
-        b = self._sparse_buf if isinstance(self._sparse_buf, dict) and self._sparse_buf.get("sharded") else dict(sharded=True, M=0, rr=0, rc=0)
-        i32 = torch.int32
-        if M > b["M"] or "req" not in b:
-            cap = max(int(M * 1.25), 64)
-            b.update(M=cap, req=torch.empty(cap, dtype=i32, device=dev), slot_of=torch.empty(cap, dtype=i32, device=dev),
-                     send_ids=torch.empty(cap, dtype=i32, device=dev), cache=torch.empty((cap, D), dtype=torch.float32, device=dev),
-                     rec=torch.empty((cap, dw), dtype=i32, device=dev), dst=torch.empty(cap, dtype=i32, device=dev),
-                     ids2=torch.empty(cap, dtype=i32, device=dev), slot_of2=torch.empty(cap, dtype=i32, device=dev),
-                     send_rows2=torch.empty(cap, dtype=i32, device=dev), send_rec=torch.empty((cap, dw), dtype=i32, device=dev),
-                     counts=torch.zeros(W, dtype=i32, device=dev), cursor=torch.zeros(W, dtype=i32, device=dev),
-                     rel_counts=torch.zeros((self.relTotal, D), dtype=i32, device=dev),
-                     rel_rows=torch.arange(self.entTotal, self.entTotal + self.relTotal, dtype=i32, device=dev),
-                     n_rel=torch.full((1,), self.relTotal, dtype=i32, device=dev), n_rows=torch.zeros(1, dtype=i32, device=dev), dw=dw)
-        if n_recv_rows > b["rr"] or "recv_ids" not in b:       # (also for an owner that is never asked for a row: an empty shard)
-            cap = max(int(n_recv_rows * 1.25), 64)
-            b.update(rr=cap, recv_ids=torch.empty(cap, dtype=i32, device=dev), rows_out=torch.empty((cap, D), dtype=torch.float32, device=dev))
-        if n_recv_rec > b["rc"] or "recv_rec" not in b:
-            cap = max(int(n_recv_rec * 1.25), 64)
-            b.update(rc=cap, recv_rows2=torch.empty(cap, dtype=i32, device=dev), recv_rec=torch.empty((cap, dw), dtype=i32, device=dev),
-                     rows=torch.empty(cap, dtype=i32, device=dev), row_counts=torch.empty((cap, D), dtype=i32, device=dev))
-        self._sparse_buf = b
-        return b
-
-    def _sharded_step(self, dev_batch, n_pos, stride, denom):
-        """Sparse-row TransE step on a SHARDED entity table (world_size > 1): every stage is O(local batch).
-        request ids -> all-to-all -> owners gather rows -> all-to-all -> emit int8 records against the fetched rows ->
-        all-to-all (row id, record) -> owners sort / sum / apply their rows; relation counts all-reduced (csrc/shard.hip).
-        Integer sums and one per-row update formula: the union of the shards equals the single-process table bit for bit."""
-        import torch
-        from . import parallel as par
-        L, st, W, D, pg = self.lib, self._stream(), self.world_size, self.hidden_size, self._pg
-        self.comm_fence("pg")
-        n_neg = self.negative_ent + self.negative_rel
-        sh = self._shard
-        chunk = sh["chunk"]
-        M = n_pos * (3 + n_neg)
-        b = self._shard_buffers(M, 0, 0)
-        dw = b["dw"]
-        h, t, r = dev_batch[0], dev_batch[1], dev_batch[2]
-        bstride = dev_batch.shape[1] // (1 + n_neg)
-        # 1. which entity rows does this slice touch, and who owns them
-        _lib.check(L.kge_shard_requests(h.data_ptr(), t.data_ptr(), r.data_ptr(), n_pos, n_neg, bstride, b["req"].data_ptr(), st), L)
-        _lib.check(L.kge_shard_count(b["req"].data_ptr(), M, chunk, W, b["counts"].data_ptr(), st), L)
-        send, recv, gmax = par.exchange_counts_max(b["counts"], pg)
-        h_counts = (ctypes.c_int64 * W)(*send)
-        _lib.check(L.kge_shard_scatter(b["req"].data_ptr(), M, chunk, W, h_counts, b["cursor"].data_ptr(), b["send_ids"].data_ptr(),
-                                       b["slot_of"].data_ptr(), st), L)
-        n_send, n_recv = sum(send), sum(recv)
-        b = self._shard_buffers(M, n_recv, 0)
-        # 2. ids out, rows back
-        par.all_to_all_rows(b["recv_ids"], b["send_ids"], recv, send, pg, max_rows=gmax)
-        _lib.check(L.kge_shard_gather_rows(self._tables[0].data_ptr(), b["recv_ids"].data_ptr(), n_recv, sh["lo"], chunk, D,
-                                           b["rows_out"].data_ptr(), st), L)
-        par.all_to_all_rows(b["cache"], b["rows_out"], send, recv, pg, max_rows=gmax)
-        # 3. the unchanged emit kernel over the fetched rows: the batch in terms of cache slots
-        if self._dev_batch2 is None or self._dev_batch2.shape != dev_batch.shape:
-            self._dev_batch2 = torch.zeros_like(dev_batch)
-        h2, t2 = self._dev_batch2[0], self._dev_batch2[1]
-        _lib.check(L.kge_shard_remap_batch(h.data_ptr(), t.data_ptr(), n_pos, n_neg, bstride, b["slot_of"].data_ptr(), h2.data_ptr(),
-                                           t2.data_ptr(), st), L)
-        desc2 = self._desc_with(ent_total=max(n_send, 1))
-        _lib.check(L.kge_transe_emit_records(ctypes.byref(desc2), b["cache"].data_ptr(), self._tables[1].data_ptr(), h2.data_ptr(),
-                                             t2.data_ptr(), r.data_ptr(), n_pos, n_neg, bstride, denom, b["rec"].data_ptr(),
-                                             b["dst"].data_ptr(), None, None, self._loss.data_ptr(), st), L)
-        # 4. relation rows: dense int32 image, all-reduced (the relation table is replicated)
-        b["rel_counts"].zero_()
-        if self._lazy_adam:
-            # which relations have a record on THIS rank -- the relation-slot destinations of its active groups and, with relation
-            # negatives, the destinations of its active relation-corrupted negatives (slots 3 + k; a relation may take records from
-            # those alone, and one process moves its row then) -- read before the reduce below rewrites the destination keys in place;
-            # summed over the ranks with the counts.  Entry R collects everything else (no record, or a fetched-row slot).
-            if "rel_live" not in b:
-                b["rel_live"] = torch.zeros(self.relTotal + 1, dtype=torch.int32, device=self.device)
-            b["rel_live"].zero_()
-            if n_pos > 0:
-                d = b["dst"][2 * n_pos:(M if self.negative_rel > 0 else 3 * n_pos)]
-                idx = torch.where(d >= int(desc2.ent_total), d - int(desc2.ent_total), torch.full_like(d, self.relTotal))
-                b["rel_live"].index_fill_(0, idx.long(), 1)
-        if D % 4 == 0 and self.negative_rel == 0 and n_pos > 0:
-            # the relation-side records are slot 2 of every group -- records [2 n_pos, 3 n_pos): ordered by relation, summed by
-            # segments into <= R compact rows, scattered into the image (per-element atomics took 0.4 ms of a 3 ms step)
-            cap = min(n_pos, self.relTotal) + 8
-            if b.get("relc_cap", 0) < cap:
-                b.update(relc_cap=cap, relc_rows=torch.empty(cap, dtype=torch.int32, device=self.device),
-                         relc_counts=torch.empty((cap, D), dtype=torch.int32, device=self.device))
-            _lib.check(L.kge_transe_reduce_records(ctypes.byref(desc2), b["rec"][2 * n_pos:3 * n_pos].data_ptr(),
-                                                   b["dst"][2 * n_pos:3 * n_pos].data_ptr(), n_pos, b["relc_rows"].data_ptr(),
-                                                   b["relc_counts"].data_ptr(), b["n_rows"].data_ptr(), st), L)
-            _lib.check(L.kge_shard_scatter_count_rows(b["relc_rows"].data_ptr(), b["relc_counts"].data_ptr(), b["n_rows"].data_ptr(),
-                                                      cap, desc2.ent_total, self.relTotal, D, b["rel_counts"].data_ptr(), st), L)
-        else:
-            _lib.check(L.kge_shard_relation_counts(b["rec"].data_ptr(), b["dst"].data_ptr(), M, desc2.ent_total, self.relTotal, dw, D,
-                                                   b["rel_counts"].data_ptr(), st), L)
-        if self._lazy_adam:
-            par.allreduce_sum([b["rel_counts"], self._loss, b["rel_live"]], pg)
-        else:
-            par.allreduce_sum([b["rel_counts"], self._loss], pg)
-        # 5. entity records to their owners
-        _lib.check(L.kge_shard_record_ids(b["dst"].data_ptr(), M, n_send, b["send_ids"].data_ptr(), b["ids2"].data_ptr(), st), L)
-        _lib.check(L.kge_shard_count(b["ids2"].data_ptr(), M, chunk, W, b["counts"].data_ptr(), st), L)
-        send2, recv2, gmax2 = par.exchange_counts_max(b["counts"], pg)
-        h_counts2 = (ctypes.c_int64 * W)(*send2)
-        _lib.check(L.kge_shard_scatter(b["ids2"].data_ptr(), M, chunk, W, h_counts2, b["cursor"].data_ptr(), b["send_rows2"].data_ptr(),
-                                       b["slot_of2"].data_ptr(), st), L)
-        _lib.check(L.kge_shard_pack_records(b["rec"].data_ptr(), b["slot_of2"].data_ptr(), M, dw, b["send_rec"].data_ptr(), st), L)
-        n_recv2 = sum(recv2)
-        b = self._shard_buffers(M, n_recv, n_recv2)
-        par.all_to_all_rows(b["recv_rows2"], b["send_rows2"], recv2, send2, pg, max_rows=gmax2)
-        par.all_to_all_rows(b["recv_rec"], b["send_rec"], recv2, send2, pg, max_rows=gmax2)
-        # 6. owner: sort by row, segmented sum, SGD (or lazy Adam: the shard's own moment rows) on the touched rows of the shard
-        if n_recv2 > 0:
-            b["recv_rows2"][:n_recv2].sub_(sh["lo"])
-            desc3 = self._desc_with(ent_total=chunk, rel_total=0)
-            if self._lazy_adam:
-                _lib.check(L.kge_transe_reduce_records(ctypes.byref(desc3), b["recv_rec"].data_ptr(), b["recv_rows2"].data_ptr(), n_recv2,
-                                                       b["rows"].data_ptr(), b["row_counts"].data_ptr(), b["n_rows"].data_ptr(), st), L)
-                _lib.check(L.kge_transe_apply_rows_adam_lazy(
-                    ctypes.byref(desc3), self._tables[0].data_ptr(), self._tables[1].data_ptr(), self._adam_m[0].data_ptr(),
-                    self._adam_m[1].data_ptr(), self._adam_v[0].data_ptr(), self._adam_v[1].data_ptr(), b["rows"].data_ptr(),
-                    b["row_counts"].data_ptr(), b["n_rows"].data_ptr(), n_recv2, denom, float(self._adam_lr_t()), self.adam_beta1,
-                    self.adam_beta2, self.adam_epsilon, st), L)
-            elif self._adagrad:
-                _lib.check(L.kge_transe_reduce_records(ctypes.byref(desc3), b["recv_rec"].data_ptr(), b["recv_rows2"].data_ptr(), n_recv2,
-                                                       b["rows"].data_ptr(), b["row_counts"].data_ptr(), b["n_rows"].data_ptr(), st), L)
-                _lib.check(L.kge_transe_apply_rows_adagrad(
-                    ctypes.byref(desc3), self._tables[0].data_ptr(), self._tables[1].data_ptr(), self._adagrad_acc[0].data_ptr(),
-                    self._adagrad_acc[1].data_ptr(), b["rows"].data_ptr(), b["row_counts"].data_ptr(), b["n_rows"].data_ptr(), n_recv2,
-                    denom, float(self.alpha), st), L)
-            else:
-                _lib.check(L.kge_transe_reduce_apply_records_sgd(
-                    ctypes.byref(desc3), b["recv_rec"].data_ptr(), b["recv_rows2"].data_ptr(), n_recv2, self._tables[0].data_ptr(),
-                    self._tables[1].data_ptr(), b["rows"].data_ptr(), b["row_counts"].data_ptr(), b["n_rows"].data_ptr(), denom,
-                    float(self.alpha), st), L)
-        # 7. every rank applies the identical relation update from the all-reduced counts
-        if self._lazy_adam:
-            # (only the relations SOME rank had a record for: a record-less row keeps its value and moments under the lazy rule)
-            _lib.check(L.kge_transe_lazy_row_live(b["rel_live"].data_ptr()), L)
-            _lib.check(L.kge_transe_apply_rows_adam_lazy(
-                ctypes.byref(self._desc), self._tables[0].data_ptr(), self._tables[1].data_ptr(), self._adam_m[0].data_ptr(),
-                self._adam_m[1].data_ptr(), self._adam_v[0].data_ptr(), self._adam_v[1].data_ptr(), b["rel_rows"].data_ptr(),
-                b["rel_counts"].data_ptr(), b["n_rel"].data_ptr(), self.relTotal, denom, float(self._adam_lr_t()), self.adam_beta1,
-                self.adam_beta2, self.adam_epsilon, st), L)
-            self._adam_advance()
-        elif self._adagrad:
-            # (no live mask: a relation whose all-reduced counts are zero has zero gradient, and the rule leaves it alone)
-            _lib.check(L.kge_transe_apply_rows_adagrad(
-                ctypes.byref(self._desc), self._tables[0].data_ptr(), self._tables[1].data_ptr(), self._adagrad_acc[0].data_ptr(),
-                self._adagrad_acc[1].data_ptr(), b["rel_rows"].data_ptr(), b["rel_counts"].data_ptr(), b["n_rel"].data_ptr(),
-                self.relTotal, denom, float(self.alpha), st), L)
-        else:
-            _lib.check(L.kge_transe_apply_rows_sgd(ctypes.byref(self._desc), self._tables[0].data_ptr(), self._tables[1].data_ptr(),
-                                                   b["rel_rows"].data_ptr(), b["rel_counts"].data_ptr(), b["n_rel"].data_ptr(),
-                                                   self.relTotal, denom, float(self.alpha), st), L)
-        self.global_step += 1
 
     def sparse_row_gradients(self):
         """(rows int32[n], counts int32[n, D]) of the last sparse step: the touched rows (entity rows first, relation

@@ -2220,13 +2220,10 @@ int kge_transe_apply_rows_sgd(const kge_model_desc *m, float *d_ent, float *d_re
     return hip_check(hipGetLastError(), "apply rows launch");
 }
 
-static const int32_t *g_lazy_row_live = nullptr;     // kge_transe_lazy_row_live: per-listed-row switch for the NEXT lazy-Adam row-list call
-
-int kge_transe_lazy_row_live(const int32_t *d_row_live) { g_lazy_row_live = d_row_live; return KGE_OK; }
-
 int kge_transe_apply_rows_adam_lazy(const kge_model_desc *m, float *d_ent, float *d_rel, float *d_m_ent, float *d_m_rel, float *d_v_ent,
                                     float *d_v_rel, const int32_t *d_rows, const int32_t *d_row_counts, const int32_t *d_n_rows,
-                                    INT max_rows, INT denom, float lr_t, float beta1, float beta2, float eps, void *stream_) {
+                                    INT max_rows, INT denom, float lr_t, float beta1, float beta2, float eps,
+                                    const int32_t *d_row_live, void *stream_) {
     hipStream_t stream = (hipStream_t)stream_;
     if (!device_ok()) return fail(KGE_ERR_NO_DEVICE, "kge_transe_apply_rows_adam_lazy: no usable HIP device");
     if (!m || !d_ent || !d_rel || !d_m_ent || !d_m_rel || !d_v_ent || !d_v_rel || !d_rows || !d_row_counts || !d_n_rows || denom <= 0)
@@ -2237,7 +2234,7 @@ int kge_transe_apply_rows_adam_lazy(const kge_model_desc *m, float *d_ent, float
     a.p = d_ent; a.p2 = d_rel; a.m = d_m_ent; a.m2 = d_m_rel; a.v = d_v_ent; a.v2 = d_v_rel;
     a.row_list = d_rows; a.S = const_cast<int32_t *>(d_row_counts); a.n_rows = d_n_rows;
     a.E = m->ent_total; a.D = m->ent_dim; a.unit = 1.0f / (float)denom; a.lr = lr_t; a.b1 = beta1; a.b2 = beta2; a.eps = eps; a.opt = kOptAdam;
-    a.row_live = g_lazy_row_live; g_lazy_row_live = nullptr;      // (one call only)
+    a.row_live = d_row_live;
     launch_apply_listed_rows(a, max_rows, stream);
     return hip_check(hipGetLastError(), "lazy adam rows launch");
 }

@@ -15,7 +15,7 @@ stale gradients.  Here the path is synchronous and every per-rank stage is O(1/N
   ALL-GATHERED.  Replicas are bit-identical by construction (one owner computes every element);
 * tables too large to replicate (config #5: 50 M x 512 = 102 GB): the entity table itself is sharded by
   row range, rows and int8 gradient records travel by ALL-TO-ALL to / from their owners
-  (Config._sharded_step, csrc/shard.hip); only the small relation table is replicated and its integer
+  (train_paths.sharded_step, csrc/shard.hip); only the small relation table is replicated and its integer
   count image all-reduced.
 
 The helpers below are thin wrappers over torch.distributed that also serve the `gloo` test rigs (gloo has no

@@ -1,0 +1,121 @@
+"""Which path a training step takes, decided once from plain values: no torch, no ctypes, no device.
+
+`plan()` is what `Config.set_model_and_session` asks before it creates anything; `shards_at_creation()` what
+`Config._plan_entity_shard` asks once it knows the world size; `large_counts_step()` the one predicate behind "TransE
+sign-count step at a large batch" (the packed negatives, the prefetch default, the step itself, the persistent launch).
+"""
+from collections import namedtuple
+
+from ._lib import KgeError, TRANSE, TRANSH, TRANSD
+
+# accepted spellings of the optimizer names (distribute_training.py:95 for Adam); any other name trains with SGD, as the reference does
+_KINDS = {"Adam": "adam", "adam": "adam",
+          "LazyAdam": "lazy_adam", "lazyadam": "lazy_adam", "lazy_adam": "lazy_adam",
+          "Adagrad": "adagrad", "adagrad": "adagrad"}
+
+
+def optimizer_kind(name):
+    """"sgd", "adam", "lazy_adam" or "adagrad"."""
+    return _KINDS.get(name, "sgd") if isinstance(name, str) else "sgd"
+
+
+class StepPlan(namedtuple("StepPlan", "optimizer use_counts sparse_rows sparse_inplace table_bytes")):
+    """optimizer: the kind (optimizer_kind).  use_counts: TransE's exact integer sign-count gradients instead of fp32 atomics.
+    sparse_rows: the int8-record touched-rows step (one rank: sparse step; N ranks: the table-sharded step).  sparse_inplace:
+    touched rows updated in place from float gradient records.  Neither: dense gradient tables (or the count image)."""
+    __slots__ = ()
+
+    @property
+    def adam(self):
+        return self.optimizer == "adam"
+
+    @property
+    def lazy_adam(self):
+        return self.optimizer == "lazy_adam"
+
+    @property
+    def adagrad(self):
+        return self.optimizer == "adagrad"
+
+    @property
+    def has_slots(self):
+        """m / v tables and beta powers exist (both Adam flavours)."""
+        return self.optimizer in ("adam", "lazy_adam")
+
+    @property
+    def rows_rule(self):
+        """Optimizers that ARE a choice of touched rows."""
+        return self.optimizer in ("lazy_adam", "adagrad")
+
+
+def wants_sparse_rows(sparse_rows, ent_total, rel_total, width, batch_size, n_neg, sparse_threshold_bytes=None):
+    """(table bytes, sparse rows wanted?) -- the caller's wish (`sparse_rows` True / False) or, left at None, the measured rule."""
+    table_bytes = (ent_total + rel_total) * width * 4
+    sparse = sparse_rows
+    if sparse is None:
+        # Measured cross-over on one MI355X (tools/sparse_crossover.sh, profiles/r03_sparse_crossover.jsonl: dim 512,
+        # B = 131 072, n = 1, tables of 0.26 .. 8.2 GB): the dense step costs the batch's work plus a sweep of the whole
+        # table and count image, the sparse step the batch's work plus its sort -- they tie at 0.26 GB (0.68 vs 0.70 ms),
+        # sparse rows win by 18 % at 0.5 GB and 5.4x at 8 GB.  The tie sits where the table is ~0.3x the bytes of the rows
+        # a step touches (1.07 GB there); below 128 MB the dense path's image fits the caches and it is kept.
+        touched_bytes = batch_size * (3 + n_neg) * width * 4
+        threshold = sparse_threshold_bytes
+        if threshold is None:
+            threshold = max(128 << 20, int(0.3 * touched_bytes))
+        sparse = table_bytes > int(threshold)
+    return table_bytes, sparse
+
+
+def plan(model_id, opt_method, sparse_rows, use_counts, counts_supported, ent_total, rel_total, width, batch_size, n_neg,
+         sparse_threshold_bytes=None, adagrad_initial_accumulator=0.1):
+    """The StepPlan of a configuration.  sparse_rows: None = automatic, True / False = the caller's wish; use_counts: the
+    caller's wish; counts_supported: what kge_transe_counts_supported said for the model's descriptor and n_neg."""
+    optimizer = optimizer_kind(opt_method)
+    adam, lazy_adam, adagrad = optimizer == "adam", optimizer == "lazy_adam", optimizer == "adagrad"
+    # LazyAdam -- opt-in, NON-PARITY: Adam on the touched rows only (tf.contrib.opt.LazyAdamOptimizer's rule) for tables whose dense
+    # TF1-Adam sweep -- 32 bytes per element per step, the reference's semantics -- would dominate the step.
+    # Adagrad -- opt-in: TF1's AdagradOptimizer (upstream OpenKE offers it; the reference sends the name to SGD).  Like LazyAdam it
+    # rides on the touched-rows paths, but exactly: an element with zero gradient keeps its value and its accumulator bit for bit,
+    # so "only the touched rows" IS the dense rule.  One accumulator table per parameter table, nothing to advance between steps.
+    # TransR has no record path and keeps its dense gradient tables (kge_adagrad_update_tables), in one process only.
+    if adagrad and not (float(adagrad_initial_accumulator) > 0.0):
+        raise KgeError("adagrad_initial_accumulator must be positive (the Adagrad rule divides by sqrt(accumulator), without an "
+                       "epsilon), got %r" % (adagrad_initial_accumulator,))
+    rows_rule = lazy_adam or adagrad
+    # TransE: exact integer sign-count gradients instead of fp32 atomics (include/kge_mi355.h)
+    use_counts = bool(use_counts) and bool(counts_supported)
+    # sparse-row mode: no dense gradient / count image at all.  The int8 records are reduced into a compact
+    # [touched rows, D] image and only those rows are updated; across ranks the records themselves are
+    # all-gathered (the sparse touched-row exchange of BASELINE config #5).  Not with Adam: TF1's sparse Adam
+    # sweeps every row of m, v and the table each step, which is the dense path by definition.
+    table_bytes, sparse = wants_sparse_rows(sparse_rows, ent_total, rel_total, width, batch_size, n_neg, sparse_threshold_bytes)
+    rows = (bool(sparse) or rows_rule) and use_counts and not adam
+    # TransH / TransD (and TransE outside the sign-count path) with SGD: the touched rows are updated in place from float
+    # gradient records (kge_forward_backward_sgd_rows) -- no gradient tables, no sweep.  On request, or by itself for tables
+    # beyond 2 GB (measured at 4 GB, dim 200, B = 131 072, n = 1: TransH 1.63 -> 0.70 ms, TransD 2.83 -> 0.97 ms per step and
+    # half the memory, profiles/r03_h_*; the dense form's sweep scales with the table, so the two tie near 1 GB)
+    # With LazyAdam the same records end in the Adam rule on the touched rows and their moments instead of the add
+    # (kge_forward_backward_adam_rows): asking for LazyAdam IS asking for touched rows, whatever `sparse_rows` says.
+    vector_model = model_id in (TRANSE, TRANSH, TRANSD)
+    inplace = bool(not rows and vector_model and not adam and
+                   (rows_rule or sparse_rows or (sparse_rows is None and table_bytes > (2 << 30))))
+    if lazy_adam and not (rows or inplace):
+        raise KgeError("LazyAdam (touched rows only, NON-PARITY) needs TransE, TransH or TransD: TransR's gradient is a whole "
+                       "matrix per relation and has no record path")
+    if sparse_rows and not (rows or inplace):
+        raise KgeError("sparse_rows needs TransE / TransH / TransD with SGD, LazyAdam or Adagrad")
+    return StepPlan(optimizer, use_counts, rows, inplace, table_bytes)
+
+
+def shards_at_creation(step_plan, model_id, world, width):
+    """Does a world of `world` ranks create the entity table row-sharded?  Where the step will be the table-sharded sparse one:
+    TransE on the sign-count path with SGD, LazyAdam or Adagrad, 2 to 64 ranks, a width that is a multiple of 4."""
+    return bool(1 < world <= 64 and width % 4 == 0 and model_id == TRANSE and step_plan.sparse_rows)
+
+
+def large_counts_step(step_plan, n_pos, n_neg, counts_min_records, world):
+    """TransE sign-count step at a large batch?  Steps with fewer gradient rows than counts_min_records per rank take the single
+    fused fp32-atomic kernel instead (launch-bound regime, tools/sweep_paths.py).  The same decision on every rank: it depends
+    on the global batch only."""
+    return (step_plan.use_counts and not step_plan.sparse_rows and not step_plan.sparse_inplace and
+            n_pos * (3 + n_neg) >= counts_min_records * world)      # (called once per training step: kept to one expression)

@@ -212,7 +212,7 @@ def test_the_count_row_stage_alone_against_the_rule(dim):
         p, m, v = [Guarded(*x.shape).put(x.view(np.int32)) for x in P], zeros(), zeros()
         _ok(L.kge_transe_apply_rows_adam_lazy(ctypes.byref(desc), p[0].ptr(), p[1].ptr(), m[0].ptr(), m[1].ptr(), v[0].ptr(), v[1].ptr(),
                                               d_rows.data_ptr(), d_counts.data_ptr(), d_n.data_ptr(), max_rows, denom, 0.01, 0.0, 0.999,
-                                              1e-8, None), _lib)
+                                              1e-8, None, None), _lib)
         return [g.get().view(np.float32) for g in m]         # m = 0 * 0 + g * (1 - 0)
 
     for general in (True, False):

@@ -90,7 +90,7 @@ def test_ranks_sharded_adagrad_with_relation_negatives(tmp_path):
 
 @pytest.mark.parametrize("model_name", ["TransH", "TransD"])
 def test_ranks_adagrad_from_gathered_records(tmp_path, model_name):
-    """Config._records_step ending in kge_float_records_apply_adagrad on 2 ranks: the replicas are bit-identical to each other;
+    """train_paths.records_step ending in kge_float_records_apply_adagrad on 2 ranks: the replicas are bit-identical to each other;
     against one process (the same records in batch order) the per-row sums differ in fp32 order only -- held to the tolerance
     tests/test_gpu_lazy_rows_dp.py applies to LazyAdam for the same comparison: 2e-4 of a table's largest element, losses to
     rtol 2e-5, rng states equal."""

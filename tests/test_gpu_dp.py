@@ -40,7 +40,7 @@ def _worker(rank, world, port, out_dir, model_name, opt, sparse=False, prefetch=
     con.prefetch_sampling = prefetch   # (data-parallel default: on; then the rng states run one batch ahead)
     con.counts_min_records = 0
     if pieces:
-        con.dp_pieces = pieces      # the flat buffers in `pieces` segments, each exchanged and updated on its own (Config._dp_exchange)
+        con.dp_pieces = pieces      # the flat buffers in `pieces` segments, each exchanged and updated on its own (train_paths.dp_exchange)
     con.init()
     con.set_model_and_session(getattr(pkg, model_name))
     assert (con.sparse_rows or con.sparse_inplace) == sparse      # (TransH / TransD: the row-wise SGD in place from float records)
@@ -210,7 +210,7 @@ def test_ranks_sharded_with_an_empty_shard(tmp_path, opt):
 def test_ranks_sharded_with_relation_negatives(tmp_path, world):
     """ent_neg_rate 2, rel_neg_rate 2: the relation-corrupted negatives' records (destination ent_total + r', slot 3 + k) request no
     entity row, reuse both cache slots of their positive, stay out of the entity exchange and reach the relation image through
-    kge_shard_relation_counts -- the branch of Config._sharded_step that no other test runs on a record."""
+    kge_shard_relation_counts -- the branch of train_paths.sharded_step that no other test runs on a record."""
     res = _run_worlds(tmp_path, [1, world], "TransE", "SGD", True, False, 10, 0, False, None, 48, 2, 2)
     _sharded_equals_one_process(res, world)
 
@@ -246,7 +246,7 @@ def _relations_only_negatives_touch(data, z, ent_neg, rel_neg):
 def test_ranks_sharded_lazy_adam_with_relation_negatives(tmp_path, world):
     """LazyAdam on a sharded table with relation negatives, 24 positives over 40 relations: in some step a relation takes records
     ONLY from relation-corrupted negatives.  One process lists that row and moves it and its moments; the sharded step must mark
-    it live too (Config._sharded_step), or the replicated relation table leaves the one-process table at that step.  The
+    it live too (train_paths.sharded_step), or the replicated relation table leaves the one-process table at that step.  The
     precondition -- such a relation exists in at least one of the four steps -- is asserted first."""
     from openkeonspark_amd import synthetic
     data = synthetic.make_typed_dataset(str(tmp_path / "kg40rel"), synthetic.SMALL_TYPED, **LAZY_REL)
@@ -258,7 +258,7 @@ def test_ranks_sharded_lazy_adam_with_relation_negatives(tmp_path, world):
 
 @pytest.mark.parametrize("model_name,world", [("TransH", 2), ("TransH", 4), ("TransD", 2)])
 def test_ranks_row_wise_sgd_from_gathered_records(tmp_path, model_name, world):
-    """sparse_rows with TransH / TransD on N ranks (Config._records_step): every rank turns its slice of the batch into float
+    """sparse_rows with TransH / TransD on N ranks (train_paths.records_step): every rank turns its slice of the batch into float
     gradient records, the records are all-gathered and every rank adds -lr * the per-row sums of ALL of them to its replica.
     Every rank reduces the same records in the same order: the replicas are bit-identical; against the single-process step
     (kge_forward_backward_sgd_rows, the same records in batch order) the per-row sums differ in fp32 order only.  A rank whose

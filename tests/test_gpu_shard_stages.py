@@ -1,5 +1,5 @@
 """The device stages of the table-sharded sparse TransE step (csrc/shard.hip, the record reduction and the row-list updates of
-csrc/transe_counts.hip), each called through the C ABI as Config._sharded_step calls it and compared with a few lines of numpy
+csrc/transe_counts.hip), each called through the C ABI as train_paths.sharded_step calls it and compared with a few lines of numpy
 written from the header's description (include/kge_mi355.h, "Table-sharded sparse path").  Every stage is integer work or a
 copy, so every comparison is exact.
 
@@ -485,9 +485,9 @@ def test_apply_rows_sgd_moves_the_listed_rows_only(dim):
 
 @pytest.mark.parametrize("dim", [48, 200, 512])
 def test_lazy_adam_rows_and_the_live_mask(dim):
-    """kge_transe_apply_rows_adam_lazy with kge_transe_lazy_row_live: rows that are not listed, and listed rows whose live flag is
+    """kge_transe_apply_rows_adam_lazy with its d_row_live argument: rows that are not listed, and listed rows whose live flag is
     0, keep their parameter row and both moment rows bit for bit; listed live rows equal the same call made without a mask; the
-    mask holds for ONE call (the next call without it moves every listed row)."""
+    mask holds for the call it is given to (the next call without it moves every listed row)."""
     torch, _lib, L = _env()
     rng = np.random.default_rng(dim + 6)
     E, R = 211, 17
@@ -502,11 +502,10 @@ def test_lazy_adam_rows_and_the_live_mask(dim):
 
     def run(mask):
         tabs = [[Guarded(*x.shape).put(x) for x in pair] for pair in start]
-        if mask:
-            _ok(L.kge_transe_lazy_row_live(d_live.data_ptr()), _lib)
         (p, p2), (m, m2), (v, v2) = tabs
         _ok(L.kge_transe_apply_rows_adam_lazy(ctypes.byref(desc), p.ptr(), p2.ptr(), m.ptr(), m2.ptr(), v.ptr(), v2.ptr(), d_rows.data_ptr(),
-                                              d_counts.data_ptr(), d_n.data_ptr(), max_rows, 100, 0.01, 0.9, 0.999, 1e-8, None), _lib)
+                                              d_counts.data_ptr(), d_n.data_ptr(), max_rows, 100, 0.01, 0.9, 0.999, 1e-8,
+                                              d_live.data_ptr() if mask else None, None), _lib)
         return [[g.get() for g in pair] for pair in tabs]
 
     plain = run(False)
@@ -525,3 +524,63 @@ def test_lazy_adam_rows_and_the_live_mask(dim):
             assert np.array_equal(part[still], was[still]), (dim, k, side)
             assert np.array_equal(part[moved_live[side]], full[moved_live[side]]), (dim, k, side)
             assert np.array_equal(after[k][side], full), (dim, k, side)
+
+
+def _tiny_lazy_case(dim):
+    """TransE E = 6, R = 3: parameter, first- and second-moment tables (as numpy), a list of 4 rows (two entity rows, two relation
+    rows) with non-zero counts, and a function that applies kge_transe_apply_rows_adam_lazy to fresh copies of the tables."""
+    torch, _lib, L = _env()
+    rng = np.random.default_rng(900 + dim)
+    E, R = 6, 3
+    start = [[(np.abs(x) if positive else x).astype(np.float32).view(np.int32)
+              for x in (rng.standard_normal((n, dim)) * scale for n in (E, R))]
+             for scale, positive in ((1.0, False), (0.01, False), (1e-4, True))]
+    listed = np.array([1, 4, E + 0, E + 2])
+    d_rows, d_n = _dev(listed), _dev([4])
+    d_counts = _dev(rng.integers(1, 20, (4, dim)) * rng.choice([-1, 1], (4, dim)))
+    desc = _desc(_lib, E, R, dim)
+
+    def fresh():
+        return [[Guarded(*x.shape).put(x) for x in pair] for pair in start]
+
+    def apply(tabs, max_rows, d_live):
+        (p, p2), (m, m2), (v, v2) = tabs
+        _ok(L.kge_transe_apply_rows_adam_lazy(ctypes.byref(desc), p.ptr(), p2.ptr(), m.ptr(), m2.ptr(), v.ptr(), v2.ptr(), d_rows.data_ptr(),
+                                              d_counts.data_ptr(), d_n.data_ptr(), max_rows, 100, 0.01, 0.9, 0.999, 1e-8,
+                                              d_live.data_ptr() if d_live is not None else None, None), _lib)
+
+    def read(tabs):
+        return [np.concatenate([g.get() for g in pair]) for pair in tabs]      # rows of the [(E + R), D] space, as the list names them
+
+    return listed, [np.concatenate(pair) for pair in start], fresh, apply, read
+
+
+@pytest.mark.parametrize("dim", [4, 6])       # (a vector team and a scalar team)
+def test_lazy_adam_row_mask_is_an_argument(dim):
+    """live = [1, 0, 1, 0] over a list of 4 rows: listed rows 1 and 3 and their moments stay bit for bit, listed rows 0 and 2 equal
+    the unmasked call on a copy of the tables."""
+    listed, start, fresh, apply, read = _tiny_lazy_case(dim)
+    plain, masked = fresh(), fresh()
+    apply(plain, 4, None)
+    apply(masked, 4, _dev([1, 0, 1, 0]))
+    for k, (was, full, part) in enumerate(zip(start, read(plain), read(masked))):      # parameters, first moments, second moments
+        assert (full[listed] != was[listed]).any(axis=1).all(), (dim, k)
+        assert np.array_equal(part[listed[[1, 3]]], was[listed[[1, 3]]]), (dim, k)
+        assert np.array_equal(part[listed[[0, 2]]], full[listed[[0, 2]]]), (dim, k)
+        rest = np.setdiff1d(np.arange(len(was)), listed)
+        assert np.array_equal(part[rest], was[rest]) and np.array_equal(full[rest], was[rest]), (dim, k)
+
+
+@pytest.mark.parametrize("dim", [4, 6])
+def test_lazy_adam_row_mask_of_an_empty_call_does_not_linger(dim):
+    """A call with max_rows = 0 returns before its launch; the mask it was given must not reach the next, unmasked call of 4 rows:
+    all four rows move, exactly as without the empty call."""
+    listed, start, fresh, apply, read = _tiny_lazy_case(dim)
+    plain, after_empty = fresh(), fresh()
+    apply(plain, 4, None)
+    apply(after_empty, 0, _dev([1, 0, 1, 0]))
+    assert all(np.array_equal(a, b) for a, b in zip(read(after_empty), start))
+    apply(after_empty, 4, None)
+    for k, (was, full, got) in enumerate(zip(start, read(plain), read(after_empty))):
+        assert (got[listed] != was[listed]).any(axis=1).all(), (dim, k)
+        assert np.array_equal(got, full), (dim, k)

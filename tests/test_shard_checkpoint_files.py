@@ -9,7 +9,7 @@ from openkeonspark_amd import distribute_training as dt
 
 
 def _write(base, table, world, moments=True):
-    """The shard files `world` ranks of a run over `table` would write (chunk = ceil(E / world), as Config._setup_shards)."""
+    """The shard files `world` ranks of a run over `table` would write (chunk = ceil(E / world), as train_paths.setup_shards)."""
     E = table.shape[0]
     chunk = -(-E // world)
     for g in range(world):
