@@ -449,6 +449,12 @@ int kge_pair_path_active(const kge_model_desc *m, INT n_pos, INT n_neg);
 /* 1 when kge_forward_backward_sampled on a TransR step of this shape takes the group layout (groups sorted by relation, the
  * vector stage in the projection's epilogue: option "transr_groups"), else 0 -- what the tests of that layout assert */
 int kge_transr_group_layout_active(const kge_model_desc *m, INT n_pos, INT n_neg);
+/* Host-only, as the two above.  The number of virtual copies of the relation rows that kge_transe_forward_counts /
+ * kge_transe_train_step_counts sort a step of n_pos groups over: 1 below 4096 groups, else option "counts_krel" (a power of
+ * two, default 4), halved while copies * rel_total > 2 * (ent_total + rel_total). */
+INT kge_transe_relation_copies(const kge_model_desc *m, INT n_pos);
+/* Records per team of the float-record segmented sum of a step with n_records records: 16, 32 from 2^18, 64 from 2^20 on. */
+INT kge_float_records_chunk_len(INT n_records);
 
 /* The same call for a batch the caller KNOWS to be sampler-shaped -- what kge_sampling_device / `sampling` produce
  * (Base.cpp:109-139): every negative differs from its positive in exactly one entity slot, or (negative_rel) in the relation.

@@ -93,6 +93,10 @@ def _declare(L):
     L.kge_stream_wait_emit.argtypes = [vp]
     L.kge_pair_path_active.argtypes = [ctypes.POINTER(ModelDesc), i64, i64]
     L.kge_transr_group_layout_active.argtypes = [ctypes.POINTER(ModelDesc), i64, i64]
+    L.kge_transe_relation_copies.restype = i64
+    L.kge_transe_relation_copies.argtypes = [ctypes.POINTER(ModelDesc), i64]
+    L.kge_float_records_chunk_len.restype = i64
+    L.kge_float_records_chunk_len.argtypes = [i64]
     L.kge_loss_limbs_target.argtypes = [vp]
     L.kge_forward_backward_sgd_rows.argtypes = [ctypes.POINTER(ModelDesc), tabs, vp, vp, vp, i64, i64, i64, i64, f32, vp, vp]
     L.kge_forward_backward_records.argtypes = [ctypes.POINTER(ModelDesc), tabs, vp, vp, vp, i64, i64, i64, i64, i64, vp, vp, i64, i64, vp, vp]

@@ -573,6 +573,10 @@ int kge_transr_group_layout_active(const kge_model_desc *m, INT n_pos, INT n_neg
     return m && transr_group_layout_active(*m, n_pos, n_neg) ? 1 : 0;
 }
 
+INT kge_transe_relation_copies(const kge_model_desc *m, INT n_pos) { return m ? transe_relation_copies(*m, n_pos) : 1; }
+
+INT kge_float_records_chunk_len(INT n_records) { return float_records_chunk_len(n_records); }
+
 int kge_stream_wait_emit(void *stream) {
     Engine &e = engine();
     // nothing recorded since the last wait (recording off, or this step's path has no emit kernel): the caller must order the

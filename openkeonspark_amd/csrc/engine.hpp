@@ -174,6 +174,8 @@ struct FloatRowSpace {   // virtual row space of models.hip's FbArgs::frec recor
 };
 bool pair_path_active(const kge_model_desc &m, int64_t n_pos, int64_t n_neg);
 bool transr_group_layout_active(const kge_model_desc &m, int64_t n_pos, int64_t n_neg);
+int transe_relation_copies(const kge_model_desc &m, int64_t n_pos);
+int float_records_chunk_len(int64_t M);
 int sgd_rows_skipped(int32_t *out);
 int float_records_workspace(int64_t M, int D, float *&rec, int32_t *&dst);
 // rec_ext / dst_ext: records held by the caller (the gathered records of a data-parallel step) instead of the workspace's

@@ -1350,6 +1350,21 @@ void launch_segsum_adam(int64_t M, const float *rec, const FloatRowSpace &rs, co
 
 }  // namespace
 
+// records per team of segsum_f32_kernel (also behind kge_float_records_chunk_len): shorter chunks while the step is small --
+// the per-team record loop is a chain of dependent loads
+int float_records_chunk_len(int64_t M) { return M >= (int64_t(1) << 20) ? 64 : (M >= (int64_t(1) << 18) ? 32 : 16); }
+
+// virtual copies of the relation rows a sign-count step of n_pos groups sorts its records over (also behind
+// kge_transe_relation_copies): option counts_krel from 4096 groups on, halved while the copies would outgrow the row space
+int transe_relation_copies(const kge_model_desc &m, int64_t n_pos) {
+    int krel = 1;
+    if (n_pos >= 4096 && m.rel_total > 0 && engine().counts_krel > 1) {
+        krel = engine().counts_krel;
+        while (krel > 1 && (int64_t)krel * m.rel_total > 2 * (m.ent_total + m.rel_total)) krel >>= 1;   // copies stay a minor part of the row space
+    }
+    return krel;
+}
+
 int float_records_workspace(int64_t M, int D, float *&rec, int32_t *&dst) {
     int rc = ensure_counts_work(M, (size_t)D);
     if (rc) return rc;
@@ -1389,8 +1404,7 @@ int float_records_reduce(int64_t M, int D, const FloatRowSpace &rs, hipStream_t 
         }
         return hip_check(hipGetLastError(), "float records deterministic reduce launch");
     }
-    // shorter chunks while the step is small: the per-team record loop is a chain of dependent loads
-    const int chunk_len = M >= (int64_t(1) << 20) ? 64 : (M >= (int64_t(1) << 18) ? 32 : 16);
+    const int chunk_len = float_records_chunk_len(M);
     for_team_shape_or_last(D, [&](auto t) {
         constexpr int L = decltype(t)::L, C = decltype(t)::C;
         const long long chunks = (M + chunk_len - 1) / chunk_len;
@@ -1923,11 +1937,7 @@ static int forward_counts_impl(const kge_model_desc *m, const float *d_ent, cons
     // a sixth of them), and in the bucketing kernels all those records count on a handful of LDS bins -- same-address LDS atomics
     // serialise, which set the tail of bkt_hist / bkt_scatter / bkt_sort (SQ_LDS_BANK_CONFLICT 64-92 % of their LDS cycles).  Group b
     // therefore addresses copy b % krel of the relation rows (virtual rows E + c R + r); the segmented sum folds them back.
-    int krel = 1;
-    if (n_pos >= 4096 && m->rel_total > 0 && engine().counts_krel > 1) {
-        krel = engine().counts_krel;
-        while (krel > 1 && (int64_t)krel * m->rel_total > 2 * (m->ent_total + m->rel_total)) krel >>= 1;   // copies stay a minor part of the row space
-    }
+    const int krel = transe_relation_copies(*m, n_pos);
     const int rows = (int)(m->ent_total + (int64_t)krel * m->rel_total);
     const int D = m->ent_dim;
     const bool nat = D % 4 == 0;   // the vectorised emit kernel writes records in natural element order

@@ -115,6 +115,36 @@ def transr_tiles(request):
 @pytest.mark.parametrize("n,nr,foreign", [(1, 0, 0.0), (5, 0, 0.0), (2, 1, 0.0), (3, 1, 0.3), (4, 0, 0.3)])
 def test_transr_forward_backward_matches_oracle(E, R, De, Dr, n, nr, foreign, transr_tiles):
     """Relation-bucketed fp32-MFMA TransR (projection, dgrad, wgrad) against the oracle."""
+    transr_case_matches_oracle(E, R, De, Dr, n, nr, foreign)
+
+
+@pytest.fixture(params=["v3-bf16x3", "v2-16x16x4"])
+def transr_tiles_with_records(request):
+    """The two tilings of transr_tiles that can store dgrad's rows as records, with the records forced at every size
+    (default: from 2^15 slots on)."""
+    from openkeonspark_amd import _lib
+    L = _lib.lib()
+    L.kge_set_option(b"transr_bf16x3", 1 if request.param == "v3-bf16x3" else 0)
+    L.kge_set_option(b"transr_v1", 0)
+    L.kge_set_option(b"transr_dgrad_records_min", 0)
+    yield request.param
+    L.kge_set_option(b"transr_dgrad_records_min", 1 << 15)
+    L.kge_set_option(b"transr_bf16x3", 1)
+
+
+@pytest.mark.parametrize("E,R,De,Dr", TRANSR_CASES + [(80, 3, 208, 16), (70, 6, 100, 208), (400, 300, 120, 116)])
+@pytest.mark.parametrize("n,nr,foreign", [(1, 0, 0.0), (5, 0, 0.0), (2, 1, 0.0), (3, 1, 0.3), (4, 0, 0.3)])
+def test_transr_forward_backward_matches_oracle_with_dgrad_records(E, R, De, Dr, n, nr, foreign, transr_tiles_with_records):
+    """The dgrad-records leg of test_transr_forward_backward_matches_oracle: the three-kernel path (B = 301 is below the group
+    layout's 64 rows per relation) with dgrad's entity-gradient rows stored as float records and summed by segments --
+    prep_kernel writes rec_dst = -1 for the alias slots, rows_gemm2/3_kernel<GEMM_DGRAD> store the records -- together with
+    relation negatives (a negative's own matrix), foreign negatives and both tilings.  At R = 300 the step has fewer than 256 R
+    slots, so the 16x16x4 tiling splits widths beyond 112 into two column blocks of 7 tiles (split_cols: De = 120, Dr = 116):
+    the one shape where records meet a second column block, whose workgroups must leave rec_dst to the first."""
+    transr_case_matches_oracle(E, R, De, Dr, n, nr, foreign)
+
+
+def transr_case_matches_oracle(E, R, De, Dr, n, nr, foreign):
     import torch
     rng = np.random.default_rng(seed_of(De, Dr, n, nr))
     B = 301

@@ -233,3 +233,39 @@ def test_transr_group_layout_selection_rule():
         assert active(Rm, 237, 200, 200, 34014, 1) == 0
     finally:
         L.kge_set_option(b"transr_groups", 1)
+
+
+def test_transe_relation_copies_rule():
+    """kge_transe_relation_copies (include/kge_mi355.h): the virtual copies of the relation rows a sign-count step sorts its
+    records over -- host logic only: 1 below 4096 groups, else option counts_krel (rounded down to a power of two, at most
+    64), halved while copies * R > 2 (E + R); forward_counts_impl asks the same function."""
+    from openkeonspark_amd import _lib
+    L = _lib.lib()
+
+    def copies(E, R, B, model=_lib.TRANSE, D=16):
+        d = _lib.ModelDesc(model, 0, E, R, D, D, 1.0, 0)
+        return L.kge_transe_relation_copies(ctypes.byref(d), B)
+
+    assert copies(61, 4, 4095) == 1 and copies(61, 4, 4096) == 4 and copies(61, 4, 4097) == 4     # the threshold
+    assert copies(14541, 237, 34014) == 4 and copies(14541, 237, 300) == 1
+    assert copies(61, 0, 4096) == 1                                                                 # no relation rows
+    # halving: 4 * 4 = 16 <= 2 * 65 keeps 4; 4 * 40 = 160 > 2 * 50 = 100 halves to 2 (80 <= 100)
+    assert copies(61, 4, 4096) == 4 and copies(10, 40, 4096) == 2
+    assert copies(1, 40, 4096) == 2 and copies(1, 400, 4096) == 2 and copies(0, 40, 4096) == 2    # k R <= 2 R always holds at k = 2
+    try:
+        for value, want in ((1, 1), (2, 2), (4, 4), (8, 8), (64, 64), (6, 4), (100, 64), (0, 1)):
+            L.kge_set_option(b"counts_krel", value)
+            assert copies(2000, 4, 4096) == want, (value, want)
+            assert copies(2000, 4, 4095) == 1
+        L.kge_set_option(b"counts_krel", 64)
+        assert copies(61, 4, 4096) == 32 and copies(10, 40, 4096) == 2                              # 32 * 4 = 128 <= 130
+    finally:
+        L.kge_set_option(b"counts_krel", 4)
+
+
+def test_float_records_chunk_length_rule():
+    """kge_float_records_chunk_len: records per team of the float-record segmented sum -- 16, 32 from 2^18 records, 64 from 2^20."""
+    from openkeonspark_amd import _lib
+    L = _lib.lib()
+    assert [L.kge_float_records_chunk_len(n) for n in (0, 1, (1 << 18) - 1, 1 << 18, (1 << 20) - 1, 1 << 20, 1 << 31)] \
+        == [16, 16, 16, 32, 32, 64, 64]
