@@ -742,6 +742,44 @@ int kge_rank_triples_range(const kge_model_desc *m, const float *const tables[KG
 int kge_rank_triples(const kge_model_desc *m, const float *const tables[KGE_MAX_TABLES], const int32_t *d_h, const int32_t *d_t,
                      const int32_t *d_r, INT n, INT test_head, int64_t *d_counts, void *stream);
 
+/* Ranks of triples against CANDIDATE LISTS instead of every entity (csrc/rank_cand.hip): triple i = (d_h[i], d_t[i], d_r[i])
+ * (DEVICE int32), each side ranked against n_cand candidates that the caller supplies or that the kernel draws.  Cost is
+ * n x n_cand x dim; no candidate table, no score matrix, no host synchronisation.
+ * d_counts (DEVICE int64 [n][2][2], every element written): side 0 ranks the list as the tail of (h, r, ?), side 1 as the head
+ *   of (?, r, t).  Column 0: the listed candidates, other than the target id, whose score is strictly below the true triple's
+ *   (NaN never counts); column 1: the same without the candidates that form a known triple with the fixed entity and the
+ *   relation (the train + valid + test union of importTestFiles).  Without KGE_RANKC_FILTERED column 1 is not computed and
+ *   equals column 0, and importTestFiles is not needed.
+ * Lists: a side's list is read at d_*_cand[i * stride + k], k < n_cand (DEVICE int32): stride >= n_cand is one list per triple,
+ *   stride == 0 one list shared by all triples.  A NULL list: that side is not ranked and its counts are zero.  An id outside
+ *   [0, ent_total) is skipped, so -1 pads ragged lists; a repeated id counts every time it is listed.
+ * KGE_RANKC_DRAWN: both list pointers are NULL and candidate k of (triple i, side s) is drawn inside the kernel (no list exists
+ *   in memory), all arithmetic mod 2^64:
+ *       c = ((2 i + s) << 32) | k;   z = seed + (c + 1) * 0x9E3779B97F4A7C15;
+ *       z = (z ^ z >> 30) * 0xBF58476D1CE4E5B9;   z = (z ^ z >> 27) * 0x94D049BB133111EB;   z ^= z >> 31;
+ *       id = ((z >> 32) * ent_total) >> 32
+ *   With KGE_RANKC_TYPED the same ((z >> 32) * len) >> 32 indexes the relation's tail (side 0) / head (side 1) type list of
+ *   importTypeFiles (len its length); a relation with an empty list takes the untyped draw.  With KGE_RANKC_NO_HEAD only the
+ *   tail side is drawn and ranked.  TYPED and NO_HEAD need DRAWN.
+ * The scores are kge_predict's bits (TransR: each relation's own matrix).  TransE / TransH / TransD take one fused kernel
+ * (a team per (triple, side), candidate rows gathered straight into registers); TransR, and every model with option
+ * "rankc_fused" = 0, takes the two-stage form: chunks of at most 2^22 (triple, candidate) pairs are spelled out in a bounded
+ * workspace, scored by kge_predict's own kernels and counted; both forms give the same counts.  Option "rankc_slices" (test
+ * hook): N > 0 cuts every list into N slices over the grid, 0 chooses; the counts do not depend on it.
+ * A triple with an id outside [0, ent_total) / [0, rel_total) is disabled: its counts stay zero, nothing is indexed with its
+ * ids and the call still returns KGE_OK.  n == 0 or n_cand == 0 checks the arguments, zeroes d_counts and launches nothing.
+ * KGE_ERR_BAD_ARG: a null model, table, triple or output array, n outside [0, 2^30), n_cand outside [0, 2^31), unknown flags,
+ * a list pointer together with DRAWN, no list at all without it, TYPED / NO_HEAD without DRAWN, a stride that is neither 0 nor
+ * >= n_cand; KGE_ERR_UNSUPPORTED: embedding (TransR: relation) dimension above 1024; KGE_ERR_NO_DATASET: FILTERED before
+ * importTestFiles, TYPED before importTypeFiles.  Nothing is written to d_counts when an error is returned. */
+#define KGE_RANKC_FILTERED 1
+#define KGE_RANKC_DRAWN 2
+#define KGE_RANKC_TYPED 4
+#define KGE_RANKC_NO_HEAD 8
+int kge_rank_candidates(const kge_model_desc *m, const float *const tables[KGE_MAX_TABLES], const int32_t *d_h, const int32_t *d_t,
+                        const int32_t *d_r, INT n, const int32_t *d_tail_cand, INT tail_stride, const int32_t *d_head_cand,
+                        INT head_stride, INT n_cand, INT flags, uint64_t seed, int64_t *d_counts, void *stream);
+
 /* Batched top-k entity prediction on the device.  Query i: d_head[i] == 0 asks for the k best tails of (d_fixed[i], d_rel[i], ?),
  * d_head[i] != 0 for the k best heads of (?, d_rel[i], d_fixed[i]); sides and relations may be mixed in any order.  d_ids /
  * d_scores (DEVICE, row-major [n][k]) receive the candidates in ascending (score, id) order -- NaN after every number -- with

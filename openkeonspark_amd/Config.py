@@ -1396,6 +1396,17 @@ class Config(object):
         return ids.cpu().numpy().astype(np.int64), scores.cpu().numpy()
 
     @staticmethod
+    def _rank_sums(d, prefix, suffix, raw, filt):
+        """Adds the un-normalised accumulators of one side's raw and filtered counts to `d`: Hits@10 / 3 / 1, MR and MRR under
+        the reference's names (main_spark.py:430-448), `prefix` r (tail side) or l (head side), `suffix` "" or "_constrain"."""
+        for name, cnt in (("", raw), ("_filter", filt)):
+            d[prefix + name + "_tot" + suffix] = float((cnt < 10).sum())                    # Hits@10
+            d[prefix + "3" + name + "_tot" + suffix] = float((cnt < 3).sum())               # Hits@3
+            d[prefix + "1" + name + "_tot" + suffix] = float((cnt < 1).sum())               # Hits@1
+            d[prefix + name + "_rank" + suffix] = float((1 + cnt).sum())                    # MR
+            d[prefix + name + "_reci_rank" + suffix] = float((1.0 / (1 + cnt)).sum())       # MRR
+
+    @staticmethod
     def _lp_sums(out, test_head=True):
         """Un-normalised accumulators of main_spark.py:430-448 over the rows of `out` (they add across test-set slices)."""
         d = {}
@@ -1403,18 +1414,17 @@ class Config(object):
             if side == 1 and not test_head:
                 continue
             raw, filt, raw_c, filt_c = (out[:, side, i] for i in range(4))
-            for name, cnt in (("", raw), ("_filter", filt)):
-                d[p + name + "_tot"] = float((cnt < 10).sum())                    # Hits@10
-                d[p + "3" + name + "_tot"] = float((cnt < 3).sum())               # Hits@3
-                d[p + "1" + name + "_tot"] = float((cnt < 1).sum())               # Hits@1
-                d[p + name + "_rank"] = float((1 + cnt).sum())                    # MR
-                d[p + name + "_reci_rank"] = float((1.0 / (1 + cnt)).sum())       # MRR
-            for name, cnt in (("", raw_c), ("_filter", filt_c)):
-                d[p + name + "_tot_constrain"] = float((cnt < 10).sum())
-                d[p + "3" + name + "_tot_constrain"] = float((cnt < 3).sum())
-                d[p + "1" + name + "_tot_constrain"] = float((cnt < 1).sum())
-                d[p + name + "_rank_constrain"] = float((1 + cnt).sum())
-                d[p + name + "_reci_rank_constrain"] = float((1.0 / (1 + cnt)).sum())
+            Config._rank_sums(d, p, "", raw, filt)
+            Config._rank_sums(d, p, "_constrain", raw_c, filt_c)
+        return d
+
+    @staticmethod
+    def _cand_sums(counts, sides=(0, 1)):
+        """The same accumulators over candidate-list counts [n, 2, 2] (raw, filtered) for the ranked sides; no _constrain names."""
+        d = {}
+        for side, p in ((0, "r"), (1, "l")):
+            if side in sides:
+                Config._rank_sums(d, p, "", counts[:, side, 0], counts[:, side, 1])
         return d
 
     @staticmethod
@@ -1533,6 +1543,155 @@ class Config(object):
         counts = shard_eval.rank_triples(self, dev, err, test_head)
         return counts, self._lp_normalise(self._lp_sums(counts, test_head), counts.shape[0])
 
+    # candidate lists instead of every entity (kge_rank_candidates) ------------------------------------------------------------
+    def _refuse_sharded_candidates(self, what):
+        if self._sharded("ent_embeddings"):
+            raise KgeError("%s over an entity table sharded across ranks is not supported: candidate lists are ranked against "
+                           "replicated tables only (rank against every entity with rank_triples_distributed, a collective on "
+                           "sharded tables)" % what)
+
+    def _candidate_list(self, cand, n, name):
+        """A candidate array ([n, C] or [C]; numpy / list / torch tensor on any device) -> (int32 device tensor, C, stride)."""
+        import torch
+        if torch.is_tensor(cand):
+            if cand.dtype not in (torch.int32, torch.int64, torch.int16, torch.int8, torch.uint8):
+                raise KgeError("%s must hold integer ids, got %s" % (name, cand.dtype))
+            dev = cand.to(device=self.device, dtype=torch.int32).contiguous()       # a device tensor stays on the device
+        else:
+            host = np.asarray(cand)
+            if host.dtype.kind not in "iu" and host.size:
+                raise KgeError("%s must hold integer ids, got %s" % (name, host.dtype))
+            if host.size and (host.min() < -2 ** 31 or host.max() >= 2 ** 31):
+                raise KgeError("%s: an id does not fit 32 bits" % name)
+            dev = torch.from_numpy(np.ascontiguousarray(host, dtype=np.int32)).to(self.device)
+        if dev.dim() == 1:
+            return dev, int(dev.shape[0]), 0
+        if dev.dim() == 2 and dev.shape[0] == n:
+            return dev, int(dev.shape[1]), int(dev.shape[1])
+        raise KgeError("%s must be [n, C] = [%d, C] or a shared list [C], got %s" % (name, n, list(dev.shape)))
+
+    def _rank_candidates_device(self, dev, tail, head, n_cand, flags, seed, first=0, into=None):
+        """kge_rank_candidates on an int32 device tensor [3, n] (ids already checked); tail / head = (tensor, stride) or None.
+        `first` is the global index of the first triple, for drawn lists (the hash is indexed by it: adding first * 2^33 times the
+        hash's multiplier to the seed moves the counter there).  -> int64 numpy [n, 2, 2], or None with `into` (a device tensor)."""
+        import torch
+        n = dev.shape[1]
+        counts = into if into is not None else torch.empty((n, 2, 2), dtype=torch.int64, device=self.device)
+        spare = torch.zeros((3, 4), dtype=torch.int32, device=self.device)        # an empty tensor has no address
+        ptr = lambda x: x.data_ptr() if x.numel() else spare.data_ptr()
+        ids = dev if n else spare
+        lists = [(None, 0) if side is None else (ptr(side[0]), side[1]) for side in (tail, head)]
+        seed = (int(seed) + ((int(first) << 33) * 0x9E3779B97F4A7C15)) & 0xFFFFFFFFFFFFFFFF
+        _lib.check(self.lib.kge_rank_candidates(ctypes.byref(self._desc), self._tab_ptrs, ids[0].data_ptr(), ids[1].data_ptr(), ids[2].data_ptr(),
+                                                n, lists[0][0], lists[0][1], lists[1][0], lists[1][1], n_cand, flags, seed,
+                                                counts.data_ptr() if n else spare.data_ptr(), self._stream()), self.lib)
+        return counts.cpu().numpy() if into is None else None
+
+    def rank_candidates(self, h, t, r, tail_candidates=None, head_candidates=None, filtered=True):
+        """Rank triples against candidate lists of the caller's instead of every entity (kge_rank_candidates): h, t, r are 1-D id
+        arrays of one length n; a candidate array is [n, C] (one list per triple) or [C] (one list shared by all), integer, as
+        numpy or as a torch tensor (a device tensor is not copied to the host).  An id outside [0, entTotal) is skipped, so -1
+        pads ragged lists; a repeated id counts every time.  Both lists must have the same C when both are given; a side
+        without a list is not ranked.  Returns (counts int64 [n, 2, 2], metrics): counts[i, 0] ranks the tail list of (h, r, ?),
+        counts[i, 1] the head list of (?, r, t); column 0 is the number of listed candidates other than the target that score
+        strictly below the true triple, column 1 the same without the candidates forming a known triple (train + valid + test;
+        needs init_link_prediction() -- with filtered=False it is not computed, equals column 0 and nothing is needed).  metrics
+        has link_prediction's raw and _filter names for the ranked sides, normalised by n.  The scores are test_step's bits.
+        An id of a TRIPLE out of range raises KgeError before anything is launched."""
+        import torch
+        self._refuse_sharded_candidates("rank_candidates")
+        host = np.stack([np.asarray(h).reshape(-1), np.asarray(t).reshape(-1), np.asarray(r).reshape(-1)]).astype(np.int32)
+        self._check_ids(host)
+        n = host.shape[1]
+        if tail_candidates is None and head_candidates is None:
+            raise KgeError("rank_candidates: give tail_candidates, head_candidates or both")
+        tail = None if tail_candidates is None else self._candidate_list(tail_candidates, n, "tail_candidates")
+        head = None if head_candidates is None else self._candidate_list(head_candidates, n, "head_candidates")
+        if tail is not None and head is not None and tail[1] != head[1]:
+            raise KgeError("rank_candidates: both lists must have the same number of candidates, got %d and %d" % (tail[1], head[1]))
+        n_cand = (tail or head)[1]
+        counts = self._rank_candidates_device(torch.from_numpy(host).to(self.device), tail and (tail[0], tail[2]), head and (head[0], head[2]),
+                                              n_cand, _lib.RANKC_FILTERED if filtered else 0, 0)
+        sides = [s for s, x in ((0, tail), (1, head)) if x is not None]
+        return counts, self._lp_normalise(self._cand_sums(counts, sides), n)
+
+    @staticmethod
+    def _sampled_flags(test_head, type_constrained, filtered):
+        return (_lib.RANKC_DRAWN | (0 if test_head else _lib.RANKC_NO_HEAD) | (_lib.RANKC_TYPED if type_constrained else 0) |
+                (_lib.RANKC_FILTERED if filtered else 0))
+
+    def _check_sampled(self, what, n_candidates):
+        if int(n_candidates) < 0 or int(n_candidates) >= 2 ** 31:
+            raise KgeError("%s: n_candidates must be in [0, 2^31), got %d" % (what, n_candidates))
+
+    def rank_triples_sampled(self, h, t, r, n_candidates, seed=0, test_head=True, type_constrained=False, filtered=True):
+        """rank_candidates against n_candidates entities per (triple, side) that the device draws from a counter hash of (seed,
+        triple index, side, position) -- sampled_candidates returns the very ids -- so no list exists in memory.  With
+        type_constrained=True they come from the relation's tail / head type list (a relation without one: from all entities;
+        needs the type lists).  test_head=False ranks the tail side only.  Returns (counts int64 [n, 2, 2], metrics) as
+        rank_candidates does; the same seed gives the same lists on every call."""
+        import torch
+        self._refuse_sharded_candidates("rank_triples_sampled")
+        self._check_sampled("rank_triples_sampled", n_candidates)
+        host = np.stack([np.asarray(h).reshape(-1), np.asarray(t).reshape(-1), np.asarray(r).reshape(-1)]).astype(np.int32)
+        self._check_ids(host)
+        counts = self._rank_candidates_device(torch.from_numpy(host).to(self.device), None, None, int(n_candidates),
+                                              self._sampled_flags(test_head, type_constrained, filtered), seed)
+        return counts, self._lp_normalise(self._cand_sums(counts, (0, 1) if test_head else (0,)), host.shape[1])
+
+    def rank_triples_sampled_distributed(self, h, t, r, n_candidates, seed=0, test_head=True, type_constrained=False, filtered=True):
+        """rank_triples_sampled as a collective on replicated tables: every rank passes the same arguments, rank g ranks the g-th
+        contiguous slice of the triples and one SUM all-reduce merges the slices.  The hash is indexed by the global triple index,
+        so the counts are those of one process.  Invalid arguments on any rank, or arguments differing between ranks, raise
+        KgeError on every rank.  With one process and no process group it is rank_triples_sampled."""
+        import torch
+        import torch.distributed as dist
+        self._refuse_sharded_candidates("rank_triples_sampled_distributed")
+        if self.world_size <= 1:
+            return self.rank_triples_sampled(h, t, r, n_candidates, seed, test_head, type_constrained, filtered)
+        err, dev, n, flags = None, None, -1, 0
+        try:
+            self._check_sampled("rank_triples_sampled_distributed", n_candidates)
+            host = np.stack([np.asarray(h).reshape(-1), np.asarray(t).reshape(-1), np.asarray(r).reshape(-1)]).astype(np.int32)
+            self._check_ids(host)
+            dev = torch.from_numpy(np.ascontiguousarray(host)).to(self.device)
+            n, flags = host.shape[1], self._sampled_flags(test_head, type_constrained, filtered)
+            self._rank_candidates_device(dev[:, :0], None, None, int(n_candidates), flags, seed)       # the arguments and the files, no launch
+        except (KgeError, ValueError, TypeError, OverflowError) as e:
+            err, n = e, -1
+        shard_eval.agree(self, "rank_triples_sampled_distributed", err, (n, flags, int(n_candidates) if err is None else 0, int(seed) & (2 ** 62 - 1) if err is None else 0),
+                         [1, 2, 3, 4], "triples, candidate counts, seeds or flags", 0, where="")
+        counts = torch.zeros((max(n, 1), 2, 2), dtype=torch.int64, device=self.device)
+        per = (n + self.world_size - 1) // self.world_size
+        c0, c1 = min(self.rank * per, n), min((self.rank + 1) * per, n)
+        if c1 > c0:
+            self._rank_candidates_device(dev[:, c0:c1].contiguous(), None, None, int(n_candidates), flags, seed, first=c0, into=counts[c0:c1])
+        shard_eval.all_reduce(self, counts, dist.ReduceOp.SUM)
+        counts = counts[:n].cpu().numpy()
+        return counts, self._lp_normalise(self._cand_sums(counts, (0, 1) if test_head else (0,)), n)
+
+    def sampled_candidates(self, n, n_candidates, seed, side, r=None, type_constrained=False):
+        """The ids rank_triples_sampled draws for `side` (0: tail lists, 1: head lists) of triples 0 .. n-1, restated in numpy:
+        int64 [n, n_candidates].  With type_constrained=True `r` (the n relation ids) is needed: the ids come from the engine's
+        tail / head type list of each triple's relation (type_constraints()), from all entities where that list is empty."""
+        if side not in (0, 1):
+            raise KgeError("sampled_candidates: side must be 0 (tail) or 1 (head)")
+        i = np.arange(int(n), dtype=np.int64)[:, None]
+        k = np.arange(int(n_candidates), dtype=np.int64)[None, :]
+        ids = _lib.drawn_candidate_index(seed, i, side, k, self.entTotal)
+        if type_constrained:
+            if r is None:
+                raise KgeError("sampled_candidates: type_constrained=True needs the triples' relation ids")
+            r = np.asarray(r, dtype=np.int64).reshape(-1)
+            if len(r) != int(n):
+                raise KgeError("sampled_candidates: r must hold n = %d relation ids" % int(n))
+            head_off, head_ids, tail_off, tail_ids = self.type_constraints()
+            off, lst = (head_off, head_ids) if side else (tail_off, tail_ids)
+            lo, length = off[r][:, None], (off[r + 1] - off[r])[:, None]
+            typed = _lib.drawn_candidate_index(seed, i, side, k, np.maximum(length, 1))
+            ids = np.where(length > 0, lst[np.minimum(lo + typed, max(len(lst) - 1, 0))] if len(lst) else ids, ids)
+        return ids
+
     def _valid_positives(self):
         """The triples of valid2id.txt in file order, int32 [3, V] (h, t, r), read once."""
         if getattr(self, "_valid_pos", None) is None:
@@ -1543,11 +1702,22 @@ class Config(object):
             self._valid_pos = np.asarray(tok[1:1 + 3 * total], dtype=np.int64).reshape(total, 3).T.astype(np.int32)   # on disk: head, tail, relation
         return self._valid_pos
 
-    def validation_link_prediction(self, test_head=True, sample=0):
+    def validation_link_prediction(self, test_head=True, sample=0, candidates=0, seed=0, type_constrained=False):
         """rank_triples on the positives of valid2id.txt (read from in_path in file order; getValidBatch is not used, so the
         libc rand() sequence does not move): (counts, metrics) as rank_triples returns them -- filtered Hits@10 and MRR on the
         validation split for model selection.  sample = N > 0 ranks the N triples at the indices floor(i V / N), i < N (all
-        of them when N >= V); one check scores V x E pairs per side otherwise.  The device ids are kept between calls."""
+        of them when N >= V); one check scores V x E pairs per side otherwise.  The device ids are kept between calls.
+        candidates = C > 0 ranks the chosen triples against C drawn candidates per side instead of every entity
+        (rank_triples_sampled with `seed`, from the type lists with type_constrained=True): (counts int64 [n, 2, 2], metrics) as
+        rank_triples_sampled returns them, V x C pairs per side."""
+        if int(candidates) < 0:
+            raise KgeError("validation_link_prediction: candidates must be >= 0, got %d" % candidates)
+        if int(candidates) > 0:
+            self._refuse_sharded_candidates("validation_link_prediction(candidates=%d)" % candidates)
+            self._check_sampled("validation_link_prediction", candidates)
+            dev = self._valid_rank_ids(sample, "validation_link_prediction")
+            counts = self._rank_candidates_device(dev, None, None, int(candidates), self._sampled_flags(test_head, type_constrained, True), seed)
+            return counts, self._lp_normalise(self._cand_sums(counts, (0, 1) if test_head else (0,)), counts.shape[0])
         self._refuse_sharded_rank("validation_link_prediction")
         counts = self._rank_device(self._valid_rank_ids(sample, "validation_link_prediction"), test_head)
         return counts, self._lp_normalise(self._lp_sums(counts, test_head), counts.shape[0])

@@ -15,6 +15,21 @@ NO_EVENT = 1   # kge_stream_wait_emit: nothing was recorded since the previous w
 KGE_MAX_TABLES = 4
 TOPK_FILTERED, TOPK_TYPED = 1, 2   # kge_topk_entities flags (include/kge_mi355.h KGE_TOPK_*)
 TOPK_MAX_K = 1024
+RANKC_FILTERED, RANKC_DRAWN, RANKC_TYPED, RANKC_NO_HEAD = 1, 2, 4, 8   # kge_rank_candidates flags (include/kge_mi355.h KGE_RANKC_*)
+
+
+def drawn_candidate_index(seed, triple, side, k, length):
+    """The index kge_rank_candidates draws for candidate k of (triple, side) into a list of `length` entries (the formula of
+    include/kge_mi355.h, in numpy uint64; the arguments broadcast) -> int64."""
+    import numpy as np
+    with np.errstate(over="ignore"):
+        u = np.uint64
+        c = ((np.asarray(triple, dtype=u) * u(2) + np.asarray(side, dtype=u)) << u(32)) | np.asarray(k, dtype=u)
+        z = u(int(seed) & 0xFFFFFFFFFFFFFFFF) + (c + u(1)) * u(0x9E3779B97F4A7C15)
+        z = (z ^ (z >> u(30))) * u(0xBF58476D1CE4E5B9)
+        z = (z ^ (z >> u(27))) * u(0x94D049BB133111EB)
+        z = z ^ (z >> u(31))
+        return (((z >> u(32)) * np.asarray(length, dtype=u)) >> u(32)).astype(np.int64)
 
 
 class KgeError(RuntimeError):
@@ -117,6 +132,7 @@ def _declare(L):
     L.kge_adam_update_tables.argtypes = [i32, vp, vp, vp, vp, vp, f32, f32, f32, f32, vp]
     L.kge_predict.argtypes = [ctypes.POINTER(ModelDesc), tabs, vp, vp, vp, i64, vp, vp]
     L.kge_rank_triples.argtypes = [ctypes.POINTER(ModelDesc), tabs, vp, vp, vp, i64, i64, vp, vp]
+    L.kge_rank_candidates.argtypes = [ctypes.POINTER(ModelDesc), tabs, vp, vp, vp, i64, vp, i64, vp, i64, i64, i64, ctypes.c_uint64, vp, vp]
     L.kge_topk_entities.argtypes = [ctypes.POINTER(ModelDesc), tabs, vp, vp, vp, i64, i64, i64, vp, vp, vp]
     L.kge_topk_entities_range.argtypes = [ctypes.POINTER(ModelDesc), tabs, i64, i64, vp, vp, vp, vp, i64, i64, i64, vp, vp]
     L.kge_topk_merge_keys.argtypes = [vp, i64, i64, i64, vp, vp, vp]

@@ -281,6 +281,8 @@ int kge_set_option(const char *name, INT value) {
     if (n == "relpred_chunk_bytes") { engine().relpred_chunk_bytes = value; return KGE_OK; }
     if (n == "lp_v1") { engine().lp_v1 = value != 0; return KGE_OK; }
     if (n == "rank_slices") { engine().rank_slices = value > 0 ? (int)value : 0; return KGE_OK; }
+    if (n == "rankc_slices") { engine().rankc_slices = value > 0 ? (int)value : 0; return KGE_OK; }
+    if (n == "rankc_fused") { engine().rankc_fused = value != 0; return KGE_OK; }
     if (n == "transr_v1") { engine().transr_v1 = (int)value; return KGE_OK; }
     if (n == "time_emit") { engine().time_emit = value > 0 ? (int)value : 0; if (value > 0) { engine().emit_launches = 0; engine().emit_seen = 0; } return KGE_OK; }
     if (n == "time_sampler") { engine().time_sampler = value > 0 ? (int)value : 0; if (value > 0) { engine().samp_launches = 0; engine().samp_seen = 0; } return KGE_OK; }

@@ -101,6 +101,8 @@ struct Engine {
     int64_t relpred_chunk_bytes = int64_t(256) << 20;  // kge_topk_relations / kge_relation_prediction: [queries x R] fp32 score block per chunk (TransR: also its projection buffer)
     int lp_v1 = 0;              // test hook: link prediction through the generic predict kernel on materialised candidate batches
     int rank_slices = 0;        // test hook: kge_rank_triples cuts the candidates into this many slices (0 = automatic)
+    int rankc_slices = 0;       // test hook: kge_rank_candidates cuts each candidate list into this many slices (0 = automatic)
+    int rankc_fused = 1;        // kge_rank_candidates: 1 = the fused kernel (TransE / TransH / TransD), 0 = the two-stage form for every model (A/B runs, test reference)
     int transr_v1 = 0;          // test hook: 1 = the 32x32x2 / 32-row-tile TransR kernels even where the v2 tiles apply; 2 = v2 with its all-tiles wgrad forced
     int fb_occ4 = 1;            // projecting models at <= 4 elements per lane: the forward/backward body compiled for four waves per SIMD
     int persist_ahead = 1;      // persistent launch: idle teams sample the next batch during the forward/backward phase
@@ -226,6 +228,10 @@ int launch_forward_backward(const kge_model_desc &m, const float *const tables[4
                             const RowRule *inplace_adam = nullptr);
 int launch_predict(const kge_model_desc &m, const float *const tables[4], const int32_t *d_h, const int32_t *d_t,
                    const int32_t *d_r, int64_t n, float *d_out, hipStream_t stream);
+// TransR kge_predict with each triple's OWN relation matrix, for callers whose triples come in aligned groups of 16 sharing one
+// relation (a group is one 32-row tile of the projection; transr.hip)
+int launch_predict_transr_grouped(const kge_model_desc &m, const float *const tables[4], const int32_t *d_h, const int32_t *d_t,
+                                  const int32_t *d_r, int64_t n, float *d_out, hipStream_t stream);
 int launch_lp_table(const kge_model_desc &m, const float *const tables[4], const float *P_all, int64_t r, float *T, hipStream_t stream);
 int launch_lp_scores(const kge_model_desc &m, const float *const tables[4], const float *T, int64_t r, const int32_t *d_req_fixed,
                      const int32_t *d_req_head, int64_t n_req, float *d_scores, hipStream_t stream);

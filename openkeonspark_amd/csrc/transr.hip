@@ -1774,6 +1774,45 @@ int launch_predict_transr(const kge_model_desc &m, const float *const tables[4],
     return launch_transr_predict_stage(tables[1], g_w.P, d_r, n, Dr, d_out, stream);
 }
 
+// predict with each triple's OWN matrix, for triples that come in aligned groups of 16 sharing one relation: a group's 32
+// slots are one tile, and the tile's relation is its first triple's.  bucket_start only bounds the last tile here.
+__global__ void predict_grouped_prep_kernel(const int32_t *__restrict__ bh, const int32_t *__restrict__ bt, const int32_t *__restrict__ br,
+                                            long long n, int R, int32_t *__restrict__ vals, int32_t *__restrict__ job_ent,
+                                            int32_t *__restrict__ bucket_start, int32_t *__restrict__ tile_rel,
+                                            int32_t *__restrict__ tile_row0, int32_t *__restrict__ n_tiles) {
+    const long long total = 2 * n;
+    for (long long slot = (long long)blockIdx.x * blockDim.x + threadIdx.x; slot < total; slot += (long long)gridDim.x * blockDim.x) {
+        vals[slot] = (int32_t)slot;
+        job_ent[slot] = (slot & 1) ? bt[slot >> 1] : bh[slot >> 1];
+        if ((slot & 31) == 0) { tile_rel[slot >> 5] = br[slot >> 1]; tile_row0[slot >> 5] = (int32_t)slot; }
+    }
+    if (blockIdx.x == 0) {
+        for (int r = threadIdx.x; r <= R + 1; r += blockDim.x) bucket_start[r] = r == 0 ? 0 : (int32_t)total;
+        if (threadIdx.x == 0) n_tiles[0] = (int)((total + 31) >> 5);
+    }
+}
+
+int launch_predict_transr_grouped(const kge_model_desc &m, const float *const tables[4], const int32_t *d_h, const int32_t *d_t,
+                                  const int32_t *d_r, int64_t n, float *d_out, hipStream_t stream) {
+    const int De = m.ent_dim, Dr = m.rel_dim;
+    const int64_t R = m.rel_total, slots = 2 * n;
+    if (n <= 0) return KGE_OK;
+    int rc = ensure_work(slots, Dr, R);
+    if (rc) return rc;
+    int blocks = (int)((slots + 255) / 256);
+    if (blocks > 4096) blocks = 4096;
+    hipLaunchKernelGGL(predict_grouped_prep_kernel, dim3(blocks), dim3(256), 0, stream, d_h, d_t, d_r, (long long)n, (int)R, g_w.vals2,
+                       g_w.job_ent, g_w.bucket_start, g_w.tile_rel, g_w.tile_row0, g_w.n_tiles);
+    GemmArgs ga = {};
+    ga.ent = tables[0]; ga.mat = tables[2]; ga.P = g_w.P;
+    ga.sorted_slots = g_w.vals2; ga.job_ent = g_w.job_ent; ga.bucket_start = g_w.bucket_start;
+    ga.tile_rel = g_w.tile_rel; ga.tile_row0 = g_w.tile_row0; ga.n_tiles = g_w.n_tiles;
+    ga.De = De; ga.Dr = Dr;
+    hipLaunchKernelGGL((rows_gemm_kernel<GEMM_PROJECT>), dim3((unsigned)((slots + 31) / 32), (Dr + TN - 1) / TN), dim3(256), 0,
+                       stream, ga);
+    return launch_transr_predict_stage(tables[1], g_w.P, d_r, n, Dr, d_out, stream);
+}
+
 // link prediction: P_out[j] = ent[j] . M_r for EVERY entity j (one relation bucket holding all E rows)
 namespace {
 __global__ void project_all_prep_kernel(long long E, int r0, int R, int32_t *__restrict__ vals, int32_t *__restrict__ job_ent,

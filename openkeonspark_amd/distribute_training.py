@@ -72,12 +72,21 @@ def parse_args(argv=None):
                    help="what an early-stop check measures on the validation split: accuracy = triple classification (the default), "
                         "hits10 / mrr = filtered Hits@10 / mean reciprocal rank of the validation triples (tail side; head side too with "
                         "--test_head 1), higher is better.  A ranking check scores every validation triple against every entity -- on a "
-                        "large graph several training epochs of GPU time -- so rank a sample with --early_stop_rank_triples and / or "
-                        "check less often with --early_stop_stopping_step.  With an entity table sharded across ranks "
+                        "large graph several training epochs of GPU time -- so rank against a drawn candidate list with "
+                        "--early_stop_candidates (cost: triples x candidates instead of triples x entities), rank a sample of the "
+                        "triples with --early_stop_rank_triples and / or check less often with --early_stop_stopping_step.  With an "
+                        "entity table sharded across ranks "
                         "(--sparse_rows 1 on N ranks, TransE) the check is a collective: every rank ranks the triples against its own "
                         "rows and the counts are all-reduced, so every rank takes the same decision")
     p.add_argument("--early_stop_rank_triples", type=int, default=0,
                    help="hits10 / mrr: rank only this many validation triples, evenly spaced through valid2id.txt (0 = all of them)")
+    p.add_argument("--early_stop_candidates", type=int, default=0,
+                   help="hits10 / mrr: rank every chosen validation triple against this many candidates per side, drawn on the device "
+                        "from a counter hash (Config.rank_triples_sampled; from the relation's type lists with "
+                        "--type_constrained_sampling 1), instead of against every entity (0, the default).  Not with an entity table "
+                        "sharded across ranks")
+    p.add_argument("--early_stop_candidates_seed", type=int, default=0,
+                   help="seed of the drawn candidates; the same for every check of a run, so that successive checks are comparable")
     p.add_argument("--model", type=str, default="TransE")
     p.add_argument("--debug", type=int, default=0)
     p.add_argument("--mode", type=str, default="train")
@@ -475,10 +484,14 @@ def _validation_rank_metric(con, argv):
     With a sharded entity table it is the collective Config.validation_link_prediction_distributed: every rank reaches the
     check at the same global step and receives the same all-reduced counts, so the decisions agree without a broadcast."""
     test_head = bool(argv.test_head)
-    rank_valid = con.validation_link_prediction_distributed if con._sharded("ent_embeddings") else con.validation_link_prediction
-    metrics = rank_valid(test_head=test_head, sample=argv.early_stop_rank_triples)[1]
     name = "_filter_tot" if argv.early_stop_metric == "hits10" else "_filter_reci_rank"
     sides = ("r", "l") if test_head else ("r",)
+    if argv.early_stop_candidates > 0:      # drawn candidate lists: replicated tables only (refused before step 0 otherwise)
+        metrics = con.validation_link_prediction(test_head=test_head, sample=argv.early_stop_rank_triples, candidates=argv.early_stop_candidates,
+                                                 seed=argv.early_stop_candidates_seed, type_constrained=bool(argv.type_constrained_sampling))[1]
+        return sum(metrics[p + name] for p in sides) / len(sides)
+    rank_valid = con.validation_link_prediction_distributed if con._sharded("ent_embeddings") else con.validation_link_prediction
+    metrics = rank_valid(test_head=test_head, sample=argv.early_stop_rank_triples)[1]
     return sum(metrics[p + name] for p in sides) / len(sides)
 
 
@@ -537,6 +550,11 @@ def main_fun(argv):
         return metrics
 
     metric = argv.early_stop_metric
+    if argv.early_stop_candidates < 0:
+        raise KgeError("--early_stop_candidates must be >= 0, got %d" % argv.early_stop_candidates)
+    if metric != "accuracy" and argv.early_stop_candidates > 0 and con._sharded("ent_embeddings"):      # before step 0
+        raise KgeError("--early_stop_candidates over an entity table sharded across ranks is not supported (Config.rank_triples_sampled "
+                       "refuses it): rank against every entity (--early_stop_candidates 0), a collective on sharded tables")
     valid = _init_validation(con, argv) if metric == "accuracy" else _init_rank_validation(con)
     best_acc, wait_steps_acc, best_step_acc = -1.0, 0, last_global_step
     iterations = con.train_times * con.nbatches + last_global_step      # distribute_training.py:205
