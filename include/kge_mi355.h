@@ -779,6 +779,27 @@ int kge_rank_triples(const kge_model_desc *m, const float *const tables[KGE_MAX_
 int kge_rank_candidates(const kge_model_desc *m, const float *const tables[KGE_MAX_TABLES], const int32_t *d_h, const int32_t *d_t,
                         const int32_t *d_r, INT n, const int32_t *d_tail_cand, INT tail_stride, const int32_t *d_head_cand,
                         INT head_stride, INT n_cand, INT flags, uint64_t seed, int64_t *d_counts, void *stream);
+/* kge_rank_candidates against a ROW RANGE of the entity table (a table sharded by rows across ranks; the RANGE form of the fused
+ * kernel in csrc/rank_cand.hip).  tables[0] holds rows [row_lo, row_lo+rows) of the entity table (row j = entity row_lo+j),
+ * tables[1] the whole relation table, and d_query_rows (DEVICE fp32 [n][2][ent_dim], kge_rank_triples_range's layout) the raw h
+ * and t row of each triple, which may lie outside the range.  Triples, lists, strides, flags, seed and the drawn ids are
+ * kge_rank_candidates'; ent_total stays the GLOBAL entity count (it bounds the listed ids and scales the drawn ones).
+ * d_counts (DEVICE int64 [n][2][2], every element written): kge_rank_candidates' two columns over the candidates whose global id
+ * lies in the range.  A candidate outside it is neither gathered nor counted; the target is excluded by its global id.  The true
+ * triple's score is formed from d_query_rows by the very operations kge_rank_candidates applies to the table's rows, so every
+ * range compares against the same score bits, and the SUM of d_counts over any cut of [0, ent_total) into ranges equals
+ * kge_rank_candidates on the whole table, bit for bit.  Work follows the candidates the range owns: a team compacts the owned
+ * ids of each batch into a pending queue and gathers rows U at a time from it, at most owned + U - 1 rows per (request, slice).
+ * A triple with an id out of range is disabled as in kge_rank_candidates (zero counts; its query rows are not read).
+ * rows == 0 only zeroes d_counts; n == 0 or n_cand == 0 checks the arguments and the files, zeroes d_counts and launches
+ * nothing.  No host synchronisation; option "rankc_slices" applies; there is no two-stage form.
+ * KGE_ERR_UNSUPPORTED: a model other than TransE, ent_dim above 1024; KGE_ERR_BAD_ARG: what kge_rank_candidates refuses, a range
+ * outside the table, null d_query_rows with n > 0; KGE_ERR_NO_DATASET as kge_rank_candidates.  Nothing is written to d_counts
+ * when an error is returned. */
+int kge_rank_candidates_range(const kge_model_desc *m, const float *const tables[KGE_MAX_TABLES], INT row_lo, INT rows,
+                              const float *d_query_rows, const int32_t *d_h, const int32_t *d_t, const int32_t *d_r, INT n,
+                              const int32_t *d_tail_cand, INT tail_stride, const int32_t *d_head_cand, INT head_stride,
+                              INT n_cand, INT flags, uint64_t seed, int64_t *d_counts, void *stream);
 
 /* Batched top-k entity prediction on the device.  Query i: d_head[i] == 0 asks for the k best tails of (d_fixed[i], d_rel[i], ?),
  * d_head[i] != 0 for the k best heads of (?, d_rel[i], d_fixed[i]); sides and relations may be mixed in any order.  d_ids /

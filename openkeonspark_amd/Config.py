@@ -1546,9 +1546,9 @@ class Config(object):
     # candidate lists instead of every entity (kge_rank_candidates) ------------------------------------------------------------
     def _refuse_sharded_candidates(self, what):
         if self._sharded("ent_embeddings"):
-            raise KgeError("%s over an entity table sharded across ranks is not supported: candidate lists are ranked against "
-                           "replicated tables only (rank against every entity with rank_triples_distributed, a collective on "
-                           "sharded tables)" % what)
+            raise KgeError("%s over an entity table sharded across ranks is not supported: call one of the collectives "
+                           "rank_candidates_distributed, rank_triples_sampled_distributed or "
+                           "validation_link_prediction_distributed(candidates=C) on every rank" % what)
 
     def _candidate_list(self, cand, n, name):
         """A candidate array ([n, C] or [C]; numpy / list / torch tensor on any device) -> (int32 device tensor, C, stride)."""
@@ -1615,6 +1615,58 @@ class Config(object):
         sides = [s for s, x in ((0, tail), (1, head)) if x is not None]
         return counts, self._lp_normalise(self._cand_sums(counts, sides), n)
 
+    def rank_candidates_distributed(self, h, t, r, tail_candidates=None, head_candidates=None, filtered=True):
+        """rank_candidates as a collective: every rank passes the same arguments and gets the same (counts int64 [n, 2, 2],
+        metrics).  Invalid arguments on any rank, or arguments differing between ranks, raise KgeError on every rank.
+        On an entity table sharded across ranks (TransE) every rank ranks the triples against the listed candidates whose rows it
+        owns (kge_rank_candidates_range), in rounds of lp_shard_query_bytes // (2 D 4) triples whose h and t rows come from their
+        owners, and one SUM all-reduce merges the counts: bit for bit rank_candidates' counts over the whole table.
+        On replicated tables rank g ranks the g-th contiguous slice of the triples and one SUM all-reduce merges the slices.
+        With one process and no process group it is rank_candidates."""
+        import torch
+        import torch.distributed as dist
+        sharded = self._sharded("ent_embeddings")
+        if sharded and not dist.is_initialized():
+            raise KgeError("rank_candidates_distributed over an entity table sharded across ranks needs the process group it was sharded over")
+        if not sharded and self.world_size <= 1:
+            return self.rank_candidates(h, t, r, tail_candidates, head_candidates, filtered)
+        what = "rank_candidates_distributed"
+        err, dev, tail, head, n, n_cand, sides = None, None, None, None, -1, 0, []
+        flags = _lib.RANKC_FILTERED if filtered else 0
+        try:
+            host = np.stack([np.asarray(h).reshape(-1), np.asarray(t).reshape(-1), np.asarray(r).reshape(-1)]).astype(np.int32)
+            self._check_ids(host)
+            n = host.shape[1]
+            if tail_candidates is None and head_candidates is None:
+                raise KgeError("%s: give tail_candidates, head_candidates or both" % what)
+            tail = None if tail_candidates is None else self._candidate_list(tail_candidates, n, "tail_candidates")
+            head = None if head_candidates is None else self._candidate_list(head_candidates, n, "head_candidates")
+            if tail is not None and head is not None and tail[1] != head[1]:
+                raise KgeError("%s: both lists must have the same number of candidates, got %d and %d" % (what, tail[1], head[1]))
+            n_cand = (tail or head)[1]
+            tail, head = tail and (tail[0], tail[2]), head and (head[0], head[2])
+            sides = [s for s, x in ((0, tail), (1, head)) if x is not None]
+            dev = torch.from_numpy(np.ascontiguousarray(host)).to(self.device)
+            if not sharded:
+                self._rank_candidates_device(dev[:, :0], tail, head, n_cand, flags, 0)       # the arguments and the files, no launch
+        except (KgeError, ValueError, TypeError, OverflowError) as e:
+            err, n = e, -1
+        if sharded:
+            counts = shard_eval.rank_candidates(self, dev, err, tail, head, n_cand, flags, 0, what)
+        else:
+            strides = [x[1] if x is not None else -1 for x in (tail, head)]
+            shard_eval.agree(self, what, err, (n, flags, n_cand if err is None else 0, strides[0], strides[1]), [1, 2, 3, 4, 5],
+                             "triples, candidate counts, lists or flags", 0, where="")
+            counts = torch.zeros((max(n, 1), 2, 2), dtype=torch.int64, device=self.device)
+            per = (n + self.world_size - 1) // self.world_size
+            c0, c1 = min(self.rank * per, n), min((self.rank + 1) * per, n)
+            if c1 > c0:      # a per-triple list starts at this slice's first triple; a shared list (stride 0) is whole
+                part = [x and ((x[0][c0:c1] if x[1] else x[0]), x[1]) for x in (tail, head)]
+                self._rank_candidates_device(dev[:, c0:c1].contiguous(), part[0], part[1], n_cand, flags, 0, into=counts[c0:c1])
+            shard_eval.all_reduce(self, counts, dist.ReduceOp.SUM)
+            counts = counts[:n].cpu().numpy()
+        return counts, self._lp_normalise(self._cand_sums(counts, sides), n)
+
     @staticmethod
     def _sampled_flags(test_head, type_constrained, filtered):
         return (_lib.RANKC_DRAWN | (0 if test_head else _lib.RANKC_NO_HEAD) | (_lib.RANKC_TYPED if type_constrained else 0) |
@@ -1640,26 +1692,38 @@ class Config(object):
         return counts, self._lp_normalise(self._cand_sums(counts, (0, 1) if test_head else (0,)), host.shape[1])
 
     def rank_triples_sampled_distributed(self, h, t, r, n_candidates, seed=0, test_head=True, type_constrained=False, filtered=True):
-        """rank_triples_sampled as a collective on replicated tables: every rank passes the same arguments, rank g ranks the g-th
-        contiguous slice of the triples and one SUM all-reduce merges the slices.  The hash is indexed by the global triple index,
+        """rank_triples_sampled as a collective: every rank passes the same arguments.  On replicated tables rank g ranks the g-th
+        contiguous slice of the triples and one SUM all-reduce merges the slices.  On an entity table sharded across ranks
+        (TransE) every rank draws every list and ranks the candidates whose rows it owns (kge_rank_candidates_range), as
+        rank_candidates_distributed does.  The hash is indexed by the global triple index,
         so the counts are those of one process.  Invalid arguments on any rank, or arguments differing between ranks, raise
         KgeError on every rank.  With one process and no process group it is rank_triples_sampled."""
-        import torch
         import torch.distributed as dist
-        self._refuse_sharded_candidates("rank_triples_sampled_distributed")
+        sharded = self._sharded("ent_embeddings")
+        if sharded and not dist.is_initialized():      # no process group, so no other rank can be waiting for this one
+            raise KgeError("rank_triples_sampled_distributed over an entity table sharded across ranks needs the process group it was sharded over")
+        if sharded:
+            return self._rank_sampled_sharded("rank_triples_sampled_distributed", lambda: self._triple_ids(h, t, r), n_candidates, seed,
+                                              test_head, type_constrained, filtered)
         if self.world_size <= 1:
             return self.rank_triples_sampled(h, t, r, n_candidates, seed, test_head, type_constrained, filtered)
+        return self._rank_sampled_replicated("rank_triples_sampled_distributed", lambda: self._triple_ids(h, t, r), n_candidates, seed,
+                                             test_head, type_constrained, filtered)
+
+    def _rank_sampled_replicated(self, what, triples, n_candidates, seed, test_head, type_constrained, filtered):
+        """Drawn candidate lists on replicated tables, more than one rank: slices of the triples, one SUM all-reduce.  `triples`
+        returns the checked int32 device tensor [3, n]."""
+        import torch
+        import torch.distributed as dist
         err, dev, n, flags = None, None, -1, 0
         try:
-            self._check_sampled("rank_triples_sampled_distributed", n_candidates)
-            host = np.stack([np.asarray(h).reshape(-1), np.asarray(t).reshape(-1), np.asarray(r).reshape(-1)]).astype(np.int32)
-            self._check_ids(host)
-            dev = torch.from_numpy(np.ascontiguousarray(host)).to(self.device)
-            n, flags = host.shape[1], self._sampled_flags(test_head, type_constrained, filtered)
+            self._check_sampled(what, n_candidates)
+            dev = triples()
+            n, flags = int(dev.shape[1]), self._sampled_flags(test_head, type_constrained, filtered)
             self._rank_candidates_device(dev[:, :0], None, None, int(n_candidates), flags, seed)       # the arguments and the files, no launch
-        except (KgeError, ValueError, TypeError, OverflowError) as e:
+        except (KgeError, ValueError, TypeError, OverflowError, OSError) as e:
             err, n = e, -1
-        shard_eval.agree(self, "rank_triples_sampled_distributed", err, (n, flags, int(n_candidates) if err is None else 0, int(seed) & (2 ** 62 - 1) if err is None else 0),
+        shard_eval.agree(self, what, err, (n, flags, int(n_candidates) if err is None else 0, int(seed) & (2 ** 62 - 1) if err is None else 0),
                          [1, 2, 3, 4], "triples, candidate counts, seeds or flags", 0, where="")
         counts = torch.zeros((max(n, 1), 2, 2), dtype=torch.int64, device=self.device)
         per = (n + self.world_size - 1) // self.world_size
@@ -1669,6 +1733,27 @@ class Config(object):
         shard_eval.all_reduce(self, counts, dist.ReduceOp.SUM)
         counts = counts[:n].cpu().numpy()
         return counts, self._lp_normalise(self._cand_sums(counts, (0, 1) if test_head else (0,)), n)
+
+    def _triple_ids(self, h, t, r):
+        """h, t, r as a checked int32 device tensor [3, n]."""
+        import torch
+        host = np.stack([np.asarray(h).reshape(-1), np.asarray(t).reshape(-1), np.asarray(r).reshape(-1)]).astype(np.int32)
+        self._check_ids(host)
+        return torch.from_numpy(np.ascontiguousarray(host)).to(self.device)
+
+    def _rank_sampled_sharded(self, what, triples, n_candidates, seed, test_head, type_constrained, filtered):
+        """Drawn candidate lists over a sharded entity table (shard_eval.rank_candidates): `triples` returns the checked int32
+        device tensor [3, n]; whatever it or the argument check raises on this rank is raised on every rank."""
+        err, dev, flags = None, None, 0
+        try:
+            self._check_sampled(what, n_candidates)
+            flags = self._sampled_flags(test_head, type_constrained, filtered)
+            seed = int(seed)
+            dev = triples()
+        except (KgeError, ValueError, TypeError, OverflowError, OSError) as e:
+            err = e
+        counts = shard_eval.rank_candidates(self, dev, err, None, None, n_candidates, flags, seed, what)
+        return counts, self._lp_normalise(self._cand_sums(counts, (0, 1) if test_head else (0,)), counts.shape[0])
 
     def sampled_candidates(self, n, n_candidates, seed, side, r=None, type_constrained=False):
         """The ids rank_triples_sampled draws for `side` (0: tail lists, 1: head lists) of triples 0 .. n-1, restated in numpy:
@@ -1742,13 +1827,35 @@ class Config(object):
             cached = self._valid_rank_dev = (sample, torch.from_numpy(host).to(self.device))
         return cached[1]
 
-    def validation_link_prediction_distributed(self, test_head=True, sample=0):
+    def validation_link_prediction_distributed(self, test_head=True, sample=0, candidates=0, seed=0, type_constrained=False):
         """validation_link_prediction as a collective, ranked as rank_triples_distributed ranks (sharded or replicated
         tables; its near-tie caveat on a sharded table applies): the same valid2id.txt positives, the same `sample` rule and
         the same cached device ids; every rank calls it with the same arguments and gets the same (counts, metrics).  A bad
-        `sample` or an unreadable valid2id.txt on any rank raises KgeError on every rank."""
-        if not self._sharded("ent_embeddings") and self.world_size <= 1:
-            return self.validation_link_prediction(test_head, sample)
+        `sample` or an unreadable valid2id.txt on any rank raises KgeError on every rank.
+        candidates = C > 0 ranks against C drawn candidates per side as validation_link_prediction(candidates=C) does, with
+        rank_triples_sampled_distributed's split (sharded: every rank counts the candidates it owns; replicated: slices of the
+        triples): (counts int64 [n, 2, 2], metrics), exactly one process's counts.  A bad value on any rank raises on every rank."""
+        sharded = self._sharded("ent_embeddings")
+        if not sharded and self.world_size <= 1:
+            return self.validation_link_prediction(test_head, sample, candidates, seed, type_constrained)
+        cand = None
+        try:
+            cand = int(candidates)
+        except (ValueError, TypeError, OverflowError):
+            pass
+        if cand is None or cand != 0:
+            what = "validation_link_prediction_distributed"
+
+            def triples():
+                if cand is None or cand < 0:
+                    raise KgeError("%s: candidates must be an integer >= 0, got %r" % (what, candidates))
+                return self._valid_rank_ids(sample, what)
+            if sharded:
+                import torch.distributed as dist
+                if not dist.is_initialized():
+                    raise KgeError("%s over an entity table sharded across ranks needs the process group it was sharded over" % what)
+                return self._rank_sampled_sharded(what, triples, cand if cand is not None and cand > 0 else 0, seed, test_head, type_constrained, True)
+            return self._rank_sampled_replicated(what, triples, cand if cand is not None and cand > 0 else 0, seed, test_head, type_constrained, True)
         err, dev = None, None
         try:
             dev = self._valid_rank_ids(sample, "validation_link_prediction_distributed")

@@ -133,6 +133,8 @@ def _declare(L):
     L.kge_predict.argtypes = [ctypes.POINTER(ModelDesc), tabs, vp, vp, vp, i64, vp, vp]
     L.kge_rank_triples.argtypes = [ctypes.POINTER(ModelDesc), tabs, vp, vp, vp, i64, i64, vp, vp]
     L.kge_rank_candidates.argtypes = [ctypes.POINTER(ModelDesc), tabs, vp, vp, vp, i64, vp, i64, vp, i64, i64, i64, ctypes.c_uint64, vp, vp]
+    L.kge_rank_candidates_range.argtypes = [ctypes.POINTER(ModelDesc), tabs, i64, i64, vp, vp, vp, vp, i64, vp, i64, vp, i64, i64, i64,
+                                            ctypes.c_uint64, vp, vp]
     L.kge_topk_entities.argtypes = [ctypes.POINTER(ModelDesc), tabs, vp, vp, vp, i64, i64, i64, vp, vp, vp]
     L.kge_topk_entities_range.argtypes = [ctypes.POINTER(ModelDesc), tabs, i64, i64, vp, vp, vp, vp, i64, i64, i64, vp, vp]
     L.kge_topk_merge_keys.argtypes = [vp, i64, i64, i64, vp, vp, vp]

@@ -20,7 +20,11 @@
 // (triple, candidate) pairs are spelled out as id arrays in a bounded workspace, scored by launch_predict (TransR: groups of 16
 // pairs of one triple share a projection tile, so each pair is projected by its own relation's matrix) and compared with the
 // target's score by a small count kernel that does the same filter search.
+//
+// Row-range form (kge_rank_candidates_range; TransE, a table sharded by rows across ranks): the fused kernel's RANGE
+// instantiations rank against the candidates whose rows one shard holds; the comment on the kernel has the rest.
 #include <algorithm>
+#include <type_traits>
 
 #include "eval_dev.hpp"
 #include "models_dev.hpp"
@@ -57,6 +61,13 @@ __host__ __device__ inline long long drawn_index(unsigned long long seed, long l
     z ^= z >> 31;
     return (long long)(((z >> 32) * (unsigned long long)len) >> 32);
 }
+
+// The row-range form (kge_rank_candidates_range): `ent` holds the rows of the global ids [row_lo, row_lo + rows) only, and the
+// raw h and t row of triple i come from qrows [n][2][D] instead of the table.
+struct RankCandRangeArgs : RankCandArgs {
+    const float *qrows;
+    long long row_lo, rows;
+};
 
 // the id of candidate k of request (i, side), or -1: list entry, or drawn (MODE) from all entities / the relation's type list
 template <int MODE>
@@ -108,8 +119,12 @@ __device__ __forceinline__ float predict_score(const float (&hn)[C], const float
     return s;
 }
 
-template <int MODEL, int L, int C, int U, int MODE>
-__global__ __launch_bounds__(256) void rank_cand_kernel(RankCandArgs a) {
+// RANGE: the candidates with a global id in [row_lo, row_lo + rows) only, gathered at their local row.  Every team still
+// walks the whole list (the ids cost a load or a hash each), but gathers and scores what it owns: the owned ids of a batch are
+// compacted to the low lanes (a ballot masked to the team's own lanes, a prefix count, one ds_permute) behind the `p` ids left
+// pending from the batches before, rounds of U rows are drawn from that queue while it holds U, and the last round is padded.
+template <int MODEL, int L, int C, int U, int MODE, bool RANGE>
+__global__ __launch_bounds__(256) void rank_cand_kernel(std::conditional_t<RANGE, RankCandRangeArgs, RankCandArgs> a) {
     constexpr int TEAMS = 256 / L;
     static_assert(L % U == 0, "a batch of ids is handed out U at a time");
     Team<L, C> tm;
@@ -147,7 +162,8 @@ __global__ __launch_bounds__(256) void rank_cand_kernel(RankCandArgs a) {
     float fx[C], inv_f;
     {
         float raw[C], aux[C];
-        tm.load(a.ent, fixed, raw);
+        if constexpr (RANGE) tm.load(a.qrows, 2 * i + (hd ? 1 : 0), raw);
+        else tm.load(a.ent, fixed, raw);
         if constexpr (MODEL == KGE_TRANSD) tm.load(a.auxe, fixed, aux);
         project_row<MODEL, L, C>(tm, raw, aux, cw, fx, inv_f);
         if (!hd) {
@@ -169,7 +185,8 @@ __global__ __launch_bounds__(256) void rank_cand_kernel(RankCandArgs a) {
     float mn;
     {
         float raw[C], aux[C];
-        tm.load(a.ent, target, raw);
+        if constexpr (RANGE) tm.load(a.qrows, 2 * i + (hd ? 0 : 1), raw);
+        else tm.load(a.ent, target, raw);
         if constexpr (MODEL == KGE_TRANSD) tm.load(a.auxe, target, aux);
         mn = score(raw, aux);
     }
@@ -181,23 +198,19 @@ __global__ __launch_bounds__(256) void rank_cand_kernel(RankCandArgs a) {
     long long c0 = 0, c1 = 0;
     const long long k_lo = (long long)blockIdx.y * a.slice_len;
     const long long k_hi = min(a.n_cand, k_lo + a.slice_len);
-    for (long long k0 = k_lo; k0 < k_hi; k0 += L) {
-        const long long k = k0 + tm.lane;
-        const int mine = k < k_hi ? candidate_id<MODE>(a, i, side, r, k) : -1;
-        const int nk = (int)min((long long)L, k_hi - k0);
-        for (int j = 0; j < nk; j += U) {
-            int id[U];
-            float x[U][C], ax[U][C];
+    if constexpr (RANGE) {
+        static_assert(MODEL == KGE_TRANSE, "only TransE shards its entity table");
+        const int tbase = (threadIdx.x % 64) / L * L;                        // the team's first lane in its wave
+        const unsigned long long tmask = L == 64 ? ~0ULL : (1ULL << (L % 64)) - 1;
+        const long long r_lo = a.row_lo, r_hi = a.row_lo + a.rows;
+        // one round: U owned ids (global; -1 pads the last round and gathers local row 0), gathered, scored and counted
+        auto round = [&](const int (&id)[U]) {
+            float x[U][C];
+#pragma unroll
+            for (int u = 0; u < U; u++) tm.load(a.ent, id[u] >= 0 ? id[u] - r_lo : 0, x[u]);
 #pragma unroll
             for (int u = 0; u < U; u++) {
-                id[u] = team_bcast<L>(mine, j + u);
-                const long long row = id[u] >= 0 ? id[u] : 0;   // a skipped id still loads a row: no branch around the gathers
-                tm.load(a.ent, row, x[u]);
-                if constexpr (MODEL == KGE_TRANSD) tm.load(a.auxe, row, ax[u]);
-            }
-#pragma unroll
-            for (int u = 0; u < U; u++) {
-                const float s = score(x[u], ax[u]);
+                const float s = score(x[u], x[u]);
                 if (tm.lane != 0 || id[u] < 0 || id[u] == target || !(s < mn)) continue;
                 c0++;
                 if (!a.filtered) continue;
@@ -207,6 +220,69 @@ __global__ __launch_bounds__(256) void rank_cand_kernel(RankCandArgs a) {
                     if (khi > klo) { kmin = known_arr[klo].z; kmax = known_arr[khi - 1].z; }
                 }
                 if (!(id[u] >= kmin && id[u] <= kmax && in_range(known_arr, klo, khi, id[u]))) c1++;
+            }
+        };
+        int pend = -1, p = 0;      // the queue: lane j < p holds a pending owned id; p < U between batches
+        for (long long k0 = k_lo; k0 < k_hi; k0 += L) {
+            const long long k = k0 + tm.lane;
+            const int mine = k < k_hi ? candidate_id<MODE>(a, i, side, r, k) : -1;
+            const bool own = mine >= r_lo && mine < r_hi;
+            const unsigned long long owned = (__ballot(own) >> tbase) & tmask;       // this team's lanes only
+            const int m = __popcll(owned), below = __popcll(owned & ((1ULL << tm.lane) - 1));
+            // a permutation of the team: the owned ids to lanes 0 .. m-1 in list order, the others behind them
+            const int fresh = __builtin_amdgcn_ds_permute((tbase + (own ? below : m + tm.lane - below)) << 2, mine);
+            int s = 0;             // queue entry e: pend's lane e while e < p, then fresh's lane e - p
+            for (; p + m - s >= U; s += U) {
+                int id[U];
+#pragma unroll
+                for (int u = 0; u < U; u++) {
+                    const int e = s + u;
+                    id[u] = team_bcast<L>(e < p ? pend : fresh, e < p ? e : e - p);
+                }
+                round(id);
+            }
+            const int src = s + tm.lane;       // what is left (fewer than U) moves to the queue's front
+            const int moved = __shfl(fresh, src >= p ? src - p : 0, L);
+            if (src >= p) pend = moved;
+            p += m - s;
+        }
+        if (p > 0) {
+            int id[U];
+#pragma unroll
+            for (int u = 0; u < U; u++) {
+                const int v = team_bcast<L>(pend, u);
+                id[u] = u < p ? v : -1;
+            }
+            round(id);
+        }
+    } else {
+        for (long long k0 = k_lo; k0 < k_hi; k0 += L) {
+            const long long k = k0 + tm.lane;
+            const int mine = k < k_hi ? candidate_id<MODE>(a, i, side, r, k) : -1;
+            const int nk = (int)min((long long)L, k_hi - k0);
+            for (int j = 0; j < nk; j += U) {
+                int id[U];
+                float x[U][C], ax[U][C];
+#pragma unroll
+                for (int u = 0; u < U; u++) {
+                    id[u] = team_bcast<L>(mine, j + u);
+                    const long long row = id[u] >= 0 ? id[u] : 0;   // a skipped id still loads a row: no branch around the gathers
+                    tm.load(a.ent, row, x[u]);
+                    if constexpr (MODEL == KGE_TRANSD) tm.load(a.auxe, row, ax[u]);
+                }
+#pragma unroll
+                for (int u = 0; u < U; u++) {
+                    const float s = score(x[u], ax[u]);
+                    if (tm.lane != 0 || id[u] < 0 || id[u] == target || !(s < mn)) continue;
+                    c0++;
+                    if (!a.filtered) continue;
+                    if (!have_range) {
+                        have_range = true;
+                        pair_range(known_arr, a.ev.n_all, fixed, r, klo, khi);
+                        if (khi > klo) { kmin = known_arr[klo].z; kmax = known_arr[khi - 1].z; }
+                    }
+                    if (!(id[u] >= kmin && id[u] <= kmax && in_range(known_arr, klo, khi, id[u]))) c1++;
+                }
             }
         }
     }
@@ -246,12 +322,31 @@ int launch_fused(RankCandArgs a, int mode, hipStream_t stream) {
         slices = (a.n_cand + a.slice_len - 1) / a.slice_len;
         a.atomic = slices > 1;
         const dim3 grid((unsigned)nblocks, (unsigned)slices);   // n < 2^30: at most 2^31 / TEAMS blocks along x
-        if (mode == kList) hipLaunchKernelGGL((rank_cand_kernel<MODEL, L, C, U, kList>), grid, dim3(256), 0, stream, a);
-        else if (mode == kDrawn) hipLaunchKernelGGL((rank_cand_kernel<MODEL, L, C, U, kDrawn>), grid, dim3(256), 0, stream, a);
-        else hipLaunchKernelGGL((rank_cand_kernel<MODEL, L, C, U, kDrawnTyped>), grid, dim3(256), 0, stream, a);
+        if (mode == kList) hipLaunchKernelGGL((rank_cand_kernel<MODEL, L, C, U, kList, false>), grid, dim3(256), 0, stream, a);
+        else if (mode == kDrawn) hipLaunchKernelGGL((rank_cand_kernel<MODEL, L, C, U, kDrawn, false>), grid, dim3(256), 0, stream, a);
+        else hipLaunchKernelGGL((rank_cand_kernel<MODEL, L, C, U, kDrawnTyped, false>), grid, dim3(256), 0, stream, a);
     });
     if (!shaped) return fail(KGE_ERR_UNSUPPORTED, "kge_rank_candidates: embedding dimension > 1024");
     return hip_check(hipGetLastError(), "rank candidates launch");
+}
+
+// the row-range form (TransE): the same grid, slices and U
+int launch_range(RankCandRangeArgs a, int mode, hipStream_t stream) {
+    const bool shaped = for_team_shape(a.D, [&](auto t) {
+        constexpr int L = decltype(t)::L, C = decltype(t)::C, U = rankc_u<KGE_TRANSE>(C);
+        constexpr long long TEAMS = 256 / L;
+        const long long nblocks = (a.n_req + TEAMS - 1) / TEAMS;
+        long long slices = rankc_slices(nblocks, a.n_cand, L);
+        a.slice_len = (a.n_cand + slices - 1) / slices;
+        slices = (a.n_cand + a.slice_len - 1) / a.slice_len;
+        a.atomic = slices > 1;
+        const dim3 grid((unsigned)nblocks, (unsigned)slices);
+        if (mode == kList) hipLaunchKernelGGL((rank_cand_kernel<KGE_TRANSE, L, C, U, kList, true>), grid, dim3(256), 0, stream, a);
+        else if (mode == kDrawn) hipLaunchKernelGGL((rank_cand_kernel<KGE_TRANSE, L, C, U, kDrawn, true>), grid, dim3(256), 0, stream, a);
+        else hipLaunchKernelGGL((rank_cand_kernel<KGE_TRANSE, L, C, U, kDrawnTyped, true>), grid, dim3(256), 0, stream, a);
+    });
+    if (!shaped) return fail(KGE_ERR_UNSUPPORTED, "kge_rank_candidates_range: embedding dimension > 1024");
+    return hip_check(hipGetLastError(), "rank candidates range launch");
 }
 
 // ---- two-stage form -------------------------------------------------------------------------------------------------------
@@ -420,4 +515,49 @@ extern "C" int kge_rank_candidates(const kge_model_desc *m, const float *const t
         case KGE_TRANSH: return launch_fused<KGE_TRANSH>(a, mode, stream);
         default: return launch_fused<KGE_TRANSD>(a, mode, stream);
     }
+}
+
+extern "C" int kge_rank_candidates_range(const kge_model_desc *m, const float *const tables[KGE_MAX_TABLES], INT row_lo, INT rows,
+                                         const float *d_query_rows, const int32_t *d_h, const int32_t *d_t, const int32_t *d_r, INT n,
+                                         const int32_t *d_tail_cand, INT tail_stride, const int32_t *d_head_cand, INT head_stride,
+                                         INT n_cand, INT flags, uint64_t seed, int64_t *d_counts, void *stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    if (!m || !tables || !d_h || !d_t || !d_r || !d_counts) return fail(KGE_ERR_BAD_ARG, "kge_rank_candidates_range: null model, tables, triple or output array");
+    if (n < 0 || n >= (INT(1) << 30)) return fail(KGE_ERR_BAD_ARG, "kge_rank_candidates_range: triple count outside [0, 2^30)");
+    if (n_cand < 0 || n_cand >= (INT(1) << 31)) return fail(KGE_ERR_BAD_ARG, "kge_rank_candidates_range: candidate count outside [0, 2^31)");
+    if (flags & ~(INT)(KGE_RANKC_FILTERED | KGE_RANKC_DRAWN | KGE_RANKC_TYPED | KGE_RANKC_NO_HEAD)) return fail(KGE_ERR_BAD_ARG, "kge_rank_candidates_range: unknown flags");
+    const bool drawn = flags & KGE_RANKC_DRAWN, typed = flags & KGE_RANKC_TYPED, no_head = flags & KGE_RANKC_NO_HEAD, filtered = flags & KGE_RANKC_FILTERED;
+    if (drawn && (d_tail_cand || d_head_cand)) return fail(KGE_ERR_BAD_ARG, "kge_rank_candidates_range: a candidate list together with KGE_RANKC_DRAWN");
+    if (!drawn && (typed || no_head)) return fail(KGE_ERR_BAD_ARG, "kge_rank_candidates_range: KGE_RANKC_TYPED / KGE_RANKC_NO_HEAD without KGE_RANKC_DRAWN");
+    if (!drawn && !d_tail_cand && !d_head_cand) return fail(KGE_ERR_BAD_ARG, "kge_rank_candidates_range: no candidate list and no KGE_RANKC_DRAWN");
+    if ((d_tail_cand && tail_stride != 0 && tail_stride < n_cand) || (d_head_cand && head_stride != 0 && head_stride < n_cand))
+        return fail(KGE_ERR_BAD_ARG, "kge_rank_candidates_range: a list stride must be 0 (shared list) or at least n_cand");
+    bool known_model = for_model(m->model, [](auto) {});
+    if (!known_model) return fail(KGE_ERR_BAD_ARG, "unknown model id");
+    if (m->model != KGE_TRANSE) return fail(KGE_ERR_UNSUPPORTED, "kge_rank_candidates_range: TransE only");
+    const int64_t E = m->ent_total;
+    const int D = (int)m->ent_dim;
+    if (m->ent_dim < 1 || E < 1 || E >= (INT(1) << 31) || m->rel_total < 1) return fail(KGE_ERR_BAD_ARG, "kge_rank_candidates_range: empty model");
+    if (m->ent_dim > 1024) return fail(KGE_ERR_UNSUPPORTED, "kge_rank_candidates_range: embedding dimension > 1024");
+    if (row_lo < 0 || rows < 0 || row_lo > E || rows > E - row_lo) return fail(KGE_ERR_BAD_ARG, "kge_rank_candidates_range: row range outside the entity table");
+    if (n > 0 && !d_query_rows) return fail(KGE_ERR_BAD_ARG, "kge_rank_candidates_range: null query rows");
+    if (!device_ok()) return fail(KGE_ERR_NO_DEVICE, "kge_rank_candidates_range: no usable HIP device");
+    RankCandRangeArgs a = {};
+    int rc;
+    if ((filtered || typed) && (rc = eval_filter_view(typed, a.ev))) return rc;
+    if (!tables[1] || (rows > 0 && !tables[0])) return fail(KGE_ERR_BAD_ARG, "kge_rank_candidates_range: null table");
+    if (n == 0) return KGE_OK;
+    if ((rc = hip_check(hipMemsetAsync(d_counts, 0, sizeof(int64_t) * 4 * (size_t)n, stream), "zero rank candidate range counts"))) return rc;
+    if (n_cand == 0 || rows == 0) return KGE_OK;
+    a.ent = tables[0]; a.rel = tables[1];
+    a.qrows = d_query_rows; a.row_lo = row_lo; a.rows = rows;
+    a.h = d_h; a.t = d_t; a.r = d_r;
+    a.cand[0] = d_tail_cand; a.cand[1] = d_head_cand; a.stride[0] = tail_stride; a.stride[1] = head_stride;
+    const bool tail_side = drawn || d_tail_cand, head_side = drawn ? !no_head : d_head_cand != nullptr;
+    a.nsides = tail_side && head_side ? 2 : 1;
+    a.side0 = tail_side ? 0 : 1;
+    a.n = n; a.n_req = n * a.nsides; a.n_cand = n_cand;
+    a.E = E; a.R = m->rel_total; a.D = D;
+    a.filtered = filtered; a.seed = seed; a.counts = (long long *)d_counts;
+    return launch_range(a, !drawn ? kList : (typed ? kDrawnTyped : kDrawn), stream);
 }

@@ -83,8 +83,9 @@ def parse_args(argv=None):
     p.add_argument("--early_stop_candidates", type=int, default=0,
                    help="hits10 / mrr: rank every chosen validation triple against this many candidates per side, drawn on the device "
                         "from a counter hash (Config.rank_triples_sampled; from the relation's type lists with "
-                        "--type_constrained_sampling 1), instead of against every entity (0, the default).  Not with an entity table "
-                        "sharded across ranks")
+                        "--type_constrained_sampling 1), instead of against every entity (0, the default).  With an entity table "
+                        "sharded across ranks the check is the collective Config.validation_link_prediction_distributed(candidates=): "
+                        "every rank ranks the candidates whose rows it owns and the counts are all-reduced")
     p.add_argument("--early_stop_candidates_seed", type=int, default=0,
                    help="seed of the drawn candidates; the same for every check of a run, so that successive checks are comparable")
     p.add_argument("--model", type=str, default="TransE")
@@ -486,9 +487,10 @@ def _validation_rank_metric(con, argv):
     test_head = bool(argv.test_head)
     name = "_filter_tot" if argv.early_stop_metric == "hits10" else "_filter_reci_rank"
     sides = ("r", "l") if test_head else ("r",)
-    if argv.early_stop_candidates > 0:      # drawn candidate lists: replicated tables only (refused before step 0 otherwise)
-        metrics = con.validation_link_prediction(test_head=test_head, sample=argv.early_stop_rank_triples, candidates=argv.early_stop_candidates,
-                                                 seed=argv.early_stop_candidates_seed, type_constrained=bool(argv.type_constrained_sampling))[1]
+    if argv.early_stop_candidates > 0:      # drawn candidate lists; on a sharded entity table every rank counts the candidates it owns
+        rank_valid = con.validation_link_prediction_distributed if con._sharded("ent_embeddings") else con.validation_link_prediction
+        metrics = rank_valid(test_head=test_head, sample=argv.early_stop_rank_triples, candidates=argv.early_stop_candidates,
+                             seed=argv.early_stop_candidates_seed, type_constrained=bool(argv.type_constrained_sampling))[1]
         return sum(metrics[p + name] for p in sides) / len(sides)
     rank_valid = con.validation_link_prediction_distributed if con._sharded("ent_embeddings") else con.validation_link_prediction
     metrics = rank_valid(test_head=test_head, sample=argv.early_stop_rank_triples)[1]
@@ -552,9 +554,6 @@ def main_fun(argv):
     metric = argv.early_stop_metric
     if argv.early_stop_candidates < 0:
         raise KgeError("--early_stop_candidates must be >= 0, got %d" % argv.early_stop_candidates)
-    if metric != "accuracy" and argv.early_stop_candidates > 0 and con._sharded("ent_embeddings"):      # before step 0
-        raise KgeError("--early_stop_candidates over an entity table sharded across ranks is not supported (Config.rank_triples_sampled "
-                       "refuses it): rank against every entity (--early_stop_candidates 0), a collective on sharded tables")
     valid = _init_validation(con, argv) if metric == "accuracy" else _init_rank_validation(con)
     best_acc, wait_steps_acc, best_step_acc = -1.0, 0, last_global_step
     iterations = con.train_times * con.nbatches + last_global_step      # distribute_training.py:205

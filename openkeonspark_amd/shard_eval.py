@@ -1,7 +1,7 @@
 """Evaluation over an entity table sharded across ranks (`con._shard`).  Every function here is a collective: each rank calls it
 the same number of times, and the order in which it enters torch.distributed collectives (fetch_rows, all_reduce, agree and the
-`parallel` calls written out in it) is its contract with the other ranks.  top_k_entities, relation_prediction and rank_triples
-open with agree; test_step and link_prediction have no header step.  rank_triples also serves replicated tables.  Functions take the Config first; its public methods dispatch here.
+`parallel` calls written out in it) is its contract with the other ranks.  top_k_entities, relation_prediction, rank_triples and
+rank_candidates open with agree; test_step and link_prediction have no header step.  rank_triples also serves replicated tables.  Functions take the Config first; its public methods dispatch here.
 """
 import ctypes
 
@@ -264,5 +264,56 @@ def rank_triples(con, ids, err, test_head):
         c0, c1 = min(con.rank * cs, n), min((con.rank + 1) * cs, n)
         if c1 > c0:
             con._rank_device(ids[:, c0:c1].contiguous(), test_head, into=counts[c0:c1])
+    all_reduce(con, counts, dist.ReduceOp.SUM)
+    return counts[:n].cpu().numpy()
+
+
+def rank_candidates(con, ids, err, tail, head, n_cand, flags, seed, what="rank_candidates_distributed"):
+    """Config.rank_candidates_distributed / rank_triples_sampled_distributed on a sharded entity table.  `ids` is the int32 device
+    tensor [3, n] (h, t, r; ids already checked) or None, `err` what this rank's own argument check raised (or None); tail /
+    head = (int32 device tensor, stride) or None; with KGE_RANKC_DRAWN in `flags` both are None and `seed` draws the lists.  The
+    ranks first agree on a header (validity, n, C, flags, which sides have a list, their strides, the seed, triples per round);
+    the arguments and the evaluation files are checked before it, without a launch.  Then, in rounds of `per` triples, the
+    2 per h and t rows come from their owners (query_rows, laid out [per][2][D]) and kge_rank_candidates_range ranks the round
+    against this rank's rows [lo, hi) into its slice of one [n, 2, 2] device tensor: a round's per-triple lists start at
+    c0 x stride, and its drawn lists are indexed by the global triple (the seed is moved there as _rank_candidates_device moves
+    it).  ONE SUM all-reduce of that tensor closes the call: every rank compares against the same target score bits and counts
+    the candidates it owns, so the sum is kge_rank_candidates over the whole table.  -> int64 numpy [n, 2, 2]."""
+    import torch
+    import torch.distributed as dist
+    L, st, D, dev = con.lib, con._stream(), con.hidden_size, con.device
+    if not dist.is_initialized():      # no process group, so no other rank can be waiting for this one
+        raise KgeError("%s over an entity table sharded across ranks needs the process group it was sharded over" % what)
+    lo, hi = con._shard["lo"], con._shard["hi"]
+    spare = torch.zeros((3, 4), dtype=torch.int32, device=dev)        # an empty tensor has no address
+    ptr = lambda x, off=0: (x.view(-1)[off:] if off else x).data_ptr() if x.numel() > off else spare.data_ptr()
+    n, fields = -1, (0, 0, 0, 0, 0, 0)
+    if err is None:
+        try:
+            n, n_cand, flags = int(ids.shape[1]), int(n_cand), int(flags)
+            lists = [(None, 0) if side is None else (ptr(side[0]), int(side[1])) for side in (tail, head)]
+            # the arguments and the evaluation files, checked without a launch (no triples)
+            _lib.check(L.kge_rank_candidates_range(ctypes.byref(con._desc), con._tab_ptrs, lo, hi - lo, None, spare.data_ptr(),
+                                                   spare.data_ptr(), spare.data_ptr(), 0, lists[0][0], lists[0][1], lists[1][0],
+                                                   lists[1][1], n_cand, flags, 0, spare.data_ptr(), st), L)
+            sides = (1 if tail is not None else 0) | (2 if head is not None else 0)
+            fields = (n_cand, flags, sides, lists[0][1], lists[1][1], int(seed) & (2 ** 62 - 1))
+        except (KgeError, ValueError, TypeError, OverflowError, AttributeError) as e:
+            err, n = e, -1
+    per = max(1, int(con.lp_shard_query_bytes) // (2 * D * 4))
+    _, per = agree(con, what, err, (n,) + tuple(fields), [1, 2, 3, 4, 5, 6, 7],
+                   "numbers of triples or candidates, flags, lists or seeds", per)
+    counts = torch.zeros((max(n, 1), 2, 2), dtype=torch.int64, device=dev)
+    for c0 in range(0, n, per):
+        m = min(per, n - c0)
+        pairs = ids[:2, c0:c0 + m].t().contiguous().view(-1)      # h0, t0, h1, t1, ...
+        query = query_rows(con, pairs, 2 * m)                      # [m][2][D]: the raw h and t row of each triple
+        round_lists = [(None, 0) if side is None else (ptr(side[0], c0 * int(side[1])), int(side[1])) for side in (tail, head)]
+        round_seed = (int(seed) + ((c0 << 33) * 0x9E3779B97F4A7C15)) & 0xFFFFFFFFFFFFFFFF
+        _lib.check(L.kge_rank_candidates_range(ctypes.byref(con._desc), con._tab_ptrs, lo, hi - lo, query.data_ptr(),
+                                               ids[0, c0:].data_ptr(), ids[1, c0:].data_ptr(), ids[2, c0:].data_ptr(), m,
+                                               round_lists[0][0], round_lists[0][1], round_lists[1][0], round_lists[1][1],
+                                               n_cand, flags, round_seed, counts[c0].data_ptr(), st), L)
+        del query
     all_reduce(con, counts, dist.ReduceOp.SUM)
     return counts[:n].cpu().numpy()

@@ -6,8 +6,13 @@ full ranking fits, in one process: five interleaved rounds after a warm-up, host
 Appends one JSON line to profiles/rank_candidates.jsonl (or --out) with the median / min / max ms of each form and the
 algorithmic gather rate n x sides x C x D x 4 B / median time.
 usage: bench_rank_candidates.py [fb|large] [MODEL] [DIM] [--out FILE] [--rounds N] [--candidates C]
-Exits non-zero when the two forms' counts differ."""
+Exits non-zero when the two forms' counts differ.
+  --range-cut W [W ...]   (large, TransE) what one rank of a W-way sharded table pays: kge_rank_candidates_range on the first 1/W of
+the rows against kge_rank_candidates on the whole table, the same triples and drawn lists, both on device-resident ids and
+counts; the query rows are prepared outside the timed region.  One JSON line per W; exits non-zero when the W ranges' counts do
+not sum to the whole table's."""
 import argparse
+import ctypes
 import json
 import os
 import sys
@@ -56,6 +61,47 @@ def large_engine(pkg, model, dim, entities, triples):
     return con, np.stack(draw(triples), 1)
 
 
+def range_cut(con, tt, C, W, rounds, seed=1):
+    """-> the JSON line of one W: the range call on rows [0, ceil(E / W)) and the whole-table call, interleaved."""
+    import torch
+    from openkeonspark_amd import _lib
+    E, D, L, st = con.entTotal, con.hidden_size, con.lib, con._stream()
+    ent, rel = con._tables[0], con._tables[1]
+    flags = _lib.RANKC_DRAWN | _lib.RANKC_FILTERED
+    ids = torch.from_numpy(np.ascontiguousarray(tt.T.astype(np.int32))).to(con.device)
+    n = ids.shape[1]
+    query = ent.index_select(0, ids[:2].t().reshape(-1).long()).contiguous()      # [n][2][D], outside the timed region
+    chunk = -(-E // W)
+    whole_counts = torch.empty((n, 2, 2), dtype=torch.int64, device=con.device)
+    part_counts = torch.empty_like(whole_counts)
+
+    def ranged(lo, hi, out):
+        _lib.check(L.kge_rank_candidates_range(ctypes.byref(con._desc), _lib.table_ptrs([ent[lo:].data_ptr(), rel.data_ptr()]), lo, hi - lo,
+                                               query.data_ptr(), ids[0].data_ptr(), ids[1].data_ptr(), ids[2].data_ptr(), n, None, 0, None, 0,
+                                               C, flags, seed, out.data_ptr(), st), L)
+    arms = {"whole": lambda: con._rank_candidates_device(ids, None, None, C, flags, seed, into=whole_counts),
+            "range": lambda: ranged(0, chunk, part_counts)}
+    times = {k: [] for k in arms}
+    for fn in arms.values():
+        fn()
+    for _ in range(rounds):
+        for k, fn in arms.items():
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            fn()
+            torch.cuda.synchronize()
+            times[k].append(time.perf_counter() - t0)
+    total = torch.zeros_like(whole_counts)
+    for g in range(W):
+        ranged(min(g * chunk, E), min((g + 1) * chunk, E), part_counts)
+        total += part_counts
+    line = {"shape": "large", "model": "TransE", "dim": D, "entities": E, "triples": n, "candidates": C, "sides": 2, "range_cut": W,
+            "range_rows": chunk, "table_bytes": float(E) * D * 4, "whole": summary(times["whole"]), "range": summary(times["range"])}
+    line["range_over_whole"] = round(float(np.median(times["range"]) / np.median(times["whole"])), 4)
+    line["counts_sum_equal_whole"] = bool(torch.equal(total, whole_counts))
+    return line
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("shape", nargs="?", default="fb", choices=("fb", "large"))
@@ -66,12 +112,27 @@ def main():
     ap.add_argument("--candidates", type=int, default=0)
     ap.add_argument("--entities", type=int, default=5000000)
     ap.add_argument("--triples", type=int, default=100000)
+    ap.add_argument("--range-cut", type=int, nargs="+", default=[], metavar="W")
     a = ap.parse_args()
+    if a.range_cut and (a.shape != "large" or a.model != "TransE" or min(a.range_cut) < 1):
+        sys.exit("--range-cut W needs the large shape, TransE and W >= 1")
     import torch
     import openkeonspark_amd as pkg
     C = a.candidates or (1000 if a.shape == "fb" else 500)
     con, tt = fb_engine(pkg, a.model, a.dim) if a.shape == "fb" else large_engine(pkg, a.model, a.dim, a.entities, a.triples)
     torch.cuda.synchronize()
+    if a.range_cut:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        ok = True
+        for W in a.range_cut:
+            line = range_cut(con, tt, C, W, a.rounds)
+            print(json.dumps(line), flush=True)
+            with open(a.out, "a") as f:
+                f.write(json.dumps(line) + "\n")
+            ok = ok and line["counts_sum_equal_whole"]
+        if not ok:
+            sys.exit("the ranges' counts do not sum to the whole table's")
+        return
     h, t, r = tt[:, 0], tt[:, 1], tt[:, 2]
     full = a.shape == "fb"
 
