@@ -156,6 +156,14 @@ const char *kge_version(void);
  *                     side (kge_sampling_device_packed), and that round body reads a group's negatives from them -- one line per
  *                     group instead of a line per negative and id array; 0 = no pack is written or read and kge_emit_pack_words
  *                     returns 0, which is the step without it, bit for bit: A/B measurements and the tests' reference
+ *   "emit_keys_grouped": 1 (default) = in kge_transe_train_step_counts at the round body's widths the emit kernel writes the record
+ *                     keys of a group side by side (key of slot s of group b at word b * (3 + n_neg) + s: one store instruction
+ *                     per group, one run of lines per workgroup) and the two-launch record sort turns a key's position into its
+ *                     record id; records, record ids and kge_transe_step_scratch_read's view of the keys stay slot-major.
+ *                     0 = slot-major keys (word s * n_pos + b), the step as it was, bit for bit.  Steps whose sort takes the
+ *                     three-launch form, and every other producer of records, write slot-major keys whatever the value
+ *   "counts_sort_test_group": test hook: S > 0 = kge_counts_sort_test takes its keys as group-major, n_keys / S groups of S (the
+ *                     pair at position p gets the id (p % S) * (n_keys / S) + p / S); two-launch form only.  Default 0
  *   "record_emit_event": 1 = record an event behind every TransE emit launch (kge_stream_wait_emit); default 0
  *   "pair_counts":       1 (default) = TransH / TransD steps of at least float_records_min entity-side rows (widths that are
  *                        multiples of 4 up to 256, at most 63 negatives, ent_total*rel_total below 2^31) take the
@@ -571,7 +579,9 @@ int kge_transe_apply_counts_range(const kge_model_desc *m, float *const d_p[2], 
  *                              which = 0 the records (3 * n_pos int8 records of kge_transe_record_dwords words each, then --
  *                              the fused step at widths that are multiples of 4 -- the 2-bit record of negative k of group b
  *                              as record k * n_pos + b of a quarter of that size), which = 1 the destination keys as the
- *                              call left them (inactive slots hold its sentinel, the largest key).  Synchronises.
+ *                              call left them (inactive slots hold its sentinel, the largest key), always in slot-major order
+ *                              (word s * n_pos + b) whichever layout the step kept them in, which = 2 the emit kernel's table of
+ *                              1/|row| (entity rows, then relation rows; fp32 words).  Synchronises.
  *   kge_counts_sort_test:      test hook.  Runs the hand-written record sort (option "counts_sort_tiles") on `stream` over the n_keys
  *                              HOST keys `keys` (a key < 0 = no record, else < rows), buckets of rpb rows (rows <= 512 * rpb,
  *                              rpb <= 8192), and copies back: sorted_keys / sorted_ids [n_keys] (the first *n_live entries are

@@ -266,6 +266,8 @@ int kge_set_option(const char *name, INT value) {
     if (n == "inv_carry") { engine().inv_carry = value != 0; tables_written(); return KGE_OK; }
     if (n == "emit_rounds") { engine().emit_rounds = value != 0; return KGE_OK; }
     if (n == "emit_pack") { engine().emit_pack = value != 0; return KGE_OK; }
+    if (n == "emit_keys_grouped") { engine().emit_keys_grouped = value != 0; return KGE_OK; }
+    if (n == "counts_sort_test_group") { engine().counts_sort_test_group = value > 0 ? (int)value : 0; return KGE_OK; }
     if (n == "float_records") { engine().float_records = value != 0; return KGE_OK; }
     if (n == "float_records_min") { engine().float_records_min = value; return KGE_OK; }
     if (n == "index_device_min") { engine().index_device_min = value; return KGE_OK; }

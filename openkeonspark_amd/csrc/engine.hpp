@@ -83,6 +83,8 @@ struct Engine {
     int inv_carry = 1;          // 0 = always recompute the table in front of the emit kernel (test hook)
     int emit_rounds = 1;        // TransE emit at 132 <= D <= 256: rounds of one corruption kind with merged reductions (models.hip transe_emit_rounds_body); 0 = the earlier body, as transe_emit_vec_v1_kernel (A/B runs, test reference)
     int emit_pack = 1;          // device-sampled TransE batches: the sampler also writes one packed word per negative, a group's words in one line, and the round body reads those instead of the strided h/t/r arrays (sampler_dev.hpp SamplerArgs::pack); 0 = no pack written or read (A/B runs, test reference)
+    int emit_keys_grouped = 1;  // fused single-process TransE step at the round body's widths: the emit kernel writes a group's 3 + n_neg record keys side by side (dst[b * S + slot], one store instruction and one run of lines per workgroup) and the two-launch sort turns positions into record ids (transe_counts.hip KeyMap); 0 = slot-major keys, the step as it was (A/B runs, test reference)
+    int counts_sort_test_group = 0;   // test hook: kge_counts_sort_test takes its keys as group-major, groups of this many (0 = slot-major)
     int64_t inv_table_max_bytes = int64_t(256) << 20;  // TransE emit: per-row inverse-norm table only while the tables are this small
     int float_records = 1;              // TransH / TransD (and TransE without counts): record + segmented-sum path instead of fp32 atomics
     int64_t float_records_min = 1 << 16; // ... from this many gradient rows per step (below it the atomic kernel alone is quicker)

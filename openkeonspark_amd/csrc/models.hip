@@ -489,7 +489,10 @@ template <int V> struct IntC { static constexpr int value = V; };
 // PACK: the negatives' ids come from the sampler's packed line of the group (FbArgs::neg_pack) -- one coalesced load of at most
 // 63 consecutive words instead of three loads that touch a line per negative each (the batch holds a group's negatives `stride`
 // words apart).  The word was made by classify_negative on the ids the sampler wrote to those arrays, so both reads agree.
-template <bool INV_TAB, bool REC2, bool PACK = false>
+// GROUPED: the keys of a group go out side by side, dst[b * S + slot] with S = 3 + n_neg (the fused step's engine-owned keys,
+// option emit_keys_grouped): one store instruction per group and one contiguous run per workgroup, where the slot-major layout
+// dst[slot * n_pos + b] scatters a group's keys over S lines that eight workgroups share.  The sort maps positions back to record ids.
+template <bool INV_TAB, bool REC2, bool PACK = false, bool GROUPED = false>
 __device__ __forceinline__ void transe_emit_rounds_body(const FbArgs &a) {
     constexpr int L = 64, TEAMS = 256 / L;
     __shared__ float red[TEAMS];
@@ -497,6 +500,7 @@ __device__ __forceinline__ void transe_emit_rounds_body(const FbArgs &a) {
     const int team_in_block = __builtin_amdgcn_readfirstlane(threadIdx.x / L);   // the wave: uniform, so are b and the positive's ids
     const int D = a.D;
     const int n_neg = (int)a.n_neg;
+    if constexpr (GROUPED) __builtin_assume(n_neg < L);   // (the sign-count path takes at most 63 negatives: one id round)
     const float *inv_ent = a.inv_norm, *inv_rel = a.inv_norm + a.ent_total;
     const bool valid = 4 * lane < D;
     const bool odd = lane & 1, hi2 = lane & 2;
@@ -538,8 +542,12 @@ __device__ __forceinline__ void transe_emit_rounds_body(const FbArgs &a) {
             }
         }
         if (__builtin_amdgcn_ballot_w64(bad) != 0) {   // not sampler-shaped: the whole group goes to the exact fp32 kernel
+            if constexpr (GROUPED) {
+                for (int sl = lane; sl < 3 + n_neg; sl += L) a.dst[b * (3 + n_neg) + sl] = -1;
+            }
             if (lane == 0) {
-                for (long long sl = 0; sl < 3 + a.n_neg; sl++) a.dst[sl * a.n_pos + b] = -1;
+                if constexpr (!GROUPED)
+                    for (long long sl = 0; sl < 3 + a.n_neg; sl++) a.dst[sl * a.n_pos + b] = -1;
                 if (a.group_list) a.group_list[atomicAdd(a.group_count, 1)] = (int32_t)b;
             }
             continue;
@@ -577,6 +585,7 @@ __device__ __forceinline__ void transe_emit_rounds_body(const FbArgs &a) {
         }
         s16x2 Ah_lo = 0, Ah_hi = 0, At_lo = 0, At_hi = 0, Ar_lo = 0, Ar_hi = 0;
         int cnt = 0;
+        int first_keys = -1;   // GROUPED: lane k holds the key of negative k < L until the positive's keys are known
         for (int k0 = 0; k0 < n_neg; k0 += L) {
             if (!PACK && k0 > 0) {   // later rounds (n_neg > L, never with a pack): fetch and classify this round's ids
                 const int my_k = k0 + lane;
@@ -672,7 +681,9 @@ __device__ __forceinline__ void transe_emit_rounds_body(const FbArgs &a) {
             // (REC2: the destination key is 2 * row + kind -- a row's int8 records and its 2-bit records form two lists)
             if (mine) {
                 const int key = my_code == 2 ? rel_row0 + my_row : my_row;
-                a.dst[(long long)(3 + k0 + lane) * a.n_pos + b] = ((act >> lane) & 1ull) ? (REC2 ? 2 * key + 1 : key) : -1;
+                const int kv = ((act >> lane) & 1ull) ? (REC2 ? 2 * key + 1 : key) : -1;
+                if constexpr (!GROUPED) a.dst[(long long)(3 + k0 + lane) * a.n_pos + b] = kv;
+                else first_keys = kv;
             }
         }
         if (cnt > 0) {
@@ -682,8 +693,13 @@ __device__ __forceinline__ void transe_emit_rounds_body(const FbArgs &a) {
             a.rec[(a.n_pos + b) * (long long)L + lane] = bytes_of(At_lo - v_lo, At_hi - v_hi);
             a.rec[(2 * a.n_pos + b) * (long long)L + lane] = bytes_of(Ar_lo + v_lo, Ar_hi + v_hi);
         }
-        if (lane == 0) {
-            constexpr int KM = REC2 ? 2 : 1;
+        constexpr int KM = REC2 ? 2 : 1;
+        if constexpr (GROUPED) {   // slots 0..2: the positive's h, t, r; slot 3 + k: negative k, moved up three lanes -- one store
+            const int S = 3 + n_neg;
+            int32_t *g = a.dst + b * S;
+            if (lane < n_neg) g[3 + lane] = first_keys;
+            if (lane < 3) g[lane] = cnt > 0 ? (int32_t)(KM * (lane == 0 ? h : (lane == 1 ? t : rel_row0 + r))) : -1;
+        } else if (lane == 0) {
             a.dst[b] = cnt > 0 ? (int32_t)(KM * h) : -1;
             a.dst[a.n_pos + b] = cnt > 0 ? (int32_t)(KM * t) : -1;
             a.dst[2 * a.n_pos + b] = cnt > 0 ? (int32_t)(KM * (rel_row0 + r)) : -1;
@@ -693,16 +709,17 @@ __device__ __forceinline__ void transe_emit_rounds_body(const FbArgs &a) {
 }
 
 // The emit kernel of the TransE sign-count path.  At L == 64, Q == 1 it runs the rounds body, elsewhere transe_emit_vec_body.
-template <int L, int Q, int K, int WPE, bool INV_TAB, bool REC2 = false>
+template <int L, int Q, int K, int WPE, bool INV_TAB, bool REC2 = false, bool GROUPED = false>
 __global__ __launch_bounds__(256, WPE) void transe_emit_vec_kernel(FbArgs a) {
-    if constexpr (L == 64 && Q == 1) transe_emit_rounds_body<INV_TAB, REC2>(a);
+    static_assert(!GROUPED || (L == 64 && Q == 1), "group-major keys: the round body only");
+    if constexpr (L == 64 && Q == 1) transe_emit_rounds_body<INV_TAB, REC2, false, GROUPED>(a);
     else transe_emit_vec_body<L, Q, K, INV_TAB, REC2>(a);
 }
 
 // The round body on the sampler's packed negatives (engine option emit_pack = 1, a device-sampled batch).  A kernel of its own, so
 // that the instantiations above keep their names in traces.
-template <bool INV_TAB, bool REC2>
-__global__ __launch_bounds__(256, 1) void transe_emit_pack_kernel(FbArgs a) { transe_emit_rounds_body<INV_TAB, REC2, true>(a); }
+template <bool INV_TAB, bool REC2, bool GROUPED = false>
+__global__ __launch_bounds__(256, 1) void transe_emit_pack_kernel(FbArgs a) { transe_emit_rounds_body<INV_TAB, REC2, true, GROUPED>(a); }
 
 // transe_emit_vec_body at every shape (engine option emit_rounds = 0): the reference the rounds body is tested against, bit for bit
 template <int L, int Q, int K, int WPE, bool INV_TAB, bool REC2 = false>
@@ -785,14 +802,25 @@ static void launch_emit(const FbArgs &a_in, float *d_loss, hipStream_t stream) {
         if constexpr (L == 64 && Q == 1) {
             if (!v1 && a.neg_pack && a.n_neg < L) {
                 packed = true;
-                if (a.rec2) {
+                if (a.rec2 && a.keys_grouped) {
+                    if (inv_tab) hipLaunchKernelGGL((transe_emit_pack_kernel<true, true, true>), grid, block, 0, stream, a);
+                    else hipLaunchKernelGGL((transe_emit_pack_kernel<false, true, true>), grid, block, 0, stream, a);
+                } else if (a.rec2) {
                     if (inv_tab) hipLaunchKernelGGL((transe_emit_pack_kernel<true, true>), grid, block, 0, stream, a);
                     else hipLaunchKernelGGL((transe_emit_pack_kernel<false, true>), grid, block, 0, stream, a);
                 } else if (inv_tab) hipLaunchKernelGGL((transe_emit_pack_kernel<true, false>), grid, block, 0, stream, a);
                 else hipLaunchKernelGGL((transe_emit_pack_kernel<false, false>), grid, block, 0, stream, a);
             }
         }
-        if (v1 || packed) {
+        bool grouped = false;   // the round body on the strided id arrays, group-major keys
+        if constexpr (L == 64 && Q == 1) {
+            if (!v1 && !packed && a.rec2 && a.keys_grouped) {
+                grouped = true;
+                if (inv_tab) hipLaunchKernelGGL((transe_emit_vec_kernel<L, Q, 4, 1, true, true, true>), grid, block, 0, stream, a);
+                else hipLaunchKernelGGL((transe_emit_vec_kernel<L, Q, 4, 1, false, true, true>), grid, block, 0, stream, a);
+            }
+        }
+        if (v1 || packed || grouped) {
         } else if (a.rec2) {
             if (inv_tab) hipLaunchKernelGGL((transe_emit_vec_kernel<L, Q, 4, 1, true, true>), grid, block, 0, stream, a);
             else hipLaunchKernelGGL((transe_emit_vec_kernel<L, Q, 4, 1, false, true>), grid, block, 0, stream, a);
@@ -839,6 +867,13 @@ void transe_team_shape(int D, int &L, int &C) {
     for_transe_team_shape_or_last(D, [&](auto t) { L = decltype(t)::L; C = decltype(t)::C; });
 }
 
+// launch_emit runs the round body at this width (its 2-bit record form has the group-major key layout): the condition of its dispatch
+bool transe_emit_groups_keys(int D) {
+    int L, C;
+    transe_team_shape(D, L, C);
+    return D % 4 == 0 && D <= 1024 && L == 64 && (C + 3) / 4 == 1 && engine().emit_rounds;
+}
+
 // groups of the LAST emit launch that were not sampler-shaped: the list an emit kernel defers them to, and how many it holds
 static DevBuf<int32_t> g_defer_list, g_defer_count;
 // room for one entry per group; zero: the count restarts on `stream`
@@ -871,7 +906,7 @@ int transe_deferred_groups(int32_t *out) {
 int launch_transe_emit(const kge_model_desc &m, const float *ent, const float *rel, float *resid_ent, float *resid_rel,
                        const int32_t *d_h, const int32_t *d_t, const int32_t *d_r, int64_t n_pos, int64_t n_neg, int64_t stride,
                        int64_t denom, uint32_t *rec, int32_t *dst, int krel, float *d_loss, hipStream_t stream, bool track_deferred,
-                       uint8_t *rec2, const int32_t *neg_pack) {
+                       uint8_t *rec2, const int32_t *neg_pack, bool keys_grouped) {
     // neg_pack: the packed negatives the sampler wrote for THIS batch (SamplerArgs::pack), or null; only the round body reads it
     // rec2: 2-bit records for the negatives (FbArgs::rec2; widths that are multiples of 4 only -- the caller checks); null = int8
     // track_deferred = false: the caller guarantees sampler-shaped negatives (a device-sampled batch): no
@@ -896,6 +931,10 @@ int launch_transe_emit(const kge_model_desc &m, const float *ent, const float *r
     a.loss_partials = e.dev.loss_partials;
     a.negative_rel = m.negative_rel;
     a.rec = rec; a.rec2 = (m.ent_dim % 4 == 0) ? rec2 : nullptr; a.dst = dst; a.ent_total = (int)m.ent_total; a.rel_total = (int)m.rel_total; a.krel = 1;
+    // keys_grouped: dst is written group-major (transe_emit_rounds_body<.., GROUPED>); the caller has asked transe_emit_groups_keys
+    if (keys_grouped && !(a.rec2 && n_neg >= 1 && n_neg <= 63 && transe_emit_groups_keys(m.ent_dim)))
+        return fail(KGE_ERR_BAD_ARG, "transe emit: no group-major key layout at this width");
+    a.keys_grouped = keys_grouped ? 1 : 0;
     a.loss_limbs = track_deferred ? nullptr : e.loss_limbs;   // (with a deferred pass the loss is finalised by loss_finalize_kernel: the caller converts it)
     while (a.krel * 2 <= krel) a.krel *= 2;      // a power of two: the kernels take b & (krel - 1)
     if (neg_pack && e.emit_pack && !track_deferred && emit_pack_shape(m.ent_total, m.rel_total, n_neg, 0) &&

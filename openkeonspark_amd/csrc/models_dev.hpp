@@ -68,6 +68,8 @@ struct FbArgs {
     // neg_pack[(b << pack_shift) + k] for slot k = 1..n_neg of group b (sampler_dev.hpp SamplerArgs::pack); null = read bh / bt / br
     const int32_t *neg_pack;
     int pack_shift;
+    // host side only (launch_emit picks the instantiation): dst is written group-major, dst[b * (3 + n_neg) + slot]
+    int keys_grouped;
 };
 
 int ensure_loss_buffers();

@@ -34,7 +34,8 @@ void transe_team_shape(int D, int &L, int &C);
 int launch_transe_emit(const kge_model_desc &m, const float *ent, const float *rel, float *resid_ent, float *resid_rel,
                        const int32_t *d_h, const int32_t *d_t, const int32_t *d_r, int64_t n_pos, int64_t n_neg, int64_t stride,
                        int64_t denom, uint32_t *rec, int32_t *dst, int krel, float *d_loss, hipStream_t stream, bool track_deferred,
-                       uint8_t *rec2 = nullptr, const int32_t *neg_pack = nullptr);
+                       uint8_t *rec2 = nullptr, const int32_t *neg_pack = nullptr, bool keys_grouped = false);
+bool transe_emit_groups_keys(int D);   // models.hip: the emit kernel launch_transe_emit takes at this width has a group-major form
 
 int transe_deferred_groups(int32_t *out);
 
@@ -59,6 +60,10 @@ struct CtWork {
     DevBuf<int4> pieces;
     DevBuf<int32_t> n_pieces;
     DevBuf<int2> row_span;
+    // layout of the keys `dst` holds: keys_S > 0 = group-major, dst[b * keys_S + slot] of keys_n_pos groups (the fused step, option
+    // "emit_keys_grouped"); 0 = slot-major, dst[slot * n_pos + b].  Every writer of dst goes through ensure_counts_work, which resets it.
+    int keys_S = 0;
+    int64_t keys_n_pos = 0;
 };
 CtWork g_c;
 
@@ -67,6 +72,7 @@ CtWork g_c;
 int ensure_counts_work(int64_t M, size_t rec_dwords) {
     int rc;
     bool grew, sort_grew;
+    g_c.keys_S = 0; g_c.keys_n_pos = 0;
     if ((rc = g_c.ids.reserve(M, "counts ids", &sort_grew))) return rc;
     if (sort_grew) {   // record ids 0..M-1 never change; written before anything else can fail, or not kept
         std::vector<int32_t> iota((size_t)M);
@@ -594,9 +600,10 @@ static void launch_bkt_sort(int2 *pairs, int rpb, int rows, int32_t *totals, int
 //                (off[t][NB] = the tile's live count).  Keys that carry no record are dropped at the load: no atomic, no store.
 //   bucket pass  one workgroup per bucket b reads column b and b + 1 of `off`: bucket_start[b] = sum_t off[t][b]; segment t of
 //                the bucket is tile_pairs[t * T + off[t][b] .. t * T + off[t][b + 1]).  The segments are read BY PAIR INDEX over
-//                all 256 threads (a bisection in the LDS table of segment starts): dst is slot-major, so a tile of relation
+//                all 256 threads (a bisection in the LDS table of segment starts): where dst is slot-major a tile of relation
 //                keys sends ~130 pairs to each of ~31 buckets where an entity bucket gets ~3 per tile -- one thread per segment
 //                would wait on the long ones.  From there on it is bucket_rows_sort, as in bkt_sort_kernel.
+//                (The fused step's keys are group-major, KeyMap below: every tile holds the same mix of slots.)
 // The bucket pass keeps two words per tile in LDS: at most kSortMaxTiles tiles (M <= 4 194 304 keys at the default tile; the
 // headline batch has 952 392), more take the three-launch form.
 // ---------------------------------------------------------------------------------------------
@@ -604,10 +611,35 @@ constexpr int kSortTile = 2048;       // keys per tile (default; 1024 and 4096 a
 constexpr int kSortMaxTiles = 2048;
 constexpr int kOffStride = NB + 1;
 
-template <int T>
+// Group-major keys (the fused step's emit kernel, option "emit_keys_grouped"): position p = b * S + slot holds the key of record
+// id = slot * n_pos + b -- the records themselves stay slot-major.  p / S is a multiply-high by a magic the host makes
+// (key_map_for): exact for every p < 2^31.
+struct KeyMap {
+    unsigned S, magic, shift;
+    int n_pos;
+};
+static KeyMap key_map_for(int S, int64_t n_pos) {
+    KeyMap k;
+    k.S = (unsigned)S; k.n_pos = (int)n_pos;
+    unsigned sh = 0;
+    while ((2u << sh) <= (unsigned)S) sh++;                    // 2^sh <= S < 2^(sh + 1)
+    if ((1u << sh) == (unsigned)S) { k.magic = 0x80000000u; k.shift = sh - 1; }   // (S >= 2) p * 2^31 / 2^32 = p >> 1
+    else {
+        // m = ceil(2^(32 + sh) / S) = (2^(32 + sh) + e) / S with 0 <= e < S < 2^(sh + 1): floor(p m / 2^(32 + sh)) = floor(p / S + p e /
+        // (S 2^(32 + sh))), and the error term stays below 1 / S while p e < 2^(32 + sh), which p < 2^31 guarantees.  m < 2^32 as 2^sh < S.
+        k.magic = (unsigned)(((uint64_t(1) << (32 + sh)) + (unsigned)S - 1) / (unsigned)S); k.shift = sh;
+    }
+    return k;
+}
+__device__ __forceinline__ int key_id_of(unsigned S, unsigned magic, unsigned shift, int n_pos, int p) {
+    const unsigned b = __umulhi((unsigned)p, magic) >> shift;
+    return (int)(((unsigned)p - b * S) * (unsigned)n_pos + b);
+}
+
+template <int T, bool GROUPED = false>
 __global__ __launch_bounds__(256) void bkt_tile_kernel(const int32_t *__restrict__ dst, int M, int rpb, int2 *__restrict__ tile_pairs,
                                                        int32_t *__restrict__ tile_off, int32_t *__restrict__ plan_counter, SamplerArgs ride,
-                                                       int n_tiles) {
+                                                       int n_tiles, unsigned km_S, unsigned km_magic, unsigned km_shift, int km_n_pos) {
     if ((int)blockIdx.x >= n_tiles) {      // a part of the next batch's sampler riding along (see bkt_scatter_kernel)
         __shared__ float bern_lds[kBernLds];
         sample_block_ride(ride, (long long)blockIdx.x - n_tiles, bern_lds);
@@ -652,7 +684,10 @@ __global__ __launch_bounds__(256) void bkt_tile_kernel(const int32_t *__restrict
     const int live = wave_total[0] + wave_total[1] + wave_total[2] + wave_total[3];
 #pragma unroll
     for (int k = 0; k < K; k++)
-        if (code[k] >= 0) stage[hist[code[k] >> 16] + (code[k] & 0xFFFF)] = make_int2(base + (int)threadIdx.x + 256 * k, d[k]);
+        if (code[k] >= 0) {
+            const int p = base + (int)threadIdx.x + 256 * k;
+            stage[hist[code[k] >> 16] + (code[k] & 0xFFFF)] = make_int2(GROUPED ? key_id_of(km_S, km_magic, km_shift, km_n_pos, p) : p, d[k]);
+        }
     __syncthreads();
     for (int i = threadIdx.x; i < live; i += 256) tile_pairs[base + i] = stage[i];
 }
@@ -722,13 +757,19 @@ __global__ __launch_bounds__(256) void bkt_merge_kernel(const int2 *__restrict__
 }
 
 template <int T>
-static void launch_tile_sort(const int32_t *dst, int n_tiles, int M, int rows, int rpb, const SegPlan *plan, hipStream_t stream) {
+static void launch_tile_sort(const int32_t *dst, int n_tiles, int M, int rows, int rpb, const SegPlan *plan, hipStream_t stream,
+                             const KeyMap *km) {
     int2 *pairs = reinterpret_cast<int2 *>(g_c.pairs.ptr());
     SamplerArgs ride = {};
     unsigned n_ride = take_ride(ride, 1, true);
-    if (n_tiles + n_ride > 0)
-        hipLaunchKernelGGL(bkt_tile_kernel<T>, dim3((unsigned)n_tiles + n_ride), dim3(256), 0, stream, dst, M, rpb, pairs, g_c.tile_off.ptr(),
-                           plan ? plan->n_pieces : nullptr, ride, n_tiles);
+    if (n_tiles + n_ride > 0) {
+        if (km)
+            hipLaunchKernelGGL((bkt_tile_kernel<T, true>), dim3((unsigned)n_tiles + n_ride), dim3(256), 0, stream, dst, M, rpb, pairs,
+                               g_c.tile_off.ptr(), plan ? plan->n_pieces : nullptr, ride, n_tiles, km->S, km->magic, km->shift, km->n_pos);
+        else
+            hipLaunchKernelGGL((bkt_tile_kernel<T, false>), dim3((unsigned)n_tiles + n_ride), dim3(256), 0, stream, dst, M, rpb, pairs,
+                               g_c.tile_off.ptr(), plan ? plan->n_pieces : nullptr, ride, n_tiles, 0u, 0u, 0u, 0);
+    }
     ride = SamplerArgs();
     n_ride = take_ride(ride, 2, true);
     if (plan)
@@ -1277,21 +1318,25 @@ __global__ __launch_bounds__(256) void segsum_pairs_kernel(const uint32_t *__res
 // plan: the fused step's form (the bucket pass also writes row spans and pieces); the first launch re-zeroes its piece counter.
 // Engine option "counts_sort_tiles": 1 = the two-launch form (tile pass + bucket pass), 0 = hist + scatter + sort; inputs of more
 // than kSortMaxTiles tiles take the latter too.
-int bucket_sort_records(const int32_t *dst, int64_t M, int rows, int rpb, const SegPlan *plan, hipStream_t stream, const int32_t *&n_live) {
+// km: the keys are group-major (KeyMap); only the two-launch form translates positions to record ids -- ask sort_takes_tiles first.
+static int sort_tile_size() { const int opt = engine().counts_sort_tiles; return opt == 1024 || opt == 4096 ? opt : kSortTile; }
+bool sort_takes_tiles(int64_t M) { return engine().counts_sort_tiles != 0 && (M + sort_tile_size() - 1) / sort_tile_size() <= kSortMaxTiles; }
+int bucket_sort_records(const int32_t *dst, int64_t M, int rows, int rpb, const SegPlan *plan, hipStream_t stream, const int32_t *&n_live,
+                        const KeyMap *km = nullptr) {
     int rc;
     bool grew;
     if ((rc = g_c.bucket_start.reserve(NB + 2, "counts bucket_start"))) return rc;
     n_live = g_c.bucket_start + NB;   // start of the trash bucket == number of live records
-    const int opt = engine().counts_sort_tiles;
-    const int T = opt == 1024 || opt == 4096 ? opt : kSortTile;
+    const int T = sort_tile_size();
     const int64_t n_tiles_new = (M + T - 1) / T;
-    if (opt != 0 && n_tiles_new <= kSortMaxTiles) {
+    if (sort_takes_tiles(M)) {
         if ((rc = g_c.tile_off.reserve((n_tiles_new + 1) * kOffStride, "counts tile offsets"))) return rc;
-        if (T == 1024) launch_tile_sort<1024>(dst, (int)n_tiles_new, (int)M, rows, rpb, plan, stream);
-        else if (T == 4096) launch_tile_sort<4096>(dst, (int)n_tiles_new, (int)M, rows, rpb, plan, stream);
-        else launch_tile_sort<kSortTile>(dst, (int)n_tiles_new, (int)M, rows, rpb, plan, stream);
+        if (T == 1024) launch_tile_sort<1024>(dst, (int)n_tiles_new, (int)M, rows, rpb, plan, stream, km);
+        else if (T == 4096) launch_tile_sort<4096>(dst, (int)n_tiles_new, (int)M, rows, rpb, plan, stream, km);
+        else launch_tile_sort<kSortTile>(dst, (int)n_tiles_new, (int)M, rows, rpb, plan, stream, km);
         return KGE_OK;
     }
+    if (km) return fail(KGE_ERR_UNSUPPORTED, "record sort: group-major keys need the two-launch form");
     if ((rc = g_c.tile_hist.reserve(2 * (NB + 2), "counts bucket totals/cursors", &grew))) return rc;
     if (grew && (rc = hip_check(hipMemset(g_c.tile_hist, 0, sizeof(int32_t) * 2 * (NB + 2)), "zero bucket totals"))) { g_c.tile_hist.free(); return rc; }
     const int n_tiles = (int)((M + BTILE - 1) / BTILE);
@@ -1948,9 +1993,12 @@ static int forward_counts_impl(const kge_model_desc *m, const float *d_ent, cons
     const bool fused = fo && nat && rpb2 <= 4096 && !engine().counts_force_sort && engine().counts_fused &&
                        (uint64_t)M * rd * 4 < (uint64_t(1) << 32) && rows2 < (1 << 30);
     uint8_t *rec2 = fused ? reinterpret_cast<uint8_t *>(g_c.rec + (size_t)3 * (size_t)n_pos * rd) : nullptr;
+    // the fused step's keys go out group-major where the emit kernel of this width has that form and the sort will translate them
+    const bool grouped = fused && engine().emit_keys_grouped && transe_emit_groups_keys(D) && sort_takes_tiles(M);
     rc = launch_transe_emit(*m, d_ent, d_rel, d_resid_ent, d_resid_rel, d_h, d_t, d_r, n_pos, n_neg, stride, denom, g_c.rec, g_c.dst,
-                            krel, d_loss, stream, d_resid_ent != nullptr && d_resid_rel != nullptr, rec2, d_pack);
+                            krel, d_loss, stream, d_resid_ent != nullptr && d_resid_rel != nullptr, rec2, d_pack, grouped);
     if (rc) return rc;
+    if (grouped) { g_c.keys_S = (int)(3 + n_neg); g_c.keys_n_pos = n_pos; }
     FuseArgs fold = FuseArgs();
     if (krel > 1) { fold.fold_E = (int)m->ent_total; fold.fold_R = (int)m->rel_total; }
     if (fused) {
@@ -1964,7 +2012,8 @@ static int forward_counts_impl(const kge_model_desc *m, const float *d_ent, cons
         SegPlan plan;
         plan.row_span = g_c.row_span; plan.pieces = g_c.pieces; plan.n_pieces = g_c.n_pieces; plan.cap = cap;
         const int32_t *n_valid_p;
-        if ((rc = bucket_sort_records(g_c.dst, M, rows2, rpb2, &plan, stream, n_valid_p))) return rc;
+        const KeyMap km = key_map_for((int)(3 + n_neg), n_pos);
+        if ((rc = bucket_sort_records(g_c.dst, M, rows2, rpb2, &plan, stream, n_valid_p, grouped ? &km : nullptr))) return rc;
         const long long all_rows = m->ent_total + m->rel_total;
         SegApplyArgs sa = {};
         sa.rec = g_c.rec; sa.rec2_off = (unsigned)((size_t)3 * (size_t)n_pos * rd * 4); sa.ids = g_c.ids_sorted; sa.row_span = g_c.row_span;
@@ -2096,7 +2145,12 @@ int kge_counts_sort_test(const int32_t *keys, INT n_keys, INT rows, INT rpb, INT
     }
     if ((rc = hip_check(hipMemcpyAsync(g_c.dst, keys, sizeof(int32_t) * (size_t)M, hipMemcpyHostToDevice, stream), "kge_counts_sort_test: upload"))) return rc;
     const int32_t *n_live_p;
-    if ((rc = bucket_sort_records(g_c.dst, M, (int)rows, (int)rpb, with_plan ? &plan : nullptr, stream, n_live_p))) return rc;
+    // option "counts_sort_test_group" = S > 0: the keys are taken as group-major, n_keys / S groups of S (two-launch form only)
+    const int S = engine().counts_sort_test_group;
+    if (S > 0 && (S < 2 || M % S != 0 || !sort_takes_tiles(M)))
+        return fail(KGE_ERR_BAD_ARG, "kge_counts_sort_test: counts_sort_test_group needs n_keys a multiple of it and the two-launch form");
+    const KeyMap km = key_map_for(S > 0 ? S : 2, S > 0 ? M / S : 0);
+    if ((rc = bucket_sort_records(g_c.dst, M, (int)rows, (int)rpb, with_plan ? &plan : nullptr, stream, n_live_p, S > 0 ? &km : nullptr))) return rc;
     if ((rc = hip_check(hipGetLastError(), "kge_counts_sort_test: launch"))) return rc;
     if ((rc = hip_check(hipDeviceSynchronize(), "kge_counts_sort_test: synchronize"))) return rc;
     if ((rc = hip_check(hipMemcpy(sorted_keys, g_c.dst_sorted, sizeof(int32_t) * (size_t)M, hipMemcpyDeviceToHost), "kge_counts_sort_test: copy"))) return rc;
@@ -2113,12 +2167,22 @@ int kge_counts_sort_test(const int32_t *keys, INT n_keys, INT rows, INT rpb, INT
 
 int kge_transe_step_scratch_read(int which, INT offset, INT count, void *host_out) {
     if (!device_ok()) return fail(KGE_ERR_NO_DEVICE, "kge_transe_step_scratch_read: no usable HIP device");
-    const size_t have = which == 0 ? (size_t)g_c.rec.cap() : (which == 1 ? (size_t)g_c.dst.cap() : 0);
-    const void *base = which == 0 ? (const void *)g_c.rec.ptr() : (const void *)g_c.dst.ptr();
+    const size_t have = which == 0 ? (size_t)g_c.rec.cap() : (which == 1 ? (size_t)g_c.dst.cap() : (which == 2 ? (size_t)engine().inv_norm.cap() : 0));
+    const void *base = which == 0 ? (const void *)g_c.rec.ptr() : (which == 1 ? (const void *)g_c.dst.ptr() : (const void *)engine().inv_norm.ptr());
     if (!host_out || offset < 0 || count < 0 || (size_t)offset + (size_t)count > have || !base)
         return fail(KGE_ERR_BAD_ARG, "kge_transe_step_scratch_read: bad arguments");
     int rc = hip_check(hipDeviceSynchronize(), "kge_transe_step_scratch_read: synchronize");
     if (rc) return rc;
+    const int64_t S = g_c.keys_S, n_pos = g_c.keys_n_pos, M = S * n_pos;
+    if (which == 1 && S > 0 && offset < M) {   // group-major keys are handed back slot-major: word slot * n_pos + b
+        std::vector<int32_t> raw((size_t)M);
+        if ((rc = hip_check(hipMemcpy(raw.data(), base, 4 * (size_t)M, hipMemcpyDeviceToHost), "kge_transe_step_scratch_read: copy"))) return rc;
+        int32_t *out = static_cast<int32_t *>(host_out);
+        const int64_t end = std::min<int64_t>(offset + count, M);
+        for (int64_t i = offset; i < end; i++) out[i - offset] = raw[(size_t)((i % n_pos) * S + i / n_pos)];
+        if (offset + count <= M) return KGE_OK;
+        host_out = out + (end - offset); count -= end - offset; offset = end;
+    }
     return hip_check(hipMemcpy(host_out, (const char *)base + 4 * (size_t)offset, 4 * (size_t)count, hipMemcpyDeviceToHost), "kge_transe_step_scratch_read: copy");
 }
 
