@@ -631,6 +631,49 @@ int kge_transe_reduce_apply_records_sgd(const kge_model_desc *m, const uint32_t 
                                         float *d_rel, int32_t *d_rows, int32_t *d_row_counts, int32_t *d_n_rows, INT denom, float lr,
                                         void *stream);
 
+/* ---- TransE on negatives SHARED by a chunk of positives (NON-PARITY, opt-in; csrc/shared_neg.hip) ----
+ * The reference draws every negative for one positive (Base.cpp:109-139).  Here a chunk of P consecutive positives scores the
+ * same N candidate entities, as large-scale trainers do (PyTorch-BigGraph, DGL-KE): a chunk gathers 3 P + N table rows instead
+ * of P (3 + N), and the P x N distances are formed on chip.  The records are kge_transe_emit_records' records, so the reduce and
+ * apply stages above serve unchanged.
+ *   Chunks.     The positives at batch positions [j P, min((j + 1) P, n_pos)) form chunk j; n_chunks = ceil(n_pos / P), the last
+ *               may be short.  1 <= P <= 127: a candidate's count lies within +-P.  1 <= N <= 63: a positive's h-side or t-side
+ *               count lies within +-2N.  Both make the counts fit the int8 record.
+ *   Candidates. All arithmetic mod 2^64; mix(z) is the finaliser of KGE_RANKC_DRAWN below (csrc/mix_dev.hpp): z = (z ^ z >> 30) *
+ *               0xBF58476D1CE4E5B9; z = (z ^ z >> 27) * 0x94D049BB133111EB; z ^= z >> 31.  G = 0x9E3779B97F4A7C15.
+ *                   step key          S  = mix(seed + (step + 1) * G)
+ *                   candidate k of chunk j:  z = mix(S + (((j << 8) | k) + 1) * G),   id = ((z >> 32) * ent_total) >> 32
+ *               Drawn with replacement: a repeated id counts every time.
+ *   Side.       Of the pair (batch position p, candidate k): z = mix(S + (((p << 8) | 128 | k) + 1) * G), v = ((z >> 32) * 1000) >> 32.
+ *               v takes the place of the draw `rand % 1000` in the head-or-tail comparison of Base.cpp:118: (float)v < 500.0f, or
+ *               < the relation's Bernoulli value with setBern(1), means a new TAIL (side 0), else a new HEAD (side 1).
+ *   Mask.       A pair is masked exactly when its corrupted triple -- (h, r, c) for a new tail, (c, r, t) for a new head -- is a
+ *               training triple; that includes c equal to the entity it replaces.
+ *   Loss.       loss = (1 / denom) * sum over the unmasked pairs of max(p_score - n_score + margin, 0), scores sum |h^ + r^ - t^| over
+ *               l2-normalised rows (TransE.py:11-15), denom = batch_size * N.  Masked pairs contribute zero and stay in the
+ *               denominator.  A hinge tie is active and sign(0) = 0, as in kge_transe_emit_records.
+ * kge_shared_negatives_draw: one launch.  d_h / d_t / d_r: the n_pos positives (DEVICE int32); first_position: the batch position
+ *   of the first of them, a multiple of P (chunk j of the call is chunk first_position / P + j of the batch).  Writes d_cand
+ *   (int32 [n_chunks][N]) and d_pair (uint8 [n_pos][N]: bit 0 = side, bit 1 = masked).  The mask is looked up in the sampler's
+ *   sorted lists -- the known tails of (h, r), the known heads of (t, r) -- by the sampler's bisection; the lists of a positive
+ *   are found by the same bisection in a directory of the groups' keys taken from the index's group records (the sampler finds
+ *   them through the training triple it picked, which the ids alone do not name).  A positive whose (h, r) / (t, r) has no
+ *   training triple masks nothing on that side.  ent_total, the Bernoulli values and setBern are the imported training set's.
+ * kge_transe_emit_records_shared: gather / score / hinge of the chunks against the lists in d_cand / d_pair (inputs: any lists,
+ *   not only drawn ones) and 3 n_pos + n_chunks N records in kge_transe_emit_records' format (kge_transe_record_dwords words
+ *   each, keys in the [0, E) + [E, E + R) row space, -1 = no record): record s * n_pos + b for slot s = 0 / 1 / 2 (h / t / r) of
+ *   positive b, then record 3 n_pos + j N + k for candidate k of chunk j.  A candidate without an active pair has key -1; so has an
+ *   h, t or r slot whose count vector is all zero.  An id outside [0, ent_total) in d_cand is masked for every pair; a positive
+ *   with an id outside its table takes no part.  d_h / d_t / d_r hold n_pos positives (`stride` >= n_pos is the arrays' length
+ *   and otherwise unused); d_loss receives the loss of this call's positives.  The norms are computed from the gathered rows.
+ *   KGE_ERR_UNSUPPORTED, with a message: another model, negative_rel != 0, P or N outside their ranges, a shape outside
+ *   kge_transe_counts_supported, an embedding width above 512 (the kernel's LDS tiles). */
+int kge_shared_negatives_draw(const int32_t *d_h, const int32_t *d_t, const int32_t *d_r, INT n_pos, INT first_position, INT P, INT N,
+                              uint64_t seed, INT step, int32_t *d_cand, uint8_t *d_pair, void *stream);
+int kge_transe_emit_records_shared(const kge_model_desc *m, const float *d_ent, const float *d_rel, const int32_t *d_h, const int32_t *d_t,
+                                   const int32_t *d_r, INT n_pos, INT stride, INT P, const int32_t *d_cand, INT N, const uint8_t *d_pair,
+                                   INT denom, uint32_t *d_rec, int32_t *d_dst, float *d_loss, void *stream);
+
 /* ---- Table-sharded sparse path (N GPUs, BASELINE config #5): rank g OWNS the entity rows [g*chunk, (g+1)*chunk); what the
  * reference does with ps tasks holding the variables and workers pulling rows / pushing IndexedSlices over gRPC
  * (distribute_training.py:193-196) becomes: request ids -> all-to-all -> owners gather rows -> all-to-all -> emit records

@@ -54,6 +54,7 @@ class Config(object):
             self.test_triple_classification = False
             self.valid_triple_classification = False
             self.type_constrained_sampling = False
+            self._shared_chunk, self._shared_seed = 0, 0      # set_shared_negatives
             # engine-side additions
             self.seed = 0                 # parameter initialisation seed
             self.device = "cuda"
@@ -138,9 +139,49 @@ class Config(object):
         from the file: after init_evaluation_from_arrays(..., type_lists=...) / (..., derive_types=True) or
         derive_type_constraints() the engine's lists are used as they stand, which is how a graph given by init_from_arrays
         gets typed negatives."""
+        if flag and self._shared_chunk:
+            raise KgeError("type-constrained sampling cannot be combined with shared negatives: the shared candidates are drawn "
+                           "from all entities (typed candidates are not built)")
         self.type_constrained_sampling = bool(flag)
         if getattr(self, "trainTotal", None) is not None:      # after init(): switch the engine now
             self._apply_typed_sampling()
+
+    def set_shared_negatives(self, chunk, seed=0):
+        """Negatives SHARED by chunks of positives (NON-PARITY, opt-in, off by default; the reference draws every negative for
+        one positive): `chunk` consecutive positives of a batch score the same set_ent_neg_rate(N) candidate entities, drawn
+        from a counter hash of (seed, global_step) -- what PyTorch-BigGraph and DGL-KE do -- so a chunk gathers 3 chunk + N table
+        rows instead of chunk (3 + N).  A pair whose corrupted triple is a training triple is masked: it adds nothing to the loss
+        and stays in its denominator (include/kge_mi355.h has the exact definition).  TransE on the sign-count path with SGD,
+        LazyAdam or Adagrad, one rank, entity negatives only, 1 <= chunk <= 127, N <= 63.  Call it before
+        set_model_and_session; chunk = 0 switches it off.  In this mode prefetch_sampling is ignored (the positives are drawn
+        when the step starts), hand-fed batches are refused and there is no persistent launch."""
+        if self.trainModel is not None:
+            raise KgeError("set_shared_negatives must be called before set_model_and_session: it decides the step's path")
+        chunk = int(chunk)
+        if chunk and not 1 <= chunk <= step_plan.SHARED_MAX_CHUNK:
+            raise KgeError("shared negatives: a chunk holds 1 to %d positives (a candidate's count lies within +-chunk and is "
+                           "carried as an int8), got %d" % (step_plan.SHARED_MAX_CHUNK, chunk))
+        if chunk and self.type_constrained_sampling:
+            raise KgeError("shared negatives cannot be combined with type-constrained sampling: the shared candidates are drawn "
+                           "from all entities (typed candidates are not built)")
+        self._shared_chunk, self._shared_seed = chunk, int(seed) & 0xFFFFFFFFFFFFFFFF
+
+    def _refuse_shared_ranks(self):
+        if self._shared_chunk and self._dp:
+            raise KgeError("shared negatives train on one rank only: more than one rank, or a row-sharded entity table, has no "
+                           "shared-negatives step")
+
+    def shared_negatives_of(self, step):
+        """(cand int32 [n_chunks, N], pair uint8 [batch, N]) of the batch that training step `step` (its global_step when it
+        began) trained on: the candidate ids of every chunk, and per (positive, candidate) bit 0 = side (0 new tail, 1 new head),
+        bit 1 = masked.  An inspector: the lists of the most recent step are kept, no others (a pair's mask depends on the step's
+        positives, which are not)."""
+        buf = self._sparse_buf if self._shared_chunk else None
+        if not buf or buf.get("shared_step") != int(step):
+            raise KgeError("shared_negatives_of: only the lists of the most recent shared-negatives step are kept (step %s)"
+                           % (buf.get("shared_step") if buf else None))
+        n_pos, n_chunks = buf["shared_shape"]
+        return buf["cand"][:n_chunks].cpu().numpy(), buf["pair"][:n_pos].cpu().numpy()
 
     def _forget_evaluation(self, arrays=False):
         """A new training or evaluation import: what an earlier import by arrays left behind no longer describes the engine.
@@ -393,11 +434,16 @@ class Config(object):
         p = self._plan = step_plan.plan(
             probe.model_id, self.opt_method, getattr(self, "sparse_rows", None), getattr(self, "use_counts", True),
             self.lib.kge_transe_counts_supported(ctypes.byref(probe.descriptor()), n_neg), self.entTotal, self.relTotal,
-            self.hidden_size, self.batch_size, n_neg, getattr(self, "sparse_threshold_bytes", None), self.adagrad_initial_accumulator)
+            self.hidden_size, self.batch_size, n_neg, getattr(self, "sparse_threshold_bytes", None), self.adagrad_initial_accumulator,
+            shared_chunk=self._shared_chunk, negative_rel=self.negative_rel)
+        if self._shared_chunk and self.type_constrained_sampling:
+            raise KgeError("shared negatives cannot be combined with type-constrained sampling: the shared candidates are drawn "
+                           "from all entities (typed candidates are not built)")
         self.use_counts, self.sparse_rows, self.sparse_inplace = p.use_counts, p.sparse_rows, p.sparse_inplace
         self._adam, self._lazy_adam, self._adagrad = p.adam, p.lazy_adam, p.adagrad
         self._has_slots, self._rows_rule = p.has_slots, p.rows_rule
-        self._shard_plan = self._plan_entity_shard(probe.model_id)
+        self._refuse_shared_ranks()
+        self._shard_plan = None if self._shared_chunk else self._plan_entity_shard(probe.model_id)
         self.trainModel = self.model(config=self, define=True)
         m = self.trainModel
         self._desc = m.descriptor()
@@ -414,6 +460,7 @@ class Config(object):
         self._refresh_pointers()
         self._dist_ready = 0
         self._dev_batch = None
+        self._dev_positives = None     # the shared-negatives step's batch: positives alone (_sample_positives)
         self._dev_pack = None          # the sampler's packed negatives of the two batch slots (_pack_for)
         self._batch_pack = 0           # pack of the batch the current step trains on (device pointer; 0 = none)
         self._prefetched_pack = 0      # ... of the batch drawn ahead
@@ -490,6 +537,7 @@ class Config(object):
         from .parallel import thread_range
         lo, hi = thread_range(self.rank, self.world_size, self.workThreads)
         self._thread_lo, self._thread_hi = lo, hi
+        self._refuse_shared_ranks()
         first = ctypes.c_int64(0)
         self._n_local = self.lib.kge_slice_positions(self.batch_size, lo, hi, ctypes.byref(first))
         self._first_pos = first.value
@@ -562,6 +610,19 @@ class Config(object):
                                                        self._thread_lo, self._thread_hi, stride, ctypes.byref(nl),
                                                        self._stream()), self.lib)
         self._batch_pack = pack        # (a pack goes with the batch drawn in the same call, and with no other)
+        return buf, nl.value
+
+    def _sample_positives(self):
+        """This rank's positives of the next batch alone (the sampler at negRate = 0, one draw per positive): (int32 [3, stride]
+        tensor, n_pos) -- the shared-negatives step's batch."""
+        import torch
+        stride = max(self._n_local, 1)
+        if getattr(self, "_dev_positives", None) is None or self._dev_positives.shape[1] != stride:
+            self._dev_positives = torch.zeros((3, stride), dtype=torch.int32, device=self.device)
+        buf = self._dev_positives
+        nl = ctypes.c_int64(0)
+        _lib.check(self.lib.kge_sampling_device(buf[0].data_ptr(), buf[1].data_ptr(), buf[2].data_ptr(), self.batch_size, 0, 0,
+                                                self._thread_lo, self._thread_hi, stride, ctypes.byref(nl), self._stream()), self.lib)
         return buf, nl.value
 
     def _next_sampled_batch(self):
@@ -723,6 +784,15 @@ class Config(object):
         if getattr(self, "_ent_is_shard", False) and not hasattr(self, "_shard"):
             raise KgeError("the entity table was created as this rank's shard of a row-sharded table (the process belongs to a "
                            "torch.distributed world): call init_distributed() before training")
+        if self._shared_chunk:
+            if batch_h is not None:
+                raise KgeError("shared negatives: a hand-fed batch is refused (the step draws its own positives and hashes its "
+                               "candidates from the global step)")
+            self._refuse_shared_ranks()
+            dev, n_pos = self._sample_positives()
+            train_paths.shared_step(self, dev, n_pos, max(self._n_local, 1), self.batch_size * self.negative_ent)
+            self.trainModel.loss = self._loss
+            return float(self._loss.item()) if sync else self._loss
         if batch_h is None:
             dev, n_pos = self._next_sampled_batch() if self.prefetch_sampling else self.sample_device()
             stride = max(self._n_local, 1)
@@ -762,7 +832,7 @@ class Config(object):
         """Can train_steps() run its steps inside one persistent launch (csrc/persist.hip)?  Single process, the dense
         fp32-accumulator path of TransE / TransH / TransD at a launch-latency-bound step size.  Not with type-constrained
         sampling: the persistent kernel has the untyped sampler only."""
-        if self.type_constrained_sampling or self._adagrad:       # (persist.hip has the SGD and Adam sweeps only)
+        if self.type_constrained_sampling or self._adagrad or self._shared_chunk:       # (persist.hip has the SGD and Adam sweeps only, and independent negatives)
             return False
         if self._dp or self.sparse_rows or self.sparse_inplace or self.hidden_size > 256:
             return False
@@ -794,7 +864,9 @@ class Config(object):
         if use and not self.persistent_supported():
             raise KgeError("train_steps(persistent=True): this configuration has no persistent-launch path" +
                            (" (type-constrained sampling is on: the persistent kernel samples untyped negatives only)"
-                            if self.type_constrained_sampling else ""))
+                            if self.type_constrained_sampling else "") +
+                           (" (shared negatives are on: the persistent kernel draws every negative for one positive)"
+                            if self._shared_chunk else ""))
         if not use:
             out = [self.train_step(sync=False).clone() for _ in range(n_steps)]   # (the loss scalar is one reused device buffer)
             return torch.stack([o.reshape(()) for o in out]).cpu().numpy()

@@ -148,6 +148,7 @@ static std::string build_and_adopt(int64_t E, int64_t R, int64_t nb, int64_t n, 
     }
     build_magic_tables(e.index, e.sampler_magic_len);
     e.dev.tables_uploaded = false;
+    e.index_generation++;
     return "";
 }
 

@@ -51,6 +51,7 @@ struct Engine {
     int64_t work_threads = 1;                 // Setting.h:34
     int64_t bern = 0;                         // Setting.h:108
     KgIndex index;
+    unsigned long long index_generation = 0;   // counts the training sets adopted: what is derived from `index` elsewhere (shared_neg.hip's group directory) knows by it when it is stale
     LibcRand libc;
     std::vector<uint64_t> streams;  // host view of next_random[] (Random.h:6)
     LcgJumpTable jump = make_jump_table();

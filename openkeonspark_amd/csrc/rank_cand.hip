@@ -27,6 +27,7 @@
 #include <type_traits>
 
 #include "eval_dev.hpp"
+#include "mix_dev.hpp"
 #include "models_dev.hpp"
 #include "team.hpp"
 #include "team_shape.hpp"
@@ -55,11 +56,7 @@ struct RankCandArgs {
 // candidate k of (triple i, side s) as an index into a list of `len` entries (the header has the formula)
 __host__ __device__ inline long long drawn_index(unsigned long long seed, long long i, int s, long long k, long long len) {
     const unsigned long long c = ((unsigned long long)(2 * i + s) << 32) | (unsigned long long)k;
-    unsigned long long z = seed + (c + 1ULL) * 0x9E3779B97F4A7C15ULL;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ULL;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBULL;
-    z ^= z >> 31;
-    return (long long)(((z >> 32) * (unsigned long long)len) >> 32);
+    return (long long)mix_scale(mix64(seed + (c + 1ULL) * kMixGamma), (unsigned long long)len);
 }
 
 // The row-range form (kge_rank_candidates_range): `ent` holds the rows of the global ids [row_lo, row_lo + rows) only, and the

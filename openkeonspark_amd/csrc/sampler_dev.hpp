@@ -135,13 +135,23 @@ __device__ __forceinline__ uint32_t mod_u64_u32(uint64_t s, uint32_t d) {
 
 // Corrupt.h:25-36 in closed form: the tmp-th id (0-based) that is NOT in the strictly increasing
 // list vals[0..len) is tmp + #{j : vals[j] - j <= tmp}; the predicate is monotone in j.
-__device__ __forceinline__ int filtered_pick(const int32_t *__restrict__ vals, int len, long long tmp) {
+// The bisection itself: how many of the positions [0, len) a monotone predicate (true, ..., true, false, ..., false) holds for.
+template <class Pred>
+__device__ __forceinline__ int bisect_count(int len, Pred pred) {
     int lo = 0, hi = len;
     while (lo < hi) {
         int mid = (lo + hi) >> 1;
-        if ((long long)vals[mid] - mid <= tmp) lo = mid + 1; else hi = mid;
+        if (pred(mid)) lo = mid + 1; else hi = mid;
     }
-    return (int)(tmp + lo);
+    return lo;
+}
+__device__ __forceinline__ int filtered_pick(const int32_t *__restrict__ vals, int len, long long tmp) {
+    return (int)(tmp + bisect_count(len, [&](int mid) { return (long long)vals[mid] - mid <= tmp; }));
+}
+// Is `id` one of the strictly increasing vals[0..len)?  The membership form of the same search (kge_shared_negatives_draw's mask).
+__device__ __forceinline__ bool sorted_contains(const int32_t *__restrict__ vals, int len, int id) {
+    const int at = bisect_count(len, [&](int mid) { return vals[mid] < id; });
+    return at < len && vals[at] == id;
 }
 
 // The draw of one corruption (Corrupt.h:25-36): tmp = s mod (total - len), then the same pick by an (M + 1)-ary search -- a level

@@ -1,0 +1,455 @@
+// TransE on negatives SHARED by a chunk of positives (NON-PARITY, opt-in; the definition is in include/kge_mi355.h).
+//
+// A chunk of P consecutive positives scores the same N candidate entities, so it gathers 3 P + N table rows instead of
+// P (3 + N); the P x N distances are formed on chip.  Two kernels:
+//
+//   shared_draw_kernel   one thread per (positive, candidate) pair and per candidate: the counter hashes of the definition, and the
+//                        mask -- is the corrupted triple a training triple? -- by the sampler's bisection (sampler_dev.hpp
+//                        bisect_count) in the sorted tails of (h, r) / heads of (t, r).  The sampler finds those lists through the
+//                        training triple it picked; here only the ids are known, so the (h, r) and (t, r) groups are found by the
+//                        same bisection in a directory of the groups' keys (GroupDir: one key and one span per group of the
+//                        index, taken from its group records once per imported training set).
+//   shared_emit_kernel   one workgroup per chunk.  The chunk's candidates are normalised once into LDS (tiles of T candidates
+//                        when N rows do not fit the budget); a wave then owns one positive at a time -- h, t, r normalised in
+//                        registers, lane l holding elements 4 (l + 64 q) .. + 3 -- and walks the tile: distance from the LDS row,
+//                        one wave reduction, hinge.  An active pair adds its signs to the positive's three integer vectors in
+//                        registers and, transposed, to the candidate's: one LDS add per dword on byte fields that hold
+//                        sum (g + 1), g in {-1, 0, 1} -- at most 2 P <= 254, so no field carries into its neighbour -- from which
+//                        the tile's end subtracts the candidate's number of active pairs.  Records leave in
+//                        kge_transe_emit_records' format for the width's team shape (natural element order at multiples of 4,
+//                        the strided team order elsewhere), through an element-ordered byte image in LDS.
+//                        With more than one tile a positive's records are completed tile by tile: the wave that wrote them adds
+//                        the next tile's share to its own earlier stores.
+// The loss is summed per wave in candidate order, per chunk in wave order and over the chunks in index order: a step is
+// reproducible bit for bit.
+#include <algorithm>
+#include <vector>
+
+#include "engine.hpp"
+#include "mix_dev.hpp"
+#include "sampler_dev.hpp"
+#include "team.hpp"
+
+namespace kge {
+
+void transe_team_shape(int D, int &L, int &C);   // models.hip
+
+namespace {
+
+// ---- the (h, r) / (t, r) groups of the index by key ------------------------------------------------
+struct GroupDir {
+    DevBuf<long long> hr_key, tr_key;    // anchor * rel_total + relation, increasing
+    DevBuf<int2> hr_span, tr_span;       // (offset, length) into tails_hr / heads_tr
+    int n_hr = 0, n_tr = 0;
+    unsigned long long generation = ~0ull;
+};
+GroupDir g_dir;
+DevBuf<float> g_partials;
+
+int ensure_group_dir() {
+    Engine &e = engine();
+    if (g_dir.generation == e.index_generation && g_dir.hr_key) return KGE_OK;
+    const KgIndex &ix = e.index;
+    struct Ent { long long key; int off, len; };
+    std::vector<Ent> hr((size_t)ix.train_dup), tr((size_t)ix.train_dup);
+    for (int64_t i = 0; i < ix.train_dup; i++) {
+        const Int4 &p = ix.pos[(size_t)i], &g = ix.grp[(size_t)i];
+        hr[(size_t)i] = {(long long)p.x * ix.rel_total + p.z, g.x, g.y};
+        tr[(size_t)i] = {(long long)p.y * ix.rel_total + p.z, g.z, g.w};
+    }
+    int rc;
+    auto put = [&](std::vector<Ent> &v, DevBuf<long long> &keys, DevBuf<int2> &spans, int &n) -> int {
+        std::sort(v.begin(), v.end(), [](const Ent &a, const Ent &b) { return a.key < b.key; });
+        v.erase(std::unique(v.begin(), v.end(), [](const Ent &a, const Ent &b) { return a.key == b.key; }), v.end());
+        std::vector<long long> k(v.size());
+        std::vector<Int2> s(v.size());
+        for (size_t i = 0; i < v.size(); i++) { k[i] = v[i].key; s[i] = {v[i].off, v[i].len}; }
+        n = (int)v.size();
+        if ((rc = keys.upload(k, "upload group keys"))) return rc;
+        return spans.upload(s, "upload group spans");
+    };
+    g_dir.generation = ~0ull;
+    if ((rc = put(hr, g_dir.hr_key, g_dir.hr_span, g_dir.n_hr))) return rc;
+    if ((rc = put(tr, g_dir.tr_key, g_dir.tr_span, g_dir.n_tr))) return rc;
+    g_dir.generation = e.index_generation;
+    return KGE_OK;
+}
+
+struct DrawArgs {
+    const int32_t *h, *t, *r;
+    long long n_pos, first_position, n_chunks;
+    int P, N;
+    unsigned long long S;            // the step key
+    int ent_total, rel_total, bern;
+    const float *bern_prob;
+    const int32_t *tails_hr, *heads_tr;
+    const long long *hr_key, *tr_key;
+    const int2 *hr_span, *tr_span;
+    int n_hr, n_tr;
+    int32_t *cand;
+    uint8_t *pair;
+};
+
+__device__ __forceinline__ int shared_candidate(unsigned long long S, long long chunk, int k, int ent_total) {
+    const unsigned long long c = ((unsigned long long)chunk << 8) | (unsigned long long)k;
+    return (int)mix_scale(mix64(S + (c + 1ULL) * kMixGamma), (unsigned long long)ent_total);
+}
+
+__global__ __launch_bounds__(256) void shared_draw_kernel(DrawArgs a) {
+    const long long n_pair = a.n_pos * a.N, n_all = n_pair + a.n_chunks * a.N;
+    const long long chunk0 = a.first_position / a.P;
+    for (long long g = (long long)blockIdx.x * 256 + threadIdx.x; g < n_all; g += (long long)gridDim.x * 256) {
+        if (g >= n_pair) {
+            const long long j = (g - n_pair) / a.N;
+            const int k = (int)((g - n_pair) % a.N);
+            a.cand[g - n_pair] = shared_candidate(a.S, chunk0 + j, k, a.ent_total);
+            continue;
+        }
+        const long long b = g / a.N;
+        const int k = (int)(g % a.N);
+        const int c = shared_candidate(a.S, chunk0 + b / a.P, k, a.ent_total);
+        const int h = a.h[b], t = a.t[b], r = a.r[b];
+        const bool r_ok = r >= 0 && r < a.rel_total;
+        // the head-or-tail coin of sample_slot with v in the place of rand % 1000: same threshold, same float comparison
+        const unsigned long long pc = ((unsigned long long)(a.first_position + b) << 8) | 128ULL | (unsigned long long)k;
+        const unsigned long long v = mix_scale(mix64(a.S + (pc + 1ULL) * kMixGamma), 1000ULL);
+        const float prob = (a.bern && r_ok) ? a.bern_prob[r] : 500.0f;
+        const bool keep_head = (float)v < prob;      // true: new tail
+        const int anchor = keep_head ? h : t;
+        bool masked = false;
+        if (r_ok && anchor >= 0 && anchor < a.ent_total) {
+            const long long key = (long long)anchor * a.rel_total + r;
+            const long long *keys = keep_head ? a.hr_key : a.tr_key;
+            const int n = keep_head ? a.n_hr : a.n_tr;
+            const int at = bisect_count(n, [&](int mid) { return keys[mid] < key; });
+            if (at < n && keys[at] == key) {
+                const int2 sp = (keep_head ? a.hr_span : a.tr_span)[at];
+                masked = sorted_contains((keep_head ? a.tails_hr : a.heads_tr) + sp.x, sp.y, c);
+            }
+        }
+        a.pair[g] = (uint8_t)((keep_head ? 0 : 1) | (masked ? 2 : 0));
+    }
+}
+
+// ---- the emit kernel -----------------------------------------------------------------------------
+struct SharedEmitArgs {
+    const float *ent, *rel;
+    const int32_t *h, *t, *r;
+    const int32_t *cand;
+    const uint8_t *pair;
+    long long n_pos, n_chunks;
+    int P, N, T, n_tiles;        // candidates per tile, tiles
+    int D, RS;                   // width; LDS row stride in floats (D rounded up to 4)
+    int RD, L, nat;              // record dwords; the width's team shape; natural element order
+    int ent_total, rel_total;
+    float margin;
+    uint32_t *rec;
+    int32_t *dst;
+    float *partials;
+};
+
+__device__ __forceinline__ uint32_t padd8(uint32_t x, uint32_t y) {  // per-byte add, no carry across bytes
+    return ((x & 0x7F7F7F7Fu) + (y & 0x7F7F7F7Fu)) ^ ((x ^ y) & 0x80808080u);
+}
+// element held by byte j of record dword w
+__device__ __forceinline__ int record_element(const SharedEmitArgs &a, int w, int j) {
+    return a.nat ? 4 * w + j : (w % a.L) + a.L * (4 * (w / a.L) + j);
+}
+__device__ __forceinline__ void wave_lds_order() {   // LDS traffic inside one wave: stores before the loads that follow
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+__device__ __forceinline__ int sgn_i(float e) { return (e > 0.f ? 1 : 0) - (e < 0.f ? 1 : 0); }
+
+template <int Q, bool VEC>
+__global__ __launch_bounds__(256) void shared_emit_kernel(SharedEmitArgs a) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
+    const int T = a.T, RS = a.RS, D = a.D;
+    float *crow = reinterpret_cast<float *>(lds);                                  // [T][RS] normalised candidate rows
+    uint32_t *ccnt = reinterpret_cast<uint32_t *>(lds + (size_t)T * RS * 4);       // [T][RS / 4] byte fields sum (g + 1)
+    int *nact = reinterpret_cast<int *>(lds + (size_t)T * RS * 5);                 // [T] active pairs
+    int *cid = nact + T;                                                           // [T] id, -1 = outside the table
+    uint8_t *stage_all = reinterpret_cast<uint8_t *>(cid + T);                     // [4 waves][3][RS] element-ordered bytes
+    float *wl = reinterpret_cast<float *>(stage_all + 4 * 3 * RS);                 // [4] wave losses
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    uint8_t *stage = stage_all + wave * 3 * RS;
+    const long long j = blockIdx.x;
+    const long long b0 = j * a.P;
+    const int Pc = (int)min((long long)a.P, a.n_pos - b0);
+    bool valid[Q];
+#pragma unroll
+    for (int q = 0; q < Q; q++) valid[q] = 4 * (lane + 64 * q) < RS;
+    auto load_row = [&](const float *__restrict__ tab, long long row, float (&x)[4 * Q]) {
+        const float *p = tab + row * D;
+#pragma unroll
+        for (int q = 0; q < Q; q++) {
+            const int e0 = 4 * (lane + 64 * q);
+            if constexpr (VEC) {
+                const float4 v = valid[q] ? *reinterpret_cast<const float4 *>(p + e0) : make_float4(0.f, 0.f, 0.f, 0.f);
+                x[4 * q] = v.x; x[4 * q + 1] = v.y; x[4 * q + 2] = v.z; x[4 * q + 3] = v.w;
+            } else {
+#pragma unroll
+                for (int i = 0; i < 4; i++) x[4 * q + i] = e0 + i < D ? p[e0 + i] : 0.f;
+            }
+        }
+    };
+    auto normalise = [&](float (&x)[4 * Q]) {
+        float ss = 0.f;
+#pragma unroll
+        for (int c = 0; c < 4 * Q; c++) ss = __builtin_fmaf(x[c], x[c], ss);
+        ss = team_sum<64>(ss);
+        const float inv = 1.0f / sqrtf(ss >= 1e-12f ? ss : 1e-12f);
+#pragma unroll
+        for (int c = 0; c < 4 * Q; c++) x[c] *= inv;
+    };
+    float lsum = 0.f;
+    for (int tile = 0; tile < a.n_tiles; tile++) {
+        const int k0 = tile * T;
+        const int Tc = min(T, a.N - k0);
+        // ---- the tile's candidates: normalised rows into LDS, counters cleared ----
+        for (int i = threadIdx.x; i < T * (RS / 4); i += 256) ccnt[i] = 0;
+        if ((int)threadIdx.x < T) nact[threadIdx.x] = 0;
+        for (int kt = wave; kt < Tc; kt += 4) {
+            const int id = a.cand[j * a.N + k0 + kt];
+            const bool ok = id >= 0 && id < a.ent_total;
+            float x[4 * Q];
+            load_row(a.ent, ok ? id : 0, x);
+            normalise(x);
+#pragma unroll
+            for (int q = 0; q < Q; q++)
+                if (valid[q])
+                    *reinterpret_cast<float4 *>(crow + (size_t)kt * RS + 4 * (lane + 64 * q)) =
+                        ok ? make_float4(x[4 * q], x[4 * q + 1], x[4 * q + 2], x[4 * q + 3]) : make_float4(0.f, 0.f, 0.f, 0.f);
+            if (lane == 0) cid[kt] = ok ? id : -1;
+        }
+        __syncthreads();
+        // ---- positives: one wave each ----
+        for (int pp = wave; pp < Pc; pp += 4) {
+            const long long b = b0 + pp;
+            const int h = a.h[b], t = a.t[b], r = a.r[b];
+            const bool ids_ok = h >= 0 && h < a.ent_total && t >= 0 && t < a.ent_total && r >= 0 && r < a.rel_total;
+            int my_pb = 2;
+            if (lane < Tc) my_pb = a.pair[b * a.N + k0 + lane];
+            float B0[4 * Q], B1[4 * Q];       // new head: e = c^ + (r^ - t^);  new tail: e = (h^ + r^) - c^
+            int sp[4 * Q], Ah[4 * Q], At[4 * Q], Ar[4 * Q];
+            float p_score;
+            {
+                float H[4 * Q], Tn[4 * Q], R[4 * Q];
+                load_row(a.ent, ids_ok ? h : 0, H); load_row(a.ent, ids_ok ? t : 0, Tn); load_row(a.rel, ids_ok ? r : 0, R);
+                normalise(H); normalise(Tn); normalise(R);
+                float acc = 0.f;
+#pragma unroll
+                for (int c = 0; c < 4 * Q; c++) {
+                    B0[c] = R[c] - Tn[c];
+                    B1[c] = H[c] + R[c];
+                    const float e = H[c] + R[c] - Tn[c];
+                    acc += fabsf(e);
+                    sp[c] = sgn_i(e);
+                    Ah[c] = 0; At[c] = 0; Ar[c] = 0;
+                }
+                p_score = team_sum<64>(acc);
+            }
+            int cnt = 0;
+            if (ids_ok) {
+                for (int kt = 0; kt < Tc; kt++) {
+                    const int pb = __builtin_amdgcn_readlane(my_pb, kt);
+                    if ((pb & 2) || cid[kt] < 0) continue;
+                    const bool new_head = pb & 1;
+                    float e[4 * Q];
+                    float acc = 0.f;
+#pragma unroll
+                    for (int q = 0; q < Q; q++) {
+                        float4 c4 = make_float4(0.f, 0.f, 0.f, 0.f);
+                        if (valid[q]) c4 = *reinterpret_cast<const float4 *>(crow + (size_t)kt * RS + 4 * (lane + 64 * q));
+                        const float cv[4] = {c4.x, c4.y, c4.z, c4.w};
+#pragma unroll
+                        for (int i = 0; i < 4; i++) {
+                            const int c = 4 * q + i;
+                            e[c] = new_head ? cv[i] + B0[c] : B1[c] - cv[i];
+                            acc += fabsf(e[c]);
+                        }
+                    }
+                    const float n_score = team_sum<64>(acc);
+                    const float v = p_score - n_score + a.margin;
+                    if (!(v >= 0.f)) continue;     // a tie is active
+                    cnt++; lsum += v;
+#pragma unroll
+                    for (int q = 0; q < Q; q++) {
+                        uint32_t f = 0;
+#pragma unroll
+                        for (int i = 0; i < 4; i++) {
+                            const int c = 4 * q + i;
+                            const int s = sgn_i(e[c]);
+                            // new head: the candidate takes -s, the kept t +s, r -s;  new tail: the candidate +s, the kept h -s, r -s
+                            const int g = new_head ? -s : s;
+                            if (new_head) At[c] += s; else Ah[c] -= s;
+                            Ar[c] -= s;
+                            f |= (uint32_t)(g + 1) << (8 * i);
+                        }
+                        if (valid[q]) atomicAdd(ccnt + (size_t)kt * (RS / 4) + lane + 64 * q, f);
+                    }
+                    if (lane == 0) atomicAdd(nact + kt, 1);
+                }
+            }
+            // ---- the positive's three records: this tile's share, in element order, then in the record's dword order ----
+#pragma unroll
+            for (int q = 0; q < Q; q++) {
+                if (!valid[q]) continue;
+                uint32_t wh = 0, wt = 0, wr = 0;
+#pragma unroll
+                for (int i = 0; i < 4; i++) {
+                    const int c = 4 * q + i, v = cnt * sp[c];
+                    wh |= (uint32_t)((Ah[c] + v) & 0xFF) << (8 * i);
+                    wt |= (uint32_t)((At[c] - v) & 0xFF) << (8 * i);
+                    wr |= (uint32_t)((Ar[c] + v) & 0xFF) << (8 * i);
+                }
+                uint32_t *s32 = reinterpret_cast<uint32_t *>(stage);
+                s32[lane + 64 * q] = wh; s32[RS / 4 + lane + 64 * q] = wt; s32[2 * (RS / 4) + lane + 64 * q] = wr;
+            }
+            wave_lds_order();
+            const bool last = tile == a.n_tiles - 1;
+            bool any[3] = {false, false, false};
+#pragma unroll
+            for (int s = 0; s < 3; s++) {
+                uint32_t *out = a.rec + ((long long)s * a.n_pos + b) * (long long)a.RD;
+                for (int w = lane; w < a.RD; w += 64) {
+                    uint32_t word = 0;
+#pragma unroll
+                    for (int i = 0; i < 4; i++) {
+                        const int el = record_element(a, w, i);
+                        if (el < D) word |= (uint32_t)stage[s * RS + el] << (8 * i);
+                    }
+                    if (tile > 0) word = padd8(word, out[w]);
+                    out[w] = word;
+                    any[s] = any[s] || word != 0;
+                }
+            }
+            wave_lds_order();     // (the image is rewritten for the wave's next positive)
+            if (last) {
+                const bool nz_h = __ballot(any[0]) != 0, nz_t = __ballot(any[1]) != 0, nz_r = __ballot(any[2]) != 0;
+                if (lane == 0) {
+                    a.dst[b] = nz_h ? h : -1;
+                    a.dst[a.n_pos + b] = nz_t ? t : -1;
+                    a.dst[2 * a.n_pos + b] = nz_r ? a.ent_total + r : -1;
+                }
+            }
+        }
+        __syncthreads();
+        // ---- the tile's candidate records ----
+        for (int i = threadIdx.x; i < Tc * a.RD; i += 256) {
+            const int kt = i / a.RD, w = i % a.RD;
+            const int n = nact[kt];
+            const uint8_t *fields = reinterpret_cast<const uint8_t *>(ccnt + (size_t)kt * (RS / 4));
+            uint32_t word = 0;
+#pragma unroll
+            for (int q = 0; q < 4; q++) {
+                const int el = record_element(a, w, q);
+                if (el < D) word |= (uint32_t)(((int)fields[el] - n) & 0xFF) << (8 * q);
+            }
+            a.rec[(3 * a.n_pos + j * a.N + k0 + kt) * (long long)a.RD + w] = word;
+        }
+        if ((int)threadIdx.x < Tc) a.dst[3 * a.n_pos + j * a.N + k0 + threadIdx.x] = nact[threadIdx.x] > 0 ? cid[threadIdx.x] : -1;
+        __syncthreads();
+    }
+    if (lane == 0) wl[wave] = lsum;
+    __syncthreads();
+    if (threadIdx.x == 0) a.partials[j] = ((wl[0] + wl[1]) + wl[2]) + wl[3];
+}
+
+// fixed-order sum of the chunks' partial hinge sums -> loss = sum / denom
+__global__ __launch_bounds__(256) void shared_loss_kernel(const float *__restrict__ partials, long long n, float unit, float *out) {
+    __shared__ float sh[256];
+    float s = 0.f;
+    for (long long i = threadIdx.x; i < n; i += 256) s += partials[i];
+    sh[threadIdx.x] = s;
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {
+        if ((int)threadIdx.x < w) sh[threadIdx.x] += sh[threadIdx.x + w];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) out[0] = sh[0] * unit;
+}
+
+constexpr int kLdsBudget = 60 * 1024;   // per workgroup: two chunks per CU at the widest shapes, five at the headline shape
+
+}  // namespace
+}  // namespace kge
+
+using namespace kge;
+
+extern "C" {
+
+int kge_shared_negatives_draw(const int32_t *d_h, const int32_t *d_t, const int32_t *d_r, INT n_pos, INT first_position, INT P, INT N,
+                              uint64_t seed, INT step, int32_t *d_cand, uint8_t *d_pair, void *stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    if (P < 1 || P > 127) return fail(KGE_ERR_BAD_ARG, "kge_shared_negatives_draw: the chunk must hold 1..127 positives (a candidate's count is within +-P, an int8)");
+    if (N < 1 || N > 63) return fail(KGE_ERR_BAD_ARG, "kge_shared_negatives_draw: 1..63 negatives per positive (a positive's count is within +-2N, an int8)");
+    if (n_pos < 0 || first_position < 0 || first_position % P != 0 || step < 0 || !d_h || !d_t || !d_r || !d_cand || !d_pair)
+        return fail(KGE_ERR_BAD_ARG, "kge_shared_negatives_draw: bad arguments (first_position must be a multiple of the chunk)");
+    int rc = ensure_device_index();
+    if (rc) return rc;
+    if ((rc = ensure_group_dir())) return rc;
+    if (n_pos == 0) return KGE_OK;
+    Engine &e = engine();
+    DrawArgs a = {};
+    a.h = d_h; a.t = d_t; a.r = d_r;
+    a.n_pos = n_pos; a.first_position = first_position; a.n_chunks = (n_pos + P - 1) / P; a.P = (int)P; a.N = (int)N;
+    a.S = mix64((unsigned long long)seed + ((unsigned long long)step + 1ULL) * kMixGamma);
+    a.ent_total = (int)e.index.ent_total; a.rel_total = (int)e.index.rel_total; a.bern = e.bern ? 1 : 0;
+    a.bern_prob = e.dev.bern_prob; a.tails_hr = e.dev.tails_hr; a.heads_tr = e.dev.heads_tr;
+    a.hr_key = g_dir.hr_key; a.tr_key = g_dir.tr_key; a.hr_span = g_dir.hr_span; a.tr_span = g_dir.tr_span;
+    a.n_hr = g_dir.n_hr; a.n_tr = g_dir.n_tr;
+    a.cand = d_cand; a.pair = d_pair;
+    long long nb = ((n_pos + a.n_chunks) * N + 255) / 256;
+    if (nb > 65536) nb = 65536;
+    hipLaunchKernelGGL(shared_draw_kernel, dim3((unsigned)nb), dim3(256), 0, stream, a);
+    return hip_check(hipGetLastError(), "shared negatives draw launch");
+}
+
+int kge_transe_emit_records_shared(const kge_model_desc *m, const float *d_ent, const float *d_rel, const int32_t *d_h, const int32_t *d_t,
+                                   const int32_t *d_r, INT n_pos, INT stride, INT P, const int32_t *d_cand, INT N, const uint8_t *d_pair,
+                                   INT denom, uint32_t *d_rec, int32_t *d_dst, float *d_loss, void *stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    if (!device_ok()) return fail(KGE_ERR_NO_DEVICE, "kge_transe_emit_records_shared: no usable HIP device");
+    if (!m || m->model != KGE_TRANSE) return fail(KGE_ERR_UNSUPPORTED, "shared negatives: TransE only");
+    if (m->negative_rel != 0) return fail(KGE_ERR_UNSUPPORTED, "shared negatives: relation negatives are not supported (negative_rel must be 0)");
+    if (P < 1 || P > 127) return fail(KGE_ERR_UNSUPPORTED, "shared negatives: the chunk must hold 1..127 positives (a candidate's count is within +-P, an int8)");
+    if (N < 1 || N > 63) return fail(KGE_ERR_UNSUPPORTED, "shared negatives: 1..63 negatives per positive (a positive's count is within +-2N, an int8)");
+    if (!kge_transe_counts_supported(m, N)) return fail(KGE_ERR_UNSUPPORTED, "shared negatives: the sign-count path's shapes only (TransE, equal widths, rows below 2^30)");
+    if (m->ent_dim > 512) return fail(KGE_ERR_UNSUPPORTED, "shared negatives: the shared emit kernel holds embedding widths up to 512");
+    if (n_pos < 0 || stride < n_pos || denom <= 0 || !d_ent || !d_rel || !d_h || !d_t || !d_r || !d_cand || !d_pair || !d_rec || !d_dst || !d_loss)
+        return fail(KGE_ERR_BAD_ARG, "kge_transe_emit_records_shared: bad arguments");
+    if (n_pos == 0) return hip_check(hipMemsetAsync(d_loss, 0, sizeof(float), stream), "zero loss");
+    const long long n_chunks = (n_pos + P - 1) / P;
+    if (3 * n_pos + n_chunks * N >= (INT(1) << 31) || n_chunks >= (INT(1) << 31)) return fail(KGE_ERR_UNSUPPORTED, "shared negatives: batch too large");
+    int rc = g_partials.reserve(n_chunks, "shared negatives loss partials");
+    if (rc) return rc;
+    SharedEmitArgs a = {};
+    a.ent = d_ent; a.rel = d_rel; a.h = d_h; a.t = d_t; a.r = d_r; a.cand = d_cand; a.pair = d_pair;
+    a.n_pos = n_pos; a.n_chunks = n_chunks; a.P = (int)P; a.N = (int)N;
+    a.D = m->ent_dim; a.RS = (a.D + 3) / 4 * 4;
+    int L, C;
+    transe_team_shape(a.D, L, C);
+    a.L = L; a.RD = L * ((C + 3) / 4); a.nat = a.D % 4 == 0;
+    a.ent_total = (int)m->ent_total; a.rel_total = (int)m->rel_total; a.margin = m->margin;
+    a.rec = d_rec; a.dst = d_dst; a.partials = g_partials;
+    const int per_cand = a.RS * 5 + 8, fixed = 12 * a.RS + 16;
+    const int t_max = (kLdsBudget - fixed) / per_cand;     // >= 21 at width 512
+    a.n_tiles = ((int)N + t_max - 1) / t_max;
+    a.T = ((int)N + a.n_tiles - 1) / a.n_tiles;
+    const size_t lds_bytes = (size_t)a.T * per_cand + fixed;
+    const dim3 grid((unsigned)n_chunks), block(256);
+    const bool vec = a.D % 4 == 0;
+    if (a.D <= 256) {
+        if (vec) hipLaunchKernelGGL((shared_emit_kernel<1, true>), grid, block, lds_bytes, stream, a);
+        else hipLaunchKernelGGL((shared_emit_kernel<1, false>), grid, block, lds_bytes, stream, a);
+    } else {
+        if (vec) hipLaunchKernelGGL((shared_emit_kernel<2, true>), grid, block, lds_bytes, stream, a);
+        else hipLaunchKernelGGL((shared_emit_kernel<2, false>), grid, block, lds_bytes, stream, a);
+    }
+    hipLaunchKernelGGL(shared_loss_kernel, dim3(1), dim3(256), 0, stream, (const float *)g_partials.ptr(), n_chunks, 1.0f / (float)denom, d_loss);
+    return hip_check(hipGetLastError(), "shared negatives emit launch");
+}
+
+}  // extern "C"

@@ -103,6 +103,11 @@ def parse_args(argv=None):
                                                              "touches and on their moments; tables and moments replicated across ranks).  Default: automatic for "
                                                              "large tables; LazyAdam and Adagrad always take the touched-rows update (Adagrad's is exact: an element with zero "
                                                              "gradient keeps its value and its accumulator, so its checkpoints hold one accumulator row per parameter row)")
+    p.add_argument("--shared_negatives_chunk", type=int, default=0,
+                   help="P > 0: NON-PARITY, opt-in: chunks of P consecutive positives (1..127) share one set of --ent_neg_rate candidate "
+                        "entities drawn from a hash of (--shared_negatives_seed, global step); pairs that are training triples are "
+                        "masked (Config.set_shared_negatives).  TransE with SGD, LazyAdam or Adagrad on one rank; 0 = off (default)")
+    p.add_argument("--shared_negatives_seed", type=int, default=0, help="seed of the shared candidates' hash; a resumed run must repeat it")
     p.add_argument("--type_constrained_sampling", type=int, default=0,
                    help="1: entity negatives of a training batch come from the relation's own head / tail type list "
                         "(type_constrain.txt in --input_path, required then) instead of from all entities; same random stream, "
@@ -142,6 +147,8 @@ def get_conf(argv):
     con.seed = getattr(argv, "seed", 0)
     if getattr(argv, "sparse_rows", -1) >= 0:
         con.sparse_rows = bool(argv.sparse_rows)
+    if getattr(argv, "shared_negatives_chunk", 0):
+        con.set_shared_negatives(argv.shared_negatives_chunk, getattr(argv, "shared_negatives_seed", 0))
     typed = bool(getattr(argv, "type_constrained_sampling", 0))
     path = argv.input_path if not argv.input_path or argv.input_path.endswith("/") else argv.input_path + "/"
     derive = bool(getattr(argv, "derive_type_constraints", 0)) and bool(path) and not os.path.exists(path + "type_constrain.txt") and \
@@ -205,6 +212,8 @@ def checkpoint_arrays(con):
             if not con._sharded(name):
                 out[name + "/Adagrad"] = a.detach().cpu().numpy()
     out["global_step"] = np.int64(con.global_step)
+    if getattr(con, "_shared_chunk", 0):      # shared negatives: the candidates are a hash of (seed, global_step), chunked by `chunk`
+        out["shared_negatives"] = np.array([con._shared_chunk, con._shared_seed], dtype=np.uint64)
     # with sampling one step ahead the device streams are one batch further than the training: store the states the
     # NEXT step's batch starts from, so that a resumed run trains on exactly the batches an uninterrupted one would
     out["rng_streams"] = con.get_stream_states(before_prefetch=True)
@@ -402,6 +411,12 @@ def restore_checkpoint(con, path, allow_growth=True, arrays=None):
     whole checkpoints restore into sharded and one-process runs alike, at any number of ranks: a rank takes its rows [lo, hi)
     of the entity table (and of its LazyAdam moments) from whichever file holds them."""
     z = arrays if arrays is not None else {k.replace("__", "/"): v for k, v in np.load(path).items()}
+    # shared negatives: a resumed run must draw the candidates the interrupted one would have drawn
+    was = tuple(int(x) for x in z["shared_negatives"]) if "shared_negatives" in z else (0, 0)
+    now = (int(getattr(con, "_shared_chunk", 0)), int(getattr(con, "_shared_seed", 0)) if getattr(con, "_shared_chunk", 0) else 0)
+    if was != now:
+        raise KgeError("the checkpoint was written with shared negatives (chunk, seed) = %s, this run has %s: resume with the same "
+                       "--shared_negatives_chunk / --shared_negatives_seed (0 0 = off)" % (was, now))
     rng = np.random.default_rng(getattr(con, "seed", 0) + 1)
     shapes = con.trainModel.table_shapes()
     for i, name in enumerate(con.trainModel.table_names):

@@ -67,9 +67,11 @@ def wants_sparse_rows(sparse_rows, ent_total, rel_total, width, batch_size, n_ne
 
 
 def plan(model_id, opt_method, sparse_rows, use_counts, counts_supported, ent_total, rel_total, width, batch_size, n_neg,
-         sparse_threshold_bytes=None, adagrad_initial_accumulator=0.1):
+         sparse_threshold_bytes=None, adagrad_initial_accumulator=0.1, shared_chunk=0, negative_rel=0):
     """The StepPlan of a configuration.  sparse_rows: None = automatic, True / False = the caller's wish; use_counts: the
-    caller's wish; counts_supported: what kge_transe_counts_supported said for the model's descriptor and n_neg."""
+    caller's wish; counts_supported: what kge_transe_counts_supported said for the model's descriptor and n_neg.
+    shared_chunk: 0 = off; P > 0 = negatives shared by chunks of P positives (NON-PARITY, opt-in: Config.set_shared_negatives),
+    which is the sparse-rows record step whatever the table size; negative_rel: how many of the n_neg are relation negatives."""
     optimizer = optimizer_kind(opt_method)
     adam, lazy_adam, adagrad = optimizer == "adam", optimizer == "lazy_adam", optimizer == "adagrad"
     # LazyAdam -- opt-in, NON-PARITY: Adam on the touched rows only (tf.contrib.opt.LazyAdamOptimizer's rule) for tables whose dense
@@ -90,6 +92,9 @@ def plan(model_id, opt_method, sparse_rows, use_counts, counts_supported, ent_to
     # sweeps every row of m, v and the table each step, which is the dense path by definition.
     table_bytes, sparse = wants_sparse_rows(sparse_rows, ent_total, rel_total, width, batch_size, n_neg, sparse_threshold_bytes)
     rows = (bool(sparse) or rows_rule) and use_counts and not adam
+    if shared_chunk:
+        check_shared_negatives(model_id, optimizer, use_counts, shared_chunk, n_neg - negative_rel, negative_rel)
+        return StepPlan(optimizer, use_counts, True, False, table_bytes)      # its records go through the touched-rows reduce
     # TransH / TransD (and TransE outside the sign-count path) with SGD: the touched rows are updated in place from float
     # gradient records (kge_forward_backward_sgd_rows) -- no gradient tables, no sweep.  On request, or by itself for tables
     # beyond 2 GB (measured at 4 GB, dim 200, B = 131 072, n = 1: TransH 1.63 -> 0.70 ms, TransD 2.83 -> 0.97 ms per step and
@@ -105,6 +110,28 @@ def plan(model_id, opt_method, sparse_rows, use_counts, counts_supported, ent_to
     if sparse_rows and not (rows or inplace):
         raise KgeError("sparse_rows needs TransE / TransH / TransD with SGD, LazyAdam or Adagrad")
     return StepPlan(optimizer, use_counts, rows, inplace, table_bytes)
+
+
+SHARED_MAX_CHUNK, SHARED_MAX_NEGATIVES = 127, 63      # a candidate's count lies within +-P, a positive's within +-2N: both int8
+
+
+def check_shared_negatives(model_id, optimizer, use_counts, chunk, negative_ent, negative_rel):
+    """Raises KgeError, naming the limit, for a configuration the shared-negatives step cannot take."""
+    if not 1 <= int(chunk) <= SHARED_MAX_CHUNK:
+        raise KgeError("shared negatives: a chunk holds 1 to %d positives (a candidate's count lies within +-chunk and is carried "
+                       "as an int8), got %r" % (SHARED_MAX_CHUNK, chunk))
+    if model_id != TRANSE:
+        raise KgeError("shared negatives are built for TransE only: TransH, TransD and TransR have no shared emit kernel")
+    if negative_rel > 0:
+        raise KgeError("shared negatives: relation negatives are not supported (negative_rel must be 0, got %d)" % negative_rel)
+    if not 1 <= negative_ent <= SHARED_MAX_NEGATIVES:
+        raise KgeError("shared negatives: 1 to %d negatives per positive (a positive's count lies within +-2N and is carried as "
+                       "an int8), got %d" % (SHARED_MAX_NEGATIVES, negative_ent))
+    if optimizer == "adam":
+        raise KgeError("shared negatives need SGD, LazyAdam or Adagrad: with TF1 Adam the dense count image has no entrance for "
+                       "shared records yet")
+    if not use_counts:
+        raise KgeError("shared negatives need TransE's sign-count path (use_counts, and a shape kge_transe_counts_supported accepts)")
 
 
 def shards_at_creation(step_plan, model_id, world, width):

@@ -474,6 +474,44 @@ def sparse_step(con, dev_batch, n_pos, stride, denom, check_shape=False):
     con.global_step += 1
 
 
+def shared_step(con, dev, n_pos, stride, denom):
+    """TransE on negatives SHARED by chunks of positives (NON-PARITY, opt-in: Config.set_shared_negatives; the definition is in
+    include/kge_mi355.h) on ONE GPU.  `dev` holds the step's positives alone (drawn by the sampler at negRate = 0): the draw
+    kernel hashes the chunk's candidates and every pair's side from (seed, global_step) and looks the mask up, the shared emit
+    kernel writes 3 n_pos + n_chunks N int8 records in the sparse step's format, and that step's reduce and rows rule finish.
+    Buffers only grow."""
+    import torch
+    P, N, D = con._shared_chunk, con.negative_ent, con.hidden_size
+    n_chunks, cap_chunks = -(-n_pos // P), -(-stride // P)
+    m_cap = 3 * stride + cap_chunks * N
+    buf = con._sparse_buf
+    if buf is None or buf.get("shared_cap", 0) < m_cap or buf["pair"].shape[0] < stride:
+        d = con.device
+        dw = int(con.lib.kge_transe_record_dwords(ctypes.byref(con._desc)))
+        buf = dict(shared_cap=m_cap,
+                   cand=torch.empty((cap_chunks, N), dtype=torch.int32, device=d),
+                   pair=torch.empty((stride, N), dtype=torch.uint8, device=d),
+                   rec=torch.empty((m_cap, dw), dtype=torch.int32, device=d),
+                   dst=torch.empty(m_cap, dtype=torch.int32, device=d),
+                   rows=torch.empty(m_cap, dtype=torch.int32, device=d),
+                   row_counts=torch.empty((m_cap, D), dtype=torch.int32, device=d),
+                   n_rows=torch.zeros(1, dtype=torch.int32, device=d))
+        con._sparse_buf = buf
+    st = con._stream()
+    h, t, r = dev[0].data_ptr(), dev[1].data_ptr(), dev[2].data_ptr()
+    _lib.check(con.lib.kge_shared_negatives_draw(h, t, r, n_pos, con._first_pos, P, N, con._shared_seed, con.global_step,
+                                                 buf["cand"].data_ptr(), buf["pair"].data_ptr(), st), con.lib)
+    _lib.check(con.lib.kge_transe_emit_records_shared(ctypes.byref(con._desc), con._tables[0].data_ptr(), con._tables[1].data_ptr(),
+                                                      h, t, r, n_pos, stride, P, buf["cand"].data_ptr(), N, buf["pair"].data_ptr(),
+                                                      denom, buf["rec"].data_ptr(), buf["dst"].data_ptr(), con._loss.data_ptr(), st),
+               con.lib)
+    buf["shared_step"], buf["shared_shape"], buf["shared_batch"] = con.global_step, (n_pos, n_chunks), dev
+    con._rule.reduce_apply(con._desc, buf["rec"], buf["dst"], 3 * n_pos + n_chunks * N, buf, denom,
+                           fused_ok=getattr(con, "sparse_fused", True) and D % 4 == 0)
+    con._rule.advance()
+    con.global_step += 1
+
+
 def shard_buffers(con, M, n_recv_rows, n_recv_rec):
     """Workspace of the sharded step, grown geometrically (receive sizes vary from step to step)."""
     import torch
