@@ -667,12 +667,30 @@ int kge_transe_reduce_apply_records_sgd(const kge_model_desc *m, const uint32_t 
  *   with an id outside its table takes no part.  d_h / d_t / d_r hold n_pos positives (`stride` >= n_pos is the arrays' length
  *   and otherwise unused); d_loss receives the loss of this call's positives.  The norms are computed from the gathered rows.
  *   KGE_ERR_UNSUPPORTED, with a message: another model, negative_rel != 0, P or N outside their ranges, a shape outside
- *   kge_transe_counts_supported, an embedding width above 512 (the kernel's LDS tiles). */
+ *   kge_transe_counts_supported, an embedding width above 512 (the kernel's LDS tiles).
+ * A SLICE of the batch (a rank's share on more than one rank: a range of the sampler's virtual threads, not of chunks).  Chunk
+ *   membership is a property of the GLOBAL batch position: position p belongs to chunk p / P.  A call that covers the positions
+ *   [first, first + n_pos) meets the chunks c0 = first / P .. c1 = (first + n_pos - 1) / P, n_chunks = c1 - c0 + 1 of them; the
+ *   first and the last may be partial.  The two `_at` entry points take any first_position >= 0 and otherwise the arguments, the
+ *   checks and the refusals of the two above:
+ * kge_shared_negatives_draw_at: d_cand[j][k] = candidate k of global chunk c0 + j (int32 [n_chunks][N]); d_pair[b][k] = side and mask
+ *   of global position first_position + b.  Every value is what ONE draw of the whole batch writes for that chunk or position.
+ * kge_transe_emit_records_shared_at: workgroup j handles the call's positions that lie in global chunk c0 + j, against row j of
+ *   d_cand.  Records as above with the call's own counts: s * n_pos + b for slot s of the call's positive b, then 3 n_pos + j N + k
+ *   for candidate k of the call's j-th chunk -- 3 n_pos + n_chunks N records.  A partial chunk's candidate records hold the signs
+ *   of the call's own pairs only (counts within +-P as ever); summed per destination key over the calls that cover a batch they
+ *   are the whole-batch call's sums.  With first_position a multiple of P the records, keys and loss are those of
+ *   kge_transe_emit_records_shared bit for bit.  d_loss: this call's hinge sum / denom (denom: the whole batch's). */
 int kge_shared_negatives_draw(const int32_t *d_h, const int32_t *d_t, const int32_t *d_r, INT n_pos, INT first_position, INT P, INT N,
                               uint64_t seed, INT step, int32_t *d_cand, uint8_t *d_pair, void *stream);
 int kge_transe_emit_records_shared(const kge_model_desc *m, const float *d_ent, const float *d_rel, const int32_t *d_h, const int32_t *d_t,
                                    const int32_t *d_r, INT n_pos, INT stride, INT P, const int32_t *d_cand, INT N, const uint8_t *d_pair,
                                    INT denom, uint32_t *d_rec, int32_t *d_dst, float *d_loss, void *stream);
+int kge_shared_negatives_draw_at(const int32_t *d_h, const int32_t *d_t, const int32_t *d_r, INT n_pos, INT first_position, INT P, INT N,
+                                 uint64_t seed, INT step, int32_t *d_cand, uint8_t *d_pair, void *stream);
+int kge_transe_emit_records_shared_at(const kge_model_desc *m, const float *d_ent, const float *d_rel, const int32_t *d_h, const int32_t *d_t,
+                                      const int32_t *d_r, INT n_pos, INT stride, INT first_position, INT P, const int32_t *d_cand, INT N,
+                                      const uint8_t *d_pair, INT denom, uint32_t *d_rec, int32_t *d_dst, float *d_loss, void *stream);
 
 /* ---- Table-sharded sparse path (N GPUs, BASELINE config #5): rank g OWNS the entity rows [g*chunk, (g+1)*chunk); what the
  * reference does with ps tasks holding the variables and workers pulling rows / pushing IndexedSlices over gRPC
@@ -688,6 +706,15 @@ int kge_transe_emit_records_shared(const kge_model_desc *m, const float *d_ent, 
  *                             than n, or more than 64 owners, is KGE_ERR_BAD_ARG and nothing is written
  *   kge_shard_remap_batch   : the batch with entity ids replaced by positions in the fetched-row list (d_slot_of from the
  *                             requests), so the unchanged emit kernel runs against the fetched rows as its "entity table"
+ *   kge_shard_requests_shared: the request list of a SHARED-negatives slice (above): d_req = [h of the n_pos positives | t of them
+ *                             | the n_cand = n_chunks N candidate ids of d_cand], 2 n_pos + n_cand entries; an id outside
+ *                             [0, ent_total) becomes -1, so nothing is requested for it.  A chunk of P positives asks for 2 P + N
+ *                             rows where kge_shard_requests asks for P (2 + N)
+ *   kge_shard_remap_shared  : the same ids as positions in the fetched-row list: d_h2[b] = d_slot_of[b], d_t2[b] =
+ *                             d_slot_of[n_pos + b], d_cand2[i] = d_slot_of[2 n_pos + i] (d_slot_of from kge_shard_scatter of that
+ *                             request list, where a -1 request has position -1); a negative id gives -1 whatever d_slot_of holds.
+ *                             -1 is "outside the table" to kge_transe_emit_records_shared_at, which runs against the fetched rows
+ *                             with ent_total = their number
  *   kge_shard_gather_rows   : d_out[i,:] = d_table[d_ids[i] - row_lo, :]  (the owner's reply; dim % 4 == 0); the ids come from a
  *                             peer, so the row index is clamped into [0, rows - 1]: nothing outside the shard is read
  *   kge_shard_record_ids    : d_ids[m] = global entity id of record m when its destination is a fetched-row slot, else -1
@@ -701,6 +728,10 @@ int kge_shard_scatter(const int32_t *d_ids, INT n, INT chunk, INT n_owners, cons
                       int32_t *d_slot_of, void *stream);
 int kge_shard_remap_batch(const int32_t *d_h, const int32_t *d_t, INT n_pos, INT n_neg, INT stride, const int32_t *d_slot_of, int32_t *d_h2,
                           int32_t *d_t2, void *stream);
+int kge_shard_requests_shared(const int32_t *d_h, const int32_t *d_t, INT n_pos, const int32_t *d_cand, INT n_cand, INT ent_total, int32_t *d_req,
+                              void *stream);
+int kge_shard_remap_shared(const int32_t *d_h, const int32_t *d_t, INT n_pos, const int32_t *d_cand, INT n_cand, const int32_t *d_slot_of,
+                           int32_t *d_h2, int32_t *d_t2, int32_t *d_cand2, void *stream);
 int kge_shard_gather_rows(const float *d_table, const int32_t *d_ids, INT n, INT row_lo, INT rows, INT dim, float *d_out, void *stream);
 int kge_shard_record_ids(const int32_t *d_dst, INT n_records, INT cache_rows, const int32_t *d_cache_ids, int32_t *d_ids, void *stream);
 int kge_shard_pack_records(const uint32_t *d_rec, const int32_t *d_slot_of, INT n_records, INT dwords, uint32_t *d_out, void *stream);

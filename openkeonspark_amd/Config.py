@@ -152,7 +152,9 @@ class Config(object):
         from a counter hash of (seed, global_step) -- what PyTorch-BigGraph and DGL-KE do -- so a chunk gathers 3 chunk + N table
         rows instead of chunk (3 + N).  A pair whose corrupted triple is a training triple is masked: it adds nothing to the loss
         and stays in its denominator (include/kge_mi355.h has the exact definition).  TransE on the sign-count path with SGD,
-        LazyAdam or Adagrad, one rank, entity negatives only, 1 <= chunk <= 127, N <= 63.  Call it before
+        LazyAdam or Adagrad, entity negatives only, 1 <= chunk <= 127, N <= 63; on more than one rank the entity table is
+        row-sharded (a width that is a multiple of 4, up to 64 ranks) and a chunk's rows cross the wire once per chunk, not once
+        per pair; the run equals the one-process run bit for bit at any rank count.  Call it before
         set_model_and_session; chunk = 0 switches it off.  In this mode prefetch_sampling is ignored (the positives are drawn
         when the step starts), hand-fed batches are refused and there is no persistent launch."""
         if self.trainModel is not None:
@@ -166,15 +168,27 @@ class Config(object):
                            "from all entities (typed candidates are not built)")
         self._shared_chunk, self._shared_seed = chunk, int(seed) & 0xFFFFFFFFFFFFFFFF
 
-    def _refuse_shared_ranks(self):
-        if self._shared_chunk and self._dp:
-            raise KgeError("shared negatives train on one rank only: more than one rank, or a row-sharded entity table, has no "
-                           "shared-negatives step")
+    def _refuse_shared_ranks(self, stepping=False):
+        """Shared negatives across ranks train a row-sharded entity table (train_paths.shared_sharded_step) and nothing else:
+        refuse, naming the limit, a world whose table cannot be sharded by rows and -- `stepping`: a step is about to run -- a
+        data-parallel step without the shards."""
+        if not (self._shared_chunk and self._dp):
+            return
+        if self.hidden_size % 4 or self.world_size > 64:
+            raise KgeError("shared negatives on more than one rank train a row-sharded entity table, which needs an embedding "
+                           "width that is a multiple of 4 (this run: %d) and at most 64 ranks (this run: %d); there is no "
+                           "replicated-table step for shared records" % (self.hidden_size, self.world_size))
+        if stepping and not hasattr(self, "_shard"):
+            raise KgeError("shared negatives: a data-parallel step needs the row shards that init_distributed() lays out "
+                           "(force_data_parallel alone sets none up); without them shared negatives train on one rank only")
 
     def shared_negatives_of(self, step):
-        """(cand int32 [n_chunks, N], pair uint8 [batch, N]) of the batch that training step `step` (its global_step when it
+        """(cand int32 [n_chunks, N], pair uint8 [n_pos, N]) of the batch that training step `step` (its global_step when it
         began) trained on: the candidate ids of every chunk, and per (positive, candidate) bit 0 = side (0 new tail, 1 new head),
-        bit 1 = masked.  An inspector: the lists of the most recent step are kept, no others (a pair's mask depends on the step's
+        bit 1 = masked.  On more than one rank these are the rank's OWN lists: its slice holds the batch positions
+        [_first_pos, _first_pos + n_pos), row 0 of `pair` is position _first_pos and row 0 of `cand` is global chunk
+        _first_pos // chunk -- which the rank may share with its neighbour, each holding the same candidates for it.
+        An inspector: the lists of the most recent step are kept, no others (a pair's mask depends on the step's
         positives, which are not)."""
         buf = self._sparse_buf if self._shared_chunk else None
         if not buf or buf.get("shared_step") != int(step):
@@ -443,7 +457,7 @@ class Config(object):
         self._adam, self._lazy_adam, self._adagrad = p.adam, p.lazy_adam, p.adagrad
         self._has_slots, self._rows_rule = p.has_slots, p.rows_rule
         self._refuse_shared_ranks()
-        self._shard_plan = None if self._shared_chunk else self._plan_entity_shard(probe.model_id)
+        self._shard_plan = self._plan_entity_shard(probe.model_id)
         self.trainModel = self.model(config=self, define=True)
         m = self.trainModel
         self._desc = m.descriptor()
@@ -761,6 +775,14 @@ class Config(object):
     def _stream_rccl(self):
         return train_paths.stream_rccl(self)
 
+    def last_exchange_sizes(self):
+        """What this rank's most recent step on a row-sharded entity table (train_paths.sharded_step / shared_sharded_step)
+        exchanged, as a dict of row counts: rows_requested (entity rows it fetched from their owners), rows_served (rows it
+        gathered for others), records_sent (entity gradient records it sent to the rows' owners), records_received.  Read-only;
+        None before the first such step."""
+        sizes = getattr(self, "_exchange_sizes", None)
+        return dict(sizes) if sizes is not None else None
+
     def sync_optimizer_state(self):
         """Data-parallel Adam keeps m and v current on their owner only; gather them before they are read as whole tables
         (checkpoints)."""
@@ -788,9 +810,10 @@ class Config(object):
             if batch_h is not None:
                 raise KgeError("shared negatives: a hand-fed batch is refused (the step draws its own positives and hashes its "
                                "candidates from the global step)")
-            self._refuse_shared_ranks()
+            self._refuse_shared_ranks(stepping=True)
             dev, n_pos = self._sample_positives()
-            train_paths.shared_step(self, dev, n_pos, max(self._n_local, 1), self.batch_size * self.negative_ent)
+            step = train_paths.shared_sharded_step if self._dp else train_paths.shared_step
+            step(self, dev, n_pos, max(self._n_local, 1), self.batch_size * self.negative_ent)
             self.trainModel.loss = self._loss
             return float(self._loss.item()) if sync else self._loss
         if batch_h is None:

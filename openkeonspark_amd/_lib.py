@@ -170,12 +170,16 @@ def _declare(L):
     # shared negatives (csrc/shared_neg.hip)
     L.kge_shared_negatives_draw.argtypes = [vp, vp, vp, i64, i64, i64, i64, ctypes.c_uint64, i64, vp, vp, vp]
     L.kge_transe_emit_records_shared.argtypes = [ctypes.POINTER(ModelDesc), vp, vp, vp, vp, vp, i64, i64, i64, vp, i64, vp, i64, vp, vp, vp, vp]
+    L.kge_shared_negatives_draw_at.argtypes = L.kge_shared_negatives_draw.argtypes      # (any first_position)
+    L.kge_transe_emit_records_shared_at.argtypes = [ctypes.POINTER(ModelDesc), vp, vp, vp, vp, vp, i64, i64, i64, i64, vp, i64, vp, i64, vp, vp, vp, vp]
     L.kge_transe_apply_counts_range.argtypes =[ctypes.POINTER(ModelDesc), vp, vp, vp, vp, vp, i64, i64, i64, i32, f32, f32, f32, f32, vp]
     # table-sharded sparse path (csrc/shard.hip)
     L.kge_shard_requests.argtypes = [vp, vp, vp, i64, i64, i64, vp, vp]
     L.kge_shard_count.argtypes = [vp, i64, i64, i64, vp, vp]
     L.kge_shard_scatter.argtypes = [vp, i64, i64, i64, vp, vp, vp, vp, vp]
     L.kge_shard_remap_batch.argtypes = [vp, vp, i64, i64, i64, vp, vp, vp, vp]
+    L.kge_shard_requests_shared.argtypes = [vp, vp, i64, vp, i64, i64, vp, vp]
+    L.kge_shard_remap_shared.argtypes = [vp, vp, i64, vp, i64, vp, vp, vp, vp, vp]
     L.kge_shard_gather_rows.argtypes = [vp, vp, i64, i64, i64, i64, vp, vp]
     L.kge_shard_record_ids.argtypes = [vp, i64, i64, vp, vp, vp]
     L.kge_shard_pack_records.argtypes = [vp, vp, i64, i64, vp, vp]

@@ -110,6 +110,34 @@ __global__ __launch_bounds__(256) void shard_remap_kernel(const int32_t *__restr
     }
 }
 
+// The shared-negatives step's request list: [h of the n_pos positives | t of them | the n_cand candidate ids]; an id outside
+// [0, ent_total) becomes -1 (nothing is requested for it)
+__global__ __launch_bounds__(256) void shard_requests_shared_kernel(const int32_t *__restrict__ bh, const int32_t *__restrict__ bt, long long n_pos,
+                                                                    const int32_t *__restrict__ cand, long long n_cand, int ent_total,
+                                                                    int32_t *__restrict__ req) {
+    const long long total = 2 * n_pos + n_cand;
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
+        const int v = i < n_pos ? bh[i] : (i < 2 * n_pos ? bt[i - n_pos] : cand[i - 2 * n_pos]);
+        req[i] = (v >= 0 && v < ent_total) ? v : -1;
+    }
+}
+
+// ... and the same ids as positions in the fetched-row list (slot_of from the scatter of that request list); a negative id stays
+// -1, which the shared emit kernel reads as "outside the table"
+__global__ __launch_bounds__(256) void shard_remap_shared_kernel(const int32_t *__restrict__ bh, const int32_t *__restrict__ bt, long long n_pos,
+                                                                 const int32_t *__restrict__ cand, long long n_cand,
+                                                                 const int32_t *__restrict__ slot_of, int32_t *__restrict__ h2,
+                                                                 int32_t *__restrict__ t2, int32_t *__restrict__ cand2) {
+    const long long total = 2 * n_pos + n_cand;
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
+        const int v = i < n_pos ? bh[i] : (i < 2 * n_pos ? bt[i - n_pos] : cand[i - 2 * n_pos]);
+        const int s = v >= 0 ? slot_of[i] : -1;
+        if (i < n_pos) h2[i] = s;
+        else if (i < 2 * n_pos) t2[i - n_pos] = s;
+        else cand2[i - 2 * n_pos] = s;
+    }
+}
+
 // out[i, :] = table[ids[i] - row_lo, :]   (D % 4 == 0; one float4 per lane)
 __global__ __launch_bounds__(256) void shard_gather_rows_kernel(const float *__restrict__ table, const int32_t *__restrict__ ids, long long n,
                                                                 long long row_lo, long long rows, int D4, float *__restrict__ out) {
@@ -234,6 +262,30 @@ int kge_shard_remap_batch(const int32_t *d_h, const int32_t *d_t, INT n_pos, INT
     hipLaunchKernelGGL(shard_remap_kernel, dim3(blocks_for(n_pos * (1 + n_neg))), dim3(256), 0, (hipStream_t)stream, d_h, d_t, (long long)n_pos,
                        (int)n_neg, (long long)stride, d_slot_of, d_h2, d_t2);
     return hip_check(hipGetLastError(), "shard remap launch");
+}
+
+int kge_shard_requests_shared(const int32_t *d_h, const int32_t *d_t, INT n_pos, const int32_t *d_cand, INT n_cand, INT ent_total, int32_t *d_req,
+                              void *stream) {
+    if (!device_ok()) return fail(KGE_ERR_NO_DEVICE, "kge_shard_requests_shared: no usable HIP device");
+    if (n_pos < 0 || n_cand < 0 || ent_total < 0 || ent_total >= (INT(1) << 31) || 2 * n_pos + n_cand >= (INT(1) << 31) || !d_req ||
+        (n_pos > 0 && (!d_h || !d_t)) || (n_cand > 0 && !d_cand))
+        return fail(KGE_ERR_BAD_ARG, "kge_shard_requests_shared: bad arguments");
+    if (2 * n_pos + n_cand == 0) return KGE_OK;
+    hipLaunchKernelGGL(shard_requests_shared_kernel, dim3(blocks_for(2 * n_pos + n_cand)), dim3(256), 0, (hipStream_t)stream, d_h, d_t,
+                       (long long)n_pos, d_cand, (long long)n_cand, (int)ent_total, d_req);
+    return hip_check(hipGetLastError(), "shard shared requests launch");
+}
+
+int kge_shard_remap_shared(const int32_t *d_h, const int32_t *d_t, INT n_pos, const int32_t *d_cand, INT n_cand, const int32_t *d_slot_of,
+                           int32_t *d_h2, int32_t *d_t2, int32_t *d_cand2, void *stream) {
+    if (!device_ok()) return fail(KGE_ERR_NO_DEVICE, "kge_shard_remap_shared: no usable HIP device");
+    if (n_pos < 0 || n_cand < 0 || 2 * n_pos + n_cand >= (INT(1) << 31) || !d_slot_of || (n_pos > 0 && (!d_h || !d_t || !d_h2 || !d_t2)) ||
+        (n_cand > 0 && (!d_cand || !d_cand2)))
+        return fail(KGE_ERR_BAD_ARG, "kge_shard_remap_shared: bad arguments");
+    if (2 * n_pos + n_cand == 0) return KGE_OK;
+    hipLaunchKernelGGL(shard_remap_shared_kernel, dim3(blocks_for(2 * n_pos + n_cand)), dim3(256), 0, (hipStream_t)stream, d_h, d_t,
+                       (long long)n_pos, d_cand, (long long)n_cand, d_slot_of, d_h2, d_t2, d_cand2);
+    return hip_check(hipGetLastError(), "shard shared remap launch");
 }
 
 int kge_shard_gather_rows(const float *d_table, const int32_t *d_ids, INT n, INT row_lo, INT rows, INT dim, float *d_out, void *stream) {

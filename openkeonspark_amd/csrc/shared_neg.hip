@@ -22,7 +22,11 @@
 //                        the next tile's share to its own earlier stores.
 // The loss is summed per wave in candidate order, per chunk in wave order and over the chunks in index order: a step is
 // reproducible bit for bit.
+// Chunk membership is a property of the GLOBAL batch position: position p belongs to chunk p / P.  The `_at` entry points take a
+// call that begins at any position -- a rank's slice of the batch -- so its first and last chunks may be partial; both kernels
+// carry that as one offset (first_position % P, zero for the older entry points) in their chunk arithmetic.
 #include <algorithm>
+#include <string>
 #include <vector>
 
 #include "engine.hpp"
@@ -98,6 +102,7 @@ __device__ __forceinline__ int shared_candidate(unsigned long long S, long long 
 __global__ __launch_bounds__(256) void shared_draw_kernel(DrawArgs a) {
     const long long n_pair = a.n_pos * a.N, n_all = n_pair + a.n_chunks * a.N;
     const long long chunk0 = a.first_position / a.P;
+    const long long off = a.first_position - chunk0 * a.P;      // positions of global chunk chunk0 that lie before the call's first
     for (long long g = (long long)blockIdx.x * 256 + threadIdx.x; g < n_all; g += (long long)gridDim.x * 256) {
         if (g >= n_pair) {
             const long long j = (g - n_pair) / a.N;
@@ -107,7 +112,7 @@ __global__ __launch_bounds__(256) void shared_draw_kernel(DrawArgs a) {
         }
         const long long b = g / a.N;
         const int k = (int)(g % a.N);
-        const int c = shared_candidate(a.S, chunk0 + b / a.P, k, a.ent_total);
+        const int c = shared_candidate(a.S, chunk0 + (off + b) / a.P, k, a.ent_total);
         const int h = a.h[b], t = a.t[b], r = a.r[b];
         const bool r_ok = r >= 0 && r < a.rel_total;
         // the head-or-tail coin of sample_slot with v in the place of rand % 1000: same threshold, same float comparison
@@ -138,6 +143,7 @@ struct SharedEmitArgs {
     const int32_t *cand;
     const uint8_t *pair;
     long long n_pos, n_chunks;
+    int off;                     // first_position % P: workgroup j holds the call's positions [j P - off, (j + 1) P - off)
     int P, N, T, n_tiles;        // candidates per tile, tiles
     int D, RS;                   // width; LDS row stride in floats (D rounded up to 4)
     int RD, L, nat;              // record dwords; the width's team shape; natural element order
@@ -175,8 +181,8 @@ __global__ __launch_bounds__(256) void shared_emit_kernel(SharedEmitArgs a) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     uint8_t *stage = stage_all + wave * 3 * RS;
     const long long j = blockIdx.x;
-    const long long b0 = j * a.P;
-    const int Pc = (int)min((long long)a.P, a.n_pos - b0);
+    const long long b0 = max(0LL, j * a.P - a.off);
+    const int Pc = (int)(min(a.n_pos, (j + 1) * a.P - a.off) - b0);
     bool valid[Q];
 #pragma unroll
     for (int q = 0; q < Q; q++) valid[q] = 4 * (lane + 64 * q) < RS;
@@ -373,20 +379,15 @@ __global__ __launch_bounds__(256) void shared_loss_kernel(const float *__restric
 
 constexpr int kLdsBudget = 60 * 1024;   // per workgroup: two chunks per CU at the widest shapes, five at the headline shape
 
-}  // namespace
-}  // namespace kge
-
-using namespace kge;
-
-extern "C" {
-
-int kge_shared_negatives_draw(const int32_t *d_h, const int32_t *d_t, const int32_t *d_r, INT n_pos, INT first_position, INT P, INT N,
-                              uint64_t seed, INT step, int32_t *d_cand, uint8_t *d_pair, void *stream_) {
-    hipStream_t stream = (hipStream_t)stream_;
-    if (P < 1 || P > 127) return fail(KGE_ERR_BAD_ARG, "kge_shared_negatives_draw: the chunk must hold 1..127 positives (a candidate's count is within +-P, an int8)");
-    if (N < 1 || N > 63) return fail(KGE_ERR_BAD_ARG, "kge_shared_negatives_draw: 1..63 negatives per positive (a positive's count is within +-2N, an int8)");
-    if (n_pos < 0 || first_position < 0 || first_position % P != 0 || step < 0 || !d_h || !d_t || !d_r || !d_cand || !d_pair)
-        return fail(KGE_ERR_BAD_ARG, "kge_shared_negatives_draw: bad arguments (first_position must be a multiple of the chunk)");
+// The two entry points of each kernel share these: `who` names the caller in the messages, `aligned` is the older entry points'
+// rule that the call begins on a chunk boundary.
+int draw_call(const char *who, bool aligned, const int32_t *d_h, const int32_t *d_t, const int32_t *d_r, INT n_pos, INT first_position, INT P,
+              INT N, uint64_t seed, INT step, int32_t *d_cand, uint8_t *d_pair, hipStream_t stream) {
+    const std::string w(who);
+    if (P < 1 || P > 127) return fail(KGE_ERR_BAD_ARG, w + ": the chunk must hold 1..127 positives (a candidate's count is within +-P, an int8)");
+    if (N < 1 || N > 63) return fail(KGE_ERR_BAD_ARG, w + ": 1..63 negatives per positive (a positive's count is within +-2N, an int8)");
+    if (n_pos < 0 || first_position < 0 || (aligned && first_position % P != 0) || step < 0 || !d_h || !d_t || !d_r || !d_cand || !d_pair)
+        return fail(KGE_ERR_BAD_ARG, w + (aligned ? ": bad arguments (first_position must be a multiple of the chunk)" : ": bad arguments"));
     int rc = ensure_device_index();
     if (rc) return rc;
     if ((rc = ensure_group_dir())) return rc;
@@ -394,7 +395,7 @@ int kge_shared_negatives_draw(const int32_t *d_h, const int32_t *d_t, const int3
     Engine &e = engine();
     DrawArgs a = {};
     a.h = d_h; a.t = d_t; a.r = d_r;
-    a.n_pos = n_pos; a.first_position = first_position; a.n_chunks = (n_pos + P - 1) / P; a.P = (int)P; a.N = (int)N;
+    a.n_pos = n_pos; a.first_position = first_position; a.n_chunks = (first_position % P + n_pos + P - 1) / P; a.P = (int)P; a.N = (int)N;
     a.S = mix64((unsigned long long)seed + ((unsigned long long)step + 1ULL) * kMixGamma);
     a.ent_total = (int)e.index.ent_total; a.rel_total = (int)e.index.rel_total; a.bern = e.bern ? 1 : 0;
     a.bern_prob = e.dev.bern_prob; a.tails_hr = e.dev.tails_hr; a.heads_tr = e.dev.heads_tr;
@@ -407,27 +408,29 @@ int kge_shared_negatives_draw(const int32_t *d_h, const int32_t *d_t, const int3
     return hip_check(hipGetLastError(), "shared negatives draw launch");
 }
 
-int kge_transe_emit_records_shared(const kge_model_desc *m, const float *d_ent, const float *d_rel, const int32_t *d_h, const int32_t *d_t,
-                                   const int32_t *d_r, INT n_pos, INT stride, INT P, const int32_t *d_cand, INT N, const uint8_t *d_pair,
-                                   INT denom, uint32_t *d_rec, int32_t *d_dst, float *d_loss, void *stream_) {
-    hipStream_t stream = (hipStream_t)stream_;
-    if (!device_ok()) return fail(KGE_ERR_NO_DEVICE, "kge_transe_emit_records_shared: no usable HIP device");
+int emit_call(const char *who, const kge_model_desc *m, const float *d_ent, const float *d_rel, const int32_t *d_h, const int32_t *d_t,
+              const int32_t *d_r, INT n_pos, INT stride, INT first_position, INT P, const int32_t *d_cand, INT N, const uint8_t *d_pair,
+              INT denom, uint32_t *d_rec, int32_t *d_dst, float *d_loss, hipStream_t stream) {
+    const std::string w(who);
+    if (!device_ok()) return fail(KGE_ERR_NO_DEVICE, w + ": no usable HIP device");
     if (!m || m->model != KGE_TRANSE) return fail(KGE_ERR_UNSUPPORTED, "shared negatives: TransE only");
     if (m->negative_rel != 0) return fail(KGE_ERR_UNSUPPORTED, "shared negatives: relation negatives are not supported (negative_rel must be 0)");
     if (P < 1 || P > 127) return fail(KGE_ERR_UNSUPPORTED, "shared negatives: the chunk must hold 1..127 positives (a candidate's count is within +-P, an int8)");
     if (N < 1 || N > 63) return fail(KGE_ERR_UNSUPPORTED, "shared negatives: 1..63 negatives per positive (a positive's count is within +-2N, an int8)");
     if (!kge_transe_counts_supported(m, N)) return fail(KGE_ERR_UNSUPPORTED, "shared negatives: the sign-count path's shapes only (TransE, equal widths, rows below 2^30)");
     if (m->ent_dim > 512) return fail(KGE_ERR_UNSUPPORTED, "shared negatives: the shared emit kernel holds embedding widths up to 512");
-    if (n_pos < 0 || stride < n_pos || denom <= 0 || !d_ent || !d_rel || !d_h || !d_t || !d_r || !d_cand || !d_pair || !d_rec || !d_dst || !d_loss)
-        return fail(KGE_ERR_BAD_ARG, "kge_transe_emit_records_shared: bad arguments");
+    if (n_pos < 0 || stride < n_pos || first_position < 0 || denom <= 0 || !d_ent || !d_rel || !d_h || !d_t || !d_r || !d_cand || !d_pair || !d_rec ||
+        !d_dst || !d_loss)
+        return fail(KGE_ERR_BAD_ARG, w + ": bad arguments");
     if (n_pos == 0) return hip_check(hipMemsetAsync(d_loss, 0, sizeof(float), stream), "zero loss");
-    const long long n_chunks = (n_pos + P - 1) / P;
+    const long long off = first_position % P;
+    const long long n_chunks = (off + n_pos + P - 1) / P;
     if (3 * n_pos + n_chunks * N >= (INT(1) << 31) || n_chunks >= (INT(1) << 31)) return fail(KGE_ERR_UNSUPPORTED, "shared negatives: batch too large");
     int rc = g_partials.reserve(n_chunks, "shared negatives loss partials");
     if (rc) return rc;
     SharedEmitArgs a = {};
     a.ent = d_ent; a.rel = d_rel; a.h = d_h; a.t = d_t; a.r = d_r; a.cand = d_cand; a.pair = d_pair;
-    a.n_pos = n_pos; a.n_chunks = n_chunks; a.P = (int)P; a.N = (int)N;
+    a.n_pos = n_pos; a.n_chunks = n_chunks; a.off = (int)off; a.P = (int)P; a.N = (int)N;
     a.D = m->ent_dim; a.RS = (a.D + 3) / 4 * 4;
     int L, C;
     transe_team_shape(a.D, L, C);
@@ -452,4 +455,37 @@ int kge_transe_emit_records_shared(const kge_model_desc *m, const float *d_ent, 
     return hip_check(hipGetLastError(), "shared negatives emit launch");
 }
 
+}  // namespace
+}  // namespace kge
+
+using namespace kge;
+
+extern "C" {
+
+int kge_shared_negatives_draw(const int32_t *d_h, const int32_t *d_t, const int32_t *d_r, INT n_pos, INT first_position, INT P, INT N,
+                              uint64_t seed, INT step, int32_t *d_cand, uint8_t *d_pair, void *stream) {
+    return draw_call("kge_shared_negatives_draw", true, d_h, d_t, d_r, n_pos, first_position, P, N, seed, step, d_cand, d_pair, (hipStream_t)stream);
+}
+
+int kge_shared_negatives_draw_at(const int32_t *d_h, const int32_t *d_t, const int32_t *d_r, INT n_pos, INT first_position, INT P, INT N,
+                                 uint64_t seed, INT step, int32_t *d_cand, uint8_t *d_pair, void *stream) {
+    return draw_call("kge_shared_negatives_draw_at", false, d_h, d_t, d_r, n_pos, first_position, P, N, seed, step, d_cand, d_pair,
+                     (hipStream_t)stream);
+}
+
+int kge_transe_emit_records_shared(const kge_model_desc *m, const float *d_ent, const float *d_rel, const int32_t *d_h, const int32_t *d_t,
+                                   const int32_t *d_r, INT n_pos, INT stride, INT P, const int32_t *d_cand, INT N, const uint8_t *d_pair,
+                                   INT denom, uint32_t *d_rec, int32_t *d_dst, float *d_loss, void *stream) {
+    return emit_call("kge_transe_emit_records_shared", m, d_ent, d_rel, d_h, d_t, d_r, n_pos, stride, 0, P, d_cand, N, d_pair, denom, d_rec, d_dst,
+                     d_loss, (hipStream_t)stream);
+}
+
+int kge_transe_emit_records_shared_at(const kge_model_desc *m, const float *d_ent, const float *d_rel, const int32_t *d_h, const int32_t *d_t,
+                                      const int32_t *d_r, INT n_pos, INT stride, INT first_position, INT P, const int32_t *d_cand, INT N,
+                                      const uint8_t *d_pair, INT denom, uint32_t *d_rec, int32_t *d_dst, float *d_loss, void *stream) {
+    return emit_call("kge_transe_emit_records_shared_at", m, d_ent, d_rel, d_h, d_t, d_r, n_pos, stride, first_position, P, d_cand, N, d_pair, denom,
+                     d_rec, d_dst, d_loss, (hipStream_t)stream);
+}
+
 }  // extern "C"
+

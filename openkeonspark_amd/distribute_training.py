@@ -106,7 +106,9 @@ def parse_args(argv=None):
     p.add_argument("--shared_negatives_chunk", type=int, default=0,
                    help="P > 0: NON-PARITY, opt-in: chunks of P consecutive positives (1..127) share one set of --ent_neg_rate candidate "
                         "entities drawn from a hash of (--shared_negatives_seed, global step); pairs that are training triples are "
-                        "masked (Config.set_shared_negatives).  TransE with SGD, LazyAdam or Adagrad on one rank; 0 = off (default)")
+                        "masked (Config.set_shared_negatives).  TransE with SGD, LazyAdam or Adagrad; on N ranks the entity table is sharded "
+                        "by row range (a width that is a multiple of 4) and the run equals the one-process run bit for bit; 0 = off "
+                        "(default)")
     p.add_argument("--shared_negatives_seed", type=int, default=0, help="seed of the shared candidates' hash; a resumed run must repeat it")
     p.add_argument("--type_constrained_sampling", type=int, default=0,
                    help="1: entity negatives of a training batch come from the relation's own head / tail type list "

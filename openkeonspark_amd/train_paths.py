@@ -512,6 +512,53 @@ def shared_step(con, dev, n_pos, stride, denom):
     con.global_step += 1
 
 
+def shared_chunk_span(first_position, n_pos, P):
+    """(c0, n_chunks): the global chunks of P positions that the batch positions [first_position, first_position + n_pos) meet --
+    c0 = first_position // P through (first_position + n_pos - 1) // P; the first and the last may be partial; no position, no
+    chunk.  The one place the host computes the span (the kernels' form is in include/kge_mi355.h)."""
+    first_position, n_pos, P = int(first_position), int(n_pos), int(P)
+    if first_position < 0 or n_pos < 0 or P < 1:
+        raise ValueError("shared_chunk_span: first_position >= 0, n_pos >= 0 and P >= 1, got %r" % ((first_position, n_pos, P),))
+    c0 = first_position // P
+    return c0, ((first_position + n_pos - 1) // P - c0 + 1 if n_pos else 0)
+
+
+def shared_sharded_step(con, dev, n_pos, stride, denom):
+    """shared_step on a SHARDED entity table (more than one rank, or the one-rank rehearsal): sharded_step's stages around the
+    shared kernels.  `dev` holds this rank's slice of the step's positives -- the batch positions [_first_pos, _first_pos + n_pos),
+    which need not begin on a chunk boundary: chunks are chunks of the GLOBAL position, so the draw at _first_pos gives this rank
+    the lists one process would hold for them.  A chunk requests its 2 P + N rows (sharded_step: P (2 + N)) and sends back records
+    for them alone; the candidate records of a chunk cut by a slice bound come from both ranks and meet at the row's owner.
+    M = 3 n_pos + n_chunks N records; `denom` is the global batch_size * N.  Integer sums, hashes of the global position: the
+    union of the shards equals the one-process shared step bit for bit.  An empty slice still joins every collective."""
+    import torch
+    L, st = con.lib, con._stream()
+    con.comm_fence("pg")
+    P, N, first = con._shared_chunk, con.negative_ent, con._first_pos
+    n_chunks = shared_chunk_span(first, n_pos, P)[1]
+    cap_chunks = max(shared_chunk_span(first, stride, P)[1], 1)
+    n_cand = n_chunks * N
+    M = 3 * n_pos + n_cand
+    b = shard_buffers(con, M, 0, 0)
+    if "pair" not in b or b["pair"].shape[0] < stride or b["cand"].shape != (cap_chunks, N):
+        d = con.device
+        b.update(cand=torch.empty((cap_chunks, N), dtype=torch.int32, device=d), cand2=torch.empty((cap_chunks, N), dtype=torch.int32, device=d),
+                 pair=torch.empty((stride, N), dtype=torch.uint8, device=d), ht2=torch.empty((2, stride), dtype=torch.int32, device=d))
+    h, t, r = dev[0].data_ptr(), dev[1].data_ptr(), dev[2].data_ptr()
+    cand, cand2, pair, h2, t2 = b["cand"].data_ptr(), b["cand2"].data_ptr(), b["pair"].data_ptr(), b["ht2"][0].data_ptr(), b["ht2"][1].data_ptr()
+    _lib.check(L.kge_shared_negatives_draw_at(h, t, r, n_pos, first, P, N, con._shared_seed, con.global_step, cand, pair, st), L)
+    # the rows of the positives and of the chunks' candidates, once per chunk
+    _lib.check(L.kge_shard_requests_shared(h, t, n_pos, cand, n_cand, con.entTotal, b["req"].data_ptr(), st), L)
+    b, n_send, n_recv = shard_fetch_rows(con, M, 2 * n_pos + n_cand)
+    _lib.check(L.kge_shard_remap_shared(h, t, n_pos, cand, n_cand, b["slot_of"].data_ptr(), h2, t2, cand2, st), L)
+    desc2 = con._desc_with(ent_total=max(n_send, 1))
+    _lib.check(L.kge_transe_emit_records_shared_at(ctypes.byref(desc2), b["cache"].data_ptr(), con._tables[1].data_ptr(), h2, t2, r, n_pos,
+                                                   stride, first, P, cand2, N, pair, denom, b["rec"].data_ptr(), b["dst"].data_ptr(),
+                                                   con._loss.data_ptr(), st), L)
+    b["shared_step"], b["shared_shape"], b["shared_batch"] = con.global_step, (n_pos, n_chunks), dev
+    shard_finish(con, b, M, n_pos, n_send, n_recv, desc2, denom)
+
+
 def shard_buffers(con, M, n_recv_rows, n_recv_rec):
     """Workspace of the sharded step, grown geometrically (receive sizes vary from step to step)."""
     import torch
@@ -541,36 +588,45 @@ def shard_buffers(con, M, n_recv_rows, n_recv_rec):
     return b
 
 
+def shard_fetch_rows(con, M, n_req):
+    """Both sharded steps, after their request list (b["req"][:n_req], ids < 0 = nothing to fetch) is written: who owns the rows,
+    ids out, rows back into b["cache"]; b["slot_of"][i] is request i's row of the cache, b["send_ids"] the cache rows' entity ids.
+    `M`: the step's number of records (the workspace is sized by it; n_req <= M).  -> (workspace, rows fetched, rows served)"""
+    L, st, W, D, pg = con.lib, con._stream(), con.world_size, con.hidden_size, con._pg
+    sh = con._shard
+    chunk = sh["chunk"]
+    b = shard_buffers(con, M, 0, 0)
+    _lib.check(L.kge_shard_count(b["req"].data_ptr(), n_req, chunk, W, b["counts"].data_ptr(), st), L)
+    send, recv, gmax = par.exchange_counts_max(b["counts"], pg)
+    h_counts = (ctypes.c_int64 * W)(*send)
+    _lib.check(L.kge_shard_scatter(b["req"].data_ptr(), n_req, chunk, W, h_counts, b["cursor"].data_ptr(), b["send_ids"].data_ptr(),
+                                   b["slot_of"].data_ptr(), st), L)
+    n_send, n_recv = sum(send), sum(recv)
+    b = shard_buffers(con, M, n_recv, 0)
+    # ids out, rows back
+    par.all_to_all_rows(b["recv_ids"], b["send_ids"], recv, send, pg, max_rows=gmax)
+    _lib.check(L.kge_shard_gather_rows(con._tables[0].data_ptr(), b["recv_ids"].data_ptr(), n_recv, sh["lo"], chunk, D,
+                                       b["rows_out"].data_ptr(), st), L)
+    par.all_to_all_rows(b["cache"], b["rows_out"], send, recv, pg, max_rows=gmax)
+    return b, n_send, n_recv
+
+
 def sharded_step(con, dev_batch, n_pos, stride, denom):
     """Sparse-row TransE step on a SHARDED entity table (world_size > 1): every stage is O(local batch).
     request ids -> all-to-all -> owners gather rows -> all-to-all -> emit int8 records against the fetched rows ->
     all-to-all (row id, record) -> owners sort / sum / apply their rows; relation counts all-reduced (csrc/shard.hip).
     Integer sums and one per-row update formula: the union of the shards equals the single-process table bit for bit."""
     import torch
-    L, st, W, D, pg = con.lib, con._stream(), con.world_size, con.hidden_size, con._pg
+    L, st = con.lib, con._stream()
     con.comm_fence("pg")
     n_neg = con.negative_ent + con.negative_rel
-    sh = con._shard
-    chunk = sh["chunk"]
     M = n_pos * (3 + n_neg)
     b = shard_buffers(con, M, 0, 0)
-    dw = b["dw"]
     h, t, r = dev_batch[0], dev_batch[1], dev_batch[2]
     bstride = dev_batch.shape[1] // (1 + n_neg)
-    # 1. which entity rows does this slice touch, and who owns them
+    # 1. which entity rows does this slice touch, and who owns them; 2. ids out, rows back
     _lib.check(L.kge_shard_requests(h.data_ptr(), t.data_ptr(), r.data_ptr(), n_pos, n_neg, bstride, b["req"].data_ptr(), st), L)
-    _lib.check(L.kge_shard_count(b["req"].data_ptr(), M, chunk, W, b["counts"].data_ptr(), st), L)
-    send, recv, gmax = par.exchange_counts_max(b["counts"], pg)
-    h_counts = (ctypes.c_int64 * W)(*send)
-    _lib.check(L.kge_shard_scatter(b["req"].data_ptr(), M, chunk, W, h_counts, b["cursor"].data_ptr(), b["send_ids"].data_ptr(),
-                                   b["slot_of"].data_ptr(), st), L)
-    n_send, n_recv = sum(send), sum(recv)
-    b = shard_buffers(con, M, n_recv, 0)
-    # 2. ids out, rows back
-    par.all_to_all_rows(b["recv_ids"], b["send_ids"], recv, send, pg, max_rows=gmax)
-    _lib.check(L.kge_shard_gather_rows(con._tables[0].data_ptr(), b["recv_ids"].data_ptr(), n_recv, sh["lo"], chunk, D,
-                                       b["rows_out"].data_ptr(), st), L)
-    par.all_to_all_rows(b["cache"], b["rows_out"], send, recv, pg, max_rows=gmax)
+    b, n_send, n_recv = shard_fetch_rows(con, M, M)
     # 3. the unchanged emit kernel over the fetched rows: the batch in terms of cache slots
     if con._dev_batch2 is None or con._dev_batch2.shape != dev_batch.shape:
         con._dev_batch2 = torch.zeros_like(dev_batch)
@@ -581,6 +637,19 @@ def sharded_step(con, dev_batch, n_pos, stride, denom):
     _lib.check(L.kge_transe_emit_records(ctypes.byref(desc2), b["cache"].data_ptr(), con._tables[1].data_ptr(), h2.data_ptr(),
                                          t2.data_ptr(), r.data_ptr(), n_pos, n_neg, bstride, denom, b["rec"].data_ptr(),
                                          b["dst"].data_ptr(), None, None, con._loss.data_ptr(), st), L)
+    shard_finish(con, b, M, n_pos, n_send, n_recv, desc2, denom)
+
+
+def shard_finish(con, b, M, n_pos, n_send, n_recv, desc2, denom):
+    """Both sharded steps, after the emit kernel: the M records in b["rec"] / b["dst"] (keys: rows of the fetched-row cache, then
+    desc2.ent_total + relation; the relation slots of the positives are records [2 n_pos, 3 n_pos)) -> relation counts
+    all-reduced with the loss, entity records to their owners, the rows rule on the owned rows and on the replicated relation
+    table; the step ends here (advance, global_step)."""
+    import torch
+    L, st, W, D, pg = con.lib, con._stream(), con.world_size, con.hidden_size, con._pg
+    sh = con._shard
+    chunk = sh["chunk"]
+    dw = b["dw"]
     # 4. relation rows: dense int32 image, all-reduced (the relation table is replicated)
     b["rel_counts"].zero_()
     rel_live = None
@@ -625,6 +694,7 @@ def sharded_step(con, dev_batch, n_pos, stride, denom):
                                    b["slot_of2"].data_ptr(), st), L)
     _lib.check(L.kge_shard_pack_records(b["rec"].data_ptr(), b["slot_of2"].data_ptr(), M, dw, b["send_rec"].data_ptr(), st), L)
     n_recv2 = sum(recv2)
+    con._exchange_sizes = dict(rows_requested=n_send, rows_served=n_recv, records_sent=sum(send2), records_received=n_recv2)
     b = shard_buffers(con, M, n_recv, n_recv2)
     par.all_to_all_rows(b["recv_rows2"], b["send_rows2"], recv2, send2, pg, max_rows=gmax2)
     par.all_to_all_rows(b["recv_rec"], b["send_rec"], recv2, send2, pg, max_rows=gmax2)
