@@ -692,6 +692,53 @@ int kge_transe_emit_records_shared_at(const kge_model_desc *m, const float *d_en
                                       const int32_t *d_r, INT n_pos, INT stride, INT first_position, INT P, const int32_t *d_cand, INT N,
                                       const uint8_t *d_pair, INT denom, uint32_t *d_rec, int32_t *d_dst, float *d_loss, void *stream);
 
+/* ---- Shared negatives on RELATION-GROUPED chunks, with typed candidates (NON-PARITY, opt-in; csrc/shared_neg.hip) ----
+ * A chunk of consecutive batch positions mixes relations, so its candidates cannot come from one relation's type list.  Here the
+ * step's positives are ordered by relation and a chunk never crosses a relation boundary (PyTorch-BigGraph's way).  mix, G and the
+ * step key S = mix(seed + (step + 1) G) are those of the definition above.
+ *   Order.      The n_pos positives are drawn as ever (the sampler at negRate = 0).  perm is the STABLE order of the batch positions
+ *               by relation id; an id outside [0, rel_total) sorts as rel_total -- one trailing run, whose positives take no part.
+ *               Sorted position b holds batch position perm[b].
+ *   Chunks.     The run of relation rho is cut from its start into pieces of P positions, the last piece of a run may be short;
+ *               chunk j counts the pieces in sorted order.  n_chunks = sum over rho of ceil(len_rho / P) <= cap = ceil(n_pos / P) +
+ *               min(rel_total + 1, n_pos).  The chunk table is int2 [cap] = (first sorted position, length); the slots from
+ *               n_chunks on have length 0 (and first position n_pos).  n_chunks stays on the device: every launch and buffer is
+ *               sized by cap, and the step gains no host synchronisation.
+ *   Side.       Per CANDIDATE, not per pair (a typed candidate is drawn from one side's list): of candidate k of chunk j,
+ *               v = ((mix(S + (((j << 8) | 128 | k) + 1) G) >> 32) * 1000) >> 32; a new TAIL iff (float)v < bern_prob[rho_j] with
+ *               setBern(1) and rho_j valid, else iff (float)v < 500.0f.  Every positive of the chunk meets candidate k on that side.
+ *   Id.         u = mix(S + (((j << 8) | k) + 1) G) >> 32.  Typed, rho_j valid: L = the side's type list of rho_j in the typed index
+ *               (type_tails / type_heads / type_bounds: sorted, duplicates removed); |L| > 0: id = L[(u |L|) >> 32].  Otherwise --
+ *               untyped, a relation without a list, an empty list -- id = (u ent_total) >> 32.  Drawn with replacement.
+ *   Mask, loss, records.  As above: a pair is masked exactly when its corrupted triple is a training triple (that includes the
+ *               candidate equal to the entity it replaces); loss = (1 / (batch_size N)) sum over the unmasked pairs, masked pairs
+ *               stay in the denominator; a hinge tie is active, sign(0) = 0.  pair[b][k] = side_k | (masked ? 2 : 0), b the SORTED
+ *               position.  Records in kge_transe_emit_records' format: record s * n_pos + b is slot s (h / t / r) of sorted
+ *               position b, record 3 n_pos + j N + k candidate k of chunk j -- 3 n_pos + cap N records; the candidate keys of an
+ *               unused chunk slot are -1.  1 <= P <= 127, 1 <= N <= 63.
+ * kge_shared_chunk_cap: the bound `cap` above (host only).
+ * kge_shared_order_by_relation: d_perm (int32 [n_pos]), the ids in sorted order d_h2 / d_t2 / d_r2 (d_r2 keeps the ids as given),
+ *   d_chunks (int2 [cap] as int32 pairs, cap = kge_shared_chunk_cap(n_pos, P, rel_total of the imported training set)) and
+ *   d_n_chunks (int32 [1]).  A stable radix sort of the clamped relation ids (rocPRIM), a max-scan of the run starts, a plus-scan of
+ *   the chunk starts; the engine itself has no size branch here.  Needs an imported training set (its rel_total).
+ * kge_shared_negatives_draw_grouped: d_cand (int32 [cap][N]; -1 in unused slots) and d_pair (uint8 [n_pos][N]) of a table -- the
+ *   ordering stage's, or any table whose used slots come first and in position order.  A thread per pair and per candidate; a pair
+ *   finds its chunk by bisection in the table, its mask by the bisection of kge_shared_negatives_draw.  typed != 0 draws from the
+ *   type lists and fails with type-constrained sampling's own error when none are imported, set or derived.
+ * kge_transe_emit_records_shared_chunks: kge_transe_emit_records_shared with workgroup j reading (first position, length) from
+ *   d_chunks[j] instead of computing them from j and P; cap workgroups, 3 n_pos + cap N records.  A slot of length 0 (or one that
+ *   points outside [0, n_pos)) writes its N candidate keys as -1 and a zero loss partial.  The loss partials are summed over all
+ *   cap slots in index order.  A table that states fixed chunks of P gives kge_transe_emit_records_shared's records, keys and loss
+ *   bit for bit.  Same refusals (there is no P to refuse; a chunk longer than 127 is the caller's error). */
+INT kge_shared_chunk_cap(INT n_pos, INT P, INT rel_total);
+int kge_shared_order_by_relation(const int32_t *d_h, const int32_t *d_t, const int32_t *d_r, INT n_pos, INT P, int32_t *d_perm, int32_t *d_h2,
+                                 int32_t *d_t2, int32_t *d_r2, int32_t *d_chunks, int32_t *d_n_chunks, void *stream);
+int kge_shared_negatives_draw_grouped(const int32_t *d_h2, const int32_t *d_t2, const int32_t *d_r2, INT n_pos, const int32_t *d_chunks, INT cap,
+                                      INT N, INT typed, uint64_t seed, INT step, int32_t *d_cand, uint8_t *d_pair, void *stream);
+int kge_transe_emit_records_shared_chunks(const kge_model_desc *m, const float *d_ent, const float *d_rel, const int32_t *d_h2, const int32_t *d_t2,
+                                          const int32_t *d_r2, INT n_pos, INT stride, const int32_t *d_chunks, INT cap, const int32_t *d_cand, INT N,
+                                          const uint8_t *d_pair, INT denom, uint32_t *d_rec, int32_t *d_dst, float *d_loss, void *stream);
+
 /* ---- Table-sharded sparse path (N GPUs, BASELINE config #5): rank g OWNS the entity rows [g*chunk, (g+1)*chunk); what the
  * reference does with ps tasks holding the variables and workers pulling rows / pushing IndexedSlices over gRPC
  * (distribute_training.py:193-196) becomes: request ids -> all-to-all -> owners gather rows -> all-to-all -> emit records

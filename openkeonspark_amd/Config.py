@@ -55,6 +55,7 @@ class Config(object):
             self.valid_triple_classification = False
             self.type_constrained_sampling = False
             self._shared_chunk, self._shared_seed = 0, 0      # set_shared_negatives
+            self._shared_by_relation = False                  # ... its chunks are cut from the batch ordered by relation
             # engine-side additions
             self.seed = 0                 # parameter initialisation seed
             self.device = "cuda"
@@ -139,14 +140,13 @@ class Config(object):
         from the file: after init_evaluation_from_arrays(..., type_lists=...) / (..., derive_types=True) or
         derive_type_constraints() the engine's lists are used as they stand, which is how a graph given by init_from_arrays
         gets typed negatives."""
-        if flag and self._shared_chunk:
-            raise KgeError("type-constrained sampling cannot be combined with shared negatives: the shared candidates are drawn "
-                           "from all entities (typed candidates are not built)")
+        if flag and self._shared_chunk and not self._shared_by_relation:
+            raise KgeError("type-constrained sampling cannot be combined with shared negatives: " + step_plan.TYPED_NEEDS_BY_RELATION)
         self.type_constrained_sampling = bool(flag)
         if getattr(self, "trainTotal", None) is not None:      # after init(): switch the engine now
             self._apply_typed_sampling()
 
-    def set_shared_negatives(self, chunk, seed=0):
+    def set_shared_negatives(self, chunk, seed=0, by_relation=False):
         """Negatives SHARED by chunks of positives (NON-PARITY, opt-in, off by default; the reference draws every negative for
         one positive): `chunk` consecutive positives of a batch score the same set_ent_neg_rate(N) candidate entities, drawn
         from a counter hash of (seed, global_step) -- what PyTorch-BigGraph and DGL-KE do -- so a chunk gathers 3 chunk + N table
@@ -156,17 +156,23 @@ class Config(object):
         row-sharded (a width that is a multiple of 4, up to 64 ranks) and a chunk's rows cross the wire once per chunk, not once
         per pair; the run equals the one-process run bit for bit at any rank count.  Call it before
         set_model_and_session; chunk = 0 switches it off.  In this mode prefetch_sampling is ignored (the positives are drawn
-        when the step starts), hand-fed batches are refused and there is no persistent launch."""
+        when the step starts), hand-fed batches are refused and there is no persistent launch.
+        by_relation=True: the step's positives are ordered by relation (stable) and a chunk never crosses a relation boundary --
+        the run of a relation is cut into pieces of `chunk`, the last may be short (train_paths.shared_grouped_step; the
+        definition is in include/kge_mi355.h).  A candidate then has ONE side for its whole chunk, and with
+        set_type_constrained_sampling(True), in either call order, it is drawn from that side's type list of the chunk's relation
+        (all entities for a relation without a list); the lists are found as typed sampling finds them.  One rank only: a
+        rank's slice would need the order of the whole batch."""
         if self.trainModel is not None:
             raise KgeError("set_shared_negatives must be called before set_model_and_session: it decides the step's path")
         chunk = int(chunk)
         if chunk and not 1 <= chunk <= step_plan.SHARED_MAX_CHUNK:
             raise KgeError("shared negatives: a chunk holds 1 to %d positives (a candidate's count lies within +-chunk and is "
                            "carried as an int8), got %d" % (step_plan.SHARED_MAX_CHUNK, chunk))
-        if chunk and self.type_constrained_sampling:
-            raise KgeError("shared negatives cannot be combined with type-constrained sampling: the shared candidates are drawn "
-                           "from all entities (typed candidates are not built)")
-        self._shared_chunk, self._shared_seed = chunk, int(seed) & 0xFFFFFFFFFFFFFFFF
+        by_relation = bool(by_relation) and chunk > 0
+        if chunk and self.type_constrained_sampling and not by_relation:
+            raise KgeError("shared negatives cannot be combined with type-constrained sampling: " + step_plan.TYPED_NEEDS_BY_RELATION)
+        self._shared_chunk, self._shared_seed, self._shared_by_relation = chunk, int(seed) & 0xFFFFFFFFFFFFFFFF, by_relation
 
     def _refuse_shared_ranks(self, stepping=False):
         """Shared negatives across ranks train a row-sharded entity table (train_paths.shared_sharded_step) and nothing else:
@@ -174,6 +180,10 @@ class Config(object):
         data-parallel step without the shards."""
         if not (self._shared_chunk and self._dp):
             return
+        if self._shared_by_relation:
+            raise KgeError("shared negatives by relation train on one rank only: the chunks are cut from the whole batch ordered by "
+                           "relation, and a rank's slice of the batch would need that global order (this run: %d ranks)"
+                           % self.world_size)
         if self.hidden_size % 4 or self.world_size > 64:
             raise KgeError("shared negatives on more than one rank train a row-sharded entity table, which needs an embedding "
                            "width that is a multiple of 4 (this run: %d) and at most 64 ranks (this run: %d); there is no "
@@ -189,12 +199,19 @@ class Config(object):
         [_first_pos, _first_pos + n_pos), row 0 of `pair` is position _first_pos and row 0 of `cand` is global chunk
         _first_pos // chunk -- which the rank may share with its neighbour, each holding the same candidates for it.
         An inspector: the lists of the most recent step are kept, no others (a pair's mask depends on the step's
-        positives, which are not)."""
+        positives, which are not).
+        With by_relation=True: (cand [n_chunks, N], pair [n_pos, N], perm int32 [n_pos], chunks int32 [n_chunks, 2]) -- row b of
+        `pair` is SORTED position b, which holds batch position perm[b]; chunks[j] = (first sorted position, length) of chunk j,
+        whose candidates are row j of `cand`; bit 0 of pair[b][k] is the side of candidate k, the same for every b of a chunk."""
         buf = self._sparse_buf if self._shared_chunk else None
         if not buf or buf.get("shared_step") != int(step):
             raise KgeError("shared_negatives_of: only the lists of the most recent shared-negatives step are kept (step %s)"
                            % (buf.get("shared_step") if buf else None))
         n_pos, n_chunks = buf["shared_shape"]
+        if self._shared_by_relation:      # (cand[:n_chunks], pair by SORTED position, perm, chunks[:n_chunks]); the count is read here, not in the step
+            n_chunks = int(buf["n_chunks"].item())
+            return (buf["cand"][:n_chunks].cpu().numpy(), buf["pair"][:n_pos].cpu().numpy(), buf["perm"][:n_pos].cpu().numpy(),
+                    buf["chunks"][:n_chunks].cpu().numpy())
         return buf["cand"][:n_chunks].cpu().numpy(), buf["pair"][:n_pos].cpu().numpy()
 
     def _forget_evaluation(self, arrays=False):
@@ -449,10 +466,8 @@ class Config(object):
             probe.model_id, self.opt_method, getattr(self, "sparse_rows", None), getattr(self, "use_counts", True),
             self.lib.kge_transe_counts_supported(ctypes.byref(probe.descriptor()), n_neg), self.entTotal, self.relTotal,
             self.hidden_size, self.batch_size, n_neg, getattr(self, "sparse_threshold_bytes", None), self.adagrad_initial_accumulator,
-            shared_chunk=self._shared_chunk, negative_rel=self.negative_rel)
-        if self._shared_chunk and self.type_constrained_sampling:
-            raise KgeError("shared negatives cannot be combined with type-constrained sampling: the shared candidates are drawn "
-                           "from all entities (typed candidates are not built)")
+            shared_chunk=self._shared_chunk, negative_rel=self.negative_rel, by_relation=self._shared_by_relation,
+            typed=bool(self._shared_chunk and self.type_constrained_sampling))
         self.use_counts, self.sparse_rows, self.sparse_inplace = p.use_counts, p.sparse_rows, p.sparse_inplace
         self._adam, self._lazy_adam, self._adagrad = p.adam, p.lazy_adam, p.adagrad
         self._has_slots, self._rows_rule = p.has_slots, p.rows_rule
@@ -812,7 +827,8 @@ class Config(object):
                                "candidates from the global step)")
             self._refuse_shared_ranks(stepping=True)
             dev, n_pos = self._sample_positives()
-            step = train_paths.shared_sharded_step if self._dp else train_paths.shared_step
+            step = (train_paths.shared_sharded_step if self._dp else
+                    train_paths.shared_grouped_step if self._shared_by_relation else train_paths.shared_step)
             step(self, dev, n_pos, max(self._n_local, 1), self.batch_size * self.negative_ent)
             self.trainModel.loss = self._loss
             return float(self._loss.item()) if sync else self._loss

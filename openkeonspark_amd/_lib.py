@@ -172,6 +172,13 @@ def _declare(L):
     L.kge_transe_emit_records_shared.argtypes = [ctypes.POINTER(ModelDesc), vp, vp, vp, vp, vp, i64, i64, i64, vp, i64, vp, i64, vp, vp, vp, vp]
     L.kge_shared_negatives_draw_at.argtypes = L.kge_shared_negatives_draw.argtypes      # (any first_position)
     L.kge_transe_emit_records_shared_at.argtypes = [ctypes.POINTER(ModelDesc), vp, vp, vp, vp, vp, i64, i64, i64, i64, vp, i64, vp, i64, vp, vp, vp, vp]
+    # ... on relation-grouped chunks, with typed candidates
+    L.kge_shared_chunk_cap.restype = i64
+    L.kge_shared_chunk_cap.argtypes = [i64, i64, i64]
+    L.kge_shared_order_by_relation.argtypes = [vp, vp, vp, i64, i64, vp, vp, vp, vp, vp, vp, vp]
+    L.kge_shared_negatives_draw_grouped.argtypes = [vp, vp, vp, i64, vp, i64, i64, i64, ctypes.c_uint64, i64, vp, vp, vp]
+    L.kge_transe_emit_records_shared_chunks.argtypes = [ctypes.POINTER(ModelDesc), vp, vp, vp, vp, vp, i64, i64, vp, i64, vp, i64, vp, i64, vp, vp,
+                                                        vp, vp]
     L.kge_transe_apply_counts_range.argtypes =[ctypes.POINTER(ModelDesc), vp, vp, vp, vp, vp, i64, i64, i64, i32, f32, f32, f32, f32, vp]
     # table-sharded sparse path (csrc/shard.hip)
     L.kge_shard_requests.argtypes = [vp, vp, vp, i64, i64, i64, vp, vp]

@@ -93,9 +93,9 @@ int ensure_typed_host_index() {
     return KGE_OK;
 }
 
-int ensure_typed_index() {
+int ensure_typed_index(bool always) {
     Engine &e = engine();
-    if (!e.typed_sampling) return KGE_OK;
+    if (!e.typed_sampling && !always) return KGE_OK;
     int rc = ensure_typed_host_index();
     if (rc) return rc;
     if (e.dev.typed_uploaded) return KGE_OK;

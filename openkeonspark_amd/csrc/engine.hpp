@@ -141,8 +141,9 @@ int fail(int code, const std::string &msg);
 bool device_ok();
 // uploads index / rng streams if needed; returns KGE_OK or an error code
 int ensure_device_index();
-// typed sampling on: builds the typed part of the host index if it is stale and uploads it (after ensure_device_index); off: nothing
-int ensure_typed_index();
+// typed sampling on: builds the typed part of the host index if it is stale and uploads it (after ensure_device_index); off: nothing,
+// unless `always` (the typed draw of shared negatives needs the lists whatever the sampler's mode)
+int ensure_typed_index(bool always = false);
 int ensure_typed_host_index();   // the host part alone (no device needed)
 // eval.hip: the imported relation type lists (importTypeFiles), false when none are
 struct TypeListsHost { const std::vector<int32_t> *head_lef, *head_rig, *head_type, *tail_lef, *tail_rig, *tail_type; };

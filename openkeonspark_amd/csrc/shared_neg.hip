@@ -25,9 +25,16 @@
 // Chunk membership is a property of the GLOBAL batch position: position p belongs to chunk p / P.  The `_at` entry points take a
 // call that begins at any position -- a rank's slice of the batch -- so its first and last chunks may be partial; both kernels
 // carry that as one offset (first_position % P, zero for the older entry points) in their chunk arithmetic.
+// RELATION-GROUPED chunks (kge_shared_order_by_relation / kge_shared_negatives_draw_grouped / kge_transe_emit_records_shared_chunks;
+// the section near the end of this file): the batch is ordered by relation, chunks never cross a relation boundary and are
+// stated by a table of (first sorted position, length); a candidate has one side for its chunk and may come from the relation's
+// type list.  The emit kernel is the same body with its positions read from the table (template parameter TABLE).
 #include <algorithm>
+#include <cstring>
 #include <string>
 #include <vector>
+
+#include <rocprim/rocprim.hpp>
 
 #include "engine.hpp"
 #include "mix_dev.hpp"
@@ -152,6 +159,7 @@ struct SharedEmitArgs {
     uint32_t *rec;
     int32_t *dst;
     float *partials;
+    const int2 *chunks;          // TABLE instantiations: [gridDim.x] (first position, length) per workgroup
 };
 
 __device__ __forceinline__ uint32_t padd8(uint32_t x, uint32_t y) {  // per-byte add, no carry across bytes
@@ -168,7 +176,9 @@ __device__ __forceinline__ void wave_lds_order() {   // LDS traffic inside one w
 }
 __device__ __forceinline__ int sgn_i(float e) { return (e > 0.f ? 1 : 0) - (e < 0.f ? 1 : 0); }
 
-template <int Q, bool VEC>
+// TABLE: workgroup j reads its positions from a.chunks[j] (relation-grouped chunks, kge_transe_emit_records_shared_chunks) instead
+// of computing them from j, P and off; a slot of length 0 blanks its N candidate keys, leaves a zero partial and is done.
+template <int Q, bool VEC, bool TABLE = false>
 __global__ __launch_bounds__(256) void shared_emit_kernel(SharedEmitArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
     const int T = a.T, RS = a.RS, D = a.D;
@@ -181,8 +191,22 @@ __global__ __launch_bounds__(256) void shared_emit_kernel(SharedEmitArgs a) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     uint8_t *stage = stage_all + wave * 3 * RS;
     const long long j = blockIdx.x;
-    const long long b0 = max(0LL, j * a.P - a.off);
-    const int Pc = (int)(min(a.n_pos, (j + 1) * a.P - a.off) - b0);
+    long long b0;
+    int Pc;
+    if constexpr (TABLE) {
+        const int2 c = a.chunks[j];
+        const bool in = c.x >= 0 && c.x < a.n_pos && c.y > 0;       // (a slot that points outside the call is an empty one)
+        b0 = in ? c.x : 0;
+        Pc = in ? (int)min((long long)c.y, a.n_pos - b0) : 0;
+        if (Pc == 0) {
+            if ((int)threadIdx.x < a.N) a.dst[3 * a.n_pos + j * a.N + threadIdx.x] = -1;
+            if (threadIdx.x == 0) a.partials[j] = 0.f;
+            return;
+        }
+    } else {
+        b0 = max(0LL, j * a.P - a.off);
+        Pc = (int)(min(a.n_pos, (j + 1) * a.P - a.off) - b0);
+    }
     bool valid[Q];
 #pragma unroll
     for (int q = 0; q < Q; q++) valid[q] = 4 * (lane + 64 * q) < RS;
@@ -408,14 +432,16 @@ int draw_call(const char *who, bool aligned, const int32_t *d_h, const int32_t *
     return hip_check(hipGetLastError(), "shared negatives draw launch");
 }
 
+// `chunks` null: chunks of P by position, as above.  Not null: the `cap` slots of a chunk table (relation-grouped chunks) -- one
+// workgroup and one loss partial per slot, P and first_position unused.
 int emit_call(const char *who, const kge_model_desc *m, const float *d_ent, const float *d_rel, const int32_t *d_h, const int32_t *d_t,
-              const int32_t *d_r, INT n_pos, INT stride, INT first_position, INT P, const int32_t *d_cand, INT N, const uint8_t *d_pair,
-              INT denom, uint32_t *d_rec, int32_t *d_dst, float *d_loss, hipStream_t stream) {
+              const int32_t *d_r, INT n_pos, INT stride, INT first_position, INT P, const int2 *chunks, INT cap, const int32_t *d_cand, INT N,
+              const uint8_t *d_pair, INT denom, uint32_t *d_rec, int32_t *d_dst, float *d_loss, hipStream_t stream) {
     const std::string w(who);
     if (!device_ok()) return fail(KGE_ERR_NO_DEVICE, w + ": no usable HIP device");
     if (!m || m->model != KGE_TRANSE) return fail(KGE_ERR_UNSUPPORTED, "shared negatives: TransE only");
     if (m->negative_rel != 0) return fail(KGE_ERR_UNSUPPORTED, "shared negatives: relation negatives are not supported (negative_rel must be 0)");
-    if (P < 1 || P > 127) return fail(KGE_ERR_UNSUPPORTED, "shared negatives: the chunk must hold 1..127 positives (a candidate's count is within +-P, an int8)");
+    if (!chunks && (P < 1 || P > 127)) return fail(KGE_ERR_UNSUPPORTED, "shared negatives: the chunk must hold 1..127 positives (a candidate's count is within +-P, an int8)");
     if (N < 1 || N > 63) return fail(KGE_ERR_UNSUPPORTED, "shared negatives: 1..63 negatives per positive (a positive's count is within +-2N, an int8)");
     if (!kge_transe_counts_supported(m, N)) return fail(KGE_ERR_UNSUPPORTED, "shared negatives: the sign-count path's shapes only (TransE, equal widths, rows below 2^30)");
     if (m->ent_dim > 512) return fail(KGE_ERR_UNSUPPORTED, "shared negatives: the shared emit kernel holds embedding widths up to 512");
@@ -423,8 +449,8 @@ int emit_call(const char *who, const kge_model_desc *m, const float *d_ent, cons
         !d_dst || !d_loss)
         return fail(KGE_ERR_BAD_ARG, w + ": bad arguments");
     if (n_pos == 0) return hip_check(hipMemsetAsync(d_loss, 0, sizeof(float), stream), "zero loss");
-    const long long off = first_position % P;
-    const long long n_chunks = (off + n_pos + P - 1) / P;
+    const long long off = chunks ? 0 : first_position % P;
+    const long long n_chunks = chunks ? cap : (off + n_pos + P - 1) / P;
     if (3 * n_pos + n_chunks * N >= (INT(1) << 31) || n_chunks >= (INT(1) << 31)) return fail(KGE_ERR_UNSUPPORTED, "shared negatives: batch too large");
     int rc = g_partials.reserve(n_chunks, "shared negatives loss partials");
     if (rc) return rc;
@@ -436,7 +462,7 @@ int emit_call(const char *who, const kge_model_desc *m, const float *d_ent, cons
     transe_team_shape(a.D, L, C);
     a.L = L; a.RD = L * ((C + 3) / 4); a.nat = a.D % 4 == 0;
     a.ent_total = (int)m->ent_total; a.rel_total = (int)m->rel_total; a.margin = m->margin;
-    a.rec = d_rec; a.dst = d_dst; a.partials = g_partials;
+    a.rec = d_rec; a.dst = d_dst; a.partials = g_partials; a.chunks = chunks;
     const int per_cand = a.RS * 5 + 8, fixed = 12 * a.RS + 16;
     const int t_max = (kLdsBudget - fixed) / per_cand;     // >= 21 at width 512
     a.n_tiles = ((int)N + t_max - 1) / t_max;
@@ -444,7 +470,15 @@ int emit_call(const char *who, const kge_model_desc *m, const float *d_ent, cons
     const size_t lds_bytes = (size_t)a.T * per_cand + fixed;
     const dim3 grid((unsigned)n_chunks), block(256);
     const bool vec = a.D % 4 == 0;
-    if (a.D <= 256) {
+    if (chunks) {
+        if (a.D <= 256) {
+            if (vec) hipLaunchKernelGGL((shared_emit_kernel<1, true, true>), grid, block, lds_bytes, stream, a);
+            else hipLaunchKernelGGL((shared_emit_kernel<1, false, true>), grid, block, lds_bytes, stream, a);
+        } else {
+            if (vec) hipLaunchKernelGGL((shared_emit_kernel<2, true, true>), grid, block, lds_bytes, stream, a);
+            else hipLaunchKernelGGL((shared_emit_kernel<2, false, true>), grid, block, lds_bytes, stream, a);
+        }
+    } else if (a.D <= 256) {
         if (vec) hipLaunchKernelGGL((shared_emit_kernel<1, true>), grid, block, lds_bytes, stream, a);
         else hipLaunchKernelGGL((shared_emit_kernel<1, false>), grid, block, lds_bytes, stream, a);
     } else {
@@ -453,6 +487,133 @@ int emit_call(const char *who, const kge_model_desc *m, const float *d_ent, cons
     }
     hipLaunchKernelGGL(shared_loss_kernel, dim3(1), dim3(256), 0, stream, (const float *)g_partials.ptr(), n_chunks, 1.0f / (float)denom, d_loss);
     return hip_check(hipGetLastError(), "shared negatives emit launch");
+}
+
+// ---- relation-grouped chunks (include/kge_mi355.h, "Shared negatives on relation-grouped chunks") -------------------------
+// Order: a stable radix sort of (relation or rel_total, batch position) -- rocPRIM's, the index build's.  One kernel gathers the
+// ids into sorted order and marks the run starts; a max-scan carries every position's run start; a position is a chunk start
+// when its distance from the run start is a multiple of P, and a plus-scan numbers the chunks; the LAST position of a chunk
+// knows its number, its first position and its length and writes the table entry.  No size branch of the engine's own (rocPRIM
+// chooses its sort and scan shapes by size); every launch is sized by n_pos or cap, and n_chunks stays on the device.
+struct OrderScratch {
+    DevBuf<uint32_t> key, key2;
+    DevBuf<int32_t> pos, start, idx;
+    DevBuf<char> tmp;
+};
+OrderScratch g_ord;
+
+__global__ __launch_bounds__(256) void order_keys_kernel(const int32_t *__restrict__ r, long long n, int rel_total, uint32_t *__restrict__ key,
+                                                         int32_t *__restrict__ pos) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const int v = r[i];
+    key[i] = (v >= 0 && v < rel_total) ? (uint32_t)v : (uint32_t)rel_total;
+    pos[i] = (int32_t)i;
+}
+
+__global__ __launch_bounds__(256) void order_gather_kernel(const int32_t *__restrict__ h, const int32_t *__restrict__ t, const int32_t *__restrict__ r,
+                                                           const uint32_t *__restrict__ key2, const int32_t *__restrict__ perm, long long n,
+                                                           int32_t *__restrict__ h2, int32_t *__restrict__ t2, int32_t *__restrict__ r2,
+                                                           int32_t *__restrict__ start) {
+    const long long b = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (b >= n) return;
+    const int p = perm[b];
+    h2[b] = h[p]; t2[b] = t[p]; r2[b] = r[p];
+    start[b] = (b > 0 && key2[b] != key2[b - 1]) ? (int32_t)b : 0;      // (max-scanned: the first position of b's run)
+}
+
+__global__ __launch_bounds__(256) void order_flags_kernel(const int32_t *__restrict__ start, long long n, int P, int32_t *__restrict__ idx) {
+    const long long b = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (b < n) idx[b] = (b - start[b]) % P == 0 ? 1 : 0;
+}
+
+__global__ __launch_bounds__(256) void order_table_kernel(const uint32_t *__restrict__ key2, const int32_t *__restrict__ start,
+                                                          const int32_t *__restrict__ idx, long long n, long long cap, int P,
+                                                          int2 *__restrict__ chunks, int32_t *__restrict__ n_chunks) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    const int total = idx[n - 1];
+    if (i == 0) n_chunks[0] = total;
+    if (i < n) {
+        const int in_run = (int)(i - start[i]);
+        const bool last = i == n - 1 || key2[i + 1] != key2[i] || (in_run + 1) % P == 0;
+        const int j = idx[i] - 1;
+        if (last && j >= 0 && j < cap) chunks[j] = make_int2((int)i - in_run % P, in_run % P + 1);
+    }
+    if (i >= total && i < cap) chunks[i] = make_int2((int)n, 0);
+}
+
+long long chunk_cap(long long n_pos, long long P, long long rel_total) {
+    return (n_pos + P - 1) / P + std::min(rel_total + 1, n_pos);
+}
+
+struct GroupedDrawArgs {
+    const int32_t *h, *t, *r;        // in sorted order
+    const int2 *chunks;
+    long long n_pos, cap;
+    int N, typed;
+    unsigned long long S;
+    int ent_total, rel_total, bern;
+    const float *bern_prob;
+    const int4 *type_bounds;
+    const int32_t *type_tails, *type_heads;
+    const int32_t *tails_hr, *heads_tr;
+    const long long *hr_key, *tr_key;
+    const int2 *hr_span, *tr_span;
+    int n_hr, n_tr;
+    int32_t *cand;
+    uint8_t *pair;
+};
+
+// side and id of candidate k of chunk j, whose relation is r (any value; outside the table: an even coin, all entities)
+__device__ __forceinline__ int grouped_candidate(const GroupedDrawArgs &a, long long j, int k, int r, bool &new_tail) {
+    const bool r_ok = r >= 0 && r < a.rel_total;
+    const unsigned long long c = ((unsigned long long)j << 8) | (unsigned long long)k;
+    const unsigned long long v = mix_scale(mix64(a.S + ((c | 128ULL) + 1ULL) * kMixGamma), 1000ULL);
+    const float prob = (a.bern && r_ok) ? a.bern_prob[r] : 500.0f;
+    new_tail = (float)v < prob;
+    const unsigned long long z = mix64(a.S + (c + 1ULL) * kMixGamma);
+    if (a.typed && r_ok) {
+        const int4 tb = a.type_bounds[r];
+        const int off = new_tail ? tb.x : tb.z, len = new_tail ? tb.y : tb.w;
+        if (len > 0) return (new_tail ? a.type_tails : a.type_heads)[off + (int)mix_scale(z, (unsigned long long)len)];
+    }
+    return (int)mix_scale(z, (unsigned long long)a.ent_total);
+}
+
+__global__ __launch_bounds__(256) void grouped_draw_kernel(GroupedDrawArgs a) {
+    const long long n_pair = a.n_pos * a.N, n_all = n_pair + a.cap * a.N;
+    for (long long g = (long long)blockIdx.x * 256 + threadIdx.x; g < n_all; g += (long long)gridDim.x * 256) {
+        bool new_tail;
+        if (g >= n_pair) {
+            const long long j = (g - n_pair) / a.N;
+            const int k = (int)((g - n_pair) % a.N);
+            const int2 ch = a.chunks[j];
+            const bool used = ch.y > 0 && ch.x >= 0 && ch.x < a.n_pos;
+            a.cand[g - n_pair] = used ? grouped_candidate(a, j, k, a.r[ch.x], new_tail) : -1;
+            continue;
+        }
+        const long long b = g / a.N;
+        const int k = (int)(g % a.N);
+        // the chunk of sorted position b: the last used slot that begins at or before it (used slots come first, in position order)
+        const int j = bisect_count((int)a.cap, [&](int mid) { const int2 ch = a.chunks[mid]; return ch.y > 0 && ch.x <= b; }) - 1;
+        const int h = a.h[b], t = a.t[b], r = a.r[b];
+        if (j < 0) { a.pair[g] = 2; continue; }        // (a table that does not cover b: the pair takes no part)
+        const int c = grouped_candidate(a, j, k, r, new_tail);
+        const bool r_ok = r >= 0 && r < a.rel_total;
+        const int anchor = new_tail ? h : t;
+        bool masked = false;
+        if (r_ok && anchor >= 0 && anchor < a.ent_total) {
+            const long long key = (long long)anchor * a.rel_total + r;
+            const long long *keys = new_tail ? a.hr_key : a.tr_key;
+            const int n = new_tail ? a.n_hr : a.n_tr;
+            const int at = bisect_count(n, [&](int mid) { return keys[mid] < key; });
+            if (at < n && keys[at] == key) {
+                const int2 sp = (new_tail ? a.hr_span : a.tr_span)[at];
+                masked = sorted_contains((new_tail ? a.tails_hr : a.heads_tr) + sp.x, sp.y, c);
+            }
+        }
+        a.pair[g] = (uint8_t)((new_tail ? 0 : 1) | (masked ? 2 : 0));
+    }
 }
 
 }  // namespace
@@ -476,15 +637,105 @@ int kge_shared_negatives_draw_at(const int32_t *d_h, const int32_t *d_t, const i
 int kge_transe_emit_records_shared(const kge_model_desc *m, const float *d_ent, const float *d_rel, const int32_t *d_h, const int32_t *d_t,
                                    const int32_t *d_r, INT n_pos, INT stride, INT P, const int32_t *d_cand, INT N, const uint8_t *d_pair,
                                    INT denom, uint32_t *d_rec, int32_t *d_dst, float *d_loss, void *stream) {
-    return emit_call("kge_transe_emit_records_shared", m, d_ent, d_rel, d_h, d_t, d_r, n_pos, stride, 0, P, d_cand, N, d_pair, denom, d_rec, d_dst,
-                     d_loss, (hipStream_t)stream);
+    return emit_call("kge_transe_emit_records_shared", m, d_ent, d_rel, d_h, d_t, d_r, n_pos, stride, 0, P, nullptr, 0, d_cand, N, d_pair, denom, d_rec,
+                     d_dst, d_loss, (hipStream_t)stream);
 }
 
 int kge_transe_emit_records_shared_at(const kge_model_desc *m, const float *d_ent, const float *d_rel, const int32_t *d_h, const int32_t *d_t,
                                       const int32_t *d_r, INT n_pos, INT stride, INT first_position, INT P, const int32_t *d_cand, INT N,
                                       const uint8_t *d_pair, INT denom, uint32_t *d_rec, int32_t *d_dst, float *d_loss, void *stream) {
-    return emit_call("kge_transe_emit_records_shared_at", m, d_ent, d_rel, d_h, d_t, d_r, n_pos, stride, first_position, P, d_cand, N, d_pair, denom,
-                     d_rec, d_dst, d_loss, (hipStream_t)stream);
+    return emit_call("kge_transe_emit_records_shared_at", m, d_ent, d_rel, d_h, d_t, d_r, n_pos, stride, first_position, P, nullptr, 0, d_cand, N, d_pair,
+                     denom, d_rec, d_dst, d_loss, (hipStream_t)stream);
+}
+
+INT kge_shared_chunk_cap(INT n_pos, INT P, INT rel_total) {
+    if (n_pos < 0 || P < 1 || rel_total < 0) return fail(KGE_ERR_BAD_ARG, "kge_shared_chunk_cap: n_pos >= 0, P >= 1 and rel_total >= 0");
+    return chunk_cap(n_pos, P, rel_total);
+}
+
+int kge_shared_order_by_relation(const int32_t *d_h, const int32_t *d_t, const int32_t *d_r, INT n_pos, INT P, int32_t *d_perm, int32_t *d_h2,
+                                 int32_t *d_t2, int32_t *d_r2, int32_t *d_chunks, int32_t *d_n_chunks, void *stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    if (!device_ok()) return fail(KGE_ERR_NO_DEVICE, "kge_shared_order_by_relation: no usable HIP device");
+    if (P < 1 || P > 127) return fail(KGE_ERR_BAD_ARG, "kge_shared_order_by_relation: the chunk must hold 1..127 positives (a candidate's count is within +-P, an int8)");
+    if (n_pos < 0 || n_pos >= (INT(1) << 31) || !d_h || !d_t || !d_r || !d_perm || !d_h2 || !d_t2 || !d_r2 || !d_chunks || !d_n_chunks)
+        return fail(KGE_ERR_BAD_ARG, "kge_shared_order_by_relation: bad arguments");
+    Engine &e = engine();
+    if (!e.index.loaded) return fail(KGE_ERR_NO_DATASET, "kge_shared_order_by_relation: no training set imported (rel_total is the imported set's)");
+    int rc;
+    if (n_pos == 0) return hip_check(hipMemsetAsync(d_n_chunks, 0, sizeof(int32_t), stream), "zero chunk count");
+    const int rel_total = (int)e.index.rel_total;
+    const long long cap = chunk_cap(n_pos, P, rel_total);
+    if ((rc = g_ord.key.reserve(n_pos, "relation order keys")) || (rc = g_ord.key2.reserve(n_pos, "relation order keys")) ||
+        (rc = g_ord.pos.reserve(n_pos, "relation order positions")) || (rc = g_ord.start.reserve(n_pos, "relation order run starts")) ||
+        (rc = g_ord.idx.reserve(n_pos, "relation order chunk numbers")))
+        return rc;
+    unsigned bits = 1;
+    while ((1ULL << bits) <= (unsigned long long)rel_total) bits++;
+    const size_t n = (size_t)n_pos;
+    size_t need_sort = 0, need_max = 0, need_sum = 0;
+    if ((rc = hip_check(rocprim::radix_sort_pairs(nullptr, need_sort, g_ord.key.ptr(), g_ord.key2.ptr(), g_ord.pos.ptr(), d_perm, n, 0, bits, stream),
+                        "relation order sort size")) ||
+        (rc = hip_check(rocprim::inclusive_scan(nullptr, need_max, g_ord.start.ptr(), g_ord.start.ptr(), n, rocprim::maximum<int32_t>(), stream),
+                        "relation order scan size")) ||
+        (rc = hip_check(rocprim::inclusive_scan(nullptr, need_sum, g_ord.idx.ptr(), g_ord.idx.ptr(), n, rocprim::plus<int32_t>(), stream),
+                        "relation order scan size")))
+        return rc;
+    const size_t need = std::max(need_sort, std::max(need_max, need_sum));
+    if ((rc = g_ord.tmp.reserve((int64_t)std::max(need, (size_t)1), "relation order scratch"))) return rc;
+    const dim3 grid((unsigned)((n_pos + 255) / 256)), block(256);
+    hipLaunchKernelGGL(order_keys_kernel, grid, block, 0, stream, d_r, (long long)n_pos, rel_total, g_ord.key.ptr(), g_ord.pos.ptr());
+    if ((rc = hip_check(rocprim::radix_sort_pairs(g_ord.tmp.ptr(), need_sort, g_ord.key.ptr(), g_ord.key2.ptr(), g_ord.pos.ptr(), d_perm, n, 0, bits, stream),
+                        "relation order sort")))
+        return rc;
+    hipLaunchKernelGGL(order_gather_kernel, grid, block, 0, stream, d_h, d_t, d_r, (const uint32_t *)g_ord.key2.ptr(), (const int32_t *)d_perm,
+                       (long long)n_pos, d_h2, d_t2, d_r2, g_ord.start.ptr());
+    if ((rc = hip_check(rocprim::inclusive_scan(g_ord.tmp.ptr(), need_max, g_ord.start.ptr(), g_ord.start.ptr(), n, rocprim::maximum<int32_t>(), stream),
+                        "relation order run scan")))
+        return rc;
+    hipLaunchKernelGGL(order_flags_kernel, grid, block, 0, stream, (const int32_t *)g_ord.start.ptr(), (long long)n_pos, (int)P, g_ord.idx.ptr());
+    if ((rc = hip_check(rocprim::inclusive_scan(g_ord.tmp.ptr(), need_sum, g_ord.idx.ptr(), g_ord.idx.ptr(), n, rocprim::plus<int32_t>(), stream),
+                        "relation order chunk scan")))
+        return rc;
+    const dim3 grid2((unsigned)((std::max((long long)n_pos, cap) + 255) / 256));
+    hipLaunchKernelGGL(order_table_kernel, grid2, block, 0, stream, (const uint32_t *)g_ord.key2.ptr(), (const int32_t *)g_ord.start.ptr(),
+                       (const int32_t *)g_ord.idx.ptr(), (long long)n_pos, cap, (int)P, reinterpret_cast<int2 *>(d_chunks), d_n_chunks);
+    return hip_check(hipGetLastError(), "relation order launch");
+}
+
+int kge_shared_negatives_draw_grouped(const int32_t *d_h2, const int32_t *d_t2, const int32_t *d_r2, INT n_pos, const int32_t *d_chunks, INT cap,
+                                      INT N, INT typed, uint64_t seed, INT step, int32_t *d_cand, uint8_t *d_pair, void *stream) {
+    if (N < 1 || N > 63) return fail(KGE_ERR_BAD_ARG, "kge_shared_negatives_draw_grouped: 1..63 negatives per positive (a positive's count is within +-2N, an int8)");
+    if (n_pos < 0 || cap < 0 || cap >= (INT(1) << 31) || step < 0 || !d_h2 || !d_t2 || !d_r2 || !d_chunks || !d_cand || !d_pair)
+        return fail(KGE_ERR_BAD_ARG, "kge_shared_negatives_draw_grouped: bad arguments");
+    int rc = ensure_device_index();
+    if (rc) return rc;
+    if ((rc = ensure_group_dir())) return rc;
+    if (typed && (rc = ensure_typed_index(true))) return rc;
+    if (n_pos == 0 && cap == 0) return KGE_OK;
+    Engine &e = engine();
+    GroupedDrawArgs a = {};
+    a.h = d_h2; a.t = d_t2; a.r = d_r2; a.chunks = reinterpret_cast<const int2 *>(d_chunks);
+    a.n_pos = n_pos; a.cap = cap; a.N = (int)N; a.typed = typed ? 1 : 0;
+    a.S = mix64((unsigned long long)seed + ((unsigned long long)step + 1ULL) * kMixGamma);
+    a.ent_total = (int)e.index.ent_total; a.rel_total = (int)e.index.rel_total; a.bern = e.bern ? 1 : 0;
+    a.bern_prob = e.dev.bern_prob; a.tails_hr = e.dev.tails_hr; a.heads_tr = e.dev.heads_tr;
+    a.type_bounds = e.dev.type_bounds; a.type_tails = e.dev.type_tails; a.type_heads = e.dev.type_heads;
+    a.hr_key = g_dir.hr_key; a.tr_key = g_dir.tr_key; a.hr_span = g_dir.hr_span; a.tr_span = g_dir.tr_span;
+    a.n_hr = g_dir.n_hr; a.n_tr = g_dir.n_tr;
+    a.cand = d_cand; a.pair = d_pair;
+    long long nb = ((n_pos + cap) * N + 255) / 256;
+    if (nb > 65536) nb = 65536;
+    hipLaunchKernelGGL(grouped_draw_kernel, dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream, a);
+    return hip_check(hipGetLastError(), "grouped shared negatives draw launch");
+}
+
+int kge_transe_emit_records_shared_chunks(const kge_model_desc *m, const float *d_ent, const float *d_rel, const int32_t *d_h2, const int32_t *d_t2,
+                                          const int32_t *d_r2, INT n_pos, INT stride, const int32_t *d_chunks, INT cap, const int32_t *d_cand, INT N,
+                                          const uint8_t *d_pair, INT denom, uint32_t *d_rec, int32_t *d_dst, float *d_loss, void *stream) {
+    if (!d_chunks || cap < 0 || (cap < 1 && n_pos > 0)) return fail(KGE_ERR_BAD_ARG, "kge_transe_emit_records_shared_chunks: bad arguments (a chunk table of at least one slot)");
+    return emit_call("kge_transe_emit_records_shared_chunks", m, d_ent, d_rel, d_h2, d_t2, d_r2, n_pos, stride, 0, 0,
+                     reinterpret_cast<const int2 *>(d_chunks), cap, d_cand, N, d_pair, denom, d_rec, d_dst, d_loss, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -110,6 +110,11 @@ def parse_args(argv=None):
                         "by row range (a width that is a multiple of 4) and the run equals the one-process run bit for bit; 0 = off "
                         "(default)")
     p.add_argument("--shared_negatives_seed", type=int, default=0, help="seed of the shared candidates' hash; a resumed run must repeat it")
+    p.add_argument("--shared_negatives_by_relation", type=int, default=0,
+                   help="1: with --shared_negatives_chunk P, the step's positives are ordered by relation and a chunk never crosses a "
+                        "relation boundary (the run of a relation is cut into pieces of P); a candidate has one side for its chunk and, "
+                        "with --type_constrained_sampling 1, comes from that side's type list of the chunk's relation "
+                        "(Config.set_shared_negatives(..., by_relation=True)).  One rank only; a resumed run must repeat it")
     p.add_argument("--type_constrained_sampling", type=int, default=0,
                    help="1: entity negatives of a training batch come from the relation's own head / tail type list "
                         "(type_constrain.txt in --input_path, required then) instead of from all entities; same random stream, "
@@ -150,7 +155,8 @@ def get_conf(argv):
     if getattr(argv, "sparse_rows", -1) >= 0:
         con.sparse_rows = bool(argv.sparse_rows)
     if getattr(argv, "shared_negatives_chunk", 0):
-        con.set_shared_negatives(argv.shared_negatives_chunk, getattr(argv, "shared_negatives_seed", 0))
+        con.set_shared_negatives(argv.shared_negatives_chunk, getattr(argv, "shared_negatives_seed", 0),
+                                 by_relation=bool(getattr(argv, "shared_negatives_by_relation", 0)))
     typed = bool(getattr(argv, "type_constrained_sampling", 0))
     path = argv.input_path if not argv.input_path or argv.input_path.endswith("/") else argv.input_path + "/"
     derive = bool(getattr(argv, "derive_type_constraints", 0)) and bool(path) and not os.path.exists(path + "type_constrain.txt") and \
@@ -215,11 +221,43 @@ def checkpoint_arrays(con):
                 out[name + "/Adagrad"] = a.detach().cpu().numpy()
     out["global_step"] = np.int64(con.global_step)
     if getattr(con, "_shared_chunk", 0):      # shared negatives: the candidates are a hash of (seed, global_step), chunked by `chunk`
-        out["shared_negatives"] = np.array([con._shared_chunk, con._shared_seed], dtype=np.uint64)
+        out["shared_negatives"] = shared_negatives_record(con)
     # with sampling one step ahead the device streams are one batch further than the training: store the states the
     # NEXT step's batch starts from, so that a resumed run trains on exactly the batches an uninterrupted one would
     out["rng_streams"] = con.get_stream_states(before_prefetch=True)
     return out
+
+
+def _shared_negatives_mode(con):
+    """(chunk, seed, by_relation, typed) of a Config's shared negatives; all zero when they are off.  typed: the candidates come
+    from the relations' type lists (type-constrained sampling on relation-grouped chunks)."""
+    chunk = int(getattr(con, "_shared_chunk", 0))
+    if not chunk:
+        return (0, 0, 0, 0)
+    by_relation = int(bool(getattr(con, "_shared_by_relation", False)))
+    return (chunk, int(getattr(con, "_shared_seed", 0)), by_relation, int(bool(by_relation and con.type_constrained_sampling)))
+
+
+def shared_negatives_record(con):
+    """What a checkpoint keeps of a run's shared negatives: uint64 [chunk, seed], and [chunk, seed, by_relation, typed] when the
+    chunks are relation-grouped (a record of two means False for both)."""
+    mode = _shared_negatives_mode(con)
+    return np.array(mode if mode[2] or mode[3] else mode[:2], dtype=np.uint64)
+
+
+def check_shared_negatives_record(z, con):
+    """A resumed run must draw the candidates the interrupted one would have drawn: refuse a checkpoint (its arrays `z`) whose
+    shared-negatives record differs from this run's."""
+    was = tuple(int(x) for x in z["shared_negatives"]) if "shared_negatives" in z else (0, 0)
+    was = (was + (0, 0))[:4]      # (a checkpoint without by_relation / typed: both off)
+    now = _shared_negatives_mode(con)
+    if was != now and not (was[2] or was[3] or now[2] or now[3]):      # chunks by position on both sides: the two fields alone
+        raise KgeError("the checkpoint was written with shared negatives (chunk, seed) = %s, this run has %s: resume with the same "
+                       "--shared_negatives_chunk / --shared_negatives_seed (0 0 = off)" % (was[:2], now[:2]))
+    if was != now:
+        raise KgeError("the checkpoint was written with shared negatives (chunk, seed, by_relation, typed) = %s, this run has %s: resume "
+                       "with the same --shared_negatives_chunk / --shared_negatives_seed / --shared_negatives_by_relation / "
+                       "--type_constrained_sampling (all 0 = off)" % (was, now))
 
 
 def _step_of(path):
@@ -414,11 +452,7 @@ def restore_checkpoint(con, path, allow_growth=True, arrays=None):
     of the entity table (and of its LazyAdam moments) from whichever file holds them."""
     z = arrays if arrays is not None else {k.replace("__", "/"): v for k, v in np.load(path).items()}
     # shared negatives: a resumed run must draw the candidates the interrupted one would have drawn
-    was = tuple(int(x) for x in z["shared_negatives"]) if "shared_negatives" in z else (0, 0)
-    now = (int(getattr(con, "_shared_chunk", 0)), int(getattr(con, "_shared_seed", 0)) if getattr(con, "_shared_chunk", 0) else 0)
-    if was != now:
-        raise KgeError("the checkpoint was written with shared negatives (chunk, seed) = %s, this run has %s: resume with the same "
-                       "--shared_negatives_chunk / --shared_negatives_seed (0 0 = off)" % (was, now))
+    check_shared_negatives_record(z, con)
     rng = np.random.default_rng(getattr(con, "seed", 0) + 1)
     shapes = con.trainModel.table_shapes()
     for i, name in enumerate(con.trainModel.table_names):

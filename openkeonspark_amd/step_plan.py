@@ -67,11 +67,13 @@ def wants_sparse_rows(sparse_rows, ent_total, rel_total, width, batch_size, n_ne
 
 
 def plan(model_id, opt_method, sparse_rows, use_counts, counts_supported, ent_total, rel_total, width, batch_size, n_neg,
-         sparse_threshold_bytes=None, adagrad_initial_accumulator=0.1, shared_chunk=0, negative_rel=0):
+         sparse_threshold_bytes=None, adagrad_initial_accumulator=0.1, shared_chunk=0, negative_rel=0, by_relation=False, typed=False):
     """The StepPlan of a configuration.  sparse_rows: None = automatic, True / False = the caller's wish; use_counts: the
     caller's wish; counts_supported: what kge_transe_counts_supported said for the model's descriptor and n_neg.
     shared_chunk: 0 = off; P > 0 = negatives shared by chunks of P positives (NON-PARITY, opt-in: Config.set_shared_negatives),
-    which is the sparse-rows record step whatever the table size; negative_rel: how many of the n_neg are relation negatives."""
+    which is the sparse-rows record step whatever the table size; negative_rel: how many of the n_neg are relation negatives;
+    by_relation: the chunks are cut from the batch ordered by relation (train_paths.shared_grouped_step); typed: type-constrained
+    sampling is on, which shared negatives take on such chunks only."""
     optimizer = optimizer_kind(opt_method)
     adam, lazy_adam, adagrad = optimizer == "adam", optimizer == "lazy_adam", optimizer == "adagrad"
     # LazyAdam -- opt-in, NON-PARITY: Adam on the touched rows only (tf.contrib.opt.LazyAdamOptimizer's rule) for tables whose dense
@@ -93,7 +95,7 @@ def plan(model_id, opt_method, sparse_rows, use_counts, counts_supported, ent_to
     table_bytes, sparse = wants_sparse_rows(sparse_rows, ent_total, rel_total, width, batch_size, n_neg, sparse_threshold_bytes)
     rows = (bool(sparse) or rows_rule) and use_counts and not adam
     if shared_chunk:
-        check_shared_negatives(model_id, optimizer, use_counts, shared_chunk, n_neg - negative_rel, negative_rel)
+        check_shared_negatives(model_id, optimizer, use_counts, shared_chunk, n_neg - negative_rel, negative_rel, by_relation, typed)
         return StepPlan(optimizer, use_counts, True, False, table_bytes)      # its records go through the touched-rows reduce
     # TransH / TransD (and TransE outside the sign-count path) with SGD: the touched rows are updated in place from float
     # gradient records (kge_forward_backward_sgd_rows) -- no gradient tables, no sweep.  On request, or by itself for tables
@@ -115,8 +117,16 @@ def plan(model_id, opt_method, sparse_rows, use_counts, counts_supported, ent_to
 SHARED_MAX_CHUNK, SHARED_MAX_NEGATIVES = 127, 63      # a candidate's count lies within +-P, a positive's within +-2N: both int8
 
 
-def check_shared_negatives(model_id, optimizer, use_counts, chunk, negative_ent, negative_rel):
-    """Raises KgeError, naming the limit, for a configuration the shared-negatives step cannot take."""
+TYPED_NEEDS_BY_RELATION = ("a chunk of consecutive batch positions mixes relations, so its candidates cannot come from one relation's "
+                           "type list; set_shared_negatives(chunk, by_relation=True) orders the batch by relation and draws typed "
+                           "candidates (without by_relation typed candidates are not built)")
+
+
+def check_shared_negatives(model_id, optimizer, use_counts, chunk, negative_ent, negative_rel, by_relation=False, typed=False):
+    """Raises KgeError, naming the limit, for a configuration the shared-negatives step cannot take.  by_relation: chunks cut from
+    the batch ordered by relation; typed: candidates from the relations' type lists, which needs by_relation."""
+    if typed and not by_relation:
+        raise KgeError("shared negatives cannot be combined with type-constrained sampling: " + TYPED_NEEDS_BY_RELATION)
     if not 1 <= int(chunk) <= SHARED_MAX_CHUNK:
         raise KgeError("shared negatives: a chunk holds 1 to %d positives (a candidate's count lies within +-chunk and is carried "
                        "as an int8), got %r" % (SHARED_MAX_CHUNK, chunk))

@@ -512,6 +512,86 @@ def shared_step(con, dev, n_pos, stride, denom):
     con.global_step += 1
 
 
+def shared_chunk_cap(n_pos, P, rel_total):
+    """The bound on the chunks of a relation-grouped batch: ceil(n_pos / P) + min(rel_total + 1, n_pos) (a run's last piece may be
+    short, and there are at most rel_total + 1 runs).  kge_shared_chunk_cap's value, for callers without the library."""
+    n_pos, P, rel_total = int(n_pos), int(P), int(rel_total)
+    if n_pos < 0 or P < 1 or rel_total < 0:
+        raise ValueError("shared_chunk_cap: n_pos >= 0, P >= 1 and rel_total >= 0, got %r" % ((n_pos, P, rel_total),))
+    return -(-n_pos // P) + min(rel_total + 1, n_pos)
+
+
+def shared_relation_chunks(r, P, rel_total):
+    """(perm int32 [n_pos], chunks int32 [cap, 2], n_chunks): the order and the chunk table of relation-grouped shared negatives,
+    in plain numpy -- the one host statement of the definition (include/kge_mi355.h).  perm is the stable order of the batch
+    positions by relation id, an id outside [0, rel_total) sorting as rel_total; the run of a relation is cut from its start into
+    pieces of P sorted positions, the last may be short; chunks[j] = (first sorted position, length) of piece j, and the slots
+    from n_chunks to cap = shared_chunk_cap(n_pos, P, rel_total) are (n_pos, 0)."""
+    import numpy as np
+    r = np.asarray(r).reshape(-1).astype(np.int64)
+    P, rel_total = int(P), int(rel_total)
+    n_pos = len(r)
+    cap = shared_chunk_cap(n_pos, P, rel_total)
+    key = np.where((r >= 0) & (r < rel_total), r, rel_total)
+    perm = np.argsort(key, kind="stable").astype(np.int32)
+    skey = key[perm]
+    starts = np.flatnonzero(np.r_[True, skey[1:] != skey[:-1]]) if n_pos else np.zeros(0, dtype=np.int64)
+    ends = np.r_[starts[1:], n_pos] if n_pos else starts
+    first = np.concatenate([np.arange(a, b, P) for a, b in zip(starts, ends)]) if n_pos else np.zeros(0, dtype=np.int64)
+    run_end = np.concatenate([np.full(-(-(b - a) // P), b) for a, b in zip(starts, ends)]) if n_pos else first
+    n_chunks = len(first)
+    chunks = np.zeros((cap, 2), dtype=np.int32)
+    chunks[:, 0] = n_pos
+    chunks[:n_chunks, 0] = first
+    chunks[:n_chunks, 1] = np.minimum(P, run_end - first)
+    return perm, chunks, n_chunks
+
+
+def shared_grouped_step(con, dev, n_pos, stride, denom):
+    """shared_step on RELATION-GROUPED chunks (Config.set_shared_negatives(..., by_relation=True); NON-PARITY, opt-in; one rank):
+    the ordering stage sorts the step's positives by relation and cuts the runs into chunks of at most P, the grouped draw hashes a
+    chunk's candidates and their sides from (seed, global_step) -- from the relation's type lists with type-constrained sampling
+    on -- and looks the masks up, the emit kernel reads its chunks from the table, and the sparse step's reduce and rows rule
+    finish over 3 n_pos + cap N records.  The chunk count stays on the device: everything is sized by cap =
+    shared_chunk_cap(stride, P, relTotal), and the step has no host synchronisation.  Buffers only grow."""
+    import torch
+    P, N, D = con._shared_chunk, con.negative_ent, con.hidden_size
+    cap = shared_chunk_cap(n_pos, P, con.relTotal)
+    cap_max = shared_chunk_cap(stride, P, con.relTotal)
+    m_cap = 3 * stride + cap_max * N
+    buf = con._sparse_buf
+    if buf is None or "chunks" not in buf or buf.get("shared_cap", 0) < m_cap or buf["pair"].shape[0] < stride:
+        d = con.device
+        dw = int(con.lib.kge_transe_record_dwords(ctypes.byref(con._desc)))
+        i32 = torch.int32
+        buf = dict(shared_cap=m_cap,
+                   perm=torch.empty(stride, dtype=i32, device=d), sorted=torch.empty((3, stride), dtype=i32, device=d),
+                   chunks=torch.empty((cap_max, 2), dtype=i32, device=d), n_chunks=torch.zeros(1, dtype=i32, device=d),
+                   cand=torch.empty((cap_max, N), dtype=i32, device=d),
+                   pair=torch.empty((stride, N), dtype=torch.uint8, device=d),
+                   rec=torch.empty((m_cap, dw), dtype=i32, device=d),
+                   dst=torch.empty(m_cap, dtype=i32, device=d),
+                   rows=torch.empty(m_cap, dtype=i32, device=d),
+                   row_counts=torch.empty((m_cap, D), dtype=i32, device=d),
+                   n_rows=torch.zeros(1, dtype=i32, device=d))
+        con._sparse_buf = buf
+    L, st = con.lib, con._stream()
+    h, t, r = dev[0].data_ptr(), dev[1].data_ptr(), dev[2].data_ptr()
+    h2, t2, r2 = (buf["sorted"][i].data_ptr() for i in range(3))
+    chunks, cand, pair = buf["chunks"].data_ptr(), buf["cand"].data_ptr(), buf["pair"].data_ptr()
+    _lib.check(L.kge_shared_order_by_relation(h, t, r, n_pos, P, buf["perm"].data_ptr(), h2, t2, r2, chunks, buf["n_chunks"].data_ptr(), st), L)
+    _lib.check(L.kge_shared_negatives_draw_grouped(h2, t2, r2, n_pos, chunks, cap, N, 1 if con.type_constrained_sampling else 0,
+                                                   con._shared_seed, con.global_step, cand, pair, st), L)
+    _lib.check(L.kge_transe_emit_records_shared_chunks(ctypes.byref(con._desc), con._tables[0].data_ptr(), con._tables[1].data_ptr(), h2, t2, r2,
+                                                       n_pos, stride, chunks, cap, cand, N, pair, denom, buf["rec"].data_ptr(),
+                                                       buf["dst"].data_ptr(), con._loss.data_ptr(), st), L)
+    buf["shared_step"], buf["shared_shape"], buf["shared_batch"] = con.global_step, (n_pos, cap), dev
+    con._rule.reduce_apply(con._desc, buf["rec"], buf["dst"], 3 * n_pos + cap * N, buf, denom,
+                           fused_ok=getattr(con, "sparse_fused", True) and D % 4 == 0)
+    con._rule.advance()
+    con.global_step += 1
+
+
 def shared_chunk_span(first_position, n_pos, P):
     """(c0, n_chunks): the global chunks of P positions that the batch positions [first_position, first_position + n_pos) meet --
     c0 = first_position // P through (first_position + n_pos - 1) // P; the first and the last may be partial; no position, no
