@@ -16,7 +16,7 @@ import os
 
 import numpy as np
 
-from . import _lib, shard_eval, step_plan, train_paths
+from . import _lib, rank_eval, shard_eval, step_plan, train_paths
 from ._lib import KgeError
 
 
@@ -1423,6 +1423,7 @@ class Config(object):
         print("triple (%d,%d,%d) is %s" % (h, t, r, "correct" if ok else "wrong"))
         return ok
 
+    # evaluation by ranking: these methods document the calls and dispatch to rank_eval ---------------------------
     def top_k_tails(self, h, r, k, filtered=False, type_constrained=False):
         """The k best tails of (h, r, ?) for every query, ranked on the device (kge_topk_entities).  h and r are ints or 1-D
         arrays, broadcast against each other.  Returns (ids int64 [n, k], scores float32 [n, k]) in ascending (score, id)
@@ -1433,11 +1434,11 @@ class Config(object):
         its own queries (possibly none) and the same k, side and flags, and gets the results of its own queries, with the bits
         of one process over the whole table (kge_topk_entities_range, kge_topk_merge_keys).  Arguments invalid on any rank,
         or k / side / flags differing between ranks, raise KgeError on every rank."""
-        return self._top_k_entities(h, r, k, False, filtered, type_constrained)
+        return rank_eval.top_k_entities(self, h, r, k, False, filtered, type_constrained)
 
     def top_k_heads(self, t, r, k, filtered=False, type_constrained=False):
         """The k best heads of (?, r, t) for every query; as top_k_tails."""
-        return self._top_k_entities(t, r, k, True, filtered, type_constrained)
+        return rank_eval.top_k_entities(self, t, r, k, True, filtered, type_constrained)
 
     def top_k_relations(self, h, t, k, filtered=False, type_constrained=False):
         """The k best relations of (h, ?, t) for every query, scored and selected on the device (kge_topk_relations).  h and t
@@ -1446,134 +1447,13 @@ class Config(object):
         tensors in give device tensors out.  Scores are kge_predict's, TransR with each relation's own matrix.  filtered drops
         relations forming a known triple (train + valid + test), type_constrained keeps relations whose head / tail type lists
         hold h / t -- both need init_link_prediction()."""
-        if self._sharded("ent_embeddings"):
-            raise KgeError("top-k relation prediction over an entity table sharded across ranks is not supported")
-        h, t, n, on_device = self._topk_queries(h, t, k, self.entTotal, self.entTotal)
-        return self._topk_call(self.lib.kge_topk_relations, (h.data_ptr(), t.data_ptr()), n, k, filtered, type_constrained, on_device)
-
-    def _top_k_entities(self, fixed, rel, k, head, filtered, type_constrained):
-        import torch
-        if self._sharded("ent_embeddings"):
-            return shard_eval.top_k_entities(self, fixed, rel, k, head, filtered, type_constrained)
-        f, r, n, on_device = self._topk_queries(fixed, rel, k, self.entTotal, self.relTotal)
-        side = torch.full((n,), 1 if head else 0, dtype=torch.int32, device=self.device)
-        return self._topk_call(self.lib.kge_topk_entities, (f.data_ptr(), r.data_ptr(), side.data_ptr()), n, k, filtered,
-                               type_constrained, on_device)
-
-    def _topk_queries(self, a, b, k, a_total, b_total):
-        """Argument handling of the top-k methods: the k check, the two id arrays broadcast against each other and checked
-        against [0, a_total) / [0, b_total) before any launch.  -> (a, b as int32 device tensors, n, on_device)."""
-        import torch
-        k = int(k)
-        if not 1 <= k <= _lib.TOPK_MAX_K:
-            raise KgeError("top-k prediction: k must be in [1, %d], got %d" % (_lib.TOPK_MAX_K, k))
-        on_device = any(isinstance(x, torch.Tensor) and x.device.type != "cpu" for x in (a, b))
-        if on_device:
-            a, b = (x if isinstance(x, torch.Tensor) else torch.as_tensor(np.asarray(x)) for x in (a, b))
-            a, b = torch.broadcast_tensors(a.to(self.device).reshape(-1), b.to(self.device).reshape(-1))
-            a = a.to(torch.int32).contiguous()
-            b = b.to(torch.int32).contiguous()
-            n = a.shape[0]
-            if n:   # the ids index device tables directly: checked before any launch (four numbers come back)
-                lim = torch.stack([a.min(), a.max(), b.min(), b.max()]).cpu().tolist()
-                if lim[0] < 0 or lim[1] >= a_total or lim[2] < 0 or lim[3] >= b_total:
-                    raise KgeError("entity / relation id out of range in the top-k queries")
-        else:
-            ah, bh = np.broadcast_arrays(np.asarray(a).reshape(-1), np.asarray(b).reshape(-1))
-            n = ah.shape[0]
-            if n and (ah.min() < 0 or ah.max() >= a_total or bh.min() < 0 or bh.max() >= b_total):
-                raise KgeError("entity / relation id out of range in the top-k queries")
-            a = torch.from_numpy(np.ascontiguousarray(ah, dtype=np.int32)).to(self.device)
-            b = torch.from_numpy(np.ascontiguousarray(bh, dtype=np.int32)).to(self.device)
-        return a, b, n, on_device
-
-    def _topk_call(self, fn, query_ptrs, n, k, filtered, type_constrained, on_device):
-        import torch
-        k = int(k)
-        ids = torch.empty((n, k), dtype=torch.int32, device=self.device)
-        scores = torch.empty((n, k), dtype=torch.float32, device=self.device)
-        _lib.check(fn(ctypes.byref(self._desc), self._tab_ptrs, *query_ptrs, n, k, self._topk_flags(filtered, type_constrained),
-                      ids.data_ptr(), scores.data_ptr(), self._stream()), self.lib)
-        return self._topk_result(ids, scores, on_device)
-
-    @staticmethod
-    def _topk_flags(filtered, type_constrained):
-        return (_lib.TOPK_FILTERED if filtered else 0) | (_lib.TOPK_TYPED if type_constrained else 0)
-
-    @staticmethod
-    def _topk_result(ids, scores, on_device):
-        if on_device:
-            return ids.long(), scores
-        return ids.cpu().numpy().astype(np.int64), scores.cpu().numpy()
-
-    @staticmethod
-    def _rank_sums(d, prefix, suffix, raw, filt):
-        """Adds the un-normalised accumulators of one side's raw and filtered counts to `d`: Hits@10 / 3 / 1, MR and MRR under
-        the reference's names (main_spark.py:430-448), `prefix` r (tail side) or l (head side), `suffix` "" or "_constrain"."""
-        for name, cnt in (("", raw), ("_filter", filt)):
-            d[prefix + name + "_tot" + suffix] = float((cnt < 10).sum())                    # Hits@10
-            d[prefix + "3" + name + "_tot" + suffix] = float((cnt < 3).sum())               # Hits@3
-            d[prefix + "1" + name + "_tot" + suffix] = float((cnt < 1).sum())               # Hits@1
-            d[prefix + name + "_rank" + suffix] = float((1 + cnt).sum())                    # MR
-            d[prefix + name + "_reci_rank" + suffix] = float((1.0 / (1 + cnt)).sum())       # MRR
-
-    @staticmethod
-    def _lp_sums(out, test_head=True):
-        """Un-normalised accumulators of main_spark.py:430-448 over the rows of `out` (they add across test-set slices)."""
-        d = {}
-        for side, p in ((0, "r"), (1, "l")):
-            if side == 1 and not test_head:
-                continue
-            raw, filt, raw_c, filt_c = (out[:, side, i] for i in range(4))
-            Config._rank_sums(d, p, "", raw, filt)
-            Config._rank_sums(d, p, "_constrain", raw_c, filt_c)
-        return d
-
-    @staticmethod
-    def _cand_sums(counts, sides=(0, 1)):
-        """The same accumulators over candidate-list counts [n, 2, 2] (raw, filtered) for the ranked sides; no _constrain names."""
-        d = {}
-        for side, p in ((0, "r"), (1, "l")):
-            if side in sides:
-                Config._rank_sums(d, p, "", counts[:, side, 0], counts[:, side, 1])
-        return d
-
-    @staticmethod
-    def _lp_normalise(sums, count):
-        n = float(max(count, 1))
-        return {k: v / n for k, v in sums.items()}
+        return rank_eval.top_k_relations(self, h, t, k, filtered, type_constrained)
 
     def link_prediction_distributed(self, test_head=True):
         """The whole test set, split into one contiguous range per rank (the static split of
         distribute_training.py:430-441) and reduced like main_spark.py:430-448: every rank returns the global metrics.
         On a sharded entity table the candidates are split instead: link_prediction over the whole test set, a collective."""
-        total = self.lib.getTestTotal()
-        if self._sharded("ent_embeddings"):
-            return self.link_prediction(0, total, test_head)[1]
-        lo, hi = self._test_slice(total)
-        out = np.zeros((hi - lo, 2, 8), dtype=np.int64)
-        if hi > lo:
-            _lib.check(self.lib.kge_link_prediction(ctypes.byref(self._desc), self._tab_ptrs, lo, hi - lo,
-                                                    1 if test_head else 0, out.ctypes.data, self._stream()), self.lib)
-        return self._lp_normalise(self._all_reduce_sums(self._lp_sums(out, test_head)), total)
-
-    def _test_slice(self, total):
-        """This rank's contiguous range [lo, hi) of `total` test triples (the static split of distribute_training.py:430-441)."""
-        per = (total + self.world_size - 1) // self.world_size
-        lo = min(self.rank * per, total)
-        return lo, min(lo + per, total)
-
-    def _all_reduce_sums(self, sums):
-        """The accumulators of every rank added up (main_spark.py:430-448's reduction)."""
-        import torch
-        import torch.distributed as dist
-        keys = sorted(sums)
-        vec = torch.tensor([sums[k] for k in keys], dtype=torch.float64)
-        if self.world_size > 1:
-            if dist.get_backend(self._pg) == "nccl":
-                vec = vec.to(self.device)
-            shard_eval.all_reduce(self, vec, dist.ReduceOp.SUM)
-        return dict(zip(keys, vec.cpu().tolist()))
+        return rank_eval.link_prediction_distributed(self, test_head)
 
     def link_prediction(self, first=0, count=None, test_head=True):
         """Rank every test triple in [first, first+count) on the device (replaces the per-triple loop of
@@ -1584,28 +1464,7 @@ class Config(object):
         result): each rank ranks the triples against its own rows (kge_link_prediction_range) and the counts and arg-mins are merged
         across ranks.  Its scores may place a near-tie (a candidate within an ulp or so of the true triple) on the other side of
         the true triple than kge_link_prediction does."""
-        if count is None:
-            count = self.lib.getTestTotal() - first
-        if self._sharded("ent_embeddings"):
-            out = shard_eval.link_prediction(self, first, count, test_head)
-        else:
-            out = np.zeros((count, 2, 8), dtype=np.int64)
-            _lib.check(self.lib.kge_link_prediction(ctypes.byref(self._desc), self._tab_ptrs, first, count,
-                                                    1 if test_head else 0, out.ctypes.data, self._stream()), self.lib)
-        return out, self._lp_normalise(self._lp_sums(out, test_head), count)
-
-    def _rank_device(self, dev, test_head, into=None):
-        """kge_rank_triples on an int32 device tensor [3, n] (h, t, r; ids already checked) -> int64 numpy [n, 2, 4]; with
-        `into` (a contiguous int64 device tensor [n, 2, 4]) the counts are left there and nothing is copied back."""
-        import torch
-        n = dev.shape[1]
-        counts = into if into is not None else torch.empty((n, 2, 4), dtype=torch.int64, device=self.device)
-        # (an empty tensor has no address and the entry point refuses null pointers: n == 0 still checks the files, on a spare row)
-        ids, out = (dev, counts) if n else (torch.zeros((3, 1), dtype=torch.int32, device=self.device),
-                                            torch.zeros((1, 2, 4), dtype=torch.int64, device=self.device))
-        _lib.check(self.lib.kge_rank_triples(ctypes.byref(self._desc), self._tab_ptrs, ids[0].data_ptr(), ids[1].data_ptr(),
-                                             ids[2].data_ptr(), n, 1 if test_head else 0, out.data_ptr(), self._stream()), self.lib)
-        return counts.cpu().numpy() if into is None else None
+        return rank_eval.link_prediction(self, first, count, test_head)
 
     def _refuse_sharded_rank(self, what):
         if self._sharded("ent_embeddings"):
@@ -1621,12 +1480,7 @@ class Config(object):
         the true triple -- raw, filtered (train + valid + test), typed, filtered + typed -- exactly columns 0..3 of
         link_prediction's rows, from the same score bits.  metrics has link_prediction's names, normalised by n.  Needs
         init_link_prediction().  An id out of range raises KgeError before anything is launched."""
-        import torch
-        self._refuse_sharded_rank("rank_triples")
-        host = np.stack([np.asarray(h).reshape(-1), np.asarray(t).reshape(-1), np.asarray(r).reshape(-1)]).astype(np.int32)
-        self._check_ids(host)
-        counts = self._rank_device(torch.from_numpy(host).to(self.device), test_head)
-        return counts, self._lp_normalise(self._lp_sums(counts, test_head), host.shape[1])
+        return rank_eval.rank_triples(self, h, t, r, test_head)
 
     def rank_triples_distributed(self, h, t, r, test_head=True):
         """rank_triples as a collective: every rank passes the same triples and gets the same (counts int64 [n, 2, 4],
@@ -1641,18 +1495,9 @@ class Config(object):
         On replicated tables (all four models) rank g ranks the g-th contiguous slice of the triples with kge_rank_triples and
         one SUM all-reduce merges the slices: exactly rank_triples's counts.  With one process and no process group it is
         rank_triples."""
-        import torch
         if not self._sharded("ent_embeddings") and self.world_size <= 1:
             return self.rank_triples(h, t, r, test_head)
-        err, dev = None, None
-        try:
-            host = np.stack([np.asarray(h).reshape(-1), np.asarray(t).reshape(-1), np.asarray(r).reshape(-1)]).astype(np.int32)
-            self._check_ids(host)
-            dev = torch.from_numpy(np.ascontiguousarray(host)).to(self.device)
-        except (KgeError, ValueError, TypeError, OverflowError) as e:
-            err = e
-        counts = shard_eval.rank_triples(self, dev, err, test_head)
-        return counts, self._lp_normalise(self._lp_sums(counts, test_head), counts.shape[0])
+        return rank_eval.rank_ids_distributed(self, lambda: rank_eval.triple_ids(self, h, t, r), test_head)
 
     # candidate lists instead of every entity (kge_rank_candidates) ------------------------------------------------------------
     def _refuse_sharded_candidates(self, what):
@@ -1660,43 +1505,6 @@ class Config(object):
             raise KgeError("%s over an entity table sharded across ranks is not supported: call one of the collectives "
                            "rank_candidates_distributed, rank_triples_sampled_distributed or "
                            "validation_link_prediction_distributed(candidates=C) on every rank" % what)
-
-    def _candidate_list(self, cand, n, name):
-        """A candidate array ([n, C] or [C]; numpy / list / torch tensor on any device) -> (int32 device tensor, C, stride)."""
-        import torch
-        if torch.is_tensor(cand):
-            if cand.dtype not in (torch.int32, torch.int64, torch.int16, torch.int8, torch.uint8):
-                raise KgeError("%s must hold integer ids, got %s" % (name, cand.dtype))
-            dev = cand.to(device=self.device, dtype=torch.int32).contiguous()       # a device tensor stays on the device
-        else:
-            host = np.asarray(cand)
-            if host.dtype.kind not in "iu" and host.size:
-                raise KgeError("%s must hold integer ids, got %s" % (name, host.dtype))
-            if host.size and (host.min() < -2 ** 31 or host.max() >= 2 ** 31):
-                raise KgeError("%s: an id does not fit 32 bits" % name)
-            dev = torch.from_numpy(np.ascontiguousarray(host, dtype=np.int32)).to(self.device)
-        if dev.dim() == 1:
-            return dev, int(dev.shape[0]), 0
-        if dev.dim() == 2 and dev.shape[0] == n:
-            return dev, int(dev.shape[1]), int(dev.shape[1])
-        raise KgeError("%s must be [n, C] = [%d, C] or a shared list [C], got %s" % (name, n, list(dev.shape)))
-
-    def _rank_candidates_device(self, dev, tail, head, n_cand, flags, seed, first=0, into=None):
-        """kge_rank_candidates on an int32 device tensor [3, n] (ids already checked); tail / head = (tensor, stride) or None.
-        `first` is the global index of the first triple, for drawn lists (the hash is indexed by it: adding first * 2^33 times the
-        hash's multiplier to the seed moves the counter there).  -> int64 numpy [n, 2, 2], or None with `into` (a device tensor)."""
-        import torch
-        n = dev.shape[1]
-        counts = into if into is not None else torch.empty((n, 2, 2), dtype=torch.int64, device=self.device)
-        spare = torch.zeros((3, 4), dtype=torch.int32, device=self.device)        # an empty tensor has no address
-        ptr = lambda x: x.data_ptr() if x.numel() else spare.data_ptr()
-        ids = dev if n else spare
-        lists = [(None, 0) if side is None else (ptr(side[0]), side[1]) for side in (tail, head)]
-        seed = (int(seed) + ((int(first) << 33) * 0x9E3779B97F4A7C15)) & 0xFFFFFFFFFFFFFFFF
-        _lib.check(self.lib.kge_rank_candidates(ctypes.byref(self._desc), self._tab_ptrs, ids[0].data_ptr(), ids[1].data_ptr(), ids[2].data_ptr(),
-                                                n, lists[0][0], lists[0][1], lists[1][0], lists[1][1], n_cand, flags, seed,
-                                                counts.data_ptr() if n else spare.data_ptr(), self._stream()), self.lib)
-        return counts.cpu().numpy() if into is None else None
 
     def rank_candidates(self, h, t, r, tail_candidates=None, head_candidates=None, filtered=True):
         """Rank triples against candidate lists of the caller's instead of every entity (kge_rank_candidates): h, t, r are 1-D id
@@ -1709,22 +1517,7 @@ class Config(object):
         needs init_link_prediction() -- with filtered=False it is not computed, equals column 0 and nothing is needed).  metrics
         has link_prediction's raw and _filter names for the ranked sides, normalised by n.  The scores are test_step's bits.
         An id of a TRIPLE out of range raises KgeError before anything is launched."""
-        import torch
-        self._refuse_sharded_candidates("rank_candidates")
-        host = np.stack([np.asarray(h).reshape(-1), np.asarray(t).reshape(-1), np.asarray(r).reshape(-1)]).astype(np.int32)
-        self._check_ids(host)
-        n = host.shape[1]
-        if tail_candidates is None and head_candidates is None:
-            raise KgeError("rank_candidates: give tail_candidates, head_candidates or both")
-        tail = None if tail_candidates is None else self._candidate_list(tail_candidates, n, "tail_candidates")
-        head = None if head_candidates is None else self._candidate_list(head_candidates, n, "head_candidates")
-        if tail is not None and head is not None and tail[1] != head[1]:
-            raise KgeError("rank_candidates: both lists must have the same number of candidates, got %d and %d" % (tail[1], head[1]))
-        n_cand = (tail or head)[1]
-        counts = self._rank_candidates_device(torch.from_numpy(host).to(self.device), tail and (tail[0], tail[2]), head and (head[0], head[2]),
-                                              n_cand, _lib.RANKC_FILTERED if filtered else 0, 0)
-        sides = [s for s, x in ((0, tail), (1, head)) if x is not None]
-        return counts, self._lp_normalise(self._cand_sums(counts, sides), n)
+        return rank_eval.rank_candidates(self, h, t, r, tail_candidates, head_candidates, filtered)
 
     def rank_candidates_distributed(self, h, t, r, tail_candidates=None, head_candidates=None, filtered=True):
         """rank_candidates as a collective: every rank passes the same arguments and gets the same (counts int64 [n, 2, 2],
@@ -1734,58 +1527,9 @@ class Config(object):
         owners, and one SUM all-reduce merges the counts: bit for bit rank_candidates' counts over the whole table.
         On replicated tables rank g ranks the g-th contiguous slice of the triples and one SUM all-reduce merges the slices.
         With one process and no process group it is rank_candidates."""
-        import torch
-        import torch.distributed as dist
-        sharded = self._sharded("ent_embeddings")
-        if sharded and not dist.is_initialized():
-            raise KgeError("rank_candidates_distributed over an entity table sharded across ranks needs the process group it was sharded over")
-        if not sharded and self.world_size <= 1:
+        if not rank_eval.sharded_in_group(self, "rank_candidates_distributed") and self.world_size <= 1:
             return self.rank_candidates(h, t, r, tail_candidates, head_candidates, filtered)
-        what = "rank_candidates_distributed"
-        err, dev, tail, head, n, n_cand, sides = None, None, None, None, -1, 0, []
-        flags = _lib.RANKC_FILTERED if filtered else 0
-        try:
-            host = np.stack([np.asarray(h).reshape(-1), np.asarray(t).reshape(-1), np.asarray(r).reshape(-1)]).astype(np.int32)
-            self._check_ids(host)
-            n = host.shape[1]
-            if tail_candidates is None and head_candidates is None:
-                raise KgeError("%s: give tail_candidates, head_candidates or both" % what)
-            tail = None if tail_candidates is None else self._candidate_list(tail_candidates, n, "tail_candidates")
-            head = None if head_candidates is None else self._candidate_list(head_candidates, n, "head_candidates")
-            if tail is not None and head is not None and tail[1] != head[1]:
-                raise KgeError("%s: both lists must have the same number of candidates, got %d and %d" % (what, tail[1], head[1]))
-            n_cand = (tail or head)[1]
-            tail, head = tail and (tail[0], tail[2]), head and (head[0], head[2])
-            sides = [s for s, x in ((0, tail), (1, head)) if x is not None]
-            dev = torch.from_numpy(np.ascontiguousarray(host)).to(self.device)
-            if not sharded:
-                self._rank_candidates_device(dev[:, :0], tail, head, n_cand, flags, 0)       # the arguments and the files, no launch
-        except (KgeError, ValueError, TypeError, OverflowError) as e:
-            err, n = e, -1
-        if sharded:
-            counts = shard_eval.rank_candidates(self, dev, err, tail, head, n_cand, flags, 0, what)
-        else:
-            strides = [x[1] if x is not None else -1 for x in (tail, head)]
-            shard_eval.agree(self, what, err, (n, flags, n_cand if err is None else 0, strides[0], strides[1]), [1, 2, 3, 4, 5],
-                             "triples, candidate counts, lists or flags", 0, where="")
-            counts = torch.zeros((max(n, 1), 2, 2), dtype=torch.int64, device=self.device)
-            per = (n + self.world_size - 1) // self.world_size
-            c0, c1 = min(self.rank * per, n), min((self.rank + 1) * per, n)
-            if c1 > c0:      # a per-triple list starts at this slice's first triple; a shared list (stride 0) is whole
-                part = [x and ((x[0][c0:c1] if x[1] else x[0]), x[1]) for x in (tail, head)]
-                self._rank_candidates_device(dev[:, c0:c1].contiguous(), part[0], part[1], n_cand, flags, 0, into=counts[c0:c1])
-            shard_eval.all_reduce(self, counts, dist.ReduceOp.SUM)
-            counts = counts[:n].cpu().numpy()
-        return counts, self._lp_normalise(self._cand_sums(counts, sides), n)
-
-    @staticmethod
-    def _sampled_flags(test_head, type_constrained, filtered):
-        return (_lib.RANKC_DRAWN | (0 if test_head else _lib.RANKC_NO_HEAD) | (_lib.RANKC_TYPED if type_constrained else 0) |
-                (_lib.RANKC_FILTERED if filtered else 0))
-
-    def _check_sampled(self, what, n_candidates):
-        if int(n_candidates) < 0 or int(n_candidates) >= 2 ** 31:
-            raise KgeError("%s: n_candidates must be in [0, 2^31), got %d" % (what, n_candidates))
+        return rank_eval.rank_candidates_distributed(self, h, t, r, tail_candidates, head_candidates, filtered)
 
     def rank_triples_sampled(self, h, t, r, n_candidates, seed=0, test_head=True, type_constrained=False, filtered=True):
         """rank_candidates against n_candidates entities per (triple, side) that the device draws from a counter hash of (seed,
@@ -1793,14 +1537,7 @@ class Config(object):
         type_constrained=True they come from the relation's tail / head type list (a relation without one: from all entities;
         needs the type lists).  test_head=False ranks the tail side only.  Returns (counts int64 [n, 2, 2], metrics) as
         rank_candidates does; the same seed gives the same lists on every call."""
-        import torch
-        self._refuse_sharded_candidates("rank_triples_sampled")
-        self._check_sampled("rank_triples_sampled", n_candidates)
-        host = np.stack([np.asarray(h).reshape(-1), np.asarray(t).reshape(-1), np.asarray(r).reshape(-1)]).astype(np.int32)
-        self._check_ids(host)
-        counts = self._rank_candidates_device(torch.from_numpy(host).to(self.device), None, None, int(n_candidates),
-                                              self._sampled_flags(test_head, type_constrained, filtered), seed)
-        return counts, self._lp_normalise(self._cand_sums(counts, (0, 1) if test_head else (0,)), host.shape[1])
+        return rank_eval.rank_triples_sampled(self, h, t, r, n_candidates, seed, test_head, type_constrained, filtered)
 
     def rank_triples_sampled_distributed(self, h, t, r, n_candidates, seed=0, test_head=True, type_constrained=False, filtered=True):
         """rank_triples_sampled as a collective: every rank passes the same arguments.  On replicated tables rank g ranks the g-th
@@ -1809,62 +1546,11 @@ class Config(object):
         rank_candidates_distributed does.  The hash is indexed by the global triple index,
         so the counts are those of one process.  Invalid arguments on any rank, or arguments differing between ranks, raise
         KgeError on every rank.  With one process and no process group it is rank_triples_sampled."""
-        import torch.distributed as dist
-        sharded = self._sharded("ent_embeddings")
-        if sharded and not dist.is_initialized():      # no process group, so no other rank can be waiting for this one
-            raise KgeError("rank_triples_sampled_distributed over an entity table sharded across ranks needs the process group it was sharded over")
-        if sharded:
-            return self._rank_sampled_sharded("rank_triples_sampled_distributed", lambda: self._triple_ids(h, t, r), n_candidates, seed,
-                                              test_head, type_constrained, filtered)
-        if self.world_size <= 1:
+        what = "rank_triples_sampled_distributed"
+        if not rank_eval.sharded_in_group(self, what) and self.world_size <= 1:
             return self.rank_triples_sampled(h, t, r, n_candidates, seed, test_head, type_constrained, filtered)
-        return self._rank_sampled_replicated("rank_triples_sampled_distributed", lambda: self._triple_ids(h, t, r), n_candidates, seed,
-                                             test_head, type_constrained, filtered)
-
-    def _rank_sampled_replicated(self, what, triples, n_candidates, seed, test_head, type_constrained, filtered):
-        """Drawn candidate lists on replicated tables, more than one rank: slices of the triples, one SUM all-reduce.  `triples`
-        returns the checked int32 device tensor [3, n]."""
-        import torch
-        import torch.distributed as dist
-        err, dev, n, flags = None, None, -1, 0
-        try:
-            self._check_sampled(what, n_candidates)
-            dev = triples()
-            n, flags = int(dev.shape[1]), self._sampled_flags(test_head, type_constrained, filtered)
-            self._rank_candidates_device(dev[:, :0], None, None, int(n_candidates), flags, seed)       # the arguments and the files, no launch
-        except (KgeError, ValueError, TypeError, OverflowError, OSError) as e:
-            err, n = e, -1
-        shard_eval.agree(self, what, err, (n, flags, int(n_candidates) if err is None else 0, int(seed) & (2 ** 62 - 1) if err is None else 0),
-                         [1, 2, 3, 4], "triples, candidate counts, seeds or flags", 0, where="")
-        counts = torch.zeros((max(n, 1), 2, 2), dtype=torch.int64, device=self.device)
-        per = (n + self.world_size - 1) // self.world_size
-        c0, c1 = min(self.rank * per, n), min((self.rank + 1) * per, n)
-        if c1 > c0:
-            self._rank_candidates_device(dev[:, c0:c1].contiguous(), None, None, int(n_candidates), flags, seed, first=c0, into=counts[c0:c1])
-        shard_eval.all_reduce(self, counts, dist.ReduceOp.SUM)
-        counts = counts[:n].cpu().numpy()
-        return counts, self._lp_normalise(self._cand_sums(counts, (0, 1) if test_head else (0,)), n)
-
-    def _triple_ids(self, h, t, r):
-        """h, t, r as a checked int32 device tensor [3, n]."""
-        import torch
-        host = np.stack([np.asarray(h).reshape(-1), np.asarray(t).reshape(-1), np.asarray(r).reshape(-1)]).astype(np.int32)
-        self._check_ids(host)
-        return torch.from_numpy(np.ascontiguousarray(host)).to(self.device)
-
-    def _rank_sampled_sharded(self, what, triples, n_candidates, seed, test_head, type_constrained, filtered):
-        """Drawn candidate lists over a sharded entity table (shard_eval.rank_candidates): `triples` returns the checked int32
-        device tensor [3, n]; whatever it or the argument check raises on this rank is raised on every rank."""
-        err, dev, flags = None, None, 0
-        try:
-            self._check_sampled(what, n_candidates)
-            flags = self._sampled_flags(test_head, type_constrained, filtered)
-            seed = int(seed)
-            dev = triples()
-        except (KgeError, ValueError, TypeError, OverflowError, OSError) as e:
-            err = e
-        counts = shard_eval.rank_candidates(self, dev, err, None, None, n_candidates, flags, seed, what)
-        return counts, self._lp_normalise(self._cand_sums(counts, (0, 1) if test_head else (0,)), counts.shape[0])
+        triples = lambda: rank_eval.triple_ids(self, h, t, r)
+        return rank_eval.rank_sampled_distributed(self, what, triples, n_candidates, seed, test_head, type_constrained, filtered)
 
     def sampled_candidates(self, n, n_candidates, seed, side, r=None, type_constrained=False):
         """The ids rank_triples_sampled draws for `side` (0: tail lists, 1: head lists) of triples 0 .. n-1, restated in numpy:
@@ -1888,16 +1574,6 @@ class Config(object):
             ids = np.where(length > 0, lst[np.minimum(lo + typed, max(len(lst) - 1, 0))] if len(lst) else ids, ids)
         return ids
 
-    def _valid_positives(self):
-        """The triples of valid2id.txt in file order, int32 [3, V] (h, t, r), read once."""
-        if getattr(self, "_valid_pos", None) is None:
-            path = self.in_path if self.in_path.endswith("/") else self.in_path + "/"
-            with open(path + "valid2id.txt") as f:
-                tok = f.read().split()
-            total = int(tok[0]) if tok else 0
-            self._valid_pos = np.asarray(tok[1:1 + 3 * total], dtype=np.int64).reshape(total, 3).T.astype(np.int32)   # on disk: head, tail, relation
-        return self._valid_pos
-
     def validation_link_prediction(self, test_head=True, sample=0, candidates=0, seed=0, type_constrained=False):
         """rank_triples on the positives of valid2id.txt (read from in_path in file order; getValidBatch is not used, so the
         libc rand() sequence does not move): (counts, metrics) as rank_triples returns them -- filtered Hits@10 and MRR on the
@@ -1906,37 +1582,7 @@ class Config(object):
         candidates = C > 0 ranks the chosen triples against C drawn candidates per side instead of every entity
         (rank_triples_sampled with `seed`, from the type lists with type_constrained=True): (counts int64 [n, 2, 2], metrics) as
         rank_triples_sampled returns them, V x C pairs per side."""
-        if int(candidates) < 0:
-            raise KgeError("validation_link_prediction: candidates must be >= 0, got %d" % candidates)
-        if int(candidates) > 0:
-            self._refuse_sharded_candidates("validation_link_prediction(candidates=%d)" % candidates)
-            self._check_sampled("validation_link_prediction", candidates)
-            dev = self._valid_rank_ids(sample, "validation_link_prediction")
-            counts = self._rank_candidates_device(dev, None, None, int(candidates), self._sampled_flags(test_head, type_constrained, True), seed)
-            return counts, self._lp_normalise(self._cand_sums(counts, (0, 1) if test_head else (0,)), counts.shape[0])
-        self._refuse_sharded_rank("validation_link_prediction")
-        counts = self._rank_device(self._valid_rank_ids(sample, "validation_link_prediction"), test_head)
-        return counts, self._lp_normalise(self._lp_sums(counts, test_head), counts.shape[0])
-
-    def _valid_rank_ids(self, sample, what):
-        """The validation positives a check ranks, as an int32 device tensor [3, n] (h, t, r; ids checked): all V of
-        valid2id.txt, or with 0 < sample < V those at the indices floor(i V / sample).  Kept between calls."""
-        import torch
-        valid = self._valid_positives()
-        total = valid.shape[1]
-        sample = int(sample)
-        if sample < 0:
-            raise KgeError("%s: sample must be >= 0, got %d" % (what, sample))
-        if 0 < sample < total:
-            valid = valid[:, (np.arange(sample, dtype=np.int64) * total) // sample]
-        else:
-            sample = 0
-        cached = getattr(self, "_valid_rank_dev", None)
-        if cached is None or cached[0] != sample:
-            host = np.ascontiguousarray(valid)
-            self._check_ids(host)
-            cached = self._valid_rank_dev = (sample, torch.from_numpy(host).to(self.device))
-        return cached[1]
+        return rank_eval.validation_link_prediction(self, test_head, sample, candidates, seed, type_constrained)
 
     def validation_link_prediction_distributed(self, test_head=True, sample=0, candidates=0, seed=0, type_constrained=False):
         """validation_link_prediction as a collective, ranked as rank_triples_distributed ranks (sharded or replicated
@@ -1946,49 +1592,9 @@ class Config(object):
         candidates = C > 0 ranks against C drawn candidates per side as validation_link_prediction(candidates=C) does, with
         rank_triples_sampled_distributed's split (sharded: every rank counts the candidates it owns; replicated: slices of the
         triples): (counts int64 [n, 2, 2], metrics), exactly one process's counts.  A bad value on any rank raises on every rank."""
-        sharded = self._sharded("ent_embeddings")
-        if not sharded and self.world_size <= 1:
+        if not self._sharded("ent_embeddings") and self.world_size <= 1:
             return self.validation_link_prediction(test_head, sample, candidates, seed, type_constrained)
-        cand = None
-        try:
-            cand = int(candidates)
-        except (ValueError, TypeError, OverflowError):
-            pass
-        if cand is None or cand != 0:
-            what = "validation_link_prediction_distributed"
-
-            def triples():
-                if cand is None or cand < 0:
-                    raise KgeError("%s: candidates must be an integer >= 0, got %r" % (what, candidates))
-                return self._valid_rank_ids(sample, what)
-            if sharded:
-                import torch.distributed as dist
-                if not dist.is_initialized():
-                    raise KgeError("%s over an entity table sharded across ranks needs the process group it was sharded over" % what)
-                return self._rank_sampled_sharded(what, triples, cand if cand is not None and cand > 0 else 0, seed, test_head, type_constrained, True)
-            return self._rank_sampled_replicated(what, triples, cand if cand is not None and cand > 0 else 0, seed, test_head, type_constrained, True)
-        err, dev = None, None
-        try:
-            dev = self._valid_rank_ids(sample, "validation_link_prediction_distributed")
-        except (KgeError, ValueError, TypeError, OverflowError, OSError) as e:
-            err = e
-        counts = shard_eval.rank_triples(self, dev, err, test_head)
-        return counts, self._lp_normalise(self._lp_sums(counts, test_head), counts.shape[0])
-
-    @staticmethod
-    def _rel_sums(out):
-        """Un-normalised relation-prediction accumulators over the rows of `out` [count, 4] (raw, filtered, typed, filtered +
-        typed counts), named as _lp_sums names them with the prefix "rel" (they add across test-set slices)."""
-        d = {}
-        for suffix, cols in (("", (0, 1)), ("_constrain", (2, 3))):
-            for name, col in (("", cols[0]), ("_filter", cols[1])):
-                cnt = out[:, col]
-                d["rel" + name + "_tot" + suffix] = float((cnt < 10).sum())                # Hits@10
-                d["rel3" + name + "_tot" + suffix] = float((cnt < 3).sum())                # Hits@3
-                d["rel1" + name + "_tot" + suffix] = float((cnt < 1).sum())                # Hits@1
-                d["rel" + name + "_rank" + suffix] = float((1 + cnt).sum())                # MR
-                d["rel" + name + "_reci_rank" + suffix] = float((1.0 / (1 + cnt)).sum())   # MRR
-        return d
+        return rank_eval.validation_link_prediction_distributed(self, test_head, sample, candidates, seed, type_constrained)
 
     def relation_prediction(self, first=0, count=None):
         """Rank the true relation of every test triple in [first, first+count) (kge_link_prediction's order) among all
@@ -1999,31 +1605,13 @@ class Config(object):
         same result, bit for bit that of one process over the whole table.  Each rank ranks one contiguous slice of the
         triples from h / t rows fetched from their owners (kge_relation_prediction_rows) and the counts are summed across
         ranks.  Arguments invalid on any rank, or first / count differing between ranks, raise KgeError on every rank."""
-        if count is None:
-            count = self.lib.getTestTotal() - first
-        if self._sharded("ent_embeddings"):
-            out = shard_eval.relation_prediction(self, first, count)
-        else:
-            out = np.zeros((count, 4), dtype=np.int64)
-            self._relation_counts(first, count, out)
-        return out, self._lp_normalise(self._rel_sums(out), count)
+        return rank_eval.relation_prediction(self, first, count)
 
     def relation_prediction_distributed(self):
         """relation_prediction over the whole test set split into one contiguous range per rank and all-reduced, as
         link_prediction_distributed does: every rank returns the global metrics.
         On a sharded entity table it is relation_prediction over the whole test set, a collective."""
-        total = self.lib.getTestTotal()
-        if self._sharded("ent_embeddings"):
-            return self.relation_prediction(0, total)[1]
-        lo, hi = self._test_slice(total)
-        out = np.zeros((hi - lo, 4), dtype=np.int64)
-        if hi > lo:
-            self._relation_counts(lo, hi - lo, out)
-        return self._lp_normalise(self._all_reduce_sums(self._rel_sums(out)), total)
-
-    def _relation_counts(self, first, count, out):
-        _lib.check(self.lib.kge_relation_prediction(ctypes.byref(self._desc), self._tab_ptrs, first, count, out.ctypes.data,
-                                                    self._stream()), self.lib)
+        return rank_eval.relation_prediction_distributed(self)
 
     # ------------------------------------------------------------------------------------------
     # parameters by the reference's variable names (Config.py:378-421)

@@ -32,6 +32,12 @@ def drawn_candidate_index(seed, triple, side, k, length):
         return (((z >> u(32)) * np.asarray(length, dtype=u)) >> u(32)).astype(np.int64)
 
 
+def drawn_seed_at(seed, first):
+    """The seed with which triple i of a call draws what `seed` draws for triple first + i: the seed enters the hash additively
+    and the counter holds the triple from bit 33 up, so first * 2^33 times the hash's multiplier moves it there (mod 2^64)."""
+    return (int(seed) + ((int(first) << 33) * 0x9E3779B97F4A7C15)) & 0xFFFFFFFFFFFFFFFF
+
+
 class KgeError(RuntimeError):
     pass
 

@@ -1,8 +1,8 @@
 """Evaluation over an entity table sharded across ranks (`con._shard`).  Every function here is a collective: each rank calls it
 the same number of times, and the order in which it enters torch.distributed collectives (fetch_rows, all_reduce, agree and the
 `parallel` calls written out in it) is its contract with the other ranks.  top_k_entities, relation_prediction, rank_triples and
-rank_candidates open with agree; test_step and link_prediction have no header step.  rank_triples also serves replicated tables.  Functions take the Config first; its public methods dispatch here.
-"""
+rank_candidates open with agree; test_step and link_prediction have no header step.  Functions take the Config first; its
+public methods dispatch here, for ranking by way of rank_eval, which prepares the arguments; nothing here calls back into either."""
 import ctypes
 
 import numpy as np
@@ -54,6 +54,15 @@ def all_reduce(con, t, op):
         h = t.cpu()
         dist.all_reduce(h, op=op, group=con._pg)
         t.copy_(h)
+
+
+def checked(check):
+    """This rank's own argument check, run before agree: -> (check(), None), or (None, what a bad argument or a missing file
+    raised) for agree to raise as KgeError on every rank.  An exception that escaped here would leave the other ranks waiting."""
+    try:
+        return check(), None
+    except (KgeError, ValueError, TypeError, OverflowError, OSError, RuntimeError, AttributeError) as e:
+        return None, e
 
 
 def agree(con, what, err, fields, same, differ, per, where=" on a sharded entity table"):
@@ -119,25 +128,21 @@ def link_prediction(con, first, count, test_head):
     return out
 
 
-def top_k_entities(con, fixed, rel, k, head, filtered, type_constrained):
-    """Config.top_k_tails / top_k_heads on a sharded entity table.  The ranks first agree on a header (query count, k, side,
-    flags, validity).  Then all ranks' queries are taken in chunks: their fixed rows are fetched from the owners, each query's
-    k best among this rank's rows [lo, hi) are selected as packed keys (kge_topk_entities_range), each requester is sent the key
-    lists of its own queries only, and the W lists received for each of this rank's queries are merged (kge_topk_merge_keys)."""
+def top_k_entities(con, f, r, n, k, err, head, flags):
+    """Config.top_k_tails / top_k_heads on a sharded entity table.  f / r are this rank's n queries (fixed entity, relation) as
+    checked int32 device tensors, `err` what their check raised (or None; k is then in range).  -> device (ids int32 [n, k],
+    scores float32 [n, k]).  The ranks first agree on a header (query count, k, side, flags, validity).  Then all ranks' queries
+    are taken in chunks: their fixed rows are fetched from the owners, each query's k best among this rank's rows [lo, hi) are
+    selected as packed keys (kge_topk_entities_range), each requester is sent the key lists of its own queries only, and the W
+    lists received for each of this rank's queries are merged (kge_topk_merge_keys)."""
     import torch
     L, st, W, D, dev, pg = con.lib, con._stream(), con.world_size, con.hidden_size, con.device, con._pg
     lo, hi = con._shard["lo"], con._shard["hi"]
-    flags = con._topk_flags(filtered, type_constrained)
-    err, f, r, n, on_device = None, None, None, 0, False
-    try:
-        f, r, n, on_device = con._topk_queries(fixed, rel, k, con.entTotal, con.relTotal)
+    if err is None:      # the arguments, and the evaluation files the flags need, checked without a launch (no queries)
         k = int(k)
-        # the arguments, and the evaluation files the flags need, checked without a launch (no queries)
-        _lib.check(L.kge_topk_entities_range(ctypes.byref(con._desc), con._tab_ptrs, lo, hi - lo, None, None, None, None, 0, k,
-                                             flags, None, st), L)
-    except (KgeError, ValueError, TypeError, RuntimeError) as e:
-        err, n = e, 0
-    kk = k if err is None else -1
+        err = checked(lambda: _lib.check(L.kge_topk_entities_range(ctypes.byref(con._desc), con._tab_ptrs, lo, hi - lo, None, None,
+                                                                   None, None, 0, k, flags, None, st), L))[1]
+    n, kk = (n, k) if err is None else (0, -1)
     per = max(1, int(con.topk_shard_query_bytes) // (4 * D + 8 * max(kk, 1)))
     allh, per = agree(con, "top-k prediction", err, (n, kk, 1 if head else 0, flags), [2, 3, 4], "k, side or flags", per)
     ns = allh[:, 1]
@@ -175,7 +180,7 @@ def top_k_entities(con, fixed, rel, k, head, filtered, type_constrained):
             if mine:      # [W][mine][k]: one key list per source rank
                 o0 = max(c0, off[me]) - off[me]
                 _lib.check(L.kge_topk_merge_keys(got.data_ptr(), mine, W, k, ids[o0].data_ptr(), scores[o0].data_ptr(), st), L)
-    return con._topk_result(ids, scores, on_device)
+    return ids, scores
 
 
 def relation_prediction(con, first, count):
@@ -189,15 +194,16 @@ def relation_prediction(con, first, count):
     L, st, W, D, dev = con.lib, con._stream(), con.world_size, con.hidden_size, con.device
     if not dist.is_initialized():      # no process group, so no other rank can be waiting for this one
         raise KgeError("relation prediction on a sharded entity table needs the process group it was sharded over")
-    err = None
-    try:
-        first, count = int(first), int(count)
-        if first < 0 or count < 0:
-            raise KgeError("relation prediction: bad range (first %d, count %d)" % (first, count))
+
+    def check():
+        f, c = int(first), int(count)
+        if f < 0 or c < 0:
+            raise KgeError("relation prediction: bad range (first %d, count %d)" % (f, c))
         # the arguments and the evaluation files, checked without a launch: the range's end, then no triples
-        _lib.check(L.kge_relation_prediction_rows(ctypes.byref(con._desc), con._tab_ptrs, None, first + count, 0, None, st), L)
-    except (KgeError, ValueError, TypeError, OverflowError) as e:
-        err, first, count = e, -1, -1
+        _lib.check(L.kge_relation_prediction_rows(ctypes.byref(con._desc), con._tab_ptrs, None, f + c, 0, None, st), L)
+        return f, c
+    span, err = checked(check)
+    first, count = span if err is None else (-1, -1)
     per = max(1, int(con.lp_shard_query_bytes) // (2 * D * 4))
     _, per = agree(con, "relation prediction", err, (first, count), [1, 2], "first or count", per)
     cs = par.chunk_size(count, W)
@@ -219,101 +225,82 @@ def relation_prediction(con, first, count):
 
 
 def rank_triples(con, ids, err, test_head):
-    """Config.rank_triples_distributed.  `ids` is the int32 device tensor [3, n] (h, t, r; ids already checked) or None, `err`
-    what this rank's own argument check raised (or None).  The ranks first agree on a header (validity, n, test_head, triples
-    per round); the evaluation files are checked before it, without a launch.  -> int64 numpy [n, 2, 4].
-    Sharded entity table: in rounds of `per` triples the 2 per h and t rows come from their owners (query_rows, laid out
+    """Config.rank_triples_distributed / validation_link_prediction_distributed on a sharded entity table.  `ids` is the int32
+    device tensor [3, n] (h, t, r; ids already checked) or None, `err` what this rank's own argument check raised (or None).
+    The ranks first agree on a header (validity, n, test_head, triples per round); the evaluation files are checked before it,
+    without a launch.  In rounds of `per` triples the 2 per h and t rows come from their owners (query_rows, laid out
     [per][2][D]) and kge_rank_triples_range ranks the round against this rank's rows [lo, hi) into its slice of one
-    [n, 2, 4] device tensor; ONE SUM all-reduce of that tensor follows the last round.
-    Replicated tables (any model): rank g ranks the g-th contiguous slice of the triples with kge_rank_triples into a zeroed
-    [n, 2, 4]; one SUM all-reduce merges the slices."""
+    [n, 2, 4] device tensor; ONE SUM all-reduce of that tensor follows the last round.  -> int64 numpy [n, 2, 4]."""
     import torch
     import torch.distributed as dist
-    L, st, W, D, dev = con.lib, con._stream(), con.world_size, con.hidden_size, con.device
-    sharded = con._sharded("ent_embeddings")
-    if sharded and not dist.is_initialized():      # no process group, so no other rank can be waiting for this one
+    L, st, D, dev = con.lib, con._stream(), con.hidden_size, con.device
+    if not dist.is_initialized():      # no process group, so no other rank can be waiting for this one
         raise KgeError("rank_triples_distributed on a sharded entity table needs the process group it was sharded over")
+    lo, hi = con._shard["lo"], con._shard["hi"]
     th = 1 if test_head else 0
-    n = -1
-    if err is None:
-        n = int(ids.shape[1])
-        try:      # the arguments and the evaluation files, checked without a launch (no triples)
-            if sharded:
-                lo, hi = con._shard["lo"], con._shard["hi"]
-                _lib.check(L.kge_rank_triples_range(ctypes.byref(con._desc), con._tab_ptrs, lo, hi - lo, None, None, None, None, 0, th,
-                                                    None, st), L)
-            else:
-                con._rank_device(ids[:, :0], test_head)
-        except KgeError as e:
-            err, n = e, -1
+    if err is None:      # the arguments and the evaluation files, checked without a launch (no triples)
+        err = checked(lambda: _lib.check(L.kge_rank_triples_range(ctypes.byref(con._desc), con._tab_ptrs, lo, hi - lo, None, None, None,
+                                                                  None, 0, th, None, st), L))[1]
+    n = int(ids.shape[1]) if err is None else -1
     per = max(1, int(con.lp_shard_query_bytes) // (2 * D * 4))
-    _, per = agree(con, "rank_triples_distributed", err, (n, th), [1, 2], "numbers of triples or test_head", per,
-                   where=" on a sharded entity table" if sharded else "")
+    _, per = agree(con, "rank_triples_distributed", err, (n, th), [1, 2], "numbers of triples or test_head", per)
     counts = torch.zeros((max(n, 1), 2, 4), dtype=torch.int64, device=dev)
-    if sharded:
-        for c0 in range(0, n, per):
-            m = min(per, n - c0)
-            pairs = ids[:2, c0:c0 + m].t().contiguous().view(-1)      # h0, t0, h1, t1, ...
-            query = query_rows(con, pairs, 2 * m)                      # [m][2][D]: the raw h and t row of each triple
-            _lib.check(L.kge_rank_triples_range(ctypes.byref(con._desc), con._tab_ptrs, lo, hi - lo, query.data_ptr(),
-                                                ids[0, c0:].data_ptr(), ids[1, c0:].data_ptr(), ids[2, c0:].data_ptr(), m, th,
-                                                counts[c0].data_ptr(), st), L)
-            del query
-    else:
-        cs = par.chunk_size(n, W)
-        c0, c1 = min(con.rank * cs, n), min((con.rank + 1) * cs, n)
-        if c1 > c0:
-            con._rank_device(ids[:, c0:c1].contiguous(), test_head, into=counts[c0:c1])
+    for c0 in range(0, n, per):
+        m = min(per, n - c0)
+        pairs = ids[:2, c0:c0 + m].t().contiguous().view(-1)      # h0, t0, h1, t1, ...
+        query = query_rows(con, pairs, 2 * m)                      # [m][2][D]: the raw h and t row of each triple
+        _lib.check(L.kge_rank_triples_range(ctypes.byref(con._desc), con._tab_ptrs, lo, hi - lo, query.data_ptr(),
+                                            ids[0, c0:].data_ptr(), ids[1, c0:].data_ptr(), ids[2, c0:].data_ptr(), m, th,
+                                            counts[c0].data_ptr(), st), L)
+        del query
     all_reduce(con, counts, dist.ReduceOp.SUM)
     return counts[:n].cpu().numpy()
 
 
 def rank_candidates(con, ids, err, tail, head, n_cand, flags, seed, what="rank_candidates_distributed"):
-    """Config.rank_candidates_distributed / rank_triples_sampled_distributed on a sharded entity table.  `ids` is the int32 device
-    tensor [3, n] (h, t, r; ids already checked) or None, `err` what this rank's own argument check raised (or None); tail /
-    head = (int32 device tensor, stride) or None; with KGE_RANKC_DRAWN in `flags` both are None and `seed` draws the lists.  The
-    ranks first agree on a header (validity, n, C, flags, which sides have a list, their strides, the seed, triples per round);
-    the arguments and the evaluation files are checked before it, without a launch.  Then, in rounds of `per` triples, the
-    2 per h and t rows come from their owners (query_rows, laid out [per][2][D]) and kge_rank_candidates_range ranks the round
-    against this rank's rows [lo, hi) into its slice of one [n, 2, 2] device tensor: a round's per-triple lists start at
-    c0 x stride, and its drawn lists are indexed by the global triple (the seed is moved there as _rank_candidates_device moves
-    it).  ONE SUM all-reduce of that tensor closes the call: every rank compares against the same target score bits and counts
-    the candidates it owns, so the sum is kge_rank_candidates over the whole table.  -> int64 numpy [n, 2, 2]."""
+    """Config.rank_candidates_distributed / rank_triples_sampled_distributed on a sharded entity table, whose process group the
+    caller has found.  `ids` is the int32 device tensor [3, n] (h, t, r; checked) or None, `err` what this rank's own argument
+    check raised (or None); tail / head = (int32 device tensor, stride) or None; with KGE_RANKC_DRAWN in `flags` both are None
+    and `seed` draws the lists.  The ranks first agree on a header (validity, n, C, flags, which sides have a list, their strides,
+    the seed, triples per round); the arguments and the evaluation files are checked before it, without a launch.  Then, in
+    rounds of `per` triples, the 2 per h and t rows come from their owners (query_rows, laid out [per][2][D]) and
+    kge_rank_candidates_range ranks the round against this rank's rows [lo, hi) into its slice of one [n, 2, 2] device tensor: a
+    round's per-triple lists start at c0 x stride, and its drawn lists are indexed by the global triple (_lib.drawn_seed_at moves
+    the seed there).  ONE SUM all-reduce of that tensor closes the call: every rank compares against the same target score bits
+    and counts the candidates it owns, so the sum is kge_rank_candidates over the whole table.  -> int64 numpy [n, 2, 2]."""
     import torch
     import torch.distributed as dist
     L, st, D, dev = con.lib, con._stream(), con.hidden_size, con.device
-    if not dist.is_initialized():      # no process group, so no other rank can be waiting for this one
-        raise KgeError("%s over an entity table sharded across ranks needs the process group it was sharded over" % what)
     lo, hi = con._shard["lo"], con._shard["hi"]
     spare = torch.zeros((3, 4), dtype=torch.int32, device=dev)        # an empty tensor has no address
     ptr = lambda x, off=0: (x.view(-1)[off:] if off else x).data_ptr() if x.numel() > off else spare.data_ptr()
-    n, fields = -1, (0, 0, 0, 0, 0, 0)
+
+    def check():      # -> the header
+        C, fl = int(n_cand), int(flags)
+        lists = [(None, 0) if side is None else (ptr(side[0]), int(side[1])) for side in (tail, head)]
+        # the arguments and the evaluation files, checked without a launch (no triples)
+        _lib.check(L.kge_rank_candidates_range(ctypes.byref(con._desc), con._tab_ptrs, lo, hi - lo, None, spare.data_ptr(),
+                                               spare.data_ptr(), spare.data_ptr(), 0, lists[0][0], lists[0][1], lists[1][0],
+                                               lists[1][1], C, fl, 0, spare.data_ptr(), st), L)
+        sides = (1 if tail is not None else 0) | (2 if head is not None else 0)
+        return int(ids.shape[1]), C, fl, sides, lists[0][1], lists[1][1], int(seed) & (2 ** 62 - 1)
     if err is None:
-        try:
-            n, n_cand, flags = int(ids.shape[1]), int(n_cand), int(flags)
-            lists = [(None, 0) if side is None else (ptr(side[0]), int(side[1])) for side in (tail, head)]
-            # the arguments and the evaluation files, checked without a launch (no triples)
-            _lib.check(L.kge_rank_candidates_range(ctypes.byref(con._desc), con._tab_ptrs, lo, hi - lo, None, spare.data_ptr(),
-                                                   spare.data_ptr(), spare.data_ptr(), 0, lists[0][0], lists[0][1], lists[1][0],
-                                                   lists[1][1], n_cand, flags, 0, spare.data_ptr(), st), L)
-            sides = (1 if tail is not None else 0) | (2 if head is not None else 0)
-            fields = (n_cand, flags, sides, lists[0][1], lists[1][1], int(seed) & (2 ** 62 - 1))
-        except (KgeError, ValueError, TypeError, OverflowError, AttributeError) as e:
-            err, n = e, -1
+        header, err = checked(check)
+    if err is not None:
+        header = (-1, 0, 0, 0, 0, 0, 0)
+    n, n_cand, flags = header[:3]
     per = max(1, int(con.lp_shard_query_bytes) // (2 * D * 4))
-    _, per = agree(con, what, err, (n,) + tuple(fields), [1, 2, 3, 4, 5, 6, 7],
-                   "numbers of triples or candidates, flags, lists or seeds", per)
+    _, per = agree(con, what, err, header, [1, 2, 3, 4, 5, 6, 7], "numbers of triples or candidates, flags, lists or seeds", per)
     counts = torch.zeros((max(n, 1), 2, 2), dtype=torch.int64, device=dev)
     for c0 in range(0, n, per):
         m = min(per, n - c0)
         pairs = ids[:2, c0:c0 + m].t().contiguous().view(-1)      # h0, t0, h1, t1, ...
         query = query_rows(con, pairs, 2 * m)                      # [m][2][D]: the raw h and t row of each triple
         round_lists = [(None, 0) if side is None else (ptr(side[0], c0 * int(side[1])), int(side[1])) for side in (tail, head)]
-        round_seed = (int(seed) + ((c0 << 33) * 0x9E3779B97F4A7C15)) & 0xFFFFFFFFFFFFFFFF
         _lib.check(L.kge_rank_candidates_range(ctypes.byref(con._desc), con._tab_ptrs, lo, hi - lo, query.data_ptr(),
                                                ids[0, c0:].data_ptr(), ids[1, c0:].data_ptr(), ids[2, c0:].data_ptr(), m,
                                                round_lists[0][0], round_lists[0][1], round_lists[1][0], round_lists[1][1],
-                                               n_cand, flags, round_seed, counts[c0].data_ptr(), st), L)
+                                               n_cand, flags, _lib.drawn_seed_at(seed, c0), counts[c0].data_ptr(), st), L)
         del query
     all_reduce(con, counts, dist.ReduceOp.SUM)
     return counts[:n].cpu().numpy()

@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 
 from conftest import ROOT
+from openkeonspark_amd import rank_eval
 from shard_rig import KG, finish_rank, load_ranks, make_config, run_worlds, start_rank, union_config
 
 pytestmark = pytest.mark.gpu
@@ -300,7 +301,7 @@ def test_ranks_equal_one_process_over_the_union_table(sharded_runs, world):
         assert m == json.loads(str(zs[0]["metrics"]))
         assert set(m["dist"]) == ref_keys and set(m["all"]) == ref_keys
         assert m["dist"] == m["all"]
-        sums = con._lp_normalise(con._lp_sums(want, True), total)
+        sums = rank_eval.normalise(rank_eval.lp_sums(want, True), total)
         assert m["all"] == pytest.approx(sums, rel=0, abs=0)
 
 

@@ -287,7 +287,7 @@ def test_errors_leave_the_counts_untouched(tmp_path, monkeypatch):
     L.kge_clear_error()
     # an id out of range: KgeError on the host, nothing launched
     launched = []
-    monkeypatch.setattr(con, "_rank_device", lambda *a: launched.append(a))
+    monkeypatch.setattr(pkg.rank_eval, "rank_device", lambda *a: launched.append(a))
     for bad in (([con.entTotal], [0], [0]), ([0], [-1], [0]), ([0], [1], [con.relTotal])):
         with pytest.raises(pkg.KgeError):
             con.rank_triples(*bad)

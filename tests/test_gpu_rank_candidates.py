@@ -13,6 +13,7 @@ import pytest
 import score_ref
 from conftest import parity_report
 from gpu_engine import make_engine
+from openkeonspark_amd import rank_eval
 from score_ref import BAND, EVAL_CASES, MAX_ASIDE
 
 pytestmark = pytest.mark.gpu
@@ -144,7 +145,7 @@ def test_axis_tables_exact_integers(model, De, Dr):
         assert got.dtype == np.int64 and got.shape == (n, 2, 2)
         assert np.array_equal(got, want), (C, np.argwhere(got != want)[:5].tolist())
         assert not got[1].any() or C == E                     # the all -1 lists
-        assert metrics == con._lp_normalise(con._cand_sums(want), n)
+        assert metrics == rank_eval.normalise(rank_eval.cand_sums(want), n)
         bites |= bool((want[:, :, 1] < want[:, :, 0]).any())
         if C == 37:
             assert want[:, :, 0].any()
@@ -333,7 +334,7 @@ def test_drawn_lists(model, De, Dr):
     # a slice of the triples ranked with its global offset gives the slice of the whole call's counts
     import torch
     dev = torch.from_numpy(np.stack([h, t, r]).astype(np.int32)).to(con.device)
-    part = con._rank_candidates_device(dev[:, 11:40].contiguous(), None, None, C, FILTERED | DRAWN, seed, first=11)
+    part = rank_eval.rank_candidates_device(con, dev[:, 11:40].contiguous(), None, None, C, FILTERED | DRAWN, seed, first=11)
     assert np.array_equal(part, con.rank_triples_sampled(h, t, r, C, seed=seed)[0][11:40])
 
 

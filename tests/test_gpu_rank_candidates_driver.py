@@ -6,7 +6,7 @@ import pytest
 
 from conftest import GOLDEN
 from openkeonspark_amd import distribute_training as dt
-from openkeonspark_amd.Config import Config
+from openkeonspark_amd import rank_eval
 
 pytestmark = pytest.mark.gpu
 
@@ -23,12 +23,12 @@ def run(tmp_path, name, extra, kg="kg_small"):
 def candidate_calls(monkeypatch):
     """Every kge_rank_candidates call Config makes in a run: (triples, candidates, flags, seed)."""
     calls = []
-    real = Config._rank_candidates_device
+    real = rank_eval.rank_candidates_device
 
-    def spy(self, dev, tail, head, n_cand, flags, seed, first=0, into=None):
+    def spy(con, dev, tail, head, n_cand, flags, seed, first=0, into=None):
         calls.append((int(dev.shape[1]), n_cand, flags, seed))
-        return real(self, dev, tail, head, n_cand, flags, seed, first, into)
-    monkeypatch.setattr(Config, "_rank_candidates_device", spy)
+        return real(con, dev, tail, head, n_cand, flags, seed, first, into)
+    monkeypatch.setattr(rank_eval, "rank_candidates_device", spy)
     return calls
 
 

@@ -14,6 +14,7 @@ import numpy as np
 import pytest
 
 from conftest import ROOT
+from openkeonspark_amd import rank_eval
 from shard_rig import KG, finish_rank, load_ranks, make_config, run_worlds, start_rank, union_config
 from test_gpu_lp_shard import cuts, known_set, lp_ranges, read_triples, sorted_test_triples, type_lists
 
@@ -427,7 +428,7 @@ def test_ranks_equal_one_process_over_the_union_table(sharded_runs, world):
             if k == "after":
                 continue
             th = "tail" not in k
-            assert met[k] == pytest.approx(con._lp_normalise(con._lp_sums(w, th), w.shape[0]), rel=0, abs=0), (g, k)
+            assert met[k] == pytest.approx(rank_eval.normalise(rank_eval.lp_sums(w, th), w.shape[0]), rel=0, abs=0), (g, k)
             assert set(met[k]) == (names if th else {x for x in names if x.startswith("r")}), (g, k)
         assert z["raised"].tolist() == [1, 1, 1, 1], g
         assert z["refused"].tolist() == [1, 1], g

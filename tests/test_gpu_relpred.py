@@ -222,9 +222,9 @@ def test_relation_ranks_on_typed_graph(tmp_path, model):
 
 def test_relation_metric_reduction():
     """The 20 rel* metrics of a hand-made [count, 4] array: MR, MRR and Hits@1/3/10 of each column."""
-    from openkeonspark_amd.Config import Config
+    from openkeonspark_amd import rank_eval
     out = np.array([[0, 0, 0, 0], [3, 1, 0, 0], [12, 9, 2, 1], [2, 2, 1, 1], [30, 0, 9, 0]], np.int64)
-    d = Config._lp_normalise(Config._rel_sums(out), len(out))
+    d = rank_eval.normalise(rank_eval.rel_sums(out), len(out))
     assert len(d) == 20
     for col, name, suffix in ((0, "", ""), (1, "_filter", ""), (2, "", "_constrain"), (3, "_filter", "_constrain")):
         c = out[:, col]

@@ -6,7 +6,7 @@ import types
 import numpy as np
 import pytest
 
-from openkeonspark_amd import _lib
+from openkeonspark_amd import _lib, rank_eval
 from openkeonspark_amd import distribute_training as dt
 from openkeonspark_amd.Config import Config
 
@@ -90,7 +90,7 @@ def test_metric_names_and_values_from_hand_made_counts():
     counts[:, 0, 1] = [0, 0, 3, 9]           # tail side, filtered
     counts[:, 1, 0] = [1, 1, 1, 100]
     counts[:, 1, 1] = [0, 1, 1, 50]
-    m = Config._lp_normalise(Config._cand_sums(counts), 4)
+    m = rank_eval.normalise(rank_eval.cand_sums(counts), 4)
     names = {p + mid + end for p in "rl" for mid in ("", "_filter") for end in ("_tot", "_rank", "_reci_rank")} | \
             {p + k + mid + "_tot" for p in "rl" for k in "31" for mid in ("", "_filter")}
     assert set(m) == names and not any("constrain" in k for k in m)
@@ -100,12 +100,12 @@ def test_metric_names_and_values_from_hand_made_counts():
     assert m["r_reci_rank"] == pytest.approx((1 + 1 / 3 + 1 / 10 + 1 / 11) / 4, rel=1e-15)
     assert m["l_tot"] == 0.75 and m["l1_tot"] == 0.0 and m["l1_filter_tot"] == 0.25
     assert m["l_filter_reci_rank"] == pytest.approx((1 + 0.5 + 0.5 + 1 / 51) / 4, rel=1e-15)
-    tail_only = Config._cand_sums(counts, (0,))
+    tail_only = rank_eval.cand_sums(counts, (0,))
     assert tail_only and all(k.startswith("r") for k in tail_only)
     # link_prediction's own sums keep their forty names and values
     out = np.zeros((4, 2, 8), np.int64)
     out[:, :, 0], out[:, :, 1] = counts[:, :, 0], counts[:, :, 1]
-    lp = Config._lp_normalise(Config._lp_sums(out), 4)
+    lp = rank_eval.normalise(rank_eval.lp_sums(out), 4)
     assert len(lp) == 40 and all(lp[k] == m[k] for k in m)
     assert lp["r_tot_constrain"] == 1.0 and lp["l_filter_reci_rank_constrain"] == 1.0
 

@@ -64,7 +64,7 @@ def large_engine(pkg, model, dim, entities, triples):
 def range_cut(con, tt, C, W, rounds, seed=1):
     """-> the JSON line of one W: the range call on rows [0, ceil(E / W)) and the whole-table call, interleaved."""
     import torch
-    from openkeonspark_amd import _lib
+    from openkeonspark_amd import _lib, rank_eval
     E, D, L, st = con.entTotal, con.hidden_size, con.lib, con._stream()
     ent, rel = con._tables[0], con._tables[1]
     flags = _lib.RANKC_DRAWN | _lib.RANKC_FILTERED
@@ -79,7 +79,7 @@ def range_cut(con, tt, C, W, rounds, seed=1):
         _lib.check(L.kge_rank_candidates_range(ctypes.byref(con._desc), _lib.table_ptrs([ent[lo:].data_ptr(), rel.data_ptr()]), lo, hi - lo,
                                                query.data_ptr(), ids[0].data_ptr(), ids[1].data_ptr(), ids[2].data_ptr(), n, None, 0, None, 0,
                                                C, flags, seed, out.data_ptr(), st), L)
-    arms = {"whole": lambda: con._rank_candidates_device(ids, None, None, C, flags, seed, into=whole_counts),
+    arms = {"whole": lambda: rank_eval.rank_candidates_device(con, ids, None, None, C, flags, seed, into=whole_counts),
             "range": lambda: ranged(0, chunk, part_counts)}
     times = {k: [] for k in arms}
     for fn in arms.values():
