@@ -739,6 +739,55 @@ int kge_transe_emit_records_shared_chunks(const kge_model_desc *m, const float *
                                           const int32_t *d_r2, INT n_pos, INT stride, const int32_t *d_chunks, INT cap, const int32_t *d_cand, INT N,
                                           const uint8_t *d_pair, INT denom, uint32_t *d_rec, int32_t *d_dst, float *d_loss, void *stream);
 
+/* ---- TransH on relation-grouped chunks (NON-PARITY, opt-in; csrc/shared_proj.hip) ----
+ * Every positive of a relation-grouped chunk has the chunk's relation, so a chunk has ONE normalised normal vector and ONE r^,
+ * and a candidate is projected and normalised once per chunk: a chunk gathers 2 P + N + 2 table rows where the unshared step
+ * gathers P (2 + N) + 2 P.
+ *   Order, draw, mask.  Exactly those of the section above: kge_shared_order_by_relation and kge_shared_negatives_draw_grouped are
+ *               called unchanged (the draw handles ids only), and cap, the candidates, their sides, the masks and the typed lists
+ *               are theirs.  b is the SORTED position throughout.
+ *   Forward.    Chunk j has the relation rho of its first position (the ordering stage gives every position of a chunk the same
+ *               one; rho outside [0, rel_total): the chunk takes no part).  l2n(x) = x / sqrt(max(sum x^2, 1e-12)).
+ *               w^ = l2n(normal_vectors[rho]), r^ = l2n(rel_embeddings[rho]).  For an entity row x: a = x . w^, x_perp = x - a w^,
+ *               x^ = l2n(x_perp) (side_project<KGE_TRANSH>, csrc/models_dev.hpp).  p_b = sum |h^_b + r^ - t^_b|.  For the pair
+ *               (b, k): e = c^_k + r^ - t^_b for a new head, h^_b + r^ - c^_k for a new tail; v = p_b - sum |e| + margin.  The pair
+ *               is ACTIVE when it is unmasked, h_b, t_b and the candidate id lie in [0, ent_total), and v >= 0 (a tie is active;
+ *               sign(0) = 0).  loss = (1 / denom) sum over the active pairs of v; masked pairs stay in the denominator.
+ *   Backward.   The gradients with respect to the NORMALISED PROJECTED vectors are integer sign counts, those of the TransE
+ *               definition (tests/shared_neg_ref.py forward, `recs`): with s = sign(e) of an active pair, G(c^_k) takes -s for a
+ *               new head and +s for a new tail, G(t^_b) +s of every new head, G(h^_b) -s of every new tail, G_r of the positive
+ *               -s of every active pair; a positive with cnt active pairs adds cnt sign(h^ + r^ - t^) to G(h^_b) and its G_r and
+ *               subtracts it from G(t^_b).  The chunk's G_r is the sum of its positives' (within +-2 N P: an int32, not an int8).
+ *               With unit = 1 / denom, every entity row goes through side_backward<KGE_TRANSH> of unit G:
+ *                 gxp = normalize_bwd(x^, unit G) = inv (unit G - [the norm was not clipped] (x^ . unit G) x^), inv = 1 / |x_perp|
+ *                 d = gxp . w^;  the row's gradient = gxp - d w^;  acw -= d x + a gxp
+ *               The chunk's rel_embeddings gradient is normalize_bwd(r^, unit G_r), its normal_vectors gradient
+ *               normalize_bwd(w^, acw), acw summed over the 2 len + N entity rows of the chunk in a fixed order (the rows with a
+ *               zero count vector add nothing).  A normal vector whose norm is clipped (an all-zero row) gives w^ = 0: the
+ *               projection is the identity and acw is zero.
+ *   Records.    M = 2 n_pos + cap (N + 2) FLOAT records of D floats: record b is h of position b, n_pos + b its t, 2 n_pos + j
+ *               the rel_embeddings row of chunk j, 2 n_pos + cap + j its normal_vectors row, 2 n_pos + 2 cap + j N + k candidate
+ *               k of chunk j.
+ *   Keys.       In the virtual row space kge_float_records_apply / _adam / _adagrad give a TransH step of n_pos_total positives and
+ *               N negatives: an entity id; hub_base + (j % hub_k) 2 R + rho for rel_embeddings and ... + R + rho for
+ *               normal_vectors, with R = rel_total, hub_base = ent_total and hub_k = min(max(n_pos_total / (64 R), 1), 4096).
+ *               A record whose count vector is all zero has key -1 (and unspecified contents); the relation record carries a key
+ *               iff G_r != 0, the normal-vector record iff any entity record of the chunk does; every key of an empty slot, and of
+ *               a position no slot covers, is -1.
+ * kge_transh_emit_records_shared_chunks: one workgroup of four waves per chunk slot; no global atomics; a wave's shares of acw are
+ *   added in the order it meets its rows, the four waves are folded in index order and the loss partials are summed over all cap
+ *   slots in index order: a step is reproducible bit for bit.  tables: ent_embeddings, rel_embeddings, normal_vectors.  denom:
+ *   batch_size * N of the whole step; n_pos_total: the step's positives (what the apply call is given).  d_rec: float [M][D], 16-byte
+ *   aligned; d_dst: int32 [M].  KGE_ERR_UNSUPPORTED, naming the limit: another model, negative_rel > 0, N outside 1..63,
+ *   ent_dim != rel_dim, a width above 512.  A chunk longer than 127 is the caller's error.
+ * kge_shared_float_supported: 1 where that entry point takes the model and N (TransH, ent_dim == rel_dim <= 512,
+ *   negative_rel == 0, 1 <= N <= 63), else 0.  Host only. */
+int kge_transh_emit_records_shared_chunks(const kge_model_desc *m, const float *const tables[KGE_MAX_TABLES], const int32_t *d_h2,
+                                          const int32_t *d_t2, const int32_t *d_r2, INT n_pos, INT stride, const int32_t *d_chunks, INT cap,
+                                          const int32_t *d_cand, INT N, const uint8_t *d_pair, INT denom, INT n_pos_total, float *d_rec,
+                                          int32_t *d_dst, float *d_loss, void *stream);
+int kge_shared_float_supported(const kge_model_desc *m, INT N);
+
 /* ---- Table-sharded sparse path (N GPUs, BASELINE config #5): rank g OWNS the entity rows [g*chunk, (g+1)*chunk); what the
  * reference does with ps tasks holding the variables and workers pulling rows / pushing IndexedSlices over gRPC
  * (distribute_training.py:193-196) becomes: request ids -> all-to-all -> owners gather rows -> all-to-all -> emit records

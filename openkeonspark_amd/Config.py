@@ -162,7 +162,11 @@ class Config(object):
         definition is in include/kge_mi355.h).  A candidate then has ONE side for its whole chunk, and with
         set_type_constrained_sampling(True), in either call order, it is drawn from that side's type list of the chunk's relation
         (all entities for a relation without a list); the lists are found as typed sampling finds them.  One rank only: a
-        rank's slice would need the order of the whole batch."""
+        rank's slice would need the order of the whole batch.
+        TransH trains on shared negatives with by_relation=True only (widths up to 512; SGD, LazyAdam or Adagrad): a chunk of one
+        relation also shares the normalised normal vector and r^, and a candidate is projected once per chunk; its float
+        gradient records go through the touched-rows rule of the unshared TransH step (include/kge_mi355.h, "TransH on
+        relation-grouped chunks").  TransD and TransR stay refused."""
         if self.trainModel is not None:
             raise KgeError("set_shared_negatives must be called before set_model_and_session: it decides the step's path")
         chunk = int(chunk)
@@ -467,7 +471,8 @@ class Config(object):
             self.lib.kge_transe_counts_supported(ctypes.byref(probe.descriptor()), n_neg), self.entTotal, self.relTotal,
             self.hidden_size, self.batch_size, n_neg, getattr(self, "sparse_threshold_bytes", None), self.adagrad_initial_accumulator,
             shared_chunk=self._shared_chunk, negative_rel=self.negative_rel, by_relation=self._shared_by_relation,
-            typed=bool(self._shared_chunk and self.type_constrained_sampling))
+            typed=bool(self._shared_chunk and self.type_constrained_sampling),
+            shared_float_supported=self.lib.kge_shared_float_supported(ctypes.byref(probe.descriptor()), self.negative_ent))
         self.use_counts, self.sparse_rows, self.sparse_inplace = p.use_counts, p.sparse_rows, p.sparse_inplace
         self._adam, self._lazy_adam, self._adagrad = p.adam, p.lazy_adam, p.adagrad
         self._has_slots, self._rows_rule = p.has_slots, p.rows_rule

@@ -185,6 +185,10 @@ def _declare(L):
     L.kge_shared_negatives_draw_grouped.argtypes = [vp, vp, vp, i64, vp, i64, i64, i64, ctypes.c_uint64, i64, vp, vp, vp]
     L.kge_transe_emit_records_shared_chunks.argtypes = [ctypes.POINTER(ModelDesc), vp, vp, vp, vp, vp, i64, i64, vp, i64, vp, i64, vp, i64, vp, vp,
                                                         vp, vp]
+    # ... TransH on those chunks, float records (csrc/shared_proj.hip)
+    L.kge_shared_float_supported.argtypes = [ctypes.POINTER(ModelDesc), i64]
+    L.kge_transh_emit_records_shared_chunks.argtypes = [ctypes.POINTER(ModelDesc), tabs, vp, vp, vp, i64, i64, vp, i64, vp, i64, vp, i64, i64,
+                                                        vp, vp, vp, vp]
     L.kge_transe_apply_counts_range.argtypes =[ctypes.POINTER(ModelDesc), vp, vp, vp, vp, vp, i64, i64, i64, i32, f32, f32, f32, f32, vp]
     # table-sharded sparse path (csrc/shard.hip)
     L.kge_shard_requests.argtypes = [vp, vp, vp, i64, i64, i64, vp, vp]

@@ -209,6 +209,8 @@ int launch_float_records_apply_adam(const kge_model_desc &m, float *const tables
                                     int64_t M_total, int64_t n_pos_total, int64_t n_neg, hipStream_t stream);
 int launch_float_records_apply(const kge_model_desc &m, float *const tables[4], const float *d_rec, int32_t *d_dst, int64_t M_total,
                                int64_t n_pos_total, int64_t n_neg, float lr, hipStream_t stream);
+// the virtual row space those three give a step of n_pos_total positives and n_neg negatives (models.hip record_space)
+void float_record_hubs(const kge_model_desc &m, int64_t n_pos_total, int64_t n_neg, int64_t &hub_base, int64_t &hub_k, int64_t &rows);
 
 // device-side index build (index_build.hip)
 bool device_index_build_supported(int64_t E, int64_t R, int64_t n);

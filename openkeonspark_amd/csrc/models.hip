@@ -1354,6 +1354,12 @@ static RecordSpace record_space(const kge_model_desc &m, int64_t n_pos, int64_t 
     return s;
 }
 
+// the same space for a kernel outside this file that keys its own float records (shared_proj.hip): first hub row, copies, all rows
+void float_record_hubs(const kge_model_desc &m, int64_t n_pos_total, int64_t n_neg, int64_t &hub_base, int64_t &hub_k, int64_t &rows) {
+    const RecordSpace sp = record_space(m, n_pos_total, n_neg);
+    hub_base = sp.ent_rows; hub_k = sp.hub_k; rows = sp.rows;
+}
+
 // Data-parallel form of the row-wise SGD in place (kge_forward_backward_sgd_rows cut in two): every rank stores the gradient rows
 // of ITS slice of the batch as float records into its slice [rec_offset, rec_offset + rec_slice) of a buffer all ranks then
 // all-gather, and every rank applies ALL records to its replica (launch_float_records_apply) -- the touched-row exchange of

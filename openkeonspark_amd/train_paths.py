@@ -553,27 +553,35 @@ def shared_grouped_step(con, dev, n_pos, stride, denom):
     chunk's candidates and their sides from (seed, global_step) -- from the relation's type lists with type-constrained sampling
     on -- and looks the masks up, the emit kernel reads its chunks from the table, and the sparse step's reduce and rows rule
     finish over 3 n_pos + cap N records.  The chunk count stays on the device: everything is sized by cap =
-    shared_chunk_cap(stride, P, relTotal), and the step has no host synchronisation.  Buffers only grow."""
+    shared_chunk_cap(stride, P, relTotal), and the step has no host synchronisation.  Buffers only grow.
+    TransH (the model is read from the Config): same order, same draw, same buffer names; the chunk's one normal vector and one
+    r^ are shared too.  kge_transh_emit_records_shared_chunks writes 2 n_pos + cap (N + 2) FLOAT records -- h and t per position,
+    the relation row, the normal vector and N candidates per chunk slot -- keyed in the row space of the unshared TransH step,
+    and the rows rule takes them as it takes that step's (RowsRule.apply_float_records)."""
     import torch
     P, N, D = con._shared_chunk, con.negative_ent, con.hidden_size
+    transh = con.trainModel.model_id == _lib.TRANSH
     cap = shared_chunk_cap(n_pos, P, con.relTotal)
     cap_max = shared_chunk_cap(stride, P, con.relTotal)
-    m_cap = 3 * stride + cap_max * N
+    m_cap = 2 * stride + cap_max * (N + 2) if transh else 3 * stride + cap_max * N
     buf = con._sparse_buf
     if buf is None or "chunks" not in buf or buf.get("shared_cap", 0) < m_cap or buf["pair"].shape[0] < stride:
         d = con.device
-        dw = int(con.lib.kge_transe_record_dwords(ctypes.byref(con._desc)))
         i32 = torch.int32
         buf = dict(shared_cap=m_cap,
                    perm=torch.empty(stride, dtype=i32, device=d), sorted=torch.empty((3, stride), dtype=i32, device=d),
                    chunks=torch.empty((cap_max, 2), dtype=i32, device=d), n_chunks=torch.zeros(1, dtype=i32, device=d),
                    cand=torch.empty((cap_max, N), dtype=i32, device=d),
                    pair=torch.empty((stride, N), dtype=torch.uint8, device=d),
-                   rec=torch.empty((m_cap, dw), dtype=i32, device=d),
-                   dst=torch.empty(m_cap, dtype=i32, device=d),
-                   rows=torch.empty(m_cap, dtype=i32, device=d),
-                   row_counts=torch.empty((m_cap, D), dtype=i32, device=d),
-                   n_rows=torch.zeros(1, dtype=i32, device=d))
+                   dst=torch.empty(m_cap, dtype=i32, device=d))
+        if transh:
+            buf.update(rec=torch.empty((m_cap, D), dtype=torch.float32, device=d))
+        else:
+            dw = int(con.lib.kge_transe_record_dwords(ctypes.byref(con._desc)))
+            buf.update(rec=torch.empty((m_cap, dw), dtype=i32, device=d),
+                       rows=torch.empty(m_cap, dtype=i32, device=d),
+                       row_counts=torch.empty((m_cap, D), dtype=i32, device=d),
+                       n_rows=torch.zeros(1, dtype=i32, device=d))
         con._sparse_buf = buf
     L, st = con.lib, con._stream()
     h, t, r = dev[0].data_ptr(), dev[1].data_ptr(), dev[2].data_ptr()
@@ -582,6 +590,16 @@ def shared_grouped_step(con, dev, n_pos, stride, denom):
     _lib.check(L.kge_shared_order_by_relation(h, t, r, n_pos, P, buf["perm"].data_ptr(), h2, t2, r2, chunks, buf["n_chunks"].data_ptr(), st), L)
     _lib.check(L.kge_shared_negatives_draw_grouped(h2, t2, r2, n_pos, chunks, cap, N, 1 if con.type_constrained_sampling else 0,
                                                    con._shared_seed, con.global_step, cand, pair, st), L)
+    if transh:
+        M = 2 * n_pos + cap * (N + 2)
+        _lib.check(L.kge_transh_emit_records_shared_chunks(ctypes.byref(con._desc), con._tab_ptrs, h2, t2, r2, n_pos, stride, chunks, cap, cand,
+                                                           N, pair, denom, con.batch_size, buf["rec"].data_ptr(), buf["dst"].data_ptr(),
+                                                           con._loss.data_ptr(), st), L)
+        buf["shared_step"], buf["shared_shape"], buf["shared_batch"] = con.global_step, (n_pos, cap), dev
+        con._rule.apply_float_records(buf["rec"], buf["dst"], M, con.batch_size, N)
+        con._rule.advance()
+        con.global_step += 1
+        return
     _lib.check(L.kge_transe_emit_records_shared_chunks(ctypes.byref(con._desc), con._tables[0].data_ptr(), con._tables[1].data_ptr(), h2, t2, r2,
                                                        n_pos, stride, chunks, cap, cand, N, pair, denom, buf["rec"].data_ptr(),
                                                        buf["dst"].data_ptr(), con._loss.data_ptr(), st), L)
