@@ -788,6 +788,54 @@ int kge_transh_emit_records_shared_chunks(const kge_model_desc *m, const float *
                                           int32_t *d_dst, float *d_loss, void *stream);
 int kge_shared_float_supported(const kge_model_desc *m, INT N);
 
+/* ---- TransD on relation-grouped chunks (NON-PARITY, opt-in; csrc/shared_proj.hip, the TransH kernel under MODEL = KGE_TRANSD) ----
+ * A chunk of one relation shares r^ and the relation's transfer vector r_p, and a candidate's two rows (ent_embeddings and
+ * ent_transfer) are gathered, projected and normalised once per chunk: a chunk gathers 2 (2 P + N) + 2 table rows where the
+ * unshared step gathers P (4 + 2 N) + 2 P.
+ *   Order, draw, mask.  Exactly those of the two sections above: kge_shared_order_by_relation and
+ *               kge_shared_negatives_draw_grouped are called unchanged, and cap, the candidates, their sides, the masks and the
+ *               typed lists are theirs.  b is the SORTED position throughout.
+ *   Forward.    Chunk j has the relation rho of its first position (rho outside [0, rel_total): the chunk takes no part).
+ *               l2n(x) = x / sqrt(max(sum x^2, 1e-12)).  r^ = l2n(rel_embeddings[rho]); r_p = rel_transfer[rho], RAW, not
+ *               normalised (ctx_forward<KGE_TRANSD>).  For an entity id with ent_embeddings row x and ent_transfer row x_p:
+ *               a = x . x_p, x_perp = x + a r_p, x^ = l2n(x_perp) (side_project<KGE_TRANSD>, csrc/models_dev.hpp).  p_b, e, v,
+ *               ACTIVE, loss and denominator are TransH's on these x^: a tie v >= 0 is active, sign(0) = 0, masked pairs stay
+ *               in the denominator.
+ *   Backward.   The gradients with respect to the NORMALISED PROJECTED vectors are the integer sign counts of the TransE / TransH
+ *               definition: G(c^_k), G(h^_b), G(t^_b), and the chunk's G_r as an int32.  With unit = 1 / denom, every entity goes
+ *               through side_backward<KGE_TRANSD> of unit G:
+ *                 gxp = normalize_bwd(x^, unit G) = inv (unit G - [the norm was not clipped] (x^ . unit G) x^), inv = 1 / |x_perp|
+ *                 d = gxp . r_p;  gradient of the ent_embeddings row = gxp + d x_p;  of the ent_transfer row = d x;  acw += a gxp
+ *               The chunk's rel_embeddings gradient is normalize_bwd(r^, unit G_r); its rel_transfer gradient is acw ITSELF (r_p
+ *               is used raw: no normalise-backward), summed over the chunk's 2 len + N entities in a fixed order: each wave in
+ *               the order it meets its rows, then the four waves in index order.  An all-zero rel_transfer row makes the
+ *               projection the identity and d = 0: the transfer records are then zero, and still carry their keys.
+ *   Records.    M = 4 n_pos + cap (2 N + 2) FLOAT records of D floats: record b is h's ent_embeddings row, n_pos + b h's
+ *               ent_transfer row, 2 n_pos + b t's ent_embeddings row, 3 n_pos + b t's ent_transfer row, 4 n_pos + j the
+ *               rel_embeddings row of chunk j, 4 n_pos + cap + j its rel_transfer row, 4 n_pos + 2 cap + j N + k candidate k's
+ *               ent_embeddings row, 4 n_pos + 2 cap + cap N + j N + k its ent_transfer row.
+ *   Keys.       In the virtual row space kge_float_records_apply / _adam / _adagrad give a TransD step of n_pos_total positives and
+ *               N negatives: ent [0, E) | ent_transfer [E, 2 E) | hub_k copies of { rel [R] | rel_transfer [R] } from
+ *               hub_base = 2 E, with hub_k = min(max(n_pos_total / (64 R), 1), 4096).  An entity row has key id, its transfer
+ *               row E + id; rel_embeddings hub_base + (j % hub_k) 2 R + rho, rel_transfer ... + R + rho.  A row whose count vector
+ *               is all zero has key -1 for BOTH of its records (contents unspecified), and an entity's transfer record carries a
+ *               key exactly when its embedding record does, even where d = 0.  The rel_embeddings record carries a key iff
+ *               G_r != 0, the rel_transfer record iff any entity record of the chunk does; every key of an empty slot, and of a
+ *               position no slot covers, is -1.
+ * kge_transd_emit_records_shared_chunks: the arguments of kge_transh_emit_records_shared_chunks; one workgroup of four waves per
+ *   chunk slot, no global atomics, fixed summation orders: a step is reproducible bit for bit.  tables: ent_embeddings,
+ *   rel_embeddings, rel_transfer, ent_transfer (all four are read).  With more than one candidate tile a positive's two count
+ *   vectors wait as int32 in record slots b and 2 n_pos + b.  d_rec: float [M][D], 16-byte aligned; d_dst: int32 [M], all blanked
+ *   first.  KGE_ERR_UNSUPPORTED, naming the limit: another model, negative_rel > 0, N outside 1..63, ent_dim != rel_dim, a width
+ *   above 512.  A chunk longer than 127 is the caller's error.
+ * kge_shared_transd_supported: 1 where that entry point takes the model and N (TransD, ent_dim == rel_dim <= 512,
+ *   negative_rel == 0, 1 <= N <= 63), else 0.  Host only.  (kge_shared_float_supported keeps answering 0 for TransD.) */
+int kge_transd_emit_records_shared_chunks(const kge_model_desc *m, const float *const tables[KGE_MAX_TABLES], const int32_t *d_h2,
+                                          const int32_t *d_t2, const int32_t *d_r2, INT n_pos, INT stride, const int32_t *d_chunks, INT cap,
+                                          const int32_t *d_cand, INT N, const uint8_t *d_pair, INT denom, INT n_pos_total, float *d_rec,
+                                          int32_t *d_dst, float *d_loss, void *stream);
+int kge_shared_transd_supported(const kge_model_desc *m, INT N);
+
 /* ---- Table-sharded sparse path (N GPUs, BASELINE config #5): rank g OWNS the entity rows [g*chunk, (g+1)*chunk); what the
  * reference does with ps tasks holding the variables and workers pulling rows / pushing IndexedSlices over gRPC
  * (distribute_training.py:193-196) becomes: request ids -> all-to-all -> owners gather rows -> all-to-all -> emit records

@@ -166,7 +166,10 @@ class Config(object):
         TransH trains on shared negatives with by_relation=True only (widths up to 512; SGD, LazyAdam or Adagrad): a chunk of one
         relation also shares the normalised normal vector and r^, and a candidate is projected once per chunk; its float
         gradient records go through the touched-rows rule of the unshared TransH step (include/kge_mi355.h, "TransH on
-        relation-grouped chunks").  TransD and TransR stay refused."""
+        relation-grouped chunks").  TransD trains the same way (by_relation=True only, widths up to 512, the same three
+        optimizers): a chunk shares r^ and its relation's raw transfer vector, an entity's two rows are gathered once per chunk, and
+        every entity writes two float records, one for its ent_embeddings row and one for its ent_transfer row ("TransD on
+        relation-grouped chunks").  TransR stays refused."""
         if self.trainModel is not None:
             raise KgeError("set_shared_negatives must be called before set_model_and_session: it decides the step's path")
         chunk = int(chunk)
@@ -472,7 +475,8 @@ class Config(object):
             self.hidden_size, self.batch_size, n_neg, getattr(self, "sparse_threshold_bytes", None), self.adagrad_initial_accumulator,
             shared_chunk=self._shared_chunk, negative_rel=self.negative_rel, by_relation=self._shared_by_relation,
             typed=bool(self._shared_chunk and self.type_constrained_sampling),
-            shared_float_supported=self.lib.kge_shared_float_supported(ctypes.byref(probe.descriptor()), self.negative_ent))
+            shared_float_supported=self.lib.kge_shared_float_supported(ctypes.byref(probe.descriptor()), self.negative_ent),
+            shared_transd_supported=self.lib.kge_shared_transd_supported(ctypes.byref(probe.descriptor()), self.negative_ent))
         self.use_counts, self.sparse_rows, self.sparse_inplace = p.use_counts, p.sparse_rows, p.sparse_inplace
         self._adam, self._lazy_adam, self._adagrad = p.adam, p.lazy_adam, p.adagrad
         self._has_slots, self._rows_rule = p.has_slots, p.rows_rule

@@ -189,6 +189,9 @@ def _declare(L):
     L.kge_shared_float_supported.argtypes = [ctypes.POINTER(ModelDesc), i64]
     L.kge_transh_emit_records_shared_chunks.argtypes = [ctypes.POINTER(ModelDesc), tabs, vp, vp, vp, i64, i64, vp, i64, vp, i64, vp, i64, i64,
                                                         vp, vp, vp, vp]
+    # ... and TransD (the same kernel with the transfer rows; all four tables are read)
+    L.kge_shared_transd_supported.argtypes = [ctypes.POINTER(ModelDesc), i64]
+    L.kge_transd_emit_records_shared_chunks.argtypes = L.kge_transh_emit_records_shared_chunks.argtypes
     L.kge_transe_apply_counts_range.argtypes =[ctypes.POINTER(ModelDesc), vp, vp, vp, vp, vp, i64, i64, i64, i32, f32, f32, f32, f32, vp]
     # table-sharded sparse path (csrc/shard.hip)
     L.kge_shard_requests.argtypes = [vp, vp, vp, i64, i64, i64, vp, vp]

@@ -19,6 +19,12 @@
 // Fixed orders everywhere, no global atomics: a wave adds its rows' shares of d/dw^ in the order it meets them, the four waves are
 // folded in index order, the loss is summed per wave in candidate order, per chunk in wave order and over all cap slots in index
 // order.  A step is reproducible bit for bit.
+//
+// TransD on the same chunks (include/kge_mi355.h, "TransD on relation-grouped chunks") is the same kernel under MODEL = KGE_TRANSD:
+// the chunk's context vector is the RAW rel_transfer row r_p, an entity gathers its ent_transfer row x_p beside its row x,
+// a = x . x_p and x^ = l2n(x + a r_p).  The pair walk does not change.  An entity writes TWO records (gxp + d x_p for its row,
+// d x for its transfer row, d = gxp . r_p), a wave's accumulator takes a gxp, and the closing fold stores the sum as the
+// rel_transfer record without a normalise-backward.  A positive's waiting count vectors sit in its two ent_embeddings slots.
 #include <algorithm>
 #include <string>
 
@@ -32,7 +38,7 @@ namespace {
 DevBuf<float> g_partials;
 
 struct ProjEmitArgs {
-    const float *ent, *rel, *nrm;    // ent_embeddings, rel_embeddings, normal_vectors
+    const float *ent, *rel, *nrm;    // ent_embeddings, rel_embeddings, the context table (normal_vectors; TransD: rel_transfer)
     const int32_t *h, *t, *r;        // in sorted order
     const int32_t *cand;
     const uint8_t *pair;
@@ -47,6 +53,7 @@ struct ProjEmitArgs {
     float *rec;
     int32_t *dst;
     float *partials;
+    const float *entp;               // TransD: ent_transfer
 };
 
 __device__ __forceinline__ int sgn_i(float e) { return (e > 0.f ? 1 : 0) - (e < 0.f ? 1 : 0); }
@@ -125,13 +132,30 @@ struct WaveRow {
 #pragma unroll
         for (int c = 0; c < V; c++) gx[c] = inv * (gy[c] - d * y[c]);
     }
-    // side_project<KGE_TRANSH> (models_dev.hpp): a = x . w^, x^ = l2n(x - a w^)
-    __device__ __forceinline__ void project(const float (&x)[V], const float (&wn)[V], float (&xn)[V], float &a, float &inv, bool &unclipped) const {
-        a = dot(x, wn);
+    // side_project<MODEL> (models_dev.hpp).  TransH: a = x . w^, x^ = l2n(x - a w^), cw = w^ (xt is not read).
+    // TransD: a = x . x_p, x^ = l2n(x + a r_p), xt = x_p, cw = r_p
+    template <int MODEL>
+    __device__ __forceinline__ void project(const float (&x)[V], const float (&xt)[V], const float (&cw)[V], float (&xn)[V], float &a, float &inv,
+                                            bool &unclipped) const {
         float xp[V];
+        if constexpr (MODEL == KGE_TRANSD) {
+            a = dot(x, xt);
 #pragma unroll
-        for (int c = 0; c < V; c++) xp[c] = x[c] - a * wn[c];
+            for (int c = 0; c < V; c++) xp[c] = x[c] + a * cw[c];
+        } else {
+            a = dot(x, cw);
+#pragma unroll
+            for (int c = 0; c < V; c++) xp[c] = x[c] - a * cw[c];
+        }
         normalize(xp, xn, inv, unclipped);
+    }
+    // row `id` of the entity table (TransD: and of ent_transfer), projected and normalised
+    template <int MODEL>
+    __device__ __forceinline__ void gather_project(const float *__restrict__ ent, const float *__restrict__ entp, long long id, const float (&cw)[V],
+                                                   float (&x)[V], float (&xt)[V], float (&xn)[V], float &a, float &inv, bool &unclipped) const {
+        load(ent + id * D, x);
+        if constexpr (MODEL == KGE_TRANSD) load(entp + id * D, xt);
+        project<MODEL>(x, xt, cw, xn, a, inv, unclipped);
     }
     __device__ __forceinline__ bool any_nonzero(const int (&g)[V]) const {
         int o = 0;
@@ -139,26 +163,42 @@ struct WaveRow {
         for (int c = 0; c < V; c++) o |= g[c];
         return __ballot(o != 0) != 0;
     }
-    // side_backward<KGE_TRANSH> of unit * G: the row's gradient record, and its share of d/dw^ into acw
-    __device__ __forceinline__ void side_record(const float (&x)[V], const float (&xn)[V], float a, float inv, bool unclipped, const int (&G)[V],
-                                                float unit, const float (&wn)[V], float (&acw)[V], float *__restrict__ out) const {
+    // side_backward<MODEL> of unit * G: the row's gradient record (TransD: and its transfer row's, into out_t), and its share of
+    // d/dw^ (TransD: d/dr_p) into acw
+    template <int MODEL>
+    __device__ __forceinline__ void side_record(const float (&x)[V], const float (&xt)[V], const float (&xn)[V], float a, float inv, bool unclipped,
+                                                const int (&G)[V], float unit, const float (&cw)[V], float (&acw)[V], float *__restrict__ out,
+                                                float *__restrict__ out_t) const {
         float g[V], gxp[V];
 #pragma unroll
         for (int c = 0; c < V; c++) g[c] = unit * (float)G[c];
         normalize_bwd(xn, g, inv, unclipped, gxp);
-        const float d = dot(gxp, wn);
+        const float d = dot(gxp, cw);
+        if constexpr (MODEL == KGE_TRANSD) {
 #pragma unroll
-        for (int c = 0; c < V; c++) {
-            g[c] = gxp[c] - d * wn[c];
-            acw[c] -= d * x[c] + a * gxp[c];
+            for (int c = 0; c < V; c++) g[c] = d * x[c];
+            store(out_t, g);
+#pragma unroll
+            for (int c = 0; c < V; c++) {
+                g[c] = gxp[c] + d * xt[c];
+                acw[c] += a * gxp[c];
+            }
+        } else {
+#pragma unroll
+            for (int c = 0; c < V; c++) {
+                g[c] = gxp[c] - d * cw[c];
+                acw[c] -= d * x[c] + a * gxp[c];
+            }
         }
         store(out, g);
     }
 };
 
-template <int Q, bool VEC>
+template <int MODEL, int Q, bool VEC>
 __global__ __launch_bounds__(256) void shared_proj_emit_kernel(ProjEmitArgs a) {
     constexpr int V = 4 * Q;
+    constexpr bool TD = MODEL == KGE_TRANSD;
+    constexpr int EW = TD ? 2 : 1;       // records per entity: TransD's transfer row follows n_pos (a candidate's: cap N) later
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
     const int T = a.T, RS = a.RS, D = a.D, N = a.N;
     float *wl = reinterpret_cast<float *>(lds);                                    // [4] wave losses
@@ -172,16 +212,21 @@ __global__ __launch_bounds__(256) void shared_proj_emit_kernel(ProjEmitArgs a) {
     float *cinv = ca + T;                                                          // [T] 1 / |c_perp|
     int *cuc = reinterpret_cast<int *>(cinv + T);                                  // [T] 0 = the norm was clipped
     float *facw = reinterpret_cast<float *>(body);                                 // after the last tile, over the same bytes:
-    int *fgr = reinterpret_cast<int *>(body + (size_t)16 * RS);                    //   [4][RS] d/dw^ and [4][RS] r counts per wave
+    int *fgr = reinterpret_cast<int *>(body + (size_t)16 * RS);                    //   [4][RS] d/dw^ (d/dr_p) and [4][RS] r counts per wave
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const long long j = blockIdx.x;
-    const long long m_rel = 2 * a.n_pos + j, m_nrm = 2 * a.n_pos + a.cap + j, m_c0 = 2 * a.n_pos + 2 * a.cap + j * N;
+    const long long m_rel = 2 * EW * a.n_pos + j, m_nrm = m_rel + a.cap, m_c0 = 2 * EW * a.n_pos + 2 * a.cap + j * N;
+    const long long ct_off = a.cap * N;       // TransD: a candidate's transfer record lies this far behind its row's
+    const long long E = a.ent_total;          // TransD: key of a transfer row = E + id
     const int2 ch = a.chunks[j];
     const bool in = ch.x >= 0 && ch.x < a.n_pos && ch.y > 0;       // (a slot that points outside the call is an empty one)
     const long long b0 = in ? ch.x : 0;
     const int Pc = in ? (int)min((long long)ch.y, a.n_pos - b0) : 0;
     if (Pc == 0) {
-        if ((int)threadIdx.x < N) a.dst[m_c0 + threadIdx.x] = -1;
+        if ((int)threadIdx.x < N) {
+            a.dst[m_c0 + threadIdx.x] = -1;
+            if constexpr (TD) a.dst[m_c0 + ct_off + threadIdx.x] = -1;
+        }
         if (threadIdx.x == 0) { a.dst[m_rel] = -1; a.dst[m_nrm] = -1; a.partials[j] = 0.f; }
         return;
     }
@@ -194,8 +239,13 @@ __global__ __launch_bounds__(256) void shared_proj_emit_kernel(ProjEmitArgs a) {
     bool uc_w, uc_r;
     {
         float x[V];
-        rw.load(a.nrm + (long long)(rho_ok ? rho : 0) * D, x);
-        rw.normalize(x, WN, inv_w, uc_w);
+        if constexpr (TD) {      // r_p raw (ctx_forward<KGE_TRANSD>)
+            rw.load(a.nrm + (long long)(rho_ok ? rho : 0) * D, WN);
+            inv_w = 1.f; uc_w = true;
+        } else {
+            rw.load(a.nrm + (long long)(rho_ok ? rho : 0) * D, x);
+            rw.normalize(x, WN, inv_w, uc_w);
+        }
         rw.load(a.rel + (long long)(rho_ok ? rho : 0) * D, x);
         rw.normalize(x, RN, inv_r, uc_r);
     }
@@ -215,10 +265,9 @@ __global__ __launch_bounds__(256) void shared_proj_emit_kernel(ProjEmitArgs a) {
         for (int kt = wave; kt < Tc; kt += 4) {
             const int id = a.cand[j * N + k0 + kt];
             const bool ok = id >= 0 && id < a.ent_total;
-            float x[V], xn[V], ax, inv;
+            float x[V], xt[V], xn[V], ax, inv;
             bool uc;
-            rw.load(a.ent + (long long)(ok ? id : 0) * D, x);
-            rw.project(x, WN, xn, ax, inv, uc);
+            rw.template gather_project<MODEL>(a.ent, a.entp, ok ? id : 0, WN, x, xt, xn, ax, inv, uc);
             if (!ok) {
 #pragma unroll
                 for (int c = 0; c < V; c++) xn[c] = 0.f;
@@ -238,12 +287,10 @@ __global__ __launch_bounds__(256) void shared_proj_emit_kernel(ProjEmitArgs a) {
             int sp[V], Ah[V], At[V];       // (the r count of a pair is -s as well: the positive's is Ah - At)
             float p_score;
             {
-                float x[V], Hn[V], Tn[V], ax, inv;
+                float x[V], xt[V], Hn[V], Tn[V], ax, inv;
                 bool uc;
-                rw.load(a.ent + (long long)(ids_ok ? h : 0) * D, x);
-                rw.project(x, WN, Hn, ax, inv, uc);
-                rw.load(a.ent + (long long)(ids_ok ? t : 0) * D, x);
-                rw.project(x, WN, Tn, ax, inv, uc);
+                rw.template gather_project<MODEL>(a.ent, a.entp, ids_ok ? h : 0, WN, x, xt, Hn, ax, inv, uc);
+                rw.template gather_project<MODEL>(a.ent, a.entp, ids_ok ? t : 0, WN, x, xt, Tn, ax, inv, uc);
                 float acc = 0.f;
 #pragma unroll
                 for (int c = 0; c < V; c++) {
@@ -304,7 +351,8 @@ __global__ __launch_bounds__(256) void shared_proj_emit_kernel(ProjEmitArgs a) {
                 GR[c] += Ah[c] - At[c] + v;
                 Ah[c] += v; At[c] -= v;
             }
-            float *rec_h = a.rec + b * (long long)D, *rec_t = a.rec + (a.n_pos + b) * (long long)D;
+            float *rec_h = a.rec + b * (long long)D, *rec_t = a.rec + (EW * a.n_pos + b) * (long long)D;
+            float *rec_hp = rec_h + a.n_pos * (long long)D, *rec_tp = rec_t + a.n_pos * (long long)D;       // TransD only
             if (a.n_tiles > 1) {      // (the lanes that stored a slot's counts are the ones that reload them)
                 if (tile > 0) {
                     int prev[V];
@@ -323,21 +371,22 @@ __global__ __launch_bounds__(256) void shared_proj_emit_kernel(ProjEmitArgs a) {
             }
             const bool nz_h = rw.any_nonzero(Ah), nz_t = rw.any_nonzero(At);
             if (nz_h) {
-                float x[V], xn[V], ax, inv;
+                float x[V], xt[V], xn[V], ax, inv;
                 bool uc;
-                rw.load(a.ent + (long long)h * D, x);
-                rw.project(x, WN, xn, ax, inv, uc);
-                rw.side_record(x, xn, ax, inv, uc, Ah, a.unit, WN, ACW, rec_h);
+                rw.template gather_project<MODEL>(a.ent, a.entp, h, WN, x, xt, xn, ax, inv, uc);
+                rw.template side_record<MODEL>(x, xt, xn, ax, inv, uc, Ah, a.unit, WN, ACW, rec_h, rec_hp);
             }
             if (nz_t) {
-                float x[V], xn[V], ax, inv;
+                float x[V], xt[V], xn[V], ax, inv;
                 bool uc;
-                rw.load(a.ent + (long long)t * D, x);
-                rw.project(x, WN, xn, ax, inv, uc);
-                rw.side_record(x, xn, ax, inv, uc, At, a.unit, WN, ACW, rec_t);
+                rw.template gather_project<MODEL>(a.ent, a.entp, t, WN, x, xt, xn, ax, inv, uc);
+                rw.template side_record<MODEL>(x, xt, xn, ax, inv, uc, At, a.unit, WN, ACW, rec_t, rec_tp);
             }
             any_ent = any_ent || nz_h || nz_t;
-            if (lane == 0) { a.dst[b] = nz_h ? h : -1; a.dst[a.n_pos + b] = nz_t ? t : -1; }
+            if (lane == 0) {
+                a.dst[b] = nz_h ? h : -1; a.dst[EW * a.n_pos + b] = nz_t ? t : -1;
+                if constexpr (TD) { a.dst[a.n_pos + b] = nz_h ? (int32_t)(E + h) : -1; a.dst[3 * a.n_pos + b] = nz_t ? (int32_t)(E + t) : -1; }
+            }
         }
         __syncthreads();
         // ---- the tile's candidate records: one wave each ----
@@ -353,13 +402,18 @@ __global__ __launch_bounds__(256) void shared_proj_emit_kernel(ProjEmitArgs a) {
             }
             const bool nz = n > 0 && rw.any_nonzero(G);
             if (nz) {
-                float x[V], xn[V];
+                float x[V], xt[V], xn[V];
                 rw.load(a.ent + (long long)id * D, x);
+                if constexpr (TD) rw.load(a.entp + (long long)id * D, xt);
                 rw.load_lds(crow + (size_t)kt * RS, xn);
-                rw.side_record(x, xn, ca[kt], cinv[kt], cuc[kt] != 0, G, a.unit, WN, ACW, a.rec + m * (long long)D);
+                rw.template side_record<MODEL>(x, xt, xn, ca[kt], cinv[kt], cuc[kt] != 0, G, a.unit, WN, ACW, a.rec + m * (long long)D,
+                                               a.rec + (m + ct_off) * (long long)D);
                 any_ent = true;
             }
-            if (lane == 0) a.dst[m] = nz ? id : -1;
+            if (lane == 0) {
+                a.dst[m] = nz ? id : -1;
+                if constexpr (TD) a.dst[m + ct_off] = nz ? (int32_t)(E + id) : -1;
+            }
         }
         __syncthreads();
     }
@@ -393,8 +447,11 @@ __global__ __launch_bounds__(256) void shared_proj_emit_kernel(ProjEmitArgs a) {
     if (any) {
 #pragma unroll
         for (int c = 0; c < V; c++) g[c] = ((f[0][c] + f[1][c]) + f[2][c]) + f[3][c];
-        rw.normalize_bwd(WN, g, inv_w, uc_w, out);
-        rw.store(a.rec + m_nrm * (long long)D, out);
+        if constexpr (TD) rw.store(a.rec + m_nrm * (long long)D, g);      // d/dr_p: r_p is used raw
+        else {
+            rw.normalize_bwd(WN, g, inv_w, uc_w, out);
+            rw.store(a.rec + m_nrm * (long long)D, out);
+        }
     }
     if (lane == 0) {
         const long long hub = a.hub_base + (j % a.hub_k) * 2LL * a.rel_total;
@@ -420,41 +477,39 @@ __global__ __launch_bounds__(256) void shared_proj_loss_kernel(const float *__re
 
 constexpr int kLdsBudget = 60 * 1024;   // per workgroup, as the TransE kernel's: two chunks per CU at the widest shapes
 
-// null: the shape is taken; otherwise the limit it breaks
-const char *float_shape_limit(const kge_model_desc &m, INT N) {
-    if (m.model == KGE_TRANSE) return "shared float records are built for TransH: TransE has its int8 records (kge_transe_emit_records_shared_chunks)";
-    if (m.model == KGE_TRANSD) return "shared float records are built for TransH: TransD needs its transfer rows as well and has no shared emit kernel";
-    if (m.model != KGE_TRANSH) return "shared float records are built for TransH: TransR has no shared emit kernel";
+// null: the shape is taken by the entry point built for `model` (KGE_TRANSH or KGE_TRANSD); otherwise the limit it breaks
+const char *float_shape_limit(const kge_model_desc &m, INT N, int model) {
+    if (model == KGE_TRANSD) {
+        if (m.model != KGE_TRANSD) return "shared float records with transfer rows are built for TransD (TransH: kge_transh_emit_records_shared_chunks; "
+                                          "TransE: kge_transe_emit_records_shared_chunks; TransR has no shared emit kernel)";
+    } else {
+        if (m.model == KGE_TRANSE) return "shared float records are built for TransH: TransE has its int8 records (kge_transe_emit_records_shared_chunks)";
+        if (m.model == KGE_TRANSD) return "shared float records are built for TransH: TransD needs its transfer rows as well (kge_transd_emit_records_shared_chunks)";
+        if (m.model != KGE_TRANSH) return "shared float records are built for TransH: TransR has no shared emit kernel";
+    }
     if (m.negative_rel != 0) return "shared negatives: relation negatives are not supported (negative_rel must be 0)";
     if (N < 1 || N > 63) return "shared negatives: 1..63 negatives per positive (a positive's count is within +-2N, an int8)";
-    if (m.ent_dim != m.rel_dim) return "shared negatives: TransH needs ent_dim == rel_dim";
+    if (m.ent_dim != m.rel_dim) return model == KGE_TRANSD ? "shared negatives: TransD needs ent_dim == rel_dim" : "shared negatives: TransH needs ent_dim == rel_dim";
     if (m.ent_dim < 1 || m.ent_dim > 512) return "shared negatives: the shared emit kernel holds embedding widths up to 512";
     return nullptr;
 }
 
-}  // namespace
-}  // namespace kge
-
-using namespace kge;
-
-extern "C" {
-
-int kge_shared_float_supported(const kge_model_desc *m, INT N) { return m && !float_shape_limit(*m, N) ? 1 : 0; }
-
-int kge_transh_emit_records_shared_chunks(const kge_model_desc *m, const float *const tables[KGE_MAX_TABLES], const int32_t *d_h2, const int32_t *d_t2,
-                                          const int32_t *d_r2, INT n_pos, INT stride, const int32_t *d_chunks, INT cap, const int32_t *d_cand, INT N,
-                                          const uint8_t *d_pair, INT denom, INT n_pos_total, float *d_rec, int32_t *d_dst, float *d_loss, void *stream_) {
-    const std::string w("kge_transh_emit_records_shared_chunks");
-    hipStream_t stream = (hipStream_t)stream_;
+// the body of both entry points; MODEL picks the instantiations and the record layout
+template <int MODEL>
+int emit_shared_chunks(const std::string &w, const kge_model_desc *m, const float *const tables[KGE_MAX_TABLES], const int32_t *d_h2, const int32_t *d_t2,
+                       const int32_t *d_r2, INT n_pos, INT stride, const int32_t *d_chunks, INT cap, const int32_t *d_cand, INT N, const uint8_t *d_pair,
+                       INT denom, INT n_pos_total, float *d_rec, int32_t *d_dst, float *d_loss, hipStream_t stream) {
+    constexpr bool TD = MODEL == KGE_TRANSD;
     if (!device_ok()) return fail(KGE_ERR_NO_DEVICE, w + ": no usable HIP device");
     if (!m) return fail(KGE_ERR_BAD_ARG, w + ": null argument");
-    if (const char *limit = float_shape_limit(*m, N)) return fail(KGE_ERR_UNSUPPORTED, limit);
-    if (!tables || !tables[0] || !tables[1] || !tables[2])
-        return fail(KGE_ERR_BAD_ARG, w + ": null table (ent_embeddings, rel_embeddings and normal_vectors are needed)");
+    if (const char *limit = float_shape_limit(*m, N, MODEL)) return fail(KGE_ERR_UNSUPPORTED, limit);
+    if (!tables || !tables[0] || !tables[1] || !tables[2] || (TD && !tables[3]))
+        return fail(KGE_ERR_BAD_ARG, w + (TD ? ": null table (ent_embeddings, rel_embeddings, rel_transfer and ent_transfer are needed)"
+                                             : ": null table (ent_embeddings, rel_embeddings and normal_vectors are needed)"));
     if (!d_chunks || cap < 0 || (cap < 1 && n_pos > 0)) return fail(KGE_ERR_BAD_ARG, w + ": bad arguments (a chunk table of at least one slot)");
     if (n_pos < 0 || stride < n_pos || denom <= 0 || n_pos_total < n_pos || !d_h2 || !d_t2 || !d_r2 || !d_cand || !d_pair || !d_rec || !d_dst || !d_loss)
         return fail(KGE_ERR_BAD_ARG, w + ": bad arguments");
-    const long long M = 2 * n_pos + cap * (N + 2);
+    const long long M = TD ? 4 * n_pos + cap * (2 * N + 2) : 2 * n_pos + cap * (N + 2);
     int64_t hub_base, hub_k, rows;
     float_record_hubs(*m, n_pos_total, N, hub_base, hub_k, rows);
     if (M >= (INT(1) << 31) || cap >= (INT(1) << 31) || rows >= (INT(1) << 31) - 1) return fail(KGE_ERR_UNSUPPORTED, "shared negatives: batch or row space too large");
@@ -464,7 +519,7 @@ int kge_transh_emit_records_shared_chunks(const kge_model_desc *m, const float *
     if (n_pos == 0) return hip_check(hipMemsetAsync(d_loss, 0, sizeof(float), stream), "zero loss");
     if ((rc = g_partials.reserve(cap, "shared negatives loss partials"))) return rc;
     ProjEmitArgs a = {};
-    a.ent = tables[0]; a.rel = tables[1]; a.nrm = tables[2];
+    a.ent = tables[0]; a.rel = tables[1]; a.nrm = tables[2]; a.entp = TD ? tables[3] : nullptr;
     a.h = d_h2; a.t = d_t2; a.r = d_r2; a.cand = d_cand; a.pair = d_pair; a.chunks = reinterpret_cast<const int2 *>(d_chunks);
     a.n_pos = n_pos; a.cap = cap; a.N = (int)N;
     a.D = m->ent_dim; a.RS = (a.D + 3) / 4 * 4;
@@ -472,7 +527,7 @@ int kge_transh_emit_records_shared_chunks(const kge_model_desc *m, const float *
     a.hub_base = hub_base; a.hub_k = (int)hub_k;
     a.rec = d_rec; a.dst = d_dst; a.partials = g_partials;
     // LDS: 32 bytes of wave slots, then per candidate its row, its byte fields and five words -- or, when that is less, the
-    // 32 RS bytes the closing fold of the four waves lays over the same space
+    // 32 RS bytes the closing fold of the four waves lays over the same space (TransD keeps no more per candidate than TransH)
     const int per_cand = a.RS * 5 + 20;
     const int t_max = (kLdsBudget - 32) / per_cand;     // 23 at width 512 (the TransE kernel: 21)
     a.n_tiles = ((int)N + t_max - 1) / t_max;
@@ -484,12 +539,36 @@ int kge_transh_emit_records_shared_chunks(const kge_model_desc *m, const float *
     for_team_shape(std::max(a.D, 129), [&](auto ts) {
         constexpr int Q = decltype(ts)::C / 4;
         if constexpr (decltype(ts)::L == 64 && Q <= 2) {
-            if (vec) hipLaunchKernelGGL((shared_proj_emit_kernel<Q, true>), grid, block, lds_bytes, stream, a);
-            else hipLaunchKernelGGL((shared_proj_emit_kernel<Q, false>), grid, block, lds_bytes, stream, a);
+            if (vec) hipLaunchKernelGGL((shared_proj_emit_kernel<MODEL, Q, true>), grid, block, lds_bytes, stream, a);
+            else hipLaunchKernelGGL((shared_proj_emit_kernel<MODEL, Q, false>), grid, block, lds_bytes, stream, a);
         }
     });
     hipLaunchKernelGGL(shared_proj_loss_kernel, dim3(1), dim3(256), 0, stream, (const float *)g_partials.ptr(), (long long)cap, a.unit, d_loss);
     return hip_check(hipGetLastError(), "shared projected emit launch");
+}
+
+}  // namespace
+}  // namespace kge
+
+using namespace kge;
+
+extern "C" {
+
+int kge_shared_float_supported(const kge_model_desc *m, INT N) { return m && !float_shape_limit(*m, N, KGE_TRANSH) ? 1 : 0; }
+int kge_shared_transd_supported(const kge_model_desc *m, INT N) { return m && !float_shape_limit(*m, N, KGE_TRANSD) ? 1 : 0; }
+
+int kge_transh_emit_records_shared_chunks(const kge_model_desc *m, const float *const tables[KGE_MAX_TABLES], const int32_t *d_h2, const int32_t *d_t2,
+                                          const int32_t *d_r2, INT n_pos, INT stride, const int32_t *d_chunks, INT cap, const int32_t *d_cand, INT N,
+                                          const uint8_t *d_pair, INT denom, INT n_pos_total, float *d_rec, int32_t *d_dst, float *d_loss, void *stream) {
+    return emit_shared_chunks<KGE_TRANSH>("kge_transh_emit_records_shared_chunks", m, tables, d_h2, d_t2, d_r2, n_pos, stride, d_chunks, cap, d_cand, N,
+                                          d_pair, denom, n_pos_total, d_rec, d_dst, d_loss, (hipStream_t)stream);
+}
+
+int kge_transd_emit_records_shared_chunks(const kge_model_desc *m, const float *const tables[KGE_MAX_TABLES], const int32_t *d_h2, const int32_t *d_t2,
+                                          const int32_t *d_r2, INT n_pos, INT stride, const int32_t *d_chunks, INT cap, const int32_t *d_cand, INT N,
+                                          const uint8_t *d_pair, INT denom, INT n_pos_total, float *d_rec, int32_t *d_dst, float *d_loss, void *stream) {
+    return emit_shared_chunks<KGE_TRANSD>("kge_transd_emit_records_shared_chunks", m, tables, d_h2, d_t2, d_r2, n_pos, stride, d_chunks, cap, d_cand, N,
+                                          d_pair, denom, n_pos_total, d_rec, d_dst, d_loss, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -68,14 +68,16 @@ def wants_sparse_rows(sparse_rows, ent_total, rel_total, width, batch_size, n_ne
 
 def plan(model_id, opt_method, sparse_rows, use_counts, counts_supported, ent_total, rel_total, width, batch_size, n_neg,
          sparse_threshold_bytes=None, adagrad_initial_accumulator=0.1, shared_chunk=0, negative_rel=0, by_relation=False, typed=False,
-         shared_float_supported=0):
+         shared_float_supported=0, shared_transd_supported=0):
     """The StepPlan of a configuration.  sparse_rows: None = automatic, True / False = the caller's wish; use_counts: the
     caller's wish; counts_supported: what kge_transe_counts_supported said for the model's descriptor and n_neg.
     shared_chunk: 0 = off; P > 0 = negatives shared by chunks of P positives (NON-PARITY, opt-in: Config.set_shared_negatives),
     which is the sparse-rows record step whatever the table size; negative_rel: how many of the n_neg are relation negatives;
     by_relation: the chunks are cut from the batch ordered by relation (train_paths.shared_grouped_step); typed: type-constrained
     sampling is on, which shared negatives take on such chunks only; shared_float_supported: what kge_shared_float_supported said
-    for the model's descriptor and the entity negatives (TransH on relation-grouped chunks, float gradient records)."""
+    for the model's descriptor and the entity negatives (TransH on relation-grouped chunks, float gradient records);
+    shared_transd_supported: what kge_shared_transd_supported said for them (TransD on such chunks, the same records with the
+    transfer rows)."""
     optimizer = optimizer_kind(opt_method)
     adam, lazy_adam, adagrad = optimizer == "adam", optimizer == "lazy_adam", optimizer == "adagrad"
     # LazyAdam -- opt-in, NON-PARITY: Adam on the touched rows only (tf.contrib.opt.LazyAdamOptimizer's rule) for tables whose dense
@@ -98,8 +100,8 @@ def plan(model_id, opt_method, sparse_rows, use_counts, counts_supported, ent_to
     rows = (bool(sparse) or rows_rule) and use_counts and not adam
     if shared_chunk:
         check_shared_negatives(model_id, optimizer, use_counts, shared_chunk, n_neg - negative_rel, negative_rel, by_relation, typed,
-                               shared_float_supported)
-        if model_id == TRANSH:      # float records, keyed in the unshared TransH step's row space: the touched-rows plan in place
+                               shared_float_supported, shared_transd_supported)
+        if model_id in (TRANSH, TRANSD):      # float records, keyed in the unshared step's row space: the touched-rows plan in place
             return StepPlan(optimizer, False, False, True, table_bytes)
         return StepPlan(optimizer, use_counts, True, False, table_bytes)      # its records go through the touched-rows reduce
     # TransH / TransD (and TransE outside the sign-count path) with SGD: the touched rows are updated in place from float
@@ -128,10 +130,11 @@ TYPED_NEEDS_BY_RELATION = ("a chunk of consecutive batch positions mixes relatio
 
 
 def check_shared_negatives(model_id, optimizer, use_counts, chunk, negative_ent, negative_rel, by_relation=False, typed=False,
-                           shared_float_supported=0):
+                           shared_float_supported=0, shared_transd_supported=0):
     """Raises KgeError, naming the limit, for a configuration the shared-negatives step cannot take.  by_relation: chunks cut from
     the batch ordered by relation; typed: candidates from the relations' type lists, which needs by_relation;
-    shared_float_supported: the library's answer for TransH on such chunks (kge_shared_float_supported), which needs no use_counts."""
+    shared_float_supported: the library's answer for TransH on such chunks (kge_shared_float_supported), which needs no use_counts;
+    shared_transd_supported: its answer for TransD on them (kge_shared_transd_supported), likewise."""
     if typed and not by_relation:
         raise KgeError("shared negatives cannot be combined with type-constrained sampling: " + TYPED_NEEDS_BY_RELATION)
     if not 1 <= int(chunk) <= SHARED_MAX_CHUNK:
@@ -141,7 +144,11 @@ def check_shared_negatives(model_id, optimizer, use_counts, chunk, negative_ent,
     if transh and not by_relation:
         raise KgeError("shared negatives on chunks by position are built for TransE only: TransH shares one normal vector per chunk, "
                        "which needs chunks of one relation -- set_shared_negatives(chunk, by_relation=True)")
-    if model_id != TRANSE and not transh:
+    transd = model_id == TRANSD and bool(shared_transd_supported)
+    if transd and not by_relation:
+        raise KgeError("shared negatives on chunks by position are built for TransE only: TransD shares one transfer vector per chunk, "
+                       "which needs chunks of one relation -- set_shared_negatives(chunk, by_relation=True)")
+    if model_id != TRANSE and not transh and not transd:
         raise KgeError("shared negatives are built for TransE only: TransH, TransD and TransR have no shared emit kernel")
     if negative_rel > 0:
         raise KgeError("shared negatives: relation negatives are not supported (negative_rel must be 0, got %d)" % negative_rel)
@@ -151,7 +158,7 @@ def check_shared_negatives(model_id, optimizer, use_counts, chunk, negative_ent,
     if optimizer == "adam":
         raise KgeError("shared negatives need SGD, LazyAdam or Adagrad: with TF1 Adam the dense count image has no entrance for "
                        "shared records yet")
-    if not use_counts and not transh:
+    if not use_counts and not transh and not transd:
         raise KgeError("shared negatives need TransE's sign-count path (use_counts, and a shape kge_transe_counts_supported accepts)")
 
 

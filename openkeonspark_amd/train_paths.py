@@ -557,13 +557,18 @@ def shared_grouped_step(con, dev, n_pos, stride, denom):
     TransH (the model is read from the Config): same order, same draw, same buffer names; the chunk's one normal vector and one
     r^ are shared too.  kge_transh_emit_records_shared_chunks writes 2 n_pos + cap (N + 2) FLOAT records -- h and t per position,
     the relation row, the normal vector and N candidates per chunk slot -- keyed in the row space of the unshared TransH step,
-    and the rows rule takes them as it takes that step's (RowsRule.apply_float_records)."""
+    and the rows rule takes them as it takes that step's (RowsRule.apply_float_records).
+    TransD: the same again with kge_transd_emit_records_shared_chunks and 4 n_pos + cap (2 N + 2) float records -- every entity
+    has a record for its ent_embeddings row and one for its ent_transfer row, the chunk slot one for rel_embeddings and one for
+    rel_transfer -- keyed in the row space of the unshared TransD step."""
     import torch
     P, N, D = con._shared_chunk, con.negative_ent, con.hidden_size
-    transh = con.trainModel.model_id == _lib.TRANSH
+    model_id = con.trainModel.model_id
+    float_rec = model_id in (_lib.TRANSH, _lib.TRANSD)      # the float-record models
+    ew = 2 if model_id == _lib.TRANSD else 1                # records per entity
     cap = shared_chunk_cap(n_pos, P, con.relTotal)
     cap_max = shared_chunk_cap(stride, P, con.relTotal)
-    m_cap = 2 * stride + cap_max * (N + 2) if transh else 3 * stride + cap_max * N
+    m_cap = 2 * ew * stride + cap_max * (ew * N + 2) if float_rec else 3 * stride + cap_max * N
     buf = con._sparse_buf
     if buf is None or "chunks" not in buf or buf.get("shared_cap", 0) < m_cap or buf["pair"].shape[0] < stride:
         d = con.device
@@ -574,7 +579,7 @@ def shared_grouped_step(con, dev, n_pos, stride, denom):
                    cand=torch.empty((cap_max, N), dtype=i32, device=d),
                    pair=torch.empty((stride, N), dtype=torch.uint8, device=d),
                    dst=torch.empty(m_cap, dtype=i32, device=d))
-        if transh:
+        if float_rec:
             buf.update(rec=torch.empty((m_cap, D), dtype=torch.float32, device=d))
         else:
             dw = int(con.lib.kge_transe_record_dwords(ctypes.byref(con._desc)))
@@ -590,11 +595,11 @@ def shared_grouped_step(con, dev, n_pos, stride, denom):
     _lib.check(L.kge_shared_order_by_relation(h, t, r, n_pos, P, buf["perm"].data_ptr(), h2, t2, r2, chunks, buf["n_chunks"].data_ptr(), st), L)
     _lib.check(L.kge_shared_negatives_draw_grouped(h2, t2, r2, n_pos, chunks, cap, N, 1 if con.type_constrained_sampling else 0,
                                                    con._shared_seed, con.global_step, cand, pair, st), L)
-    if transh:
-        M = 2 * n_pos + cap * (N + 2)
-        _lib.check(L.kge_transh_emit_records_shared_chunks(ctypes.byref(con._desc), con._tab_ptrs, h2, t2, r2, n_pos, stride, chunks, cap, cand,
-                                                           N, pair, denom, con.batch_size, buf["rec"].data_ptr(), buf["dst"].data_ptr(),
-                                                           con._loss.data_ptr(), st), L)
+    if float_rec:
+        M = 2 * ew * n_pos + cap * (ew * N + 2)
+        emit = L.kge_transd_emit_records_shared_chunks if model_id == _lib.TRANSD else L.kge_transh_emit_records_shared_chunks
+        _lib.check(emit(ctypes.byref(con._desc), con._tab_ptrs, h2, t2, r2, n_pos, stride, chunks, cap, cand, N, pair, denom, con.batch_size,
+                        buf["rec"].data_ptr(), buf["dst"].data_ptr(), con._loss.data_ptr(), st), L)
         buf["shared_step"], buf["shared_shape"], buf["shared_batch"] = con.global_step, (n_pos, cap), dev
         con._rule.apply_float_records(buf["rec"], buf["dst"], M, con.batch_size, N)
         con._rule.advance()
