@@ -129,8 +129,14 @@ const char *kge_version(void);
  *                        tables "ent_magic" / "rel_magic" (kge_index_copy), longer ones from two fp64 divisions.  Same draws; the
  *                        tables of an imported training set are rebuilt at once (tests lower it so that both ways run)
  *   "counts_fused_diag": measurement hook of the fused kernel (1: no record loops, 2: no row update);
- *                        any value but 0 gives WRONG results
- *   "counts_fused_cap":  test hook: rows of more than this many records take the image path (0 = the kernel's capacity)
+ *                        any value but 0 gives WRONG results.  With "counts_fused_tail" on, the teams of the image path still
+ *                        take their tickets at 2 and the last one resets the row's counters: the next step starts clean
+ *   "counts_fused_cap":  test hook: rows of more than this many records take the image path (0 = the default, 64)
+ *   "counts_fused_tail": 1 (default) = in the fused step the rows that go through the count image (entity rows with a list
+ *                        longer than the cap, and every relation row) are updated inside the fused kernel, by the last of
+ *                        the teams that add into the row's image, and no closing apply launch is made; byte 3 of
+ *                        "ride_shares" then rides in the fused kernel.  0 = the fused kernel, then the apply kernel over
+ *                        those rows.  Same bits.
  *   "inv_table_max_bytes": the TransE emit kernel reads 1/|row| from a per-row table rebuilt every step while
  *                        the two tables are at most this many bytes (default 256 MiB); larger tables (or 0)
  *                        compute the norms from the gathered rows

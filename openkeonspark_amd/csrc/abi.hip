@@ -261,6 +261,7 @@ int kge_set_option(const char *name, INT value) {
     if (n == "counts_fused") { engine().counts_fused = value != 0; return KGE_OK; }
     if (n == "counts_fused_diag") { engine().counts_fused_diag = (int)value; return KGE_OK; }
     if (n == "counts_fused_cap") { engine().counts_fused_cap = value > 0 ? (int)value : 0; return KGE_OK; }
+    if (n == "counts_fused_tail") { engine().counts_fused_tail = value != 0; return KGE_OK; }
     if (n == "inv_table_max_bytes") { engine().inv_table_max_bytes = value; return KGE_OK; }
     if (n == "tables_changed") { tables_written(); return KGE_OK; }     // the caller wrote device tables itself (value ignored)
     if (n == "counts_krel") { int k = 1; while (k * 2 <= value && k < 64) k *= 2; engine().counts_krel = k; return KGE_OK; }

@@ -124,7 +124,8 @@ struct Engine {
     int counts_fused = 1;       // kge_transe_train_step_counts: 1 = segmented sum and optimizer in one kernel (segapply_kernel); 0 = segsum + apply kernels
     int counts_fused_diag = 0;  // measurement hook, see SegApplyArgs::diag
     int typed_sampling = 0;     // kge_set_typed_sampling: entity negatives from the relation's type lists (sampler_dev.hpp typed_pick)
-    int counts_fused_cap = 0;   // test hook: rows of more than this many records go through the count image (0 = the kernel's capacity, 3 x team width)
+    int counts_fused_cap = 0;   // test hook: rows of more than this many records go through the count image (0 = the default, 64 records; never more than the kernel's capacity min(127, 4 x team width))
+    int counts_fused_tail = 1;  // fused single-process TransE step: 1 = the last segapply_kernel team to add into a row of the count image (hub entities, relation rows) applies that row, and the closing apply_counts_kernel launch is gone (transe_counts.hip, "the last arrival applies the row"); 0 = segapply + apply_counts, the step as it was (A/B runs, test reference)
 };
 
 Engine &engine();

@@ -60,6 +60,7 @@ struct CtWork {
     DevBuf<int4> pieces;
     DevBuf<int32_t> n_pieces;
     DevBuf<int2> row_span;
+    DevBuf<int32_t> expect, arrived;   // [E + R] each: arrivals planned / tickets taken per count-image row (SegPlan::expect), zero between steps
     // layout of the keys `dst` holds: keys_S > 0 = group-major, dst[b * keys_S + slot] of keys_n_pos groups (the fused step, option
     // "emit_keys_grouped"); 0 = slot-major, dst[slot * n_pos + b].  Every writer of dst goes through ensure_counts_work, which resets it.
     int keys_S = 0;
@@ -473,12 +474,27 @@ static void launch_bkt_scatter(const int32_t *dst, int n_tiles, int M, int rpb, 
 // homogeneous record lists).  A row with a list of more than `cap` records is cut into pieces of at most `cap` records of one
 // list (slots from one global counter, zeroed by the first launch of the sort), each piece a team of its own that adds into the count image.
 // rpb is even, so the two keys of a row lie in the same bucket.
+// expect != nullptr (engine option "counts_fused_tail"): the planner also counts, per row of the REAL row space [E + R], the
+// segapply_kernel teams that will arrive at the row's count image -- the pieces of both lists of a long row; one for a virtual
+// relation row that is not cut into pieces and has records, and one for EVERY copy-0 relation row that is not cut, records or not
+// (its team always arrives, so that every relation has at least one arrival and exactly one team that finds itself last).  The
+// copies of a relation lie in different buckets: a device-scope atomicAdd, read by segapply_kernel behind the kernel boundary.
 struct SegPlan {
-    int2 *row_span;        // [2 * virtual rows]
-    int4 *pieces;          // [max_pieces]  (key, first position, records, 0)
-    int32_t *n_pieces;
-    int cap;
+    int2 *row_span = nullptr;        // [2 * virtual rows]
+    int4 *pieces = nullptr;          // [max_pieces]  (key, first position, records, 0)
+    int32_t *n_pieces = nullptr;
+    int cap = 0;
+    int32_t *expect = nullptr;       // [E + R] arrivals planned per image row, all zero between steps (null: not counted)
+    int E = 0, R = 0;                // entity rows; relations (virtual row E + c R + r is copy c of relation r)
 };
+
+// the planner's count of segapply_kernel teams arriving at the image of virtual row `row`, whose lists hold c0 and c1 records
+__device__ __forceinline__ void plan_arrivals(const SegPlan &plan, int row, int c0, int c1) {
+    int n = 0;
+    if (c0 > plan.cap || c1 > plan.cap) n = (c0 + plan.cap - 1) / plan.cap + (c1 + plan.cap - 1) / plan.cap;
+    else if (row >= plan.E && (c0 + c1 > 0 || row - plan.E < plan.R)) n = 1;
+    if (n) atomicAdd(plan.expect + (row < plan.E ? row : plan.E + (row - plan.E) % plan.R), n);
+}
 
 // The part of the second level that both forms of the sort share: the pairs of bucket `row0 / rpb` are pair 0 .. end - start - 1 of
 // `fetch`; lds_h [rpb] is the histogram, then the running offsets.  The caller has made whatever fetch reads visible to the block.
@@ -488,7 +504,11 @@ __device__ __forceinline__ void bucket_rows_sort(int row0, int start, int end, i
     for (int i = threadIdx.x; i < rpb; i += 256) lds_h[i] = 0;
     if (end == start) {
         if constexpr (PLAN)
-            for (int i = threadIdx.x; i < rpb; i += 256) if (row0 + i < rows) plan.row_span[row0 + i] = make_int2(start, 0);
+            for (int i = threadIdx.x; i < rpb; i += 256)
+                if (row0 + i < rows) {
+                    plan.row_span[row0 + i] = make_int2(start, 0);
+                    if (plan.expect && !(i & 1)) plan_arrivals(plan, (row0 + i) >> 1, 0, 0);
+                }
         return;
     }
     const int n = end - start;
@@ -557,6 +577,7 @@ __device__ __forceinline__ void bucket_rows_sort(int row0, int start, int end, i
                 const int base = atomicAdd(plan.n_pieces, np);
                 for (int q = 0; q < np; q++) plan.pieces[base + q] = make_int4(key, start + lo + q * cap, min(cap, c - q * cap), 0);
             }
+            if (plan.expect && !(i & 1)) plan_arrivals(plan, key >> 1, c, co);     // once per row: at its even key (row0 is even)
         }
     }
 }
@@ -1732,7 +1753,16 @@ __global__ __launch_bounds__(256) void apply_counts_kernel(ApplyArgs a, SamplerA
 // ids and base addresses live in scalar registers (scalar loads, scalar address arithmetic), the vector unit only adds.
 //   * A row of more than `cap` records (hub entities) is cut into pieces by the planner; the pieces are further teams of this
 //     launch that add into the int32 count image with atomics, and so does every relation row (virtual copies fold onto one row;
-//     a hub relation has thousands of records).  apply_counts_kernel then runs over those rows only (row_span tells it which).
+//     a hub relation has thousands of records).
+//   * THE LAST ARRIVAL APPLIES THE ROW (engine option "counts_fused_tail", the default).  No single team knows when such a row's
+//     image is complete, so the planner counts the teams that will arrive at it (SegPlan::expect) and every team of the image
+//     path, its adds performed, takes a ticket from the row's `arrived` counter.  The team whose ticket is expect - 1 reads the
+//     sums back with atomic exchanges (which leave the image zero), resets both counters and calls apply_row_update with what
+//     apply_counts_kernel would have passed: same function, same integer sums, same bits.  Nobody waits for anybody: no team
+//     polls, spins or sleeps on a counter, so a lost arrival would be a row left as it was, never a hang.  The copy-0 team of
+//     a relation always arrives, with or without records: every relation row has an owner (TF1 Adam moves record-less rows, a
+//     hand-fed batch can leave residual-only ones), and whether it is the owner never depends on a counter another team resets.
+//     With the option at 0 apply_counts_kernel runs over those rows instead (row_span tells it which).
 // What this saves against segsum_kernel + apply_counts_kernel: the image traffic of nearly all rows (written, read, re-zeroed:
 // 35 MB of a bench step), the boundary atomics (a chunk of 64 sorted records there ends inside a row almost always), the key
 // comparisons per record, and three quarters of the record bytes.
@@ -1750,13 +1780,26 @@ struct SegApplyArgs {
     int RD, cap;
     int32_t *S;              // count image
     int fold_R;              // relations: row >= ap.E is copy (row - E) / fold_R of relation (row - E) % fold_R
-    int diag;                // measurement hook (option "counts_fused_diag"): 1 = no record loops, 2 = no row update (WRONG results)
+    int diag;                // measurement hook (option "counts_fused_diag"): 1 = no record loops, 2 = no row update (WRONG results;
+                             // the image path's teams still take their tickets and the last one resets the counters)
+    int32_t *expect;         // [E + R] teams that will arrive at a row's image (the planner's count); null: apply_counts_kernel follows
+    int32_t *arrived;        // [E + R] tickets taken so far; both all zero between steps
     ApplyArgs ap;
 };
 
-template <int L, int C>
-__global__ __launch_bounds__(256) void segapply_kernel(SegApplyArgs sa) {
+// TAIL: the form of option "counts_fused_tail" -- tickets, owners, and, as the launch that ends the step, a part of the next
+// batch's sampler in the workgroups from n_own on (n_own > 0, see apply_counts_kernel).  Without it the kernel is compiled
+// exactly as it was before there were owners.
+template <int L, int C, bool TAIL>
+__global__ __launch_bounds__(256) void segapply_kernel(SegApplyArgs sa, SamplerArgs ride = SamplerArgs(), int n_own = 0) {
     constexpr int TEAMS = 256 / L;
+    if constexpr (TAIL) {
+        if (n_own > 0 && (int)blockIdx.x >= n_own) {
+            __shared__ float bern_lds[kBernLds];
+            sample_block_ride(ride, (long long)blockIdx.x - n_own, bern_lds);
+            return;
+        }
+    }
     constexpr int Q = C / 4;
     constexpr int U = 16;             // records in flight per team
     constexpr int J = 128 / L > 0 ? (128 / L > 4 ? 4 : 128 / L) : 1;   // id registers per list: a list holds at most J * L records (the planner's cap)
@@ -1792,9 +1835,20 @@ __global__ __launch_bounds__(256) void segapply_kernel(SegApplyArgs sa) {
         const int4 sp = *reinterpret_cast<const int4 *>(sa.row_span + 2 * row);     // both lists of the row
         start8 = uni(sp.x); n8 = uni(sp.y); start2 = uni(sp.z); n2 = uni(sp.w);
         if (n8 > sa.cap || n2 > sa.cap) return;                                      // a long row: its pieces are teams of their own
-        if (n8 + n2 == 0 && (row >= ap.E || (ap.opt != kOptAdam && !ap.resid))) return;        // nothing to do (TF1 Adam moves record-less rows too)
+        // nothing to do (TF1 Adam moves record-less rows too; with tickets the copy-0 team of a relation always arrives)
+        const bool arrives = TAIL && row >= ap.E && row - (int)ap.E < sa.fold_R;
+        if (n8 + n2 == 0 && !arrives && (row >= ap.E || (ap.opt != kOptAdam && !ap.resid))) return;
     }
     const bool direct = !piece && row < ap.E;
+    // the row in the real row space [E + R]: image-path teams only, and in 32 bits (a 64-bit remainder here stood in front of
+    // every team's first loads)
+    int irow = row;
+    if (!direct && row >= ap.E) irow = (int)ap.E + (int)((unsigned)(row - (int)ap.E) % (unsigned)sa.fold_R);
+    // An image-path team asks now how many arrivals the planner counted for its row.  The count was written before this launch
+    // and is reset only by the row's last arrival, after every team has taken its ticket -- and a team takes its ticket behind a
+    // wait that covers this load: a plain load, in flight with the record ids.
+    int want = 0;
+    if constexpr (TAIL) { if (!direct) want = sa.expect[irow]; }
     float x[C], mo[C], vo[C];
     if (direct) {                      // requested now, needed after the records
         tm.load(ap.p, row, x);
@@ -1887,7 +1941,7 @@ __global__ __launch_bounds__(256) void segapply_kernel(SegApplyArgs sa) {
     int si[C];
 #pragma unroll
     for (int c = 0; c < C; c++) { const int e = lane + L * c; si[c] = e < ap.D ? stage[e] : 0; }
-    if (sa.diag & 2) return;
+    if ((sa.diag & 2) && (direct || !TAIL)) return;
     if (direct) {
         float sf[C], rs[C];
         float *rp = ap.resid ? ap.resid + (long long)row * ap.D : nullptr;
@@ -1895,10 +1949,47 @@ __global__ __launch_bounds__(256) void segapply_kernel(SegApplyArgs sa) {
         for (int c = 0; c < C; c++) { const int e = lane + L * c; sf[c] = (float)si[c]; rs[c] = (rp && e < ap.D) ? rp[e] : 0.f; }
         apply_row_update<L, C, false>(tm, ap, ap.p, ap.m, ap.v, row, row, sf, rs, x, mo, vo, true, nullptr, rp);
     } else {
-        const long long irow = row < ap.E ? row : ap.E + (row - ap.E) % sa.fold_R;
-        int32_t *p = sa.S + irow * ap.D;
+        int32_t *p = sa.S + (long long)irow * ap.D;
+        if (!(sa.diag & 2)) {
 #pragma unroll
-        for (int c = 0; c < C; c++) { const int e = lane + L * c; if (e < ap.D && si[c] != 0) atomicAdd(p + e, si[c]); }
+            for (int c = 0; c < C; c++) { const int e = lane + L * c; if (e < ap.D && si[c] != 0) atomicAdd(p + e, si[c]); }
+        }
+        if constexpr (!TAIL) return;
+        // ---- the last arrival applies the row.
+        // HARDWARE ASSUMPTION (gfx950, the one finish_loss makes, models_dev.hpp): agent-scope atomics are performed at the memory
+        // side and each stays counted in vmcnt until it has been, so behind s_waitcnt vmcnt(0) this team's adds are part of the
+        // image before its ticket is taken.  The image is touched by nothing but atomics inside this launch (these adds, the
+        // owner's exchanges), which never leave a copy in an XCD's L2: no release fence, no write-back.  The row's p / m / v /
+        // residual rows are read and written by its owner alone in this launch: plain loads and stores.
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // (the clobber also keeps the compiler from moving the ticket above the adds)
+        int ticket = 0;
+        if (lane == 0) ticket = __hip_atomic_fetch_add(sa.arrived + irow, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if constexpr (L == 64) ticket = __builtin_amdgcn_readfirstlane(ticket); else ticket = __shfl(ticket, 0, L);
+        if (ticket != want - 1) return;
+        if (lane == 0) {      // both counters back to zero for the next step: this was the row's last arrival
+            __hip_atomic_store(sa.arrived + irow, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __hip_atomic_store(sa.expect + irow, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+        if (sa.diag & 2) return;
+        const bool ent = row < ap.E;
+        const long long trow = ent ? row : irow - ap.E;     // the row in its own table
+        float *rt = ent ? ap.resid : ap.resid2;
+        float *rp = rt ? rt + trow * ap.D : nullptr;
+        float *table = ent ? ap.p : ap.p2, *mt = ent ? ap.m : ap.m2, *vt = ent ? ap.v : ap.v2;
+        const bool every_row = ap.opt == kOptAdam;       // as in apply_counts_kernel: the rows are requested together with the sums
+        if (every_row) { tm.load(table, trow, x); tm.load(mt, trow, mo); tm.load(vt, trow, vo); }
+        int sv[C];
+        float sf[C], rs[C];
+#pragma unroll
+        for (int c = 0; c < C; c++) {     // the exchange reads the sums where the adds were performed and leaves the image zero
+            const int e = lane + L * c;
+            sv[c] = 0;
+            if (e < ap.D) sv[c] = atomicExch(p + e, 0);
+            rs[c] = (rp && e < ap.D) ? rp[e] : 0.f;
+        }
+#pragma unroll
+        for (int c = 0; c < C; c++) sf[c] = (float)sv[c];    // (converted behind the loop: all exchanges are in flight together)
+        apply_row_update<L, C, false>(tm, ap, table, mt, vt, trow, irow, sf, rs, x, mo, vo, every_row, nullptr, rp);
     }
 }
 
@@ -2009,31 +2100,48 @@ static int forward_counts_impl(const kge_model_desc *m, const float *d_ent, cons
         if ((rc = g_c.n_pieces.reserve(1, "fused step piece counter", &grew))) return rc;
         if (grew && (rc = hip_check(hipMemset(g_c.n_pieces, 0, sizeof(int32_t)), "zero piece counter"))) { g_c.n_pieces.free(); return rc; }
         if ((rc = g_c.row_span.reserve(rows2, "fused step row spans"))) return rc;
+        const long long all_rows = m->ent_total + m->rel_total;
+        // the last arrival at a row's image applies it, and no apply launch follows (option "counts_fused_tail")
+        const bool tail = engine().counts_fused_tail != 0;
+        if (tail) {
+            DevBuf<int32_t> *const cnt[2] = {&g_c.expect, &g_c.arrived};
+            for (int i = 0; i < 2; i++) {
+                if ((rc = cnt[i]->reserve(all_rows, "fused step arrival counters", &grew))) return rc;
+                // (on the step's stream: in front of the planner that adds to them)
+                if (grew && (rc = hip_check(hipMemsetAsync(cnt[i]->ptr(), 0, sizeof(int32_t) * (size_t)all_rows, stream), "zero arrival counters"))) { cnt[i]->free(); return rc; }
+            }
+        }
         SegPlan plan;
         plan.row_span = g_c.row_span; plan.pieces = g_c.pieces; plan.n_pieces = g_c.n_pieces; plan.cap = cap;
+        if (tail) { plan.expect = g_c.expect; plan.E = (int)m->ent_total; plan.R = (int)m->rel_total; }
         const int32_t *n_valid_p;
         const KeyMap km = key_map_for((int)(3 + n_neg), n_pos);
         if ((rc = bucket_sort_records(g_c.dst, M, rows2, rpb2, &plan, stream, n_valid_p, grouped ? &km : nullptr))) return rc;
-        const long long all_rows = m->ent_total + m->rel_total;
         SegApplyArgs sa = {};
         sa.rec = g_c.rec; sa.rec2_off = (unsigned)((size_t)3 * (size_t)n_pos * rd * 4); sa.ids = g_c.ids_sorted; sa.row_span = g_c.row_span;
         sa.pieces = g_c.pieces; sa.n_pieces = g_c.n_pieces;
         sa.n8 = (int)(3 * n_pos); sa.m_last = (int)M - 1; sa.n_rows_v = rows; sa.RD = (int)rd; sa.cap = cap; sa.S = d_counts; sa.fold_R = (int)m->rel_total; sa.diag = engine().counts_fused_diag;
+        if (tail) { sa.expect = g_c.expect; sa.arrived = g_c.arrived; }
         ApplyArgs &a = sa.ap;
         a.p = fo->p[0]; a.p2 = fo->p[1]; a.resid = d_resid_ent; a.resid2 = d_resid_rel;
         if (fo->adam) { a.m = fo->m[0]; a.m2 = fo->m[1]; a.v = fo->v[0]; a.v2 = fo->v[1]; }
         a.S = d_counts; a.rows = all_rows; a.row_lo = 0; a.E = m->ent_total; a.D = D;
         a.unit = 1.0f / (float)denom; a.lr = fo->lr; a.b1 = fo->b1; a.b2 = fo->b2; a.eps = fo->eps; a.opt = fo->adam ? kOptAdam : kOptSgd;
         a.row_span = g_c.row_span; a.span_cap = cap;
-        a.inv_out = inv_table_kept(true, fo->p[0], fo->p[1], all_rows);   // (the two kernels together rewrite every row's 1/|row| entry)
+        a.inv_out = inv_table_kept(true, fo->p[0], fo->p[1], all_rows);   // (the step rewrites every row's 1/|row| entry: segapply's direct teams and its owners, or the apply kernel behind it)
         const bool shaped = for_transe_team_shape(D, [&](auto t) {
             constexpr int L = decltype(t)::L, C = decltype(t)::C;
             if constexpr (C >= 4) {   // natural-layout records only: the ladder starts at (16, 4)
                 const long long nb = ((long long)rows + max_pieces + (256 / L) - 1) / (256 / L);
-                hipLaunchKernelGGL((segapply_kernel<L, C>), dim3((unsigned)nb), dim3(256), 0, stream, sa);
+                SamplerArgs ride = {};
+                if (tail) {      // the launch that ends the step: it takes what the sort's launches left of an armed sampler
+                    const unsigned n_ride = take_ride(ride, 3);
+                    hipLaunchKernelGGL((segapply_kernel<L, C, true>), dim3((unsigned)nb + n_ride), dim3(256), 0, stream, sa, ride, (int)nb);
+                    return;
+                }
+                hipLaunchKernelGGL((segapply_kernel<L, C, false>), dim3((unsigned)nb), dim3(256), 0, stream, sa, ride, 0);
                 long long nb2 = (all_rows + (256 / L) - 1) / (256 / L);
                 if (nb2 > 8192) nb2 = 8192;
-                SamplerArgs ride = {};
                 const unsigned n_ride = take_ride(ride, 3);
                 hipLaunchKernelGGL((apply_counts_kernel<L, C, false>), dim3((unsigned)nb2 + n_ride), dim3(256), 0, stream, a, ride, (int)nb2);
             }
