@@ -842,6 +842,49 @@ int kge_transd_emit_records_shared_chunks(const kge_model_desc *m, const float *
                                           int32_t *d_dst, float *d_loss, void *stream);
 int kge_shared_transd_supported(const kge_model_desc *m, INT N);
 
+/* ---- TransR on relation-grouped chunks (NON-PARITY, opt-in; csrc/shared_transr.hip, the row GEMMs of csrc/transr.hip) ----
+ * A chunk of one relation has ONE matrix M_rho, so its 2 len positive rows and its N candidates are projected once each: a chunk
+ * of P positives puts 2 P + N rows through the three row GEMMs (12 De Dr FLOPs a row) where the unshared step puts P (2 + N).
+ *   Order, draw, mask.  Exactly those of "TransH on relation-grouped chunks": kge_shared_order_by_relation and
+ *               kge_shared_negatives_draw_grouped are called unchanged, and cap, the candidates, their sides, the masks, the typed
+ *               lists and the loss denominator are theirs.  b is the SORTED position throughout.
+ *   Forward.    Chunk j has the relation rho of its first position (rho outside [0, rel_total): the chunk takes no part).
+ *               l2n(x) = x / sqrt(max(sum x^2, 1e-12)).  r^ = l2n(rel_embeddings[rho]); for an entity row x: x^ = l2n(x . M_rho),
+ *               M_rho = transfer_matrix[rho] as [ent_dim][rel_dim] (TransR.py:16-23; with negative_rel == 0 every negative takes
+ *               the positive's matrix, TransR.py:57-60).  p_b = sum |h^_b + r^ - t^_b|.  For the pair (b, k): e = c^_k + r^ - t^_b
+ *               for a new head, h^_b + r^ - c^_k for a new tail; v = p_b - sum |e| + margin.  The pair is ACTIVE when it is
+ *               unmasked, h_b, t_b and the candidate id lie in [0, ent_total), and v >= 0 (a tie is active; sign(0) = 0: the
+ *               rules of transr_vec_kernel).  loss = (1 / denom) sum over the active pairs of v; masked pairs stay in the
+ *               denominator.
+ *   Backward.   The gradients with respect to the NORMALISED PROJECTED vectors are the integer sign counts of the TransE / TransH
+ *               definition: G(c^_k), G(h^_b), G(t^_b), and the chunk's G_r as an int32.  With unit = 1 / denom a row's GP row
+ *               (width rel_dim) is normalize_bwd(x^, unit G) = inv (unit G - [the norm was not clipped] (x^ . unit G) x^),
+ *               inv = 1 / |x . M_rho|; a row with a zero count vector, an invalid id or an inactive chunk has a zero GP row.
+ *               ent_embeddings[id] += GP . M_rho^T per row, transfer_matrix[rho] += sum over the chunk's rows of x^T GP,
+ *               rel_embeddings[rho] += normalize_bwd(r^, unit G_r).
+ *   Rows.       J = 2 n_pos + cap N rows, chunk-major: slot c begins at row 2 first_c + c N and holds its len head rows, its len
+ *               tail rows, then its N candidates (the used slots come first, in position order, and cover the positions without a
+ *               gap, so no scan is needed; the slots are in relation order, so the rows are).  A slot of length 0, of a length above
+ *               127, one that points outside [0, n_pos) or one whose relation lies outside the table owns no row; a row no slot
+ *               owns has the key rel_total, the bucket the GEMMs skip, and a zero GP row.
+ * kge_transr_forward_backward_shared_chunks: job list -> projection -> pair walk -> dgrad -> wgrad, ADDING into the dense gradient
+ *   tables grads[0..2] (ent_embeddings, rel_embeddings, transfer_matrix) exactly as kge_forward_backward does for TransR; the
+ *   chunk count stays on the device and the call has no host synchronisation.  The GEMM kernels are the unshared plain layout's,
+ *   chosen by the same dimension rules and sized by J; dgrad takes its float-record mode by the existing size rule.  The pair walk
+ *   is one workgroup of four waves per chunk slot; the loss partials are summed over all cap slots in index order (the loss is
+ *   reproducible bit for bit), the relation row's gradient, dgrad below its record size and wgrad are fp32 atomics (the gradient
+ *   tables are reproducible to rounding, not bit for bit).  d_h2 / d_t2 / d_r2: the sorted positives; stride >= n_pos; denom:
+ *   batch_size * N of the whole step.  n_pos == 0 zeroes the loss and touches no gradient.  KGE_ERR_UNSUPPORTED, naming the limit:
+ *   another model, negative_rel > 0, N outside 1..63, rel_dim above 512, more than 2^31 - 1 rows.
+ * kge_shared_transr_supported: 1 where that entry point takes the model and N (TransR, negative_rel == 0, 1 <= N <= 63,
+ *   1 <= rel_dim <= 512, ent_dim >= 1), else 0; 0 for a null descriptor.  Host only.  (The TransH and TransD answers stay 0 for
+ *   TransR.) */
+int kge_transr_forward_backward_shared_chunks(const kge_model_desc *m, const float *const tables[KGE_MAX_TABLES], const int32_t *d_h2,
+                                              const int32_t *d_t2, const int32_t *d_r2, INT n_pos, INT stride, const int32_t *d_chunks, INT cap,
+                                              const int32_t *d_cand, INT N, const uint8_t *d_pair, INT denom, float *const grads[KGE_MAX_TABLES],
+                                              float *d_loss, void *stream);
+int kge_shared_transr_supported(const kge_model_desc *m, INT N);
+
 /* ---- Table-sharded sparse path (N GPUs, BASELINE config #5): rank g OWNS the entity rows [g*chunk, (g+1)*chunk); what the
  * reference does with ps tasks holding the variables and workers pulling rows / pushing IndexedSlices over gRPC
  * (distribute_training.py:193-196) becomes: request ids -> all-to-all -> owners gather rows -> all-to-all -> emit records

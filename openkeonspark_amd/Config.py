@@ -169,7 +169,10 @@ class Config(object):
         relation-grouped chunks").  TransD trains the same way (by_relation=True only, widths up to 512, the same three
         optimizers): a chunk shares r^ and its relation's raw transfer vector, an entity's two rows are gathered once per chunk, and
         every entity writes two float records, one for its ent_embeddings row and one for its ent_transfer row ("TransD on
-        relation-grouped chunks").  TransR stays refused."""
+        relation-grouped chunks").  TransR trains the same way (by_relation=True only, rel_dim up to 512; SGD, Adagrad or TF1 Adam,
+        not LazyAdam): a chunk shares its relation's matrix, so 2 chunk + N rows go through the projection, dgrad and wgrad GEMMs
+        where the unshared step puts chunk (2 + N), and the gradients are the dense tables of the unshared TransR step ("TransR on
+        relation-grouped chunks")."""
         if self.trainModel is not None:
             raise KgeError("set_shared_negatives must be called before set_model_and_session: it decides the step's path")
         chunk = int(chunk)
@@ -476,7 +479,8 @@ class Config(object):
             shared_chunk=self._shared_chunk, negative_rel=self.negative_rel, by_relation=self._shared_by_relation,
             typed=bool(self._shared_chunk and self.type_constrained_sampling),
             shared_float_supported=self.lib.kge_shared_float_supported(ctypes.byref(probe.descriptor()), self.negative_ent),
-            shared_transd_supported=self.lib.kge_shared_transd_supported(ctypes.byref(probe.descriptor()), self.negative_ent))
+            shared_transd_supported=self.lib.kge_shared_transd_supported(ctypes.byref(probe.descriptor()), self.negative_ent),
+            shared_transr_supported=self.lib.kge_shared_transr_supported(ctypes.byref(probe.descriptor()), self.negative_ent))
         self.use_counts, self.sparse_rows, self.sparse_inplace = p.use_counts, p.sparse_rows, p.sparse_inplace
         self._adam, self._lazy_adam, self._adagrad = p.adam, p.lazy_adam, p.adagrad
         self._has_slots, self._rows_rule = p.has_slots, p.rows_rule

@@ -192,6 +192,10 @@ def _declare(L):
     # ... and TransD (the same kernel with the transfer rows; all four tables are read)
     L.kge_shared_transd_supported.argtypes = [ctypes.POINTER(ModelDesc), i64]
     L.kge_transd_emit_records_shared_chunks.argtypes = L.kge_transh_emit_records_shared_chunks.argtypes
+    # ... and TransR: job list -> projection -> pair walk -> dgrad -> wgrad into the dense gradient tables (csrc/shared_transr.hip)
+    L.kge_shared_transr_supported.argtypes = [ctypes.POINTER(ModelDesc), i64]
+    L.kge_transr_forward_backward_shared_chunks.argtypes = [ctypes.POINTER(ModelDesc), tabs, vp, vp, vp, i64, i64, vp, i64, vp, i64, vp, i64, tabs,
+                                                            vp, vp]
     L.kge_transe_apply_counts_range.argtypes =[ctypes.POINTER(ModelDesc), vp, vp, vp, vp, vp, i64, i64, i64, i32, f32, f32, f32, f32, vp]
     # table-sharded sparse path (csrc/shard.hip)
     L.kge_shard_requests.argtypes = [vp, vp, vp, i64, i64, i64, vp, vp]

@@ -96,6 +96,7 @@ struct Engine {
     int transr_bf16x3 = 1;      // TransR row GEMMs (projection, dgrad): fp32 products as six bf16 x bf16 term products of an exact three-term split, on the bf16 matrix pipe (transr.hip rows_gemm3_kernel); 0 = the fp32 MFMA kernels
     int transr_groups = 1;      // TransR, device-sampled batches, 2 + n <= 16: groups (not jobs) sorted by relation, a group's rows side by side in one 16-row sub-tile (transr.hip GemmArgs); 1 = steps with well-filled buckets, 2 = always, 0 = never
     int transr_fuse_vec = 1;    // group layout: the vector stage inside the projection's epilogue (0: transr_vec_kernel on P)
+    int shared_transr_stages = 5;   // measurement hook: kge_transr_forward_backward_shared_chunks stops behind this many of its stages (job list, projection, pair walk, dgrad, wgrad); 5 = the whole step
     int transr_lean = 1;        // TransR vector stage: the float4-per-lane kernel that also zero-fills GP (0 = generic fwdbwd_kernel + memset)
     int pair_counts = 1;        // TransH / TransD: int8 sign records keyed by (entity, relation) + per-pair backward (pairs.hip) instead of float records
     int pair_counts_min_neg = 0;   // ... from this many negatives per positive; 0 = the measured cross-over (TransH 5, TransD 3)
@@ -239,6 +240,22 @@ int launch_predict(const kge_model_desc &m, const float *const tables[4], const 
 // relation (a group is one 32-row tile of the projection; transr.hip)
 int launch_predict_transr_grouped(const kge_model_desc &m, const float *const tables[4], const int32_t *d_h, const int32_t *d_t,
                                   const int32_t *d_r, int64_t n, float *d_out, hipStream_t stream);
+// TransR on relation-grouped chunks (shared_transr.hip): the caller writes a job list of J rows ALREADY in relation order -- row p
+// is slot p: keys[p] = its matrix relation (rel_total = a row the GEMMs skip), slots[p] = p, job_ent[p] = its entity, rec_dst[p] = -1
+// where dgrad runs in float-record mode (rec_dst non-null) -- and GP between the projection and dgrad.  The launches are the plain
+// layout's, chosen by the dimensions and sized by J (transr.hip).
+struct TransrSharedRows {
+    float *P, *GP;                     // [J][rel_dim]
+    int32_t *keys, *slots, *job_ent;   // [J]
+    float *drec;                       // dgrad's float records, null = fp32 atomics
+    int32_t *rec_dst;
+};
+int transr_shared_workspace(const kge_model_desc &m, int64_t J, TransrSharedRows &w);
+int launch_transr_shared_project(const kge_model_desc &m, const float *const tables[4], const TransrSharedRows &w, int64_t J, hipStream_t stream);
+int launch_transr_shared_dgrad(const kge_model_desc &m, const float *const tables[4], float *const grads[4], const TransrSharedRows &w, int64_t J,
+                               hipStream_t stream);
+int launch_transr_shared_wgrad(const kge_model_desc &m, const float *const tables[4], float *const grads[4], const TransrSharedRows &w, int64_t J,
+                               hipStream_t stream);
 int launch_lp_table(const kge_model_desc &m, const float *const tables[4], const float *P_all, int64_t r, float *T, hipStream_t stream);
 int launch_lp_scores(const kge_model_desc &m, const float *const tables[4], const float *T, int64_t r, const int32_t *d_req_fixed,
                      const int32_t *d_req_head, int64_t n_req, float *d_scores, hipStream_t stream);

@@ -31,6 +31,7 @@
 #include "engine.hpp"
 #include "team.hpp"
 #include "team_shape.hpp"
+#include "wave_row.hpp"
 
 namespace kge {
 namespace {
@@ -54,144 +55,6 @@ struct ProjEmitArgs {
     int32_t *dst;
     float *partials;
     const float *entp;               // TransD: ent_transfer
-};
-
-__device__ __forceinline__ int sgn_i(float e) { return (e > 0.f ? 1 : 0) - (e < 0.f ? 1 : 0); }
-
-// A wave's view of one row of width D: lane l holds elements 4 (l + 64 q) .. + 3, q < Q; elements from D on are zero.
-template <int Q, bool VEC>
-struct WaveRow {
-    static constexpr int V = 4 * Q;
-    int lane, D, RS;
-    __device__ __forceinline__ bool has(int q) const { return 4 * (lane + 64 * q) < RS; }
-    template <typename T>
-    __device__ __forceinline__ void load(const T *__restrict__ p, T (&x)[V]) const {
-        typedef T T4 __attribute__((ext_vector_type(4)));
-#pragma unroll
-        for (int q = 0; q < Q; q++) {
-            const int e0 = 4 * (lane + 64 * q);
-            if constexpr (VEC) {
-                T4 v = {0, 0, 0, 0};
-                if (has(q)) v = *reinterpret_cast<const T4 *>(p + e0);
-                x[4 * q] = v.x; x[4 * q + 1] = v.y; x[4 * q + 2] = v.z; x[4 * q + 3] = v.w;
-            } else {
-#pragma unroll
-                for (int i = 0; i < 4; i++) x[4 * q + i] = e0 + i < D ? p[e0 + i] : T(0);
-            }
-        }
-    }
-    template <typename T>
-    __device__ __forceinline__ void store(T *__restrict__ p, const T (&x)[V]) const {
-        typedef T T4 __attribute__((ext_vector_type(4)));
-#pragma unroll
-        for (int q = 0; q < Q; q++) {
-            const int e0 = 4 * (lane + 64 * q);
-            if constexpr (VEC) {
-                if (has(q)) { T4 v = {x[4 * q], x[4 * q + 1], x[4 * q + 2], x[4 * q + 3]}; *reinterpret_cast<T4 *>(p + e0) = v; }
-            } else {
-#pragma unroll
-                for (int i = 0; i < 4; i++) if (e0 + i < D) p[e0 + i] = x[4 * q + i];
-            }
-        }
-    }
-    // rows in LDS have stride RS and zeros from D on: one 16-byte access per q at every width
-    template <typename T>
-    __device__ __forceinline__ void load_lds(const T *p, T (&x)[V]) const {
-        typedef T T4 __attribute__((ext_vector_type(4)));
-#pragma unroll
-        for (int q = 0; q < Q; q++) {
-            T4 v = {0, 0, 0, 0};
-            if (has(q)) v = *reinterpret_cast<const T4 *>(p + 4 * (lane + 64 * q));
-            x[4 * q] = v.x; x[4 * q + 1] = v.y; x[4 * q + 2] = v.z; x[4 * q + 3] = v.w;
-        }
-    }
-    template <typename T>
-    __device__ __forceinline__ void store_lds(T *p, const T (&x)[V]) const {
-        typedef T T4 __attribute__((ext_vector_type(4)));
-#pragma unroll
-        for (int q = 0; q < Q; q++)
-            if (has(q)) { T4 v = {x[4 * q], x[4 * q + 1], x[4 * q + 2], x[4 * q + 3]}; *reinterpret_cast<T4 *>(p + 4 * (lane + 64 * q)) = v; }
-    }
-    __device__ __forceinline__ float dot(const float (&a)[V], const float (&b)[V]) const {
-        float s = 0.f;
-#pragma unroll
-        for (int c = 0; c < V; c++) s = __builtin_fmaf(a[c], b[c], s);
-        return team_sum<64>(s);
-    }
-    // Team::normalize / normalize_bwd (team.hpp) in this layout: x rsqrt(max(sum x^2, 1e-12)); clipped: the backward is inv * gy
-    __device__ __forceinline__ void normalize(const float (&x)[V], float (&y)[V], float &inv, bool &unclipped) const {
-        const float ss = dot(x, x);
-        unclipped = ss >= 1e-12f;
-        inv = 1.0f / sqrtf(unclipped ? ss : 1e-12f);
-#pragma unroll
-        for (int c = 0; c < V; c++) y[c] = x[c] * inv;
-    }
-    __device__ __forceinline__ void normalize_bwd(const float (&y)[V], const float (&gy)[V], float inv, bool unclipped, float (&gx)[V]) const {
-        float d = dot(y, gy);
-        if (!unclipped) d = 0.f;
-#pragma unroll
-        for (int c = 0; c < V; c++) gx[c] = inv * (gy[c] - d * y[c]);
-    }
-    // side_project<MODEL> (models_dev.hpp).  TransH: a = x . w^, x^ = l2n(x - a w^), cw = w^ (xt is not read).
-    // TransD: a = x . x_p, x^ = l2n(x + a r_p), xt = x_p, cw = r_p
-    template <int MODEL>
-    __device__ __forceinline__ void project(const float (&x)[V], const float (&xt)[V], const float (&cw)[V], float (&xn)[V], float &a, float &inv,
-                                            bool &unclipped) const {
-        float xp[V];
-        if constexpr (MODEL == KGE_TRANSD) {
-            a = dot(x, xt);
-#pragma unroll
-            for (int c = 0; c < V; c++) xp[c] = x[c] + a * cw[c];
-        } else {
-            a = dot(x, cw);
-#pragma unroll
-            for (int c = 0; c < V; c++) xp[c] = x[c] - a * cw[c];
-        }
-        normalize(xp, xn, inv, unclipped);
-    }
-    // row `id` of the entity table (TransD: and of ent_transfer), projected and normalised
-    template <int MODEL>
-    __device__ __forceinline__ void gather_project(const float *__restrict__ ent, const float *__restrict__ entp, long long id, const float (&cw)[V],
-                                                   float (&x)[V], float (&xt)[V], float (&xn)[V], float &a, float &inv, bool &unclipped) const {
-        load(ent + id * D, x);
-        if constexpr (MODEL == KGE_TRANSD) load(entp + id * D, xt);
-        project<MODEL>(x, xt, cw, xn, a, inv, unclipped);
-    }
-    __device__ __forceinline__ bool any_nonzero(const int (&g)[V]) const {
-        int o = 0;
-#pragma unroll
-        for (int c = 0; c < V; c++) o |= g[c];
-        return __ballot(o != 0) != 0;
-    }
-    // side_backward<MODEL> of unit * G: the row's gradient record (TransD: and its transfer row's, into out_t), and its share of
-    // d/dw^ (TransD: d/dr_p) into acw
-    template <int MODEL>
-    __device__ __forceinline__ void side_record(const float (&x)[V], const float (&xt)[V], const float (&xn)[V], float a, float inv, bool unclipped,
-                                                const int (&G)[V], float unit, const float (&cw)[V], float (&acw)[V], float *__restrict__ out,
-                                                float *__restrict__ out_t) const {
-        float g[V], gxp[V];
-#pragma unroll
-        for (int c = 0; c < V; c++) g[c] = unit * (float)G[c];
-        normalize_bwd(xn, g, inv, unclipped, gxp);
-        const float d = dot(gxp, cw);
-        if constexpr (MODEL == KGE_TRANSD) {
-#pragma unroll
-            for (int c = 0; c < V; c++) g[c] = d * x[c];
-            store(out_t, g);
-#pragma unroll
-            for (int c = 0; c < V; c++) {
-                g[c] = gxp[c] + d * xt[c];
-                acw[c] += a * gxp[c];
-            }
-        } else {
-#pragma unroll
-            for (int c = 0; c < V; c++) {
-                g[c] = gxp[c] - d * cw[c];
-                acw[c] -= d * x[c] + a * gxp[c];
-            }
-        }
-        store(out, g);
-    }
 };
 
 template <int MODEL, int Q, bool VEC>
@@ -481,11 +344,11 @@ constexpr int kLdsBudget = 60 * 1024;   // per workgroup, as the TransE kernel's
 const char *float_shape_limit(const kge_model_desc &m, INT N, int model) {
     if (model == KGE_TRANSD) {
         if (m.model != KGE_TRANSD) return "shared float records with transfer rows are built for TransD (TransH: kge_transh_emit_records_shared_chunks; "
-                                          "TransE: kge_transe_emit_records_shared_chunks; TransR has no shared emit kernel)";
+                                          "TransE: kge_transe_emit_records_shared_chunks; TransR: kge_transr_forward_backward_shared_chunks)";
     } else {
         if (m.model == KGE_TRANSE) return "shared float records are built for TransH: TransE has its int8 records (kge_transe_emit_records_shared_chunks)";
         if (m.model == KGE_TRANSD) return "shared float records are built for TransH: TransD needs its transfer rows as well (kge_transd_emit_records_shared_chunks)";
-        if (m.model != KGE_TRANSH) return "shared float records are built for TransH: TransR has no shared emit kernel";
+        if (m.model != KGE_TRANSH) return "shared float records are built for TransH: TransR trains through dense gradient tables (kge_transr_forward_backward_shared_chunks)";
     }
     if (m.negative_rel != 0) return "shared negatives: relation negatives are not supported (negative_rel must be 0)";
     if (N < 1 || N > 63) return "shared negatives: 1..63 negatives per positive (a positive's count is within +-2N, an int8)";

@@ -1560,6 +1560,103 @@ bool transr_v2_dims(const kge_model_desc &m) {
     return De % 4 == 0 && Dr % 4 == 0 && De >= 4 && Dr >= 4 && De <= LDB2 && Dr <= LDB2 && engine().transr_v1 != 1;
 }
 
+// ---- the plain (non-group) layout: its GEMM launches over a sorted job list of `slots` rows, the kernels chosen by the dimensions ----
+// (drec / ddst: dgrad's float-record mode, null = fp32 atomics; the group layout's fields stay zero, and its pad row is whatever
+// the projection of the next group-layout call writes there)
+GemmArgs plain_gemm_args(const kge_model_desc &m, const float *const tables[4], float *const grads[4], float *drec, int32_t *ddst) {
+    GemmArgs ga = {};
+    ga.ent = tables[0]; ga.mat = tables[2]; ga.GP = g_w.GP; ga.P = g_w.P; ga.g_ent = grads ? grads[0] : nullptr;
+    ga.sorted_slots = g_w.vals2; ga.job_ent = g_w.job_ent; ga.bucket_start = g_w.bucket_start;
+    ga.tile_rel = g_w.tile_rel; ga.tile_row0 = g_w.tile_row0; ga.n_tiles = g_w.n_tiles;
+    ga.De = m.ent_dim; ga.Dr = m.rel_dim;
+    ga.rec_out = drec; ga.rec_dst = ddst; ga.row_ent = g_w.row_ent;
+    return ga;
+}
+
+struct PlainShape {
+    bool v2, v3, split_cols;
+    unsigned max_tiles;
+};
+PlainShape plain_shape(const kge_model_desc &m, int64_t slots) {
+    PlainShape s;
+    const int64_t R = m.rel_total;
+    s.v2 = transr_v2_dims(m);
+    s.max_tiles = (unsigned)(slots / (s.v2 ? RW2 : 32) + R + 1);
+    // sparse buckets (config #4's auto batch: 46 rows per relation, ~one tile per relation, fewer tiles than CUs): two column
+    // blocks of 7 tiles per row tile instead of one of 13
+    s.split_cols = s.v2 && slots < 256 * R && engine().transr_v1 == 0;
+    // v3: the same tiles with the products on the bf16 matrix pipe (three-term split, rows_gemm3_kernel)
+    s.v3 = s.v2 && engine().transr_bf16x3 && engine().transr_v1 == 0;
+    return s;
+}
+
+void launch_plain_project(const kge_model_desc &m, const GemmArgs &ga, int64_t slots, hipStream_t stream) {
+    const int Dr = m.rel_dim;
+    const PlainShape s = plain_shape(m, slots);
+    const bool v2 = s.v2, v3 = s.v3, split_cols = s.split_cols;
+    const unsigned max_tiles = s.max_tiles;
+    if (v3 && Dr <= 112) hipLaunchKernelGGL((rows_gemm3_kernel<GEMM_PROJECT, 7>), dim3(max_tiles), dim3(256), 0, stream, ga);
+    else if (v3) hipLaunchKernelGGL((rows_gemm3_kernel<GEMM_PROJECT, 13>), dim3(max_tiles), dim3(256), 0, stream, ga);
+    else if (v2 && Dr <= 112) hipLaunchKernelGGL((rows_gemm2_kernel<GEMM_PROJECT, 7>), dim3(max_tiles, 1), dim3(256), 0, stream, ga);
+    else if (v2 && split_cols) hipLaunchKernelGGL((rows_gemm2_kernel<GEMM_PROJECT, 7>), dim3(max_tiles, (Dr + 111) / 112), dim3(256), 0, stream, ga);
+    else if (v2) hipLaunchKernelGGL((rows_gemm2_kernel<GEMM_PROJECT, 13>), dim3(max_tiles, 1), dim3(256), 0, stream, ga);
+    else hipLaunchKernelGGL((rows_gemm_kernel<GEMM_PROJECT>), dim3(max_tiles, (Dr + TN - 1) / TN), dim3(256), 0, stream, ga);
+}
+
+// g_ent += GP . M^T (ga.rec_out: as float records, summed per entity here)
+int launch_plain_dgrad(const kge_model_desc &m, const GemmArgs &ga, int64_t slots, hipStream_t stream) {
+    const int De = m.ent_dim;
+    const PlainShape s = plain_shape(m, slots);
+    const bool v3 = s.v3, split_cols = s.split_cols;
+    const unsigned max_tiles = s.max_tiles;
+    if (!s.v2) {
+        hipLaunchKernelGGL((rows_gemm_kernel<GEMM_DGRAD>), dim3(max_tiles, (De + TN - 1) / TN), dim3(256), 0, stream, ga);
+        return KGE_OK;
+    }
+    if (v3 && De <= 112) hipLaunchKernelGGL((rows_gemm3_kernel<GEMM_DGRAD, 7>), dim3(max_tiles), dim3(256), 0, stream, ga);
+    else if (v3) hipLaunchKernelGGL((rows_gemm3_kernel<GEMM_DGRAD, 13>), dim3(max_tiles), dim3(256), 0, stream, ga);
+    else if (De <= 112) hipLaunchKernelGGL((rows_gemm2_kernel<GEMM_DGRAD, 7>), dim3(max_tiles, 1), dim3(256), 0, stream, ga);
+    else if (split_cols) hipLaunchKernelGGL((rows_gemm2_kernel<GEMM_DGRAD, 7>), dim3(max_tiles, (De + 111) / 112), dim3(256), 0, stream, ga);
+    else hipLaunchKernelGGL((rows_gemm2_kernel<GEMM_DGRAD, 13>), dim3(max_tiles, 1), dim3(256), 0, stream, ga);
+    if (ga.rec_out) {
+        FloatRowSpace rs = {};
+        rs.g_ent = ga.g_ent; rs.E = m.ent_total; rs.R = 0; rs.hub_base = m.ent_total; rs.hub_rows = 1; rs.rows = m.ent_total;
+        return float_records_reduce(slots, De, rs, stream);
+    }
+    return KGE_OK;
+}
+
+// g_mat[r] += X_r^T . GP_r
+void launch_plain_wgrad(const kge_model_desc &m, const GemmArgs &ga, float *g_mat, int64_t slots, hipStream_t stream) {
+    const int De = m.ent_dim, Dr = m.rel_dim;
+    const int64_t R = m.rel_total;
+    const PlainShape s = plain_shape(m, slots);
+    const unsigned max_tiles = s.max_tiles;
+    if (!s.v2) {
+        const int tiles_i = (De + 31) / 32;
+        const unsigned groups = (max_tiles + WG_TILES - 1) / WG_TILES;
+        hipLaunchKernelGGL(wgrad_kernel, dim3(groups * tiles_i, (Dr + TN - 1) / TN), dim3(256), 0, stream, ga, g_mat, tiles_i, 32, WG_TILES);
+        return;
+    }
+    // the all-output-tiles wgrad (full 13 x 13 tile grid only) pays one 160 kB flush per relation change: only with
+    // well-filled buckets (measured: 316 vs 400 us at 574 rows per relation, 131 vs 77 us at 46)
+    const bool full_grid = De > 192 && Dr > 192;
+    const int opt = engine().transr_v1;
+    if (full_grid && opt != 3) {
+        // well-filled buckets: 512 rows between flushes; sparse buckets (a tile = one relation's whole bucket, stored by its
+        // single owner): one tile per workgroup so that every tile is in flight
+        const int span = (slots >= 256 * R || opt == 2) ? SPAN2 : 1;
+        const dim3 wg2((max_tiles + span - 1) / span, 2);
+        if (s.v3) hipLaunchKernelGGL(wgrad3_kernel, wg2, dim3(256), 0, stream, ga, g_mat, span);
+        else hipLaunchKernelGGL(wgrad2_kernel, wg2, dim3(256), 0, stream, ga, g_mat, span);
+    } else {
+        const int tiles_i1 = (De + 31) / 32;
+        const int wgt = WG_TILES * 32 / RW2;   // the same 256 rows between flushes as with 32-row tiles
+        const unsigned groups1 = (max_tiles + wgt - 1) / wgt;
+        hipLaunchKernelGGL(wgrad_kernel, dim3(groups1 * tiles_i1, (Dr + TN - 1) / TN), dim3(256), 0, stream, ga, g_mat, tiles_i1, RW2, wgt);
+    }
+}
+
 }  // namespace
 
 // does a sampler-shaped TransR step of this shape take the group layout?  (also behind kge_transr_group_layout_active)
@@ -1694,64 +1791,49 @@ int launch_forward_backward_transr(const kge_model_desc &m, const float *const t
         hipLaunchKernelGGL(bounds_kernel, dim3(1), dim3(1024), 0, stream, g_w.keys2, (int)slots, (int)R, g_w.bucket_start,
                            g_w.tile_rel, g_w.tile_row0, g_w.n_tiles, v2 ? 7 : 5);
     }
-    GemmArgs ga = {};
-    ga.ent = tables[0]; ga.mat = tables[2]; ga.GP = g_w.GP; ga.P = g_w.P; ga.g_ent = grads[0];
-    ga.sorted_slots = g_w.vals2; ga.job_ent = g_w.job_ent; ga.bucket_start = g_w.bucket_start;
-    ga.tile_rel = g_w.tile_rel; ga.tile_row0 = g_w.tile_row0; ga.n_tiles = g_w.n_tiles;
-    ga.De = De; ga.Dr = Dr;
-    ga.rec_out = drec; ga.rec_dst = ddst; ga.row_ent = g_w.row_ent;
-    const unsigned max_tiles = (unsigned)(slots / (v2 ? RW2 : 32) + R + 1);
-    // sparse buckets (config #4's auto batch: 46 rows per relation, ~one tile per relation, fewer tiles than CUs): two column
-    // blocks of 7 tiles per row tile instead of one of 13
-    const bool split_cols = v2 && slots < 256 * R && engine().transr_v1 == 0;
-    // v3: the same tiles with the products on the bf16 matrix pipe (three-term split, rows_gemm3_kernel)
-    const bool v3 = v2 && engine().transr_bf16x3 && engine().transr_v1 == 0;
-    if (v3 && Dr <= 112) hipLaunchKernelGGL((rows_gemm3_kernel<GEMM_PROJECT, 7>), dim3(max_tiles), dim3(256), 0, stream, ga);
-    else if (v3) hipLaunchKernelGGL((rows_gemm3_kernel<GEMM_PROJECT, 13>), dim3(max_tiles), dim3(256), 0, stream, ga);
-    else if (v2 && Dr <= 112) hipLaunchKernelGGL((rows_gemm2_kernel<GEMM_PROJECT, 7>), dim3(max_tiles, 1), dim3(256), 0, stream, ga);
-    else if (v2 && split_cols) hipLaunchKernelGGL((rows_gemm2_kernel<GEMM_PROJECT, 7>), dim3(max_tiles, (Dr + 111) / 112), dim3(256), 0, stream, ga);
-    else if (v2) hipLaunchKernelGGL((rows_gemm2_kernel<GEMM_PROJECT, 13>), dim3(max_tiles, 1), dim3(256), 0, stream, ga);
-    else hipLaunchKernelGGL((rows_gemm_kernel<GEMM_PROJECT>), dim3(max_tiles, (Dr + TN - 1) / TN), dim3(256), 0, stream, ga);
+    const GemmArgs ga = plain_gemm_args(m, tables, grads, drec, ddst);
+    launch_plain_project(m, ga, slots, stream);
     const bool lean = transr_lean_vector_stage(Dr);   // the lean vector stage writes every GP row that dgrad / wgrad read
     if (!lean && (rc = hip_check(hipMemsetAsync(g_w.GP, 0, sizeof(float) * (size_t)slots * Dr, stream), "zero GP"))) return rc;
     rc = launch_transr_vector_stage(tables[1], grads[1], g_w.P, g_w.GP, d_h, d_t, d_r, n_pos, n_neg, stride, denom, Dr, m.margin,
                                     m.negative_rel, d_loss, stream, lean, sampler_shaped, R);
     if (rc) return rc;
-    if (v2) {
-        if (v3 && De <= 112) hipLaunchKernelGGL((rows_gemm3_kernel<GEMM_DGRAD, 7>), dim3(max_tiles), dim3(256), 0, stream, ga);
-        else if (v3) hipLaunchKernelGGL((rows_gemm3_kernel<GEMM_DGRAD, 13>), dim3(max_tiles), dim3(256), 0, stream, ga);
-        else if (De <= 112) hipLaunchKernelGGL((rows_gemm2_kernel<GEMM_DGRAD, 7>), dim3(max_tiles, 1), dim3(256), 0, stream, ga);
-        else if (split_cols) hipLaunchKernelGGL((rows_gemm2_kernel<GEMM_DGRAD, 7>), dim3(max_tiles, (De + 111) / 112), dim3(256), 0, stream, ga);
-        else hipLaunchKernelGGL((rows_gemm2_kernel<GEMM_DGRAD, 13>), dim3(max_tiles, 1), dim3(256), 0, stream, ga);
-        if (dgrad_records) {
-            FloatRowSpace rs = {};
-            rs.g_ent = grads[0]; rs.E = m.ent_total; rs.R = 0; rs.hub_base = m.ent_total; rs.hub_rows = 1; rs.rows = m.ent_total;
-            if ((rc = float_records_reduce(slots, De, rs, stream))) return rc;
-        }
-        // the all-output-tiles wgrad (full 13 x 13 tile grid only) pays one 160 kB flush per relation change: only with
-        // well-filled buckets (measured: 316 vs 400 us at 574 rows per relation, 131 vs 77 us at 46)
-        const bool full_grid = De > 192 && Dr > 192;
-        const int opt = engine().transr_v1;
-        if (full_grid && opt != 3) {
-            // well-filled buckets: 512 rows between flushes; sparse buckets (a tile = one relation's whole bucket, stored by its
-            // single owner): one tile per workgroup so that every tile is in flight
-            const int span = (slots >= 256 * R || opt == 2) ? SPAN2 : 1;
-            const dim3 wg2((max_tiles + span - 1) / span, 2);
-            if (v3) hipLaunchKernelGGL(wgrad3_kernel, wg2, dim3(256), 0, stream, ga, grads[2], span);
-            else hipLaunchKernelGGL(wgrad2_kernel, wg2, dim3(256), 0, stream, ga, grads[2], span);
-        } else {
-            const int tiles_i1 = (De + 31) / 32;
-            const int wgt = WG_TILES * 32 / RW2;   // the same 256 rows between flushes as with 32-row tiles
-            const unsigned groups1 = (max_tiles + wgt - 1) / wgt;
-            hipLaunchKernelGGL(wgrad_kernel, dim3(groups1 * tiles_i1, (Dr + TN - 1) / TN), dim3(256), 0, stream, ga, grads[2], tiles_i1, RW2, wgt);
-        }
-        return hip_check(hipGetLastError(), "transr launch");
-    }
-    hipLaunchKernelGGL((rows_gemm_kernel<GEMM_DGRAD>), dim3(max_tiles, (De + TN - 1) / TN), dim3(256), 0, stream, ga);
-    const int tiles_i = (De + 31) / 32;
-    const unsigned groups = (max_tiles + WG_TILES - 1) / WG_TILES;
-    hipLaunchKernelGGL(wgrad_kernel, dim3(groups * tiles_i, (Dr + TN - 1) / TN), dim3(256), 0, stream, ga, grads[2], tiles_i, 32, WG_TILES);
+    if ((rc = launch_plain_dgrad(m, ga, slots, stream))) return rc;
+    launch_plain_wgrad(m, ga, grads[2], slots, stream);
     return hip_check(hipGetLastError(), "transr launch");
+}
+
+// ---- TransR on relation-grouped chunks (shared_transr.hip): the plain layout's GEMMs over a job list the caller writes ----
+static bool transr_shared_records(const kge_model_desc &m, int64_t J) {
+    return transr_v2_dims(m) && engine().transr_dgrad_records && J >= engine().transr_dgrad_records_min;
+}
+
+int transr_shared_workspace(const kge_model_desc &m, int64_t J, TransrSharedRows &w) {
+    int rc = ensure_work(J, m.rel_dim, m.rel_total);
+    if (rc) return rc;
+    w = TransrSharedRows{};
+    if (transr_shared_records(m, J) && (rc = float_records_workspace(J, m.ent_dim, w.drec, w.rec_dst))) return rc;
+    w.P = g_w.P; w.GP = g_w.GP; w.keys = g_w.keys2; w.slots = g_w.vals2; w.job_ent = g_w.job_ent;
+    return KGE_OK;
+}
+
+int launch_transr_shared_project(const kge_model_desc &m, const float *const tables[4], const TransrSharedRows &w, int64_t J, hipStream_t stream) {
+    hipLaunchKernelGGL(bounds_kernel, dim3(1), dim3(1024), 0, stream, w.keys, (int)J, (int)m.rel_total, g_w.bucket_start, g_w.tile_rel,
+                       g_w.tile_row0, g_w.n_tiles, transr_v2_dims(m) ? 7 : 5);
+    launch_plain_project(m, plain_gemm_args(m, tables, nullptr, w.drec, w.rec_dst), J, stream);
+    return hip_check(hipGetLastError(), "transr shared projection launch");
+}
+
+int launch_transr_shared_dgrad(const kge_model_desc &m, const float *const tables[4], float *const grads[4], const TransrSharedRows &w, int64_t J,
+                               hipStream_t stream) {
+    const int rc = launch_plain_dgrad(m, plain_gemm_args(m, tables, grads, w.drec, w.rec_dst), J, stream);
+    return rc ? rc : hip_check(hipGetLastError(), "transr shared dgrad launch");
+}
+
+int launch_transr_shared_wgrad(const kge_model_desc &m, const float *const tables[4], float *const grads[4], const TransrSharedRows &w, int64_t J,
+                               hipStream_t stream) {
+    launch_plain_wgrad(m, plain_gemm_args(m, tables, grads, w.drec, w.rec_dst), grads[2], J, stream);
+    return hip_check(hipGetLastError(), "transr shared wgrad launch");
 }
 
 int launch_predict_transr(const kge_model_desc &m, const float *const tables[4], const int32_t *d_h, const int32_t *d_t,

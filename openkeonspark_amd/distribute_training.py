@@ -116,7 +116,9 @@ def parse_args(argv=None):
                         "with --type_constrained_sampling 1, comes from that side's type list of the chunk's relation "
                         "(Config.set_shared_negatives(..., by_relation=True)).  One rank only; a resumed run must repeat it.  "
                         "With --model TransH or TransD (widths up to 512) this is the one form of shared negatives: a chunk also "
-                        "shares its relation's normal vector (TransD: transfer vector) and every candidate's projection")
+                        "shares its relation's normal vector (TransD: transfer vector) and every candidate's projection.  With --model "
+                        "TransR (rel_dim up to 512; SGD, Adagrad or Adam) likewise: a chunk shares its relation's matrix, and 2 P + N rows "
+                        "go through the row GEMMs where the unshared step puts P (2 + N)")
     p.add_argument("--type_constrained_sampling", type=int, default=0,
                    help="1: entity negatives of a training batch come from the relation's own head / tail type list "
                         "(type_constrain.txt in --input_path, required then) instead of from all entities; same random stream, "

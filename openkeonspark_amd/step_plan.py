@@ -6,7 +6,7 @@ sign-count step at a large batch" (the packed negatives, the prefetch default, t
 """
 from collections import namedtuple
 
-from ._lib import KgeError, TRANSE, TRANSH, TRANSD
+from ._lib import KgeError, TRANSE, TRANSH, TRANSR, TRANSD
 
 # accepted spellings of the optimizer names (distribute_training.py:95 for Adam); any other name trains with SGD, as the reference does
 _KINDS = {"Adam": "adam", "adam": "adam",
@@ -68,7 +68,7 @@ def wants_sparse_rows(sparse_rows, ent_total, rel_total, width, batch_size, n_ne
 
 def plan(model_id, opt_method, sparse_rows, use_counts, counts_supported, ent_total, rel_total, width, batch_size, n_neg,
          sparse_threshold_bytes=None, adagrad_initial_accumulator=0.1, shared_chunk=0, negative_rel=0, by_relation=False, typed=False,
-         shared_float_supported=0, shared_transd_supported=0):
+         shared_float_supported=0, shared_transd_supported=0, shared_transr_supported=0):
     """The StepPlan of a configuration.  sparse_rows: None = automatic, True / False = the caller's wish; use_counts: the
     caller's wish; counts_supported: what kge_transe_counts_supported said for the model's descriptor and n_neg.
     shared_chunk: 0 = off; P > 0 = negatives shared by chunks of P positives (NON-PARITY, opt-in: Config.set_shared_negatives),
@@ -77,7 +77,8 @@ def plan(model_id, opt_method, sparse_rows, use_counts, counts_supported, ent_to
     sampling is on, which shared negatives take on such chunks only; shared_float_supported: what kge_shared_float_supported said
     for the model's descriptor and the entity negatives (TransH on relation-grouped chunks, float gradient records);
     shared_transd_supported: what kge_shared_transd_supported said for them (TransD on such chunks, the same records with the
-    transfer rows)."""
+    transfer rows); shared_transr_supported: what kge_shared_transr_supported said for them (TransR on such chunks, through its
+    dense gradient tables: the plan of its unshared step)."""
     optimizer = optimizer_kind(opt_method)
     adam, lazy_adam, adagrad = optimizer == "adam", optimizer == "lazy_adam", optimizer == "adagrad"
     # LazyAdam -- opt-in, NON-PARITY: Adam on the touched rows only (tf.contrib.opt.LazyAdamOptimizer's rule) for tables whose dense
@@ -100,7 +101,9 @@ def plan(model_id, opt_method, sparse_rows, use_counts, counts_supported, ent_to
     rows = (bool(sparse) or rows_rule) and use_counts and not adam
     if shared_chunk:
         check_shared_negatives(model_id, optimizer, use_counts, shared_chunk, n_neg - negative_rel, negative_rel, by_relation, typed,
-                               shared_float_supported, shared_transd_supported)
+                               shared_float_supported, shared_transd_supported, shared_transr_supported)
+        if model_id == TRANSR:      # dense gradient tables and the optimizer on the whole tables, as its unshared step
+            return StepPlan(optimizer, False, False, False, table_bytes)
         if model_id in (TRANSH, TRANSD):      # float records, keyed in the unshared step's row space: the touched-rows plan in place
             return StepPlan(optimizer, False, False, True, table_bytes)
         return StepPlan(optimizer, use_counts, True, False, table_bytes)      # its records go through the touched-rows reduce
@@ -130,11 +133,12 @@ TYPED_NEEDS_BY_RELATION = ("a chunk of consecutive batch positions mixes relatio
 
 
 def check_shared_negatives(model_id, optimizer, use_counts, chunk, negative_ent, negative_rel, by_relation=False, typed=False,
-                           shared_float_supported=0, shared_transd_supported=0):
+                           shared_float_supported=0, shared_transd_supported=0, shared_transr_supported=0):
     """Raises KgeError, naming the limit, for a configuration the shared-negatives step cannot take.  by_relation: chunks cut from
     the batch ordered by relation; typed: candidates from the relations' type lists, which needs by_relation;
     shared_float_supported: the library's answer for TransH on such chunks (kge_shared_float_supported), which needs no use_counts;
-    shared_transd_supported: its answer for TransD on them (kge_shared_transd_supported), likewise."""
+    shared_transd_supported: its answer for TransD on them (kge_shared_transd_supported), likewise; shared_transr_supported: its
+    answer for TransR on them (kge_shared_transr_supported): dense gradient tables, so TF1 Adam is taken and LazyAdam is not."""
     if typed and not by_relation:
         raise KgeError("shared negatives cannot be combined with type-constrained sampling: " + TYPED_NEEDS_BY_RELATION)
     if not 1 <= int(chunk) <= SHARED_MAX_CHUNK:
@@ -148,13 +152,22 @@ def check_shared_negatives(model_id, optimizer, use_counts, chunk, negative_ent,
     if transd and not by_relation:
         raise KgeError("shared negatives on chunks by position are built for TransE only: TransD shares one transfer vector per chunk, "
                        "which needs chunks of one relation -- set_shared_negatives(chunk, by_relation=True)")
-    if model_id != TRANSE and not transh and not transd:
+    transr = model_id == TRANSR and bool(shared_transr_supported)
+    if transr and not by_relation:
+        raise KgeError("shared negatives on chunks by position are built for TransE only: TransR shares one matrix per chunk, "
+                       "which needs chunks of one relation -- set_shared_negatives(chunk, by_relation=True)")
+    if model_id != TRANSE and not transh and not transd and not transr:
         raise KgeError("shared negatives are built for TransE only: TransH, TransD and TransR have no shared emit kernel")
     if negative_rel > 0:
         raise KgeError("shared negatives: relation negatives are not supported (negative_rel must be 0, got %d)" % negative_rel)
     if not 1 <= negative_ent <= SHARED_MAX_NEGATIVES:
         raise KgeError("shared negatives: 1 to %d negatives per positive (a positive's count lies within +-2N and is carried as "
                        "an int8), got %d" % (SHARED_MAX_NEGATIVES, negative_ent))
+    if transr:      # (the gradients are dense tables: SGD, Adagrad and TF1 Adam sweep them as they do in the unshared step)
+        if optimizer == "lazy_adam":
+            raise KgeError("LazyAdam (touched rows only, NON-PARITY) needs TransE, TransH or TransD: TransR's gradient is a whole "
+                           "matrix per relation and has no record path")
+        return
     if optimizer == "adam":
         raise KgeError("shared negatives need SGD, LazyAdam or Adagrad: with TF1 Adam the dense count image has no entrance for "
                        "shared records yet")

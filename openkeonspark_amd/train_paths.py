@@ -560,10 +560,15 @@ def shared_grouped_step(con, dev, n_pos, stride, denom):
     and the rows rule takes them as it takes that step's (RowsRule.apply_float_records).
     TransD: the same again with kge_transd_emit_records_shared_chunks and 4 n_pos + cap (2 N + 2) float records -- every entity
     has a record for its ent_embeddings row and one for its ent_transfer row, the chunk slot one for rel_embeddings and one for
-    rel_transfer -- keyed in the row space of the unshared TransD step."""
+    rel_transfer -- keyed in the row space of the unshared TransD step.
+    TransR: same order, same draw, same buffer names, no records: kge_transr_forward_backward_shared_chunks puts the chunk table's
+    2 n_pos + cap N rows through the projection, the pair walk, dgrad and wgrad into the dense gradient tables, and
+    Config.apply_gradients finishes as it does for the unshared TransR step."""
     import torch
     P, N, D = con._shared_chunk, con.negative_ent, con.hidden_size
     model_id = con.trainModel.model_id
+    if model_id == _lib.TRANSR:
+        return shared_grouped_transr_step(con, dev, n_pos, stride, denom)
     float_rec = model_id in (_lib.TRANSH, _lib.TRANSD)      # the float-record models
     ew = 2 if model_id == _lib.TRANSD else 1                # records per entity
     cap = shared_chunk_cap(n_pos, P, con.relTotal)
@@ -613,6 +618,33 @@ def shared_grouped_step(con, dev, n_pos, stride, denom):
                            fused_ok=getattr(con, "sparse_fused", True) and D % 4 == 0)
     con._rule.advance()
     con.global_step += 1
+
+
+def shared_grouped_transr_step(con, dev, n_pos, stride, denom):
+    """shared_grouped_step for TransR (one rank): order -> grouped draw -> kge_transr_forward_backward_shared_chunks into the dense
+    gradient tables -> the optimizer on the whole tables.  The lists stay in con._sparse_buf under the names the other models use."""
+    import torch
+    P, N = con._shared_chunk, con.negative_ent
+    cap = shared_chunk_cap(n_pos, P, con.relTotal)
+    cap_max = shared_chunk_cap(stride, P, con.relTotal)
+    buf = con._sparse_buf
+    if buf is None or "chunks" not in buf or buf["chunks"].shape[0] < cap_max or buf["pair"].shape[0] < stride:
+        d, i32 = con.device, torch.int32
+        buf = dict(perm=torch.empty(stride, dtype=i32, device=d), sorted=torch.empty((3, stride), dtype=i32, device=d),
+                   chunks=torch.empty((cap_max, 2), dtype=i32, device=d), n_chunks=torch.zeros(1, dtype=i32, device=d),
+                   cand=torch.empty((cap_max, N), dtype=i32, device=d), pair=torch.empty((stride, N), dtype=torch.uint8, device=d))
+        con._sparse_buf = buf
+    L, st = con.lib, con._stream()
+    h2, t2, r2 = (buf["sorted"][i].data_ptr() for i in range(3))
+    chunks, cand, pair = buf["chunks"].data_ptr(), buf["cand"].data_ptr(), buf["pair"].data_ptr()
+    _lib.check(L.kge_shared_order_by_relation(dev[0].data_ptr(), dev[1].data_ptr(), dev[2].data_ptr(), n_pos, P, buf["perm"].data_ptr(),
+                                              h2, t2, r2, chunks, buf["n_chunks"].data_ptr(), st), L)
+    _lib.check(L.kge_shared_negatives_draw_grouped(h2, t2, r2, n_pos, chunks, cap, N, 1 if con.type_constrained_sampling else 0,
+                                                   con._shared_seed, con.global_step, cand, pair, st), L)
+    _lib.check(L.kge_transr_forward_backward_shared_chunks(ctypes.byref(con._desc), con._tab_ptrs, h2, t2, r2, n_pos, stride, chunks, cap, cand,
+                                                           N, pair, denom, con._grad_ptrs, con._loss.data_ptr(), st), L)
+    buf["shared_step"], buf["shared_shape"], buf["shared_batch"] = con.global_step, (n_pos, cap), dev
+    con.apply_gradients()      # (advances global_step)
 
 
 def shared_chunk_span(first_position, n_pos, P):
