@@ -457,6 +457,22 @@ int kge_forward_backward_adagrad_rows(const kge_model_desc *m, float *const tabl
                                       float lr, float *d_loss, void *stream);
 int kge_float_records_apply_adagrad(const kge_model_desc *m, float *const tables[KGE_MAX_TABLES], float *const acc[KGE_MAX_TABLES],
                                     const float *d_rec, int32_t *d_dst, INT n_records, INT n_pos_total, INT n_neg, float lr, void *stream);
+/* Opt-in ("RowAdagrad"): the same two entry points ending in row-wise Adagrad (PyTorch-BigGraph's RowAdagrad) on the touched rows.
+ * ONE fp32 accumulator per table row: `acc` holds, for each table of the model, [rows] floats (not a table-shaped array).  With
+ * g[0..D) the row's complete gradient sum (record order, hub copies folded in copy order -- as for lazy Adam and Adagrad), in
+ * fp32 with contraction off:
+ *     q = sum_j g[j]*g[j];  a += q / D;  s = sqrt(a);  p[j] -= (lr * g[j]) / s  for every j with g[j] != 0
+ * q is summed in one fixed order per width (a lane's elements in index order, then the team's butterfly), the same in every run.
+ * No epsilon, nothing advances between steps: the caller fills the accumulators with a positive value before the first step
+ * (PBG's own form starts at 0 and adds 1e-10 to the root; this keeps the Adagrad entry points' convention).  Like Adagrad it IS
+ * the dense rule: a row whose gradient is all zero -- no record, or records of zeros -- keeps its value and its accumulator bit
+ * for bit, and so does an element with g = 0 in a row that moves.  A missing accumulator: KGE_ERR_BAD_ARG before anything is
+ * launched.  TransE / TransH / TransD; TransR: KGE_ERR_UNSUPPORTED (its form is kge_rowadagrad_update_tables). */
+int kge_forward_backward_rowadagrad_rows(const kge_model_desc *m, float *const tables[KGE_MAX_TABLES], float *const acc[KGE_MAX_TABLES],
+                                         const int32_t *d_h, const int32_t *d_t, const int32_t *d_r, INT n_pos, INT n_neg, INT stride, INT denom,
+                                         float lr, float *d_loss, void *stream);
+int kge_float_records_apply_rowadagrad(const kge_model_desc *m, float *const tables[KGE_MAX_TABLES], float *const acc[KGE_MAX_TABLES],
+                                       const float *d_rec, int32_t *d_dst, INT n_records, INT n_pos_total, INT n_neg, float lr, void *stream);
 /* 1 when kge_forward_backward on a step of this shape takes the TransH / TransD pair-count path (whose emit kernel also records
  * the event above), else 0 */
 int kge_pair_path_active(const kge_model_desc *m, INT n_pos, INT n_neg);
@@ -507,6 +523,14 @@ int kge_adam_update_tables(int32_t n_tables, float *const d_p[KGE_MAX_TABLES], f
                            float lr_t, float beta1, float beta2, float eps, void *stream);
 int kge_adagrad_update_tables(int32_t n_tables, float *const d_p[KGE_MAX_TABLES], float *const d_acc[KGE_MAX_TABLES],
                               float *const d_g[KGE_MAX_TABLES], const INT numel[KGE_MAX_TABLES], float lr, void *stream);
+/* Row-wise Adagrad (the rule above) on dense summed gradients, for TransR: table i has rows[i] rows of row_len[i] elements (a
+ * relation's whole De x Dr matrix is ONE row; row_len up to 2^24), d_acc[i] holds rows[i] floats.  One wave per row up to 1024
+ * elements, one workgroup per row beyond; the sum of squares loops over the row in a fixed order.  The gradient consumed is
+ * zeroed; a row whose gradient is all zero is read once (g) and nothing of it -- p, accumulator, g -- is written.  One launch per
+ * table.  Null pointers, a negative row count or a row length outside [1, 2^24]: KGE_ERR_BAD_ARG, nothing launched. */
+int kge_rowadagrad_update_tables(int32_t n_tables, float *const d_p[KGE_MAX_TABLES], float *const d_acc[KGE_MAX_TABLES],
+                                 float *const d_g[KGE_MAX_TABLES], const INT rows[KGE_MAX_TABLES], const INT row_len[KGE_MAX_TABLES], float lr,
+                                 void *stream);
 
 /* ---- TransE sign-count path (exact integer gradients, no fp32 atomics) ----------------------
  * For the L1 score of TransE.py:11-15 the gradient w.r.t. every l2-normalised vector is (1/denom) x an
@@ -629,6 +653,14 @@ int kge_transe_apply_rows_adam_lazy(const kge_model_desc *m, float *d_ent, float
  * are listed with all-reduced counts, and the touched rows are all the dense rule would move. */
 int kge_transe_apply_rows_adagrad(const kge_model_desc *m, float *d_ent, float *d_rel, float *d_acc_ent, float *d_acc_rel, const int32_t *d_rows,
                                   const int32_t *d_row_counts, const int32_t *d_n_rows, INT max_rows, INT denom, float lr, void *stream);
+/* Opt-in ("RowAdagrad"): row-wise Adagrad (see kge_forward_backward_rowadagrad_rows) on the rows listed in d_rows, from their
+ * counts -- the row's gradient g is formed as kge_transe_apply_rows_adagrad forms it (same team shape, same bits), then
+ * q = sum g^2; a += q / D; p[j] -= (lr * g[j]) / sqrt(a) where g[j] != 0.  d_acc_ent / d_acc_rel hold ONE float per row ([E] and
+ * [R]).  Rows that are not listed and listed rows whose counts are all zero keep value and accumulator bit for bit, so no live
+ * mask is needed where all rows of a table are listed with all-reduced counts.  A kernel of its own: the SGD / lazy-Adam /
+ * Adagrad row-list launch is untouched. */
+int kge_transe_apply_rows_rowadagrad(const kge_model_desc *m, float *d_ent, float *d_rel, float *d_acc_ent, float *d_acc_rel, const int32_t *d_rows,
+                                     const int32_t *d_row_counts, const int32_t *d_n_rows, INT max_rows, INT denom, float lr, void *stream);
 /* reduce + apply in one pass (embedding width a multiple of 4): rows whose records all fall inside one 64-record chunk
  * of the sorted list are updated straight from the registers that hold their sum; only chunk-boundary rows go through
  * d_row_counts and a second, small pass.  Same bits as kge_transe_reduce_records + kge_transe_apply_rows_sgd.

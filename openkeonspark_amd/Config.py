@@ -7,7 +7,7 @@ Same constructor, setters, attributes, `init()` and `sampling()` as the referenc
 `sess.run([train_op, loss, global_step], feed_dict)` (distribute_training.py:282) built by
 `create_model` (distribute_training.py:74-105) -- is `train_step()` here: sample on the device,
 run the fused forward/backward operator, exchange gradients over RCCL when data-parallel, apply
-SGD, TF-parity Adam or -- opt-in -- lazy Adam / Adagrad on the touched rows.  Nothing in this module computes on the CPU; without the HIP library or a
+SGD, TF-parity Adam or -- opt-in -- lazy Adam / Adagrad / row-wise Adagrad on the touched rows.  Nothing in this module computes on the CPU; without the HIP library or a
 GPU the device calls raise.
 """
 import ctypes
@@ -62,6 +62,7 @@ class Config(object):
             self.adam_beta1, self.adam_beta2, self.adam_epsilon = 0.9, 0.999, 1e-8  # TF1 AdamOptimizer defaults
             self.adagrad_initial_accumulator = 0.1   # TF1 AdagradOptimizer's default; must be positive (the rule has no epsilon)
             self._adagrad = False                    # set_model_and_session decides it from opt_method
+            self._row_adagrad = False                # likewise ("RowAdagrad": one accumulator per table row, from the same initial value)
             self.trainModel = None
             self.global_step = 0
             self.rank, self.world_size = 0, 1
@@ -483,6 +484,7 @@ class Config(object):
             shared_transr_supported=self.lib.kge_shared_transr_supported(ctypes.byref(probe.descriptor()), self.negative_ent))
         self.use_counts, self.sparse_rows, self.sparse_inplace = p.use_counts, p.sparse_rows, p.sparse_inplace
         self._adam, self._lazy_adam, self._adagrad = p.adam, p.lazy_adam, p.adagrad
+        self._row_adagrad = p.row_adagrad
         self._has_slots, self._rows_rule = p.has_slots, p.rows_rule
         self._refuse_shared_ranks()
         self._shard_plan = self._plan_entity_shard(probe.model_id)
@@ -498,6 +500,9 @@ class Config(object):
             self._beta2_power = np.float32(self.adam_beta2)
         if self._adagrad:      # shaped like the tables: a row-sharded entity table (Model.embedding_def) gets a shard-sized accumulator
             self._adagrad_acc = [torch.full_like(t, float(self.adagrad_initial_accumulator)) for t in self._tables]
+        if self._row_adagrad:  # ONE float per table row (TransR's transfer_matrix: per relation); shard-sized where the entity table is
+            self._rowadagrad_acc = [torch.full((t.shape[0],), float(self.adagrad_initial_accumulator), dtype=torch.float32, device=t.device)
+                                    for t in self._tables]
         self._loss = torch.zeros(1, dtype=torch.float32, device=self.device)
         self._refresh_pointers()
         self._dist_ready = 0
@@ -587,6 +592,9 @@ class Config(object):
             if self._adagrad and not (self.sparse_rows or self.sparse_inplace):
                 raise KgeError("TransR with Adagrad is single-process only: the data-parallel dense step has no flat accumulator "
                                "for its reduce-scatter exchange")
+            if self._row_adagrad and not (self.sparse_rows or self.sparse_inplace):
+                raise KgeError("TransR with RowAdagrad is single-process only: the data-parallel dense step cuts its flat buffer "
+                               "anywhere, and the rule needs a row's complete gradient")
             if self.sparse_inplace:
                 pass          # replicated tables, the step's gradient records all-gathered (train_paths.records_step): nothing to lay out
             elif self.sparse_rows:
@@ -605,6 +613,10 @@ class Config(object):
             self._adam_v_ptrs = _lib.table_ptrs([t.data_ptr() for t in self._adam_v])
         if self._adagrad:
             self._adagrad_ptrs = _lib.table_ptrs([t.data_ptr() for t in self._adagrad_acc])
+        if self._row_adagrad:
+            self._rowadagrad_ptrs = _lib.table_ptrs([t.data_ptr() for t in self._rowadagrad_acc])
+            self._table_rows = (ctypes.c_int64 * _lib.KGE_MAX_TABLES)(*[t.shape[0] for t in self._tables])
+            self._row_len = (ctypes.c_int64 * _lib.KGE_MAX_TABLES)(*[t.numel() // max(t.shape[0], 1) for t in self._tables])
         self._rule = train_paths.RowsRule(self)      # (it holds these pointers)
 
     def _stream(self):
@@ -758,6 +770,8 @@ class Config(object):
         if own:       # one piece of this rank's share (train_step's exchange loop calls it per piece and advances Adam once)
             if self._adagrad:
                 raise KgeError("TransR with Adagrad is single-process only")
+            if self._row_adagrad:
+                raise KgeError("TransR with RowAdagrad is single-process only")
             lo, hi = self._piece_own[piece]
             n = hi - lo
             if hi > self._loss_tail:
@@ -779,6 +793,9 @@ class Config(object):
         elif self._adagrad:     # (TransR: every other model takes a touched-rows path under Adagrad)
             _lib.check(self.lib.kge_adagrad_update_tables(len(self._tables), self._tab_ptrs, self._adagrad_ptrs, self._grad_ptrs,
                                                           self._numel, float(self.alpha), st), self.lib)
+        elif self._row_adagrad:  # (TransR likewise; a row of transfer_matrix is one relation's whole matrix)
+            _lib.check(self.lib.kge_rowadagrad_update_tables(len(self._tables), self._tab_ptrs, self._rowadagrad_ptrs, self._grad_ptrs,
+                                                             self._table_rows, self._row_len, float(self.alpha), st), self.lib)
         else:
             _lib.check(self.lib.kge_sgd_update_tables(len(self._tables), self._tab_ptrs, self._grad_ptrs, self._numel,
                                                       float(self.alpha), st), self.lib)
@@ -884,7 +901,7 @@ class Config(object):
         """Can train_steps() run its steps inside one persistent launch (csrc/persist.hip)?  Single process, the dense
         fp32-accumulator path of TransE / TransH / TransD at a launch-latency-bound step size.  Not with type-constrained
         sampling: the persistent kernel has the untyped sampler only."""
-        if self.type_constrained_sampling or self._adagrad or self._shared_chunk:       # (persist.hip has the SGD and Adam sweeps only, and independent negatives)
+        if self.type_constrained_sampling or self._adagrad or self._row_adagrad or self._shared_chunk:       # (persist.hip has the SGD and Adam sweeps only, and independent negatives)
             return False
         if self._dp or self.sparse_rows or self.sparse_inplace or self.hidden_size > 256:
             return False

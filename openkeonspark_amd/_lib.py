@@ -133,6 +133,10 @@ def _declare(L):
     L.kge_adagrad_update.argtypes = [vp, vp, vp, i64, f32, vp]
     L.kge_adagrad_update_tables.argtypes = [i32, vp, vp, vp, vp, f32, vp]
     L.kge_transe_apply_rows_adagrad.argtypes = [ctypes.POINTER(ModelDesc), vp, vp, vp, vp, vp, vp, vp, i64, i64, f32, vp]
+    L.kge_forward_backward_rowadagrad_rows.argtypes = [ctypes.POINTER(ModelDesc), tabs, tabs, vp, vp, vp, i64, i64, i64, i64, f32, vp, vp]
+    L.kge_float_records_apply_rowadagrad.argtypes = [ctypes.POINTER(ModelDesc), tabs, tabs, vp, vp, i64, i64, i64, f32, vp]
+    L.kge_rowadagrad_update_tables.argtypes = [i32, vp, vp, vp, vp, vp, f32, vp]
+    L.kge_transe_apply_rows_rowadagrad.argtypes = [ctypes.POINTER(ModelDesc), vp, vp, vp, vp, vp, vp, vp, i64, i64, f32, vp]
     L.kge_adam_update.argtypes = [vp, vp, vp, vp, i64, f32, f32, f32, f32, vp]
     L.kge_sgd_update_tables.argtypes = [i32, vp, vp, vp, f32, vp]
     L.kge_adam_update_tables.argtypes = [i32, vp, vp, vp, vp, vp, f32, f32, f32, f32, vp]

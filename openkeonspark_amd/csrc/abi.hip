@@ -564,6 +564,39 @@ int kge_float_records_apply_adagrad(const kge_model_desc *m, float *const tables
     return launch_float_records_apply_adam(*m, tables, ad, d_rec, d_dst, n_records, n_pos_total, n_neg, (hipStream_t)stream);
 }
 
+// the per-row accumulators of the model's tables ([rows] floats each) as the row rule's one slot each, or false if one is missing
+static bool rowadagrad_rows_of(float *const tables[KGE_MAX_TABLES], float *const acc[KGE_MAX_TABLES], float lr, RowRule &ad) {
+    ad = {};
+    for (int t = 0; t < 4; t++) {
+        if (!tables[t]) continue;
+        if (!acc[t]) return false;
+        ad.m[t] = acc[t];
+    }
+    ad.lr_t = lr; ad.rule = kRuleRowAdagrad;
+    return true;
+}
+
+int kge_forward_backward_rowadagrad_rows(const kge_model_desc *m, float *const tables[KGE_MAX_TABLES], float *const acc[KGE_MAX_TABLES],
+                                         const int32_t *d_h, const int32_t *d_t, const int32_t *d_r, INT n_pos, INT n_neg, INT stride, INT denom,
+                                         float lr, float *d_loss, void *stream) {
+    if (!m || !tables || !acc || !d_loss) return fail(KGE_ERR_BAD_ARG, "kge_forward_backward_rowadagrad_rows: null argument");
+    if (m->model == KGE_TRANSR) return fail(KGE_ERR_UNSUPPORTED, "row-wise Adagrad on the touched rows: TransE / TransH / TransD only");
+    RowRule ad;
+    if (!rowadagrad_rows_of(tables, acc, lr, ad))
+        return fail(KGE_ERR_BAD_ARG, "kge_forward_backward_rowadagrad_rows: every table needs its row accumulators");
+    return launch_forward_backward(*m, tables, d_h, d_t, d_r, n_pos, n_neg, stride, denom, tables, d_loss, (hipStream_t)stream, false, 0.f, &ad);
+}
+
+int kge_float_records_apply_rowadagrad(const kge_model_desc *m, float *const tables[KGE_MAX_TABLES], float *const acc[KGE_MAX_TABLES],
+                                       const float *d_rec, int32_t *d_dst, INT n_records, INT n_pos_total, INT n_neg, float lr, void *stream) {
+    if (!m || !tables || !acc) return fail(KGE_ERR_BAD_ARG, "kge_float_records_apply_rowadagrad: null argument");
+    if (m->model == KGE_TRANSR) return fail(KGE_ERR_UNSUPPORTED, "row-wise Adagrad on the touched rows: TransE / TransH / TransD only");
+    RowRule ad;
+    if (!rowadagrad_rows_of(tables, acc, lr, ad))
+        return fail(KGE_ERR_BAD_ARG, "kge_float_records_apply_rowadagrad: every table needs its row accumulators");
+    return launch_float_records_apply_adam(*m, tables, ad, d_rec, d_dst, n_records, n_pos_total, n_neg, (hipStream_t)stream);
+}
+
 int kge_loss_limbs_target(int32_t *d_limbs4) {
     engine().loss_limbs = d_limbs4;
     return KGE_OK;
@@ -634,6 +667,13 @@ int kge_adagrad_update_tables(int32_t n_tables, float *const d_p[KGE_MAX_TABLES]
                               float *const d_g[KGE_MAX_TABLES], const INT numel[KGE_MAX_TABLES], float lr, void *stream) {
     tables_written();
     return launch_adagrad_tables(n_tables, d_p, d_acc, d_g, (const int64_t *)numel, lr, (hipStream_t)stream);
+}
+
+int kge_rowadagrad_update_tables(int32_t n_tables, float *const d_p[KGE_MAX_TABLES], float *const d_acc[KGE_MAX_TABLES],
+                                 float *const d_g[KGE_MAX_TABLES], const INT rows[KGE_MAX_TABLES], const INT row_len[KGE_MAX_TABLES], float lr,
+                                 void *stream) {
+    tables_written();
+    return launch_rowadagrad_tables(n_tables, d_p, d_acc, d_g, (const int64_t *)rows, (const int64_t *)row_len, lr, (hipStream_t)stream);
 }
 
 int kge_predict(const kge_model_desc *m, const float *const tables[KGE_MAX_TABLES], const int32_t *d_h,

@@ -194,8 +194,10 @@ int float_records_reduce(int64_t M, int D, const FloatRowSpace &rs, hipStream_t 
 //   kRuleAdam    : lazy Adam on the touched rows (NON-PARITY): m, v = the moments, lr_t = the bias-corrected rate, b1, b2, eps
 //   kRuleAdagrad : adagrad_one (exact, not NON-PARITY: a zero-gradient element keeps p and a bit for bit, so the touched rows are all
 //                  the dense rule moves): m = the accumulators, v unused (null), lr_t = the plain learning rate, b1 / b2 / eps unused
-// The functions that carry it keep `adam` in their names: they are the LazyAdam layers, serving both rules.
-enum { kRuleAdam = 0, kRuleAdagrad = 1 };
+//   kRuleRowAdagrad : row-wise Adagrad (optim_dev.hpp; exact on the touched rows as Adagrad is): m = the accumulators, ONE float per
+//                  table row ([rows], not shaped like the table), v unused (null), lr_t = the plain learning rate
+// The functions that carry it keep `adam` in their names: they are the LazyAdam layers, serving all three rules.
+enum { kRuleAdam = 0, kRuleAdagrad = 1, kRuleRowAdagrad = 2 };
 struct RowRule {
     float *m[4], *v[4];
     float lr_t, b1, b2, eps;
@@ -268,5 +270,7 @@ int launch_adam(float *p, float *m, float *v, float *g, int64_t n, float lr_t, f
                 hipStream_t stream);
 int launch_adagrad_tables(int n_tables, float *const *p, float *const *acc, float *const *g, const int64_t *numel, float lr, hipStream_t stream);
 int launch_adagrad(float *p, float *acc, float *g, int64_t n, float lr, hipStream_t stream);
+int launch_rowadagrad_tables(int n_tables, float *const *p, float *const *acc, float *const *g, const int64_t *rows, const int64_t *row_len,
+                             float lr, hipStream_t stream);
 
 }  // namespace kge

@@ -7,7 +7,9 @@
 // A13).  Both are single streaming passes here: 16 B per lane, grid-stride, the accumulator is
 // re-zeroed in the same pass so no separate memset is needed.  HBM-bound by construction:
 // SGD 16 B/element (read p,g; write p,g), Adam 32 B/element.  Adagrad (TF1 AdagradOptimizer; upstream OpenKE offers it, the
-// reference sends the name to SGD) reads g alone where a group's gradient is zero and moves 24 B/element elsewhere.
+// reference sends the name to SGD) reads g alone where a group's gradient is zero and moves 24 B/element elsewhere.  Row-wise Adagrad (PyTorch-BigGraph's; one
+// accumulator per ROW) is not a sweep of elements but one wave or workgroup per row: it reads g once where a row's gradient is
+// zero, and g twice, p and 8 B per row elsewhere.
 #include "optim_dev.hpp"
 
 namespace kge {
@@ -89,6 +91,41 @@ int launch_adagrad_tables(int n_tables, float *const *p, float *const *acc, floa
     if (n_max <= 0) return KGE_OK;
     hipLaunchKernelGGL(adagrad_kernel, dim3(sweep_blocks(n_max), (unsigned)n_tables), dim3(256), 0, stream, tb, lr);
     return hip_check(hipGetLastError(), "adagrad launch");
+}
+
+// Row-wise Adagrad (optim_dev.hpp), one launch per table: the tables of a model differ in row length, and the row length picks
+// the kernel -- a wave per row up to 1024 elements, the workgroup beyond (TransR's matrices: 40 000 elements at 200 x 200).
+template <int T, int V>
+__global__ __launch_bounds__(256) void rowadagrad_kernel(float *__restrict__ p, float *__restrict__ acc, float *__restrict__ g, long long rows,
+                                                         int len, float lr) {
+    __shared__ float wave_q[4];
+    rowadagrad_rows<T, V>(p, acc, g, rows, len, lr, wave_q);
+}
+
+int launch_rowadagrad_tables(int n_tables, float *const *p, float *const *acc, float *const *g, const int64_t *rows, const int64_t *row_len,
+                             float lr, hipStream_t stream) {
+    if (!device_ok()) return fail(KGE_ERR_NO_DEVICE, "kge_rowadagrad_update_tables: no usable HIP device");
+    if (n_tables < 1 || n_tables > 4 || !p || !acc || !g || !rows || !row_len) return fail(KGE_ERR_BAD_ARG, "kge_rowadagrad_update_tables: 1..4 tables");
+    for (int i = 0; i < n_tables; i++) {
+        if (!p[i] || !g[i] || !acc[i])
+            return fail(KGE_ERR_BAD_ARG, "kge_rowadagrad_update_tables: every table needs its gradient and its accumulator");
+        if (rows[i] < 0 || row_len[i] < 1 || row_len[i] > (int64_t(1) << 24))
+            return fail(KGE_ERR_BAD_ARG, "kge_rowadagrad_update_tables: rows >= 0 and 1 <= row length <= 2^24");
+    }
+    for (int i = 0; i < n_tables; i++) {
+        if (rows[i] == 0) continue;
+        const int len = (int)row_len[i];
+        const bool vec = len % 4 == 0 && ((reinterpret_cast<uintptr_t>(p[i]) | reinterpret_cast<uintptr_t>(g[i])) & 15) == 0;
+        const bool group = len > 1024;
+        long long nb = group ? rows[i] : (rows[i] + 3) / 4;
+        if (nb > (1 << 20)) nb = 1 << 20;       // grid-stride beyond that
+        const dim3 grid((unsigned)nb), block(256);
+        if (group && vec) hipLaunchKernelGGL((rowadagrad_kernel<256, 4>), grid, block, 0, stream, p[i], acc[i], g[i], (long long)rows[i], len, lr);
+        else if (group) hipLaunchKernelGGL((rowadagrad_kernel<256, 1>), grid, block, 0, stream, p[i], acc[i], g[i], (long long)rows[i], len, lr);
+        else if (vec) hipLaunchKernelGGL((rowadagrad_kernel<64, 4>), grid, block, 0, stream, p[i], acc[i], g[i], (long long)rows[i], len, lr);
+        else hipLaunchKernelGGL((rowadagrad_kernel<64, 1>), grid, block, 0, stream, p[i], acc[i], g[i], (long long)rows[i], len, lr);
+    }
+    return hip_check(hipGetLastError(), "row-wise adagrad launch");
 }
 
 int launch_sgd(float *p, float *g, int64_t n, float lr, hipStream_t stream) {

@@ -1054,6 +1054,51 @@ __device__ __forceinline__ void adam_row_apply(float *p, float *m, float *v, con
     }
 }
 
+// RULE = kRuleRowAdagrad (a body of its own: the two rules above keep theirs).  The row's table base in `p` and its ONE accumulator
+// in `a` (RowRule::m holds [rows] floats here), for virtual row `row` or hub row `q` as adam_row_ptrs.
+__device__ __forceinline__ float *rowadagrad_row_ptrs(const FloatRowSpace &rs, const RowRule &ad, bool hub, long long row, int D, float *&a) {
+    int t;
+    long long r;
+    if (!hub) { t = row < rs.E ? 0 : 3; r = row < rs.E ? row : row - rs.E; }
+    else { t = row < rs.R ? 1 : 2; r = row < rs.R ? row : row - rs.R; }
+    a = ad.m[t] + r;
+    return (t == 0 ? rs.g_ent : t == 1 ? rs.g_rel : t == 2 ? rs.g_auxr : rs.g_auxe) + r * D;
+}
+
+// Row-wise Adagrad on one row from its complete gradient g (team layout: lane l holds groups l, l + L, ... of V floats; a lane's
+// groups past the row's end hold zeros -- the callers zero-fill and add inside `e < D` only -- so they add nothing to the sum of
+// squares at widths that are no multiple of the team's span).  Squares: a lane's elements in index order, then team_sum<L>,
+// which hands every lane of the team the same total.  Called by whole teams only (the reduction needs all L lanes).
+template <int L, int C, int V>
+__device__ __forceinline__ void rowadagrad_row_apply(float *p, float *a, const RowVec<V> (&g)[C], int lane, int D, float lr) {
+    RowVec<V> pv[C];
+    bool any[C];
+    float q = 0.f;
+#pragma unroll
+    for (int c = 0; c < C; c++) {
+        const int e = (lane + L * c) * V;
+        any[c] = false;
+#pragma unroll
+        for (int k = 0; k < V; k++) { q = rowadagrad_sq(q, g[c].x[k]); any[c] = any[c] || g[c].x[k] != 0.f; }
+        if (e < D && any[c]) pv[c].load(p + e);
+    }
+    float acc = *a;                     // one address for the team; read by every lane before lane 0 writes it below
+    q = team_sum<L>(q);
+    const float a_old = acc;
+    const float root = rowadagrad_root(acc, q, D);
+#pragma unroll
+    for (int c = 0; c < C; c++) {
+        const int e = (lane + L * c) * V;
+        if (e < D && any[c]) {          // a group whose gradient is all zero is neither read nor written
+#pragma unroll
+            for (int k = 0; k < V; k++)
+                if (g[c].x[k] != 0.f) pv[c].x[k] = rowadagrad_one(pv[c].x[k], g[c].x[k], lr, root);
+            pv[c].store(p + e);
+        }
+    }
+    if (lane == 0 && __builtin_bit_cast(unsigned, acc) != __builtin_bit_cast(unsigned, a_old)) *a = acc;
+}
+
 template <int L, int C, int V, int RULE>
 __global__ __launch_bounds__(256) void segsum_adam_runs_kernel(const float *__restrict__ rec, const int32_t *__restrict__ keys,
                                                                const int32_t *__restrict__ ids, const int32_t *__restrict__ n_valid_p,
@@ -1091,9 +1136,15 @@ __global__ __launch_bounds__(256) void segsum_adam_runs_kernel(const float *__re
             j++;
         } while (more);
         if (key < rs.hub_base) {
-            float *m, *v;
-            float *p = adam_row_ptrs(rs, ad, false, key, D, m, v);
-            adam_row_apply<L, C, V, RULE>(p, m, v, acc, lane, D, ad);
+            if constexpr (RULE == kRuleRowAdagrad) {
+                float *a;
+                float *p = rowadagrad_row_ptrs(rs, ad, false, key, D, a);
+                rowadagrad_row_apply<L, C, V>(p, a, acc, lane, D, ad.lr_t);
+            } else {
+                float *m, *v;
+                float *p = adam_row_ptrs(rs, ad, false, key, D, m, v);
+                adam_row_apply<L, C, V, RULE>(p, m, v, acc, lane, D, ad);
+            }
         } else {
             float *p = hub_sums + (long long)(key - rs.hub_base) * D;
 #pragma unroll
@@ -1139,9 +1190,15 @@ __global__ __launch_bounds__(256) void hub_fold_adam_kernel(float *__restrict__ 
         // every lane has consumed the marks it read (the branch above depends on them) before lane 0 clears them
         if (lane == 0)
             for (int k = 0; k < K; k++) hub_marks[(long long)k * rs.hub_rows + q] = 0;
-        float *m, *v;
-        float *p = adam_row_ptrs(rs, ad, true, q, D, m, v);
-        adam_row_apply<L, C, V, RULE>(p, m, v, acc, lane, D, ad);
+        if constexpr (RULE == kRuleRowAdagrad) {     // (the row's sum arrives from the fold: the squares are summed here, once, over the whole row)
+            float *a;
+            float *p = rowadagrad_row_ptrs(rs, ad, true, q, D, a);
+            rowadagrad_row_apply<L, C, V>(p, a, acc, lane, D, ad.lr_t);
+        } else {
+            float *m, *v;
+            float *p = adam_row_ptrs(rs, ad, true, q, D, m, v);
+            adam_row_apply<L, C, V, RULE>(p, m, v, acc, lane, D, ad);
+        }
     }
 }
 
@@ -1411,6 +1468,7 @@ void launch_segsum_rule(int64_t M, const float *rec, const FloatRowSpace &rs, co
 template <int L, int C, int V>
 void launch_segsum_adam(int64_t M, const float *rec, const FloatRowSpace &rs, const RowRule &ad, int D, int K, hipStream_t stream) {
     if (ad.rule == kRuleAdagrad) launch_segsum_rule<L, C, V, kRuleAdagrad>(M, rec, rs, ad, D, K, stream);
+    else if (ad.rule == kRuleRowAdagrad) launch_segsum_rule<L, C, V, kRuleRowAdagrad>(M, rec, rs, ad, D, K, stream);
     else launch_segsum_rule<L, C, V, kRuleAdam>(M, rec, rs, ad, D, K, stream);
 }
 
@@ -1501,8 +1559,9 @@ int float_records_reduce_adam(int64_t M, int D, const FloatRowSpace &rs, const R
     // float4 rows where every row of every buffer starts on 16 bytes
     bool vec = D % 4 == 0 && (reinterpret_cast<uintptr_t>(rec) & 15) == 0;
     const float *const bases[4] = {rs.g_ent, rs.g_rel, rs.g_auxr, rs.g_auxe};
+    const bool row_slots = ad.rule == kRuleRowAdagrad;       // (one float per row, read as a float: no alignment to ask of it)
     for (int t = 0; t < 4; t++)
-        vec = vec && ((reinterpret_cast<uintptr_t>(bases[t]) | reinterpret_cast<uintptr_t>(ad.m[t]) | reinterpret_cast<uintptr_t>(ad.v[t])) & 15) == 0;
+        vec = vec && ((reinterpret_cast<uintptr_t>(bases[t]) | (row_slots ? 0 : reinterpret_cast<uintptr_t>(ad.m[t])) | reinterpret_cast<uintptr_t>(ad.v[t])) & 15) == 0;
     // groups of V floats per row; the float4 ladder stops at (64, 4): 256 units = width 1024
     const int units = vec ? std::min(D / 4, 256) : D;
     for_team_shape_or_last(units, [&](auto t) {
@@ -2005,6 +2064,69 @@ void launch_segsum(bool nat, int64_t M, const uint32_t *rec, const int32_t *n_va
                             n_valid_p, uidx, S, D, fold);
 }
 
+// Row-wise Adagrad over a row list from sign counts, a kernel of its own (apply_row_update keeps its three rules and their
+// instructions).  The row's gradient is formed as apply_row_update forms it in the row-list form -- counts through the
+// normalisation's backward, no residuals -- on the same team shape, so g has the bits kge_transe_apply_rows_adagrad sees; then
+// the rule of optim_dev.hpp with the row's ONE accumulator (a.m / a.m2: [E] and [R] floats).  A listed row whose counts are all
+// zero is left alone, accumulator included: no live mask is needed where every row of a table is listed.
+template <int L, int C>
+__global__ __launch_bounds__(256) void apply_rows_rowadagrad_kernel(ApplyArgs a) {
+#pragma clang fp contract(off)
+    constexpr int TEAMS = 256 / L;
+    Team<L, C> tm;
+    tm.lane = threadIdx.x % L;
+    tm.D = a.D;
+    const long long n_rows = (long long)a.n_rows[0];
+    for (long long i = (long long)blockIdx.x * TEAMS + threadIdx.x / L; i < n_rows; i += (long long)gridDim.x * TEAMS) {
+        long long row = (long long)a.row_list[i];
+        float *table = a.p, *at = a.m;
+        if (row >= a.E) { row -= a.E; table = a.p2; at = a.m2; }
+        const int32_t *Sp = a.S + i * a.D;
+        float s[C];
+        float touched = 0.f;
+#pragma unroll
+        for (int c = 0; c < C; c++) {
+            const int e = tm.lane + L * c;
+            s[c] = (float)(e < a.D ? Sp[e] : 0);
+            touched += s[c] != 0.f ? 1.f : 0.f;
+        }
+        touched = team_sum<L>(touched);
+        if (touched == 0.f) continue;           // (the same for every lane of the team)
+        float x[C], xn[C], g[C], inv;
+        bool uc;
+        tm.load(table, row, x);
+        float acc = at[row];                    // read by every lane before lane 0 writes it below
+        tm.normalize(x, xn, inv, uc);
+        float d = tm.dot(xn, s);
+        if (!uc) d = 0.f;
+        float q = 0.f;
+#pragma unroll
+        for (int c = 0; c < C; c++) {           // lanes past the row's end: s = xn = 0, so g = 0 and nothing is added to q
+            g[c] = add_rn(count_grad(a.unit, inv, s[c], d, xn[c]), 0.f);
+            q = rowadagrad_sq(q, g[c]);
+        }
+        q = team_sum<L>(q);
+        const float a_old = acc;
+        const float root = rowadagrad_root(acc, q, a.D);
+        float *pp = table + row * a.D;
+#pragma unroll
+        for (int c = 0; c < C; c++) {
+            const int e = tm.lane + L * c;
+            if (e < a.D && g[c] != 0.f) pp[e] = rowadagrad_one(x[c], g[c], a.lr, root);
+        }
+        if (tm.lane == 0 && __builtin_bit_cast(unsigned, acc) != __builtin_bit_cast(unsigned, a_old)) at[row] = acc;
+    }
+}
+
+void launch_apply_listed_rows_rowadagrad(const ApplyArgs &a, long long max_rows, hipStream_t stream) {
+    for_transe_team_shape_or_last(a.D, [&](auto t) {
+        constexpr int L = decltype(t)::L, C = decltype(t)::C;
+        long long nb = (max_rows + (256 / L) - 1) / (256 / L);
+        if (nb > 8192) nb = 8192;
+        hipLaunchKernelGGL((apply_rows_rowadagrad_kernel<L, C>), dim3((unsigned)nb), dim3(256), 0, stream, a);
+    });
+}
+
 // apply_counts_kernel over a row list: row-wise SGD, lazy Adam and Adagrad are the same launch
 void launch_apply_listed_rows(const ApplyArgs &a, long long max_rows, hipStream_t stream) {
     for_transe_team_shape_or_last(a.D, [&](auto t) {
@@ -2437,6 +2559,24 @@ int kge_transe_apply_rows_adagrad(const kge_model_desc *m, float *d_ent, float *
     a.E = m->ent_total; a.D = m->ent_dim; a.unit = 1.0f / (float)denom; a.lr = lr; a.opt = kOptAdagrad;
     launch_apply_listed_rows(a, max_rows, stream);
     return hip_check(hipGetLastError(), "adagrad rows launch");
+}
+
+int kge_transe_apply_rows_rowadagrad(const kge_model_desc *m, float *d_ent, float *d_rel, float *d_acc_ent, float *d_acc_rel, const int32_t *d_rows,
+                                     const int32_t *d_row_counts, const int32_t *d_n_rows, INT max_rows, INT denom, float lr, void *stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    if (!device_ok()) return fail(KGE_ERR_NO_DEVICE, "kge_transe_apply_rows_rowadagrad: no usable HIP device");
+    if (!m || !d_ent || !d_rel || !d_acc_ent || !d_acc_rel || !d_rows || !d_row_counts || !d_n_rows || denom <= 0)
+        return fail(KGE_ERR_BAD_ARG, "kge_transe_apply_rows_rowadagrad: bad arguments");
+    if (m->model != KGE_TRANSE || m->ent_dim != m->rel_dim || m->ent_dim > 1024)
+        return fail(KGE_ERR_UNSUPPORTED, "kge_transe_apply_rows_rowadagrad: the sign-count path is TransE's, dim <= 1024");
+    tables_written();
+    if (max_rows <= 0) return KGE_OK;
+    ApplyArgs a = {};
+    a.p = d_ent; a.p2 = d_rel; a.m = d_acc_ent; a.m2 = d_acc_rel;      // (one float per row)
+    a.row_list = d_rows; a.S = const_cast<int32_t *>(d_row_counts); a.n_rows = d_n_rows;
+    a.E = m->ent_total; a.D = m->ent_dim; a.unit = 1.0f / (float)denom; a.lr = lr; a.opt = kOptSgd;    // (opt is not read by this kernel)
+    launch_apply_listed_rows_rowadagrad(a, max_rows, stream);
+    return hip_check(hipGetLastError(), "row-wise adagrad rows launch");
 }
 
 int kge_transe_apply_counts(float *d_p, float *d_m, float *d_v, int32_t *d_counts, float *d_resid, int64_t rows, int32_t dim,

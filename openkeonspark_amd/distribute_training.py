@@ -7,8 +7,8 @@ patience + 5` (`:103,226-234`), loss-based early stop with `stop.txt` (`:336-360
 on restore (`main_spark.py:74-98`: xavier rows for parameters, zero rows for the Adam slots, rows of the initial value for Adagrad's accumulators).  One
 process per GPU (torchrun) replaces the ps/worker cluster; rank 0 plays the chief.
 
-A run whose entity table is sharded by row range (`--sparse_rows 1` on N ranks, SGD, LazyAdam or Adagrad) checkpoints without gathering
-it: every rank writes its rows -- with LazyAdam their two moment rows, with Adagrad their accumulator rows too -- into `model.ckpt-<step>.shard<g>of<N>.npz` beside the
+A run whose entity table is sharded by row range (`--sparse_rows 1` on N ranks, SGD, LazyAdam, Adagrad or RowAdagrad) checkpoints without gathering
+it: every rank writes its rows -- with LazyAdam their two moment rows, with Adagrad their accumulator rows, with RowAdagrad their one accumulator each too -- into `model.ckpt-<step>.shard<g>of<N>.npz` beside the
 main file.  Such a checkpoint resumes at any number of ranks or in one process, a one-process checkpoint resumes sharded, and
 new entities are grown on shards exactly as one process grows them.
 
@@ -64,7 +64,10 @@ def parse_args(argv=None):
                    help="SGD (the default, and what any other name means), Adam (TF1's AdamOptimizer: every row moves every step), "
                         "LazyAdam (opt-in, non-parity: the Adam rule on the rows a step touches) or Adagrad (TF1's AdagradOptimizer, "
                         "accumulators from 0.1: on the touched rows for TransE / TransH / TransD, which is exactly the dense rule; one "
-                        "accumulator table per parameter table, checkpointed as <var>/Adagrad; TransR in one process only)")
+                        "accumulator table per parameter table, checkpointed as <var>/Adagrad; TransR in one process only) or RowAdagrad "
+                        "(PyTorch-BigGraph's row-wise Adagrad: ONE accumulator per table row, which takes the row's mean squared "
+                        "gradient, from 0.1 and without an epsilon; the same touched-rows paths, exact likewise; checkpointed as "
+                        "<var>/RowAdagrad, float32 [rows]; TransR in one process only)")
     p.add_argument("--early_stop_patience", type=int, default=5)
     p.add_argument("--early_stop_stopping_step", type=int, default=1)
     p.add_argument("--early_stop_start_step", type=int, default=1)
@@ -223,6 +226,10 @@ def checkpoint_arrays(con):
         for name, a in zip(con.trainModel.table_names, con._adagrad_acc):
             if not con._sharded(name):
                 out[name + "/Adagrad"] = a.detach().cpu().numpy()
+    if getattr(con, "_row_adagrad", False):  # one float per row, float32 [rows]; a shard-sized one is in the shard file as `rowadagrad`
+        for name, a in zip(con.trainModel.table_names, con._rowadagrad_acc):
+            if not con._sharded(name):
+                out[name + "/RowAdagrad"] = a.detach().cpu().numpy()
     out["global_step"] = np.int64(con.global_step)
     if getattr(con, "_shared_chunk", 0):      # shared negatives: the candidates are a hash of (seed, global_step), chunked by `chunk`
         out["shared_negatives"] = shared_negatives_record(con)
@@ -300,6 +307,8 @@ def save_checkpoint(con, output_path, max_to_keep=10, write=True):
             parts.update(adam=host(con._adam_m[0]), adam_1=host(con._adam_v[0]))
         if getattr(con, "_adagrad", False):     # Adagrad: the accumulator rows do
             parts.update(adagrad=host(con._adagrad_acc[0]))
+        if getattr(con, "_row_adagrad", False): # RowAdagrad: one accumulator per entity row
+            parts.update(rowadagrad=host(con._rowadagrad_acc[0]))
         _atomic_savez(base + ".shard%dof%d.npz" % (con.rank, con.world_size), **parts)
         import torch.distributed as dist
         con.comm_fence("pg")
@@ -353,7 +362,7 @@ def read_entity_rows(base, lo, hi, dim, key="rows", parts=None, fill=0.0):
     (array of hi - lo rows, ent_total): rows at or beyond the checkpoint's entity count `ent_total` are NEW entities, left at
     `fill` (zero: for the caller to fill, or an Adam moment; an Adagrad accumulator starts at its initial value); a row below it that no shard file holds is an error (shard_files; `parts`: its result)."""
     parts, ent_total = parts if parts is not None else shard_files(base, (key,))
-    out = np.full((hi - lo, dim), fill, np.float32)
+    out = np.full((hi - lo,) if dim is None else (hi - lo, dim), fill, np.float32)     # dim None: one value per row (`rowadagrad`)
     for path, plo, phi in parts:
         a, b = max(lo, plo), min(hi, phi, ent_total)
         if a < b:
@@ -362,16 +371,19 @@ def read_entity_rows(base, lo, hi, dim, key="rows", parts=None, fill=0.0):
     return out, ent_total
 
 
-def slot_keys(z, adam_slots, adagrad):
+def slot_keys(z, adam_slots, adagrad, row_adagrad=False):
     """Which arrays a shard file must hold beside `rows` for a run with these optimizer slots resuming the checkpoint whose main
     file is `z`: the two moment arrays where an Adam-family run resumes an Adam-family checkpoint (it has `beta1_power`), the
-    accumulator where an Adagrad run resumes an Adagrad checkpoint (its replicated tables have `<var>/Adagrad`).  Anything else
+    accumulator where an Adagrad run resumes an Adagrad checkpoint (its replicated tables have `<var>/Adagrad`), the per-row
+    accumulator `rowadagrad` where a RowAdagrad run resumes a RowAdagrad checkpoint (`<var>/RowAdagrad`).  Anything else
     -- an SGD checkpoint, or slots the new run has no use for -- reads the rows alone: the run starts from fresh slots."""
     keys = ("rows",)
     if adam_slots and "beta1_power" in z:
         keys += ("adam", "adam_1")
     if adagrad and any(k.endswith("/Adagrad") for k in z):
         keys += ("adagrad",)
+    if row_adagrad and any(k.endswith("/RowAdagrad") for k in z):
+        keys += ("rowadagrad",)
     return keys
 
 
@@ -410,16 +422,27 @@ def _set_accumulator(con, i, name, acc):
         con._adagrad_acc[i].copy_(torch.from_numpy(np.ascontiguousarray(acc.reshape(tuple(con._adagrad_acc[i].shape)))))
 
 
+def _set_row_accumulator(con, i, name, acc):
+    """RowAdagrad accumulator of table i from a whole [rows] array; a sharded entity table keeps its rows [lo, hi)."""
+    import torch
+    if con._sharded(name):
+        lo, hi = con._shard["lo"], con._shard["hi"]
+        con._rowadagrad_acc[i][:hi - lo].copy_(torch.from_numpy(np.ascontiguousarray(acc[lo:hi])))
+    else:
+        con._rowadagrad_acc[i].copy_(torch.from_numpy(np.ascontiguousarray(acc)))
+
+
 def _restore_sharded_rows(con, i, name, base, z, rows, dim, allow_growth, rng):
     """Table i (the entity table) from the shard files of a sharded checkpoint, into this rank's shard [lo, hi) of the new run or,
     in one process, whole.  Rows of entities the checkpoint does not know are grown as one process grows them (grow_table):
     every rank draws the same xavier block for rows [ent_total, rows) from `rng` and keeps its own part; their moments are zero.
     An Adam-family checkpoint (it has `beta1_power`) resumed with slots must carry the moment rows in its shard files; an SGD
     checkpoint resumed with slots starts from zero moments.  Adagrad alike (slot_keys): its accumulator rows come from the shard
-    files' `adagrad`, new entities' rows -- and every row, from a checkpoint without accumulators -- hold the initial value."""
+    files' `adagrad`, new entities' rows -- and every row, from a checkpoint without accumulators -- hold the initial value.
+    RowAdagrad the same with `rowadagrad`, one value per row."""
     import torch
-    adagrad = getattr(con, "_adagrad", False)
-    keys = slot_keys(z, con._has_slots, adagrad)
+    adagrad, row_adagrad = getattr(con, "_adagrad", False), getattr(con, "_row_adagrad", False)
+    keys = slot_keys(z, con._has_slots, adagrad, row_adagrad)
     parts = shard_files(base, keys)
     ent_total = parts[1]
     if rows != ent_total and (not allow_growth or rows < ent_total):
@@ -435,9 +458,13 @@ def _restore_sharded_rows(con, i, name, base, z, rows, dim, allow_growth, rng):
         dsts.update(adagrad=con._adagrad_acc[i])
     elif adagrad:
         con._adagrad_acc[i].fill_(float(con.adagrad_initial_accumulator))
+    if "rowadagrad" in keys:
+        dsts.update(rowadagrad=con._rowadagrad_acc[i])
+    elif row_adagrad:
+        con._rowadagrad_acc[i].fill_(float(con.adagrad_initial_accumulator))
     for key, dst in dsts.items():
-        part, _ = read_entity_rows(base, lo, hi, dim, key, parts,
-                                   fill=float(con.adagrad_initial_accumulator) if key == "adagrad" else 0.0)
+        part, _ = read_entity_rows(base, lo, hi, None if key == "rowadagrad" else dim, key, parts,
+                                   fill=float(con.adagrad_initial_accumulator) if key in ("adagrad", "rowadagrad") else 0.0)
         if key == "rows" and new is not None and hi > ent_total:
             a = max(lo, ent_total)
             part[a - lo:] = new[a - ent_total:hi - ent_total]
@@ -479,6 +506,14 @@ def restore_checkpoint(con, path, allow_growth=True, arrays=None):
             acc = grow_table(z[name + "/Adagrad"], rows, rng, zeros=True, fill=a0) if name + "/Adagrad" in z else \
                 np.full((rows, shapes[name][1]), a0, np.float32)
             _set_accumulator(con, i, name, acc)
+        if getattr(con, "_row_adagrad", False):  # likewise; rows of new entities start at the initial value
+            acc = np.full(rows, float(con.adagrad_initial_accumulator), np.float32)
+            if name + "/RowAdagrad" in z:
+                old = np.asarray(z[name + "/RowAdagrad"], np.float32).reshape(-1)
+                if old.shape[0] > rows:
+                    raise ValueError("checkpoint accumulator %s/RowAdagrad has %d rows, model needs %d" % (name, old.shape[0], rows))
+                acc[:old.shape[0]] = old
+            _set_row_accumulator(con, i, name, acc)
     if con._has_slots and "beta1_power" in z:
         con._beta1_power = np.float32(z["beta1_power"])
         con._beta2_power = np.float32(z["beta2_power"])

@@ -11,11 +11,12 @@ from ._lib import KgeError, TRANSE, TRANSH, TRANSR, TRANSD
 # accepted spellings of the optimizer names (distribute_training.py:95 for Adam); any other name trains with SGD, as the reference does
 _KINDS = {"Adam": "adam", "adam": "adam",
           "LazyAdam": "lazy_adam", "lazyadam": "lazy_adam", "lazy_adam": "lazy_adam",
-          "Adagrad": "adagrad", "adagrad": "adagrad"}
+          "Adagrad": "adagrad", "adagrad": "adagrad",
+          "RowAdagrad": "row_adagrad", "rowadagrad": "row_adagrad", "row_adagrad": "row_adagrad"}
 
 
 def optimizer_kind(name):
-    """"sgd", "adam", "lazy_adam" or "adagrad"."""
+    """"sgd", "adam", "lazy_adam", "adagrad" or "row_adagrad"."""
     return _KINDS.get(name, "sgd") if isinstance(name, str) else "sgd"
 
 
@@ -38,6 +39,10 @@ class StepPlan(namedtuple("StepPlan", "optimizer use_counts sparse_rows sparse_i
         return self.optimizer == "adagrad"
 
     @property
+    def row_adagrad(self):
+        return self.optimizer == "row_adagrad"
+
+    @property
     def has_slots(self):
         """m / v tables and beta powers exist (both Adam flavours)."""
         return self.optimizer in ("adam", "lazy_adam")
@@ -45,7 +50,7 @@ class StepPlan(namedtuple("StepPlan", "optimizer use_counts sparse_rows sparse_i
     @property
     def rows_rule(self):
         """Optimizers that ARE a choice of touched rows."""
-        return self.optimizer in ("lazy_adam", "adagrad")
+        return self.optimizer in ("lazy_adam", "adagrad", "row_adagrad")
 
 
 def wants_sparse_rows(sparse_rows, ent_total, rel_total, width, batch_size, n_neg, sparse_threshold_bytes=None):
@@ -81,16 +86,21 @@ def plan(model_id, opt_method, sparse_rows, use_counts, counts_supported, ent_to
     dense gradient tables: the plan of its unshared step)."""
     optimizer = optimizer_kind(opt_method)
     adam, lazy_adam, adagrad = optimizer == "adam", optimizer == "lazy_adam", optimizer == "adagrad"
+    row_adagrad = optimizer == "row_adagrad"
     # LazyAdam -- opt-in, NON-PARITY: Adam on the touched rows only (tf.contrib.opt.LazyAdamOptimizer's rule) for tables whose dense
     # TF1-Adam sweep -- 32 bytes per element per step, the reference's semantics -- would dominate the step.
     # Adagrad -- opt-in: TF1's AdagradOptimizer (upstream OpenKE offers it; the reference sends the name to SGD).  Like LazyAdam it
     # rides on the touched-rows paths, but exactly: an element with zero gradient keeps its value and its accumulator bit for bit,
     # so "only the touched rows" IS the dense rule.  One accumulator table per parameter table, nothing to advance between steps.
     # TransR has no record path and keeps its dense gradient tables (kge_adagrad_update_tables), in one process only.
-    if adagrad and not (float(adagrad_initial_accumulator) > 0.0):
+    # RowAdagrad -- opt-in: PyTorch-BigGraph's row-wise Adagrad, ONE accumulator per table row, which takes the mean squared gradient
+    # of the row each step (a += sum g^2 / L; p -= lr * g / sqrt(a)).  Exact on the touched rows for Adagrad's reason -- a row whose
+    # gradient is zero keeps its value and its accumulator bit for bit -- and on the same paths; it starts from the same positive
+    # value (adagrad_initial_accumulator) and has no epsilon.  TransR: dense tables (kge_rowadagrad_update_tables), one process.
+    if (adagrad or row_adagrad) and not (float(adagrad_initial_accumulator) > 0.0):
         raise KgeError("adagrad_initial_accumulator must be positive (the Adagrad rule divides by sqrt(accumulator), without an "
                        "epsilon), got %r" % (adagrad_initial_accumulator,))
-    rows_rule = lazy_adam or adagrad
+    rows_rule = lazy_adam or adagrad or row_adagrad
     # TransE: exact integer sign-count gradients instead of fp32 atomics (include/kge_mi355.h)
     use_counts = bool(use_counts) and bool(counts_supported)
     # sparse-row mode: no dense gradient / count image at all.  The int8 records are reduced into a compact
@@ -163,7 +173,7 @@ def check_shared_negatives(model_id, optimizer, use_counts, chunk, negative_ent,
     if not 1 <= negative_ent <= SHARED_MAX_NEGATIVES:
         raise KgeError("shared negatives: 1 to %d negatives per positive (a positive's count lies within +-2N and is carried as "
                        "an int8), got %d" % (SHARED_MAX_NEGATIVES, negative_ent))
-    if transr:      # (the gradients are dense tables: SGD, Adagrad and TF1 Adam sweep them as they do in the unshared step)
+    if transr:      # (the gradients are dense tables: SGD, Adagrad, RowAdagrad and TF1 Adam sweep them as they do in the unshared step)
         if optimizer == "lazy_adam":
             raise KgeError("LazyAdam (touched rows only, NON-PARITY) needs TransE, TransH or TransD: TransR's gradient is a whole "
                            "matrix per relation and has no record path")

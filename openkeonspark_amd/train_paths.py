@@ -12,7 +12,7 @@ from ._lib import KgeError
 
 
 class RowsRule(object):
-    """The optimizer of the touched-rows paths -- SGD, lazy Adam or Adagrad -- as a host-side dispatch: which C entry point each
+    """The optimizer of the touched-rows paths -- SGD, lazy Adam, Adagrad or row-wise Adagrad -- as a host-side dispatch: which C entry point each
     of the three row-wise applications goes to, with which slot tables and which rate arguments.  Made by
     Config._refresh_pointers (it holds table and slot pointers) ; alpha and lazy Adam's lr_t are read from the Config at call
     time.  The SGD entry points are kernels of their own (atomic adds, a fused reduce-apply), not a third case of the device's
@@ -34,6 +34,11 @@ class RowsRule(object):
                 L.kge_forward_backward_adagrad_rows, L.kge_float_records_apply_adagrad, L.kge_transe_apply_rows_adagrad
             self.slot_ptrs = (con._adagrad_ptrs,)
             self.row_slots = (con._adagrad_acc[0].data_ptr(), con._adagrad_acc[1].data_ptr())
+        elif kind == "row_adagrad":     # one accumulator per table row: [rows] floats where Adagrad has a table
+            self._fb_rows, self._float_records, self._listed_rows = \
+                L.kge_forward_backward_rowadagrad_rows, L.kge_float_records_apply_rowadagrad, L.kge_transe_apply_rows_rowadagrad
+            self.slot_ptrs = (con._rowadagrad_ptrs,)
+            self.row_slots = (con._rowadagrad_acc[0].data_ptr(), con._rowadagrad_acc[1].data_ptr())
         else:
             self._fb_rows, self._float_records, self._listed_rows = \
                 L.kge_forward_backward_sgd_rows, L.kge_float_records_apply, L.kge_transe_apply_rows_sgd
@@ -71,7 +76,7 @@ class RowsRule(object):
     def reduce_apply(self, desc, rec, dst, n, buf, denom, fused_ok):
         """`n` int8 records (`rec`, destination rows `dst`) -> per-row sign counts in buf's rows / row_counts / n_rows -> the rule
         on those rows.  SGD with fused_ok: reduce + apply in one pass, only chunk-boundary rows go through the compact count
-        image.  (Lazy Adam and Adagrad are not linear in the gradient: they need a row's complete sum.)"""
+        image.  (Lazy Adam and both Adagrads are not linear in the gradient: they need a row's complete sum.)"""
         con = self.con
         rows, counts, n_rows = buf["rows"].data_ptr(), buf["row_counts"].data_ptr(), buf["n_rows"].data_ptr()
         if self.kind == "sgd" and fused_ok:
@@ -207,6 +212,12 @@ def setup_shards(con):
         con._adagrad_acc[0] = torch.full((chunk, D), float(con.adagrad_initial_accumulator), dtype=torch.float32, device=shard.device)
         if hi > lo:
             con._adagrad_acc[0][:hi - lo].copy_(old[lo:hi])
+        del old
+    if con._row_adagrad:   # ... and the per-row accumulators of the entity rows, one float each
+        old = con._rowadagrad_acc[0]
+        con._rowadagrad_acc[0] = torch.full((chunk,), float(con.adagrad_initial_accumulator), dtype=torch.float32, device=shard.device)
+        if hi > lo:
+            con._rowadagrad_acc[0][:hi - lo].copy_(old[lo:hi])
         del old
     torch.cuda.empty_cache()
     con._shard = dict(chunk=chunk, lo=lo, hi=hi)

@@ -25,9 +25,10 @@ def main():
     ap.add_argument("--dense", action="store_true", help="dense count image instead of the sparse-row path")
     ap.add_argument("--force-dp", action="store_true", help="one-rank RCCL group + Config.force_data_parallel: the table-sharded multi-GPU step, every exchange a copy")
     ap.add_argument("--model", default="TransE", help="TransE | TransH | TransD (the latter two: --dense = gradient tables + sweep, else the row-wise "
-                                                      "update in place from float records: SGD, or with --opt LazyAdam / Adagrad that rule on the touched rows)")
+                                                      "update in place from float records: SGD, or with --opt LazyAdam / Adagrad / RowAdagrad that rule on the touched rows)")
     ap.add_argument("--opt", default="SGD", help="SGD | Adam (TF1 dense sweep, parity; implies --dense) | LazyAdam (touched rows only, NON-PARITY) | "
-                                             "Adagrad (TF1 AdagradOptimizer on the touched rows: exact)")
+                                             "Adagrad (TF1 AdagradOptimizer on the touched rows: exact) | RowAdagrad (row-wise Adagrad, one accumulator "
+                                             "per table row, on the touched rows: exact)")
     a = ap.parse_args()
     import numpy as np
     import torch
@@ -83,6 +84,7 @@ def main():
         ("dense image / gradient tables + sweep" if (a.dense or a.opt == "Adam") else
          "sparse rows: lazy Adam in place from float records" if (con.sparse_inplace and con._lazy_adam) else
          "sparse rows: Adagrad in place from float records" if (con.sparse_inplace and con._adagrad) else
+         "sparse rows: row-wise Adagrad in place from float records" if (con.sparse_inplace and con._row_adagrad) else
          "sparse rows: SGD in place from float records" if con.sparse_inplace else "sparse rows") +
         (", data-parallel step on a one-rank RCCL group" if a.force_dp and con.sparse_inplace else
          ", table-sharded step on a one-rank RCCL group" if a.force_dp else "")),
