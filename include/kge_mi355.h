@@ -777,6 +777,41 @@ int kge_transe_emit_records_shared_chunks(const kge_model_desc *m, const float *
                                           const int32_t *d_r2, INT n_pos, INT stride, const int32_t *d_chunks, INT cap, const int32_t *d_cand, INT N,
                                           const uint8_t *d_pair, INT denom, uint32_t *d_rec, int32_t *d_dst, float *d_loss, void *stream);
 
+/* ---- In-chunk candidates (NON-PARITY, opt-in; csrc/shared_neg.hip) ----
+ * Batch negatives (PyTorch-BigGraph's num_batch_negs, DGL-KE's neg_deg_sample): beside the N DRAWN candidates of a relation-grouped
+ * chunk, K more are the entities of the chunk's own positives.  They are sampled by the data distribution and, on chunks of one
+ * relation, type-consistent by construction.  The order, the chunk table, cap, S, mix, G, the drawn candidates, their sides and
+ * their masks are those of "Shared negatives on RELATION-GROUPED chunks"; none of them changes.
+ * N = the drawn candidates per chunk, K >= 0 the in-chunk ones, Nt = N + K.  A used chunk slot j = (first_j, len_j) of relation
+ * rho_j has Nt candidate columns:
+ *   Columns k < N.       The section above's candidate and side: the same hash keys, the same bits for every K.
+ *   Columns k = N + i, 0 <= i < K.
+ *     Side.       The per-candidate formula above with this k: v = ((mix(S + (((j << 8) | 128 | k) + 1) G) >> 32) * 1000) >> 32,
+ *                 the same Bernoulli / 500 comparison (k <= 62: the key space reserved for sides).
+ *     Rotation.   o_j = ((mix(S + (((j << 8) | 64) + 1) G) >> 32) * len_j) >> 32.  No candidate key (k <= 62) and no side key
+ *                 (>= 128) has the low byte 64.
+ *     Id.         i < len_j: q = first_j + ((o_j + i) mod len_j); the id is t2[q] for a new tail, h2[q] for a new head.
+ *                 i >= len_j: the id is -1 and every pair of the column is masked.  The type lists are not consulted.
+ *     Trailing run.  A slot whose relation lies outside [0, rel_total) has its K in-chunk ids at -1 and their pairs masked; its
+ *                 drawn columns stay what the section above makes them, and its positives take no part, as ever.
+ *   Mask of an in-chunk pair (b, k): the lookup above (the corrupted triple is a training triple), OR the candidate id equals
+ *                 the entity it replaces -- t2[b] for a new tail, h2[b] for a new head.  The second rule is for in-chunk columns
+ *                 alone: a hand-fed positive that is not a training triple does not score against itself.
+ *   Unused slots have all Nt ids at -1.
+ *   Loss, records.  The section above's with Nt for N: the denominator is batch_size Nt, masked pairs and -1 columns stay in it.
+ *                 TransE 3 n_pos + cap Nt records, TransH 2 n_pos + cap (Nt + 2), TransD 4 n_pos + cap (2 Nt + 2), TransR
+ *                 2 n_pos + cap Nt rows through the GEMMs.  Every emit entry point is called with Nt where it took N and with the
+ *                 wider lists; a candidate id outside the table is masked for every pair in all of them (TransR projects row 0 in
+ *                 its place and gives it no gradient).  The K rows are gathered again, not re-used from the positives on chip.
+ *   Limit.      1 <= N, 0 <= K, N + K <= 63: a positive's sign count lies within +-2 Nt <= 126; a candidate's within +-P as before
+ *                 (an in-chunk candidate meets at most P positives), so the LDS byte fields still see at most 2 P.
+ * kge_shared_negatives_draw_grouped_mixed: d_cand (int32 [cap][N + K]) and d_pair (uint8 [n_pos][N + K]) of a table, by a sibling of
+ *   the grouped draw kernel (a thread per pair and per candidate, no LDS, no scratch): a pair thread of an in-chunk column has its
+ *   slot from the bisection, hashes o_j and gathers one more id.  K = 0 IS kge_shared_negatives_draw_grouped, bit for bit. */
+int kge_shared_negatives_draw_grouped_mixed(const int32_t *d_h2, const int32_t *d_t2, const int32_t *d_r2, INT n_pos, const int32_t *d_chunks,
+                                            INT cap, INT N, INT K, INT typed, uint64_t seed, INT step, int32_t *d_cand, uint8_t *d_pair,
+                                            void *stream);
+
 /* ---- TransH on relation-grouped chunks (NON-PARITY, opt-in; csrc/shared_proj.hip) ----
  * Every positive of a relation-grouped chunk has the chunk's relation, so a chunk has ONE normalised normal vector and ONE r^,
  * and a candidate is projected and normalised once per chunk: a chunk gathers 2 P + N + 2 table rows where the unshared step

@@ -56,6 +56,7 @@ class Config(object):
             self.type_constrained_sampling = False
             self._shared_chunk, self._shared_seed = 0, 0      # set_shared_negatives
             self._shared_by_relation = False                  # ... its chunks are cut from the batch ordered by relation
+            self._shared_in_chunk = 0                         # ... K of a chunk's candidates are its own positives' entities
             # engine-side additions
             self.seed = 0                 # parameter initialisation seed
             self.device = "cuda"
@@ -147,7 +148,7 @@ class Config(object):
         if getattr(self, "trainTotal", None) is not None:      # after init(): switch the engine now
             self._apply_typed_sampling()
 
-    def set_shared_negatives(self, chunk, seed=0, by_relation=False):
+    def set_shared_negatives(self, chunk, seed=0, by_relation=False, in_chunk=0):
         """Negatives SHARED by chunks of positives (NON-PARITY, opt-in, off by default; the reference draws every negative for
         one positive): `chunk` consecutive positives of a batch score the same set_ent_neg_rate(N) candidate entities, drawn
         from a counter hash of (seed, global_step) -- what PyTorch-BigGraph and DGL-KE do -- so a chunk gathers 3 chunk + N table
@@ -173,7 +174,13 @@ class Config(object):
         relation-grouped chunks").  TransR trains the same way (by_relation=True only, rel_dim up to 512; SGD, Adagrad or TF1 Adam,
         not LazyAdam): a chunk shares its relation's matrix, so 2 chunk + N rows go through the projection, dgrad and wgrad GEMMs
         where the unshared step puts chunk (2 + N), and the gradients are the dense tables of the unshared TransR step ("TransR on
-        relation-grouped chunks")."""
+        relation-grouped chunks").
+        in_chunk=K (by_relation=True only, every model above): beside the N drawn candidates a chunk scores K of its OWN entities --
+        PyTorch-BigGraph's batch negatives: column N + i of a chunk is the tail (the head, for a new-head column) of the positive
+        at rotated position i of the chunk, so the K candidates follow the data distribution and are observed heads / tails of
+        the chunk's relation whether or not it has a type list, which is not consulted for them.  A chunk shorter than K leaves
+        the columns past its length empty (-1, masked); a candidate equal to the entity it would replace is masked.  The loss and
+        every record count take N + K where they took N; N + K <= 63 ("In-chunk candidates").  0 = off: the step is today's."""
         if self.trainModel is not None:
             raise KgeError("set_shared_negatives must be called before set_model_and_session: it decides the step's path")
         chunk = int(chunk)
@@ -183,7 +190,10 @@ class Config(object):
         by_relation = bool(by_relation) and chunk > 0
         if chunk and self.type_constrained_sampling and not by_relation:
             raise KgeError("shared negatives cannot be combined with type-constrained sampling: " + step_plan.TYPED_NEEDS_BY_RELATION)
+        in_chunk = int(in_chunk) if chunk else 0
+        step_plan.check_in_chunk(in_chunk, by_relation)
         self._shared_chunk, self._shared_seed, self._shared_by_relation = chunk, int(seed) & 0xFFFFFFFFFFFFFFFF, by_relation
+        self._shared_in_chunk = in_chunk
 
     def _refuse_shared_ranks(self, stepping=False):
         """Shared negatives across ranks train a row-sharded entity table (train_paths.shared_sharded_step) and nothing else:
@@ -213,7 +223,9 @@ class Config(object):
         positives, which are not).
         With by_relation=True: (cand [n_chunks, N], pair [n_pos, N], perm int32 [n_pos], chunks int32 [n_chunks, 2]) -- row b of
         `pair` is SORTED position b, which holds batch position perm[b]; chunks[j] = (first sorted position, length) of chunk j,
-        whose candidates are row j of `cand`; bit 0 of pair[b][k] is the side of candidate k, the same for every b of a chunk."""
+        whose candidates are row j of `cand`; bit 0 of pair[b][k] is the side of candidate k, the same for every b of a chunk.
+        With in_chunk=K the lists are N + K wide: columns 0 .. N - 1 are the drawn candidates, the same ids and sides as with
+        K = 0; columns N .. N + K - 1 are the chunk's own entities (train_paths.shared_in_chunk_candidates), -1 past its length."""
         buf = self._sparse_buf if self._shared_chunk else None
         if not buf or buf.get("shared_step") != int(step):
             raise KgeError("shared_negatives_of: only the lists of the most recent shared-negatives step are kept (step %s)"
@@ -481,7 +493,8 @@ class Config(object):
             typed=bool(self._shared_chunk and self.type_constrained_sampling),
             shared_float_supported=self.lib.kge_shared_float_supported(ctypes.byref(probe.descriptor()), self.negative_ent),
             shared_transd_supported=self.lib.kge_shared_transd_supported(ctypes.byref(probe.descriptor()), self.negative_ent),
-            shared_transr_supported=self.lib.kge_shared_transr_supported(ctypes.byref(probe.descriptor()), self.negative_ent))
+            shared_transr_supported=self.lib.kge_shared_transr_supported(ctypes.byref(probe.descriptor()), self.negative_ent),
+            in_chunk=self._shared_in_chunk)
         self.use_counts, self.sparse_rows, self.sparse_inplace = p.use_counts, p.sparse_rows, p.sparse_inplace
         self._adam, self._lazy_adam, self._adagrad = p.adam, p.lazy_adam, p.adagrad
         self._row_adagrad = p.row_adagrad
@@ -859,7 +872,7 @@ class Config(object):
             dev, n_pos = self._sample_positives()
             step = (train_paths.shared_sharded_step if self._dp else
                     train_paths.shared_grouped_step if self._shared_by_relation else train_paths.shared_step)
-            step(self, dev, n_pos, max(self._n_local, 1), self.batch_size * self.negative_ent)
+            step(self, dev, n_pos, max(self._n_local, 1), self.batch_size * (self.negative_ent + self._shared_in_chunk))
             self.trainModel.loss = self._loss
             return float(self._loss.item()) if sync else self._loss
         if batch_h is None:

@@ -187,6 +187,7 @@ def _declare(L):
     L.kge_shared_chunk_cap.argtypes = [i64, i64, i64]
     L.kge_shared_order_by_relation.argtypes = [vp, vp, vp, i64, i64, vp, vp, vp, vp, vp, vp, vp]
     L.kge_shared_negatives_draw_grouped.argtypes = [vp, vp, vp, i64, vp, i64, i64, i64, ctypes.c_uint64, i64, vp, vp, vp]
+    L.kge_shared_negatives_draw_grouped_mixed.argtypes = [vp, vp, vp, i64, vp, i64, i64, i64, i64, ctypes.c_uint64, i64, vp, vp, vp]      # (N, K)
     L.kge_transe_emit_records_shared_chunks.argtypes = [ctypes.POINTER(ModelDesc), vp, vp, vp, vp, vp, i64, i64, vp, i64, vp, i64, vp, i64, vp, vp,
                                                         vp, vp]
     # ... TransH on those chunks, float records (csrc/shared_proj.hip)

@@ -29,6 +29,9 @@
 // the section near the end of this file): the batch is ordered by relation, chunks never cross a relation boundary and are
 // stated by a table of (first sorted position, length); a candidate has one side for its chunk and may come from the relation's
 // type list.  The emit kernel is the same body with its positions read from the table (template parameter TABLE).
+// IN-CHUNK candidates (kge_shared_negatives_draw_grouped_mixed, behind the grouped draw): K more columns of a chunk's lists are the
+// chunk's own heads / tails at rotated positions; a sibling of the grouped draw kernel writes them, the emit kernels take the wider
+// lists as they take any.
 #include <algorithm>
 #include <cstring>
 #include <string>
@@ -616,6 +619,85 @@ __global__ __launch_bounds__(256) void grouped_draw_kernel(GroupedDrawArgs a) {
     }
 }
 
+// ---- in-chunk candidates (include/kge_mi355.h, "In-chunk candidates") -------------------------------------------------------
+// A sibling of grouped_draw_kernel with its own argument block, so that kernel keeps its instruction stream: the lists are
+// Nt = N + K wide, columns below N are grouped_candidate's, column N + i is the entity at rotated position i of the chunk on the
+// column's side.  Still a thread per pair and per candidate: a pair thread has its slot from the bisection, reads the slot's
+// (first, length), hashes the rotation and gathers one more id.
+struct MixedDrawArgs {
+    GroupedDrawArgs g;
+    int K;
+};
+
+// side of column k of slot j (grouped_candidate's coin), without an id
+__device__ __forceinline__ bool grouped_side(const GroupedDrawArgs &a, long long j, int k, int r) {
+    const bool r_ok = r >= 0 && r < a.rel_total;
+    const unsigned long long c = ((unsigned long long)j << 8) | 128ULL | (unsigned long long)k;
+    const unsigned long long v = mix_scale(mix64(a.S + (c + 1ULL) * kMixGamma), 1000ULL);
+    return (float)v < ((a.bern && r_ok) ? a.bern_prob[r] : 500.0f);
+}
+
+// id of in-chunk column i of the used slot j = (first, len) whose relation is r: -1 past the chunk's length and for a relation
+// outside the table (the trailing run's positives take no part, and its ids would be another relation's entities)
+__device__ __forceinline__ int in_chunk_candidate(const GroupedDrawArgs &a, long long j, int2 ch, int i, int r, bool new_tail) {
+    const int len = (int)min((long long)ch.y, a.n_pos - ch.x);
+    if (i >= len || r < 0 || r >= a.rel_total) return -1;
+    const unsigned long long c = ((unsigned long long)j << 8) | 64ULL;
+    const int o = (int)mix_scale(mix64(a.S + (c + 1ULL) * kMixGamma), (unsigned long long)len);
+    const long long q = ch.x + (o + i) % len;
+    return (new_tail ? a.t : a.h)[q];
+}
+
+__global__ __launch_bounds__(256) void grouped_draw_mixed_kernel(MixedDrawArgs m) {
+    const GroupedDrawArgs &a = m.g;
+    const int Nt = a.N + m.K;
+    const long long n_pair = a.n_pos * Nt, n_all = n_pair + a.cap * Nt;
+    for (long long g = (long long)blockIdx.x * 256 + threadIdx.x; g < n_all; g += (long long)gridDim.x * 256) {
+        bool new_tail;
+        if (g >= n_pair) {
+            const long long j = (g - n_pair) / Nt;
+            const int k = (int)((g - n_pair) % Nt);
+            const int2 ch = a.chunks[j];
+            const bool used = ch.y > 0 && ch.x >= 0 && ch.x < a.n_pos;
+            int id = -1;
+            if (used) {
+                const int r = a.r[ch.x];
+                if (k < a.N) id = grouped_candidate(a, j, k, r, new_tail);
+                else id = in_chunk_candidate(a, j, ch, k - a.N, r, grouped_side(a, j, k, r));
+            }
+            a.cand[g - n_pair] = id;
+            continue;
+        }
+        const long long b = g / Nt;
+        const int k = (int)(g % Nt);
+        const int j = bisect_count((int)a.cap, [&](int mid) { const int2 ch = a.chunks[mid]; return ch.y > 0 && ch.x <= b; }) - 1;
+        const int h = a.h[b], t = a.t[b], r = a.r[b];
+        if (j < 0) { a.pair[g] = 2; continue; }
+        int c;
+        bool masked = false;
+        if (k < a.N) {
+            c = grouped_candidate(a, j, k, r, new_tail);
+        } else {
+            new_tail = grouped_side(a, j, k, r);
+            c = in_chunk_candidate(a, j, a.chunks[j], k - a.N, r, new_tail);
+            masked = c < 0 || c == (new_tail ? t : h);      // no candidate; the entity it would replace
+        }
+        const bool r_ok = r >= 0 && r < a.rel_total;
+        const int anchor = new_tail ? h : t;
+        if (!masked && r_ok && anchor >= 0 && anchor < a.ent_total) {
+            const long long key = (long long)anchor * a.rel_total + r;
+            const long long *keys = new_tail ? a.hr_key : a.tr_key;
+            const int n = new_tail ? a.n_hr : a.n_tr;
+            const int at = bisect_count(n, [&](int mid) { return keys[mid] < key; });
+            if (at < n && keys[at] == key) {
+                const int2 sp = (new_tail ? a.hr_span : a.tr_span)[at];
+                masked = sorted_contains((new_tail ? a.tails_hr : a.heads_tr) + sp.x, sp.y, c);
+            }
+        }
+        a.pair[g] = (uint8_t)((new_tail ? 0 : 1) | (masked ? 2 : 0));
+    }
+}
+
 }  // namespace
 }  // namespace kge
 
@@ -728,6 +810,38 @@ int kge_shared_negatives_draw_grouped(const int32_t *d_h2, const int32_t *d_t2, 
     if (nb > 65536) nb = 65536;
     hipLaunchKernelGGL(grouped_draw_kernel, dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream, a);
     return hip_check(hipGetLastError(), "grouped shared negatives draw launch");
+}
+
+int kge_shared_negatives_draw_grouped_mixed(const int32_t *d_h2, const int32_t *d_t2, const int32_t *d_r2, INT n_pos, const int32_t *d_chunks,
+                                            INT cap, INT N, INT K, INT typed, uint64_t seed, INT step, int32_t *d_cand, uint8_t *d_pair,
+                                            void *stream) {
+    if (N < 1 || K < 0 || N + K > 63)
+        return fail(KGE_ERR_BAD_ARG, "kge_shared_negatives_draw_grouped_mixed: 1 <= N, 0 <= K and N + K <= 63 candidates per positive (a positive's count is within +-2 (N + K), an int8)");
+    if (n_pos < 0 || cap < 0 || cap >= (INT(1) << 31) || step < 0 || !d_h2 || !d_t2 || !d_r2 || !d_chunks || !d_cand || !d_pair)
+        return fail(KGE_ERR_BAD_ARG, "kge_shared_negatives_draw_grouped_mixed: bad arguments");
+    if (K == 0) return kge_shared_negatives_draw_grouped(d_h2, d_t2, d_r2, n_pos, d_chunks, cap, N, typed, seed, step, d_cand, d_pair, stream);
+    int rc = ensure_device_index();
+    if (rc) return rc;
+    if ((rc = ensure_group_dir())) return rc;
+    if (typed && (rc = ensure_typed_index(true))) return rc;
+    if (n_pos == 0 && cap == 0) return KGE_OK;
+    Engine &e = engine();
+    MixedDrawArgs m = {};
+    GroupedDrawArgs &a = m.g;
+    m.K = (int)K;
+    a.h = d_h2; a.t = d_t2; a.r = d_r2; a.chunks = reinterpret_cast<const int2 *>(d_chunks);
+    a.n_pos = n_pos; a.cap = cap; a.N = (int)N; a.typed = typed ? 1 : 0;
+    a.S = mix64((unsigned long long)seed + ((unsigned long long)step + 1ULL) * kMixGamma);
+    a.ent_total = (int)e.index.ent_total; a.rel_total = (int)e.index.rel_total; a.bern = e.bern ? 1 : 0;
+    a.bern_prob = e.dev.bern_prob; a.tails_hr = e.dev.tails_hr; a.heads_tr = e.dev.heads_tr;
+    a.type_bounds = e.dev.type_bounds; a.type_tails = e.dev.type_tails; a.type_heads = e.dev.type_heads;
+    a.hr_key = g_dir.hr_key; a.tr_key = g_dir.tr_key; a.hr_span = g_dir.hr_span; a.tr_span = g_dir.tr_span;
+    a.n_hr = g_dir.n_hr; a.n_tr = g_dir.n_tr;
+    a.cand = d_cand; a.pair = d_pair;
+    long long nb = ((n_pos + cap) * (N + K) + 255) / 256;
+    if (nb > 65536) nb = 65536;
+    hipLaunchKernelGGL(grouped_draw_mixed_kernel, dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream, m);
+    return hip_check(hipGetLastError(), "mixed shared negatives draw launch");
 }
 
 int kge_transe_emit_records_shared_chunks(const kge_model_desc *m, const float *d_ent, const float *d_rel, const int32_t *d_h2, const int32_t *d_t2,

@@ -122,6 +122,11 @@ def parse_args(argv=None):
                         "shares its relation's normal vector (TransD: transfer vector) and every candidate's projection.  With --model "
                         "TransR (rel_dim up to 512; SGD, Adagrad or Adam) likewise: a chunk shares its relation's matrix, and 2 P + N rows "
                         "go through the row GEMMs where the unshared step puts P (2 + N)")
+    p.add_argument("--shared_negatives_in_chunk", type=int, default=0,
+                   help="K > 0: with --shared_negatives_by_relation 1, K more candidates of every chunk are the chunk's own entities "
+                        "(batch negatives: the tails, or heads, of its other positives, rotated by a hash of the step) beside the "
+                        "--ent_neg_rate drawn ones; --ent_neg_rate + K <= 63 (Config.set_shared_negatives(..., in_chunk=K)).  "
+                        "A resumed run must repeat it; 0 = off (default)")
     p.add_argument("--type_constrained_sampling", type=int, default=0,
                    help="1: entity negatives of a training batch come from the relation's own head / tail type list "
                         "(type_constrain.txt in --input_path, required then) instead of from all entities; same random stream, "
@@ -163,7 +168,8 @@ def get_conf(argv):
         con.sparse_rows = bool(argv.sparse_rows)
     if getattr(argv, "shared_negatives_chunk", 0):
         con.set_shared_negatives(argv.shared_negatives_chunk, getattr(argv, "shared_negatives_seed", 0),
-                                 by_relation=bool(getattr(argv, "shared_negatives_by_relation", 0)))
+                                 by_relation=bool(getattr(argv, "shared_negatives_by_relation", 0)),
+                                 in_chunk=getattr(argv, "shared_negatives_in_chunk", 0))
     typed = bool(getattr(argv, "type_constrained_sampling", 0))
     path = argv.input_path if not argv.input_path or argv.input_path.endswith("/") else argv.input_path + "/"
     derive = bool(getattr(argv, "derive_type_constraints", 0)) and bool(path) and not os.path.exists(path + "type_constrain.txt") and \
@@ -249,19 +255,27 @@ def _shared_negatives_mode(con):
     return (chunk, int(getattr(con, "_shared_seed", 0)), by_relation, int(bool(by_relation and con.type_constrained_sampling)))
 
 
+def _shared_in_chunk(con):
+    """K of a Config's in-chunk candidates (Config.set_shared_negatives(..., in_chunk=K)); 0 when they, or shared negatives, are off."""
+    return int(getattr(con, "_shared_in_chunk", 0)) if int(getattr(con, "_shared_chunk", 0)) else 0
+
+
 def shared_negatives_record(con):
     """What a checkpoint keeps of a run's shared negatives: uint64 [chunk, seed], and [chunk, seed, by_relation, typed] when the
-    chunks are relation-grouped (a record of two means False for both)."""
+    chunks are relation-grouped (a record of two means False for both); a fifth field, in_chunk, only when it is not 0, so every
+    record without in-chunk candidates keeps its length."""
     mode = _shared_negatives_mode(con)
-    return np.array(mode if mode[2] or mode[3] else mode[:2], dtype=np.uint64)
+    k = _shared_in_chunk(con)
+    return np.array(mode + (k,) if k else mode if mode[2] or mode[3] else mode[:2], dtype=np.uint64)
 
 
 def check_shared_negatives_record(z, con):
     """A resumed run must draw the candidates the interrupted one would have drawn: refuse a checkpoint (its arrays `z`) whose
     shared-negatives record differs from this run's."""
     was = tuple(int(x) for x in z["shared_negatives"]) if "shared_negatives" in z else (0, 0)
-    was = (was + (0, 0))[:4]      # (a checkpoint without by_relation / typed: both off)
-    now = _shared_negatives_mode(con)
+    was = (was + (0, 0, 0))[:5]      # (a checkpoint without by_relation / typed / in_chunk: all off)
+    was, was_k = was[:4], was[4]
+    now, now_k = _shared_negatives_mode(con), _shared_in_chunk(con)
     if was != now and not (was[2] or was[3] or now[2] or now[3]):      # chunks by position on both sides: the two fields alone
         raise KgeError("the checkpoint was written with shared negatives (chunk, seed) = %s, this run has %s: resume with the same "
                        "--shared_negatives_chunk / --shared_negatives_seed (0 0 = off)" % (was[:2], now[:2]))
@@ -269,6 +283,9 @@ def check_shared_negatives_record(z, con):
         raise KgeError("the checkpoint was written with shared negatives (chunk, seed, by_relation, typed) = %s, this run has %s: resume "
                        "with the same --shared_negatives_chunk / --shared_negatives_seed / --shared_negatives_by_relation / "
                        "--type_constrained_sampling (all 0 = off)" % (was, now))
+    if was_k != now_k:
+        raise KgeError("the checkpoint was written with %d in-chunk candidates per chunk of shared negatives, this run has %d: resume "
+                       "with the same --shared_negatives_in_chunk (0 = off)" % (was_k, now_k))
 
 
 def _step_of(path):

@@ -73,7 +73,7 @@ def wants_sparse_rows(sparse_rows, ent_total, rel_total, width, batch_size, n_ne
 
 def plan(model_id, opt_method, sparse_rows, use_counts, counts_supported, ent_total, rel_total, width, batch_size, n_neg,
          sparse_threshold_bytes=None, adagrad_initial_accumulator=0.1, shared_chunk=0, negative_rel=0, by_relation=False, typed=False,
-         shared_float_supported=0, shared_transd_supported=0, shared_transr_supported=0):
+         shared_float_supported=0, shared_transd_supported=0, shared_transr_supported=0, in_chunk=0):
     """The StepPlan of a configuration.  sparse_rows: None = automatic, True / False = the caller's wish; use_counts: the
     caller's wish; counts_supported: what kge_transe_counts_supported said for the model's descriptor and n_neg.
     shared_chunk: 0 = off; P > 0 = negatives shared by chunks of P positives (NON-PARITY, opt-in: Config.set_shared_negatives),
@@ -83,7 +83,8 @@ def plan(model_id, opt_method, sparse_rows, use_counts, counts_supported, ent_to
     for the model's descriptor and the entity negatives (TransH on relation-grouped chunks, float gradient records);
     shared_transd_supported: what kge_shared_transd_supported said for them (TransD on such chunks, the same records with the
     transfer rows); shared_transr_supported: what kge_shared_transr_supported said for them (TransR on such chunks, through its
-    dense gradient tables: the plan of its unshared step)."""
+    dense gradient tables: the plan of its unshared step); in_chunk: K >= 0 of a chunk's candidates are its own positives' entities
+    beside the n_neg - negative_rel drawn ones (relation-grouped chunks only); it is checked and changes no plan."""
     optimizer = optimizer_kind(opt_method)
     adam, lazy_adam, adagrad = optimizer == "adam", optimizer == "lazy_adam", optimizer == "adagrad"
     row_adagrad = optimizer == "row_adagrad"
@@ -111,7 +112,7 @@ def plan(model_id, opt_method, sparse_rows, use_counts, counts_supported, ent_to
     rows = (bool(sparse) or rows_rule) and use_counts and not adam
     if shared_chunk:
         check_shared_negatives(model_id, optimizer, use_counts, shared_chunk, n_neg - negative_rel, negative_rel, by_relation, typed,
-                               shared_float_supported, shared_transd_supported, shared_transr_supported)
+                               shared_float_supported, shared_transd_supported, shared_transr_supported, in_chunk)
         if model_id == TRANSR:      # dense gradient tables and the optimizer on the whole tables, as its unshared step
             return StepPlan(optimizer, False, False, False, table_bytes)
         if model_id in (TRANSH, TRANSD):      # float records, keyed in the unshared step's row space: the touched-rows plan in place
@@ -142,19 +143,33 @@ TYPED_NEEDS_BY_RELATION = ("a chunk of consecutive batch positions mixes relatio
                            "candidates (without by_relation typed candidates are not built)")
 
 
+def check_in_chunk(in_chunk, by_relation):
+    """Raises KgeError for an in-chunk candidate count that is negative, or positive without relation-grouped chunks."""
+    if int(in_chunk) < 0:
+        raise KgeError("shared negatives: in_chunk counts the candidates a chunk takes from its own positives and must be 0 or more, "
+                       "got %r" % (in_chunk,))
+    if in_chunk and not by_relation:
+        raise KgeError("shared negatives: in-chunk candidates need chunks of one relation -- set_shared_negatives(chunk, "
+                       "by_relation=True, in_chunk=%d): in a chunk by position a candidate has no single side, and on more than one "
+                       "rank a slice of another rank would own its entities" % in_chunk)
+
+
 def check_shared_negatives(model_id, optimizer, use_counts, chunk, negative_ent, negative_rel, by_relation=False, typed=False,
-                           shared_float_supported=0, shared_transd_supported=0, shared_transr_supported=0):
+                           shared_float_supported=0, shared_transd_supported=0, shared_transr_supported=0, in_chunk=0):
     """Raises KgeError, naming the limit, for a configuration the shared-negatives step cannot take.  by_relation: chunks cut from
     the batch ordered by relation; typed: candidates from the relations' type lists, which needs by_relation;
     shared_float_supported: the library's answer for TransH on such chunks (kge_shared_float_supported), which needs no use_counts;
     shared_transd_supported: its answer for TransD on them (kge_shared_transd_supported), likewise; shared_transr_supported: its
-    answer for TransR on them (kge_shared_transr_supported): dense gradient tables, so TF1 Adam is taken and LazyAdam is not."""
+    answer for TransR on them (kge_shared_transr_supported): dense gradient tables, so TF1 Adam is taken and LazyAdam is not.
+    in_chunk: K of a chunk's candidates are the entities of its own positives (include/kge_mi355.h, "In-chunk candidates"), beside the
+    negative_ent drawn ones."""
     if typed and not by_relation:
         raise KgeError("shared negatives cannot be combined with type-constrained sampling: " + TYPED_NEEDS_BY_RELATION)
     if not 1 <= int(chunk) <= SHARED_MAX_CHUNK:
         raise KgeError("shared negatives: a chunk holds 1 to %d positives (a candidate's count lies within +-chunk and is carried "
                        "as an int8), got %r" % (SHARED_MAX_CHUNK, chunk))
-    transh = model_id == TRANSH and bool(shared_float_supported)
+    check_in_chunk(in_chunk, by_relation)
+    transh =model_id == TRANSH and bool(shared_float_supported)
     if transh and not by_relation:
         raise KgeError("shared negatives on chunks by position are built for TransE only: TransH shares one normal vector per chunk, "
                        "which needs chunks of one relation -- set_shared_negatives(chunk, by_relation=True)")
@@ -173,6 +188,10 @@ def check_shared_negatives(model_id, optimizer, use_counts, chunk, negative_ent,
     if not 1 <= negative_ent <= SHARED_MAX_NEGATIVES:
         raise KgeError("shared negatives: 1 to %d negatives per positive (a positive's count lies within +-2N and is carried as "
                        "an int8), got %d" % (SHARED_MAX_NEGATIVES, negative_ent))
+    if negative_ent + int(in_chunk) > SHARED_MAX_NEGATIVES:
+        raise KgeError("shared negatives: drawn and in-chunk candidates together are at most %d per positive (a positive's count lies "
+                       "within +-2 (N + in_chunk) and is carried as an int8), got %d + %d"
+                       % (SHARED_MAX_NEGATIVES, negative_ent, in_chunk))
     if transr:      # (the gradients are dense tables: SGD, Adagrad, RowAdagrad and TF1 Adam sweep them as they do in the unshared step)
         if optimizer == "lazy_adam":
             raise KgeError("LazyAdam (touched rows only, NON-PARITY) needs TransE, TransH or TransD: TransR's gradient is a whole "

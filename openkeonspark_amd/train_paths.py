@@ -558,6 +558,63 @@ def shared_relation_chunks(r, P, rel_total):
     return perm, chunks, n_chunks
 
 
+def _mix64(z):
+    """splitmix64's output function on numpy uint64 (csrc/mix_dev.hpp mix64), mod 2^64."""
+    u = np.uint64
+    with np.errstate(over="ignore"):
+        z = np.asarray(z, dtype=u)
+        z = (z ^ (z >> u(30))) * u(0xBF58476D1CE4E5B9)
+        z = (z ^ (z >> u(27))) * u(0x94D049BB133111EB)
+        return z ^ (z >> u(31))
+
+
+def shared_in_chunk_candidates(h2, t2, chunks, n_chunks, sides, N, K, seed, step, valid=None):
+    """int32 [n_chunks, K]: the in-chunk candidates of relation-grouped shared negatives, in plain numpy -- the one host statement
+    of their rotation and ids (include/kge_mi355.h, "In-chunk candidates").  h2 / t2: the positives in sorted order; chunks: the
+    table of shared_relation_chunks; sides: [n_chunks, K] for the in-chunk columns, or [n_chunks, N + K] for all (columns N on
+    are read), 0 = new tail, 1 = new head -- bit 0 of `pair` at any position of the chunk.  Chunk j = (first, len) is rotated by
+    o_j = ((mix(S + (((j << 8) | 64) + 1) G) >> 32) * len) >> 32 with S = mix(seed + (step + 1) G); column N + i is
+    t2[first + (o_j + i) % len] for a new tail, h2[...] for a new head, and -1 for i >= len.  valid (bool [n_chunks], optional):
+    False where the chunk's relation lies outside the table -- the trailing run, whose K ids are -1."""
+    u = np.uint64
+    G = 0x9E3779B97F4A7C15
+    h2, t2 = np.asarray(h2).reshape(-1), np.asarray(t2).reshape(-1)
+    chunks = np.asarray(chunks).reshape(-1, 2)[:int(n_chunks)].astype(np.int64)
+    N, K, n_chunks = int(N), int(K), int(n_chunks)
+    sides = np.asarray(sides).astype(np.int64)
+    sides = sides.reshape(n_chunks, sides.size // n_chunks if n_chunks else K)
+    if sides.shape[1] not in (K, N + K):
+        raise ValueError("shared_in_chunk_candidates: sides is [n_chunks, K] or [n_chunks, N + K], got %r" % (sides.shape,))
+    sides = sides[:, sides.shape[1] - K:] & 1
+    S = _mix64(u((int(seed) + (int(step) + 1) * G) & 0xFFFFFFFFFFFFFFFF))
+    first, length = chunks[:, 0], chunks[:, 1]
+    with np.errstate(over="ignore"):
+        key = (np.arange(n_chunks, dtype=u) << u(8)) | u(64)
+        o = (((_mix64(S + (key + u(1)) * u(G)) >> u(32)) * length.astype(u)) >> u(32)).astype(np.int64)
+    i = np.arange(K, dtype=np.int64)[None, :]
+    inside = i < length[:, None]
+    if valid is not None:
+        inside = inside & np.asarray(valid, dtype=bool).reshape(-1, 1)
+    q = np.where(inside, first[:, None] + (o[:, None] + i) % np.maximum(length, 1)[:, None], 0)
+    if len(h2) == 0:
+        return np.full((n_chunks, K), -1, dtype=np.int32)
+    ids = np.where(sides == 0, t2[q], h2[q])
+    return np.where(inside, ids, -1).astype(np.int32)
+
+
+def shared_grouped_draw(con,h2, t2, r2, n_pos, chunks, cap, cand, pair):
+    """The draw stage of both grouped steps (device pointers): the N = negative_ent drawn candidates of every chunk slot, and with
+    in_chunk = K > 0 the K in-chunk ones beside them, into lists N + K wide.  K = 0 makes the call it always made."""
+    L, N, K = con.lib, con.negative_ent, con._shared_in_chunk
+    typed = 1 if con.type_constrained_sampling else 0
+    if K:
+        _lib.check(L.kge_shared_negatives_draw_grouped_mixed(h2, t2, r2, n_pos, chunks, cap, N, K, typed, con._shared_seed, con.global_step,
+                                                             cand, pair, con._stream()), L)
+    else:
+        _lib.check(L.kge_shared_negatives_draw_grouped(h2, t2, r2, n_pos, chunks, cap, N, typed, con._shared_seed, con.global_step,
+                                                       cand, pair, con._stream()), L)
+
+
 def shared_grouped_step(con, dev, n_pos, stride, denom):
     """shared_step on RELATION-GROUPED chunks (Config.set_shared_negatives(..., by_relation=True); NON-PARITY, opt-in; one rank):
     the ordering stage sorts the step's positives by relation and cuts the runs into chunks of at most P, the grouped draw hashes a
@@ -576,10 +633,12 @@ def shared_grouped_step(con, dev, n_pos, stride, denom):
     2 n_pos + cap N rows through the projection, the pair walk, dgrad and wgrad into the dense gradient tables, and
     Config.apply_gradients finishes as it does for the unshared TransR step."""
     import torch
-    P, N, D = con._shared_chunk, con.negative_ent, con.hidden_size
     model_id = con.trainModel.model_id
     if model_id == _lib.TRANSR:
         return shared_grouped_transr_step(con, dev, n_pos, stride, denom)
+    # N: the candidate columns of a chunk, drawn and in-chunk (set_shared_negatives(..., in_chunk=K); "In-chunk candidates"): the
+    # emit kernels and the rows rule take the wider lists as they take any
+    P, N, D = con._shared_chunk, con.negative_ent + con._shared_in_chunk, con.hidden_size
     float_rec = model_id in (_lib.TRANSH, _lib.TRANSD)      # the float-record models
     ew = 2 if model_id == _lib.TRANSD else 1                # records per entity
     cap = shared_chunk_cap(n_pos, P, con.relTotal)
@@ -609,8 +668,7 @@ def shared_grouped_step(con, dev, n_pos, stride, denom):
     h2, t2, r2 = (buf["sorted"][i].data_ptr() for i in range(3))
     chunks, cand, pair = buf["chunks"].data_ptr(), buf["cand"].data_ptr(), buf["pair"].data_ptr()
     _lib.check(L.kge_shared_order_by_relation(h, t, r, n_pos, P, buf["perm"].data_ptr(), h2, t2, r2, chunks, buf["n_chunks"].data_ptr(), st), L)
-    _lib.check(L.kge_shared_negatives_draw_grouped(h2, t2, r2, n_pos, chunks, cap, N, 1 if con.type_constrained_sampling else 0,
-                                                   con._shared_seed, con.global_step, cand, pair, st), L)
+    shared_grouped_draw(con, h2, t2, r2, n_pos, chunks, cap, cand, pair)
     if float_rec:
         M = 2 * ew * n_pos + cap * (ew * N + 2)
         emit = L.kge_transd_emit_records_shared_chunks if model_id == _lib.TRANSD else L.kge_transh_emit_records_shared_chunks
@@ -635,7 +693,7 @@ def shared_grouped_transr_step(con, dev, n_pos, stride, denom):
     """shared_grouped_step for TransR (one rank): order -> grouped draw -> kge_transr_forward_backward_shared_chunks into the dense
     gradient tables -> the optimizer on the whole tables.  The lists stay in con._sparse_buf under the names the other models use."""
     import torch
-    P, N = con._shared_chunk, con.negative_ent
+    P, N = con._shared_chunk, con.negative_ent + con._shared_in_chunk      # (N: all candidate columns, drawn and in-chunk)
     cap = shared_chunk_cap(n_pos, P, con.relTotal)
     cap_max = shared_chunk_cap(stride, P, con.relTotal)
     buf = con._sparse_buf
@@ -650,8 +708,7 @@ def shared_grouped_transr_step(con, dev, n_pos, stride, denom):
     chunks, cand, pair = buf["chunks"].data_ptr(), buf["cand"].data_ptr(), buf["pair"].data_ptr()
     _lib.check(L.kge_shared_order_by_relation(dev[0].data_ptr(), dev[1].data_ptr(), dev[2].data_ptr(), n_pos, P, buf["perm"].data_ptr(),
                                               h2, t2, r2, chunks, buf["n_chunks"].data_ptr(), st), L)
-    _lib.check(L.kge_shared_negatives_draw_grouped(h2, t2, r2, n_pos, chunks, cap, N, 1 if con.type_constrained_sampling else 0,
-                                                   con._shared_seed, con.global_step, cand, pair, st), L)
+    shared_grouped_draw(con, h2, t2, r2, n_pos, chunks, cap, cand, pair)
     _lib.check(L.kge_transr_forward_backward_shared_chunks(ctypes.byref(con._desc), con._tab_ptrs, h2, t2, r2, n_pos, stride, chunks, cap, cand,
                                                            N, pair, denom, con._grad_ptrs, con._loss.data_ptr(), st), L)
     buf["shared_step"], buf["shared_shape"], buf["shared_batch"] = con.global_step, (n_pos, cap), dev
