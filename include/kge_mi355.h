@@ -669,6 +669,53 @@ int kge_transe_reduce_apply_records_sgd(const kge_model_desc *m, const uint32_t 
                                         float *d_rel, int32_t *d_rows, int32_t *d_row_counts, int32_t *d_n_rows, INT denom, float lr,
                                         void *stream);
 
+/* ---- bf16 table storage (NON-PARITY, opt-in: Config.set_table_dtype("bf16"); csrc/bf16_tables.hip) ----
+ * TransE's two tables are STORED as bf16 -- there is no fp32 copy beside them -- and trained by the one-rank int8-record
+ * touched-rows step (emit -> kge_transe_reduce_records -> apply) with SGD or row-wise Adagrad.  Every gather and every
+ * touched-row update moves half the bytes, and a table takes half the memory.  With the mode off nothing changes.
+ *
+ * Storage.  [E, D] and [R, D], dense row-major, one uint16 per element: the top 16 bits of the fp32 pattern.  D % 8 == 0 and
+ *   D <= 1024, so rows are 16-byte aligned; other widths are refused with the reason (KGE_ERR_UNSUPPORTED).
+ * Forward / backward.  A stored value is widened exactly (bits << 16).  From there the arithmetic is kge_transe_emit_records'
+ *   without the inverse-norm table: the norms come from the gathered rows in fp32, 1 / sqrt(max(sum x^2, 1e-12)) (eps inside the
+ *   max), e = fma(f, x, B) against the group's constants, sign(0) = 0, a hinge tie is active.  Records, keys, loss and the deferral
+ *   of groups that are not sampler-shaped have that call's format: byte e of a record is element e, records are
+ *   kge_transe_record_dwords words apart (bytes from D on are not written), key -1 = no record, entity e -> e, relation r -> E + r.
+ *   kge_transe_reduce_records therefore serves unchanged and kge_transe_deferred_groups reports the deferred groups.  The order
+ *   of the fp32 sums differs from kge_transe_emit_records' (another team shape): scores agree to rounding, the loss to 1e-5.
+ *   1 to 127 negatives; a positive's int8 sums hold 2 x 63 signs, so a group with MORE than 63 ACTIVE negatives is deferred as well
+ *   (keys -1, counted, nothing added to the loss) rather than written wrapped.
+ * Update.  A listed row's gradient g is formed from its int32 counts exactly as kge_transe_apply_rows_rowadagrad forms it (same
+ *   team shape, same operations: normalise, then unit * inv * (s - d * x^) with every operation rounded on its own), with the
+ *   widened row as x.  SGD: y = x - lr * g.  RowAdagrad: q = sum g^2; a += q / D; y = x - (lr * g) / sqrt(a), the accumulators
+ *   fp32, one per row, as in kge_transe_apply_rows_rowadagrad.  y is an fp32 value and is stored by stochastic rounding.
+ * Stochastic rounding.  All arithmetic mod 2^64, mix = splitmix64's finaliser and G = 0x9E3779B97F4A7C15 (csrc/mix_dev.hpp):
+ *     k      = mix(seed + G * (step + 1))                      step: global step of the update, 0 for the first
+ *     z      = mix(k + G * (key * (D / 4) + (j >> 2) + 1))     key: the row in the record row space; j: the column
+ *     rnd    = (z >> (16 * (j & 3))) & 0xFFFF
+ *     stored = exponent(y) all ones ? bits(y) >> 16 : (bits(y) + rnd) >> 16
+ *   One mix serves four columns.  The expected stored value is y (a plain down-cast would drop almost every update: one step
+ *   moves an element by far less than a bf16 ulp).  A value that is already a bf16 value is stored unchanged whatever rnd is, so
+ *   elements with zero gradient, rows that are not listed, and listed rows whose counts are all zero (their accumulators too)
+ *   keep their bits.  inf stays inf and a NaN whose top mantissa bits are set stays a NaN.  The stored bits depend on (seed,
+ *   step, key, column, y) only: a run is reproducible bit for bit and a resumed run equals the uninterrupted one.
+ *
+ * kge_bf16_tables_supported: 1 when the descriptor and negative count can take the mode, else 0.
+ * kge_transe_emit_records_bf16: kge_transe_emit_records' arguments with bf16 tables and no residual pointers.
+ * kge_transe_apply_rows_sgd_bf16 / kge_transe_apply_rows_rowadagrad_bf16: their fp32 namesakes' arguments plus seed and step.
+ * kge_bf16_round_stochastic: test hook -- the rounding rule alone on d_y [rows, D] fp32 -> d_out [rows, D] uint16, row i under
+ *   the key first_key + i (D % 8 == 0, D <= 1024). */
+int kge_bf16_tables_supported(const kge_model_desc *m, INT n_neg);
+int kge_transe_emit_records_bf16(const kge_model_desc *m, const uint16_t *d_ent, const uint16_t *d_rel, const int32_t *d_h, const int32_t *d_t,
+                                 const int32_t *d_r, INT n_pos, INT n_neg, INT stride, INT denom, uint32_t *d_rec, int32_t *d_dst,
+                                 float *d_loss, void *stream);
+int kge_transe_apply_rows_sgd_bf16(const kge_model_desc *m, uint16_t *d_ent, uint16_t *d_rel, const int32_t *d_rows, const int32_t *d_row_counts,
+                                   const int32_t *d_n_rows, INT max_rows, INT denom, float lr, uint64_t seed, uint64_t step, void *stream);
+int kge_transe_apply_rows_rowadagrad_bf16(const kge_model_desc *m, uint16_t *d_ent, uint16_t *d_rel, float *d_acc_ent, float *d_acc_rel,
+                                          const int32_t *d_rows, const int32_t *d_row_counts, const int32_t *d_n_rows, INT max_rows, INT denom,
+                                          float lr, uint64_t seed, uint64_t step, void *stream);
+int kge_bf16_round_stochastic(const float *d_y, INT rows, INT D, INT first_key, uint64_t seed, uint64_t step, uint16_t *d_out, void *stream);
+
 /* ---- TransE on negatives SHARED by a chunk of positives (NON-PARITY, opt-in; csrc/shared_neg.hip) ----
  * The reference draws every negative for one positive (Base.cpp:109-139).  Here a chunk of P consecutive positives scores the
  * same N candidate entities, as large-scale trainers do (PyTorch-BigGraph, DGL-KE): a chunk gathers 3 P + N table rows instead

@@ -57,6 +57,8 @@ class Config(object):
             self._shared_chunk, self._shared_seed = 0, 0      # set_shared_negatives
             self._shared_by_relation = False                  # ... its chunks are cut from the batch ordered by relation
             self._shared_in_chunk = 0                         # ... K of a chunk's candidates are its own positives' entities
+            self._table_dtype, self._table_seed = "fp32", 0   # set_table_dtype
+            self._eval_view = None                            # bf16 tables: the float32 view the evaluation paths read (_tab_ptrs)
             # engine-side additions
             self.seed = 0                 # parameter initialisation seed
             self.device = "cuda"
@@ -194,6 +196,57 @@ class Config(object):
         step_plan.check_in_chunk(in_chunk, by_relation)
         self._shared_chunk, self._shared_seed, self._shared_by_relation = chunk, int(seed) & 0xFFFFFFFFFFFFFFFF, by_relation
         self._shared_in_chunk = in_chunk
+
+    def set_table_dtype(self, dtype, seed=0):
+        """How TransE's tables are STORED (before set_model_and_session).  "fp32": the default.  "bf16" (NON-PARITY, opt-in;
+        the definition is in include/kge_mi355.h, "bf16 table storage"): ent_embeddings and rel_embeddings are bf16 tensors -- half
+        the bytes in memory and in every gather and touched-row update -- trained on the one-rank int8-record touched-rows step
+        with SGD or RowAdagrad; every updated row is stored by stochastic rounding from a hash of (seed, global step, row,
+        column), so a run is reproducible bit for bit and a resumed run must repeat the seed.  get_parameters / checkpoints give
+        float32 (an exact widening), set_parameters rounds to nearest-even, and the evaluation paths read a float32 view that
+        lives until the next training step.  Configurations the mode cannot take are refused by set_model_and_session."""
+        step_plan.check_table_dtype(dtype)
+        seed = int(seed)
+        if not 0 <= seed < (1 << 64):
+            raise KgeError("set_table_dtype: the rounding seed is an unsigned 64-bit value, got %r" % (seed,))
+        self._table_dtype, self._table_seed = dtype, seed
+
+    @property
+    def _bf16(self):
+        return getattr(self, "_table_dtype", "fp32") == "bf16"
+
+    def _refuse_bf16_ranks(self):
+        """bf16 table storage is one rank: the row-sharded step and the replicated exchanges move fp32 rows."""
+        if self._bf16 and self._dp:
+            raise KgeError("bf16 table storage is single-process only: the row-sharded step and the data-parallel exchanges are "
+                           "built for fp32 tables (world size %d)" % self.world_size)
+
+    # The evaluation kernels read fp32 tables.  With bf16 storage every path that passes `_tab_ptrs` gets a float32 view made by
+    # widening (exact), cached until the next training step or set_parameters and freed there: training memory is unaffected.
+    @property
+    def _tab_ptrs(self):
+        if self._bf16 and getattr(self, "_tables", None):
+            return self._eval_table_ptrs()
+        return self._tab_ptrs_raw
+
+    @_tab_ptrs.setter
+    def _tab_ptrs(self, value):
+        self._tab_ptrs_raw = value
+
+    def _eval_table_ptrs(self):
+        import torch
+        if self._eval_view is None:
+            need = sum(t.numel() for t in self._tables) * 4
+            try:
+                views = [t.float() for t in self._tables]
+            except (torch.cuda.OutOfMemoryError, RuntimeError) as e:
+                raise KgeError("bf16 table storage: evaluation reads a float32 view of the tables and its %d bytes could not be "
+                               "allocated (%s)" % (need, str(e).splitlines()[0] if str(e) else type(e).__name__))
+            self._eval_view = (views, _lib.table_ptrs([v.data_ptr() for v in views]))
+        return self._eval_view[1]
+
+    def _drop_eval_view(self):
+        self._eval_view = None
 
     def _refuse_shared_ranks(self, stepping=False):
         """Shared negatives across ranks train a row-sharded entity table (train_paths.shared_sharded_step) and nothing else:
@@ -494,12 +547,15 @@ class Config(object):
             shared_float_supported=self.lib.kge_shared_float_supported(ctypes.byref(probe.descriptor()), self.negative_ent),
             shared_transd_supported=self.lib.kge_shared_transd_supported(ctypes.byref(probe.descriptor()), self.negative_ent),
             shared_transr_supported=self.lib.kge_shared_transr_supported(ctypes.byref(probe.descriptor()), self.negative_ent),
-            in_chunk=self._shared_in_chunk)
+            in_chunk=self._shared_in_chunk, table_dtype=getattr(self, "_table_dtype", "fp32"),
+            bf16_supported=self.lib.kge_bf16_tables_supported(ctypes.byref(probe.descriptor()), n_neg) if self._bf16 else 0)
+        self._drop_eval_view()
         self.use_counts, self.sparse_rows, self.sparse_inplace = p.use_counts, p.sparse_rows, p.sparse_inplace
         self._adam, self._lazy_adam, self._adagrad = p.adam, p.lazy_adam, p.adagrad
         self._row_adagrad = p.row_adagrad
         self._has_slots, self._rows_rule = p.has_slots, p.rows_rule
         self._refuse_shared_ranks()
+        self._refuse_bf16_ranks()
         self._shard_plan = self._plan_entity_shard(probe.model_id)
         self.trainModel = self.model(config=self, define=True)
         m = self.trainModel
@@ -570,6 +626,7 @@ class Config(object):
         self._pg = process_group
         self.rank = dist.get_rank(process_group)
         self.world_size = dist.get_world_size(process_group)
+        self._refuse_bf16_ranks()
         if self.trainModel is not None:
             self._setup_partition()
         if getattr(self, "_prefetch_auto", getattr(self, "prefetch_sampling", None) is None):
@@ -598,6 +655,7 @@ class Config(object):
         lo, hi = thread_range(self.rank, self.world_size, self.workThreads)
         self._thread_lo, self._thread_hi = lo, hi
         self._refuse_shared_ranks()
+        self._refuse_bf16_ranks()
         first = ctypes.c_int64(0)
         self._n_local = self.lib.kge_slice_positions(self.batch_size, lo, hi, ctypes.byref(first))
         self._first_pos = first.value
@@ -861,6 +919,9 @@ class Config(object):
         '''
         import torch
         n_neg = self.negative_ent + self.negative_rel
+        if self._bf16:
+            self._refuse_bf16_ranks()
+            self._drop_eval_view()      # the view is of the tables before this step
         if getattr(self, "_ent_is_shard", False) and not hasattr(self, "_shard"):
             raise KgeError("the entity table was created as this rank's shard of a row-sharded table (the process belongs to a "
                            "torch.distributed world): call init_distributed() before training")
@@ -943,6 +1004,9 @@ class Config(object):
         if n_steps <= 0:
             return np.zeros(0, np.float32)
         use = self.persistent_preferred() if persistent is None else bool(persistent)
+        if use and self._bf16:
+            raise KgeError("train_steps(persistent=True): bf16 table storage has no persistent-launch path (the persistent kernel "
+                           "reads and sweeps fp32 tables)")
         if use and not self.persistent_supported():
             raise KgeError("train_steps(persistent=True): this configuration has no persistent-launch path" +
                            (" (type-constrained sampling is on: the persistent kernel samples untyped negatives only)"
@@ -1675,6 +1739,8 @@ class Config(object):
                 full = torch.empty((self._shard["chunk"] * self.world_size, t.shape[1]), dtype=t.dtype, device=t.device)
                 all_gather_chunks(full.view(-1), t.reshape(-1), self._pg)
                 return full[:self.entTotal].cpu().numpy()
+            if self._bf16:      # float32 out: an exact widening
+                return t.detach().float().cpu().numpy()
             return t.detach().cpu().numpy()
         return None
 
@@ -1708,7 +1774,8 @@ class Config(object):
                 lo, hi = self._shard["lo"], self._shard["hi"]
                 dst[:hi - lo].copy_(src.reshape(self.entTotal, -1)[lo:hi])
             else:
-                dst.copy_(src.reshape(dst.shape))
+                dst.copy_(src.reshape(dst.shape))      # (bf16 tables: the copy rounds to nearest-even)
+            self._drop_eval_view()
             self.tables_changed()
 
     def set_parameters(self, lists):

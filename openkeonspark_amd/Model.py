@@ -29,17 +29,28 @@ def xavier_normal(rng, shape, fan_in=None):
 LARGE_TABLE_ELEMS = 1 << 28   # beyond 1 GiB of fp32 a table is initialised in HBM, never staged on the host
 
 
-def xavier_normal_device(shape, device, seed, row_range=None, out_rows=None):
+def xavier_normal_device(shape, device, seed, row_range=None, out_rows=None, dtype=None):
     """Same distribution as xavier_normal, drawn by the device generator in row blocks (a 50M x 512
     table is 102 GB: it exists only in HBM).  row_range=(lo, hi): only those rows are kept, in a tensor of `out_rows`
     rows (a rank's shard of a row-sharded table: the generator still walks the whole table block by block, through one
-    512 MB scratch block, so every rank's rows are the rows of the single-process table -- but the table itself never exists)."""
+    512 MB scratch block, so every rank's rows are the rows of the single-process table -- but the table itself never exists).
+    dtype=torch.bfloat16: the table is bf16 storage; every block is drawn in fp32 through that scratch block, exactly as the fp32
+    table draws it, and rounded to nearest-even into its rows -- no whole fp32 copy of the table exists."""
     import torch
     rows, cols = shape
     std = float(np.sqrt(2.6 / (rows + cols)))
     gen = torch.Generator(device=device)
     gen.manual_seed(int(seed))
     block = max(1, (1 << 27) // max(cols, 1))
+    if dtype is not None and dtype != torch.float32 and row_range is None:
+        out = torch.empty(shape, dtype=dtype, device=device)
+        scratch = torch.empty((min(block, rows), cols), dtype=torch.float32, device=device)
+        for r0 in range(0, rows, block):
+            part = scratch[:min(r0 + block, rows) - r0]
+            torch.nn.init.trunc_normal_(part, 0.0, std, -2.0 * std, 2.0 * std, generator=gen)
+            out[r0:r0 + block].copy_(part)
+        del scratch
+        return out
     if row_range is None:
         out = torch.empty(shape, dtype=torch.float32, device=device)
         for r0 in range(0, rows, block):
@@ -57,6 +68,18 @@ def xavier_normal_device(shape, device, seed, row_range=None, out_rows=None):
         if b > a:
             out[a - lo:b - lo].copy_(part[a - r0:b - r0])
     del scratch
+    return out
+
+
+def to_bf16_blocks(table):
+    """A float32 device table as a bf16 one (round to nearest-even), converted in row blocks of at most 128 MB.  For the tables
+    drawn on the host (up to LARGE_TABLE_ELEMS); a larger table is drawn straight into bf16 storage (xavier_normal_device)."""
+    import torch
+    rows, cols = table.shape
+    out = torch.empty((rows, cols), dtype=torch.bfloat16, device=table.device)
+    block = max(1, (1 << 25) // max(cols, 1))
+    for r0 in range(0, rows, block):
+        out[r0:r0 + block].copy_(table[r0:r0 + block])
     return out
 
 
@@ -131,6 +154,7 @@ class Model(object):
         rng = np.random.default_rng(getattr(config, "seed", 0))
         device = getattr(config, "device", "cuda")
         self.parameter_lists = {}
+        bf16 = getattr(config, "_table_dtype", "fp32") == "bf16"      # (one rank: never with a shard plan)
         plan = getattr(config, "_shard_plan", None)     # row-sharded entity table (Config._plan_entity_shard): this rank's rows only
         for name in self.table_names:
             shape = self.table_shapes()[name]
@@ -140,7 +164,8 @@ class Model(object):
                     self.parameter_lists[name] = xavier_normal_device(shape, device, getattr(config, "seed", 0),
                                                                       row_range=(shard["lo"], shard["hi"]), out_rows=shard["chunk"])
                 else:
-                    self.parameter_lists[name] = xavier_normal_device(shape, device, getattr(config, "seed", 0))
+                    self.parameter_lists[name] = xavier_normal_device(shape, device, getattr(config, "seed", 0),
+                                                                      dtype=torch.bfloat16 if bf16 else None)
             else:
                 full = xavier_normal(rng, shape)
                 if shard is not None:
@@ -148,6 +173,10 @@ class Model(object):
                     part[:shard["hi"] - shard["lo"]] = full[shard["lo"]:shard["hi"]]
                     full = part
                 self.parameter_lists[name] = torch.from_numpy(full).to(device)
+        if bf16:      # drawn as the fp32 run draws them, then rounded to nearest-even
+            for name in self.table_names:
+                if self.parameter_lists[name].dtype != torch.bfloat16:
+                    self.parameter_lists[name] = to_bf16_blocks(self.parameter_lists[name])
         config._ent_is_shard = plan is not None
         for name, t in self.parameter_lists.items():
             setattr(self, name, t)

@@ -177,6 +177,13 @@ def _declare(L):
     L.kge_transe_apply_rows_sgd.argtypes = [ctypes.POINTER(ModelDesc), vp, vp, vp, vp, vp, i64, i64, f32, vp]
     L.kge_transe_apply_rows_adam_lazy.argtypes = [ctypes.POINTER(ModelDesc), vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, i64, f32, f32, f32, f32, vp, vp]
     L.kge_transe_reduce_apply_records_sgd.argtypes = [ctypes.POINTER(ModelDesc), vp, vp, i64, vp, vp, vp, vp, vp, i64, f32, vp]
+    # bf16 table storage (csrc/bf16_tables.hip)
+    u64 = ctypes.c_uint64
+    L.kge_bf16_tables_supported.argtypes = [ctypes.POINTER(ModelDesc), i64]
+    L.kge_transe_emit_records_bf16.argtypes = [ctypes.POINTER(ModelDesc), vp, vp, vp, vp, vp, i64, i64, i64, i64, vp, vp, vp, vp]
+    L.kge_transe_apply_rows_sgd_bf16.argtypes = [ctypes.POINTER(ModelDesc), vp, vp, vp, vp, vp, i64, i64, f32, u64, u64, vp]
+    L.kge_transe_apply_rows_rowadagrad_bf16.argtypes = [ctypes.POINTER(ModelDesc), vp, vp, vp, vp, vp, vp, vp, i64, i64, f32, u64, u64, vp]
+    L.kge_bf16_round_stochastic.argtypes = [vp, i64, i64, i64, u64, u64, vp, vp]
     # shared negatives (csrc/shared_neg.hip)
     L.kge_shared_negatives_draw.argtypes = [vp, vp, vp, i64, i64, i64, i64, ctypes.c_uint64, i64, vp, vp, vp]
     L.kge_transe_emit_records_shared.argtypes = [ctypes.POINTER(ModelDesc), vp, vp, vp, vp, vp, i64, i64, i64, vp, i64, vp, i64, vp, vp, vp, vp]

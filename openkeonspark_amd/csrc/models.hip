@@ -903,6 +903,13 @@ int transe_deferred_groups(int32_t *out) {
     return hip_check(hipMemcpy(out, g_defer_count, sizeof(int32_t), hipMemcpyDeviceToHost), "read deferred count");
 }
 
+// the same list and counter for an emit kernel that lives in another file (bf16_tables.hip), the count restarted on `stream`
+int transe_defer_buffers(int64_t n_pos, hipStream_t stream, int32_t *&list, int32_t *&count) {
+    const int rc = ensure_defer_list(n_pos, true, stream);
+    list = g_defer_list; count = g_defer_count;
+    return rc;
+}
+
 int launch_transe_emit(const kge_model_desc &m, const float *ent, const float *rel, float *resid_ent, float *resid_rel,
                        const int32_t *d_h, const int32_t *d_t, const int32_t *d_r, int64_t n_pos, int64_t n_neg, int64_t stride,
                        int64_t denom, uint32_t *rec, int32_t *dst, int krel, float *d_loss, hipStream_t stream, bool track_deferred,

@@ -127,6 +127,12 @@ def parse_args(argv=None):
                         "(batch negatives: the tails, or heads, of its other positives, rotated by a hash of the step) beside the "
                         "--ent_neg_rate drawn ones; --ent_neg_rate + K <= 63 (Config.set_shared_negatives(..., in_chunk=K)).  "
                         "A resumed run must repeat it; 0 = off (default)")
+    p.add_argument("--table_dtype", type=str, default="fp32", choices=("fp32", "bf16"),
+                   help="bf16 (NON-PARITY, opt-in): TransE's tables are stored as bf16 -- half the memory and half the bytes of every "
+                        "gather and touched-row update -- and trained on the one-rank int8-record touched-rows step with SGD or "
+                        "RowAdagrad; updated rows are stored by stochastic rounding.  Checkpoints stay float32 (exact) and record the mode")
+    p.add_argument("--table_rounding_seed", type=int, default=0,
+                   help="seed of the stochastic rounding's hash (--table_dtype bf16); a resumed run must repeat it")
     p.add_argument("--type_constrained_sampling", type=int, default=0,
                    help="1: entity negatives of a training batch come from the relation's own head / tail type list "
                         "(type_constrain.txt in --input_path, required then) instead of from all entities; same random stream, "
@@ -170,6 +176,8 @@ def get_conf(argv):
         con.set_shared_negatives(argv.shared_negatives_chunk, getattr(argv, "shared_negatives_seed", 0),
                                  by_relation=bool(getattr(argv, "shared_negatives_by_relation", 0)),
                                  in_chunk=getattr(argv, "shared_negatives_in_chunk", 0))
+    if getattr(argv, "table_dtype", "fp32") != "fp32":
+        con.set_table_dtype(argv.table_dtype, seed=getattr(argv, "table_rounding_seed", 0))
     typed = bool(getattr(argv, "type_constrained_sampling", 0))
     path = argv.input_path if not argv.input_path or argv.input_path.endswith("/") else argv.input_path + "/"
     derive = bool(getattr(argv, "derive_type_constraints", 0)) and bool(path) and not os.path.exists(path + "type_constrain.txt") and \
@@ -237,12 +245,35 @@ def checkpoint_arrays(con):
             if not con._sharded(name):
                 out[name + "/RowAdagrad"] = a.detach().cpu().numpy()
     out["global_step"] = np.int64(con.global_step)
+    if getattr(con, "_bf16", False):      # bf16 table storage: the arrays above are float32 (an exact widening); the mode and its rounding seed
+        out["table_dtype"] = table_dtype_record(con)
     if getattr(con, "_shared_chunk", 0):      # shared negatives: the candidates are a hash of (seed, global_step), chunked by `chunk`
         out["shared_negatives"] = shared_negatives_record(con)
     # with sampling one step ahead the device streams are one batch further than the training: store the states the
     # NEXT step's batch starts from, so that a resumed run trains on exactly the batches an uninterrupted one would
     out["rng_streams"] = con.get_stream_states(before_prefetch=True)
     return out
+
+
+def table_dtype_record(con):
+    """What a checkpoint keeps of a run's bf16 table storage: uint64 [1, rounding seed].  An fp32 run writes no record."""
+    return np.array([1, int(getattr(con, "_table_seed", 0))], dtype=np.uint64)
+
+
+def check_table_dtype_record(z, con):
+    """bf16 table storage across a resume.  The stored arrays are float32 either way, so an fp32 run resumes from a bf16
+    checkpoint as from any other, and a bf16 run from an fp32 one -- its tables are rounded to nearest-even once, which is said.
+    A bf16 run that resumes a bf16 checkpoint must repeat the rounding seed: the resumed run then equals the uninterrupted one
+    bit for bit (the hash depends on the seed and the global step only)."""
+    if not getattr(con, "_bf16", False):
+        return
+    if "table_dtype" not in z:
+        print("restore: the checkpoint holds fp32 tables; this run stores bf16 tables: they are rounded to nearest-even once")
+        return
+    was = [int(x) for x in np.asarray(z["table_dtype"]).reshape(-1)]
+    if was[0] == 1 and was[1] != int(con._table_seed):
+        raise KgeError("the checkpoint was written with bf16 table storage and rounding seed %d, this run has %d: resume with the "
+                       "same --table_rounding_seed" % (was[1], int(con._table_seed)))
 
 
 def _shared_negatives_mode(con):
@@ -501,6 +532,7 @@ def restore_checkpoint(con, path, allow_growth=True, arrays=None):
     z = arrays if arrays is not None else {k.replace("__", "/"): v for k, v in np.load(path).items()}
     # shared negatives: a resumed run must draw the candidates the interrupted one would have drawn
     check_shared_negatives_record(z, con)
+    check_table_dtype_record(z, con)
     rng = np.random.default_rng(getattr(con, "seed", 0) + 1)
     shapes = con.trainModel.table_shapes()
     for i, name in enumerate(con.trainModel.table_names):

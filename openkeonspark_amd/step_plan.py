@@ -73,7 +73,8 @@ def wants_sparse_rows(sparse_rows, ent_total, rel_total, width, batch_size, n_ne
 
 def plan(model_id, opt_method, sparse_rows, use_counts, counts_supported, ent_total, rel_total, width, batch_size, n_neg,
          sparse_threshold_bytes=None, adagrad_initial_accumulator=0.1, shared_chunk=0, negative_rel=0, by_relation=False, typed=False,
-         shared_float_supported=0, shared_transd_supported=0, shared_transr_supported=0, in_chunk=0):
+         shared_float_supported=0, shared_transd_supported=0, shared_transr_supported=0, in_chunk=0, table_dtype="fp32",
+         bf16_supported=0):
     """The StepPlan of a configuration.  sparse_rows: None = automatic, True / False = the caller's wish; use_counts: the
     caller's wish; counts_supported: what kge_transe_counts_supported said for the model's descriptor and n_neg.
     shared_chunk: 0 = off; P > 0 = negatives shared by chunks of P positives (NON-PARITY, opt-in: Config.set_shared_negatives),
@@ -84,8 +85,12 @@ def plan(model_id, opt_method, sparse_rows, use_counts, counts_supported, ent_to
     shared_transd_supported: what kge_shared_transd_supported said for them (TransD on such chunks, the same records with the
     transfer rows); shared_transr_supported: what kge_shared_transr_supported said for them (TransR on such chunks, through its
     dense gradient tables: the plan of its unshared step); in_chunk: K >= 0 of a chunk's candidates are its own positives' entities
-    beside the n_neg - negative_rel drawn ones (relation-grouped chunks only); it is checked and changes no plan."""
+    beside the n_neg - negative_rel drawn ones (relation-grouped chunks only); it is checked and changes no plan.
+    table_dtype: "fp32", or "bf16" = the tables are STORED as bf16 (NON-PARITY, opt-in: Config.set_table_dtype), which is the
+    sparse-rows record step whatever the table size, as for the rows-rule optimizers; bf16_supported: what kge_bf16_tables_supported
+    said for the model's descriptor and n_neg."""
     optimizer = optimizer_kind(opt_method)
+    check_table_dtype(table_dtype)
     adam, lazy_adam, adagrad = optimizer == "adam", optimizer == "lazy_adam", optimizer == "adagrad"
     row_adagrad = optimizer == "row_adagrad"
     # LazyAdam -- opt-in, NON-PARITY: Adam on the touched rows only (tf.contrib.opt.LazyAdamOptimizer's rule) for tables whose dense
@@ -101,6 +106,9 @@ def plan(model_id, opt_method, sparse_rows, use_counts, counts_supported, ent_to
     if (adagrad or row_adagrad) and not (float(adagrad_initial_accumulator) > 0.0):
         raise KgeError("adagrad_initial_accumulator must be positive (the Adagrad rule divides by sqrt(accumulator), without an "
                        "epsilon), got %r" % (adagrad_initial_accumulator,))
+    if table_dtype == "bf16":      # storage, not a shadow copy: the record step on the touched rows is the only step that reads it
+        check_bf16_tables(model_id, optimizer, use_counts, counts_supported, width, shared_chunk, bf16_supported)
+        return StepPlan(optimizer, True, True, False, (ent_total + rel_total) * width * 2)
     rows_rule = lazy_adam or adagrad or row_adagrad
     # TransE: exact integer sign-count gradients instead of fp32 atomics (include/kge_mi355.h)
     use_counts = bool(use_counts) and bool(counts_supported)
@@ -133,6 +141,33 @@ def plan(model_id, opt_method, sparse_rows, use_counts, counts_supported, ent_to
     if sparse_rows and not (rows or inplace):
         raise KgeError("sparse_rows needs TransE / TransH / TransD with SGD, LazyAdam or Adagrad")
     return StepPlan(optimizer, use_counts, rows, inplace, table_bytes)
+
+
+TABLE_DTYPES = ("fp32", "bf16")
+
+
+def check_table_dtype(table_dtype):
+    if table_dtype not in TABLE_DTYPES:
+        raise KgeError("table_dtype is \"fp32\" or \"bf16\", got %r" % (table_dtype,))
+
+
+def check_bf16_tables(model_id, optimizer, use_counts, counts_supported, width, shared_chunk=0, bf16_supported=1):
+    """Raises KgeError, naming the limit, for a configuration that bf16 table storage cannot take: it is built for TransE on the
+    one-rank int8-record touched-rows step with SGD or RowAdagrad (include/kge_mi355.h, "bf16 table storage")."""
+    if model_id != TRANSE:
+        raise KgeError("bf16 table storage is built for TransE only: TransH, TransD and TransR have no bf16 emit kernel")
+    if shared_chunk:
+        raise KgeError("bf16 table storage cannot be combined with shared negatives: the shared emit kernels read fp32 tables")
+    if optimizer not in ("sgd", "row_adagrad"):
+        raise KgeError("bf16 table storage needs SGD or RowAdagrad: LazyAdam, Adagrad and TF1 Adam keep fp32 slot tables shaped like "
+                       "the parameter tables and have no bf16 apply kernel")
+    if width % 8 != 0:
+        raise KgeError("bf16 table storage needs an embedding width that is a multiple of 8 (rows of 16-byte chunks), got %d" % width)
+    if not (use_counts and counts_supported):
+        raise KgeError("bf16 table storage needs TransE's sign-count path (use_counts, and a shape kge_transe_counts_supported "
+                       "accepts: width up to 1024, 1 to 63 negatives)")
+    if not bf16_supported:
+        raise KgeError("bf16 table storage: kge_bf16_tables_supported refuses this shape (TransE, width a multiple of 8 up to 1024)")
 
 
 SHARED_MAX_CHUNK, SHARED_MAX_NEGATIVES = 127, 63      # a candidate's count lies within +-P, a positive's within +-2N: both int8

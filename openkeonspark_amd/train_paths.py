@@ -22,7 +22,8 @@ class RowsRule(object):
         L = con.lib
         self.con = con
         self.kind = kind = con._plan.optimizer
-        self.tabs = con._tab_ptrs
+        self.bf16 = bool(con._bf16)      # bf16 table storage: the listed-rows application alone, through its own entry points
+        self.tabs = None if self.bf16 else con._tab_ptrs
         self.ent, self.rel = [t.data_ptr() for t in con._tables[:2]] if len(con._tables) >= 2 else (0, 0)
         if kind == "lazy_adam":
             self._fb_rows, self._float_records, self._listed_rows = \
@@ -43,6 +44,9 @@ class RowsRule(object):
             self._fb_rows, self._float_records, self._listed_rows = \
                 L.kge_forward_backward_sgd_rows, L.kge_float_records_apply, L.kge_transe_apply_rows_sgd
             self.slot_ptrs = self.row_slots = ()
+        if self.bf16:
+            self._fb_rows = self._float_records = None      # (the float-record paths read fp32 tables)
+            self._listed_rows = L.kge_transe_apply_rows_rowadagrad_bf16 if kind == "row_adagrad" else L.kge_transe_apply_rows_sgd_bf16
 
     def _rate(self):
         """The rate arguments every entry point of this rule takes after its data: lr_t and Adam's constants, or alpha."""
@@ -70,6 +74,8 @@ class RowsRule(object):
         i is processed only where live[i] != 0; None = every listed row."""
         con = self.con
         mask = (live.data_ptr() if live is not None else None,) if self.kind == "lazy_adam" else ()
+        if self.bf16:       # stochastic rounding: the hash takes the seed and the global step of this update
+            mask = (ctypes.c_uint64(con._table_seed), ctypes.c_uint64(con.global_step))
         _lib.check(self._listed_rows(ctypes.byref(desc), self.ent, self.rel, *self.row_slots, rows, counts, n_rows, max_rows,
                                      denom, *self._rate(), *mask, con._stream()), con.lib)
 
@@ -79,7 +85,7 @@ class RowsRule(object):
         image.  (Lazy Adam and both Adagrads are not linear in the gradient: they need a row's complete sum.)"""
         con = self.con
         rows, counts, n_rows = buf["rows"].data_ptr(), buf["row_counts"].data_ptr(), buf["n_rows"].data_ptr()
-        if self.kind == "sgd" and fused_ok:
+        if self.kind == "sgd" and fused_ok and not self.bf16:
             _lib.check(con.lib.kge_transe_reduce_apply_records_sgd(ctypes.byref(desc), rec.data_ptr(), dst.data_ptr(), n, self.ent,
                                                                    self.rel, rows, counts, n_rows, denom, float(con.alpha),
                                                                    con._stream()), con.lib)
@@ -468,11 +474,17 @@ def sparse_step(con, dev_batch, n_pos, stride, denom, check_shape=False):
         con._sparse_buf = buf
     st = con._stream()
     buf["dst"].fill_(-1)
-    _lib.check(con.lib.kge_transe_emit_records(
-        ctypes.byref(con._desc), con._tables[0].data_ptr(), con._tables[1].data_ptr(),
-        dev_batch[0].data_ptr(), dev_batch[1].data_ptr(), dev_batch[2].data_ptr(), n_pos, n_neg,
-        dev_batch.shape[1] // (1 + n_neg), denom, buf["rec"].data_ptr(), buf["dst"].data_ptr(), None, None,
-        con._loss.data_ptr(), st), con.lib)
+    if con._bf16:       # bf16 table storage: its own emit kernel, the same records
+        _lib.check(con.lib.kge_transe_emit_records_bf16(
+            ctypes.byref(con._desc), con._tables[0].data_ptr(), con._tables[1].data_ptr(),
+            dev_batch[0].data_ptr(), dev_batch[1].data_ptr(), dev_batch[2].data_ptr(), n_pos, n_neg,
+            dev_batch.shape[1] // (1 + n_neg), denom, buf["rec"].data_ptr(), buf["dst"].data_ptr(), con._loss.data_ptr(), st), con.lib)
+    else:
+        _lib.check(con.lib.kge_transe_emit_records(
+            ctypes.byref(con._desc), con._tables[0].data_ptr(), con._tables[1].data_ptr(),
+            dev_batch[0].data_ptr(), dev_batch[1].data_ptr(), dev_batch[2].data_ptr(), n_pos, n_neg,
+            dev_batch.shape[1] // (1 + n_neg), denom, buf["rec"].data_ptr(), buf["dst"].data_ptr(), None, None,
+            con._loss.data_ptr(), st), con.lib)
     if check_shape:
         nd = ctypes.c_int32(0)
         _lib.check(con.lib.kge_transe_deferred_groups(ctypes.byref(nd)), con.lib)
