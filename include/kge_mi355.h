@@ -859,6 +859,33 @@ int kge_shared_negatives_draw_grouped_mixed(const int32_t *d_h2, const int32_t *
                                             INT cap, INT N, INT K, INT typed, uint64_t seed, INT step, int32_t *d_cand, uint8_t *d_pair,
                                             void *stream);
 
+/* ---- Shared negatives on bf16 tables (NON-PARITY, opt-in; csrc/shared_neg.hip, the shared emit kernel under BF16) ----
+ * The two sections "bf16 table storage" and "TransE on negatives SHARED by a chunk of positives" together: the tables are stored
+ * as bf16 and a chunk gathers 3 P + N rows of them, each half as long.
+ *   Definition. `kge_transe_emit_records_shared[_chunks]` on the exactly widened tables, bit for bit -- records, keys and loss.
+ *   (A lane reads its four elements 4 (l + 64 q) .. + 3 in one 8-byte load and widens them, bits << 16; from there the kernel is
+ *   the fp32 one: same lane-to-element map, same order of every fp32 sum.)  The draw, order and in-chunk kernels work on ids and
+ *   serve unchanged, kge_transe_reduce_records takes the records, and kge_transe_apply_rows_sgd_bf16 /
+ *   kge_transe_apply_rows_rowadagrad_bf16 the row lists it makes.
+ *   Refused (KGE_ERR_UNSUPPORTED, with the reason): a model other than TransE, negative_rel != 0, N outside 1..63, a width that is
+ *   not a multiple of 8 (rows are 16-byte aligned, a lane's load 8-byte aligned), a width above 512 (the kernel's LDS tiles), a
+ *   shape outside kge_transe_counts_supported.  There is no `_at` form: more than one rank stays refused.
+ *   Seeds.  The rounding hash and the shared-negatives hashes start from the same step key, mix(seed + (step + 1) G): with one seed
+ *   for both, the word that rounds columns 4 g .. 4 g + 3 of row `key` is the word that drew the candidate (or the side) whose
+ *   counter is key (D / 4) + g.  The library takes the seeds in different calls and cannot see the pair; Config refuses equal seeds.
+ * kge_bf16_shared_supported: 1 exactly where the two calls accept the model and N (TransE, ent_dim == rel_dim, negative_rel == 0,
+ *   width % 8 == 0, width <= 512, 1 <= N <= 63, fewer than 2^30 rows), else 0.  Host only.
+ * kge_transe_emit_records_shared_bf16 / kge_transe_emit_records_shared_chunks_bf16: the arguments of their fp32 namesakes with
+ *   tables of stored bf16. */
+int kge_bf16_shared_supported(const kge_model_desc *m, INT N);
+int kge_transe_emit_records_shared_bf16(const kge_model_desc *m, const uint16_t *d_ent, const uint16_t *d_rel, const int32_t *d_h, const int32_t *d_t,
+                                        const int32_t *d_r, INT n_pos, INT stride, INT P, const int32_t *d_cand, INT N, const uint8_t *d_pair,
+                                        INT denom, uint32_t *d_rec, int32_t *d_dst, float *d_loss, void *stream);
+int kge_transe_emit_records_shared_chunks_bf16(const kge_model_desc *m, const uint16_t *d_ent, const uint16_t *d_rel, const int32_t *d_h2,
+                                               const int32_t *d_t2, const int32_t *d_r2, INT n_pos, INT stride, const int32_t *d_chunks, INT cap,
+                                               const int32_t *d_cand, INT N, const uint8_t *d_pair, INT denom, uint32_t *d_rec, int32_t *d_dst,
+                                               float *d_loss, void *stream);
+
 /* ---- TransH on relation-grouped chunks (NON-PARITY, opt-in; csrc/shared_proj.hip) ----
  * Every positive of a relation-grouped chunk has the chunk's relation, so a chunk has ONE normalised normal vector and ONE r^,
  * and a candidate is projected and normalised once per chunk: a chunk gathers 2 P + N + 2 table rows where the unshared step

@@ -204,7 +204,12 @@ class Config(object):
         with SGD or RowAdagrad; every updated row is stored by stochastic rounding from a hash of (seed, global step, row,
         column), so a run is reproducible bit for bit and a resumed run must repeat the seed.  get_parameters / checkpoints give
         float32 (an exact widening), set_parameters rounds to nearest-even, and the evaluation paths read a float32 view that
-        lives until the next training step.  Configurations the mode cannot take are refused by set_model_and_session."""
+        lives until the next training step.  Configurations the mode cannot take are refused by set_model_and_session.
+        With set_shared_negatives(chunk, ...), in either call order, the shared step reads the bf16 tables (one rank, widths up to
+        512, chunks by position or by relation, typed and in-chunk candidates included): its records are the fp32 shared emit's
+        on the widened tables bit for bit (include/kge_mi355.h, "Shared negatives on bf16 tables").  The two seeds must then
+        differ -- both hashes start from the same step key, so one seed would round rows with the bits that drew the candidates --
+        and set_model_and_session refuses equal ones, the two defaults of 0 included."""
         step_plan.check_table_dtype(dtype)
         seed = int(seed)
         if not 0 <= seed < (1 << 64):
@@ -548,7 +553,11 @@ class Config(object):
             shared_transd_supported=self.lib.kge_shared_transd_supported(ctypes.byref(probe.descriptor()), self.negative_ent),
             shared_transr_supported=self.lib.kge_shared_transr_supported(ctypes.byref(probe.descriptor()), self.negative_ent),
             in_chunk=self._shared_in_chunk, table_dtype=getattr(self, "_table_dtype", "fp32"),
-            bf16_supported=self.lib.kge_bf16_tables_supported(ctypes.byref(probe.descriptor()), n_neg) if self._bf16 else 0)
+            bf16_supported=self.lib.kge_bf16_tables_supported(ctypes.byref(probe.descriptor()), n_neg) if self._bf16 else 0,
+            bf16_shared_supported=self.lib.kge_bf16_shared_supported(ctypes.byref(probe.descriptor()), self.negative_ent + self._shared_in_chunk)
+            if self._bf16 and self._shared_chunk else 0)
+        if self._bf16 and self._shared_chunk:      # (a shape the plan takes: the two hashes must be keyed apart)
+            step_plan.check_bf16_shared_seeds(self._table_seed, self._shared_seed)
         self._drop_eval_view()
         self.use_counts, self.sparse_rows, self.sparse_inplace = p.use_counts, p.sparse_rows, p.sparse_inplace
         self._adam, self._lazy_adam, self._adagrad = p.adam, p.lazy_adam, p.adagrad

@@ -197,6 +197,10 @@ def _declare(L):
     L.kge_shared_negatives_draw_grouped_mixed.argtypes = [vp, vp, vp, i64, vp, i64, i64, i64, i64, ctypes.c_uint64, i64, vp, vp, vp]      # (N, K)
     L.kge_transe_emit_records_shared_chunks.argtypes = [ctypes.POINTER(ModelDesc), vp, vp, vp, vp, vp, i64, i64, vp, i64, vp, i64, vp, i64, vp, vp,
                                                         vp, vp]
+    # ... on bf16 tables: the arguments of the fp32 namesakes
+    L.kge_bf16_shared_supported.argtypes = [ctypes.POINTER(ModelDesc), i64]
+    L.kge_transe_emit_records_shared_bf16.argtypes = L.kge_transe_emit_records_shared.argtypes
+    L.kge_transe_emit_records_shared_chunks_bf16.argtypes = L.kge_transe_emit_records_shared_chunks.argtypes
     # ... TransH on those chunks, float records (csrc/shared_proj.hip)
     L.kge_shared_float_supported.argtypes = [ctypes.POINTER(ModelDesc), i64]
     L.kge_transh_emit_records_shared_chunks.argtypes = [ctypes.POINTER(ModelDesc), tabs, vp, vp, vp, i64, i64, vp, i64, vp, i64, vp, i64, i64,

@@ -32,6 +32,9 @@
 // IN-CHUNK candidates (kge_shared_negatives_draw_grouped_mixed, behind the grouped draw): K more columns of a chunk's lists are the
 // chunk's own heads / tails at rotated positions; a sibling of the grouped draw kernel writes them, the emit kernels take the wider
 // lists as they take any.
+// bf16 TABLES (kge_transe_emit_records_shared_bf16 / _shared_chunks_bf16; include/kge_mi355.h, "Shared negatives on bf16 tables"): the
+// emit kernel under BF16 reads rows of stored bf16 -- a lane's four elements in one 8-byte load, widened exactly -- and is the
+// fp32 kernel from there on, so it writes what that kernel writes on the widened tables bit for bit.
 #include <algorithm>
 #include <cstring>
 #include <string>
@@ -39,6 +42,7 @@
 
 #include <rocprim/rocprim.hpp>
 
+#include "bf16_dev.hpp"
 #include "engine.hpp"
 #include "mix_dev.hpp"
 #include "sampler_dev.hpp"
@@ -148,7 +152,7 @@ __global__ __launch_bounds__(256) void shared_draw_kernel(DrawArgs a) {
 
 // ---- the emit kernel -----------------------------------------------------------------------------
 struct SharedEmitArgs {
-    const float *ent, *rel;
+    const float *ent, *rel;      // (BF16 instantiations: rows of D stored bf16, uint16_t each)
     const int32_t *h, *t, *r;
     const int32_t *cand;
     const uint8_t *pair;
@@ -181,8 +185,10 @@ __device__ __forceinline__ int sgn_i(float e) { return (e > 0.f ? 1 : 0) - (e < 
 
 // TABLE: workgroup j reads its positions from a.chunks[j] (relation-grouped chunks, kge_transe_emit_records_shared_chunks) instead
 // of computing them from j, P and off; a slot of length 0 blanks its N candidate keys, leaves a zero partial and is done.
-template <int Q, bool VEC, bool TABLE = false>
+// BF16: a.ent / a.rel are bf16 tables (widths that are multiples of 8, so VEC): load_row widens, nothing else differs.
+template <int Q, bool VEC, bool TABLE = false, bool BF16 = false>
 __global__ __launch_bounds__(256) void shared_emit_kernel(SharedEmitArgs a) {
+    static_assert(!BF16 || VEC, "bf16 rows are read four elements at a time");
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
     const int T = a.T, RS = a.RS, D = a.D;
     float *crow = reinterpret_cast<float *>(lds);                                  // [T][RS] normalised candidate rows
@@ -214,6 +220,17 @@ __global__ __launch_bounds__(256) void shared_emit_kernel(SharedEmitArgs a) {
 #pragma unroll
     for (int q = 0; q < Q; q++) valid[q] = 4 * (lane + 64 * q) < RS;
     auto load_row = [&](const float *__restrict__ tab, long long row, float (&x)[4 * Q]) {
+        if constexpr (BF16) {      // elements e0 .. e0 + 3 are two dwords of the stored row: (e0, e0 + 1) and (e0 + 2, e0 + 3)
+            const uint16_t *p = reinterpret_cast<const uint16_t *>(tab) + row * D;
+#pragma unroll
+            for (int q = 0; q < Q; q++) {
+                const int e0 = 4 * (lane + 64 * q);
+                const uint2 v = valid[q] ? *reinterpret_cast<const uint2 *>(p + e0) : make_uint2(0u, 0u);
+                x[4 * q] = bf16_widen_lo(v.x); x[4 * q + 1] = bf16_widen_hi(v.x);
+                x[4 * q + 2] = bf16_widen_lo(v.y); x[4 * q + 3] = bf16_widen_hi(v.y);
+            }
+            return;
+        }
         const float *p = tab + row * D;
 #pragma unroll
         for (int q = 0; q < Q; q++) {
@@ -435,13 +452,28 @@ int draw_call(const char *who, bool aligned, const int32_t *d_h, const int32_t *
     return hip_check(hipGetLastError(), "shared negatives draw launch");
 }
 
+// what the bf16 entry points accept, as a reason where they do not (kge_bf16_shared_supported is this, host only)
+const char *bf16_shared_refusal(const kge_model_desc *m, INT N) {
+    if (!m) return "no model descriptor";
+    if (m->model != KGE_TRANSE) return "shared negatives on bf16 tables: TransE only (the tables of TransH, TransD and TransR stay fp32)";
+    if (m->negative_rel != 0) return "shared negatives on bf16 tables: relation negatives are not supported (negative_rel must be 0)";
+    if (N < 1 || N > 63) return "shared negatives on bf16 tables: 1..63 negatives per positive (a positive's count is within +-2N, an int8)";
+    if (m->ent_dim < 8 || m->ent_dim % 8 != 0)
+        return "shared negatives on bf16 tables: a width that is a multiple of 8 (a lane reads four stored values in one 8-byte load)";
+    if (m->ent_dim > 512) return "shared negatives on bf16 tables: the shared emit kernel holds embedding widths up to 512";
+    if (!kge_transe_counts_supported(m, N)) return "shared negatives on bf16 tables: the sign-count path's shapes only (TransE, equal widths, rows below 2^30)";
+    return nullptr;
+}
+
 // `chunks` null: chunks of P by position, as above.  Not null: the `cap` slots of a chunk table (relation-grouped chunks) -- one
-// workgroup and one loss partial per slot, P and first_position unused.
-int emit_call(const char *who, const kge_model_desc *m, const float *d_ent, const float *d_rel, const int32_t *d_h, const int32_t *d_t,
+// workgroup and one loss partial per slot, P and first_position unused.  bf16: d_ent / d_rel are tables of stored bf16.
+int emit_call(const char *who, const kge_model_desc *m, const void *d_ent, const void *d_rel, const int32_t *d_h, const int32_t *d_t,
               const int32_t *d_r, INT n_pos, INT stride, INT first_position, INT P, const int2 *chunks, INT cap, const int32_t *d_cand, INT N,
-              const uint8_t *d_pair, INT denom, uint32_t *d_rec, int32_t *d_dst, float *d_loss, hipStream_t stream) {
+              const uint8_t *d_pair, INT denom, uint32_t *d_rec, int32_t *d_dst, float *d_loss, hipStream_t stream, bool bf16 = false) {
     const std::string w(who);
     if (!device_ok()) return fail(KGE_ERR_NO_DEVICE, w + ": no usable HIP device");
+    if (bf16)
+        if (const char *why = bf16_shared_refusal(m, N)) return fail(KGE_ERR_UNSUPPORTED, w + ": " + why);
     if (!m || m->model != KGE_TRANSE) return fail(KGE_ERR_UNSUPPORTED, "shared negatives: TransE only");
     if (m->negative_rel != 0) return fail(KGE_ERR_UNSUPPORTED, "shared negatives: relation negatives are not supported (negative_rel must be 0)");
     if (!chunks && (P < 1 || P > 127)) return fail(KGE_ERR_UNSUPPORTED, "shared negatives: the chunk must hold 1..127 positives (a candidate's count is within +-P, an int8)");
@@ -458,7 +490,7 @@ int emit_call(const char *who, const kge_model_desc *m, const float *d_ent, cons
     int rc = g_partials.reserve(n_chunks, "shared negatives loss partials");
     if (rc) return rc;
     SharedEmitArgs a = {};
-    a.ent = d_ent; a.rel = d_rel; a.h = d_h; a.t = d_t; a.r = d_r; a.cand = d_cand; a.pair = d_pair;
+    a.ent = static_cast<const float *>(d_ent); a.rel = static_cast<const float *>(d_rel); a.h = d_h; a.t = d_t; a.r = d_r; a.cand = d_cand; a.pair = d_pair;
     a.n_pos = n_pos; a.n_chunks = n_chunks; a.off = (int)off; a.P = (int)P; a.N = (int)N;
     a.D = m->ent_dim; a.RS = (a.D + 3) / 4 * 4;
     int L, C;
@@ -473,7 +505,15 @@ int emit_call(const char *who, const kge_model_desc *m, const float *d_ent, cons
     const size_t lds_bytes = (size_t)a.T * per_cand + fixed;
     const dim3 grid((unsigned)n_chunks), block(256);
     const bool vec = a.D % 4 == 0;
-    if (chunks) {
+    if (bf16) {
+        if (chunks) {
+            if (a.D <= 256) hipLaunchKernelGGL((shared_emit_kernel<1, true, true, true>), grid, block, lds_bytes, stream, a);
+            else hipLaunchKernelGGL((shared_emit_kernel<2, true, true, true>), grid, block, lds_bytes, stream, a);
+        } else {
+            if (a.D <= 256) hipLaunchKernelGGL((shared_emit_kernel<1, true, false, true>), grid, block, lds_bytes, stream, a);
+            else hipLaunchKernelGGL((shared_emit_kernel<2, true, false, true>), grid, block, lds_bytes, stream, a);
+        }
+    } else if (chunks) {
         if (a.D <= 256) {
             if (vec) hipLaunchKernelGGL((shared_emit_kernel<1, true, true>), grid, block, lds_bytes, stream, a);
             else hipLaunchKernelGGL((shared_emit_kernel<1, false, true>), grid, block, lds_bytes, stream, a);
@@ -850,6 +890,26 @@ int kge_transe_emit_records_shared_chunks(const kge_model_desc *m, const float *
     if (!d_chunks || cap < 0 || (cap < 1 && n_pos > 0)) return fail(KGE_ERR_BAD_ARG, "kge_transe_emit_records_shared_chunks: bad arguments (a chunk table of at least one slot)");
     return emit_call("kge_transe_emit_records_shared_chunks", m, d_ent, d_rel, d_h2, d_t2, d_r2, n_pos, stride, 0, 0,
                      reinterpret_cast<const int2 *>(d_chunks), cap, d_cand, N, d_pair, denom, d_rec, d_dst, d_loss, (hipStream_t)stream);
+}
+
+// ---- shared negatives on bf16 tables (include/kge_mi355.h, "Shared negatives on bf16 tables") ----
+int kge_bf16_shared_supported(const kge_model_desc *m, INT N) { return bf16_shared_refusal(m, N) ? 0 : 1; }
+
+int kge_transe_emit_records_shared_bf16(const kge_model_desc *m, const uint16_t *d_ent, const uint16_t *d_rel, const int32_t *d_h, const int32_t *d_t,
+                                        const int32_t *d_r, INT n_pos, INT stride, INT P, const int32_t *d_cand, INT N, const uint8_t *d_pair,
+                                        INT denom, uint32_t *d_rec, int32_t *d_dst, float *d_loss, void *stream) {
+    return emit_call("kge_transe_emit_records_shared_bf16", m, d_ent, d_rel, d_h, d_t, d_r, n_pos, stride, 0, P, nullptr, 0, d_cand, N, d_pair, denom,
+                     d_rec, d_dst, d_loss, (hipStream_t)stream, true);
+}
+
+int kge_transe_emit_records_shared_chunks_bf16(const kge_model_desc *m, const uint16_t *d_ent, const uint16_t *d_rel, const int32_t *d_h2,
+                                               const int32_t *d_t2, const int32_t *d_r2, INT n_pos, INT stride, const int32_t *d_chunks, INT cap,
+                                               const int32_t *d_cand, INT N, const uint8_t *d_pair, INT denom, uint32_t *d_rec, int32_t *d_dst,
+                                               float *d_loss, void *stream) {
+    if (!d_chunks || cap < 0 || (cap < 1 && n_pos > 0))
+        return fail(KGE_ERR_BAD_ARG, "kge_transe_emit_records_shared_chunks_bf16: bad arguments (a chunk table of at least one slot)");
+    return emit_call("kge_transe_emit_records_shared_chunks_bf16", m, d_ent, d_rel, d_h2, d_t2, d_r2, n_pos, stride, 0, 0,
+                     reinterpret_cast<const int2 *>(d_chunks), cap, d_cand, N, d_pair, denom, d_rec, d_dst, d_loss, (hipStream_t)stream, true);
 }
 
 }  // extern "C"

@@ -130,7 +130,11 @@ def parse_args(argv=None):
     p.add_argument("--table_dtype", type=str, default="fp32", choices=("fp32", "bf16"),
                    help="bf16 (NON-PARITY, opt-in): TransE's tables are stored as bf16 -- half the memory and half the bytes of every "
                         "gather and touched-row update -- and trained on the one-rank int8-record touched-rows step with SGD or "
-                        "RowAdagrad; updated rows are stored by stochastic rounding.  Checkpoints stay float32 (exact) and record the mode")
+                        "RowAdagrad; updated rows are stored by stochastic rounding.  Checkpoints stay float32 (exact) and record the mode.  "
+                        "With --shared_negatives_chunk P (one rank, widths up to 512, with or without --shared_negatives_by_relation) "
+                        "the shared step gathers its 3 P + N rows per chunk from the bf16 tables; --table_rounding_seed and "
+                        "--shared_negatives_seed must then differ (equal seeds, the defaults included, are refused: the two hashes would "
+                        "share their bits)")
     p.add_argument("--table_rounding_seed", type=int, default=0,
                    help="seed of the stochastic rounding's hash (--table_dtype bf16); a resumed run must repeat it")
     p.add_argument("--type_constrained_sampling", type=int, default=0,

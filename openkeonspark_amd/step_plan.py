@@ -74,7 +74,7 @@ def wants_sparse_rows(sparse_rows, ent_total, rel_total, width, batch_size, n_ne
 def plan(model_id, opt_method, sparse_rows, use_counts, counts_supported, ent_total, rel_total, width, batch_size, n_neg,
          sparse_threshold_bytes=None, adagrad_initial_accumulator=0.1, shared_chunk=0, negative_rel=0, by_relation=False, typed=False,
          shared_float_supported=0, shared_transd_supported=0, shared_transr_supported=0, in_chunk=0, table_dtype="fp32",
-         bf16_supported=0):
+         bf16_supported=0, bf16_shared_supported=0):
     """The StepPlan of a configuration.  sparse_rows: None = automatic, True / False = the caller's wish; use_counts: the
     caller's wish; counts_supported: what kge_transe_counts_supported said for the model's descriptor and n_neg.
     shared_chunk: 0 = off; P > 0 = negatives shared by chunks of P positives (NON-PARITY, opt-in: Config.set_shared_negatives),
@@ -88,7 +88,8 @@ def plan(model_id, opt_method, sparse_rows, use_counts, counts_supported, ent_to
     beside the n_neg - negative_rel drawn ones (relation-grouped chunks only); it is checked and changes no plan.
     table_dtype: "fp32", or "bf16" = the tables are STORED as bf16 (NON-PARITY, opt-in: Config.set_table_dtype), which is the
     sparse-rows record step whatever the table size, as for the rows-rule optimizers; bf16_supported: what kge_bf16_tables_supported
-    said for the model's descriptor and n_neg."""
+    said for the model's descriptor and n_neg; bf16_shared_supported: what kge_bf16_shared_supported said for the descriptor and the
+    entity negatives with in_chunk -- the two modes together are the shared-negatives step on bf16 tables, one rank."""
     optimizer = optimizer_kind(opt_method)
     check_table_dtype(table_dtype)
     adam, lazy_adam, adagrad = optimizer == "adam", optimizer == "lazy_adam", optimizer == "adagrad"
@@ -107,7 +108,11 @@ def plan(model_id, opt_method, sparse_rows, use_counts, counts_supported, ent_to
         raise KgeError("adagrad_initial_accumulator must be positive (the Adagrad rule divides by sqrt(accumulator), without an "
                        "epsilon), got %r" % (adagrad_initial_accumulator,))
     if table_dtype == "bf16":      # storage, not a shadow copy: the record step on the touched rows is the only step that reads it
-        check_bf16_tables(model_id, optimizer, use_counts, counts_supported, width, shared_chunk, bf16_supported)
+        check_bf16_tables(model_id, optimizer, use_counts, counts_supported, width, shared_chunk, bf16_supported,
+                          bf16_shared_supported, negative_rel)
+        if shared_chunk:      # the chunk, the candidate counts, typed and in-chunk candidates: the shared step's own limits
+            check_shared_negatives(model_id, optimizer, use_counts, shared_chunk, n_neg - negative_rel, negative_rel, by_relation, typed,
+                                   in_chunk=in_chunk)
         return StepPlan(optimizer, True, True, False, (ent_total + rel_total) * width * 2)
     rows_rule = lazy_adam or adagrad or row_adagrad
     # TransE: exact integer sign-count gradients instead of fp32 atomics (include/kge_mi355.h)
@@ -151,13 +156,24 @@ def check_table_dtype(table_dtype):
         raise KgeError("table_dtype is \"fp32\" or \"bf16\", got %r" % (table_dtype,))
 
 
-def check_bf16_tables(model_id, optimizer, use_counts, counts_supported, width, shared_chunk=0, bf16_supported=1):
+BF16_SHARED_MAX_WIDTH = 512      # the shared emit kernel's LDS tiles
+
+
+def check_bf16_tables(model_id, optimizer, use_counts, counts_supported, width, shared_chunk=0, bf16_supported=1, bf16_shared_supported=0,
+                      negative_rel=0):
     """Raises KgeError, naming the limit, for a configuration that bf16 table storage cannot take: it is built for TransE on the
-    one-rank int8-record touched-rows step with SGD or RowAdagrad (include/kge_mi355.h, "bf16 table storage")."""
+    one-rank int8-record touched-rows step with SGD or RowAdagrad (include/kge_mi355.h, "bf16 table storage").  shared_chunk > 0:
+    together with shared negatives, which the shared emit kernel takes on bf16 tables where kge_bf16_shared_supported says so
+    (bf16_shared_supported: its answer; "Shared negatives on bf16 tables")."""
     if model_id != TRANSE:
-        raise KgeError("bf16 table storage is built for TransE only: TransH, TransD and TransR have no bf16 emit kernel")
-    if shared_chunk:
-        raise KgeError("bf16 table storage cannot be combined with shared negatives: the shared emit kernels read fp32 tables")
+        raise KgeError("bf16 table storage is built for TransE only: TransH, TransD and TransR have no bf16 emit kernel"
+                       + (", shared or not: their tables stay fp32" if shared_chunk else ""))
+    if shared_chunk and negative_rel:
+        raise KgeError("bf16 table storage with shared negatives: relation negatives are not supported (negative_rel must be 0, "
+                       "got %d)" % negative_rel)
+    if shared_chunk and width > BF16_SHARED_MAX_WIDTH:
+        raise KgeError("bf16 table storage with shared negatives: the shared emit kernel holds embedding widths up to %d, got %d"
+                       % (BF16_SHARED_MAX_WIDTH, width))
     if optimizer not in ("sgd", "row_adagrad"):
         raise KgeError("bf16 table storage needs SGD or RowAdagrad: LazyAdam, Adagrad and TF1 Adam keep fp32 slot tables shaped like "
                        "the parameter tables and have no bf16 apply kernel")
@@ -168,6 +184,23 @@ def check_bf16_tables(model_id, optimizer, use_counts, counts_supported, width, 
                        "accepts: width up to 1024, 1 to 63 negatives)")
     if not bf16_supported:
         raise KgeError("bf16 table storage: kge_bf16_tables_supported refuses this shape (TransE, width a multiple of 8 up to 1024)")
+    if shared_chunk and not bf16_shared_supported:
+        raise KgeError("bf16 table storage cannot be combined with shared negatives at this shape: kge_bf16_shared_supported refuses "
+                       "it (TransE, entity negatives only, a width that is a multiple of 8 up to %d, 1 to %d candidates per "
+                       "positive)" % (BF16_SHARED_MAX_WIDTH, SHARED_MAX_NEGATIVES))
+
+
+def check_bf16_shared_seeds(table_seed, shared_seed):
+    """Raises KgeError when bf16 table storage and shared negatives would hash from the same seed.  Both counter hashes start from
+    the step key mix(seed + (step + 1) G) (include/kge_mi355.h: "Stochastic rounding", "Candidates"): with equal seeds the 64 bits
+    that round the columns 4 g .. 4 g + 3 of row `key` are the bits that drew the candidate or the side whose counter equals
+    key (D / 4) + g, and the rounding would no longer be independent of the rows a step updates.  The definitions of the two
+    hashes are fixed (runs repeat bit for bit), so the seeds must differ."""
+    if int(table_seed) == int(shared_seed):
+        raise KgeError("bf16 table storage with shared negatives: the rounding seed and the shared-negatives seed must differ (both are "
+                       "%d): the two counter hashes share their step key, so with one seed the bits that round a row are the bits that "
+                       "drew a candidate -- set_table_dtype(\"bf16\", seed=...) / set_shared_negatives(chunk, seed=...), "
+                       "--table_rounding_seed / --shared_negatives_seed" % int(table_seed))
 
 
 SHARED_MAX_CHUNK, SHARED_MAX_NEGATIVES = 127, 63      # a candidate's count lies within +-P, a positive's within +-2N: both int8

@@ -524,9 +524,11 @@ def shared_step(con, dev, n_pos, stride, denom):
     h, t, r = dev[0].data_ptr(), dev[1].data_ptr(), dev[2].data_ptr()
     _lib.check(con.lib.kge_shared_negatives_draw(h, t, r, n_pos, con._first_pos, P, N, con._shared_seed, con.global_step,
                                                  buf["cand"].data_ptr(), buf["pair"].data_ptr(), st), con.lib)
-    _lib.check(con.lib.kge_transe_emit_records_shared(ctypes.byref(con._desc), con._tables[0].data_ptr(), con._tables[1].data_ptr(),
-                                                      h, t, r, n_pos, stride, P, buf["cand"].data_ptr(), N, buf["pair"].data_ptr(),
-                                                      denom, buf["rec"].data_ptr(), buf["dst"].data_ptr(), con._loss.data_ptr(), st),
+    # bf16 table storage: the same kernel reading stored bf16 rows, the same records
+    emit = con.lib.kge_transe_emit_records_shared_bf16 if con._bf16 else con.lib.kge_transe_emit_records_shared
+    _lib.check(emit(ctypes.byref(con._desc), con._tables[0].data_ptr(), con._tables[1].data_ptr(),
+                    h, t, r, n_pos, stride, P, buf["cand"].data_ptr(), N, buf["pair"].data_ptr(),
+                    denom, buf["rec"].data_ptr(), buf["dst"].data_ptr(), con._loss.data_ptr(), st),
                con.lib)
     buf["shared_step"], buf["shared_shape"], buf["shared_batch"] = con.global_step, (n_pos, n_chunks), dev
     con._rule.reduce_apply(con._desc, buf["rec"], buf["dst"], 3 * n_pos + n_chunks * N, buf, denom,
@@ -691,9 +693,10 @@ def shared_grouped_step(con, dev, n_pos, stride, denom):
         con._rule.advance()
         con.global_step += 1
         return
-    _lib.check(L.kge_transe_emit_records_shared_chunks(ctypes.byref(con._desc), con._tables[0].data_ptr(), con._tables[1].data_ptr(), h2, t2, r2,
-                                                       n_pos, stride, chunks, cap, cand, N, pair, denom, buf["rec"].data_ptr(),
-                                                       buf["dst"].data_ptr(), con._loss.data_ptr(), st), L)
+    emit = L.kge_transe_emit_records_shared_chunks_bf16 if con._bf16 else L.kge_transe_emit_records_shared_chunks      # (bf16 table storage)
+    _lib.check(emit(ctypes.byref(con._desc), con._tables[0].data_ptr(), con._tables[1].data_ptr(), h2, t2, r2,
+                    n_pos, stride, chunks, cap, cand, N, pair, denom, buf["rec"].data_ptr(),
+                    buf["dst"].data_ptr(), con._loss.data_ptr(), st), L)
     buf["shared_step"], buf["shared_shape"], buf["shared_batch"] = con.global_step, (n_pos, cap), dev
     con._rule.reduce_apply(con._desc, buf["rec"], buf["dst"], 3 * n_pos + cap * N, buf, denom,
                            fused_ok=getattr(con, "sparse_fused", True) and D % 4 == 0)
