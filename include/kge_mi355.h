@@ -119,6 +119,11 @@ const char *kge_version(void);
  *                        histogram, scatter through global cursors, bucket sort), which inputs of more than 2048 tiles (4 194 304
  *                        keys) take as well.  Same sorted keys and row spans; the order inside a key is unspecified in both.
  *                        1024 / 4096 = the two-launch form at that tile size (measurements)
+ *   "counts_sort_blocked": layout of the two-launch sort's per-tile bucket offsets and order of its bucket pass: 1 (default) = one
+ *                        packed word (start | length << 16) per (tile, bucket), stored block-major in blocks of 8 buckets, and
+ *                        the bucket pass's workgroups take the buckets in an order that keeps neighbouring buckets on one XCD
+ *                        (speed only); 0 = a row of 513 exclusive offsets per tile and bucket = workgroup index.  Same results.
+ *                        4 / 16 = blocks of that many buckets (measurements; tile size 2048 only, other tile sizes take 8)
  *   "ride_shares":       where an armed sampler (kge_sampling_attach) rides: percent of its workgroups for the bucket histogram /
  *                        bucket scatter / bucket sort / the launch that ends the step, one byte each; parts that no launch took
  *                        are launched by kge_sampling_flush.  The two-launch sort has no histogram launch: byte 0 is ignored

@@ -254,6 +254,7 @@ int kge_set_option(const char *name, INT value) {
         return KGE_OK;
     }
     if (n == "counts_sort_tiles") { engine().counts_sort_tiles = value > 0 ? (int)value : 0; return KGE_OK; }
+    if (n == "counts_sort_blocked") { engine().counts_sort_blocked = value > 0 ? (int)value : 0; return KGE_OK; }
     if (n == "ride_shares") { engine().ride_shares = (int)value; return KGE_OK; }
     if (n == "transr_bf16x3") { engine().transr_bf16x3 = value != 0; return KGE_OK; }
     if (n == "transr_groups") { engine().transr_groups = (int)value; return KGE_OK; }

@@ -115,6 +115,7 @@ struct Engine {
     int persist_threads = 512;  // threads per workgroup of the persistent launch (512, or 1024: spills at its 128-register cap, measured slower)
     int counts_force_sort = 0;  // test hook: take the sort+segsum reduction even for small tables
     int counts_sort_tiles = 1;  // record sort of the counting paths: 1 = two launches (per-tile sort, then one workgroup per bucket collecting its segments: transe_counts.hip bkt_tile_kernel / bkt_merge_kernel), 0 = histogram + scatter + sort (A/B runs, test reference); 1024 / 4096 = two launches at that tile size (measurements; 1 means 2048)
+    int counts_sort_blocked = 1;  // two-launch record sort: 1 = the tile pass publishes one packed word (start | len << 16) per (tile, bucket), block-major in blocks of 8 buckets, and the bucket pass takes its buckets in XCD-affine order; 0 = [tile][NB + 1] exclusive offsets and bucket = blockIdx.x (A/B runs, test reference); 4 / 16 = blocks of that many buckets (measurements; 1 means 8).  Same results
     // percent of an armed sampler's workgroups riding in bkt_hist / bkt_scatter / bkt_sort / the launch that ends the step (byte 0..3).
     // The two-launch sort has no histogram launch: byte 0 is IGNORED there, byte 1 is its tile pass, byte 2 its bucket pass.
     // -1 (default) = automatic: the three-launch form carries all of it in the scatter launch -- spread 20/35/20/25 over the four it was

@@ -51,7 +51,7 @@ struct CtWork {
     DevBuf<int32_t> n_valid;
     DevBuf<int32_t> tile_hist, bucket_start;   // LDS-bucket path: bucket totals + cursors, bucket starts
     DevBuf<int32_t> pairs;                     // [2*M] (record id, destination) grouped by bucket (two-launch sort: by tile, then bucket)
-    DevBuf<int32_t> tile_off;                  // two-launch sort: [tiles][NB + 1] exclusive bucket offsets inside each tile
+    DevBuf<int32_t> tile_off;                  // two-launch sort: one packed word per (tile, bucket), block-major (option "counts_sort_blocked" = 0: [tiles][NB + 1] exclusive bucket offsets inside each tile)
     DevBuf<float2> pair_aux;                   // [M] pair-count path: (a, +-1/|projected|) per record
     DevBuf<char> sort_tmp;                     // rocPRIM scratch (sort, scan)
     DevBuf<float> ctxn;                        // pair-count path, TransH: normalised normal vectors
@@ -627,10 +627,23 @@ static void launch_bkt_sort(int2 *pairs, int rpb, int rows, int32_t *totals, int
 //                (The fused step's keys are group-major, KeyMap below: every tile holds the same mix of slots.)
 // The bucket pass keeps two words per tile in LDS: at most kSortMaxTiles tiles (M <= 4 194 304 keys at the default tile; the
 // headline batch has 952 392), more take the three-launch form.
+// Engine option "counts_sort_blocked" (default 1; template parameter G > 0) changes how the offsets travel and which workgroup takes
+// which bucket, and nothing else:
+//   packed, block-major offsets   cell (t, b) is ONE word, start | len << 16 (the cell's first pair inside the tile's run and its
+//                pair count, both <= T), at off_pk[((b / G) * n_tiles + t) * G + b % G].  The tile pass writes its NB words as NB / G
+//                pieces of 4 G contiguous bytes; a bucket-pass thread reads one word per tile, 4 G bytes apart, so a workgroup's reads
+//                cover n_tiles * G / 32 lines where a column of off[t][0 .. NB] touches one line per tile, and the G buckets of a
+//                block read the same lines.  The tile's live count is not stored: bucket_start[NB] is the last bucket's end.
+//   XCD-affine bucket order       workgroup i of the bucket pass takes bucket (i % 8) * (NB / 8) + i / 8.  Workgroups are observed
+//                to be dealt round-robin over the 8 XCDs, so workgroups i and i + 8 -- neighbouring buckets -- share an L2, and
+//                with it the off_pk lines of their block and the tile_pairs lines that hold the pairs of adjacent buckets.  This
+//                is for SPEED ONLY: every placement gives the same outputs, and nothing relies on which XCD a workgroup gets.
+// G = 0 is the sort as it was: off[t][0 .. NB] exclusive offsets (off[t][NB] = the tile's live count), bucket = blockIdx.x.
 // ---------------------------------------------------------------------------------------------
 constexpr int kSortTile = 2048;       // keys per tile (default; 1024 and 4096 are compiled for measurements)
 constexpr int kSortMaxTiles = 2048;
 constexpr int kOffStride = NB + 1;
+constexpr int kSortBlock = 8;         // buckets per block of packed offsets (default; 4 and 16 are compiled for measurements)
 
 // Group-major keys (the fused step's emit kernel, option "emit_keys_grouped"): position p = b * S + slot holds the key of record
 // id = slot * n_pos + b -- the records themselves stay slot-major.  p / S is a multiply-high by a magic the host makes
@@ -657,7 +670,7 @@ __device__ __forceinline__ int key_id_of(unsigned S, unsigned magic, unsigned sh
     return (int)(((unsigned)p - b * S) * (unsigned)n_pos + b);
 }
 
-template <int T, bool GROUPED = false>
+template <int T, bool GROUPED = false, int G = 0>
 __global__ __launch_bounds__(256) void bkt_tile_kernel(const int32_t *__restrict__ dst, int M, int rpb, int2 *__restrict__ tile_pairs,
                                                        int32_t *__restrict__ tile_off, int32_t *__restrict__ plan_counter, SamplerArgs ride,
                                                        int n_tiles, unsigned km_S, unsigned km_magic, unsigned km_shift, int km_n_pos) {
@@ -666,6 +679,8 @@ __global__ __launch_bounds__(256) void bkt_tile_kernel(const int32_t *__restrict
         sample_block_ride(ride, (long long)blockIdx.x - n_tiles, bern_lds);
         return;
     }
+    static_assert(T < 65536, "a cell's start and length share one 32-bit word");
+    static_assert(G == 0 || (G % 2 == 0 && NB % G == 0), "a thread's two buckets lie in one block");
     constexpr int K = T / 256;
     __shared__ int hist[NB];
     __shared__ int wave_total[4];
@@ -697,9 +712,15 @@ __global__ __launch_bounds__(256) void bkt_tile_kernel(const int32_t *__restrict
         int excl = incl - run;
         for (int w = 0; w < wave; w++) excl += wave_total[w];
         hist[2 * threadIdx.x] = excl; hist[2 * threadIdx.x + 1] = excl + v0;
-        int32_t *off = tile_off + (size_t)blockIdx.x * kOffStride;
-        off[2 * threadIdx.x] = excl; off[2 * threadIdx.x + 1] = excl + v0;
-        if (threadIdx.x == 255) off[NB] = excl + run;
+        if constexpr (G > 0) {             // buckets 2 tid and 2 tid + 1 are neighbours inside block 2 tid / G: one 8-byte store
+            const int b0 = 2 * threadIdx.x;
+            int32_t *pk = tile_off + ((size_t)(b0 / G) * n_tiles + blockIdx.x) * G + b0 % G;
+            *reinterpret_cast<int2 *>(pk) = make_int2(excl | (v0 << 16), (excl + v0) | (v1 << 16));
+        } else {
+            int32_t *off = tile_off + (size_t)blockIdx.x * kOffStride;
+            off[2 * threadIdx.x] = excl; off[2 * threadIdx.x + 1] = excl + v0;
+            if (threadIdx.x == 255) off[NB] = excl + run;
+        }
     }
     __syncthreads();
     const int live = wave_total[0] + wave_total[1] + wave_total[2] + wave_total[3];
@@ -713,7 +734,7 @@ __global__ __launch_bounds__(256) void bkt_tile_kernel(const int32_t *__restrict
     for (int i = threadIdx.x; i < live; i += 256) tile_pairs[base + i] = stage[i];
 }
 
-template <bool PLAN, int T>
+template <bool PLAN, int T, int G = 0>
 __global__ __launch_bounds__(256) void bkt_merge_kernel(const int2 *__restrict__ tile_pairs, const int32_t *__restrict__ tile_off, int n_tiles,
                                                         int32_t *__restrict__ bucket_start, int M, int rpb, int rows,
                                                         int32_t *__restrict__ out_keys, int32_t *__restrict__ out_ids, SegPlan plan,
@@ -727,7 +748,9 @@ __global__ __launch_bounds__(256) void bkt_merge_kernel(const int2 *__restrict__
     __shared__ int seg_pre[kSortMaxTiles + 1];   // pairs of the bucket in the tiles before t
     __shared__ int seg_src[kSortMaxTiles];       // where segment t starts in tile_pairs
     __shared__ int wave_len[4], wave_below[4];
-    const int b = blockIdx.x;
+    static_assert(NB % 8 == 0 && (G == 0 || NB % G == 0), "the XCD runs and the offset blocks tile the buckets");
+    // G > 0: workgroups i and i + 8 take neighbouring buckets (see above: speed only, no placement is relied on)
+    const int b = G > 0 ? ((int)blockIdx.x % 8) * (NB / 8) + (int)blockIdx.x / 8 : (int)blockIdx.x;
     // every thread takes a contiguous span of the tiles (all its loads in flight together); the block scans the span sums
     constexpr int PER = kSortMaxTiles / 256;
     const int per = (n_tiles + 255) / 256;
@@ -735,10 +758,17 @@ __global__ __launch_bounds__(256) void bkt_merge_kernel(const int2 *__restrict__
     int a[PER], e[PER];
 #pragma unroll
     for (int j = 0; j < PER; j++) {
-        const int32_t *off = tile_off + (size_t)min(t_lo + j, max(n_tiles - 1, 0)) * kOffStride + b;   // (clamped: always a valid row)
+        const int tc = min(t_lo + j, max(n_tiles - 1, 0));   // (clamped: always a valid row)
         const bool mine = t_lo + j < t_hi;
-        a[j] = mine ? off[0] : 0;
-        e[j] = mine ? off[1] : 0;
+        if constexpr (G > 0) {
+            const unsigned w = mine ? (unsigned)tile_off[((size_t)(b / G) * n_tiles + tc) * G + b % G] : 0u;
+            a[j] = (int)(w & 0xFFFFu);
+            e[j] = a[j] + (int)(w >> 16);
+        } else {
+            const int32_t *off = tile_off + (size_t)tc * kOffStride + b;
+            a[j] = mine ? off[0] : 0;
+            e[j] = mine ? off[1] : 0;
+        }
     }
     int len = 0, below = 0;
 #pragma unroll
@@ -777,7 +807,7 @@ __global__ __launch_bounds__(256) void bkt_merge_kernel(const int2 *__restrict__
     });
 }
 
-template <int T>
+template <int T, int G>
 static void launch_tile_sort(const int32_t *dst, int n_tiles, int M, int rows, int rpb, const SegPlan *plan, hipStream_t stream,
                              const KeyMap *km) {
     int2 *pairs = reinterpret_cast<int2 *>(g_c.pairs.ptr());
@@ -785,19 +815,19 @@ static void launch_tile_sort(const int32_t *dst, int n_tiles, int M, int rows, i
     unsigned n_ride = take_ride(ride, 1, true);
     if (n_tiles + n_ride > 0) {
         if (km)
-            hipLaunchKernelGGL((bkt_tile_kernel<T, true>), dim3((unsigned)n_tiles + n_ride), dim3(256), 0, stream, dst, M, rpb, pairs,
+            hipLaunchKernelGGL((bkt_tile_kernel<T, true, G>), dim3((unsigned)n_tiles + n_ride), dim3(256), 0, stream, dst, M, rpb, pairs,
                                g_c.tile_off.ptr(), plan ? plan->n_pieces : nullptr, ride, n_tiles, km->S, km->magic, km->shift, km->n_pos);
         else
-            hipLaunchKernelGGL((bkt_tile_kernel<T, false>), dim3((unsigned)n_tiles + n_ride), dim3(256), 0, stream, dst, M, rpb, pairs,
+            hipLaunchKernelGGL((bkt_tile_kernel<T, false, G>), dim3((unsigned)n_tiles + n_ride), dim3(256), 0, stream, dst, M, rpb, pairs,
                                g_c.tile_off.ptr(), plan ? plan->n_pieces : nullptr, ride, n_tiles, 0u, 0u, 0u, 0);
     }
     ride = SamplerArgs();
     n_ride = take_ride(ride, 2, true);
     if (plan)
-        hipLaunchKernelGGL((bkt_merge_kernel<true, T>), dim3(NB + n_ride), dim3(256), sizeof(int) * (size_t)rpb, stream, pairs, g_c.tile_off.ptr(),
+        hipLaunchKernelGGL((bkt_merge_kernel<true, T, G>), dim3(NB + n_ride), dim3(256), sizeof(int) * (size_t)rpb, stream, pairs, g_c.tile_off.ptr(),
                            n_tiles, g_c.bucket_start.ptr(), M, rpb, rows, g_c.dst_sorted.ptr(), g_c.ids_sorted.ptr(), *plan, ride);
     else
-        hipLaunchKernelGGL((bkt_merge_kernel<false, T>), dim3(NB + n_ride), dim3(256), sizeof(int) * (size_t)rpb, stream, pairs, g_c.tile_off.ptr(),
+        hipLaunchKernelGGL((bkt_merge_kernel<false, T, G>), dim3(NB + n_ride), dim3(256), sizeof(int) * (size_t)rpb, stream, pairs, g_c.tile_off.ptr(),
                            n_tiles, g_c.bucket_start.ptr(), M, rpb, rows, g_c.dst_sorted.ptr(), g_c.ids_sorted.ptr(), SegPlan(), ride);
 }
 
@@ -1398,6 +1428,8 @@ __global__ __launch_bounds__(256) void segsum_pairs_kernel(const uint32_t *__res
 // than kSortMaxTiles tiles take the latter too.
 // km: the keys are group-major (KeyMap); only the two-launch form translates positions to record ids -- ask sort_takes_tiles first.
 static int sort_tile_size() { const int opt = engine().counts_sort_tiles; return opt == 1024 || opt == 4096 ? opt : kSortTile; }
+// Engine option "counts_sort_blocked": buckets per block of packed tile offsets, 0 = the [tile][NB + 1] layout (see bkt_tile_kernel)
+static int sort_block_size() { const int opt = engine().counts_sort_blocked; return opt == 4 || opt == 16 ? opt : opt ? kSortBlock : 0; }
 bool sort_takes_tiles(int64_t M) { return engine().counts_sort_tiles != 0 && (M + sort_tile_size() - 1) / sort_tile_size() <= kSortMaxTiles; }
 int bucket_sort_records(const int32_t *dst, int64_t M, int rows, int rpb, const SegPlan *plan, hipStream_t stream, const int32_t *&n_live,
                         const KeyMap *km = nullptr) {
@@ -1408,10 +1440,19 @@ int bucket_sort_records(const int32_t *dst, int64_t M, int rows, int rpb, const 
     const int T = sort_tile_size();
     const int64_t n_tiles_new = (M + T - 1) / T;
     if (sort_takes_tiles(M)) {
-        if ((rc = g_c.tile_off.reserve((n_tiles_new + 1) * kOffStride, "counts tile offsets"))) return rc;
-        if (T == 1024) launch_tile_sort<1024>(dst, (int)n_tiles_new, (int)M, rows, rpb, plan, stream, km);
-        else if (T == 4096) launch_tile_sort<4096>(dst, (int)n_tiles_new, (int)M, rows, rpb, plan, stream, km);
-        else launch_tile_sort<kSortTile>(dst, (int)n_tiles_new, (int)M, rows, rpb, plan, stream, km);
+        const int G = sort_block_size();
+        if ((rc = g_c.tile_off.reserve(G ? (n_tiles_new + 1) * NB : (n_tiles_new + 1) * kOffStride, "counts tile offsets"))) return rc;
+        const int n_tiles = (int)n_tiles_new;
+        if (T == 1024) {                   // (the measurement tile sizes take the default block size)
+            if (G) launch_tile_sort<1024, kSortBlock>(dst, n_tiles, (int)M, rows, rpb, plan, stream, km);
+            else launch_tile_sort<1024, 0>(dst, n_tiles, (int)M, rows, rpb, plan, stream, km);
+        } else if (T == 4096) {
+            if (G) launch_tile_sort<4096, kSortBlock>(dst, n_tiles, (int)M, rows, rpb, plan, stream, km);
+            else launch_tile_sort<4096, 0>(dst, n_tiles, (int)M, rows, rpb, plan, stream, km);
+        } else if (G == 4) launch_tile_sort<kSortTile, 4>(dst, n_tiles, (int)M, rows, rpb, plan, stream, km);
+        else if (G == 16) launch_tile_sort<kSortTile, 16>(dst, n_tiles, (int)M, rows, rpb, plan, stream, km);
+        else if (G) launch_tile_sort<kSortTile, kSortBlock>(dst, n_tiles, (int)M, rows, rpb, plan, stream, km);
+        else launch_tile_sort<kSortTile, 0>(dst, n_tiles, (int)M, rows, rpb, plan, stream, km);
         return KGE_OK;
     }
     if (km) return fail(KGE_ERR_UNSUPPORTED, "record sort: group-major keys need the two-launch form");
