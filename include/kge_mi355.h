@@ -1224,6 +1224,31 @@ int kge_rank_candidates_range(const kge_model_desc *m, const float *const tables
                               const int32_t *d_tail_cand, INT tail_stride, const int32_t *d_head_cand, INT head_stride,
                               INT n_cand, INT flags, uint64_t seed, int64_t *d_counts, void *stream);
 
+/* ---- Evaluation on bf16 tables (csrc/bf16_eval.hip; csrc/rank_cand.hip, the fused kernel under BF16) ----
+ * The evaluators whose cost is the rows they gather -- kge_predict and kge_rank_candidates -- on tables STORED as bf16 ("bf16
+ * table storage"): d_ent [ent_total, D] and d_rel [rel_total, D], one uint16 per element, in place of tables[].  No float32 copy
+ * of a table is made or needed, and a gathered row is half the bytes.
+ * Definition.  A stored row is read in the team layout of the fp32 kernels (lane l of a team of L holds elements l, l + L, ...;
+ *   (L, C) is for_team_shape's rung for D), each element widened exactly (bits << 16), elements from D on are 0.  Every operation
+ *   after the load is the fp32 kernel's, in its order.  So:
+ *     kge_predict_bf16          returns, bit for bit, the scores kge_predict returns on the widened tables;
+ *     kge_rank_candidates_bf16  returns the counts kge_rank_candidates returns on the widened tables, in every candidate mode
+ *                               (lists, DRAWN, DRAWN | TYPED), both sides, NO_HEAD, FILTERED, any "rankc_slices", and in the
+ *                               two-stage form of option "rankc_fused" = 0 (pairs spelled out, scored by kge_predict_bf16's kernel,
+ *                               counted), which gives the fused form's counts.
+ *   The rows are deliberately not read as packed pairs: that would change the order of the sums, and with it the bits.
+ * kge_bf16_eval_supported (host only, no device needed): 1 exactly when the model is TransE, ent_dim == rel_dim, D % 8 == 0 and
+ *   8 <= D <= 1024 -- the storage rule of "bf16 table storage" -- else 0.  The two calls refuse every other descriptor with
+ *   KGE_ERR_UNSUPPORTED and the limit's name.
+ * Arguments, the n == 0 and n_cand == 0 cases, disabled triples, the files FILTERED / TYPED need and every other error are those of
+ * the fp32 namesakes, with "a null table" meaning d_ent or d_rel; nothing is written when an error is returned. */
+int kge_bf16_eval_supported(const kge_model_desc *m);
+int kge_predict_bf16(const kge_model_desc *m, const uint16_t *d_ent, const uint16_t *d_rel, const int32_t *d_h, const int32_t *d_t,
+                     const int32_t *d_r, INT n, float *d_out, void *stream);
+int kge_rank_candidates_bf16(const kge_model_desc *m, const uint16_t *d_ent, const uint16_t *d_rel, const int32_t *d_h, const int32_t *d_t,
+                             const int32_t *d_r, INT n, const int32_t *d_tail_cand, INT tail_stride, const int32_t *d_head_cand,
+                             INT head_stride, INT n_cand, INT flags, uint64_t seed, int64_t *d_counts, void *stream);
+
 /* Batched top-k entity prediction on the device.  Query i: d_head[i] == 0 asks for the k best tails of (d_fixed[i], d_rel[i], ?),
  * d_head[i] != 0 for the k best heads of (?, d_rel[i], d_fixed[i]); sides and relations may be mixed in any order.  d_ids /
  * d_scores (DEVICE, row-major [n][k]) receive the candidates in ascending (score, id) order -- NaN after every number -- with

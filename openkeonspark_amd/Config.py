@@ -58,7 +58,7 @@ class Config(object):
             self._shared_by_relation = False                  # ... its chunks are cut from the batch ordered by relation
             self._shared_in_chunk = 0                         # ... K of a chunk's candidates are its own positives' entities
             self._table_dtype, self._table_seed = "fp32", 0   # set_table_dtype
-            self._eval_view = None                            # bf16 tables: the float32 view the evaluation paths read (_tab_ptrs)
+            self._eval_view = None                            # bf16 tables: the float32 view the full-entity evaluators read (_tab_ptrs)
             # engine-side additions
             self.seed = 0                 # parameter initialisation seed
             self.device = "cuda"
@@ -203,8 +203,10 @@ class Config(object):
         the bytes in memory and in every gather and touched-row update -- trained on the one-rank int8-record touched-rows step
         with SGD or RowAdagrad; every updated row is stored by stochastic rounding from a hash of (seed, global step, row,
         column), so a run is reproducible bit for bit and a resumed run must repeat the seed.  get_parameters / checkpoints give
-        float32 (an exact widening), set_parameters rounds to nearest-even, and the evaluation paths read a float32 view that
-        lives until the next training step.  Configurations the mode cannot take are refused by set_model_and_session.
+        float32 (an exact widening), set_parameters rounds to nearest-even, and the full-entity evaluators (link_prediction,
+        rank_triples, top-k, relation prediction) read a float32 view that lives until the next training step; test_step, triple
+        classification, rank_candidates, rank_triples_sampled and validation_link_prediction(candidates=C) read the stored bf16
+        rows directly, with the same score bits and counts and no view.  Configurations the mode cannot take are refused by set_model_and_session.
         With set_shared_negatives(chunk, ...), in either call order, the shared step reads the bf16 tables (one rank, widths up to
         512, chunks by position or by relation, typed and in-chunk candidates included): its records are the fp32 shared emit's
         on the widened tables bit for bit (include/kge_mi355.h, "Shared negatives on bf16 tables").  The two seeds must then
@@ -226,8 +228,9 @@ class Config(object):
             raise KgeError("bf16 table storage is single-process only: the row-sharded step and the data-parallel exchanges are "
                            "built for fp32 tables (world size %d)" % self.world_size)
 
-    # The evaluation kernels read fp32 tables.  With bf16 storage every path that passes `_tab_ptrs` gets a float32 view made by
-    # widening (exact), cached until the next training step or set_parameters and freed there: training memory is unaffected.
+    # The full-entity evaluation kernels read fp32 tables.  With bf16 storage every path that passes `_tab_ptrs` gets a float32 view
+    # made by widening (exact), cached until the next training step or set_parameters and freed there: training memory is
+    # unaffected.  The evaluators that only gather rows (_predict, rank_eval.rank_candidates_device) take _bf16_eval_tables instead.
     @property
     def _tab_ptrs(self):
         if self._bf16 and getattr(self, "_tables", None):
@@ -245,13 +248,34 @@ class Config(object):
             try:
                 views = [t.float() for t in self._tables]
             except (torch.cuda.OutOfMemoryError, RuntimeError) as e:
-                raise KgeError("bf16 table storage: evaluation reads a float32 view of the tables and its %d bytes could not be "
-                               "allocated (%s)" % (need, str(e).splitlines()[0] if str(e) else type(e).__name__))
+                raise KgeError("bf16 table storage: the full-entity evaluators read a float32 view of the tables and its %d bytes "
+                               "could not be allocated (%s).  test_step, triple_classification, validation_accuracy, roc_auc, "
+                               "rank_candidates, rank_triples_sampled and validation_link_prediction(candidates=C) read the bf16 "
+                               "tables directly and need no view" % (need, str(e).splitlines()[0] if str(e) else type(e).__name__))
             self._eval_view = (views, _lib.table_ptrs([v.data_ptr() for v in views]))
         return self._eval_view[1]
 
     def _drop_eval_view(self):
         self._eval_view = None
+
+    def _bf16_eval_tables(self):
+        """The stored bf16 tables' addresses (ent, rel) where the evaluators that gather rows read them directly
+        (kge_predict_bf16, kge_rank_candidates_bf16; include/kge_mi355.h, "Evaluation on bf16 tables"), else None.  Asking
+        makes no float32 view."""
+        if not (self._bf16 and getattr(self, "_tables", None)):
+            return None
+        if not self.lib.kge_bf16_eval_supported(ctypes.byref(self._desc)):
+            return None
+        return self._tables[0].data_ptr(), self._tables[1].data_ptr()
+
+    def _predict(self, h_ptr, t_ptr, r_ptr, n, out_ptr):
+        """kge_predict on the tables as they are stored: bf16 tables are scored from their own rows, with the same bits."""
+        raw = self._bf16_eval_tables()
+        if raw is not None:
+            rc = self.lib.kge_predict_bf16(ctypes.byref(self._desc), raw[0], raw[1], h_ptr, t_ptr, r_ptr, n, out_ptr, self._stream())
+        else:
+            rc = self.lib.kge_predict(ctypes.byref(self._desc), self._tab_ptrs, h_ptr, t_ptr, r_ptr, n, out_ptr, self._stream())
+        _lib.check(rc, self.lib)
 
     def _refuse_shared_ranks(self, stepping=False):
         """Shared negatives across ranks train a row-sharded entity table (train_paths.shared_sharded_step) and nothing else:
@@ -1150,8 +1174,7 @@ class Config(object):
             return shard_eval.test_step(self, host)
         dev = torch.from_numpy(host).to(self.device)
         out = torch.empty(host.shape[1], dtype=torch.float32, device=self.device)
-        _lib.check(self.lib.kge_predict(ctypes.byref(self._desc), self._tab_ptrs, dev[0].data_ptr(), dev[1].data_ptr(),
-                                        dev[2].data_ptr(), host.shape[1], out.data_ptr(), self._stream()), self.lib)
+        self._predict(dev[0].data_ptr(), dev[1].data_ptr(), dev[2].data_ptr(), host.shape[1], out.data_ptr())
         self.trainModel.predict = out
         return out.cpu().numpy()
 
@@ -1250,8 +1273,7 @@ class Config(object):
         n = ids.shape[1]
         out = torch.empty((2, n), dtype=torch.float32, device=self.device)
         for side in range(2):
-            _lib.check(self.lib.kge_predict(ctypes.byref(self._desc), self._tab_ptrs, ids[3 * side].data_ptr(), ids[3 * side + 1].data_ptr(),
-                                            ids[3 * side + 2].data_ptr(), n, out[side].data_ptr(), self._stream()), self.lib)
+            self._predict(ids[3 * side].data_ptr(), ids[3 * side + 1].data_ptr(), ids[3 * side + 2].data_ptr(), n, out[side].data_ptr())
         return out
 
     def _tc_result_buffer(self):

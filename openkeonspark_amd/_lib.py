@@ -184,6 +184,10 @@ def _declare(L):
     L.kge_transe_apply_rows_sgd_bf16.argtypes = [ctypes.POINTER(ModelDesc), vp, vp, vp, vp, vp, i64, i64, f32, u64, u64, vp]
     L.kge_transe_apply_rows_rowadagrad_bf16.argtypes = [ctypes.POINTER(ModelDesc), vp, vp, vp, vp, vp, vp, vp, i64, i64, f32, u64, u64, vp]
     L.kge_bf16_round_stochastic.argtypes = [vp, i64, i64, i64, u64, u64, vp, vp]
+    # evaluation on bf16 tables (csrc/bf16_eval.hip, csrc/rank_cand.hip): the fp32 namesakes' arguments, two tables for tables[]
+    L.kge_bf16_eval_supported.argtypes = [ctypes.POINTER(ModelDesc)]
+    L.kge_predict_bf16.argtypes = [ctypes.POINTER(ModelDesc), vp, vp, vp, vp, vp, i64, vp, vp]
+    L.kge_rank_candidates_bf16.argtypes = [ctypes.POINTER(ModelDesc), vp, vp, vp, vp, vp, i64, vp, i64, vp, i64, i64, i64, ctypes.c_uint64, vp, vp]
     # shared negatives (csrc/shared_neg.hip)
     L.kge_shared_negatives_draw.argtypes = [vp, vp, vp, i64, i64, i64, i64, ctypes.c_uint64, i64, vp, vp, vp]
     L.kge_transe_emit_records_shared.argtypes = [ctypes.POINTER(ModelDesc), vp, vp, vp, vp, vp, i64, i64, i64, vp, i64, vp, i64, vp, vp, vp, vp]

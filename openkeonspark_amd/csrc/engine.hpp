@@ -239,6 +239,10 @@ int launch_forward_backward(const kge_model_desc &m, const float *const tables[4
                             const RowRule *inplace_adam = nullptr);
 int launch_predict(const kge_model_desc &m, const float *const tables[4], const int32_t *d_h, const int32_t *d_t,
                    const int32_t *d_r, int64_t n, float *d_out, hipStream_t stream);
+// Evaluation on stored bf16 tables (bf16_eval.hip): null, or the limit the model breaks; kge_predict's bits on the widened tables
+const char *bf16_eval_refusal(const kge_model_desc *m);
+int launch_predict_bf16(const kge_model_desc &m, const uint16_t *d_ent, const uint16_t *d_rel, const int32_t *d_h, const int32_t *d_t,
+                        const int32_t *d_r, int64_t n, float *d_out, hipStream_t stream);
 // TransR kge_predict with each triple's OWN relation matrix, for callers whose triples come in aligned groups of 16 sharing one
 // relation (a group is one 32-row tile of the projection; transr.hip)
 int launch_predict_transr_grouped(const kge_model_desc &m, const float *const tables[4], const int32_t *d_h, const int32_t *d_t,

@@ -7,14 +7,9 @@
 // candidate ids arrive L at a time in one coalesced load (or one hash per lane), are handed out by lane broadcast, and U rows
 // are gathered into registers before the first is consumed.  No T_r, no score block: the cost is n x n_cand x D.
 //
-// The scores are kge_predict's bits.  predict_kernel (models.hip) leaves e = hn + rn - tn to the compiler's contraction
-// licence, and as compiled (all 21 instantiations read in the ISA) it is
-//     e = fma(-xt, inv_t, fma(r_raw, inv_r, hn))        hn = xh * inv_h rounded on its own
-// with xh / xt the projected, un-normalised sides (TransH: fma(-a, w, raw); TransD: fma(a, r_p, raw)), inv_* = 1 / sqrt(max(ss,
-// 1e-12)) from Team::dot, the per-lane sum of |e| in index order, team_sum<L> and lane 0's value; TransE divides by (float)D.
-// It is written out here operation by operation (__builtin_fmaf, mul_rn), so that the bits do not hang on this kernel's
-// optimiser -- here the fixed side is loop-invariant and the compiler would contract differently.  The true triple's score is
-// the same code applied to the target's row.
+// The scores are kge_predict's bits: predict_kernel's compiled form, written out operation by operation in predict_dev.hpp
+// (project_row, predict_score), so that the bits do not hang on this kernel's optimiser -- here the fixed side is loop-invariant
+// and the compiler would contract differently.  The true triple's score is the same code applied to the target's row.
 //
 // Two-stage form (TransR; every model with option rankc_fused = 0; the fused kernel's reference): chunks of at most 2^22
 // (triple, candidate) pairs are spelled out as id arrays in a bounded workspace, scored by launch_predict (TransR: groups of 16
@@ -23,12 +18,17 @@
 //
 // Row-range form (kge_rank_candidates_range; TransE, a table sharded by rows across ranks): the fused kernel's RANGE
 // instantiations rank against the candidates whose rows one shard holds; the comment on the kernel has the rest.
+//
+// Stored bf16 tables (kge_rank_candidates_bf16; TransE, the list form): the fused kernel's BF16 instantiations read `ent` and
+// `rel` as uint16 rows through Team::load's widening overload -- same team shape, same operations after the load, so the counts
+// are those of the fp32 kernel on the widened tables.  Its two-stage form scores the pairs with launch_predict_bf16.
 #include <algorithm>
 #include <type_traits>
 
 #include "eval_dev.hpp"
 #include "mix_dev.hpp"
 #include "models_dev.hpp"
+#include "predict_dev.hpp"
 #include "team.hpp"
 #include "team_shape.hpp"
 
@@ -39,7 +39,8 @@ namespace {
 enum { kList = 0, kDrawn = 1, kDrawnTyped = 2 };
 
 struct RankCandArgs {
-    const float *ent, *rel, *auxr, *auxe;
+    const void *ent, *rel;     // fp32 rows; stored bf16 rows (uint16) for the kernel's BF16 instantiations
+    const float *auxr, *auxe;
     EvalFilterView ev;
     const int32_t *h, *t, *r;
     const int32_t *cand[2];    // per side; null = not ranked (list mode)
@@ -82,48 +83,17 @@ __device__ __forceinline__ int candidate_id(const RankCandArgs &a, long long i, 
     return (id >= 0 && id < a.E) ? id : -1;
 }
 
-// the projected, un-normalised vector of an entity row and 1 / |it|: side_project's operations (models_dev.hpp), with the
-// products it leaves to contraction written as the fma predict_kernel compiles them to
-template <int MODEL, int L, int C>
-__device__ __forceinline__ void project_row(const Team<L, C> &tm, const float (&raw)[C], const float (&aux)[C], const float (&cw)[C],
-                                            float (&xp)[C], float &inv) {
-    if constexpr (MODEL == KGE_TRANSH) {
-        const float a = tm.dot(raw, cw);
-#pragma unroll
-        for (int c = 0; c < C; c++) xp[c] = __builtin_fmaf(-a, cw[c], raw[c]);
-    } else if constexpr (MODEL == KGE_TRANSD) {
-        const float a = tm.dot(raw, aux);
-#pragma unroll
-        for (int c = 0; c < C; c++) xp[c] = __builtin_fmaf(a, cw[c], raw[c]);
-    } else {
-#pragma unroll
-        for (int c = 0; c < C; c++) xp[c] = raw[c];
-    }
-    const float ss = tm.dot(xp, xp);
-    inv = 1.0f / sqrtf(ss >= 1e-12f ? ss : 1e-12f);
-}
-
-// predict_kernel's score of (head, relation, tail) from the head's normalised vector hn, the relation's raw row and 1 / |row|,
-// and the tail's projected vector and 1 / |it|; lane 0's team_sum value in every lane of the team
-template <int MODEL, int L, int C>
-__device__ __forceinline__ float predict_score(const float (&hn)[C], const float (&rr)[C], float inv_r, const float (&xt)[C], float inv_t, int D) {
-    float s = 0.f;
-#pragma unroll
-    for (int c = 0; c < C; c++) s = add_rn(s, fabsf(__builtin_fmaf(-xt[c], inv_t, __builtin_fmaf(rr[c], inv_r, hn[c]))));
-    s = team_sum<L>(s);
-    if constexpr (L != 64) s = __shfl(s, 0, L);
-    if constexpr (MODEL == KGE_TRANSE) s = s / (float)D;
-    return s;
-}
-
+// BF16: `ent` and `rel` are stored bf16 rows (uint16), widened exactly as they are loaded; TransE without RANGE only.
 // RANGE: the candidates with a global id in [row_lo, row_lo + rows) only, gathered at their local row.  Every team still
 // walks the whole list (the ids cost a load or a hash each), but gathers and scores what it owns: the owned ids of a batch are
 // compacted to the low lanes (a ballot masked to the team's own lanes, a prefix count, one ds_permute) behind the `p` ids left
 // pending from the batches before, rounds of U rows are drawn from that queue while it holds U, and the last round is padded.
-template <int MODEL, int L, int C, int U, int MODE, bool RANGE>
+template <int MODEL, int L, int C, int U, int MODE, bool RANGE, bool BF16 = false>
 __global__ __launch_bounds__(256) void rank_cand_kernel(std::conditional_t<RANGE, RankCandRangeArgs, RankCandArgs> a) {
     constexpr int TEAMS = 256 / L;
     static_assert(L % U == 0, "a batch of ids is handed out U at a time");
+    static_assert(!BF16 || (MODEL == KGE_TRANSE && !RANGE), "stored bf16 rows: TransE's list form only");
+    using Tab = std::conditional_t<BF16, uint16_t, float>;      // (a.ent / a.rel are cast where they are read, as the fp32 kernel reads them)
     Team<L, C> tm;
     tm.lane = threadIdx.x % L;
     tm.D = a.D;
@@ -137,7 +107,7 @@ __global__ __launch_bounds__(256) void rank_cand_kernel(std::conditional_t<RANGE
     const int fixed = hd ? t : h, target = hd ? h : t;
     // relation context: the raw relation row and 1 / |row|; TransH's normalised normal vector / TransD's r_p
     float rr[C], cw[C], inv_r;
-    tm.load(a.rel, r, rr);
+    tm.load((const Tab *)a.rel, r, rr);
     {
         const float ss = tm.dot(rr, rr);
         inv_r = 1.0f / sqrtf(ss >= 1e-12f ? ss : 1e-12f);
@@ -160,7 +130,7 @@ __global__ __launch_bounds__(256) void rank_cand_kernel(std::conditional_t<RANGE
     {
         float raw[C], aux[C];
         if constexpr (RANGE) tm.load(a.qrows, 2 * i + (hd ? 1 : 0), raw);
-        else tm.load(a.ent, fixed, raw);
+        else tm.load((const Tab *)a.ent, fixed, raw);
         if constexpr (MODEL == KGE_TRANSD) tm.load(a.auxe, fixed, aux);
         project_row<MODEL, L, C>(tm, raw, aux, cw, fx, inv_f);
         if (!hd) {
@@ -183,7 +153,7 @@ __global__ __launch_bounds__(256) void rank_cand_kernel(std::conditional_t<RANGE
     {
         float raw[C], aux[C];
         if constexpr (RANGE) tm.load(a.qrows, 2 * i + (hd ? 0 : 1), raw);
-        else tm.load(a.ent, target, raw);
+        else tm.load((const Tab *)a.ent, target, raw);
         if constexpr (MODEL == KGE_TRANSD) tm.load(a.auxe, target, aux);
         mn = score(raw, aux);
     }
@@ -204,7 +174,7 @@ __global__ __launch_bounds__(256) void rank_cand_kernel(std::conditional_t<RANGE
         auto round = [&](const int (&id)[U]) {
             float x[U][C];
 #pragma unroll
-            for (int u = 0; u < U; u++) tm.load(a.ent, id[u] >= 0 ? id[u] - r_lo : 0, x[u]);
+            for (int u = 0; u < U; u++) tm.load((const Tab *)a.ent, id[u] >= 0 ? id[u] - r_lo : 0, x[u]);
 #pragma unroll
             for (int u = 0; u < U; u++) {
                 const float s = score(x[u], x[u]);
@@ -264,7 +234,7 @@ __global__ __launch_bounds__(256) void rank_cand_kernel(std::conditional_t<RANGE
                 for (int u = 0; u < U; u++) {
                     id[u] = team_bcast<L>(mine, j + u);
                     const long long row = id[u] >= 0 ? id[u] : 0;   // a skipped id still loads a row: no branch around the gathers
-                    tm.load(a.ent, row, x[u]);
+                    tm.load((const Tab *)a.ent, row, x[u]);
                     if constexpr (MODEL == KGE_TRANSD) tm.load(a.auxe, row, ax[u]);
                 }
 #pragma unroll
@@ -308,7 +278,7 @@ long long rankc_slices(long long nblocks, long long n_cand, int L) {
     return std::max(1LL, std::min({slices, n_cand, 65535LL}));
 }
 
-template <int MODEL>
+template <int MODEL, bool BF16 = false>
 int launch_fused(RankCandArgs a, int mode, hipStream_t stream) {
     const bool shaped = for_team_shape(a.D, [&](auto t) {
         constexpr int L = decltype(t)::L, C = decltype(t)::C, U = rankc_u<MODEL>(C);
@@ -319,9 +289,9 @@ int launch_fused(RankCandArgs a, int mode, hipStream_t stream) {
         slices = (a.n_cand + a.slice_len - 1) / a.slice_len;
         a.atomic = slices > 1;
         const dim3 grid((unsigned)nblocks, (unsigned)slices);   // n < 2^30: at most 2^31 / TEAMS blocks along x
-        if (mode == kList) hipLaunchKernelGGL((rank_cand_kernel<MODEL, L, C, U, kList, false>), grid, dim3(256), 0, stream, a);
-        else if (mode == kDrawn) hipLaunchKernelGGL((rank_cand_kernel<MODEL, L, C, U, kDrawn, false>), grid, dim3(256), 0, stream, a);
-        else hipLaunchKernelGGL((rank_cand_kernel<MODEL, L, C, U, kDrawnTyped, false>), grid, dim3(256), 0, stream, a);
+        if (mode == kList) hipLaunchKernelGGL((rank_cand_kernel<MODEL, L, C, U, kList, false, BF16>), grid, dim3(256), 0, stream, a);
+        else if (mode == kDrawn) hipLaunchKernelGGL((rank_cand_kernel<MODEL, L, C, U, kDrawn, false, BF16>), grid, dim3(256), 0, stream, a);
+        else hipLaunchKernelGGL((rank_cand_kernel<MODEL, L, C, U, kDrawnTyped, false, BF16>), grid, dim3(256), 0, stream, a);
     });
     if (!shaped) return fail(KGE_ERR_UNSUPPORTED, "kge_rank_candidates: embedding dimension > 1024");
     return hip_check(hipGetLastError(), "rank candidates launch");
@@ -417,13 +387,15 @@ DevBuf<float> g_sc, g_tgt;
 
 unsigned blocks_for(long long len) { return (unsigned)std::max(1LL, std::min((len + 255) / 256, 8192LL)); }
 
-int score_pairs(const kge_model_desc &m, const float *const tables[4], const int32_t *ph, const int32_t *pt, const int32_t *pr,
-                long long len, float *out, hipStream_t stream) {
+// bf16: a.ent / a.rel are stored bf16 tables (kge_rank_candidates_bf16) and `tables` is not read
+int score_pairs(const kge_model_desc &m, bool bf16, const float *const tables[4], const RankCandArgs &a, const int32_t *ph, const int32_t *pt,
+                const int32_t *pr, long long len, float *out, hipStream_t stream) {
+    if (bf16) return launch_predict_bf16(m, (const uint16_t *)a.ent, (const uint16_t *)a.rel, ph, pt, pr, len, out, stream);
     if (m.model == KGE_TRANSR) return launch_predict_transr_grouped(m, tables, ph, pt, pr, len, out, stream);
     return launch_predict(m, tables, ph, pt, pr, len, out, stream);
 }
 
-int two_stage(const kge_model_desc &m, const float *const tables[4], const RankCandArgs &a, int mode, hipStream_t stream) {
+int two_stage(const kge_model_desc &m, bool bf16, const float *const tables[4], const RankCandArgs &a, int mode, hipStream_t stream) {
     const bool tr = m.model == KGE_TRANSR;
     const long long G = tr ? 16 : 1;
     const long long Cp = (a.n_cand + G - 1) / G * G;
@@ -442,7 +414,7 @@ int two_stage(const kge_model_desc &m, const float *const tables[4], const RankC
     for (long long g0 = 0; g0 < a.n_req * G; g0 += chunk) {
         sp.g0 = g0; sp.len = std::min(chunk, a.n_req * G - g0);
         hipLaunchKernelGGL(spell_kernel, dim3(blocks_for(sp.len)), dim3(256), 0, stream, sp);
-        if ((rc = score_pairs(m, tables, sp.ph, sp.pt, sp.pr, sp.len, g_tgt + g0, stream))) return rc;
+        if ((rc = score_pairs(m, bf16, tables, a, sp.ph, sp.pt, sp.pr, sp.len, g_tgt + g0, stream))) return rc;
     }
     sp.targets = 0; sp.Cp = Cp;
     CountArgs ca = {};
@@ -451,49 +423,48 @@ int two_stage(const kge_model_desc &m, const float *const tables[4], const RankC
     for (long long g0 = 0; g0 < total; g0 += chunk) {
         sp.g0 = ca.g0 = g0; sp.len = ca.len = std::min(chunk, total - g0);
         hipLaunchKernelGGL(spell_kernel, dim3(blocks_for(sp.len)), dim3(256), 0, stream, sp);
-        if ((rc = score_pairs(m, tables, sp.ph, sp.pt, sp.pr, sp.len, g_sc, stream))) return rc;
+        if ((rc = score_pairs(m, bf16, tables, a, sp.ph, sp.pt, sp.pr, sp.len, g_sc, stream))) return rc;
         hipLaunchKernelGGL(count_kernel, dim3(blocks_for(ca.len)), dim3(256), 0, stream, ca);
     }
     return hip_check(hipGetLastError(), "rank candidates two-stage launch");
 }
 
-}  // namespace
-
-}  // namespace kge
-
-using namespace kge;
-
-extern "C" int kge_rank_candidates(const kge_model_desc *m, const float *const tables[KGE_MAX_TABLES], const int32_t *d_h, const int32_t *d_t,
-                                   const int32_t *d_r, INT n, const int32_t *d_tail_cand, INT tail_stride, const int32_t *d_head_cand,
-                                   INT head_stride, INT n_cand, INT flags, uint64_t seed, int64_t *d_counts, void *stream_) {
-    hipStream_t stream = (hipStream_t)stream_;
-    if (!m || !tables || !d_h || !d_t || !d_r || !d_counts) return fail(KGE_ERR_BAD_ARG, "kge_rank_candidates: null model, tables, triple or output array");
-    if (n < 0 || n >= (INT(1) << 30)) return fail(KGE_ERR_BAD_ARG, "kge_rank_candidates: triple count outside [0, 2^30)");
-    if (n_cand < 0 || n_cand >= (INT(1) << 31)) return fail(KGE_ERR_BAD_ARG, "kge_rank_candidates: candidate count outside [0, 2^31)");
-    if (flags & ~(INT)(KGE_RANKC_FILTERED | KGE_RANKC_DRAWN | KGE_RANKC_TYPED | KGE_RANKC_NO_HEAD)) return fail(KGE_ERR_BAD_ARG, "kge_rank_candidates: unknown flags");
+// kge_rank_candidates (`tables`) and kge_rank_candidates_bf16 (`bf16`: tables == nullptr, d_ent / d_rel are stored bf16 rows): one
+// argument path, one order of checks
+int rank_candidates_call(const std::string &who, bool bf16, const kge_model_desc *m, const float *const tables[KGE_MAX_TABLES],
+                         const uint16_t *d_ent, const uint16_t *d_rel, const int32_t *d_h, const int32_t *d_t, const int32_t *d_r, INT n,
+                         const int32_t *d_tail_cand, INT tail_stride, const int32_t *d_head_cand, INT head_stride, INT n_cand, INT flags,
+                         uint64_t seed, int64_t *d_counts, hipStream_t stream) {
+    if (!m || (bf16 ? !d_ent || !d_rel : !tables) || !d_h || !d_t || !d_r || !d_counts) return fail(KGE_ERR_BAD_ARG, who + ": null model, tables, triple or output array");
+    if (n < 0 || n >= (INT(1) << 30)) return fail(KGE_ERR_BAD_ARG, who + ": triple count outside [0, 2^30)");
+    if (n_cand < 0 || n_cand >= (INT(1) << 31)) return fail(KGE_ERR_BAD_ARG, who + ": candidate count outside [0, 2^31)");
+    if (flags & ~(INT)(KGE_RANKC_FILTERED | KGE_RANKC_DRAWN | KGE_RANKC_TYPED | KGE_RANKC_NO_HEAD)) return fail(KGE_ERR_BAD_ARG, who + ": unknown flags");
     const bool drawn = flags & KGE_RANKC_DRAWN, typed = flags & KGE_RANKC_TYPED, no_head = flags & KGE_RANKC_NO_HEAD, filtered = flags & KGE_RANKC_FILTERED;
-    if (drawn && (d_tail_cand || d_head_cand)) return fail(KGE_ERR_BAD_ARG, "kge_rank_candidates: a candidate list together with KGE_RANKC_DRAWN");
-    if (!drawn && (typed || no_head)) return fail(KGE_ERR_BAD_ARG, "kge_rank_candidates: KGE_RANKC_TYPED / KGE_RANKC_NO_HEAD without KGE_RANKC_DRAWN");
-    if (!drawn && !d_tail_cand && !d_head_cand) return fail(KGE_ERR_BAD_ARG, "kge_rank_candidates: no candidate list and no KGE_RANKC_DRAWN");
+    if (drawn && (d_tail_cand || d_head_cand)) return fail(KGE_ERR_BAD_ARG, who + ": a candidate list together with KGE_RANKC_DRAWN");
+    if (!drawn && (typed || no_head)) return fail(KGE_ERR_BAD_ARG, who + ": KGE_RANKC_TYPED / KGE_RANKC_NO_HEAD without KGE_RANKC_DRAWN");
+    if (!drawn && !d_tail_cand && !d_head_cand) return fail(KGE_ERR_BAD_ARG, who + ": no candidate list and no KGE_RANKC_DRAWN");
     if ((d_tail_cand && tail_stride != 0 && tail_stride < n_cand) || (d_head_cand && head_stride != 0 && head_stride < n_cand))
-        return fail(KGE_ERR_BAD_ARG, "kge_rank_candidates: a list stride must be 0 (shared list) or at least n_cand");
+        return fail(KGE_ERR_BAD_ARG, who + ": a list stride must be 0 (shared list) or at least n_cand");
     bool known_model = for_model(m->model, [](auto) {});
     if (!known_model) return fail(KGE_ERR_BAD_ARG, "unknown model id");
     const int64_t E = m->ent_total;
     const int D = m->model == KGE_TRANSR ? (int)m->rel_dim : (int)m->ent_dim;
-    if (D < 1 || m->ent_dim < 1 || E < 1 || E >= (INT(1) << 31) || m->rel_total < 1) return fail(KGE_ERR_BAD_ARG, "kge_rank_candidates: empty model");
-    if (D > 1024) return fail(KGE_ERR_UNSUPPORTED, "kge_rank_candidates: embedding dimension > 1024");
-    if (!device_ok()) return fail(KGE_ERR_NO_DEVICE, "kge_rank_candidates: no usable HIP device");
+    if (D < 1 || m->ent_dim < 1 || E < 1 || E >= (INT(1) << 31) || m->rel_total < 1) return fail(KGE_ERR_BAD_ARG, who + ": empty model");
+    if (D > 1024) return fail(KGE_ERR_UNSUPPORTED, who + ": embedding dimension > 1024");
+    if (bf16)
+        if (const char *why = bf16_eval_refusal(m)) return fail(KGE_ERR_UNSUPPORTED, who + ": " + why);
+    if (!device_ok()) return fail(KGE_ERR_NO_DEVICE, who + ": no usable HIP device");
     RankCandArgs a = {};
     int rc;
     if ((filtered || typed) && (rc = eval_filter_view(typed, a.ev))) return rc;
     const int n_tables = m->model == KGE_TRANSE ? 2 : (m->model == KGE_TRANSD ? 4 : 3);
-    for (int k = 0; k < n_tables; k++)
-        if (!tables[k]) return fail(KGE_ERR_BAD_ARG, "kge_rank_candidates: null table");
+    for (int k = 0; k < n_tables && !bf16; k++)
+        if (!tables[k]) return fail(KGE_ERR_BAD_ARG, who + ": null table");
     if (n == 0) return KGE_OK;
     if ((rc = hip_check(hipMemsetAsync(d_counts, 0, sizeof(int64_t) * 4 * (size_t)n, stream), "zero rank candidate counts"))) return rc;
     if (n_cand == 0) return KGE_OK;
-    a.ent = tables[0]; a.rel = tables[1]; a.auxr = tables[2]; a.auxe = tables[3];
+    if (bf16) { a.ent = d_ent; a.rel = d_rel; }
+    else { a.ent = tables[0]; a.rel = tables[1]; a.auxr = tables[2]; a.auxe = tables[3]; }
     a.h = d_h; a.t = d_t; a.r = d_r;
     a.cand[0] = d_tail_cand; a.cand[1] = d_head_cand; a.stride[0] = tail_stride; a.stride[1] = head_stride;
     const bool tail_side = drawn || d_tail_cand, head_side = drawn ? !no_head : d_head_cand != nullptr;
@@ -505,13 +476,35 @@ extern "C" int kge_rank_candidates(const kge_model_desc *m, const float *const t
     const int mode = !drawn ? kList : (typed ? kDrawnTyped : kDrawn);
     if (m->model == KGE_TRANSR || !engine().rankc_fused) {
         a.atomic = 1;
-        return two_stage(*m, tables, a, mode, stream);
+        return two_stage(*m, bf16, tables, a, mode, stream);
     }
+    if (bf16) return launch_fused<KGE_TRANSE, true>(a, mode, stream);
     switch (m->model) {
         case KGE_TRANSE: return launch_fused<KGE_TRANSE>(a, mode, stream);
         case KGE_TRANSH: return launch_fused<KGE_TRANSH>(a, mode, stream);
         default: return launch_fused<KGE_TRANSD>(a, mode, stream);
     }
+}
+
+}  // namespace
+
+}  // namespace kge
+
+using namespace kge;
+
+extern "C" int kge_rank_candidates(const kge_model_desc *m, const float *const tables[KGE_MAX_TABLES], const int32_t *d_h, const int32_t *d_t,
+                                   const int32_t *d_r, INT n, const int32_t *d_tail_cand, INT tail_stride, const int32_t *d_head_cand,
+                                   INT head_stride, INT n_cand, INT flags, uint64_t seed, int64_t *d_counts, void *stream) {
+    return rank_candidates_call("kge_rank_candidates", false, m, tables, nullptr, nullptr, d_h, d_t, d_r, n, d_tail_cand, tail_stride, d_head_cand,
+                                head_stride, n_cand, flags, seed, d_counts, (hipStream_t)stream);
+}
+
+extern "C" int kge_rank_candidates_bf16(const kge_model_desc *m, const uint16_t *d_ent, const uint16_t *d_rel, const int32_t *d_h,
+                                        const int32_t *d_t, const int32_t *d_r, INT n, const int32_t *d_tail_cand, INT tail_stride,
+                                        const int32_t *d_head_cand, INT head_stride, INT n_cand, INT flags, uint64_t seed, int64_t *d_counts,
+                                        void *stream) {
+    return rank_candidates_call("kge_rank_candidates_bf16", true, m, nullptr, d_ent, d_rel, d_h, d_t, d_r, n, d_tail_cand, tail_stride, d_head_cand,
+                                head_stride, n_cand, flags, seed, d_counts, (hipStream_t)stream);
 }
 
 extern "C" int kge_rank_candidates_range(const kge_model_desc *m, const float *const tables[KGE_MAX_TABLES], INT row_lo, INT rows,

@@ -5,6 +5,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "bf16_dev.hpp"
+
 namespace kge {
 
 // ------------------------------------------------------------------------------------------------
@@ -111,6 +113,13 @@ struct Team {
         const float *p = tab + row * D;
 #pragma unroll
         for (int c = 0; c < C; c++) { int e = lane + L * c; x[c] = e < D ? p[e] : 0.f; }
+    }
+    // a row of STORED bf16 (bf16_dev.hpp) in the same layout: one 2-byte load per element, widened exactly, so everything after
+    // the load has the bits it has on the widened fp32 table
+    __device__ __forceinline__ void load(const uint16_t *__restrict__ tab, long long row, float (&x)[C]) const {
+        const uint16_t *p = tab + row * D;
+#pragma unroll
+        for (int c = 0; c < C; c++) { int e = lane + L * c; x[c] = e < D ? bf16_widen(p[e]) : 0.f; }
     }
     __device__ __forceinline__ void add(float *__restrict__ tab, long long row, const float (&v)[C]) const {
         float *p = tab + row * D;

@@ -195,9 +195,11 @@ def rank_candidates_device(con, dev, tail, head, n_cand, flags, seed, first=0, i
     ptr = lambda x: x.data_ptr() if x.numel() else spare.data_ptr()
     ids = dev if n else spare
     lists = [(None, 0) if side is None else (ptr(side[0]), side[1]) for side in (tail, head)]
-    _lib.check(con.lib.kge_rank_candidates(ctypes.byref(con._desc), con._tab_ptrs, ids[0].data_ptr(), ids[1].data_ptr(), ids[2].data_ptr(),
-                                           n, lists[0][0], lists[0][1], lists[1][0], lists[1][1], n_cand, flags, _lib.drawn_seed_at(seed, first),
-                                           counts.data_ptr() if n else spare.data_ptr(), con._stream()), con.lib)
+    raw = con._bf16_eval_tables()      # stored bf16 tables are ranked from their own rows: no float32 view, the same counts
+    fn, tabs = (con.lib.kge_rank_candidates, (con._tab_ptrs,)) if raw is None else (con.lib.kge_rank_candidates_bf16, raw)
+    _lib.check(fn(ctypes.byref(con._desc), *tabs, ids[0].data_ptr(), ids[1].data_ptr(), ids[2].data_ptr(),
+                  n, lists[0][0], lists[0][1], lists[1][0], lists[1][1], n_cand, flags, _lib.drawn_seed_at(seed, first),
+                  counts.data_ptr() if n else spare.data_ptr(), con._stream()), con.lib)
     return counts.cpu().numpy() if into is None else None
 
 
