@@ -1248,6 +1248,31 @@ int kge_predict_bf16(const kge_model_desc *m, const uint16_t *d_ent, const uint1
 int kge_rank_candidates_bf16(const kge_model_desc *m, const uint16_t *d_ent, const uint16_t *d_rel, const int32_t *d_h, const int32_t *d_t,
                              const int32_t *d_r, INT n, const int32_t *d_tail_cand, INT tail_stride, const int32_t *d_head_cand,
                              INT head_stride, INT n_cand, INT flags, uint64_t seed, int64_t *d_counts, void *stream);
+/* The FULL-ENTITY evaluators on stored bf16 tables (csrc/rank.hip and csrc/topk.hip, their kernels under BF16): every entity is a
+ * candidate, and the candidate rows are streamed from the stored table once per request block -- no float32 view of a table and no
+ * [E, D] candidate table is made.  Same descriptors as above (kge_bf16_eval_supported), refused the same way, before the device
+ * check.
+ *     kge_rank_triples_bf16    returns all [n][2][4] counts kge_rank_triples returns on the widened tables, for every "rank_slices".
+ *                              kge_rank_triples scores rows of a table of NORMALISED rows; here each candidate, fixed and target
+ *                              row is normalised as it is read, by the same function (each lane's own 1 / |x|, a rounded product),
+ *                              which costs one more team reduction per row.  Allocates its request and block arrays only.
+ *     kge_topk_entities_bf16   returns every id and every score bit kge_topk_entities returns on the widened tables (padding and NaN
+ *                              order included), for both settings of "topk_table_max_bytes" (the budget is compared with
+ *                              E * D * 4, as there).  d_rel_tab is the relation TABLE, d_rel the queries' relation ids.  Allocates
+ *                              the [E] float32 inverse norms (within the budget) and the partial key lists, nothing of E * D.
+ * Arguments, n == 0, and every other error are those of the fp32 namesakes, with "a null table" meaning d_ent or the relation
+ * table; nothing is written when an error is returned. */
+int kge_rank_triples_bf16(const kge_model_desc *m, const uint16_t *d_ent, const uint16_t *d_rel, const int32_t *d_h, const int32_t *d_t,
+                          const int32_t *d_r, INT n, INT test_head, int64_t *d_counts, void *stream);
+int kge_topk_entities_bf16(const kge_model_desc *m, const uint16_t *d_ent, const uint16_t *d_rel_tab, const int32_t *d_fixed,
+                           const int32_t *d_rel, const int32_t *d_head, INT n, INT k, INT flags, int32_t *d_ids, float *d_scores,
+                           void *stream);
+
+/* The engine's own device memory.  Its workspaces are allocated with hipMalloc (csrc/dev_buf.hpp), which a caller's allocator
+ * statistics (torch's, for one) do not see.  *live: bytes held now by all of them; *peak: the largest *live since the last reset
+ * (or since the process began).  reset_peak != 0 sets the peak to the current live bytes after reporting it.  Either pointer may
+ * be null.  Host only: no device needed, and 0 / 0 in a process that has allocated nothing.  Always KGE_OK. */
+int kge_workspace_bytes(int64_t *live, int64_t *peak, int reset_peak);
 
 /* Batched top-k entity prediction on the device.  Query i: d_head[i] == 0 asks for the k best tails of (d_fixed[i], d_rel[i], ?),
  * d_head[i] != 0 for the k best heads of (?, d_rel[i], d_fixed[i]); sides and relations may be mixed in any order.  d_ids /

@@ -13,6 +13,7 @@ GPU the device calls raise.
 import ctypes
 import json
 import os
+import sys
 
 import numpy as np
 
@@ -59,6 +60,7 @@ class Config(object):
             self._shared_in_chunk = 0                         # ... K of a chunk's candidates are its own positives' entities
             self._table_dtype, self._table_seed = "fp32", 0   # set_table_dtype
             self._eval_view = None                            # bf16 tables: the float32 view the full-entity evaluators read (_tab_ptrs)
+            self._bf16_evaluation = "view"                    # set_bf16_evaluation
             # engine-side additions
             self.seed = 0                 # parameter initialisation seed
             self.device = "cuda"
@@ -203,10 +205,13 @@ class Config(object):
         the bytes in memory and in every gather and touched-row update -- trained on the one-rank int8-record touched-rows step
         with SGD or RowAdagrad; every updated row is stored by stochastic rounding from a hash of (seed, global step, row,
         column), so a run is reproducible bit for bit and a resumed run must repeat the seed.  get_parameters / checkpoints give
-        float32 (an exact widening), set_parameters rounds to nearest-even, and the full-entity evaluators (link_prediction,
-        rank_triples, top-k, relation prediction) read a float32 view that lives until the next training step; test_step, triple
-        classification, rank_candidates, rank_triples_sampled and validation_link_prediction(candidates=C) read the stored bf16
-        rows directly, with the same score bits and counts and no view.  Configurations the mode cannot take are refused by set_model_and_session.
+        float32 (an exact widening), set_parameters rounds to nearest-even.  test_step, triple classification, rank_candidates,
+        rank_triples_sampled and validation_link_prediction(candidates=C) read the stored bf16 rows directly, with the same score
+        bits and counts and no view.  The full-entity evaluators read a float32 view that lives until the next training step;
+        rank_triples, validation_link_prediction(), top_k_tails and top_k_heads can instead stream the stored rows, with the same
+        counts, ids and score bits and no memory of the table's size (set_bf16_evaluation("stored")), and do so by themselves when
+        the view cannot be allocated.  link_prediction, relation_prediction and top_k_relations have no stored form and need
+        the view.  Configurations the mode cannot take are refused by set_model_and_session.
         With set_shared_negatives(chunk, ...), in either call order, the shared step reads the bf16 tables (one rank, widths up to
         512, chunks by position or by relation, typed and in-chunk candidates included): its records are the fp32 shared emit's
         on the widened tables bit for bit (include/kge_mi355.h, "Shared negatives on bf16 tables").  The two seeds must then
@@ -217,6 +222,18 @@ class Config(object):
         if not 0 <= seed < (1 << 64):
             raise KgeError("set_table_dtype: the rounding seed is an unsigned 64-bit value, got %r" % (seed,))
         self._table_dtype, self._table_seed = dtype, seed
+
+    def set_bf16_evaluation(self, mode):
+        """What rank_triples, validation_link_prediction() without candidates (the driver's early stop on hits10 / mrr included),
+        top_k_tails and top_k_heads read on bf16 tables (set_table_dtype); no effect on fp32 tables, and it may be called at any
+        time.  "view" (the default): the float32 view of the tables, made once and cached until the next training step -- twice
+        the tables' bytes again, and kge_rank_triples builds an [E, D] float32 candidate table beside it; the faster choice where
+        it fits.  When the view cannot be allocated these methods read the stored rows instead and say so on stderr.  "stored":
+        kge_rank_triples_bf16 / kge_topk_entities_bf16 (include/kge_mi355.h, "Evaluation on bf16 tables") stream the stored bf16
+        rows: the same counts, ids and score bits, nothing allocated that grows with E * D, and no view is made or dropped."""
+        if mode not in ("view", "stored"):
+            raise KgeError("set_bf16_evaluation: mode must be \"view\" or \"stored\", got %r" % (mode,))
+        self._bf16_evaluation = mode
 
     @property
     def _bf16(self):
@@ -248,12 +265,32 @@ class Config(object):
             try:
                 views = [t.float() for t in self._tables]
             except (torch.cuda.OutOfMemoryError, RuntimeError) as e:
-                raise KgeError("bf16 table storage: the full-entity evaluators read a float32 view of the tables and its %d bytes "
-                               "could not be allocated (%s).  test_step, triple_classification, validation_accuracy, roc_auc, "
-                               "rank_candidates, rank_triples_sampled and validation_link_prediction(candidates=C) read the bf16 "
-                               "tables directly and need no view" % (need, str(e).splitlines()[0] if str(e) else type(e).__name__))
+                raise self._eval_view_error(need, str(e).splitlines()[0] if str(e) else type(e).__name__)
             self._eval_view = (views, _lib.table_ptrs([v.data_ptr() for v in views]))
         return self._eval_view[1]
+
+    @staticmethod
+    def _eval_view_error(need, why):
+        return KgeError("bf16 table storage: link_prediction, relation_prediction and top_k_relations read a float32 view of the "
+                        "tables and its %d bytes could not be allocated (%s).  rank_triples, validation_link_prediction(), "
+                        "top_k_tails and top_k_heads rank and select over every entity from the stored bf16 rows and need no view; "
+                        "so do test_step, triple_classification, validation_accuracy, roc_auc, rank_candidates, "
+                        "rank_triples_sampled and validation_link_prediction(candidates=C)" % (need, why))
+
+    def _bf16_full_eval_tables(self, what):
+        """The stored bf16 tables' addresses (ent, rel) when the full-entity evaluator `what` (rank_eval.rank_device,
+        rank_eval.top_k_entities) is to stream the stored rows (kge_rank_triples_bf16 / kge_topk_entities_bf16), else None: fp32
+        tables, or "view" mode with a view that exists or can be made.  "stored" mode makes no view and drops none."""
+        raw = self._bf16_eval_tables()
+        if raw is None or self._bf16_evaluation == "stored":
+            return raw
+        try:
+            self._eval_table_ptrs()
+        except KgeError:
+            print("%s: the float32 view of the bf16 tables could not be allocated; reading the stored bf16 rows instead "
+                  "(the same results)" % what, file=sys.stderr)
+            return raw
+        return None
 
     def _drop_eval_view(self):
         self._eval_view = None
@@ -1567,7 +1604,8 @@ class Config(object):
         arrays, broadcast against each other.  Returns (ids int64 [n, k], scores float32 [n, k]) in ascending (score, id)
         order, padded with -1 / +inf where fewer than k candidates are eligible; numpy in gives numpy out, device tensors in
         give device tensors out.  filtered drops known triples (train + valid + test), type_constrained keeps the relation's
-        tail type list -- both need init_link_prediction().
+        tail type list -- both need init_link_prediction().  bf16 tables: set_bf16_evaluation chooses between a float32 view and
+        the stored rows (kge_topk_entities_bf16), with the same ids and score bits.
         On an entity table sharded across ranks it is a collective: every rank calls it the same number of times, each with
         its own queries (possibly none) and the same k, side and flags, and gets the results of its own queries, with the bits
         of one process over the whole table (kge_topk_entities_range, kge_topk_merge_keys).  Arguments invalid on any rank,
@@ -1617,7 +1655,8 @@ class Config(object):
         (zeros with test_head=False); the columns are the numbers of candidates other than the target that score strictly below
         the true triple -- raw, filtered (train + valid + test), typed, filtered + typed -- exactly columns 0..3 of
         link_prediction's rows, from the same score bits.  metrics has link_prediction's names, normalised by n.  Needs
-        init_link_prediction().  An id out of range raises KgeError before anything is launched."""
+        init_link_prediction().  An id out of range raises KgeError before anything is launched.  bf16 tables:
+        set_bf16_evaluation chooses between a float32 view and the stored rows (kge_rank_triples_bf16), with the same counts."""
         return rank_eval.rank_triples(self, h, t, r, test_head)
 
     def rank_triples_distributed(self, h, t, r, test_head=True):

@@ -188,6 +188,10 @@ def _declare(L):
     L.kge_bf16_eval_supported.argtypes = [ctypes.POINTER(ModelDesc)]
     L.kge_predict_bf16.argtypes = [ctypes.POINTER(ModelDesc), vp, vp, vp, vp, vp, i64, vp, vp]
     L.kge_rank_candidates_bf16.argtypes = [ctypes.POINTER(ModelDesc), vp, vp, vp, vp, vp, i64, vp, i64, vp, i64, i64, i64, ctypes.c_uint64, vp, vp]
+    L.kge_rank_triples_bf16.argtypes = [ctypes.POINTER(ModelDesc), vp, vp, vp, vp, vp, i64, i64, vp, vp]
+    L.kge_topk_entities_bf16.argtypes = [ctypes.POINTER(ModelDesc), vp, vp, vp, vp, vp, i64, i64, i64, vp, vp, vp]
+    # the engine's own device memory (csrc/dev_buf.hpp): live bytes, peak, reset
+    L.kge_workspace_bytes.argtypes = [ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64), ctypes.c_int]
     # shared negatives (csrc/shared_neg.hip)
     L.kge_shared_negatives_draw.argtypes = [vp, vp, vp, i64, i64, i64, i64, ctypes.c_uint64, i64, vp, vp, vp]
     L.kge_transe_emit_records_shared.argtypes = [ctypes.POINTER(ModelDesc), vp, vp, vp, vp, vp, i64, i64, i64, vp, i64, vp, i64, vp, vp, vp, vp]

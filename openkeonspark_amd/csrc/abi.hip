@@ -239,6 +239,12 @@ size_t kge_last_error(char *buf, size_t n) {
 }
 
 void kge_clear_error(void) { engine().last_error.clear(); }
+int kge_workspace_bytes(int64_t *live, int64_t *peak, int reset_peak) {
+    if (live) *live = g_dev_buf_bytes.live;
+    if (peak) *peak = g_dev_buf_bytes.peak;
+    if (reset_peak) g_dev_buf_bytes.peak = g_dev_buf_bytes.live;
+    return KGE_OK;
+}
 int kge_device_available(void) { return device_ok() ? 1 : 0; }
 const char *kge_version(void) { return "kge_mi355 0.1 (gfx950)"; }
 

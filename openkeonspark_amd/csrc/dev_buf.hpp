@@ -13,6 +13,18 @@ namespace kge {
 
 int hip_check(hipError_t e, const char *what);   // 0, or an error code after recording `what`
 
+// Bytes held by every DevBuf / ScopedDevBuf of the process (kge_workspace_bytes): hipMalloc is invisible to a caller's own
+// allocator statistics, so the engine counts what it owns.  `peak` is the largest `live` since the last reset.  Inline variables:
+// one total per process, header only.  The engine is driven from one host thread at a time, as its workspaces are.
+struct DevBufBytes {
+    int64_t live = 0, peak = 0;
+    void add(int64_t bytes) {
+        live += bytes;
+        if (live > peak) peak = live;
+    }
+};
+inline DevBufBytes g_dev_buf_bytes;
+
 template <typename T>
 class DevBuf {
 public:
@@ -49,20 +61,20 @@ public:
     void free() {
         if (p_) (void)hipFree(p_);
         p_ = nullptr;
-        cap_ = 0;
+        set_cap(0);
     }
     // hands the allocation to the caller
     T *release() {
         T *p = p_;
         p_ = nullptr;
-        cap_ = 0;
+        set_cap(0);
         return p;
     }
     // takes over an allocation of n elements (the other half of release()); what was held is freed
     void adopt(T *p, int64_t n) {
         free();
         p_ = p;
-        cap_ = p ? n : 0;
+        set_cap(p ? n : 0);
     }
 
 private:
@@ -70,8 +82,13 @@ private:
         free();
         int rc = hip_check(hipMalloc(&p_, sizeof(T) * (size_t)n), what);
         if (rc) p_ = nullptr;
-        else cap_ = n;
+        else set_cap(n);
         return rc;
+    }
+    // the one place the capacity changes: the process total follows it
+    void set_cap(int64_t n) {
+        g_dev_buf_bytes.add((int64_t)sizeof(T) * (n - cap_));
+        cap_ = n;
     }
     T *p_ = nullptr;
     int64_t cap_ = 0;

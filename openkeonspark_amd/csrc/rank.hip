@@ -27,6 +27,10 @@
 // strictly below the true triple searches the filter (pair_range once per request, in_range per hit) and the relation's type
 // list.  Counts reduce in LDS; one 64-bit atomicAdd per (request, column) and workgroup into the zeroed d_counts.  Integer sums:
 // the result does not depend on the schedule nor on the number of slices.
+//
+// Stored bf16 tables (kge_rank_triples_bf16; TransE): the kernel's BF16 instantiations read the entity table itself in place of T
+// and normalise every row they load (load_cand_row), so no [E, D] table is built and the counts are those of the fp32 kernel
+// on the widened tables.
 #include <algorithm>
 #include <cstring>
 #include <vector>
@@ -40,8 +44,9 @@ namespace kge {
 namespace {
 
 struct RankTriplesArgs {
-    const float *rel;          // rel_embeddings
+    const float *rel;          // rel_embeddings (BF16 instantiations: stored bf16 rows, cast where they are read)
     const float *T;            // T_r [E][D]: every entity's projected + normalised vector under the blocks' relation
+                               // (BF16 instantiations: the stored bf16 entity table itself, normalised row by row as it is read)
     EvalFilterView ev;
     const int4 *req;           // (fixed entity, target entity, 2 * triple + side, 0), grouped by (relation, side)
     const int4 *blk;           // per request block: (first request, requests, relation, side)
@@ -75,8 +80,27 @@ __device__ __forceinline__ float l1_against(const float (&v)[C], const float (&y
     return team_sum<L>(l1_lane<C>(v, y));
 }
 
-template <bool MEAN, int L, int C, int NR, int U>
+// Row `row` of the candidate table.  BF16 (kge_rank_triples_bf16, TransE): there is no T; the stored bf16 row is loaded in the same
+// lane layout, widened exactly, and normalised here as lp_table_kernel normalises it into T -- Team::normalize's inv (each
+// lane its own: team_sum<16> / <32> leave lane-dependent bits) and the ROUNDED product x * inv, which is what a stored T holds;
+// left to the optimiser, v - x * inv would come out as one fma.
+template <bool BF16, int L, int C>
+__device__ __forceinline__ void load_cand_row(const Team<L, C> &tm, const float *T, long long row, float (&x)[C]) {
+    if constexpr (BF16) {
+        float raw[C], y[C], inv;
+        bool uc;
+        tm.load((const uint16_t *)T, row, raw);
+        tm.normalize(raw, y, inv, uc);
+#pragma unroll
+        for (int c = 0; c < C; c++) x[c] = mul_rn(raw[c], inv);
+    } else {
+        tm.load(T, row, x);
+    }
+}
+
+template <bool MEAN, int L, int C, int NR, int U, bool BF16 = false>
 __global__ __launch_bounds__(256) void rank_triples_kernel(RankTriplesArgs a) {
+    static_assert(!BF16 || MEAN, "stored bf16 rows: TransE only");
     constexpr int TEAMS = 256 / L;
     __shared__ int s_cnt[NR][4];
     // per request, read on the slow path only: known range (and its first / last id), type range (and its first / last id)
@@ -113,7 +137,8 @@ __global__ __launch_bounds__(256) void rank_triples_kernel(RankTriplesArgs a) {
     float rr[C], rn[C], rinv;
     {
         float nrm[C]; bool uc;
-        tm.load(a.rel, r, rr);
+        if constexpr (BF16) tm.load((const uint16_t *)a.rel, r, rr);
+        else tm.load(a.rel, r, rr);
         tm.normalize(rr, nrm, rinv, uc);
 #pragma unroll
         for (int c = 0; c < C; c++) rn[c] = mul_rn(rr[c], rinv);
@@ -128,8 +153,8 @@ __global__ __launch_bounds__(256) void rank_triples_kernel(RankTriplesArgs a) {
         if (q < nb) {
             const int4 rq = a.req[q0 + q];
             float f[C], y[C];
-            tm.load(a.T, rq.x, f);
-            tm.load(a.T, rq.y, y);
+            if constexpr (BF16) { load_cand_row<true>(tm, a.T, rq.x, f); load_cand_row<true>(tm, a.T, rq.y, y); }
+            else { tm.load(a.T, rq.x, f); tm.load(a.T, rq.y, y); }
 #pragma unroll
             for (int c = 0; c < C; c++) {
                 V[q][c] = hd ? f[c] : __builtin_fmaf(rr[c], rinv, f[c]);
@@ -151,8 +176,10 @@ __global__ __launch_bounds__(256) void rank_triples_kernel(RankTriplesArgs a) {
 #pragma unroll
         for (int u = 0; u < U; u++) {
             const long long j = base + (long long)team * U + u;
-            if (j < j1) tm.load(a.T, j, x[u]);
-            else {
+            if (j < j1) {
+                if constexpr (BF16) load_cand_row<true>(tm, a.T, j, x[u]);
+                else tm.load(a.T, j, x[u]);
+            } else {
 #pragma unroll
                 for (int c = 0; c < C; c++) x[u][c] = 0.f;
             }
@@ -231,6 +258,7 @@ int requests_per_block(int D) {
 }
 
 // about 2 048 workgroups (eight per CU) over the (request block x slice) grid, slices of at least 1 024 rows
+template <bool BF16 = false>
 int launch_rank(bool mean, RankTriplesArgs a, long long nblocks, hipStream_t stream) {
     long long slices = engine().rank_slices;
     if (slices <= 0) {
@@ -248,7 +276,8 @@ int launch_rank(bool mean, RankTriplesArgs a, long long nblocks, hipStream_t str
         for (long long b0 = 0; b0 < nblocks; b0 += kMaxBlocks) {
             a.blk = blk + b0;
             const dim3 grid((unsigned)std::min(kMaxBlocks, nblocks - b0), (unsigned)slices);
-            if (mean) hipLaunchKernelGGL((rank_triples_kernel<true, L, C, rank_nr(L, C), rank_u(C)>), grid, dim3(256), 0, stream, a);
+            if constexpr (BF16) hipLaunchKernelGGL((rank_triples_kernel<true, L, C, rank_nr(L, C), rank_u(C), true>), grid, dim3(256), 0, stream, a);
+            else if (mean) hipLaunchKernelGGL((rank_triples_kernel<true, L, C, rank_nr(L, C), rank_u(C)>), grid, dim3(256), 0, stream, a);
             else hipLaunchKernelGGL((rank_triples_kernel<false, L, C, rank_nr(L, C), rank_u(C)>), grid, dim3(256), 0, stream, a);
         }
     });
@@ -268,24 +297,30 @@ hipEvent_t g_req_done = nullptr;
 
 using namespace kge;
 
-extern "C" int kge_rank_triples(const kge_model_desc *m, const float *const tables[KGE_MAX_TABLES], const int32_t *d_h, const int32_t *d_t,
-                                const int32_t *d_r, INT n, INT test_head, int64_t *d_counts, void *stream_) {
-    hipStream_t stream = (hipStream_t)stream_;
-    if (!m || !tables || !d_h || !d_t || !d_r || !d_counts) return fail(KGE_ERR_BAD_ARG, "kge_rank_triples: null model, tables, triple or output array");
-    if (n < 0) return fail(KGE_ERR_BAD_ARG, "kge_rank_triples: negative triple count");
-    if (n >= (INT(1) << 30)) return fail(KGE_ERR_BAD_ARG, "kge_rank_triples: more than 2^30 triples in one call");
+namespace {
+
+// kge_rank_triples (`tables`) and kge_rank_triples_bf16 (`bf16`: tables == nullptr, d_ent / d_rel are stored bf16 rows): one argument
+// path, one grouping of the requests.  The bf16 form builds no candidate table: its kernel normalises the stored rows as it reads them.
+int rank_triples_call(const std::string &who, bool bf16, const kge_model_desc *m, const float *const tables[KGE_MAX_TABLES], const uint16_t *d_ent,
+                      const uint16_t *d_rel, const int32_t *d_h, const int32_t *d_t, const int32_t *d_r, INT n, INT test_head, int64_t *d_counts,
+                      hipStream_t stream) {
+    if (!m || (bf16 ? !d_ent || !d_rel : !tables) || !d_h || !d_t || !d_r || !d_counts) return fail(KGE_ERR_BAD_ARG, who + ": null model, tables, triple or output array");
+    if (n < 0) return fail(KGE_ERR_BAD_ARG, who + ": negative triple count");
+    if (n >= (INT(1) << 30)) return fail(KGE_ERR_BAD_ARG, who + ": more than 2^30 triples in one call");
     bool known_model = for_model(m->model, [](auto) {});
     if (!known_model) return fail(KGE_ERR_BAD_ARG, "unknown model id");
+    if (bf16)
+        if (const char *why = bf16_eval_refusal(m)) return fail(KGE_ERR_UNSUPPORTED, who + ": " + why);
     const int64_t E = m->ent_total;
     const int D = m->model == KGE_TRANSR ? (int)m->rel_dim : (int)m->ent_dim;
-    if (D < 1 || E < 1 || m->rel_total < 1) return fail(KGE_ERR_BAD_ARG, "kge_rank_triples: empty model");
-    if (D > 1024) return fail(KGE_ERR_UNSUPPORTED, "kge_rank_triples: embedding dimension > 1024");
-    if (!device_ok()) return fail(KGE_ERR_NO_DEVICE, "kge_rank_triples: no usable HIP device");
+    if (D < 1 || E < 1 || m->rel_total < 1) return fail(KGE_ERR_BAD_ARG, who + ": empty model");
+    if (D > 1024) return fail(KGE_ERR_UNSUPPORTED, who + ": embedding dimension > 1024");
+    if (!device_ok()) return fail(KGE_ERR_NO_DEVICE, who + ": no usable HIP device");
     RankTriplesArgs a = {};
     int rc = eval_filter_view(false, a.ev);
     if (rc) return rc;
     if (n == 0) return KGE_OK;
-    if (!tables[0] || !tables[1]) return fail(KGE_ERR_BAD_ARG, "kge_rank_triples: null table");
+    if (!bf16 && (!tables[0] || !tables[1])) return fail(KGE_ERR_BAD_ARG, who + ": null table");
     // the one synchronisation: the triples come to the host to be grouped by (relation, side)
     std::vector<int32_t> ids((size_t)n * 3);
     if ((rc = hip_check(hipMemcpyAsync(ids.data(), d_h, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, stream), "copy heads"))) return rc;
@@ -297,7 +332,7 @@ extern "C" int kge_rank_triples(const kge_model_desc *m, const float *const tabl
     const int sides = test_head ? 2 : 1;
     const int64_t R = m->rel_total, n_req = n * sides;
     for (int64_t i = 0; i < n; i++)
-        if (hr[i] < 0 || hr[i] >= R) return fail(KGE_ERR_BAD_ARG, "kge_rank_triples: relation id out of range");
+        if (hr[i] < 0 || hr[i] >= R) return fail(KGE_ERR_BAD_ARG, who + ": relation id out of range");
     // counting sort by key = 2 * relation + side
     std::vector<int64_t> start((size_t)(2 * R + 1), 0);
     for (int64_t i = 0; i < n; i++)
@@ -328,13 +363,19 @@ extern "C" int kge_rank_triples(const kge_model_desc *m, const float *const tabl
         rel_block[(size_t)R] = b;
     }
     if ((rc = g_req.reserve(n_req + n_blocks, "alloc rank requests"))) return rc;
-    if ((rc = g_T.reserve(E * D, "alloc rank candidate table"))) return rc;
+    if (!bf16 && (rc = g_T.reserve(E * D, "alloc rank candidate table"))) return rc;
     if (m->model == KGE_TRANSR && (rc = g_P.reserve((E + 1) * D, "alloc rank projections"))) return rc;
     if (!g_req_done && (rc = hip_check(hipEventCreateWithFlags(&g_req_done, hipEventDisableTiming), "create rank event"))) return rc;
     if ((rc = hip_check(hipMemcpyAsync(g_req, host.data(), sizeof(Int4) * host.size(), hipMemcpyHostToDevice, stream), "upload rank requests"))) return rc;
     if ((rc = hip_check(hipEventRecord(g_req_done, stream), "record rank request upload"))) return rc;
     if ((rc = hip_check(hipMemsetAsync(d_counts, 0, sizeof(int64_t) * 8 * (size_t)n, stream), "zero rank counts"))) return rc;
-    a.rel = tables[1]; a.T = g_T; a.req = g_req; a.E = E; a.D = D; a.counts = (long long *)d_counts;
+    a.req = g_req; a.E = E; a.D = D; a.counts = (long long *)d_counts;
+    if (bf16) {   // TransE on the stored rows: no T, one launch over every block
+        a.rel = (const float *)d_rel; a.T = (const float *)d_ent;   // (read as uint16 rows by the BF16 instantiations)
+        a.blk = g_req + n_req;
+        return launch_rank<true>(true, a, n_blocks, stream);
+    }
+    a.rel = tables[1]; a.T = g_T;
     const bool mean = m->model == KGE_TRANSE;
     if (mean) {   // TransE's candidates do not depend on the relation: one table, one launch over every block
         if ((rc = launch_lp_table(*m, tables, nullptr, hr[0], g_T, stream))) return rc;
@@ -350,4 +391,16 @@ extern "C" int kge_rank_triples(const kge_model_desc *m, const float *const tabl
         if ((rc = launch_rank(false, a, b1 - b0, stream))) return rc;
     }
     return KGE_OK;
+}
+
+}  // namespace
+
+extern "C" int kge_rank_triples(const kge_model_desc *m, const float *const tables[KGE_MAX_TABLES], const int32_t *d_h, const int32_t *d_t,
+                                const int32_t *d_r, INT n, INT test_head, int64_t *d_counts, void *stream) {
+    return rank_triples_call("kge_rank_triples", false, m, tables, nullptr, nullptr, d_h, d_t, d_r, n, test_head, d_counts, (hipStream_t)stream);
+}
+
+extern "C" int kge_rank_triples_bf16(const kge_model_desc *m, const uint16_t *d_ent, const uint16_t *d_rel, const int32_t *d_h, const int32_t *d_t,
+                                     const int32_t *d_r, INT n, INT test_head, int64_t *d_counts, void *stream) {
+    return rank_triples_call("kge_rank_triples_bf16", true, m, nullptr, d_ent, d_rel, d_h, d_t, d_r, n, test_head, d_counts, (hipStream_t)stream);
 }

@@ -20,6 +20,9 @@
 // rank).  The same side_xp, fma chain, team_sum and (L, C) bucket as the whole table, so every candidate's key carries the same
 // bits; both stages leave packed keys.  kge_topk_merge_keys takes the k smallest of several sources' key lists and unpacks
 // them: keys are unique per query (the id is the low word), so the k smallest of k-smallests over any cut is the whole table's.
+// Stored bf16 tables (kge_topk_entities_bf16; TransE, the whole table): the BF16 instantiations of the table and select kernels
+// read the entity and relation rows as uint16 and widen them exactly; everything after the load is the fp32 code, so ids and
+// score bits are those of kge_topk_entities on the widened tables.  Only the [E] inverse norms and the partial lists are allocated.
 #include <algorithm>
 #include <cstring>
 #include <vector>
@@ -34,11 +37,15 @@ namespace kge {
 namespace {
 
 // The projected (not yet normalised) entity side x of `row` under the relation context cw, as side_project forms it, and
-// 1/|x| from Team::normalize -- the two factors of predict_kernel's contracted score
-template <int MODEL, int L, int C>
+// 1/|x| from Team::normalize -- the two factors of predict_kernel's contracted score.
+// BF16 (kge_topk_entities_bf16, TransE): a.ent is the stored bf16 table, cast here where it is read; the row is widened exactly
+// in the same lane layout, so everything after the load has the bits it has on the widened table.
+template <int MODEL, int L, int C, bool BF16 = false>
 __device__ __forceinline__ float side_xp(const Team<L, C> &tm, const FbArgs &a, long long row, const float (&cw)[C], float (&xp)[C]) {
+    static_assert(!BF16 || MODEL == KGE_TRANSE, "stored bf16 rows: TransE only");
     float raw[C];
-    if constexpr (MODEL == KGE_TRANSR) tm.load(a.P, row, raw);
+    if constexpr (BF16) tm.load((const uint16_t *)a.ent, row, raw);
+    else if constexpr (MODEL == KGE_TRANSR) tm.load(a.P, row, raw);
     else tm.load(a.ent, row, raw);
     if constexpr (MODEL == KGE_TRANSE || MODEL == KGE_TRANSR) {
 #pragma unroll
@@ -62,17 +69,34 @@ __device__ __forceinline__ float side_xp(const Team<L, C> &tm, const FbArgs &a, 
 
 // candidate table of one relation: projected rows into T (nullptr for TransE / TransR, whose rows are the parameter /
 // projection rows themselves) and 1/|row| into inv
-template <int MODEL, int L, int C>
+// The relation context of a query on stored bf16 tables (a.rel is the bf16 relation table, cast here): ctx_forward's TransE case -- the
+// row, Team::normalize, no projection vector -- on the widened row.
+template <int L, int C>
+__device__ __forceinline__ void ctx_forward_bf16(const Team<L, C> &tm, const FbArgs &a, long long r, Ctx<C> &cx) {
+    float raw[C];
+    tm.load((const uint16_t *)a.rel, r, raw);
+    tm.normalize(raw, cx.rn, cx.inv_r, cx.uc_r);
+    cx.inv_w = 1.f; cx.uc_w = true;
+#pragma unroll
+    for (int c = 0; c < C; c++) cx.cw[c] = 0.f;
+}
+
+template <int MODEL, int L, int C, bool BF16 = false>
 __global__ __launch_bounds__(256) void topk_table_kernel(FbArgs a, long long r, long long E, float *__restrict__ T, float *__restrict__ inv) {
     constexpr int TEAMS = 256 / L;
     Team<L, C> tm;
     tm.lane = threadIdx.x % L;
     tm.D = a.D;
     Ctx<C> cx;
-    ctx_forward<MODEL, L, C>(tm, a, r, cx);
+    if constexpr (BF16) {   // TransE has no projection vector, and the relation table is not read
+#pragma unroll
+        for (int c = 0; c < C; c++) cx.cw[c] = 0.f;
+    } else {
+        ctx_forward<MODEL, L, C>(tm, a, r, cx);
+    }
     for (long long j = (long long)blockIdx.x * TEAMS + threadIdx.x / L; j < E; j += (long long)gridDim.x * TEAMS) {
         float xp[C];
-        const float v = side_xp<MODEL, L, C>(tm, a, j, cx.cw, xp);
+        const float v = side_xp<MODEL, L, C, BF16>(tm, a, j, cx.cw, xp);
         if (T) tm.store(T, j, xp);
         if (tm.lane == 0) inv[j] = v;
     }
@@ -117,8 +141,9 @@ __device__ __forceinline__ bool eligible(const TopkArgs &a, bool hd, long long k
     return true;
 }
 
-template <int MODEL, int L, int C, int Q, int U, bool DIRECT, bool RANGE>
+template <int MODEL, int L, int C, int Q, int U, bool DIRECT, bool RANGE, bool BF16 = false>
 __global__ __launch_bounds__(256) void topk_select_kernel(TopkArgs a) {
+    static_assert(!BF16 || (MODEL == KGE_TRANSE && !RANGE), "stored bf16 rows: TransE over the whole table only");
     constexpr int TEAMS = 256 / L;
     constexpr int ROUND = TEAMS * U;   // candidates per round: the most a buffer can grow between two checks
     extern __shared__ uint64_t s_keys[];
@@ -168,7 +193,8 @@ __global__ __launch_bounds__(256) void topk_select_kernel(TopkArgs a) {
             const int f = a.fixed[qi], r = a.rel[qi];
             const bool hd = a.head[qi] != 0;
             Ctx<C> cx;
-            ctx_forward<MODEL, L, C>(tm, a.fa, r, cx);
+            if constexpr (BF16) ctx_forward_bf16<L, C>(tm, a.fa, r, cx);
+            else ctx_forward<MODEL, L, C>(tm, a.fa, r, cx);
             if (q == 0) {
 #pragma unroll
                 for (int c = 0; c < C; c++) cw0[c] = cx.cw[c];   // one relation per launch for the projecting models
@@ -179,9 +205,10 @@ __global__ __launch_bounds__(256) void topk_select_kernel(TopkArgs a) {
                 qa.ent = a.qrows;
                 finv = side_xp<MODEL, L, C>(tm, qa, qi, cx.cw, fv);
             } else if constexpr (DIRECT) {
-                finv = side_xp<MODEL, L, C>(tm, a.fa, f, cx.cw, fv);
+                finv = side_xp<MODEL, L, C, BF16>(tm, a.fa, f, cx.cw, fv);
             } else {
-                tm.load(a.T, f, fv);
+                if constexpr (BF16) tm.load((const uint16_t *)a.T, f, fv);   // (TransE: T is the entity table itself)
+                else tm.load(a.T, f, fv);
                 finv = a.Tinv[f];
             }
             if (hd) {
@@ -211,9 +238,10 @@ __global__ __launch_bounds__(256) void topk_select_kernel(TopkArgs a) {
             float x[C], xinv = 0.f;
             if (j < j1) {
                 if constexpr (DIRECT) {
-                    xinv = side_xp<MODEL, L, C>(tm, a.fa, j, cw0, x);
+                    xinv = side_xp<MODEL, L, C, BF16>(tm, a.fa, j, cw0, x);
                 } else {
-                    tm.load(a.T, j, x);
+                    if constexpr (BF16) tm.load((const uint16_t *)a.T, j, x);
+                    else tm.load(a.T, j, x);
                     xinv = a.Tinv[j];
                 }
             } else {
@@ -324,9 +352,21 @@ int launch_table(int model, const FbArgs &a, int64_t r, int64_t E, float *T, flo
     return hip_check(hipGetLastError(), "top-k table launch");
 }
 
+// 1/|row| of every row of a stored bf16 entity table (a.ent cast by the kernel) into inv
+int launch_table_bf16(const FbArgs &a, int64_t E, float *inv, hipStream_t stream) {
+    const bool shaped = for_team_shape(a.D, [&](auto t) {
+        constexpr int L = decltype(t)::L, C = decltype(t)::C;
+        long long blocks = (E + (256 / L) - 1) / (256 / L);
+        if (blocks > 4096) blocks = 4096;
+        hipLaunchKernelGGL((topk_table_kernel<KGE_TRANSE, L, C, true>), dim3((unsigned)blocks), dim3(256), 0, stream, a, 0LL, (long long)E, (float *)nullptr, inv);
+    });
+    if (!shaped) return fail(KGE_ERR_UNSUPPORTED, "kge_topk_entities_bf16: embedding dimension > 1024");
+    return hip_check(hipGetLastError(), "top-k bf16 table launch");
+}
+
 constexpr int kSelectLdsBytes = 48 << 10;   // key buffers of one workgroup: two workgroups of 4 waves per CU
 
-template <int MODEL, int L, int C, int Q, int U, bool DIRECT, bool RANGE>
+template <int MODEL, int L, int C, int Q, int U, bool DIRECT, bool RANGE, bool BF16 = false>
 int launch_select_t(TopkArgs a, hipStream_t stream) {
     const int KP = (int)pow2_at_least((unsigned)std::max(a.k, 64));
     a.cap = 2 * KP;   // >= k + ROUND (ROUND <= 64)
@@ -345,7 +385,8 @@ int launch_select_t(TopkArgs a, hipStream_t stream) {
         a.part = RANGE ? a.keys : nullptr;
     }
     const size_t lds = (size_t)a.qn * a.cap * sizeof(uint64_t);
-    hipLaunchKernelGGL((topk_select_kernel<MODEL, L, C, Q, U, DIRECT, RANGE>), dim3((unsigned)qblocks, (unsigned)slices), dim3(256), lds, stream, a);
+    if constexpr (BF16) hipLaunchKernelGGL((topk_select_kernel<MODEL, L, C, Q, U, DIRECT, RANGE, true>), dim3((unsigned)qblocks, (unsigned)slices), dim3(256), lds, stream, a);
+    else hipLaunchKernelGGL((topk_select_kernel<MODEL, L, C, Q, U, DIRECT, RANGE>), dim3((unsigned)qblocks, (unsigned)slices), dim3(256), lds, stream, a);
     if ((rc = hip_check(hipGetLastError(), "top-k select launch"))) return rc;
     if (slices > 1) {
         a.cap = (int)pow2_at_least((unsigned)(a.k + 256));
@@ -361,12 +402,12 @@ int launch_select_t(TopkArgs a, hipStream_t stream) {
 constexpr int select_q(int C) { return C <= 4 ? 16 : (C <= 8 ? 8 : 4); }
 constexpr int select_u(int C) { return C <= 4 ? 4 : (C <= 8 ? 2 : 1); }
 
-template <int MODEL, bool DIRECT, bool RANGE = false>
+template <int MODEL, bool DIRECT, bool RANGE = false, bool BF16 = false>
 int launch_select_d(const TopkArgs &a, hipStream_t stream) {
     int rc = KGE_OK;
     const bool shaped = for_team_shape(a.fa.D, [&](auto t) {
         constexpr int L = decltype(t)::L, C = decltype(t)::C;
-        rc = launch_select_t<MODEL, L, C, select_q(C), select_u(C), DIRECT, RANGE>(a, stream);
+        rc = launch_select_t<MODEL, L, C, select_q(C), select_u(C), DIRECT, RANGE, BF16>(a, stream);
     });
     return shaped ? rc : fail(KGE_ERR_UNSUPPORTED, "kge_topk_entities: embedding dimension > 1024");
 }
@@ -386,26 +427,32 @@ int launch_select(int model, bool direct, const TopkArgs &a, hipStream_t stream)
 
 using namespace kge;
 
-extern "C" int kge_topk_entities(const kge_model_desc *m, const float *const tables[KGE_MAX_TABLES], const int32_t *d_fixed,
-                                 const int32_t *d_rel, const int32_t *d_head, INT n, INT k, INT flags, int32_t *d_ids,
-                                 float *d_scores, void *stream_) {
-    hipStream_t stream = (hipStream_t)stream_;
-    if (!m || !tables) return fail(KGE_ERR_BAD_ARG, "kge_topk_entities: null model or tables");
-    if (k < 1 || k > 1024) return fail(KGE_ERR_BAD_ARG, "kge_topk_entities: k must be in [1, 1024]");
-    if (flags & ~(INT)(KGE_TOPK_FILTERED | KGE_TOPK_TYPED)) return fail(KGE_ERR_BAD_ARG, "kge_topk_entities: unknown flags");
-    if (n < 0) return fail(KGE_ERR_BAD_ARG, "kge_topk_entities: negative query count");
-    if (m->ent_total < 1 || m->rel_total < 1) return fail(KGE_ERR_BAD_ARG, "kge_topk_entities: empty model");
-    if (!device_ok()) return fail(KGE_ERR_NO_DEVICE, "kge_topk_entities: no usable HIP device");
+namespace {
+
+// kge_topk_entities (`tables`) and kge_topk_entities_bf16 (`bf16`: tables == nullptr, d_ent / d_rel_tab are stored bf16 rows): one
+// argument path.  The bf16 form allocates the [E] inverse norms (within the table budget) and the partial key lists, nothing else.
+int topk_entities_call(const std::string &who, bool bf16, const kge_model_desc *m, const float *const tables[KGE_MAX_TABLES], const uint16_t *d_ent,
+                       const uint16_t *d_rel_tab, const int32_t *d_fixed, const int32_t *d_rel, const int32_t *d_head, INT n, INT k, INT flags,
+                       int32_t *d_ids, float *d_scores, hipStream_t stream) {
+    if (!m || (bf16 ? !d_ent || !d_rel_tab : !tables)) return fail(KGE_ERR_BAD_ARG, who + ": null model or tables");
+    if (k < 1 || k > 1024) return fail(KGE_ERR_BAD_ARG, who + ": k must be in [1, 1024]");
+    if (flags & ~(INT)(KGE_TOPK_FILTERED | KGE_TOPK_TYPED)) return fail(KGE_ERR_BAD_ARG, who + ": unknown flags");
+    if (n < 0) return fail(KGE_ERR_BAD_ARG, who + ": negative query count");
+    if (bf16)
+        if (const char *why = bf16_eval_refusal(m)) return fail(KGE_ERR_UNSUPPORTED, who + ": " + why);
+    if (m->ent_total < 1 || m->rel_total < 1) return fail(KGE_ERR_BAD_ARG, who + ": empty model");
+    if (!device_ok()) return fail(KGE_ERR_NO_DEVICE, who + ": no usable HIP device");
     TopkArgs a = {};
     if (flags) {
         int rc = eval_filter_view((flags & KGE_TOPK_TYPED) != 0, a.ev);
         if (rc) return rc;
     }
     if (n == 0) return KGE_OK;
-    if (!d_fixed || !d_rel || !d_head || !d_ids || !d_scores) return fail(KGE_ERR_BAD_ARG, "kge_topk_entities: null query or output array");
+    if (!d_fixed || !d_rel || !d_head || !d_ids || !d_scores) return fail(KGE_ERR_BAD_ARG, who + ": null query or output array");
     const int64_t E = m->ent_total;
     const int D = m->model == KGE_TRANSR ? (int)m->rel_dim : (int)m->ent_dim;
-    a.fa.ent = tables[0]; a.fa.rel = tables[1]; a.fa.auxr = tables[2]; a.fa.auxe = tables[3];
+    if (bf16) { a.fa.ent = (const float *)d_ent; a.fa.rel = (const float *)d_rel_tab; }   // (read as uint16 rows by the BF16 instantiations)
+    else { a.fa.ent = tables[0]; a.fa.rel = tables[1]; a.fa.auxr = tables[2]; a.fa.auxe = tables[3]; }
     a.fa.D = D;
     a.fixed = d_fixed; a.rel = d_rel; a.head = d_head;
     a.E = E; a.k = (int)k; a.flags = (int)flags;
@@ -417,6 +464,13 @@ extern "C" int kge_topk_entities(const kge_model_desc *m, const float *const tab
     const bool own_rows = m->model == KGE_TRANSH || m->model == KGE_TRANSD;
     if (table && own_rows && (rc = g_T.reserve(E * D, "alloc top-k candidate table"))) return rc;
     if (table && (rc = g_inv.reserve(E, "alloc top-k inverse norms"))) return rc;
+    if (bf16) {   // TransE on the stored rows: the fp32 form's one launch, the same budget rule (counted in fp32 bytes, as there)
+        if (table && (rc = launch_table_bf16(a.fa, E, g_inv, stream))) return rc;
+        a.T = table ? a.fa.ent : nullptr;
+        a.Tinv = table ? g_inv : nullptr;
+        a.order = nullptr; a.nq = n;
+        return table ? launch_select_d<KGE_TRANSE, false, false, true>(a, stream) : launch_select_d<KGE_TRANSE, true, false, true>(a, stream);
+    }
     if (m->model == KGE_TRANSE) {
         // the candidates do not depend on the relation: all queries in the caller's order, one launch, no synchronisation
         if (table && (rc = launch_table(m->model, a.fa, 0, E, nullptr, g_inv, stream))) return rc;
@@ -453,6 +507,22 @@ extern "C" int kge_topk_entities(const kge_model_desc *m, const float *const tab
         q0 = q1;
     }
     return KGE_OK;
+}
+
+}  // namespace
+
+extern "C" int kge_topk_entities(const kge_model_desc *m, const float *const tables[KGE_MAX_TABLES], const int32_t *d_fixed,
+                                 const int32_t *d_rel, const int32_t *d_head, INT n, INT k, INT flags, int32_t *d_ids,
+                                 float *d_scores, void *stream) {
+    return topk_entities_call("kge_topk_entities", false, m, tables, nullptr, nullptr, d_fixed, d_rel, d_head, n, k, flags, d_ids, d_scores,
+                              (hipStream_t)stream);
+}
+
+extern "C" int kge_topk_entities_bf16(const kge_model_desc *m, const uint16_t *d_ent, const uint16_t *d_rel_tab, const int32_t *d_fixed,
+                                      const int32_t *d_rel, const int32_t *d_head, INT n, INT k, INT flags, int32_t *d_ids,
+                                      float *d_scores, void *stream) {
+    return topk_entities_call("kge_topk_entities_bf16", true, m, nullptr, d_ent, d_rel_tab, d_fixed, d_rel, d_head, n, k, flags, d_ids, d_scores,
+                              (hipStream_t)stream);
 }
 
 extern "C" int kge_topk_entities_range(const kge_model_desc *m, const float *const tables[KGE_MAX_TABLES], INT row_lo, INT rows,

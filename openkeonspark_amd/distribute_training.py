@@ -137,6 +137,11 @@ def parse_args(argv=None):
                         "share their bits)")
     p.add_argument("--table_rounding_seed", type=int, default=0,
                    help="seed of the stochastic rounding's hash (--table_dtype bf16); a resumed run must repeat it")
+    p.add_argument("--bf16_evaluation", type=str, default="view", choices=("view", "stored"),
+                   help="what the early stop on hits10 / mrr without --early_stop_candidates (and rank_triples, top-k entities) reads "
+                        "with --table_dtype bf16: view = a cached float32 view of the tables (twice their bytes again, faster; the "
+                        "stored rows where it cannot be allocated), stored = the stored bf16 rows themselves, the same metrics with "
+                        "no memory of the table's size (Config.set_bf16_evaluation).  No effect on fp32 tables")
     p.add_argument("--type_constrained_sampling", type=int, default=0,
                    help="1: entity negatives of a training batch come from the relation's own head / tail type list "
                         "(type_constrain.txt in --input_path, required then) instead of from all entities; same random stream, "
@@ -182,6 +187,7 @@ def get_conf(argv):
                                  in_chunk=getattr(argv, "shared_negatives_in_chunk", 0))
     if getattr(argv, "table_dtype", "fp32") != "fp32":
         con.set_table_dtype(argv.table_dtype, seed=getattr(argv, "table_rounding_seed", 0))
+    con.set_bf16_evaluation(getattr(argv, "bf16_evaluation", "view"))
     typed = bool(getattr(argv, "type_constrained_sampling", 0))
     path = argv.input_path if not argv.input_path or argv.input_path.endswith("/") else argv.input_path + "/"
     derive = bool(getattr(argv, "derive_type_constraints", 0)) and bool(path) and not os.path.exists(path + "type_constrain.txt") and \

@@ -172,15 +172,18 @@ def valid_rank_ids(con, sample, what):
 
 def rank_device(con, dev, test_head, into=None):
     """kge_rank_triples on an int32 device tensor [3, n] (h, t, r; ids already checked) -> int64 numpy [n, 2, 4]; with
-    `into` (a contiguous int64 device tensor [n, 2, 4]) the counts are left there and nothing is copied back."""
+    `into` (a contiguous int64 device tensor [n, 2, 4]) the counts are left there and nothing is copied back.  bf16 tables under
+    set_bf16_evaluation("stored"), or whose float32 view cannot be made: kge_rank_triples_bf16 on the stored rows, the same counts."""
     import torch
     n = dev.shape[1]
     counts = into if into is not None else torch.empty((n, 2, 4), dtype=torch.int64, device=con.device)
     # (an empty tensor has no address and the entry point refuses null pointers: n == 0 still checks the files, on a spare row)
     ids, out = (dev, counts) if n else (torch.zeros((3, 1), dtype=torch.int32, device=con.device),
                                         torch.zeros((1, 2, 4), dtype=torch.int64, device=con.device))
-    _lib.check(con.lib.kge_rank_triples(ctypes.byref(con._desc), con._tab_ptrs, ids[0].data_ptr(), ids[1].data_ptr(),
-                                        ids[2].data_ptr(), n, 1 if test_head else 0, out.data_ptr(), con._stream()), con.lib)
+    raw = con._bf16_full_eval_tables("rank_triples")
+    fn, tabs = (con.lib.kge_rank_triples, (con._tab_ptrs,)) if raw is None else (con.lib.kge_rank_triples_bf16, raw)
+    _lib.check(fn(ctypes.byref(con._desc), *tabs, ids[0].data_ptr(), ids[1].data_ptr(), ids[2].data_ptr(), n, 1 if test_head else 0,
+                  out.data_ptr(), con._stream()), con.lib)
     return counts.cpu().numpy() if into is None else None
 
 
@@ -235,12 +238,14 @@ def topk_flags(filtered, type_constrained):
     return (_lib.TOPK_FILTERED if filtered else 0) | (_lib.TOPK_TYPED if type_constrained else 0)
 
 
-def topk_call(con, fn, query_ptrs, n, k, flags, on_device):
+def topk_call(con, fn, query_ptrs, n, k, flags, on_device, tabs=None):
+    """`tabs`: the table arguments, where they are not the float32 tables (stored bf16 tables: the two addresses)."""
     import torch
     k = int(k)
     ids = torch.empty((n, k), dtype=torch.int32, device=con.device)
     scores = torch.empty((n, k), dtype=torch.float32, device=con.device)
-    _lib.check(fn(ctypes.byref(con._desc), con._tab_ptrs, *query_ptrs, n, k, flags, ids.data_ptr(), scores.data_ptr(), con._stream()), con.lib)
+    tabs = (con._tab_ptrs,) if tabs is None else tabs
+    _lib.check(fn(ctypes.byref(con._desc), *tabs, *query_ptrs, n, k, flags, ids.data_ptr(), scores.data_ptr(), con._stream()), con.lib)
     return topk_result(ids, scores, on_device)
 
 
@@ -257,7 +262,9 @@ def top_k_entities(con, fixed, rel, k, head, filtered, type_constrained):
         return topk_result(*shard_eval.top_k_entities(con, f, r, n, k, err, head, flags), on_device)
     f, r, n, on_device = topk_queries(con, fixed, rel, k, con.entTotal, con.relTotal)
     side = torch.full((n,), 1 if head else 0, dtype=torch.int32, device=con.device)
-    return topk_call(con, con.lib.kge_topk_entities, (f.data_ptr(), r.data_ptr(), side.data_ptr()), n, k, flags, on_device)
+    raw = con._bf16_full_eval_tables("top_k_heads" if head else "top_k_tails")      # stored bf16 rows: the same ids and score bits
+    fn = con.lib.kge_topk_entities if raw is None else con.lib.kge_topk_entities_bf16
+    return topk_call(con, fn, (f.data_ptr(), r.data_ptr(), side.data_ptr()), n, k, flags, on_device, tabs=raw)
 
 
 def top_k_relations(con, h, t, k, filtered, type_constrained):
